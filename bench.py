@@ -14,15 +14,21 @@ Arrays / streams are independent units: with N GPUs every rank owns its own bloc
 compute, one RCCL all_gather of the DOA bins + prob per step (mcarray_amd/dist.py; --gather-audio adds the beamformed audio, to
 rank 0).  `python bench.py --gpus N` without a launcher starts its own N ranks (or refuses if fewer GPUs are visible).
 
-Prints ONE JSON line (rank 0).  `value` = frames of all ranks / max-over-ranks time of K steps.  `roofline` is for the dominant
-kernel, timed with HIP events recorded by the library on the launch stream inside the timed region.  `cpu_baseline` = the CPU
-oracle (a scalar double-precision restatement of the reference, oracle/) on a bounded sample of the same input, rank 0, N=1 only.
+Prints ONE JSON line (rank 0).  `value` = frames of all ranks / max-over-ranks time of K steps.
+
+A plain run does only what that figure needs: it sets up, lets the clocks settle (settle_clocks), runs the --warmup steps, times
+the --steps steps, writes the outputs of the last timed step with --dump-outputs DIR, and prints the headline line.  --full adds
+everything else, as a plain run did before --full existed: the other BASELINE configurations, the CPU baselines and the oracle
+checks, the per-kernel table and the rooflines.  There `roofline` is for the dominant kernel, timed with HIP events recorded by the
+library on the launch stream inside the timed region, and `cpu_baseline` = the CPU oracle (a scalar double-precision restatement
+of the reference, oracle/) on a bounded sample of the same input, rank 0, N=1 only.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -38,6 +44,8 @@ PEAK_TFLOPS = {"fp32": 157.3, "fp16x3": 2500.0, "fp16": 2500.0, "adaptive": 2500
 PREC = {"fp32": 0, "fp16x3": 1, "fp16": 2, "adaptive": 3}
 ROW_PAD = 64                                           # floats of padding behind every channel row of the synthetic input (synth_batch)
 PROFILE_TAG = "r06"                                    # profiles/<tag>_pmc_traffic_<precision>.json of the committed PMC passes
+SETTLE_S = 2.0                                         # seconds of load a plain run puts on the GPU ahead of its warm-up (settle_clocks)
+DUMP_ROWS = {"doa": 1 << 20, "audio": 8192}            # --dump-outputs: rows kept per output before it is sampled (<= 16 + 16 MB)
 
 
 MERGED_REALS = {8: 3968, 4: 1600}     # reals per merged one-plane A row (2 x the distinct products k (j - i), padded to the K stage of the kernel; 8-mic ULA: 1 962 complex)
@@ -45,7 +53,7 @@ MERGED_REALS = {8: 3968, 4: 1600}     # reals per merged one-plane A row (2 x th
 
 def compact_line(line):
     """The record the driver's stdout tail must hold whole (under 6 KB): numbers only -- the notes, sources and
-    sub-measurements stay in the full record (--detail-out / --full; what every field means: profiles/bench_notes.md)."""
+    sub-measurements stay in the full record (--detail-out / --print-record; what every field means: profiles/bench_notes.md)."""
     def pick(d, keys):
         return {k: d[k] for k in keys if d is not None and k in d and d[k] is not None}
 
@@ -199,6 +207,40 @@ def timed_loop(step, drain, steps, warmup, use_dist, dist, dev, before_timed=Non
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+def settle_clocks(step, seconds):
+    """The clock warm-up of a plain run: the GPU needs load before its clocks settle (with 0 / 1 warm-up steps and nothing ahead of
+    them a step takes 42 / 3 % longer: profiles/r06_bench_warmup0.json / _warmup1.json).  --full gets that load from the other
+    configurations it runs ahead of the warm-up; a plain run gets it from `step`, the timed path on a context of its own, so that the
+    timed context still sees exactly --warmup + --steps steps and what it computes does not depend on how many steps this took.
+    No collective runs here: every rank settles on its own.  Returns {steps, seconds}."""
+    n, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(8):
+            step()
+        n += 8
+        torch.cuda.synchronize()
+    return {"steps": n, "seconds": time.perf_counter() - t0,
+            "note": "untimed steps of the same path on a context of its own, ahead of the --warmup steps (bench.py settle_clocks)"}
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs DIR: what the last timed step handed its caller, one DIR/<name>.npy per output, in float32 (float64 for the
+    integer DOA bins).  outputs: {name: (tensor whose leading dims are [units][frames], kind)}; an output of more (unit, frame) rows
+    than DUMP_ROWS[kind] keeps a fixed, seeded sample of them, [rows][...], and DIR/<name>_rows.npy holds which (unit * frames +
+    frame, float64).  The inputs depend only on the arguments, so two builds can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, kind) in sorted(outputs.items()):
+        if t is None:
+            continue
+        rows = t.shape[0] * t.shape[1]
+        if rows > DUMP_ROWS[kind]:
+            pick = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(rows, size=DUMP_ROWS[kind], replace=False))
+            t = t.reshape((rows,) + tuple(t.shape[2:])).index_select(0, torch.from_numpy(pick).to(t.device))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), pick.astype(np.float64))
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype.kind in "iu" else np.float32))
 
 
 def traffic_table(precision, shape_matches):
@@ -462,10 +504,20 @@ def run_ssl(args, world, rank, local_rank, dev, use_dist, dist):
     # spread of the repair pass -- run BEFORE the warm-up, outside the timed region: a few seconds of the same kernels, which is also
     # what brings the GPU's clocks to their loaded state (the driver's command has 5 warm-up steps = 3.6 ms; the clocks need ~25 ms:
     # the first steps of a cold process read 6-8 % slower).  The CPU baselines and configs[3] follow the timed region.
-    single = das = spread = None
+    # A plain run does none of that: its clocks settle on a context of its own (settle_clocks) and no kernel is bracketed.
+    single = das = spread = settle = None
     torch.cuda.synchronize()
     t_extras = time.perf_counter()
-    if rank == 0 and world == 1 and args.single_stream:
+    if not args.full:
+        cs = api.Context(FS, synth.ULA8, NFFT, STEP_DEG, 1, srp_precision=PREC[args.precision], max_arrays=A, device=local_rank)
+        cs.reserve(A, F)
+        sb = torch.empty(A, F, 1, dtype=torch.int32, device=dev)
+        sr, sq = torch.empty_like(sb, dtype=torch.float32), torch.empty_like(sb, dtype=torch.float32)
+        so = torch.empty_like(out_local)
+        settle = settle_clocks(lambda: cs.process_frames_dev(pcm, F, sb, sr, sq, None, so, stream=stream), SETTLE_S)
+        cs.close()
+        del sb, sr, sq, so
+    if args.full and rank == 0 and world == 1 and args.single_stream:
         # the literal BASELINE configs[2]: ONE 8-mic array, 4096 frames batched per call (a batch this small is bound by the
         # dependent chain of its ~10 kernels, not by throughput; an ADAPTIVE context takes its adaptive path from 4096 rows)
         c1 = api.Context(FS, synth.ULA8, NFFT, STEP_DEG, 1, srp_precision=PREC[args.precision], max_arrays=1, device=local_rank)
@@ -487,18 +539,64 @@ def run_ssl(args, world, rank, local_rank, dev, use_dist, dist):
         single["graph_replay"] = {"value": F1 * n1 / eg, "unit": "frames/s", "ms_per_call": eg / n1 * 1e3, "calls": n1}
         g1.close()
         c1.close()
-    if rank == 0 and world == 1 and args.extras:
+    if args.full and rank == 0 and world == 1 and args.extras:
         das = das_single_stream(pcm if F >= 936 else synth_batch(synth.ULA8, [0x5EED0000], 936, dev)[0], theta, dev, stream, local_rank, args.steps)
         spread = repair_spread(args, dev, stream, local_rank, 0.0)
 
     torch.cuda.synchronize()
     t_extras = time.perf_counter() - t_extras
     ctx.set_timing(False)
-    elapsed = timed_loop(step, xg.drain, args.steps, args.warmup, use_dist, dist, dev, arm, after_first_warmup)
+    if args.full:
+        elapsed = timed_loop(step, xg.drain, args.steps, args.warmup, use_dist, dist, dev, arm, after_first_warmup)
+    else:
+        elapsed = timed_loop(step, xg.drain, args.steps, args.warmup, use_dist, dist, dev)
     ctx.set_timing(False)
     last = state["last"]
     last_bin = xg.doa_buffers(last)[0]
     value = A * F * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # what a caller of the sharded path holds after the step: every rank's DOA bins + probabilities (the all_gather), this
+        # rank's angles, and the beamformed audio (all ranks' with --gather-audio)
+        g_bin, g_prob = xg.gathered_doa(last)
+        audio = xg.gathered_audio(last) if args.gather_audio else out_local
+        dump_outputs(args.dump_outputs, {"doa_bin": (g_bin, "doa"), "doa_rad": (doa_rad, "doa"), "prob": (g_prob, "doa"),
+                                         "audio": (audio.reshape(audio.shape[0], F, HOP), "audio")})
+
+    def check_gathered():
+        if not use_dist:
+            return
+        # the gathered buffers hold every rank's block at its global position
+        all_bin, all_prob = xg.gathered_doa(last)
+        mine_bin, mine_prob = xg.doa_buffers(last)
+        ok = torch.equal(all_bin[rank * A:(rank + 1) * A], mine_bin) and torch.equal(all_prob[rank * A:(rank + 1) * A], mine_prob)
+        if args.gather_audio and rank == 0:
+            ok = ok and torch.equal(xg.gathered_audio(last)[:A], xg.audio_buffer(last))
+        if not ok:
+            print("rank %d: gathered buffers do not contain this rank's block" % rank, file=sys.stderr)
+            dist.destroy_process_group()
+            raise SystemExit(3)
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "STFT frames/sec, 8-mic GCC-PHAT + SRP-PHAT(361) + delay-and-sum beamform @48kHz/1024-pt",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32" if args.precision == "fp32" else "f32 (SRP operands %s)" % args.precision, "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2] geometry (8-mic ULA 0.04 m, 48 kHz, N=1024, hop 512, 361 angles, "
+                                   "1 source, no power floor), %d arrays x %d frames per GPU per step; channel rows padded by %d floats" % (A, F, ROW_PAD),
+                       "arrays_per_gpu": A, "frames_per_array": F, "srp_precision": args.precision,
+                       "parallelism": "arrays sharded over %d GPU(s), all_gather of DOA bins+prob%s" % (world, " + gather of the beamformed audio to rank 0" if args.gather_audio else "")},
+            "algorithmic_GBps": value * BYTES_PER_FRAME / 1e9,
+            "hbm_roofline_frac": value * BYTES_PER_FRAME / 1e9 / (HBM_PEAK_GBPS * world),
+            "exchange": {"backend": dist.get_backend() if use_dist else None, "gather_audio": bool(args.gather_audio),
+                         "bytes_per_step_per_rank": 8 * A * F + (4 * A * F * HOP if args.gather_audio else 0)},
+        }
+        if settle:
+            line["clock_settle"] = settle
+    if not args.full:
+        check_gathered()
+        return line
     if args.no_kernel_timing:
         if rank == 0:
             print(json.dumps({"value": value, "ms_per_step": elapsed / args.steps * 1e3, "note": "A/B run without kernel timing"}))
@@ -601,7 +699,6 @@ def run_ssl(args, world, rank, local_rank, dev, use_dist, dist):
     roof["path_note"] = ("end to end: frames/s x %d algorithmic bytes per frame (SURVEY 8d) / (%d GPU x %.0f GB/s); `frac` is the dominant "
                          "kernel alone -- the two FFT kernels each count the PCM read, so per-kernel fractions are not additive" % (BYTES_PER_FRAME, world, HBM_PEAK_GBPS))
 
-    line = None
     if rank == 0:
         cpu = mvdr = None
         if spread:
@@ -634,21 +731,12 @@ def run_ssl(args, world, rank, local_rank, dev, use_dist, dist):
             import copy
             a2 = copy.copy(args)
             a2.steps, a2.warmup, a2.cpu_frames = max(10, min(args.steps, 30)), 5, (2048 if args.cpu_frames > 0 else 0)
+            a2.dump_outputs = None
             ml = run_mvdr(a2, 1, 0, local_rank, dev, False, None)
             mvdr = {k_: ml[k_] for k_ in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "algorithmic_GBps", "hbm_roofline_frac", "kernels", "roofline", "cpu_baseline")}
             mvdr["workload"] = ml["config"]["workload"]
-        line = {
-            "metric": "STFT frames/sec, 8-mic GCC-PHAT + SRP-PHAT(361) + delay-and-sum beamform @48kHz/1024-pt",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32" if args.precision == "fp32" else "f32 (SRP operands %s)" % args.precision, "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2] geometry (8-mic ULA 0.04 m, 48 kHz, N=1024, hop 512, 361 angles, "
-                                   "1 source, no power floor), %d arrays x %d frames per GPU per step; channel rows padded by %d floats" % (A, F, ROW_PAD),
-                       "arrays_per_gpu": A, "frames_per_array": F, "srp_precision": args.precision,
-                       "parallelism": "arrays sharded over %d GPU(s), all_gather of DOA bins+prob%s" % (world, " + gather of the beamformed audio to rank 0" if args.gather_audio else ""),
-                       "single_stream_4096": single, "das_single_stream": das, "mvdr_256x64": mvdr},
-            "algorithmic_GBps": value * BYTES_PER_FRAME / 1e9,
-            "hbm_roofline_frac": value * BYTES_PER_FRAME / 1e9 / (HBM_PEAK_GBPS * world),
+        line["config"].update({"single_stream_4096": single, "das_single_stream": das, "mvdr_256x64": mvdr})
+        line.update({
             "kernels": kt, "roofline": roof, "roofline_by_kernel": by_kernel, "cpu_baseline": cpu, "repair": repair, "repair_spread": spread,
             "order": "config.single_stream_4096, config.das_single_stream and repair_spread ran BEFORE the warm-up steps (outside the timed region: the same "
                      "kernels on other shapes, which also brings the clocks to their loaded state); cpu_baseline and config.mvdr_256x64 after the timed region",
@@ -658,20 +746,8 @@ def run_ssl(args, world, rank, local_rank, dev, use_dist, dist):
                                                          "_warmup1.json: 39.0 / 46.1 M frames/s with 0 / 1 warm-up steps and no extras, against 48.3 M for this order on the same box)"},
             "kernels_note": "hipEvent pairs on the launch stream: %s over the timed region, the other groups in a "
                             "pass of %d steps after it (bracketing all of them inside the timed region costs ~2.5 %%)" % (" and ".join(kt_timed), table_steps),
-            "exchange": {"backend": dist.get_backend() if use_dist else None, "gather_audio": bool(args.gather_audio),
-                         "bytes_per_step_per_rank": 8 * A * F + (4 * A * F * HOP if args.gather_audio else 0)},
-        }
-    if use_dist:
-        # the gathered buffers hold every rank's block at its global position
-        all_bin, all_prob = xg.gathered_doa(last)
-        mine_bin, mine_prob = xg.doa_buffers(last)
-        ok = torch.equal(all_bin[rank * A:(rank + 1) * A], mine_bin) and torch.equal(all_prob[rank * A:(rank + 1) * A], mine_prob)
-        if args.gather_audio and rank == 0:
-            ok = ok and torch.equal(xg.gathered_audio(last)[:A], xg.audio_buffer(last))
-        if not ok:
-            print("rank %d: gathered buffers do not contain this rank's block" % rank, file=sys.stderr)
-            dist.destroy_process_group()
-            raise SystemExit(3)
+        })
+    check_gathered()
     return line
 
 
@@ -696,9 +772,35 @@ def run_mvdr(args, world, rank, local_rank, dev, use_dist, dist):
     def arm():
         bf.set_timing(True)
 
-    elapsed = timed_loop(step, lambda: None, args.steps, args.warmup, use_dist, dist, dev, arm)
+    settle = None
+    if not args.full:
+        # a plain run: the clocks settle on a beamformer of its own (settle_clocks) and no kernel is bracketed
+        bs = api.MvdrBeamformer(FS, xs, NFFT, max_streams=S_, device=local_rank)
+        so = torch.empty_like(out)
+        settle = settle_clocks(lambda: bs.process_dev(pcm, F, doa, out_pcm=so, stream=stream), SETTLE_S)
+        bs.close()
+        del so
+    elapsed = timed_loop(step, lambda: None, args.steps, args.warmup, use_dist, dist, dev, arm if args.full else None)
     bf.set_timing(False)
     value = S_ * F * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"audio": (out.view(S_, F, HOP), "audio")})
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "STFT frames/sec, 16-mic frequency-domain beamformer with per-bin spatial covariance (MVDR) @48kHz/1024-pt",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[3]: 16-mic ULA 0.02 m, 48 kHz, N=1024, hop 512, covariance memory 0.95, loading 1e-3, "
+                                   "%d concurrent streams x %d frames per GPU per step" % (S_, F),
+                       "streams_per_gpu": S_, "frames_per_stream": F, "parallelism": "streams sharded over %d GPU(s), no exchange" % world},
+            "algorithmic_GBps": value * bytes_per_frame / 1e9, "hbm_roofline_frac": value * bytes_per_frame / 1e9 / (HBM_PEAK_GBPS * world),
+        }
+        if settle:
+            line["clock_settle"] = settle
+    if not args.full:
+        return line
     kt = {}
     for kid, name in ((0, "k_mvdr_analyse"), (1, "k_mvdr_solve"), (2, "k_mvdr_synth")):
         n, ms = bf.get_timing(kid)
@@ -735,7 +837,6 @@ def run_mvdr(args, world, rank, local_rank, dev, use_dist, dist):
         roof["note"] = ("`frac` is the HBM fraction of k_mvdr_solve's algorithmic bytes (the [bin][mic] spectra in, one beamformed bin out per problem); the kernel is "
                         "bound by its vector work (K Cholesky factorisations of order 16 per frame and stream): `flop_roofline` prices the problem's multiply-"
                         "accumulates against the fp32 vector peak, `valu_roofline` the instructions it actually issues against the issue rate")
-    line = None
     if rank == 0:
         cpu = None
         if world == 1 and args.cpu_frames > 0:
@@ -758,17 +859,7 @@ def run_mvdr(args, world, rank, local_rank, dev, use_dist, dist):
                    "sample": "streams 0..%d, %d frames each of the same input, %.1f s, double-precision scalar C restatement of the same algorithm "
                              "(oracle/mca_oracle.c mca_or_mvdr_*, -O3); GPU/oracle audio error on the sample (first call of a fresh state): %.1e of the peak"
                              % (n_cpu - 1, F, dt, worst)}
-        line = {
-            "metric": "STFT frames/sec, 16-mic frequency-domain beamformer with per-bin spatial covariance (MVDR) @48kHz/1024-pt",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[3]: 16-mic ULA 0.02 m, 48 kHz, N=1024, hop 512, covariance memory 0.95, loading 1e-3, "
-                                   "%d concurrent streams x %d frames per GPU per step" % (S_, F),
-                       "streams_per_gpu": S_, "frames_per_stream": F, "parallelism": "streams sharded over %d GPU(s), no exchange" % world},
-            "algorithmic_GBps": value * bytes_per_frame / 1e9, "hbm_roofline_frac": value * bytes_per_frame / 1e9 / (HBM_PEAK_GBPS * world),
-            "kernels": kt, "roofline": roof, "cpu_baseline": cpu,
-        }
+        line.update({"kernels": kt, "roofline": roof, "cpu_baseline": cpu})
     return line
 
 
@@ -784,16 +875,21 @@ def main():
     ap.add_argument("--streams", type=int, default=256, help="--config mvdr: concurrent 16-mic streams per GPU")
     ap.add_argument("--mvdr-frames", type=int, default=64, help="--config mvdr: frames per stream per step")
     ap.add_argument("--precision", choices=list(PREC), default=os.environ.get("MCA_SRP_PRECISION", "adaptive"))
-    ap.add_argument("--cpu-frames", type=int, default=4096, help="frames timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--cpu-all-cores", type=int, default=1, help="also time the oracle on all host cores, one array per process (0 = skip)")
-    ap.add_argument("--single-stream", type=int, default=1, help="also time the literal configs[2] call: 1 array x 4096 frames (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="also report configs[1] (delay-and-sum single stream), configs[3] (MVDR 256 x 64) and the "
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB: larger outputs are a seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (the options below): the other BASELINE configurations, the CPU "
+                         "baselines and oracle checks, the per-kernel table and the rooflines; a plain run only times the --steps steps")
+    ap.add_argument("--cpu-frames", type=int, default=4096, help="--full: frames timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-all-cores", type=int, default=1, help="--full: also time the oracle on all host cores, one array per process (0 = skip)")
+    ap.add_argument("--single-stream", type=int, default=1, help="--full: also time the literal configs[2] call: 1 array x 4096 frames (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1, help="--full: also report configs[1] (delay-and-sum single stream), configs[3] (MVDR 256 x 64) and the "
                     "content spread of the repair pass in the same line, outside the timed region (0 = skip)")
     ap.add_argument("--gather-audio", action="store_true",
                     help="N > 1: also gather the beamformed audio (2 KB per frame) to rank 0 every step (BASELINE configs[4]: 'RCCL gather of DOA/output')")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket the kernels with HIP events (A/B of the event overhead)")
-    ap.add_argument("--full", action="store_true", help="print the full record (every note, source and sub-measurement: ~15 KB) instead of the compact line")
-    ap.add_argument("--detail-out", default=None, help="file the full record is written to (default: gpurun_out/bench_detail.json when that directory exists)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: do not bracket the kernels with HIP events (A/B of the event overhead)")
+    ap.add_argument("--print-record", action="store_true", help="--full: print the full record (every note, source and sub-measurement: ~15 KB) instead of the compact line")
+    ap.add_argument("--detail-out", default=None, help="file the record is written to")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -827,20 +923,12 @@ def main():
 
     line = (run_mvdr if args.config == "mvdr" else run_ssl)(args, world, rank, local_rank, dev, use_dist, dist)
     if rank == 0 and line is not None:
-        detail = args.detail_out or (os.path.join("gpurun_out", "bench_detail.json") if os.path.isdir("gpurun_out") else None)
-        if detail:
-            try:
-                with open(detail, "w") as fh:
-                    json.dump(line, fh)
-            except OSError:
-                detail = None
-        if args.full:
-            print(json.dumps(line))
-        else:
-            out = compact_line(line)
-            if detail:
-                out["detail"] = detail
-            print(json.dumps(out))
+        if args.detail_out:
+            with open(args.detail_out, "w") as fh:
+                json.dump(line, fh)
+        if args.full and not args.print_record:
+            line = dict(compact_line(line), **({"detail": args.detail_out} if args.detail_out else {}))
+        print(json.dumps(line))
     if use_dist:
         dist.destroy_process_group()
 

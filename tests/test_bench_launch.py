@@ -67,6 +67,32 @@ def test_bench_single_rank_rccl_exchange():
     assert r["n_gpus"] == 1 and r["value"] > 0 and r["exchange"]["backend"] == "nccl" and r["exchange"]["gather_audio"] is True
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline fields only, `value` and `ms_per_step` both from exactly --steps timed steps, and
+    --dump-outputs writes what the last timed step computed: one float32 / float64 .npy per output, within 64 MB."""
+    import numpy as np
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--arrays", "2", "--frames", "512",
+                        "--dump-outputs", str(tmp_path)], env=_clean_env(), capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [line for line in p.stdout.splitlines() if line.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "frames/s" and r["higher_is_better"] is True
+    assert abs(r["value"] - 2 * 512 * 1e3 / r["ms_per_step"]) <= 1e-9 * r["value"]
+    assert not any(k in r for k in ("kernels", "roofline", "cpu_baseline", "repair_spread"))
+    files = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    assert set(files) == {"doa_bin.npy", "doa_rad.npy", "prob.npy", "audio.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    bins = files["doa_bin.npy"]
+    assert bins.shape == (2, 512, 1) and (bins == np.round(bins)).all() and ((bins >= 0) & (bins < 361)).all()
+    assert files["doa_rad.npy"].shape == files["prob.npy"].shape == (2, 512, 1)
+    assert files["audio.npy"].shape == (2, 512, 512) and np.isfinite(files["audio.npy"]).all() and np.abs(files["audio.npy"]).max() > 0
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+
+
 def test_the_printed_line_is_compact_and_complete():
     """The driver reads the END of bench.py's stdout: the line it prints must stay well under 6 KB and still carry every field
     of the contract, `roofline` (with `traffic`) and `cpu_baseline`, and the three other BASELINE configs measured in the same run.  Checked on

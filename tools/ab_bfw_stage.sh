@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 export MCA_HIP_LIB=$GRAFT_REPO_ROOT/abtest/lib_measure.so
 run() {
-  python bench.py --full --steps 100 --warmup 20 --cpu-frames 0 --single-stream 0 --extras 0 $2 2> /dev/null | grep "^{" | tail -1 > /tmp/ab.json
+  python bench.py --full --print-record --steps 100 --warmup 20 --cpu-frames 0 --single-stream 0 --extras 0 $2 2> /dev/null | grep "^{" | tail -1 > /tmp/ab.json
   python - "$1" <<PY
 import json,sys
 d=json.load(open('/tmp/ab.json'))

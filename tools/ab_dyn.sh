@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 A=${1:-8}; F=${2:-4096}
 export MCA_HIP_LIB=$GRAFT_REPO_ROOT/abtest/lib_measure.so
 run() {
-  python bench.py --arrays $A --frames $F --steps 100 --warmup 20 --cpu-frames 0 --single-stream 0 --extras 0 2> /dev/null | grep "^{" | tail -1 > /tmp/ab_dyn.json
+  python bench.py --full --arrays $A --frames $F --steps 100 --warmup 20 --cpu-frames 0 --single-stream 0 --extras 0 2> /dev/null | grep "^{" | tail -1 > /tmp/ab_dyn.json
   python - "$1" <<PY
 import json,sys
 d=json.load(open('/tmp/ab_dyn.json'))

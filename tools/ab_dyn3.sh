@@ -1,11 +1,12 @@
 #!/bin/bash
 # round 5: structure of the exit-clock spread of the static analysis kernel (per workgroup, per XCD)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+OUT=${OUT:-runs}        # where the logs and profiles go (the repository ignores runs/)
 export MCA_HIP_LIB=$GRAFT_REPO_ROOT/abtest/lib_measure.so
-MCA_HIP_WAVE_CLOCK=$GRAFT_REPO_ROOT/gpurun_out/r05_wave_clock_static.txt python bench.py --steps 30 --warmup 10 --cpu-frames 0 --single-stream 0 --extras 0 > /dev/null 2>&1
+MCA_HIP_WAVE_CLOCK=$PWD/$OUT/r05_wave_clock_static.txt python bench.py --full --steps 30 --warmup 10 --cpu-frames 0 --single-stream 0 --extras 0 > /dev/null 2>&1
 python - <<PY
 import numpy as np
-a=np.loadtxt('gpurun_out/r05_wave_clock_static.txt').reshape(-1,4)
+a=np.loadtxt('$OUT/r05_wave_clock_static.txt').reshape(-1,4)
 t0=a[:,1].min(); end=(a[:,2]-t0)/100.0
 wg=end.reshape(-1,4)
 print('waves', len(end), 'exit mean %.1f max %.1f' % (end.mean(), end.max()))

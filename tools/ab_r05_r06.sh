@@ -3,7 +3,7 @@
 # balance of the pair transforms (csrc/pair_balance.h), the fixed-lag policy and the rest of the round cost or gained on the headline step
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 run() {
-  python bench.py --full --steps 100 --warmup 20 --cpu-frames 0 --single-stream 0 --extras 0 2> /dev/null | grep "^{" | tail -1 > /tmp/ab.json
+  python bench.py --full --print-record --steps 100 --warmup 20 --cpu-frames 0 --single-stream 0 --extras 0 2> /dev/null | grep "^{" | tail -1 > /tmp/ab.json
   python - "$1" <<PY
 import json,sys
 d=json.load(open('/tmp/ab.json'))
