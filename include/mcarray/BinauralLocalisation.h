@@ -1,8 +1,14 @@
 // mca::FreqGCCBinauralLocalisation -- 2-microphone GCC-PHAT localiser, deterministic part of the reference class
 // (include/mcarray/BinauralLocalisation.h:188-247; src/mcarray/BinauralLocalisation.cpp:320-631): smoothed
-// correlation, first-max argmax, the author's DOA smoothing (#else branch :502-504) and setProbability.  The
-// particle filter (:456-473) is a stochastic DSPONE component and is out of scope.
-// The time-domain TemporalGCCBinauralLocalisation of the same header is out of scope.
+// correlation, first-max argmax, the author's DOA smoothing (#else branch :502-504), the per-frame DSPONE hook
+// processParametrisation (:406-567) and setProbability at caller-given angles (:569-631, the weights of the particle
+// filter's observation model).  The particle filter itself (:456-473) is a stochastic DSPONE component and is out of
+// scope.  The time-domain TemporalGCCBinauralLocalisation of the same header is out of scope
+// (SURVEY 2 row 12).
+//
+// Two ways in, each with its own state on the GPU: process() (chunked PCM, the batched stream path, float) and
+// processParametrisation() (one frame of CCS spectra, double).  An object driven through both keeps two states;
+// setProbability reads the one of the path the object used last.
 #ifndef MCA_HIP_BINAURALLOCALISATION_H
 #define MCA_HIP_BINAURALLOCALISATION_H
 #include <cmath>
@@ -55,6 +61,7 @@ public:
         std::vector<int> idx(static_cast<size_t>(F));
         for (int c = 0; c < 2; ++c) std::copy(_pending[c].begin(), _pending[c].begin() + static_cast<long>(L), pcm.begin() + static_cast<long>(L) * c);
         _ctx->check(mca_hip_gcc2_frames_host(_ctx->get(), pcm.data(), 1, F, idx.data(), doa.data(), prob.data(), nullptr));
+        _framePathLast = false;
         std::vector<unsigned char> voiced(static_cast<size_t>(F), 1);
         std::vector<float> power(static_cast<size_t>(F), 0.f);
         if (_usePowerFloor) _ctx->check(mca_hip_copy_gate(_ctx->get(), voiced.data(), power.data()));
@@ -68,6 +75,34 @@ public:
         return F;
     }
     const std::vector<int> &lastArgmax() const { return _lastArgmax; }
+
+    // The DSPONE per-frame hook (BinauralLocalisation.cpp:406-567): analysisFrames[0..1] = CCS spectra double[analysisLength]
+    // (not modified).  Like the reference it computes nothing when no callback is set (:410-414).  On a frame that passes the
+    // gate it updates _currentDOA / _prob and fires setDOA(degrees, prob, power, 1) (:521).
+    virtual void processParametrisation(std::vector<double *> &analysisFrames, int analysisLength, std::vector<double *> &dataChannels,
+                                        int dataLength)
+    {
+        (void)dataChannels; (void)dataLength;
+        if (!_ptrCallback) return;
+        if (analysisLength != getAnalysisLength()) throw MCArrayException("analysisLength does not match the module's FFT size");
+        if (analysisFrames.size() < 2) throw MCArrayException("processParametrisation needs 2 analysis frames");
+        const double *fr[2] = {analysisFrames[0], analysisFrames[1]};
+        int voiced = 0;
+        double doa = 0, prob = 0, power = 0;
+        _ctx->check(mca_hip_gcc2_process_frame(_ctx->get(), fr, analysisLength, &voiced, &doa, &prob, &power, nullptr, nullptr));
+        _framePathLast = true;
+        if (!voiced) return;
+        _currentDOA[0] = doa; _prob[0] = prob;
+        _ptrCallback->setDOA(toDegrees(_currentDOA, 1), _prob, power, 1);
+    }
+
+    // setProbability (BinauralLocalisation.cpp:569-631) at caller-given angles in radians, on the smoothed correlation of the
+    // path used last: processParametrisation's, or else process()'s.  Zeros before any frame has fired.
+    void setProbability(const double *doas, double *probs, int size) override
+    {
+        if (_framePathLast) _ctx->check(mca_hip_gcc2_frame_set_probability(_ctx->get(), doas, probs, size));
+        else _ctx->check(mca_hip_gcc2_set_probability(_ctx->get(), 0, doas, probs, size));
+    }
 
     // the SignalVector / SignalVector16s overloads the reference's callers use (test_mcarray.cpp:618; mcadefs.h:86-88)
     int process(const SignalVector &in, int nSamples)
@@ -90,6 +125,7 @@ private:
     std::shared_ptr<detail::HipContext> _ctx;
     std::vector<float> _pending[2];
     std::vector<int> _lastArgmax;
+    bool _framePathLast = false;       // processParametrisation ran after the last process() (setProbability reads its state)
 };
 
 }  // namespace mca

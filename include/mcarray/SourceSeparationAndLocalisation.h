@@ -3,8 +3,9 @@
 // src/mcarray/SourceSeparationAndLocalisation.cpp:51-107).
 //
 // The reference IS-A dsp::STFT (DSPONE, absent here).  Two ways in:
-//   * processParametrisation(std::vector<double*>&, ...) -- the DSPONE per-frame hook, unchanged signature: a
-//     DSPONE build calls it from its own STFT; frames are modified in place (frame API, double on the GPU).
+//   * processParametrisation(std::vector<double*>&, ...) / processParametrisation(SignalVector&, ...) -- the DSPONE
+//     per-frame hooks, unchanged signatures: a DSPONE build calls them from its own STFT; frames are modified in place
+//     (frame API, double on the GPU).
 //   * process(in, nSamples, out, outSize) -- a stand-in for the dsp::ShortTimeProcess::process overloads the
 //     reference's callers use (mcabeamf.cpp:112, test_mcarray.cpp:869): buffers chunked PCM, runs every complete
 //     frame of the chunk through the batched stream API in ONE device call (STFT, GCC-PHAT, SRP, pick,
@@ -56,16 +57,22 @@ public:
     int getMaxLatency() const { return 1 << _order; }
     int getNumberOfChannels() const { return _nchannels; }
 
-    // The DSPONE hook (SourceSeparationAndLocalisation.cpp:66-94): localise, then separate in place.
-    virtual void processParametrisation(std::vector<double *> &analysisFrames, int analysisLength,
+    // The DSPONE hooks (SourceSeparationAndLocalisation.cpp:66-94): localise, then separate in place.
+    virtual void processParametrisation(SignalVector &analysisFrames, int analysisLength,
                                         std::vector<double *> &dataChannels, int dataLength)
     {
         (void)dataChannels; (void)dataLength;
         if (analysisLength != getAnalysisLength()) throw MCArrayException("analysisLength does not match the module's FFT size");
+        _impl->processFrameLocalisation(analysisFrames, _wienerCoefs);     // .cpp:87
+        _impl->processFrameSeparation(analysisFrames, analysisFrames);     // .cpp:92
+    }
+    // the std::vector<double*> form wraps the frames and delegates (.cpp:66-75)
+    virtual void processParametrisation(std::vector<double *> &analysisFrames, int analysisLength,
+                                        std::vector<double *> &dataChannels, int dataLength)
+    {
         SignalVector sf;
         for (double *p : analysisFrames) sf.push_back(SignalPtr(p, [](double *) {}));   // non-owning, like null_deleter (.cpp:33-49)
-        _impl->processFrameLocalisation(sf, _wienerCoefs);     // .cpp:87
-        _impl->processFrameSeparation(sf, sf);                 // .cpp:92
+        processParametrisation(sf, analysisLength, dataChannels, dataLength);
     }
 
     // process(): chunked PCM in (one pointer per channel), beamformed PCM out (one pointer per source channel;

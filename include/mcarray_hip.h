@@ -169,7 +169,7 @@ int mca_hip_get_pair_delays(const mca_hip_ctx *ctx, float *out);
 int mca_hip_get_doa_grid(const mca_hip_ctx *ctx, float *out);
 
 /* ---- state ----------------------------------------------------------------- */
-/* zero E_prev / DOA / overlap-add tails of every array (a freshly constructed module) */
+/* zero E_prev / DOA / overlap-add tails of every array and the FreqGCC frame hook's state (a freshly constructed module) */
 int mca_hip_reset(mca_hip_ctx *ctx, void *stream);
 /* pre-size the internal workspace so later *_dev calls allocate nothing (graph capture) */
 int mca_hip_reserve(mca_hip_ctx *ctx, int n_arrays, int n_frames);
@@ -178,7 +178,11 @@ int mca_hip_reserve(mca_hip_ctx *ctx, int n_arrays, int n_frames);
  * (SoundLocalisationImpl.h:84-86), _currentDOA / _prob (BeamformingSeparationAndLocalisation.cpp:51-52), the 2-mic
  * path's smoothed DOA and frame count, the frame API's E_prev.  A blob is only valid for a context created with
  * the same geometry, grid, frame length, n_sources and max_arrays (checked: MCA_HIP_ERR_INVALID_ARGUMENT).
- * mca_hip_state_size returns the number of bytes (or a negative status). */
+ * mca_hip_state_size returns the number of bytes (or a negative status).
+ * Version 3 blobs end with the FreqGCC frame hook's part (mca_hip_gcc2_process_frame), 8 * (D + 8) bytes: its smoothed
+ * correlation double[D], then 8 doubles _powerFloor, samples consumed for it, _noiseEstimated, _silenceFramesCounter,
+ * _corrMemoryFactor, _doaMemoryFactor, _currentDOA, _prob.  Version 1 and 2 blobs (without that part) still load and leave
+ * the frame hook as a newly built module. */
 long long mca_hip_state_size(const mca_hip_ctx *ctx);
 int mca_hip_state_save(mca_hip_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_state_load(mca_hip_ctx *ctx, const void *blob, long long blob_bytes);
@@ -295,6 +299,33 @@ int mca_hip_gcc2_frames_dev(mca_hip_ctx *ctx, const float *pcm_dev, long long ar
                             float *doa_rad_dev, float *prob_dev, float *corr_dev, void *stream);
 int mca_hip_gcc2_frames_host(mca_hip_ctx *ctx, const float *pcm, int n_arrays, int n_frames,
                              int *argmax, float *doa_rad, float *prob, float *corr);
+
+/* FreqGCCBinauralLocalisation::setProbability (BinauralLocalisation.cpp:569-631) at caller-given angles (radians), what the
+ * particle filter's observation model asks for (SoundLocalisationParticleFilter.cpp:51): min and sum of the smoothed
+ * correlation, linear interpolation between the neighbouring grid points (the two edge cells take their own value), values
+ * below 0.01 set to 0, in the reference's float/double sequence (angle2DOAidx on a float angle).  A correlation whose
+ * sum - min * D is not positive -- a context freshly created or reset -- gives all zeros (the reference reads its
+ * uninitialised buffer there).  n == 0 is a no-op; n_mics != 2, n < 0 and NULL pointers with n > 0 are invalid.
+ * On the smoothed correlation the last mca_hip_gcc2_frames_* call left for array `array_index` (gated-out frames do not
+ * change it), array_index in [0, max_arrays).  Synchronises the device. */
+int mca_hip_gcc2_set_probability(mca_hip_ctx *ctx, int array_index, const double *doas, double *probs, int n);
+/* The same for arrays 0..n_arrays-1 in one launch: doas_dev / probs_dev [n_arrays][n] float, n_arrays <= max_arrays.
+ * Enqueued on `stream`: no allocation and no synchronisation (usable between gcc2_frames_dev calls of a tracker loop).
+ * Row a of the result equals float(mca_hip_gcc2_set_probability(a, double(doas[a]))) bit for bit. */
+int mca_hip_gcc2_set_probability_dev(mca_hip_ctx *ctx, int n_arrays, const float *doas_dev, float *probs_dev, int n,
+                                     void *stream);
+/* FreqGCCBinauralLocalisation::processParametrisation (BinauralLocalisation.cpp:406-567, deterministic branch) for one
+ * frame: frames[0..1] -> double[ccs_len] CCS spectra, ccs_len = fft_size + 2; double on the GPU; its own state, separate
+ * from the stream state (a context driven through both keeps two).  The power-floor estimation runs for the first 3 s
+ * whether use_power_floor is set or not, and `power` is the floor meanwhile (:387-404, :429); then FFTLogPower.
+ * voiced = 1 where the gate passed (the reference's callback fires: setDOA(degrees(doa_rad), prob, power, 1), :521).
+ * doa_rad / prob = _currentDOA / _prob after the frame (0 / -1 before the first voiced frame); prob is setProbability of
+ * the previous DOA on the new correlation (:454).  power = the value handed to setDOA.  argmax (may be NULL) = first-max
+ * index, -1 on gated-out frames.  corr (may be NULL) = double[D], the smoothed correlation after the frame. */
+int mca_hip_gcc2_process_frame(mca_hip_ctx *ctx, const double *const *frames, int ccs_len, int *voiced,
+                               double *doa_rad, double *prob, double *power, int *argmax, double *corr);
+/* setProbability, as mca_hip_gcc2_set_probability, on the frame hook's correlation */
+int mca_hip_gcc2_frame_set_probability(mca_hip_ctx *ctx, const double *doas, double *probs, int n);
 
 /* ---- binaural masking (FastBinauralMasking) --------------------------------------------- */
 typedef struct mca_hip_mask_ctx mca_hip_mask_ctx;

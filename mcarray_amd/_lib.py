@@ -118,6 +118,11 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
       C.c_void_p, C.c_void_p]),
     ("mca_hip_gcc2_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, c_ip, c_fp, c_fp, c_fp]),
+    ("mca_hip_gcc2_set_probability", C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, C.c_int]),
+    ("mca_hip_gcc2_set_probability_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    ("mca_hip_gcc2_process_frame", C.c_int,
+     [C.c_void_p, C.POINTER(c_dp), C.c_int, c_ip, c_dp, c_dp, c_dp, c_ip, c_dp]),
+    ("mca_hip_gcc2_frame_set_probability", C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int]),
     ("mca_hip_mask_create", C.c_int, [C.POINTER(MaskConfig), C.POINTER(C.c_void_p)]),
     ("mca_hip_mask_destroy", None, [C.c_void_p]),
     ("mca_hip_mask_last_error", C.c_char_p, [C.c_void_p]),

@@ -239,6 +239,52 @@ class Context:
             res["power"] = power
         return res
 
+    def gcc2_frames_dev(self, pcm, n_frames, argmax, doa_rad=None, prob=None, corr=None, stream=None):
+        """mca_hip_gcc2_frames_dev: pcm torch float32 cuda tensor [A][2][>= (F+1)*hop]; outputs preallocated cuda tensors
+        argmax int32 [A][F], doa_rad / prob float32 [A][F], corr float32 [A][F][D] (all but argmax optional)."""
+        A, M, L = pcm.shape
+        if M != 2 or not pcm.is_contiguous():
+            raise MCArrayHipError("pcm must be a contiguous [A][2][L] tensor")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(self._lib.mca_hip_gcc2_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
+                                                      ptr(corr), stream))
+
+    def gcc2_set_probability(self, doas, array_index=0):
+        """setProbability (BinauralLocalisation.cpp:569-631) at the angles `doas` (radians) on the smoothed correlation the last
+        gcc2_frames_* call left for array `array_index` -> float64 [n]"""
+        doas = np.ascontiguousarray(doas, dtype=np.float64).reshape(-1)
+        probs = np.empty(len(doas))
+        self._check(self._lib.mca_hip_gcc2_set_probability(self.h, int(array_index), doas.ctypes.data_as(_lib.c_dp),
+                                                           probs.ctypes.data_as(_lib.c_dp), len(doas)))
+        return probs
+
+    def gcc2_set_probability_dev(self, doas, probs, stream=None):
+        """The same for arrays 0..A-1 in one launch: doas / probs torch float32 cuda tensors [A][n], enqueued on `stream`."""
+        if doas.dim() != 2 or tuple(probs.shape) != tuple(doas.shape) or not doas.is_contiguous() or not probs.is_contiguous():
+            raise MCArrayHipError("doas and probs must be contiguous [A][n] tensors of one shape")
+        A, n = doas.shape
+        self._check(self._lib.mca_hip_gcc2_set_probability_dev(self.h, A, C.c_void_p(doas.data_ptr()), C.c_void_p(probs.data_ptr()), n,
+                                                               stream))
+
+    def gcc2_process_frame(self, frames):
+        """FreqGCCBinauralLocalisation::processParametrisation for one frame: frames [2][N+2] CCS (double) ->
+        dict(voiced, doa, prob, power, argmax, corr [D]) after the frame (BinauralLocalisation.cpp:406-567)."""
+        frames, arr = self._rows(frames)
+        v, i = C.c_int(0), C.c_int(0)
+        doa, prob, power = C.c_double(0), C.c_double(0), C.c_double(0)
+        corr = np.empty(self.D)
+        self._check(self._lib.mca_hip_gcc2_process_frame(self.h, arr, frames.shape[1], C.byref(v), C.byref(doa), C.byref(prob),
+                                                         C.byref(power), C.byref(i), corr.ctypes.data_as(_lib.c_dp)))
+        return dict(voiced=bool(v.value), doa=doa.value, prob=prob.value, power=power.value, argmax=i.value, corr=corr)
+
+    def gcc2_frame_set_probability(self, doas):
+        """setProbability on the frame hook's correlation (gcc2_process_frame) -> float64 [n]"""
+        doas = np.ascontiguousarray(doas, dtype=np.float64).reshape(-1)
+        probs = np.empty(len(doas))
+        self._check(self._lib.mca_hip_gcc2_frame_set_probability(self.h, doas.ctypes.data_as(_lib.c_dp), probs.ctypes.data_as(_lib.c_dp),
+                                                                 len(doas)))
+        return probs
+
     # ---- frame API ----
     def _rows(self, frames):
         frames = np.ascontiguousarray(frames, dtype=np.float64)
@@ -409,7 +455,9 @@ class SourceLocalisation(SourceSeparationAndLocalisation):
 class FreqGCCBinauralLocalisation:
     """mca::FreqGCCBinauralLocalisation(int sampleRate, ArrayDescription, bool usePowerFloor)
     (BinauralLocalisation.h:191), deterministic part: smoothed GCC-PHAT correlation, first-max argmax,
-    DOA smoothing and setProbability.  The reference's grid is 3 degrees (BinauralLocalisation.cpp:328)."""
+    DOA smoothing and setProbability.  The reference's grid is 3 degrees (BinauralLocalisation.cpp:328).
+    process() (PCM, batched stream path) and process_frame() (one frame of CCS spectra, the per-frame hook) keep separate
+    states; set_probability() reads the one of the path used last."""
 
     FRAME_SECONDS = 0.075        # _frameRate (BinauralLocalisation.h:196)
 
@@ -421,6 +469,7 @@ class FreqGCCBinauralLocalisation:
         if self.ctx.M != 2:
             raise MCArrayHipError("FreqGCCBinauralLocalisation needs exactly 2 microphones")
         self.callback = None
+        self._frame_path_last = False
 
     def set_callback(self, cb):
         self.callback = cb
@@ -429,6 +478,7 @@ class FreqGCCBinauralLocalisation:
         """-> dict(argmax, doa, prob[, corr][, voiced, power]); the callback fires per frame of array 0 that passed the gate
         as setDOA(degrees, prob, power, 1) (BinauralLocalisation.cpp:521)."""
         r = self.ctx.gcc2_frames_host(pcm, want_corr)
+        self._frame_path_last = False
         if self.callback is not None:
             for t in range(r["doa"].shape[1]):
                 if "voiced" in r and not r["voiced"][0, t]:
@@ -436,6 +486,22 @@ class FreqGCCBinauralLocalisation:
                 self.callback(np.array([np.rad2deg(float(r["doa"][0, t]))]), np.array([r["prob"][0, t]]),
                               float(r["power"][0, t]) if "power" in r else 0.0, 1)
         return r
+
+    def process_frame(self, left, right):
+        """processParametrisation (BinauralLocalisation.cpp:406-567) for one frame of CCS spectra double[N+2] -> dict(voiced, doa,
+        prob, power, argmax, corr); the callback fires on a voiced frame as setDOA(degrees, prob, power, 1) (:521)."""
+        r = self.ctx.gcc2_process_frame(np.stack([np.asarray(left, dtype=np.float64), np.asarray(right, dtype=np.float64)]))
+        self._frame_path_last = True
+        if self.callback is not None and r["voiced"]:
+            self.callback(np.array([np.rad2deg(r["doa"])]), np.array([r["prob"]]), r["power"], 1)
+        return r
+
+    def set_probability(self, doas, array_index=0):
+        """setProbability (BinauralLocalisation.cpp:569-631) at the angles `doas` (radians) -> float64: on process_frame()'s state
+        if that path ran last, else on process()'s state of array `array_index`."""
+        if self._frame_path_last:
+            return self.ctx.gcc2_frame_set_probability(doas)
+        return self.ctx.gcc2_set_probability(doas, array_index)
 
 
 class _StateBlob:

@@ -106,6 +106,16 @@ struct Workspace {
     }
 };
 
+// FreqGCCBinauralLocalisation::processParametrisation (mca_hip_gcc2_process_frame): the scalars of BinauralLocalisation.cpp:320-404
+// and :530-560, host side.  All of them are doubles (the ints, the bool and the float memory factors exactly) so that the blob part
+// they make (mca_hip_state_save, version 3) is 8 doubles in this order.
+struct G2FrameState {
+    double power_floor = 0, samples = 0, noise_estimated = 0;   // _powerFloor, _samplesConsumedForNoise, _noiseEstimated
+    double silence = 0;                                         // _silenceFramesCounter
+    double corr_mem = 0, doa_mem = 0;                           // _corrMemoryFactor, _doaMemoryFactor (floats, :323-324)
+    double doa = 0, prob = -1;                                  // _currentDOA, _prob (:339-340)
+};
+
 struct mca_hip_ctx {
     mca_hip_config cfg{};
     std::vector<double> xyz;
@@ -195,6 +205,10 @@ struct mca_hip_ctx {
     double *d_res = nullptr;      // [S] doa, [S] prob, power
     int *d_bins = nullptr;
     double *d_out64 = nullptr; size_t out64_elems = 0;
+    // FreqGCC frame hook (double): its own smoothed correlation, apart from the stream state d_E and the steering frame state d_E64
+    double *d_g2f_corr[2] = {nullptr, nullptr}; int g2f_cur = 0;   // _prevCorrelationsReal [D], double buffered like d_E64
+    double *d_g2f_res = nullptr;                                   // [4] argmax, prob, DOA (k_frame_gcc2), linear power (k_frame_power)
+    G2FrameState g2f;
     std::vector<double> h_stage;
     StagePool stage;              // device staging of the host-pointer entry points
     // timing
@@ -262,6 +276,7 @@ void free_ctx(mca_hip_ctx *c)
     for (auto &q : c->io_stream) if (q) (void)hipStreamDestroy(q);
     F(c->d_last_bin); F(c->d_last_rad); F(c->d_last_prob);
     F(c->d_fr); F(c->d_E64[0]); F(c->d_E64[1]); F(c->d_res); F(c->d_bins); F(c->d_out64);
+    F(c->d_g2f_corr[0]); F(c->d_g2f_corr[1]); F(c->d_g2f_res);
     c->stage.release();
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : c->pool) (void)hipEventDestroy(e);
@@ -1217,7 +1232,9 @@ int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
         (rc = zalloc((void **)&c->d_silence, na * 4)) || (rc = zalloc((void **)&c->d_g2_post0, na * 4)) ||
         (rc = zalloc((void **)&c->d_rstats, 32)) || (rc = zalloc((void **)&c->d_queue, 64)) ||
         (rc = zalloc((void **)&c->d_E64[0], c->D * 8)) || (rc = zalloc((void **)&c->d_E64[1], c->D * 8)) ||
-        (rc = zalloc((void **)&c->d_res, (2 * MCA_MAX_SOURCES + 1) * 8)) || (rc = zalloc((void **)&c->d_bins, MCA_MAX_SOURCES * 4))) {
+        (rc = zalloc((void **)&c->d_res, (2 * MCA_MAX_SOURCES + 1) * 8)) || (rc = zalloc((void **)&c->d_bins, MCA_MAX_SOURCES * 4)) ||
+        (rc = zalloc((void **)&c->d_g2f_corr[0], c->D * 8)) || (rc = zalloc((void **)&c->d_g2f_corr[1], c->D * 8)) ||
+        (rc = zalloc((void **)&c->d_g2f_res, 4 * 8))) {
         g_create_error = c->err; free_ctx(c); return rc;
     }
     if (lazy_context(c)) {
@@ -1277,6 +1294,7 @@ int mca_hip_reset(mca_hip_ctx *c, void *stream)
         HIP_TRY(c, hipMemsetAsync(c->d_E[i], 0, na * c->D * 4, st));
         HIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, na * c->S * c->H * 4, st));
         HIP_TRY(c, hipMemsetAsync(c->d_E64[i], 0, (size_t)c->D * 8, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_g2f_corr[i], 0, (size_t)c->D * 8, st));
         HIP_TRY(c, hipMemsetAsync(c->d_doa[i], 0, na * 4, st));
         HIP_TRY(c, hipMemsetAsync(c->d_vdone[i], 0, na * 8, st));
     }
@@ -1293,6 +1311,7 @@ int mca_hip_reset(mca_hip_ctx *c, void *stream)
         if (w.d_nlist) HIP_TRY(c, hipMemsetAsync(w.d_nlist, 0, 16, st));
     }
     c->gcc2_frames_done = 0;
+    c->g2f = G2FrameState();                                                              // the frame hook as a newly built module
     return init_last_state(c, st);
 }
 
@@ -1305,7 +1324,7 @@ struct StateHeader {
     long long gcc2_frames_done;
 };
 constexpr unsigned STATE_MAGIC = 0x4d434153u;   // "MCAS"
-constexpr int STATE_VERSION = 2;                // 2: + _silenceFramesCounter per array
+constexpr int STATE_VERSION = 3;                // 2: + _silenceFramesCounter per array; 3: + the FreqGCC frame hook (frame_part_bytes)
 
 unsigned delays_hash(const mca_hip_ctx *c)
 {
@@ -1325,8 +1344,13 @@ std::vector<StatePart> state_parts(mca_hip_ctx *c)
         {c->d_last_bin, na * MCA_MAX_SOURCES * 4}, {c->d_last_rad, na * MCA_MAX_SOURCES * 4}, {c->d_last_prob, na * MCA_MAX_SOURCES * 4},
         {c->d_doa[c->doa_cur], na * 4}, {c->d_E64[c->e64_cur], (size_t)c->D * 8}, {c->d_vdone[c->doa_cur], na * 8},
         {c->d_silence, na * 4},
+        {c->d_g2f_corr[c->g2f_cur], (size_t)c->D * 8},     // version 3: the frame hook's correlation, then its scalars (host side)
     };
 }
+
+// the part a version-3 blob ends with: the frame hook's double correlation [D], then G2FrameState as 8 doubles
+size_t frame_part_bytes(const mca_hip_ctx *c) { return (size_t)c->D * 8 + sizeof(G2FrameState); }
+static_assert(sizeof(G2FrameState) == 8 * sizeof(double), "G2FrameState is the 8 doubles of the blob");
 
 }  // namespace
 }  // extern "C++"
@@ -1334,7 +1358,7 @@ std::vector<StatePart> state_parts(mca_hip_ctx *c)
 long long mca_hip_state_size(const mca_hip_ctx *c)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    long long n = sizeof(StateHeader);
+    long long n = sizeof(StateHeader) + (long long)sizeof(G2FrameState);
     for (const StatePart &p : state_parts(const_cast<mca_hip_ctx *>(c))) n += (long long)p.bytes;
     return n;
 }
@@ -1354,6 +1378,7 @@ int mca_hip_state_save(mca_hip_ctx *c, void *blob, long long blob_bytes)
     unsigned char *out = static_cast<unsigned char *>(blob);
     std::memcpy(out, &h, sizeof(h)); out += sizeof(h);
     for (const StatePart &p : state_parts(c)) { HIP_TRY(c, hipMemcpy(out, p.ptr, p.bytes, hipMemcpyDeviceToHost)); out += p.bytes; }
+    std::memcpy(out, &c->g2f, sizeof(G2FrameState));
     return MCA_HIP_OK;
 }
 
@@ -1363,20 +1388,25 @@ int mca_hip_state_load(mca_hip_ctx *c, const void *blob, long long blob_bytes)
     if (!blob || blob_bytes < (long long)sizeof(StateHeader)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob is NULL or truncated");
     StateHeader h;
     std::memcpy(&h, blob, sizeof(h));
-    // version 1 blobs end before the _silenceFramesCounter part (the only change of version 2): they load with the counters at zero
-    if (h.magic != STATE_MAGIC || (h.version != STATE_VERSION && h.version != 1)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "not a state blob of this library version");
+    // version 1 blobs end before the _silenceFramesCounter part (the change of version 2): they load with the counters at zero;
+    // version 1 and 2 blobs end before the frame hook's part (the change of version 3): they load with a fresh frame hook
+    if (h.magic != STATE_MAGIC || h.version < 1 || h.version > STATE_VERSION) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "not a state blob of this library version");
     if (h.M != c->M || h.D != c->D || h.S != c->S || h.H != c->H || h.max_arrays != c->cfg.max_arrays || h.use_floor != c->cfg.use_power_floor ||
         h.delays_hash != delays_hash(c))
         return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with a different configuration");
-    const long long v1_short = h.version == 1 ? (long long)c->cfg.max_arrays * 4 : 0;       // bytes of the part a version-1 blob lacks
-    if (blob_bytes < mca_hip_state_size(c) - v1_short) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob is truncated");
+    const long long short_by = (h.version == 1 ? (long long)c->cfg.max_arrays * 4 : 0) +         // bytes of the parts an older blob lacks
+                               (h.version < 3 ? (long long)frame_part_bytes(c) : 0);
+    if (blob_bytes < mca_hip_state_size(c) - short_by) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob is truncated");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipDeviceSynchronize());
     const unsigned char *in = static_cast<const unsigned char *>(blob) + sizeof(h);
     for (const StatePart &p : state_parts(c)) {
         if (h.version == 1 && p.ptr == c->d_silence) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
+        if (h.version < 3 && p.ptr == c->d_g2f_corr[c->g2f_cur]) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
         HIP_TRY(c, hipMemcpy(p.ptr, in, p.bytes, hipMemcpyHostToDevice)); in += p.bytes;
     }
+    if (h.version >= 3) std::memcpy(&c->g2f, in, sizeof(G2FrameState));
+    else c->g2f = G2FrameState();
     c->gcc2_frames_done = h.gcc2_frames_done;
     c->hist_pending = false;                      // (a blob holds the exact state)
     return MCA_HIP_OK;
@@ -2624,6 +2654,122 @@ int mca_hip_get_energy(mca_hip_ctx *c, double *out)
     if (!c || !out) return MCA_HIP_ERR_INVALID_ARGUMENT;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipMemcpy(out, c->d_E64[c->e64_cur], (size_t)c->D * 8, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+// ---- FreqGCC: setProbability at caller-given angles and the frame hook ---------------------------------------------------
+static int gcc2_prob_args(mca_hip_ctx *c, const void *doas, const void *probs, int n)
+{
+    if (c->M != 2) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "setProbability of the 2-microphone GCC path needs a context with n_mics == 2");
+    if (n < 0) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n < 0");
+    if (n > 0 && (!doas || !probs)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doas/probs is NULL");
+    return MCA_HIP_OK;
+}
+
+// host angles in, host probabilities out, one correlation row (synchronises: the row may still be written by a *_dev call)
+extern "C++" template <typename TC>
+static int gcc2_prob_host(mca_hip_ctx *c, const TC *row, const double *doas, double *probs, int n)
+{
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    double *d_in = (double *)c->stage.get(5, (size_t)n * 8), *d_out = (double *)c->stage.get(6, (size_t)n * 8);
+    if (!d_in || !d_out) return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    HIP_TRY(c, hipMemcpy(d_in, doas, (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((k_gcc2_prob<TC, double>), dim3((n + 255) / 256, 1), dim3(256), 0, 0, row, 0LL, c->D, c->step, c->d_grid, d_in, d_out, n);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpy(probs, d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+int mca_hip_gcc2_set_probability(mca_hip_ctx *c, int array_index, const double *doas, double *probs, int n)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    int rc = gcc2_prob_args(c, doas, probs, n);
+    if (rc) return rc;
+    if (array_index < 0 || array_index >= c->cfg.max_arrays) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "array_index outside [0, max_arrays)");
+    if (n == 0) return MCA_HIP_OK;
+    return gcc2_prob_host<float>(c, c->d_E[c->e_cur] + (size_t)array_index * c->D, doas, probs, n);
+}
+
+int mca_hip_gcc2_set_probability_dev(mca_hip_ctx *c, int n_arrays, const float *doas_dev, float *probs_dev, int n, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    int rc = gcc2_prob_args(c, doas_dev, probs_dev, n);
+    if (rc) return rc;
+    if (n_arrays < 0 || n_arrays > c->cfg.max_arrays) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays outside [0, max_arrays]");
+    if (n == 0 || n_arrays == 0) return MCA_HIP_OK;
+    // d_E[e_cur] is the row the last ENQUEUED gcc2_frames_dev call writes: stream order does the rest
+    hipLaunchKernelGGL((k_gcc2_prob<float, float>), dim3((n + 255) / 256, n_arrays), dim3(256), 0, (hipStream_t)stream, c->d_E[c->e_cur],
+                       (long long)c->D, c->D, c->step, c->d_grid, doas_dev, probs_dev, n);
+    HIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_gcc2_frame_set_probability(mca_hip_ctx *c, const double *doas, double *probs, int n)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    int rc = gcc2_prob_args(c, doas, probs, n);
+    if (rc) return rc;
+    if (n == 0) return MCA_HIP_OK;
+    return gcc2_prob_host<double>(c, c->d_g2f_corr[c->g2f_cur], doas, probs, n);
+}
+
+// FreqGCCBinauralLocalisation::processParametrisation (BinauralLocalisation.cpp:406-567), deterministic branch, one frame.  The
+// correlation, its smoothing, argmax, setProbability of the previous DOA and the DOA recursion are enqueued whatever the gate
+// decides (one round trip per frame); a gated-out frame leaves the state's half of the double buffer current, so it changes nothing.
+int mca_hip_gcc2_process_frame(mca_hip_ctx *c, const double *const *frames, int ccs_len, int *voiced, double *doa_rad,
+                               double *prob, double *power, int *argmax, double *corr)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (c->M != 2) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the FreqGCC frame hook needs a context with n_mics == 2");
+    if (!voiced || !doa_rad || !prob || !power) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "voiced/doa_rad/prob/power is NULL");
+    int rc = upload_frames(c, frames, ccs_len);
+    if (rc) return rc;
+    G2FrameState &g = c->g2f;
+    const float corr_mem = (float)g.corr_mem, doa_mem = (float)g.doa_mem;
+    const C2<double> *X = reinterpret_cast<const C2<double> *>(c->d_fr);
+    double *Ein = c->d_g2f_corr[c->g2f_cur], *Eout = c->d_g2f_corr[c->g2f_cur ^ 1];
+    hipLaunchKernelGGL(k_frame_power<double>, dim3(1), dim3(256), 0, 0, X, 2, c->K, c->d_g2f_res + 3);
+    // GCC-PHAT at the D delays of the pair (0, 1), corr = (1 - mu) R + mu prev (:438-448)
+    hipLaunchKernelGGL(k_frame_srp<double>, dim3(c->D), dim3(256), 0, 0, X, c->K, c->D, 1, c->d_pairs, c->d_delays, Ein, Eout,
+                       (double)corr_mem, (double)(1 - corr_mem), c->cfg.gcc_weighting == MCA_HIP_GCC_NONE ? 1 : 0);
+    hipLaunchKernelGGL(k_frame_gcc2<double>, dim3(1), dim3(64), 0, 0, Eout, c->D, c->step, c->d_grid, g.doa, (double)doa_mem,
+                       (double)(1 - doa_mem), c->d_g2f_res);
+    HIP_TRY(c, hipGetLastError());
+    double res[4];
+    HIP_TRY(c, hipMemcpy(res, c->d_g2f_res, sizeof(res), hipMemcpyDeviceToHost));
+    // the gate (:425-434): setPowerFloor while the floor is estimated -- with or without usePowerFloor -- and `power` is the floor
+    // meanwhile (:387-404); FFTLogPower afterwards
+    double pw;
+    if (g.noise_estimated == 0) {
+        const int needed = (int)(3.0 * c->cfg.sample_rate);                    // _durationToEstimatePowerFloor (SoundLocalisationImpl.h:77)
+        g.power_floor += res[3] * (ccs_len - 2) + 1e-10;                       // :390-391
+        g.samples += ccs_len - 2;                                              // :392
+        if (g.samples >= needed) {
+            g.noise_estimated = 1;
+            if (g.samples > 0) g.power_floor /= g.samples;
+            g.power_floor = 10 * std::log10(g.power_floor) + (double)6.0f;      // _noiseMarginDB (BinauralLocalisation.h:197)
+        }
+        pw = g.power_floor;
+    } else {
+        pw = 10.0 * std::log10(res[3]);
+    }
+    const bool fire = pw > g.power_floor || !c->cfg.use_power_floor;          // :434
+    if (fire) {
+        g.prob = res[1];                                                       // :454
+        g.doa = res[2];                                                        // :502-504
+        g.corr_mem = 0.8f; g.doa_mem = 0.6f; g.silence = 0;                    // :523-525
+        c->g2f_cur ^= 1;
+    } else if (g.noise_estimated != 0) {                                       // the silence rule (:530-560)
+        const int windows_to_decay = 3 * c->cfg.sample_rate / (ccs_len / 2 - 1);
+        if (g.silence < windows_to_decay) { g.corr_mem = 0.8f; g.doa_mem = 0.6f; }
+        else { g.corr_mem = 0; g.doa_mem = 0; }
+        g.silence += 1;
+    }
+    *voiced = fire ? 1 : 0;
+    *doa_rad = g.doa; *prob = g.prob; *power = pw;
+    if (argmax) *argmax = fire ? (int)res[0] : -1;
+    if (corr) HIP_TRY(c, hipMemcpy(corr, c->d_g2f_corr[c->g2f_cur], (size_t)c->D * 8, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
 }
 

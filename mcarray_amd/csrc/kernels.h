@@ -52,6 +52,11 @@ __global__ void k_gcc2_scan(Gcc2ScanArgs p);
 __global__ void k_gcc2_compact(const unsigned char *voiced, int n_frames, int *vidx, int *nv, const int *post0, int *silence,
                                int windows_to_decay, unsigned char *vreset);
 __global__ void k_gcc2_fill(Gcc2FillArgs p);
+template <typename TC, typename TA>       // setProbability at caller-given angles (kernels_gcc2_prob.hip)
+__global__ void k_gcc2_prob(const TC *corr, long long corr_stride, int D, float step, const float *grid, const TA *doas, TA *probs, int n);
+template <typename T>
+__global__ void k_frame_gcc2(const T *corr, int D, float step, const float *grid, double doa_prev, double doa_mem, double one_minus_doa_mem,
+                             double *res);
 __global__ void k_mask_stream(MaskArgs p);
 __global__ void k_mask_stream_gen(MaskGenArgs p);
 __global__ void k_mask_stream_2048(MaskGenArgs p);
