@@ -35,45 +35,30 @@ struct mca_hip_graph;
 // ---- switches --------------------------------------------------------------------------------------------------------------
 // Read ONCE, by mca_hip_create, into the context: nothing on a call path reads the environment.  The product switches are fields of
 // mca_hip_config (adaptive_fallback, adaptive_min_rows, adaptive_max_sources, scan_carry) with an environment override for tests and
-// tools that reach a context only through a wrapper.  The A/B switches that exist so that a measured claim of DESIGN.md can be
-// repeated -- one of them (MCA_HIP_BFW_ABL) returns deliberately wrong audio -- are compiled in only with -DMCA_MEASURE
-// (make MEASURE=1, tools/*.py say when they need it); in the default build they are the constants below.
+// tools that reach a context only through a wrapper.
 // The back-off policy reads the report of an adaptive call at a FIXED lag: the eligible call FB_LAG calls after the one that enqueued
 // it (and blocks on the page-locked word if it has not arrived: at a lag of two the work of the call in between is still queued
 // behind it, so the device does not idle).  What a call does therefore depends on the sequence of calls and their content only, not
 // on when a report happens to land: two runs of one stream return the same bits.
 constexpr int FB_LAG = 2, FB_RING = 64, FB_WAIT_MS = 4000;
 struct Knobs {
-    // product
     bool fb_enabled = true;            // MCA_HIP_ADAPT_FALLBACK=0 / cfg.adaptive_fallback = OFF
     long long adapt_min_rows = 4096;   // MCA_HIP_ADAPT_MIN_ROWS / cfg.adaptive_min_rows
-    int repair_items = 768;            // (measurement) MCA_HIP_REPAIR_ITEMS: work items above which the repair contraction halves its K split (0: never)
     int adapt_max_sources = 1;         // MCA_HIP_ADAPT_MAX_SOURCES / cfg.adaptive_max_sources
     double tau_scale = 1.0;            // MCA_HIP_ADAPT_TAU_SCALE (tools/adaptive_check.py: 1e9 turns the repair off to measure the coarse error)
     long long ws_max_bytes = 4LL << 30;   // MCA_HIP_WS_MAX_MB: A-operand workspace budget per slice of frames (tests force the sliced path)
     bool force_generic = false;        // MCA_HIP_FORCE_GENERIC: the any-length kernels at N = 1024 too (parity test of both)
+    bool no_n2048 = false;             // MCA_HIP_NO_N2048: the any-length kernels at 2048-sample frames (parity of both paths)
     bool scan_carry = false;           // MCA_HIP_SCAN_CARRY / cfg.scan_carry
-    bool lazy_ks_shape = false;        // (measurement) MCA_HIP_LAZY_KS_SHAPE: the repair contraction's K segments by the call's shape also with lazy tails
     int cand = -1;                     // MCA_HIP_ADAPT_CAND: -1 / unset = by the back-off policy's reports (cand_call), 1 = wherever the call's shape allows, 0 = never (whole-row repair kernels)
-    bool cand_fuse = true;             // (measurement) MCA_HIP_CAND_FUSE=0: k_srp_cand as a launch of its own
-    int cand_grid = 512;               // (measurement) MCA_HIP_CAND_GRID: workgroups of k_srp_cand
     bool lazy_tails = true;            // MCA_HIP_ADAPT_LAZY=0: every adaptive call repairs its own last rows for the state it hands over (round 4)
-    // measurement only (-DMCA_MEASURE)
-    bool gemm_ks2 = false;             // MCA_HIP_GEMM_KS2: two K halves for 16 384 ... 32 767 rows (round 4) instead of four quarters
-    bool no_merge = false, stft_wg = false, bf_ola = false, bf_occ2 = false, no_fused_partial = false, gemm_v1 = false, gemm_v2 = false,
-         v1_nosplit = false, no_n512 = false, no_sub2 = false, no_n2048 = false, no_adapt_other_n = false;   // (no_n2048: MCA_HIP_NO_N2048, the any-length kernels at 2048-sample frames: A/B and parity of both)
-    int spw_fpw = 0, bfw_ft = 0, bfw_abl = 0, bfw_var = 15, repair_ksplit = 0, v2_min_rows = 0, repick_grid = 256, list_grid = 512;
-    bool dyn = false;                  // MCA_HIP_DYN: k_stft_phat_wave takes its runs off a device-side queue (round 5: measured slower, profiles/r05_run_queue_negative.log)
-    int spw_waves = 4;                 // MCA_HIP_SPW_WAVES: 8 = the regular launches of k_stft_phat_wave as one workgroup of eight waves per CU
-    int bfw_skew = -1;                 // MCA_HIP_BFW_SKEW: BeamformWaveArgs::skew (-1: the shipped rule, 0: off)
-    int spw_skew = -1;                 // MCA_HIP_SPW_SKEW: StftPhatArgs::skew (-1: the shipped rule, 0: off)
-    int spw_lds_pad = 0;               // MCA_HIP_SPW_LDS_PAD: KiB of unused LDS added to every k_stft_phat_wave launch (fewer workgroups per CU: occupancy A/B, tools/third_wave.sh)
-    bool spw_xcd = false;              // MCA_HIP_SPW_XCD: StftPhatArgs::xcd_map
-    bool no_balance = false;           // MCA_HIP_NO_BALANCE: StftPhatArgs::no_balance (the cost / the effect of pair_balance.h)
-    bool dyn_flat = false;             // MCA_HIP_DYN_FLAT: every run of the queue has the first runs' length
-    const char *wave_clock = nullptr;  // MCA_HIP_WAVE_CLOCK=<file>: entry / exit clocks of every wave of the last k_stft_phat_wave launch, written at destruction
-    int dyn_len0 = 0;                  // MCA_HIP_DYN_LEN0: length of the first (longest) runs of the queue (0: half a wave's share, at most 16)
 };
+
+// Fixed launch shapes of the adaptive repair pass, whose kernels walk device-side work lists
+constexpr int REPAIR_ITEMS = 768;     // work items above which the repair contraction halves its K split (repair_ksplit_eff)
+constexpr int LIST_GRID = 512;        // workgroups of the list-mode analysis
+constexpr int CAND_GRID = 512;        // workgroups of k_srp_cand
+constexpr int REPICK_GRID = 256;      // workgroups of k_scan_repick
 
 // Per-call workspace (everything a stream call allocates besides the per-array state, which lives in the context).  A call
 // can be worked off in pieces over a sub-range of its arrays -- the chunks of the host-pointer path -- with the per-array
@@ -124,7 +109,6 @@ struct mca_hip_ctx {
     bool n512 = false;             // 512-sample frames with <= 8 microphones: k_stft_phat_512 / k_beamform_512 instead of the any-length kernels
     bool n2048 = false;            // 2048-sample frames on the wave-level 1024-point transform (kernels_2048.hip): the beamformer for any M, the analysis for M <= 8 and > 2
     std::string stream_why;       // why the stream API is unavailable for this configuration
-    int v2_min_rows = 16384;       // one operand plane; twice that with two (plan_gemm)
     float step = 0.f;
     std::vector<float> delays, grid;
     std::vector<int2> pairs;
@@ -169,7 +153,6 @@ struct mca_hip_ctx {
     // adaptive SRP precision: fp16 coarse scan (one plane) + exact repair (hi + lo planes)
     int tab_planes = 1;            // planes of the steering tables (2: FP16X3 and ADAPTIVE)
     unsigned long long *d_rstats = nullptr;
-    unsigned long long *d_wave_clock = nullptr; int wave_clock_n = 0;   // (measurement) StftPhatArgs::wave_clock of the last regular launch
     // lazy tails (mca_internal.h, HIST_FRAMES): what the last lazy adaptive call left for the next one, double buffered like d_E
     float *d_hist_pcm[2] = {nullptr, nullptr};     // [max_arrays][M][HIST_SAMPLES]
     float *d_hist_C[2] = {nullptr, nullptr};       // [max_arrays][HIST_FRAMES][Dp] coarse rows (patched where a repair pass recomputed them)
@@ -179,7 +162,6 @@ struct mca_hip_ctx {
     bool lazy_now = false;                         // (localise_impl) this call leaves its tails to the next: the coarse analysis keeps the PCM
     bool host_call = false;                        // inside a host-pointer entry point: its calls keep the eager form (the pageable and the page-locked path return the same bits)
     bool lazy_entry = false;                       // this API call may leave its tails to the next (device-pointer stream calls outside captures)
-    unsigned *d_queue = nullptr;   // [16] run-queue words of the wave-per-run kernels (StftPhatArgs::queue), zero between launches
     int n_cu = 256;
     unsigned long long adapt_frames_total = 0;
     float tau_en = 0.f;            // normalised energies closer than this cannot be ordered from the coarse map
@@ -255,20 +237,11 @@ double distance(const std::vector<double> &xyz, int i, int j)                   
 void free_ctx(mca_hip_ctx *c)
 {
     if (!c) return;
-    if (c->d_wave_clock && c->kn.wave_clock) {                      // (measurement builds only)
-        std::vector<unsigned long long> h(3 * (size_t)c->wave_clock_n);
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h.data(), c->d_wave_clock, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE *f = std::fopen(c->kn.wave_clock, "w")) {
-                for (int i = 0; i < c->wave_clock_n; ++i) std::fprintf(f, "%d %llu %llu %llu\n", i, h[3 * i], h[3 * i + 1], h[3 * i + 2]);
-                std::fclose(f);
-            }
-        (void)hipFree(c->d_wave_clock);
-    }
     auto F = [](void *p) { if (p) (void)hipFree(p); };
     F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
     F(c->d_E[0]); F(c->d_E[1]); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_doa[0]); F(c->d_doa[1]); F(c->d_vdone[0]); F(c->d_vdone[1]); F(c->d_g2_vidx); F(c->d_g2_nv); F(c->d_g2_rad); F(c->d_g2_prob);
     F(c->d_g2_reset); F(c->d_g2_post0); F(c->d_silence);
-    F(c->d_rstats); F(c->d_gate_state); F(c->d_queue);
+    F(c->d_rstats); F(c->d_gate_state);
     for (int i = 0; i < 2; ++i) { F(c->d_hist_pcm[i]); F(c->d_hist_C[i]); F(c->d_ehist[i]); }
     if (c->h_probe) (void)hipHostFree(c->h_probe);
     for (Workspace &w : c->lanes) w.release();
@@ -301,43 +274,8 @@ Knobs read_knobs(const mca_hip_config &cfg)
     k.force_generic = env_str("MCA_HIP_FORCE_GENERIC") != nullptr;
     k.scan_carry = cfg.scan_carry != 0 || env_str("MCA_HIP_SCAN_CARRY") != nullptr;
     if (const char *v = env_str("MCA_HIP_ADAPT_LAZY")) k.lazy_tails = std::atoi(v) != 0;
-    // measurement only: constants unless the library was built with -DMCA_MEASURE
-    k.no_merge = measure_env("MCA_HIP_NO_MERGE") != nullptr;
-    k.repair_items = (int)geti(measure_env("MCA_HIP_REPAIR_ITEMS"), 768);
     if (const char *v = env_str("MCA_HIP_ADAPT_CAND")) k.cand = std::atoi(v) != 0 ? 1 : 0;
-    k.cand_grid = (int)geti(measure_env("MCA_HIP_CAND_GRID"), 512);
-    k.cand_fuse = geti(measure_env("MCA_HIP_CAND_FUSE"), 1) != 0;
-    k.stft_wg = measure_env("MCA_HIP_STFT_WG") != nullptr;
-    k.bf_ola = measure_env("MCA_HIP_BF_OLA") != nullptr;
-    k.bf_occ2 = measure_env("MCA_HIP_BF_OCC2") != nullptr;
-    k.no_fused_partial = measure_env("MCA_HIP_NO_FUSED_PARTIAL") != nullptr;
-    k.gemm_v1 = measure_env("MCA_HIP_GEMM_V1") != nullptr;
-    k.gemm_v2 = measure_env("MCA_HIP_GEMM_V2") != nullptr;
-    k.gemm_ks2 = measure_env("MCA_HIP_GEMM_KS2") != nullptr;
-    k.v1_nosplit = measure_env("MCA_HIP_V1_NOSPLIT") != nullptr;
-    k.no_n512 = measure_env("MCA_HIP_NO_N512") != nullptr;
     k.no_n2048 = env_str("MCA_HIP_NO_N2048") != nullptr;
-    k.no_sub2 = measure_env("MCA_HIP_NO_SUB2") != nullptr;
-    k.no_adapt_other_n = measure_env("MCA_HIP_NO_ADAPT_OTHER_N") != nullptr;     // (A/B: 512- and 2048-sample frames as round 6 began, ADAPTIVE = FP16X3 there)
-    k.spw_fpw = (int)geti(measure_env("MCA_HIP_SPW_FPW"), 0);
-    k.bfw_ft = (int)geti(measure_env("MCA_HIP_BFW_FT"), 0);
-    k.bfw_abl = (int)geti(measure_env("MCA_HIP_BFW_ABL"), 0);
-    k.bfw_var = (int)geti(measure_env("MCA_HIP_BFW_VAR"), 15);
-    k.repair_ksplit = (int)geti(measure_env("MCA_HIP_REPAIR_KSPLIT"), 0);
-    k.v2_min_rows = (int)geti(measure_env("MCA_HIP_V2_MIN_ROWS"), 0);
-    k.repick_grid = (int)geti(measure_env("MCA_HIP_REPICK_GRID"), 256);
-    k.list_grid = (int)geti(measure_env("MCA_HIP_LIST_GRID"), 512);
-    k.dyn = measure_env("MCA_HIP_DYN") != nullptr;
-    k.dyn_len0 = (int)geti(measure_env("MCA_HIP_DYN_LEN0"), 0);
-    k.dyn_flat = measure_env("MCA_HIP_DYN_FLAT") != nullptr;
-    k.spw_xcd = measure_env("MCA_HIP_SPW_XCD") != nullptr;
-    k.no_balance = measure_env("MCA_HIP_NO_BALANCE") != nullptr;
-    k.spw_lds_pad = (int)geti(measure_env("MCA_HIP_SPW_LDS_PAD"), 0);
-    k.lazy_ks_shape = measure_env("MCA_HIP_LAZY_KS_SHAPE") != nullptr;
-    k.spw_skew = (int)geti(measure_env("MCA_HIP_SPW_SKEW"), -1);
-    k.bfw_skew = (int)geti(measure_env("MCA_HIP_BFW_SKEW"), -1);
-    k.spw_waves = (int)geti(measure_env("MCA_HIP_SPW_WAVES"), 4);
-    k.wave_clock = measure_env("MCA_HIP_WAVE_CLOCK");
     return k;
 }
 
@@ -420,7 +358,7 @@ int build_merged_tables(mca_hip_ctx *c)
 {
     c->merged = false;
     // (round 6: also at 2048-sample frames, k_stft_phat_2048<..., MERGE>)
-    if (!c->ula || (c->generic && !c->n2048) || c->n512 || (c->M != 4 && c->M != 8) || c->Dp % 64 != 0 || c->kn.no_merge || c->kn.stft_wg) return MCA_HIP_OK;
+    if (!c->ula || (c->generic && !c->n2048) || c->n512 || (c->M != 4 && c->M != 8) || c->Dp % 64 != 0) return MCA_HIP_OK;
     if (c->prec != MCA_HIP_SRP_ADAPTIVE && c->prec != MCA_HIP_SRP_FP16) return MCA_HIP_OK;
     const int K = c->K, D = c->D, Dp = c->Dp, G = c->G;
     const double N = 2.0 * (K - 1);
@@ -502,13 +440,13 @@ GemmPlan plan_gemm(const mca_hip_ctx *c, long long rows)
     // (round 6: a contraction twice as deep -- 2048-sample frames, 16 microphones: 14 350 / 15 390 elements per plane -- gives a 256 x 384
     // workgroup of a K QUARTER the work a K half has at 7 182: two planes take the big tiles from 16 384 rows there, profiles/r06_n2048.log)
     const long long deep = cur_kp(c) >= 12288 ? 2 : 1;
-    g.v2 = c->prec != MCA_HIP_SRP_FP32 && c->Dp == 384 && rows * (c->a_planes == 2 ? deep : 1) >= (long long)c->v2_min_rows * (c->a_planes == 2 ? 2 : 1) && !c->kn.gemm_v1;
+    g.v2 = c->prec != MCA_HIP_SRP_FP32 && c->Dp == 384 && rows * (c->a_planes == 2 ? deep : 1) >= 16384LL * (c->a_planes == 2 ? 2 : 1);
     if (g.v2) {
         // 256 x 384 tiles need >= ~256 workgroups to fill the chip: one K range from 65 536 rows, two halves from 32 768, and below that four
         // quarters where the contraction is deep (round 5: 16 microphones, 15 392 terms per row -- 16 384 rows were 128 workgroups on half
         // the CUs: 0.280 -> 0.183 ms + 0.021 for k_sum_planes, which folds the four partial maps before the scan; with the 3 968 merged terms
         // of 8 microphones the fold costs what the quarters save: 75 -> 54 + 22 us, profiles/r05_gemm_ksplit4.log)
-        g.ksplit = rows >= 65536 ? 1 : (rows >= 32768 || c->kn.gemm_ks2 || cur_kp(c) < 6144 ? 2 : 4);      // (6144: the merged rows of 2048-sample frames, 7 936 deep, take quarters)
+        g.ksplit = rows >= 65536 ? 1 : (rows >= 32768 || cur_kp(c) < 6144 ? 2 : 4);      // (6144: the merged rows of 2048-sample frames, 7 936 deep, take quarters)
     } else {
         // 128 x 192 tiles: small batches (a single stream) would leave most CUs idle and walk the whole K range
         // in a handful of workgroups (0.29 ms however few frames); split K until ~512 workgroups exist, keeping
@@ -519,7 +457,7 @@ GemmPlan plan_gemm(const mca_hip_ctx *c, long long rows)
         if (ks > nk / 8) ks = nk / 8;
         if (ks > 16) ks = 16;
         if (ks < 1) ks = 1;
-        g.ksplit = c->kn.v1_nosplit ? 1 : (int)ks;
+        g.ksplit = (int)ks;
     }
     return g;
 }
@@ -614,7 +552,7 @@ bool adaptive_shape(const mca_hip_ctx *c, int n_arrays, int n_frames)
     // (more than one source: the S-th pick is a weak peak more often than not -- a second source, or noise when fewer than S
     // are active -- and a third to all of the frames are flagged: 8 x 4096 frames with S = 2 / 3 / 4 real sources spend 0.89 / 1.60 /
     // 1.76 ms in the repair pass, more than the 0.3 ms the coarse contraction saves; MCA_HIP_ADAPT_MAX_SOURCES lifts the limit)
-    return c->prec == MCA_HIP_SRP_ADAPTIVE && ((!c->generic && !c->n512 && c->N == FFT_N) || ((c->n2048 || c->n512) && c->M <= 8 && !c->kn.no_adapt_other_n)) && c->M > 2 && c->S <= c->kn.adapt_max_sources &&
+    return c->prec == MCA_HIP_SRP_ADAPTIVE && ((!c->generic && !c->n512 && c->N == FFT_N) || ((c->n2048 || c->n512) && c->M <= 8)) && c->M > 2 && c->S <= c->kn.adapt_max_sources &&
            rows >= c->kn.adapt_min_rows && n_frames >= 2 * SCAN_CHUNK;
 }
 bool adaptive_applies(const mca_hip_ctx *c, int n_arrays, int n_frames) { return adaptive_shape(c, n_arrays, n_frames) && !c->adapt_suspended; }
@@ -623,7 +561,7 @@ bool adaptive_applies(const mca_hip_ctx *c, int n_arrays, int n_frames) { return
 bool lazy_context(const mca_hip_ctx *c)
 {
     return c->prec == MCA_HIP_SRP_ADAPTIVE && c->kn.lazy_tails && !c->cfg.use_power_floor && (c->M == 8 || c->M == 4) && !c->generic && !c->n512 &&
-           !c->kn.stft_wg && c->cfg.gcc_weighting == MCA_HIP_GCC_PHAT && c->stream_ok;
+           c->cfg.gcc_weighting == MCA_HIP_GCC_PHAT && c->stream_ok;
 }
 
 // Candidate columns (k_srp_cand) for this call?  Lazy calls (no frame is repeated for the state's sake) of contexts whose coarse analysis
@@ -719,10 +657,9 @@ void adapt_policy_begin(mca_hip_ctx *c, int n_arrays, int n_frames)
 // 128 arrays leave thousands, where 32 partial maps per row cost more (k_repair_patch reads them all) than they buy.
 int repair_ksplit_for(const mca_hip_ctx *c, int n_arrays)
 {
-    if (c->kn.repair_ksplit > 0) return std::min(c->kn.repair_ksplit, REPAIR_KSPLIT_MAX);
     // lazy tails: no array lists its last rows as a matter of course -- the list is as long as the content makes it, and the device-side
     // rule (repair_ksplit_eff) halves the segments when it is long
-    if (lazy_context(c) && !c->kn.lazy_ks_shape) return REPAIR_KSPLIT_MAX;
+    if (lazy_context(c)) return REPAIR_KSPLIT_MAX;
     const long long arrays = c->plan_arrays > 0 ? c->plan_arrays : n_arrays;
     const long long tail_rows = arrays * (REPAIR_WARM + 1 + REPAIR_GROUP);
     return tail_rows <= 1024 ? 32 : (tail_rows <= 2560 ? 16 : 8);
@@ -827,7 +764,7 @@ static float exact_reciprocal(float d)
 // the coarse (one fp16 plane) analysis of a 16-microphone uniform linear array runs on k_stft_phat_wave16
 static bool wave16_applies(const mca_hip_ctx *c)
 {
-    return c->M == 16 && c->ula && !c->generic && c->cfg.gcc_weighting != MCA_HIP_GCC_NONE && !c->kn.stft_wg;
+    return c->M == 16 && c->ula && !c->generic && c->cfg.gcc_weighting != MCA_HIP_GCC_NONE;
 }
 
 // 512-sample frames, up to 8 microphones: two frames of up to 8 channels per pass on the wave-level transform (k_stft_phat_512).
@@ -907,13 +844,12 @@ int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, h
     if constexpr (sizeof(OutT) == 2) {
         if (wave16_applies(c) && a.a_planes == 1 && !a.list) {
             StftPhatArgs w = a;
-            w.no_balance = c->kn.no_balance ? 1 : 0;
             w.fpb = 16;
             while (w.fpb > 1 && (long long)grid.y * ((a.n_frames + w.fpb - 1) / w.fpb) < 2048) w.fpb >>= 1;
             dim3 gw(((a.n_frames + w.fpb - 1) / w.fpb + 3) / 4, grid.y);
             // (one resident round of two workgroups per CU: the older workgroup's waves take more frames, StftPhatArgs::skew)
-            if (c->kn.spw_skew != 0 && (gw.x & 1) == 0 && (long long)gw.x * gw.y == 2LL * c->n_cu && (long long)gw.x * 4 * w.fpb == a.n_frames) {
-                const int sk = c->kn.spw_skew > 0 ? c->kn.spw_skew : (3 * w.fpb + 8) / 16;
+            if ((gw.x & 1) == 0 && (long long)gw.x * gw.y == 2LL * c->n_cu && (long long)gw.x * 4 * w.fpb == a.n_frames) {
+                const int sk = (3 * w.fpb + 8) / 16;
                 if (sk > 0 && sk < w.fpb) { w.skew = sk; gw = dim3(gw.y, gw.x); }
             }
             const int fpa = w.fpb + w.skew;
@@ -930,71 +866,36 @@ int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, h
         }
     }
     // 4 or 8 microphones: one wave per run of frames on the 1024-point transform of channel pairs (k_stft_phat_wave)
-    if ((M == 8 || M == 4) && (a.no_phat || !c->kn.stft_wg)) {
+    if (M == 8 || M == 4) {
         StftPhatArgs w = a;
-        w.no_balance = c->kn.no_balance ? 1 : 0;
         dim3 gw;
         if (a.list) { w.fpb = 1; gw = dim3(grid.x, 1); }      // a listed group of REPAIR_GROUP = 4 frames per workgroup, a frame per wave
         else {
-            const int env = c->kn.spw_fpw;
-            w.fpb = env > 0 ? env : 16;       // frames per wave: two waves per SIMD want 2048 runs
-            while (!env && w.fpb > 1 && (long long)grid.y * ((a.n_frames + w.fpb - 1) / w.fpb) < 2048) w.fpb >>= 1;
+            w.fpb = 16;       // frames per wave: two waves per SIMD want 2048 runs
+            while (w.fpb > 1 && (long long)grid.y * ((a.n_frames + w.fpb - 1) / w.fpb) < 2048) w.fpb >>= 1;
             gw = dim3(((a.n_frames + w.fpb - 1) / w.fpb + 3) / 4, grid.y);
         }
-        // Dynamic runs (round 5, measurement builds only: MCA_HIP_DYN).  With one static run per wave the kernel is exactly one round of
-        // resident waves and the average wave lives 85 % of the kernel (SQ counters), which looked like SIMDs waiting for the slowest wave.
-        // The waves' exit clocks (MCA_HIP_WAVE_CLOCK) say otherwise: the spread is not between waves of equal standing -- the FIRST workgroup
-        // of every CU (arrays 0..3 of the bench shape) is done at 180 us, the SECOND (arrays 4..7) at 244 us, 4 us apart inside a workgroup:
-        // the CU issues oldest-first, the younger workgroup gets what is left and then runs alone at 83 % of the two-wave rate
-        // (HISTORY.md section 8: one workgroup per CU).  Perfect balance is worth 11 of 290 us.  A queue of runs per WAVE (tickets in
-        // arrival order) costs more than that: waves of a workgroup no longer stream neighbouring frames, and the same 16-frame runs take
-        // 357 instead of 287 us; runs of 8 / 4 / 2 / 1 frames 357 / 343 / 375 / 515 us (profiles/r05_run_queue_negative.log).
-        const int wg_per_cu = M == 4 ? 3 : 2;                                        // (by registers: 164 ... 175 / 233 ... 253)
-        const long long share = a.list ? 0 : (long long)grid.y * a.n_frames / ((long long)wg_per_cu * c->n_cu * 4);   // frames per wave
-        if (!a.list && c->kn.dyn && !c->kn.spw_fpw && share >= 8 && a.n_frames >= 64) {
-            int len0 = c->kn.dyn_len0 > 0 ? c->kn.dyn_len0 : 16;
-            while (!c->kn.dyn_len0 && len0 > 1 && len0 > share / 2) len0 >>= 1;
-            w.queue = c->d_queue;
-            w.q_sh0 = 0;
-            while ((1 << (w.q_sh0 + 1)) <= len0) ++w.q_sh0;
-            w.q_arrays = (int)grid.y;
-            int t0, t1, t2, t3, t4;
-            w.q_flat = c->kn.dyn_flat ? 1 : 0;
-            w.q_total = dyn_run(0x7fffffff, a.n_frames, w.q_arrays, w.q_sh0, t0, t1, t2, t3, t4, w.q_flat);
-            w.fpb = 1 << w.q_sh0;                                                          // (sizes the Nyquist slots of the unmerged kernels)
-            gw = dim3(wg_per_cu * c->n_cu, 1);
-        }
-        w.xcd_map = c->kn.spw_xcd ? 1 : 0;
         // One resident round of two workgroups per CU (the bench shapes: 8 x 4096 and 128 x 256 frames of 8 microphones): the CU issues
-        // oldest-first, so the workgroup it got first finishes early and the other then runs alone at 83 % of the two-wave rate.  The first
-        // half of every array's run groups -- dispatched first -- takes more frames per wave (StftPhatArgs::skew).
-        if (!a.list && !w.queue && c->kn.spw_skew != 0 && M == 8 && (gw.x & 1) == 0 && (long long)gw.x * gw.y == 2LL * c->n_cu &&
-            (long long)gw.x * 4 * w.fpb == a.n_frames) {
-            const int sk = c->kn.spw_skew > 0 ? c->kn.spw_skew : (3 * w.fpb + 8) / 16;      // 16 frames per wave: 19 / 13 (measured 1 ... 4: 3 is best)
+        // oldest-first, so the FIRST workgroup of every CU is done early (180 against 244 us on the bench shape, profiles/
+        // r05_run_queue_negative.log) and the other then runs alone at 83 % of the two-wave rate.  The first half of every array's run
+        // groups -- dispatched first -- takes more frames per wave (StftPhatArgs::skew).  (A device-side run queue, an XCD-aware mapping
+        // and one 8-wave workgroup per CU were measured slower, HISTORY.md section 10.)
+        if (!a.list && M == 8 && (gw.x & 1) == 0 && (long long)gw.x * gw.y == 2LL * c->n_cu && (long long)gw.x * 4 * w.fpb == a.n_frames) {
+            const int sk = (3 * w.fpb + 8) / 16;      // 16 frames per wave: 19 / 13 (measured 1 ... 4: 3 is best)
             if (sk > 0 && sk < w.fpb) {
                 w.skew = sk;
                 gw = dim3(gw.y, gw.x);             // (arrays, run groups): the first half of the run groups of EVERY array is dispatched first
             }
         }
-        // (measurement) MCA_HIP_SPW_WAVES=8: the same runs as ONE workgroup of eight waves per CU -- waves of one age, no skew needed
-        int nwv = 4;
-        if (!a.list && !w.queue && c->kn.spw_waves == 8 && (gw.x & 1) == 0 && !w.skew) { nwv = 8; gw = dim3(gw.x / 2, gw.y); }
-        else if (!a.list && !w.queue && c->kn.spw_waves == 8 && w.skew) { w.skew = 0; gw = dim3(gw.y / 2, gw.x); nwv = 8; }   // (the skew rule had swapped the grid)
-        if (c->kn.wave_clock && !a.list) {
-            if (!c->d_wave_clock) HIP_TRY(c, hipMalloc((void **)&c->d_wave_clock, 3 * 8 * 16384));
-            HIP_TRY(c, hipMemsetAsync(c->d_wave_clock, 0, 3 * 8 * 16384, st));
-            c->wave_clock_n = std::min<int>(16384, (int)(gw.x * gw.y * 4));
-            if ((int)(gw.x * gw.y * 4) <= 16384) w.wave_clock = c->d_wave_clock;
-        }
         const bool mg = w.mrank != nullptr && !a.list;
         const int nrank = 2 * (M - 1) * 64 * 4 + 8, regw = mg ? std::max(F1K_SCRATCH, (w.n_merged + 63) & ~63) : F1K_SCRATCH;
         // (the merged kernel keeps its Nyquist bins in registers: with its 15.5 KiB regions two workgroups just fit the 160 KiB of a CU)
-        const size_t smw = (size_t)(F1K_TWORDS + (mg ? nrank / 4 : 0) + nwv * regw + (mg ? 0 : nwv * (w.fpb + w.skew) * (M / 2))) * sizeof(float2) + (size_t)c->kn.spw_lds_pad * 1024;
+        const size_t smw = (size_t)(F1K_TWORDS + (mg ? nrank / 4 : 0) + 4 * regw + (mg ? 0 : 4 * (w.fpb + w.skew) * (M / 2))) * sizeof(float2);
         const bool pl2 = a.a_planes == 2, pw = a.power != nullptr;
 #define LAUNCH_K(K)                                                                                                 \
         do {                                                                                                         \
             if (smw > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw)); \
-            hipLaunchKernelGGL(K, gw, dim3(64 * nwv), smw, st, w);                                                   \
+            hipLaunchKernelGGL(K, gw, dim3(256), smw, st, w);                                                        \
         } while (0)
 #define LAUNCH_W2(MT, U, PL2, NP)                                                                                  \
         do {                                                                                                         \
@@ -1041,12 +942,8 @@ int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, h
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smf));           \
         hipLaunchKernelGGL((k_stft_phat_few<MT, U, OutT>), grid, dim3(512), smf, st, a);                     \
     } while (0)
-    // (measured: 0.51 -> 0.33 ms for 131 072 two-channel frames; no gain with 4 channels, which stay on k_stft_phat)
+    // (measured: 0.51 -> 0.33 ms for 131 072 two-channel frames)
     if (M == 2 && !ula) LAUNCH_FEW(2, false);
-    else if (M == 4 && ula) LAUNCH(4, true);
-    else if (M == 4) LAUNCH(4, false);
-    else if (M == 8 && ula) LAUNCH(8, true);
-    else if (M == 8) LAUNCH(8, false);
     else if (M == 16 && ula) LAUNCH(16, true);
     else if (ula) LAUNCH(0, true);
     else LAUNCH(0, false);
@@ -1151,9 +1048,8 @@ int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
         c->stream_ok = false;
         c->stream_why = "gcc_weighting NONE: the stream API serves it at fft_size 1024 with 4 or 8 microphones (the frame API takes any shape)";
     }
-    c->n512 = c->N == 512 && c->M <= 8 && c->stream_ok && !c->kn.no_n512;
+    c->n512 = c->N == 512 && c->M <= 8 && c->stream_ok;
     c->n2048 = c->N == 2048 && c->stream_ok && !c->kn.no_n2048;
-    if (c->kn.v2_min_rows > 0) c->v2_min_rows = c->kn.v2_min_rows;
 
     // generateLookupTable (SteeringBeamforming.cpp:58-94): pairs i<j lexicographic, float delays
     c->delays.resize((size_t)c->P * c->D);
@@ -1230,7 +1126,7 @@ int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
         (rc = zalloc((void **)&c->d_doa[0], na * 4)) || (rc = zalloc((void **)&c->d_doa[1], na * 4)) ||
         (rc = zalloc((void **)&c->d_vdone[0], na * 8)) || (rc = zalloc((void **)&c->d_vdone[1], na * 8)) ||
         (rc = zalloc((void **)&c->d_silence, na * 4)) || (rc = zalloc((void **)&c->d_g2_post0, na * 4)) ||
-        (rc = zalloc((void **)&c->d_rstats, 32)) || (rc = zalloc((void **)&c->d_queue, 64)) ||
+        (rc = zalloc((void **)&c->d_rstats, 32)) ||
         (rc = zalloc((void **)&c->d_E64[0], c->D * 8)) || (rc = zalloc((void **)&c->d_E64[1], c->D * 8)) ||
         (rc = zalloc((void **)&c->d_res, (2 * MCA_MAX_SOURCES + 1) * 8)) || (rc = zalloc((void **)&c->d_bins, MCA_MAX_SOURCES * 4)) ||
         (rc = zalloc((void **)&c->d_g2f_corr[0], c->D * 8)) || (rc = zalloc((void **)&c->d_g2f_corr[1], c->D * 8)) ||
@@ -1458,7 +1354,7 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
     // The 256 x 384 contraction leaves the chunk-local results of the scan over frames (k_scan_partial's job) when every
     // 32-row block of every launch is one scan chunk of one map: no gate, one map, whole chunks, that kernel for every slice.
     bool fused_partial = SCAN_CHUNK == 32 && c->a_planes == 1 && !c->cfg.use_power_floor && n_frames % SCAN_CHUNK == 0 && fc % SCAN_CHUNK == 0 &&
-                         plan_gemm(c, (long long)n_arrays * fc).ksplit <= 2 && !c->kn.no_fused_partial;
+                         plan_gemm(c, (long long)n_arrays * fc).ksplit <= 2;
     for (int f0 = 0; fused_partial && f0 < n_frames; f0 += (int)fc)
         fused_partial = plan_gemm(c, (long long)n_arrays * std::min<long long>(fc, n_frames - f0)).v2;
     c->ws().partial_done = fused_partial;
@@ -1484,7 +1380,7 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         time_begin(c, MCA_HIP_K_STFT_PHAT, st);
         if (c->n512) {
             rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft_512<float>(c, sa, dim3(0, n_arrays), st) : launch_stft_512<_Float16>(c, sa, dim3(0, n_arrays), st);
-        } else if ((c->N == 4096 || c->N == 2048) && c->M == 2 && c->stream_ok && !c->kn.no_sub2) {
+        } else if ((c->N == 4096 || c->N == 2048) && c->M == 2 && c->stream_ok) {
             // two microphones at 2048- / 4096-sample frames (FreqGCC at 32 / 44.1 / 48 kHz): 512-sample sub-sequences per channel
             sa.fpb = 8;
             while (sa.fpb > 2 && (long long)n_arrays * ((nf + sa.fpb - 1) / sa.fpb) < 512) sa.fpb >>= 1;
@@ -1548,10 +1444,8 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
                 HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
                 hipLaunchKernelGGL(K, gv, dim3(512), smem, st, ga);                                                       \
             } while (0)
-            const bool use_v3 = !c->kn.gemm_v2;       // (A/B switch: the 32x32x16 one-plane kernel)
-            if (c->a_planes == 2) V2_LAUNCH((k_srp_gemm_f16_v2<true>));
-            else if (use_v3) V2_LAUNCH(k_srp_gemm_f16_v3);
-            else V2_LAUNCH((k_srp_gemm_f16_v2<false>));
+            if (c->a_planes == 2) V2_LAUNCH(k_srp_gemm_f16_v2);
+            else V2_LAUNCH(k_srp_gemm_f16_v3);
 #undef V2_LAUNCH
         } else {
             dim3 g2((ga.rows + 127) / 128, c->Dp == 64 ? 1 : c->Dp / 192, ksplit);
@@ -1591,7 +1485,7 @@ static void launch_repair_contraction(mca_hip_ctx *c, Workspace &w, long long li
     ga.rows = (int)pass_rows; ga.chunk_frames = (int)pass_rows; ga.total_frames = (int)pass_rows; ga.frame0 = 0;
     ga.Kp = c->Kp; ga.Dp = c->Dp; ga.a_row_elems = c->a_row_elems; ga.c_plane_elems = pass_rows * c->Dp;
     ga.n_list = n_list; ga.list0 = (int)list0;
-    ga.repair_ksplit = repair_ksplit_for(c, ksplit_arrays); ga.repair_items = c->kn.repair_items;
+    ga.repair_ksplit = repair_ksplit_for(c, ksplit_arrays); ga.repair_items = REPAIR_ITEMS;
     const int col_tiles = c->Dp == 64 ? 1 : c->Dp / 192;
     const long long max_work = (pass_rows + 127) / 128 * col_tiles * ga.repair_ksplit;
     dim3 gg((unsigned)std::min<long long>(max_work, 768));
@@ -1772,15 +1666,15 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
                 ca.umask = c->ws().d_umask; ca.umask_words = pa.umask_words; ca.need = c->ws().d_need; ca.groups_per_array = gpa; ca.n_frames = n_frames;
                 ca.C = c->ws().d_C; ca.c_planes = c->ws().c_planes; ca.c_plane_stride = c->ws().c_plane;
                 if (hist_valid) { ca.hist_C = c->d_hist_C[c->hist_cur]; ca.hist_base = n_arrays * gpa; }
-                if (c->kn.cand_fuse && (c->M == 8 || c->M == 4) && !c->kn.stft_wg) { sa.cand_on = 1; sa.cand = ca; }
+                if (c->M == 8 || c->M == 4) { sa.cand_on = 1; sa.cand = ca; }
             }
             const size_t smem1 = ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
             // fixed, moderate grids: the kernels of the repair pass walk their device-side work lists
-            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, std::max(1, c->kn.list_grid)), 1), smem1, st))) { set_call_planes(c, 1); return rc; }
+            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, LIST_GRID), 1), smem1, st))) { set_call_planes(c, 1); return rc; }
             if (pa.umask && sa.cand_on) continue;
             if (pa.umask) {
                 const long long max_items = pass_rows / REPAIR_GROUP;
-                hipLaunchKernelGGL(k_srp_cand, dim3((unsigned)std::min<long long>(max_items, std::max(1, c->kn.cand_grid))), dim3(1024), 0, st, ca);
+                hipLaunchKernelGGL(k_srp_cand, dim3((unsigned)std::min<long long>(max_items, CAND_GRID)), dim3(1024), 0, st, ca);
                 continue;
             }
             RepairPatchArgs pp{};
@@ -1798,7 +1692,7 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
             sa.list = pa.list_full; sa.n_list = pa.n_list_full; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = gpa;
             const size_t smem1 = ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
-            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, std::max(1, c->kn.list_grid)), 1), smem1, st))) { set_call_planes(c, 1); return rc; }
+            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, LIST_GRID), 1), smem1, st))) { set_call_planes(c, 1); return rc; }
             RepairPatchArgs pp{};
             pp.groups_per_array = gpa;
             pp.C = c->ws().d_C; pp.c_planes = c->ws().c_planes; pp.c_plane_stride = c->ws().c_plane; pp.n_frames = n_frames;
@@ -1806,12 +1700,11 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         }
         set_call_planes(c, 1);
         const size_t smem4 = (size_t)32 * (c->Dp + 8) * sizeof(float);
-        const int repick_grid = std::max(1, c->kn.repick_grid);
 #define LAUNCH_REPICK(PL)                                                                                                           \
         do {                                                                                                                        \
             if (smem4 > 64 * 1024)      /* grids finer than 0.45 degrees: Dp >= 512 */                                              \
                 HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scan_repick<PL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)); \
-            hipLaunchKernelGGL((k_scan_repick<PL>), dim3((unsigned)std::min<long long>((long long)pa.n_chunks * n_arrays, repick_grid)), dim3(std::max(nthr, 512)), smem4, st, pa); \
+            hipLaunchKernelGGL((k_scan_repick<PL>), dim3((unsigned)std::min<long long>((long long)pa.n_chunks * n_arrays, REPICK_GRID)), dim3(std::max(nthr, 512)), smem4, st, pa); \
         } while (0)
         if (ppl == 2) LAUNCH_REPICK(2); else if (ppl == 6) LAUNCH_REPICK(6); else LAUNCH_REPICK(8);
 #undef LAUNCH_REPICK
@@ -1858,7 +1751,7 @@ static bool wave_beamformer_applies(const mca_hip_ctx *c)
 {
     // several sources: up to 8 microphones k_beamform_wave_ms (forward transforms shared, the pair spectra in registers); more
     // microphones with two sources a grid row of k_beamform_wave per source, with three or four k_beamform_ola
-    return !c->kn.bf_ola && !c->generic && !c->n512 && (c->S <= 2 || c->M <= 8) && c->M >= 2 && c->M <= MCA_MAX_MICS;
+    return !c->generic && !c->n512 && (c->S <= 2 || c->M <= 8) && c->M >= 2 && c->M <= MCA_MAX_MICS;
 }
 
 // steering rows of every grid angle (+ the initial DOA): allocated and built once, outside any capture
@@ -1913,15 +1806,11 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         BeamformWaveArgs wa{};
         wa.pcm = pcm; wa.array_stride = array_stride; wa.mic_stride = mic_stride;
         wa.M = c->M; wa.n_pairs = c->bf_pairs; wa.n_frames = n_frames; wa.S = c->S;
-        // frames per run (one wave each; every run re-analyses one extra frame for its overlap-add carry): long runs are
-        // cheaper per frame, short ones fill the chip -- two waves per SIMD want 2048 runs
-        const int ft_env = c->kn.bfw_ft;
-        wa.ft = ft_env > 0 ? ft_env : 16;
-        while (!ft_env && wa.ft > 2 && (long long)n_arrays * c->S * ((n_frames + wa.ft - 1) / wa.ft) < 2048) wa.ft >>= 1;
         wa.window = c->d_window; wa.doa_bin = doa_bin; wa.table = c->d_bftab; wa.out = out_pcm;
         wa.tail_in = c->d_tail[c->tail_cur] + a0 * c->S * c->H; wa.tail_out = c->d_tail[c->tail_cur ^ 1] + a0 * c->S * c->H;
         if (c->S >= 2 && c->M <= 8) {
-            // the forward transforms of a frame shared by its sources
+            // the forward transforms of a frame shared by its sources.  Frames per run (one wave each; every run re-analyses one extra
+            // frame for its overlap-add carry): long runs are cheaper per frame, short ones fill the chip -- two waves per SIMD want 2048 runs
             wa.ft = 16;
             while (wa.ft > 2 && (long long)n_arrays * ((n_frames + wa.ft - 1) / wa.ft) < 2048) wa.ft >>= 1;
             const int runs = (n_frames + wa.ft - 1) / wa.ft;
@@ -1949,49 +1838,22 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             HIP_TRY(c, hipGetLastError());
             return MCA_HIP_OK;
         }
-        const int abl = c->kn.bfw_abl & 3;     // (-DMCA_MEASURE only: ablations with wrong results)
-        int var = abl ? 14 : (c->kn.bfw_var & 31);
-        // (MEASURE builds, MCA_HIP_BFW_VAR=31) the staged variant needs 16-byte aligned rows: otherwise the shipped one
-        if ((var & 16) && (var != 31 || (mic_stride & 3) || (array_stride & 3) || (reinterpret_cast<uintptr_t>(pcm) & 15))) var = 15;
-        // workgroups per array: 4 runs of ft frames each, or (hand-off of the overlap-add carries inside the workgroup, VAR bit 1)
-        // 4 ft - 1 frames.  With the hand-off ft is the smallest run length whose workgroups are all resident at once (two per
-        // CU: 512) -- one workgroup more than that costs a whole extra round.
-        if ((var & 2) && !ft_env) {
-            wa.ft = 2;
-            while (wa.ft < 256 && (long long)n_arrays * c->S * ((n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1)) > 512) ++wa.ft;
-        }
-        const int wgs = (var & 2) ? (n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1) : ((n_frames + wa.ft - 1) / wa.ft + 3) / 4;
-        const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2) + ((var & 2) ? 4 * FFT_H * sizeof(float) : 0) + ((var & 16) ? 3 * 8192 : 0);
+        // A workgroup covers 4 ft - 1 frames (the overlap-add carries are handed off inside it, k_beamform_wave); ft is the smallest run
+        // length whose workgroups are all resident at once (two per CU: 512) -- one workgroup more than that costs a whole extra round.
+        wa.ft = 2;
+        while (wa.ft < 256 && (long long)n_arrays * c->S * ((n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1)) > 512) ++wa.ft;
+        const int wgs = (n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1);
+        const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2) + 4 * FFT_H * sizeof(float);
         // one resident round of (nearly) two workgroups per CU: the older workgroup of every CU takes longer runs (BeamformWaveArgs::skew)
         dim3 gb(wgs, n_arrays, c->S);
-        if ((var & 2) && !abl && c->kn.bfw_skew != 0 && c->S == 1 && (wgs & 1) == 0 && wa.ft >= 8 &&
-            (long long)wgs * n_arrays > (long long)c->n_cu * 3 / 2 && (long long)wgs * n_arrays <= 2LL * c->n_cu) {
-            wa.skew = c->kn.bfw_skew > 0 ? c->kn.bfw_skew : (3 * wa.ft + 8) / 16;
+        if (c->S == 1 && (wgs & 1) == 0 && wa.ft >= 8 && (long long)wgs * n_arrays > (long long)c->n_cu * 3 / 2 && (long long)wgs * n_arrays <= 2LL * c->n_cu) {
+            wa.skew = (3 * wa.ft + 8) / 16;
             if (wa.skew >= wa.ft) wa.skew = 0;
             else gb = dim3(n_arrays, wgs, c->S);
         }
         time_begin(c, MCA_HIP_K_BEAMFORM, st);
-#define BFW_CASE(V) case V: if (c->M & 1) hipLaunchKernelGGL((k_beamform_wave<true, V, 0>), gb, dim3(256), smem, st, wa); \
-                            else hipLaunchKernelGGL((k_beamform_wave<false, V, 0>), gb, dim3(256), smem, st, wa); break;
-#ifdef MCA_MEASURE
-        if (abl == 1) hipLaunchKernelGGL((k_beamform_wave<false, 14, 1>), dim3(wgs, n_arrays, c->S), dim3(256), smem, st, wa);
-        else if (abl == 2) hipLaunchKernelGGL((k_beamform_wave<false, 14, 2>), dim3(wgs, n_arrays, c->S), dim3(256), smem, st, wa);
-        else if (abl == 3) hipLaunchKernelGGL((k_beamform_wave<false, 14, 3>), dim3(wgs, n_arrays, c->S), dim3(256), smem, st, wa);
-        else
-        switch (var) {
-            BFW_CASE(0) BFW_CASE(1) BFW_CASE(2) BFW_CASE(3) BFW_CASE(4) BFW_CASE(5) BFW_CASE(6) BFW_CASE(7)
-            BFW_CASE(8) BFW_CASE(9) BFW_CASE(10) BFW_CASE(11) BFW_CASE(12) BFW_CASE(13) BFW_CASE(14) BFW_CASE(15)
-            case 31:
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_beamform_wave<false, 31, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_beamform_wave<true, 31, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                if (c->M & 1) hipLaunchKernelGGL((k_beamform_wave<true, 31, 0>), gb, dim3(256), smem, st, wa);
-                else hipLaunchKernelGGL((k_beamform_wave<false, 31, 0>), gb, dim3(256), smem, st, wa);
-                break;
-        }
-#else
-        switch (var) { BFW_CASE(15) }
-#endif
-#undef BFW_CASE
+        if (c->M & 1) hipLaunchKernelGGL(k_beamform_wave<true>, gb, dim3(256), smem, st, wa);
+        else hipLaunchKernelGGL(k_beamform_wave<false>, gb, dim3(256), smem, st, wa);
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
         return MCA_HIP_OK;
@@ -2056,15 +1918,13 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     if (smem > 160 * 1024) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "n_mics/n_sources combination exceeds the 160 KiB LDS of a CU");
     dim3 g((n_frames + ba.ft - 1) / ba.ft, n_arrays);
     time_begin(c, MCA_HIP_K_BEAMFORM, st);
-    const bool occ4 = !c->kn.bf_occ2;
 #define BF_LAUNCH(K)                                                                                                     \
     do {                                                                                                                 \
         if (smem > 64 * 1024)                                                                                            \
             HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         hipLaunchKernelGGL(K, g, dim3(512), smem, st, ba);                                                               \
     } while (0)
-    if (c->M <= 8 && occ4) BF_LAUNCH((k_beamform_ola<1, 4>));
-    else if (c->M <= 8) BF_LAUNCH((k_beamform_ola<1, 2>));
+    if (c->M <= 8) BF_LAUNCH((k_beamform_ola<1, 4>));
     else BF_LAUNCH((k_beamform_ola<2, 2>));
 #undef BF_LAUNCH
     time_end(c, st);

@@ -4,7 +4,6 @@
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
-#include "knobs.h"
 #include "stage.h"
 #include "state_blob.h"
 
@@ -235,8 +234,7 @@ int mca_hip_mask_frames_dev(mca_hip_mask_ctx *c, const float *pcm, long long str
     a.Q_in = c->d_Q[c->q_cur]; a.Q_out = c->d_Q[c->q_cur ^ 1]; a.noise = c->d_noise;
     a.tail_in = c->d_tail[c->tail_cur]; a.tail_out = c->d_tail[c->tail_cur ^ 1];
     a.out = out_pcm; a.decisions = decisions;
-    static const bool no_tuned = mca::measure_env("MCA_HIP_MASK_GENERIC") != nullptr;      // A/B switch for measurements
-    if (c->N == FFT_N && !no_tuned) {
+    if (c->N == FFT_N) {
         // 79 KiB: two workgroups per CU
         const size_t smem = (size_t)MK_NB * 2 * FFT_SCRATCH * sizeof(float2) + (size_t)MK_NB * 3 * 520 * sizeof(float) +
                             TW_WIN * sizeof(float2) + (size_t)MK_NB * 48 * 8 * sizeof(float) + 520 * sizeof(float2) + 528;
@@ -244,7 +242,7 @@ int mca_hip_mask_frames_dev(mca_hip_mask_ctx *c, const float *pcm, long long str
             MHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mask_stream), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         dim3 g((n_frames + a.ft - 1) / a.ft, n_streams);
         hipLaunchKernelGGL(k_mask_stream, g, dim3(512), smem, st, a);
-    } else if (c->N == 2048 && !no_tuned) {
+    } else if (c->N == 2048) {
         // 2048-sample frames (44.1 / 48 kHz): four 512-sample sub-sequences per frame on the wave-level transform
         MaskGenArgs ga{};
         ga.a = a; ga.N = c->N; ga.logH = c->logH; ga.tw = c->d_tw; ga.kw = c->d_kw; ga.kb = c->d_kb;

@@ -4,7 +4,6 @@
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
-#include "knobs.h"
 #include "stage.h"
 #include "state_blob.h"
 
@@ -231,15 +230,14 @@ int mca_hip_mb_frames_dev(mca_hip_mb_ctx *c, const float *pcm, long long array_s
     aa.N = c->N; aa.logH = c->logH; aa.nbins = c->nb; aa.D = c->D;
     aa.window = c->d_window; aa.tw = c->d_tw; aa.coef = c->d_coef; aa.lo = c->d_lo; aa.hi = c->d_hi; aa.T = c->d_T;
     aa.raw = c->d_raw; aa.band_energy = c->d_be; aa.p_full = c->d_pf; aa.p_half = c->d_ph;
-    static const bool no_tuned = mca::measure_env("MCA_HIP_MB_GENERIC") != nullptr;     // A/B switch for measurements
-    if (c->N == FFT_N && !no_tuned) {
+    if (c->N == FFT_N) {
         // 1024-sample frames: wave-level FFT, 4 frames x 2 channels per pass
         int fpb = 16;
         while (fpb > 4 && (long long)n_arrays * ((n_frames + fpb - 1) / fpb) < 512) fpb >>= 1;
         const size_t smem1 = (size_t)8 * FFT_SCRATCH * 8 + (size_t)4 * 520 * (8 + 4) + (size_t)TW_WORDS * 8 + 16 * 4;
         BHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mb_analyse_1024), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
         hipLaunchKernelGGL(k_mb_analyse_1024, dim3((n_frames + fpb - 1) / fpb, n_arrays), dim3(512), smem1, st, aa, fpb);
-    } else if (c->N == 512 && !no_tuned) {
+    } else if (c->N == 512) {
         // 512-sample frames: both channels of a frame in one 512-point complex transform, 8 frames per pass
         int fpb = 32;
         while (fpb > 8 && (long long)n_arrays * ((n_frames + fpb - 1) / fpb) < 512) fpb >>= 1;

@@ -5,7 +5,6 @@
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
-#include "knobs.h"
 #include "stage.h"
 #include "state_blob.h"
 
@@ -218,16 +217,15 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
     aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = doa_rad;
     aa.X = c->d_X; aa.T = c->d_T; aa.mic_x = c->d_micx;
     aa.unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;                      // Beamformer.cpp:59 without 2 pi
-    static const bool no_tuned = mca::measure_env("MCA_HIP_MVDR_GENERIC") != nullptr;     // A/B switch for measurements
     t_begin(c, 0, st);
-    if (c->N == FFT_N && !no_tuned) {
+    if (c->N == FFT_N) {
         // 1024-sample frames: wave-level FFT, one wave per channel, eight channels per pass
         int fpb = 8;
         while (fpb > 1 && (long long)n_streams * ((n_frames + fpb - 1) / fpb) < 1024) fpb >>= 1;
         const size_t smem1 = (size_t)(8 * 580 + TW_WORDS) * sizeof(float2);
         VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_analyse_1024), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
         hipLaunchKernelGGL(k_mvdr_analyse_1024, dim3((n_frames + fpb - 1) / fpb, n_streams), dim3(512), smem1, st, aa, fpb);
-    } else if (c->N == 512 && !no_tuned) {
+    } else if (c->N == 512) {
         // 512-sample frames: two channels per wave pass (kernels_stream.hip)
         int fpb = 8;
         while (fpb > 1 && (long long)n_streams * ((n_frames + fpb - 1) / fpb) < 1024) fpb >>= 1;
@@ -271,14 +269,12 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
     // 512 workgroups are resident (two per CU at 253 VGPRs) and all take the same time: the workgroups behind the last whole
     // round (256 streams x 513 bins: 4 of 2052) would hold the GPU for a round of their own.  They go in a second launch,
     // cut along the FRAMES into pieces that each repeat the (cheap) covariance recursion of the frames before their own.
-    static const int env_pieces = mca::measure_env("MCA_HIP_MVDR_PIECES") ? std::atoi(mca::measure_env("MCA_HIP_MVDR_PIECES")) : -1;   // A/B switch
     const long long n_prob = (long long)n_streams * c->K, n_wg = (n_prob + 63) / 64;
     const long long rem_wg = n_wg % 512;
     int pieces = 1;
     if (n_wg > 512 && rem_wg > 0 && rem_wg <= 128) {
         while (pieces < 8 && rem_wg * pieces * 2 <= 512 && n_frames / (pieces * 2) >= 4) pieces *= 2;
     }
-    if (env_pieces >= 0 && (env_pieces <= 1 || (n_wg > 512 && rem_wg > 0 && rem_wg <= 128))) pieces = env_pieces == 0 ? 1 : std::min(std::max(env_pieces, 1), n_frames);
     t_begin(c, 1, st);
     if (pieces > 1 && n_wg > 512) {
         const long long main_prob = (n_wg - rem_wg) * 64, tail_prob = n_prob - main_prob;       // tail_prob <= 128 x 64: the scratch copy's size

@@ -23,7 +23,7 @@ __global__ void k_beamform_512(BeamformArgs p);
 template <int R, typename OutT> __global__ void k_stft_phat_sub2(StftPhatArgs p);
 __global__ void k_beamform_gen(BeamformArgs p);
 __global__ void k_bf_table(float2 *tab, const float *grid, const double *mic_x, int M, int n_pairs, double unit);
-template <bool ODD, int VAR, int ABL> __global__ void k_beamform_wave(BeamformWaveArgs p);
+template <bool ODD> __global__ void k_beamform_wave(BeamformWaveArgs p);
 template <bool POWER> __global__ void k_stft_phat_wave16(StftPhatArgs p);   // 16-microphone ULA, one fp16 plane
 template <int MT, bool ULA, typename OutT, bool MERGE = false> __global__ void k_stft_phat_2048(StftPhatArgs p);   // 2048-sample frames, M <= 8 (kernels_2048.hip)
 __global__ void k_bf_table_2048(float2 *tab, const float *grid, const double *mic_x, int M, double unit);
@@ -33,7 +33,7 @@ template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bo
 
 __global__ void k_srp_gemm_f32(GemmArgs p);
 template <bool SPLIT, int BN> __global__ void k_srp_gemm_f16(GemmArgs p);
-template <bool SPLIT> __global__ void k_srp_gemm_f16_v2(GemmArgs p);
+__global__ void k_srp_gemm_f16_v2(GemmArgs p);      // hi + lo planes, v_mfma_f32_32x32x16_f16
 __global__ void k_srp_gemm_f16_v3(GemmArgs p);      // one plane, v_mfma_f32_16x16x32_f16
 template <int BN> __global__ void k_srp_gemm_repair(GemmArgs p);
 __global__ void k_srp_cand(CandArgs p);

@@ -289,16 +289,13 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int V3_BK = 32, V3_ROWB = 64;
 
-template <bool SPLIT>
+// This kernel takes the hi + lo operand planes (C += Ahi Bhi + Alo Bhi + Ahi Blo); the one-plane rows run on k_srp_gemm_f16_v3 below.
 __global__ __launch_bounds__(512) void k_srp_gemm_f16_v2(GemmArgs p)
 {
-    constexpr int NP = SPLIT ? 2 : 1;
+    constexpr int NP = 2;
     constexpr int A_BYTES = V2_BM * V3_ROWB, B_BYTES = V2_BN * V3_ROWB;      // per plane: 16 KiB, 24 KiB
-    constexpr int STAGE = NP * (A_BYTES + B_BYTES);                         // 80 KiB (SPLIT)
-    // stages in LDS: two with the hi + lo planes (all 160 KiB); the one-plane kernel has room for four, so that the loads of a
-    // stage are issued three stages (~2 us) ahead of their use instead of one
-    constexpr int NS = SPLIT ? 2 : 4;
-    constexpr int LPS = NP * 5;                                             // load instructions per wave and stage (2 A + 3 B per plane)
+    constexpr int STAGE = NP * (A_BYTES + B_BYTES);                         // 80 KiB
+    constexpr int NS = 2;                                                   // stages in LDS: all 160 KiB
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem_g[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -369,12 +366,8 @@ __global__ __launch_bounds__(512) void k_srp_gemm_f16_v2(GemmArgs p)
     for (int q = 0; q < NS - 1; ++q)
         if (q < ns) { issue_a(q, q); issue_b(q, q); }
     for (int s = 0; s < ns; ++s) {
-        // the loads of stage s have landed when at most those of the stages issued after it are outstanding (loads of one
-        // wave return in order)
-        const int later = min(NS - 2, ns - 1 - s);
-        if (later >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
-        else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the loads of stage s have landed (with two stages no later stage has been issued yet)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (s + NS - 1 < ns) issue_a(s + NS - 1, (s + NS - 1) % NS);      // that buffer was last read in stage s-1
 #define LDS_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
@@ -403,19 +396,13 @@ __global__ __launch_bounds__(512) void k_srp_gemm_f16_v2(GemmArgs p)
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 constexpr int Y1 = NP;                 // younger reads allowed in flight: block j+1
-                if constexpr (SPLIT) {
-                    if (j == 0) asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[1][0]), "+v"(af[1][1]), "+v"(bs[0][0]), "+v"(bs[0][1]) : "n"(Y1));
-                    else if (j < 5) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(bs[j % 2][0]), "+v"(bs[j % 2][1]) : "n"(Y1));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bs[j % 2][0]), "+v"(bs[j % 2][1]));
-                    acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][0], bs[j % 2][0], acc[0][j], 0, 0, 0);
-                    acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][1], bs[j % 2][0], acc[1][j], 0, 0, 0);
-                    acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][0], bs[j % 2][1], acc[0][j], 0, 0, 0);
-                    acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][1], bs[j % 2][1], acc[1][j], 0, 0, 0);
-                } else {
-                    if (j == 0) asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(bs[0][0]) : "n"(Y1));
-                    else if (j < 5) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(bs[j % 2][0]) : "n"(Y1));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bs[j % 2][0]));
-                }
+                if (j == 0) asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[1][0]), "+v"(af[1][1]), "+v"(bs[0][0]), "+v"(bs[0][1]) : "n"(Y1));
+                else if (j < 5) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(bs[j % 2][0]), "+v"(bs[j % 2][1]) : "n"(Y1));
+                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bs[j % 2][0]), "+v"(bs[j % 2][1]));
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][0], bs[j % 2][0], acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][1], bs[j % 2][0], acc[1][j], 0, 0, 0);
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][0], bs[j % 2][1], acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][1], bs[j % 2][1], acc[1][j], 0, 0, 0);
                 acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][0], bs[j % 2][0], acc[0][j], 0, 0, 0);
                 acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][1], bs[j % 2][0], acc[1][j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
@@ -441,37 +428,11 @@ __global__ __launch_bounds__(512) void k_srp_gemm_f16_v2(GemmArgs p)
                 for (int j = 0; j < 6; ++j) crow[j * 32] = acc[i][j][r];
             }
         }
-    if constexpr (!SPLIT) if (p.part) {      // (the two-plane kernel has no registers to spare for it)
-        // Every 32-row block of the tile is one chunk of the scan over frames (the host only asks for this when that holds):
-        // its chunk-local recursion result is a weighted sum over the block's rows, 16 of them in this lane and 16 in
-        // lane ^ 32, so k_scan_partial's pass over the map is not needed.
-        const int h = lane >> 5;
-        float wt[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) wt[r] = h ? p.scan_w[(r & 3) + 8 * (r >> 2) + 4] : p.scan_w[(r & 3) + 8 * (r >> 2)];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int frow0 = row0 + wm * 64 + i * 32;
-            if (frow0 < p.rows) {
-                const int arr = frow0 / p.chunk_frames, chunk = (p.frame0 + frow0 - arr * p.chunk_frames) >> 5;
-                float *out = p.part + blockIdx.y * p.part_plane_stride + ((long long)arr * p.n_chunks + chunk) * p.D + wn * 192 + (lane & 31);
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    float sacc = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sacc = fmaf(wt[r], acc[i][j][r], sacc);
-                    sacc += __shfl_xor(sacc, 32);
-                    if (h == 0 && wn * 192 + j * 32 + (lane & 31) < p.D) out[j * 32] = sacc;
-                }
-                if (wn == 0 && lane == 0 && blockIdx.y == 0) p.nvoiced[(long long)arr * p.n_chunks + chunk] = 32;
-            }
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------
 // k_srp_gemm_f16_v3: the one-plane 256 x 384 contraction on v_mfma_f32_16x16x32_f16.
-// Same tile, stages, DMA and split-K as k_srp_gemm_f16_v2<false>; the 16x16x32 form needs the same fragment bytes per
+// Same tile, DMA and split-K as k_srp_gemm_f16_v2, one plane in four stages; the 16x16x32 form needs the same fragment bytes per
 // MAC (a fragment spans the stage's whole 32-deep K: 4 A + 12 B reads and 48 MFMAs per stage and wave instead of
 // 2 x (2 + 6) reads and 24 MFMAs) and runs the matrix pipe at a higher clock under the same load (timing probe with the
 // 32x32 kernel's operand stream: 168.6 -> 155.4 us).  Fragment: lane l holds row (l & 15), K chunk (l >> 4) of the
@@ -622,8 +583,5 @@ __global__ __launch_bounds__(512) void k_srp_gemm_f16_v3(GemmArgs p)
         }
     }
 }
-
-template __global__ void k_srp_gemm_f16_v2<true>(GemmArgs);
-template __global__ void k_srp_gemm_f16_v2<false>(GemmArgs);
 
 }  // namespace mca

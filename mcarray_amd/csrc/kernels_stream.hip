@@ -137,12 +137,8 @@ __global__ __launch_bounds__(512) void k_stft_phat(StftPhatArgs p)
 
 #define INST_STFT(MT, ULA, T) template __global__ void k_stft_phat<MT, ULA, T>(StftPhatArgs);
 INST_STFT(0, false, float) INST_STFT(0, true, float)
-INST_STFT(4, false, float) INST_STFT(4, true, float)
-INST_STFT(8, false, float) INST_STFT(8, true, float)
 INST_STFT(16, true, float)
 INST_STFT(0, false, _Float16) INST_STFT(0, true, _Float16)
-INST_STFT(4, false, _Float16) INST_STFT(4, true, _Float16)
-INST_STFT(8, false, _Float16) INST_STFT(8, true, _Float16)
 INST_STFT(16, true, _Float16)
 
 // --------------------------------------------------------------------------------------
@@ -748,11 +744,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
                 if (lane < S) s_bin[tl * MCA_MAX_SOURCES + lane] = -1;
                 continue;
             }
-#ifdef MCA_ABL_PICK      /* measurement only: wrong results */
-            const bool sens = false; if (lane < S) { s_bin[tl * MCA_MAX_SOURCES + lane] = 5; s_val[tl * MCA_MAX_SOURCES + lane] = sEn[tl * Dl + lane]; }
-#else
             const bool sens = wave_pick_pl<MODE >= 1, PL>(sEn + tl * Dl, D, S, p.tau, s_bin + tl * MCA_MAX_SOURCES, s_val + tl * MCA_MAX_SOURCES, lane);
-#endif
             if (MODE >= 1 && lane == 0 && (sens || t == t_force || ((um >> tl) & 0x7full) != 0)) atomicOr(&s_flagmask, 1u << tl);
         }
         __syncthreads();
@@ -1331,7 +1323,6 @@ __global__ __launch_bounds__(512, OCC) void k_beamform_ola(BeamformArgs p)
     }
 }
 
-template __global__ void k_beamform_ola<1, 2>(BeamformArgs);
 template __global__ void k_beamform_ola<1, 4>(BeamformArgs);
 template __global__ void k_beamform_ola<2, 2>(BeamformArgs);
 

@@ -65,70 +65,47 @@ __device__ __forceinline__ float2 win_hi(float a, float b, v2f w)
 // (z = (x_a, x_b) w), the 1024-point transform, W += Z T[doa bin]; then the inverse transform of W, whose real part is the
 // beamformed frame.  A wave's work is ONE loop over its (frame, pair) steps with the same loads in every step -- the next
 // step's samples (the last step reloads its own) and this step's table row, requested in the middle of the transform -- so
-// that the counted waits on the row leave the sample loads in flight behind the transform.
+// that the counted waits on the row leave the sample loads in flight behind the transform.  The stage-A twiddles live in
+// registers and scheduling barriers keep the loads where they are issued (fft1024c OPT = 7).
 //
-// Overlap-add carries (HANDOFF): a workgroup covers 4 ft - 1 consecutive frames; wave 0 takes the frame BEFORE them too (only
-// its second half counts: the carry into the workgroup's first hop) and ft - 1 frames, waves 1..3 take ft frames each.  A wave
-// does not wait for its predecessor's carry: it keeps the first half of its first frame in registers, the waves leave their
-// final carries in LDS, and after one barrier at the very end each wave adds its predecessor's carry and stores that hop.
-// One frame in 4 ft is analysed twice (without HANDOFF every wave re-analyses the frame before its run: one in ft + 1).
-// ODD: the last pair has one channel (its imaginary input is zero).  VAR: bit 0 stage-A twiddles in registers, bit 1 HANDOFF,
-// bit 2 table row requested in the middle of the transform, bit 3 scheduling barriers (A/B switches; api.hip picks one).
-#ifndef BFW_OCC
-#define BFW_OCC 2
-#endif
-template <bool ODD, int VAR, int ABL>
-__global__ __launch_bounds__(256, BFW_OCC) void k_beamform_wave(BeamformWaveArgs p)
+// Overlap-add carries: a workgroup covers 4 ft - 1 consecutive frames; wave 0 takes the frame BEFORE them too (only its second
+// half counts: the carry into the workgroup's first hop) and ft - 1 frames, waves 1..3 take ft frames each.  A wave does not wait
+// for its predecessor's carry: it keeps the first half of its first frame in registers, the waves leave their final carries in
+// LDS, and after one barrier at the very end each wave adds its predecessor's carry and stores that hop.  One frame in 4 ft is
+// analysed twice.  ODD: the last pair has one channel (its imaginary input is zero).
+template <bool ODD>
+__global__ __launch_bounds__(256, 2) void k_beamform_wave(BeamformWaveArgs p)
 {
-    constexpr bool T1REG = VAR & 1, HANDOFF = VAR & 2, TMID = VAR & 4;
-    // (round 6 A/B; MEASURE builds) STAGE: the next step's samples go to LDS with eight global_load_lds_dwordx4 (16 bytes
-    // per lane whatever the transform's register layout wants) and are read from there with ds_read_b32, instead of 32 four-byte loads into
-    // registers that stay live through the transform.  The staging buffer of a wave is 8 KiB; wave 0 takes the twiddle table's place (dead
-    // once the stage-A twiddles are in registers), so that two workgroups still share a CU.
-    constexpr bool STAGE = (VAR & 16) != 0;
-    static_assert(!STAGE || (T1REG && TMID), "the staged variant reuses the twiddle table's LDS and requests its steering rows in the middle of the transform");
-    constexpr int FOPT = 1 | ((VAR >> 3) & 1) << 1 | (T1REG ? 4 : 0);
+    constexpr int FOPT = 7;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *tab = reinterpret_cast<float2 *>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float2 *buf = tab + F1K_TWORDS + wave * F1K_SCRATCH;
-    float *xcarry = reinterpret_cast<float *>(tab + F1K_TWORDS + 4 * F1K_SCRATCH);      // HANDOFF: [4 waves][512] final carries
+    float *xcarry = reinterpret_cast<float *>(tab + F1K_TWORDS + 4 * F1K_SCRATCH);      // [4 waves][512] final carries
     f1k_table_init(tab, tid, 256);
     F1kLane lc;
     lc.init(lane);
     __syncthreads();
-    if (T1REG) lc.load_t1(tab, lane);
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    float *stage = nullptr;
-    if (STAGE) {
-        __syncthreads();                                                   // (every wave has its twiddles: the table's place is free)
-        stage = wave == 0 ? reinterpret_cast<float *>(tab) : reinterpret_cast<float *>(tab + F1K_TWORDS + 4 * F1K_SCRATCH) + 4 * FFT_H + (wave - 1) * 2048;
-    }
+    lc.load_t1(tab, lane);
 
     const int a = p.skew ? blockIdx.x : blockIdx.y;
     const long long as = (long long)a * p.S + blockIdx.z;                // (array, source): output channel, overlap-add carry
-    int t0, t1;
-    if (HANDOFF) {
-        int w0 = (int)blockIdx.x * (4 * p.ft - 1), ft = p.ft;            // the workgroup's first frame, frames per wave
-        if (p.skew) {
-            const int g = blockIdx.y, half = gridDim.y >> 1, hi = p.ft + p.skew, lo = p.ft - p.skew;
-            ft = g < half ? hi : lo;
-            w0 = g < half ? g * (4 * hi - 1) : half * (4 * hi - 1) + (g - half) * (4 * lo - 1);
-        }
-        t0 = wave == 0 ? w0 : w0 + wave * ft - 1;
-        t1 = min(w0 + (wave + 1) * ft - 1, p.n_frames);
-    } else {
-        t0 = ((int)blockIdx.x * 4 + wave) * p.ft;
-        t1 = min(t0 + p.ft, p.n_frames);
+    int w0 = (int)blockIdx.x * (4 * p.ft - 1), ft = p.ft;                // the workgroup's first frame, frames per wave
+    if (p.skew) {
+        const int g = blockIdx.y, half = gridDim.y >> 1, hi = p.ft + p.skew, lo = p.ft - p.skew;
+        ft = g < half ? hi : lo;
+        w0 = g < half ? g * (4 * hi - 1) : half * (4 * hi - 1) + (g - half) * (4 * lo - 1);
     }
+    const int t0 = wave == 0 ? w0 : w0 + wave * ft - 1;
+    const int t1 = min(w0 + (wave + 1) * ft - 1, p.n_frames);
     const bool active = t0 < t1;
     // (Every array is cut at the same frames and the frames of a run go in order -- the overlap-add carry --, so waves that
     // start together stream the same piece of their rows.  Layouts whose row pitch is a power of two plus a little (128 arrays
     // x 257 half frames of 512 floats: 2^19 + 2^11 bytes) then put the loads of all resident waves onto the same few memory
     // channels: 0.33 instead of 0.295 ms per 32 768 frames; 64 floats of padding per row avoid it.  Shifting the run
     // boundaries per array costs an extra, mostly empty round of waves: 0.36 ms.  k_stft_phat_wave rotates its frame order.)
-    const bool lead_in = HANDOFF ? (wave == 0 && t0 > 0) : t0 > 0;       // this wave analyses frame t0 - 1 for its carry
-    const bool deferred = HANDOFF && wave > 0;                           // the carry into hop t0 comes from the wave before
+    const bool lead_in = wave == 0 && t0 > 0;                            // this wave analyses frame t0 - 1 for its carry
+    const bool deferred = wave > 0;                                      // the carry into hop t0 comes from the wave before
     const int tfirst = lead_in ? t0 - 1 : t0;
     const int NP = p.n_pairs;
     float carry[8], first[8];
@@ -149,24 +126,8 @@ __global__ __launch_bounds__(256, BFW_OCC) void k_beamform_wave(BeamformWaveArgs
         auto load_pair = [&](int t, int pr) {
             const float *pa = base + (long long)(2 * pr) * p.mic_stride + (long long)t * FFT_H;
             const float *pb = (ODD && pr == NP - 1) ? pa : pa + p.mic_stride;
-            if (STAGE) {
-                // lane l, instruction q: samples 4 (64 q + l) .. + 3 -> the same words of the buffer (a linear copy of the frame)
-                const float *ga = pa - lane + 4 * lane, *gb = pb - lane + 4 * lane;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(ga + 256 * q), (lds_void_t *)(stage + 256 * q), 16, 0, 0);
-                    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(gb + 256 * q), (lds_void_t *)(stage + 1024 + 256 * q), 16, 0, 0);
-                }
-            } else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { xa[i] = pa[64 * i]; xb[i] = pb[64 * i]; }
-            }
-        };
-        auto take_pair = [&]() {                                           // STAGE: the staged step into registers
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { xa[i] = stage[lane + 64 * i]; xb[i] = stage[1024 + lane + 64 * i]; }
-            wave_lds_fence();
         };
         load_pair(tfirst, 0);
 
@@ -177,7 +138,6 @@ __global__ __launch_bounds__(256, BFW_OCC) void k_beamform_wave(BeamformWaveArgs
         const float2 *trow = p.table + ((long long)(bins[(long long)t * p.S] + 1) * NP) * 1024 + lane;
         for (;;) {
             float2 z[16], T[16];
-            if (STAGE) take_pair();
 #pragma unroll
             for (int i = 0; i < 8; ++i) { z[2 * i] = win_lo(xa[2 * i], xb[2 * i], win[i]); z[2 * i + 1] = win_hi(xa[2 * i + 1], xb[2 * i + 1], win[i]); }
             if (ODD && pr == NP - 1) {
@@ -185,18 +145,11 @@ __global__ __launch_bounds__(256, BFW_OCC) void k_beamform_wave(BeamformWaveArgs
                 for (int i = 0; i < 16; ++i) z[i].y = 0.f;
             }
             const bool last_pair = pr == NP - 1, last = last_pair && t + 1 >= t1;
-            if (!TMID) {
+            load_pair(last ? t : (last_pair ? t + 1 : t), last ? pr : (last_pair ? 0 : pr + 1));
+            __builtin_amdgcn_sched_barrier(0);
+            fft1024c<false, FOPT>(z, buf, lane, tab, lc, [&]() {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) T[i] = trow[pr * 1024 + 64 * dr16(i)];
-                if (FOPT & 2) __builtin_amdgcn_sched_barrier(0);
-            }
-            if (!(ABL & 1)) load_pair(last ? t : (last_pair ? t + 1 : t), last ? pr : (last_pair ? 0 : pr + 1));
-            if (FOPT & 2) __builtin_amdgcn_sched_barrier(0);
-            fft1024c<false, FOPT>(z, buf, lane, tab, lc, [&]() {
-                if (TMID) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) T[i] = (ABL & 2) ? make_float2(1e-3f * (float)(i + pr), 1e-3f) : trow[pr * 1024 + 64 * dr16(i)];
-                }
             });
 #pragma unroll
             for (int i = 0; i < 16; ++i) W[i] = cmac(W[i], z[i], T[i]);
@@ -232,27 +185,17 @@ __global__ __launch_bounds__(256, BFW_OCC) void k_beamform_wave(BeamformWaveArgs
             for (int i = 0; i < 8; ++i) p.tail_out[as * FFT_H + lane + 64 * i] = carry[i];
         }
     }
-    if (HANDOFF) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) xcarry[wave * FFT_H + lane + 64 * i] = carry[i];
-        __syncthreads();
-        if (active && deferred) {
-            float *o = p.out + as * p.n_frames * FFT_H + (long long)t0 * FFT_H + lane;
+    for (int i = 0; i < 8; ++i) xcarry[wave * FFT_H + lane + 64 * i] = carry[i];
+    __syncthreads();
+    if (active && deferred) {
+        float *o = p.out + as * p.n_frames * FFT_H + (long long)t0 * FFT_H + lane;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) o[64 * i] = xcarry[(wave - 1) * FFT_H + lane + 64 * i] + first[i];
-        }
+        for (int i = 0; i < 8; ++i) o[64 * i] = xcarry[(wave - 1) * FFT_H + lane + 64 * i] + first[i];
     }
 }
-
-#define INST_BFW(V) template __global__ void k_beamform_wave<false, V, 0>(BeamformWaveArgs); template __global__ void k_beamform_wave<true, V, 0>(BeamformWaveArgs);
-INST_BFW(15)              // the shipped variant
-#ifdef MCA_MEASURE        // the A/B variants and the ablations (wrong results) of DESIGN.md's measurements: make MEASURE=1 only
-template __global__ void k_beamform_wave<false, 14, 1>(BeamformWaveArgs); template __global__ void k_beamform_wave<false, 14, 2>(BeamformWaveArgs);
-template __global__ void k_beamform_wave<false, 14, 3>(BeamformWaveArgs);
-INST_BFW(0) INST_BFW(1) INST_BFW(2) INST_BFW(3) INST_BFW(4) INST_BFW(5) INST_BFW(6) INST_BFW(7)
-INST_BFW(8) INST_BFW(9) INST_BFW(10) INST_BFW(11) INST_BFW(12) INST_BFW(13) INST_BFW(14)
-INST_BFW(31)              // the shipped variant with its samples staged through LDS (round 6 A/B: profiles/r06_bfw_lds_stage_negative.log)
-#endif
+template __global__ void k_beamform_wave<false>(BeamformWaveArgs);
+template __global__ void k_beamform_wave<true>(BeamformWaveArgs);
 
 // --------------------------------------------------------------------------------------
 // k_beamform_wave_ms: several sources per array, the forward transforms SHARED (round 4; up to 8 microphones)
@@ -457,7 +400,7 @@ __device__ __forceinline__ float wave_sum64(float v)
 // rank[m] -- every instruction hits 64 different words and the instructions of a wave execute in order, so the sums are
 // formed in a fixed order --, and the region is read back as the row: n_merged instead of (M - 1) * 513 complex values.
 template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bool MERGE, bool CAND = false>
-__global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 4 or 8 waves (256 registers either way: two waves per SIMD)
+__global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // launched with 4 waves (256 registers: two waves per SIMD)
 {
     static_assert(!MERGE || (ULA && !PL2 && !NOPHAT && sizeof(OutT) == 2), "the merged index serves the one-plane fp16 rows of a ULA");
     constexpr int NP = MT / 2, NOUT = PairOut<MT, ULA>::N;
@@ -501,33 +444,15 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
 
     // regular mode: wave w of workgroup b takes the run of p.fpb frames number 4 b + w.  List mode (repair pass of the adaptive
     // SRP precision): workgroup b walks the listed groups of REPAIR_GROUP = 4 frames, wave w takes frame w of a group.
-    // Dynamic runs (p.queue; see StftPhatArgs): the wave takes its runs off the device-side counter; the request for the next run goes
-    // out at the top of a run's last frame and is read when the run is done.
     const int li_end = p.list ? min(n_list_now, p.list0 + p.list_cap) : 1, li_step = p.list ? (int)gridDim.x : 1;
-    unsigned rq = 0, rq_pending = 0;
-    const unsigned long long clock_in = p.wave_clock ? wall_clock64() : 0ull;
-    int runs_taken = 0;
-    if (p.queue) {
-        if (lane == 0) rq_pending = atomicAdd(p.queue, 1u);
-        rq = __builtin_amdgcn_readfirstlane(rq_pending);
-    }
-    for (int li = p.list ? p.list0 + (int)blockIdx.x : 0; p.queue ? rq < (unsigned)p.q_total : li < li_end; li += li_step) {
+    for (int li = p.list ? p.list0 + (int)blockIdx.x : 0; li < li_end; li += li_step) {
         int a = blockIdx.y;
-        // (measurement: xcd_map -- consecutive workgroups go to consecutive XCDs; give every XCD one contiguous piece of the array instead)
-        const int bxm = (p.xcd_map && (gridDim.x & 7) == 0) ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-        int f_begin = (bxm * nw + wave) * p.fpb, f_end = min(f_begin + p.fpb, p.n_frames);
+        int f_begin = ((int)blockIdx.x * nw + wave) * p.fpb, f_end = min(f_begin + p.fpb, p.n_frames);
         if (p.skew) {
             const int g = blockIdx.y, half = gridDim.y >> 1, hi = p.fpb + p.skew, lo = p.fpb - p.skew;
             a = blockIdx.x;
             if (g < half) { f_begin = (g * nw + wave) * hi; f_end = f_begin + hi; }
             else { f_begin = half * nw * hi + ((g - half) * nw + wave) * lo; f_end = f_begin + lo; }
-        }
-        if (p.queue) {
-            int rr = 0, rpa = 1, f_first = 0, len = 1, f_last = 0;
-            dyn_run((int)rq, p.n_frames, p.q_arrays, p.q_sh0, rr, rpa, f_first, len, f_last, p.q_flat);
-            a = __builtin_amdgcn_readfirstlane(rr / rpa);                     // (the division runs on the vector ALU: back to scalar registers, or every address below turns into vector code)
-            f_begin = f_first + (rr - a * rpa) * len;
-            f_end = min(f_begin + len, f_last);
         }
         long long row_base = (long long)a * p.n_frames;     // A row of frame f = row_base + f
         bool hist_unit = false;                                // list mode, lazy tails: a unit of the PREVIOUS call's last frames (StftPhatArgs::hist_in)
@@ -543,10 +468,7 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
             f_begin = g_begin + wave; f_end = min(f_begin + 1, hist_unit ? HIST_FRAMES : p.n_frames);
         }
         const bool has_frame = f_begin < f_end;
-        if (!has_frame) {
-            if (p.queue) break;                     // (cannot happen: every listed run holds a frame)
-            if (!CAND) continue;                    // (candidate-column list mode: the wave still helps to contract the unit's rows below)
-        }
+        if (!has_frame && !CAND) continue;          // (candidate-column list mode: the wave still helps to contract the unit's rows below)
         if (has_frame) {
         const float *base = hist_unit ? p.hist_in + (long long)a * MT * HIST_SAMPLES + lane : p.pcm + (long long)a * p.array_stride + lane;
         const long long mstride = hist_unit ? (long long)HIST_SAMPLES : p.mic_stride;
@@ -568,7 +490,6 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
         load_pair(frame_of(0), 0);
         for (int fi = 0; fi < nfr; ++fi) {
             const int f = frame_of(fi);
-            if (p.queue && fi == nfr - 1 && lane == 0) rq_pending = atomicAdd(p.queue, 1u);     // the next run: asked for a frame ahead of its use
             float2 Xh[MT][8], zn[NP];
             v2f ptime = {0.f, 0.f};                                                // POWER: sum of the squared windowed samples (Parseval)
             bool any_alive = false;                                                // (wave-uniform)
@@ -601,7 +522,7 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
 #pragma unroll
                 for (int i = 3; i < 15; i += 2) { ma = max3abs(ma, z[i].x, z[i + 1].x); mb = max3abs(mb, z[i].y, z[i + 1].y); }
                 ma = max2abs(ma, z[15].x); mb = max2abs(mb, z[15].y);
-                const PairBalance pb = pair_balance(ma, mb, !p.no_balance);
+                const PairBalance pb = pair_balance(ma, mb);
                 const bool alive_a = pb.alive_a, alive_b = pb.alive_b;
                 any_alive = any_alive || alive_a || alive_b;
                 if (pb.scaled()) {
@@ -774,17 +695,6 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                 cand_unit<4>(p.cand, li - p.list0, e_unit, reinterpret_cast<unsigned char *>(wbase), tid);
             }
         }
-        if (p.queue) rq = __builtin_amdgcn_readfirstlane(rq_pending);
-        ++runs_taken;
-    }
-    if (p.wave_clock && lane == 0) {
-        unsigned long long *wc = p.wave_clock + 3ull * ((blockIdx.y * gridDim.x + blockIdx.x) * (unsigned)nw + wave);
-        wc[0] = clock_in; wc[1] = wall_clock64(); wc[2] = (unsigned long long)runs_taken;
-    }
-    // the last wave to leave zeroes the counters (every wave has made its last request by then)
-    if (p.queue && lane == 0) {
-        __threadfence();
-        if (atomicAdd(p.queue + 1, 1u) == gridDim.x * gridDim.y * (unsigned)nw - 1u) { p.queue[0] = 0u; p.queue[1] = 0u; }
     }
 }
 
@@ -883,7 +793,7 @@ __global__ __launch_bounds__(256, 2) void k_stft_phat_wave16(StftPhatArgs p)
 #pragma unroll
             for (int i = 3; i < 15; i += 2) { ma = max3abs(ma, z[i].x, z[i + 1].x); mb = max3abs(mb, z[i].y, z[i + 1].y); }
             ma = max2abs(ma, z[15].x); mb = max2abs(mb, z[15].y);
-            const PairBalance pb = pair_balance(ma, mb, !p.no_balance);
+            const PairBalance pb = pair_balance(ma, mb);
             const bool alive_a = pb.alive_a, alive_b = pb.alive_b;
             float dc_a = ref_a, dc_b = ref_b;
             if (pb.scaled()) {

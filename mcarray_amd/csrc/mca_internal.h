@@ -90,22 +90,12 @@ struct StftPhatArgs {
     const unsigned short *mrank; int n_merged;   // k_stft_phat_wave, merged index (ULA, one fp16 plane): rank of the product m = k (j - i)
                              // among the n_merged distinct ones, [(M - 1) * 512 + 1]; NULL: per-group index g * 513 + k
     int no_phat;             // 1: gcc_weighting NONE -- the pair products of the spectra themselves (k_stft_phat_wave, fp32 rows only)
-    int no_balance;          // (measurement, make MEASURE=1 + MCA_HIP_NO_BALANCE) 1: the two channels of a pair transform are never level-balanced (pair_balance.h): round 5's analysis
-    // k_stft_phat_wave, dynamic runs (round 5): queue != NULL -- the grid is one resident wave set and every wave takes runs of frames off
-    // a device-side counter until none is left: queue[0] next run, queue[1] waves that have left (the last one zeroes both: the words
-    // are clean for the next launch, recorded graphs included).  The runs get shorter towards the end (dyn_run below: 8, 4, 2, 1 frames
-    // at the bench shape), so that the waves finish within about a frame of each other whatever their individual speed.
-    unsigned *queue;
-    int q_sh0, q_total, q_arrays;   // log2 of the first runs' length, number of runs, arrays of the launch
-    int q_flat;                     // (measurement) 1: every run has the first runs' length
-    int xcd_map;                    // (measurement) 1: workgroups of one XCD (linear id mod 8) take neighbouring runs of frames
     int skew;                       // > 0 (round 5; a launch that is exactly one resident round of two workgroups per CU): grid (arrays, run groups),
                                     // and the run groups of the first half -- dispatched first: the OLDER workgroup of every CU, which the CU's
                                     // oldest-first issue favours (its waves were done at 180 us, the younger one's at 244: profiles/
                                     // r05_run_queue_negative.log) -- take fpb + skew frames per wave, the others fpb - skew, so that both finish
                                     // together (19 / 13 frames: 302 -> 281 us per 32 768 frames, profiles/r05_skew.log).  The rows do not
                                     // depend on which wave forms them: the same bits.
-    unsigned long long *wave_clock; // (measurement, make MEASURE=1 + MCA_HIP_WAVE_CLOCK) [waves][3]: wall_clock64 at entry and exit, runs taken
     unsigned char *dead;     // k_stft_phat_wave in the coarse pass of a candidate-column call, else NULL: [arrays][total_frames] 1 = every channel of the frame is
                              // exact zeros (digital silence): its row is zero in the coarse and in the exact map alike, the repair pass need not list it
     unsigned char *unsure;   // k_stft_phat_wave16 in the adaptive coarse pass, else NULL: [arrays][total_frames] 1 = a channel's DC or Nyquist bin of this
@@ -116,28 +106,6 @@ struct StftPhatArgs {
     // k_srp_cand's work without its launch
     int cand_on; CandArgs cand;
 };
-
-// The run schedule of the dynamic mode, the same arithmetic on the host (the number of runs) and in the kernel (run r -> array, frames):
-// per array, half of the frames that are left go in runs of 2^sh frames, then sh drops by one; the last phase takes one frame at a
-// time.  Runs are numbered phase by phase, array-major inside a phase.  Shifts and multiplies only (scalar ALU) up to the one division
-// by the caller.  Returns the number of runs when r is past the end (a, f_begin, f_end untouched).
-__host__ __device__ inline int dyn_run(int r, int n_frames, int n_arrays, int sh0, int &rr, int &rpa, int &f_first, int &len, int &f_last, int flat = 0)
-{
-    int f0 = 0, first = 0;
-    if (flat) {
-        const int n = (n_frames + (1 << sh0) - 1) >> sh0;
-        if (r < n * n_arrays) { rr = r; rpa = n; f_first = 0; len = 1 << sh0; f_last = n_frames; return -1; }
-        return n * n_arrays;
-    }
-    for (int sh = sh0; ; --sh) {
-        const bool lastph = sh <= 0;
-        const int nfr = lastph ? n_frames - f0 : (((n_frames - f0) >> 1) >> sh) << sh;
-        const int n = lastph ? nfr : nfr >> sh;
-        if (r >= first && r < first + n * n_arrays) { rr = r - first; rpa = n; f_first = f0; len = lastph ? 1 : 1 << sh; f_last = f0 + nfr; return -1; }
-        first += n * n_arrays; f0 += nfr;
-        if (lastph) return first;
-    }
-}
 
 __device__ __forceinline__ void store_a(float *row, const StftPhatArgs &, int cidx, float2 v)
 {

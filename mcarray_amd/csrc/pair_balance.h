@@ -75,13 +75,13 @@ struct PairBalance {
 };
 
 // ma, mb: per lane, the largest |windowed sample| of channel a / b among the lane's samples of the frame
-__device__ __forceinline__ PairBalance pair_balance(float ma, float mb, bool enable = true)
+__device__ __forceinline__ PairBalance pair_balance(float ma, float mb)
 {
     PairBalance r;
     r.na = r.nb = 0;
     r.alive_a = __any(ma > 0.f);
     r.alive_b = __any(mb > 0.f);
-    if (enable && (__any(ma > PB_SCREEN * mb) || __any(mb > PB_SCREEN * ma))) {
+    if (__any(ma > PB_SCREEN * mb) || __any(mb > PB_SCREEN * ma)) {
         wave_max64_2(ma, mb);
         const int ea = (int)(__float_as_uint(ma) >> 23), eb = (int)(__float_as_uint(mb) >> 23);      // (non-negative values: no sign bit)
         if (__float_as_uint(ma) != 0u && __float_as_uint(mb) != 0u) {          // (both alive; integer compares: scalar ALU)

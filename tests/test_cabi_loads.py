@@ -52,9 +52,9 @@ def test_product_package_does_not_import_oracle():
 
 
 def test_measurement_switches_are_not_in_the_shipped_library():
-    """the A/B switches behind DESIGN.md's measurements (one of them, MCA_HIP_BFW_ABL, returns wrong audio on
-    purpose) are compiled in only with `make MEASURE=1`; the shipped library knows the ten product switches, reads them once in
-    mca_hip_create (csrc/knobs.h is the only place that touches the environment) and nothing else."""
+    """the library knows the ten product switches, reads them once in mca_hip_create (csrc/knobs.h is the only
+    place that touches the environment) and nothing else; the A/B switches behind DESIGN.md's measurements are gone from the
+    sources."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     blob = open(os.path.join(root, "mcarray_amd", "libmcarray_hip.so"), "rb").read()
@@ -66,6 +66,25 @@ def test_measurement_switches_are_not_in_the_shipped_library():
     for f in os.listdir(src):
         if f.endswith((".hip", ".h")) and f != "knobs.h":
             assert "getenv" not in open(os.path.join(src, f)).read(), f
+
+
+def test_scripts_name_only_switches_the_library_reads():
+    """A tool, test or wrapper that sets an MCA_HIP_* variable the library no longer reads measures the default build while it
+    claims to measure something else: every such name is one of the ten product switches, MCA_HIP_LIB (the library to load) or a
+    constant of include/mcarray_hip.h."""
+    import glob
+    known = {"MCA_HIP_ADAPT_CAND", "MCA_HIP_ADAPT_FALLBACK", "MCA_HIP_ADAPT_LAZY", "MCA_HIP_ADAPT_MAX_SOURCES", "MCA_HIP_ADAPT_MIN_ROWS", "MCA_HIP_ADAPT_TAU_SCALE",
+             "MCA_HIP_FORCE_GENERIC", "MCA_HIP_NO_N2048", "MCA_HIP_SCAN_CARRY", "MCA_HIP_WS_MAX_MB", "MCA_HIP_LIB"}
+    files = [os.path.join(ROOT, "bench.py")]
+    for pattern in ("tools/*.py", "tools/*.sh", "tests/*.py", "mcarray_amd/*.py"):
+        files += glob.glob(os.path.join(ROOT, pattern))
+    unknown = {}
+    for f in sorted(files):
+        names = set(re.findall(r"MCA_HIP_[A-Z0-9_]{3,}", open(f).read()))
+        names = {n for n in names if not re.match(r"MCA_HIP_(OK|ERR_|SRP_|GCC_|K_|ADAPT_FALLBACK_(AUTO|OFF))", n)} - known
+        if names:
+            unknown[os.path.relpath(f, ROOT)] = sorted(names)
+    assert not unknown, unknown
 
 
 def test_no_packed_fp32_instruction_takes_the_high_half_of_src1_into_the_low_result():
