@@ -489,6 +489,12 @@ int mca_hip_get_repair_stats(mca_hip_ctx *ctx, unsigned long long *frames, unsig
  * candidate_columns: their number summed over the flagged frames; whole_row_frames: the flagged frames that took every delay
  * (no lower bound from the coarse row, a frame repeated for the carried state's sake, a row the coarse analysis could not vouch for). */
 int mca_hip_get_repair_columns(mca_hip_ctx *ctx, unsigned long long *candidate_columns, unsigned long long *whole_row_frames);
+/* Delay-and-sum on the half spectrum (mca_hip_process_frames_dev of a one-source, ungated 8-microphone ULA at 1024-sample frames, ADAPTIVE or
+ * FP16): the analysis steers every frame at the array's PREDICTED bin -- its last pick of the previous call -- and a patch pass redoes the
+ * frames whose pick came out different.  frames: frames such calls have processed since creation; missed_frames: those whose pick was not
+ * the predicted bin; fused_calls: calls whose analysis steered ahead (the others steered every frame after the picks).  The audio does not
+ * depend on any of this: both passes run one routine. */
+int mca_hip_get_steer_stats(mca_hip_ctx *ctx, unsigned long long *frames, unsigned long long *missed_frames, unsigned long long *fused_calls);
 
 /* library version string */
 const char *mca_hip_version(void);

@@ -342,6 +342,12 @@ class Context:
         self._check(self._lib.mca_hip_get_repair_stats(self.h, C.byref(a), C.byref(b), C.byref(c_)))
         return {"frames": a.value, "flagged": b.value, "recomputed": c_.value}
 
+    def steer_stats(self):
+        """dict(frames, missed, fused_calls) of the device-pointer calls that steer on the half spectrum (mca_hip_get_steer_stats)"""
+        a, b, c_ = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self._lib.mca_hip_get_steer_stats(self.h, C.byref(a), C.byref(b), C.byref(c_)))
+        return {"frames": a.value, "missed": b.value, "fused_calls": c_.value}
+
     def repair_columns(self):
         """SRP_ADAPTIVE: dict(candidate_columns, whole_row_frames) since the last reset_timing() (mca_hip_get_repair_columns)"""
         a, b = C.c_ulonglong(0), C.c_ulonglong(0)

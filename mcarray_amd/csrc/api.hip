@@ -125,6 +125,18 @@ struct mca_hip_ctx {
     bool merged = false; int n_merged = 0, Kp_m = 0;
     void *d_Bm = nullptr, *d_Btm = nullptr; unsigned short *d_mrank = nullptr;
     float2 *d_bftab = nullptr; int bf_pairs = 0;   // k_beamform_wave: steering rows per grid angle, [D + 1][bf_pairs][1024] (built on first use)
+    // Delay-and-sum on the half spectrum (steer.h; steer_applies): the per-channel steering table, the predicted bin per array (the last pick of
+    // the previous call; -1 on a new stream), the running miss total, the rows of Y (grown on demand) and two carries between frame passes
+    float4 *d_steer_rows = nullptr; float2 *d_steer_q = nullptr; float *d_steer_nyq = nullptr; int *d_steer_pred = nullptr; unsigned long long *d_steer_miss = nullptr;
+    float2 *d_steer_Y = nullptr; size_t steer_Y_rows = 0; float *d_steer_tail = nullptr;
+    bool steer_now = false, steer_fused_now = false;        // this call: the analysis may steer ahead (Y holds the whole call) / did
+    unsigned long long steer_frames_total = 0, steer_fused_calls = 0;
+    // the guard of that path (steer_policy_begin): a call steers ahead of its picks unless the report of the call FB_LAG calls before it -- its
+    // frames whose pick was not the predicted bin, through page-locked memory, consumed at that fixed lag like the AUTO policy's -- had more
+    // than STEER_MISS_NUM / STEER_MISS_DEN of its frames missing
+    unsigned long long *h_steer = nullptr;              // [FB_RING][2] per call (seq - 1) % FB_RING: missed frames, sequence number
+    unsigned long long steer_seq = 0, steer_seq_seen = 0, steer_call_frames[FB_RING] = {};
+    bool steer_spec = true, steer_lost = false;
     // stream state (double buffered: kernels read [cur], write [cur^1])
     float *d_E[2] = {nullptr, nullptr};
     float *d_tail[2] = {nullptr, nullptr};
@@ -238,12 +250,13 @@ void free_ctx(mca_hip_ctx *c)
 {
     if (!c) return;
     auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
+    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
     F(c->d_E[0]); F(c->d_E[1]); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_doa[0]); F(c->d_doa[1]); F(c->d_vdone[0]); F(c->d_vdone[1]); F(c->d_g2_vidx); F(c->d_g2_nv); F(c->d_g2_rad); F(c->d_g2_prob);
     F(c->d_g2_reset); F(c->d_g2_post0); F(c->d_silence);
     F(c->d_rstats); F(c->d_gate_state);
     for (int i = 0; i < 2; ++i) { F(c->d_hist_pcm[i]); F(c->d_hist_C[i]); F(c->d_ehist[i]); }
     if (c->h_probe) (void)hipHostFree(c->h_probe);
+    if (c->h_steer) (void)hipHostFree(c->h_steer);
     for (Workspace &w : c->lanes) w.release();
     for (auto &e : c->io_ev) if (e) (void)hipEventDestroy(e);
     for (auto &q : c->io_stream) if (q) (void)hipStreamDestroy(q);
@@ -890,7 +903,8 @@ int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, h
         const bool mg = w.mrank != nullptr && !a.list;
         const int nrank = 2 * (M - 1) * 64 * 4 + 8, regw = mg ? std::max(F1K_SCRATCH, (w.n_merged + 63) & ~63) : F1K_SCRATCH;
         // (the merged kernel keeps its Nyquist bins in registers: with its 15.5 KiB regions two workgroups just fit the 160 KiB of a CU)
-        const size_t smw = (size_t)(F1K_TWORDS + (mg ? nrank / 4 : 0) + 4 * regw + (mg ? 0 : 4 * (w.fpb + w.skew) * (M / 2))) * sizeof(float2);
+        const bool fuse = mg && M == 8 && w.bf.rows != nullptr && a.power == nullptr && regw >= F1K_SCRATCH + STEER_LDS_ROWS * 64;      // steering ahead of the picks (steer.h): + the waves' steps Q
+        const size_t smw = (size_t)(F1K_TWORDS + (mg ? nrank / 4 : 0) + 4 * regw + (mg ? 0 : 4 * (w.fpb + w.skew) * (M / 2)) + (fuse ? 4 * STEER_QWORDS : 0)) * sizeof(float2);
         const bool pl2 = a.a_planes == 2, pw = a.power != nullptr;
 #define LAUNCH_K(K)                                                                                                 \
         do {                                                                                                         \
@@ -912,7 +926,8 @@ int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, h
         } while (0)
         if constexpr (sizeof(OutT) == 2) {
             if (mg) {          // merged contraction index: ULA, one plane
-                if (M == 8) { if (pw) LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true>)); }
+                if (fuse) { LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true, false, true>)); c->steer_fused_now = true; }      // steering ahead of the picks (steer.h)
+                else if (M == 8) { if (pw) LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true>)); }
                 else { if (pw) LAUNCH_K((k_stft_phat_wave<4, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<4, true, OutT, false, false, false, true>)); }
                 HIP_TRY(c, hipGetLastError());
                 return MCA_HIP_OK;
@@ -1206,6 +1221,8 @@ int mca_hip_reset(mca_hip_ctx *c, void *stream)
         if (w.d_chunk_from) HIP_TRY(c, hipMemsetAsync(w.d_chunk_from, 0x7f, w.adapt_chunks * 4, st));
         if (w.d_nlist) HIP_TRY(c, hipMemsetAsync(w.d_nlist, 0, 16, st));
     }
+    if (c->d_steer_pred) HIP_TRY(c, hipMemsetAsync(c->d_steer_pred, 0xff, na * 4, st));      // no pick yet: bin -1, the initial DOA
+    c->steer_spec = true; c->steer_lost = false; c->steer_seq_seen = c->steer_seq;              // (reports still in flight belong to the old streams)
     c->gcc2_frames_done = 0;
     c->g2f = G2FrameState();                                                              // the frame hook as a newly built module
     return init_last_state(c, st);
@@ -1330,6 +1347,7 @@ static int reserve_lane(mca_hip_ctx *c, int n_arrays, int n_frames)
     return ensure_scan_workspace(c, n_arrays, n_frames, n_chunks);
 }
 
+static int steer_reserve(mca_hip_ctx *c, int n_arrays, int n_frames);
 static int reserve_impl(mca_hip_ctx *c, int n_arrays, int n_frames)
 {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -1340,7 +1358,8 @@ static int reserve_impl(mca_hip_ctx *c, int n_arrays, int n_frames)
 int mca_hip_reserve(mca_hip_ctx *c, int n_arrays, int n_frames)
 {
     if (!c || n_arrays < 1 || n_frames < 1) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    return reserve_impl(c, n_arrays, n_frames);
+    const int rc = reserve_impl(c, n_arrays, n_frames);
+    return rc ? rc : steer_reserve(c, n_arrays, n_frames);      // (the rows of Y of a context that steers on the half spectrum)
 }
 
 // STFT + PHAT + steering contraction for every frame: fills c->ws().d_C [arrays][n_frames][Dp]
@@ -1377,6 +1396,9 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         if (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 1 && wave16_applies(c)) sa.unsure = c->ws().d_unsure;   // (adaptive coarse pass)
         if (c->lazy_now && cand_call(c, true)) sa.dead = c->ws().d_unsure;                                               // (... of a candidate-column call: frames of exact zeros)
         if (c->lazy_now) sa.hist_out = c->d_hist_pcm[c->hist_cur ^ 1];       // lazy tails: the call's last frames of PCM stay behind
+        if (c->steer_now && sa.mrank && !sa.power) {                          // the merged 8-microphone kernel also steers every frame at the array's predicted bin
+            sa.bf.rows = c->d_steer_rows; sa.bf.q = c->d_steer_q; sa.bf.nyq = c->d_steer_nyq; sa.bf.pred = c->d_steer_pred + c->a0; sa.bf.Y = c->d_steer_Y;
+        }
         time_begin(c, MCA_HIP_K_STFT_PHAT, st);
         if (c->n512) {
             rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft_512<float>(c, sa, dim3(0, n_arrays), st) : launch_stft_512<_Float16>(c, sa, dim3(0, n_arrays), st);
@@ -1733,6 +1755,19 @@ int mca_hip_get_repair_stats(mca_hip_ctx *c, unsigned long long *frames, unsigne
     return MCA_HIP_OK;
 }
 
+int mca_hip_get_steer_stats(mca_hip_ctx *c, unsigned long long *frames, unsigned long long *missed_frames, unsigned long long *fused_calls)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    unsigned long long m = 0;
+    if (c->d_steer_miss) HIP_TRY(c, hipMemcpy(&m, c->d_steer_miss, sizeof(m), hipMemcpyDeviceToHost));
+    if (frames) *frames = c->steer_frames_total;
+    if (missed_frames) *missed_frames = m;
+    if (fused_calls) *fused_calls = c->steer_fused_calls;
+    return MCA_HIP_OK;
+}
+
 int mca_hip_get_repair_columns(mca_hip_ctx *c, unsigned long long *candidate_columns, unsigned long long *whole_row_frames)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
@@ -1775,6 +1810,114 @@ static int ensure_bf_table(mca_hip_ctx *c)
     hipLaunchKernelGGL(k_bf_table, dim3(c->D + 1, np), dim3(256), 0, nullptr, c->d_bftab, c->d_grid, c->d_micx, c->M, np, unit);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipDeviceSynchronize());
+    return MCA_HIP_OK;
+}
+
+// Delay-and-sum on the half spectrum of the separated channels (steer.h): device-pointer calls of the one-source, ungated 8-microphone ULA at
+// 1024-sample frames whose coarse rows are the merged one-plane ones (ADAPTIVE, FP16).  Such a context ALWAYS takes this path for
+// mca_hip_process_frames_dev -- whether a call's analysis steered ahead of the picks or not, its audio comes from the same routine.
+static bool steer_applies(const mca_hip_ctx *c)
+{
+    return !c->generic && !c->n512 && !c->n2048 && c->N == FFT_N && c->M == 8 && c->ula && c->S == 1 && !c->cfg.use_power_floor && c->merged &&
+           (c->prec == MCA_HIP_SRP_ADAPTIVE || c->prec == MCA_HIP_SRP_FP16) && c->cfg.gcc_weighting != MCA_HIP_GCC_NONE;
+}
+
+// frames of Y per pass: the whole call while its rows fit the workspace budget (MCA_HIP_WS_MAX_MB)
+static int steer_pass_frames(const mca_hip_ctx *c, int n_arrays, int n_frames)
+{
+    const long long cap = ws_max_bytes(c) / ((long long)n_arrays * STEER_ROW * (long long)sizeof(float2));
+    return (int)std::max<long long>(1, std::min<long long>(n_frames, cap));
+}
+
+// The guard for content that moves.  Call number s consumes the report of call s - FB_LAG (waiting for it if need be: the call in between is
+// still queued behind it), so which call switches depends on the calls and their content only -- reproducible run to run, like the AUTO
+// policy (adapt_policy_begin).  Without page-locked memory, or once a report stayed away for FB_WAIT_MS, every call steers ahead.
+static void steer_policy_begin(mca_hip_ctx *c)
+{
+    const unsigned long long s = c->steer_seq + 1;                              // this call
+    if (!c->h_steer || c->steer_lost || s <= FB_LAG) return;
+    const unsigned long long r = s - FB_LAG;
+    if (r <= c->steer_seq_seen) return;
+    const unsigned long long *slot = c->h_steer + 2 * ((r - 1) % FB_RING);
+    const auto t0 = std::chrono::steady_clock::now();
+    while (__atomic_load_n(&slot[1], __ATOMIC_ACQUIRE) != r) {
+        if (std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > FB_WAIT_MS) { c->steer_lost = true; c->steer_spec = true; return; }
+        std::this_thread::yield();
+    }
+    c->steer_seq_seen = r;
+    c->steer_spec = __atomic_load_n(&slot[0], __ATOMIC_RELAXED) * STEER_MISS_DEN <= c->steer_call_frames[(r - 1) % FB_RING] * STEER_MISS_NUM;
+}
+
+// table (once, outside any capture), state, rows of Y for this call
+static int steer_prepare(mca_hip_ctx *c, int n_arrays, int n_frames)
+{
+    if (!c->d_steer_rows) {
+        const size_t na = (size_t)c->cfg.max_arrays;
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_rows, (size_t)(c->D + 1) * 4 * 64 * sizeof(float4)));
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_q, (size_t)(c->D + 1) * c->M * 8 * sizeof(float2)));
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_nyq, (size_t)(c->D + 1) * c->M * sizeof(float)));
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_pred, na * sizeof(int)));
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_miss, 3 * sizeof(unsigned long long)));      // running total; the guard's (arrays that had a prediction); the guard's at the end of the previous call
+        if (hipHostMalloc((void **)&c->h_steer, FB_RING * 16, hipHostMallocDefault) == hipSuccess) std::memset(c->h_steer, 0, FB_RING * 16); else { c->h_steer = nullptr; (void)hipGetLastError(); }
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_tail, 2 * na * FFT_H * sizeof(float)));
+        HIP_TRY(c, hipMemset(c->d_steer_pred, 0xff, na * sizeof(int)));
+        HIP_TRY(c, hipMemset(c->d_steer_miss, 0, 3 * sizeof(unsigned long long)));
+        const double unit = (double)c->cfg.sample_rate / (double)FFT_N / 346.1;     // Beamformer.cpp:59 without 2 pi
+        hipLaunchKernelGGL(k_steer_table, dim3(c->D + 1, 4), dim3(64), 0, nullptr, c->d_steer_rows, c->d_steer_q, c->d_steer_nyq, c->d_grid, c->d_micx, c->M, unit);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipDeviceSynchronize());
+    }
+    const size_t rows = (size_t)n_arrays * steer_pass_frames(c, n_arrays, n_frames);
+    if (rows > c->steer_Y_rows) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        if (c->d_steer_Y) (void)hipFree(c->d_steer_Y);
+        c->d_steer_Y = nullptr; c->steer_Y_rows = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_Y, rows * STEER_ROW * sizeof(float2)));
+        c->steer_Y_rows = rows;
+    }
+    return MCA_HIP_OK;
+}
+
+static int steer_reserve(mca_hip_ctx *c, int n_arrays, int n_frames) { return steer_applies(c) ? steer_prepare(c, n_arrays, n_frames) : MCA_HIP_OK; }
+
+// the separation stage of such a call: patch pass (the frames whose pick is not the predicted bin; every frame if the analysis did not steer)
+// and synthesis, in passes of frames when Y does not hold the whole call
+static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride, int n_arrays, int n_frames,
+                          const int *doa_bin, float *out_pcm, hipStream_t st)
+{
+    const size_t a0 = (size_t)c->a0;
+    const int pf = steer_pass_frames(c, n_arrays, n_frames);
+    const bool fused = c->steer_fused_now && pf == n_frames;
+    const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2);
+    float *tails[2] = {c->d_steer_tail, c->d_steer_tail + (size_t)c->cfg.max_arrays * FFT_H};
+    time_begin(c, MCA_HIP_K_BEAMFORM, st);
+    int pass = 0;
+    for (int f0 = 0; f0 < n_frames; f0 += pf, ++pass) {
+        const int f1 = std::min(n_frames, f0 + pf), np = f1 - f0;
+        const bool last = f1 == n_frames;
+        SteerPatchArgs pa{};
+        pa.pcm = pcm; pa.array_stride = array_stride; pa.mic_stride = mic_stride; pa.n_arrays = n_arrays; pa.n_frames = n_frames; pa.f0 = f0; pa.f1 = f1;
+        pa.window = c->d_window; pa.doa_bin = doa_bin; pa.all = fused ? 0 : 1; pa.miss = c->d_steer_miss;
+        pa.bf.rows = c->d_steer_rows; pa.bf.q = c->d_steer_q; pa.bf.nyq = c->d_steer_nyq; pa.bf.pred = c->d_steer_pred + a0; pa.bf.Y = c->d_steer_Y;
+        pa.y_f0 = f0; pa.y_frames = fused ? n_frames : np;
+        hipLaunchKernelGGL(k_steer_patch, dim3(std::min(STEER_PATCH_WGS, (np + 3) / 4)), dim3(256), smem, st, pa);
+        SteerSynthArgs sy{};
+        sy.Y = c->d_steer_Y; sy.n_frames = n_frames; sy.f0 = f0; sy.f1 = f1; sy.y_f0 = pa.y_f0; sy.y_frames = pa.y_frames;
+        sy.ft = 16;
+        while (sy.ft > 2 && (long long)n_arrays * ((np + sy.ft - 1) / sy.ft) < 1024) sy.ft >>= 1;      // (a thousand runs: one wave each)
+        sy.out = out_pcm;
+        sy.tail_in = pass == 0 ? c->d_tail[c->tail_cur] + a0 * FFT_H : tails[(pass - 1) & 1];
+        sy.tail_out = last ? c->d_tail[c->tail_cur ^ 1] + a0 * FFT_H : tails[pass & 1];
+        sy.doa_bin = doa_bin; sy.pred_out = last ? c->d_steer_pred + a0 : nullptr;
+        if (last && c->h_steer) { sy.report = c->h_steer + 2 * (c->steer_seq % FB_RING); sy.seq = c->steer_seq + 1; sy.miss_total = c->d_steer_miss; }
+        const int runs = (np + sy.ft - 1) / sy.ft;
+        hipLaunchKernelGGL(k_steer_synth, dim3((runs + 3) / 4, n_arrays), dim3(256), smem, st, sy);
+    }
+    time_end(c, st);
+    HIP_TRY(c, hipGetLastError());
+    c->steer_call_frames[c->steer_seq % FB_RING] = (unsigned long long)n_arrays * n_frames; ++c->steer_seq;
+    c->steer_frames_total += (unsigned long long)n_arrays * n_frames;
+    if (fused) ++c->steer_fused_calls;
     return MCA_HIP_OK;
 }
 
@@ -1992,11 +2135,17 @@ int mca_hip_process_frames_dev(mca_hip_ctx *c, const float *pcm, long long array
     if (!out_pcm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev/out_pcm_dev is NULL");
     if ((rc = ensure_bf_table(c))) return rc;
     c->n_lanes_last = 1; c->cur_lane = 0; c->a0 = 0;
+    const bool steer = steer_applies(c) && !c->host_call && !c->capturing;
+    if (steer && (rc = steer_prepare(c, n_arrays, n_frames))) return rc;
+    if (steer) steer_policy_begin(c);
+    c->steer_now = steer && c->steer_spec && steer_pass_frames(c, n_arrays, n_frames) == n_frames; c->steer_fused_now = false;
     adapt_policy_begin(c, n_arrays, n_frames);
     c->lazy_entry = !c->host_call;
     rc = localise_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, (hipStream_t)stream);
     c->lazy_entry = false;
-    if (!rc) rc = separate_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
+    c->steer_now = false;
+    if (!rc && steer) rc = steer_separate(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, out_pcm, (hipStream_t)stream);
+    else if (!rc) rc = separate_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
     if (rc) return rc;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
     c->e_cur ^= 1; c->tail_cur ^= 1;

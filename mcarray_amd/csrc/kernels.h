@@ -29,7 +29,10 @@ template <int MT, bool ULA, typename OutT, bool MERGE = false> __global__ void k
 __global__ void k_bf_table_2048(float2 *tab, const float *grid, const double *mic_x, int M, double unit);
 __global__ void k_beamform_wave_2048(BeamformWaveArgs p);
 template <int NPT, bool ODD> __global__ void k_beamform_wave_ms(BeamformWaveArgs p);   // several sources, forward transforms shared (M <= 8)
-template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bool MERGE, bool CAND = false> __global__ void k_stft_phat_wave(StftPhatArgs p);
+template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bool MERGE, bool CAND = false, bool FUSE = false> __global__ void k_stft_phat_wave(StftPhatArgs p);
+__global__ void k_steer_table(float4 *rows, float2 *q, float *nyq, const float *grid, const double *mic_x, int M, double unit);      // 8-microphone ULA contexts (steer.h)
+__global__ void k_steer_patch(SteerPatchArgs p);
+__global__ void k_steer_synth(SteerSynthArgs p);
 
 __global__ void k_srp_gemm_f32(GemmArgs p);
 template <bool SPLIT, int BN> __global__ void k_srp_gemm_f16(GemmArgs p);

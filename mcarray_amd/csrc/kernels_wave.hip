@@ -18,6 +18,7 @@
 #include "cand_unit.h"
 #include "phat_pairs.h"
 #include "pair_balance.h"
+#include "steer.h"
 
 namespace mca {
 
@@ -399,10 +400,11 @@ __device__ __forceinline__ float wave_sum64(float v)
 // the lane's 8 x (M - 1) sums go into the wave's LDS region (the transform's scratch, free by then) with ds_add_f32 at
 // rank[m] -- every instruction hits 64 different words and the instructions of a wave execute in order, so the sums are
 // formed in a fixed order --, and the region is read back as the row: n_merged instead of (M - 1) * 513 complex values.
-template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bool MERGE, bool CAND = false>
+template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bool MERGE, bool CAND = false, bool FUSE = false>
 __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // launched with 4 waves (256 registers: two waves per SIMD)
 {
     static_assert(!MERGE || (ULA && !PL2 && !NOPHAT && sizeof(OutT) == 2), "the merged index serves the one-plane fp16 rows of a ULA");
+    static_assert(!FUSE || (MERGE && MT == 8 && !POWER), "the steered half spectrum rides in the free words of the 8-microphone merged region");
     constexpr int NP = MT / 2, NOUT = PairOut<MT, ULA>::N;
     constexpr int NRANK = 2 * (MT - 1) * 64 * 4 + 8;                              // u16 entries of the offset table (+ the Nyquist bin's)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -470,7 +472,9 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
         const bool has_frame = f_begin < f_end;
         if (!has_frame && !CAND) continue;          // (candidate-column list mode: the wave still helps to contract the unit's rows below)
         if (has_frame) {
-        const float *base = hist_unit ? p.hist_in + (long long)a * MT * HIST_SAMPLES + lane : p.pcm + (long long)a * p.array_stride + lane;
+        // (FUSE: the lane rides in the loads' offset register -- no 64-bit address per lane and pair)
+        const unsigned lofs = FUSE ? (unsigned)lane : 0u;
+        const float *base = hist_unit ? p.hist_in + (long long)a * MT * HIST_SAMPLES + (FUSE ? 0 : lane) : p.pcm + (long long)a * p.array_stride + (FUSE ? 0 : lane);
         const long long mstride = hist_unit ? (long long)HIST_SAMPLES : p.mic_stride;
         const int fr0 = hist_unit ? 0 : p.frame0;
         float xa[16], xb[16];
@@ -478,7 +482,7 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
             const float *pa = base + (long long)(2 * pr) * mstride + (long long)(fr0 + f) * FFT_H;
             const float *pb = pa + mstride;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { xa[i] = pa[64 * i]; xb[i] = pb[64 * i]; }
+            for (int i = 0; i < 16; ++i) { xa[i] = pa[lofs + 64 * i]; xb[i] = pb[lofs + 64 * i]; }
         };
         // The frames of a run are independent: each run starts at its own offset and wraps around.  Waves that start
         // together then stream different 2 KB pieces of their rows -- with every run starting at its first frame, layouts
@@ -488,9 +492,23 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
         const int rot = p.list ? 0 : (int)((unsigned)(5 * a + 3 * ((int)blockIdx.x * nw + wave)) % (unsigned)nfr);
         auto frame_of = [&](int i) { const int j = i + rot; return f_begin + (j >= nfr ? j - nfr : j); };
         load_pair(frame_of(0), 0);
+        // FUSE: the frame is also steered at the array's predicted DOA bin while its separated spectra are here (steer.h): the
+        // half spectrum Y accumulates over the pairs in the words of the wave's region that the exchange does not use (lane-private
+        // addresses) and leaves for the synthesis kernel with the last pair
+        const float4 *srow = nullptr; const float *snyq = nullptr;
+        float2 *Yl = buf + F1K_SCRATCH + lam;
+        float2 *Qs = wbase + nw * regw + wave * STEER_QWORDS;                     // the steps Q_c[1..7] of the predicted bin
+        if (FUSE) {
+            const int pred = __builtin_amdgcn_readfirstlane(p.bf.pred[a]) + 1;
+            srow = p.bf.rows + (long long)pred * (NP * 64);                      // wave-uniform: the lane rides in the load's offset register
+            snyq = p.bf.nyq + pred * MT;
+            if (lane < STEER_QWORDS) Qs[lane] = p.bf.q[(pred * MT + 2 * (lane / 14) + (lane & 1)) * 8 + (lane % 14) / 2 + 1];      // [pair][s - 1][a, b]
+            wave_lds_fence();
+        }
         for (int fi = 0; fi < nfr; ++fi) {
             const int f = frame_of(fi);
             float2 Xh[MT][8], zn[NP];
+            float2 *yrow = FUSE ? p.bf.Y + ((long long)a * p.total_frames + p.frame0 + f) * STEER_ROW : nullptr;     // (wave-uniform)
             v2f ptime = {0.f, 0.f};                                                // POWER: sum of the squared windowed samples (Parseval)
             bool any_alive = false;                                                // (wave-uniform)
 #pragma unroll
@@ -501,12 +519,12 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                     // history = samples [512 j, 512 j + 1024) of a channel's HIST_SAMPLES)
                     const int j = p.frame0 + f - (p.total_frames - HIST_FRAMES);
                     if (j >= 0) {
-                        float *ha = p.hist_out + ((long long)a * MT + 2 * pr) * HIST_SAMPLES + j * FFT_H + lane;
+                        float *ha = p.hist_out + ((long long)a * MT + 2 * pr) * HIST_SAMPLES + j * FFT_H + (FUSE ? 0 : lane);
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) { ha[64 * i] = xa[i]; ha[HIST_SAMPLES + 64 * i] = xb[i]; }
+                        for (int i = 0; i < 8; ++i) { ha[lofs + 64 * i] = xa[i]; ha[lofs + HIST_SAMPLES + 64 * i] = xb[i]; }
                         if (j == HIST_FRAMES - 1) {
 #pragma unroll
-                            for (int i = 0; i < 8; ++i) { ha[FFT_H + 64 * i] = xa[8 + i]; ha[HIST_SAMPLES + FFT_H + 64 * i] = xb[8 + i]; }
+                            for (int i = 0; i < 8; ++i) { ha[lofs + FFT_H + 64 * i] = xa[8 + i]; ha[lofs + HIST_SAMPLES + FFT_H + 64 * i] = xb[8 + i]; }
                         }
                     }
                 }
@@ -531,8 +549,12 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                     for (int i = 0; i < 16; ++i) z[i] = make_float2(z[i].x * sa, z[i].y * sb);
                 }
                 // the next pair's samples (the run's last step reloads its own) are requested in the middle of the transform
+                // FUSE: the steering base (P_a, P_b)[lam] of the pair, requested AHEAD of the next samples (loads return in order: a wait on
+                // a load behind them would expose their latency)
+                const float4 Bl = FUSE ? (srow + pr * 64)[(unsigned)lane] : make_float4(0.f, 0.f, 0.f, 0.f);
                 fft1024c<false, 3>(z, buf, lane, tab, lc, [&]() {
                     const bool lastp = pr == NP - 1, last = lastp && fi + 1 >= nfr;
+                    if (FUSE) { Yl[64 * STEER_Y_BASE] = make_float2(Bl.x, Bl.y); Yl[64 * (STEER_Y_BASE + 1)] = make_float2(Bl.z, Bl.w); }      // (parked in the lane's own words across the transform's second half)
                     load_pair(last ? f : (lastp ? frame_of(fi + 1) : f), last ? pr : (lastp ? 0 : pr + 1));
                 }, lam);
                 // z[q] = Z[lam + 64 dr16(q)];  the register of bin index s is dr16(s)
@@ -541,7 +563,8 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                 // the partner's j + 4 in slot j: the mirror of bin s is read from slot mate(15 - s).  Lanes 0 and 32 are their own
                 // mirrors -- lane 32: register 15 - s, lane 0: register (16 - s) & 15 -- and put those into the same slots.
                 const float un_a = pb.un_a(), un_b = pb.un_b();                                  // back to the channel's own scale (0: exact zeros)
-                if (MERGE) zn[pr] = make_float2(z[dr16(8)].x * un_a, z[dr16(8)].y * un_b);     // (lane 0's is the Nyquist bin)
+                if (MERGE && !FUSE) zn[pr] = make_float2(z[dr16(8)].x * un_a, z[dr16(8)].y * un_b);     // (lane 0's is the Nyquist bin)
+                if (FUSE) { const float2 n = make_float2(z[dr16(8)].x * un_a, z[dr16(8)].y * un_b); if (pr < NP - 1) Yl[64 * (STEER_Y_ZN + pr)] = n; else zn[pr] = n; }   // (parked behind Y: registers are short below)
                 if (lane == 0) {
                     const float2 n = z[dr16(8)];
                     if (!MERGE) nyq[(f - f_begin) * NP + pr] = make_float2(n.x * un_a, n.y * un_b);
@@ -564,6 +587,8 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                 // z = 2 s X (s: the channel's power of two): |X|^2 > 1e-30 <=> |z|^2 > 4e-30 s^2;  NOPHAT: X = z / (2 s)
                 const float thr_a = PairBalance::thr(4e-30f, pb.na, alive_a), thr_b = PairBalance::thr(4e-30f, pb.nb, alive_b);
                 const float half_a = PairBalance::down(0.5f, pb.na, alive_a), half_b = PairBalance::down(0.5f, pb.nb, alive_b);
+                float4 Bu = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (FUSE) { const float2 ba = Yl[64 * STEER_Y_BASE], bb = Yl[64 * (STEER_Y_BASE + 1)]; Bu = steer_base(make_float4(ba.x, ba.y, bb.x, bb.y), un_a, un_b); }
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     const float2 zk = z[dr16(s)], zm = z[dr16(15 - s < 12 ? 15 - s + 4 : 15 - s - 4)];      // Z[k], Z[1024 - k] (slot mate(15 - s))
@@ -572,8 +597,20 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                     float pwa, pwb;
                     Xh[2 * pr][s] = whiten4<NOPHAT>(a2, pwa, thr_a, half_a);
                     Xh[2 * pr + 1][s] = whiten4<NOPHAT>(b2, pwb, thr_b, half_b);
+                    if (FUSE) {
+                        float2 y = pr == 0 ? make_float2(0.f, 0.f) : Yl[64 * s];
+                        if (s == 0) y = steer_mac<true>(y, a2, b2, Bu, a2, b2);
+                        else { const float4 qq = reinterpret_cast<const float4 *>(Qs)[pr * 7 + s - 1]; y = steer_mac<false>(y, a2, b2, Bu, make_float2(qq.x, qq.y), make_float2(qq.z, qq.w)); }
+                        if (pr < NP - 1) Yl[64 * s] = y;
+                        else yrow[(unsigned)lam + 64 * s] = s == 0 ? steer_dc(y, lane) : y;
+                    }
                 }
             }
+            if (FUSE) {
+#pragma unroll
+                for (int pr = 0; pr < NP - 1; ++pr) zn[pr] = Yl[64 * (STEER_Y_ZN + pr)];
+            }
+            if (FUSE && lane == 0) yrow[FFT_H] = make_float2(steer_nyquist<NP>(zn, snyq), 0.f);
             if (p.dead && lane == 0) p.dead[(long long)a * p.total_frames + p.frame0 + f] = any_alive ? 0 : 1;
             OutT *arow = reinterpret_cast<OutT *>(p.A) + (row_base + f) * (long long)p.a_row_elems;
             if (MERGE) {
@@ -695,6 +732,204 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                 cand_unit<4>(p.cand, li - p.list0, e_unit, reinterpret_cast<unsigned char *>(wbase), tid);
             }
         }
+    }
+}
+
+// --------------------------------------------------------------------------------------
+// Delay-and-sum on the half spectrum of the separated channels (steer.h): table, patch pass, synthesis
+// --------------------------------------------------------------------------------------
+// grid (D + 1, pairs) x 64: thread = lane of the analysis kernel, which holds the bins lam + 64 s.  Row 0: DOA = 0 rad (k_bf_table).
+__global__ __launch_bounds__(64) void k_steer_table(float4 *rows, float2 *q, float *nyq, const float *grid, const double *mic_x, int M, double unit)
+{
+    const int d = blockIdx.x, pr = blockIdx.y, lane = threadIdx.x, lam = lane <= 32 ? lane : 96 - lane;
+    const double doa = d == 0 ? 0.0 : (double)grid[d - 1];
+    const double cd = cos(doa + 1.57079632679489661923);                   // cos(DOA + M_PI/2), Beamformer.cpp:59
+    const double sc = 1.0 / ((double)M * 1024.0);
+    auto phasor = [&](int c, int k, double &cs, double &sn) {
+        double turns = (double)k * (unit * mic_x[c] * cd);                 // k s_c / (2 pi), s_c of Beamformer.cpp:59
+        turns -= rint(turns);
+        sincospi(2.0 * turns, &sn, &cs);
+    };
+    double ca, sa, cb, sb;
+    phasor(2 * pr, lam, ca, sa); phasor(2 * pr + 1, lam, cb, sb);
+    rows[((long long)d * gridDim.y + pr) * 64 + lane] = make_float4((float)(ca * sc), (float)(sa * sc), (float)(cb * sc), (float)(sb * sc));
+    if (lane < 16) {                                                       // the steps P_c[64 s] of the pair's two channels
+        const int c = 2 * pr + (lane >> 3), s = lane & 7;
+        double cs, sn;
+        phasor(c, 64 * s, cs, sn);
+        q[((long long)d * M + c) * 8 + s] = make_float2((float)cs, (float)sn);
+    }
+    if (lane < 2) {                                                        // Im Y[512] is dropped by the CCS inverse: the real part of P_c[512]
+        double cs, sn;
+        phasor(2 * pr + lane, 512, cs, sn);
+        nyq[d * M + 2 * pr + lane] = (float)(cs * sc);
+    }
+}
+
+// grid (workgroups) x 256, 4 waves; wave w of workgroup b takes the frames (4 b + w) + 4 gridDim.x i of the pass, array by array.
+// Per pair the steps of k_stft_phat_wave up to the separated spectra 2 X_a, 2 X_b -- the same transform, balance and mirror exchange,
+// hence the same bits -- and steer_mac / steer_nyquist on them in the same order.
+__global__ __launch_bounds__(256, 2) void k_steer_patch(SteerPatchArgs p)
+{
+    constexpr int NP = 4, MT = 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float2 *tab = reinterpret_cast<float2 *>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float2 *buf = tab + F1K_TWORDS + wave * F1K_SCRATCH;
+    const int npass = p.f1 - p.f0, stride = 4 * (int)gridDim.x;
+    // nothing to do for this workgroup (the usual case behind an analysis that steered ahead): the lanes look at the waves' frames side by side
+    int work = p.all;
+    if (!work) {
+        for (int a = 0; a < p.n_arrays; ++a) {
+            const int pred = p.bf.pred[a];
+            for (int fo = (int)blockIdx.x * 4 + wave + stride * lane; fo < npass; fo += stride * 64)
+                work |= p.doa_bin[(long long)a * p.n_frames + p.f0 + fo] != pred;
+        }
+    }
+    if (!__syncthreads_or(work)) return;
+    f1k_table_init(tab, tid, 256);
+    F1kLane lc;
+    lc.init(lane);
+    __syncthreads();
+    const int lam = lane <= 32 ? lane : 96 - lane;
+    const bool self = (lane & 31) == 0;
+    v2f win[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { win[i].x = p.window[lane + 128 * i]; win[i].y = p.window[lane + 128 * i + 64]; }
+    for (int a = 0; a < p.n_arrays; ++a) {
+        const int pred = __builtin_amdgcn_readfirstlane(p.bf.pred[a]);
+        const bool every = p.all != 0;
+        int missed = 0;
+        for (int fo = (int)blockIdx.x * 4 + wave; fo < npass; fo += stride) {
+            const int f = p.f0 + fo;
+            const int bin = __builtin_amdgcn_readfirstlane(p.doa_bin[(long long)a * p.n_frames + f]);
+            if (bin != pred) ++missed;
+            else if (!every) continue;
+            const float4 *srow = p.bf.rows + (long long)(bin + 1) * (NP * 64);
+            const float2 *qrow = p.bf.q + (long long)(bin + 1) * (MT * 8);            // (wave-uniform)
+            const float *base = p.pcm + (long long)a * p.array_stride + (long long)f * FFT_H;
+            float2 *yrow = p.bf.Y + ((long long)a * p.y_frames + f - p.y_f0) * STEER_ROW;
+            float xa[16], xb[16];
+            auto load_pair = [&](int pr) {
+                const float *pa = base + (long long)(2 * pr) * p.mic_stride, *pb = pa + p.mic_stride;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { xa[i] = pa[(unsigned)lane + 64 * i]; xb[i] = pb[(unsigned)lane + 64 * i]; }
+            };
+            load_pair(0);
+            float2 Y[8], zn[NP];
+#pragma unroll
+            for (int pr = 0; pr < NP; ++pr) {
+                float2 z[16];
+                float4 B;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { z[2 * i] = win_lo(xa[2 * i], xb[2 * i], win[i]); z[2 * i + 1] = win_hi(xa[2 * i + 1], xb[2 * i + 1], win[i]); }
+                float ma = max3abs(z[0].x, z[1].x, z[2].x), mb = max3abs(z[0].y, z[1].y, z[2].y);
+#pragma unroll
+                for (int i = 3; i < 15; i += 2) { ma = max3abs(ma, z[i].x, z[i + 1].x); mb = max3abs(mb, z[i].y, z[i + 1].y); }
+                ma = max2abs(ma, z[15].x); mb = max2abs(mb, z[15].y);
+                const PairBalance pb = pair_balance(ma, mb);
+                if (pb.scaled()) {
+                    const float sa = pb.sa(), sb = pb.sb();
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) z[i] = make_float2(z[i].x * sa, z[i].y * sb);
+                }
+                fft1024c<false, 3>(z, buf, lane, tab, lc, [&]() {
+                    B = (srow + pr * 64)[(unsigned)lane];
+                    if (pr < NP - 1) load_pair(pr + 1);
+                }, lam);
+                const float un_a = pb.un_a(), un_b = pb.un_b();
+                zn[pr] = make_float2(z[dr16(8)].x * un_a, z[dr16(8)].y * un_b);
+                const float4 Bu = steer_base(B, un_a, un_b);
+                // the mirror exchange of k_stft_phat_wave
+                if (lane == 0) {
+                    float2 t[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) t[j] = z[dr16(j)];
+#pragma unroll
+                    for (int j = 8; j < 16; ++j) z[dr16(j < 12 ? j + 4 : j - 4)] = t[(j + 1) & 15];
+                } else if (self) {
+#pragma unroll
+                    for (int j = 8; j < 12; ++j) { const float2 t = z[dr16(j)]; z[dr16(j)] = z[dr16(j + 4)]; z[dr16(j + 4)] = t; }
+                } else {
+#pragma unroll
+                    for (int j = 8; j < 12; ++j) {
+                        float2 &u = z[dr16(j)], &w = z[dr16(j + 4)];
+                        swap_rows32(u.x, w.x); swap_rows32(w.x, u.x);
+                        swap_rows32(u.y, w.y); swap_rows32(w.y, u.y);
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const float2 zk = z[dr16(s)], zm = z[dr16(15 - s < 12 ? 15 - s + 4 : 15 - s - 4)];
+                    const float2 a2 = make_float2(zk.x + zm.x, zk.y - zm.y);                               // 2 X_a
+                    const float2 b2 = make_float2(zk.y + zm.y, zm.x - zk.x);                               // 2 X_b
+                    const float2 y = pr == 0 ? make_float2(0.f, 0.f) : Y[s];
+                    if (s == 0) Y[s] = steer_mac<true>(y, a2, b2, Bu, a2, b2);
+                    else Y[s] = steer_mac<false>(y, a2, b2, Bu, qrow[(2 * pr) * 8 + s], qrow[(2 * pr + 1) * 8 + s]);
+                }
+                wave_lds_fence();
+            }
+#pragma unroll
+            for (int s = 0; s < 8; ++s) yrow[(unsigned)lam + 64 * s] = s == 0 ? steer_dc(Y[s], lane) : Y[s];
+            if (lane == 0) yrow[FFT_H] = make_float2(steer_nyquist<NP>(zn, p.bf.nyq + (bin + 1) * MT), 0.f);
+        }
+        if (missed && lane == 0) { atomicAdd(p.miss, (unsigned long long)missed); if (pred >= 0) atomicAdd(p.miss + 1, (unsigned long long)missed); }   // ([1]: the guard's -- an array without a pick yet misses by construction)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_steer_synth(SteerSynthArgs p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float2 *tab = reinterpret_cast<float2 *>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float2 *buf = tab + F1K_TWORDS + wave * F1K_SCRATCH;
+    f1k_table_init(tab, tid, 256);
+    F1kLane lc;
+    lc.init(lane);
+    __syncthreads();
+    const int a = blockIdx.y;
+    if (p.pred_out && blockIdx.x == 0 && tid == 0) p.pred_out[a] = p.doa_bin[(long long)a * p.n_frames + p.n_frames - 1];      // the array's next call steers here
+    if (p.report && blockIdx.x == 0 && a == 0 && tid == 0) {
+        const unsigned long long tot = p.miss_total[1];
+        p.report[0] = tot - p.miss_total[2];
+        p.miss_total[2] = tot;
+        __hip_atomic_store(&p.report[1], p.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    const int t0 = p.f0 + ((int)blockIdx.x * 4 + wave) * p.ft, t1 = min(t0 + p.ft, p.f1);
+    if (t0 >= t1) return;
+    const float2 *Yb = p.Y + ((long long)a * p.y_frames - p.y_f0) * STEER_ROW;
+    float *ob = p.out + (long long)a * p.n_frames * FFT_H;
+    float carry[8];
+    if (t0 == p.f0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) carry[i] = p.tail_in[(long long)a * FFT_H + lane + 64 * i];
+    }
+    int t = t0 > p.f0 ? t0 - 1 : t0;                                           // (t0 - 1: only its second half counts, the carry into hop t0)
+    float2 yv[8], nv[8];
+    float yn, nn = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) yv[i] = Yb[(long long)t * STEER_ROW + (unsigned)lane + 64 * i];
+    yn = Yb[(long long)t * STEER_ROW + FFT_H].x;
+    for (; t < t1; ++t) {
+        float2 y[16];
+        steer_inverse(y, yv, yn, buf, lane, tab, lc, [&]() {
+            if (t + 1 < t1) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) nv[i] = Yb[(long long)(t + 1) * STEER_ROW + (unsigned)lane + 64 * i];
+                nn = Yb[(long long)(t + 1) * STEER_ROW + FFT_H].x;
+            }
+        });
+        if (t >= t0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ob[(long long)t * FFT_H + (unsigned)lane + 64 * i] = carry[i] + y[dr16(i)].x;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { carry[i] = y[dr16(i + 8)].x; yv[i] = nv[i]; }
+        yn = nn;
+    }
+    if (t1 == p.f1) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) p.tail_out[(long long)a * FFT_H + lane + 64 * i] = carry[i];
     }
 }
 
@@ -908,6 +1143,7 @@ INST_SPW(8, true) INST_SPW(8, false) INST_SPW(4, true) INST_SPW(4, false)
 template __global__ void k_stft_phat_wave<8, true, _Float16, false, false, false, true>(StftPhatArgs);
 template __global__ void k_stft_phat_wave<8, true, _Float16, false, true, false, true>(StftPhatArgs);
 template __global__ void k_stft_phat_wave<4, true, _Float16, false, false, false, true>(StftPhatArgs);
+template __global__ void k_stft_phat_wave<8, true, _Float16, false, false, false, true, false, true>(StftPhatArgs);      // FUSE
 template __global__ void k_stft_phat_wave<4, true, _Float16, false, true, false, true>(StftPhatArgs);
 // list mode of a candidate-column call: two planes, no gate, with the candidate contraction of the unit behind its rows (CAND)
 template __global__ void k_stft_phat_wave<8, true, _Float16, true, false, false, false, true>(StftPhatArgs);

@@ -67,6 +67,44 @@ struct CandArgs {
     float *hist_C; int hist_base;                            // lazy tails: units >= hist_base are rows of hist_C
 };
 
+// Delay-and-sum on the half spectrum (steer.h): k_stft_phat_wave<..., FUSE> steers every frame at the array's PREDICTED bin while it
+// holds the separated spectra, k_steer_patch redoes the frames whose pick came out different, k_steer_synth turns the rows into audio.
+constexpr int STEER_QWORDS = 8 * 7;   // float2 words of a wave's copy of the steps Q_c[1..7] of its array's predicted bin (LDS)
+constexpr int STEER_LDS_ROWS = 13;     // 64-word rows of a wave's region behind the exchange scratch: 8 of Y, 3 of parked Nyquist values, 2 of the parked base
+constexpr int STEER_Y_ZN = 8, STEER_Y_BASE = 11;
+constexpr int STEER_MISS_NUM = 1, STEER_MISS_DEN = 3;   // the guard (api.hip, steer_policy_begin): half of the measured break-even of 0.66 (profiles/r07_miss_share_sweep.log)
+constexpr int STEER_ROW = 520;   // float2 words per row of Y: A[k] = {1, 2, ..., 2, 1} Y[k] / N at bins 0..512, padded to whole 64-byte lines
+struct SteerArgs {
+    const float4 *rows;      // [D + 1][pairs][64 lanes] (P_a, P_b)[lam] / (M N): the base of the lane's bins lam + 64 s (k_steer_table); row 0: DOA 0 rad
+    const float2 *q;         // [D + 1][M][8] P_c[64 s]: their wave-uniform steps
+    const float *nyq;        // [D + 1][M] Re P_c[512] / (M N)
+    const int *pred;         // [arrays] the predicted bin: the array's last pick of the previous call (-1: none yet, the initial DOA)
+    float2 *Y;               // [arrays][total_frames][STEER_ROW]
+};
+// k_steer_patch: the frames whose pick is not the predicted bin (all = 1: every frame -- the analysis of this call did not steer) through
+// the same routine at their final bins, one wave per frame, a fixed grid striding over the call's frames; counts the misses
+constexpr int STEER_PATCH_WGS = 512;      // k_steer_patch: a fixed grid (two workgroups per CU) strides over the frames
+struct SteerPatchArgs {
+    const float *pcm; long long array_stride, mic_stride;
+    int n_arrays, n_frames;  // n_frames: the call's (rows of Y, of doa_bin)
+    int f0, f1;              // the frames of this pass
+    const float *window;
+    const int *doa_bin;      // [arrays][n_frames] final picks
+    SteerArgs bf;
+    int y_f0, y_frames;      // Y holds the frames y_f0 ... y_f0 + y_frames - 1 of every array
+    int all;
+    unsigned long long *miss;   // [0] running total of frames whose pick was not the predicted bin, [1] those of arrays that had a prediction (the guard's)
+};
+// k_steer_synth: rows of Y -> inverse transform -> overlap-add; grid (runs / 4, arrays) x 256, one wave per run of ft frames (it transforms
+// the frame in front of its run once more for the carry).  The workgroup (0, a) of the call's LAST pass leaves the array's last pick as the next call's prediction.
+struct SteerSynthArgs {
+    const float2 *Y; int n_frames, f0, f1, ft, y_f0, y_frames;
+    float *out;              // [arrays][n_frames * hop]
+    const float *tail_in; float *tail_out;    // [arrays][hop] the carry into hop f0 / out of frame f1 - 1 (the stream's, or the one between two passes)
+    const int *doa_bin; int *pred_out;        // pred_out: NULL unless this is the call's last pass
+    unsigned long long *report; unsigned long long seq; unsigned long long *miss_total;   // last pass: the call's missed frames and its number, to page-locked memory
+};
+
 struct StftPhatArgs {
     const float *pcm;
     long long array_stride, mic_stride;
@@ -105,6 +143,7 @@ struct StftPhatArgs {
     // list mode of a candidate-column call: the workgroup that wrote a unit's four rows contracts them at the unit's columns (cand_unit.h) --
     // k_srp_cand's work without its launch
     int cand_on; CandArgs cand;
+    SteerArgs bf;            // k_stft_phat_wave<..., FUSE>
 };
 
 __device__ __forceinline__ void store_a(float *row, const StftPhatArgs &, int cidx, float2 v)
