@@ -3,25 +3,126 @@
 // correlation, first-max argmax, the author's DOA smoothing (#else branch :502-504), the per-frame DSPONE hook
 // processParametrisation (:406-567) and setProbability at caller-given angles (:569-631, the weights of the particle
 // filter's observation model).  The particle filter itself (:456-473) is a stochastic DSPONE component and is out of
-// scope.  The time-domain TemporalGCCBinauralLocalisation of the same header is out of scope
-// (SURVEY 2 row 12).
+// scope.
 //
 // Two ways in, each with its own state on the GPU: process() (chunked PCM, the batched stream path, float) and
 // processParametrisation() (one frame of CCS spectra, double).  An object driven through both keeps two states;
 // setProbability reads the one of the path the object used last.
+//
+// mca::TemporalGCCBinauralLocalisation -- the time-domain 2-microphone localiser of the same reference header
+// (BinauralLocalisation.h:43-185; BinauralLocalisation.cpp:66-314): nd delay pairs, each a (2 nd + 1)-lag cross-correlation
+// of the raw frame, the first maximum of the normalised index -> DOA in degrees, the power gate, and
+// _currentDOA = 0.5 _currentDOA + 0.5 DOA.  The same two ways in (process(): float PCM, batched; processParametrisation():
+// one frame of doubles), each with its own state.  setProbability stays the base class's uniform value, as in the reference.
 #ifndef MCA_HIP_BINAURALLOCALISATION_H
 #define MCA_HIP_BINAURALLOCALISATION_H
 #include <cmath>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "mcadefs.h"
 
+#include "../mcarray_hip.h"
 #include "HipContext.h"
 #include "SoundLocalisationImpl.h"
 #include "microhponeArrayHelpers.h"
 
 namespace mca {
+
+class TemporalGCCBinauralLocalisation : public SoundLocalisationImpl {
+public:
+    // usePowerFloor = false (an extension, as FreqGCCBinauralLocalisation's flag): every frame passes the gate, power = logPower
+    TemporalGCCBinauralLocalisation(int sampleRate, ArrayDescription microphonePositions, bool usePowerFloor = true)
+        : SoundLocalisationImpl(microphonePositions)
+    {
+        if (microphonePositions.size() != 2) throw MCArrayException("TemporalGCCBinauralLocalisation needs an ArrayDescription with 2 microphones");
+        std::vector<double> xyz = microphonePositions.xyz();
+        mca_hip_tgcc_config cfg = mca_hip_tgcc_config();
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.device = 0;
+        cfg.sample_rate = sampleRate;
+        for (int j = 0; j < 6; ++j) cfg.mic_xyz[j / 3][j % 3] = xyz[static_cast<size_t>(j)];
+        cfg.use_power_floor = usePowerFloor ? 1 : 0;
+        cfg.max_arrays = 1;
+        if (mca_hip_tgcc_create(&cfg, &_ctx) != MCA_HIP_OK) throw MCArrayException(std::string("mca_hip_tgcc_create: ") + mca_hip_tgcc_last_error(nullptr));
+        check(mca_hip_tgcc_get_geometry(_ctx, &_windowSize, &_hop, &_ndelays));
+        _currentDOA.reset(new BaseType[1]);
+        _prob.reset(new BaseType[1]);
+        _currentDOA[0] = 0; _prob[0] = -1;                   // BinauralLocalisation.cpp:86-89
+    }
+    virtual ~TemporalGCCBinauralLocalisation() { mca_hip_tgcc_destroy(_ctx); }
+    TemporalGCCBinauralLocalisation(const TemporalGCCBinauralLocalisation &) = delete;
+    TemporalGCCBinauralLocalisation &operator=(const TemporalGCCBinauralLocalisation &) = delete;
+
+    int getWindowSize() const { return _windowSize; }
+    int getAnalysisLength() const { return _windowSize; }
+    int getNumberOfDelays() const { return _ndelays; }
+    int getNumberOfChannels() const { return 2; }
+
+    // chunked PCM in (2 channels); fires setDOA(degrees, prob, power, 1) once per completed frame that passes the gate
+    // (BinauralLocalisation.cpp:189-190).  Returns the number of frames completed by this chunk.
+    template <typename Tin> int process(const std::vector<Tin *> &in, int nSamples)
+    {
+        const int W = _windowSize, hop = _hop;
+        for (int c = 0; c < 2; ++c)
+            for (int i = 0; i < nSamples; ++i) _pending[c].push_back(static_cast<float>(in[static_cast<size_t>(c)][i]));
+        const int have = static_cast<int>(_pending[0].size());
+        const int F = have >= W ? (have - W) / hop + 1 : 0;
+        if (F == 0) return 0;
+        const size_t L = static_cast<size_t>(F - 1) * static_cast<size_t>(hop) + static_cast<size_t>(W);
+        std::vector<float> pcm(2 * L), doa(static_cast<size_t>(F)), prob(static_cast<size_t>(F)), power(static_cast<size_t>(F));
+        std::vector<unsigned char> voiced(static_cast<size_t>(F));
+        for (int c = 0; c < 2; ++c) std::copy(_pending[c].begin(), _pending[c].begin() + static_cast<long>(L), pcm.begin() + static_cast<long>(L) * c);
+        check(mca_hip_tgcc_frames_host(_ctx, pcm.data(), 1, F, doa.data(), prob.data(), voiced.data(), power.data(), nullptr, nullptr));
+        for (int t = 0; t < F; ++t) {
+            _currentDOA[0] = doa[static_cast<size_t>(t)]; _prob[0] = prob[static_cast<size_t>(t)];
+            if (voiced[static_cast<size_t>(t)] && _ptrCallback) _ptrCallback->setDOA(_currentDOA, _prob, power[static_cast<size_t>(t)], 1);
+        }
+        for (int c = 0; c < 2; ++c) _pending[c].erase(_pending[c].begin(), _pending[c].begin() + static_cast<long>(F) * hop);
+        return F;
+    }
+
+    // the SignalVector / SignalVector16s overloads the reference's callers use (test_mcarray.cpp:618; mcadefs.h:86-88)
+    int process(const SignalVector &in, int nSamples)
+    {
+        std::vector<const BaseType *> pi;
+        for (size_t c = 0; c < in.size(); ++c) pi.push_back(in[c].get());
+        return process(pi, nSamples);
+    }
+    int process(const SignalVector16s &in, int nSamples)
+    {
+        std::vector<const BaseType16s *> pi;
+        for (size_t c = 0; c < in.size(); ++c) pi.push_back(in[c].get());
+        return process(pi, nSamples);
+    }
+
+    // The per-frame hook (BinauralLocalisation.cpp:134-192): analysisFrames[0..1] = the raw frames, double[analysisLength]
+    // (not modified).  The state advances on every frame; setDOA(degrees, prob, power, 1) fires on a voiced frame when a
+    // callback is set (the reference would dereference a null one).
+    virtual void processParametrisation(std::vector<double *> &analysisFrames, int analysisLength, std::vector<double *> &dataChannels,
+                                        int dataLength)
+    {
+        (void)dataChannels; (void)dataLength;
+        if (analysisLength != getAnalysisLength()) throw MCArrayException("analysisLength does not match the module's window size");
+        if (analysisFrames.size() < 2) throw MCArrayException("processParametrisation needs 2 analysis frames");
+        const double *fr[2] = {analysisFrames[0], analysisFrames[1]};
+        int voiced = 0;
+        double doa = 0, prob = 0, power = 0;
+        check(mca_hip_tgcc_process_frame(_ctx, fr, analysisLength, &voiced, &doa, &prob, &power, nullptr, nullptr));
+        _currentDOA[0] = doa; _prob[0] = prob;
+        if (voiced && _ptrCallback) _ptrCallback->setDOA(_currentDOA, _prob, power, 1);
+    }
+
+private:
+    void check(int rc) const
+    {
+        if (rc != MCA_HIP_OK) throw MCArrayException(std::string("libmcarray_hip: ") + mca_hip_tgcc_last_error(_ctx));
+    }
+    mca_hip_tgcc_ctx *_ctx = nullptr;
+    int _windowSize = 0, _hop = 0, _ndelays = 0;
+    std::vector<float> _pending[2];
+};
 
 class FreqGCCBinauralLocalisation : public SoundLocalisationImpl {
 public:

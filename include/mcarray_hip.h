@@ -410,6 +410,50 @@ long long mca_hip_mb_state_size(const mca_hip_mb_ctx *ctx);
 int mca_hip_mb_state_save(mca_hip_mb_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_mb_state_load(mca_hip_mb_ctx *ctx, const void *blob, long long blob_bytes);
 
+/* ---- TemporalGCCBinauralLocalisation (2 microphones, time domain) -------------
+ * Replaces mca::TemporalGCCBinauralLocalisation(int sampleRate, ArrayDescription) (include/mcarray/BinauralLocalisation.h:43)
+ * and its per-frame hook processParametrisation (src/mcarray/BinauralLocalisation.cpp:134-192), in double.  Frames of
+ * W = (int)(2 * (0.075 * fs)) raw samples at hop W / 2; nd = (int)(distance(0,1) * fs / 346.1) delay pairs, each a
+ * (2 nd + 1)-lag cross-correlation divided by the two deviations and summed in magnitude; + a small triangle, max-min
+ * normalisation, first maximum -> DOA = samples2Degrees - 90 (degrees); the power gate of setPowerFloor / logPower;
+ * _currentDOA = 0.5 _currentDOA + 0.5 DOA.  The [BUILD-DEFINES] decisions are listed in DESIGN.md.
+ * Supported: 2 <= nd <= 32 and sample_rate <= 96000 (MCA_HIP_ERR_INVALID_ARGUMENT at create otherwise). */
+typedef struct mca_hip_tgcc_ctx mca_hip_tgcc_ctx;
+typedef struct {
+    int struct_size;
+    int device;
+    int sample_rate;
+    double mic_xyz[2][3];    /* metres */
+    int use_power_floor;     /* 1 = the reference (3 s floor estimation, then the gate); 0 = every frame voiced, power = logPower */
+    int max_arrays;          /* independent module objects (streams) this context holds state for, <= 65535 */
+} mca_hip_tgcc_config;
+int  mca_hip_tgcc_create(const mca_hip_tgcc_config *cfg, mca_hip_tgcc_ctx **out);
+void mca_hip_tgcc_destroy(mca_hip_tgcc_ctx *ctx);
+const char *mca_hip_tgcc_last_error(const mca_hip_tgcc_ctx *ctx);
+int  mca_hip_tgcc_reset(mca_hip_tgcc_ctx *ctx, void *stream);     /* every array and the frame hook back to a new module */
+/* window W (= analysis length), hop W / 2 and the number of delay pairs nd; any pointer may be NULL */
+int  mca_hip_tgcc_get_geometry(const mca_hip_tgcc_ctx *ctx, int *window, int *hop, int *nd);
+/* n_frames frames of arrays 0..n_arrays-1: array a, channel ch starts at pcm_dev + a * array_stride + ch * ch_stride and
+ * holds (n_frames - 1) * hop + W samples; frame f starts at sample f * hop.  Each array continues its own state.
+ * Per frame (all [arrays][F]): doa_deg = _currentDOA[0] after the frame (degrees), prob = _prob[0], voiced = 1 where setDOA
+ * fires, power = the value handed to setDOA (during the floor estimation: the floor so far), delay_idx = the first-max
+ * pair index, -1 on gated frames.  index [arrays][F][nd] = the normalised index of every frame (voiced or not).  Every
+ * output except doa_deg may be NULL. */
+int mca_hip_tgcc_frames_dev(mca_hip_tgcc_ctx *ctx, const float *pcm_dev, long long array_stride, long long ch_stride,
+                            int n_arrays, int n_frames, float *doa_deg_dev, float *prob_dev, unsigned char *voiced_dev,
+                            float *power_dev, int *delay_idx_dev, double *index_dev, void *stream);
+/* the same from host memory: pcm [arrays][2][(n_frames - 1) * hop + W] */
+int mca_hip_tgcc_frames_host(mca_hip_tgcc_ctx *ctx, const float *pcm, int n_arrays, int n_frames, float *doa_deg, float *prob,
+                             unsigned char *voiced, float *power, int *delay_idx, double *index);
+/* the per-frame hook processParametrisation: frames[0..1] = the two channels' double[length] analysis frames, length == W;
+ * its own state (separate from every array's).  Outputs as above, in double; any may be NULL. */
+int mca_hip_tgcc_process_frame(mca_hip_tgcc_ctx *ctx, const double *const *frames, int length, int *voiced, double *doa_deg,
+                               double *prob, double *power, int *delay_idx, double *index);
+/* checkpoint / resume as mca_hip_state_*: _currentDOA, _prob and the power-floor estimation of every array and of the hook */
+long long mca_hip_tgcc_state_size(const mca_hip_tgcc_ctx *ctx);
+int mca_hip_tgcc_state_save(mca_hip_tgcc_ctx *ctx, void *blob, long long blob_bytes);
+int mca_hip_tgcc_state_load(mca_hip_tgcc_ctx *ctx, const void *blob, long long blob_bytes);
+
 /* ---- MVDR-style beamformer with a per-bin spatial covariance (BASELINE.json configs[3]) ---------
  * [BUILD-DEFINES -- NO REFERENCE COUNTERPART]: the reference's only beamformer is the delay-and-sum of
  * mca::Beamformer::processFrame (src/mcarray/Beamformer.cpp:51-71); this module keeps its interface shape

@@ -81,6 +81,17 @@ class MvdrConfig(C.Structure):
     ]
 
 
+class TgccConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("device", C.c_int),
+        ("sample_rate", C.c_int),
+        ("mic_xyz", C.c_double * 6),
+        ("use_power_floor", C.c_int),
+        ("max_arrays", C.c_int),
+    ]
+
+
 # every symbol include/mcarray_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("mca_hip_create", C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -165,6 +176,20 @@ SYMBOLS = [
     ("mca_hip_mb_state_size", C.c_longlong, [C.c_void_p]),
     ("mca_hip_mb_state_save", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
     ("mca_hip_mb_state_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
+    ("mca_hip_tgcc_create", C.c_int, [C.POINTER(TgccConfig), C.POINTER(C.c_void_p)]),
+    ("mca_hip_tgcc_destroy", None, [C.c_void_p]),
+    ("mca_hip_tgcc_last_error", C.c_char_p, [C.c_void_p]),
+    ("mca_hip_tgcc_reset", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mca_hip_tgcc_get_geometry", C.c_int, [C.c_void_p, c_ip, c_ip, c_ip]),
+    ("mca_hip_tgcc_frames_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_tgcc_frames_host", C.c_int,
+     [C.c_void_p, c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_void_p, c_fp, c_ip, c_dp]),
+    ("mca_hip_tgcc_process_frame", C.c_int, [C.c_void_p, C.POINTER(c_dp), C.c_int, c_ip, c_dp, c_dp, c_dp, c_ip, c_dp]),
+    ("mca_hip_tgcc_state_size", C.c_longlong, [C.c_void_p]),
+    ("mca_hip_tgcc_state_save", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
+    ("mca_hip_tgcc_state_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
     ("mca_hip_mvdr_state_size", C.c_longlong, [C.c_void_p]),
     ("mca_hip_mvdr_state_save", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
     ("mca_hip_mvdr_state_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),

@@ -611,6 +611,126 @@ class MultibandBinarualLocalisation(_StateBlob):
         return dict(doa=doa, prob=prob, voiced=voiced, power=power, band_idx=bi, energy_in_doa=eid, band_corr=bc)
 
 
+class TemporalGCCBinauralLocalisation(_StateBlob):
+    _STATE = "tgcc"
+    """mca::TemporalGCCBinauralLocalisation(int sampleRate, ArrayDescription) (BinauralLocalisation.h:43): nd delay pairs of
+    time-domain cross-correlations over raw frames of W = (int)(2 * 0.075 fs) samples at hop W / 2, DOA in degrees.
+    use_power_floor=False (an extension, as FreqGCC's flag) voices every frame.  process() (PCM, batched stream path, float in)
+    and process_frame() (one frame of doubles, the per-frame hook) keep separate states."""
+
+    def __init__(self, sample_rate, mic_positions, use_power_floor=True, max_arrays=1, device=0):
+        self._lib = _lib.load()
+        xyz = _xyz(mic_positions)
+        if len(xyz) != 2:
+            raise MCArrayHipError("TemporalGCCBinauralLocalisation needs exactly 2 microphones")
+        cfg = _lib.TgccConfig()
+        cfg.struct_size = C.sizeof(_lib.TgccConfig)
+        cfg.device = device
+        cfg.sample_rate = sample_rate
+        for j, v in enumerate(xyz.reshape(-1)):
+            cfg.mic_xyz[j] = float(v)
+        cfg.use_power_floor = int(use_power_floor)
+        cfg.max_arrays = max_arrays
+        h = C.c_void_p()
+        rc = self._lib.mca_hip_tgcc_create(C.byref(cfg), C.byref(h))
+        if rc != 0:
+            raise MCArrayHipError("mca_hip_tgcc_create failed (%d): %s" % (rc, self._lib.mca_hip_tgcc_last_error(None).decode()))
+        self.h = h
+        w, hop, nd = C.c_int(), C.c_int(), C.c_int()
+        self._check(self._lib.mca_hip_tgcc_get_geometry(h, C.byref(w), C.byref(hop), C.byref(nd)))
+        self.W, self.hop, self.nd = w.value, hop.value, nd.value
+        self.max_arrays = max_arrays
+        self.callback = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._lib.mca_hip_tgcc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise MCArrayHipError("libmcarray_hip error %d: %s" % (rc, self._lib.mca_hip_tgcc_last_error(self.h).decode()))
+
+    def set_callback(self, cb):
+        self.callback = cb
+
+    def reset(self):
+        self._check(self._lib.mca_hip_tgcc_reset(self.h, None))
+
+    def get_window_size(self):
+        return self.W
+
+    get_analysis_length = get_window_size
+
+    def num_frames(self, n_samples):
+        return (n_samples - self.W) // self.hop + 1 if n_samples >= self.W else 0
+
+    def process(self, pcm, want_index=False):
+        """pcm float32 [A][2][(F-1)*hop + W] -> dict(doa [A][F] degrees, prob, voiced, power, delay_idx[, index [A][F][nd]]);
+        the callback fires per voiced frame of array 0 as setDOA(degrees, prob, power, 1) (BinauralLocalisation.cpp:189-190)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 2:
+            pcm = pcm[None]
+        A, ch, L = pcm.shape
+        F = self.num_frames(L)
+        if ch != 2 or F < 1 or (F - 1) * self.hop + self.W != L:
+            raise MCArrayHipError("pcm must be [A][2][(F-1)*hop + W]")
+        doa = np.empty((A, F), dtype=np.float32)
+        prob = np.empty((A, F), dtype=np.float32)
+        voiced = np.empty((A, F), dtype=np.uint8)
+        power = np.empty((A, F), dtype=np.float32)
+        k = np.empty((A, F), dtype=np.int32)
+        index = np.empty((A, F, self.nd), dtype=np.float64) if want_index else None
+        fp = _lib.c_fp
+        self._check(self._lib.mca_hip_tgcc_frames_host(
+            self.h, pcm.ctypes.data_as(fp), A, F, doa.ctypes.data_as(fp), prob.ctypes.data_as(fp),
+            voiced.ctypes.data_as(C.c_void_p), power.ctypes.data_as(fp), k.ctypes.data_as(_lib.c_ip),
+            index.ctypes.data_as(_lib.c_dp) if want_index else None))
+        if self.callback is not None:
+            for t in range(F):
+                if voiced[0, t]:
+                    self.callback(np.array([float(doa[0, t])]), np.array([float(prob[0, t])]), float(power[0, t]), 1)
+        return dict(doa=doa, prob=prob, voiced=voiced, power=power, delay_idx=k, index=index)
+
+    def process_dev(self, pcm, stream=None, want_index=False):
+        """device-pointer form: pcm a torch float32 CUDA tensor [A][2][(F-1)*hop + W] -> dict of torch tensors as process()."""
+        import torch
+        A, ch, L = pcm.shape
+        F = self.num_frames(L)
+        if ch != 2 or F < 1 or (F - 1) * self.hop + self.W != L or not pcm.is_contiguous() or pcm.dtype != torch.float32:
+            raise MCArrayHipError("pcm must be a contiguous float32 tensor [A][2][(F-1)*hop + W]")
+        dev = pcm.device
+        out = dict(doa=torch.empty((A, F), dtype=torch.float32, device=dev), prob=torch.empty((A, F), dtype=torch.float32, device=dev),
+                   voiced=torch.empty((A, F), dtype=torch.uint8, device=dev), power=torch.empty((A, F), dtype=torch.float32, device=dev),
+                   delay_idx=torch.empty((A, F), dtype=torch.int32, device=dev))
+        out["index"] = torch.empty((A, F, self.nd), dtype=torch.float64, device=dev) if want_index else None
+        self._check(self._lib.mca_hip_tgcc_frames_dev(
+            self.h, C.c_void_p(pcm.data_ptr()), 2 * L, L, A, F, C.c_void_p(out["doa"].data_ptr()), C.c_void_p(out["prob"].data_ptr()),
+            C.c_void_p(out["voiced"].data_ptr()), C.c_void_p(out["power"].data_ptr()), C.c_void_p(out["delay_idx"].data_ptr()),
+            C.c_void_p(out["index"].data_ptr()) if want_index else None, stream))
+        return out
+
+    def process_frame(self, left, right):
+        """processParametrisation (BinauralLocalisation.cpp:134-192) for one frame of double[W] per channel -> dict(voiced, doa
+        (degrees), prob, power, delay_idx, index); the callback fires on a voiced frame as setDOA(degrees, prob, power, 1)."""
+        fr = [np.ascontiguousarray(left, dtype=np.float64), np.ascontiguousarray(right, dtype=np.float64)]
+        if fr[0].shape != (self.W,) or fr[1].shape != (self.W,):
+            raise MCArrayHipError("process_frame needs two frames of W = %d samples" % self.W)
+        ptrs = (_lib.c_dp * 2)(fr[0].ctypes.data_as(_lib.c_dp), fr[1].ctypes.data_as(_lib.c_dp))
+        v, k = C.c_int(), C.c_int()
+        doa, prob, power = C.c_double(), C.c_double(), C.c_double()
+        index = np.empty(self.nd)
+        self._check(self._lib.mca_hip_tgcc_process_frame(self.h, ptrs, self.W, C.byref(v), C.byref(doa), C.byref(prob), C.byref(power),
+                                                         C.byref(k), index.ctypes.data_as(_lib.c_dp)))
+        r = dict(voiced=bool(v.value), doa=doa.value, prob=prob.value, power=power.value, delay_idx=k.value, index=index)
+        if self.callback is not None and r["voiced"]:
+            self.callback(np.array([r["doa"]]), np.array([r["prob"]]), r["power"], 1)
+        return r
+
+
 class MvdrBeamformer(_StateBlob):
     _STATE = "mvdr"
     """Frequency-domain beamformer with a per-bin spatial covariance (BASELINE.json configs[3]; SURVEY A.9).

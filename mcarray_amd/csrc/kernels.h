@@ -74,5 +74,8 @@ __global__ void k_mvdr_analyse_1024(MvdrAnalyseArgs p, int fpb);
 __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
 template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
+__global__ void k_tgcc_frames(TgccFrameArgs p);
+__global__ void k_tgcc_frame_f64(const double *Lp, const double *Rp, int W, int nd, int rem, double *res, double *index);
+__global__ void k_tgcc_gate(TgccGateArgs p);
 
 }  // namespace mca

@@ -471,4 +471,31 @@ struct MvdrSynthArgs {
     float *out;               // [streams][n_frames * N/2]
 };
 
+// ---- TemporalGCCBinauralLocalisation (kernels_tgcc.hip) ----
+constexpr int TGCC_MAX_ND = 32;          // delay pairs the kernels support (4 nd - 1 <= 127 lags)
+constexpr int TGCC_RPAD_FRONT = 64;      // zeros in front of channel 1 (lags down to -2 nd)
+constexpr int TGCC_RPAD_BACK = 80;       // and behind its W rounded up to 8 (the last tile reads up to 2 nd + 13 past it)
+constexpr int TGCC_RES = 6;              // per frame: DOA (deg), log-likelihood, pick, logPower, energy of W, of the floor's last part
+constexpr int TGCC_STATE = 8;            // per array: _currentDOA, _prob, _powerFloor, samples consumed, _noiseEstimated, 3 spare
+// doubles of LDS scratch in front of the staged channels: body sums [8][16], wave partials [4][16], totals [16],
+// divisors [32], index [32], channel statistics [8], |c| [nd][2nd+1]; even, so that the channels behind it start 16-byte aligned
+inline __host__ __device__ int tgcc_frame_ws_doubles(int nd) { return (8 * 16 + 4 * 16 + 16 + 2 * TGCC_MAX_ND + 8 + nd * (2 * nd + 1) + 1) & ~1; }
+
+struct TgccFrameArgs {
+    const float *pcm;
+    long long array_stride, ch_stride;
+    int n_frames, W, hop, nd, rem;  // rem = needed % W: the length of the floor estimation's last, partial frame
+    double *res;                    // [arrays][n_frames][TGCC_RES]
+    double *index;                  // [arrays][n_frames][nd] normalised index (may be NULL)
+};
+
+struct TgccGateArgs {
+    const double *res;
+    double *state;                  // [arrays][TGCC_STATE]
+    int n_arrays, n_frames, W, needed, use_floor;
+    float *doa_deg, *prob, *power;  // [arrays][n_frames], may be NULL
+    unsigned char *voiced; int *delay_idx;
+    double *out_f64;                // frame hook: [n_frames][5] {voiced, doa, prob, power, pick} (may be NULL)
+};
+
 }  // namespace mca
