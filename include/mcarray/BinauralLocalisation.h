@@ -2,8 +2,10 @@
 // (include/mcarray/BinauralLocalisation.h:188-247; src/mcarray/BinauralLocalisation.cpp:320-631): smoothed
 // correlation, first-max argmax, the author's DOA smoothing (#else branch :502-504), the per-frame DSPONE hook
 // processParametrisation (:406-567) and setProbability at caller-given angles (:569-631, the weights of the particle
-// filter's observation model).  The particle filter itself (:456-473) is a stochastic DSPONE component and is out of
-// scope.
+// filter's observation model).  The particle filter the reference is compiled with (:38, :456-473, :536-558) is opt-in:
+// useParticleFilter() attaches the DOA tracker of mcarray_hip.h (mca_hip_gcc2_tracker_attach; DSPONE's filter engine is
+// not available, DESIGN.md "The DOA tracker" defines ours), and then _currentDOA is the filter's estimate, the callback also
+// fires while a track coasts through a pause, and getSourceCounter() counts the tracks.  Without it the class is unchanged.
 //
 // Two ways in, each with its own state on the GPU: process() (chunked PCM, the batched stream path, float) and
 // processParametrisation() (one frame of CCS spectra, double).  An object driven through both keeps two states;
@@ -148,9 +150,26 @@ public:
     int getMaxLatency() const { return 1 << _order; }
     int getNumberOfChannels() const { return 2; }
 
+    // Not in the reference (which is compiled with the filter, BinauralLocalisation.cpp:38): switch the DOA from the #else
+    // branch's smoothing to the particle filter.  Call before the first frame, once.  nInject: particles re-drawn uniformly per
+    // update (0 = nParticles / 20, -1 = none); sigmaInit / sigmaStep in radians (0 = the grid step).
+    void useParticleFilter(unsigned long long seed = 0, int nParticles = 500, int nInject = 0, double sigmaInit = 0.0, double sigmaStep = 0.0)
+    {
+        mca_hip_gcc2_tracker_config cfg = mca_hip_gcc2_tracker_config();
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.n_particles = nParticles; cfg.n_inject = nInject; cfg.seed = seed;
+        cfg.sigma_init = sigmaInit; cfg.sigma_step = sigmaStep;
+        _ctx->check(mca_hip_gcc2_tracker_attach(_ctx->get(), &cfg));
+        _tracked = true;
+    }
+    bool usesParticleFilter() const { return _tracked; }
+    // _sourceCounter (BinauralLocalisation.cpp:458): the number of the current or last track of the path used last; 0 without a filter
+    int getSourceCounter() const { return _sourceCounter; }
+
     // chunked PCM in (2 channels); fires the callback once per completed frame: setDOA(degrees, prob, power, 1) (:521)
     template <typename Tin> int process(const std::vector<Tin *> &in, int nSamples)
     {
+        if (_tracked) return processTracked(in, nSamples);
         const int N = getWindowSize(), hop = N / 2;
         for (int c = 0; c < 2; ++c)
             for (int i = 0; i < nSamples; ++i) _pending[c].push_back(static_cast<float>(in[static_cast<size_t>(c)][i]));
@@ -192,7 +211,8 @@ public:
         double doa = 0, prob = 0, power = 0;
         _ctx->check(mca_hip_gcc2_process_frame(_ctx->get(), fr, analysisLength, &voiced, &doa, &prob, &power, nullptr, nullptr));
         _framePathLast = true;
-        if (!voiced) return;
+        if (_tracked) _ctx->check(mca_hip_gcc2_tracker_get_particles(_ctx->get(), -1, nullptr, nullptr, &_sourceCounter));
+        if (!voiced) return;                                     // (with the filter: fired, 1 voiced or 2 a coasting track, :545-548)
         _currentDOA[0] = doa; _prob[0] = prob;
         _ptrCallback->setDOA(toDegrees(_currentDOA, 1), _prob, power, 1);
     }
@@ -220,6 +240,35 @@ public:
     }
 
 private:
+    // process() with the particle filter: setDOA on every frame whose fired is 1 (voiced, :521) or 2 (coasting, :548)
+    template <typename Tin> int processTracked(const std::vector<Tin *> &in, int nSamples)
+    {
+        const int N = getWindowSize(), hop = N / 2;
+        for (int c = 0; c < 2; ++c)
+            for (int i = 0; i < nSamples; ++i) _pending[c].push_back(static_cast<float>(in[static_cast<size_t>(c)][i]));
+        const int have = static_cast<int>(_pending[0].size());
+        const int F = have >= N ? (have - N) / hop + 1 : 0;
+        if (F == 0) return 0;
+        const size_t L = static_cast<size_t>(F + 1) * static_cast<size_t>(hop), nf = static_cast<size_t>(F);
+        std::vector<float> pcm(2 * L), doa(nf), prob(nf), power(nf, 0.f);
+        std::vector<int> idx(nf), track(nf);
+        std::vector<unsigned char> fired(nf);
+        for (int c = 0; c < 2; ++c) std::copy(_pending[c].begin(), _pending[c].begin() + static_cast<long>(L), pcm.begin() + static_cast<long>(L) * c);
+        _ctx->check(mca_hip_gcc2_tracked_frames_host(_ctx->get(), pcm.data(), 1, F, idx.data(), doa.data(), prob.data(), fired.data(),
+                                                     track.data(), nullptr));
+        _framePathLast = false;
+        if (_usePowerFloor) _ctx->check(mca_hip_copy_gate(_ctx->get(), nullptr, power.data()));
+        for (size_t t = 0; t < nf; ++t) {
+            _sourceCounter = track[t];
+            if (!fired[t]) continue;
+            _currentDOA[0] = doa[t]; _prob[0] = prob[t];
+            if (_ptrCallback) _ptrCallback->setDOA(toDegrees(_currentDOA, 1), _prob, static_cast<double>(power[t]), 1);
+        }
+        for (int c = 0; c < 2; ++c) _pending[c].erase(_pending[c].begin(), _pending[c].begin() + static_cast<long>(F) * hop);
+        _lastArgmax = idx;
+        return F;
+    }
+
     static constexpr float _frameRate = 0.075f;      // BinauralLocalisation.h:196
     const int _order;
     bool _usePowerFloor = true;
@@ -227,6 +276,8 @@ private:
     std::vector<float> _pending[2];
     std::vector<int> _lastArgmax;
     bool _framePathLast = false;       // processParametrisation ran after the last process() (setProbability reads its state)
+    bool _tracked = false;             // useParticleFilter() was called
+    int _sourceCounter = 0;
 };
 
 }  // namespace mca

@@ -1,6 +1,7 @@
 // mca::SoundLocalisationImpl -- base holding the callback pointer, current DOA/prob and the power-floor
 // bookkeeping (reference include/mcarray/SoundLocalisationImpl.h:44-87).  The particle-filter members of the
-// reference are out of scope.
+// reference are not members here: the filter runs on the GPU behind FreqGCCBinauralLocalisation::useParticleFilter()
+// (BinauralLocalisation.h), the one localiser the reference runs it for.
 #ifndef MCA_HIP_SOUNDLOCALISATIONIMPL_H
 #define MCA_HIP_SOUNDLOCALISATIONIMPL_H
 #include "ArrayDescription.h"

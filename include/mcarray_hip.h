@@ -182,7 +182,7 @@ int mca_hip_reserve(mca_hip_ctx *ctx, int n_arrays, int n_frames);
  * Version 3 blobs end with the FreqGCC frame hook's part (mca_hip_gcc2_process_frame), 8 * (D + 8) bytes: its smoothed
  * correlation double[D], then 8 doubles _powerFloor, samples consumed for it, _noiseEstimated, _silenceFramesCounter,
  * _corrMemoryFactor, _doaMemoryFactor, _currentDOA, _prob.  Version 1 and 2 blobs (without that part) still load and leave
- * the frame hook as a newly built module. */
+ * the frame hook as a newly built module.  A context with a DOA tracker (mca_hip_gcc2_tracker_attach) writes version 4. */
 long long mca_hip_state_size(const mca_hip_ctx *ctx);
 int mca_hip_state_save(mca_hip_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_state_load(mca_hip_ctx *ctx, const void *blob, long long blob_bytes);
@@ -287,8 +287,8 @@ void mca_hip_graph_destroy(mca_hip_graph *g);
  * correlation smoothing corr = (1-mu) corr + mu prev with mu = 0 on a stream's first frame and
  * 0.8f afterwards (:445-448, :523), first-max argmax and the author's deterministic DOA smoothing
  * DOA = m DOA + (1-m) angle, m = 0 then 0.6f (the #else branch :502-504; the particle filter of
- * :456-473 is a stochastic DSPONE component and stays out of scope), and setProbability of the
- * previous DOA (:454, :569-631).  With use_power_floor = 1 the gate of :387-404 / :425-434 runs on the GPU (3 s of floor
+ * :456-473, which the reference is compiled with, is the DOA tracker below: mca_hip_gcc2_tracker_attach),
+ * and setProbability of the previous DOA (:454, :569-631).  With use_power_floor = 1 the gate of :387-404 / :425-434 runs on the GPU (3 s of floor
  * estimation, then a frame fires when its FFTLogPower exceeds the floor + 6 dB): the recursions only see the frames that
  * fired, the others repeat the outputs of the last fired frame (argmax -1, DOA 0, prob -1 before the first), and
  * mca_hip_copy_gate returns voiced[A][F] / power[A][F] of the call.
@@ -326,6 +326,46 @@ int mca_hip_gcc2_process_frame(mca_hip_ctx *ctx, const double *const *frames, in
                                double *doa_rad, double *prob, double *power, int *argmax, double *corr);
 /* setProbability, as mca_hip_gcc2_set_probability, on the frame hook's correlation */
 int mca_hip_gcc2_frame_set_probability(mca_hip_ctx *ctx, const double *doas, double *probs, int n);
+
+/* ---- the particle-filter DOA tracker of FreqGCCBinauralLocalisation (BinauralLocalisation.cpp:38 USE_PARTICLE_FILTER) ----
+ * As the reference is compiled, _currentDOA is the estimate of a 500-particle filter seeded at the first voiced frame
+ * (:457-465), updated on every voiced frame (:473) and through up to windowsToDecay gated-out frames, which still fire the
+ * callback (:536-548), and dropped after that (:551-558).  The filter engine is DSPONE's and not available: what the reference
+ * pins is kept (500 particles, the observation model = setProbability of the particles on the smoothed correlation, the
+ * prediction's clamp to [-pi/2, pi/2], the control flow), the rest is defined in DESIGN.md ("The DOA tracker") so that the
+ * result is a pure function of (seed, array index, track number, update number) and the rows: counter-based integer random
+ * numbers, integer weights, systematic resampling, a few particles re-injected uniformly per update.  It runs on the GPU, one
+ * wave per array, inside the stream call and the frame hook; tests/gcc2_tracker_twin.py restates it and matches bit for bit.
+ * Opt-in: a context without a tracker behaves, and writes state blobs, exactly as before. */
+typedef struct {
+    int struct_size;
+    int n_particles;            /* 0 = 500 (BinauralLocalisation.cpp:463); 16..1024 */
+    int n_inject;               /* particles re-drawn uniformly over [-pi/2, pi/2] per update: 0 = n_particles / 20, -1 = none, < n_particles */
+    unsigned long long seed;
+    double sigma_init, sigma_step;   /* radians: spread around the argmax at seeding, random-walk step per update; 0 = the grid step */
+} mca_hip_gcc2_tracker_config;
+/* n_mics == 2 only; allocates the state of max_arrays arrays and of the frame hook; a second attach is refused.  From then on
+ * mca_hip_gcc2_process_frame runs the tracker on the hook's state (`voiced` becomes fired: 1 voiced, 2 a coasting track whose
+ * callback fires, 0 nothing; doa_rad / prob the tracked ones), mca_hip_gcc2_frames_* are refused (call the tracked form),
+ * mca_hip_reset forgets every track (track numbers start at 1 again), mca_hip_gcc2_set_probability* work as before, and state
+ * blobs are version 4 = version 3 + the tracker's part (its configuration, checked on load; per array and for the hook alive,
+ * track, update number, DOA, prob, the particles).  Blobs of version <= 3 load and leave every track unstarted. */
+int mca_hip_gcc2_tracker_attach(mca_hip_ctx *ctx, const mca_hip_gcc2_tracker_config *cfg);
+/* mca_hip_gcc2_frames_dev with the tracker in place of the DOA recursion.  All outputs [A][F]; corr_dev [A][F][D]; only
+ * doa_rad_dev is required.  Per frame: fired_dev 1 = voiced (seeds a track if none is alive, then DOA = updateFilter()),
+ * 2 = gated out with a live track and fewer than windowsToDecay silent frames (DOA = updateFilter() on the unchanged row),
+ * 0 = nothing (the track is dropped once the silence counter reaches windowsToDecay).  doa_rad_dev = float(_currentDOA),
+ * prob_dev = float(setProbability(DOA before the frame)) of the last voiced frame, track_dev = the number of the array's
+ * current or last track (_sourceCounter; 0 before the first).  mca_hip_copy_gate returns voiced / power of the call.
+ * Cannot be recorded into a HIP graph (MCA_HIP_ERR_UNSUPPORTED). */
+int mca_hip_gcc2_tracked_frames_dev(mca_hip_ctx *ctx, const float *pcm_dev, long long array_stride, long long mic_stride,
+                                    int n_arrays, int n_frames, int *argmax_dev, float *doa_rad_dev, float *prob_dev,
+                                    unsigned char *fired_dev, int *track_dev, float *corr_dev, void *stream);
+int mca_hip_gcc2_tracked_frames_host(mca_hip_ctx *ctx, const float *pcm, int n_arrays, int n_frames, int *argmax,
+                                     float *doa_rad, float *prob, unsigned char *fired, int *track, float *corr);
+/* the particles double[n_particles] (radians), whether a track is alive and its number, of array `array_index` of the stream
+ * state, or of the frame hook with array_index = -1.  Any output may be NULL.  Synchronises the device. */
+int mca_hip_gcc2_tracker_get_particles(mca_hip_ctx *ctx, int array_index, double *particles, int *alive, int *track);
 
 /* ---- binaural masking (FastBinauralMasking) --------------------------------------------- */
 typedef struct mca_hip_mask_ctx mca_hip_mask_ctx;

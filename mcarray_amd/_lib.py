@@ -81,6 +81,17 @@ class MvdrConfig(C.Structure):
     ]
 
 
+class Gcc2TrackerConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("n_particles", C.c_int),
+        ("n_inject", C.c_int),
+        ("seed", C.c_ulonglong),
+        ("sigma_init", C.c_double),
+        ("sigma_step", C.c_double),
+    ]
+
+
 class TgccConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -134,6 +145,13 @@ SYMBOLS = [
     ("mca_hip_gcc2_process_frame", C.c_int,
      [C.c_void_p, C.POINTER(c_dp), C.c_int, c_ip, c_dp, c_dp, c_dp, c_ip, c_dp]),
     ("mca_hip_gcc2_frame_set_probability", C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int]),
+    ("mca_hip_gcc2_tracker_attach", C.c_int, [C.c_void_p, C.POINTER(Gcc2TrackerConfig)]),
+    ("mca_hip_gcc2_tracked_frames_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_gcc2_tracked_frames_host", C.c_int,
+     [C.c_void_p, c_fp, C.c_int, C.c_int, c_ip, c_fp, c_fp, C.c_void_p, c_ip, c_fp]),
+    ("mca_hip_gcc2_tracker_get_particles", C.c_int, [C.c_void_p, C.c_int, c_dp, c_ip, c_ip]),
     ("mca_hip_mask_create", C.c_int, [C.POINTER(MaskConfig), C.POINTER(C.c_void_p)]),
     ("mca_hip_mask_destroy", None, [C.c_void_p]),
     ("mca_hip_mask_last_error", C.c_char_p, [C.c_void_p]),

@@ -249,6 +249,66 @@ class Context:
         self._check(self._lib.mca_hip_gcc2_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
                                                       ptr(corr), stream))
 
+    # ---- the particle-filter DOA tracker of the 2-microphone path ----
+    def gcc2_tracker_attach(self, seed=0, n_particles=0, n_inject=0, sigma_init=0.0, sigma_step=0.0):
+        """mca_hip_gcc2_tracker_attach: from now on the tracked calls below replace gcc2_frames_*, and gcc2_process_frame runs the
+        tracker on the frame hook's state.  0 = the defaults (500 particles, n_particles / 20 injected, sigmas = the grid step);
+        n_inject = -1: none."""
+        cfg = _lib.Gcc2TrackerConfig()
+        cfg.struct_size = C.sizeof(_lib.Gcc2TrackerConfig)
+        cfg.n_particles, cfg.n_inject, cfg.seed = int(n_particles), int(n_inject), int(seed)
+        cfg.sigma_init, cfg.sigma_step = float(sigma_init), float(sigma_step)
+        self._check(self._lib.mca_hip_gcc2_tracker_attach(self.h, C.byref(cfg)))
+        self.tracked = True
+        self.n_particles = int(n_particles) or 500
+
+    def gcc2_tracked_frames_host(self, pcm, want_corr=False):
+        """pcm float32 [A][2][(F+1)*hop] -> dict(argmax, doa (tracked, rad), prob, fired (1 voiced, 2 coasting, 0 nothing), track
+        [A][F], corr [A][F][D][, voiced, power])"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 2:
+            pcm = pcm[None]
+        A, M, L = pcm.shape
+        F = L // self.hop - 1
+        if M != 2 or F < 1 or (F + 1) * self.hop != L:
+            raise MCArrayHipError("pcm must be [A][2][(F+1)*hop]")
+        idx = np.empty((A, F), dtype=np.int32)
+        doa = np.empty((A, F), dtype=np.float32)
+        prob = np.empty((A, F), dtype=np.float32)
+        fired = np.empty((A, F), dtype=np.uint8)
+        track = np.empty((A, F), dtype=np.int32)
+        corr = np.empty((A, F, self.D), dtype=np.float32) if want_corr else None
+        fp = _lib.c_fp
+        self._check(self._lib.mca_hip_gcc2_tracked_frames_host(
+            self.h, pcm.ctypes.data_as(fp), A, F, idx.ctypes.data_as(_lib.c_ip), doa.ctypes.data_as(fp), prob.ctypes.data_as(fp),
+            fired.ctypes.data_as(C.c_void_p), track.ctypes.data_as(_lib.c_ip), corr.ctypes.data_as(fp) if want_corr else None))
+        res = dict(argmax=idx, doa=doa, prob=prob, fired=fired, track=track, corr=corr)
+        if self.use_power_floor:
+            voiced = np.empty((A, F), dtype=np.uint8)
+            power = np.empty((A, F), dtype=np.float32)
+            self._check(self._lib.mca_hip_copy_gate(self.h, voiced.ctypes.data_as(C.c_void_p), power.ctypes.data_as(fp)))
+            res["voiced"] = voiced
+            res["power"] = power
+        return res
+
+    def gcc2_tracked_frames_dev(self, pcm, n_frames, doa_rad, argmax=None, prob=None, fired=None, track=None, corr=None, stream=None):
+        """mca_hip_gcc2_tracked_frames_dev: pcm torch float32 cuda tensor [A][2][>= (F+1)*hop]; outputs preallocated cuda tensors
+        doa_rad / prob float32, argmax / track int32, fired uint8 [A][F], corr float32 [A][F][D] (all but doa_rad optional)."""
+        A, M, L = pcm.shape
+        if M != 2 or not pcm.is_contiguous():
+            raise MCArrayHipError("pcm must be a contiguous [A][2][L] tensor")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(self._lib.mca_hip_gcc2_tracked_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
+                                                              ptr(fired), ptr(track), ptr(corr), stream))
+
+    def gcc2_tracker_particles(self, array_index=0):
+        """-> dict(particles float64 [n_particles] (rad), alive, track) of array `array_index`; -1: of the frame hook"""
+        x = np.empty(getattr(self, "n_particles", 500))
+        alive, track = C.c_int(0), C.c_int(0)
+        self._check(self._lib.mca_hip_gcc2_tracker_get_particles(self.h, int(array_index), x.ctypes.data_as(_lib.c_dp), C.byref(alive),
+                                                                 C.byref(track)))
+        return dict(particles=x, alive=bool(alive.value), track=track.value)
+
     def gcc2_set_probability(self, doas, array_index=0):
         """setProbability (BinauralLocalisation.cpp:569-631) at the angles `doas` (radians) on the smoothed correlation the last
         gcc2_frames_* call left for array `array_index` -> float64 [n]"""
@@ -275,7 +335,12 @@ class Context:
         corr = np.empty(self.D)
         self._check(self._lib.mca_hip_gcc2_process_frame(self.h, arr, frames.shape[1], C.byref(v), C.byref(doa), C.byref(prob),
                                                          C.byref(power), C.byref(i), corr.ctypes.data_as(_lib.c_dp)))
-        return dict(voiced=bool(v.value), doa=doa.value, prob=prob.value, power=power.value, argmax=i.value, corr=corr)
+        r = dict(voiced=bool(v.value), doa=doa.value, prob=prob.value, power=power.value, argmax=i.value, corr=corr)
+        if getattr(self, "tracked", False):      # with a tracker `voiced` carries fired: 1 voiced, 2 a coasting track, 0 nothing
+            r["voiced"] = v.value == 1
+            r["fired"] = v.value
+            r["track"] = self.gcc2_tracker_particles(-1)["track"]
+        return r
 
     def gcc2_frame_set_probability(self, doas):
         """setProbability on the frame hook's correlation (gcc2_process_frame) -> float64 [n]"""
@@ -463,17 +528,23 @@ class FreqGCCBinauralLocalisation:
     (BinauralLocalisation.h:191), deterministic part: smoothed GCC-PHAT correlation, first-max argmax,
     DOA smoothing and setProbability.  The reference's grid is 3 degrees (BinauralLocalisation.cpp:328).
     process() (PCM, batched stream path) and process_frame() (one frame of CCS spectra, the per-frame hook) keep separate
-    states; set_probability() reads the one of the path used last."""
+    states; set_probability() reads the one of the path used last.
+    particle_filter: None, or a dict of Context.gcc2_tracker_attach's arguments ({} = the defaults): the DOA then comes from the
+    particle filter the reference is compiled with (BinauralLocalisation.cpp:38), process() / process_frame() also return `fired`
+    and `track`, and the callback fires on every frame whose fired is 1 or 2 (a track coasting through a pause, :536-548)."""
 
     FRAME_SECONDS = 0.075        # _frameRate (BinauralLocalisation.h:196)
 
     def __init__(self, sample_rate, mic_positions, use_power_floor=False, doa_step_deg=3.0, fft_size=None,
-                 srp_precision=SRP_FP32, max_arrays=1, device=0):
+                 srp_precision=SRP_FP32, max_arrays=1, device=0, particle_filter=None):
         if fft_size is None:
             fft_size = 1 << calculate_order_from_sample_rate(sample_rate, self.FRAME_SECONDS)
         self.ctx = Context(sample_rate, mic_positions, fft_size, doa_step_deg, 1, use_power_floor, srp_precision, max_arrays, device)
         if self.ctx.M != 2:
             raise MCArrayHipError("FreqGCCBinauralLocalisation needs exactly 2 microphones")
+        self.tracked = particle_filter is not None
+        if self.tracked:
+            self.ctx.gcc2_tracker_attach(**particle_filter)
         self.callback = None
         self._frame_path_last = False
 
@@ -483,11 +554,11 @@ class FreqGCCBinauralLocalisation:
     def process(self, pcm, want_corr=False):
         """-> dict(argmax, doa, prob[, corr][, voiced, power]); the callback fires per frame of array 0 that passed the gate
         as setDOA(degrees, prob, power, 1) (BinauralLocalisation.cpp:521)."""
-        r = self.ctx.gcc2_frames_host(pcm, want_corr)
+        r = self.ctx.gcc2_tracked_frames_host(pcm, want_corr) if self.tracked else self.ctx.gcc2_frames_host(pcm, want_corr)
         self._frame_path_last = False
         if self.callback is not None:
             for t in range(r["doa"].shape[1]):
-                if "voiced" in r and not r["voiced"][0, t]:
+                if (not r["fired"][0, t]) if self.tracked else ("voiced" in r and not r["voiced"][0, t]):
                     continue
                 self.callback(np.array([np.rad2deg(float(r["doa"][0, t]))]), np.array([r["prob"][0, t]]),
                               float(r["power"][0, t]) if "power" in r else 0.0, 1)
@@ -498,7 +569,7 @@ class FreqGCCBinauralLocalisation:
         prob, power, argmax, corr); the callback fires on a voiced frame as setDOA(degrees, prob, power, 1) (:521)."""
         r = self.ctx.gcc2_process_frame(np.stack([np.asarray(left, dtype=np.float64), np.asarray(right, dtype=np.float64)]))
         self._frame_path_last = True
-        if self.callback is not None and r["voiced"]:
+        if self.callback is not None and (r["fired"] if self.tracked else r["voiced"]):
             self.callback(np.array([np.rad2deg(r["doa"])]), np.array([r["prob"]]), r["power"], 1)
         return r
 

@@ -159,6 +159,14 @@ struct mca_hip_ctx {
     unsigned char *d_g2_reset = nullptr;    // [rows] per fired frame: the memory factors are zero (silence rule)
     int *d_g2_post0 = nullptr;              // [max_arrays] first frame of the call at which the floor estimate exists
     int *d_silence = nullptr;               // [max_arrays] _silenceFramesCounter (BinauralLocalisation.cpp:326), stream state
+    // the DOA tracker (mca_hip_gcc2_tracker_attach; kernels_gcc2_track.hip): slots 0 .. max_arrays - 1 belong to the stream state,
+    // slot max_arrays to the frame hook
+    bool tracked = false;
+    mca_hip_gcc2_tracker_config trk{};      // as resolved by attach (no zeros left)
+    double *d_trk_x = nullptr, *d_trk_sd = nullptr; int *d_trk_si = nullptr;   // [slots][N] particles, [slots][2] DOA / prob, [slots][4] alive / track / upd
+    int *d_trk_sil = nullptr;               // [max_arrays] the silence counters before the call (k_gcc2_compact overwrites d_silence)
+    float *d_trk_corr = nullptr; int *d_trk_idx = nullptr; size_t trk_rows = 0;   // the rows / argmaxes of a call whose caller did not ask for them
+    double *d_trk_res = nullptr;            // [4] what the frame hook's launch returns: DOA, prob, fired (the first byte of [2]), track (an int in [3])
     // workspace
     unsigned long long ws_gen = 0;          // bumped whenever a workspace buffer is reallocated: recorded graphs hold the old pointers
     std::vector<mca_hip_graph *> graphs;   // live graphs of this context (orphaned by mca_hip_destroy)
@@ -253,6 +261,7 @@ void free_ctx(mca_hip_ctx *c)
     F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
     F(c->d_E[0]); F(c->d_E[1]); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_doa[0]); F(c->d_doa[1]); F(c->d_vdone[0]); F(c->d_vdone[1]); F(c->d_g2_vidx); F(c->d_g2_nv); F(c->d_g2_rad); F(c->d_g2_prob);
     F(c->d_g2_reset); F(c->d_g2_post0); F(c->d_silence);
+    F(c->d_trk_x); F(c->d_trk_sd); F(c->d_trk_si); F(c->d_trk_sil); F(c->d_trk_corr); F(c->d_trk_idx); F(c->d_trk_res);
     F(c->d_rstats); F(c->d_gate_state);
     for (int i = 0; i < 2; ++i) { F(c->d_hist_pcm[i]); F(c->d_hist_C[i]); F(c->d_ehist[i]); }
     if (c->h_probe) (void)hipHostFree(c->h_probe);
@@ -1196,6 +1205,19 @@ int mca_hip_get_doa_grid(const mca_hip_ctx *c, float *out)
     return MCA_HIP_OK;
 }
 
+// the DOA tracker as mca_hip_gcc2_tracker_attach leaves it: no track anywhere, _currentDOA = 0, _prob = -1
+static int trk_init_state(mca_hip_ctx *c, hipStream_t st)
+{
+    const size_t slots = (size_t)c->cfg.max_arrays + 1;
+    std::vector<double> sd(slots * 2);
+    for (size_t i = 0; i < slots; ++i) { sd[i * 2] = 0.0; sd[i * 2 + 1] = -1.0; }
+    HIP_TRY(c, hipMemsetAsync(c->d_trk_x, 0, slots * c->trk.n_particles * 8, st));
+    HIP_TRY(c, hipMemsetAsync(c->d_trk_si, 0, slots * 4 * 4, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_trk_sd, sd.data(), slots * 2 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return MCA_HIP_OK;
+}
+
 int mca_hip_reset(mca_hip_ctx *c, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
@@ -1225,6 +1247,7 @@ int mca_hip_reset(mca_hip_ctx *c, void *stream)
     c->steer_spec = true; c->steer_lost = false; c->steer_seq_seen = c->steer_seq;              // (reports still in flight belong to the old streams)
     c->gcc2_frames_done = 0;
     c->g2f = G2FrameState();                                                              // the frame hook as a newly built module
+    if (c->tracked) { const int rc = trk_init_state(c, st); if (rc) return rc; }          // every track forgotten: track numbers start at 1 again
     return init_last_state(c, st);
 }
 
@@ -1238,6 +1261,7 @@ struct StateHeader {
 };
 constexpr unsigned STATE_MAGIC = 0x4d434153u;   // "MCAS"
 constexpr int STATE_VERSION = 3;                // 2: + _silenceFramesCounter per array; 3: + the FreqGCC frame hook (frame_part_bytes)
+constexpr int STATE_VERSION_TRACKED = 4;        // 3 + the DOA tracker's part (tracker_part_bytes), written by contexts with a tracker only
 
 unsigned delays_hash(const mca_hip_ctx *c)
 {
@@ -1265,6 +1289,23 @@ std::vector<StatePart> state_parts(mca_hip_ctx *c)
 size_t frame_part_bytes(const mca_hip_ctx *c) { return (size_t)c->D * 8 + sizeof(G2FrameState); }
 static_assert(sizeof(G2FrameState) == 8 * sizeof(double), "G2FrameState is the 8 doubles of the blob");
 
+// the part a version-4 blob ends with: the tracker's configuration, then for the max_arrays arrays and the frame hook
+// alive / track / upd / 0 as int[4], DOA / prob as double[2], the particles double[N] (three arrays, in this order)
+struct TrackerBlobHead { int n_particles, n_inject; unsigned long long seed; double sigma_init, sigma_step; };
+static_assert(sizeof(TrackerBlobHead) == 32, "TrackerBlobHead is 32 bytes of the blob");
+std::vector<StatePart> tracker_parts(const mca_hip_ctx *c)
+{
+    const size_t slots = (size_t)c->cfg.max_arrays + 1;
+    return {{c->d_trk_si, slots * 16}, {c->d_trk_sd, slots * 16}, {c->d_trk_x, slots * c->trk.n_particles * 8}};
+}
+size_t tracker_part_bytes(const mca_hip_ctx *c)
+{
+    if (!c->tracked) return 0;
+    size_t n = sizeof(TrackerBlobHead);
+    for (const StatePart &p : tracker_parts(c)) n += p.bytes;
+    return n;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -1273,7 +1314,7 @@ long long mca_hip_state_size(const mca_hip_ctx *c)
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     long long n = sizeof(StateHeader) + (long long)sizeof(G2FrameState);
     for (const StatePart &p : state_parts(const_cast<mca_hip_ctx *>(c))) n += (long long)p.bytes;
-    return n;
+    return n + (long long)tracker_part_bytes(c);
 }
 
 int mca_hip_state_save(mca_hip_ctx *c, void *blob, long long blob_bytes)
@@ -1287,11 +1328,16 @@ int mca_hip_state_save(mca_hip_ctx *c, void *blob, long long blob_bytes)
         if (rc) return rc;
     }
     HIP_TRY(c, hipDeviceSynchronize());
-    StateHeader h{STATE_MAGIC, STATE_VERSION, c->M, c->D, c->S, c->H, c->cfg.max_arrays, c->cfg.use_power_floor, delays_hash(c), c->gcc2_frames_done};
+    StateHeader h{STATE_MAGIC, c->tracked ? STATE_VERSION_TRACKED : STATE_VERSION, c->M, c->D, c->S, c->H, c->cfg.max_arrays, c->cfg.use_power_floor, delays_hash(c), c->gcc2_frames_done};
     unsigned char *out = static_cast<unsigned char *>(blob);
     std::memcpy(out, &h, sizeof(h)); out += sizeof(h);
     for (const StatePart &p : state_parts(c)) { HIP_TRY(c, hipMemcpy(out, p.ptr, p.bytes, hipMemcpyDeviceToHost)); out += p.bytes; }
-    std::memcpy(out, &c->g2f, sizeof(G2FrameState));
+    std::memcpy(out, &c->g2f, sizeof(G2FrameState)); out += sizeof(G2FrameState);
+    if (c->tracked) {
+        const TrackerBlobHead th{c->trk.n_particles, c->trk.n_inject, c->trk.seed, c->trk.sigma_init, c->trk.sigma_step};
+        std::memcpy(out, &th, sizeof(th)); out += sizeof(th);
+        for (const StatePart &p : tracker_parts(c)) { HIP_TRY(c, hipMemcpy(out, p.ptr, p.bytes, hipMemcpyDeviceToHost)); out += p.bytes; }
+    }
     return MCA_HIP_OK;
 }
 
@@ -1303,12 +1349,27 @@ int mca_hip_state_load(mca_hip_ctx *c, const void *blob, long long blob_bytes)
     std::memcpy(&h, blob, sizeof(h));
     // version 1 blobs end before the _silenceFramesCounter part (the change of version 2): they load with the counters at zero;
     // version 1 and 2 blobs end before the frame hook's part (the change of version 3): they load with a fresh frame hook
-    if (h.magic != STATE_MAGIC || h.version < 1 || h.version > STATE_VERSION) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "not a state blob of this library version");
+    // version 4 = version 3 + the DOA tracker's part: only a context with the same tracker loads it; older blobs load into a
+    // context with a tracker and leave every track unstarted
+    if (h.magic != STATE_MAGIC || h.version < 1 || h.version > STATE_VERSION_TRACKED) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "not a state blob of this library version");
     if (h.M != c->M || h.D != c->D || h.S != c->S || h.H != c->H || h.max_arrays != c->cfg.max_arrays || h.use_floor != c->cfg.use_power_floor ||
         h.delays_hash != delays_hash(c))
         return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with a different configuration");
+    if (h.version == STATE_VERSION_TRACKED && !c->tracked)
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with a DOA tracker (mca_hip_gcc2_tracker_attach first)");
+    if (h.version == STATE_VERSION_TRACKED) {      // the tracker's configuration first: nothing is loaded from a blob that does not fit
+        long long at = sizeof(StateHeader) + sizeof(G2FrameState);
+        for (const StatePart &p : state_parts(c)) at += (long long)p.bytes;
+        TrackerBlobHead th;
+        if (blob_bytes < at + (long long)sizeof(th)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob is truncated");
+        std::memcpy(&th, static_cast<const unsigned char *>(blob) + at, sizeof(th));
+        if (th.n_particles != c->trk.n_particles || th.n_inject != c->trk.n_inject || th.seed != c->trk.seed ||
+            th.sigma_init != c->trk.sigma_init || th.sigma_step != c->trk.sigma_step)
+            return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with a different DOA tracker configuration");
+    }
     const long long short_by = (h.version == 1 ? (long long)c->cfg.max_arrays * 4 : 0) +         // bytes of the parts an older blob lacks
-                               (h.version < 3 ? (long long)frame_part_bytes(c) : 0);
+                               (h.version < 3 ? (long long)frame_part_bytes(c) : 0) +
+                               (h.version < STATE_VERSION_TRACKED ? (long long)tracker_part_bytes(c) : 0);
     if (blob_bytes < mca_hip_state_size(c) - short_by) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob is truncated");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipDeviceSynchronize());
@@ -1318,8 +1379,17 @@ int mca_hip_state_load(mca_hip_ctx *c, const void *blob, long long blob_bytes)
         if (h.version < 3 && p.ptr == c->d_g2f_corr[c->g2f_cur]) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
         HIP_TRY(c, hipMemcpy(p.ptr, in, p.bytes, hipMemcpyHostToDevice)); in += p.bytes;
     }
-    if (h.version >= 3) std::memcpy(&c->g2f, in, sizeof(G2FrameState));
+    if (h.version >= 3) { std::memcpy(&c->g2f, in, sizeof(G2FrameState)); in += sizeof(G2FrameState); }
     else c->g2f = G2FrameState();
+    if (c->tracked) {
+        if (h.version == STATE_VERSION_TRACKED) {
+            in += sizeof(TrackerBlobHead);          // (checked above)
+            for (const StatePart &p : tracker_parts(c)) { HIP_TRY(c, hipMemcpy(p.ptr, in, p.bytes, hipMemcpyHostToDevice)); in += p.bytes; }
+        } else {
+            const int rc = trk_init_state(c, nullptr);
+            if (rc) return rc;
+        }
+    }
     c->gcc2_frames_done = h.gcc2_frames_done;
     c->hist_pending = false;                      // (a blob holds the exact state)
     return MCA_HIP_OK;
@@ -2455,17 +2525,61 @@ int mca_hip_host_unregister(void *p)
     return MCA_HIP_OK;
 }
 
-int mca_hip_gcc2_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
-                            int n_arrays, int n_frames, int *argmax, float *doa_rad, float *prob, float *corr, void *stream)
+// what the tracked call (mca_hip_gcc2_tracked_frames_dev) adds to the stream call: the tracker's outputs
+struct Gcc2TrackOut { float *doa_rad, *prob; unsigned char *fired; int *track; };
+
+// the launch of k_gcc2_track: SLOTS = particles per lane (8 up to 512 particles, 16 up to 1024)
+extern "C++" template <typename TC>
+static void launch_gcc2_track(mca_hip_ctx *c, Gcc2TrackArgs &ta, hipStream_t st)
+{
+    ta.grid = c->d_grid; ta.step = c->step; ta.D = c->D;
+    ta.N = c->trk.n_particles; ta.n_inject = c->trk.n_inject; ta.seed = c->trk.seed;
+    const int slots = ta.N <= 512 ? 8 : 16, Dl = (ta.D + 1) & ~1;
+    ta.slice_bytes = (unsigned)(((size_t)slots * 64 * 16 + (size_t)Dl * (sizeof(TC) + 4) + 15) / 16 * 16);
+    ta.sigma_init = c->trk.sigma_init; ta.sigma_step = c->trk.sigma_step;
+    ta.x = c->d_trk_x; ta.sd = c->d_trk_sd; ta.si = c->d_trk_si;
+    const dim3 g((ta.n_arrays + GCC2_TRACK_WAVES - 1) / GCC2_TRACK_WAVES), b(64 * GCC2_TRACK_WAVES);
+    const size_t smem = (size_t)ta.slice_bytes * GCC2_TRACK_WAVES;      // at most 2 x 17.9 KB
+    if (slots == 8) hipLaunchKernelGGL((k_gcc2_track<TC, 8>), g, b, smem, st, ta);
+    else hipLaunchKernelGGL((k_gcc2_track<TC, 16>), g, b, smem, st, ta);
+}
+
+// mca_hip_gcc2_frames_dev, and with `trk` the tracked call: the same kernels up to the smoothed rows and their argmaxes, then
+// k_gcc2_track instead of the outputs of the scan's DOA recursion
+static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+                            int n_arrays, int n_frames, int *argmax, float *doa_rad, float *prob, float *corr, void *stream,
+                            const Gcc2TrackOut *trk)
 {
     int rc = check_stream_args(c, pcm, array_stride, mic_stride, n_arrays, n_frames);
     if (rc) return rc;
     if (c->M != 2) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the 2-microphone GCC path needs a context with n_mics == 2");
     if (c->Dp > 192) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "the 2-microphone GCC path supports up to 192 steering delays");
-    if (!argmax) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "argmax_dev is NULL");
+    if (!argmax && !trk) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "argmax_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
+    if (trk) {
+        if (!trk->doa_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (c->capturing || (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
+            return fail(c, MCA_HIP_ERR_UNSUPPORTED, "the tracked call cannot be recorded into a HIP graph");
+        // the rows and argmaxes of the call, where the caller does not take them
+        const size_t rows = (size_t)n_arrays * n_frames;
+        if ((!corr || !argmax) && rows > c->trk_rows) {
+            if (c->d_trk_corr) (void)hipFree(c->d_trk_corr);
+            if (c->d_trk_idx) (void)hipFree(c->d_trk_idx);
+            c->d_trk_corr = nullptr; c->d_trk_idx = nullptr; c->trk_rows = 0;
+            HIP_TRY(c, hipMalloc((void **)&c->d_trk_corr, rows * c->D * 4));
+            HIP_TRY(c, hipMalloc((void **)&c->d_trk_idx, rows * 4));
+            c->trk_rows = rows;
+        }
+        if (!argmax) argmax = c->d_trk_idx;
+    }
     if (c->prec == MCA_HIP_SRP_ADAPTIVE) set_call_planes(c, 2);      // the 2-microphone path always runs the exact split
-    if ((rc = run_correlation_map(c, pcm, array_stride, mic_stride, n_arrays, n_frames, st))) return rc;
+    // the tracked call plans its contraction as one K range whatever the batch (plan_gemm): the rows of an array, and so its track,
+    // then do not depend on how many arrays run beside it.  (The K range of two microphones is short: the split buys little.)
+    if (trk) c->plan_rows = 1LL << 40;
+    rc = run_correlation_map(c, pcm, array_stride, mic_stride, n_arrays, n_frames, st);
+    if (trk) c->plan_rows = 0;
+    if (rc) return rc;
     Gcc2ScanArgs ga{};
     ga.C = c->ws().d_C; ga.c_planes = c->ws().c_planes; ga.c_plane_stride = c->ws().c_plane; ga.n_frames = n_frames; ga.Dp = c->Dp; ga.D = c->D;
     // frames per chunk: every chunk re-reads 160 warm-up frames (recursion + DOA smoothing), so long chunks are cheaper;
@@ -2479,6 +2593,7 @@ int mca_hip_gcc2_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_st
     ga.corr_in = c->d_E[c->e_cur]; ga.corr_out = c->d_E[c->e_cur ^ 1];
     ga.doa_in = c->d_doa[c->doa_cur]; ga.doa_out = c->d_doa[c->doa_cur ^ 1];
     ga.grid = c->d_grid; ga.argmax = argmax; ga.doa_rad = doa_rad; ga.prob = prob; ga.corr = corr;
+    if (trk && !ga.corr) ga.corr = c->d_trk_corr;
     const bool gate = c->cfg.use_power_floor != 0;
     time_begin(c, MCA_HIP_K_GCC2_SCAN, st);
     if (gate) {
@@ -2506,6 +2621,7 @@ int mca_hip_gcc2_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_st
         hipLaunchKernelGGL(k_gate, dim3(n_arrays), dim3(256), 0, st, gg);
         // the silence rule (:530-560): windowsToDecay = 3 * fs / (analysisLength / 2 - 1), int arithmetic, analysisLength = N + 2
         const int windows_to_decay = 3 * c->cfg.sample_rate / c->H;
+        if (trk) HIP_TRY(c, hipMemcpyAsync(c->d_trk_sil, c->d_silence, (size_t)n_arrays * 4, hipMemcpyDeviceToDevice, st));   // the counters before the call
         hipLaunchKernelGGL(k_gcc2_compact, dim3(n_arrays), dim3(256), 0, st, c->ws().d_voiced, n_frames, c->d_g2_vidx, c->d_g2_nv,
                            c->d_g2_post0, c->d_silence, windows_to_decay, c->d_g2_reset);
         ga.vidx = c->d_g2_vidx; ga.nv = c->d_g2_nv; ga.vreset = c->d_g2_reset;
@@ -2525,11 +2641,118 @@ int mca_hip_gcc2_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_st
         fa.last_idx = c->d_last_bin; fa.last_rad = c->d_last_rad; fa.last_prob = c->d_last_prob;
         hipLaunchKernelGGL(k_gcc2_fill, dim3(n_arrays), dim3(1024), 0, st, fa);
     }
+    if (trk) {
+        Gcc2TrackArgs ta{};
+        ta.corr = ga.corr; ta.corr_state = ga.corr_in; ta.argmax = argmax;
+        if (gate) { ta.voiced = c->ws().d_voiced; ta.post0 = c->d_g2_post0; ta.sil_in = c->d_trk_sil; }
+        ta.windows_to_decay = 3 * c->cfg.sample_rate / c->H;
+        ta.n_arrays = n_arrays; ta.n_frames = n_frames;
+        ta.key_a = -1; ta.state0 = 0; ta.one_kind = -1;
+        ta.doa_out = trk->doa_rad; ta.prob_out = trk->prob; ta.fired = trk->fired; ta.track = trk->track;
+        launch_gcc2_track<float>(c, ta, st);
+    }
     time_end(c, st);
     HIP_TRY(c, hipGetLastError());
     c->e_cur ^= 1; c->doa_cur ^= 1;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
     c->n_lanes_last = 1; c->lanes[0].last_a0 = 0; c->lanes[0].last_arrays = n_arrays;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_gcc2_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+                            int n_arrays, int n_frames, int *argmax, float *doa_rad, float *prob, float *corr, void *stream)
+{
+    if (c && c->tracked)
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "this context has a DOA tracker attached: call mca_hip_gcc2_tracked_frames_dev / _host");
+    return gcc2_frames_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, argmax, doa_rad, prob, corr, stream, nullptr);
+}
+
+int mca_hip_gcc2_tracked_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride, int n_arrays,
+                                    int n_frames, int *argmax, float *doa_rad, float *prob, unsigned char *fired, int *track,
+                                    float *corr, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->tracked) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "no DOA tracker attached (mca_hip_gcc2_tracker_attach)");
+    const Gcc2TrackOut out{doa_rad, prob, fired, track};
+    return gcc2_frames_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, argmax, nullptr, nullptr, corr, stream, &out);
+}
+
+int mca_hip_gcc2_tracked_frames_host(mca_hip_ctx *c, const float *pcm, int n_arrays, int n_frames, int *argmax, float *doa_rad,
+                                     float *prob, unsigned char *fired, int *track, float *corr)
+{
+    if (!c || !pcm || !doa_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_arrays < 1 || n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays/n_frames < 1");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const long long ms = (long long)(n_frames + 1) * c->H, as = ms * c->M;
+    const size_t n_pcm = (size_t)as * n_arrays, n_f = (size_t)n_arrays * n_frames, n_corr = corr ? n_f * c->D : 0;
+    float *d_pcm = (float *)c->stage.get(0, n_pcm * 4), *d_rad = (float *)c->stage.get(2, n_f * 4), *d_prob = (float *)c->stage.get(3, n_f * 4);
+    float *d_corr = (float *)c->stage.get(4, n_corr * 4);
+    int *d_idx = (int *)c->stage.get(1, n_f * 4), *d_track = (int *)c->stage.get(5, n_f * 4);
+    unsigned char *d_fired = (unsigned char *)c->stage.get(6, n_f);
+    if (!d_pcm || !d_idx || !d_rad || !d_prob || !d_track || !d_fired || (corr && !d_corr))
+        return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    HIP_TRY(c, hipMemcpy(d_pcm, pcm, n_pcm * 4, hipMemcpyHostToDevice));
+    const int rc = mca_hip_gcc2_tracked_frames_dev(c, d_pcm, as, ms, n_arrays, n_frames, d_idx, d_rad, d_prob, d_fired, d_track, d_corr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy(doa_rad, d_rad, n_f * 4, hipMemcpyDeviceToHost));
+    if (argmax) HIP_TRY(c, hipMemcpy(argmax, d_idx, n_f * 4, hipMemcpyDeviceToHost));
+    if (prob) HIP_TRY(c, hipMemcpy(prob, d_prob, n_f * 4, hipMemcpyDeviceToHost));
+    if (fired) HIP_TRY(c, hipMemcpy(fired, d_fired, n_f, hipMemcpyDeviceToHost));
+    if (track) HIP_TRY(c, hipMemcpy(track, d_track, n_f * 4, hipMemcpyDeviceToHost));
+    if (corr) HIP_TRY(c, hipMemcpy(corr, d_corr, n_corr * 4, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+int mca_hip_gcc2_tracker_attach(mca_hip_ctx *c, const mca_hip_gcc2_tracker_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg || cfg->struct_size != (int)sizeof(mca_hip_gcc2_tracker_config))
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "tracker config is NULL or struct_size != sizeof(mca_hip_gcc2_tracker_config)");
+    if (c->M != 2) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the DOA tracker needs a context with n_mics == 2");
+    if (c->tracked) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "a DOA tracker is already attached to this context");
+    mca_hip_gcc2_tracker_config t = *cfg;
+    if (t.n_particles == 0) t.n_particles = 500;                                   // BinauralLocalisation.cpp:463
+    if (t.n_particles < 16 || t.n_particles > GCC2_TRACK_MAX_PARTICLES) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_particles must be 0 (500) or in [16, 1024]");
+    if (t.n_inject == 0) t.n_inject = t.n_particles / 20;
+    else if (t.n_inject == -1) t.n_inject = 0;
+    else if (t.n_inject < 0 || t.n_inject >= t.n_particles) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_inject must be -1 (none), 0 (n_particles / 20) or in [1, n_particles)");
+    if (!(t.sigma_init >= 0.0) || !(t.sigma_step >= 0.0) || std::isinf(t.sigma_init) || std::isinf(t.sigma_step))
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "sigma_init / sigma_step must be finite and >= 0 (0 = the grid step)");
+    if (t.sigma_init == 0.0) t.sigma_init = (double)c->step;
+    if (t.sigma_step == 0.0) t.sigma_step = (double)c->step;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t slots = (size_t)c->cfg.max_arrays + 1;
+    auto drop = [&]() {
+        for (void *q : {(void *)c->d_trk_x, (void *)c->d_trk_sd, (void *)c->d_trk_si, (void *)c->d_trk_sil, (void *)c->d_trk_res}) if (q) (void)hipFree(q);
+        c->d_trk_x = c->d_trk_sd = c->d_trk_res = nullptr; c->d_trk_si = c->d_trk_sil = nullptr;
+    };
+    if (hipMalloc((void **)&c->d_trk_x, slots * t.n_particles * 8) != hipSuccess || hipMalloc((void **)&c->d_trk_sd, slots * 16) != hipSuccess ||
+        hipMalloc((void **)&c->d_trk_si, slots * 16) != hipSuccess || hipMalloc((void **)&c->d_trk_sil, slots * 4) != hipSuccess ||
+        hipMalloc((void **)&c->d_trk_res, 32) != hipSuccess) {
+        (void)hipGetLastError(); drop();
+        return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device memory for the DOA tracker's state");
+    }
+    c->trk = t;
+    const int rc = trk_init_state(c, nullptr);
+    if (rc) { drop(); return rc; }
+    c->tracked = true;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_gcc2_tracker_get_particles(mca_hip_ctx *c, int array_index, double *particles, int *alive, int *track)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->tracked) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "no DOA tracker attached (mca_hip_gcc2_tracker_attach)");
+    if (array_index < -1 || array_index >= c->cfg.max_arrays) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "array_index outside [-1, max_arrays) (-1: the frame hook)");
+    const size_t slot = array_index < 0 ? (size_t)c->cfg.max_arrays : (size_t)array_index;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (particles) HIP_TRY(c, hipMemcpy(particles, c->d_trk_x + slot * c->trk.n_particles, (size_t)c->trk.n_particles * 8, hipMemcpyDeviceToHost));
+    int si[4];
+    HIP_TRY(c, hipMemcpy(si, c->d_trk_si + slot * 4, sizeof(si), hipMemcpyDeviceToHost));
+    if (alive) *alive = si[0];
+    if (track) *track = si[1];
     return MCA_HIP_OK;
 }
 
@@ -2764,6 +2987,27 @@ int mca_hip_gcc2_process_frame(mca_hip_ctx *c, const double *const *frames, int 
         pw = 10.0 * std::log10(res[3]);
     }
     const bool fire = pw > g.power_floor || !c->cfg.use_power_floor;          // :434
+    int fired = fire ? 1 : 0;
+    if (c->tracked) {
+        // the DOA tracker on the hook's own state (slot max_arrays, key index 0xFFFFFFFF): one frame of the table in DESIGN.md.
+        // The gate's decision and the counter are the host's, so they go in by value; DOA / prob / fired / track come back.
+        Gcc2TrackArgs ta{};
+        ta.corr = Eout; ta.corr_state = Ein;
+        ta.windows_to_decay = 3 * c->cfg.sample_rate / (ccs_len / 2 - 1);
+        ta.n_arrays = 1; ta.n_frames = 1;
+        ta.key_a = 0xFFFFFFFFll; ta.state0 = c->cfg.max_arrays;
+        ta.one_kind = fire ? 1 : (g.noise_estimated != 0 ? 2 : 0); ta.one_sil = (int)g.silence; ta.one_argmax = (int)res[0];
+        ta.doa_out = c->d_trk_res; ta.prob_out = c->d_trk_res + 1;
+        ta.fired = reinterpret_cast<unsigned char *>(c->d_trk_res + 2); ta.track = reinterpret_cast<int *>(c->d_trk_res + 3);
+        launch_gcc2_track<double>(c, ta, nullptr);
+        HIP_TRY(c, hipGetLastError());
+        double out[4];
+        HIP_TRY(c, hipMemcpy(out, c->d_trk_res, sizeof(out), hipMemcpyDeviceToHost));
+        unsigned char f8; std::memcpy(&f8, &out[2], 1);
+        fired = f8;
+        res[1] = out[1]; res[2] = out[0];                                      // _prob (:454) and _currentDOA = updateFilter() (:473)
+        if (!fire) { g.doa = out[0]; g.prob = out[1]; }                        // a coasting track moves the DOA (:545)
+    }
     if (fire) {
         g.prob = res[1];                                                       // :454
         g.doa = res[2];                                                        // :502-504
@@ -2775,7 +3019,7 @@ int mca_hip_gcc2_process_frame(mca_hip_ctx *c, const double *const *frames, int 
         else { g.corr_mem = 0; g.doa_mem = 0; }
         g.silence += 1;
     }
-    *voiced = fire ? 1 : 0;
+    *voiced = fired;
     *doa_rad = g.doa; *prob = g.prob; *power = pw;
     if (argmax) *argmax = fire ? (int)res[0] : -1;
     if (corr) HIP_TRY(c, hipMemcpy(corr, c->d_g2f_corr[c->g2f_cur], (size_t)c->D * 8, hipMemcpyDeviceToHost));

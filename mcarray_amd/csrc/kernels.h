@@ -60,6 +60,8 @@ __global__ void k_gcc2_prob(const TC *corr, long long corr_stride, int D, float 
 template <typename T>
 __global__ void k_frame_gcc2(const T *corr, int D, float step, const float *grid, double doa_prev, double doa_mem, double one_minus_doa_mem,
                              double *res);
+template <typename TC, int SLOTS>       // the DOA tracker (kernels_gcc2_track.hip); SLOTS: particles per lane
+__global__ void k_gcc2_track(Gcc2TrackArgs p);
 __global__ void k_mask_stream(MaskArgs p);
 __global__ void k_mask_stream_gen(MaskGenArgs p);
 __global__ void k_mask_stream_2048(MaskGenArgs p);

@@ -351,6 +351,32 @@ struct Gcc2FillArgs {
     int *last_idx; float *last_rad, *last_prob;          // [arrays] values of the last frame, carried to the next call
 };
 
+// k_gcc2_track (kernels_gcc2_track.hip): the particle-filter DOA tracker, one wave per array, the frames of the call in order
+constexpr int GCC2_TRACK_WAVES = 2;            // arrays per workgroup
+constexpr int GCC2_TRACK_MAX_PARTICLES = 1024;
+struct Gcc2TrackArgs {
+    const void *corr;              // [arrays][n_frames][D] smoothed rows of the frames that fired (TC)
+    const void *corr_state;        // [arrays][D] the row before the call (TC)
+    const int *argmax;             // [arrays][n_frames] first-max argmax of the frames that fired
+    const unsigned char *voiced;   // [arrays][n_frames]; NULL: every frame fired
+    const int *post0, *sil_in;     // [arrays] with `voiced`: first frame with a known floor, _silenceFramesCounter before the call
+    int windows_to_decay;
+    int n_arrays, n_frames, D;
+    float step; const float *grid;
+    int N, n_inject; unsigned long long seed; double sigma_init, sigma_step;
+    long long key_a;               // >= 0: the array index that enters the key (the frame hook's 0xFFFFFFFF); < 0: the array's own
+    int state0;                    // state slot of array 0 of this launch
+    double *x;                     // [slots][N] particles
+    double *sd;                    // [slots][2] DOA, prob
+    int *si;                       // [slots][4] alive, track, upd, -
+    void *doa_out, *prob_out;      // [arrays][n_frames] (TC); prob_out may be NULL
+    unsigned char *fired; int *track;   // [arrays][n_frames], may be NULL
+    // the frame hook (one array, one frame): the host knows the gate's decision and the counter
+    int one_kind;                  // < 0: not used; 0 nothing happens, 1 the frame fired, 2 gated out with a known floor
+    int one_sil, one_argmax;
+    unsigned slice_bytes;          // LDS per wave
+};
+
 struct MaskParams {
     float thr[45];
     int lo[45], hi[45];       // support of band b (bins with H_b > 0), lo > hi for an empty band
