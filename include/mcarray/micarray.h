@@ -4,6 +4,7 @@
 #include "ArrayDescription.h"
 #include "ArrayModules.h"
 #include "BinauralLocalisation.h"
+#include "BinauralMaskingImpl.h"
 #include "FastBinauralMasking.h"
 #include "MultibandBinarualLocalisation.h"
 #include "MvdrBeamformer.h"

@@ -412,6 +412,63 @@ long long mca_hip_mask_state_size(const mca_hip_mask_ctx *ctx);
 int mca_hip_mask_state_save(mca_hip_mask_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_mask_state_load(mca_hip_mask_ctx *ctx, const void *blob, long long blob_bytes);
 
+/* ---- filter-bank binaural masking (BinauralMaskingImpl) --------------------------------------
+ * The time-domain formulation of the same masking: every windowed frame goes through 45 mel filters, each band signal
+ * pair is kept, temporally masked or spatially masked, the bands are summed again.  It is its own
+ * module: its own decision rule (plain means, no reject factor), three methods, a per-channel RELATIVE gain. */
+typedef struct mca_hip_bmask_ctx mca_hip_bmask_ctx;
+/* BinauralMaskingImpl::MaskingMethod (BinauralMaskingImpl.h:67) */
+typedef enum { MCA_HIP_BMASK_FACTOR = 0, MCA_HIP_BMASK_RELATIVE = 1, MCA_HIP_BMASK_FULL = 3 } mca_hip_bmask_method;
+/* constructor arguments of BinauralMaskingImpl(int samplerate, double microDistance, float lowFreq, float highFreq,
+ * MaskingMethod) (BinauralMaskingImpl.h:78-82) */
+typedef struct {
+    int struct_size;
+    int device;
+    int sample_rate;
+    int frame_size;          /* W = 2^calculateOrderFromSampleRate(fs, 0.050): 1024 at 16 kHz and 2048 at 44.1 / 48 kHz have tuned
+                                kernels, the other powers of two in [256, 8192] (256, 512, 4096, 8192) run on the any-length
+                                transform.  Everything else is refused with INVALID_ARGUMENT: 64, 128 and 16384, which
+                                mca_hip_mask_create takes, and every length that is not a power of two */
+    double micro_distance;
+    float low_freq, high_freq;
+    int method;              /* mca_hip_bmask_method */
+    int max_streams;
+} mca_hip_bmask_config;
+int mca_hip_bmask_create(const mca_hip_bmask_config *cfg, mca_hip_bmask_ctx **out);
+void mca_hip_bmask_destroy(mca_hip_bmask_ctx *ctx);
+const char *mca_hip_bmask_last_error(const mca_hip_bmask_ctx *ctx);
+/* zeroes the short-time powers, the overlap-add tails and the frame counters of every stream and the hook's powers */
+int mca_hip_bmask_reset(mca_hip_bmask_ctx *ctx);
+/* _thresholds (cos(2 pi f_b d sin(10 deg) / c) * 0.9) and the band centres (cycles/sample): out[45] each */
+int mca_hip_bmask_get_thresholds(const mca_hip_bmask_ctx *ctx, double *thresholds, double *center_freqs);
+/* windowing + filter bank + BinauralMaskingImpl::processParametrisation + re-summation + overlap-add for n_frames frames
+ * (hop W/2, periodic Hann) of n_streams independent 2-channel streams, fp32.
+ * pcm_dev: sample n of channel c of stream s at pcm[s*stream_stride + c*ch_stride + n], (F+1)*hop samples; 8-byte aligned, even
+ * strides.  Streams are independent: stream s of a call continues slot s of the context, any n_streams <= max_streams.
+ * out_pcm_dev [streams][2][F*hop]; decisions_dev (may be NULL) [streams][F][45] int32: 0 enhance, 1 temporal mask, 2 spatial
+ * mask.  Asynchronous on `stream`; a call that needs a larger workspace than any before it allocates (and synchronises). */
+int mca_hip_bmask_frames_dev(mca_hip_bmask_ctx *ctx, const float *pcm_dev, long long stream_stride, long long ch_stride,
+                             int n_streams, int n_frames, float *out_pcm_dev, int *decisions_dev, void *stream);
+int mca_hip_bmask_frames_host(mca_hip_bmask_ctx *ctx, const float *pcm, int n_streams, int n_frames, float *out_pcm,
+                              int *decisions);
+/* the three hooks of the class, one frame of one channel (pair) each, double on the GPU; they keep a short-time power of their own.
+ * frame_analysis: band b of in_frame[W] to analysis[b*W .. b*W+W) for every b < 45 that fits into analysis_length, and the
+ * residual (the frame minus its 45 bands) to slot 45 when analysis_length >= 46*W; the rest of the buffer is not written. */
+int mca_hip_bmask_frame_analysis(mca_hip_bmask_ctx *ctx, const double *in_frame, double *analysis, int frame_length,
+                                 int analysis_length, int channel);
+/* processParametrisation: left/right hold 45 band signals of W doubles each (analysis_length >= 45*W), scaled in place;
+ * decisions (may be NULL) int[45] */
+int mca_hip_bmask_process_frame(mca_hip_bmask_ctx *ctx, double *left, double *right, int analysis_length, int *decisions);
+/* frameSynthesis, the reference's literal loop: out_frame[W] = the sum of the slots 0, 1, ... while slot <= 45 and
+ * slot*W < analysis_length - W (46*W: the 45 bands, no residual; 45*W: the first 44 bands) */
+int mca_hip_bmask_frame_synthesis(mca_hip_bmask_ctx *ctx, double *out_frame, const double *analysis, int frame_length,
+                                  int analysis_length, int channel);
+/* checkpoint / resume as mca_hip_state_*: the short-time powers of every stream, the overlap-add tails, the frame counters
+ * and the hook's short-time powers */
+long long mca_hip_bmask_state_size(const mca_hip_bmask_ctx *ctx);
+int mca_hip_bmask_state_save(mca_hip_bmask_ctx *ctx, void *blob, long long blob_bytes);
+int mca_hip_bmask_state_load(mca_hip_bmask_ctx *ctx, const void *blob, long long blob_bytes);
+
 /* ---- MultibandBinarualLocalisation (2 microphones) ---------------------------
  * Replaces mca::MultibandBinarualLocalisation(int sampleRate, ArrayDescription, int nbins = 15, bool usePowerFloor = 1)
  * (include/mcarray/MultibandBinarualLocalisation.h:38) with its per-frame hooks processSetup / processOneSubband /

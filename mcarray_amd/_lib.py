@@ -54,6 +54,20 @@ class MaskConfig(C.Structure):
     ]
 
 
+class BmaskConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("device", C.c_int),
+        ("sample_rate", C.c_int),
+        ("frame_size", C.c_int),
+        ("micro_distance", C.c_double),
+        ("low_freq", C.c_float),
+        ("high_freq", C.c_float),
+        ("method", C.c_int),
+        ("max_streams", C.c_int),
+    ]
+
+
 class MbConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -161,6 +175,20 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mask_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, c_fp, c_ip]),
     ("mca_hip_mask_process_frame", C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int, c_ip]),
+    ("mca_hip_bmask_create", C.c_int, [C.POINTER(BmaskConfig), C.POINTER(C.c_void_p)]),
+    ("mca_hip_bmask_destroy", None, [C.c_void_p]),
+    ("mca_hip_bmask_last_error", C.c_char_p, [C.c_void_p]),
+    ("mca_hip_bmask_reset", C.c_int, [C.c_void_p]),
+    ("mca_hip_bmask_get_thresholds", C.c_int, [C.c_void_p, c_dp, c_dp]),
+    ("mca_hip_bmask_frames_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_bmask_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, c_fp, c_ip]),
+    ("mca_hip_bmask_frame_analysis", C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int, C.c_int, C.c_int]),
+    ("mca_hip_bmask_process_frame", C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int, c_ip]),
+    ("mca_hip_bmask_frame_synthesis", C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int, C.c_int, C.c_int]),
+    ("mca_hip_bmask_state_size", C.c_longlong, [C.c_void_p]),
+    ("mca_hip_bmask_state_save", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
+    ("mca_hip_bmask_state_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
     ("mca_hip_mb_create", C.c_int, [C.POINTER(MbConfig), C.POINTER(C.c_void_p)]),
     ("mca_hip_mb_destroy", None, [C.c_void_p]),
     ("mca_hip_mb_last_error", C.c_char_p, [C.c_void_p]),

@@ -967,3 +967,104 @@ class FastBinauralMasking(_StateBlob):
         self._check(self._lib.mca_hip_mask_process_frame(self.h, left.ctypes.data_as(_lib.c_dp), right.ctypes.data_as(_lib.c_dp),
                                                          len(left), dec.ctypes.data_as(_lib.c_ip)))
         return left, right, dec
+
+
+class BinauralMaskingImpl(_StateBlob):
+    _STATE = "bmask"
+    """mca::BinauralMaskingImpl(int samplerate, double microDistance, float lowFreq, float highFreq, MaskingMethod = RELATIVE)
+    (BinauralMaskingImpl.h:78-82): the filter-bank (time-domain) formulation of the binaural masking.  The frame length is the
+    module's own, W = 2^calculateOrderFromSampleRate(fs, 0.050), the hop W/2.  Methods: FACTOR, RELATIVE, FULL."""
+    N_BANDS = 45
+
+    def __init__(self, samplerate, micro_distance, low_freq, high_freq, method=RELATIVE, max_streams=1, device=0):
+        self._lib = _lib.load()
+        self.W = 1 << calculate_order_from_sample_rate(samplerate, float(np.float32(0.050)))
+        self.hop = self.W // 2
+        cfg = _lib.BmaskConfig()
+        cfg.struct_size = C.sizeof(_lib.BmaskConfig)
+        cfg.device = device
+        cfg.sample_rate = samplerate
+        cfg.frame_size = self.W
+        cfg.micro_distance = micro_distance
+        cfg.low_freq = low_freq
+        cfg.high_freq = high_freq
+        cfg.method = method
+        cfg.max_streams = max_streams
+        h = C.c_void_p()
+        rc = self._lib.mca_hip_bmask_create(C.byref(cfg), C.byref(h))
+        if rc != 0:
+            raise MCArrayHipError("mca_hip_bmask_create failed (%d): %s" % (rc, self._lib.mca_hip_bmask_last_error(None).decode()))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._lib.mca_hip_bmask_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise MCArrayHipError("libmcarray_hip error %d: %s" % (rc, self._lib.mca_hip_bmask_last_error(self.h).decode()))
+
+    def reset(self):
+        self._check(self._lib.mca_hip_bmask_reset(self.h))
+
+    def thresholds(self):
+        thr = np.empty(45)
+        cen = np.empty(45)
+        self._check(self._lib.mca_hip_bmask_get_thresholds(self.h, thr.ctypes.data_as(_lib.c_dp), cen.ctypes.data_as(_lib.c_dp)))
+        return thr, cen
+
+    def process(self, pcm, want_decisions=True):
+        """pcm float32 [streams][2][(F+1)*hop] -> (out [streams][2][F*hop], decisions [streams][F][45])"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 2:
+            pcm = pcm[None]
+        ns, ch, L = pcm.shape
+        F = L // self.hop - 1
+        if ch != 2:
+            raise MCArrayHipError("Sound localisation is only working for 2 channels by now.")
+        if F < 1 or (F + 1) * self.hop != L:
+            raise MCArrayHipError("pcm must be [streams][2][(F+1)*hop]")
+        out = np.empty((ns, 2, F * self.hop), dtype=np.float32)
+        dec = np.empty((ns, F, 45), dtype=np.int32) if want_decisions else None
+        self._check(self._lib.mca_hip_bmask_frames_host(self.h, pcm.ctypes.data_as(_lib.c_fp), ns, F, out.ctypes.data_as(_lib.c_fp),
+                                                        dec.ctypes.data_as(_lib.c_ip) if want_decisions else None))
+        return out, dec
+
+    state = _StateBlob.state_save
+    load_state = _StateBlob.state_load
+
+    def frame_analysis(self, frame, analysis_length=None, channel=0):
+        """frameAnalysis: one windowed frame double[W] -> the analysis buffer double[analysis_length] (default 46 W): band b at
+        b*W for every band that fits, the residual in slot 45 when there is room; what is not written stays zero."""
+        frame = np.ascontiguousarray(frame, dtype=np.float64)
+        n = 46 * self.W if analysis_length is None else int(analysis_length)
+        ana = np.zeros(n)
+        self._check(self._lib.mca_hip_bmask_frame_analysis(self.h, frame.ctypes.data_as(_lib.c_dp), ana.ctypes.data_as(_lib.c_dp),
+                                                           len(frame), n, channel))
+        return ana
+
+    def process_parametrisation(self, left, right):
+        """The hook for one frame: two analysis buffers (>= 45 W doubles), returns the modified copies + decisions."""
+        left = np.array(left, dtype=np.float64, order="C")
+        right = np.array(right, dtype=np.float64, order="C")
+        if len(left) != len(right):
+            raise MCArrayHipError("left and right analysis buffers differ in length")
+        dec = np.zeros(45, dtype=np.int32)
+        self._check(self._lib.mca_hip_bmask_process_frame(self.h, left.ctypes.data_as(_lib.c_dp), right.ctypes.data_as(_lib.c_dp),
+                                                          len(left), dec.ctypes.data_as(_lib.c_ip)))
+        return left, right, dec
+
+    def frame_synthesis(self, analysis, analysis_length=None, channel=0):
+        """frameSynthesis: the sum of the band slots the reference's loop reads for this analysis_length -> double[W]."""
+        analysis = np.ascontiguousarray(analysis, dtype=np.float64)
+        n = len(analysis) if analysis_length is None else int(analysis_length)
+        if n > len(analysis):
+            raise MCArrayHipError("analysis_length exceeds the buffer")
+        out = np.empty(self.W)
+        self._check(self._lib.mca_hip_bmask_frame_synthesis(self.h, out.ctypes.data_as(_lib.c_dp), analysis.ctypes.data_as(_lib.c_dp),
+                                                            self.W, n, channel))
+        return out
