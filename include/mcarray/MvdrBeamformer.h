@@ -45,6 +45,20 @@ public:
     int getMaxLatency() const { return _N; }
     int getNumberOfChannels() const { return _nchannels; }
     void setDOA(double doaRadians) { _doa = doaRadians; }      // look direction of the frames completed from now on
+    // Several look directions per frame from the one covariance (mca_hip_mvdr_sources_frames_*): setMaxSources(1 ... 4) once,
+    // then setDOAs() with up to that many directions and the process() overload with one output pointer per direction.
+    void setMaxSources(int maxSources)
+    {
+        check(mca_hip_mvdr_set_max_sources(_ctx, maxSources));
+        _maxSources = maxSources;
+        if (static_cast<int>(_doas.size()) > maxSources) _doas.resize(static_cast<size_t>(maxSources));   // the directions that still fit
+    }
+    void setDOAs(const std::vector<double> &doasRadians)
+    {
+        if (doasRadians.empty() || static_cast<int>(doasRadians.size()) > _maxSources)
+            throw MCArrayException("setDOAs: between 1 and the setMaxSources() maximum of look directions");
+        _doas = doasRadians;
+    }
     void reset()
     {
         check(mca_hip_mvdr_reset(_ctx, nullptr));
@@ -56,6 +70,44 @@ public:
     int process(const std::vector<Tin *> &in, int nSamples, Tout *out, int outSize)
     {
         const int hop = _N / 2;
+        const int F = pend(in, nSamples);
+        if (F == 0) return 0;
+        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
+        std::vector<float> pcm = frames(F);
+        std::vector<float> doa(static_cast<size_t>(F), static_cast<float>(_doa)), audio(static_cast<size_t>(F) * static_cast<size_t>(hop));
+        check(mca_hip_mvdr_frames_host(_ctx, pcm.data(), 1, F, doa.data(), audio.data(), nullptr));
+        for (int i = 0; i < F * hop; ++i) out[i] = static_cast<Tout>(audio[static_cast<size_t>(i)]);
+        consume(F);
+        return F * hop;
+    }
+
+    // the same for the look directions of setDOAs(): out[s] receives the output of direction s; returns the samples written per output.
+    // A direction that a call leaves out (fewer directions than in the call before) restarts from silence.
+    template <typename Tin, typename Tout>
+    int process(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize)
+    {
+        const int hop = _N / 2, S = static_cast<int>(_doas.size());
+        if (S == 0) throw MCArrayException("process: setDOAs() first");
+        if (static_cast<int>(out.size()) < S) throw MCArrayException("process: one output pointer per look direction of setDOAs()");
+        const int F = pend(in, nSamples);
+        if (F == 0) return 0;
+        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
+        std::vector<float> pcm = frames(F);
+        std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
+        for (int t = 0; t < F; ++t)
+            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+        check(mca_hip_mvdr_sources_frames_host(_ctx, pcm.data(), 1, F, S, doa.data(), audio.data(), nullptr));
+        for (int s = 0; s < S; ++s)
+            for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
+        consume(F);
+        return F * hop;
+    }
+
+private:
+    // appends a chunk to the pending samples; returns the frames they complete
+    template <typename Tin>
+    int pend(const std::vector<Tin *> &in, int nSamples)
+    {
         for (int c = 0; c < _nchannels; ++c) {
             std::vector<float> &buf = _pending[static_cast<size_t>(c)];
             const size_t old = buf.size();
@@ -63,28 +115,29 @@ public:
             for (int i = 0; i < nSamples; ++i) buf[old + static_cast<size_t>(i)] = static_cast<float>(in[static_cast<size_t>(c)][i]);
         }
         const int have = static_cast<int>(_pending[0].size());
-        const int F = have >= _N ? (have - _N) / hop + 1 : 0;
-        if (F == 0) return 0;
-        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
-        const size_t L = static_cast<size_t>(F + 1) * static_cast<size_t>(hop);
+        return have >= _N ? (have - _N) / (_N / 2) + 1 : 0;
+    }
+    std::vector<float> frames(int F) const      // [channel][(F + 1) hop]
+    {
+        const size_t L = static_cast<size_t>(F + 1) * static_cast<size_t>(_N / 2);
         std::vector<float> pcm(L * static_cast<size_t>(_nchannels));
         for (int c = 0; c < _nchannels; ++c)
             std::copy(_pending[static_cast<size_t>(c)].begin(), _pending[static_cast<size_t>(c)].begin() + static_cast<long>(L), pcm.begin() + static_cast<long>(L * static_cast<size_t>(c)));
-        std::vector<float> doa(static_cast<size_t>(F), static_cast<float>(_doa)), audio(static_cast<size_t>(F) * static_cast<size_t>(hop));
-        check(mca_hip_mvdr_frames_host(_ctx, pcm.data(), 1, F, doa.data(), audio.data(), nullptr));
-        for (int i = 0; i < F * hop; ++i) out[i] = static_cast<Tout>(audio[static_cast<size_t>(i)]);
-        for (int c = 0; c < _nchannels; ++c)
-            _pending[static_cast<size_t>(c)].erase(_pending[static_cast<size_t>(c)].begin(), _pending[static_cast<size_t>(c)].begin() + static_cast<long>(F) * hop);
-        return F * hop;
+        return pcm;
     }
-
-private:
+    void consume(int F)
+    {
+        for (int c = 0; c < _nchannels; ++c)
+            _pending[static_cast<size_t>(c)].erase(_pending[static_cast<size_t>(c)].begin(), _pending[static_cast<size_t>(c)].begin() + static_cast<long>(F) * (_N / 2));
+    }
     void check(int rc) const
     {
         if (rc != MCA_HIP_OK) throw MCArrayException(std::string("libmcarray_hip: ") + mca_hip_mvdr_last_error(_ctx));
     }
     int _nchannels, _N;
     double _doa = 0.0;
+    int _maxSources = 1;
+    std::vector<double> _doas;
     mca_hip_mvdr_ctx *_ctx = nullptr;
     std::vector<std::vector<float> > _pending;
 };

@@ -587,6 +587,23 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev, long lo
                             float *out_spec_dev, void *stream);
 int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, const float *doa_rad,
                              float *out_pcm, float *out_spec);
+/* Several look directions per frame from ONE analysis, covariance recursion and factorisation (e.g. the talkers a localiser with
+ * n_sources > 1 reports).  Output s is what the single-look call gives on the same stream state with doa[:, :, s]; the covariance
+ * afterwards is what any of those calls leaves.  Opt-in: mca_hip_mvdr_set_max_sources(ctx, 1 ... 4) gives every stream that many
+ * overlap-add tails (slots both sizes have keep their content, new ones start at zero; default 1).
+ *   doa_rad_dev  [streams][F][n_sources] float -- the layout mca_hip_localise_frames_dev writes
+ *   out_pcm_dev  [streams][n_sources][F*hop] float (may be NULL)
+ *   out_spec_dev [streams][n_sources][F][N/2+1] interleaved re,im float (may be NULL; not both)
+ * n_sources <= the context's maximum.  The tail slots s >= n_sources of the streams in the call are zeroed: a source a call
+ * leaves out restarts from silence.  The single-look entry points use slot 0 on any context, and n_sources = 1 here gives
+ * their bytes.  A context with a maximum above 1 writes state blobs of a second version that also carry the extra tails and the
+ * maximum; a blob loads only into a context with the maximum it was saved with. */
+int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *ctx, int max_sources);
+int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev, long long stream_stride, long long mic_stride,
+                                    int n_streams, int n_frames, int n_sources, const float *doa_rad_dev, float *out_pcm_dev,
+                                    float *out_spec_dev, void *stream);
+int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
+                                     const float *doa_rad, float *out_pcm, float *out_spec);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream */

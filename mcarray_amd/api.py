@@ -806,11 +806,12 @@ class MvdrBeamformer(_StateBlob):
     _STATE = "mvdr"
     """Frequency-domain beamformer with a per-bin spatial covariance (BASELINE.json configs[3]; SURVEY A.9).
     No reference counterpart: the interface follows mca::Beamformer (Beamformer.h:39,49: frames in, one channel out,
-    a look direction in radians) with the delay-and-sum weights replaced by MVDR weights."""
+    a look direction in radians) with the delay-and-sum weights replaced by MVDR weights.
+    max_sources > 1 (up to 4) lets process_sources() separate that many look directions per frame from the one covariance."""
 
     K_ANALYSE, K_SOLVE, K_SYNTH = 0, 1, 2
 
-    def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0):
+    def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1):
         self._lib = _lib.load()
         xyz = _xyz(mic_positions)
         cfg = _lib.MvdrConfig()
@@ -829,6 +830,18 @@ class MvdrBeamformer(_StateBlob):
             raise MCArrayHipError("mca_hip_mvdr_create failed (%d): %s" % (rc, self._lib.mca_hip_mvdr_last_error(None).decode()))
         self.h = h
         self.M, self.N, self.hop, self.K = len(xyz), fft_size, fft_size // 2, fft_size // 2 + 1
+        self.max_sources = 1
+        if max_sources != 1:
+            try:
+                self.set_max_sources(max_sources)
+            except MCArrayHipError:
+                self.close()
+                raise
+
+    def set_max_sources(self, max_sources):
+        """look directions per frame process_sources() may carry (1 ... 4): one overlap-add tail per stream and source"""
+        self._check(self._lib.mca_hip_mvdr_set_max_sources(self.h, int(max_sources)))
+        self.max_sources = int(max_sources)
 
     def close(self):
         if getattr(self, "h", None):
@@ -870,6 +883,41 @@ class MvdrBeamformer(_StateBlob):
         A = pcm.shape[0]
         self._check(self._lib.mca_hip_mvdr_frames_dev(
             self.h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), A, n_frames, doa_rad.data_ptr(),
+            out_pcm.data_ptr() if out_pcm is not None else None, out_spec.data_ptr() if out_spec is not None else None, stream))
+
+    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True):
+        """S look directions per frame from one analysis, covariance recursion and factorisation: pcm float32
+        [streams][M][(F+1)*hop], doa_rad [streams][F][S] (S <= max_sources; the layout of the localiser's "doa") ->
+        dict(out [streams][S][F*hop], spec complex64 [streams][S][F][K]).  Output s is what process() gives with doa_rad[:, :, s]."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 2:
+            pcm = pcm[None]
+        A, M, L = pcm.shape
+        F = L // self.hop - 1
+        if M != self.M or F < 1 or (F + 1) * self.hop != L:
+            raise MCArrayHipError("pcm must be [streams][M][(F+1)*hop]")
+        doa = np.asarray(doa_rad, dtype=np.float32)
+        if doa.ndim != 3 or doa.shape[:2] != (A, F):
+            raise MCArrayHipError("doa_rad must be [streams][F][S]")
+        doa = np.ascontiguousarray(doa)
+        S = doa.shape[2]
+        out = np.empty((A, S, F * self.hop), dtype=np.float32) if want_audio else None
+        spec = np.empty((A, S, F, self.K), dtype=np.complex64) if want_spec else None
+        fp = _lib.c_fp
+        self._check(self._lib.mca_hip_mvdr_sources_frames_host(
+            self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp), out.ctypes.data_as(fp) if want_audio else None,
+            spec.ctypes.data_as(fp) if want_spec else None))
+        return dict(out=out, spec=spec)
+
+    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None):
+        """device tensors (torch, contiguous): pcm [streams][M][>= (F+1)*hop] float32, doa_rad [streams][F][S] float32 (e.g. the
+        doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec [streams][S][F][K][2];
+        asynchronous on `stream` (a raw hipStream_t or None)."""
+        A = pcm.shape[0]
+        if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
+            raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
+        self._check(self._lib.mca_hip_mvdr_sources_frames_dev(
+            self.h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), A, n_frames, doa_rad.shape[2], doa_rad.data_ptr(),
             out_pcm.data_ptr() if out_pcm is not None else None, out_spec.data_ptr() if out_spec is not None else None, stream))
 
     def covariance(self, stream_index=0):

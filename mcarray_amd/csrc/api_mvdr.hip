@@ -25,10 +25,11 @@ struct mca_hip_mvdr_ctx {
     float2 *d_phi = nullptr;      // [max_streams][K][tri]
     float *d_trace = nullptr;     // [max_streams][K]
     float2 *d_phi_tail = nullptr; float *d_trace_tail = nullptr;   // exit state of the pieced tail launch (<= 128 workgroups x 64 problems), copied back behind it
-    float *d_tail[2] = {nullptr, nullptr}; int tail_cur = 0;   // [max_streams][H]
+    int max_sources = 1;          // look directions per frame a call may carry (mca_hip_mvdr_set_max_sources)
+    float *d_tail[2] = {nullptr, nullptr}; int tail_cur = 0;   // [max_streams][max_sources][H]; a single-look call uses slot 0
     // workspace
     float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
-    float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // d_T: factored steering phasors [rows][M][N/64 + 33]
+    float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // rows x look directions; d_T: factored steering phasors [rows][M][N/64 + 33]
     StagePool stage;
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
@@ -72,12 +73,12 @@ int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
     const size_t ns = (size_t)c->cfg.max_streams;
     VHIP_TRY(c, hipMemsetAsync(c->d_phi, 0, ns * c->K * c->tri * sizeof(float2), st));
     VHIP_TRY(c, hipMemsetAsync(c->d_trace, 0, ns * c->K * 4, st));
-    for (int i = 0; i < 2; ++i) VHIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, ns * c->H * 4, st));
+    for (int i = 0; i < 2; ++i) VHIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, ns * c->max_sources * c->H * 4, st));
     VHIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
-int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows)
+int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources)
 {
     auto F = [](void *p) { if (p) (void)hipFree(p); };
     if (rows > c->x_rows) {
@@ -85,11 +86,12 @@ int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows)
         VHIP_TRY(c, hipMalloc((void **)&c->d_X, rows * c->K * c->M * sizeof(float2)));
         c->x_rows = rows;
     }
-    if (rows > c->y_rows) {
+    const size_t yrows = rows * n_sources;
+    if (yrows > c->y_rows) {
         F(c->d_Y); F(c->d_T); c->d_Y = nullptr; c->d_T = nullptr; c->y_rows = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_Y, rows * c->K * sizeof(float2)));
-        VHIP_TRY(c, hipMalloc((void **)&c->d_T, rows * c->M * (c->N / 64 + 33) * sizeof(float2)));
-        c->y_rows = rows;
+        VHIP_TRY(c, hipMalloc((void **)&c->d_Y, yrows * c->K * sizeof(float2)));
+        VHIP_TRY(c, hipMalloc((void **)&c->d_T, yrows * c->M * (c->N / 64 + 33) * sizeof(float2)));
+        c->y_rows = yrows;
     }
     return MCA_HIP_OK;
 }
@@ -189,10 +191,40 @@ int mca_hip_mvdr_reset(mca_hip_mvdr_ctx *c, void *stream)
     return init_state(c, (hipStream_t)stream);
 }
 
-int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
-                            int n_frames, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
+int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (max_sources < 1 || max_sources > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_sources must be in [1,4]");
+    if (max_sources == c->max_sources) return MCA_HIP_OK;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());
+    // new tails [max_streams][max_sources][H]: the slots both layouts have keep their content, the others start at zero
+    const size_t ns = (size_t)c->cfg.max_streams, row = (size_t)c->H * 4, bytes = ns * max_sources * row;
+    const int keep = max_sources < c->max_sources ? max_sources : c->max_sources;
+    float *nt[2] = {nullptr, nullptr};
+    hipError_t e = hipMalloc((void **)&nt[0], bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&nt[1], bytes);
+    if (e == hipSuccess) e = hipMemset(nt[0], 0, bytes);
+    if (e == hipSuccess) e = hipMemset(nt[1], 0, bytes);
+    if (e == hipSuccess) e = hipMemcpy2D(nt[0], max_sources * row, c->d_tail[c->tail_cur], c->max_sources * row, keep * row, ns, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        if (nt[0]) (void)hipFree(nt[0]);
+        if (nt[1]) (void)hipFree(nt[1]);
+        return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("overlap-add tails of the new sources: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(c->d_tail[0]); (void)hipFree(c->d_tail[1]);
+    c->d_tail[0] = nt[0]; c->d_tail[1] = nt[1]; c->tail_cur = 0; c->max_sources = max_sources;
+    return MCA_HIP_OK;
+}
+
+// the three launches of a call with n_sources look directions per frame: doa_rad [streams][F][n_sources],
+// out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]
+int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                    int n_frames, int n_sources, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (n_sources < 1 || n_sources > c->max_sources)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
     if (!pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
     if (!out_pcm && !out_spec) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
     if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
@@ -208,13 +240,13 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
     const size_t rows = (size_t)n_streams * n_frames;
     // the beamformed spectra go straight to the caller's buffer when one is given
     float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : nullptr;
-    int rc = ensure_ws(c, rows);
+    int rc = ensure_ws(c, rows, n_sources);
     if (rc) return rc;
     if (!Y) Y = c->d_Y;
 
     MvdrAnalyseArgs aa{};
     aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = n_frames;
-    aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = doa_rad;
+    aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.S = n_sources; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = doa_rad;
     aa.X = c->d_X; aa.T = c->d_T; aa.mic_x = c->d_micx;
     aa.unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;                      // Beamformer.cpp:59 without 2 pi
     t_begin(c, 0, st);
@@ -246,7 +278,7 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
     sa.alpha = (float)c->cfg.alpha; sa.one_minus_alpha = (float)(1.0 - c->cfg.alpha);
     sa.loading_over_m = (float)(c->cfg.loading / c->M);
     sa.phi = c->d_phi; sa.trace = c->d_trace; sa.Y = Y;
-    sa.n_streams = n_streams;
+    sa.n_streams = n_streams; sa.S = n_sources;
     const int Q = (c->M + 3) / 4;                                                     // row slots per lane
     auto launch_solve = [&](long long pid0, long long n_prob, int pieces) {
         sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
@@ -260,7 +292,18 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
         if (c->M == 4 * (QQ)) hipLaunchKernelGGL((k_mvdr_solve<QQ, true>), sgrid, dim3(256), 0, st, sa);   \
         else hipLaunchKernelGGL((k_mvdr_solve<QQ, false>), sgrid, dim3(256), 0, st, sa);                   \
     } while (0)
-        if (Q == 1) SOLVE(1);
+        if (n_sources > 1) {
+            // several look directions: the instantiation of (row slots, directions), with its directions per pass (mca_internal.h)
+            const bool full = c->M == 4 * Q;
+#define SOLVE_SOURCES(QQ, SS, S1F, S1P)                                                                                    \
+    if (Q == QQ && n_sources == SS) {                                                                                     \
+        if (full) hipLaunchKernelGGL((k_mvdr_solve_sources<QQ, true, SS, S1F>), sgrid, dim3(256), 0, st, sa);             \
+        else hipLaunchKernelGGL((k_mvdr_solve_sources<QQ, false, SS, S1P>), sgrid, dim3(256), 0, st, sa);                 \
+    }
+            MCA_MVDR_SOURCES_TABLE(SOLVE_SOURCES)
+#undef SOLVE_SOURCES
+        }
+        else if (Q == 1) SOLVE(1);
         else if (Q == 2) SOLVE(2);
         else if (Q == 3) SOLVE(3);
         else SOLVE(4);
@@ -290,14 +333,21 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
     if (out_pcm) {
         MvdrSynthArgs ya{};
         ya.Y = Y; ya.n_frames = n_frames; ya.N = c->N; ya.logH = c->logH; ya.tw = c->d_tw;
+        ya.S = n_sources; ya.tail_slots = c->max_sources;
+        const int n_out = n_streams * n_sources;                                          // one inverse transform + overlap-add each
         ya.ft = 16;
-        while (ya.ft > 2 && (long long)n_streams * ((n_frames + ya.ft - 1) / ya.ft) < 1024) ya.ft >>= 1;
+        while (ya.ft > 2 && (long long)n_out * ((n_frames + ya.ft - 1) / ya.ft) < 1024) ya.ft >>= 1;
         ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = out_pcm;
         const size_t smem3 = (size_t)(c->H + 1) * sizeof(float2) + (size_t)c->H * 4;
         if (smem3 > 64 * 1024)
             VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_synth), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3));
+        // a slot the call leaves out restarts from silence.  The kernel writes only the slots below n_sources, so the clear goes
+        // first: if it fails, nothing has touched the tails yet and tail_cur still names the valid ones
+        if (n_sources < c->max_sources)
+            VHIP_TRY(c, hipMemset2DAsync(ya.tail_out + (size_t)n_sources * c->H, (size_t)c->max_sources * c->H * 4, 0,
+                                         (size_t)(c->max_sources - n_sources) * c->H * 4, (size_t)n_streams, st));
         t_begin(c, 2, st);
-        hipLaunchKernelGGL(k_mvdr_synth, dim3((n_frames + ya.ft - 1) / ya.ft, n_streams), dim3(c->H >= 1024 ? 512 : 256), smem3, st, ya);
+        hipLaunchKernelGGL(k_mvdr_synth, dim3((n_frames + ya.ft - 1) / ya.ft, n_out), dim3(c->H >= 1024 ? 512 : 256), smem3, st, ya);
         t_end(c, st);
         c->tail_cur ^= 1;
     }
@@ -305,14 +355,20 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
     return MCA_HIP_OK;
 }
 
-int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, const float *doa_rad,
-                             float *out_pcm, float *out_spec)
+int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                            int n_frames, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
+{
+    return mca_hip_mvdr_sources_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, 1, doa_rad, out_pcm, out_spec, stream);
+}
+
+int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                                     float *out_pcm, float *out_spec)
 {
     if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_streams < 1 || n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames < 1");
+    if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long ms = (long long)(n_frames + 1) * c->H, ss = ms * c->M;
-    const size_t nf = (size_t)n_streams * n_frames;
+    const size_t nf = (size_t)n_streams * n_frames * n_sources;
     float *d_pcm = (float *)c->stage.get(0, (size_t)ss * n_streams * 4), *d_doa = (float *)c->stage.get(1, nf * 4);
     float *d_out = out_pcm ? (float *)c->stage.get(2, nf * c->H * 4) : nullptr;
     float *d_spec = out_spec ? (float *)c->stage.get(3, nf * c->K * 8) : nullptr;
@@ -320,12 +376,18 @@ int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_stream
         return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
     VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
-    const int rc = mca_hip_mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, d_doa, d_out, d_spec, nullptr);
+    const int rc = mca_hip_mvdr_sources_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_out, d_spec, nullptr);
     if (rc) return rc;
     VHIP_TRY(c, hipDeviceSynchronize());
     if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
     if (out_spec) VHIP_TRY(c, hipMemcpy(out_spec, d_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, const float *doa_rad,
+                             float *out_pcm, float *out_spec)
+{
+    return mca_hip_mvdr_sources_frames_host(c, pcm, n_streams, n_frames, 1, doa_rad, out_pcm, out_spec);
 }
 
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
@@ -354,7 +416,7 @@ constexpr unsigned MVDR_MAGIC = 0x4d435644u;   // "MCVD"
 std::vector<BlobPart> mvdr_parts(mca_hip_mvdr_ctx *c)
 {
     const size_t ns = (size_t)c->cfg.max_streams;
-    return {{c->d_phi, ns * c->K * c->tri * sizeof(float2)}, {c->d_trace, ns * c->K * 4}, {c->d_tail[c->tail_cur], ns * c->H * 4}};
+    return {{c->d_phi, ns * c->K * c->tri * sizeof(float2)}, {c->d_trace, ns * c->K * 4}, {c->d_tail[c->tail_cur], ns * c->max_sources * c->H * 4}};
 }
 unsigned mvdr_cfg_hash(const mca_hip_mvdr_ctx *c)
 {
@@ -375,7 +437,9 @@ int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *c, void *blob, long long bytes)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    BlobHeader h{MVDR_MAGIC, 1, mvdr_cfg_hash(c), 0, {0, 0, 0, 0}};
+    // version 1: one tail per stream (a context that never raised max_sources writes what it always wrote);
+    // version 2: max_sources tails per stream, the maximum in host[0]
+    BlobHeader h{MVDR_MAGIC, c->max_sources > 1 ? 2 : 1, mvdr_cfg_hash(c), 0, {c->max_sources > 1 ? c->max_sources : 0, 0, 0, 0}};
     const int rc = blob_save(mvdr_parts(c), h, blob, bytes);
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
@@ -385,7 +449,14 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long byt
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     BlobHeader h;
-    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h);
+    if (blob && bytes >= (long long)sizeof(BlobHeader)) {
+        std::memcpy(&h, blob, sizeof(h));
+        const int blob_max = h.version == 2 ? (int)h.host[0] : 1;
+        if (h.magic == MVDR_MAGIC && (h.version == 1 || h.version == 2) && blob_max != c->max_sources)
+            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with max_sources = " + std::to_string(blob_max) +
+                                                              ", this one has " + std::to_string(c->max_sources));
+    }
+    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->max_sources > 1 ? 2 : 1);
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
 

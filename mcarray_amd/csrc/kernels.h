@@ -75,6 +75,7 @@ __global__ void k_mvdr_analyse(MvdrAnalyseArgs p);
 __global__ void k_mvdr_analyse_1024(MvdrAnalyseArgs p, int fpb);
 __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
 template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
+template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(MvdrSolveArgs p);
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 __global__ void k_tgcc_frames(TgccFrameArgs p);
 __global__ void k_tgcc_frame_f64(const double *Lp, const double *Rp, int W, int nd, int rem, double *res, double *index);

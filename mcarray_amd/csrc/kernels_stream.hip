@@ -1520,9 +1520,9 @@ __global__ __launch_bounds__(512) void k_mvdr_analyse_512(MvdrAnalyseArgs p, int
     // factored steering phasors of the block's frames (MvdrAnalyseArgs::T)
     {
         const int nhi = (512 >> 6) + 1, nph = nhi + 32;
-        for (int e = tid; e < (f_end - f_begin) * M * nph; e += 512) {
-            const int f = f_begin + e / (M * nph), rem = e % (M * nph), m = rem / nph, i = rem - m * nph;
-            const long long o = (long long)a * p.n_frames + f;
+        for (int e = tid; e < (f_end - f_begin) * p.S * M * nph; e += 512) {                  // rows (frame, look direction)
+            const int rem = e % (M * nph), m = rem / nph, i = rem - m * nph;
+            const long long o = ((long long)a * p.n_frames + f_begin) * p.S + e / (M * nph);
             const double cd = cos((double)p.doa_rad[o] + 1.57079632679489661923);   // cos(DOA + M_PI/2), Beamformer.cpp:59
             const int kk = i < nhi ? (i << 5) : i - nhi;
             double turns = (double)kk * (p.unit * p.mic_x[m] * cd);

@@ -458,14 +458,15 @@ struct MvdrAnalyseArgs {
     const float *pcm;
     long long stream_stride, mic_stride;
     int n_frames, N, logH, M;
+    int S;                    // look directions per frame (1 ... MCA_MAX_SOURCES)
     const float *window;
     const float2 *tw;         // [N/2]
-    const float *doa_rad;     // [streams][n_frames]
+    const float *doa_rad;     // [streams][n_frames][S]
     float2 *X;                // [streams][n_frames][K][M] one-sided spectra, microphone fastest
     // steering phasors of every (stream, frame, microphone), factored: d_m[k] = T[k >> 5] * T[nhi + (k & 31)] with
     // T[i < nhi] = exp(-j 2 pi 32 i u), T[nhi + i] = exp(-j 2 pi i u), u = fs/N/c x_m cos(DOA + pi/2) (Beamformer.cpp:59);
     // the phase is reduced in double.  N/64 + 33 sincos per microphone and frame instead of N/2 + 1.
-    float2 *T;                // [streams][n_frames][M][nhi + 32], nhi = N/64 + 1
+    float2 *T;                // [streams][n_frames][S][M][nhi + 32], nhi = N/64 + 1
     const double *mic_x;      // [M]
     double unit;              // fs / N / 346.1
 };
@@ -477,7 +478,7 @@ struct MvdrSolveArgs {
     long long pid0, n_prob;
     int pieces;
     const float2 *X;          // [streams][n_frames][K][M]
-    const float2 *T;          // [streams][n_frames][M][nhi + 32] factored steering phasors (MvdrAnalyseArgs)
+    const float2 *T;          // [streams][n_frames][S][M][nhi + 32] factored steering phasors (MvdrAnalyseArgs)
     int n_streams, n_frames, K, M;
     float alpha, one_minus_alpha, loading_over_m;
     float2 *phi;              // [streams][K][M(M+1)/2] lower triangle of the covariance, row-major (state at entry)
@@ -486,15 +487,25 @@ struct MvdrSolveArgs {
     // launch (every problem is read and written by one workgroup); a launch cut into pieces writes to a scratch copy, because
     // every piece reads the entry state when it starts and nothing orders that before the last piece's stores
     float2 *phi_out; float *trace_out; long long out_base;
-    float2 *Y;                // [streams][n_frames][K] beamformed spectrum
+    float2 *Y;                // [streams][S][n_frames][K] beamformed spectra
+    int S;                    // look directions per frame: k_mvdr_solve is the S == 1 kernel, k_mvdr_solve_sources<.., S, ..> the others
 };
 
+// k_mvdr_solve_sources<Q, FULL, S, S1>: S look directions per frame, S1 of them per pass of the factorisation's column loop.
+// X(Q, S, S1 of FULL, S1 of !FULL): S1 = S wherever that leaves the kernel without scratch under its launch bounds
+#define MCA_MVDR_SOURCES_TABLE(X) \
+    X(1, 2, 2, 2) X(1, 3, 3, 3) X(1, 4, 4, 4) \
+    X(2, 2, 2, 2) X(2, 3, 3, 3) X(2, 4, 4, 4) \
+    X(3, 2, 2, 2) X(3, 3, 3, 3) X(3, 4, 4, 4) \
+    X(4, 2, 2, 2) X(4, 3, 3, 3) X(4, 4, 2, 2)
+
 struct MvdrSynthArgs {
-    const float2 *Y;          // [streams][n_frames][K]
+    const float2 *Y;          // [streams][S][n_frames][K]
     int n_frames, N, logH, ft;
+    int S, tail_slots;        // outputs per stream in this call; tail slots per stream in the context (>= S)
     const float2 *tw;
-    const float *tail_in; float *tail_out;   // [streams][N/2] overlap-add carry
-    float *out;               // [streams][n_frames * N/2]
+    const float *tail_in; float *tail_out;   // [streams][tail_slots][N/2] overlap-add carry
+    float *out;               // [streams][S][n_frames * N/2]
 };
 
 // ---- TemporalGCCBinauralLocalisation (kernels_tgcc.hip) ----

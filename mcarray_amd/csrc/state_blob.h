@@ -38,12 +38,13 @@ inline int blob_save(const std::vector<BlobPart> &parts, const BlobHeader &h, vo
 }
 
 // 0 = ok, 1 = NULL / truncated, 2 = HIP error, 3 = not a blob of this kind / version, 4 = other configuration
-inline int blob_load(const std::vector<BlobPart> &parts, unsigned magic, unsigned cfg_hash, const void *blob, long long bytes, BlobHeader *h_out)
+inline int blob_load(const std::vector<BlobPart> &parts, unsigned magic, unsigned cfg_hash, const void *blob, long long bytes, BlobHeader *h_out,
+                     int version = 1)
 {
     if (!blob || bytes < (long long)sizeof(BlobHeader)) return 1;
     BlobHeader h;
     std::memcpy(&h, blob, sizeof(h));
-    if (h.magic != magic || h.version != 1) return 3;
+    if (h.magic != magic || h.version != version) return 3;
     if (h.cfg_hash != cfg_hash) return 4;
     if (bytes < blob_size(parts)) return 1;
     if (hipDeviceSynchronize() != hipSuccess) return 2;
