@@ -59,6 +59,15 @@ public:
             throw MCArrayException("setDOAs: between 1 and the setMaxSources() maximum of look directions");
         _doas = doasRadians;
     }
+    // Soft nulls at the other look directions of setDOAs() (mca_hip_mvdr_set_null_gain: finite, 0 ... 1000; 0, the default, is
+    // the plain MVDR output).  Applies to the frames completed from now on; no part of the stream's state.
+    void setNullGain(double nullGain) { check(mca_hip_mvdr_set_null_gain(_ctx, nullGain)); }
+    double getNullGain() const
+    {
+        double g = 0.0;
+        check(mca_hip_mvdr_get_null_gain(_ctx, &g));
+        return g;
+    }
     void reset()
     {
         check(mca_hip_mvdr_reset(_ctx, nullptr));

@@ -604,6 +604,22 @@ int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev,
                                     float *out_spec_dev, void *stream);
 int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
                                      const float *doa_rad, float *out_pcm, float *out_spec);
+/* Soft nulls at the other look directions of a mca_hip_mvdr_sources_frames_* call (n_sources >= 2).  With d_s the steering
+ * vector of look direction s, PhiL the loaded covariance as above and g = null_gain >= 0, per stream, bin and frame:
+ *     p_r   = 1 / (d_r^H PhiL^-1 d_r)                     the MVDR power estimate towards r
+ *     Phi_s = PhiL + g * sum_{r != s} p_r d_r d_r^H        a virtual interferer at every other look direction, g times that power
+ *     w_s   = Phi_s^-1 d_s / (d_s^H Phi_s^-1 d_s),  Y_s[k] = w_s^H x
+ * g = 0 (the default) is the plain MVDR output of the call above, by the same kernel and with the same bytes; g -> infinity tends
+ * to the hard LCMV nulls.  Every finite g is well posed, coincident directions, bin 0 (where all d_s are equal) and
+ * n_sources > n_mics included: there the output tends to the plain MVDR output.  The response towards the own direction is 1 for
+ * every g, and a bin in digital silence (trace <= 1e-30) keeps w = d/M per direction.
+ * Accepted: finite values in [0, 1000]; anything else is MCA_HIP_ERR_INVALID_ARGUMENT and leaves the gain as it was (the output's
+ * denominator cancels by up to 1 + g where directions coincide: fp32 eps * 1001 stays an order of magnitude under the 5e-4 of the
+ * peak this module is held to).  The gain is a processing parameter, not stream state: it may change between calls, the
+ * covariance a call leaves does not depend on it, state blobs neither carry nor check it.  With n_sources = 1 and through the
+ * single-look entry points it has no effect. */
+int mca_hip_mvdr_set_null_gain(mca_hip_mvdr_ctx *ctx, double null_gain);
+int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *ctx, double *null_gain);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream */

@@ -214,6 +214,8 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp]),
     ("mca_hip_mvdr_set_max_sources", C.c_int, [C.c_void_p, C.c_int]),
+    ("mca_hip_mvdr_set_null_gain", C.c_int, [C.c_void_p, C.c_double]),
+    ("mca_hip_mvdr_get_null_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("mca_hip_mvdr_sources_frames_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_sources_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp]),

@@ -807,11 +807,14 @@ class MvdrBeamformer(_StateBlob):
     """Frequency-domain beamformer with a per-bin spatial covariance (BASELINE.json configs[3]; SURVEY A.9).
     No reference counterpart: the interface follows mca::Beamformer (Beamformer.h:39,49: frames in, one channel out,
     a look direction in radians) with the delay-and-sum weights replaced by MVDR weights.
-    max_sources > 1 (up to 4) lets process_sources() separate that many look directions per frame from the one covariance."""
+    max_sources > 1 (up to 4) lets process_sources() separate that many look directions per frame from the one covariance;
+    null_gain > 0 (up to 1000) makes every output of process_sources() steer a soft null at the other look directions of its
+    frame (include/mcarray_hip.h, mca_hip_mvdr_set_null_gain; 0 is the plain MVDR output)."""
 
     K_ANALYSE, K_SOLVE, K_SYNTH = 0, 1, 2
 
-    def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1):
+    def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
+                 null_gain=0.0):
         self._lib = _lib.load()
         xyz = _xyz(mic_positions)
         cfg = _lib.MvdrConfig()
@@ -831,17 +834,31 @@ class MvdrBeamformer(_StateBlob):
         self.h = h
         self.M, self.N, self.hop, self.K = len(xyz), fft_size, fft_size // 2, fft_size // 2 + 1
         self.max_sources = 1
-        if max_sources != 1:
-            try:
+        self.null_gain = 0.0
+        try:
+            if max_sources != 1:
                 self.set_max_sources(max_sources)
-            except MCArrayHipError:
-                self.close()
-                raise
+            if null_gain != 0.0:
+                self.set_null_gain(null_gain)
+        except MCArrayHipError:
+            self.close()
+            raise
 
     def set_max_sources(self, max_sources):
         """look directions per frame process_sources() may carry (1 ... 4): one overlap-add tail per stream and source"""
         self._check(self._lib.mca_hip_mvdr_set_max_sources(self.h, int(max_sources)))
         self.max_sources = int(max_sources)
+
+    def set_null_gain(self, null_gain):
+        """gain of the soft nulls process_sources() steers at the other look directions (finite, 0 ... 1000; 0: plain MVDR).  A
+        processing parameter: it may change between calls and is no part of the state blobs."""
+        self._check(self._lib.mca_hip_mvdr_set_null_gain(self.h, float(null_gain)))
+        self.null_gain = float(null_gain)
+
+    def get_null_gain(self):
+        g = C.c_double(0.0)
+        self._check(self._lib.mca_hip_mvdr_get_null_gain(self.h, C.byref(g)))
+        return g.value
 
     def close(self):
         if getattr(self, "h", None):

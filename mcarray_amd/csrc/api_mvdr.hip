@@ -26,6 +26,8 @@ struct mca_hip_mvdr_ctx {
     float *d_trace = nullptr;     // [max_streams][K]
     float2 *d_phi_tail = nullptr; float *d_trace_tail = nullptr;   // exit state of the pieced tail launch (<= 128 workgroups x 64 problems), copied back behind it
     int max_sources = 1;          // look directions per frame a call may carry (mca_hip_mvdr_set_max_sources)
+    double null_gain = 0.0;       // soft nulls at the other look directions of a call with n_sources >= 2 (mca_hip_mvdr_set_null_gain);
+                                  // a processing parameter, not stream state: no part of the state blobs
     float *d_tail[2] = {nullptr, nullptr}; int tail_cur = 0;   // [max_streams][max_sources][H]; a single-look call uses slot 0
     // workspace
     float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
@@ -217,6 +219,24 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_set_null_gain(mca_hip_mvdr_ctx *c, double null_gain)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    // the cap: the denominator of the nulled output cancels by up to 1 + null_gain, and fp32 eps (1 + 1000) stays an order of
+    // magnitude under the module's 5e-4 parity bar
+    if (!std::isfinite(null_gain) || null_gain < 0.0 || null_gain > 1000.0)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "null_gain must be finite and in [0,1000]");
+    c->null_gain = null_gain;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *c, double *null_gain)
+{
+    if (!c || !null_gain) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    *null_gain = c->null_gain;
+    return MCA_HIP_OK;
+}
+
 // the three launches of a call with n_sources look directions per frame: doa_rad [streams][F][n_sources],
 // out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]
 int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
@@ -279,6 +299,8 @@ int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long 
     sa.loading_over_m = (float)(c->cfg.loading / c->M);
     sa.phi = c->d_phi; sa.trace = c->d_trace; sa.Y = Y;
     sa.n_streams = n_streams; sa.S = n_sources;
+    const float null_gain = (float)c->null_gain;
+    const bool nulls = n_sources > 1 && null_gain > 0.f;                              // a gain that rounds to 0 in fp32 is gain 0
     const int Q = (c->M + 3) / 4;                                                     // row slots per lane
     auto launch_solve = [&](long long pid0, long long n_prob, int pieces) {
         sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
@@ -292,7 +314,16 @@ int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long 
         if (c->M == 4 * (QQ)) hipLaunchKernelGGL((k_mvdr_solve<QQ, true>), sgrid, dim3(256), 0, st, sa);   \
         else hipLaunchKernelGGL((k_mvdr_solve<QQ, false>), sgrid, dim3(256), 0, st, sa);                   \
     } while (0)
-        if (n_sources > 1) {
+        if (nulls) {
+            // several look directions with soft nulls at each other's: a kernel of its own, dynamic LDS by its instantiation (44 KiB at the most)
+            const MvdrNullsArgs na{sa, null_gain};
+#define SOLVE_NULLS(QQ, SS, S1, PF)                                                                                         \
+    if (Q == QQ && n_sources == SS)                                                                                        \
+        hipLaunchKernelGGL((k_mvdr_nulls<QQ, SS, S1, PF>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, na);
+            MCA_MVDR_NULLS_TABLE(SOLVE_NULLS)
+#undef SOLVE_NULLS
+        }
+        else if (n_sources > 1) {
             // several look directions: the instantiation of (row slots, directions), with its directions per pass (mca_internal.h)
             const bool full = c->M == 4 * Q;
 #define SOLVE_SOURCES(QQ, SS, S1F, S1P)                                                                                    \

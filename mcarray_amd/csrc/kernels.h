@@ -76,6 +76,7 @@ __global__ void k_mvdr_analyse_1024(MvdrAnalyseArgs p, int fpb);
 __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
 template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
 template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(MvdrSolveArgs p);
+template <int Q, int S, int S1, bool PF> __global__ void k_mvdr_nulls(MvdrNullsArgs pa);   // soft nulls at the other look directions
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 __global__ void k_tgcc_frames(TgccFrameArgs p);
 __global__ void k_tgcc_frame_f64(const double *Lp, const double *Rp, int W, int nd, int rem, double *res, double *index);

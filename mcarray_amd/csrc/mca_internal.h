@@ -499,6 +499,23 @@ struct MvdrSolveArgs {
     X(3, 2, 2, 2) X(3, 3, 3, 3) X(3, 4, 4, 4) \
     X(4, 2, 2, 2) X(4, 3, 3, 3) X(4, 4, 2, 2)
 
+// k_mvdr_nulls<Q, S, S1, PF>: the same with soft nulls at the other look directions.  X(Q, S, S1, PF): the
+// directions per pass and whether the next frame's spectra are loaded a frame ahead, again by what leaves the kernel without
+// scratch; one instantiation serves M = 4Q and M < 4Q (the branch-free M = 4Q form costs this kernel registers, it saves none)
+#define MCA_MVDR_NULLS_TABLE(X) \
+    X(1, 2, 2, true) X(1, 3, 3, true) X(1, 4, 4, true) \
+    X(2, 2, 2, true) X(2, 3, 3, true) X(2, 4, 4, true) \
+    X(3, 2, 2, true) X(3, 3, 3, true) X(3, 4, 4, true) \
+    X(4, 2, 2, true) X(4, 3, 3, true) X(4, 4, 2, false)
+// dynamic LDS of a k_mvdr_nulls workgroup: the parked u [Q][S][256] float2 and, with several passes, num / den [S][256]
+inline int mvdr_nulls_lds_bytes(int Q, int S, int S1) { return 256 * (8 * Q * S + (S1 < S ? 12 * S : 0)); }
+// the arguments of k_mvdr_nulls: a struct of its own, so that MvdrSolveArgs and with it the code of the kernels that take it
+// stay as they are
+struct MvdrNullsArgs {
+    MvdrSolveArgs s;
+    float null_gain;          // > 0: gain of the soft nulls at the other look directions
+};
+
 struct MvdrSynthArgs {
     const float2 *Y;          // [streams][S][n_frames][K]
     int n_frames, N, logH, ft;

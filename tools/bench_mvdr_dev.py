@@ -1,6 +1,10 @@
 """Device-side throughput of the MVDR path (BASELINE.json configs[3]: 16 microphones, 256 concurrent streams x 64 frames)
 on device buffers, with the per-kernel split from the library's HIP events and a parity spot check of stream 0
-against the CPU oracle.  Usage: python tools/bench_mvdr_dev.py [--streams 256] [--frames 64] [--mics 16] [--steps 10]"""
+against the CPU oracle.  Usage: python tools/bench_mvdr_dev.py [--streams 256] [--frames 64] [--mics 16] [--steps 10]
+With --sources S (2 ... 4) it times the sources call with S look directions per frame instead, under --null-gain g (soft nulls
+at the other look directions; 0, the default, is the plain sources call), and the spot check goes against the float64 twin of
+that call (tests/mvdr_nulls_twin.py).  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the
+entry points it lacks are left unbound, --null-gain must then stay 0."""
 import argparse
 import json
 import os
@@ -12,7 +16,17 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from mcarray_amd import api, synth  # noqa: E402
+from mcarray_amd import _lib, api, synth  # noqa: E402
+
+LOOK = [0.35, -0.15, 0.8, -0.45]       # look directions of --sources (radians): the first two 0.5 rad apart
+
+
+def bind_what_the_library_has():
+    """an older build side by side (MCA_HIP_LIB): leave the entry points it lacks unbound"""
+    import ctypes as C
+    _lib._pin_single_hip_runtime()
+    probe = C.CDLL(_lib.LIB_PATH)
+    _lib.SYMBOLS = [sym for sym in _lib.SYMBOLS if hasattr(probe, sym[0])]
 
 
 def main():
@@ -23,7 +37,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--check", type=int, default=1)
+    ap.add_argument("--sources", type=int, default=0, help="time the sources call with this many look directions per frame")
+    ap.add_argument("--null-gain", type=float, default=0.0, help="gain of the soft nulls of the sources call")
     a = ap.parse_args()
+    if a.null_gain != 0.0 and a.sources < 2:
+        ap.error("--null-gain needs --sources 2 ... 4")
+    if os.environ.get("MCA_HIP_LIB"):
+        bind_what_the_library_has()
     fs, N = 48000, 1024
     hop, K = N // 2, N // 2 + 1
     xs = [0.32 / a.mics * m for m in range(a.mics)] if a.mics != 16 else synth.ULA16
@@ -34,15 +54,34 @@ def main():
     if a.check:
         p0 = synth.noise_source_stream(xs, np.deg2rad(20.0), fs, L, 77) + synth.noise_source_stream(xs, np.deg2rad(-50.0), fs, L, 78, snr_db=60)
         pcm[0] = torch.from_numpy(p0.astype(np.float32)).to(dev)
-    doa = torch.full((a.streams, a.frames), float(np.deg2rad(20.0)), device=dev, dtype=torch.float32)
-    out = torch.empty((a.streams, a.frames * hop), device=dev, dtype=torch.float32)
-    bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams)
     st = torch.cuda.current_stream().cuda_stream
+    if a.sources:
+        look = torch.tensor(LOOK[:a.sources], device=dev, dtype=torch.float32)
+        doa = look[None, None, :].expand(a.streams, a.frames, a.sources).contiguous()
+        out = torch.empty((a.streams, a.sources, a.frames * hop), device=dev, dtype=torch.float32)
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=a.sources)
+        if a.null_gain != 0.0:
+            bf.set_null_gain(a.null_gain)
+        step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
+    else:
+        doa = torch.full((a.streams, a.frames), float(np.deg2rad(20.0)), device=dev, dtype=torch.float32)
+        out = torch.empty((a.streams, a.frames * hop), device=dev, dtype=torch.float32)
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams)
+        step = lambda: bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
     for _ in range(a.warmup):
-        bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
+        step()
     torch.cuda.synchronize()
     res = {}
-    if a.check:
+    if a.check and a.sources:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import mvdr_nulls_twin as nt
+        bf.reset()
+        step()
+        torch.cuda.synchronize()
+        tw = nt.mvdr_nulls_stream(fs, N, xs, pcm[0].cpu().numpy().astype(np.float64), doa[0].cpu().numpy(), a.null_gain)
+        res["audio_err_rel_max"] = float(max(np.abs(out[0, s].cpu().numpy() - tw["out"][s]).max() / np.abs(tw["out"][s]).max()
+                                             for s in range(a.sources)))
+    elif a.check:
         from oracle import pyoracle as po
         bf.reset()
         bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
@@ -54,10 +93,12 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
+        step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     frames = a.streams * a.frames
+    if a.sources:
+        res.update(dict(sources=a.sources, null_gain=a.null_gain, lib=os.environ.get("MCA_HIP_LIB", "default")))
     res.update(dict(workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N), ms_per_step=dt * 1e3,
                     frames_per_s=frames / dt, algorithmic_GBps=frames / dt * (a.mics * hop * 4 + hop * 4) / 1e9))
     for kid, name in ((0, "k_mvdr_analyse"), (1, "k_mvdr_solve"), (2, "k_mvdr_synth")):

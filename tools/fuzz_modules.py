@@ -1,4 +1,4 @@
-"""Randomised parity sweep of the 2-channel masking module and the MVDR beamformer against the CPU oracle (a one-off check like
+"""Randomised parity sweep of the 2-channel masking module, the MVDR beamformer and its sources call with soft nulls against the CPU oracle (a one-off check like
 tools/fuzz_parity.py): random frame lengths, methods / algorithms, channel counts, geometries, memories, loadings, chunked calls.
 usage (GPU box): python tools/fuzz_modules.py [cases] [seed]"""
 import os
@@ -9,6 +9,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mcarray_amd import api, synth  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import mvdr_nulls_twin as nt  # noqa: E402
 
 
 def mask_case(rng):
@@ -75,18 +78,55 @@ def mvdr_case(rng):
     return worst <= 5e-4, "%s cut=%d worst rel err %.1e" % (tag, cut, worst)
 
 
+def mvdr_nulls_case(rng):
+    """the sources call with soft nulls at the other look directions against its float64 twin (tests/mvdr_nulls_twin.py):
+    random geometry, frame size, S, gain and directions, now and then with two directions equal"""
+    fs, N = [(8000, 256), (16000, 512), (48000, 1024)][int(rng.integers(0, 3))]
+    M, S = int(rng.integers(2, 17)), int(rng.integers(2, 5))
+    xs = np.sort(rng.uniform(0, 0.03 * M, M))
+    F, A = int(rng.integers(1, 25)), int(rng.integers(1, 4))
+    alpha, loading = float(rng.choice([0.0, 0.5, 0.9, 0.95, 0.99])), float(rng.choice([1e-3, 1e-2, 1e-1]))
+    gain = float(rng.choice([0.1, 1.0, 10.0, 100.0, rng.uniform(0.0, 100.0)]))
+    hop = N // 2
+    pcm = np.stack([synth.noise_source_stream(xs, rng.uniform(-1.3, 1.3), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)))
+                    + synth.noise_source_stream(xs, rng.uniform(-1.3, 1.3), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)), snr_db=50)
+                    for _ in range(A)]).astype(np.float32)
+    doa = rng.uniform(-1.4, 1.4, (A, F, S)).astype(np.float32)
+    same = bool(rng.integers(0, 3) == 0)
+    if same:
+        doa[:, :, S - 1] = doa[:, :, 0]
+    tag = "mvdr nulls fs=%d N=%d M=%d S=%d A=%d F=%d alpha=%.2f loading=%.0e gain=%.3g%s" % (fs, N, M, S, A, F, alpha, loading, gain,
+                                                                                            " coincident" if same else "")
+    bf = api.MvdrBeamformer(fs, xs, N, alpha, loading, max_streams=A, max_sources=S, null_gain=gain)
+    cut = int(rng.integers(1, F)) if F > 2 and rng.integers(0, 2) else 0
+    if cut:
+        ra = bf.process_sources(pcm[:, :, :(cut + 1) * hop], doa[:, :cut])
+        rb = bf.process_sources(pcm[:, :, cut * hop:], doa[:, cut:])
+        out, spec = np.concatenate([ra["out"], rb["out"]], axis=2), np.concatenate([ra["spec"], rb["spec"]], axis=2)
+    else:
+        r = bf.process_sources(pcm, doa); out, spec = r["out"], r["spec"]
+    worst = 0.0
+    for a in range(A):
+        tw = nt.mvdr_nulls_stream(fs, N, xs, pcm[a].astype(np.float64), doa[a], gain, alpha, loading)
+        for s_ in range(S):
+            worst = max(worst, np.abs(spec[a, s_] - tw["spec"][s_]).max() / np.abs(tw["spec"][s_]).max(),
+                        np.abs(out[a, s_] - tw["out"][s_]).max() / np.abs(tw["out"][s_]).max())
+    bf.close()
+    return bool(np.isfinite(worst) and worst <= 5e-4), "%s cut=%d worst rel err %.1e" % (tag, cut, worst)
+
+
 def main(cases, seed):
     rng = np.random.default_rng(seed)
     bad = 0
     for case in range(cases):
-        for fn in (mask_case, mvdr_case):
+        for fn in (mask_case, mvdr_case, mvdr_nulls_case):
             try:
                 ok, msg = fn(rng)
             except api.MCArrayHipError as e:
                 ok, msg = False, "%s raised %s" % (fn.__name__, e)
             print(("ok   " if ok else "FAIL ") + "case %d: %s" % (case, msg), flush=True)
             bad += 0 if ok else 1
-    print("%d cases x 2, %d failures" % (cases, bad))
+    print("%d cases x 3, %d failures" % (cases, bad))
     return 1 if bad else 0
 
 
