@@ -68,6 +68,44 @@ public:
         check(mca_hip_mvdr_get_null_gain(_ctx, &g));
         return g;
     }
+    // The Capon spatial spectrum of the covariance the stream holds, and its peaks (mca_hip_mvdr_spectrum_*): nAngles 2 ... 361 from
+    // -pi/2 to pi/2, the band of bins [binLo, binHi], weighting MCA_HIP_MVDR_SPECTRUM_POWER / _NORMALISED, nPeaks 1 ... 4.  The peak
+    // angles are look directions as setDOAs() takes them: process a chunk, read peaks(), setDOAs() for the next chunk.
+    void configureSpectrum(int nAngles, int binLo, int binHi, int weighting = MCA_HIP_MVDR_SPECTRUM_NORMALISED, int nPeaks = 1)
+    {
+        mca_hip_mvdr_spectrum_config cfg;
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.n_angles = nAngles;
+        cfg.bin_lo = binLo;
+        cfg.bin_hi = binHi;
+        cfg.weighting = weighting;
+        cfg.n_peaks = nPeaks;
+        check(mca_hip_mvdr_spectrum_configure(_ctx, &cfg));
+        _nAngles = nAngles;
+        _nPeaks = nPeaks;
+    }
+    std::vector<double> spectrumGrid() const                   // the grid's angles (radians)
+    {
+        if (_nAngles == 0) throw MCArrayException("spectrumGrid: configureSpectrum() first");
+        std::vector<float> g(static_cast<size_t>(_nAngles));
+        check(mca_hip_mvdr_spectrum_get_grid(_ctx, g.data()));
+        return std::vector<double>(g.begin(), g.end());
+    }
+    void spectrum(std::vector<double> &values)                 // [nAngles]
+    {
+        if (_nAngles == 0) throw MCArrayException("spectrum: configureSpectrum() first");
+        std::vector<float> s(static_cast<size_t>(_nAngles));
+        check(mca_hip_mvdr_spectrum_host(_ctx, 1, s.data(), nullptr, nullptr));
+        values.assign(s.begin(), s.end());
+    }
+    void peaks(std::vector<double> &doaRadians, std::vector<double> &values)   // [nPeaks] each, ranked by value
+    {
+        if (_nAngles == 0) throw MCArrayException("peaks: configureSpectrum() first");
+        std::vector<float> d(static_cast<size_t>(_nPeaks)), v(static_cast<size_t>(_nPeaks));
+        check(mca_hip_mvdr_spectrum_host(_ctx, 1, nullptr, d.data(), v.data()));
+        doaRadians.assign(d.begin(), d.end());
+        values.assign(v.begin(), v.end());
+    }
     void reset()
     {
         check(mca_hip_mvdr_reset(_ctx, nullptr));
@@ -146,6 +184,7 @@ private:
     int _nchannels, _N;
     double _doa = 0.0;
     int _maxSources = 1;
+    int _nAngles = 0, _nPeaks = 0;
     std::vector<double> _doas;
     mca_hip_mvdr_ctx *_ctx = nullptr;
     std::vector<std::vector<float> > _pending;

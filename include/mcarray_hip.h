@@ -620,13 +620,50 @@ int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *ctx, const float *pcm, in
  * single-look entry points it has no effect. */
 int mca_hip_mvdr_set_null_gain(mca_hip_mvdr_ctx *ctx, double null_gain);
 int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *ctx, double *null_gain);
+/* Capon (minimum-variance) spatial spectrum of the covariance the context holds now (after its last frames call or state load),
+ * and its peaks: the MVDR power estimate p = 1 / (d^H PhiL^-1 d) of the nulls above on a grid of angles.  Per stream, with
+ *     theta_i      = -pi/2 + i pi/(D-1), i = 0 ... D-1 (in double),       D = n_angles
+ *     d(theta,k)_m = exp(-j k 2 pi fs/(N c) x_m cos(theta + pi/2))        the steering of this module (Beamformer.cpp:59)
+ *     PhiL[k]      = Phi[k] + loading tr[k]/M I                           the module's loading
+ *     q[k][i]      = d(theta_i,k)^H PhiL[k]^-1 d(theta_i,k)               real, > 0
+ *     P[i]         = sum over k in [bin_lo, bin_hi] with tr[k] > 1e-30 of w[k] / q[k][i]
+ * MCA_HIP_MVDR_SPECTRUM_POWER: w[k] = 1, the sum of the per-bin Capon power estimates.  MCA_HIP_MVDR_SPECTRUM_NORMALISED:
+ * w[k] = M / tr[k], every bin weighted by its own level (the PHAT-like choice; a spatially white bin adds (1 + loading)/M at every
+ * angle).  Bins in digital silence (trace <= 1e-30) add nothing; a stream with no live bin in the band has P = 0 everywhere.
+ * Peaks: i is a local maximum if P[i] > 0, P[i] > P[i-1] (or i = 0) and P[i] >= P[i+1] (or i = D-1); local maxima are ranked by
+ * value, descending, ties to the lower index; slot r < n_peaks gets peak_doa[r] = (float) theta_i and peak_val[r] = P[i].  Slots
+ * beyond the number of local maxima get peak_val = 0 and the peak_doa of slot 0 (0.0 rad if there is no local maximum at all):
+ * repeating slot 0 is safe to hand to mca_hip_mvdr_sources_frames_*, where coincident directions are well posed.  A peak angle
+ * means what every other look direction of this module means.
+ * Accepted: n_angles 2 ... 361, 0 <= bin_lo <= bin_hi <= N/2, weighting 0 or 1, n_peaks 1 ... 4 (the most look directions a call carries); anything else is
+ * MCA_HIP_ERR_INVALID_ARGUMENT and leaves the former configuration in place.  A spectrum call before configure, with n_streams
+ * outside 1 ... max_streams or with all three outputs NULL is MCA_HIP_ERR_INVALID_ARGUMENT.  Streams 0 ... n_streams-1 are
+ * scanned.  The configuration is a processing parameter like the null gain: it may change between calls, state blobs neither
+ * carry nor check it.  The call reads the stream state and writes none of it; its result is a pure function of state and
+ * configuration (no atomics: the same bytes on every run).
+ *   spectrum_dev [streams][D] float, peak_doa_dev / peak_val_dev [streams][n_peaks] float; each may be NULL, not all three */
+#define MCA_HIP_MVDR_SPECTRUM_POWER 0
+#define MCA_HIP_MVDR_SPECTRUM_NORMALISED 1
+typedef struct {
+    int struct_size;
+    int n_angles;            /* D */
+    int bin_lo, bin_hi;      /* the band, both ends included */
+    int weighting;           /* MCA_HIP_MVDR_SPECTRUM_POWER / _NORMALISED */
+    int n_peaks;
+} mca_hip_mvdr_spectrum_config;
+int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_spectrum_config *cfg);
+int mca_hip_mvdr_spectrum_get_grid(const mca_hip_mvdr_ctx *ctx, float *doa_rad);      /* [D] (float) theta_i */
+int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum_dev, float *peak_doa_dev, float *peak_val_dev,
+                              void *stream);
+int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum, float *peak_doa, float *peak_val);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream */
 long long mca_hip_mvdr_state_size(const mca_hip_mvdr_ctx *ctx);
 int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long blob_bytes);
-/* per-kernel timing as mca_hip_set_timing / mca_hip_get_timing: kernel_id 0 = analysis, 1 = solve, 2 = synthesis */
+/* per-kernel timing as mca_hip_set_timing / mca_hip_get_timing: kernel_id 0 = analysis, 1 = solve, 2 = synthesis,
+ * 3 = spectrum (both kernels of a mca_hip_mvdr_spectrum_* call) */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

@@ -95,6 +95,17 @@ class MvdrConfig(C.Structure):
     ]
 
 
+class MvdrSpectrumConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("n_angles", C.c_int),
+        ("bin_lo", C.c_int),
+        ("bin_hi", C.c_int),
+        ("weighting", C.c_int),
+        ("n_peaks", C.c_int),
+    ]
+
+
 class Gcc2TrackerConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -219,6 +230,10 @@ SYMBOLS = [
     ("mca_hip_mvdr_sources_frames_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_sources_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_spectrum_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrSpectrumConfig)]),
+    ("mca_hip_mvdr_spectrum_get_grid", C.c_int, [C.c_void_p, c_fp]),
+    ("mca_hip_mvdr_spectrum_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_spectrum_host", C.c_int, [C.c_void_p, C.c_int, c_fp, c_fp, c_fp]),
     ("mca_hip_mvdr_get_covariance", C.c_int, [C.c_void_p, C.c_int, c_dp]),
     ("mca_hip_mvdr_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mca_hip_mvdr_get_timing", C.c_int, [C.c_void_p, C.c_int, c_ip, c_dp]),

@@ -809,9 +809,11 @@ class MvdrBeamformer(_StateBlob):
     a look direction in radians) with the delay-and-sum weights replaced by MVDR weights.
     max_sources > 1 (up to 4) lets process_sources() separate that many look directions per frame from the one covariance;
     null_gain > 0 (up to 1000) makes every output of process_sources() steer a soft null at the other look directions of its
-    frame (include/mcarray_hip.h, mca_hip_mvdr_set_null_gain; 0 is the plain MVDR output)."""
+    frame (include/mcarray_hip.h, mca_hip_mvdr_set_null_gain; 0 is the plain MVDR output).
+    configure_spectrum() / spectrum() read the Capon spatial spectrum of the held covariance and its peaks: the look directions
+    of the next chunk (mca_hip_mvdr_spectrum_*)."""
 
-    K_ANALYSE, K_SOLVE, K_SYNTH = 0, 1, 2
+    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM = 0, 1, 2, 3
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  null_gain=0.0):
@@ -835,6 +837,8 @@ class MvdrBeamformer(_StateBlob):
         self.M, self.N, self.hop, self.K = len(xyz), fft_size, fft_size // 2, fft_size // 2 + 1
         self.max_sources = 1
         self.null_gain = 0.0
+        self.max_streams = max_streams
+        self.spectrum_config = None
         try:
             if max_sources != 1:
                 self.set_max_sources(max_sources)
@@ -936,6 +940,53 @@ class MvdrBeamformer(_StateBlob):
         self._check(self._lib.mca_hip_mvdr_sources_frames_dev(
             self.h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), A, n_frames, doa_rad.shape[2], doa_rad.data_ptr(),
             out_pcm.data_ptr() if out_pcm is not None else None, out_spec.data_ptr() if out_spec is not None else None, stream))
+
+    SPECTRUM_POWER, SPECTRUM_NORMALISED = 0, 1
+
+    def configure_spectrum(self, n_angles, bin_lo=None, bin_hi=None, weighting="normalised", n_peaks=1):
+        """the Capon spatial spectrum spectrum() evaluates on the covariance the context holds (include/mcarray_hip.h,
+        mca_hip_mvdr_spectrum_configure): n_angles 2 ... 361 from -pi/2 to pi/2, the band of bins [bin_lo, bin_hi] (default
+        1 ... N/2 - 1), weighting "power" or "normalised", n_peaks 1 ... 4.  A processing parameter: it may change between calls
+        and is no part of the state blobs."""
+        kinds = {"power": self.SPECTRUM_POWER, "normalised": self.SPECTRUM_NORMALISED}
+        cfg = _lib.MvdrSpectrumConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrSpectrumConfig)
+        cfg.n_angles = int(n_angles)
+        cfg.bin_lo = 1 if bin_lo is None else int(bin_lo)
+        cfg.bin_hi = self.N // 2 - 1 if bin_hi is None else int(bin_hi)
+        cfg.weighting = kinds[weighting] if weighting in kinds else int(weighting)
+        cfg.n_peaks = int(n_peaks)
+        self._check(self._lib.mca_hip_mvdr_spectrum_configure(self.h, C.byref(cfg)))
+        self.spectrum_config = dict(n_angles=cfg.n_angles, bin_lo=cfg.bin_lo, bin_hi=cfg.bin_hi, weighting=cfg.weighting, n_peaks=cfg.n_peaks)
+
+    def spectrum_grid(self):
+        """float32 [D]: the angles of the spectrum's grid (radians), as peak_doa reports them"""
+        if getattr(self, "spectrum_config", None) is None:
+            raise MCArrayHipError("configure_spectrum() first")
+        g = np.empty(self.spectrum_config["n_angles"], dtype=np.float32)
+        self._check(self._lib.mca_hip_mvdr_spectrum_get_grid(self.h, g.ctypes.data_as(_lib.c_fp)))
+        return g
+
+    def spectrum(self, n_streams=None):
+        """the spectrum of streams 0 ... n_streams - 1 (default: all) and its peaks -> dict(spectrum [A][D], peak_doa [A][P] radians,
+        peak_val [A][P]), float32.  peak_doa is a valid doa_rad[:, t, :] of the next process_sources() call.  Reads the stream state,
+        writes none of it."""
+        cfgd = getattr(self, "spectrum_config", None)
+        A = self.max_streams if n_streams is None else int(n_streams)
+        D, P = (cfgd["n_angles"], cfgd["n_peaks"]) if cfgd else (1, 1)
+        spec = np.empty((max(A, 0), D), dtype=np.float32)
+        doa = np.empty((max(A, 0), P), dtype=np.float32)
+        val = np.empty((max(A, 0), P), dtype=np.float32)
+        fp = _lib.c_fp
+        self._check(self._lib.mca_hip_mvdr_spectrum_host(self.h, A, spec.ctypes.data_as(fp), doa.ctypes.data_as(fp), val.ctypes.data_as(fp)))
+        return dict(spectrum=spec, peak_doa=doa, peak_val=val)
+
+    def spectrum_dev(self, n_streams, spectrum=None, peak_doa=None, peak_val=None, stream=None):
+        """device tensors (torch, contiguous float32): spectrum [A][D], peak_doa / peak_val [A][n_peaks]; any may be None, not all;
+        asynchronous on `stream` (a raw hipStream_t or None)"""
+        self._check(self._lib.mca_hip_mvdr_spectrum_dev(
+            self.h, int(n_streams), spectrum.data_ptr() if spectrum is not None else None, peak_doa.data_ptr() if peak_doa is not None else None,
+            peak_val.data_ptr() if peak_val is not None else None, stream))
 
     def covariance(self, stream_index=0):
         out = np.empty((self.K, self.M, self.M, 2))

@@ -32,12 +32,20 @@ struct mca_hip_mvdr_ctx {
     // workspace
     float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
     float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // rows x look directions; d_T: factored steering phasors [rows][M][N/64 + 33]
+    // the Capon spectrum of the held covariance (mca_hip_mvdr_spectrum_*): a processing parameter like null_gain, no part of the state blobs
+    bool spec_set = false;
+    mca_hip_mvdr_spectrum_config spec{};
+    int spec_dpad = 0;                              // n_angles rounded up to whole waves
+    std::vector<float> spec_grid;                   // [D] (float) theta_i
+    float *d_spec_grid = nullptr;
+    float2 *d_spec_T = nullptr;                     // [M][N/64 + 33][Dpad] factored steering phasors of the grid (MvdrSpectrumArgs::T)
+    float *d_spec_part = nullptr; size_t spec_part_cap = 0;   // partial sums [streams][chunks][4][Dpad]
     StagePool stage;
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[3] = {};
-    double t_ms[3] = {};
+    int t_launches[4] = {};
+    double t_ms[4] = {};
     std::string err;
 };
 
@@ -64,7 +72,7 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
     if (!c) return;
     auto F = [](void *p) { if (p) (void)hipFree(p); };
     F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
-    F(c->d_X); F(c->d_Y); F(c->d_T);
+    F(c->d_X); F(c->d_Y); F(c->d_T); F(c->d_spec_grid); F(c->d_spec_T); F(c->d_spec_part);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->stage.release();
     delete c;
@@ -421,6 +429,126 @@ int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_stream
     return mca_hip_mvdr_sources_frames_host(c, pcm, n_streams, n_frames, 1, doa_rad, out_pcm, out_spec);
 }
 
+int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spectrum_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_spectrum_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->n_angles < 2 || cfg->n_angles > MVDR_SPEC_MAX_ANGLES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [2,361]");
+    if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
+    if (cfg->weighting != MCA_HIP_MVDR_SPECTRUM_POWER && cfg->weighting != MCA_HIP_MVDR_SPECTRUM_NORMALISED)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "weighting must be 0 (power) or 1 (normalised)");
+    if (cfg->n_peaks < 1 || cfg->n_peaks > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_peaks must be in [1,4]");
+    if (c->spec_set && cfg->n_angles == c->spec.n_angles) { c->spec = *cfg; return MCA_HIP_OK; }    // the grid and its phasors stay
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    // grid and steering phasors of the new angle count, in double: theta_i = -pi/2 + i pi/(D-1), u = fs/(N c) x_m cos(theta + pi/2)
+    // (Beamformer.cpp:59), factors exp(-j 2 pi 32 i u), i <= N/64, and exp(-j 2 pi i u), i < 32, as in MvdrAnalyseArgs::T
+    const int D = cfg->n_angles, Dpad = (D + 63) & ~63, nhi = c->N / 64 + 1, nph = nhi + 32, M = c->M;
+    std::vector<double> mx(M);
+    VHIP_TRY(c, hipMemcpy(mx.data(), c->d_micx, (size_t)M * 8, hipMemcpyDeviceToHost));
+    std::vector<float> grid(D);
+    std::vector<float2> T((size_t)M * nph * Dpad);
+    const double unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;
+    for (int i = 0; i < Dpad; ++i) {
+        const double th = -M_PI / 2 + (double)(i < D ? i : D - 1) * M_PI / (double)(D - 1);     // the surplus lanes repeat the last angle
+        if (i < D) grid[i] = (float)th;
+        for (int m = 0; m < M; ++m) {
+            const double u = unit * mx[m] * std::cos(th + M_PI / 2);
+            for (int e = 0; e < nph; ++e) {
+                double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * u;
+                t -= std::floor(t);
+                T[((size_t)m * nph + e) * Dpad + i] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
+            }
+        }
+    }
+    float *ng = nullptr; float2 *nT = nullptr;
+    hipError_t e = hipMalloc((void **)&ng, (size_t)D * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&nT, T.size() * sizeof(float2));
+    if (e == hipSuccess) e = hipMemcpy(ng, grid.data(), (size_t)D * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(nT, T.data(), T.size() * sizeof(float2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();            // no spectrum call in flight reads the former tables
+    if (e != hipSuccess) {
+        if (ng) (void)hipFree(ng);
+        if (nT) (void)hipFree(nT);
+        return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("steering tables of the spectrum: ") + hipGetErrorString(e));
+    }
+    if (c->d_spec_grid) (void)hipFree(c->d_spec_grid);
+    if (c->d_spec_T) (void)hipFree(c->d_spec_T);
+    c->d_spec_grid = ng; c->d_spec_T = nT; c->spec_grid.swap(grid); c->spec_dpad = Dpad; c->spec = *cfg; c->spec_set = true;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_spectrum_get_grid(const mca_hip_mvdr_ctx *c, float *doa_rad)
+{
+    if (!c || !doa_rad || !c->spec_set) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    std::memcpy(doa_rad, c->spec_grid.data(), c->spec_grid.size() * 4);
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum_dev, peak_doa_dev and peak_val_dev are all NULL");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrSpectrumArgs sa{};
+    sa.phi = c->d_phi; sa.trace = c->d_trace; sa.T = c->d_spec_T;
+    sa.K = c->K; sa.M = c->M; sa.D = c->spec.n_angles; sa.Dpad = c->spec_dpad; sa.nhi = c->N / 64 + 1; sa.nph = sa.nhi + 32;
+    sa.bin_lo = c->spec.bin_lo; sa.bin_hi = c->spec.bin_hi;
+    sa.chunk0 = sa.bin_lo / MVDR_SPEC_CHUNK; sa.n_chunks = sa.bin_hi / MVDR_SPEC_CHUNK - sa.chunk0 + 1;
+    sa.power = c->spec.weighting == MCA_HIP_MVDR_SPECTRUM_POWER;
+    sa.loading = (float)c->cfg.loading;
+    const size_t need = (size_t)n_streams * sa.n_chunks * 4 * sa.Dpad;
+    if (need > c->spec_part_cap) {
+        VHIP_TRY(c, hipDeviceSynchronize());
+        if (c->d_spec_part) (void)hipFree(c->d_spec_part);
+        c->d_spec_part = nullptr; c->spec_part_cap = 0;
+        VHIP_TRY(c, hipMalloc((void **)&c->d_spec_part, need * 4));
+        c->spec_part_cap = need;
+    }
+    sa.part = c->d_spec_part;
+    MvdrSpectrumPickArgs pa{};
+    pa.part = c->d_spec_part; pa.grid = c->d_spec_grid; pa.n_slices = sa.n_chunks * 4; pa.D = sa.D; pa.Dpad = sa.Dpad; pa.n_peaks = c->spec.n_peaks;
+    pa.spectrum = spectrum; pa.peak_doa = peak_doa; pa.peak_val = peak_val;
+    const int Q = (c->M + 3) / 4;
+    const size_t smem = (size_t)MVDR_SPEC_CHUNK * (c->tri * sizeof(float2) + 4);          // 68 KiB at 16 microphones
+    const dim3 grid((unsigned)((long long)n_streams * sa.n_chunks));
+    const void *kernel = Q == 1 ? reinterpret_cast<const void *>(k_mvdr_spectrum<1>) : Q == 2 ? reinterpret_cast<const void *>(k_mvdr_spectrum<2>)
+                       : Q == 3 ? reinterpret_cast<const void *>(k_mvdr_spectrum<3>) : reinterpret_cast<const void *>(k_mvdr_spectrum<4>);
+    if (smem > 64 * 1024) VHIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    void *kargs[1] = {&sa};
+    t_begin(c, 3, st);
+    (void)hipLaunchKernel(kernel, grid, dim3(256), kargs, smem, st);
+    hipLaunchKernelGGL(k_mvdr_spectrum_pick, dim3(n_streams), dim3(256), 0, st, pa);
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum, peak_doa and peak_val are all NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t sb = (size_t)n_streams * c->spec.n_angles * 4, pb = (size_t)n_streams * c->spec.n_peaks * 4;
+    float *d_s = spectrum ? (float *)c->stage.get(4, sb) : nullptr;
+    float *d_d = peak_doa ? (float *)c->stage.get(5, pb) : nullptr, *d_v = peak_val ? (float *)c->stage.get(6, pb) : nullptr;
+    if ((spectrum && !d_s) || (peak_doa && !d_d) || (peak_val && !d_v))
+        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    const int rc = mca_hip_mvdr_spectrum_dev(c, n_streams, d_s, d_d, d_v, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    if (spectrum) VHIP_TRY(c, hipMemcpy(spectrum, d_s, sb, hipMemcpyDeviceToHost));
+    if (peak_doa) VHIP_TRY(c, hipMemcpy(peak_doa, d_d, pb, hipMemcpyDeviceToHost));
+    if (peak_val) VHIP_TRY(c, hipMemcpy(peak_val, d_v, pb, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
 {
     if (!c || !out) return MCA_HIP_ERR_INVALID_ARGUMENT;
@@ -500,7 +628,7 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id >= 3) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c || kernel_id < 0 || kernel_id >= 4) return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));
         float ms = 0.f;

@@ -78,6 +78,8 @@ template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
 template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(MvdrSolveArgs p);
 template <int Q, int S, int S1, bool PF> __global__ void k_mvdr_nulls(MvdrNullsArgs pa);   // soft nulls at the other look directions
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
+template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance
+__global__ void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs p);
 __global__ void k_tgcc_frames(TgccFrameArgs p);
 __global__ void k_tgcc_frame_f64(const double *Lp, const double *Rp, int W, int nd, int rem, double *res, double *index);
 __global__ void k_tgcc_gate(TgccGateArgs p);

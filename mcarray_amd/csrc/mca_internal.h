@@ -516,6 +516,32 @@ struct MvdrNullsArgs {
     float null_gain;          // > 0: gain of the soft nulls at the other look directions
 };
 
+// k_mvdr_spectrum<Q> / k_mvdr_spectrum_pick (kernels_mvdr_spectrum.hip): the Capon spatial spectrum of the covariance a
+// context holds, P[i] = sum_k w[k] / (d(theta_i,k)^H PhiL[k]^-1 d(theta_i,k)).  A workgroup takes one stream and one chunk of
+// MVDR_SPEC_CHUNK consecutive bins (chunk c = bins 64 c ... 64 c + 63, cut to the band); its four waves leave one partial sum per
+// angle each, and the pick kernel adds the partial sums of a stream in (chunk, wave) order and selects the peaks.
+constexpr int MVDR_SPEC_CHUNK = 64;
+constexpr int MVDR_SPEC_MAX_ANGLES = 361;
+struct MvdrSpectrumArgs {
+    const float2 *phi;        // [streams][K][M(M+1)/2] (read only)
+    const float *trace;       // [streams][K] (read only)
+    // factored steering phasors of the grid, angle fastest: d_m(theta_i, k) = T[(m nph + (k >> 5)) Dpad + i] * T[(m nph + nhi + (k & 31)) Dpad + i]
+    // (the factors of MvdrAnalyseArgs::T); the angles D ... Dpad - 1 repeat angle D - 1
+    const float2 *T;
+    float *part;              // [streams][n_chunks][4][Dpad] partial sums
+    int K, M, D, Dpad, nph, nhi;
+    int bin_lo, bin_hi, chunk0, n_chunks;
+    int power;                // 1: w[k] = 1 (MCA_HIP_MVDR_SPECTRUM_POWER), 0: w[k] = M / tr[k]
+    float loading;
+};
+struct MvdrSpectrumPickArgs {
+    const float *part;        // [streams][n_slices][Dpad]
+    const float *grid;        // [D] (float) theta_i
+    int n_slices, D, Dpad, n_peaks;
+    float *spectrum;          // [streams][D] or NULL
+    float *peak_doa, *peak_val;   // [streams][n_peaks] or NULL
+};
+
 struct MvdrSynthArgs {
     const float2 *Y;          // [streams][S][n_frames][K]
     int n_frames, N, logH, ft;
