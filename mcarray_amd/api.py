@@ -43,6 +43,25 @@ class PinnedBuffer:
         self.close()
 
 
+def pcm_layout(pcm):
+    """(ptr, array_stride, ch_stride) of a torch float32 tensor [A][C][L] for the *_frames_dev entry points: sample n of channel c
+    of array a at ptr[a*array_stride + c*ch_stride + n].  Rows and arrays may be padded and the view may start anywhere in its
+    allocation; L may exceed what the call reads.  Reads data_ptr(), stride() and dtype only (CPU tensors work as well); the C
+    layer checks ranges, parity and alignment."""
+    if len(pcm.shape) != 3:
+        raise MCArrayHipError("pcm must be a tensor [A][C][L]")
+    if "float32" not in str(pcm.dtype):
+        raise MCArrayHipError("pcm must be float32, not %s" % pcm.dtype)
+    sa, sc, sn = pcm.stride()
+    if sn != 1:
+        raise MCArrayHipError("the samples of a pcm row must be adjacent (inner stride 1, not %d)" % sn)
+    return C.c_void_p(pcm.data_ptr()), int(sa), int(sc)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def _xyz(x):
     a = np.asarray(x, dtype=np.float64)
     if a.ndim == 1:   # ArrayDescription::make_linear_array_description (ArrayDescription.cpp:41-49)
@@ -176,27 +195,27 @@ class Context:
     # ---- stream API, device tensors (torch used for memory only) ----
     def process_frames_dev(self, pcm, n_frames, doa_bin, doa_rad, prob, energy=None, out_pcm=None, stream=None,
                            localise=True, separate=True, bins_are_grid=False):
-        """pcm: torch float32 cuda tensor [A][M][>= (F+1)*hop]; outputs preallocated cuda tensors.
+        """pcm: torch float32 cuda tensor [A][M][>= (F+1)*hop], rows and arrays at any even strides (pcm_layout); outputs
+        preallocated cuda tensors.
         bins_are_grid (separation only): doa_rad holds the grid angles of doa_bin (the localiser's own picks)."""
         A, M, L = pcm.shape
         if M != self.M:
             raise MCArrayHipError("pcm has %d channels, context has %d microphones" % (M, self.M))
-        if not pcm.is_contiguous():
-            raise MCArrayHipError("pcm must be contiguous")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        p, sa, sc = pcm_layout(pcm)
+        ptr = _ptr
         if localise and separate and out_pcm is not None and doa_rad is not None:
-            self._check(self._lib.mca_hip_process_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(doa_bin), ptr(doa_rad), ptr(prob),
+            self._check(self._lib.mca_hip_process_frames_dev(self.h, p, sa, sc, A, n_frames, ptr(doa_bin), ptr(doa_rad), ptr(prob),
                                                              ptr(energy), ptr(out_pcm), stream))
             return
         if localise:
-            self._check(self._lib.mca_hip_localise_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(doa_bin),
+            self._check(self._lib.mca_hip_localise_frames_dev(self.h, p, sa, sc, A, n_frames, ptr(doa_bin),
                                                               ptr(doa_rad), ptr(prob), ptr(energy), stream))
         if separate and out_pcm is not None:
             if bins_are_grid and doa_bin is not None:
-                self._check(self._lib.mca_hip_separate_frames_bins_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(doa_bin), ptr(doa_rad),
+                self._check(self._lib.mca_hip_separate_frames_bins_dev(self.h, p, sa, sc, A, n_frames, ptr(doa_bin), ptr(doa_rad),
                                                                        ptr(out_pcm), stream))
             else:
-                self._check(self._lib.mca_hip_separate_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(doa_rad),
+                self._check(self._lib.mca_hip_separate_frames_dev(self.h, p, sa, sc, A, n_frames, ptr(doa_rad),
                                                                   ptr(out_pcm), stream))
 
     # ---- real-time mode: the stream call as a HIP graph ----
@@ -204,11 +223,12 @@ class Context:
         """Fixes the shape and buffers (torch cuda tensors, as process_frames_dev) of a stream call; returns a StreamGraph
         whose launch() replays the call's kernels as one HIP graph on the current contents of `pcm`."""
         A, M, L = pcm.shape
-        if M != self.M or not pcm.is_contiguous():
-            raise MCArrayHipError("pcm must be a contiguous [A][M][L] tensor with M = the context's microphones")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if M != self.M:
+            raise MCArrayHipError("pcm must be a [A][M][L] tensor with M = the context's microphones")
+        p, sa, sc = pcm_layout(pcm)
+        ptr = _ptr
         h = C.c_void_p()
-        self._check(self._lib.mca_hip_graph_create(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(doa_bin), ptr(doa_rad), ptr(prob),
+        self._check(self._lib.mca_hip_graph_create(self.h, p, sa, sc, A, n_frames, ptr(doa_bin), ptr(doa_rad), ptr(prob),
                                                    ptr(energy), ptr(out_pcm), C.byref(h)))
         return StreamGraph(self, h, (pcm, doa_bin, doa_rad, prob, energy, out_pcm))
 
@@ -243,10 +263,11 @@ class Context:
         """mca_hip_gcc2_frames_dev: pcm torch float32 cuda tensor [A][2][>= (F+1)*hop]; outputs preallocated cuda tensors
         argmax int32 [A][F], doa_rad / prob float32 [A][F], corr float32 [A][F][D] (all but argmax optional)."""
         A, M, L = pcm.shape
-        if M != 2 or not pcm.is_contiguous():
-            raise MCArrayHipError("pcm must be a contiguous [A][2][L] tensor")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(self._lib.mca_hip_gcc2_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
+        if M != 2:
+            raise MCArrayHipError("pcm must be a [A][2][L] tensor")
+        p, sa, sc = pcm_layout(pcm)
+        ptr = _ptr
+        self._check(self._lib.mca_hip_gcc2_frames_dev(self.h, p, sa, sc, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
                                                       ptr(corr), stream))
 
     # ---- the particle-filter DOA tracker of the 2-microphone path ----
@@ -295,10 +316,11 @@ class Context:
         """mca_hip_gcc2_tracked_frames_dev: pcm torch float32 cuda tensor [A][2][>= (F+1)*hop]; outputs preallocated cuda tensors
         doa_rad / prob float32, argmax / track int32, fired uint8 [A][F], corr float32 [A][F][D] (all but doa_rad optional)."""
         A, M, L = pcm.shape
-        if M != 2 or not pcm.is_contiguous():
-            raise MCArrayHipError("pcm must be a contiguous [A][2][L] tensor")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(self._lib.mca_hip_gcc2_tracked_frames_dev(self.h, ptr(pcm), M * L, L, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
+        if M != 2:
+            raise MCArrayHipError("pcm must be a [A][2][L] tensor")
+        p, sa, sc = pcm_layout(pcm)
+        ptr = _ptr
+        self._check(self._lib.mca_hip_gcc2_tracked_frames_dev(self.h, p, sa, sc, A, n_frames, ptr(argmax), ptr(doa_rad), ptr(prob),
                                                               ptr(fired), ptr(track), ptr(corr), stream))
 
     def gcc2_tracker_particles(self, array_index=0):
@@ -681,6 +703,18 @@ class MultibandBinarualLocalisation(_StateBlob):
                     self.callback(np.array([np.rad2deg(float(doa[0, t]))]), np.array([prob[0, t]]), float(power[0, t]), 1)
         return dict(doa=doa, prob=prob, voiced=voiced, power=power, band_idx=bi, energy_in_doa=eid, band_corr=bc)
 
+    def process_dev(self, pcm, n_frames, doa_rad, prob, voiced=None, power=None, band_idx=None, energy_in_doa=None, band_corr=None,
+                    stream=None):
+        """device tensors (torch): pcm [A][2][>= (F+1)*hop] float32 at any even strides (pcm_layout); outputs preallocated and
+        contiguous, shapes and types as process() returns them (doa_rad, prob required); asynchronous on `stream` (a raw
+        hipStream_t or None)."""
+        A, ch, L = pcm.shape
+        if ch != 2:
+            raise MCArrayHipError("pcm must be [A][2][L]")
+        p, sa, sc = pcm_layout(pcm)
+        self._check(self._lib.mca_hip_mb_frames_dev(self.h, p, sa, sc, A, int(n_frames), _ptr(doa_rad), _ptr(prob), _ptr(voiced),
+                                                    _ptr(power), _ptr(band_idx), _ptr(energy_in_doa), _ptr(band_corr), stream))
+
 
 class TemporalGCCBinauralLocalisation(_StateBlob):
     _STATE = "tgcc"
@@ -766,22 +800,26 @@ class TemporalGCCBinauralLocalisation(_StateBlob):
                     self.callback(np.array([float(doa[0, t])]), np.array([float(prob[0, t])]), float(power[0, t]), 1)
         return dict(doa=doa, prob=prob, voiced=voiced, power=power, delay_idx=k, index=index)
 
-    def process_dev(self, pcm, stream=None, want_index=False):
-        """device-pointer form: pcm a torch float32 CUDA tensor [A][2][(F-1)*hop + W] -> dict of torch tensors as process()."""
+    def process_dev(self, pcm, stream=None, want_index=False, n_frames=None, out=None):
+        """device-pointer form: pcm a torch float32 CUDA tensor [A][2][(F-1)*hop + W], rows and arrays at any strides
+        (pcm_layout) -> dict of torch tensors as process().  n_frames: process that many frames of rows that may be longer.
+        out: a dict of preallocated tensors (doa, prob, power float32, voiced uint8, delay_idx int32 [A][F]; index float64
+        [A][F][nd] with want_index) to write instead of fresh ones.  Asynchronous on `stream` (a raw hipStream_t or None)."""
         import torch
         A, ch, L = pcm.shape
-        F = self.num_frames(L)
-        if ch != 2 or F < 1 or (F - 1) * self.hop + self.W != L or not pcm.is_contiguous() or pcm.dtype != torch.float32:
-            raise MCArrayHipError("pcm must be a contiguous float32 tensor [A][2][(F-1)*hop + W]")
+        F = self.num_frames(L) if n_frames is None else int(n_frames)
+        if ch != 2 or F < 1 or (n_frames is None and (F - 1) * self.hop + self.W != L):
+            raise MCArrayHipError("pcm must be a float32 tensor [A][2][(F-1)*hop + W]")
+        p, sa, sc = pcm_layout(pcm)
         dev = pcm.device
-        out = dict(doa=torch.empty((A, F), dtype=torch.float32, device=dev), prob=torch.empty((A, F), dtype=torch.float32, device=dev),
-                   voiced=torch.empty((A, F), dtype=torch.uint8, device=dev), power=torch.empty((A, F), dtype=torch.float32, device=dev),
-                   delay_idx=torch.empty((A, F), dtype=torch.int32, device=dev))
-        out["index"] = torch.empty((A, F, self.nd), dtype=torch.float64, device=dev) if want_index else None
+        if out is None:
+            out = dict(doa=torch.empty((A, F), dtype=torch.float32, device=dev), prob=torch.empty((A, F), dtype=torch.float32, device=dev),
+                       voiced=torch.empty((A, F), dtype=torch.uint8, device=dev), power=torch.empty((A, F), dtype=torch.float32, device=dev),
+                       delay_idx=torch.empty((A, F), dtype=torch.int32, device=dev))
+            out["index"] = torch.empty((A, F, self.nd), dtype=torch.float64, device=dev) if want_index else None
         self._check(self._lib.mca_hip_tgcc_frames_dev(
-            self.h, C.c_void_p(pcm.data_ptr()), 2 * L, L, A, F, C.c_void_p(out["doa"].data_ptr()), C.c_void_p(out["prob"].data_ptr()),
-            C.c_void_p(out["voiced"].data_ptr()), C.c_void_p(out["power"].data_ptr()), C.c_void_p(out["delay_idx"].data_ptr()),
-            C.c_void_p(out["index"].data_ptr()) if want_index else None, stream))
+            self.h, p, sa, sc, A, F, _ptr(out["doa"]), _ptr(out["prob"]), _ptr(out["voiced"]), _ptr(out["power"]), _ptr(out["delay_idx"]),
+            _ptr(out.get("index")) if want_index else None, stream))
         return out
 
     def process_frame(self, left, right):
@@ -899,12 +937,12 @@ class MvdrBeamformer(_StateBlob):
         return dict(out=out, spec=spec)
 
     def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None):
-        """device tensors (torch, contiguous): pcm [streams][M][>= (F+1)*hop] float32, doa_rad [streams][F] float32,
-        out_pcm [streams][F*hop], out_spec [streams][F][K][2]; asynchronous on `stream` (a raw hipStream_t or None)."""
+        """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F]
+        float32, out_pcm [streams][F*hop], out_spec [streams][F][K][2] (contiguous); asynchronous on `stream` (a raw hipStream_t
+        or None)."""
         A = pcm.shape[0]
-        self._check(self._lib.mca_hip_mvdr_frames_dev(
-            self.h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), A, n_frames, doa_rad.data_ptr(),
-            out_pcm.data_ptr() if out_pcm is not None else None, out_spec.data_ptr() if out_spec is not None else None, stream))
+        p, sa, sc = pcm_layout(pcm)
+        self._check(self._lib.mca_hip_mvdr_frames_dev(self.h, p, sa, sc, A, n_frames, _ptr(doa_rad), _ptr(out_pcm), _ptr(out_spec), stream))
 
     def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True):
         """S look directions per frame from one analysis, covariance recursion and factorisation: pcm float32
@@ -931,15 +969,15 @@ class MvdrBeamformer(_StateBlob):
         return dict(out=out, spec=spec)
 
     def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None):
-        """device tensors (torch, contiguous): pcm [streams][M][>= (F+1)*hop] float32, doa_rad [streams][F][S] float32 (e.g. the
-        doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec [streams][S][F][K][2];
-        asynchronous on `stream` (a raw hipStream_t or None)."""
+        """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F][S]
+        float32 (e.g. the doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec
+        [streams][S][F][K][2] (contiguous); asynchronous on `stream` (a raw hipStream_t or None)."""
         A = pcm.shape[0]
+        p, sa, sc = pcm_layout(pcm)
         if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
             raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
-        self._check(self._lib.mca_hip_mvdr_sources_frames_dev(
-            self.h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), A, n_frames, doa_rad.shape[2], doa_rad.data_ptr(),
-            out_pcm.data_ptr() if out_pcm is not None else None, out_spec.data_ptr() if out_spec is not None else None, stream))
+        self._check(self._lib.mca_hip_mvdr_sources_frames_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad), _ptr(out_pcm),
+                                                              _ptr(out_spec), stream))
 
     SPECTRUM_POWER, SPECTRUM_NORMALISED = 0, 1
 
@@ -1075,6 +1113,16 @@ class FastBinauralMasking(_StateBlob):
                                                        dec.ctypes.data_as(_lib.c_ip) if want_decisions else None))
         return out, dec
 
+    def process_dev(self, pcm, n_frames, out_pcm, decisions=None, stream=None):
+        """device tensors (torch): pcm [streams][2][>= (F+1)*hop] float32 at any even strides (pcm_layout), out_pcm
+        [streams][2][F*hop] float32, decisions [streams][F][45] int32 or None (contiguous, preallocated); asynchronous on `stream`
+        (a raw hipStream_t or None)."""
+        ns, ch, L = pcm.shape
+        if ch != 2:
+            raise MCArrayHipError("pcm must be [streams][2][L]")
+        p, sa, sc = pcm_layout(pcm)
+        self._check(self._lib.mca_hip_mask_frames_dev(self.h, p, sa, sc, ns, int(n_frames), _ptr(out_pcm), _ptr(decisions), stream))
+
     def process_parametrisation(self, left, right):
         """The DSPONE hook for one frame: CCS double[N+2] spectra, returns the modified copies + decisions."""
         left = np.array(left, dtype=np.float64, order="C")
@@ -1149,6 +1197,16 @@ class BinauralMaskingImpl(_StateBlob):
         self._check(self._lib.mca_hip_bmask_frames_host(self.h, pcm.ctypes.data_as(_lib.c_fp), ns, F, out.ctypes.data_as(_lib.c_fp),
                                                         dec.ctypes.data_as(_lib.c_ip) if want_decisions else None))
         return out, dec
+
+    def process_dev(self, pcm, n_frames, out_pcm, decisions=None, stream=None):
+        """device tensors (torch): pcm [streams][2][>= (F+1)*hop] float32 at any even strides (pcm_layout), out_pcm
+        [streams][2][F*hop] float32, decisions [streams][F][45] int32 or None (contiguous, preallocated); asynchronous on `stream`
+        (a raw hipStream_t or None)."""
+        ns, ch, L = pcm.shape
+        if ch != 2:
+            raise MCArrayHipError("pcm must be [streams][2][L]")
+        p, sa, sc = pcm_layout(pcm)
+        self._check(self._lib.mca_hip_bmask_frames_dev(self.h, p, sa, sc, ns, int(n_frames), _ptr(out_pcm), _ptr(decisions), stream))
 
     state = _StateBlob.state_save
     load_state = _StateBlob.state_load
