@@ -1,6 +1,6 @@
 // cand_unit.h -- the repair contraction of ONE listed unit (4 rows) at the unit's candidate columns (CandArgs, mca_internal.h), by the NW
-// waves of a workgroup.  Shared by k_srp_cand (NW = 16: a launch of its own) and the list mode of k_stft_phat_wave (NW = 4: the workgroup
-// that wrote the unit's rows contracts them right away).
+// waves of a workgroup.  Called by the list mode of k_stft_phat_wave (NW = 4: the workgroup that wrote the unit's rows contracts them right
+// away).
 //
 // The shape is 4 x 8 with a depth of thousands, so the matrix instruction is the 16-block 4 x 4 x 4 one with the BLOCKS AS DEPTH SLICES:
 // lane 4 b + q holds row q of A / column q of B over the eight depth positions of slice b of a 128-deep step (one 16-byte load per operand

@@ -10,7 +10,6 @@
 //   k_srp_gemm_f32   v_mfma_f32_32x32x2_f32: bit-exact fp32 fma chain, parity anchor
 //   k_srp_gemm_f16   v_mfma_f32_32x32x16_f16 with 1 (fp16) or 3 (fp16x3 hi/lo split) products
 #include "mca_internal.h"
-#include "cand_unit.h"
 
 namespace mca {
 
@@ -236,18 +235,6 @@ __global__ __launch_bounds__(256) void k_srp_gemm_repair(GemmArgs p)
         const int ct = t % col_tiles, rt = t / col_tiles;
         gemm_f16_tile<true, BN>(p, rt * G16_BM, ct * BN, z, ksplit, n_rows, plane_elems, As, Bs);
     }
-}
-
-// ---------------------------------------------------------------------------------------
-// k_srp_cand -- the repair contraction at the CANDIDATE COLUMNS only (CandArgs, mca_internal.h): one workgroup of sixteen waves per
-// listed unit, cand_unit.h.  A fixed grid walks the units.  (4 / 8-microphone contexts do this inside the list-mode analysis launch,
-// StftPhatArgs::cand_on; this launch serves the contexts whose list-mode analysis is another kernel.)
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_srp_cand(CandArgs p)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char lds[cand_unit_lds_bytes<16>()];
-    const int n_here = min(*p.n_list - p.list0, p.pass_rows / REPAIR_GROUP);
-    for (int g = blockIdx.x; g < n_here; g += gridDim.x) cand_unit<16>(p, g, p.list[p.list0 + g], lds, (int)threadIdx.x);
 }
 
 template __global__ void k_srp_gemm_repair<192>(GemmArgs);

@@ -46,7 +46,7 @@ constexpr int REPAIR_GROUP = 4;   // frames per repair unit = frames per list-mo
 constexpr int HIST_FRAMES = REPAIR_WARM, HIST_UNITS = HIST_FRAMES / REPAIR_GROUP, HIST_SAMPLES = (HIST_FRAMES + 1) * 512;
 static_assert(HIST_FRAMES % REPAIR_GROUP == 0, "history = whole repair units");
 
-// cand_unit.h / k_srp_cand: the exact values of the listed rows AT THEIR CANDIDATE COLUMNS, written straight into the map.
+// cand_unit.h: the exact values of the listed rows AT THEIR CANDIDATE COLUMNS, written straight into the map.
 // Which columns (wave_candidates, kernels_stream.hip): a flagged frame's pick is, on the exact map, among the positions whose coarse |En|
 // reaches v - tau, v the best GUARANTEED peak of the coarse row -- a window in which the median-filtered sign chain, with every first
 // difference within tau taken as of either sign, is pinned to "rising" at one end and to "falling" at the other: the exact map has a
@@ -140,8 +140,7 @@ struct StftPhatArgs {
                              // frame is at the rounding level of the transform.  PHAT keeps only the SIGN of such a bin, and the exact rows of 16
                              // microphones come from another kernel (k_stft_phat<16>) that need not round it the same way: k_scan_pick repairs the
                              // frame and the six after it whatever the map says ("A limit of PHAT itself")
-    // list mode of a candidate-column call: the workgroup that wrote a unit's four rows contracts them at the unit's columns (cand_unit.h) --
-    // k_srp_cand's work without its launch
+    // list mode of a candidate-column call: the workgroup that wrote a unit's four rows contracts them at the unit's columns (cand_unit.h)
     int cand_on; CandArgs cand;
     SteerArgs bf;            // k_stft_phat_wave<..., FUSE>
 };
@@ -231,13 +230,9 @@ struct ScanPickArgs {
     float *hist_C_out, *e_hist_out;
     const float *hist_C_in, *e_hist_in;
     // candidate columns (round 5): per repair unit the delays its rows are needed at, one bit per column, umask_words = Dp / 32 words
-    // per unit (k_scan_pick ORs a flagged frame's candidate columns into every unit it lists; k_srp_cand -- one workgroup per unit -- takes
+    // per unit (k_scan_pick ORs a flagged frame's candidate columns into every unit it lists; cand_unit -- one workgroup per unit -- takes
     // and clears them and releases the unit's test-and-set word).  NULL: whole rows (k_srp_gemm_repair + k_repair_patch).
     unsigned *umask; int umask_words;
-    // two work lists (round 6; k_scan_pick<PL, 2>: contexts whose flagged frames include whole rows by construction -- eager tails, the
-    // 16-microphone unsure marks): a frame that takes every column lists its units HERE (test-and-set words, list, length; walked by a
-    // second list-mode analysis + k_srp_gemm_repair + k_repair_patch), the others on `list` with their column masks.  NULL: one list.
-    int *need_full, *list_full, *n_list_full;
 };
 
 // The repair contraction runs on however many rows the coarse pass listed (a device-side count): the K range is what

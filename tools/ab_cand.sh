@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 5: candidate columns (shipped: k_srp_cand writes the exact values of the listed rows at the columns the flagged frames need)
+# round 5: candidate columns (shipped: cand_unit.h, inside the list-mode analysis launch, writes the exact values of the listed rows at the columns the flagged frames need)
 # against whole rows (MCA_HIP_ADAPT_CAND=0: k_srp_gemm_repair + k_repair_patch, round 4); the shipped library
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for cand in 0 1 0 1; do
