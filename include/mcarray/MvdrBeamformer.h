@@ -62,6 +62,12 @@ public:
     // Soft nulls at the other look directions of setDOAs() (mca_hip_mvdr_set_null_gain: finite, 0 ... 1000; 0, the default, is
     // the plain MVDR output).  Applies to the frames completed from now on; no part of the stream's state.
     void setNullGain(double nullGain) { check(mca_hip_mvdr_set_null_gain(_ctx, nullGain)); }
+    // Covariance update weight of the frames completed from now on (mca_hip_mvdr_sources_frames_weighted_*): 1, the default,
+    // learns as usual; 0 leaves the covariance as it is and beamforms with it (e.g. while a voice-activity decision says that the
+    // target talks: a noise-only covariance); values between scale the step 1 - alpha.  Clamped to [0, 1], NaN counts as 0.
+    // Both process() overloads honour it; no part of the stream's state.
+    void setUpdateWeight(double updateWeight) { _update = updateWeight; }
+    double getUpdateWeight() const { return _update; }
     double getNullGain() const
     {
         double g = 0.0;
@@ -106,6 +112,12 @@ public:
         doaRadians.assign(d.begin(), d.end());
         values.assign(v.begin(), v.end());
     }
+    // the covariance the stream holds (mca_hip_mvdr_get_covariance): [N/2+1][M][M] complex as (re, im) pairs of doubles
+    void covariance(std::vector<double> &phi)
+    {
+        phi.resize(static_cast<size_t>(_N / 2 + 1) * static_cast<size_t>(_nchannels) * static_cast<size_t>(_nchannels) * 2);
+        check(mca_hip_mvdr_get_covariance(_ctx, 0, phi.data()));
+    }
     void reset()
     {
         check(mca_hip_mvdr_reset(_ctx, nullptr));
@@ -122,7 +134,8 @@ public:
         if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
         std::vector<float> pcm = frames(F);
         std::vector<float> doa(static_cast<size_t>(F), static_cast<float>(_doa)), audio(static_cast<size_t>(F) * static_cast<size_t>(hop));
-        check(mca_hip_mvdr_frames_host(_ctx, pcm.data(), 1, F, doa.data(), audio.data(), nullptr));
+        const std::vector<float> upd = weights(F);
+        check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, 1, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
         for (int i = 0; i < F * hop; ++i) out[i] = static_cast<Tout>(audio[static_cast<size_t>(i)]);
         consume(F);
         return F * hop;
@@ -143,7 +156,8 @@ public:
         std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
         for (int t = 0; t < F; ++t)
             for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
-        check(mca_hip_mvdr_sources_frames_host(_ctx, pcm.data(), 1, F, S, doa.data(), audio.data(), nullptr));
+        const std::vector<float> upd = weights(F);
+        check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, S, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
         consume(F);
@@ -172,6 +186,10 @@ private:
             std::copy(_pending[static_cast<size_t>(c)].begin(), _pending[static_cast<size_t>(c)].begin() + static_cast<long>(L), pcm.begin() + static_cast<long>(L * static_cast<size_t>(c)));
         return pcm;
     }
+    std::vector<float> weights(int F) const     // [F] update weights of a call, empty for the default (all 1: no weights passed)
+    {
+        return _update == 1.0 ? std::vector<float>() : std::vector<float>(static_cast<size_t>(F), static_cast<float>(_update));
+    }
     void consume(int F)
     {
         for (int c = 0; c < _nchannels; ++c)
@@ -182,7 +200,7 @@ private:
         if (rc != MCA_HIP_OK) throw MCArrayException(std::string("libmcarray_hip: ") + mca_hip_mvdr_last_error(_ctx));
     }
     int _nchannels, _N;
-    double _doa = 0.0;
+    double _doa = 0.0, _update = 1.0;
     int _maxSources = 1;
     int _nAngles = 0, _nPeaks = 0;
     std::vector<double> _doas;

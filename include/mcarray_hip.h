@@ -620,6 +620,32 @@ int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *ctx, const float *pcm, in
  * single-look entry points it has no effect. */
 int mca_hip_mvdr_set_null_gain(mca_hip_mvdr_ctx *ctx, double null_gain);
 int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *ctx, double *null_gain);
+/* Per-frame covariance update weights: the covariance learns only where the caller lets it, e.g. where a voice-activity decision
+ * says that the target is absent (a noise-only covariance: MVDR proper, where the unweighted recursion gives the minimum-power
+ * beamformer that cancels a target whose look direction is a little off).
+ *   update_dev [streams][F] float   one weight per stream and frame, for all look directions of the frame (they share one
+ *                                   covariance); NULL = all 1
+ * With u = fminf(fmaxf(update, 0), 1), per stream, bin and frame:
+ *     a_t   = 1 - (1 - alpha) u_t
+ *     Phi_t = a_t Phi_{t-1} + (1 - a_t) x x^H
+ *     tr_t  = a_t tr_{t-1} + (1 - a_t) |x|^2
+ * and everything behind the recursion is as stated above: the loading, the weights, the outputs, the delay-and-sum rule of a
+ * trace <= 1e-30, the soft nulls and the Capon spectrum of the held covariance.  Nothing is refused on the device: a weight
+ * below 0 counts as 0, one above 1 as 1, and a NaN as 0 (the fminf(fmaxf()) form).  Three points are exact:
+ *   - u_t == 1 uses the context's own fp32 alpha and 1 - alpha and the operations of the unweighted call.  A call whose weights
+ *     are all 1, or whose weight pointer is NULL, returns the bytes of mca_hip_mvdr_sources_frames_* and leaves the same
+ *     covariance bytes;
+ *   - u_t == 0 leaves Phi and tr bit for bit as they were.  The frame is still beamformed, with the frozen covariance and its
+ *     own x and look directions;
+ *   - a frozen fresh stream (tr = 0) gives the reference's delay-and-sum, as an unweighted call on silence does.
+ * The weights are an input of the call like doa_rad, not stream state: state blobs neither carry nor check them.  n_sources = 1
+ * on any context is the single-look form.  The argument checks are those of mca_hip_mvdr_sources_frames_dev; how a call is cut
+ * into calls does not change its bytes.  The localisers' voiced[A][F] bytes become weights as INTEGRATION.md shows. */
+int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev, long long stream_stride, long long mic_stride,
+                                             int n_streams, int n_frames, int n_sources, const float *doa_rad_dev,
+                                             const float *update_dev, float *out_pcm_dev, float *out_spec_dev, void *stream);
+int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
+                                              const float *doa_rad, const float *update, float *out_pcm, float *out_spec);
 /* Capon (minimum-variance) spatial spectrum of the covariance the context holds now (after its last frames call or state load),
  * and its peaks: the MVDR power estimate p = 1 / (d^H PhiL^-1 d) of the nulls above on a grid of angles.  Per stream, with
  *     theta_i      = -pi/2 + i pi/(D-1), i = 0 ... D-1 (in double),       D = n_angles

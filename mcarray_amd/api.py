@@ -849,7 +849,10 @@ class MvdrBeamformer(_StateBlob):
     null_gain > 0 (up to 1000) makes every output of process_sources() steer a soft null at the other look directions of its
     frame (include/mcarray_hip.h, mca_hip_mvdr_set_null_gain; 0 is the plain MVDR output).
     configure_spectrum() / spectrum() read the Capon spatial spectrum of the held covariance and its peaks: the look directions
-    of the next chunk (mca_hip_mvdr_spectrum_*)."""
+    of the next chunk (mca_hip_mvdr_spectrum_*).
+    update= of the process calls: per-frame covariance update weights [streams][F] in [0, 1] (1: learn as usual, 0: leave the
+    covariance as it is and beamform with it), e.g. 1 - voiced of a localiser for a noise-only covariance
+    (mca_hip_mvdr_sources_frames_weighted_*; None: all 1)."""
 
     K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM = 0, 1, 2, 3
 
@@ -917,9 +920,21 @@ class MvdrBeamformer(_StateBlob):
     def reset(self):
         self._check(self._lib.mca_hip_mvdr_reset(self.h, None))
 
-    def process(self, pcm, doa_rad, want_audio=True, want_spec=False):
-        """pcm float32 [streams][M][(F+1)*hop], doa_rad [streams][F] (or a scalar) ->
-        dict(out [streams][F*hop], spec complex64 [streams][F][K])"""
+    def _update_host(self, update, A, F):
+        """float32 [streams][F] from a scalar, [F] or [streams][F]"""
+        try:
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(update, dtype=np.float32), (A, F)))
+        except ValueError:
+            raise MCArrayHipError("update must broadcast to [streams][F]")
+
+    def _update_dev(self, update, A, n_frames):
+        if update.dim() != 2 or not update.is_contiguous() or update.shape[0] != A or update.shape[1] != n_frames or update.element_size() != 4:
+            raise MCArrayHipError("update must be a contiguous float32 tensor [streams][F]")
+        return _ptr(update)
+
+    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None):
+        """pcm float32 [streams][M][(F+1)*hop], doa_rad [streams][F] (or a scalar), update None or [streams][F] covariance update
+        weights -> dict(out [streams][F*hop], spec complex64 [streams][F][K])"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
             pcm = pcm[None]
@@ -931,22 +946,31 @@ class MvdrBeamformer(_StateBlob):
         out = np.empty((A, F * self.hop), dtype=np.float32) if want_audio else None
         spec = np.empty((A, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
-        self._check(self._lib.mca_hip_mvdr_frames_host(
-            self.h, pcm.ctypes.data_as(fp), A, F, doa.ctypes.data_as(fp), out.ctypes.data_as(fp) if want_audio else None,
-            spec.ctypes.data_as(fp) if want_spec else None))
+        po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
+        if update is None:
+            self._check(self._lib.mca_hip_mvdr_frames_host(self.h, pcm.ctypes.data_as(fp), A, F, doa.ctypes.data_as(fp), po, ps))
+        else:
+            upd = self._update_host(update, A, F)
+            self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_host(self.h, pcm.ctypes.data_as(fp), A, F, 1, doa.ctypes.data_as(fp),
+                                                                            upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None):
+    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F]
-        float32, out_pcm [streams][F*hop], out_spec [streams][F][K][2] (contiguous); asynchronous on `stream` (a raw hipStream_t
-        or None)."""
+        float32, out_pcm [streams][F*hop], out_spec [streams][F][K][2] (contiguous), update None or [streams][F] float32 covariance
+        update weights (contiguous); asynchronous on `stream` (a raw hipStream_t or None)."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
-        self._check(self._lib.mca_hip_mvdr_frames_dev(self.h, p, sa, sc, A, n_frames, _ptr(doa_rad), _ptr(out_pcm), _ptr(out_spec), stream))
+        if update is None:
+            self._check(self._lib.mca_hip_mvdr_frames_dev(self.h, p, sa, sc, A, n_frames, _ptr(doa_rad), _ptr(out_pcm), _ptr(out_spec), stream))
+        else:
+            self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_dev(self.h, p, sa, sc, A, n_frames, 1, _ptr(doa_rad),
+                                                                           self._update_dev(update, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
 
-    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True):
+    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None):
         """S look directions per frame from one analysis, covariance recursion and factorisation: pcm float32
-        [streams][M][(F+1)*hop], doa_rad [streams][F][S] (S <= max_sources; the layout of the localiser's "doa") ->
+        [streams][M][(F+1)*hop], doa_rad [streams][F][S] (S <= max_sources; the layout of the localiser's "doa"), update None or
+        [streams][F] covariance update weights (one per frame for all its directions) ->
         dict(out [streams][S][F*hop], spec complex64 [streams][S][F][K]).  Output s is what process() gives with doa_rad[:, :, s]."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
@@ -963,21 +987,30 @@ class MvdrBeamformer(_StateBlob):
         out = np.empty((A, S, F * self.hop), dtype=np.float32) if want_audio else None
         spec = np.empty((A, S, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
-        self._check(self._lib.mca_hip_mvdr_sources_frames_host(
-            self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp), out.ctypes.data_as(fp) if want_audio else None,
-            spec.ctypes.data_as(fp) if want_spec else None))
+        po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
+        if update is None:
+            self._check(self._lib.mca_hip_mvdr_sources_frames_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp), po, ps))
+        else:
+            upd = self._update_host(update, A, F)
+            self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp),
+                                                                            upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None):
+    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F][S]
         float32 (e.g. the doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec
-        [streams][S][F][K][2] (contiguous); asynchronous on `stream` (a raw hipStream_t or None)."""
+        [streams][S][F][K][2] (contiguous), update None or [streams][F] float32 covariance update weights (contiguous);
+        asynchronous on `stream` (a raw hipStream_t or None)."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
         if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
             raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
-        self._check(self._lib.mca_hip_mvdr_sources_frames_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad), _ptr(out_pcm),
-                                                              _ptr(out_spec), stream))
+        if update is None:
+            self._check(self._lib.mca_hip_mvdr_sources_frames_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad), _ptr(out_pcm),
+                                                                  _ptr(out_spec), stream))
+        else:
+            self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad),
+                                                                           self._update_dev(update, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
 
     SPECTRUM_POWER, SPECTRUM_NORMALISED = 0, 1
 

@@ -246,9 +246,11 @@ int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *c, double *null_gain)
 }
 
 // the three launches of a call with n_sources look directions per frame: doa_rad [streams][F][n_sources],
-// out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]
-int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
-                                    int n_frames, int n_sources, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
+// out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]; update [streams][F] covariance update weights or NULL
+// (all 1: the unweighted solve kernels)
+int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                             int n_frames, int n_sources, const float *doa_rad, const float *update, float *out_pcm,
+                                             float *out_spec, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (n_sources < 1 || n_sources > c->max_sources)
@@ -317,6 +319,24 @@ int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long 
         if (pieces > 1) { sa.phi_out = c->d_phi_tail; sa.trace_out = c->d_trace_tail; sa.out_base = pid0; }
         else { sa.phi_out = c->d_phi; sa.trace_out = c->d_trace; sa.out_base = 0; }
         const dim3 sgrid((unsigned)((n_prob + 63) / 64 * pieces));
+        if (update) {
+            // per-frame covariance update weights: the instantiation of kernels_mvdr_gate.hip that stands for the kernel chosen below
+            const MvdrGateArgs ga{sa, update, null_gain};
+            const bool full = c->M == 4 * Q;
+#define SOLVE_GATE_NULLS(QQ, SS, S1, PF, R)                                                                                 \
+    if (nulls && Q == QQ && n_sources == SS)                                                                               \
+        hipLaunchKernelGGL((k_mvdr_gated<QQ, false, SS, S1, PF, true, R>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga);
+            MCA_MVDR_GATE_NULLS_TABLE(SOLVE_GATE_NULLS)
+#undef SOLVE_GATE_NULLS
+#define SOLVE_GATE(QQ, SS, S1F, S1P, RF, RP)                                                                                \
+    if (!nulls && Q == QQ && n_sources == SS) {                                                                            \
+        if (full) hipLaunchKernelGGL((k_mvdr_gated<QQ, true, SS, S1F, true, false, RF>), sgrid, dim3(256), 0, st, ga);   \
+        else hipLaunchKernelGGL((k_mvdr_gated<QQ, false, SS, S1P, true, false, RP>), sgrid, dim3(256), 0, st, ga);       \
+    }
+            MCA_MVDR_GATE_PLAIN_TABLE(SOLVE_GATE)
+#undef SOLVE_GATE
+            return;
+        }
 #define SOLVE(QQ)                                                                                          \
     do {                                                                                                   \
         if (c->M == 4 * (QQ)) hipLaunchKernelGGL((k_mvdr_solve<QQ, true>), sgrid, dim3(256), 0, st, sa);   \
@@ -394,14 +414,20 @@ int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long 
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                    int n_frames, int n_sources, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
+{
+    return mca_hip_mvdr_sources_frames_weighted_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, nullptr, out_pcm, out_spec, stream);
+}
+
 int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
                             int n_frames, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
 {
-    return mca_hip_mvdr_sources_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, 1, doa_rad, out_pcm, out_spec, stream);
+    return mca_hip_mvdr_sources_frames_weighted_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, 1, doa_rad, nullptr, out_pcm, out_spec, stream);
 }
 
-int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
-                                     float *out_pcm, float *out_spec)
+int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                                              const float *update, float *out_pcm, float *out_spec)
 {
     if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
@@ -411,11 +437,14 @@ int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int 
     float *d_pcm = (float *)c->stage.get(0, (size_t)ss * n_streams * 4), *d_doa = (float *)c->stage.get(1, nf * 4);
     float *d_out = out_pcm ? (float *)c->stage.get(2, nf * c->H * 4) : nullptr;
     float *d_spec = out_spec ? (float *)c->stage.get(3, nf * c->K * 8) : nullptr;
-    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec))
+    const size_t nu = (size_t)n_streams * n_frames;
+    float *d_upd = update ? (float *)c->stage.get(7, nu * 4) : nullptr;               // (slots 4 ... 6: the spectrum's)
+    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd))
         return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
     VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
-    const int rc = mca_hip_mvdr_sources_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_out, d_spec, nullptr);
+    if (update) VHIP_TRY(c, hipMemcpy(d_upd, update, nu * 4, hipMemcpyHostToDevice));
+    const int rc = mca_hip_mvdr_sources_frames_weighted_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, d_out, d_spec, nullptr);
     if (rc) return rc;
     VHIP_TRY(c, hipDeviceSynchronize());
     if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
@@ -423,10 +452,16 @@ int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int 
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                                     float *out_pcm, float *out_spec)
+{
+    return mca_hip_mvdr_sources_frames_weighted_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, nullptr, out_pcm, out_spec);
+}
+
 int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, const float *doa_rad,
                              float *out_pcm, float *out_spec)
 {
-    return mca_hip_mvdr_sources_frames_host(c, pcm, n_streams, n_frames, 1, doa_rad, out_pcm, out_spec);
+    return mca_hip_mvdr_sources_frames_weighted_host(c, pcm, n_streams, n_frames, 1, doa_rad, nullptr, out_pcm, out_spec);
 }
 
 int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spectrum_config *cfg)

@@ -76,6 +76,7 @@ __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
 template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
 template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(MvdrSolveArgs p);
 template <int Q, int S, int S1, bool PF> __global__ void k_mvdr_nulls(MvdrNullsArgs pa);   // soft nulls at the other look directions
+template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE> __global__ void k_mvdr_gated(MvdrGateArgs pa);   // per-frame covariance update weights
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance
 __global__ void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs p);

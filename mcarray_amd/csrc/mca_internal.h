@@ -511,6 +511,29 @@ struct MvdrNullsArgs {
     float null_gain;          // > 0: gain of the soft nulls at the other look directions
 };
 
+// k_mvdr_gated<Q, FULL, S, S1, PF, NULLS, REUSE> (kernels_mvdr_gate.hip): the solve kernels above with a per-frame
+// covariance update weight, update[streams][n_frames] (mca_hip_mvdr_sources_frames_weighted_dev).  A struct of its own like
+// MvdrNullsArgs, for the same reason.  null_gain is read by the NULLS instantiations only.
+struct MvdrGateArgs {
+    MvdrSolveArgs s;
+    const float *update;      // [streams][n_frames], never NULL here: a call without weights takes the unweighted kernels
+    float null_gain;
+};
+// NULLS = false, X(Q, S, S1 of FULL, S1 of !FULL, REUSE of FULL, REUSE of !FULL): S = 1 stands for k_mvdr_solve, the others are the rows
+// of MCA_MVDR_SOURCES_TABLE.  REUSE (a frozen frame behind a solved one runs the substitutions only) wherever it leaves the kernel
+// without scratch under its launch bounds; the others factorise on frozen frames too.
+#define MCA_MVDR_GATE_PLAIN_TABLE(X) \
+    X(1, 1, 1, 1, true, true) X(1, 2, 2, 2, true, true) X(1, 3, 3, 3, true, true) X(1, 4, 4, 4, true, true) \
+    X(2, 1, 1, 1, true, true) X(2, 2, 2, 2, true, true) X(2, 3, 3, 3, true, true) X(2, 4, 4, 4, true, true) \
+    X(3, 1, 1, 1, true, true) X(3, 2, 2, 2, true, true) X(3, 3, 3, 3, true, true) X(3, 4, 4, 4, true, true) \
+    X(4, 1, 1, 1, true, true) X(4, 2, 2, 2, false, false) X(4, 3, 3, 3, false, false) X(4, 4, 2, 2, false, false)
+// NULLS = true, X(Q, S, S1, PF, REUSE): the rows of MCA_MVDR_NULLS_TABLE
+#define MCA_MVDR_GATE_NULLS_TABLE(X) \
+    X(1, 2, 2, true, true) X(1, 3, 3, true, true) X(1, 4, 4, true, true) \
+    X(2, 2, 2, true, true) X(2, 3, 3, true, true) X(2, 4, 4, true, true) \
+    X(3, 2, 2, true, true) X(3, 3, 3, true, true) X(3, 4, 4, true, false) \
+    X(4, 2, 2, true, false) X(4, 3, 3, true, false) X(4, 4, 2, false, false)
+
 // k_mvdr_spectrum<Q> / k_mvdr_spectrum_pick (kernels_mvdr_spectrum.hip): the Capon spatial spectrum of the covariance a
 // context holds, P[i] = sum_k w[k] / (d(theta_i,k)^H PhiL[k]^-1 d(theta_i,k)).  A workgroup takes one stream and one chunk of
 // MVDR_SPEC_CHUNK consecutive bins (chunk c = bins 64 c ... 64 c + 63, cut to the band); its four waves leave one partial sum per

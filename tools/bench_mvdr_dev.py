@@ -3,8 +3,11 @@ on device buffers, with the per-kernel split from the library's HIP events and a
 against the CPU oracle.  Usage: python tools/bench_mvdr_dev.py [--streams 256] [--frames 64] [--mics 16] [--steps 10]
 With --sources S (2 ... 4) it times the sources call with S look directions per frame instead, under --null-gain g (soft nulls
 at the other look directions; 0, the default, is the plain sources call), and the spot check goes against the float64 twin of
-that call (tests/mvdr_nulls_twin.py).  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the
-entry points it lacks are left unbound, --null-gain must then stay 0."""
+that call (tests/mvdr_nulls_twin.py).  --update ones / half passes per-frame covariance update weights (the weighted solve kernel):
+all 1, or every second run of 8 frames frozen (weight 0; the frames a noise-only covariance freezes, and where the solve reuses
+its factor); the spot check then goes against tests/mvdr_gate_twin.py.  The weighted row of DESIGN.md 4.5 is k_mvdr_solve_ms of
+--update none, ones and half.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+points it lacks are left unbound, --null-gain must then stay 0 and --update none."""
 import argparse
 import json
 import os
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--check", type=int, default=1)
     ap.add_argument("--sources", type=int, default=0, help="time the sources call with this many look directions per frame")
     ap.add_argument("--null-gain", type=float, default=0.0, help="gain of the soft nulls of the sources call")
+    ap.add_argument("--update", choices=["none", "ones", "half"], default="none", help="covariance update weights of the call")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -55,6 +59,12 @@ def main():
         p0 = synth.noise_source_stream(xs, np.deg2rad(20.0), fs, L, 77) + synth.noise_source_stream(xs, np.deg2rad(-50.0), fs, L, 78, snr_db=60)
         pcm[0] = torch.from_numpy(p0.astype(np.float32)).to(dev)
     st = torch.cuda.current_stream().cuda_stream
+    upd = None
+    if a.update != "none":
+        w = np.ones((a.streams, a.frames), dtype=np.float32)
+        if a.update == "half":
+            w[:, (np.arange(a.frames) // 8) % 2 == 1] = 0.0
+        upd = torch.from_numpy(w).to(dev)
     if a.sources:
         look = torch.tensor(LOOK[:a.sources], device=dev, dtype=torch.float32)
         doa = look[None, None, :].expand(a.streams, a.frames, a.sources).contiguous()
@@ -62,17 +72,26 @@ def main():
         bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=a.sources)
         if a.null_gain != 0.0:
             bf.set_null_gain(a.null_gain)
-        step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
+        step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **({} if upd is None else {"update": upd}))
     else:
         doa = torch.full((a.streams, a.frames), float(np.deg2rad(20.0)), device=dev, dtype=torch.float32)
         out = torch.empty((a.streams, a.frames * hop), device=dev, dtype=torch.float32)
         bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams)
-        step = lambda: bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
+        step = lambda: bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **({} if upd is None else {"update": upd}))
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize()
     res = {}
-    if a.check and a.sources:
+    if a.check and upd is not None:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import mvdr_gate_twin as gt
+        bf.reset()
+        step()
+        torch.cuda.synchronize()
+        tw = gt.mvdr_gate_stream(fs, N, xs, pcm[0].cpu().numpy().astype(np.float64), doa[0].cpu().numpy(), a.null_gain, upd[0].cpu().numpy())
+        o0 = out[0].cpu().numpy().reshape(tw["out"].shape)
+        res["audio_err_rel_max"] = float(max(np.abs(o0[s] - tw["out"][s]).max() / np.abs(tw["out"][s]).max() for s in range(o0.shape[0])))
+    elif a.check and a.sources:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
         import mvdr_nulls_twin as nt
         bf.reset()
@@ -84,7 +103,7 @@ def main():
     elif a.check:
         from oracle import pyoracle as po
         bf.reset()
-        bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st)
+        step()
         torch.cuda.synchronize()
         o = po.MVDR(fs, N, xs).stream(pcm[0].cpu().numpy().astype(np.float64), np.full(a.frames, float(np.float32(np.deg2rad(20.0)))))
         err = np.abs(out[0].cpu().numpy() - o["out"]).max() / np.abs(o["out"]).max()
@@ -98,7 +117,8 @@ def main():
     dt = (time.perf_counter() - t0) / a.steps
     frames = a.streams * a.frames
     if a.sources:
-        res.update(dict(sources=a.sources, null_gain=a.null_gain, lib=os.environ.get("MCA_HIP_LIB", "default")))
+        res.update(dict(sources=a.sources, null_gain=a.null_gain))
+    res.update(dict(update=a.update, lib=os.environ.get("MCA_HIP_LIB", "default")))
     res.update(dict(workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N), ms_per_step=dt * 1e3,
                     frames_per_s=frames / dt, algorithmic_GBps=frames / dt * (a.mics * hop * 4 + hop * 4) / 1e9))
     for kid, name in ((0, "k_mvdr_analyse"), (1, "k_mvdr_solve"), (2, "k_mvdr_synth")):

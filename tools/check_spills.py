@@ -1,7 +1,7 @@
 """Register lint of the built library: no MVDR solve kernel may spill to scratch.
 
-The k_mvdr_solve / k_mvdr_solve_sources / k_mvdr_nulls instantiations for 13 ... 16 microphones sit a register or two under the
-256 that __launch_bounds__(256, 2) allows (DESIGN.md sections 4.2, 4.3), so another compiler version may start to spill them without a word;
+The k_mvdr_solve / k_mvdr_solve_sources / k_mvdr_nulls / k_mvdr_gated instantiations for 13 ... 16 microphones sit a register or two under
+the 256 that __launch_bounds__(256, 2) allows (DESIGN.md sections 4.2, 4.3, 4.5), so another compiler version may start to spill them without a word;
 a spilled column loop costs more than the sharing gains.  This script reads the kernel metadata of every gfx950 code object
 inside mcarray_amd/libmcarray_hip.so and lists the kernels whose name matches the pattern and whose .vgpr_spill_count or
 .private_segment_fixed_size is not 0.  (.sgpr_spill_count is not in the rule: scalar registers spill into lanes of a vector
@@ -17,6 +17,7 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 FIELDS = ("vgpr_spill_count", "private_segment_fixed_size")
+DEFAULT_PATTERNS = (r"k_mvdr_(solve|nulls)", r"k_mvdr_gated")      # the unweighted solve kernels; those with update weights
 KEY = re.compile(r"^(?:  - |    )\.(\w+):\s*(.*)$")       # a key of a kernel's own map (those of its arguments sit deeper)
 
 
@@ -52,7 +53,7 @@ def kernels(lib):
 
 if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mcarray_amd", "libmcarray_hip.so")
-    pat = re.compile(sys.argv[2] if len(sys.argv) > 2 else r"k_mvdr_(solve|nulls)")
+    pat = re.compile(sys.argv[2] if len(sys.argv) > 2 else "|".join(DEFAULT_PATTERNS))
     ks = [k for k in kernels(lib) if pat.search(k.get("name", ""))]
     if not ks or any(f not in k for k in ks for f in FIELDS + ("vgpr_count",)):
         raise RuntimeError("kernel metadata of %s not understood (%d kernels match)" % (lib, len(ks)))
