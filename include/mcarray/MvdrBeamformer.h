@@ -74,6 +74,28 @@ public:
         check(mca_hip_mvdr_get_null_gain(_ctx, &g));
         return g;
     }
+    // The decision-directed Wiener post-filter on the outputs of both process() overloads (mca_hip_mvdr_set_postfilter): smoothing in
+    // [0, 1), gainFloor in [0, 1], noiseScale in (0, 100].  Enabling starts the filter's state from zero, disabling frees it; the three
+    // values may change between chunks without touching that state.
+    void setPostFilter(bool enable, double smoothing = 0.98, double gainFloor = 0.1, double noiseScale = 1.0)
+    {
+        mca_hip_mvdr_postfilter_config cfg;
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.enable = enable ? 1 : 0;
+        cfg.smoothing = smoothing;
+        cfg.gain_floor = gainFloor;
+        cfg.noise_scale = noiseScale;
+        check(mca_hip_mvdr_set_postfilter(_ctx, &cfg));
+    }
+    void getPostFilter(bool &enable, double &smoothing, double &gainFloor, double &noiseScale) const
+    {
+        mca_hip_mvdr_postfilter_config cfg;
+        check(mca_hip_mvdr_get_postfilter(_ctx, &cfg));
+        enable = cfg.enable != 0;
+        smoothing = cfg.smoothing;
+        gainFloor = cfg.gain_floor;
+        noiseScale = cfg.noise_scale;
+    }
     // The Capon spatial spectrum of the covariance the stream holds, and its peaks (mca_hip_mvdr_spectrum_*): nAngles 2 ... 361 from
     // -pi/2 to pi/2, the band of bins [binLo, binHi], weighting MCA_HIP_MVDR_SPECTRUM_POWER / _NORMALISED, nPeaks 1 ... 4.  The peak
     // angles are look directions as setDOAs() takes them: process a chunk, read peaks(), setDOAs() for the next chunk.

@@ -646,6 +646,45 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *ctx, const float 
                                              const float *update_dev, float *out_pcm_dev, float *out_spec_dev, void *stream);
 int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
                                               const float *doa_rad, const float *update, float *out_pcm, float *out_spec);
+/* Decision-directed Wiener post-filter on the beamformed spectra: the single-channel stage that turns an MVDR with a noise-only
+ * covariance (the update weights above) into the multichannel Wiener filter.  MVDR removes what is spatially separable; the
+ * residual noise at its output has the power 1 / (d^H PhiL^-1 d), the p_r of the soft nulls.  Per stream, output slot s (look
+ * direction), bin k and frame t, with Y the output of the call as stated above (plain, sources or nulls; weighted or not), PhiL_t
+ * the loaded covariance AFTER the frame's update, tr_t its trace and d_s the frame's steering vector:
+ *     p   = noise_scale / (d_s^H PhiL_t^-1 d_s)      if tr_t > 1e-30, else 0
+ *           (for every null gain the PLAIN estimate p_s of the soft-null definition, not the nulled denominator)
+ *     N   = smoothing * A_{t-1} + (1 - smoothing) * max(|Y|^2 - p, 0)
+ *     G   = 1                                        if p == 0   (digital silence so far: delay-and-sum, nothing to subtract)
+ *           fmaxf(gain_floor, N / (N + p))           otherwise   (N + p > 0 there)
+ *     Z   = G * Y,      A_t = |Z|^2
+ * the decision-directed Wiener gain with a priori SNR N/p, written without a division by p.  out_spec and out_pcm carry Z in
+ * place of Y; the covariance, its trace, the Capon spectrum and the update weights are untouched by the filter.
+ * A is stream state: fp32 [max_streams][max_sources][K], zero on a fresh context, after mca_hip_mvdr_reset and on enabling.  The
+ * slots s >= n_sources of the streams in a call are zeroed by that call, whether it has out_pcm or not (the tails' rule: a source
+ * that a call leaves out restarts from silence); the single-look entry points use slot 0; mca_hip_mvdr_set_max_sources on an
+ * enabled context keeps the slots that both sizes have and zeroes the others, as it does for the tails.
+ * Accepted, all finite: smoothing in [0, 1) (default 0.98), gain_floor in [0, 1] (default 0.1), noise_scale in (0, 100] (default
+ * 1); anything else, a wrong struct_size included, is MCA_HIP_ERR_INVALID_ARGUMENT and leaves configuration and state as they were.
+ * The three values are processing parameters like the null gain: they may change between calls without touching A, state blobs
+ * neither carry nor check them.  enable 1 -> 0 frees A, 0 -> 1 starts from zero.  All six mca_hip_mvdr_*frames* calls honour the
+ * setting.  Exact points:
+ *   - disabled (the default) is the call as it was: the same kernels launched, the same bytes;
+ *   - gain_floor == 1 gives the bytes of the disabled call (fmaxf(1, x <= 1) == 1 and 1 * Y is exact), in spectra and audio, and
+ *     the same covariance bytes;
+ *   - how a stream is cut into calls does not change its bytes.
+ * State blobs: an enabled context writes version 3 -- covariances, traces, tails, then A, host[0] = max_sources, host[1] = 1 -- which
+ * loads only into an enabled context with the same max_sources.  Version 1 and 2 blobs are refused by an enabled context, a
+ * version 3 blob by a disabled one (MCA_HIP_ERR_INVALID_ARGUMENT, the state untouched); disabled contexts read and write what
+ * they always did. */
+typedef struct {
+    int struct_size;
+    int enable;
+    double smoothing;
+    double gain_floor;
+    double noise_scale;
+} mca_hip_mvdr_postfilter_config;
+int mca_hip_mvdr_set_postfilter(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_postfilter_config *cfg);
+int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_postfilter_config *cfg);
 /* Capon (minimum-variance) spatial spectrum of the covariance the context holds now (after its last frames call or state load),
  * and its peaks: the MVDR power estimate p = 1 / (d^H PhiL^-1 d) of the nulls above on a grid of angles.  Per stream, with
  *     theta_i      = -pi/2 + i pi/(D-1), i = 0 ... D-1 (in double),       D = n_angles
@@ -684,12 +723,15 @@ int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *spect
 int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum, float *peak_doa, float *peak_val);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
-/* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream */
+/* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream (and the
+ * post-filter's A of a context that has it enabled: version 3, above) */
 long long mca_hip_mvdr_state_size(const mca_hip_mvdr_ctx *ctx);
 int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long blob_bytes);
 /* per-kernel timing as mca_hip_set_timing / mca_hip_get_timing: kernel_id 0 = analysis, 1 = solve, 2 = synthesis,
- * 3 = spectrum (both kernels of a mca_hip_mvdr_spectrum_* call) */
+ * 3 = spectrum (both kernels of a mca_hip_mvdr_spectrum_* call), 4 = post-filter.  kernel_id 4 exists on a context that has had the
+ * post-filter enabled at some time (it stays readable after disabling); a context that never enabled it refuses 4 like every
+ * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT) */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

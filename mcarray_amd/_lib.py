@@ -106,6 +106,16 @@ class MvdrSpectrumConfig(C.Structure):
     ]
 
 
+class MvdrPostfilterConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("enable", C.c_int),
+        ("smoothing", C.c_double),
+        ("gain_floor", C.c_double),
+        ("noise_scale", C.c_double),
+    ]
+
+
 class Gcc2TrackerConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -227,6 +237,8 @@ SYMBOLS = [
     ("mca_hip_mvdr_set_max_sources", C.c_int, [C.c_void_p, C.c_int]),
     ("mca_hip_mvdr_set_null_gain", C.c_int, [C.c_void_p, C.c_double]),
     ("mca_hip_mvdr_get_null_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("mca_hip_mvdr_set_postfilter", C.c_int, [C.c_void_p, C.POINTER(MvdrPostfilterConfig)]),
+    ("mca_hip_mvdr_get_postfilter", C.c_int, [C.c_void_p, C.POINTER(MvdrPostfilterConfig)]),
     ("mca_hip_mvdr_sources_frames_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_sources_frames_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp]),

@@ -852,9 +852,11 @@ class MvdrBeamformer(_StateBlob):
     of the next chunk (mca_hip_mvdr_spectrum_*).
     update= of the process calls: per-frame covariance update weights [streams][F] in [0, 1] (1: learn as usual, 0: leave the
     covariance as it is and beamform with it), e.g. 1 - voiced of a localiser for a noise-only covariance
-    (mca_hip_mvdr_sources_frames_weighted_*; None: all 1)."""
+    (mca_hip_mvdr_sources_frames_weighted_*; None: all 1).
+    set_postfilter() puts the decision-directed Wiener post-filter behind the solve of every process call: the noise-only MVDR
+    becomes the multichannel Wiener filter (mca_hip_mvdr_set_postfilter)."""
 
-    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM = 0, 1, 2, 3
+    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER = 0, 1, 2, 3, 4
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  null_gain=0.0):
@@ -904,6 +906,24 @@ class MvdrBeamformer(_StateBlob):
         g = C.c_double(0.0)
         self._check(self._lib.mca_hip_mvdr_get_null_gain(self.h, C.byref(g)))
         return g.value
+
+    def set_postfilter(self, enable=True, smoothing=0.98, gain_floor=0.1, noise_scale=1.0):
+        """the decision-directed Wiener post-filter on the outputs of every process call (include/mcarray_hip.h,
+        mca_hip_mvdr_set_postfilter): smoothing in [0, 1), gain_floor in [0, 1], noise_scale in (0, 100].  The three values are
+        processing parameters; enabling starts the filter's state from zero, disabling frees it."""
+        cfg = _lib.MvdrPostfilterConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrPostfilterConfig)
+        cfg.enable = 1 if enable else 0
+        cfg.smoothing = float(smoothing)
+        cfg.gain_floor = float(gain_floor)
+        cfg.noise_scale = float(noise_scale)
+        self._check(self._lib.mca_hip_mvdr_set_postfilter(self.h, C.byref(cfg)))
+
+    def get_postfilter(self):
+        """dict(enable, smoothing, gain_floor, noise_scale) as the context holds them"""
+        cfg = _lib.MvdrPostfilterConfig()
+        self._check(self._lib.mca_hip_mvdr_get_postfilter(self.h, C.byref(cfg)))
+        return dict(enable=bool(cfg.enable), smoothing=cfg.smoothing, gain_floor=cfg.gain_floor, noise_scale=cfg.noise_scale)
 
     def close(self):
         if getattr(self, "h", None):

@@ -29,6 +29,13 @@ struct mca_hip_mvdr_ctx {
     double null_gain = 0.0;       // soft nulls at the other look directions of a call with n_sources >= 2 (mca_hip_mvdr_set_null_gain);
                                   // a processing parameter, not stream state: no part of the state blobs
     float *d_tail[2] = {nullptr, nullptr}; int tail_cur = 0;   // [max_streams][max_sources][H]; a single-look call uses slot 0
+    // the Wiener post-filter (mca_hip_mvdr_set_postfilter): the three values are processing parameters like null_gain; A is stream state
+    bool pf_on = false;
+    bool pf_ever = false;         // enabled at some time: timing slot 4 exists (a context that never enabled it refuses kernel_id 4 as it always did)
+    double pf_smoothing = 0.98, pf_gain_floor = 0.1, pf_noise_scale = 1.0;
+    float *d_pf_A = nullptr;      // [max_streams][max_sources][K] |Z|^2 of the frame before; allocated while enabled
+    float *d_pf_pn = nullptr;     // workspace [y_rows][K]: the residual noise power of every output of the call; while enabled
+    float *d_pf_ones = nullptr; size_t pf_ones_n = 0;   // update weights of a call that brings none, all 1
     // workspace
     float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
     float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // rows x look directions; d_T: factored steering phasors [rows][M][N/64 + 33]
@@ -44,8 +51,8 @@ struct mca_hip_mvdr_ctx {
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[4] = {};
-    double t_ms[4] = {};
+    int t_launches[5] = {};
+    double t_ms[5] = {};
     std::string err;
 };
 
@@ -72,6 +79,7 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
     if (!c) return;
     auto F = [](void *p) { if (p) (void)hipFree(p); };
     F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
+    F(c->d_pf_A); F(c->d_pf_pn); F(c->d_pf_ones);
     F(c->d_X); F(c->d_Y); F(c->d_T); F(c->d_spec_grid); F(c->d_spec_T); F(c->d_spec_part);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->stage.release();
@@ -84,13 +92,23 @@ int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
     VHIP_TRY(c, hipMemsetAsync(c->d_phi, 0, ns * c->K * c->tri * sizeof(float2), st));
     VHIP_TRY(c, hipMemsetAsync(c->d_trace, 0, ns * c->K * 4, st));
     for (int i = 0; i < 2; ++i) VHIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, ns * c->max_sources * c->H * 4, st));
+    if (c->d_pf_A) VHIP_TRY(c, hipMemsetAsync(c->d_pf_A, 0, ns * c->max_sources * c->K * 4, st));
     VHIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
-int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources)
+int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_ones)
 {
     auto F = [](void *p) { if (p) (void)hipFree(p); };
+    if (c->pf_on && want_ones && rows > c->pf_ones_n) {
+        // a call without update weights still takes the gated kernels (they emit the noise plane): weights of 1, whose bytes are
+        // those of the unweighted kernels
+        F(c->d_pf_ones); c->d_pf_ones = nullptr; c->pf_ones_n = 0;
+        VHIP_TRY(c, hipMalloc((void **)&c->d_pf_ones, rows * 4));
+        std::vector<float> ones(rows, 1.f);
+        VHIP_TRY(c, hipMemcpy(c->d_pf_ones, ones.data(), rows * 4, hipMemcpyHostToDevice));
+        c->pf_ones_n = rows;
+    }
     if (rows > c->x_rows) {
         F(c->d_X); c->d_X = nullptr; c->x_rows = 0;
         VHIP_TRY(c, hipMalloc((void **)&c->d_X, rows * c->K * c->M * sizeof(float2)));
@@ -98,11 +116,12 @@ int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources)
     }
     const size_t yrows = rows * n_sources;
     if (yrows > c->y_rows) {
-        F(c->d_Y); F(c->d_T); c->d_Y = nullptr; c->d_T = nullptr; c->y_rows = 0;
+        F(c->d_Y); F(c->d_T); F(c->d_pf_pn); c->d_Y = nullptr; c->d_T = nullptr; c->d_pf_pn = nullptr; c->y_rows = 0;
         VHIP_TRY(c, hipMalloc((void **)&c->d_Y, yrows * c->K * sizeof(float2)));
         VHIP_TRY(c, hipMalloc((void **)&c->d_T, yrows * c->M * (c->N / 64 + 33) * sizeof(float2)));
         c->y_rows = yrows;
     }
+    if (c->pf_on && !c->d_pf_pn && c->y_rows) VHIP_TRY(c, hipMalloc((void **)&c->d_pf_pn, c->y_rows * c->K * 4));
     return MCA_HIP_OK;
 }
 
@@ -222,6 +241,21 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
         if (nt[1]) (void)hipFree(nt[1]);
         return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("overlap-add tails of the new sources: ") + hipGetErrorString(e));
     }
+    // the post-filter's A [max_streams][max_sources][K] of an enabled context, by the same rule
+    float *na = nullptr;
+    if (c->pf_on) {
+        const size_t arow = (size_t)c->K * 4, abytes = ns * max_sources * arow;
+        e = hipMalloc((void **)&na, abytes);
+        if (e == hipSuccess) e = hipMemset(na, 0, abytes);
+        if (e == hipSuccess) e = hipMemcpy2D(na, max_sources * arow, c->d_pf_A, c->max_sources * arow, keep * arow, ns, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (na) (void)hipFree(na);
+            (void)hipFree(nt[0]); (void)hipFree(nt[1]);
+            return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("post-filter state of the new sources: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(c->d_pf_A);
+        c->d_pf_A = na;
+    }
     (void)hipFree(c->d_tail[0]); (void)hipFree(c->d_tail[1]);
     c->d_tail[0] = nt[0]; c->d_tail[1] = nt[1]; c->tail_cur = 0; c->max_sources = max_sources;
     return MCA_HIP_OK;
@@ -242,6 +276,54 @@ int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *c, double *null_gain)
 {
     if (!c || !null_gain) return MCA_HIP_ERR_INVALID_ARGUMENT;
     *null_gain = c->null_gain;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_set_postfilter(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_postfilter_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_postfilter_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!std::isfinite(cfg->smoothing) || cfg->smoothing < 0.0 || cfg->smoothing >= 1.0)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "smoothing must be finite and in [0,1)");
+    if (!std::isfinite(cfg->gain_floor) || cfg->gain_floor < 0.0 || cfg->gain_floor > 1.0)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "gain_floor must be finite and in [0,1]");
+    if (!std::isfinite(cfg->noise_scale) || !(cfg->noise_scale > 0.0) || cfg->noise_scale > 100.0)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "noise_scale must be finite and in (0,100]");
+    const bool on = cfg->enable != 0;
+    if (on != c->pf_on) {
+        VHIP_TRY(c, hipSetDevice(c->cfg.device));
+        VHIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
+        if (on) {
+            // A starts from zero; the noise plane and the ones come with the first call (ensure_ws)
+            const size_t bytes = (size_t)c->cfg.max_streams * c->max_sources * c->K * 4;
+            float *na = nullptr;
+            hipError_t e = hipMalloc((void **)&na, bytes);
+            if (e == hipSuccess) e = hipMemset(na, 0, bytes);
+            if (e != hipSuccess) {
+                if (na) (void)hipFree(na);
+                return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("post-filter state: ") + hipGetErrorString(e));
+            }
+            c->d_pf_A = na;
+        } else {
+            if (c->d_pf_A) (void)hipFree(c->d_pf_A);
+            if (c->d_pf_pn) (void)hipFree(c->d_pf_pn);
+            if (c->d_pf_ones) (void)hipFree(c->d_pf_ones);
+            c->d_pf_A = nullptr; c->d_pf_pn = nullptr; c->d_pf_ones = nullptr; c->pf_ones_n = 0;
+        }
+        c->pf_on = on;
+        if (on) c->pf_ever = true;
+    }
+    c->pf_smoothing = cfg->smoothing; c->pf_gain_floor = cfg->gain_floor; c->pf_noise_scale = cfg->noise_scale;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_postfilter_config *cfg)
+{
+    if (!c || !cfg) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    cfg->struct_size = (int)sizeof(mca_hip_mvdr_postfilter_config);
+    cfg->enable = c->pf_on ? 1 : 0;
+    cfg->smoothing = c->pf_smoothing; cfg->gain_floor = c->pf_gain_floor; cfg->noise_scale = c->pf_noise_scale;
     return MCA_HIP_OK;
 }
 
@@ -270,9 +352,11 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
     const size_t rows = (size_t)n_streams * n_frames;
     // the beamformed spectra go straight to the caller's buffer when one is given
     float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : nullptr;
-    int rc = ensure_ws(c, rows, n_sources);
+    int rc = ensure_ws(c, rows, n_sources, !update);
     if (rc) return rc;
     if (!Y) Y = c->d_Y;
+    const bool pf = c->pf_on;
+    if (pf && !update) update = c->d_pf_ones;                                          // the gated kernels emit the noise plane
 
     MvdrAnalyseArgs aa{};
     aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = n_frames;
@@ -319,19 +403,37 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
         if (pieces > 1) { sa.phi_out = c->d_phi_tail; sa.trace_out = c->d_trace_tail; sa.out_base = pid0; }
         else { sa.phi_out = c->d_phi; sa.trace_out = c->d_trace; sa.out_base = 0; }
         const dim3 sgrid((unsigned)((n_prob + 63) / 64 * pieces));
+        if (pf) {
+            // post-filter: the instantiation of kernels_mvdr_gate_noise.hip, which leaves the residual noise power beside Y
+            const MvdrGateNoiseArgs gn{MvdrGateArgs{sa, update, null_gain}, c->d_pf_pn};
+            const bool full = c->M == 4 * Q;
+#define SOLVE_NOISE_NULLS(QQ, SS, S1, PF, R)                                                                                \
+    if (nulls && Q == QQ && n_sources == SS)                                                                               \
+        hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, true>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, gn);
+            MCA_MVDR_GATE_NULLS_TABLE(SOLVE_NOISE_NULLS)
+#undef SOLVE_NOISE_NULLS
+#define SOLVE_NOISE(QQ, SS, S1F, S1P, PFP, RF, RP)                                                                               \
+    if (!nulls && Q == QQ && n_sources == SS) {                                                                                 \
+        if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, true>), sgrid, dim3(256), 0, st, gn);   \
+        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, PFP, false, RP, true>), sgrid, dim3(256), 0, st, gn);        \
+    }
+            MCA_MVDR_NOISE_PLAIN_TABLE(SOLVE_NOISE)
+#undef SOLVE_NOISE
+            return;
+        }
         if (update) {
             // per-frame covariance update weights: the instantiation of kernels_mvdr_gate.hip that stands for the kernel chosen below
             const MvdrGateArgs ga{sa, update, null_gain};
             const bool full = c->M == 4 * Q;
 #define SOLVE_GATE_NULLS(QQ, SS, S1, PF, R)                                                                                 \
     if (nulls && Q == QQ && n_sources == SS)                                                                               \
-        hipLaunchKernelGGL((k_mvdr_gated<QQ, false, SS, S1, PF, true, R>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga);
+        hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, false>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga);
             MCA_MVDR_GATE_NULLS_TABLE(SOLVE_GATE_NULLS)
 #undef SOLVE_GATE_NULLS
 #define SOLVE_GATE(QQ, SS, S1F, S1P, RF, RP)                                                                                \
     if (!nulls && Q == QQ && n_sources == SS) {                                                                            \
-        if (full) hipLaunchKernelGGL((k_mvdr_gated<QQ, true, SS, S1F, true, false, RF>), sgrid, dim3(256), 0, st, ga);   \
-        else hipLaunchKernelGGL((k_mvdr_gated<QQ, false, SS, S1P, true, false, RP>), sgrid, dim3(256), 0, st, ga);       \
+        if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, false>), sgrid, dim3(256), 0, st, ga);   \
+        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, true, false, RP, false>), sgrid, dim3(256), 0, st, ga);       \
     }
             MCA_MVDR_GATE_PLAIN_TABLE(SOLVE_GATE)
 #undef SOLVE_GATE
@@ -388,6 +490,23 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
         launch_solve(0, n_prob, 1);
     }
     t_end(c, st);
+
+    if (pf) {
+        // Z = G Y in place, between the solve and the synthesis.  A slot the call leaves out restarts from silence, whether the
+        // call has out_pcm or not; the kernel touches only the slots below n_sources
+        if (n_sources < c->max_sources)
+            VHIP_TRY(c, hipMemset2DAsync(c->d_pf_A + (size_t)n_sources * c->K, (size_t)c->max_sources * c->K * 4, 0,
+                                         (size_t)(c->max_sources - n_sources) * c->K * 4, (size_t)n_streams, st));
+        MvdrPostfilterArgs fa{};
+        fa.Y = Y; fa.pn = c->d_pf_pn; fa.A = c->d_pf_A;
+        fa.n_streams = n_streams; fa.S = n_sources; fa.slots = c->max_sources; fa.n_frames = n_frames; fa.K = c->K;
+        fa.smoothing = (float)c->pf_smoothing; fa.one_minus_smoothing = (float)(1.0 - c->pf_smoothing);
+        fa.gain_floor = (float)c->pf_gain_floor; fa.noise_scale = (float)c->pf_noise_scale;
+        const long long cells = (long long)n_streams * n_sources * c->K;
+        t_begin(c, 4, st);
+        hipLaunchKernelGGL(k_mvdr_postfilter, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fa);
+        t_end(c, st);
+    }
 
     if (out_pcm) {
         MvdrSynthArgs ya{};
@@ -610,7 +729,9 @@ constexpr unsigned MVDR_MAGIC = 0x4d435644u;   // "MCVD"
 std::vector<BlobPart> mvdr_parts(mca_hip_mvdr_ctx *c)
 {
     const size_t ns = (size_t)c->cfg.max_streams;
-    return {{c->d_phi, ns * c->K * c->tri * sizeof(float2)}, {c->d_trace, ns * c->K * 4}, {c->d_tail[c->tail_cur], ns * c->max_sources * c->H * 4}};
+    std::vector<BlobPart> parts{{c->d_phi, ns * c->K * c->tri * sizeof(float2)}, {c->d_trace, ns * c->K * 4}, {c->d_tail[c->tail_cur], ns * c->max_sources * c->H * 4}};
+    if (c->pf_on) parts.push_back({c->d_pf_A, ns * c->max_sources * c->K * 4});
+    return parts;
 }
 unsigned mvdr_cfg_hash(const mca_hip_mvdr_ctx *c)
 {
@@ -632,8 +753,10 @@ int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *c, void *blob, long long bytes)
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     // version 1: one tail per stream (a context that never raised max_sources writes what it always wrote);
-    // version 2: max_sources tails per stream, the maximum in host[0]
+    // version 2: max_sources tails per stream, the maximum in host[0];
+    // version 3: a context with the post-filter enabled -- the same and A behind the tails, the maximum in host[0], 1 in host[1]
     BlobHeader h{MVDR_MAGIC, c->max_sources > 1 ? 2 : 1, mvdr_cfg_hash(c), 0, {c->max_sources > 1 ? c->max_sources : 0, 0, 0, 0}};
+    if (c->pf_on) { h.version = 3; h.host[0] = c->max_sources; h.host[1] = 1; }
     const int rc = blob_save(mvdr_parts(c), h, blob, bytes);
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
@@ -645,12 +768,15 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long byt
     BlobHeader h;
     if (blob && bytes >= (long long)sizeof(BlobHeader)) {
         std::memcpy(&h, blob, sizeof(h));
-        const int blob_max = h.version == 2 ? (int)h.host[0] : 1;
-        if (h.magic == MVDR_MAGIC && (h.version == 1 || h.version == 2) && blob_max != c->max_sources)
+        const int blob_max = h.version == 2 || h.version == 3 ? (int)h.host[0] : 1;
+        if (h.magic == MVDR_MAGIC && h.version >= 1 && h.version <= 3 && (h.version == 3) != c->pf_on)
+            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, h.version == 3 ? "state blob was saved with the post-filter enabled, this context has it disabled"
+                                                                         : "state blob was saved without the post-filter, this context has it enabled");
+        if (h.magic == MVDR_MAGIC && h.version >= 1 && h.version <= 3 && blob_max != c->max_sources)
             return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with max_sources = " + std::to_string(blob_max) +
                                                               ", this one has " + std::to_string(c->max_sources));
     }
-    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->max_sources > 1 ? 2 : 1);
+    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1);
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
 
@@ -663,7 +789,7 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id >= 4) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c || kernel_id < 0 || kernel_id >= (c->pf_ever ? 5 : 4)) return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));
         float ms = 0.f;

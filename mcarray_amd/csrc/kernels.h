@@ -76,7 +76,9 @@ __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
 template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
 template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(MvdrSolveArgs p);
 template <int Q, int S, int S1, bool PF> __global__ void k_mvdr_nulls(MvdrNullsArgs pa);   // soft nulls at the other look directions
-template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE> __global__ void k_mvdr_gated(MvdrGateArgs pa);   // per-frame covariance update weights
+// per-frame covariance update weights (mvdr_gate.h); NOISE: ... and the noise plane of the post-filter, with MvdrGateNoiseArgs
+template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, bool NOISE> __global__ void k_mvdr_gated_t(MvdrGateArgsOf<NOISE> pa);
+__global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                                   // decision-directed Wiener gain on the solve's output
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance
 __global__ void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs p);

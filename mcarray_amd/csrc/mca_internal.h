@@ -511,7 +511,7 @@ struct MvdrNullsArgs {
     float null_gain;          // > 0: gain of the soft nulls at the other look directions
 };
 
-// k_mvdr_gated<Q, FULL, S, S1, PF, NULLS, REUSE> (kernels_mvdr_gate.hip): the solve kernels above with a per-frame
+// k_mvdr_gated_t<Q, FULL, S, S1, PF, NULLS, REUSE, NOISE = false> (mvdr_gate.h, kernels_mvdr_gate.hip): the solve kernels above with a per-frame
 // covariance update weight, update[streams][n_frames] (mca_hip_mvdr_sources_frames_weighted_dev).  A struct of its own like
 // MvdrNullsArgs, for the same reason.  null_gain is read by the NULLS instantiations only.
 struct MvdrGateArgs {
@@ -533,6 +533,36 @@ struct MvdrGateArgs {
     X(2, 2, 2, true, true) X(2, 3, 3, true, true) X(2, 4, 4, true, true) \
     X(3, 2, 2, true, true) X(3, 3, 3, true, true) X(3, 4, 4, true, false) \
     X(4, 2, 2, true, false) X(4, 3, 3, true, false) X(4, 4, 2, false, false)
+
+// k_mvdr_gated_t<..., NOISE = true> (kernels_mvdr_gate_noise.hip): the gated solve that also stores
+// the residual noise power of every output, 1 / (d_s^H PhiL^-1 d_s) or 0 for a silent bin, to pn at the index of Y -- the solve of a
+// context with the post-filter enabled.  A struct of its own, for the reason MvdrNullsArgs has one.
+struct MvdrGateNoiseArgs {
+    MvdrGateArgs g;
+    float *pn;                // [streams][S][n_frames][K] fp32
+};
+template <bool NOISE> struct MvdrGateArgsSel { using type = MvdrGateArgs; };
+template <> struct MvdrGateArgsSel<true> { using type = MvdrGateNoiseArgs; };
+template <bool NOISE> using MvdrGateArgsOf = typename MvdrGateArgsSel<NOISE>::type;   // the argument of k_mvdr_gated_t<..., NOISE>
+// NULLS = false, X(Q, S, S1 of FULL, S1 of !FULL, PF of !FULL, REUSE of FULL, REUSE of !FULL): the rows of MCA_MVDR_GATE_PLAIN_TABLE
+// but for the two that spill 12 bytes per lane with the store (M = 13 ... 15 with three and four directions): those give up the load a
+// frame ahead (250 VGPRs, no scratch; one direction per pass is clean too, but repeats the factorisation per direction).  The
+// NULLS = true kernels take the rows of MCA_MVDR_GATE_NULLS_TABLE as they are.
+#define MCA_MVDR_NOISE_PLAIN_TABLE(X) \
+    X(1, 1, 1, 1, true, true, true) X(1, 2, 2, 2, true, true, true) X(1, 3, 3, 3, true, true, true) X(1, 4, 4, 4, true, true, true) \
+    X(2, 1, 1, 1, true, true, true) X(2, 2, 2, 2, true, true, true) X(2, 3, 3, 3, true, true, true) X(2, 4, 4, 4, true, true, true) \
+    X(3, 1, 1, 1, true, true, true) X(3, 2, 2, 2, true, true, true) X(3, 3, 3, 3, true, true, true) X(3, 4, 4, 4, true, true, true) \
+    X(4, 1, 1, 1, true, true, true) X(4, 2, 2, 2, true, false, false) X(4, 3, 3, 3, false, false, false) X(4, 4, 2, 2, false, false, false)
+
+// the decision-directed Wiener post-filter on the beamformed spectra (kernels_mvdr_postfilter.hip): one thread per
+// (stream, slot, bin), bins fastest; Y is rewritten in place, A is read and written once
+struct MvdrPostfilterArgs {
+    float2 *Y;                // [streams][S][n_frames][K] output of the solve, replaced by Z = G Y
+    const float *pn;          // [streams][S][n_frames][K] 1 / (d^H PhiL^-1 d), 0 = silent (MvdrGateNoiseArgs)
+    float *A;                 // [streams][slots][K] |Z|^2 of the frame before
+    int n_streams, S, slots, n_frames, K;
+    float smoothing, one_minus_smoothing, gain_floor, noise_scale;
+};
 
 // k_mvdr_spectrum<Q> / k_mvdr_spectrum_pick (kernels_mvdr_spectrum.hip): the Capon spatial spectrum of the covariance a
 // context holds, P[i] = sum_k w[k] / (d(theta_i,k)^H PhiL[k]^-1 d(theta_i,k)).  A workgroup takes one stream and one chunk of

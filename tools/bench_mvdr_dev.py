@@ -6,8 +6,11 @@ at the other look directions; 0, the default, is the plain sources call), and th
 that call (tests/mvdr_nulls_twin.py).  --update ones / half passes per-frame covariance update weights (the weighted solve kernel):
 all 1, or every second run of 8 frames frozen (weight 0; the frames a noise-only covariance freezes, and where the solve reuses
 its factor); the spot check then goes against tests/mvdr_gate_twin.py.  The weighted row of DESIGN.md 4.5 is k_mvdr_solve_ms of
---update none, ones and half.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
-points it lacks are left unbound, --null-gain must then stay 0 and --update none."""
+--update none, ones and half.  --postfilter enables the decision-directed Wiener post-filter (defaults of
+mca_hip_mvdr_set_postfilter): the solve then also writes the noise plane, k_mvdr_postfilter runs behind it, the result carries its
+time and its traffic (20 B per cell and the state once each way) as a rate, and the spot check goes against
+tests/mvdr_postfilter_twin.py on the scale of the twin's unfiltered audio.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+points it lacks are left unbound, --null-gain must then stay 0, --update none and --postfilter off (as far as the build lacks them)."""
 import argparse
 import json
 import os
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--sources", type=int, default=0, help="time the sources call with this many look directions per frame")
     ap.add_argument("--null-gain", type=float, default=0.0, help="gain of the soft nulls of the sources call")
     ap.add_argument("--update", choices=["none", "ones", "half"], default="none", help="covariance update weights of the call")
+    ap.add_argument("--postfilter", action="store_true", help="enable the Wiener post-filter (its defaults)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -78,11 +82,23 @@ def main():
         out = torch.empty((a.streams, a.frames * hop), device=dev, dtype=torch.float32)
         bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams)
         step = lambda: bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **({} if upd is None else {"update": upd}))
+    if a.postfilter:
+        bf.set_postfilter(True)
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize()
     res = {}
-    if a.check and upd is not None:
+    if a.check and a.postfilter:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import mvdr_postfilter_twin as pt
+        bf.reset()
+        step()
+        torch.cuda.synchronize()
+        tw = pt.mvdr_postfilter_stream(fs, N, xs, pcm[0].cpu().numpy().astype(np.float64), doa[0].cpu().numpy(), a.null_gain,
+                                       None if upd is None else upd[0].cpu().numpy())
+        o0 = out[0].cpu().numpy().reshape(tw["out"].shape)
+        res["audio_err_of_unfiltered_peak_max"] = float(max(np.abs(o0[s] - tw["out"][s]).max() / np.abs(tw["raw_out"][s]).max() for s in range(o0.shape[0])))
+    elif a.check and upd is not None:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
         import mvdr_gate_twin as gt
         bf.reset()
@@ -124,6 +140,12 @@ def main():
     for kid, name in ((0, "k_mvdr_analyse"), (1, "k_mvdr_solve"), (2, "k_mvdr_synth")):
         n, ms = bf.get_timing(kid)
         res[name + "_ms"] = ms / max(n, 1)
+    if a.postfilter:
+        n, ms = bf.get_timing(bf.K_POSTFILTER)
+        slots = max(a.sources, 1)
+        traffic = 20.0 * a.streams * slots * a.frames * K + 2 * 4.0 * a.streams * slots * K
+        res.update(dict(postfilter=True, k_mvdr_postfilter_ms=ms / max(n, 1), k_mvdr_postfilter_bytes=traffic,
+                        k_mvdr_postfilter_GBps=traffic / (ms / max(n, 1) * 1e-3) / 1e9 if ms > 0 else 0.0))
     print(json.dumps(res))
 
 

@@ -1,7 +1,7 @@
-"""Register lint of the built library: no MVDR solve kernel may spill to scratch.
+"""Register lint of the built library: no MVDR solve kernel, nor the post-filter behind it, may spill to scratch.
 
 The k_mvdr_solve / k_mvdr_solve_sources / k_mvdr_nulls / k_mvdr_gated instantiations for 13 ... 16 microphones sit a register or two under
-the 256 that __launch_bounds__(256, 2) allows (DESIGN.md sections 4.2, 4.3, 4.5), so another compiler version may start to spill them without a word;
+the 256 that __launch_bounds__(256, 2) allows (DESIGN.md sections 4.2, 4.3, 4.5, 4.6), so another compiler version may start to spill them without a word;
 a spilled column loop costs more than the sharing gains.  This script reads the kernel metadata of every gfx950 code object
 inside mcarray_amd/libmcarray_hip.so and lists the kernels whose name matches the pattern and whose .vgpr_spill_count or
 .private_segment_fixed_size is not 0.  (.sgpr_spill_count is not in the rule: scalar registers spill into lanes of a vector
@@ -17,7 +17,8 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 FIELDS = ("vgpr_spill_count", "private_segment_fixed_size")
-DEFAULT_PATTERNS = (r"k_mvdr_(solve|nulls)", r"k_mvdr_gated")      # the unweighted solve kernels; those with update weights
+# the unweighted solve kernels; those with update weights (k_mvdr_gated_t, with and without the noise plane); the post-filter
+DEFAULT_PATTERNS = (r"k_mvdr_(solve|nulls)", r"k_mvdr_gated", r"k_mvdr_postfilter")
 KEY = re.compile(r"^(?:  - |    )\.(\w+):\s*(.*)$")       # a key of a kernel's own map (those of its arguments sit deeper)
 
 
