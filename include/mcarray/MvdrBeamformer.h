@@ -68,6 +68,12 @@ public:
     // Both process() overloads honour it; no part of the stream's state.
     void setUpdateWeight(double updateWeight) { _update = updateWeight; }
     double getUpdateWeight() const { return _update; }
+    // The frames the next process() chunk of nSamples samples per channel will complete: the rows of the updateMask it may carry.
+    int framesCompletedBy(int nSamples) const
+    {
+        const long have = static_cast<long>(_pending[0].size()) + (nSamples > 0 ? nSamples : 0);
+        return have >= _N ? static_cast<int>((have - _N) / (_N / 2) + 1) : 0;
+    }
     double getNullGain() const
     {
         double g = 0.0;
@@ -146,9 +152,11 @@ public:
         for (std::vector<float> &b : _pending) b.clear();
     }
 
-    // chunked PCM in (one pointer per channel), beamformed PCM out; returns the samples written (a multiple of the hop)
+    // chunked PCM in (one pointer per channel), beamformed PCM out; returns the samples written (a multiple of the hop).
+    // updateMask: covariance update weights per frame and bin, [framesCompletedBy(nSamples)][N/2 + 1]
+    // (mca_hip_mvdr_sources_frames_masked_*); it overrides setUpdateWeight() for this call.
     template <typename Tin, typename Tout>
-    int process(const std::vector<Tin *> &in, int nSamples, Tout *out, int outSize)
+    int process(const std::vector<Tin *> &in, int nSamples, Tout *out, int outSize, const float *updateMask = nullptr)
     {
         const int hop = _N / 2;
         const int F = pend(in, nSamples);
@@ -157,16 +165,18 @@ public:
         std::vector<float> pcm = frames(F);
         std::vector<float> doa(static_cast<size_t>(F), static_cast<float>(_doa)), audio(static_cast<size_t>(F) * static_cast<size_t>(hop));
         const std::vector<float> upd = weights(F);
-        check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, 1, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
+        if (updateMask) check(mca_hip_mvdr_sources_frames_masked_host(_ctx, pcm.data(), 1, F, 1, doa.data(), updateMask, audio.data(), nullptr));
+        else check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, 1, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
         for (int i = 0; i < F * hop; ++i) out[i] = static_cast<Tout>(audio[static_cast<size_t>(i)]);
         consume(F);
         return F * hop;
     }
 
     // the same for the look directions of setDOAs(): out[s] receives the output of direction s; returns the samples written per output.
-    // A direction that a call leaves out (fewer directions than in the call before) restarts from silence.
+    // A direction that a call leaves out (fewer directions than in the call before) restarts from silence.  updateMask as above (one
+    // mask for all directions: they share the covariance).
     template <typename Tin, typename Tout>
-    int process(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize)
+    int process(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize, const float *updateMask = nullptr)
     {
         const int hop = _N / 2, S = static_cast<int>(_doas.size());
         if (S == 0) throw MCArrayException("process: setDOAs() first");
@@ -179,7 +189,8 @@ public:
         for (int t = 0; t < F; ++t)
             for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
         const std::vector<float> upd = weights(F);
-        check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, S, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
+        if (updateMask) check(mca_hip_mvdr_sources_frames_masked_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMask, audio.data(), nullptr));
+        else check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, S, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
         consume(F);

@@ -646,6 +646,35 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *ctx, const float 
                                              const float *update_dev, float *out_pcm_dev, float *out_spec_dev, void *stream);
 int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
                                               const float *doa_rad, const float *update, float *out_pcm, float *out_spec);
+/* Time-frequency update masks: the same with one weight per stream, frame AND bin.  A target such as speech is sparse in time and
+ * frequency: after its onset almost every frame holds it in some bins and only noise in the others, so no per-frame weight both
+ * keeps the target and lets the covariance follow the noise.  The mask of a mask estimator, of a coherence or SNR
+ * rule, or the expanded per-band decisions of the masking modules goes in as it is.
+ *   update_mask_dev [streams][F][K] float   contiguous, K = N/2 + 1, for all look directions of the frame; NULL = all 1.  The
+ *                                           index (a F + t) K + k is formed in 64 bits.
+ * With u = fminf(fmaxf(update_mask[a][t][k], 0), 1) (a NaN counts as 0), per stream a, frame t and bin k:
+ *     a_tk     = 1 - (1 - alpha) u
+ *     Phi_t[k] = a_tk Phi_{t-1}[k] + (1 - a_tk) x[k] x[k]^H
+ *     tr_t[k]  = a_tk tr_{t-1}[k] + (1 - a_tk) |x[k]|^2
+ * and everything behind the recursion is as stated for the weighted call: the loading, the weights for one to four look
+ * directions, the soft nulls, the post-filter (whose p, A and G are per bin already), the Capon spectrum of the held covariance,
+ * and the delay-and-sum rule of a trace <= 1e-30 -- now per bin: a bin whose cells were all closed since the reset stays
+ * delay-and-sum while its neighbours are MVDR.  Exact points:
+ *   - a NULL mask, or a mask whose every cell is 1, gives the bytes of mca_hip_mvdr_sources_frames_* in spectra, audio,
+ *     covariance, traces and post-filter state;
+ *   - update_mask[a][t][k] == update[a][t] for all k gives the bytes of mca_hip_mvdr_sources_frames_weighted_* with that update;
+ *   - a cell with u == 0 leaves Phi[k] and tr[k] bit for bit; the frame is still beamformed in that bin, and the other bins of the
+ *     frame update;
+ *   - the bytes of bin k (spectra, covariance) depend on column k of the mask only, whatever its neighbours' cells are;
+ *   - how a stream is cut into calls does not change its bytes.
+ * Per-frame weights and a mask are not combined: a caller who has both multiplies them.  The mask is an input of the call: state
+ * blobs neither carry nor check it.  The argument checks are those of the weighted call; n_sources = 1 on any context is the
+ * single-look form.  The host call stages the mask in a stage slot of its own. */
+int mca_hip_mvdr_sources_frames_masked_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev, long long stream_stride, long long mic_stride,
+                                           int n_streams, int n_frames, int n_sources, const float *doa_rad_dev,
+                                           const float *update_mask_dev, float *out_pcm_dev, float *out_spec_dev, void *stream);
+int mca_hip_mvdr_sources_frames_masked_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
+                                            const float *doa_rad, const float *update_mask, float *out_pcm, float *out_spec);
 /* Decision-directed Wiener post-filter on the beamformed spectra: the single-channel stage that turns an MVDR with a noise-only
  * covariance (the update weights above) into the multichannel Wiener filter.  MVDR removes what is spatially separable; the
  * residual noise at its output has the power 1 / (d^H PhiL^-1 d), the p_r of the soft nulls.  Per stream, output slot s (look

@@ -245,6 +245,9 @@ SYMBOLS = [
     ("mca_hip_mvdr_sources_frames_weighted_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_sources_frames_weighted_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_sources_frames_masked_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_sources_frames_masked_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]),
     ("mca_hip_mvdr_spectrum_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrSpectrumConfig)]),
     ("mca_hip_mvdr_spectrum_get_grid", C.c_int, [C.c_void_p, c_fp]),
     ("mca_hip_mvdr_spectrum_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

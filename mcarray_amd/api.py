@@ -840,6 +840,21 @@ class TemporalGCCBinauralLocalisation(_StateBlob):
         return r
 
 
+def update_mask_from_decisions(decisions, center_freqs, fft_size):
+    """The per-band decisions of the masking modules (FastBinauralMasking.process / BinauralMaskingImpl.process: int32 [...][45],
+    0 = enhance, the band is kept as the target's; 1 = temporal mask, 2 = spatial mask, the band is attenuated) as the update_mask of
+    MvdrBeamformer [...][K], K = fft_size/2 + 1: 0 where the band is enhanced (the covariance must not learn the target), 1 where it
+    is masked.  center_freqs [45]: the band centres in cycles per sample, thresholds()[1] of the masking object; bin k, at
+    k / fft_size cycles per sample, takes the band with the nearest centre -- the mel triangle that weighs most there."""
+    dec = np.asarray(decisions)
+    cen = np.asarray(center_freqs, dtype=np.float64)
+    if dec.shape[-1:] != cen.shape or cen.ndim != 1 or np.any(np.diff(cen) <= 0):
+        raise MCArrayHipError("decisions must be [...][B] and center_freqs [B], ascending")
+    K = int(fft_size) // 2 + 1
+    band_of = np.searchsorted(0.5 * (cen[:-1] + cen[1:]), np.arange(K) / float(fft_size), side="left")
+    return np.ascontiguousarray((dec != 0)[..., band_of], dtype=np.float32)
+
+
 class MvdrBeamformer(_StateBlob):
     _STATE = "mvdr"
     """Frequency-domain beamformer with a per-bin spatial covariance (BASELINE.json configs[3]; SURVEY A.9).
@@ -853,6 +868,9 @@ class MvdrBeamformer(_StateBlob):
     update= of the process calls: per-frame covariance update weights [streams][F] in [0, 1] (1: learn as usual, 0: leave the
     covariance as it is and beamform with it), e.g. 1 - voiced of a localiser for a noise-only covariance
     (mca_hip_mvdr_sources_frames_weighted_*; None: all 1).
+    update_mask= instead: one weight per frame and bin, [streams][F][K] -- the mask of a mask estimator or an SNR rule: a bin
+    that holds the target in a frame is left alone while the other bins of that frame learn
+    (mca_hip_mvdr_sources_frames_masked_*).  update= and update_mask= are not combined: multiply them.
     set_postfilter() puts the decision-directed Wiener post-filter behind the solve of every process call: the noise-only MVDR
     becomes the multichannel Wiener filter (mca_hip_mvdr_set_postfilter)."""
 
@@ -952,9 +970,29 @@ class MvdrBeamformer(_StateBlob):
             raise MCArrayHipError("update must be a contiguous float32 tensor [streams][F]")
         return _ptr(update)
 
-    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None):
+    def _mask_host(self, update, update_mask, A, F):
+        """float32 [streams][F][K] from anything that broadcasts to it"""
+        if update is not None:
+            raise MCArrayHipError("update and update_mask are not combined: pass their product as update_mask")
+        try:
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(update_mask, dtype=np.float32), (A, F, self.K)))
+        except (ValueError, TypeError):
+            raise MCArrayHipError("update_mask must broadcast to [streams][F][K]")
+
+    def _mask_dev(self, update, update_mask, A, n_frames):
+        if update is not None:
+            raise MCArrayHipError("update and update_mask are not combined: pass their product as update_mask")
+        m = update_mask
+        if not getattr(m, "is_cuda", False):
+            raise MCArrayHipError("update_mask must be a contiguous float32 tensor [streams][F][K] on the device")
+        if m.dim() != 3 or not m.is_contiguous() or tuple(m.shape) != (A, n_frames, self.K) or m.element_size() != 4 or not m.is_floating_point():
+            raise MCArrayHipError("update_mask must be a contiguous float32 tensor [streams][F][K]")
+        return _ptr(m)
+
+    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None, update_mask=None):
         """pcm float32 [streams][M][(F+1)*hop], doa_rad [streams][F] (or a scalar), update None or [streams][F] covariance update
-        weights -> dict(out [streams][F*hop], spec complex64 [streams][F][K])"""
+        weights, or update_mask None or [streams][F][K] weights per frame and bin -> dict(out [streams][F*hop], spec complex64
+        [streams][F][K])"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
             pcm = pcm[None]
@@ -967,7 +1005,11 @@ class MvdrBeamformer(_StateBlob):
         spec = np.empty((A, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
         po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
-        if update is None:
+        if update_mask is not None:
+            upd = self._mask_host(update, update_mask, A, F)
+            self._check(self._lib.mca_hip_mvdr_sources_frames_masked_host(self.h, pcm.ctypes.data_as(fp), A, F, 1, doa.ctypes.data_as(fp),
+                                                                          upd.ctypes.data_as(fp), po, ps))
+        elif update is None:
             self._check(self._lib.mca_hip_mvdr_frames_host(self.h, pcm.ctypes.data_as(fp), A, F, doa.ctypes.data_as(fp), po, ps))
         else:
             upd = self._update_host(update, A, F)
@@ -975,22 +1017,26 @@ class MvdrBeamformer(_StateBlob):
                                                                             upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None):
+    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F]
         float32, out_pcm [streams][F*hop], out_spec [streams][F][K][2] (contiguous), update None or [streams][F] float32 covariance
-        update weights (contiguous); asynchronous on `stream` (a raw hipStream_t or None)."""
+        update weights (contiguous), or update_mask None or [streams][F][K] float32 (contiguous); asynchronous on `stream` (a raw
+        hipStream_t or None)."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
-        if update is None:
+        if update_mask is not None:
+            self._check(self._lib.mca_hip_mvdr_sources_frames_masked_dev(self.h, p, sa, sc, A, n_frames, 1, _ptr(doa_rad),
+                                                                         self._mask_dev(update, update_mask, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
+        elif update is None:
             self._check(self._lib.mca_hip_mvdr_frames_dev(self.h, p, sa, sc, A, n_frames, _ptr(doa_rad), _ptr(out_pcm), _ptr(out_spec), stream))
         else:
             self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_dev(self.h, p, sa, sc, A, n_frames, 1, _ptr(doa_rad),
                                                                            self._update_dev(update, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
 
-    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None):
+    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None, update_mask=None):
         """S look directions per frame from one analysis, covariance recursion and factorisation: pcm float32
         [streams][M][(F+1)*hop], doa_rad [streams][F][S] (S <= max_sources; the layout of the localiser's "doa"), update None or
-        [streams][F] covariance update weights (one per frame for all its directions) ->
+        [streams][F] covariance update weights (one per frame for all its directions), or update_mask None or [streams][F][K] ->
         dict(out [streams][S][F*hop], spec complex64 [streams][S][F][K]).  Output s is what process() gives with doa_rad[:, :, s]."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
@@ -1008,7 +1054,11 @@ class MvdrBeamformer(_StateBlob):
         spec = np.empty((A, S, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
         po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
-        if update is None:
+        if update_mask is not None:
+            upd = self._mask_host(update, update_mask, A, F)
+            self._check(self._lib.mca_hip_mvdr_sources_frames_masked_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp),
+                                                                          upd.ctypes.data_as(fp), po, ps))
+        elif update is None:
             self._check(self._lib.mca_hip_mvdr_sources_frames_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp), po, ps))
         else:
             upd = self._update_host(update, A, F)
@@ -1016,16 +1066,19 @@ class MvdrBeamformer(_StateBlob):
                                                                             upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None):
+    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F][S]
         float32 (e.g. the doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec
-        [streams][S][F][K][2] (contiguous), update None or [streams][F] float32 covariance update weights (contiguous);
-        asynchronous on `stream` (a raw hipStream_t or None)."""
+        [streams][S][F][K][2] (contiguous), update None or [streams][F] float32 covariance update weights (contiguous), or
+        update_mask None or [streams][F][K] float32 (contiguous); asynchronous on `stream` (a raw hipStream_t or None)."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
         if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
             raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
-        if update is None:
+        if update_mask is not None:
+            self._check(self._lib.mca_hip_mvdr_sources_frames_masked_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad),
+                                                                         self._mask_dev(update, update_mask, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
+        elif update is None:
             self._check(self._lib.mca_hip_mvdr_sources_frames_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad), _ptr(out_pcm),
                                                                   _ptr(out_spec), stream))
         else:

@@ -327,12 +327,14 @@ int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_postfilt
     return MCA_HIP_OK;
 }
 
+namespace {
+
 // the three launches of a call with n_sources look directions per frame: doa_rad [streams][F][n_sources],
-// out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]; update [streams][F] covariance update weights or NULL
-// (all 1: the unweighted solve kernels)
-int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
-                                             int n_frames, int n_sources, const float *doa_rad, const float *update, float *out_pcm,
-                                             float *out_spec, void *stream)
+// out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]; update: covariance update weights [streams][F], or
+// [streams][F][K] (masked: k_mvdr_masked_t), or NULL (all 1: the unweighted solve kernels)
+int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                    int n_frames, int n_sources, const float *doa_rad, const float *update, bool masked, float *out_pcm,
+                    float *out_spec, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (n_sources < 1 || n_sources > c->max_sources)
@@ -356,6 +358,7 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
     if (rc) return rc;
     if (!Y) Y = c->d_Y;
     const bool pf = c->pf_on;
+    if (!update) masked = false;
     if (pf && !update) update = c->d_pf_ones;                                          // the gated kernels emit the noise plane
 
     MvdrAnalyseArgs aa{};
@@ -408,32 +411,41 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
             const MvdrGateNoiseArgs gn{MvdrGateArgs{sa, update, null_gain}, c->d_pf_pn};
             const bool full = c->M == 4 * Q;
 #define SOLVE_NOISE_NULLS(QQ, SS, S1, PF, R)                                                                                \
-    if (nulls && Q == QQ && n_sources == SS)                                                                               \
-        hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, true>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, gn);
+    if (nulls && Q == QQ && n_sources == SS) {                                                                             \
+        if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1, PF && MCA_MVDR_MASK_PF(QQ, SS), true, false, true>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, gn); \
+        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, true>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, gn);        \
+    }
             MCA_MVDR_GATE_NULLS_TABLE(SOLVE_NOISE_NULLS)
 #undef SOLVE_NOISE_NULLS
 #define SOLVE_NOISE(QQ, SS, S1F, S1P, PFP, RF, RP)                                                                               \
     if (!nulls && Q == QQ && n_sources == SS) {                                                                                 \
-        if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, true>), sgrid, dim3(256), 0, st, gn);   \
-        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, PFP, false, RP, true>), sgrid, dim3(256), 0, st, gn);        \
+        if (masked && full) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, true, SS, S1F, MCA_MVDR_MASK_PF(QQ, SS), false, false, true>), sgrid, dim3(256), 0, st, gn);    \
+        else if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1P, PFP && MCA_MVDR_MASK_PF(QQ, SS), false, false, true>), sgrid, dim3(256), 0, st, gn);     \
+        else if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, true>), sgrid, dim3(256), 0, st, gn);       \
+        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, PFP, false, RP, true>), sgrid, dim3(256), 0, st, gn);                 \
     }
             MCA_MVDR_NOISE_PLAIN_TABLE(SOLVE_NOISE)
 #undef SOLVE_NOISE
             return;
         }
         if (update) {
-            // per-frame covariance update weights: the instantiation of kernels_mvdr_gate.hip that stands for the kernel chosen below
+            // covariance update weights: the instantiation of kernels_mvdr_gate.hip (per frame) or kernels_mvdr_mask.hip (per frame and
+            // bin) that stands for the kernel chosen below
             const MvdrGateArgs ga{sa, update, null_gain};
             const bool full = c->M == 4 * Q;
 #define SOLVE_GATE_NULLS(QQ, SS, S1, PF, R)                                                                                 \
-    if (nulls && Q == QQ && n_sources == SS)                                                                               \
-        hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, false>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga);
+    if (nulls && Q == QQ && n_sources == SS) {                                                                             \
+        if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1, PF && MCA_MVDR_MASK_PF(QQ, SS), true, false, false>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga); \
+        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, false>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga);        \
+    }
             MCA_MVDR_GATE_NULLS_TABLE(SOLVE_GATE_NULLS)
 #undef SOLVE_GATE_NULLS
 #define SOLVE_GATE(QQ, SS, S1F, S1P, RF, RP)                                                                                \
     if (!nulls && Q == QQ && n_sources == SS) {                                                                            \
-        if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, false>), sgrid, dim3(256), 0, st, ga);   \
-        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, true, false, RP, false>), sgrid, dim3(256), 0, st, ga);       \
+        if (masked && full) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, true, SS, S1F, MCA_MVDR_MASK_PF(QQ, SS), false, false, false>), sgrid, dim3(256), 0, st, ga);   \
+        else if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1P, MCA_MVDR_MASK_PF(QQ, SS), false, false, false>), sgrid, dim3(256), 0, st, ga);   \
+        else if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, false>), sgrid, dim3(256), 0, st, ga);      \
+        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, true, false, RP, false>), sgrid, dim3(256), 0, st, ga);               \
     }
             MCA_MVDR_GATE_PLAIN_TABLE(SOLVE_GATE)
 #undef SOLVE_GATE
@@ -533,6 +545,50 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
     return MCA_HIP_OK;
 }
 
+// the host-pointer form: n_upd floats of weights per (stream, frame), 1 or K
+int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                     const float *update, bool masked, float *out_pcm, float *out_spec)
+{
+    if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const long long ms = (long long)(n_frames + 1) * c->H, ss = ms * c->M;
+    const size_t nf = (size_t)n_streams * n_frames * n_sources;
+    float *d_pcm = (float *)c->stage.get(0, (size_t)ss * n_streams * 4), *d_doa = (float *)c->stage.get(1, nf * 4);
+    float *d_out = out_pcm ? (float *)c->stage.get(2, nf * c->H * 4) : nullptr;
+    float *d_spec = out_spec ? (float *)c->stage.get(3, nf * c->K * 8) : nullptr;
+    const size_t nu = (size_t)n_streams * n_frames * (masked ? (size_t)c->K : 1);
+    float *d_upd = update ? (float *)c->stage.get(masked ? 8 : 7, nu * 4) : nullptr;  // (slots 4 ... 6: the spectrum's; 8: the mask's own)
+    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd))
+        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
+    VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
+    if (update) VHIP_TRY(c, hipMemcpy(d_upd, update, nu * 4, hipMemcpyHostToDevice));
+    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, masked, d_out, d_spec, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
+    if (out_spec) VHIP_TRY(c, hipMemcpy(out_spec, d_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+}  // namespace
+
+int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                             int n_frames, int n_sources, const float *doa_rad, const float *update, float *out_pcm,
+                                             float *out_spec, void *stream)
+{
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update, false, out_pcm, out_spec, stream);
+}
+
+// update_mask [streams][F][K] or NULL (all 1)
+int mca_hip_mvdr_sources_frames_masked_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                           int n_frames, int n_sources, const float *doa_rad, const float *update_mask, float *out_pcm,
+                                           float *out_spec, void *stream)
+{
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, stream);
+}
+
 int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
                                     int n_frames, int n_sources, const float *doa_rad, float *out_pcm, float *out_spec, void *stream)
 {
@@ -548,27 +604,13 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
 int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                               const float *update, float *out_pcm, float *out_spec)
 {
-    if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const long long ms = (long long)(n_frames + 1) * c->H, ss = ms * c->M;
-    const size_t nf = (size_t)n_streams * n_frames * n_sources;
-    float *d_pcm = (float *)c->stage.get(0, (size_t)ss * n_streams * 4), *d_doa = (float *)c->stage.get(1, nf * 4);
-    float *d_out = out_pcm ? (float *)c->stage.get(2, nf * c->H * 4) : nullptr;
-    float *d_spec = out_spec ? (float *)c->stage.get(3, nf * c->K * 8) : nullptr;
-    const size_t nu = (size_t)n_streams * n_frames;
-    float *d_upd = update ? (float *)c->stage.get(7, nu * 4) : nullptr;               // (slots 4 ... 6: the spectrum's)
-    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd))
-        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
-    VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
-    if (update) VHIP_TRY(c, hipMemcpy(d_upd, update, nu * 4, hipMemcpyHostToDevice));
-    const int rc = mca_hip_mvdr_sources_frames_weighted_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, d_out, d_spec, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
-    if (out_spec) VHIP_TRY(c, hipMemcpy(out_spec, d_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update, false, out_pcm, out_spec);
+}
+
+int mca_hip_mvdr_sources_frames_masked_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                                            const float *update_mask, float *out_pcm, float *out_spec)
+{
+    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec);
 }
 
 int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,

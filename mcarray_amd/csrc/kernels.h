@@ -78,6 +78,8 @@ template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(
 template <int Q, int S, int S1, bool PF> __global__ void k_mvdr_nulls(MvdrNullsArgs pa);   // soft nulls at the other look directions
 // per-frame covariance update weights (mvdr_gate.h); NOISE: ... and the noise plane of the post-filter, with MvdrGateNoiseArgs
 template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, bool NOISE> __global__ void k_mvdr_gated_t(MvdrGateArgsOf<NOISE> pa);
+// ... with a weight per frame and bin, MvdrGateArgs::update = update_mask[streams][n_frames][K] (kernels_mvdr_mask.hip, kernels_mvdr_mask_noise.hip)
+template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, bool NOISE> __global__ void k_mvdr_masked_t(MvdrGateArgsOf<NOISE> pa);
 __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                                   // decision-directed Wiener gain on the solve's output
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance

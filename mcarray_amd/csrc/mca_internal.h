@@ -554,6 +554,14 @@ template <bool NOISE> using MvdrGateArgsOf = typename MvdrGateArgsSel<NOISE>::ty
     X(3, 1, 1, 1, true, true, true) X(3, 2, 2, 2, true, true, true) X(3, 3, 3, 3, true, true, true) X(3, 4, 4, 4, true, true, true) \
     X(4, 1, 1, 1, true, true, true) X(4, 2, 2, 2, true, false, false) X(4, 3, 3, 3, false, false, false) X(4, 4, 2, 2, false, false, false)
 
+// k_mvdr_masked_t<...> (mvdr_gate.h, kernels_mvdr_mask.hip, kernels_mvdr_mask_noise.hip): the gated kernels with a
+// weight per frame and bin, MvdrGateArgs::update = update_mask[streams][n_frames][K] (mca_hip_mvdr_sources_frames_masked_dev).  One
+// instantiation per row of the four tables above with the row's Q, S and S1 (so the per-frame-constant mask gives the bytes of the
+// gated kernel of that row), REUSE = false everywhere (with REUSE and a weight per quad the instantiations of three and four row
+// slots spill up to 158 registers, and a mixed wave would run both column bodies), and without the load a frame ahead where the
+// cell's address would otherwise cost scratch (four row slots with three and four directions)
+#define MCA_MVDR_MASK_PF(Q, S) ((Q) < 4 || (S) < 3)
+
 // the decision-directed Wiener post-filter on the beamformed spectra (kernels_mvdr_postfilter.hip): one thread per
 // (stream, slot, bin), bins fastest; Y is rewritten in place, A is read and written once
 struct MvdrPostfilterArgs {

@@ -9,7 +9,11 @@ its factor); the spot check then goes against tests/mvdr_gate_twin.py.  The weig
 --update none, ones and half.  --postfilter enables the decision-directed Wiener post-filter (defaults of
 mca_hip_mvdr_set_postfilter): the solve then also writes the noise plane, k_mvdr_postfilter runs behind it, the result carries its
 time and its traffic (20 B per cell and the state once each way) as a rate, and the spot check goes against
-tests/mvdr_postfilter_twin.py on the scale of the twin's unfiltered audio.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+tests/mvdr_postfilter_twin.py on the scale of the twin's unfiltered audio.  --mask times the table of DESIGN.md 4.7
+instead, one JSON line per row: for one and for three look directions the unweighted call, the per-frame weighted call (every second
+run of 8 frames frozen) and the masked call (update_mask [streams][F][K]) under a mask of ones, that per-frame pattern along the
+bins, blocks of 4 frames x 16 bins half of them open, and independent random binary cells (the worst divergence of the quads of a
+wave); a build without the masked entry points (MCA_HIP_LIB) runs the first two rows only.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
 points it lacks are left unbound, --null-gain must then stay 0, --update none and --postfilter off (as far as the build lacks them)."""
 import argparse
 import json
@@ -35,6 +39,47 @@ def bind_what_the_library_has():
     _lib.SYMBOLS = [sym for sym in _lib.SYMBOLS if hasattr(probe, sym[0])]
 
 
+def mask_table(a, fs, N, xs, pcm, st):
+    """the rows of DESIGN.md 4.7: solve kernel and whole call per update rule, for one and three look directions"""
+    hop, K = N // 2, N // 2 + 1
+    dev = pcm.device
+    rng = np.random.default_rng(7)
+    frame = np.ones((a.streams, a.frames), dtype=np.float32)
+    frame[:, (np.arange(a.frames) // 8) % 2 == 1] = 0.0
+    blocks = (rng.random((a.streams, (a.frames + 3) // 4, (K + 15) // 16)) < 0.5).astype(np.float32)
+    blocks = np.repeat(np.repeat(blocks, 4, axis=1), 16, axis=2)[:, :a.frames, :K]
+    rules = [("unweighted", {}), ("per-frame weights", dict(update=torch.from_numpy(frame).to(dev)))]
+    if hasattr(_lib.load(), "mca_hip_mvdr_sources_frames_masked_dev"):
+        masks = (("mask of ones", np.ones((a.streams, a.frames, K), dtype=np.float32)),
+                 ("mask constant along the bins", np.repeat(frame[:, :, None], K, axis=2)),
+                 ("mask of 4 x 16 blocks", blocks),
+                 ("mask of random cells", (rng.random((a.streams, a.frames, K)) < 0.5).astype(np.float32)))
+        rules += [(name, dict(update_mask=torch.from_numpy(np.ascontiguousarray(m)).to(dev))) for name, m in masks]
+    for S in (1, 3):
+        look = torch.tensor(LOOK[:S], device=dev, dtype=torch.float32)
+        doa = look[None, None, :].expand(a.streams, a.frames, S).contiguous()
+        out = torch.empty((a.streams, S, a.frames * hop), device=dev, dtype=torch.float32)
+        for name, kw in rules:
+            bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=S)
+            if a.postfilter:
+                bf.set_postfilter(True)
+            step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **kw)
+            for _ in range(a.warmup):
+                step()
+            bf.set_timing(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                step()
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / a.steps
+            n, ms = bf.get_timing(bf.K_SOLVE)
+            print(json.dumps(dict(rule=name, sources=S, postfilter=bool(a.postfilter), lib=os.environ.get("MCA_HIP_LIB", "default"),
+                                  workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N),
+                                  k_mvdr_solve_ms=ms / max(n, 1), ms_per_step=dt * 1e3)), flush=True)
+            bf.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -47,6 +92,7 @@ def main():
     ap.add_argument("--null-gain", type=float, default=0.0, help="gain of the soft nulls of the sources call")
     ap.add_argument("--update", choices=["none", "ones", "half"], default="none", help="covariance update weights of the call")
     ap.add_argument("--postfilter", action="store_true", help="enable the Wiener post-filter (its defaults)")
+    ap.add_argument("--mask", action="store_true", help="time the table of the time-frequency update masks (DESIGN.md 4.7)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -63,6 +109,8 @@ def main():
         p0 = synth.noise_source_stream(xs, np.deg2rad(20.0), fs, L, 77) + synth.noise_source_stream(xs, np.deg2rad(-50.0), fs, L, 78, snr_db=60)
         pcm[0] = torch.from_numpy(p0.astype(np.float32)).to(dev)
     st = torch.cuda.current_stream().cuda_stream
+    if a.mask:
+        return mask_table(a, fs, N, xs, pcm, st)
     upd = None
     if a.update != "none":
         w = np.ones((a.streams, a.frames), dtype=np.float32)

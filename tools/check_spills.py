@@ -17,8 +17,9 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 FIELDS = ("vgpr_spill_count", "private_segment_fixed_size")
-# the unweighted solve kernels; those with update weights (k_mvdr_gated_t, with and without the noise plane); the post-filter
-DEFAULT_PATTERNS = (r"k_mvdr_(solve|nulls)", r"k_mvdr_gated", r"k_mvdr_postfilter")
+# the unweighted solve kernels; those with update weights per frame (k_mvdr_gated_t, with and without the noise plane) and per
+# frame and bin (k_mvdr_masked_t, the same); the post-filter
+DEFAULT_PATTERNS = (r"k_mvdr_(solve|nulls)", r"k_mvdr_gated", r"k_mvdr_masked", r"k_mvdr_postfilter")
 KEY = re.compile(r"^(?:  - |    )\.(\w+):\s*(.*)$")       # a key of a kernel's own map (those of its arguments sit deeper)
 
 
