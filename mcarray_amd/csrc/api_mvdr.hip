@@ -1,7 +1,7 @@
 // api_mvdr.hip -- C ABI of the MVDR-style beamformer with a per-bin spatial covariance (include/mcarray_hip.h,
 // mca_hip_mvdr_*; BASELINE.json configs[3]; SURVEY A.9 -- no reference counterpart, conventions of Beamformer.cpp:59).
 // Host side only: owns the per-stream state (covariances, their traces, overlap-add tails) and the spectra
-// workspace, enqueues the three kernels of kernels_mvdr.hip.  No CPU fallback.
+// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h and kernels_mvdr_postfilter.hip.  No CPU fallback.
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
@@ -149,6 +149,28 @@ int fft_threads(int N, int nch)
 }
 
 }  // namespace
+
+namespace mca {
+
+// The solve kernel of a call (kernels.h): the hand-written kernel of kernels_mvdr.hip for the single look direction without weights, an
+// instantiation of k_mvdr_solve_t (mvdr_solve.h) for everything else.  Under the nulls one instantiation serves M = 4Q and M < 4Q.
+const void *mvdr_solve_kernel(int Q, bool full, int S, bool nulls, MvdrWeight w, bool noise, int *lds_bytes)
+{
+    *lds_bytes = 0;
+    if (mvdr_solve_hand_written(S, w, noise)) {
+        const void *k[4][2] = {{(const void *)k_mvdr_solve<1, false>, (const void *)k_mvdr_solve<1, true>}, {(const void *)k_mvdr_solve<2, false>, (const void *)k_mvdr_solve<2, true>},
+                               {(const void *)k_mvdr_solve<3, false>, (const void *)k_mvdr_solve<3, true>}, {(const void *)k_mvdr_solve<4, false>, (const void *)k_mvdr_solve<4, true>}};
+        return Q >= 1 && Q <= 4 ? k[Q - 1][full] : nullptr;
+    }
+    if (nulls) full = false;
+    switch (w) {
+    case MvdrWeight::NONE: return noise ? nullptr : mvdr_solve_kernel_of<MvdrWeight::NONE, false>(Q, full, S, nulls, lds_bytes);
+    case MvdrWeight::FRAME: return noise ? mvdr_solve_kernel_of<MvdrWeight::FRAME, true>(Q, full, S, nulls, lds_bytes) : mvdr_solve_kernel_of<MvdrWeight::FRAME, false>(Q, full, S, nulls, lds_bytes);
+    default: return noise ? mvdr_solve_kernel_of<MvdrWeight::CELL, true>(Q, full, S, nulls, lds_bytes) : mvdr_solve_kernel_of<MvdrWeight::CELL, false>(Q, full, S, nulls, lds_bytes);
+    }
+}
+
+}  // namespace mca
 
 extern "C" {
 
@@ -329,38 +351,10 @@ int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_postfilt
 
 namespace {
 
-// the three launches of a call with n_sources look directions per frame: doa_rad [streams][F][n_sources],
-// out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]; update: covariance update weights [streams][F], or
-// [streams][F][K] (masked: k_mvdr_masked_t), or NULL (all 1: the unweighted solve kernels)
-int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
-                    int n_frames, int n_sources, const float *doa_rad, const float *update, bool masked, float *out_pcm,
-                    float *out_spec, void *stream)
+// the analysis (timing slot 0): PCM -> X, and the steering tables T of doa_rad [streams][F][n_sources]
+int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams, int n_frames,
+                   int n_sources, const float *doa_rad, hipStream_t st)
 {
-    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (n_sources < 1 || n_sources > c->max_sources)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
-    if (!pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
-    if (!out_pcm && !out_spec) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
-    const long long need = (long long)(n_frames + 1) * c->H;
-    if (mic_stride < need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_stride shorter than (n_frames+1)*hop samples");
-    if (n_streams > 1 && stream_stride < (long long)(c->M - 1) * mic_stride + need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_stride too short");
-    if ((mic_stride & 1) || (stream_stride & 1) || (reinterpret_cast<uintptr_t>(pcm) & 7))
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
-    if (out_spec && (reinterpret_cast<uintptr_t>(out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const size_t rows = (size_t)n_streams * n_frames;
-    // the beamformed spectra go straight to the caller's buffer when one is given
-    float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : nullptr;
-    int rc = ensure_ws(c, rows, n_sources, !update);
-    if (rc) return rc;
-    if (!Y) Y = c->d_Y;
-    const bool pf = c->pf_on;
-    if (!update) masked = false;
-    if (pf && !update) update = c->d_pf_ones;                                          // the gated kernels emit the noise plane
-
     MvdrAnalyseArgs aa{};
     aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = n_frames;
     aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.S = n_sources; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = doa_rad;
@@ -388,7 +382,13 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
         hipLaunchKernelGGL(k_mvdr_analyse, dim3(n_frames, n_streams), dim3(fft_threads(c->N, c->M)), smem1, st, aa);
     }
     t_end(c, st);
+    return MCA_HIP_OK;
+}
 
+// the solve (timing slot 1): X, T -> Y, the covariance and, for the post-filter, the noise plane.  update: covariance update
+// weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
+int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float *update, bool masked, float2 *Y, hipStream_t st)
+{
     MvdrSolveArgs sa{};
     sa.X = c->d_X; sa.T = c->d_T;
     sa.n_frames = n_frames; sa.K = c->K; sa.M = c->M;
@@ -396,91 +396,24 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     sa.loading_over_m = (float)(c->cfg.loading / c->M);
     sa.phi = c->d_phi; sa.trace = c->d_trace; sa.Y = Y;
     sa.n_streams = n_streams; sa.S = n_sources;
-    const float null_gain = (float)c->null_gain;
-    const bool nulls = n_sources > 1 && null_gain > 0.f;                              // a gain that rounds to 0 in fp32 is gain 0
+    // the kernels that store the noise plane take weights: a call without them passes ones, whose bytes are those of no weights
+    sa.update = update ? update : c->pf_on ? c->d_pf_ones : nullptr;
+    sa.null_gain = (float)c->null_gain;
+    sa.pn = c->pf_on ? c->d_pf_pn : nullptr;
+    const bool nulls = n_sources > 1 && sa.null_gain > 0.f;                           // a gain that rounds to 0 in fp32 is gain 0
     const int Q = (c->M + 3) / 4;                                                     // row slots per lane
-    auto launch_solve = [&](long long pid0, long long n_prob, int pieces) {
+    int lds = 0;
+    const void *kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
+                                           c->pf_on, &lds);
+    if (!kernel) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
+    auto launch = [&](long long pid0, long long n_prob, int pieces) {
         sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
         // an unsplit launch updates the state in place; the pieces of a split one all read the entry state, so the last piece
         // writes the exit state to a scratch copy that is moved over behind the launch
         if (pieces > 1) { sa.phi_out = c->d_phi_tail; sa.trace_out = c->d_trace_tail; sa.out_base = pid0; }
         else { sa.phi_out = c->d_phi; sa.trace_out = c->d_trace; sa.out_base = 0; }
-        const dim3 sgrid((unsigned)((n_prob + 63) / 64 * pieces));
-        if (pf) {
-            // post-filter: the instantiation of kernels_mvdr_gate_noise.hip, which leaves the residual noise power beside Y
-            const MvdrGateNoiseArgs gn{MvdrGateArgs{sa, update, null_gain}, c->d_pf_pn};
-            const bool full = c->M == 4 * Q;
-#define SOLVE_NOISE_NULLS(QQ, SS, S1, PF, R)                                                                                \
-    if (nulls && Q == QQ && n_sources == SS) {                                                                             \
-        if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1, PF && MCA_MVDR_MASK_PF(QQ, SS), true, false, true>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, gn); \
-        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, true>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, gn);        \
-    }
-            MCA_MVDR_GATE_NULLS_TABLE(SOLVE_NOISE_NULLS)
-#undef SOLVE_NOISE_NULLS
-#define SOLVE_NOISE(QQ, SS, S1F, S1P, PFP, RF, RP)                                                                               \
-    if (!nulls && Q == QQ && n_sources == SS) {                                                                                 \
-        if (masked && full) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, true, SS, S1F, MCA_MVDR_MASK_PF(QQ, SS), false, false, true>), sgrid, dim3(256), 0, st, gn);    \
-        else if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1P, PFP && MCA_MVDR_MASK_PF(QQ, SS), false, false, true>), sgrid, dim3(256), 0, st, gn);     \
-        else if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, true>), sgrid, dim3(256), 0, st, gn);       \
-        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, PFP, false, RP, true>), sgrid, dim3(256), 0, st, gn);                 \
-    }
-            MCA_MVDR_NOISE_PLAIN_TABLE(SOLVE_NOISE)
-#undef SOLVE_NOISE
-            return;
-        }
-        if (update) {
-            // covariance update weights: the instantiation of kernels_mvdr_gate.hip (per frame) or kernels_mvdr_mask.hip (per frame and
-            // bin) that stands for the kernel chosen below
-            const MvdrGateArgs ga{sa, update, null_gain};
-            const bool full = c->M == 4 * Q;
-#define SOLVE_GATE_NULLS(QQ, SS, S1, PF, R)                                                                                 \
-    if (nulls && Q == QQ && n_sources == SS) {                                                                             \
-        if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1, PF && MCA_MVDR_MASK_PF(QQ, SS), true, false, false>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga); \
-        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1, PF, true, R, false>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, ga);        \
-    }
-            MCA_MVDR_GATE_NULLS_TABLE(SOLVE_GATE_NULLS)
-#undef SOLVE_GATE_NULLS
-#define SOLVE_GATE(QQ, SS, S1F, S1P, RF, RP)                                                                                \
-    if (!nulls && Q == QQ && n_sources == SS) {                                                                            \
-        if (masked && full) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, true, SS, S1F, MCA_MVDR_MASK_PF(QQ, SS), false, false, false>), sgrid, dim3(256), 0, st, ga);   \
-        else if (masked) hipLaunchKernelGGL((k_mvdr_masked_t<QQ, false, SS, S1P, MCA_MVDR_MASK_PF(QQ, SS), false, false, false>), sgrid, dim3(256), 0, st, ga);   \
-        else if (full) hipLaunchKernelGGL((k_mvdr_gated_t<QQ, true, SS, S1F, true, false, RF, false>), sgrid, dim3(256), 0, st, ga);      \
-        else hipLaunchKernelGGL((k_mvdr_gated_t<QQ, false, SS, S1P, true, false, RP, false>), sgrid, dim3(256), 0, st, ga);               \
-    }
-            MCA_MVDR_GATE_PLAIN_TABLE(SOLVE_GATE)
-#undef SOLVE_GATE
-            return;
-        }
-#define SOLVE(QQ)                                                                                          \
-    do {                                                                                                   \
-        if (c->M == 4 * (QQ)) hipLaunchKernelGGL((k_mvdr_solve<QQ, true>), sgrid, dim3(256), 0, st, sa);   \
-        else hipLaunchKernelGGL((k_mvdr_solve<QQ, false>), sgrid, dim3(256), 0, st, sa);                   \
-    } while (0)
-        if (nulls) {
-            // several look directions with soft nulls at each other's: a kernel of its own, dynamic LDS by its instantiation (44 KiB at the most)
-            const MvdrNullsArgs na{sa, null_gain};
-#define SOLVE_NULLS(QQ, SS, S1, PF)                                                                                         \
-    if (Q == QQ && n_sources == SS)                                                                                        \
-        hipLaunchKernelGGL((k_mvdr_nulls<QQ, SS, S1, PF>), sgrid, dim3(256), mvdr_nulls_lds_bytes(QQ, SS, S1), st, na);
-            MCA_MVDR_NULLS_TABLE(SOLVE_NULLS)
-#undef SOLVE_NULLS
-        }
-        else if (n_sources > 1) {
-            // several look directions: the instantiation of (row slots, directions), with its directions per pass (mca_internal.h)
-            const bool full = c->M == 4 * Q;
-#define SOLVE_SOURCES(QQ, SS, S1F, S1P)                                                                                    \
-    if (Q == QQ && n_sources == SS) {                                                                                     \
-        if (full) hipLaunchKernelGGL((k_mvdr_solve_sources<QQ, true, SS, S1F>), sgrid, dim3(256), 0, st, sa);             \
-        else hipLaunchKernelGGL((k_mvdr_solve_sources<QQ, false, SS, S1P>), sgrid, dim3(256), 0, st, sa);                 \
-    }
-            MCA_MVDR_SOURCES_TABLE(SOLVE_SOURCES)
-#undef SOLVE_SOURCES
-        }
-        else if (Q == 1) SOLVE(1);
-        else if (Q == 2) SOLVE(2);
-        else if (Q == 3) SOLVE(3);
-        else SOLVE(4);
-#undef SOLVE
+        void *kargs[1] = {&sa};
+        (void)hipLaunchKernel(kernel, dim3((unsigned)((n_prob + 63) / 64 * pieces)), dim3(256), kargs, (size_t)lds, st);
     };
     // 512 workgroups are resident (two per CU at 253 VGPRs) and all take the same time: the workgroups behind the last whole
     // round (256 streams x 513 bins: 4 of 2052) would hold the GPU for a round of their own.  They go in a second launch,
@@ -494,53 +427,91 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     t_begin(c, 1, st);
     if (pieces > 1 && n_wg > 512) {
         const long long main_prob = (n_wg - rem_wg) * 64, tail_prob = n_prob - main_prob;       // tail_prob <= 128 x 64: the scratch copy's size
-        launch_solve(0, main_prob, 1);
-        launch_solve(main_prob, tail_prob, pieces);
+        launch(0, main_prob, 1);
+        launch(main_prob, tail_prob, pieces);
         VHIP_TRY(c, hipMemcpyAsync(c->d_phi + main_prob * c->tri, c->d_phi_tail, (size_t)tail_prob * c->tri * sizeof(float2), hipMemcpyDeviceToDevice, st));
         VHIP_TRY(c, hipMemcpyAsync(c->d_trace + main_prob, c->d_trace_tail, (size_t)tail_prob * 4, hipMemcpyDeviceToDevice, st));
     } else {
-        launch_solve(0, n_prob, 1);
+        launch(0, n_prob, 1);
     }
     t_end(c, st);
+    return MCA_HIP_OK;
+}
 
-    if (pf) {
-        // Z = G Y in place, between the solve and the synthesis.  A slot the call leaves out restarts from silence, whether the
-        // call has out_pcm or not; the kernel touches only the slots below n_sources
-        if (n_sources < c->max_sources)
-            VHIP_TRY(c, hipMemset2DAsync(c->d_pf_A + (size_t)n_sources * c->K, (size_t)c->max_sources * c->K * 4, 0,
-                                         (size_t)(c->max_sources - n_sources) * c->K * 4, (size_t)n_streams, st));
-        MvdrPostfilterArgs fa{};
-        fa.Y = Y; fa.pn = c->d_pf_pn; fa.A = c->d_pf_A;
-        fa.n_streams = n_streams; fa.S = n_sources; fa.slots = c->max_sources; fa.n_frames = n_frames; fa.K = c->K;
-        fa.smoothing = (float)c->pf_smoothing; fa.one_minus_smoothing = (float)(1.0 - c->pf_smoothing);
-        fa.gain_floor = (float)c->pf_gain_floor; fa.noise_scale = (float)c->pf_noise_scale;
-        const long long cells = (long long)n_streams * n_sources * c->K;
-        t_begin(c, 4, st);
-        hipLaunchKernelGGL(k_mvdr_postfilter, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fa);
-        t_end(c, st);
-    }
+// the post-filter (timing slot 4): Z = G Y in place, between the solve and the synthesis
+int launch_postfilter(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, float2 *Y, hipStream_t st)
+{
+    // A slot the call leaves out restarts from silence, whether the call has out_pcm or not; the kernel touches only the slots
+    // below n_sources
+    if (n_sources < c->max_sources)
+        VHIP_TRY(c, hipMemset2DAsync(c->d_pf_A + (size_t)n_sources * c->K, (size_t)c->max_sources * c->K * 4, 0,
+                                     (size_t)(c->max_sources - n_sources) * c->K * 4, (size_t)n_streams, st));
+    MvdrPostfilterArgs fa{};
+    fa.Y = Y; fa.pn = c->d_pf_pn; fa.A = c->d_pf_A;
+    fa.n_streams = n_streams; fa.S = n_sources; fa.slots = c->max_sources; fa.n_frames = n_frames; fa.K = c->K;
+    fa.smoothing = (float)c->pf_smoothing; fa.one_minus_smoothing = (float)(1.0 - c->pf_smoothing);
+    fa.gain_floor = (float)c->pf_gain_floor; fa.noise_scale = (float)c->pf_noise_scale;
+    const long long cells = (long long)n_streams * n_sources * c->K;
+    t_begin(c, 4, st);
+    hipLaunchKernelGGL(k_mvdr_postfilter, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fa);
+    t_end(c, st);
+    return MCA_HIP_OK;
+}
 
-    if (out_pcm) {
-        MvdrSynthArgs ya{};
-        ya.Y = Y; ya.n_frames = n_frames; ya.N = c->N; ya.logH = c->logH; ya.tw = c->d_tw;
-        ya.S = n_sources; ya.tail_slots = c->max_sources;
-        const int n_out = n_streams * n_sources;                                          // one inverse transform + overlap-add each
-        ya.ft = 16;
-        while (ya.ft > 2 && (long long)n_out * ((n_frames + ya.ft - 1) / ya.ft) < 1024) ya.ft >>= 1;
-        ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = out_pcm;
-        const size_t smem3 = (size_t)(c->H + 1) * sizeof(float2) + (size_t)c->H * 4;
-        if (smem3 > 64 * 1024)
-            VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_synth), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3));
-        // a slot the call leaves out restarts from silence.  The kernel writes only the slots below n_sources, so the clear goes
-        // first: if it fails, nothing has touched the tails yet and tail_cur still names the valid ones
-        if (n_sources < c->max_sources)
-            VHIP_TRY(c, hipMemset2DAsync(ya.tail_out + (size_t)n_sources * c->H, (size_t)c->max_sources * c->H * 4, 0,
-                                         (size_t)(c->max_sources - n_sources) * c->H * 4, (size_t)n_streams, st));
-        t_begin(c, 2, st);
-        hipLaunchKernelGGL(k_mvdr_synth, dim3((n_frames + ya.ft - 1) / ya.ft, n_out), dim3(c->H >= 1024 ? 512 : 256), smem3, st, ya);
-        t_end(c, st);
-        c->tail_cur ^= 1;
-    }
+// the synthesis (timing slot 2): Y -> out_pcm [streams][n_sources][F hop], and the overlap-add tails
+int launch_synth(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float2 *Y, float *out_pcm, hipStream_t st)
+{
+    MvdrSynthArgs ya{};
+    ya.Y = Y; ya.n_frames = n_frames; ya.N = c->N; ya.logH = c->logH; ya.tw = c->d_tw;
+    ya.S = n_sources; ya.tail_slots = c->max_sources;
+    const int n_out = n_streams * n_sources;                                          // one inverse transform + overlap-add each
+    ya.ft = 16;
+    while (ya.ft > 2 && (long long)n_out * ((n_frames + ya.ft - 1) / ya.ft) < 1024) ya.ft >>= 1;
+    ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = out_pcm;
+    const size_t smem3 = (size_t)(c->H + 1) * sizeof(float2) + (size_t)c->H * 4;
+    if (smem3 > 64 * 1024)
+        VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_synth), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3));
+    // a slot the call leaves out restarts from silence.  The kernel writes only the slots below n_sources, so the clear goes
+    // first: if it fails, nothing has touched the tails yet and tail_cur still names the valid ones
+    if (n_sources < c->max_sources)
+        VHIP_TRY(c, hipMemset2DAsync(ya.tail_out + (size_t)n_sources * c->H, (size_t)c->max_sources * c->H * 4, 0,
+                                     (size_t)(c->max_sources - n_sources) * c->H * 4, (size_t)n_streams, st));
+    t_begin(c, 2, st);
+    hipLaunchKernelGGL(k_mvdr_synth, dim3((n_frames + ya.ft - 1) / ya.ft, n_out), dim3(c->H >= 1024 ? 512 : 256), smem3, st, ya);
+    t_end(c, st);
+    c->tail_cur ^= 1;
+    return MCA_HIP_OK;
+}
+
+// a call with n_sources look directions per frame: doa_rad [streams][F][n_sources], out_pcm [streams][n_sources][F hop],
+// out_spec [streams][n_sources][F][K]; update: covariance update weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
+int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                    int n_frames, int n_sources, const float *doa_rad, const float *update, bool masked, float *out_pcm,
+                    float *out_spec, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (n_sources < 1 || n_sources > c->max_sources)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
+    if (!pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
+    if (!out_pcm && !out_spec) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+    const long long need = (long long)(n_frames + 1) * c->H;
+    if (mic_stride < need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_stride shorter than (n_frames+1)*hop samples");
+    if (n_streams > 1 && stream_stride < (long long)(c->M - 1) * mic_stride + need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_stride too short");
+    if ((mic_stride & 1) || (stream_stride & 1) || (reinterpret_cast<uintptr_t>(pcm) & 7))
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
+    if (out_spec && (reinterpret_cast<uintptr_t>(out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !update);
+    if (rc) return rc;
+    // the beamformed spectra go straight to the caller's buffer when one is given
+    float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : c->d_Y;
+    if ((rc = launch_analyse(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, st))) return rc;
+    if ((rc = launch_solve(c, n_streams, n_frames, n_sources, update, masked, Y, st))) return rc;
+    if (c->pf_on && (rc = launch_postfilter(c, n_streams, n_frames, n_sources, Y, st))) return rc;
+    if (out_pcm && (rc = launch_synth(c, n_streams, n_frames, n_sources, Y, out_pcm, st))) return rc;
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }

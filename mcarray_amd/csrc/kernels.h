@@ -73,13 +73,13 @@ __global__ void k_mb_summary(MbSummaryArgs p);
 __global__ void k_mvdr_analyse(MvdrAnalyseArgs p);
 __global__ void k_mvdr_analyse_1024(MvdrAnalyseArgs p, int fpb);
 __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
-template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);
-template <int Q, bool FULL, int S, int S1> __global__ void k_mvdr_solve_sources(MvdrSolveArgs p);
-template <int Q, int S, int S1, bool PF> __global__ void k_mvdr_nulls(MvdrNullsArgs pa);   // soft nulls at the other look directions
-// per-frame covariance update weights (mvdr_gate.h); NOISE: ... and the noise plane of the post-filter, with MvdrGateNoiseArgs
-template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, bool NOISE> __global__ void k_mvdr_gated_t(MvdrGateArgsOf<NOISE> pa);
-// ... with a weight per frame and bin, MvdrGateArgs::update = update_mask[streams][n_frames][K] (kernels_mvdr_mask.hip, kernels_mvdr_mask_noise.hip)
-template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, bool NOISE> __global__ void k_mvdr_masked_t(MvdrGateArgsOf<NOISE> pa);
+template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);                 // one look direction, no weights (kernels_mvdr.hip)
+// every other solve (mvdr_solve.h; mca_internal.h on the parameters and on mvdr_solve_form, which fixes S1, PF and REUSE per row)
+template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, MvdrWeight WEIGHT, bool NOISE> __global__ void k_mvdr_solve_t(MvdrSolveArgs p);
+// the instantiations of one (WEIGHT, NOISE), each group in a translation unit of its own (kernels_mvdr_solve_*.hip)
+template <MvdrWeight WEIGHT, bool NOISE> const void *mvdr_solve_kernel_of(int Q, bool full, int S, bool nulls, int *lds_bytes);
+// the solve kernel of a call with Q row slots, M == 4 Q (full), S look directions, ...; its dynamic LDS; nullptr: not in the build
+const void *mvdr_solve_kernel(int Q, bool full, int S, bool nulls, MvdrWeight w, bool noise, int *lds_bytes);
 __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                                   // decision-directed Wiener gain on the solve's output
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance

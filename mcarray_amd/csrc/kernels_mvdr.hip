@@ -10,7 +10,9 @@
 // forward substitutions, no back substitution, and only cond(L) = sqrt(cond(PhiL)) enters the fp32 error.
 //
 //   k_mvdr_analyse(_1024)   PCM -> windowed N-pt real FFT of the M channels -> X [stream][frame][bin][mic]
-//   k_mvdr_solve     the recursion + factorisation above; four lanes per (stream, bin) problem, rows dealt cyclically
+//   k_mvdr_solve     the recursion + factorisation above; four lanes per (stream, bin) problem, rows dealt cyclically.  The
+//                    hand-written kernel of one look direction without weights; every other call takes an instantiation of
+//                    k_mvdr_solve_t (mvdr_solve.h), chosen like this one by mvdr_solve_kernel (api_mvdr.hip)
 //   k_mvdr_synth     Y -> inverse FFT -> overlap-add
 //
 // The covariance (M(M+1)/2 complex per bin: 1.1 KB at M = 16, 0.56 MB per stream) never leaves the registers of
@@ -269,185 +271,6 @@ template __global__ void k_mvdr_solve<1, true>(MvdrSolveArgs);
 template __global__ void k_mvdr_solve<2, true>(MvdrSolveArgs);
 template __global__ void k_mvdr_solve<3, true>(MvdrSolveArgs);
 template __global__ void k_mvdr_solve<4, true>(MvdrSolveArgs);
-
-// --------------------------------------------------------------------------------------
-// k_mvdr_solve_sources<Q, FULL, S, S1>: the same solve for S look directions per frame (MvdrSolveArgs::S == S, 2 ... 4).  The
-// covariance recursion, the pivots, L and v = L^-1 x do not depend on the look direction; a direction adds its own u = L^-1 d
-// (rd, num, den: about 11 registers with four row slots).  S1 directions ride one pass of the column loop.  S1 == S wherever the
-// registers of two workgroups per CU allow it; four directions on four row slots do not fit and take two passes of two, the
-// second one repeating the factorisation.  The frame's loads and the covariance recursion happen once in any case.
-// Every direction runs exactly the operations of k_mvdr_solve in its order (the complex helpers are inline asm), so output s has
-// the bits of a single-look launch with that direction.
-// --------------------------------------------------------------------------------------
-template <int Q, bool FULL, int S, int S1>
-__global__ __launch_bounds__(256, 2) void k_mvdr_solve_sources(MvdrSolveArgs p)
-{
-    static_assert(S >= 2 && S <= MCA_MAX_SOURCES && S1 >= 1 && S % S1 == 0, "look directions per frame, in whole passes");
-    constexpr int NE = 2 * Q * (Q + 1);          // row slot q holds 4 (q + 1) entries, starting at 2 q (q + 1)
-    const int tid = threadIdx.x, l = tid & 3;
-    const int M = p.M, K = p.K, F = p.n_frames;
-    const int piece = (int)(blockIdx.x % (unsigned)p.pieces);
-    const int t_first = (int)((long long)piece * F / p.pieces), t_last = (int)((long long)(piece + 1) * F / p.pieces);   // frames this workgroup solves
-    const long long total = p.pid0 + p.n_prob;
-    const long long pid = p.pid0 + (long long)(blockIdx.x / (unsigned)p.pieces) * 64 + (tid >> 2);
-    const bool pv = pid < total;
-    const long long pc = pv ? pid : total - 1;   // surplus quads shadow the last problem and store nothing
-    const int a = (int)(pc / K), k = (int)(pc - (long long)a * K);
-
-    const int tri = M * (M + 1) / 2;
-    float2 *st = p.phi + pc * tri;
-    float2 P[NE], L[NE];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int i = 4 * q + l;
-#pragma unroll
-        for (int m = 0; m < 4 * (q + 1); ++m)
-            P[2 * q * (q + 1) + m] = (i < M && m <= i) ? st[i * (i + 1) / 2 + m] : make_float2(0.f, 0.f);
-    }
-    float tr = p.trace[pc];
-    const int nhi = ((K - 1) >> 5) + 1, nph = nhi + 32;
-    const float2 *T = p.T + (long long)a * F * S * M * nph + (k >> 5);     // + ((t S + s) M + m) nph: hi factor; + lo_off: lo
-    const int lo_off = nhi - (k >> 5) + (k & 31);
-    const long long fstride = (long long)K * M;
-    const float2 *X = p.X + (long long)a * F * fstride + (long long)k * M + l;
-    const float al = p.alpha, oma = p.one_minus_alpha;
-    float2 *yo = p.Y + (long long)a * S * F * K + k;                        // + (s F + t) K
-
-    float2 xn[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) xn[q] = (FULL || 4 * q + l < M) ? X[4 * q] : make_float2(0.f, 0.f);
-    for (int t = 0; t < t_last; ++t) {
-        float2 x[Q], rd[S1][Q], rx[Q];
-        float dsum[Q];
-        // the loads of the frame first, as in k_mvdr_solve; the steering vectors become the right-hand sides at once and are
-        // not kept beside them (the silence branch reads the tables again)
-        const long long tn = (long long)min(t + 1, t_last - 1) * fstride;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) x[q] = xn[q];
-        if (t >= t_first) {
-#pragma unroll
-            for (int s = 0; s < S1; ++s) mvdr_steer_rows<Q, FULL>(rd[s], T, (long long)t * S + s, M, nph, lo_off, l);
-        }
-#pragma unroll
-        for (int q = 0; q < Q; ++q) xn[q] = (FULL || 4 * q + l < M) ? X[tn + 4 * q] : make_float2(0.f, 0.f);
-        // Phi <- alpha Phi + (1 - alpha) x x^H (the rows of this lane), tr <- alpha tr + (1 - alpha) |x|^2
-        float e = 0.f;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const float2 xs = make_float2(oma * x[q].x, oma * x[q].y);
-#pragma unroll
-            for (int m = 0; m < 4 * (q + 1); ++m)
-                if (FULL || m < M) {
-                    const float2 xm = quad_bcast(x[m >> 2], m & 3);
-                    float2 &e_ = P[2 * q * (q + 1) + m];
-                    e_ = cmacc(make_float2(al * e_.x, al * e_.y), xs, xm);
-                    if (q == Q - 1) e = fmaf(xm.x, xm.x, fmaf(xm.y, xm.y, e));
-                }
-        }
-        tr = fmaf(al, tr, oma * e);
-        if (t < t_first) continue;               // (an earlier piece solves this frame)
-        // The loading as k_mvdr_solve applies it, which the compiler decides there and this kernel has to repeat to keep its bits:
-        // with all columns in one basic block (FULL) the product is contracted into the pivot, fma(loading, tr, Phi_jj); behind
-        // the "j < M" branches it is rounded on its own first.  Spelled out here, because the loop over the passes moves the
-        // product out of the columns' block and would leave that choice to chance.
-        float delta = p.loading_over_m * tr;
-        asm volatile("" : "+v"(delta));
-
-        // one pass per S1 look directions, s0 ... s0 + S1 - 1
-#pragma unroll 1
-        for (int s0 = 0;;) {
-            float2 num[S1];
-            float den[S1];
-#pragma unroll
-            for (int s = 0; s < S1; ++s) { num[s] = make_float2(0.f, 0.f); den[s] = 0.f; }
-#pragma unroll
-            for (int q = 0; q < Q; ++q) { rx[q] = x[q]; dsum[q] = 0.f; }
-            mvdr_static_for<0, 4 * Q>([&](auto jc) __attribute__((always_inline)) {
-                constexpr int j = decltype(jc)::value;
-                if (FULL || j < M) {
-                    constexpr int jq = j >> 2, jl = j & 3, jo = 2 * jq * (jq + 1);
-                    // pivot and the substitution values of row j, from its owner
-                    const float pjj = FULL ? fmaf(p.loading_over_m, tr, P[jo + j].x) : P[jo + j].x + delta;
-                    const float inv = __builtin_amdgcn_rsqf(quad_bcast1<jl>(pjj - dsum[jq]));
-                    float2 uj[S1], vj = quad_bcast(rx[jq], jl);
-                    vj = make_float2(vj.x * inv, vj.y * inv);
-#pragma unroll
-                    for (int s = 0; s < S1; ++s) {
-                        uj[s] = quad_bcast(rd[s][jq], jl);
-                        uj[s] = make_float2(uj[s].x * inv, uj[s].y * inv);
-                        num[s] = cmacc(num[s], vj, uj[s]);                  // conj(u_j) v_j
-                        den[s] = fmaf(uj[s].x, uj[s].x, fmaf(uj[s].y, uj[s].y, den[s]));
-                    }
-                    // L_ij = (Phi_ij - sum_{m<j} L_im conj(L_jm)) / L_jj for the rows below j (rows <= j compute dead values)
-                    float2 s_[Q];
-#pragma unroll
-                    for (int q = jq; q < Q; ++q) s_[q] = P[2 * q * (q + 1) + j];
-#pragma unroll
-                    for (int m = 0; m < j; ++m) {
-                        const float2 r = quad_bcast(L[jo + m], jl);
-#pragma unroll
-                        for (int q = jq; q < Q; ++q) s_[q] = cnmacc(s_[q], L[2 * q * (q + 1) + m], r);
-                    }
-#pragma unroll
-                    for (int q = jq; q < Q; ++q) {
-                        const float2 lq = make_float2(s_[q].x * inv, s_[q].y * inv);
-                        L[2 * q * (q + 1) + j] = lq;
-                        dsum[q] = fmaf(lq.x, lq.x, fmaf(lq.y, lq.y, dsum[q]));
-#pragma unroll
-                        for (int s = 0; s < S1; ++s) rd[s][q] = cnmac(rd[s][q], lq, uj[s]);
-                        rx[q] = cnmac(rx[q], lq, vj);
-                    }
-                }
-            });
-            float2 y[S1];
-#pragma unroll
-            for (int s = 0; s < S1; ++s) {
-                const float rden = __builtin_amdgcn_rcpf(den[s]);
-                y[s] = make_float2(num[s].x * rden, num[s].y * rden);
-            }
-            if (!(tr > 1e-30f)) {
-                // digital silence so far: w = d/M, the reference's delay-and-sum (Beamformer.cpp:51-71), per direction
-#pragma unroll
-                for (int s = 0; s < S1; ++s) {
-                    float2 d[Q];
-                    mvdr_steer_rows<Q, FULL>(d, T, (long long)t * S + s0 + s, M, nph, lo_off, l);
-                    float2 acc = make_float2(0.f, 0.f);
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) acc = cmacc(acc, x[q], d[q]);   // conj(d_i) x_i
-                    acc.x += __shfl_xor(acc.x, 1, 4); acc.y += __shfl_xor(acc.y, 1, 4);
-                    acc.x += __shfl_xor(acc.x, 2, 4); acc.y += __shfl_xor(acc.y, 2, 4);
-                    y[s] = make_float2(acc.x / (float)M, acc.y / (float)M);
-                }
-            }
-            // every lane of the quad holds the S1 results: lane s stores direction s0 + s
-            float2 ys = y[0];
-#pragma unroll
-            for (int s = 1; s < S1; ++s) if (l == s) ys = y[s];
-            if (l < S1 && pv) yo[((long long)(s0 + l) * F + t) * K] = ys;
-            s0 += S1;
-            if (S1 == S || s0 >= S) break;
-#pragma unroll
-            for (int s = 0; s < S1; ++s) mvdr_steer_rows<Q, FULL>(rd[s], T, (long long)t * S + s0 + s, M, nph, lo_off, l);
-        }
-    }
-    if (pv && t_last == F) {
-        float2 *so = p.phi_out + (pc - p.out_base) * tri;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int i = 4 * q + l;
-#pragma unroll
-            for (int m = 0; m < 4 * (q + 1); ++m)
-                if (i < M && m <= i) so[i * (i + 1) / 2 + m] = P[2 * q * (q + 1) + m];
-        }
-        if (l == 0) p.trace_out[pc - p.out_base] = tr;
-    }
-}
-
-#define MCA_MVDR_SOURCES_INST(Q, S, S1F, S1P)                                        \
-    template __global__ void k_mvdr_solve_sources<Q, true, S, S1F>(MvdrSolveArgs);   \
-    template __global__ void k_mvdr_solve_sources<Q, false, S, S1P>(MvdrSolveArgs);
-MCA_MVDR_SOURCES_TABLE(MCA_MVDR_SOURCES_INST)
-#undef MCA_MVDR_SOURCES_INST
 
 // --------------------------------------------------------------------------------------
 // k_mvdr_synth: grid (runs of ft frames, streams * sources), 256 threads, LDS = (H + 1) float2 + H floats.

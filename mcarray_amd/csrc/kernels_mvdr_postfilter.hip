@@ -1,5 +1,5 @@
 // kernels_mvdr_postfilter.hip -- the decision-directed Wiener post-filter on the beamformed spectra (gfx950; include/mcarray_hip.h,
-// mca_hip_mvdr_set_postfilter).  It runs between the solve (k_mvdr_gated_noise, which leaves Y and the residual noise
+// mca_hip_mvdr_set_postfilter).  It runs between the solve (k_mvdr_solve_t<..., NOISE = true>, which leaves Y and the residual noise
 // power 1 / (d^H PhiL^-1 d) of every output) and k_mvdr_synth, and rewrites Y in place.
 //
 // Per stream a, slot s, bin k and frame t, with p = noise_scale * pn (pn == 0: the bin is digitally silent so far):

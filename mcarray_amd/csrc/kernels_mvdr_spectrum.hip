@@ -1,6 +1,6 @@
 // kernels_mvdr_spectrum.hip -- the Capon (minimum-variance) spatial spectrum of the covariance an MVDR context holds (gfx950;
-// include/mcarray_hip.h, mca_hip_mvdr_spectrum_*).  A translation unit of its own, as kernels_mvdr_nulls.hip is and
-// for the same reason: the solve kernels keep the instruction streams they have.  Read-only on the stream state.
+// include/mcarray_hip.h, mca_hip_mvdr_spectrum_*).  A translation unit of its own:
+// the solve kernels keep the instruction streams they have.  Read-only on the stream state.
 //
 //     PhiL[k] = Phi[k] + loading tr[k]/M I,   q[k][i] = d(theta_i,k)^H PhiL[k]^-1 d(theta_i,k),   P[i] = sum_k w[k] / q[k][i]
 //

@@ -483,90 +483,63 @@ struct MvdrSolveArgs {
     // every piece reads the entry state when it starts and nothing orders that before the last piece's stores
     float2 *phi_out; float *trace_out; long long out_base;
     float2 *Y;                // [streams][S][n_frames][K] beamformed spectra
-    int S;                    // look directions per frame: k_mvdr_solve is the S == 1 kernel, k_mvdr_solve_sources<.., S, ..> the others
+    int S;                    // look directions per frame
+    // what only some instantiations of k_mvdr_solve_t read (a kernel loads the fields it uses, no others)
+    const float *update;      // WEIGHT = FRAME: [streams][n_frames]; CELL: [streams][n_frames][K]; NONE: not read
+    float null_gain;          // NULLS: > 0, gain of the soft nulls at the other look directions
+    float *pn;                // NOISE: [streams][S][n_frames][K] fp32, 1 / (d_s^H PhiL^-1 d_s) of every output, 0 = silent
 };
 
-// k_mvdr_solve_sources<Q, FULL, S, S1>: S look directions per frame, S1 of them per pass of the factorisation's column loop.
-// X(Q, S, S1 of FULL, S1 of !FULL): S1 = S wherever that leaves the kernel without scratch under its launch bounds
-#define MCA_MVDR_SOURCES_TABLE(X) \
-    X(1, 2, 2, 2) X(1, 3, 3, 3) X(1, 4, 4, 4) \
-    X(2, 2, 2, 2) X(2, 3, 3, 3) X(2, 4, 4, 4) \
-    X(3, 2, 2, 2) X(3, 3, 3, 3) X(3, 4, 4, 4) \
-    X(4, 2, 2, 2) X(4, 3, 3, 3) X(4, 4, 2, 2)
-
-// k_mvdr_nulls<Q, S, S1, PF>: the same with soft nulls at the other look directions.  X(Q, S, S1, PF): the
-// directions per pass and whether the next frame's spectra are loaded a frame ahead, again by what leaves the kernel without
-// scratch; one instantiation serves M = 4Q and M < 4Q (the branch-free M = 4Q form costs this kernel registers, it saves none)
-#define MCA_MVDR_NULLS_TABLE(X) \
-    X(1, 2, 2, true) X(1, 3, 3, true) X(1, 4, 4, true) \
-    X(2, 2, 2, true) X(2, 3, 3, true) X(2, 4, 4, true) \
-    X(3, 2, 2, true) X(3, 3, 3, true) X(3, 4, 4, true) \
-    X(4, 2, 2, true) X(4, 3, 3, true) X(4, 4, 2, false)
-// dynamic LDS of a k_mvdr_nulls workgroup: the parked u [Q][S][256] float2 and, with several passes, num / den [S][256]
+// ---- the instantiations of the MVDR solve (mvdr_solve.h) ----
+// k_mvdr_solve_t<Q, FULL, S, S1, PF, NULLS, REUSE, WEIGHT, NOISE>: Q row slots per lane, FULL: M == 4 Q, S look directions per frame,
+// NULLS: soft nulls at the other directions (4.3), WEIGHT: the covariance update weight of a frame (4.5, 4.7), NOISE: the noise plane
+// of the post-filter beside Y (4.6).  A call fixes these six; mvdr_solve_form() adds the three that only say how the kernel is built.
+enum class MvdrWeight { NONE, FRAME, CELL };   // no weight (all 1) / update[streams][n_frames] / update_mask[streams][n_frames][K]
+struct MvdrSolveForm {
+    int S1;        // look directions per pass of the factorisation's column loop (S1 < S: several passes, each repeats the factorisation)
+    bool PF;       // the next frame's spectra are loaded a frame ahead
+    bool REUSE;    // a frame with weight 0 behind a solved one runs the substitutions against the held factor only
+};
+// Every choice is by what leaves the kernel without scratch under __launch_bounds__(256, 2) (tools/check_spills.py holds the build to it).
+constexpr MvdrSolveForm mvdr_solve_form(int Q, bool FULL, int S, bool NULLS, MvdrWeight WEIGHT, bool NOISE)
+{
+    const bool big = Q == 4 && S >= 3;             // 13 ... 16 microphones with three or four directions: the rows a register or two short
+    MvdrSolveForm f{S, true, false};
+    // four directions on four row slots do not fit in one pass: two passes of two, the second repeating the factorisation
+    if (Q == 4 && S == 4) f.S1 = 2;
+    // the load a frame ahead costs 2 Q registers.  Given up by the two-pass nulls kernel; by the two NOISE rows that spill 12 bytes
+    // per lane with the store of the noise plane (M = 13 ... 15, three and four directions, per-frame weights: 250 VGPRs without it;
+    // one direction per pass is clean too, but repeats the factorisation per direction); and by every CELL row of that size, where
+    // the cell's 64-bit address would otherwise cost scratch
+    if (NULLS && Q == 4 && S == 4) f.PF = false;
+    if (WEIGHT == MvdrWeight::FRAME && NOISE && !NULLS && !FULL && big) f.PF = false;
+    if (WEIGHT == MvdrWeight::CELL && big) f.PF = false;
+    // REUSE keeps the inverse pivots (Q registers) and a second column body.  Per-frame weights only: without weights no frame is
+    // frozen, and with a weight per quad the rows of three and four row slots spill up to 158 registers and a mixed wave would run
+    // both column bodies.  Off where it spills: four row slots with several directions, and the nulls of three row slots with four
+    if (WEIGHT == MvdrWeight::FRAME) f.REUSE = NULLS ? !(Q == 4 || (Q == 3 && S == 4)) : !(Q == 4 && S >= 2);
+    return f;
+}
+// The single-look call without weights keeps the hand-written k_mvdr_solve<Q, FULL> (kernels_mvdr.hip; DESIGN.md 4.2 on the
+// measurement that decided it); every other call takes an instantiation of the template.
+constexpr bool mvdr_solve_hand_written(int S, MvdrWeight WEIGHT, bool NOISE) { return S == 1 && WEIGHT == MvdrWeight::NONE && !NOISE; }
+// the (Q, FULL, S, NULLS) a build instantiates per (WEIGHT, NOISE): one instantiation serves M = 4Q and M < 4Q under the nulls (the
+// branch-free M = 4Q form costs that kernel registers, it saves none); the noise plane comes with weights (a call without them
+// passes ones)
+constexpr bool mvdr_solve_row(int Q, bool FULL, int S, bool NULLS, MvdrWeight WEIGHT, bool NOISE)
+{
+    return Q >= 1 && Q <= 4 && S >= 1 && S <= MCA_MAX_SOURCES && (!NULLS || (S >= 2 && !FULL)) && !(NOISE && WEIGHT == MvdrWeight::NONE) &&
+           !mvdr_solve_hand_written(S, WEIGHT, NOISE);
+}
+// dynamic LDS of a NULLS workgroup: the parked u [Q][S][256] float2 and, with several passes, num / den [S][256]
 inline int mvdr_nulls_lds_bytes(int Q, int S, int S1) { return 256 * (8 * Q * S + (S1 < S ? 12 * S : 0)); }
-// the arguments of k_mvdr_nulls: a struct of its own, so that MvdrSolveArgs and with it the code of the kernels that take it
-// stay as they are
-struct MvdrNullsArgs {
-    MvdrSolveArgs s;
-    float null_gain;          // > 0: gain of the soft nulls at the other look directions
-};
 
-// k_mvdr_gated_t<Q, FULL, S, S1, PF, NULLS, REUSE, NOISE = false> (mvdr_gate.h, kernels_mvdr_gate.hip): the solve kernels above with a per-frame
-// covariance update weight, update[streams][n_frames] (mca_hip_mvdr_sources_frames_weighted_dev).  A struct of its own like
-// MvdrNullsArgs, for the same reason.  null_gain is read by the NULLS instantiations only.
-struct MvdrGateArgs {
-    MvdrSolveArgs s;
-    const float *update;      // [streams][n_frames], never NULL here: a call without weights takes the unweighted kernels
-    float null_gain;
-};
-// NULLS = false, X(Q, S, S1 of FULL, S1 of !FULL, REUSE of FULL, REUSE of !FULL): S = 1 stands for k_mvdr_solve, the others are the rows
-// of MCA_MVDR_SOURCES_TABLE.  REUSE (a frozen frame behind a solved one runs the substitutions only) wherever it leaves the kernel
-// without scratch under its launch bounds; the others factorise on frozen frames too.
-#define MCA_MVDR_GATE_PLAIN_TABLE(X) \
-    X(1, 1, 1, 1, true, true) X(1, 2, 2, 2, true, true) X(1, 3, 3, 3, true, true) X(1, 4, 4, 4, true, true) \
-    X(2, 1, 1, 1, true, true) X(2, 2, 2, 2, true, true) X(2, 3, 3, 3, true, true) X(2, 4, 4, 4, true, true) \
-    X(3, 1, 1, 1, true, true) X(3, 2, 2, 2, true, true) X(3, 3, 3, 3, true, true) X(3, 4, 4, 4, true, true) \
-    X(4, 1, 1, 1, true, true) X(4, 2, 2, 2, false, false) X(4, 3, 3, 3, false, false) X(4, 4, 2, 2, false, false)
-// NULLS = true, X(Q, S, S1, PF, REUSE): the rows of MCA_MVDR_NULLS_TABLE
-#define MCA_MVDR_GATE_NULLS_TABLE(X) \
-    X(1, 2, 2, true, true) X(1, 3, 3, true, true) X(1, 4, 4, true, true) \
-    X(2, 2, 2, true, true) X(2, 3, 3, true, true) X(2, 4, 4, true, true) \
-    X(3, 2, 2, true, true) X(3, 3, 3, true, true) X(3, 4, 4, true, false) \
-    X(4, 2, 2, true, false) X(4, 3, 3, true, false) X(4, 4, 2, false, false)
-
-// k_mvdr_gated_t<..., NOISE = true> (kernels_mvdr_gate_noise.hip): the gated solve that also stores
-// the residual noise power of every output, 1 / (d_s^H PhiL^-1 d_s) or 0 for a silent bin, to pn at the index of Y -- the solve of a
-// context with the post-filter enabled.  A struct of its own, for the reason MvdrNullsArgs has one.
-struct MvdrGateNoiseArgs {
-    MvdrGateArgs g;
-    float *pn;                // [streams][S][n_frames][K] fp32
-};
-template <bool NOISE> struct MvdrGateArgsSel { using type = MvdrGateArgs; };
-template <> struct MvdrGateArgsSel<true> { using type = MvdrGateNoiseArgs; };
-template <bool NOISE> using MvdrGateArgsOf = typename MvdrGateArgsSel<NOISE>::type;   // the argument of k_mvdr_gated_t<..., NOISE>
-// NULLS = false, X(Q, S, S1 of FULL, S1 of !FULL, PF of !FULL, REUSE of FULL, REUSE of !FULL): the rows of MCA_MVDR_GATE_PLAIN_TABLE
-// but for the two that spill 12 bytes per lane with the store (M = 13 ... 15 with three and four directions): those give up the load a
-// frame ahead (250 VGPRs, no scratch; one direction per pass is clean too, but repeats the factorisation per direction).  The
-// NULLS = true kernels take the rows of MCA_MVDR_GATE_NULLS_TABLE as they are.
-#define MCA_MVDR_NOISE_PLAIN_TABLE(X) \
-    X(1, 1, 1, 1, true, true, true) X(1, 2, 2, 2, true, true, true) X(1, 3, 3, 3, true, true, true) X(1, 4, 4, 4, true, true, true) \
-    X(2, 1, 1, 1, true, true, true) X(2, 2, 2, 2, true, true, true) X(2, 3, 3, 3, true, true, true) X(2, 4, 4, 4, true, true, true) \
-    X(3, 1, 1, 1, true, true, true) X(3, 2, 2, 2, true, true, true) X(3, 3, 3, 3, true, true, true) X(3, 4, 4, 4, true, true, true) \
-    X(4, 1, 1, 1, true, true, true) X(4, 2, 2, 2, true, false, false) X(4, 3, 3, 3, false, false, false) X(4, 4, 2, 2, false, false, false)
-
-// k_mvdr_masked_t<...> (mvdr_gate.h, kernels_mvdr_mask.hip, kernels_mvdr_mask_noise.hip): the gated kernels with a
-// weight per frame and bin, MvdrGateArgs::update = update_mask[streams][n_frames][K] (mca_hip_mvdr_sources_frames_masked_dev).  One
-// instantiation per row of the four tables above with the row's Q, S and S1 (so the per-frame-constant mask gives the bytes of the
-// gated kernel of that row), REUSE = false everywhere (with REUSE and a weight per quad the instantiations of three and four row
-// slots spill up to 158 registers, and a mixed wave would run both column bodies), and without the load a frame ahead where the
-// cell's address would otherwise cost scratch (four row slots with three and four directions)
-#define MCA_MVDR_MASK_PF(Q, S) ((Q) < 4 || (S) < 3)
 
 // the decision-directed Wiener post-filter on the beamformed spectra (kernels_mvdr_postfilter.hip): one thread per
 // (stream, slot, bin), bins fastest; Y is rewritten in place, A is read and written once
 struct MvdrPostfilterArgs {
     float2 *Y;                // [streams][S][n_frames][K] output of the solve, replaced by Z = G Y
-    const float *pn;          // [streams][S][n_frames][K] 1 / (d^H PhiL^-1 d), 0 = silent (MvdrGateNoiseArgs)
+    const float *pn;          // [streams][S][n_frames][K] 1 / (d^H PhiL^-1 d), 0 = silent (MvdrSolveArgs::pn)
     float *A;                 // [streams][slots][K] |Z|^2 of the frame before
     int n_streams, S, slots, n_frames, K;
     float smoothing, one_minus_smoothing, gain_floor, noise_scale;

@@ -1,5 +1,5 @@
-// mvdr_nulls.h -- the small per-direction solves of the MVDR kernels with soft nulls (k_mvdr_nulls of kernels_mvdr_nulls.hip and the
-// weighted kernel of kernels_mvdr_gate.hip): the quad sums, the pair index of the Gram matrix and the (S-1) x (S-1) solve of one output.
+// mvdr_nulls.h -- the small per-direction solves of the MVDR solve with soft nulls (k_mvdr_solve_t<..., NULLS = true, ...>): the quad
+// sums, the pair index of the Gram matrix and the (S-1) x (S-1) solve of one output.  Included by mvdr_solve.h, behind its helpers.
 #pragma once
 #include "mvdr_solve.h"
 

@@ -554,7 +554,7 @@ def test_mvdr_strided_equals_contiguous(xs, fs, N):
 
 @pytest.mark.parametrize("gain", [0.0, 100.0])
 def test_mvdr_sources_strided_equals_contiguous(gain):
-    """mca_hip_mvdr_sources_frames_dev, S = 3: k_mvdr_solve_sources (gain 0, against po.MVDR per look direction) and k_mvdr_nulls
+    """mca_hip_mvdr_sources_frames_dev, S = 3: k_mvdr_solve_t (gain 0, against po.MVDR per look direction) and its NULLS form
     (gain 100, against tests/mvdr_nulls_twin.py under the bar of tests/test_gpu_mvdr_nulls.py)"""
     import mvdr_nulls_twin as nt
     import test_gpu_mvdr_nulls as tn

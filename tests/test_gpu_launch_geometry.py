@@ -138,7 +138,7 @@ def _mvdr_case(M, S, gain, A):
 @pytest.mark.parametrize("gain", [0.0, 100.0])
 @pytest.mark.parametrize("M,S", [(2, 2), (5, 3), (8, 4), (16, 4)])
 def test_mvdr_sources_batches_that_move_the_launch_shapes(M, S, gain, A):
-    """k_mvdr_solve_sources (gain 0) and k_mvdr_nulls (gain 100) behind an analysis that writes one steering table per look
+    """k_mvdr_solve_t without (gain 0) and with NULLS (gain 100) behind an analysis that writes one steering table per look
     direction with fpb = 2 / 4 / 8 frames per block, in front of a synthesis of ft = 4 ... 16 frames per block; A = 128: the tail
     launch in 8 and then 4 pieces ((16, 4): the two-pass instantiation inside a pieced launch).  The second call continues the
     covariances and the overlap-add tails the first one left."""

@@ -1,5 +1,5 @@
-"""GPU: per-frame covariance update weights of the MVDR calls (mca_hip_mvdr_sources_frames_weighted_*; k_mvdr_gated in
-kernels_mvdr_gate.hip) against the float64 twin of the dense definition (tests/mvdr_gate_twin.py).
+"""GPU: per-frame covariance update weights of the MVDR calls (mca_hip_mvdr_sources_frames_weighted_*; k_mvdr_solve_t<..., WEIGHT = FRAME, ...>
+of mvdr_solve.h) against the float64 twin of the dense definition (tests/mvdr_gate_twin.py).
 
 The bars are the ones tests/test_gpu_mvdr.py sets for this solve: 5e-4 of the peak for spectra and audio, 5e-6 for the covariance.
 tests/test_mvdr_gate_twin.py shows that the weighted spectra and covariance differ from the unweighted ones by more than 0.1 of

@@ -1,5 +1,5 @@
-"""GPU: time-frequency update masks of the MVDR calls (mca_hip_mvdr_sources_frames_masked_*; k_mvdr_masked_t in
-kernels_mvdr_mask.hip and kernels_mvdr_mask_noise.hip) against the float64 twin of the dense definition (tests/mvdr_mask_twin.py).
+"""GPU: time-frequency update masks of the MVDR calls (mca_hip_mvdr_sources_frames_masked_*; k_mvdr_solve_t<..., WEIGHT = CELL, ...>
+of mvdr_solve.h) against the float64 twin of the dense definition (tests/mvdr_mask_twin.py).
 
 The bars are those of tests/test_gpu_mvdr_gate.py, from tests/test_gpu_mvdr.py: 5e-4 of the peak for spectra and audio, 5e-6 for the
 covariance.  tests/test_mvdr_mask_twin.py shows that on the scene and mask used here the masked spectra and covariance differ from

@@ -1,5 +1,5 @@
-"""GPU: soft nulls at the other look directions of an MVDR sources call (mca_hip_mvdr_set_null_gain; k_mvdr_nulls in
-kernels_mvdr_nulls.hip) against the float64 twin of the dense definition (tests/mvdr_nulls_twin.py).
+"""GPU: soft nulls at the other look directions of an MVDR sources call (mca_hip_mvdr_set_null_gain; k_mvdr_solve_t<..., NULLS = true, ...>
+of mvdr_solve.h) against the float64 twin of the dense definition (tests/mvdr_nulls_twin.py).
 
 The bar is the one tests/test_gpu_mvdr.py sets for this solve: 5e-4 of the peak for spectra and audio, 5e-6 for the covariance.
 tests/test_mvdr_nulls_twin.py shows that the nulled spectra differ from plain MVDR's by more than 0.1 of the peak on the scene

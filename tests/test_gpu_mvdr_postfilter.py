@@ -1,5 +1,5 @@
-"""GPU: the decision-directed Wiener post-filter of the MVDR calls (mca_hip_mvdr_set_postfilter; k_mvdr_gated_t<..., NOISE> in
-kernels_mvdr_gate_noise.hip, k_mvdr_postfilter in kernels_mvdr_postfilter.hip) against the float64 twin of the dense definition
+"""GPU: the decision-directed Wiener post-filter of the MVDR calls (mca_hip_mvdr_set_postfilter; k_mvdr_solve_t<..., NOISE = true> of
+mvdr_solve.h, k_mvdr_postfilter in kernels_mvdr_postfilter.hip) against the float64 twin of the dense definition
 (tests/mvdr_postfilter_twin.py).
 
 The bars: 5e-4 of the peak of the twin's UNFILTERED spectra (audio) of the call for the filtered spectra (audio) -- the absolute bar

@@ -1,5 +1,5 @@
 """GPU: several look directions per frame through one MVDR analysis, covariance recursion and factorisation
-(mca_hip_mvdr_set_max_sources, mca_hip_mvdr_sources_frames_*; k_mvdr_solve_sources in kernels_mvdr.hip).
+(mca_hip_mvdr_set_max_sources, mca_hip_mvdr_sources_frames_*; k_mvdr_solve_t of mvdr_solve.h).
 
 Nothing new is defined numerically: output s of a call is what the single-look call gives on the same stream state with
 doa[:, :, s], and the covariance afterwards is what any of those calls leaves.  So the oracle for output s is

@@ -1,6 +1,6 @@
 """CPU: the interface of the time-frequency update masks of the MVDR context (mca_hip_mvdr_sources_frames_masked_*) is declared,
 bound, present in the built library and exposed through the Python and C++ classes, and its kernels -- every instantiation of
-k_mvdr_masked_t -- use no scratch."""
+k_mvdr_solve_t<..., WEIGHT = CELL, ...> -- use no scratch."""
 import ctypes as C
 import inspect
 import os
@@ -79,12 +79,13 @@ def test_masked_kernels_use_no_scratch():
     spec = importlib.util.spec_from_file_location("check_spills", os.path.join(ROOT, "tools", "check_spills.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    assert any(re.search(p, "k_mvdr_masked_t") for p in mod.DEFAULT_PATTERNS)            # the lint at the link covers them
-    masked = [k for k in mod.kernels(_lib.LIB_PATH) if "k_mvdr_masked_t" in k.get("name", "")]
-    # one per gated kernel: the last template argument is NOISE, the one before it REUSE (never, under a mask)
-    noise = [k for k in masked if re.search(r"ELb1EEEv", k["name"])]
+    assert any(re.search(p, "k_mvdr_solve_t") for p in mod.DEFAULT_PATTERNS)             # the lint at the link covers them
+    every = mod.kernels(_lib.LIB_PATH)
+    masked = mod.solve_t(every, WEIGHT=2)
+    # one per kernel with a weight per frame: with and without the noise plane, REUSE never under a mask
+    noise = mod.solve_t(every, WEIGHT=2, NOISE=1)
     assert len(masked) == 88 and len(noise) == 44, (len(masked), len(noise))
-    assert all(re.search(r"ELb0ELb[01]EEEv", k["name"]) for k in masked)
+    assert masked == mod.solve_t(every, WEIGHT=2, REUSE=0)
     bad = {k["name"]: [k[f] for f in mod.FIELDS] for k in masked if any(int(k[f]) for f in mod.FIELDS)}
     assert not bad, bad
     assert all(int(k["vgpr_count"]) <= 256 for k in masked)    # two workgroups of four waves per CU (__launch_bounds__(256, 2))

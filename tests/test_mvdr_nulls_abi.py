@@ -53,12 +53,12 @@ def test_no_nulls_kernel_spills():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     every = mod.kernels(_lib.LIB_PATH)
-    ks = [k for k in every if "k_mvdr_nulls" in k.get("name", "")]
+    ks = mod.solve_t(every, WEIGHT=0, NULLS=1)          # k_mvdr_solve_t<..., NULLS = true, ...> without weights
     assert len(ks) == 12, len(ks)                       # Q = 1 ... 4 row slots x S = 2 ... 4 look directions
     assert all(int(k["vgpr_count"]) <= 256 for k in ks)
     bad = {k["name"]: [k[f] for f in mod.FIELDS] for k in ks if any(int(k[f]) for f in mod.FIELDS)}
     assert not bad, bad
-    # the lint's default pattern covers them beside the 32 kernels it covered before
-    default = re.compile(r"k_mvdr_(solve|nulls)")
-    assert sum(1 for k in every if default.search(k.get("name", ""))) == 44
-    assert 'r"k_mvdr_(solve|nulls)"' in open(os.path.join(ROOT, "tools", "check_spills.py")).read()
+    # the lint's default pattern covers them beside the 32 kernels without weights that it covered before
+    default = re.compile(mod.DEFAULT_PATTERNS[0])
+    assert all(default.search(k["name"]) for k in ks)
+    assert sum(1 for k in every if default.search(k.get("name", "")) and not mod.solve_t([k], WEIGHT=1) and not mod.solve_t([k], WEIGHT=2)) == 44

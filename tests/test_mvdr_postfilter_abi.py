@@ -64,12 +64,12 @@ def test_postfilter_kernels_use_no_scratch():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     assert any(re.search(p, "k_mvdr_postfilter") for p in mod.DEFAULT_PATTERNS)           # the lint at the link covers it
-    assert any(re.search(p, "k_mvdr_gated_t") for p in mod.DEFAULT_PATTERNS)
+    assert any(re.search(p, "k_mvdr_solve_t") for p in mod.DEFAULT_PATTERNS)
     all_k = mod.kernels(_lib.LIB_PATH)
     pf = [k for k in all_k if "k_mvdr_postfilter" in k.get("name", "")]
-    # the gated solve: the last template argument is NOISE (Lb1 = with the noise plane)
-    gated = [k for k in all_k if "k_mvdr_gated_t" in k.get("name", "")]
-    noise = [k for k in gated if re.search(r"ELb1EEEv", k["name"])]
+    # the solve with a weight per frame: with and without the noise plane
+    gated = mod.solve_t(all_k, WEIGHT=1)
+    noise = mod.solve_t(all_k, WEIGHT=1, NOISE=1)
     assert len(pf) == 1 and len(gated) == 88 and len(noise) == 44, (len(pf), len(gated), len(noise))
     bad = {k["name"]: [k[f] for f in mod.FIELDS] for k in pf + noise if any(int(k[f]) for f in mod.FIELDS)}
     assert not bad, bad

@@ -1,7 +1,7 @@
 """Register lint of the built library: no MVDR solve kernel, nor the post-filter behind it, may spill to scratch.
 
-The k_mvdr_solve / k_mvdr_solve_sources / k_mvdr_nulls / k_mvdr_gated instantiations for 13 ... 16 microphones sit a register or two under
-the 256 that __launch_bounds__(256, 2) allows (DESIGN.md sections 4.2, 4.3, 4.5, 4.6), so another compiler version may start to spill them without a word;
+The k_mvdr_solve / k_mvdr_solve_t instantiations for 13 ... 16 microphones sit a register or two under
+the 256 that __launch_bounds__(256, 2) allows, so another compiler version may start to spill them without a word;
 a spilled column loop costs more than the sharing gains.  This script reads the kernel metadata of every gfx950 code object
 inside mcarray_amd/libmcarray_hip.so and lists the kernels whose name matches the pattern and whose .vgpr_spill_count or
 .private_segment_fixed_size is not 0.  (.sgpr_spill_count is not in the rule: scalar registers spill into lanes of a vector
@@ -17,10 +17,21 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 FIELDS = ("vgpr_spill_count", "private_segment_fixed_size")
-# the unweighted solve kernels; those with update weights per frame (k_mvdr_gated_t, with and without the noise plane) and per
-# frame and bin (k_mvdr_masked_t, the same); the post-filter
-DEFAULT_PATTERNS = (r"k_mvdr_(solve|nulls)", r"k_mvdr_gated", r"k_mvdr_masked", r"k_mvdr_postfilter")
+# the solve kernels (the hand-written k_mvdr_solve<Q, FULL> and every k_mvdr_solve_t<...>); the post-filter
+DEFAULT_PATTERNS = (r"k_mvdr_solve", r"k_mvdr_postfilter")
+# the template arguments a mangled k_mvdr_solve_t name ends with: NULLS, REUSE, WEIGHT (0 none, 1 per frame, 2 per frame and bin), NOISE
+SOLVE_T = re.compile(r"k_mvdr_solve_tI.*ELb(?P<NULLS>[01])ELb(?P<REUSE>[01])ELNS_10MvdrWeightE(?P<WEIGHT>[012])ELb(?P<NOISE>[01])EEEv")
 KEY = re.compile(r"^(?:  - |    )\.(\w+):\s*(.*)$")       # a key of a kernel's own map (those of its arguments sit deeper)
+
+
+def solve_t(ks, **want):
+    """the k_mvdr_solve_t instantiations among ks whose NULLS / REUSE / WEIGHT / NOISE are those of want (ints)"""
+    out = []
+    for k in ks:
+        m = SOLVE_T.search(k.get("name", ""))
+        if m and all(int(m.group(f)) == v for f, v in want.items()):
+            out.append(k)
+    return out
 
 
 def kernels(lib):

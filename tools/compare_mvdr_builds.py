@@ -1,0 +1,124 @@
+"""Bytes of the MVDR calls of this build against an older build of the library (the yardstick of a refactor of the solve kernels).
+usage: python tools/compare_mvdr_builds.py PARENT_LIB
+
+The same inputs go through PARENT_LIB and through mcarray_amd/libmcarray_hip.so, each in a fresh child process (MCA_HIP_LIB names
+the library, as for the bench tools) under a time limit of its own; the second child is not started when the first one fails.  A
+child binds only the entry points its library has, runs the cases below through the host-pointer calls and leaves one SHA-256 per
+case over the spectra, the audio and the covariance read back.  The parent process requires equal digests of every case the older build ran
+(exit code 1 otherwise) and never opens the GPU itself.
+
+Cases (N = 64, fs = 16 kHz, 3 streams, two calls of 5 + 4 frames; stream 2 starts with digital silence): 3, 4, 6, 8, 11, 12, 15
+and 16 microphones (both forms of every number of row slots) x 1 ... 4 look directions x null_gain 0 and 7.5 (two directions and
+more) x no update weights, a weight per frame (zeros, fractions and ones) and a weight per frame and bin x post-filter off and on.
+Then one call whose solve takes the pieced tail launch: 1000 streams x 8 frames, 16 microphones, 2 directions (516 workgroups: a
+remainder of 4, in 2 pieces)."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FS, N = 16000, 64
+HOP, K = N // 2, N // 2 + 1
+FRAME_WEIGHTS = (1.0, 0.5, 0.0, 0.0, 1.0, 0.25, 0.0, 1.0, 0.75)
+CHILD_SECONDS = 240
+
+
+def digest(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def child(out_path):
+    import ctypes as C
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from mcarray_amd import _lib, api
+    _lib._pin_single_hip_runtime()
+    probe = C.CDLL(_lib.LIB_PATH)
+    _lib.SYMBOLS = [sym for sym in _lib.SYMBOLS if hasattr(probe, sym[0])]     # an older build: what it lacks stays unbound
+    lib = _lib.load()
+    has = lambda name: hasattr(lib, name)
+    res = {}
+
+    def run(name, bf, calls, streams):
+        parts = []
+        for pcm, doa, kw in calls:
+            r = bf.process_sources(pcm, doa, **kw) if doa.ndim == 3 else bf.process(pcm, doa, want_spec=True, **kw)
+            parts += [r["spec"], r["out"]]
+        parts += [bf.covariance(a) for a in streams]
+        bf.close()
+        res[name] = digest(*parts)
+
+    A, F1, F = 3, 5, 9
+    for M in (3, 4, 6, 8, 11, 12, 15, 16):
+        rng = np.random.default_rng(100 + M)
+        xs = [0.3 / M * m for m in range(M)]
+        pcm = rng.standard_normal((A, M, (F + 1) * HOP)).astype(np.float32)
+        pcm[2, :, :3 * HOP] = 0.0
+        cell = rng.choice(np.array([0.0, 0.0, 1.0, 1.0, 0.3, 0.8], dtype=np.float32), size=(A, F, K))
+        frame = np.tile(np.asarray(FRAME_WEIGHTS, dtype=np.float32), (A, 1))
+        frame[1] = frame[1, ::-1]
+        for S in (1, 2, 3, 4):
+            doa = rng.uniform(-1.3, 1.3, (A, F, S)).astype(np.float32)
+            for gain in ((0.0,) if S == 1 else (0.0, 7.5)):
+                for rule, upd in (("none", None), ("frame", frame), ("cell", cell)):
+                    for pf in (False, True):
+                        if (gain and not has("mca_hip_mvdr_set_null_gain")) or (pf and not has("mca_hip_mvdr_set_postfilter")) or \
+                           (rule == "frame" and not has("mca_hip_mvdr_sources_frames_weighted_host")) or \
+                           (rule == "cell" and not has("mca_hip_mvdr_sources_frames_masked_host")) or (S > 1 and not has("mca_hip_mvdr_sources_frames_host")):
+                            continue
+                        bf = api.MvdrBeamformer(FS, xs, N, max_streams=A, max_sources=S, null_gain=gain)
+                        if pf:
+                            bf.set_postfilter(True)
+                        calls = []
+                        for t0, t1 in ((0, F1), (F1, F)):
+                            kw = {} if upd is None else {"update" if rule == "frame" else "update_mask": upd[:, t0:t1]}
+                            calls.append((pcm[:, :, t0 * HOP:(t1 + 1) * HOP], doa[:, t0:t1] if S > 1 else doa[:, t0:t1, 0], kw))
+                        run("M=%d S=%d gain=%g update=%s postfilter=%d" % (M, S, gain, rule, pf), bf, calls, range(A))
+    if has("mca_hip_mvdr_sources_frames_host"):
+        A, F, M, S = 1000, 8, 16, 2
+        rng = np.random.default_rng(7)
+        pcm = rng.standard_normal((A, M, (F + 1) * HOP)).astype(np.float32)
+        doa = rng.uniform(-1.3, 1.3, (A, F, S)).astype(np.float32)
+        bf = api.MvdrBeamformer(FS, [0.3 / M * m for m in range(M)], N, max_streams=A, max_sources=S)
+        run("pieced tail launch: 1000 streams x 8 frames, M=16 S=2", bf, [(pcm, doa, {})], (0, 991, 992, 999))
+    with open(out_path, "w") as f:
+        json.dump(res, f)
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--child":
+        return child(sys.argv[2])
+    if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
+        sys.exit(__doc__)
+    got = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for tag, lib in (("parent", os.path.abspath(sys.argv[1])), ("this", None)):
+            env = dict(os.environ)
+            env.pop("MCA_HIP_LIB", None)
+            if lib:
+                env["MCA_HIP_LIB"] = lib
+            out = os.path.join(tmp, tag + ".json")
+            rc = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), sys.executable, os.path.abspath(__file__), "--child", out], env=env).returncode
+            if rc != 0:
+                sys.exit("%s build (%s): the child ended with %d; nothing further is started" % (tag, lib or "default", rc))
+            got.append(json.load(open(out)))
+    par, new = got
+    missing = [name for name in par if name not in new]
+    if missing:
+        print("this build did not run %d of the parent's %d cases: %s ..." % (len(missing), len(par), missing[0]))
+        sys.exit(1)
+    bad = [name for name in par if par[name] != new[name]]
+    for name in par:
+        print("%s  %s  %s" % ("DIFFERENT" if name in bad else "equal    ", new[name][:16], name))
+    print("%d cases, %d with different bytes (spectra, audio, covariance) against %s" % (len(par), len(bad), sys.argv[1]))
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
