@@ -102,6 +102,30 @@ public:
         gainFloor = cfg.gain_floor;
         noiseScale = cfg.noise_scale;
     }
+    // Steering vectors estimated from the data (mca_hip_mvdr_set_rtf): a second covariance over the cells of a target mask, and its
+    // dominant direction beside the noise covariance as the relative transfer function towards microphone refMic.  targetAlpha in
+    // [0, 1) (negative: keep the value the context holds, its alpha at first), iterations 1 ... 4, refMic 0 ... M - 1, minShare in
+    // [0, 1).  Enabling allocates the target covariances (zero), disabling frees them.  The processRtf() calls use it.
+    void setRtf(bool enable, double targetAlpha = -1.0, int iterations = 2, int refMic = 0, double minShare = 0.05)
+    {
+        mca_hip_mvdr_rtf_config cfg;
+        check(mca_hip_mvdr_get_rtf(_ctx, &cfg));
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.enable = enable ? 1 : 0;
+        if (targetAlpha >= 0.0) cfg.target_alpha = targetAlpha;
+        cfg.iterations = iterations;
+        cfg.ref_mic = refMic;
+        cfg.min_share = minShare;
+        check(mca_hip_mvdr_set_rtf(_ctx, &cfg));
+    }
+    // the steering vectors a frame with look direction doaRadians would take from the held state (mca_hip_mvdr_get_steering):
+    // d [N/2+1][M] complex as (re, im) pairs of doubles, estimated [N/2+1] (1: the RTF, 0: the geometric vector)
+    void steering(double doaRadians, std::vector<double> &d, std::vector<unsigned char> &estimated, int source = 0)
+    {
+        d.resize(static_cast<size_t>(_N / 2 + 1) * static_cast<size_t>(_nchannels) * 2);
+        estimated.resize(static_cast<size_t>(_N / 2 + 1));
+        check(mca_hip_mvdr_get_steering(_ctx, 0, source, doaRadians, d.data(), estimated.data()));
+    }
     // The Capon spatial spectrum of the covariance the stream holds, and its peaks (mca_hip_mvdr_spectrum_*): nAngles 2 ... 361 from
     // -pi/2 to pi/2, the band of bins [binLo, binHi], weighting MCA_HIP_MVDR_SPECTRUM_POWER / _NORMALISED, nPeaks 1 ... 4.  The peak
     // angles are look directions as setDOAs() takes them: process a chunk, read peaks(), setDOAs() for the next chunk.
@@ -191,6 +215,44 @@ public:
         const std::vector<float> upd = weights(F);
         if (updateMask) check(mca_hip_mvdr_sources_frames_masked_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMask, audio.data(), nullptr));
         else check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, S, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
+        for (int s = 0; s < S; ++s)
+            for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
+        consume(F);
+        return F * hop;
+    }
+
+    // process() with estimated steering vectors (setRtf(true) first; mca_hip_mvdr_sources_frames_rtf_*): targetMask
+    // [look directions][framesCompletedBy(nSamples)][N/2 + 1], 1 where the cell holds that direction's target (nullptr: nothing is
+    // learned, the held target covariance steers); updateMask as above (nullptr: all 1), usually 1 - max over the directions of
+    // targetMask.  The output is the target as microphone refMic records it.
+    template <typename Tin, typename Tout>
+    int processRtf(const std::vector<Tin *> &in, int nSamples, Tout *out, int outSize, const float *updateMask, const float *targetMask)
+    {
+        const int hop = _N / 2;
+        const int F = pend(in, nSamples);
+        if (F == 0) return 0;
+        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
+        std::vector<float> pcm = frames(F);
+        std::vector<float> doa(static_cast<size_t>(F), static_cast<float>(_doa)), audio(static_cast<size_t>(F) * static_cast<size_t>(hop));
+        check(mca_hip_mvdr_sources_frames_rtf_host(_ctx, pcm.data(), 1, F, 1, doa.data(), updateMask, targetMask, audio.data(), nullptr));
+        for (int i = 0; i < F * hop; ++i) out[i] = static_cast<Tout>(audio[static_cast<size_t>(i)]);
+        consume(F);
+        return F * hop;
+    }
+    template <typename Tin, typename Tout>
+    int processRtf(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize, const float *updateMask, const float *targetMask)
+    {
+        const int hop = _N / 2, S = static_cast<int>(_doas.size());
+        if (S == 0) throw MCArrayException("processRtf: setDOAs() first");
+        if (static_cast<int>(out.size()) < S) throw MCArrayException("processRtf: one output pointer per look direction of setDOAs()");
+        const int F = pend(in, nSamples);
+        if (F == 0) return 0;
+        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
+        std::vector<float> pcm = frames(F);
+        std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
+        for (int t = 0; t < F; ++t)
+            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+        check(mca_hip_mvdr_sources_frames_rtf_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMask, targetMask, audio.data(), nullptr));
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
         consume(F);

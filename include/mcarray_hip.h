@@ -714,6 +714,79 @@ typedef struct {
 } mca_hip_mvdr_postfilter_config;
 int mca_hip_mvdr_set_postfilter(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_postfilter_config *cfg);
 int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_postfilter_config *cfg);
+/* Steering vectors estimated from the data: the relative transfer function (RTF) towards a reference microphone, from a second
+ * covariance kept over the cells in which the target is present.  The geometric vector d_m = exp(-j k ... x_m cos(theta + pi/2)) of
+ * every other call knows nothing of microphone gains, position errors or a look direction a few degrees off, and a distortionless
+ * constraint towards the wrong vector distorts the target whatever the noise covariance does.  A target mask is
+ * the same kind of array as the update mask: INTEGRATION.md says how a mask estimator's output becomes the two.
+ * State of an enabled context, fp32: Psi [max_streams][max_sources][K] packed triangles, stored as Phi is; cpsi
+ * [max_streams][max_sources][K] and cphi [max_streams][K], the sums of the weights that Psi and Phi hold.  On enabling Psi = 0,
+ * cpsi = 0 and cphi = 1 where the bin's trace is > 1e-30, else 0; after mca_hip_mvdr_reset all are zero;
+ * mca_hip_mvdr_set_max_sources keeps the slots that both sizes have and zeroes the others; the slots s >= n_sources of the streams
+ * in a mca_hip_mvdr_sources_frames_rtf_* call are zeroed by that call (the tails' rule).
+ * Per stream a, slot s, bin k and frame t, with x the frame's spectra, u and a_tk of the masked call above,
+ * m = fminf(fmaxf(target_mask[a][s][t][k], 0), 1) (a NaN counts as 0), b = 1 - (1 - target_alpha) m, g0 the geometric vector of
+ * doa_rad[a][t][s]:
+ *     Phi_t, tr_t   exactly the masked call's recursion under update_mask
+ *     cphi_t = a_tk cphi + (1 - a_tk)                                   (untouched where u == 0)
+ *     Psi_t  = b Psi + (1 - b) x x^H,   cpsi_t = b cpsi + (1 - b)        (both untouched, bit for bit, where m == 0)
+ *     tau    = tr(Psi_t) / cpsi_t                                        needs cpsi_t > 0 and tau > 1e-30
+ *     Delta  = Psi_t / (cpsi_t tau) - [cphi_t > 0] Phi_t / (cphi_t tau)
+ *     v = g0 / sqrt(M);  `iterations` times:  g = Delta v,  n = |g|^2 (needs n > 1e-20),  v_prev = v,  v = g / sqrt(n)
+ *     rho    = Re(v_prev^H g)                                            needs rho > min_share
+ *                                                                        needs |g[ref_mic]|^2 > 1e-6 n
+ *     d      = g / g[ref_mic]                                            the RTF: d[ref_mic] = 1
+ *     any "needs" not met, or a non-finite value: d = g0
+ *     w = PhiL_t^-1 d / (d^H PhiL_t^-1 d),  Y = w^H x                    with the loaded covariance as everywhere
+ * The output is the target as the reference microphone records it.  A bin whose noise trace is <= 1e-30 keeps the delay-and-sum
+ * with the GEOMETRIC vector (w = g0 / M).  The post-filter's p is noise_scale / (d^H PhiL^-1 d) with the d the frame used.
+ * Accepted, all finite: target_alpha in [0, 1) (default: the context's alpha), iterations 1 ... 4 (default 2), ref_mic 0 ... M-1
+ * (default 0), min_share in [0, 1) (default 0.05); anything else, a wrong struct_size included, is MCA_HIP_ERR_INVALID_ARGUMENT and
+ * leaves configuration and state as they were.  The four values are processing parameters like the null gain; enable 0 -> 1
+ * allocates the state as stated, 1 -> 0 frees it.
+ *   target_mask_dev [streams][n_sources][F][K] float   contiguous; NULL = all 0: nothing is learned and the held Psi steers
+ *   update_mask_dev [streams][F][K] float              as in the masked call; NULL = all 1
+ * mca_hip_mvdr_sources_frames_rtf_* on a context without RTF enabled is MCA_HIP_ERR_INVALID_ARGUMENT; with a null gain != 0 it is
+ * MCA_HIP_ERR_UNSUPPORTED (nulls at estimated vectors are not built); the other argument checks are those of the masked call.  The
+ * steering plane [streams][n_sources][frames][K][M] (8 bytes each) is workspace with a cap of 1 GiB
+ * (mca_hip_mvdr_set_rtf_workspace(ctx, max_bytes >= 8) sets another; a processing parameter): a call above it is cut along the
+ * frames internally, a frame at a time at the least, which changes no byte.  The host call stages both masks.  Exact points:
+ *   - with a NULL or all-zero target mask on fresh RTF state the call gives the bytes of mca_hip_mvdr_sources_frames_masked_* under
+ *     the same update mask, in spectra, audio and covariance;
+ *   - the bytes of bin k depend on column k of both masks only; how a stream is cut into calls, and where it sits in the batch, do
+ *     not change its bytes.
+ * The six other mca_hip_mvdr_*frames* calls are untouched on any context, enabled or not: the same kernels launched, geometric
+ * steering, Psi, cpsi and cphi not advanced.  cphi therefore UNDER-COUNTS the weights in Phi when entry points are mixed on one
+ * stream: keep a stream on the RTF entry point while RTF is enabled.
+ * State blobs: an RTF-enabled context writes version 4 -- covariances, traces, tails, A if the post-filter is enabled, then Psi, cpsi
+ * and cphi; host[0] = max_sources, host[1] = post-filter enabled, host[2] = 1 -- which loads only into a context with the same
+ * max_sources, post-filter enablement and RTF enablement; every other combination is refused with the state untouched
+ * (MCA_HIP_ERR_INVALID_ARGUMENT).  Contexts without RTF read and write what they always did. */
+typedef struct {
+    int struct_size;
+    int enable;
+    double target_alpha;
+    int iterations;
+    int ref_mic;
+    double min_share;
+} mca_hip_mvdr_rtf_config;
+int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_rtf_config *cfg);
+int mca_hip_mvdr_get_rtf(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_rtf_config *cfg);
+int mca_hip_mvdr_set_rtf_workspace(mca_hip_mvdr_ctx *ctx, long long max_bytes);
+int mca_hip_mvdr_sources_frames_rtf_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev, long long stream_stride, long long mic_stride,
+                                        int n_streams, int n_frames, int n_sources, const float *doa_rad_dev,
+                                        const float *update_mask_dev, const float *target_mask_dev, float *out_pcm_dev,
+                                        float *out_spec_dev, void *stream);
+int mca_hip_mvdr_sources_frames_rtf_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
+                                         const float *doa_rad, const float *update_mask, const float *target_mask, float *out_pcm,
+                                         float *out_spec);
+/* the estimator above on the state the context holds now, for look direction doa_rad: out [K][M] interleaved re,im double,
+ * estimated [K] bytes (1: the RTF, 0: the geometric vector).  A pure function of state and configuration, like the spectrum call;
+ * the silence rule of the frames call is not part of it.  RTF must be enabled; source in 0 ... max_sources - 1. */
+int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *ctx, int stream_index, int source, double doa_rad, double *out, unsigned char *estimated);
+/* copy of the target covariance of one stream and slot: out [K][M][M] interleaved re,im double (full Hermitian matrices), norm [K]
+ * double (cpsi); either may be NULL, not both */
+int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, int source, double *out, double *norm);
 /* Capon (minimum-variance) spatial spectrum of the covariance the context holds now (after its last frames call or state load),
  * and its peaks: the MVDR power estimate p = 1 / (d^H PhiL^-1 d) of the nulls above on a grid of angles.  Per stream, with
  *     theta_i      = -pi/2 + i pi/(D-1), i = 0 ... D-1 (in double),       D = n_angles
@@ -753,14 +826,15 @@ int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *spec
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream (and the
- * post-filter's A of a context that has it enabled: version 3, above) */
+ * post-filter's A of a context that has it enabled: version 3, above; Psi, cpsi and cphi of one with RTF enabled: version 4, above) */
 long long mca_hip_mvdr_state_size(const mca_hip_mvdr_ctx *ctx);
 int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *ctx, void *blob, long long blob_bytes);
 int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long blob_bytes);
 /* per-kernel timing as mca_hip_set_timing / mca_hip_get_timing: kernel_id 0 = analysis, 1 = solve, 2 = synthesis,
  * 3 = spectrum (both kernels of a mca_hip_mvdr_spectrum_* call), 4 = post-filter.  kernel_id 4 exists on a context that has had the
  * post-filter enabled at some time (it stays readable after disabling); a context that never enabled it refuses 4 like every
- * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT) */
+ * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT).  5 = k_mvdr_rtf, by the same rule: it exists on a
+ * context that has had RTF enabled at some time */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

@@ -116,6 +116,17 @@ class MvdrPostfilterConfig(C.Structure):
     ]
 
 
+class MvdrRtfConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("enable", C.c_int),
+        ("target_alpha", C.c_double),
+        ("iterations", C.c_int),
+        ("ref_mic", C.c_int),
+        ("min_share", C.c_double),
+    ]
+
+
 class Gcc2TrackerConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -248,6 +259,15 @@ SYMBOLS = [
     ("mca_hip_mvdr_sources_frames_masked_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_sources_frames_masked_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_set_rtf", C.c_int, [C.c_void_p, C.POINTER(MvdrRtfConfig)]),
+    ("mca_hip_mvdr_get_rtf", C.c_int, [C.c_void_p, C.POINTER(MvdrRtfConfig)]),
+    ("mca_hip_mvdr_set_rtf_workspace", C.c_int, [C.c_void_p, C.c_longlong]),
+    ("mca_hip_mvdr_sources_frames_rtf_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_void_p]),
+    ("mca_hip_mvdr_sources_frames_rtf_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_get_steering", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, c_dp, C.c_void_p]),
+    ("mca_hip_mvdr_get_target_covariance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_dp]),
     ("mca_hip_mvdr_spectrum_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrSpectrumConfig)]),
     ("mca_hip_mvdr_spectrum_get_grid", C.c_int, [C.c_void_p, c_fp]),
     ("mca_hip_mvdr_spectrum_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -872,9 +872,13 @@ class MvdrBeamformer(_StateBlob):
     that holds the target in a frame is left alone while the other bins of that frame learn
     (mca_hip_mvdr_sources_frames_masked_*).  update= and update_mask= are not combined: multiply them.
     set_postfilter() puts the decision-directed Wiener post-filter behind the solve of every process call: the noise-only MVDR
-    becomes the multichannel Wiener filter (mca_hip_mvdr_set_postfilter)."""
+    becomes the multichannel Wiener filter (mca_hip_mvdr_set_postfilter).
+    set_rtf() and target_mask= of the process calls: the steering vector of every look direction is estimated from a second
+    covariance kept over the cells of its target mask [streams][S][F][K] -- the relative transfer function towards a reference
+    microphone, which knows the microphones' gains and positions and the true direction where the geometric vector does not
+    (mca_hip_mvdr_set_rtf, mca_hip_mvdr_sources_frames_rtf_*).  A call with target_mask= takes update_mask= beside it, not update=."""
 
-    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER = 0, 1, 2, 3, 4
+    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF = 0, 1, 2, 3, 4, 5
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  null_gain=0.0):
@@ -943,6 +947,45 @@ class MvdrBeamformer(_StateBlob):
         self._check(self._lib.mca_hip_mvdr_get_postfilter(self.h, C.byref(cfg)))
         return dict(enable=bool(cfg.enable), smoothing=cfg.smoothing, gain_floor=cfg.gain_floor, noise_scale=cfg.noise_scale)
 
+    def set_rtf(self, enable=True, target_alpha=None, iterations=2, ref_mic=0, min_share=0.05):
+        """steering vectors estimated from a target covariance (include/mcarray_hip.h, mca_hip_mvdr_set_rtf): target_alpha in [0, 1)
+        (None: the value the context holds, its alpha at first), iterations 1 ... 4, ref_mic 0 ... M - 1, min_share in [0, 1).  The
+        four values are processing parameters; enabling allocates the target covariances (zero), disabling frees them."""
+        cfg = _lib.MvdrRtfConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrRtfConfig)
+        cfg.enable = 1 if enable else 0
+        cfg.target_alpha = self.get_rtf()["target_alpha"] if target_alpha is None else float(target_alpha)
+        cfg.iterations = int(iterations)
+        cfg.ref_mic = int(ref_mic)
+        cfg.min_share = float(min_share)
+        self._check(self._lib.mca_hip_mvdr_set_rtf(self.h, C.byref(cfg)))
+
+    def get_rtf(self):
+        """dict(enable, target_alpha, iterations, ref_mic, min_share) as the context holds them"""
+        cfg = _lib.MvdrRtfConfig()
+        self._check(self._lib.mca_hip_mvdr_get_rtf(self.h, C.byref(cfg)))
+        return dict(enable=bool(cfg.enable), target_alpha=cfg.target_alpha, iterations=cfg.iterations, ref_mic=cfg.ref_mic, min_share=cfg.min_share)
+
+    def set_rtf_workspace(self, max_bytes):
+        """cap of the steering plane a target_mask= call holds at a time (default 1 GiB): a call above it is cut along the frames
+        internally, which changes no byte (mca_hip_mvdr_set_rtf_workspace)"""
+        self._check(self._lib.mca_hip_mvdr_set_rtf_workspace(self.h, int(max_bytes)))
+
+    def target_covariance(self, stream_index=0, source=0):
+        """(Psi complex [K][M][M], cpsi [K]) of one stream and slot"""
+        out, norm = np.empty((self.K, self.M, self.M, 2)), np.empty(self.K)
+        self._check(self._lib.mca_hip_mvdr_get_target_covariance(self.h, int(stream_index), int(source), out.ctypes.data_as(_lib.c_dp),
+                                                                 norm.ctypes.data_as(_lib.c_dp)))
+        return out[..., 0] + 1j * out[..., 1], norm
+
+    def steering(self, doa_rad, stream_index=0, source=0):
+        """the steering vectors a frame with look direction doa_rad would take from the held state -> (d complex [K][M], estimated
+        bool [K]: the RTF, or the geometric vector where the estimate is refused)"""
+        out, est = np.empty((self.K, self.M, 2)), np.empty(self.K, dtype=np.uint8)
+        self._check(self._lib.mca_hip_mvdr_get_steering(self.h, int(stream_index), int(source), float(doa_rad), out.ctypes.data_as(_lib.c_dp),
+                                                        est.ctypes.data_as(C.c_void_p)))
+        return out[..., 0] + 1j * out[..., 1], est.astype(bool)
+
     def close(self):
         if getattr(self, "h", None):
             self._lib.mca_hip_mvdr_destroy(self.h)
@@ -989,10 +1032,43 @@ class MvdrBeamformer(_StateBlob):
             raise MCArrayHipError("update_mask must be a contiguous float32 tensor [streams][F][K]")
         return _ptr(m)
 
-    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None, update_mask=None):
+    def _tmask_host(self, update, target_mask, A, S, F):
+        """float32 [streams][S][F][K] from anything that broadcasts to it"""
+        if update is not None:
+            raise MCArrayHipError("target_mask goes with update_mask, not with update")
+        try:
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(target_mask, dtype=np.float32), (A, S, F, self.K)))
+        except (ValueError, TypeError):
+            raise MCArrayHipError("target_mask must broadcast to [streams][S][F][K]")
+
+    def _tmask_dev(self, update, target_mask, A, S, n_frames):
+        if update is not None:
+            raise MCArrayHipError("target_mask goes with update_mask, not with update")
+        m = target_mask
+        if not getattr(m, "is_cuda", False):
+            raise MCArrayHipError("target_mask must be a contiguous float32 tensor [streams][S][F][K] on the device")
+        if m.dim() != 4 or not m.is_contiguous() or tuple(m.shape) != (A, S, n_frames, self.K) or m.element_size() != 4 or not m.is_floating_point():
+            raise MCArrayHipError("target_mask must be a contiguous float32 tensor [streams][S][F][K]")
+        return _ptr(m)
+
+    def _rtf_host(self, pcm, A, F, S, doa, update, update_mask, target_mask, po, ps):
+        fp = _lib.c_fp
+        tm = self._tmask_host(update, target_mask, A, S, F)
+        upd = None if update_mask is None else self._mask_host(None, update_mask, A, F)
+        self._check(self._lib.mca_hip_mvdr_sources_frames_rtf_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp),
+                                                                   None if upd is None else upd.ctypes.data_as(fp), tm.ctypes.data_as(fp), po, ps))
+
+    def _rtf_dev(self, p, sa, sc, A, n_frames, S, doa_rad, update, update_mask, target_mask, out_pcm, out_spec, stream):
+        tm = self._tmask_dev(update, target_mask, A, S, n_frames)
+        upd = None if update_mask is None else self._mask_dev(None, update_mask, A, n_frames)
+        self._check(self._lib.mca_hip_mvdr_sources_frames_rtf_dev(self.h, p, sa, sc, A, n_frames, S, _ptr(doa_rad), upd, tm, _ptr(out_pcm),
+                                                                  _ptr(out_spec), stream))
+
+    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None, update_mask=None, target_mask=None):
         """pcm float32 [streams][M][(F+1)*hop], doa_rad [streams][F] (or a scalar), update None or [streams][F] covariance update
         weights, or update_mask None or [streams][F][K] weights per frame and bin -> dict(out [streams][F*hop], spec complex64
-        [streams][F][K])"""
+        [streams][F][K]).  target_mask [streams][1][F][K] (or what broadcasts to it): the call steers with the estimated vector
+        (set_rtf(); mca_hip_mvdr_sources_frames_rtf_*)"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
             pcm = pcm[None]
@@ -1005,7 +1081,9 @@ class MvdrBeamformer(_StateBlob):
         spec = np.empty((A, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
         po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
-        if update_mask is not None:
+        if target_mask is not None:
+            self._rtf_host(pcm, A, F, 1, doa, update, update_mask, target_mask, po, ps)
+        elif update_mask is not None:
             upd = self._mask_host(update, update_mask, A, F)
             self._check(self._lib.mca_hip_mvdr_sources_frames_masked_host(self.h, pcm.ctypes.data_as(fp), A, F, 1, doa.ctypes.data_as(fp),
                                                                           upd.ctypes.data_as(fp), po, ps))
@@ -1017,14 +1095,16 @@ class MvdrBeamformer(_StateBlob):
                                                                             upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None):
+    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None, target_mask=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F]
         float32, out_pcm [streams][F*hop], out_spec [streams][F][K][2] (contiguous), update None or [streams][F] float32 covariance
-        update weights (contiguous), or update_mask None or [streams][F][K] float32 (contiguous); asynchronous on `stream` (a raw
-        hipStream_t or None)."""
+        update weights (contiguous), or update_mask None or [streams][F][K] float32 (contiguous), target_mask None or
+        [streams][1][F][K] float32 (contiguous; set_rtf()); asynchronous on `stream` (a raw hipStream_t or None)."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
-        if update_mask is not None:
+        if target_mask is not None:
+            self._rtf_dev(p, sa, sc, A, n_frames, 1, doa_rad, update, update_mask, target_mask, out_pcm, out_spec, stream)
+        elif update_mask is not None:
             self._check(self._lib.mca_hip_mvdr_sources_frames_masked_dev(self.h, p, sa, sc, A, n_frames, 1, _ptr(doa_rad),
                                                                          self._mask_dev(update, update_mask, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
         elif update is None:
@@ -1033,11 +1113,13 @@ class MvdrBeamformer(_StateBlob):
             self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_dev(self.h, p, sa, sc, A, n_frames, 1, _ptr(doa_rad),
                                                                            self._update_dev(update, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
 
-    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None, update_mask=None):
+    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None, update_mask=None, target_mask=None):
         """S look directions per frame from one analysis, covariance recursion and factorisation: pcm float32
         [streams][M][(F+1)*hop], doa_rad [streams][F][S] (S <= max_sources; the layout of the localiser's "doa"), update None or
         [streams][F] covariance update weights (one per frame for all its directions), or update_mask None or [streams][F][K] ->
-        dict(out [streams][S][F*hop], spec complex64 [streams][S][F][K]).  Output s is what process() gives with doa_rad[:, :, s]."""
+        dict(out [streams][S][F*hop], spec complex64 [streams][S][F][K]).  Output s is what process() gives with doa_rad[:, :, s].
+        target_mask None or [streams][S][F][K]: the cells that hold the target of look direction s, from which its steering vector
+        is estimated (set_rtf(); mca_hip_mvdr_sources_frames_rtf_*)."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
             pcm = pcm[None]
@@ -1054,7 +1136,9 @@ class MvdrBeamformer(_StateBlob):
         spec = np.empty((A, S, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
         po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
-        if update_mask is not None:
+        if target_mask is not None:
+            self._rtf_host(pcm, A, F, S, doa, update, update_mask, target_mask, po, ps)
+        elif update_mask is not None:
             upd = self._mask_host(update, update_mask, A, F)
             self._check(self._lib.mca_hip_mvdr_sources_frames_masked_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp),
                                                                           upd.ctypes.data_as(fp), po, ps))
@@ -1066,16 +1150,20 @@ class MvdrBeamformer(_StateBlob):
                                                                             upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None):
+    def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None,
+                            target_mask=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F][S]
         float32 (e.g. the doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec
         [streams][S][F][K][2] (contiguous), update None or [streams][F] float32 covariance update weights (contiguous), or
-        update_mask None or [streams][F][K] float32 (contiguous); asynchronous on `stream` (a raw hipStream_t or None)."""
+        update_mask None or [streams][F][K] float32 (contiguous), target_mask None or [streams][S][F][K] float32 (contiguous;
+        set_rtf()); asynchronous on `stream` (a raw hipStream_t or None)."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
         if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
             raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
-        if update_mask is not None:
+        if target_mask is not None:
+            self._rtf_dev(p, sa, sc, A, n_frames, doa_rad.shape[2], doa_rad, update, update_mask, target_mask, out_pcm, out_spec, stream)
+        elif update_mask is not None:
             self._check(self._lib.mca_hip_mvdr_sources_frames_masked_dev(self.h, p, sa, sc, A, n_frames, doa_rad.shape[2], _ptr(doa_rad),
                                                                          self._mask_dev(update, update_mask, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
         elif update is None:

@@ -1,13 +1,14 @@
 // api_mvdr.hip -- C ABI of the MVDR-style beamformer with a per-bin spatial covariance (include/mcarray_hip.h,
 // mca_hip_mvdr_*; BASELINE.json configs[3]; SURVEY A.9 -- no reference counterpart, conventions of Beamformer.cpp:59).
 // Host side only: owns the per-stream state (covariances, their traces, overlap-add tails) and the spectra
-// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h and kernels_mvdr_postfilter.hip.  No CPU fallback.
+// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip and kernels_mvdr_postfilter.hip.  No CPU fallback.
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
 #include "stage.h"
 #include "state_blob.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -36,6 +37,19 @@ struct mca_hip_mvdr_ctx {
     float *d_pf_A = nullptr;      // [max_streams][max_sources][K] |Z|^2 of the frame before; allocated while enabled
     float *d_pf_pn = nullptr;     // workspace [y_rows][K]: the residual noise power of every output of the call; while enabled
     float *d_pf_ones = nullptr; size_t pf_ones_n = 0;   // update weights of a call that brings none, all 1
+    // steering vectors estimated from a target covariance (mca_hip_mvdr_set_rtf): the four values are processing parameters like
+    // null_gain; Psi, cpsi and cphi are stream state, allocated while enabled
+    bool rtf_on = false;
+    bool rtf_ever = false;        // enabled at some time: timing slot 5 exists
+    double rtf_alpha = 0.0, rtf_min_share = 0.05;   // (rtf_alpha: the context's alpha until set)
+    int rtf_iterations = 2, rtf_ref = 0;
+    float2 *d_psi = nullptr;      // [max_streams][max_sources][K][tri]
+    float *d_cpsi = nullptr;      // [max_streams][max_sources][K]
+    float *d_cphi = nullptr;      // [max_streams][K]
+    float *d_cphi_next = nullptr; // exit value of the streams of a call, copied over d_cphi behind k_mvdr_rtf (MvdrRtfArgs::cphi_out)
+    float2 *d_D = nullptr; size_t d_cap = 0;              // workspace: the steering plane [rows x look directions][K][M] of a chunk of frames
+    size_t plane_cap_cells = (size_t)1 << 27;            // its cap (1 GiB; mca_hip_mvdr_set_rtf_workspace): a call above it is cut along the frames
+    float *d_rtf_ones = nullptr; size_t rtf_ones_n = 0;   // update mask of an RTF call that brings none, all 1 [rows][K]
     // workspace
     float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
     float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // rows x look directions; d_T: factored steering phasors [rows][M][N/64 + 33]
@@ -51,8 +65,8 @@ struct mca_hip_mvdr_ctx {
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[5] = {};
-    double t_ms[5] = {};
+    int t_launches[6] = {};
+    double t_ms[6] = {};
     std::string err;
 };
 
@@ -80,6 +94,7 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
     auto F = [](void *p) { if (p) (void)hipFree(p); };
     F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
     F(c->d_pf_A); F(c->d_pf_pn); F(c->d_pf_ones);
+    F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
     F(c->d_X); F(c->d_Y); F(c->d_T); F(c->d_spec_grid); F(c->d_spec_T); F(c->d_spec_part);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->stage.release();
@@ -93,13 +108,35 @@ int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
     VHIP_TRY(c, hipMemsetAsync(c->d_trace, 0, ns * c->K * 4, st));
     for (int i = 0; i < 2; ++i) VHIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, ns * c->max_sources * c->H * 4, st));
     if (c->d_pf_A) VHIP_TRY(c, hipMemsetAsync(c->d_pf_A, 0, ns * c->max_sources * c->K * 4, st));
+    if (c->rtf_on) {
+        VHIP_TRY(c, hipMemsetAsync(c->d_psi, 0, ns * c->max_sources * c->K * c->tri * sizeof(float2), st));
+        VHIP_TRY(c, hipMemsetAsync(c->d_cpsi, 0, ns * c->max_sources * c->K * 4, st));
+        VHIP_TRY(c, hipMemsetAsync(c->d_cphi, 0, ns * c->K * 4, st));
+    }
     VHIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
-int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_ones)
+int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_ones, bool rtf, size_t plane_rows = 0)
 {
     auto F = [](void *p) { if (p) (void)hipFree(p); };
+    if (rtf) {
+        const size_t cells = plane_rows * n_sources * c->K * c->M;
+        if (cells > c->d_cap) {
+            F(c->d_D); c->d_D = nullptr; c->d_cap = 0;
+            VHIP_TRY(c, hipMalloc((void **)&c->d_D, cells * sizeof(float2)));
+            c->d_cap = cells;
+        }
+        if (want_ones && rows * c->K > c->rtf_ones_n) {
+            // the solve behind k_mvdr_rtf takes a weight per cell: a call without an update mask passes ones, whose bytes are those of no weights
+            F(c->d_rtf_ones); c->d_rtf_ones = nullptr; c->rtf_ones_n = 0;
+            VHIP_TRY(c, hipMalloc((void **)&c->d_rtf_ones, rows * c->K * 4));
+            std::vector<float> ones(rows * c->K, 1.f);
+            VHIP_TRY(c, hipMemcpy(c->d_rtf_ones, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
+            c->rtf_ones_n = rows * c->K;
+        }
+        want_ones = false;
+    }
     if (c->pf_on && want_ones && rows > c->pf_ones_n) {
         // a call without update weights still takes the gated kernels (they emit the noise plane): weights of 1, whose bytes are
         // those of the unweighted kernels
@@ -198,6 +235,7 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
 
     mca_hip_mvdr_ctx *c = new mca_hip_mvdr_ctx();
     c->cfg = *cfg; c->cfg.mic_xyz = nullptr;
+    c->rtf_alpha = cfg->alpha;
     c->N = cfg->fft_size; c->H = c->N / 2; c->K = c->H + 1; c->M = cfg->n_mics; c->tri = c->M * (c->M + 1) / 2;
     while ((1 << c->logH) < c->H) ++c->logH;
     std::vector<float> win(c->N);
@@ -263,6 +301,23 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
         if (nt[1]) (void)hipFree(nt[1]);
         return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("overlap-add tails of the new sources: ") + hipGetErrorString(e));
     }
+    // Psi and cpsi [max_streams][max_sources][...] of a context with RTF enabled, by the same rule
+    float2 *npsi = nullptr; float *ncpsi = nullptr;
+    if (c->rtf_on) {
+        const size_t prow = (size_t)c->K * c->tri * sizeof(float2), crow = (size_t)c->K * 4;
+        e = hipMalloc((void **)&npsi, ns * max_sources * prow);
+        if (e == hipSuccess) e = hipMalloc((void **)&ncpsi, ns * max_sources * crow);
+        if (e == hipSuccess) e = hipMemset(npsi, 0, ns * max_sources * prow);
+        if (e == hipSuccess) e = hipMemset(ncpsi, 0, ns * max_sources * crow);
+        if (e == hipSuccess) e = hipMemcpy2D(npsi, max_sources * prow, c->d_psi, c->max_sources * prow, keep * prow, ns, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy2D(ncpsi, max_sources * crow, c->d_cpsi, c->max_sources * crow, keep * crow, ns, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (npsi) (void)hipFree(npsi);
+            if (ncpsi) (void)hipFree(ncpsi);
+            (void)hipFree(nt[0]); (void)hipFree(nt[1]);
+            return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("target covariances of the new sources: ") + hipGetErrorString(e));
+        }
+    }
     // the post-filter's A [max_streams][max_sources][K] of an enabled context, by the same rule
     float *na = nullptr;
     if (c->pf_on) {
@@ -272,11 +327,17 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
         if (e == hipSuccess) e = hipMemcpy2D(na, max_sources * arow, c->d_pf_A, c->max_sources * arow, keep * arow, ns, hipMemcpyDeviceToDevice);
         if (e != hipSuccess) {
             if (na) (void)hipFree(na);
+            if (npsi) (void)hipFree(npsi);
+            if (ncpsi) (void)hipFree(ncpsi);
             (void)hipFree(nt[0]); (void)hipFree(nt[1]);
             return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("post-filter state of the new sources: ") + hipGetErrorString(e));
         }
         (void)hipFree(c->d_pf_A);
         c->d_pf_A = na;
+    }
+    if (c->rtf_on) {
+        (void)hipFree(c->d_psi); (void)hipFree(c->d_cpsi);
+        c->d_psi = npsi; c->d_cpsi = ncpsi;
     }
     (void)hipFree(c->d_tail[0]); (void)hipFree(c->d_tail[1]);
     c->d_tail[0] = nt[0]; c->d_tail[1] = nt[1]; c->tail_cur = 0; c->max_sources = max_sources;
@@ -349,6 +410,71 @@ int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_postfilt
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_rtf_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_rtf_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!std::isfinite(cfg->target_alpha) || cfg->target_alpha < 0.0 || cfg->target_alpha >= 1.0)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "target_alpha must be finite and in [0,1)");
+    if (cfg->iterations < 1 || cfg->iterations > 4) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "iterations must be in [1,4]");
+    if (cfg->ref_mic < 0 || cfg->ref_mic >= c->M) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "ref_mic must be in [0, n_mics)");
+    if (!std::isfinite(cfg->min_share) || cfg->min_share < 0.0 || cfg->min_share >= 1.0)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_share must be finite and in [0,1)");
+    const bool on = cfg->enable != 0;
+    if (on != c->rtf_on) {
+        VHIP_TRY(c, hipSetDevice(c->cfg.device));
+        VHIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
+        auto F = [](void *p) { if (p) (void)hipFree(p); };
+        if (on) {
+            // Psi = 0, cpsi = 0; cphi = 1 where the covariance holds something (its weights were not counted: taken as complete)
+            const size_t ns = (size_t)c->cfg.max_streams, nk = ns * c->K;
+            const size_t pb = ns * c->max_sources * c->K * c->tri * sizeof(float2), cb = ns * c->max_sources * c->K * 4;
+            float2 *npsi = nullptr; float *ncpsi = nullptr, *ncphi = nullptr, *nnext = nullptr;
+            std::vector<float> tr(nk);
+            hipError_t e = hipMalloc((void **)&npsi, pb);
+            if (e == hipSuccess) e = hipMalloc((void **)&ncpsi, cb);
+            if (e == hipSuccess) e = hipMalloc((void **)&ncphi, nk * 4);
+            if (e == hipSuccess) e = hipMalloc((void **)&nnext, nk * 4);
+            if (e == hipSuccess) e = hipMemset(npsi, 0, pb);
+            if (e == hipSuccess) e = hipMemset(ncpsi, 0, cb);
+            if (e == hipSuccess) e = hipMemcpy(tr.data(), c->d_trace, nk * 4, hipMemcpyDeviceToHost);
+            for (auto &v : tr) v = v > 1e-30f ? 1.f : 0.f;
+            if (e == hipSuccess) e = hipMemcpy(ncphi, tr.data(), nk * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                F(npsi); F(ncpsi); F(ncphi); F(nnext);
+                return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("RTF state: ") + hipGetErrorString(e));
+            }
+            c->d_psi = npsi; c->d_cpsi = ncpsi; c->d_cphi = ncphi; c->d_cphi_next = nnext;
+        } else {
+            F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
+            c->d_psi = nullptr; c->d_cpsi = nullptr; c->d_cphi = nullptr; c->d_cphi_next = nullptr;
+            c->d_D = nullptr; c->d_cap = 0; c->d_rtf_ones = nullptr; c->rtf_ones_n = 0;
+        }
+        c->rtf_on = on;
+        if (on) c->rtf_ever = true;
+    }
+    c->rtf_alpha = cfg->target_alpha; c->rtf_iterations = cfg->iterations; c->rtf_ref = cfg->ref_mic; c->rtf_min_share = cfg->min_share;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_set_rtf_workspace(mca_hip_mvdr_ctx *c, long long max_bytes)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (max_bytes < 8) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_bytes must be at least 8");
+    c->plane_cap_cells = (size_t)(max_bytes / 8);          // (a plane already held stays until a call needs a larger one)
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_rtf(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_rtf_config *cfg)
+{
+    if (!c || !cfg) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    cfg->struct_size = (int)sizeof(mca_hip_mvdr_rtf_config);
+    cfg->enable = c->rtf_on ? 1 : 0;
+    cfg->target_alpha = c->rtf_alpha; cfg->iterations = c->rtf_iterations; cfg->ref_mic = c->rtf_ref; cfg->min_share = c->rtf_min_share;
+    return MCA_HIP_OK;
+}
+
 namespace {
 
 // the analysis (timing slot 0): PCM -> X, and the steering tables T of doa_rad [streams][F][n_sources]
@@ -387,8 +513,11 @@ int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_strid
 
 // the solve (timing slot 1): X, T -> Y, the covariance and, for the post-filter, the noise plane.  update: covariance update
 // weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
-int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float *update, bool masked, float2 *Y, hipStream_t st)
+// rtf: the frames f0 ... f0 + n_loop - 1 of the call (the steering plane holds those), else the whole call
+int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float *update, bool masked, bool rtf, float2 *Y, hipStream_t st,
+                 int f0 = 0, int n_loop = 0)
 {
+    if (!rtf) n_loop = n_frames;
     MvdrSolveArgs sa{};
     sa.X = c->d_X; sa.T = c->d_T;
     sa.n_frames = n_frames; sa.K = c->K; sa.M = c->M;
@@ -403,8 +532,17 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
     const bool nulls = n_sources > 1 && sa.null_gain > 0.f;                           // a gain that rounds to 0 in fp32 is gain 0
     const int Q = (c->M + 3) / 4;                                                     // row slots per lane
     int lds = 0;
-    const void *kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
-                                           c->pf_on, &lds);
+    const void *kernel;
+    if (rtf) {
+        // the right-hand sides come from the steering plane; a weight per cell always (ones for a call without an update mask)
+        sa.D = c->d_D; sa.n_loop = n_loop;
+        sa.update = (update ? update : c->d_rtf_ones) + (size_t)f0 * c->K;
+        sa.X += (size_t)f0 * c->K * c->M; sa.Y += (size_t)f0 * c->K;
+        if (sa.pn) sa.pn += (size_t)f0 * c->K;
+        kernel = c->pf_on ? mvdr_solve_rtf_kernel_of<true>(Q, c->M == 4 * Q, n_sources) : mvdr_solve_rtf_kernel_of<false>(Q, c->M == 4 * Q, n_sources);
+    } else
+        kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
+                                   c->pf_on, &lds);
     if (!kernel) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
     auto launch = [&](long long pid0, long long n_prob, int pieces) {
         sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
@@ -422,7 +560,7 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
     const long long rem_wg = n_wg % 512;
     int pieces = 1;
     if (n_wg > 512 && rem_wg > 0 && rem_wg <= 128) {
-        while (pieces < 8 && rem_wg * pieces * 2 <= 512 && n_frames / (pieces * 2) >= 4) pieces *= 2;
+        while (pieces < 8 && rem_wg * pieces * 2 <= 512 && n_loop / (pieces * 2) >= 4) pieces *= 2;
     }
     t_begin(c, 1, st);
     if (pieces > 1 && n_wg > 512) {
@@ -435,6 +573,38 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
         launch(0, n_prob, 1);
     }
     t_end(c, st);
+    return MCA_HIP_OK;
+}
+
+// the target covariances and the steering plane (timing slot 5): X, T, the masks -> D, Psi, cpsi, cphi; between the analysis and the solve
+int launch_rtf(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float *update, const float *tmask, hipStream_t st, int f0, int n_loop)
+{
+    // a slot the call leaves out restarts from nothing learned; the kernel touches only the slots below n_sources
+    if (f0 == 0 && n_sources < c->max_sources) {
+        const size_t prow = (size_t)c->K * c->tri * sizeof(float2), crow = (size_t)c->K * 4;
+        VHIP_TRY(c, hipMemset2DAsync(reinterpret_cast<char *>(c->d_psi) + n_sources * prow, c->max_sources * prow, 0,
+                                     (c->max_sources - n_sources) * prow, (size_t)n_streams, st));
+        VHIP_TRY(c, hipMemset2DAsync(reinterpret_cast<char *>(c->d_cpsi) + n_sources * crow, c->max_sources * crow, 0,
+                                     (c->max_sources - n_sources) * crow, (size_t)n_streams, st));
+    }
+    MvdrRtfArgs ra{};
+    const size_t nph = (size_t)c->N / 64 + 33;
+    ra.X = c->d_X + (size_t)f0 * c->K * c->M; ra.T = c->d_T + (size_t)f0 * n_sources * c->M * nph;
+    ra.update = update ? update + (size_t)f0 * c->K : nullptr; ra.tmask = tmask ? tmask + (size_t)f0 * c->K : nullptr; ra.n_loop = n_loop;
+    ra.n_streams = n_streams; ra.n_frames = n_frames; ra.K = c->K; ra.M = c->M; ra.S = n_sources; ra.slots = c->max_sources;
+    ra.alpha = (float)c->cfg.alpha; ra.one_minus_alpha = (float)(1.0 - c->cfg.alpha);
+    ra.talpha = (float)c->rtf_alpha; ra.one_minus_talpha = (float)(1.0 - c->rtf_alpha);
+    ra.min_share = (float)c->rtf_min_share; ra.iterations = c->rtf_iterations; ra.ref_mic = c->rtf_ref;
+    ra.phi = c->d_phi; ra.trace = c->d_trace; ra.psi = c->d_psi; ra.cpsi = c->d_cpsi; ra.cphi_in = c->d_cphi; ra.cphi_out = c->d_cphi_next;
+    ra.D = c->d_D;
+    const int Q = (c->M + 3) / 4;
+    const void *kernel = mvdr_rtf_kernel(Q, false);
+    const long long n_prob = (long long)n_streams * n_sources * c->K;
+    void *kargs[1] = {&ra};
+    t_begin(c, 5, st);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)((n_prob + 63) / 64)), dim3(256), kargs, 0, st);
+    t_end(c, st);
+    VHIP_TRY(c, hipMemcpyAsync(c->d_cphi, c->d_cphi_next, (size_t)n_streams * c->K * 4, hipMemcpyDeviceToDevice, st));
     return MCA_HIP_OK;
 }
 
@@ -485,11 +655,14 @@ int launch_synth(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
 
 // a call with n_sources look directions per frame: doa_rad [streams][F][n_sources], out_pcm [streams][n_sources][F hop],
 // out_spec [streams][n_sources][F][K]; update: covariance update weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
+// rtf: the call of mca_hip_mvdr_sources_frames_rtf_*, tmask [streams][n_sources][F][K] or NULL (all 0), update its update mask
 int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
                     int n_frames, int n_sources, const float *doa_rad, const float *update, bool masked, float *out_pcm,
-                    float *out_spec, void *stream)
+                    float *out_spec, void *stream, const float *tmask = nullptr, bool rtf = false)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (rtf && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (rtf && c->null_gain != 0.0) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0");
     if (n_sources < 1 || n_sources > c->max_sources)
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
     if (!pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
@@ -504,12 +677,27 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     if (out_spec && (reinterpret_cast<uintptr_t>(out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !update);
+    // the steering plane of an RTF call holds fc frames: all of them, or as many as the workspace cap takes (how a stream is cut does not change bytes)
+    int fc = n_frames;
+    if (rtf) {
+        const size_t per_frame = (size_t)n_streams * n_sources * c->K * c->M;
+        if (per_frame * n_frames > c->plane_cap_cells) {
+            const int fmax = (int)std::max<size_t>(1, c->plane_cap_cells / per_frame), chunks = (n_frames + fmax - 1) / fmax;
+            fc = (n_frames + chunks - 1) / chunks;          // chunks of equal length, the last one shorter at most
+        }
+    }
+    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !update, rtf, (size_t)n_streams * fc);
     if (rc) return rc;
     // the beamformed spectra go straight to the caller's buffer when one is given
     float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : c->d_Y;
     if ((rc = launch_analyse(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, st))) return rc;
-    if ((rc = launch_solve(c, n_streams, n_frames, n_sources, update, masked, Y, st))) return rc;
+    if (rtf) {
+        for (int f0 = 0; f0 < n_frames; f0 += fc) {
+            const int n = std::min(fc, n_frames - f0);
+            if ((rc = launch_rtf(c, n_streams, n_frames, n_sources, update, tmask, st, f0, n))) return rc;
+            if ((rc = launch_solve(c, n_streams, n_frames, n_sources, update, masked, true, Y, st, f0, n))) return rc;
+        }
+    } else if ((rc = launch_solve(c, n_streams, n_frames, n_sources, update, masked, false, Y, st))) return rc;
     if (c->pf_on && (rc = launch_postfilter(c, n_streams, n_frames, n_sources, Y, st))) return rc;
     if (out_pcm && (rc = launch_synth(c, n_streams, n_frames, n_sources, Y, out_pcm, st))) return rc;
     VHIP_TRY(c, hipGetLastError());
@@ -518,7 +706,7 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
 
 // the host-pointer form: n_upd floats of weights per (stream, frame), 1 or K
 int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
-                     const float *update, bool masked, float *out_pcm, float *out_spec)
+                     const float *update, bool masked, float *out_pcm, float *out_spec, const float *tmask = nullptr, bool rtf = false)
 {
     if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
@@ -530,12 +718,14 @@ int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n
     float *d_spec = out_spec ? (float *)c->stage.get(3, nf * c->K * 8) : nullptr;
     const size_t nu = (size_t)n_streams * n_frames * (masked ? (size_t)c->K : 1);
     float *d_upd = update ? (float *)c->stage.get(masked ? 8 : 7, nu * 4) : nullptr;  // (slots 4 ... 6: the spectrum's; 8: the mask's own)
-    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd))
+    float *d_tm = tmask ? (float *)c->stage.get(9, nf * c->K * 4) : nullptr;        // [streams][n_sources][F][K]
+    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd) || (tmask && !d_tm))
         return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    if (tmask) VHIP_TRY(c, hipMemcpy(d_tm, tmask, nf * c->K * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
     if (update) VHIP_TRY(c, hipMemcpy(d_upd, update, nu * 4, hipMemcpyHostToDevice));
-    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, masked, d_out, d_spec, nullptr);
+    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, masked, d_out, d_spec, nullptr, d_tm, rtf);
     if (rc) return rc;
     VHIP_TRY(c, hipDeviceSynchronize());
     if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
@@ -558,6 +748,21 @@ int mca_hip_mvdr_sources_frames_masked_dev(mca_hip_mvdr_ctx *c, const float *pcm
                                            float *out_spec, void *stream)
 {
     return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, stream);
+}
+
+// update_mask [streams][F][K] or NULL (all 1), target_mask [streams][n_sources][F][K] or NULL (all 0)
+int mca_hip_mvdr_sources_frames_rtf_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                        int n_frames, int n_sources, const float *doa_rad, const float *update_mask, const float *target_mask,
+                                        float *out_pcm, float *out_spec, void *stream)
+{
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, stream, target_mask, true);
+}
+
+int mca_hip_mvdr_sources_frames_rtf_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                                         const float *update_mask, const float *target_mask, float *out_pcm, float *out_spec)
+{
+    if (c && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, target_mask, true);
 }
 
 int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
@@ -736,6 +941,85 @@ int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *c, int s, int source, double *out, double *norm)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!out && !norm) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out and norm are both NULL");
+    if (!c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
+    if (source < 0 || source >= c->max_sources) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "source outside [0, max_sources)");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());
+    const size_t slot = (size_t)s * c->max_sources + source;
+    const int M = c->M;
+    if (out) {
+        std::vector<float2> h((size_t)c->K * c->tri);
+        VHIP_TRY(c, hipMemcpy(h.data(), c->d_psi + slot * c->K * c->tri, h.size() * sizeof(float2), hipMemcpyDeviceToHost));
+        for (int k = 0; k < c->K; ++k)
+            for (int i = 0; i < M; ++i)
+                for (int j = 0; j <= i; ++j) {
+                    const float2 v = h[(size_t)k * c->tri + i * (i + 1) / 2 + j];
+                    double *lo = out + (((size_t)k * M + i) * M + j) * 2, *up = out + (((size_t)k * M + j) * M + i) * 2;
+                    lo[0] = v.x; lo[1] = i == j ? 0.0 : v.y;
+                    up[0] = v.x; up[1] = i == j ? 0.0 : -(double)v.y;
+                }
+    }
+    if (norm) {
+        std::vector<float> h((size_t)c->K);
+        VHIP_TRY(c, hipMemcpy(h.data(), c->d_cpsi + slot * c->K, h.size() * 4, hipMemcpyDeviceToHost));
+        for (int k = 0; k < c->K; ++k) norm[k] = h[k];
+    }
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa_rad, double *out, unsigned char *estimated)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!out && !estimated) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out and estimated are both NULL");
+    if (!c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
+    if (source < 0 || source >= c->max_sources) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "source outside [0, max_sources)");
+    if (!std::isfinite(doa_rad)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is not finite");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());
+    // the factored phasors of the look direction, as the analysis forms them (MvdrAnalyseArgs::T), the phase in double
+    const int M = c->M, K = c->K, nhi = c->N / 64 + 1, nph = nhi + 32;
+    std::vector<double> mx(M);
+    VHIP_TRY(c, hipMemcpy(mx.data(), c->d_micx, (size_t)M * 8, hipMemcpyDeviceToHost));
+    std::vector<float2> T((size_t)M * nph);
+    const double unit = (double)c->cfg.sample_rate / (double)c->N / 346.1, cd = std::cos(doa_rad + M_PI / 2);
+    for (int m = 0; m < M; ++m)
+        for (int e = 0; e < nph; ++e) {
+            double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * (unit * mx[m] * cd);
+            t -= std::rint(t);
+            T[(size_t)m * nph + e] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
+        }
+    const size_t tb = T.size() * sizeof(float2), ob = (size_t)K * M * sizeof(float2);
+    char *buf = nullptr;                                        // T, the vectors, the flags
+    VHIP_TRY(c, hipMalloc((void **)&buf, tb + ob + (size_t)K));
+    MvdrRtfSteerArgs ga{};
+    const size_t slot = (size_t)s * c->max_sources + source;
+    ga.phi = c->d_phi + (size_t)s * K * c->tri; ga.psi = c->d_psi + slot * K * c->tri;
+    ga.cpsi = c->d_cpsi + slot * K; ga.cphi = c->d_cphi + (size_t)s * K;
+    ga.T = reinterpret_cast<float2 *>(buf); ga.K = K; ga.M = M;
+    ga.min_share = (float)c->rtf_min_share; ga.iterations = c->rtf_iterations; ga.ref_mic = c->rtf_ref;
+    ga.out = reinterpret_cast<float2 *>(buf + tb); ga.estimated = reinterpret_cast<unsigned char *>(buf + tb + ob);
+    std::vector<float2> h((size_t)K * M);
+    std::vector<unsigned char> he((size_t)K);
+    const int Q = (M + 3) / 4;
+    void *kargs[1] = {&ga};
+    hipError_t e = hipMemcpy(buf, T.data(), tb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipLaunchKernel(mvdr_rtf_kernel(Q, true), dim3((unsigned)((K + 63) / 64)), dim3(256), kargs, 0, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), buf + tb, ob, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(he.data(), buf + tb + ob, (size_t)K, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return vfail(c, MCA_HIP_ERR_HIP, std::string("steering vectors: ") + hipGetErrorString(e));
+    if (out)
+        for (size_t i = 0; i < h.size(); ++i) { out[2 * i] = h[i].x; out[2 * i + 1] = h[i].y; }
+    if (estimated) std::memcpy(estimated, he.data(), (size_t)K);
+    return MCA_HIP_OK;
+}
+
 extern "C++" {
 namespace {
 constexpr unsigned MVDR_MAGIC = 0x4d435644u;   // "MCVD"
@@ -744,6 +1028,11 @@ std::vector<BlobPart> mvdr_parts(mca_hip_mvdr_ctx *c)
     const size_t ns = (size_t)c->cfg.max_streams;
     std::vector<BlobPart> parts{{c->d_phi, ns * c->K * c->tri * sizeof(float2)}, {c->d_trace, ns * c->K * 4}, {c->d_tail[c->tail_cur], ns * c->max_sources * c->H * 4}};
     if (c->pf_on) parts.push_back({c->d_pf_A, ns * c->max_sources * c->K * 4});
+    if (c->rtf_on) {
+        parts.push_back({c->d_psi, ns * c->max_sources * c->K * c->tri * sizeof(float2)});
+        parts.push_back({c->d_cpsi, ns * c->max_sources * c->K * 4});
+        parts.push_back({c->d_cphi, ns * c->K * 4});
+    }
     return parts;
 }
 unsigned mvdr_cfg_hash(const mca_hip_mvdr_ctx *c)
@@ -770,6 +1059,8 @@ int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *c, void *blob, long long bytes)
     // version 3: a context with the post-filter enabled -- the same and A behind the tails, the maximum in host[0], 1 in host[1]
     BlobHeader h{MVDR_MAGIC, c->max_sources > 1 ? 2 : 1, mvdr_cfg_hash(c), 0, {c->max_sources > 1 ? c->max_sources : 0, 0, 0, 0}};
     if (c->pf_on) { h.version = 3; h.host[0] = c->max_sources; h.host[1] = 1; }
+    // version 4: a context with RTF enabled -- the same (A only with the post-filter, 1 in host[1] then), Psi, cpsi and cphi behind it, 1 in host[2]
+    if (c->rtf_on) { h.version = 4; h.host[0] = c->max_sources; h.host[1] = c->pf_on ? 1 : 0; h.host[2] = 1; }
     const int rc = blob_save(mvdr_parts(c), h, blob, bytes);
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
@@ -781,15 +1072,19 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long byt
     BlobHeader h;
     if (blob && bytes >= (long long)sizeof(BlobHeader)) {
         std::memcpy(&h, blob, sizeof(h));
-        const int blob_max = h.version == 2 || h.version == 3 ? (int)h.host[0] : 1;
-        if (h.magic == MVDR_MAGIC && h.version >= 1 && h.version <= 3 && (h.version == 3) != c->pf_on)
-            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, h.version == 3 ? "state blob was saved with the post-filter enabled, this context has it disabled"
-                                                                         : "state blob was saved without the post-filter, this context has it enabled");
-        if (h.magic == MVDR_MAGIC && h.version >= 1 && h.version <= 3 && blob_max != c->max_sources)
+        const int blob_max = h.version >= 2 && h.version <= 4 ? (int)h.host[0] : 1;
+        const bool blob_pf = h.version == 3 || (h.version == 4 && h.host[1] != 0), known = h.magic == MVDR_MAGIC && h.version >= 1 && h.version <= 4;
+        if (known && (h.version == 4) != c->rtf_on)
+            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, h.version == 4 ? "state blob was saved with RTF enabled, this context has it disabled"
+                                                                         : "state blob was saved without RTF, this context has it enabled");
+        if (known && blob_pf != c->pf_on)
+            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, blob_pf ? "state blob was saved with the post-filter enabled, this context has it disabled"
+                                                                  : "state blob was saved without the post-filter, this context has it enabled");
+        if (known && blob_max != c->max_sources)
             return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with max_sources = " + std::to_string(blob_max) +
                                                               ", this one has " + std::to_string(c->max_sources));
     }
-    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1);
+    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->rtf_on ? 4 : c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1);
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
 
@@ -802,7 +1097,7 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id >= (c->pf_ever ? 5 : 4)) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c || kernel_id < 0 || kernel_id > 5 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever)) return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));
         float ms = 0.f;

@@ -80,6 +80,12 @@ template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, Mvdr
 template <MvdrWeight WEIGHT, bool NOISE> const void *mvdr_solve_kernel_of(int Q, bool full, int S, bool nulls, int *lds_bytes);
 // the solve kernel of a call with Q row slots, M == 4 Q (full), S look directions, ...; its dynamic LDS; nullptr: not in the build
 const void *mvdr_solve_kernel(int Q, bool full, int S, bool nulls, MvdrWeight w, bool noise, int *lds_bytes);
+// the solve with the right-hand sides from the steering plane of k_mvdr_rtf (mvdr_solve.h; kernels_mvdr_solve_rtf*.hip)
+template <int Q, bool FULL, int S, int S1, bool PF, bool NOISE> __global__ void k_mvdr_solve_rtf_t(MvdrSolveArgs p);
+template <bool NOISE> const void *mvdr_solve_rtf_kernel_of(int Q, bool full, int S);
+template <int Q> __global__ void k_mvdr_rtf(MvdrRtfArgs p);                     // target covariances and estimated steering vectors
+template <int Q> __global__ void k_mvdr_rtf_steering(MvdrRtfSteerArgs p);
+const void *mvdr_rtf_kernel(int Q, bool steering);                              // kernels_mvdr_rtf.hip
 __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                                   // decision-directed Wiener gain on the solve's output
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance

@@ -488,6 +488,44 @@ struct MvdrSolveArgs {
     const float *update;      // WEIGHT = FRAME: [streams][n_frames]; CELL: [streams][n_frames][K]; NONE: not read
     float null_gain;          // NULLS: > 0, gain of the soft nulls at the other look directions
     float *pn;                // NOISE: [streams][S][n_frames][K] fp32, 1 / (d_s^H PhiL^-1 d_s) of every output, 0 = silent
+    // k_mvdr_solve_rtf_t: [streams][S][n_loop][K][M] steering vectors (MvdrRtfArgs::D), T is not read; the launch walks n_loop frames of
+    // a call of n_frames (a call whose plane exceeds the workspace cap is cut along the frames: X, update, Y and pn then point at the
+    // chunk's first frame and keep n_frames as their stride)
+    const float2 *D; int n_loop;
+};
+
+// k_mvdr_rtf<Q> (kernels_mvdr_rtf.hip): the target covariances Psi and the steering vectors estimated from them,
+// between the analysis and the solve.  One quad per (stream, slot, bin), the layout of the solve.
+struct MvdrRtfArgs {
+    const float2 *X;          // [streams][n_frames][K][M]
+    const float2 *T;          // [streams][n_frames][S][M][nhi + 32] (MvdrAnalyseArgs): the geometric vectors, start and fallback
+    const float *update;      // [streams][n_frames][K] update mask of the noise covariance, or NULL (all 1)
+    const float *tmask;       // [streams][S][n_frames][K] target masks, or NULL (all 0)
+    int n_streams, n_frames, K, M;
+    int n_loop;               // frames this launch walks (<= n_frames: X, T and the masks point at the chunk's first frame, stride n_frames)
+    int S, slots;             // look directions of the call; slots per stream in the context (>= S)
+    float alpha, one_minus_alpha;             // of the noise covariance (MvdrSolveArgs)
+    float talpha, one_minus_talpha;           // of the target covariance
+    float min_share;
+    int iterations, ref_mic;
+    const float2 *phi;        // [streams][K][tri] noise covariance at entry (read only: the solve behind this kernel advances it)
+    const float *trace;       // [streams][K]
+    float2 *psi;              // [streams][slots][K][tri] target covariances, read and written
+    float *cpsi;              // [streams][slots][K] sum of the weights in Psi
+    const float *cphi_in;     // [streams][K] sum of the weights in Phi at entry; every slot's quad reads it, so the exit value goes to
+    float *cphi_out;          // a second buffer (slot 0 writes it) and the host swaps the two
+    float2 *D;                // [streams][S][n_loop][K][M]
+};
+// k_mvdr_rtf_steering<Q>: the estimator alone on the held state of one stream and slot (mca_hip_mvdr_get_steering)
+struct MvdrRtfSteerArgs {
+    const float2 *phi, *psi;  // [K][tri] of the stream, of the stream and slot
+    const float *cpsi, *cphi; // [K]
+    const float2 *T;          // [M][nhi + 32] factored phasors of the look direction
+    int K, M;
+    float min_share;
+    int iterations, ref_mic;
+    float2 *out;              // [K][M]
+    unsigned char *estimated; // [K]
 };
 
 // ---- the instantiations of the MVDR solve (mvdr_solve.h) ----

@@ -1,4 +1,5 @@
-// mvdr_solve.h -- k_mvdr_solve_t, the one template of the MVDR solve (gfx950), and the lookup that instantiates it.
+// mvdr_solve.h -- k_mvdr_solve_t, the one template of the MVDR solve (gfx950), its arm k_mvdr_solve_rtf_t that takes the
+// steering vectors from a plane (4.8), and the lookups that instantiate them.
 // The translation units kernels_mvdr_solve_*.hip instantiate one (WEIGHT, NOISE) group each (build parallelism, nothing else); the
 // hand-written single-look kernel k_mvdr_solve of kernels_mvdr.hip shares the helpers below.
 //
@@ -99,10 +100,14 @@ __device__ __forceinline__ void mvdr_steer_rows(float2 (&d)[Q], const float2 *T,
 
 namespace mca {
 
-// grid (ceil(problems / 64) * pieces), 256 threads, dynamic LDS mvdr_nulls_lds_bytes (NULLS) or none
-template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, MvdrWeight WEIGHT, bool NOISE>
-__global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
+// The body of the solve kernels.  RTF: the right-hand sides of the S look directions are not formed from the factored
+// phasors T but read from the steering plane D [stream][slot][frame][bin][mic] that k_mvdr_rtf (kernels_mvdr_rtf.hip) wrote -- the
+// way X is read -- and so is the vector of the silence branch (k_mvdr_rtf leaves the geometric vector in the cells of a silent bin).
+// Nothing else differs: a plane that holds cmul(T_hi, T_lo) gives the bits of the kernel without RTF.
+template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, MvdrWeight WEIGHT, bool NOISE, bool RTF>
+__device__ __forceinline__ void mvdr_solve_body(const MvdrSolveArgs &p)
 {
+    static_assert(!RTF || (!NULLS && WEIGHT == MvdrWeight::CELL), "the steering plane comes with the masks; nulls at estimated vectors are not built");
     constexpr bool WEIGHTED = WEIGHT != MvdrWeight::NONE, CELL = WEIGHT == MvdrWeight::CELL;
     static_assert(!REUSE || WEIGHT == MvdrWeight::FRAME, "no frame is frozen without weights; a wave of quads with weights of their own would run both column bodies");
     static_assert(S >= 1 && S <= MCA_MAX_SOURCES && S1 >= 1 && S % S1 == 0, "look directions per frame, in whole passes");
@@ -118,8 +123,9 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
     float *Ds = reinterpret_cast<float *>(Ns + S * 256);    // [s][thread]: den
     const int tid = threadIdx.x, l = tid & 3;
     const int M = p.M, K = p.K, F = p.n_frames;
+    const int FL = RTF ? p.n_loop : F;          // frames of the launch (RTF: a chunk of the call, F stays the stride of X, update, Y, pn)
     const int piece = (int)(blockIdx.x % (unsigned)p.pieces);
-    const int t_first = (int)((long long)piece * F / p.pieces), t_last = (int)((long long)(piece + 1) * F / p.pieces);   // frames this workgroup solves
+    const int t_first = (int)((long long)piece * FL / p.pieces), t_last = (int)((long long)(piece + 1) * FL / p.pieces);   // frames this workgroup solves
     const long long total = p.pid0 + p.n_prob;
     const long long pid = p.pid0 + (long long)(blockIdx.x / (unsigned)p.pieces) * 64 + (tid >> 2);
     const bool pv = pid < total;
@@ -147,6 +153,15 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
     const int uw0 = CELL ? 0 : a * F;                                       // + t: the weight of the frame, the same for the four lanes (< 2^31: T is larger)
     const float *um = CELL ? p.update + ((long long)a * F * K + k) : nullptr;     // + t K: the weight of the cell (64-bit index), the same for the four lanes
     float2 *yo = p.Y + (long long)a * S * F * K + k;                        // + (s F + t) K
+    const float2 *Dp = RTF ? p.D + ((long long)a * S * FL * K + k) * M + l : nullptr;   // RTF: + ((s FL + t) K) M + 4 q
+    // the steering vector of look direction s in frame t, the rows of this lane
+    auto steer = [&](float2 (&d)[Q], int t, int s) __attribute__((always_inline)) {
+        if constexpr (RTF) {
+            const float2 *dq = Dp + ((long long)s * FL + t) * fstride;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) d[q] = (FULL || 4 * q + l < M) ? dq[4 * q] : make_float2(0.f, 0.f);
+        } else mvdr_steer_rows<Q, FULL>(d, T, (long long)t * S + s, M, nph, lo_off, l);
+    };
     float *pno = NOISE ? p.pn : nullptr;                                   // NOISE: the same index
     if constexpr (NOISE) pno += (long long)a * S * F * K + k;
 
@@ -168,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
         for (int q = 0; q < Q; ++q) x[q] = PF ? xn[q] : ((FULL || 4 * q + l < M) ? X[(long long)t * fstride + 4 * q] : make_float2(0.f, 0.f));
         if (t >= t_first) {
 #pragma unroll
-            for (int s = 0; s < S1; ++s) mvdr_steer_rows<Q, FULL>(rd[s], T, (long long)t * S + s, M, nph, lo_off, l);
+            for (int s = 0; s < S1; ++s) steer(rd[s], t, s);
         }
         if constexpr (PF) {
 #pragma unroll
@@ -304,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
 #pragma unroll
                 for (int s = 0; s < S1; ++s) {
                     float2 d[Q];
-                    mvdr_steer_rows<Q, FULL>(d, T, (long long)t * S + s0 + s, M, nph, lo_off, l);
+                    steer(d, t, s0 + s);
                     float2 acc = make_float2(0.f, 0.f);
 #pragma unroll
                     for (int q = 0; q < Q; ++q) acc = cmacc(acc, xr[q], d[q]);   // conj(d_i) x_i
@@ -340,7 +355,7 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
                 for (int q = 0; q < Q; ++q) rx[q] = (FULL || 4 * q + l < M) ? X[(long long)t * fstride + 4 * q] : make_float2(0.f, 0.f);
             }
 #pragma unroll
-            for (int s = 0; s < S1; ++s) mvdr_steer_rows<Q, FULL>(rd[s], T, (long long)t * S + s0 + s, M, nph, lo_off, l);
+            for (int s = 0; s < S1; ++s) steer(rd[s], t, s0 + s);
         }
         if constexpr (NULLS) {
             if (silent) continue;
@@ -397,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
             }
         }
     }
-    if (pv && t_last == F) {
+    if (pv && t_last == FL) {
         float2 *so = p.phi_out + (pc - p.out_base) * tri;
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
@@ -408,6 +423,20 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
         }
         if (l == 0) p.trace_out[pc - p.out_base] = tr;
     }
+}
+
+// grid (ceil(problems / 64) * pieces), 256 threads, dynamic LDS mvdr_nulls_lds_bytes (NULLS) or none
+template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, MvdrWeight WEIGHT, bool NOISE>
+__global__ __launch_bounds__(256, 2) void k_mvdr_solve_t(MvdrSolveArgs p)
+{
+    mvdr_solve_body<Q, FULL, S, S1, PF, NULLS, REUSE, WEIGHT, NOISE, false>(p);
+}
+
+// the same with the right-hand sides from the steering plane; a weight per frame and bin, no nulls (mca_hip_mvdr_sources_frames_rtf_*)
+template <int Q, bool FULL, int S, int S1, bool PF, bool NOISE>
+__global__ __launch_bounds__(256, 2) void k_mvdr_solve_rtf_t(MvdrSolveArgs p)
+{
+    mvdr_solve_body<Q, FULL, S, S1, PF, false, false, MvdrWeight::CELL, NOISE, true>(p);
 }
 
 // The instantiation of a call, or nullptr where the build has none, and the dynamic LDS of its workgroups.  The definition is the
@@ -427,6 +456,20 @@ const void *mvdr_solve_kernel_of(int Q, bool full, int S, bool nulls, int *lds_b
                 *lds_bytes = RNULLS ? mvdr_nulls_lds_bytes(RQ, RS, f.S1) : 0;
             }
         }
+    });
+    return kernel;
+}
+
+// The same for k_mvdr_solve_rtf_t: every (Q, FULL, S) row without NULLS, with the form of the CELL row.
+template <bool NOISE>
+const void *mvdr_solve_rtf_kernel_of(int Q, bool full, int S)
+{
+    const void *kernel = nullptr;
+    mvdr_static_for<0, 4 * 2 * MCA_MAX_SOURCES>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, RQ = r / (2 * MCA_MAX_SOURCES) + 1, RS = r / 2 % MCA_MAX_SOURCES + 1;
+        constexpr bool RFULL = r & 1;
+        constexpr MvdrSolveForm f = mvdr_solve_form(RQ, RFULL, RS, false, MvdrWeight::CELL, NOISE);
+        if (Q == RQ && full == RFULL && S == RS) kernel = reinterpret_cast<const void *>(k_mvdr_solve_rtf_t<RQ, RFULL, RS, f.S1, f.PF, NOISE>);
     });
     return kernel;
 }

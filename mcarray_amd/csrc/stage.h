@@ -7,7 +7,7 @@
 namespace mca {
 
 struct StagePool {
-    static constexpr int N = 9;           // (slot 8: the update mask of the MVDR host calls)
+    static constexpr int N = 10;          // (slots 8, 9: the update mask and the target masks of the MVDR host calls)
     void *p[N] = {};
     size_t cap[N] = {};
     // returns a device buffer of at least `bytes` bytes for slot i (nullptr on allocation failure or bytes == 0)

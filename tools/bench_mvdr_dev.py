@@ -13,7 +13,9 @@ tests/mvdr_postfilter_twin.py on the scale of the twin's unfiltered audio (DESIG
 instead, one JSON line per row: for one and for three look directions the unweighted call, the per-frame weighted call (every second
 run of 8 frames frozen) and the masked call (update_mask [streams][F][K]) under a mask of ones, that per-frame pattern along the
 bins, blocks of 4 frames x 16 bins half of them open, and independent random binary cells (the worst divergence of the quads of a
-wave); a build without the masked entry points (MCA_HIP_LIB) runs the first two rows only.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+wave); a build without the masked entry points (MCA_HIP_LIB) runs the first two rows only.  --rtf times the table of DESIGN.md 4.8, one
+JSON line for one and one for two look directions: k_mvdr_rtf, the solve that reads the steering plane beside the masked (CELL) solve
+under the same update mask, and both calls' totals; update mask and target masks are complementary blocks of 4 frames x 16 bins.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
 points it lacks are left unbound, --null-gain must then stay 0, --update none and --postfilter off (as far as the build lacks them)."""
 import argparse
 import json
@@ -80,6 +82,46 @@ def mask_table(a, fs, N, xs, pcm, st):
             bf.close()
 
 
+def rtf_table(a, fs, N, xs, pcm, st):
+    """the rows of DESIGN.md 4.8: the masked call and the RTF call under the same update mask, for one and two look directions"""
+    hop, K = N // 2, N // 2 + 1
+    dev = pcm.device
+    rng = np.random.default_rng(7)
+    for S in (1, 2):
+        blocks = (rng.random((a.streams, S, (a.frames + 3) // 4, (K + 15) // 16)) < 0.5 / S).astype(np.float32)
+        tm = np.ascontiguousarray(np.repeat(np.repeat(blocks, 4, axis=2), 16, axis=3)[:, :, :a.frames, :K])       # the targets' cells
+        upd = torch.from_numpy(np.ascontiguousarray(1.0 - tm.max(axis=1))).to(dev)                                  # the noise learns elsewhere
+        tmask = torch.from_numpy(tm).to(dev)
+        look = torch.tensor(LOOK[:S], device=dev, dtype=torch.float32)
+        doa = look[None, None, :].expand(a.streams, a.frames, S).contiguous()
+        out = torch.empty((a.streams, S, a.frames * hop), device=dev, dtype=torch.float32)
+        row = dict(sources=S, postfilter=bool(a.postfilter), workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N),
+                   steering_plane_MB=a.streams * S * a.frames * K * a.mics * 8 / 1e6)
+        for name, kw in (("masked", dict(update_mask=upd)), ("rtf", dict(update_mask=upd, target_mask=tmask))):
+            bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=S)
+            if a.postfilter:
+                bf.set_postfilter(True)
+            if name == "rtf":
+                bf.set_rtf(True)
+            step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **kw)
+            for _ in range(a.warmup):
+                step()
+            bf.set_timing(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                step()
+            torch.cuda.synchronize()
+            row[name + "_ms_per_step"] = (time.perf_counter() - t0) / a.steps * 1e3
+            n, ms = bf.get_timing(bf.K_SOLVE)
+            row[("k_mvdr_solve_cell" if name == "masked" else "k_mvdr_solve_rtf") + "_ms"] = ms / max(n, 1)
+            if name == "rtf":
+                n, ms = bf.get_timing(bf.K_RTF)
+                row["k_mvdr_rtf_ms"] = ms / max(n, 1)
+            bf.close()
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -93,6 +135,7 @@ def main():
     ap.add_argument("--update", choices=["none", "ones", "half"], default="none", help="covariance update weights of the call")
     ap.add_argument("--postfilter", action="store_true", help="enable the Wiener post-filter (its defaults)")
     ap.add_argument("--mask", action="store_true", help="time the table of the time-frequency update masks (DESIGN.md 4.7)")
+    ap.add_argument("--rtf", action="store_true", help="time the table of the estimated steering vectors (DESIGN.md 4.8)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -111,6 +154,8 @@ def main():
     st = torch.cuda.current_stream().cuda_stream
     if a.mask:
         return mask_table(a, fs, N, xs, pcm, st)
+    if a.rtf:
+        return rtf_table(a, fs, N, xs, pcm, st)
     upd = None
     if a.update != "none":
         w = np.ones((a.streams, a.frames), dtype=np.float32)
