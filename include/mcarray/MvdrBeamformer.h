@@ -126,6 +126,34 @@ public:
         estimated.resize(static_cast<size_t>(_N / 2 + 1));
         check(mca_hip_mvdr_get_steering(_ctx, 0, source, doaRadians, d.data(), estimated.data()));
     }
+    // Masks estimated on the device from the chunk's own spectra (mca_hip_mvdr_set_mask_estimator): every cell goes to the look
+    // direction of setDOA() / setDOAs() whose steering vector explains it best, and the winner's steered coherence between
+    // coherenceLo and coherenceHi becomes its target mask; the first nProtected directions (0: all) close the noise covariance where
+    // they win, the others are competitors.  The band of bins [binLo, binHi] (-1: N/2); outside it the plain recursion.  A single
+    // look direction needs absolute thresholds such as 0.2 / 0.4.  The processAuto() calls use it; it holds no state.
+    void setMaskEstimator(bool enable, int binLo = 0, int binHi = -1, double coherenceLo = 0.0, double coherenceHi = 0.05, int nProtected = 0)
+    {
+        mca_hip_mvdr_estmask_config cfg;
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.enable = enable ? 1 : 0;
+        cfg.bin_lo = binLo;
+        cfg.bin_hi = binHi < 0 ? _N / 2 : binHi;
+        cfg.coherence_lo = coherenceLo;
+        cfg.coherence_hi = coherenceHi;
+        cfg.n_protected = nProtected;
+        check(mca_hip_mvdr_set_mask_estimator(_ctx, &cfg));
+    }
+    void getMaskEstimator(bool &enable, int &binLo, int &binHi, double &coherenceLo, double &coherenceHi, int &nProtected) const
+    {
+        mca_hip_mvdr_estmask_config cfg;
+        check(mca_hip_mvdr_get_mask_estimator(_ctx, &cfg));
+        enable = cfg.enable != 0;
+        binLo = cfg.bin_lo;
+        binHi = cfg.bin_hi;
+        coherenceLo = cfg.coherence_lo;
+        coherenceHi = cfg.coherence_hi;
+        nProtected = cfg.n_protected;
+    }
     // The Capon spatial spectrum of the covariance the stream holds, and its peaks (mca_hip_mvdr_spectrum_*): nAngles 2 ... 361 from
     // -pi/2 to pi/2, the band of bins [binLo, binHi], weighting MCA_HIP_MVDR_SPECTRUM_POWER / _NORMALISED, nPeaks 1 ... 4.  The peak
     // angles are look directions as setDOAs() takes them: process a chunk, read peaks(), setDOAs() for the next chunk.
@@ -253,6 +281,44 @@ public:
         for (int t = 0; t < F; ++t)
             for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
         check(mca_hip_mvdr_sources_frames_rtf_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMask, targetMask, audio.data(), nullptr));
+        for (int s = 0; s < S; ++s)
+            for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
+        consume(F);
+        return F * hop;
+    }
+
+    // process() with masks estimated from the chunk's spectra (setMaskEstimator(true) first; mca_hip_mvdr_sources_frames_auto_*): with
+    // setRtf(true) the call continues as processRtf() does with the two masks, else as process() does with the update mask.
+    // updateMaskOut [framesCompletedBy(nSamples)][N/2 + 1] and targetMaskOut [look directions][framesCompletedBy(nSamples)][N/2 + 1]
+    // receive the masks; either may be nullptr.
+    template <typename Tin, typename Tout>
+    int processAuto(const std::vector<Tin *> &in, int nSamples, Tout *out, int outSize, float *updateMaskOut = nullptr, float *targetMaskOut = nullptr)
+    {
+        const int hop = _N / 2;
+        const int F = pend(in, nSamples);
+        if (F == 0) return 0;
+        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
+        std::vector<float> pcm = frames(F);
+        std::vector<float> doa(static_cast<size_t>(F), static_cast<float>(_doa)), audio(static_cast<size_t>(F) * static_cast<size_t>(hop));
+        check(mca_hip_mvdr_sources_frames_auto_host(_ctx, pcm.data(), 1, F, 1, doa.data(), updateMaskOut, targetMaskOut, audio.data(), nullptr));
+        for (int i = 0; i < F * hop; ++i) out[i] = static_cast<Tout>(audio[static_cast<size_t>(i)]);
+        consume(F);
+        return F * hop;
+    }
+    template <typename Tin, typename Tout>
+    int processAuto(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize, float *updateMaskOut = nullptr, float *targetMaskOut = nullptr)
+    {
+        const int hop = _N / 2, S = static_cast<int>(_doas.size());
+        if (S == 0) throw MCArrayException("processAuto: setDOAs() first");
+        if (static_cast<int>(out.size()) < S) throw MCArrayException("processAuto: one output pointer per look direction of setDOAs()");
+        const int F = pend(in, nSamples);
+        if (F == 0) return 0;
+        if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
+        std::vector<float> pcm = frames(F);
+        std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
+        for (int t = 0; t < F; ++t)
+            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+        check(mca_hip_mvdr_sources_frames_auto_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMaskOut, targetMaskOut, audio.data(), nullptr));
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
         consume(F);

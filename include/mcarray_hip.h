@@ -787,6 +787,55 @@ int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *ctx, int stream_index, int sourc
 /* copy of the target covariance of one stream and slot: out [K][M][M] interleaved re,im double (full Hermitian matrices), norm [K]
  * double (cpsi); either may be NULL, not both */
 int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, int source, double *out, double *norm);
+/* Masks estimated on the device from the call's own spectra: the update mask of the masked call and the target masks of the RTF
+ * call, formed by the steered coherence of every cell towards the call's look directions, between the analysis and the rest of the
+ * call (k_mvdr_estmask).  No second transform, no host step: the look directions may be the peaks the Capon spectrum
+ * returned for the chunk before.  Per stream a, frame t and bin k, with x the frame's M spectra of that bin, g_s the
+ * geometric steering vector of doa_rad[a][t][s] as everywhere in this module, and S the call's n_sources:
+ *     e    = sum_m |x_m|^2
+ *     c_s  = |g_s^H x|^2 / (M e)                 in [0, 1]; 0 for every s where e <= 1e-30
+ *     w    = the s with the largest c_s, searched s = 0 ... S-1 with a strict '>' (ties and NaNs stay with the lower index)
+ *     v    = fminf(fmaxf((c_w - coherence_lo) / (coherence_hi - coherence_lo), 0), 1)        (a NaN counts as 0)
+ *     target_mask[a][s][t][k] = v if s == w, else 0
+ *     update_mask[a][t][k]    = 1 - max over s < P of target_mask[a][s][t][k]
+ *                               P = n_protected, or S where n_protected is 0 or above S
+ * Outside the band [bin_lo, bin_hi] every target mask is 0 and the update mask is 1: the plain recursion, meant for the lowest bins,
+ * where all steering vectors coincide and the assignment means nothing.  Look directions s >= P are competitors: directions of known
+ * interferers (further Capon peaks, say) that take cells away from the protected sources and get their own target mask and output,
+ * but do not close the noise covariance.  The estimator is stateless: the masks of bin k of frame t depend on that cell's spectra
+ * and on the frame's look directions only; nothing is added to the stream state or to state blobs.
+ * Accepted, all finite: 0 <= bin_lo <= bin_hi <= N/2 (defaults 0 and N/2); 0 <= coherence_lo < coherence_hi <= 1 with
+ * coherence_hi - coherence_lo >= 1e-3 (defaults 0 and 0.05: RELATIVE thresholds, for calls in which a competitor takes the cells
+ * that are not the target's -- a call with ONE look direction has no competitor and needs absolute thresholds such as 0.2 / 0.4);
+ * n_protected 0 ... 4 (default 0: all).  Anything else, a wrong struct_size included, is MCA_HIP_ERR_INVALID_ARGUMENT and leaves the
+ * configuration as it was.  The values are processing parameters like the null gain; enable allocates (with the first call, growing
+ * with the call's shape) or frees the mask workspace, and opens timing slot 6.
+ *   update_mask_out_dev [streams][F][K] float                 contiguous; NULL: the mask lives in the workspace only
+ *   target_mask_out_dev [streams][n_sources][F][K] float      contiguous; NULL likewise
+ * mca_hip_mvdr_sources_frames_auto_* runs the analysis once, the estimator over the whole call, and then
+ *   - on a context with RTF enabled exactly what mca_hip_mvdr_sources_frames_rtf_* does with these two masks, the cut along the frames
+ *     under the workspace cap included (the masks are formed once ahead of the chunks, as the analysis is);
+ *   - on a context without RTF exactly what mca_hip_mvdr_sources_frames_masked_* does with the update mask (the target masks are
+ *     still written if asked for).
+ * The bytes of spectra, audio and state are those of that call fed the masks this one returns.  Without the estimator enabled the
+ * call is MCA_HIP_ERR_INVALID_ARGUMENT; whatever the underlying call refuses is refused with that call's code (a null gain with RTF:
+ * MCA_HIP_ERR_UNSUPPORTED).  The seven other mca_hip_mvdr_*frames* calls are untouched on any context: the same kernels launched, the
+ * same bytes.  The host call stages the masks it hands back. */
+typedef struct {
+    int struct_size;
+    int enable;
+    int bin_lo, bin_hi;      /* the band, both ends included */
+    double coherence_lo;
+    double coherence_hi;
+    int n_protected;
+} mca_hip_mvdr_estmask_config;
+int mca_hip_mvdr_set_mask_estimator(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_estmask_config *cfg);
+int mca_hip_mvdr_get_mask_estimator(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_estmask_config *cfg);
+int mca_hip_mvdr_sources_frames_auto_dev(mca_hip_mvdr_ctx *ctx, const float *pcm_dev, long long stream_stride, long long mic_stride,
+                                         int n_streams, int n_frames, int n_sources, const float *doa_rad_dev,
+                                         float *update_mask_out_dev, float *target_mask_out_dev, float *out_pcm_dev, float *out_spec_dev, void *stream);
+int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
+                                          const float *doa_rad, float *update_mask_out, float *target_mask_out, float *out_pcm, float *out_spec);
 /* Capon (minimum-variance) spatial spectrum of the covariance the context holds now (after its last frames call or state load),
  * and its peaks: the MVDR power estimate p = 1 / (d^H PhiL^-1 d) of the nulls above on a grid of angles.  Per stream, with
  *     theta_i      = -pi/2 + i pi/(D-1), i = 0 ... D-1 (in double),       D = n_angles
@@ -834,7 +883,7 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long b
  * 3 = spectrum (both kernels of a mca_hip_mvdr_spectrum_* call), 4 = post-filter.  kernel_id 4 exists on a context that has had the
  * post-filter enabled at some time (it stays readable after disabling); a context that never enabled it refuses 4 like every
  * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT).  5 = k_mvdr_rtf, by the same rule: it exists on a
- * context that has had RTF enabled at some time */
+ * context that has had RTF enabled at some time.  6 = k_mvdr_estmask, by the same rule (the mask estimator) */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

@@ -127,6 +127,18 @@ class MvdrRtfConfig(C.Structure):
     ]
 
 
+class MvdrEstmaskConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("enable", C.c_int),
+        ("bin_lo", C.c_int),
+        ("bin_hi", C.c_int),
+        ("coherence_lo", C.c_double),
+        ("coherence_hi", C.c_double),
+        ("n_protected", C.c_int),
+    ]
+
+
 class Gcc2TrackerConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -266,6 +278,12 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
       C.c_void_p]),
     ("mca_hip_mvdr_sources_frames_rtf_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_set_mask_estimator", C.c_int, [C.c_void_p, C.POINTER(MvdrEstmaskConfig)]),
+    ("mca_hip_mvdr_get_mask_estimator", C.c_int, [C.c_void_p, C.POINTER(MvdrEstmaskConfig)]),
+    ("mca_hip_mvdr_sources_frames_auto_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_void_p]),
+    ("mca_hip_mvdr_sources_frames_auto_host", C.c_int, [C.c_void_p, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     ("mca_hip_mvdr_get_steering", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, c_dp, C.c_void_p]),
     ("mca_hip_mvdr_get_target_covariance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_dp]),
     ("mca_hip_mvdr_spectrum_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrSpectrumConfig)]),

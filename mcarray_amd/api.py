@@ -876,9 +876,13 @@ class MvdrBeamformer(_StateBlob):
     set_rtf() and target_mask= of the process calls: the steering vector of every look direction is estimated from a second
     covariance kept over the cells of its target mask [streams][S][F][K] -- the relative transfer function towards a reference
     microphone, which knows the microphones' gains and positions and the true direction where the geometric vector does not
-    (mca_hip_mvdr_set_rtf, mca_hip_mvdr_sources_frames_rtf_*).  A call with target_mask= takes update_mask= beside it, not update=."""
+    (mca_hip_mvdr_set_rtf, mca_hip_mvdr_sources_frames_rtf_*).  A call with target_mask= takes update_mask= beside it, not update=.
+    set_mask_estimator() and estimate_masks=True of the process calls: both masks are formed on the device from the call's own
+    spectra, by the steered coherence of every cell towards the call's look directions, and come back in the result
+    (mca_hip_mvdr_set_mask_estimator, mca_hip_mvdr_sources_frames_auto_*).  Not together with a caller's update=, update_mask= or
+    target_mask=."""
 
-    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF = 0, 1, 2, 3, 4, 5
+    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK = 0, 1, 2, 3, 4, 5, 6
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  null_gain=0.0):
@@ -970,6 +974,29 @@ class MvdrBeamformer(_StateBlob):
         """cap of the steering plane a target_mask= call holds at a time (default 1 GiB): a call above it is cut along the frames
         internally, which changes no byte (mca_hip_mvdr_set_rtf_workspace)"""
         self._check(self._lib.mca_hip_mvdr_set_rtf_workspace(self.h, int(max_bytes)))
+
+    def set_mask_estimator(self, enable=True, bin_lo=0, bin_hi=None, coherence_lo=0.0, coherence_hi=0.05, n_protected=0):
+        """the mask estimator behind estimate_masks=True (include/mcarray_hip.h, mca_hip_mvdr_set_mask_estimator): the band of bins
+        [bin_lo, bin_hi] (None: N/2) outside which the masks are the plain recursion's, the thresholds 0 <= coherence_lo <
+        coherence_hi <= 1 between which the winner's steered coherence becomes its mask (a call with one look direction needs
+        absolute ones such as 0.2 / 0.4), n_protected 0 ... 4 look directions that close the noise covariance where they win (0: all).
+        Processing parameters; the estimator holds no state."""
+        cfg = _lib.MvdrEstmaskConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrEstmaskConfig)
+        cfg.enable = 1 if enable else 0
+        cfg.bin_lo = int(bin_lo)
+        cfg.bin_hi = self.N // 2 if bin_hi is None else int(bin_hi)
+        cfg.coherence_lo = float(coherence_lo)
+        cfg.coherence_hi = float(coherence_hi)
+        cfg.n_protected = int(n_protected)
+        self._check(self._lib.mca_hip_mvdr_set_mask_estimator(self.h, C.byref(cfg)))
+
+    def get_mask_estimator(self):
+        """dict(enable, bin_lo, bin_hi, coherence_lo, coherence_hi, n_protected) as the context holds them"""
+        cfg = _lib.MvdrEstmaskConfig()
+        self._check(self._lib.mca_hip_mvdr_get_mask_estimator(self.h, C.byref(cfg)))
+        return dict(enable=bool(cfg.enable), bin_lo=cfg.bin_lo, bin_hi=cfg.bin_hi, coherence_lo=cfg.coherence_lo, coherence_hi=cfg.coherence_hi,
+                    n_protected=cfg.n_protected)
 
     def target_covariance(self, stream_index=0, source=0):
         """(Psi complex [K][M][M], cpsi [K]) of one stream and slot"""
@@ -1064,11 +1091,44 @@ class MvdrBeamformer(_StateBlob):
         self._check(self._lib.mca_hip_mvdr_sources_frames_rtf_dev(self.h, p, sa, sc, A, n_frames, S, _ptr(doa_rad), upd, tm, _ptr(out_pcm),
                                                                   _ptr(out_spec), stream))
 
-    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None, update_mask=None, target_mask=None):
+    @staticmethod
+    def _auto_check(update, update_mask, target_mask):
+        if update is not None or update_mask is not None or target_mask is not None:
+            raise MCArrayHipError("estimate_masks forms the masks itself: not together with update, update_mask or target_mask")
+
+    def _auto_host(self, pcm, A, F, S, doa, po, ps):
+        """-> (update_mask [streams][F][K], target_mask [streams][S][F][K]) float32"""
+        fp = _lib.c_fp
+        um, tm = np.empty((A, F, self.K), dtype=np.float32), np.empty((A, S, F, self.K), dtype=np.float32)
+        self._check(self._lib.mca_hip_mvdr_sources_frames_auto_host(self.h, pcm.ctypes.data_as(fp), A, F, S, doa.ctypes.data_as(fp),
+                                                                    um.ctypes.data_as(fp), tm.ctypes.data_as(fp), po, ps))
+        return um, tm
+
+    def _auto_dev(self, p, sa, sc, A, n_frames, S, doa_rad, out_pcm, out_spec, stream, like, masks_out):
+        """-> dict(update_mask [streams][F][K], target_mask [streams][S][F][K]) float32 tensors on the device of `like`: the pair
+        masks_out = (update_mask, target_mask) of the caller, or new tensors.  New tensors come from torch's allocator on torch's
+        CURRENT stream: a caller whose `stream` is another one passes masks_out (or orders the two streams), as for every other
+        tensor of the call."""
+        import torch
+        if masks_out is not None:
+            um, tm = masks_out
+            for t, shape, name in ((um, (A, n_frames, self.K), "update_mask"), (tm, (A, S, n_frames, self.K), "target_mask")):
+                if not getattr(t, "is_cuda", False) or tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32:
+                    raise MCArrayHipError("masks_out: %s must be a contiguous float32 device tensor %s" % (name, list(shape)))
+        else:
+            um = torch.empty((A, n_frames, self.K), dtype=torch.float32, device=like.device)
+            tm = torch.empty((A, S, n_frames, self.K), dtype=torch.float32, device=like.device)
+        self._check(self._lib.mca_hip_mvdr_sources_frames_auto_dev(self.h, p, sa, sc, A, n_frames, S, _ptr(doa_rad), _ptr(um), _ptr(tm), _ptr(out_pcm),
+                                                                   _ptr(out_spec), stream))
+        return dict(update_mask=um, target_mask=tm)
+
+    def process(self, pcm, doa_rad, want_audio=True, want_spec=False, update=None, update_mask=None, target_mask=None, estimate_masks=False):
         """pcm float32 [streams][M][(F+1)*hop], doa_rad [streams][F] (or a scalar), update None or [streams][F] covariance update
         weights, or update_mask None or [streams][F][K] weights per frame and bin -> dict(out [streams][F*hop], spec complex64
         [streams][F][K]).  target_mask [streams][1][F][K] (or what broadcasts to it): the call steers with the estimated vector
-        (set_rtf(); mca_hip_mvdr_sources_frames_rtf_*)"""
+        (set_rtf(); mca_hip_mvdr_sources_frames_rtf_*).  estimate_masks: the masks are estimated from the spectra
+        (set_mask_estimator(); mca_hip_mvdr_sources_frames_auto_*) and the result also carries update_mask [streams][F][K] and
+        target_mask [streams][1][F][K]"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
             pcm = pcm[None]
@@ -1081,6 +1141,10 @@ class MvdrBeamformer(_StateBlob):
         spec = np.empty((A, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
         po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
+        if estimate_masks:
+            self._auto_check(update, update_mask, target_mask)
+            um, tm = self._auto_host(pcm, A, F, 1, doa, po, ps)
+            return dict(out=out, spec=spec, update_mask=um, target_mask=tm)
         if target_mask is not None:
             self._rtf_host(pcm, A, F, 1, doa, update, update_mask, target_mask, po, ps)
         elif update_mask is not None:
@@ -1095,13 +1159,19 @@ class MvdrBeamformer(_StateBlob):
                                                                             upd.ctypes.data_as(fp), po, ps))
         return dict(out=out, spec=spec)
 
-    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None, target_mask=None):
+    def process_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None, target_mask=None,
+                    estimate_masks=False, masks_out=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F]
         float32, out_pcm [streams][F*hop], out_spec [streams][F][K][2] (contiguous), update None or [streams][F] float32 covariance
         update weights (contiguous), or update_mask None or [streams][F][K] float32 (contiguous), target_mask None or
-        [streams][1][F][K] float32 (contiguous; set_rtf()); asynchronous on `stream` (a raw hipStream_t or None)."""
+        [streams][1][F][K] float32 (contiguous; set_rtf()); asynchronous on `stream` (a raw hipStream_t or None).  estimate_masks
+        (set_mask_estimator()): returns dict(update_mask [streams][F][K], target_mask [streams][1][F][K]), the tensors of masks_out =
+        (update_mask, target_mask) or, without it, new device tensors allocated on torch's current stream."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
+        if estimate_masks:
+            self._auto_check(update, update_mask, target_mask)
+            return self._auto_dev(p, sa, sc, A, n_frames, 1, doa_rad, out_pcm, out_spec, stream, pcm, masks_out)
         if target_mask is not None:
             self._rtf_dev(p, sa, sc, A, n_frames, 1, doa_rad, update, update_mask, target_mask, out_pcm, out_spec, stream)
         elif update_mask is not None:
@@ -1113,13 +1183,15 @@ class MvdrBeamformer(_StateBlob):
             self._check(self._lib.mca_hip_mvdr_sources_frames_weighted_dev(self.h, p, sa, sc, A, n_frames, 1, _ptr(doa_rad),
                                                                            self._update_dev(update, A, n_frames), _ptr(out_pcm), _ptr(out_spec), stream))
 
-    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None, update_mask=None, target_mask=None):
+    def process_sources(self, pcm, doa_rad, want_audio=True, want_spec=True, update=None, update_mask=None, target_mask=None, estimate_masks=False):
         """S look directions per frame from one analysis, covariance recursion and factorisation: pcm float32
         [streams][M][(F+1)*hop], doa_rad [streams][F][S] (S <= max_sources; the layout of the localiser's "doa"), update None or
         [streams][F] covariance update weights (one per frame for all its directions), or update_mask None or [streams][F][K] ->
         dict(out [streams][S][F*hop], spec complex64 [streams][S][F][K]).  Output s is what process() gives with doa_rad[:, :, s].
         target_mask None or [streams][S][F][K]: the cells that hold the target of look direction s, from which its steering vector
-        is estimated (set_rtf(); mca_hip_mvdr_sources_frames_rtf_*)."""
+        is estimated (set_rtf(); mca_hip_mvdr_sources_frames_rtf_*).  estimate_masks: both masks are estimated from the spectra
+        (set_mask_estimator(); mca_hip_mvdr_sources_frames_auto_*) and the result also carries update_mask [streams][F][K] and
+        target_mask [streams][S][F][K]."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 2:
             pcm = pcm[None]
@@ -1136,6 +1208,10 @@ class MvdrBeamformer(_StateBlob):
         spec = np.empty((A, S, F, self.K), dtype=np.complex64) if want_spec else None
         fp = _lib.c_fp
         po, ps = out.ctypes.data_as(fp) if want_audio else None, spec.ctypes.data_as(fp) if want_spec else None
+        if estimate_masks:
+            self._auto_check(update, update_mask, target_mask)
+            um, tm = self._auto_host(pcm, A, F, S, doa, po, ps)
+            return dict(out=out, spec=spec, update_mask=um, target_mask=tm)
         if target_mask is not None:
             self._rtf_host(pcm, A, F, S, doa, update, update_mask, target_mask, po, ps)
         elif update_mask is not None:
@@ -1151,16 +1227,21 @@ class MvdrBeamformer(_StateBlob):
         return dict(out=out, spec=spec)
 
     def process_sources_dev(self, pcm, n_frames, doa_rad, out_pcm=None, out_spec=None, stream=None, update=None, update_mask=None,
-                            target_mask=None):
+                            target_mask=None, estimate_masks=False, masks_out=None):
         """device tensors (torch): pcm [streams][M][>= (F+1)*hop] float32 at any even strides (pcm_layout), doa_rad [streams][F][S]
         float32 (e.g. the doa_rad tensor Context.process_frames_dev wrote, as it is), out_pcm [streams][S][F*hop], out_spec
         [streams][S][F][K][2] (contiguous), update None or [streams][F] float32 covariance update weights (contiguous), or
         update_mask None or [streams][F][K] float32 (contiguous), target_mask None or [streams][S][F][K] float32 (contiguous;
-        set_rtf()); asynchronous on `stream` (a raw hipStream_t or None)."""
+        set_rtf()); asynchronous on `stream` (a raw hipStream_t or None).  estimate_masks (set_mask_estimator()): returns
+        dict(update_mask [streams][F][K], target_mask [streams][S][F][K]), the tensors of masks_out = (update_mask, target_mask) or,
+        without it, new device tensors allocated on torch's current stream."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
         if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
             raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
+        if estimate_masks:
+            self._auto_check(update, update_mask, target_mask)
+            return self._auto_dev(p, sa, sc, A, n_frames, doa_rad.shape[2], doa_rad, out_pcm, out_spec, stream, pcm, masks_out)
         if target_mask is not None:
             self._rtf_dev(p, sa, sc, A, n_frames, doa_rad.shape[2], doa_rad, update, update_mask, target_mask, out_pcm, out_spec, stream)
         elif update_mask is not None:

@@ -1,7 +1,8 @@
 // api_mvdr.hip -- C ABI of the MVDR-style beamformer with a per-bin spatial covariance (include/mcarray_hip.h,
 // mca_hip_mvdr_*; BASELINE.json configs[3]; SURVEY A.9 -- no reference counterpart, conventions of Beamformer.cpp:59).
 // Host side only: owns the per-stream state (covariances, their traces, overlap-add tails) and the spectra
-// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip and kernels_mvdr_postfilter.hip.  No CPU fallback.
+// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip, kernels_mvdr_estmask.hip and
+// kernels_mvdr_postfilter.hip.  No CPU fallback.
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
@@ -50,6 +51,13 @@ struct mca_hip_mvdr_ctx {
     float2 *d_D = nullptr; size_t d_cap = 0;              // workspace: the steering plane [rows x look directions][K][M] of a chunk of frames
     size_t plane_cap_cells = (size_t)1 << 27;            // its cap (1 GiB; mca_hip_mvdr_set_rtf_workspace): a call above it is cut along the frames
     float *d_rtf_ones = nullptr; size_t rtf_ones_n = 0;   // update mask of an RTF call that brings none, all 1 [rows][K]
+    // the mask estimator (mca_hip_mvdr_set_mask_estimator): processing parameters like null_gain, and no state at all
+    bool em_on = false;
+    bool em_ever = false;         // enabled at some time: timing slot 6 exists
+    int em_bin_lo = 0, em_bin_hi = 0, em_protected = 0;   // (em_bin_hi: N/2 until set)
+    double em_lo = 0.0, em_hi = 0.05;
+    float *d_em_update = nullptr; size_t em_update_n = 0;   // workspace [rows][K]: the update mask of an auto call that hands none back; while enabled
+    float *d_em_target = nullptr; size_t em_target_n = 0;   // workspace [rows x look directions][K]: its target masks
     // workspace
     float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
     float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // rows x look directions; d_T: factored steering phasors [rows][M][N/64 + 33]
@@ -65,8 +73,8 @@ struct mca_hip_mvdr_ctx {
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[6] = {};
-    double t_ms[6] = {};
+    int t_launches[7] = {};
+    double t_ms[7] = {};
     std::string err;
 };
 
@@ -95,6 +103,7 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
     F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
     F(c->d_pf_A); F(c->d_pf_pn); F(c->d_pf_ones);
     F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
+    F(c->d_em_update); F(c->d_em_target);
     F(c->d_X); F(c->d_Y); F(c->d_T); F(c->d_spec_grid); F(c->d_spec_T); F(c->d_spec_part);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->stage.release();
@@ -159,6 +168,23 @@ int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_ones, b
         c->y_rows = yrows;
     }
     if (c->pf_on && !c->d_pf_pn && c->y_rows) VHIP_TRY(c, hipMalloc((void **)&c->d_pf_pn, c->y_rows * c->K * 4));
+    return MCA_HIP_OK;
+}
+
+// the masks of an auto call that the caller does not take back: workspace that grows with the call's shape, as d_T does
+int ensure_estmask_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_update, bool want_target)
+{
+    auto F = [](void *p) { if (p) (void)hipFree(p); };
+    if (want_update && rows * c->K > c->em_update_n) {
+        F(c->d_em_update); c->d_em_update = nullptr; c->em_update_n = 0;
+        VHIP_TRY(c, hipMalloc((void **)&c->d_em_update, rows * c->K * 4));
+        c->em_update_n = rows * c->K;
+    }
+    if (want_target && rows * n_sources * c->K > c->em_target_n) {
+        F(c->d_em_target); c->d_em_target = nullptr; c->em_target_n = 0;
+        VHIP_TRY(c, hipMalloc((void **)&c->d_em_target, rows * n_sources * c->K * 4));
+        c->em_target_n = rows * n_sources * c->K;
+    }
     return MCA_HIP_OK;
 }
 
@@ -237,6 +263,7 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     c->cfg = *cfg; c->cfg.mic_xyz = nullptr;
     c->rtf_alpha = cfg->alpha;
     c->N = cfg->fft_size; c->H = c->N / 2; c->K = c->H + 1; c->M = cfg->n_mics; c->tri = c->M * (c->M + 1) / 2;
+    c->em_bin_hi = c->N / 2;
     while ((1 << c->logH) < c->H) ++c->logH;
     std::vector<float> win(c->N);
     for (int n = 0; n < c->N; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / c->N));
@@ -475,6 +502,42 @@ int mca_hip_mvdr_get_rtf(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_rtf_config *cfg
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_set_mask_estimator(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_estmask_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_estmask_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
+    if (!std::isfinite(cfg->coherence_lo) || !std::isfinite(cfg->coherence_hi) || cfg->coherence_lo < 0.0 || cfg->coherence_hi > 1.0 ||
+        !(cfg->coherence_hi - cfg->coherence_lo >= 1e-3))
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the thresholds must be finite with 0 <= coherence_lo, coherence_hi <= 1 and coherence_hi - coherence_lo >= 1e-3");
+    if (cfg->n_protected < 0 || cfg->n_protected > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_protected must be in [0,4]");
+    const bool on = cfg->enable != 0;
+    if (on != c->em_on) {
+        if (!on) {
+            VHIP_TRY(c, hipSetDevice(c->cfg.device));
+            VHIP_TRY(c, hipDeviceSynchronize());               // no call in flight reads what is freed here
+            if (c->d_em_update) (void)hipFree(c->d_em_update);
+            if (c->d_em_target) (void)hipFree(c->d_em_target);
+            c->d_em_update = nullptr; c->d_em_target = nullptr; c->em_update_n = 0; c->em_target_n = 0;
+        }
+        c->em_on = on;                                         // (the workspace comes with the first auto call: ensure_estmask_ws)
+        if (on) c->em_ever = true;
+    }
+    c->em_bin_lo = cfg->bin_lo; c->em_bin_hi = cfg->bin_hi; c->em_lo = cfg->coherence_lo; c->em_hi = cfg->coherence_hi; c->em_protected = cfg->n_protected;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_mask_estimator(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_estmask_config *cfg)
+{
+    if (!c || !cfg) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    cfg->struct_size = (int)sizeof(mca_hip_mvdr_estmask_config);
+    cfg->enable = c->em_on ? 1 : 0;
+    cfg->bin_lo = c->em_bin_lo; cfg->bin_hi = c->em_bin_hi; cfg->coherence_lo = c->em_lo; cfg->coherence_hi = c->em_hi; cfg->n_protected = c->em_protected;
+    return MCA_HIP_OK;
+}
+
 namespace {
 
 // the analysis (timing slot 0): PCM -> X, and the steering tables T of doa_rad [streams][F][n_sources]
@@ -608,6 +671,26 @@ int launch_rtf(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, 
     return MCA_HIP_OK;
 }
 
+// the mask estimator (timing slot 6): X, T -> the update mask and the target masks of the whole call; between the analysis and
+// k_mvdr_rtf / the solve.  target may be NULL (a call without RTF whose caller takes no target masks back)
+int launch_estmask(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, float *update, float *target, hipStream_t st)
+{
+    MvdrEstmaskArgs ea{};
+    ea.X = c->d_X; ea.T = c->d_T;
+    ea.n_streams = n_streams; ea.n_frames = n_frames; ea.K = c->K; ea.M = c->M; ea.S = n_sources;
+    ea.bin_lo = c->em_bin_lo; ea.bin_hi = c->em_bin_hi;
+    ea.n_protected = c->em_protected == 0 || c->em_protected > n_sources ? n_sources : c->em_protected;
+    ea.coherence_lo = (float)c->em_lo; ea.coherence_span = (float)(c->em_hi - c->em_lo);
+    ea.update = update; ea.target = target;
+    const void *kernel = mvdr_estmask_kernel((c->M + 3) / 4);
+    const long long cells = (long long)n_streams * n_frames * c->K;
+    void *kargs[1] = {&ea};
+    t_begin(c, 6, st);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)((cells + 63) / 64)), dim3(256), kargs, 0, st);
+    t_end(c, st);
+    return MCA_HIP_OK;
+}
+
 // the post-filter (timing slot 4): Z = G Y in place, between the solve and the synthesis
 int launch_postfilter(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, float2 *Y, hipStream_t st)
 {
@@ -656,11 +739,15 @@ int launch_synth(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
 // a call with n_sources look directions per frame: doa_rad [streams][F][n_sources], out_pcm [streams][n_sources][F hop],
 // out_spec [streams][n_sources][F][K]; update: covariance update weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
 // rtf: the call of mca_hip_mvdr_sources_frames_rtf_*, tmask [streams][n_sources][F][K] or NULL (all 0), update its update mask
+// est: the call of mca_hip_mvdr_sources_frames_auto_* (masked, rtf on a context with RTF enabled; update and tmask NULL): both masks
+// come from k_mvdr_estmask, into em_update / em_target where the caller takes them back, else into the workspace
 int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
                     int n_frames, int n_sources, const float *doa_rad, const float *update, bool masked, float *out_pcm,
-                    float *out_spec, void *stream, const float *tmask = nullptr, bool rtf = false)
+                    float *out_spec, void *stream, const float *tmask = nullptr, bool rtf = false, bool est = false,
+                    float *em_update = nullptr, float *em_target = nullptr)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (est && !c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
     if (rtf && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
     if (rtf && c->null_gain != 0.0) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0");
     if (n_sources < 1 || n_sources > c->max_sources)
@@ -686,11 +773,19 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
             fc = (n_frames + chunks - 1) / chunks;          // chunks of equal length, the last one shorter at most
         }
     }
-    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !update, rtf, (size_t)n_streams * fc);
+    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !update && !est, rtf, (size_t)n_streams * fc);
     if (rc) return rc;
+    if (est && (rc = ensure_estmask_ws(c, (size_t)n_streams * n_frames, n_sources, !em_update, rtf && !em_target))) return rc;
     // the beamformed spectra go straight to the caller's buffer when one is given
     float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : c->d_Y;
     if ((rc = launch_analyse(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, st))) return rc;
+    if (est) {
+        // the masks of the whole call, once, ahead of the chunk loop as the analysis is
+        if (!em_update) em_update = c->d_em_update;
+        if (!em_target && rtf) em_target = c->d_em_target;
+        if ((rc = launch_estmask(c, n_streams, n_frames, n_sources, em_update, em_target, st))) return rc;
+        update = em_update; tmask = em_target;
+    }
     if (rtf) {
         for (int f0 = 0; f0 < n_frames; f0 += fc) {
             const int n = std::min(fc, n_frames - f0);
@@ -706,7 +801,8 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
 
 // the host-pointer form: n_upd floats of weights per (stream, frame), 1 or K
 int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
-                     const float *update, bool masked, float *out_pcm, float *out_spec, const float *tmask = nullptr, bool rtf = false)
+                     const float *update, bool masked, float *out_pcm, float *out_spec, const float *tmask = nullptr, bool rtf = false,
+                     bool est = false, float *em_update = nullptr, float *em_target = nullptr)
 {
     if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
@@ -719,15 +815,19 @@ int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n
     const size_t nu = (size_t)n_streams * n_frames * (masked ? (size_t)c->K : 1);
     float *d_upd = update ? (float *)c->stage.get(masked ? 8 : 7, nu * 4) : nullptr;  // (slots 4 ... 6: the spectrum's; 8: the mask's own)
     float *d_tm = tmask ? (float *)c->stage.get(9, nf * c->K * 4) : nullptr;        // [streams][n_sources][F][K]
-    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd) || (tmask && !d_tm))
+    // the masks an auto call hands back are staged where the other calls stage the masks they take
+    float *d_eu = em_update ? (float *)c->stage.get(8, nu * 4) : nullptr, *d_et = em_target ? (float *)c->stage.get(9, nf * c->K * 4) : nullptr;
+    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd) || (tmask && !d_tm) || (em_update && !d_eu) || (em_target && !d_et))
         return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
     if (tmask) VHIP_TRY(c, hipMemcpy(d_tm, tmask, nf * c->K * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
     if (update) VHIP_TRY(c, hipMemcpy(d_upd, update, nu * 4, hipMemcpyHostToDevice));
-    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, masked, d_out, d_spec, nullptr, d_tm, rtf);
+    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, masked, d_out, d_spec, nullptr, d_tm, rtf, est, d_eu, d_et);
     if (rc) return rc;
     VHIP_TRY(c, hipDeviceSynchronize());
+    if (em_update) VHIP_TRY(c, hipMemcpy(em_update, d_eu, nu * 4, hipMemcpyDeviceToHost));
+    if (em_target) VHIP_TRY(c, hipMemcpy(em_target, d_et, nf * c->K * 4, hipMemcpyDeviceToHost));
     if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
     if (out_spec) VHIP_TRY(c, hipMemcpy(out_spec, d_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
@@ -763,6 +863,27 @@ int mca_hip_mvdr_sources_frames_rtf_host(mca_hip_mvdr_ctx *c, const float *pcm, 
 {
     if (c && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
     return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, target_mask, true);
+}
+
+// update_mask_out [streams][F][K] and target_mask_out [streams][n_sources][F][K]: either may be NULL
+int mca_hip_mvdr_sources_frames_auto_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
+                                         int n_frames, int n_sources, const float *doa_rad, float *update_mask_out, float *target_mask_out,
+                                         float *out_pcm, float *out_spec, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(update_mask_out) | reinterpret_cast<uintptr_t>(target_mask_out)) & 3)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "update_mask_out_dev / target_mask_out_dev must be 4-byte aligned");
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, nullptr, true, out_pcm, out_spec, stream, nullptr,
+                           c->rtf_on, true, update_mask_out, target_mask_out);
+}
+
+int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
+                                          float *update_mask_out, float *target_mask_out, float *out_pcm, float *out_spec)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
+    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, nullptr, true, out_pcm, out_spec, nullptr, c->rtf_on, true, update_mask_out,
+                            target_mask_out);
 }
 
 int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
@@ -1097,7 +1218,8 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id > 5 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever)) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c || kernel_id < 0 || kernel_id > 6 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever))
+        return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));
         float ms = 0.f;

@@ -86,6 +86,8 @@ template <bool NOISE> const void *mvdr_solve_rtf_kernel_of(int Q, bool full, int
 template <int Q> __global__ void k_mvdr_rtf(MvdrRtfArgs p);                     // target covariances and estimated steering vectors
 template <int Q> __global__ void k_mvdr_rtf_steering(MvdrRtfSteerArgs p);
 const void *mvdr_rtf_kernel(int Q, bool steering);                              // kernels_mvdr_rtf.hip
+template <int Q> __global__ void k_mvdr_estmask(MvdrEstmaskArgs p);             // update and target masks from the call's spectra
+const void *mvdr_estmask_kernel(int Q);                                         // kernels_mvdr_estmask.hip
 __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                                   // decision-directed Wiener gain on the solve's output
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance

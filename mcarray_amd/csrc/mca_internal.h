@@ -528,6 +528,19 @@ struct MvdrRtfSteerArgs {
     unsigned char *estimated; // [K]
 };
 
+// k_mvdr_estmask<Q> (kernels_mvdr_estmask.hip): the update mask and the target masks of a call from its own spectra,
+// between the analysis and k_mvdr_rtf / the solve.  One quad per (stream, frame, bin) cell, the layout of the solve; stateless.
+struct MvdrEstmaskArgs {
+    const float2 *X;          // [streams][n_frames][K][M]
+    const float2 *T;          // [streams][n_frames][S][M][nhi + 32] (MvdrAnalyseArgs): the geometric vectors
+    int n_streams, n_frames, K, M, S;
+    int bin_lo, bin_hi;       // the band, both ends included; outside it target 0 and update 1
+    int n_protected;          // P (>= 1): the look directions s < P close the update mask where they win
+    float coherence_lo, coherence_span;       // v = clamp((c_w - lo) / span), span = hi - lo formed in double
+    float *update;            // [streams][n_frames][K]
+    float *target;            // [streams][S][n_frames][K], or NULL: not stored
+};
+
 // ---- the instantiations of the MVDR solve (mvdr_solve.h) ----
 // k_mvdr_solve_t<Q, FULL, S, S1, PF, NULLS, REUSE, WEIGHT, NOISE>: Q row slots per lane, FULL: M == 4 Q, S look directions per frame,
 // NULLS: soft nulls at the other directions (4.3), WEIGHT: the covariance update weight of a frame (4.5, 4.7), NOISE: the noise plane

@@ -15,7 +15,9 @@ run of 8 frames frozen) and the masked call (update_mask [streams][F][K]) under 
 bins, blocks of 4 frames x 16 bins half of them open, and independent random binary cells (the worst divergence of the quads of a
 wave); a build without the masked entry points (MCA_HIP_LIB) runs the first two rows only.  --rtf times the table of DESIGN.md 4.8, one
 JSON line for one and one for two look directions: k_mvdr_rtf, the solve that reads the steering plane beside the masked (CELL) solve
-under the same update mask, and both calls' totals; update mask and target masks are complementary blocks of 4 frames x 16 bins.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+under the same update mask, and both calls' totals; update mask and target masks are complementary blocks of 4 frames x 16 bins.  --estmask times the table of DESIGN.md 4.9, one JSON line for one and one for two look directions: k_mvdr_estmask against its own
+traffic (X and T read, S + 1 masks written) as a share of the measured float4 copy rate, and the auto call's total beside the RTF
+call fed the masks the auto call returned.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
 points it lacks are left unbound, --null-gain must then stay 0, --update none and --postfilter off (as far as the build lacks them)."""
 import argparse
 import json
@@ -122,6 +124,59 @@ def rtf_table(a, fs, N, xs, pcm, st):
         print(json.dumps(row), flush=True)
 
 
+COPY_TBPS = 6.29       # the measured float4 copy rate of the MI355X
+
+
+def estmask_table(a, fs, N, xs, pcm, st):
+    """the rows of DESIGN.md 4.9: k_mvdr_estmask against its traffic, the auto call beside the RTF call fed its masks"""
+    hop, K = N // 2, N // 2 + 1
+    dev = pcm.device
+    nph = N // 64 + 33
+    for S in (1, 2):
+        look = torch.tensor(LOOK[:S], device=dev, dtype=torch.float32)
+        doa = look[None, None, :].expand(a.streams, a.frames, S).contiguous()
+        out = torch.empty((a.streams, S, a.frames * hop), device=dev, dtype=torch.float32)
+        cells = a.streams * a.frames * K
+        traffic = cells * a.mics * 8.0 + a.streams * a.frames * S * a.mics * nph * 8.0 + cells * (S + 1) * 4.0
+        row = dict(sources=S, postfilter=bool(a.postfilter), workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N),
+                   k_mvdr_estmask_bytes=traffic)
+        masks = None
+        for name in ("auto", "rtf"):
+            bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=S)
+            if a.postfilter:
+                bf.set_postfilter(True)
+            bf.set_rtf(True)
+            if name == "auto":
+                # one look direction: absolute thresholds; two: the second is the competitor
+                bf.set_mask_estimator(True, coherence_lo=0.2 if S == 1 else 0.0, coherence_hi=0.4 if S == 1 else 0.05, n_protected=1)
+                masks = bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, estimate_masks=True)
+                # the timed step hands no masks back: they stay in the workspace
+                step = lambda: bf._check(bf._lib.mca_hip_mvdr_sources_frames_auto_dev(bf.h, *api.pcm_layout(pcm), a.streams, a.frames, S, api._ptr(doa), None,
+                                                                                     None, api._ptr(out), None, st))
+            else:
+                step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **masks)
+            for _ in range(a.warmup):
+                step()
+            bf.set_timing(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                step()
+            torch.cuda.synchronize()
+            row[name + "_ms_per_step"] = (time.perf_counter() - t0) / a.steps * 1e3
+            for kid, kname in ((bf.K_ANALYSE, "k_mvdr_analyse"), (bf.K_RTF, "k_mvdr_rtf"), (bf.K_SOLVE, "k_mvdr_solve_rtf")):
+                n, ms = bf.get_timing(kid)
+                row["%s_%s_ms" % (name, kname)] = ms / max(n, 1)
+            if name == "auto":
+                n, ms = bf.get_timing(bf.K_ESTMASK)
+                row["k_mvdr_estmask_ms"] = ms / max(n, 1)
+                row["k_mvdr_estmask_TBps"] = traffic / (ms / max(n, 1) * 1e-3) / 1e12 if ms > 0 else 0.0
+                row["k_mvdr_estmask_share_of_copy_rate"] = row["k_mvdr_estmask_TBps"] / COPY_TBPS
+                row["protected_cells_share"] = float((masks["update_mask"] < 1).float().mean())
+            bf.close()
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -136,6 +191,7 @@ def main():
     ap.add_argument("--postfilter", action="store_true", help="enable the Wiener post-filter (its defaults)")
     ap.add_argument("--mask", action="store_true", help="time the table of the time-frequency update masks (DESIGN.md 4.7)")
     ap.add_argument("--rtf", action="store_true", help="time the table of the estimated steering vectors (DESIGN.md 4.8)")
+    ap.add_argument("--estmask", action="store_true", help="time the table of the mask estimator (DESIGN.md 4.9)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -156,6 +212,8 @@ def main():
         return mask_table(a, fs, N, xs, pcm, st)
     if a.rtf:
         return rtf_table(a, fs, N, xs, pcm, st)
+    if a.estmask:
+        return estmask_table(a, fs, N, xs, pcm, st)
     upd = None
     if a.update != "none":
         w = np.ones((a.streams, a.frames), dtype=np.float32)

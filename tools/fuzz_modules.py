@@ -1,4 +1,5 @@
-"""Randomised parity sweep of the 2-channel masking module, the MVDR beamformer and its sources call with soft nulls against the CPU oracle (a one-off check like
+"""Randomised parity sweep of the 2-channel masking module, the MVDR beamformer and its sources call with soft nulls against the CPU oracle, and of the MVDR auto
+call (estimated masks) against the call fed its masks (a one-off check like
 tools/fuzz_parity.py): random frame lengths, methods / algorithms, channel counts, geometries, memories, loadings, chunked calls.
 usage (GPU box): python tools/fuzz_modules.py [cases] [seed]"""
 import os
@@ -115,18 +116,56 @@ def mvdr_nulls_case(rng):
     return bool(np.isfinite(worst) and worst <= 5e-4), "%s cut=%d worst rel err %.1e" % (tag, cut, worst)
 
 
+def mvdr_auto_case(rng):
+    """the auto call (masks estimated from the spectra, mca_hip_mvdr_sources_frames_auto_*) against the RTF or the masked call fed
+    the masks it returned, bit for bit, and the masks against their own definition: random geometry, frame size, S, band,
+    thresholds and number of protected directions"""
+    fs, N = [(8000, 256), (16000, 512), (48000, 1024)][int(rng.integers(0, 3))]
+    M, S = int(rng.integers(2, 17)), int(rng.integers(1, 5))
+    xs = np.sort(rng.uniform(0, 0.03 * M, M))
+    F, A, rtf = int(rng.integers(1, 25)), int(rng.integers(1, 4)), bool(rng.integers(0, 2))
+    hop = N // 2
+    pcm = np.stack([synth.noise_source_stream(xs, rng.uniform(-1.3, 1.3), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)))
+                    + synth.noise_source_stream(xs, rng.uniform(-1.3, 1.3), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)), snr_db=50)
+                    for _ in range(A)]).astype(np.float32)
+    doa = rng.uniform(-1.4, 1.4, (A, F, S)).astype(np.float32)
+    lo = float(rng.uniform(0.0, 0.5))
+    cfg = dict(bin_lo=int(rng.integers(0, 9)), bin_hi=N // 2 - int(rng.integers(0, 9)), coherence_lo=lo, coherence_hi=lo + float(rng.uniform(0.002, 0.5)),
+               n_protected=int(rng.integers(0, 5)))
+    tag = "mvdr auto fs=%d N=%d M=%d S=%d A=%d F=%d rtf=%d %s" % (fs, N, M, S, A, F, rtf, cfg)
+    res = []
+    for est in (True, False):
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=A, max_sources=S)
+        if rtf:
+            bf.set_rtf(True)
+        if est:
+            bf.set_mask_estimator(True, **cfg)
+            res.append(bf.process_sources(pcm, doa, estimate_masks=True))
+        else:
+            kw = dict(update_mask=res[0]["update_mask"], **(dict(target_mask=res[0]["target_mask"]) if rtf else {}))
+            res.append(bf.process_sources(pcm, doa, **kw))
+        res[-1]["blob"] = bf.state_save()
+        bf.close()
+    um, tm = res[0]["update_mask"], res[0]["target_mask"]
+    P = S if cfg["n_protected"] == 0 or cfg["n_protected"] > S else cfg["n_protected"]
+    ok = bool(np.array_equal(res[0]["spec"].view(np.float32), res[1]["spec"].view(np.float32)) and np.array_equal(res[0]["out"], res[1]["out"])
+              and res[0]["blob"] == res[1]["blob"] and np.all((tm >= 0) & (tm <= 1)) and np.all((tm > 0).sum(axis=1) <= 1)
+              and np.array_equal(um, np.float32(1) - tm[:, :P].max(axis=1)) and not tm[..., :cfg["bin_lo"]].any() and not tm[..., cfg["bin_hi"] + 1:].any())
+    return ok, "%s assigned %.0f %%" % (tag, 100.0 * float((tm > 0).any(axis=1).mean()))
+
+
 def main(cases, seed):
     rng = np.random.default_rng(seed)
     bad = 0
     for case in range(cases):
-        for fn in (mask_case, mvdr_case, mvdr_nulls_case):
+        for fn in (mask_case, mvdr_case, mvdr_nulls_case, mvdr_auto_case):
             try:
                 ok, msg = fn(rng)
             except api.MCArrayHipError as e:
                 ok, msg = False, "%s raised %s" % (fn.__name__, e)
             print(("ok   " if ok else "FAIL ") + "case %d: %s" % (case, msg), flush=True)
             bad += 0 if ok else 1
-    print("%d cases x 3, %d failures" % (cases, bad))
+    print("%d cases x 4, %d failures" % (cases, bad))
     return 1 if bad else 0
 
 
