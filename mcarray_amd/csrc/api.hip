@@ -127,7 +127,10 @@ struct mca_hip_ctx {
     // the previous call; -1 on a new stream), the running miss total, the rows of Y (grown on demand) and two carries between frame passes
     float4 *d_steer_rows = nullptr; float2 *d_steer_q = nullptr; float *d_steer_nyq = nullptr; int *d_steer_pred = nullptr; unsigned long long *d_steer_miss = nullptr;
     float2 *d_steer_Y = nullptr; size_t steer_Y_rows = 0; float *d_steer_tail = nullptr;
+    int *d_steer_mlist = nullptr;                           // the miss list of the patching second pick (ScanPickArgs::n_miss): [0] its length, then steer_Y_rows entries
     bool steer_now = false, steer_fused_now = false;        // this call: the analysis may steer ahead (Y holds the whole call) / did
+    bool steer_mlist_dirty = false;                         // misses were listed by a call whose synthesis (which empties the list) has not been enqueued
+    bool steer_patched_now = false;                         // this call: the second pick patches the missed frames (no k_steer_patch launch)
     unsigned long long steer_frames_total = 0, steer_fused_calls = 0;
     // the guard of that path (steer_policy_begin): a call steers ahead of its picks unless the report of the call FB_LAG calls before it -- its
     // frames whose pick was not the predicted bin, through page-locked memory, consumed at that fixed lag like the AUTO policy's -- had more
@@ -256,7 +259,7 @@ void free_ctx(mca_hip_ctx *c)
 {
     if (!c) return;
     auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
+    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_mlist); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
     F(c->d_E[0]); F(c->d_E[1]); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_doa[0]); F(c->d_doa[1]); F(c->d_vdone[0]); F(c->d_vdone[1]); F(c->d_g2_vidx); F(c->d_g2_nv); F(c->d_g2_rad); F(c->d_g2_prob);
     F(c->d_g2_reset); F(c->d_g2_post0); F(c->d_silence);
     F(c->d_trk_x); F(c->d_trk_sd); F(c->d_trk_si); F(c->d_trk_sil); F(c->d_trk_corr); F(c->d_trk_idx); F(c->d_trk_res);
@@ -1225,6 +1228,7 @@ int mca_hip_reset(mca_hip_ctx *c, void *stream)
         if (w.d_nlist) HIP_TRY(c, hipMemsetAsync(w.d_nlist, 0, 16, st));
     }
     if (c->d_steer_pred) HIP_TRY(c, hipMemsetAsync(c->d_steer_pred, 0xff, na * 4, st));      // no pick yet: bin -1, the initial DOA
+    if (c->d_steer_mlist) { HIP_TRY(c, hipMemsetAsync(c->d_steer_mlist, 0, 4, st)); c->steer_mlist_dirty = false; }   // (a call that failed half way may have left misses listed)
     c->steer_spec = true; c->steer_lost = false; c->steer_seq_seen = c->steer_seq;              // (reports still in flight belong to the old streams)
     c->gcc2_frames_done = 0;
     c->g2f = G2FrameState();                                                              // the frame hook as a newly built module
@@ -1670,6 +1674,25 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         if (hist_valid) { pa.hist_valid = 1; pa.hist_C_in = c->d_hist_C[c->hist_cur]; pa.e_hist_in = c->d_ehist[c->hist_cur]; }
         if (cand_call(c, lazy)) { pa.umask = c->ws().d_umask; pa.umask_words = c->Dp / 32; pa.dead = c->ws().d_unsure; }   // (dead: the unsure bytes, unused by these contexts)
         pa.clist = c->ws().d_chunk_from + c->ws().adapt_chunks; pa.n_clist = c->ws().d_nlist + 1;   // (+ 2: see ScanPickArgs)
+        // steered tail: the analysis of this call steered every frame at its array's predicted bin, so the frames that miss it are patched inside
+        // the second pick's launch (k_scan_repick<PL, true>) and steer_separate launches no k_steer_patch.  One batch of k_scan_pick per chunk
+        // is what makes "no flagged frame in the batch" mean "the chunk's coarse picks are final".
+        // Not the widest peak pick (D > 386: k_scan_pick<8, 1> has no register left for the append), and only while the launch's LDS -- energy
+        // rows, the transform's table, a scratch per wave, the static arrays -- fits a CU: those calls keep the stand-alone k_steer_patch.
+        const size_t tail_lds = (size_t)32 * (c->Dp + 8) * sizeof(float) + (size_t)(F1K_TWORDS + 8 * F1K_SCRATCH) * sizeof(float2) + 2048;
+        if (c->steer_now && c->steer_fused_now && c->d_steer_mlist && SCAN_SUB == SCAN_CHUNK && c->S == 1 && !gate && (size_t)n_arrays * n_frames <= c->steer_Y_rows &&
+            c->D - 2 <= 384 && c->D <= 512 && tail_lds <= 160 * 1024) {
+            // the list is empty unless a call that listed misses never reached its synthesis (which empties it): an error in between
+            if (c->steer_mlist_dirty) HIP_TRY(c, hipMemsetAsync(c->d_steer_mlist, 0, sizeof(int), st));
+            c->steer_mlist_dirty = true;
+            pa.n_miss = c->d_steer_mlist; pa.miss_cap = (int)((size_t)n_arrays * n_frames);
+            SteerPatchArgs &sp = pa.sp;
+            sp.pcm = pcm; sp.array_stride = array_stride; sp.mic_stride = mic_stride; sp.n_arrays = n_arrays; sp.n_frames = n_frames; sp.f0 = 0; sp.f1 = n_frames;
+            sp.window = c->d_window; sp.doa_bin = doa_bin; sp.all = 0; sp.miss = c->d_steer_miss;
+            sp.bf.rows = c->d_steer_rows; sp.bf.q = c->d_steer_q; sp.bf.nyq = c->d_steer_nyq; sp.bf.pred = c->d_steer_pred + a0; sp.bf.Y = c->d_steer_Y;
+            sp.y_f0 = 0; sp.y_frames = n_frames;
+            c->steer_patched_now = true;
+        }
         if (c->h_probe && !c->capturing) {
             c->fb_frames_ring[c->fb_calls % FB_RING] = c->adapt_frames_total + (unsigned long long)n_arrays * n_frames;
             c->fb_launch_m[c->fb_calls % FB_RING] = c->fb_m > 0 ? c->fb_m - 1 : 0;       // (the eligible call this piece belongs to)
@@ -1744,14 +1767,18 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             launch_repair_contraction(c, c->ws(), g0, pass_rows, n_arrays, pp, st);
         }
         set_call_planes(c, 1);
-        const size_t smem4 = (size_t)32 * (c->Dp + 8) * sizeof(float);
-#define LAUNCH_REPICK(PL)                                                                                                           \
+        const int repick_thr = std::max(nthr, 512);
+        const bool tail = pa.n_miss != nullptr;             // the launch also patches the steered rows: the transform's table and a scratch per wave behind the energy rows
+        const size_t smem4 = (size_t)32 * (c->Dp + 8) * sizeof(float) + (tail ? (size_t)(F1K_TWORDS + repick_thr / 64 * F1K_SCRATCH) * sizeof(float2) : 0);
+        const unsigned repick_wgs = (unsigned)std::min<long long>((long long)pa.n_chunks * n_arrays, REPICK_GRID) + (tail ? STEER_TAIL_WGS : 0);
+#define LAUNCH_REPICK(PL, T)                                                                                                        \
         do {                                                                                                                        \
-            if (smem4 > 64 * 1024)      /* grids finer than 0.45 degrees: Dp >= 512 */                                              \
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scan_repick<PL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)); \
-            hipLaunchKernelGGL((k_scan_repick<PL>), dim3((unsigned)std::min<long long>((long long)pa.n_chunks * n_arrays, REPICK_GRID)), dim3(std::max(nthr, 512)), smem4, st, pa); \
+            if (smem4 > 64 * 1024)      /* grids finer than 0.45 degrees: Dp >= 512; the patching launch always */                  \
+                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scan_repick<PL, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)); \
+            hipLaunchKernelGGL((k_scan_repick<PL, T>), dim3(repick_wgs), dim3(repick_thr), smem4, st, pa);                          \
         } while (0)
-        if (ppl == 2) LAUNCH_REPICK(2); else if (ppl == 6) LAUNCH_REPICK(6); else LAUNCH_REPICK(8);
+        if (tail) { if (ppl == 2) LAUNCH_REPICK(2, true); else if (ppl == 6) LAUNCH_REPICK(6, true); else LAUNCH_REPICK(8, true); }
+        else { if (ppl == 2) LAUNCH_REPICK(2, false); else if (ppl == 6) LAUNCH_REPICK(6, false); else LAUNCH_REPICK(8, false); }
 #undef LAUNCH_REPICK
         if (gate) hipLaunchKernelGGL(k_doa_fill, dim3(n_arrays), dim3(1024), 0, st, fa);   // gated-out frames repeat the last FINAL pick
         time_end(c, st);
@@ -1896,6 +1923,11 @@ static int steer_prepare(mca_hip_ctx *c, int n_arrays, int n_frames)
         if (c->d_steer_Y) (void)hipFree(c->d_steer_Y);
         c->d_steer_Y = nullptr; c->steer_Y_rows = 0;
         HIP_TRY(c, hipMalloc((void **)&c->d_steer_Y, rows * STEER_ROW * sizeof(float2)));
+        if (c->d_steer_mlist) (void)hipFree(c->d_steer_mlist);
+        c->d_steer_mlist = nullptr;
+        HIP_TRY(c, hipMalloc((void **)&c->d_steer_mlist, (rows + 1) * sizeof(int)));          // an entry per row of Y at most
+        HIP_TRY(c, hipMemset(c->d_steer_mlist, 0, sizeof(int)));
+        c->steer_mlist_dirty = false;
         c->steer_Y_rows = rows;
     }
     return MCA_HIP_OK;
@@ -1911,6 +1943,7 @@ static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stri
     const size_t a0 = (size_t)c->a0;
     const int pf = steer_pass_frames(c, n_arrays, n_frames);
     const bool fused = c->steer_fused_now && pf == n_frames;
+    const bool patched = fused && c->steer_patched_now;       // the second pick of the localiser patched the missed frames and counted them (localise_impl)
     const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2);
     float *tails[2] = {c->d_steer_tail, c->d_steer_tail + (size_t)c->cfg.max_arrays * FFT_H};
     time_begin(c, MCA_HIP_K_BEAMFORM, st);
@@ -1923,7 +1956,7 @@ static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stri
         pa.window = c->d_window; pa.doa_bin = doa_bin; pa.all = fused ? 0 : 1; pa.miss = c->d_steer_miss;
         pa.bf.rows = c->d_steer_rows; pa.bf.q = c->d_steer_q; pa.bf.nyq = c->d_steer_nyq; pa.bf.pred = c->d_steer_pred + a0; pa.bf.Y = c->d_steer_Y;
         pa.y_f0 = f0; pa.y_frames = fused ? n_frames : np;
-        hipLaunchKernelGGL(k_steer_patch, dim3(std::min(STEER_PATCH_WGS, (np + 3) / 4)), dim3(256), smem, st, pa);
+        if (!patched) hipLaunchKernelGGL(k_steer_patch, dim3(std::min(STEER_PATCH_WGS, (np + 3) / 4)), dim3(256), smem, st, pa);
         SteerSynthArgs sy{};
         sy.Y = c->d_steer_Y; sy.n_frames = n_frames; sy.f0 = f0; sy.f1 = f1; sy.y_f0 = pa.y_f0; sy.y_frames = pa.y_frames;
         sy.ft = 16;
@@ -1933,6 +1966,7 @@ static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stri
         sy.tail_out = last ? c->d_tail[c->tail_cur ^ 1] + a0 * FFT_H : tails[pass & 1];
         sy.doa_bin = doa_bin; sy.pred_out = last ? c->d_steer_pred + a0 : nullptr;
         if (last && c->h_steer) { sy.report = c->h_steer + 2 * (c->steer_seq % FB_RING); sy.seq = c->steer_seq + 1; sy.miss_total = c->d_steer_miss; }
+        if (patched) sy.n_miss = c->d_steer_mlist;
         const int runs = (np + sy.ft - 1) / sy.ft;
         hipLaunchKernelGGL(k_steer_synth, dim3((runs + 3) / 4, n_arrays), dim3(256), smem, st, sy);
     }
@@ -1941,6 +1975,7 @@ static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stri
     c->steer_call_frames[c->steer_seq % FB_RING] = (unsigned long long)n_arrays * n_frames; ++c->steer_seq;
     c->steer_frames_total += (unsigned long long)n_arrays * n_frames;
     if (fused) ++c->steer_fused_calls;
+    if (patched) c->steer_mlist_dirty = false;                 // (the synthesis above empties the miss list)
     return MCA_HIP_OK;
 }
 
@@ -2161,7 +2196,7 @@ int mca_hip_process_frames_dev(mca_hip_ctx *c, const float *pcm, long long array
     const bool steer = steer_applies(c) && !c->host_call && !c->capturing;
     if (steer && (rc = steer_prepare(c, n_arrays, n_frames))) return rc;
     if (steer) steer_policy_begin(c);
-    c->steer_now = steer && c->steer_spec && steer_pass_frames(c, n_arrays, n_frames) == n_frames; c->steer_fused_now = false;
+    c->steer_now = steer && c->steer_spec && steer_pass_frames(c, n_arrays, n_frames) == n_frames; c->steer_fused_now = false; c->steer_patched_now = false;
     adapt_policy_begin(c, n_arrays, n_frames);
     c->lazy_entry = !c->host_call;
     rc = localise_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, (hipStream_t)stream);
@@ -2169,6 +2204,7 @@ int mca_hip_process_frames_dev(mca_hip_ctx *c, const float *pcm, long long array
     c->steer_now = false;
     if (!rc && steer) rc = steer_separate(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, out_pcm, (hipStream_t)stream);
     else if (!rc) rc = separate_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
+    c->steer_fused_now = false; c->steer_patched_now = false;      // (they describe this call only)
     if (rc) return rc;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
     c->e_cur ^= 1; c->tail_cur ^= 1;

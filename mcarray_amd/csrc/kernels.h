@@ -10,7 +10,7 @@ __global__ void k_sum_planes(float *C, long long n4, int planes, long long strid
 __global__ void k_scan_partial(ScanPickArgs p);
 __global__ void k_scan_carry(ScanPickArgs p);
 template <int PL, int MODE> __global__ void k_scan_pick(ScanPickArgs p);   // PL: positions per lane of the peak pick (2 / 6 / 8, by D); MODE 0 plain, 1 adaptive coarse pass
-template <int PL> __global__ void k_scan_repick(ScanPickArgs p);
+template <int PL, bool PATCH> __global__ void k_scan_repick(ScanPickArgs p);   // PATCH: also patches the steered rows of the frames that missed their predicted bin
 __global__ void k_repair_patch(RepairPatchArgs p);
 __global__ void k_hist_list(int *list, int *n_list, int *need, int n_units);      // lazy tails (round 5): settle_history
 __global__ void k_hist_settle(const float *e_hist, const float *hist_C, float *state, int *n_list, int D, int Dp, float mu, float omu);

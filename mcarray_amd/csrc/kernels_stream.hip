@@ -12,6 +12,7 @@
 #include "mca_internal.h"
 #include "phat_pairs.h"
 #include "pair_balance.h"
+#include "steer.h"
 
 namespace mca {
 
@@ -761,6 +762,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         if (MODE == 1) {
             const unsigned fm = s_flagmask;
             if (d < te - ts) p.flags[(long long)a * p.n_frames + ts + d] = (fm >> d) & 1u;
+            // (PL < 8: the widest pick has no register left for it -- 4 more would spill; such grids keep the stand-alone k_steer_patch, api.hip)
+            if (PL < 8 && p.n_miss && fm == 0u && wave == 0) {
+                // steered tail: no flagged frame, so the chunk's coarse picks are final -- its frames that missed the predicted bin go onto
+                // the miss list; the workgroups of the second pick's launch that walk the list patch and count them.  (A chunk with a
+                // flagged frame is its re-pick's.  The list has room for every frame of the call and is empty when the call starts.)
+                const bool miss = lane < te - ts && s_bin[lane * MCA_MAX_SOURCES] != p.sp.bf.pred[a];
+                const unsigned long long mm = __ballot(miss);
+                if (mm) {
+                    int at = 0;
+                    if (lane == 0) at = atomicAdd(p.n_miss, __popcll(mm));
+                    at = __builtin_amdgcn_readfirstlane(at) + __popcll(mm & ((1ull << lane) - 1ull));
+                    if (miss) p.n_miss[1 + at] = a * p.n_frames + ts + lane;
+                }
+            }
             // plan the repair of the flagged frames, one wave per frame
             int k = 0;
             const bool plan_lds = p.umask != nullptr && !vc;            // (candidate-column calls are ungated: a frame needs its own row and the 16 before it)
@@ -875,13 +890,44 @@ template __global__ void k_scan_pick<8, 1>(ScanPickArgs);
 // so that at a flagged frame at most 0.8^(REPAIR_WARM+1) of the coarse error is left; the flagged frames are picked again
 // (every other frame's coarse pick is safe).  32 rows in flight per thread, the picks of a batch of 32 frames after it.
 // The chunk with the array's last advancing frame leaves the exact state.
+//
+// PATCH (steered tail; an ADAPTIVE call whose analysis steered ahead, ScanPickArgs::n_miss): the launch also redoes the steered rows of
+// the frames whose final pick is not the predicted bin, through steer_patch_frame, one frame per wave -- what k_steer_patch did in a
+// launch of its own.  The last STEER_TAIL_WGS workgroups of the grid (dispatched behind the re-pick ones) stride over the miss list
+// k_scan_pick left of the chunks without a flagged frame; a re-pick workgroup patches the misses among the 32 frames of its own chunk
+// once their final picks are written.  Nobody waits for anybody: a workgroup without a miss leaves (or goes on) after one look, before
+// any table set-up or window load.  LDS: the transform's table and the waves' scratch sit behind the energy rows.
 constexpr int REPICK_B = 32;
 
-template <int PL>
+template <int PL, bool PATCH>
 __global__ __launch_bounds__(512) void k_scan_repick(ScanPickArgs p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float *sEn = reinterpret_cast<float *>(smem_raw);                   // [REPICK_B][Dl]
+    float2 *tab = reinterpret_cast<float2 *>(smem_raw + (size_t)REPICK_B * (p.Dp + 8) * sizeof(float));   // PATCH: [F1K_TWORDS], then a wave's [F1K_SCRATCH] each
+    const int n_repick = PATCH ? (int)gridDim.x - STEER_TAIL_WGS : (int)gridDim.x;   // workgroups that walk the chunk list
+    if (PATCH && (int)blockIdx.x >= n_repick) {
+        const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)blockDim.x >> 6;
+        const int n_miss = min(*p.n_miss, p.miss_cap), b = (int)blockIdx.x - n_repick;
+        if (b * nw >= n_miss) return;
+        f1k_table_init(tab, tid, blockDim.x);
+        F1kLane lc;
+        lc.init(lane);
+        __syncthreads();
+        v2f win[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { win[i].x = p.sp.window[lane + 128 * i]; win[i].y = p.sp.window[lane + 128 * i + 64]; }
+        int n_all = 0, n_guard = 0;                                              // SteerPatchArgs::miss [0], [1]: the frames this wave patched
+        for (int i = b * nw + wave; i < n_miss; i += STEER_TAIL_WGS * nw) {
+            const int e = __builtin_amdgcn_readfirstlane(p.n_miss[1 + i]), a = e / p.n_frames;
+            ++n_all;
+            if (__builtin_amdgcn_readfirstlane(p.sp.bf.pred[a]) >= 0) ++n_guard;
+            steer_patch_frame(p.sp, a, e - a * p.n_frames, __builtin_amdgcn_readfirstlane(p.doa_bin[e]), win, tab + F1K_TWORDS + wave * F1K_SCRATCH, tab, lc, lane);
+        }
+        if (lane == 0 && n_all) { atomicAdd(p.sp.miss, (unsigned long long)n_all); if (n_guard) atomicAdd(p.sp.miss + 1, (unsigned long long)n_guard); }
+        return;
+    }
+    bool tab_ready = false;
     __shared__ int s_bin[REPICK_B * MCA_MAX_SOURCES];
     __shared__ float s_val[REPICK_B * MCA_MAX_SOURCES];
     const int d = threadIdx.x, lane = d & 63, wave = d >> 6, nwaves = blockDim.x >> 6;
@@ -897,7 +943,7 @@ __global__ __launch_bounds__(512) void k_scan_repick(ScanPickArgs p)
         __threadfence_system();
         __hip_atomic_store(&p.probe[2], p.probe_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    for (int li = blockIdx.x; li < n_listed; li += gridDim.x) {
+    for (int li = blockIdx.x; li < n_listed; li += n_repick) {
     const int ci = p.clist[li];
     const int a = ci / p.n_chunks, chunk = ci - a * p.n_chunks;
     const int c_from = p.chunk_from[ci];
@@ -989,19 +1035,50 @@ __global__ __launch_bounds__(512) void k_scan_repick(ScanPickArgs p)
     __syncthreads();                                                        // (every thread has read chunk_from[ci])
     if (d == 0) p.chunk_from[ci] = 0x7f7f7f7f;                              // consumed: no flagged frame
     }
+    if (PATCH) {
+        // the final picks of this workgroup's chunks are out (the flagged frames' from the loop above, the others' from k_scan_pick): their
+        // misses, one frame per wave.  A loop of its own: inside the one above the transform's registers were allocated together with the 64
+        // map rows it holds in flight, and a hundred of them spilled.
+        for (int li = blockIdx.x; li < n_listed; li += n_repick) {
+            const int ci = p.clist[li];
+            const int a = ci / p.n_chunks, t_start = (ci - a * p.n_chunks) * p.chunk, t_end = min(t_start + p.chunk, p.n_frames);
+            const int pred = p.sp.bf.pred[a], u = t_start + (lane & 31);
+            const unsigned mm = (unsigned)__ballot(lane < 32 && u < t_end && p.doa_bin[(long long)a * p.n_frames + u] != pred);
+            if (!mm) continue;
+            if (d == 0) {
+                atomicAdd(p.sp.miss, (unsigned long long)__popc(mm));
+                if (pred >= 0) atomicAdd(p.sp.miss + 1, (unsigned long long)__popc(mm));          // ([1]: the guard's, SteerPatchArgs::miss)
+            }
+            if (!tab_ready) { f1k_table_init(tab, d, blockDim.x); tab_ready = true; __syncthreads(); }
+            F1kLane lc;
+            lc.init(lane);
+            v2f win[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { win[i].x = p.sp.window[lane + 128 * i]; win[i].y = p.sp.window[lane + 128 * i + 64]; }
+            int k = 0;
+            for (unsigned rest = mm; rest; rest &= rest - 1, ++k) {
+                if (k % nwaves != wave) continue;
+                const int f = t_start + __ffs((int)rest) - 1;
+                steer_patch_frame(p.sp, a, f, __builtin_amdgcn_readfirstlane(p.doa_bin[(long long)a * p.n_frames + f]), win, tab + F1K_TWORDS + __builtin_amdgcn_readfirstlane(wave) * F1K_SCRATCH, tab, lc, lane);
+            }
+        }
+    }
     // the last workgroup to get here leaves both lists of the repair pass empty for the next call (every reader of n_list ran
     // before this kernel, every reader of n_clist is a workgroup of it that has counted itself in)
     // (only the workgroups that had a chunk to work on count themselves in -- min(grid, listed chunks) of them, a number every workgroup
     // knows; with nothing listed workgroup 0 does the reset: 256 fences and atomics on one word cost the kernel 3 of its 15 us)
-    const int n_part = min((int)gridDim.x, n_listed);
+    const int n_part = min(n_repick, n_listed);
     if (d == 0 && ((int)blockIdx.x < n_part || (n_part == 0 && blockIdx.x == 0))) {
         __threadfence();
         if (atomicAdd(p.n_clist + 1, 1) >= max(n_part, 1) - 1) { *p.n_list = 0; *p.n_clist = 0; p.n_clist[1] = 0; }
     }
 }
-template __global__ void k_scan_repick<2>(ScanPickArgs);
-template __global__ void k_scan_repick<6>(ScanPickArgs);
-template __global__ void k_scan_repick<8>(ScanPickArgs);
+template __global__ void k_scan_repick<2, false>(ScanPickArgs);
+template __global__ void k_scan_repick<6, false>(ScanPickArgs);
+template __global__ void k_scan_repick<8, false>(ScanPickArgs);
+template __global__ void k_scan_repick<2, true>(ScanPickArgs);
+template __global__ void k_scan_repick<6, true>(ScanPickArgs);
+template __global__ void k_scan_repick<8, true>(ScanPickArgs);
 
 // k_repair_patch: a fixed grid walks the rows of this pass, 128 threads per row: the exact row (sum of the repair contraction's
 // split-K partial maps, plane 0 first) replaces plane 0 of the map, the other planes of that row become zero; the group's

@@ -48,20 +48,6 @@ __global__ __launch_bounds__(256) void k_bf_table(float2 *tab, const float *grid
     }
 }
 
-// (x_a, x_b) * w for two consecutive points whose window samples share a register pair: op_sel broadcasts the low / high half
-__device__ __forceinline__ float2 win_lo(float a, float b, v2f w)
-{
-    v2f x = {a, b}, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(x), "v"(w));
-    return from_v2f(r);
-}
-__device__ __forceinline__ float2 win_hi(float a, float b, v2f w)
-{
-    v2f x = {a, b}, r;
-    asm("v_pk_mul_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "v"(x), "v"(w));   // w in src0: its high half may feed the low result there (fft512.h, RULE)
-    return from_v2f(r);
-}
-
 // grid (workgroups per array, arrays) x 256 threads = 4 waves.  Per frame: for each channel pair the windowed samples
 // (z = (x_a, x_b) w), the 1024-point transform, W += Z T[doa bin]; then the inverse transform of W, whose real part is the
 // beamformed frame.  A wave's work is ONE loop over its (frame, pair) steps with the same loads in every step -- the next
@@ -767,23 +753,25 @@ __global__ __launch_bounds__(64) void k_steer_table(float4 *rows, float2 *q, flo
 }
 
 // grid (workgroups) x 256, 4 waves; wave w of workgroup b takes the frames (4 b + w) + 4 gridDim.x i of the pass, array by array.
-// Per pair the steps of k_stft_phat_wave up to the separated spectra 2 X_a, 2 X_b -- the same transform, balance and mirror exchange,
-// hence the same bits -- and steer_mac / steer_nyquist on them in the same order.
+// Every frame goes through steer_patch_frame (steer.h).  The stand-alone patch pass: the calls whose second pick did not patch (FP16, calls
+// the adaptive mode does not take, calls that did not steer ahead).
 __global__ __launch_bounds__(256, 2) void k_steer_patch(SteerPatchArgs p)
 {
-    constexpr int NP = 4, MT = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *tab = reinterpret_cast<float2 *>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float2 *buf = tab + F1K_TWORDS + wave * F1K_SCRATCH;
     const int npass = p.f1 - p.f0, stride = 4 * (int)gridDim.x;
-    // nothing to do for this workgroup (the usual case behind an analysis that steered ahead): the lanes look at the waves' frames side by side
+    // nothing to do for this workgroup (the usual case behind an analysis that steered ahead): the lanes look at the wave's frames of
+    // every array side by side -- lane item = (array, frame of the wave), prediction and pick requested together -- so the look is one
+    // round trip for up to 64 items, not one per array
     int work = p.all;
     if (!work) {
-        for (int a = 0; a < p.n_arrays; ++a) {
-            const int pred = p.bf.pred[a];
-            for (int fo = (int)blockIdx.x * 4 + wave + stride * lane; fo < npass; fo += stride * 64)
-                work |= p.doa_bin[(long long)a * p.n_frames + p.f0 + fo] != pred;
+        const int first = (int)blockIdx.x * 4 + wave;
+        const int per = first < npass ? (npass - first + stride - 1) / stride : 0, items = per * p.n_arrays;
+        for (int i = lane; i < items; i += 64) {
+            const int a = i / per, fo = first + stride * (i - a * per);
+            work |= p.doa_bin[(long long)a * p.n_frames + p.f0 + fo] != p.bf.pred[a];
         }
     }
     if (!__syncthreads_or(work)) return;
@@ -791,8 +779,6 @@ __global__ __launch_bounds__(256, 2) void k_steer_patch(SteerPatchArgs p)
     F1kLane lc;
     lc.init(lane);
     __syncthreads();
-    const int lam = lane <= 32 ? lane : 96 - lane;
-    const bool self = (lane & 31) == 0;
     v2f win[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { win[i].x = p.window[lane + 128 * i]; win[i].y = p.window[lane + 128 * i + 64]; }
@@ -805,73 +791,7 @@ __global__ __launch_bounds__(256, 2) void k_steer_patch(SteerPatchArgs p)
             const int bin = __builtin_amdgcn_readfirstlane(p.doa_bin[(long long)a * p.n_frames + f]);
             if (bin != pred) ++missed;
             else if (!every) continue;
-            const float4 *srow = p.bf.rows + (long long)(bin + 1) * (NP * 64);
-            const float2 *qrow = p.bf.q + (long long)(bin + 1) * (MT * 8);            // (wave-uniform)
-            const float *base = p.pcm + (long long)a * p.array_stride + (long long)f * FFT_H;
-            float2 *yrow = p.bf.Y + ((long long)a * p.y_frames + f - p.y_f0) * STEER_ROW;
-            float xa[16], xb[16];
-            auto load_pair = [&](int pr) {
-                const float *pa = base + (long long)(2 * pr) * p.mic_stride, *pb = pa + p.mic_stride;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { xa[i] = pa[(unsigned)lane + 64 * i]; xb[i] = pb[(unsigned)lane + 64 * i]; }
-            };
-            load_pair(0);
-            float2 Y[8], zn[NP];
-#pragma unroll
-            for (int pr = 0; pr < NP; ++pr) {
-                float2 z[16];
-                float4 B;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { z[2 * i] = win_lo(xa[2 * i], xb[2 * i], win[i]); z[2 * i + 1] = win_hi(xa[2 * i + 1], xb[2 * i + 1], win[i]); }
-                float ma = max3abs(z[0].x, z[1].x, z[2].x), mb = max3abs(z[0].y, z[1].y, z[2].y);
-#pragma unroll
-                for (int i = 3; i < 15; i += 2) { ma = max3abs(ma, z[i].x, z[i + 1].x); mb = max3abs(mb, z[i].y, z[i + 1].y); }
-                ma = max2abs(ma, z[15].x); mb = max2abs(mb, z[15].y);
-                const PairBalance pb = pair_balance(ma, mb);
-                if (pb.scaled()) {
-                    const float sa = pb.sa(), sb = pb.sb();
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) z[i] = make_float2(z[i].x * sa, z[i].y * sb);
-                }
-                fft1024c<false, 3>(z, buf, lane, tab, lc, [&]() {
-                    B = (srow + pr * 64)[(unsigned)lane];
-                    if (pr < NP - 1) load_pair(pr + 1);
-                }, lam);
-                const float un_a = pb.un_a(), un_b = pb.un_b();
-                zn[pr] = make_float2(z[dr16(8)].x * un_a, z[dr16(8)].y * un_b);
-                const float4 Bu = steer_base(B, un_a, un_b);
-                // the mirror exchange of k_stft_phat_wave
-                if (lane == 0) {
-                    float2 t[16];
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) t[j] = z[dr16(j)];
-#pragma unroll
-                    for (int j = 8; j < 16; ++j) z[dr16(j < 12 ? j + 4 : j - 4)] = t[(j + 1) & 15];
-                } else if (self) {
-#pragma unroll
-                    for (int j = 8; j < 12; ++j) { const float2 t = z[dr16(j)]; z[dr16(j)] = z[dr16(j + 4)]; z[dr16(j + 4)] = t; }
-                } else {
-#pragma unroll
-                    for (int j = 8; j < 12; ++j) {
-                        float2 &u = z[dr16(j)], &w = z[dr16(j + 4)];
-                        swap_rows32(u.x, w.x); swap_rows32(w.x, u.x);
-                        swap_rows32(u.y, w.y); swap_rows32(w.y, u.y);
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const float2 zk = z[dr16(s)], zm = z[dr16(15 - s < 12 ? 15 - s + 4 : 15 - s - 4)];
-                    const float2 a2 = make_float2(zk.x + zm.x, zk.y - zm.y);                               // 2 X_a
-                    const float2 b2 = make_float2(zk.y + zm.y, zm.x - zk.x);                               // 2 X_b
-                    const float2 y = pr == 0 ? make_float2(0.f, 0.f) : Y[s];
-                    if (s == 0) Y[s] = steer_mac<true>(y, a2, b2, Bu, a2, b2);
-                    else Y[s] = steer_mac<false>(y, a2, b2, Bu, qrow[(2 * pr) * 8 + s], qrow[(2 * pr + 1) * 8 + s]);
-                }
-                wave_lds_fence();
-            }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) yrow[(unsigned)lam + 64 * s] = s == 0 ? steer_dc(Y[s], lane) : Y[s];
-            if (lane == 0) yrow[FFT_H] = make_float2(steer_nyquist<NP>(zn, p.bf.nyq + (bin + 1) * MT), 0.f);
+            steer_patch_frame(p, a, f, bin, win, buf, tab, lc, lane);
         }
         if (missed && lane == 0) { atomicAdd(p.miss, (unsigned long long)missed); if (pred >= 0) atomicAdd(p.miss + 1, (unsigned long long)missed); }   // ([1]: the guard's -- an array without a pick yet misses by construction)
     }
@@ -895,6 +815,7 @@ __global__ __launch_bounds__(256) void k_steer_synth(SteerSynthArgs p)
         p.miss_total[2] = tot;
         __hip_atomic_store(&p.report[1], p.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+    if (p.n_miss && blockIdx.x == 0 && a == 0 && tid == 0) *p.n_miss = 0;        // the miss list of the second pick: every reader ran before this launch
     const int t0 = p.f0 + ((int)blockIdx.x * 4 + wave) * p.ft, t1 = min(t0 + p.ft, p.f1);
     if (t0 >= t1) return;
     const float2 *Yb = p.Y + ((long long)a * p.y_frames - p.y_f0) * STEER_ROW;

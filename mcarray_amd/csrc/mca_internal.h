@@ -82,7 +82,9 @@ struct SteerArgs {
     float2 *Y;               // [arrays][total_frames][STEER_ROW]
 };
 // k_steer_patch: the frames whose pick is not the predicted bin (all = 1: every frame -- the analysis of this call did not steer) through
-// the same routine at their final bins, one wave per frame, a fixed grid striding over the call's frames; counts the misses
+// the same routine at their final bins, one wave per frame, a fixed grid striding over the call's frames; counts the misses.
+// An ADAPTIVE call that steered ahead has no such launch: its second pick patches (k_scan_repick<PL, true>, STEER_TAIL_WGS).
+constexpr int STEER_TAIL_WGS = 256;       // k_scan_repick<PL, true>: workgroups behind the re-pick ones that stride over the miss list
 constexpr int STEER_PATCH_WGS = 512;      // k_steer_patch: a fixed grid (two workgroups per CU) strides over the frames
 struct SteerPatchArgs {
     const float *pcm; long long array_stride, mic_stride;
@@ -103,6 +105,7 @@ struct SteerSynthArgs {
     const float *tail_in; float *tail_out;    // [arrays][hop] the carry into hop f0 / out of frame f1 - 1 (the stream's, or the one between two passes)
     const int *doa_bin; int *pred_out;        // pred_out: NULL unless this is the call's last pass
     unsigned long long *report; unsigned long long seq; unsigned long long *miss_total;   // last pass: the call's missed frames and its number, to page-locked memory
+    int *n_miss;             // the length of the miss list (ScanPickArgs::n_miss), emptied here for the next call; NULL: the second pick did not patch
 };
 
 struct StftPhatArgs {
@@ -233,6 +236,15 @@ struct ScanPickArgs {
     // per unit (k_scan_pick ORs a flagged frame's candidate columns into every unit it lists; cand_unit -- one workgroup per unit -- takes
     // and clears them and releases the unit's test-and-set word).  NULL: whole rows (k_srp_gemm_repair + k_repair_patch).
     unsigned *umask; int umask_words;
+    // steered tail: the frames whose final pick is not the predicted bin are patched inside the second-pick launch.  k_scan_pick<PL, 1>
+    // appends the misses of a chunk WITHOUT a flagged frame (its coarse picks are final; one batch per chunk: SCAN_SUB == SCAN_CHUNK) to
+    // the miss list n_miss[1 ...] (entry = array * n_frames + frame, each frame at most once; n_miss[0] is its length, miss_cap its
+    // room: a call's frames, and the list is empty when a call starts).  The last STEER_TAIL_WGS workgroups of k_scan_repick<PL, true>
+    // stride over the list, patch and count; the workgroup that owns a chunk WITH a flagged frame patches and counts that chunk's misses
+    // itself once its final picks are out.  NULL unless the call is an ADAPTIVE one whose analysis steered ahead (api.hip,
+    // localise_impl); *n_miss is reset by k_steer_synth, which runs behind every reader.
+    int *n_miss; int miss_cap;
+    SteerPatchArgs sp;       // what steer_patch_frame reads, and pred / miss (all = 0, the whole call in Y)
 };
 
 // The repair contraction runs on however many rows the coarse pass listed (a device-side count): the K range is what
