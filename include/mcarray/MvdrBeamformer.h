@@ -80,6 +80,16 @@ public:
         check(mca_hip_mvdr_get_null_gain(_ctx, &g));
         return g;
     }
+    // Soft nulls at ESTIMATED steering vectors (mca_hip_mvdr_set_rtf_nulls): processRtf(), and processAuto() with setRtf() enabled,
+    // honour setNullGain() with the nulls at the vectors the frame itself uses for the other look directions.  Off by default, and
+    // then those calls refuse a non-zero null gain.  May change between chunks; no part of the stream's state.
+    void setRtfNulls(bool enable) { check(mca_hip_mvdr_set_rtf_nulls(_ctx, enable ? 1 : 0)); }
+    bool getRtfNulls() const
+    {
+        int e = 0;
+        check(mca_hip_mvdr_get_rtf_nulls(_ctx, &e));
+        return e != 0;
+    }
     // The decision-directed Wiener post-filter on the outputs of both process() overloads (mca_hip_mvdr_set_postfilter): smoothing in
     // [0, 1), gainFloor in [0, 1], noiseScale in (0, 100].  Enabling starts the filter's state from zero, disabling frees it; the three
     // values may change between chunks without touching that state.

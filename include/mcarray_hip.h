@@ -747,7 +747,7 @@ int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_postfi
  *   target_mask_dev [streams][n_sources][F][K] float   contiguous; NULL = all 0: nothing is learned and the held Psi steers
  *   update_mask_dev [streams][F][K] float              as in the masked call; NULL = all 1
  * mca_hip_mvdr_sources_frames_rtf_* on a context without RTF enabled is MCA_HIP_ERR_INVALID_ARGUMENT; with a null gain != 0 it is
- * MCA_HIP_ERR_UNSUPPORTED (nulls at estimated vectors are not built); the other argument checks are those of the masked call.  The
+ * MCA_HIP_ERR_UNSUPPORTED unless mca_hip_mvdr_set_rtf_nulls (below) has enabled nulls at estimated vectors; the other argument checks are those of the masked call.  The
  * steering plane [streams][n_sources][frames][K][M] (8 bytes each) is workspace with a cap of 1 GiB
  * (mca_hip_mvdr_set_rtf_workspace(ctx, max_bytes >= 8) sets another; a processing parameter): a call above it is cut along the
  * frames internally, a frame at a time at the least, which changes no byte.  The host call stages both masks.  Exact points:
@@ -818,8 +818,8 @@ int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, 
  *   - on a context without RTF exactly what mca_hip_mvdr_sources_frames_masked_* does with the update mask (the target masks are
  *     still written if asked for).
  * The bytes of spectra, audio and state are those of that call fed the masks this one returns.  Without the estimator enabled the
- * call is MCA_HIP_ERR_INVALID_ARGUMENT; whatever the underlying call refuses is refused with that call's code (a null gain with RTF:
- * MCA_HIP_ERR_UNSUPPORTED).  The seven other mca_hip_mvdr_*frames* calls are untouched on any context: the same kernels launched, the
+ * call is MCA_HIP_ERR_INVALID_ARGUMENT; whatever the underlying call refuses is refused with that call's code (a null gain with RTF and
+ * without mca_hip_mvdr_set_rtf_nulls: MCA_HIP_ERR_UNSUPPORTED).  The seven other mca_hip_mvdr_*frames* calls are untouched on any context: the same kernels launched, the
  * same bytes.  The host call stages the masks it hands back. */
 typedef struct {
     int struct_size;
@@ -836,6 +836,33 @@ int mca_hip_mvdr_sources_frames_auto_dev(mca_hip_mvdr_ctx *ctx, const float *pcm
                                          float *update_mask_out_dev, float *target_mask_out_dev, float *out_pcm_dev, float *out_spec_dev, void *stream);
 int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *ctx, const float *pcm, int n_streams, int n_frames, int n_sources,
                                           const float *doa_rad, float *update_mask_out, float *target_mask_out, float *out_pcm, float *out_spec);
+/* Soft nulls at ESTIMATED steering vectors: with enable = 1 the calls that steer by the RTF -- mca_hip_mvdr_sources_frames_rtf_* and,
+ * on a context with RTF enabled, mca_hip_mvdr_sources_frames_auto_* -- honour the null gain (mca_hip_mvdr_set_null_gain) instead of
+ * refusing it.  A talker whose cells the update mask protects is kept out of the noise covariance, so the weights of output s do
+ * nothing against talker r; the null puts it back as a virtual interferer along the vector the frame itself uses for r (DESIGN.md
+ * 4.10).  Per stream, bin and frame, with d_s the vector the frame uses for slot s -- the RTF, or g0 where the estimator fell back:
+ * exactly what the estimator above left for the solve -- PhiL the loaded covariance and g = null_gain:
+ *     p_r   = 1 / (d_r^H PhiL^-1 d_r)
+ *     Phi_s = PhiL + g * sum_{r != s} p_r d_r d_r^H
+ *     w_s   = Phi_s^-1 d_s / (d_s^H Phi_s^-1 d_s),  Y_s = w_s^H x
+ *   - scale: p_r d_r d_r^H does not depend on the scale of d_r, so the normalisation of the RTF to the reference microphone does not
+ *     enter the nulls; it sets only the scale of the own output, as without nulls (w_s^H d_s = 1 for every g);
+ *   - a bin whose noise trace is <= 1e-30 keeps w = g0 / M per direction;
+ *   - the post-filter's p stays the plain noise_scale / (d_s^H PhiL^-1 d_s) with the d_s the frame used, as under geometric nulls;
+ *   - the recursions of Phi, tr, Psi, cpsi and cphi see neither the gain nor this switch: the state a call leaves is the same bytes
+ *     for every g (the exceptions follow the output: the post-filter's A, and the overlap-add tails of a call with out_pcm);
+ *   - g == 0, a gain that rounds to 0 in fp32, or n_sources == 1 launch the kernels of the call without nulls and give its bytes,
+ *     whatever the switch is;
+ *   - on fresh RTF state with a NULL target mask every d is g0, and the RTF call gives the bytes of
+ *     mca_hip_mvdr_sources_frames_masked_* under the same update mask and the same g, in spectra, audio and covariance;
+ *   - how a stream is cut into calls, the workspace cap and where a stream sits in the batch change no byte, as without nulls.
+ * With enable = 0 (the default) those calls are as they were: a null gain != 0 is MCA_HIP_ERR_UNSUPPORTED.  The seven other
+ * mca_hip_mvdr_*frames* calls are untouched by the switch, the auto call on a context without RTF among them (it honours the null
+ * gain at the geometric vectors, through the masked call).  Accepted: 0 or 1; anything else is MCA_HIP_ERR_INVALID_ARGUMENT and
+ * leaves the switch as it was.  A processing parameter like the null gain: it may change between calls, may be set whether or not
+ * RTF is enabled, and state blobs neither carry nor check it. */
+int mca_hip_mvdr_set_rtf_nulls(mca_hip_mvdr_ctx *ctx, int enable);
+int mca_hip_mvdr_get_rtf_nulls(const mca_hip_mvdr_ctx *ctx, int *enable);
 /* Capon (minimum-variance) spatial spectrum of the covariance the context holds now (after its last frames call or state load),
  * and its peaks: the MVDR power estimate p = 1 / (d^H PhiL^-1 d) of the nulls above on a grid of angles.  Per stream, with
  *     theta_i      = -pi/2 + i pi/(D-1), i = 0 ... D-1 (in double),       D = n_angles

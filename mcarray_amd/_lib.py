@@ -260,6 +260,8 @@ SYMBOLS = [
     ("mca_hip_mvdr_set_max_sources", C.c_int, [C.c_void_p, C.c_int]),
     ("mca_hip_mvdr_set_null_gain", C.c_int, [C.c_void_p, C.c_double]),
     ("mca_hip_mvdr_get_null_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("mca_hip_mvdr_set_rtf_nulls", C.c_int, [C.c_void_p, C.c_int]),
+    ("mca_hip_mvdr_get_rtf_nulls", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("mca_hip_mvdr_set_postfilter", C.c_int, [C.c_void_p, C.POINTER(MvdrPostfilterConfig)]),
     ("mca_hip_mvdr_get_postfilter", C.c_int, [C.c_void_p, C.POINTER(MvdrPostfilterConfig)]),
     ("mca_hip_mvdr_sources_frames_dev", C.c_int,

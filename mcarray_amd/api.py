@@ -880,12 +880,14 @@ class MvdrBeamformer(_StateBlob):
     set_mask_estimator() and estimate_masks=True of the process calls: both masks are formed on the device from the call's own
     spectra, by the steered coherence of every cell towards the call's look directions, and come back in the result
     (mca_hip_mvdr_set_mask_estimator, mca_hip_mvdr_sources_frames_auto_*).  Not together with a caller's update=, update_mask= or
-    target_mask=."""
+    target_mask=.
+    set_rtf_nulls() / rtf_nulls=True: the calls that steer by estimated vectors honour null_gain, with the nulls at the vectors the
+    frame itself uses for the other look directions (mca_hip_mvdr_set_rtf_nulls); without it they refuse a non-zero null gain."""
 
     K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK = 0, 1, 2, 3, 4, 5, 6
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
-                 null_gain=0.0):
+                 null_gain=0.0, rtf_nulls=False):
         self._lib = _lib.load()
         xyz = _xyz(mic_positions)
         cfg = _lib.MvdrConfig()
@@ -913,6 +915,8 @@ class MvdrBeamformer(_StateBlob):
                 self.set_max_sources(max_sources)
             if null_gain != 0.0:
                 self.set_null_gain(null_gain)
+            if rtf_nulls:
+                self.set_rtf_nulls(True)
         except MCArrayHipError:
             self.close()
             raise
@@ -932,6 +936,17 @@ class MvdrBeamformer(_StateBlob):
         g = C.c_double(0.0)
         self._check(self._lib.mca_hip_mvdr_get_null_gain(self.h, C.byref(g)))
         return g.value
+
+    def set_rtf_nulls(self, enable=True):
+        """let the calls with target_mask= or estimate_masks=True on an RTF context honour the null gain, at the estimated vectors
+        (mca_hip_mvdr_set_rtf_nulls).  A processing parameter like the null gain; off by default, and then such a call refuses a
+        non-zero null gain."""
+        self._check(self._lib.mca_hip_mvdr_set_rtf_nulls(self.h, 1 if enable else 0))
+
+    def get_rtf_nulls(self):
+        e = C.c_int(0)
+        self._check(self._lib.mca_hip_mvdr_get_rtf_nulls(self.h, C.byref(e)))
+        return bool(e.value)
 
     def set_postfilter(self, enable=True, smoothing=0.98, gain_floor=0.1, noise_scale=1.0):
         """the decision-directed Wiener post-filter on the outputs of every process call (include/mcarray_hip.h,

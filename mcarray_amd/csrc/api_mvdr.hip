@@ -30,6 +30,8 @@ struct mca_hip_mvdr_ctx {
     int max_sources = 1;          // look directions per frame a call may carry (mca_hip_mvdr_set_max_sources)
     double null_gain = 0.0;       // soft nulls at the other look directions of a call with n_sources >= 2 (mca_hip_mvdr_set_null_gain);
                                   // a processing parameter, not stream state: no part of the state blobs
+    bool rtf_nulls = false;       // the RTF-bodied calls honour null_gain, at the vectors of the steering plane (mca_hip_mvdr_set_rtf_nulls);
+                                  // a processing parameter like null_gain
     float *d_tail[2] = {nullptr, nullptr}; int tail_cur = 0;   // [max_streams][max_sources][H]; a single-look call uses slot 0
     // the Wiener post-filter (mca_hip_mvdr_set_postfilter): the three values are processing parameters like null_gain; A is stream state
     bool pf_on = false;
@@ -389,6 +391,21 @@ int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *c, double *null_gain)
     return MCA_HIP_OK;
 }
 
+int mca_hip_mvdr_set_rtf_nulls(mca_hip_mvdr_ctx *c, int enable)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (enable != 0 && enable != 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
+    c->rtf_nulls = enable == 1;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_rtf_nulls(const mca_hip_mvdr_ctx *c, int *enable)
+{
+    if (!c || !enable) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    *enable = c->rtf_nulls ? 1 : 0;
+    return MCA_HIP_OK;
+}
+
 int mca_hip_mvdr_set_postfilter(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_postfilter_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
@@ -602,7 +619,9 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
         sa.update = (update ? update : c->d_rtf_ones) + (size_t)f0 * c->K;
         sa.X += (size_t)f0 * c->K * c->M; sa.Y += (size_t)f0 * c->K;
         if (sa.pn) sa.pn += (size_t)f0 * c->K;
-        kernel = c->pf_on ? mvdr_solve_rtf_kernel_of<true>(Q, c->M == 4 * Q, n_sources) : mvdr_solve_rtf_kernel_of<false>(Q, c->M == 4 * Q, n_sources);
+        // nulls at the vectors of the plane (mvdr_frames_dev lets a gain through only under mca_hip_mvdr_set_rtf_nulls); else the RTF kernels
+        if (nulls) kernel = c->pf_on ? mvdr_solve_rtf_nulls_kernel_of<true>(Q, n_sources, &lds) : mvdr_solve_rtf_nulls_kernel_of<false>(Q, n_sources, &lds);
+        else kernel = c->pf_on ? mvdr_solve_rtf_kernel_of<true>(Q, c->M == 4 * Q, n_sources) : mvdr_solve_rtf_kernel_of<false>(Q, c->M == 4 * Q, n_sources);
     } else
         kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
                                    c->pf_on, &lds);
@@ -749,7 +768,8 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (est && !c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
     if (rtf && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
-    if (rtf && c->null_gain != 0.0) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0");
+    if (rtf && c->null_gain != 0.0 && !c->rtf_nulls)
+        return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0, or enable them (mca_hip_mvdr_set_rtf_nulls)");
     if (n_sources < 1 || n_sources > c->max_sources)
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
     if (!pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");

@@ -83,6 +83,9 @@ const void *mvdr_solve_kernel(int Q, bool full, int S, bool nulls, MvdrWeight w,
 // the solve with the right-hand sides from the steering plane of k_mvdr_rtf (mvdr_solve.h; kernels_mvdr_solve_rtf*.hip)
 template <int Q, bool FULL, int S, int S1, bool PF, bool NOISE> __global__ void k_mvdr_solve_rtf_t(MvdrSolveArgs p);
 template <bool NOISE> const void *mvdr_solve_rtf_kernel_of(int Q, bool full, int S);
+// the same with soft nulls at the vectors of the plane (kernels_mvdr_solve_rtf_nulls*.hip)
+template <int Q, int S, int S1, bool PF, bool NOISE> __global__ void k_mvdr_solve_rtf_nulls_t(MvdrSolveArgs p);
+template <bool NOISE> const void *mvdr_solve_rtf_nulls_kernel_of(int Q, int S, int *lds_bytes);
 template <int Q> __global__ void k_mvdr_rtf(MvdrRtfArgs p);                     // target covariances and estimated steering vectors
 template <int Q> __global__ void k_mvdr_rtf_steering(MvdrRtfSteerArgs p);
 const void *mvdr_rtf_kernel(int Q, bool steering);                              // kernels_mvdr_rtf.hip

@@ -1,5 +1,6 @@
-// mvdr_solve.h -- k_mvdr_solve_t, the one template of the MVDR solve (gfx950), its arm k_mvdr_solve_rtf_t that takes the
-// steering vectors from a plane (4.8), and the lookups that instantiate them.
+// mvdr_solve.h -- k_mvdr_solve_t, the one template of the MVDR solve (gfx950), its arms k_mvdr_solve_rtf_t that takes the
+// steering vectors from a plane (4.8) and k_mvdr_solve_rtf_nulls_t that puts soft nulls at those vectors (4.10), and the lookups that
+// instantiate them.
 // The translation units kernels_mvdr_solve_*.hip instantiate one (WEIGHT, NOISE) group each (build parallelism, nothing else); the
 // hand-written single-look kernel k_mvdr_solve of kernels_mvdr.hip shares the helpers below.
 //
@@ -104,10 +105,13 @@ namespace mca {
 // phasors T but read from the steering plane D [stream][slot][frame][bin][mic] that k_mvdr_rtf (kernels_mvdr_rtf.hip) wrote -- the
 // way X is read -- and so is the vector of the silence branch (k_mvdr_rtf leaves the geometric vector in the cells of a silent bin).
 // Nothing else differs: a plane that holds cmul(T_hi, T_lo) gives the bits of the kernel without RTF.
+// RTF with NULLS (4.10): the nulls algebra needs only U = L^-1 [d_0 ... d_{S-1}] and p_r d_r d_r^H does not depend on the scale of d_r,
+// so the vectors of the plane -- normalised to the reference microphone, or the geometric vector where the estimator fell back --
+// enter it as they are.
 template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, MvdrWeight WEIGHT, bool NOISE, bool RTF>
 __device__ __forceinline__ void mvdr_solve_body(const MvdrSolveArgs &p)
 {
-    static_assert(!RTF || (!NULLS && WEIGHT == MvdrWeight::CELL), "the steering plane comes with the masks; nulls at estimated vectors are not built");
+    static_assert(!RTF || WEIGHT == MvdrWeight::CELL, "the steering plane comes with the masks");
     constexpr bool WEIGHTED = WEIGHT != MvdrWeight::NONE, CELL = WEIGHT == MvdrWeight::CELL;
     static_assert(!REUSE || WEIGHT == MvdrWeight::FRAME, "no frame is frozen without weights; a wave of quads with weights of their own would run both column bodies");
     static_assert(S >= 1 && S <= MCA_MAX_SOURCES && S1 >= 1 && S % S1 == 0, "look directions per frame, in whole passes");
@@ -439,6 +443,14 @@ __global__ __launch_bounds__(256, 2) void k_mvdr_solve_rtf_t(MvdrSolveArgs p)
     mvdr_solve_body<Q, FULL, S, S1, PF, false, false, MvdrWeight::CELL, NOISE, true>(p);
 }
 
+// the nulls of k_mvdr_solve_t at the vectors of the steering plane (mca_hip_mvdr_set_rtf_nulls); dynamic LDS
+// mvdr_nulls_lds_bytes.  One instantiation serves M = 4Q and M < 4Q, as in the nulls kernel without RTF
+template <int Q, int S, int S1, bool PF, bool NOISE>
+__global__ __launch_bounds__(256, 2) void k_mvdr_solve_rtf_nulls_t(MvdrSolveArgs p)
+{
+    mvdr_solve_body<Q, false, S, S1, PF, true, false, MvdrWeight::CELL, NOISE, true>(p);
+}
+
 // The instantiation of a call, or nullptr where the build has none, and the dynamic LDS of its workgroups.  The definition is the
 // row list: it names every (Q, FULL, S, NULLS) of mvdr_solve_row with the form of mvdr_solve_form, once, and a translation unit
 // that instantiates it for its (WEIGHT, NOISE) thereby instantiates those kernels.
@@ -470,6 +482,22 @@ const void *mvdr_solve_rtf_kernel_of(int Q, bool full, int S)
         constexpr bool RFULL = r & 1;
         constexpr MvdrSolveForm f = mvdr_solve_form(RQ, RFULL, RS, false, MvdrWeight::CELL, NOISE);
         if (Q == RQ && full == RFULL && S == RS) kernel = reinterpret_cast<const void *>(k_mvdr_solve_rtf_t<RQ, RFULL, RS, f.S1, f.PF, NOISE>);
+    });
+    return kernel;
+}
+
+// The same for k_mvdr_solve_rtf_nulls_t: every (Q, S >= 2), with the form of the CELL nulls row, and the dynamic LDS of its workgroups.
+template <bool NOISE>
+const void *mvdr_solve_rtf_nulls_kernel_of(int Q, int S, int *lds_bytes)
+{
+    const void *kernel = nullptr;
+    mvdr_static_for<0, 4 * (MCA_MAX_SOURCES - 1)>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, RQ = r / (MCA_MAX_SOURCES - 1) + 1, RS = r % (MCA_MAX_SOURCES - 1) + 2;
+        constexpr MvdrSolveForm f = mvdr_solve_form(RQ, false, RS, true, MvdrWeight::CELL, NOISE);
+        if (Q == RQ && S == RS) {
+            kernel = reinterpret_cast<const void *>(k_mvdr_solve_rtf_nulls_t<RQ, RS, f.S1, f.PF, NOISE>);
+            *lds_bytes = mvdr_nulls_lds_bytes(RQ, RS, f.S1);
+        }
     });
     return kernel;
 }

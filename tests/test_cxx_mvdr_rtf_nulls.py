@@ -1,0 +1,35 @@
+"""Builds the C++ test of mca::MvdrBeamformer::setRtfNulls / getRtfNulls (tests/cxx/test_mvdr_rtf_nulls.cpp) against the header, and
+runs it on the GPU: with the switch on, processRtf() under a null gain changes both outputs of a two-direction call and leaves the
+covariance; with gain 0 it moves no byte; switched off again, the call refuses the gain."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cxx", "test_mvdr_rtf_nulls.cpp")
+
+
+def _cxx():
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    return cxx
+
+
+def test_cxx_program_compiles_against_the_header(tmp_path):
+    """plain C++11 with every warning: the declarations and both template overloads instantiate"""
+    subprocess.check_call([_cxx(), "-std=c++11", "-O0", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c", SRC,
+                           "-o", str(tmp_path / "test_mvdr_rtf_nulls.o")], timeout=300)
+
+
+@pytest.mark.gpu
+def test_cxx_process_rtf_under_nulls_on_gpu(tmp_path):
+    exe = tmp_path / "test_mvdr_rtf_nulls"
+    lib_dir = os.path.join(ROOT, "mcarray_amd")
+    subprocess.check_call([_cxx(), "-std=c++11", "-O2", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"), SRC, "-o", str(exe), "-L" + lib_dir,
+                           "-lmcarray_hip", "-Wl,-rpath," + lib_dir], timeout=300)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ALL PASSED" in r.stdout

@@ -17,7 +17,9 @@ wave); a build without the masked entry points (MCA_HIP_LIB) runs the first two 
 JSON line for one and one for two look directions: k_mvdr_rtf, the solve that reads the steering plane beside the masked (CELL) solve
 under the same update mask, and both calls' totals; update mask and target masks are complementary blocks of 4 frames x 16 bins.  --estmask times the table of DESIGN.md 4.9, one JSON line for one and one for two look directions: k_mvdr_estmask against its own
 traffic (X and T read, S + 1 masks written) as a share of the measured float4 copy rate, and the auto call's total beside the RTF
-call fed the masks the auto call returned.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+call fed the masks the auto call returned.  --rtf-nulls times the table of DESIGN.md 4.10, one JSON line for two look directions: the solve
+of the RTF call at null gain 0 (k_mvdr_solve_rtf_t) and 100 (k_mvdr_solve_rtf_nulls_t, mca_hip_mvdr_set_rtf_nulls), the CELL nulls solve
+of the masked call at gain 100 under the same update mask, and the calls' totals; masks as in --rtf.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
 points it lacks are left unbound, --null-gain must then stay 0, --update none and --postfilter off (as far as the build lacks them)."""
 import argparse
 import json
@@ -124,6 +126,44 @@ def rtf_table(a, fs, N, xs, pcm, st):
         print(json.dumps(row), flush=True)
 
 
+def rtf_nulls_table(a, fs, N, xs, pcm, st, gain=100.0):
+    """the row of DESIGN.md 4.10: the RTF call without and with nulls at the estimated vectors beside the masked call with geometric
+    nulls, two look directions, the masks of rtf_table()"""
+    hop, K = N // 2, N // 2 + 1
+    dev = pcm.device
+    rng = np.random.default_rng(7)
+    S = 2
+    blocks = (rng.random((a.streams, S, (a.frames + 3) // 4, (K + 15) // 16)) < 0.5 / S).astype(np.float32)
+    tm = np.ascontiguousarray(np.repeat(np.repeat(blocks, 4, axis=2), 16, axis=3)[:, :, :a.frames, :K])
+    upd = torch.from_numpy(np.ascontiguousarray(1.0 - tm.max(axis=1))).to(dev)
+    tmask = torch.from_numpy(tm).to(dev)
+    look = torch.tensor(LOOK[:S], device=dev, dtype=torch.float32)
+    doa = look[None, None, :].expand(a.streams, a.frames, S).contiguous()
+    out = torch.empty((a.streams, S, a.frames * hop), device=dev, dtype=torch.float32)
+    row = dict(sources=S, null_gain=gain, postfilter=bool(a.postfilter), workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N))
+    for name, g, kw in (("rtf_g0", 0.0, dict(update_mask=upd, target_mask=tmask)), ("rtf_nulls", gain, dict(update_mask=upd, target_mask=tmask)),
+                        ("masked_nulls", gain, dict(update_mask=upd))):
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=S, null_gain=g, rtf_nulls=True)
+        if a.postfilter:
+            bf.set_postfilter(True)
+        if name != "masked_nulls":
+            bf.set_rtf(True)
+        step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **kw)
+        for _ in range(a.warmup):
+            step()
+        bf.set_timing(True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        torch.cuda.synchronize()
+        row[name + "_ms_per_step"] = (time.perf_counter() - t0) / a.steps * 1e3
+        n, ms = bf.get_timing(bf.K_SOLVE)
+        row[name + "_solve_ms"] = ms / max(n, 1)
+        bf.close()
+    print(json.dumps(row), flush=True)
+
+
 COPY_TBPS = 6.29       # the measured float4 copy rate of the MI355X (DESIGN.md 4.6)
 
 
@@ -192,6 +232,7 @@ def main():
     ap.add_argument("--mask", action="store_true", help="time the table of the time-frequency update masks (DESIGN.md 4.7)")
     ap.add_argument("--rtf", action="store_true", help="time the table of the estimated steering vectors (DESIGN.md 4.8)")
     ap.add_argument("--estmask", action="store_true", help="time the table of the mask estimator (DESIGN.md 4.9)")
+    ap.add_argument("--rtf-nulls", action="store_true", help="time the table of the nulls at estimated steering vectors (DESIGN.md 4.10)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -214,6 +255,8 @@ def main():
         return rtf_table(a, fs, N, xs, pcm, st)
     if a.estmask:
         return estmask_table(a, fs, N, xs, pcm, st)
+    if a.rtf_nulls:
+        return rtf_nulls_table(a, fs, N, xs, pcm, st)
     upd = None
     if a.update != "none":
         w = np.ones((a.streams, a.frames), dtype=np.float32)

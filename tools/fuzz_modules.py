@@ -1,5 +1,6 @@
 """Randomised parity sweep of the 2-channel masking module, the MVDR beamformer and its sources call with soft nulls against the CPU oracle, and of the MVDR auto
-call (estimated masks) against the call fed its masks (a one-off check like
+call (estimated masks) against the call fed its masks, and of the RTF call under a null gain (nulls at the estimated vectors) against its exact
+points (a one-off check like
 tools/fuzz_parity.py): random frame lengths, methods / algorithms, channel counts, geometries, memories, loadings, chunked calls.
 usage (GPU box): python tools/fuzz_modules.py [cases] [seed]"""
 import os
@@ -154,18 +155,63 @@ def mvdr_auto_case(rng):
     return ok, "%s assigned %.0f %%" % (tag, 100.0 * float((tm > 0).any(axis=1).mean()))
 
 
+def mvdr_rtf_nulls_case(rng):
+    """the RTF call under a null gain (mca_hip_mvdr_set_rtf_nulls) at its exact points: with a target mask of zeros on fresh state the
+    bytes of the masked call under the same update mask and gain; with random target masks the bytes do not depend on how the stream
+    is cut, the covariances are those of gain 0, and the gain moves the output; random geometry, frame size, S, gain and masks"""
+    fs, N = [(8000, 256), (16000, 512), (48000, 1024)][int(rng.integers(0, 3))]
+    M, S = int(rng.integers(2, 17)), int(rng.integers(2, 5))
+    xs = np.sort(rng.uniform(0, 0.03 * M, M))
+    F, A = int(rng.integers(2, 25)), int(rng.integers(1, 4))
+    gain = float(rng.choice([0.1, 1.0, 10.0, 100.0, 1000.0, rng.uniform(0.0, 100.0)]))
+    hop, K = N // 2, N // 2 + 1
+    pcm = np.stack([synth.noise_source_stream(xs, rng.uniform(-1.3, 1.3), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)))
+                    + synth.noise_source_stream(xs, rng.uniform(-1.3, 1.3), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)), snr_db=50)
+                    for _ in range(A)]).astype(np.float32)
+    doa = rng.uniform(-1.4, 1.4, (A, F, S)).astype(np.float32)
+    upd = rng.choice(np.array([0, 1, 1, .5], dtype=np.float32), size=(A, F, K))
+    tm = rng.choice(np.array([0, 0, 1, .5], dtype=np.float32), size=(A, S, F, K))
+    pf = bool(rng.integers(0, 2))
+    tag = "mvdr rtf nulls fs=%d N=%d M=%d S=%d A=%d F=%d gain=%.3g pf=%d" % (fs, N, M, S, A, F, gain, pf)
+
+    def run(g, rtf, tmask, cut=0):
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=A, max_sources=S, null_gain=g, rtf_nulls=True)
+        if pf:
+            bf.set_postfilter(True)
+        if rtf:
+            bf.set_rtf(True, iterations=int(1 + M % 4), ref_mic=int(M // 2))
+        kw = (lambda t0, t1: dict(target_mask=np.ascontiguousarray(tmask[:, :, t0:t1]))) if rtf else (lambda t0, t1: {})
+        rs = [bf.process_sources(pcm[:, :, t0 * hop:(t1 + 1) * hop].copy(), doa[:, t0:t1].copy(), update_mask=np.ascontiguousarray(upd[:, t0:t1]), **kw(t0, t1))
+              for t0, t1 in ([(0, cut), (cut, F)] if cut else [(0, F)])]
+        cov = [bf.covariance(a) for a in range(A)]
+        bf.close()
+        return np.concatenate([r["spec"] for r in rs], axis=2), np.concatenate([r["out"] for r in rs], axis=2), cov
+
+    def same(p, q):
+        return bool(np.array_equal(p[0].view(np.float32), q[0].view(np.float32), equal_nan=True) and np.array_equal(p[1], q[1], equal_nan=True)
+                    and all(np.array_equal(u, v) for u, v in zip(p[2], q[2])))
+
+    geometric = same(run(gain, True, np.zeros_like(tm)), run(gain, False, None))
+    whole, plain = run(gain, True, tm), run(0.0, True, tm)
+    cut = same(run(gain, True, tm, int(rng.integers(1, F))), whole)
+    state = all(np.array_equal(u, v) for u, v in zip(whole[2], plain[2]))
+    moved = gain == 0.0 or not np.array_equal(whole[0], plain[0])
+    ok = geometric and cut and state and moved and bool(np.isfinite(whole[1]).all())
+    return ok, "%s geometric plane %d cut %d state %d moved %d" % (tag, geometric, cut, state, moved)
+
+
 def main(cases, seed):
     rng = np.random.default_rng(seed)
     bad = 0
     for case in range(cases):
-        for fn in (mask_case, mvdr_case, mvdr_nulls_case, mvdr_auto_case):
+        for fn in (mask_case, mvdr_case, mvdr_nulls_case, mvdr_auto_case, mvdr_rtf_nulls_case):
             try:
                 ok, msg = fn(rng)
             except api.MCArrayHipError as e:
                 ok, msg = False, "%s raised %s" % (fn.__name__, e)
             print(("ok   " if ok else "FAIL ") + "case %d: %s" % (case, msg), flush=True)
             bad += 0 if ok else 1
-    print("%d cases x 4, %d failures" % (cases, bad))
+    print("%d cases x 5, %d failures" % (cases, bad))
     return 1 if bad else 0
 
 
