@@ -202,6 +202,46 @@ public:
         doaRadians.assign(d.begin(), d.end());
         values.assign(v.begin(), v.end());
     }
+    // Tracks of the look directions, kept on the device between chunks (mca_hip_mvdr_tracks_*): nTracks 1 ... maxSources slots, of which
+    // the first nOwn follow their own target covariance (setRtf(true) first) and the others the Capon peaks (configureSpectrum()
+    // first), associated by angle with birth and release.  seedTracks(): one direction per slot, NaN leaves the slot.  Per chunk:
+    // process, updateTracks().  tracks(): the look directions as the next chunk would take them (a dead slot repeats the lowest alive
+    // one) and which slots are alive.  followTracks(true): the overloads of process(), processRtf() and processAuto() with several
+    // outputs take their look directions from the tracks (mca_hip_mvdr_tracks_fill_*) instead of from setDOAs(), one output per slot.
+    void configureTracks(int nTracks, int nOwn = 0, double maxStepRadians = 0.2, double minSepRadians = 0.1, int hold = 3)
+    {
+        mca_hip_mvdr_tracks_config cfg;
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.enable = 1;
+        cfg.n_tracks = nTracks;
+        cfg.n_own = nOwn;
+        cfg.max_step_rad = maxStepRadians;
+        cfg.min_sep_rad = minSepRadians;
+        cfg.hold = hold;
+        check(mca_hip_mvdr_tracks_configure(_ctx, &cfg));
+        _nTracks = nTracks;
+    }
+    void seedTracks(const std::vector<double> &doasRadians)
+    {
+        if (static_cast<int>(doasRadians.size()) != _nTracks || _nTracks == 0) throw MCArrayException("seedTracks: one direction per slot of configureTracks()");
+        std::vector<float> d(doasRadians.begin(), doasRadians.end());
+        check(mca_hip_mvdr_tracks_seed_host(_ctx, 1, d.data()));
+    }
+    void updateTracks() { check(mca_hip_mvdr_tracks_update_host(_ctx, 1, nullptr, nullptr)); }
+    void tracks(std::vector<double> &doasRadians, std::vector<int> &alive)
+    {
+        if (_nTracks == 0) throw MCArrayException("tracks: configureTracks() first");
+        std::vector<float> d(static_cast<size_t>(_nTracks));
+        alive.assign(static_cast<size_t>(_nTracks), 0);
+        check(mca_hip_mvdr_tracks_fill_host(_ctx, 1, 1, d.data()));
+        check(mca_hip_mvdr_tracks_get(_ctx, 1, nullptr, alive.data(), nullptr, nullptr));
+        doasRadians.assign(d.begin(), d.end());
+    }
+    void followTracks(bool follow)
+    {
+        if (follow && _nTracks == 0) throw MCArrayException("followTracks: configureTracks() first");
+        _follow = follow;
+    }
     // the covariance the stream holds (mca_hip_mvdr_get_covariance): [N/2+1][M][M] complex as (re, im) pairs of doubles
     void covariance(std::vector<double> &phi)
     {
@@ -240,7 +280,7 @@ public:
     template <typename Tin, typename Tout>
     int process(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize, const float *updateMask = nullptr)
     {
-        const int hop = _N / 2, S = static_cast<int>(_doas.size());
+        const int hop = _N / 2, S = _follow ? _nTracks : static_cast<int>(_doas.size());
         if (S == 0) throw MCArrayException("process: setDOAs() first");
         if (static_cast<int>(out.size()) < S) throw MCArrayException("process: one output pointer per look direction of setDOAs()");
         const int F = pend(in, nSamples);
@@ -248,8 +288,7 @@ public:
         if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
         std::vector<float> pcm = frames(F);
         std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
-        for (int t = 0; t < F; ++t)
-            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+        lookDirections(F, S, doa);
         const std::vector<float> upd = weights(F);
         if (updateMask) check(mca_hip_mvdr_sources_frames_masked_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMask, audio.data(), nullptr));
         else check(mca_hip_mvdr_sources_frames_weighted_host(_ctx, pcm.data(), 1, F, S, doa.data(), upd.empty() ? nullptr : upd.data(), audio.data(), nullptr));
@@ -280,7 +319,7 @@ public:
     template <typename Tin, typename Tout>
     int processRtf(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize, const float *updateMask, const float *targetMask)
     {
-        const int hop = _N / 2, S = static_cast<int>(_doas.size());
+        const int hop = _N / 2, S = _follow ? _nTracks : static_cast<int>(_doas.size());
         if (S == 0) throw MCArrayException("processRtf: setDOAs() first");
         if (static_cast<int>(out.size()) < S) throw MCArrayException("processRtf: one output pointer per look direction of setDOAs()");
         const int F = pend(in, nSamples);
@@ -288,8 +327,7 @@ public:
         if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
         std::vector<float> pcm = frames(F);
         std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
-        for (int t = 0; t < F; ++t)
-            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+        lookDirections(F, S, doa);
         check(mca_hip_mvdr_sources_frames_rtf_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMask, targetMask, audio.data(), nullptr));
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
@@ -318,7 +356,7 @@ public:
     template <typename Tin, typename Tout>
     int processAuto(const std::vector<Tin *> &in, int nSamples, const std::vector<Tout *> &out, int outSize, float *updateMaskOut = nullptr, float *targetMaskOut = nullptr)
     {
-        const int hop = _N / 2, S = static_cast<int>(_doas.size());
+        const int hop = _N / 2, S = _follow ? _nTracks : static_cast<int>(_doas.size());
         if (S == 0) throw MCArrayException("processAuto: setDOAs() first");
         if (static_cast<int>(out.size()) < S) throw MCArrayException("processAuto: one output pointer per look direction of setDOAs()");
         const int F = pend(in, nSamples);
@@ -326,8 +364,7 @@ public:
         if (F * hop > outSize) throw MCArrayException("output buffer too small for the frames completed by this chunk");
         std::vector<float> pcm = frames(F);
         std::vector<float> doa(static_cast<size_t>(F) * static_cast<size_t>(S)), audio(doa.size() * static_cast<size_t>(hop));
-        for (int t = 0; t < F; ++t)
-            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+        lookDirections(F, S, doa);
         check(mca_hip_mvdr_sources_frames_auto_host(_ctx, pcm.data(), 1, F, S, doa.data(), updateMaskOut, targetMaskOut, audio.data(), nullptr));
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < F * hop; ++i) out[static_cast<size_t>(s)][i] = static_cast<Tout>(audio[static_cast<size_t>(s) * static_cast<size_t>(F * hop) + static_cast<size_t>(i)]);
@@ -361,6 +398,13 @@ private:
     {
         return _update == 1.0 ? std::vector<float>() : std::vector<float>(static_cast<size_t>(F), static_cast<float>(_update));
     }
+    // [F][S]: the directions of setDOAs(), or with followTracks(true) those of the tracks
+    void lookDirections(int F, int S, std::vector<float> &doa)
+    {
+        if (_follow) { check(mca_hip_mvdr_tracks_fill_host(_ctx, 1, F, doa.data())); return; }
+        for (int t = 0; t < F; ++t)
+            for (int s = 0; s < S; ++s) doa[static_cast<size_t>(t * S + s)] = static_cast<float>(_doas[static_cast<size_t>(s)]);
+    }
     void consume(int F)
     {
         for (int c = 0; c < _nchannels; ++c)
@@ -374,6 +418,8 @@ private:
     double _doa = 0.0, _update = 1.0;
     int _maxSources = 1;
     int _nAngles = 0, _nPeaks = 0;
+    int _nTracks = 0;
+    bool _follow = false;
     std::vector<double> _doas;
     mca_hip_mvdr_ctx *_ctx = nullptr;
     std::vector<std::vector<float> > _pending;

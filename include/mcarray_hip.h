@@ -899,6 +899,78 @@ int mca_hip_mvdr_spectrum_get_grid(const mca_hip_mvdr_ctx *ctx, float *doa_rad);
 int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum_dev, float *peak_doa_dev, float *peak_val_dev,
                               void *stream);
 int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum, float *peak_doa, float *peak_val);
+/* Tracks of the look directions, kept on the device between chunks: which talker owns which slot.  The spectrum's peaks are ranked
+ * by value, so two talkers swap slots when their levels cross -- and a slot is more than an output index: it owns a target covariance
+ * Psi and cpsi, the RTF estimated from it, a place among the first n_protected directions of the mask estimator and the null aimed
+ * at it.  A context with tracks configured holds, per stream and slot s < n_tracks: theta (float, rad), alive (0/1), miss (int,
+ * updates in a row without a match) and gen (int, incremented by every seed and birth: a new gen means a new talker in the slot).
+ * All are zero after configure, after mca_hip_mvdr_reset and after mca_hip_mvdr_state_load: state blobs do not carry the tracks and
+ * keep their versions; a loaded context is seeded again.
+ *
+ * Slots s < n_own are OWN tracks: talkers to keep, whom the update mask keeps out of Phi and who therefore fade from the Capon
+ * spectrum.  They follow a steered spectrum of their own estimated steering vector.  For every stream, own slot s that is alive and
+ * bin k of the spectrum's band, the estimator of mca_hip_mvdr_set_rtf runs on the held state (Psi_s, cpsi_s, Phi, cphi) with the
+ * context's iterations, ref_mic and min_share; g0 is the geometric vector the frames calls form for doa = theta_s (the steering
+ * tables of the analysis, operation for operation).  A bin is USED if the estimator did not fall back and the bin's noise trace is
+ * > 1e-30.  With d the estimate, u = d / |d| and d(theta_i, k) the grid vectors of the Capon spectrum (its phasor table):
+ *     T_s[i] = sum over the used bins k of |d(theta_i,k)^H u_k|^2 / M        every used bin adds a value in [0, 1]
+ *     phi_s  = the grid angle that maximises T_s among the angles with |theta_i - theta_s| <= max_step_rad (both as float, the
+ *              comparison in float, the lower index wins ties); NaN if no bin is used, if no grid angle lies in the window or if
+ *              the maximum is not > 0
+ * The slots n_own <= s < n_tracks follow the Capon peaks of the call -- exactly those of mca_hip_mvdr_spectrum_dev, from the same
+ * kernels, n_peaks of them.
+ *
+ * The association, per stream, all in float32 (mca_hip_mvdr_tracks_associate_dev runs it on candidates the caller gives -- the picks of
+ * an SRP-PHAT context for instance; mca_hip_mvdr_tracks_update_dev on phi and the Capon peaks):
+ *   1. own slots: s < n_own, alive and own_doa[s] finite: theta_s += clamp(own_doa[s] - theta_s, +-max_step_rad), miss = 0.  An
+ *      alive own slot without a finite own_doa: miss += 1.  Own tracks are never released; a dead own slot stays dead, untouched,
+ *      until it is seeded.
+ *   2. candidates in the order given: one whose val is not > 0 or whose angle psi is not finite is skipped; so is one within
+ *      min_sep_rad of an alive own track (|psi - theta_s| <= min_sep_rad, the updated angle): that is the talker, not an
+ *      interferer.  Otherwise the nearest slot among the alive slots s >= n_own not yet matched in this call with
+ *      |psi - theta_s| <= max_step_rad, the lower slot winning ties, takes theta = psi, miss = 0 and is matched.  If there is none
+ *      the candidate waits as a birth.
+ *   3. alive slots s >= n_own that were not matched: miss += 1; if miss > hold, alive = 0.
+ *   4. births in candidate order: the lowest slot s >= n_own with alive == 0 (one released in step 3 among them) takes theta = psi,
+ *      alive = 1, miss = 0, gen += 1; on a context with RTF enabled Psi and cpsi of that slot are set to zero -- they belong to
+ *      whoever held the slot before.  Candidates without a free slot are dropped.
+ * mca_hip_mvdr_tracks_seed_*: doa[streams][n_tracks]; a finite value sets theta, alive = 1, miss = 0, gen += 1 and leaves Psi alone;
+ * a NaN (or an infinity) leaves the slot as it is.  mca_hip_mvdr_tracks_fill_dev writes the doa_rad array of the next frames call,
+ * [streams][n_frames][n_tracks]: theta of every alive slot for every frame; a dead slot reports theta of the lowest alive slot, or
+ * 0 rad if none is alive (coincident directions are well posed everywhere).  mca_hip_mvdr_tracks_get copies [streams][n_tracks] of each
+ * array that is not NULL to the host (it synchronises the device).
+ *   own_spectrum_dev [streams][n_own][D] float: T_s, or NULL; own_used_dev [streams][n_own][N/2+1] bytes: used, or NULL (0 outside the
+ *   band; both all zero for a dead slot); neither is touched when n_own == 0
+ * Accepted: struct_size as compiled, enable 0 or 1, n_tracks 1 ... max_sources, n_own 0 ... n_tracks, max_step_rad in (0, pi],
+ * min_sep_rad in [0, pi], hold 0 ... 1000, all finite; the spectrum configured first (its grid, band and n_peaks are the ones the
+ * tracks use, as they are at the time of a call); n_own > 0 needs RTF enabled.  Anything else is MCA_HIP_ERR_INVALID_ARGUMENT and
+ * leaves configuration and state as they were.  seed, update, associate, fill and get before a configure with enable = 1, with
+ * n_streams outside 1 ... max_streams, n_cand outside 1 ... 8 or a NULL array they need are MCA_HIP_ERR_INVALID_ARGUMENT.  Disabling RTF
+ * disables the tracks, and so does mca_hip_mvdr_set_max_sources below n_tracks; they are configured anew.
+ * update, fill and get change no byte of Phi, tr, Psi, cpsi, cphi or the tails, but Psi and cpsi of a slot at its birth.  The result
+ * is a pure function of state and configuration (no atomics) and does not depend on where a stream sits in the batch.  No
+ * mca_hip_mvdr_*frames* or spectrum call changes behaviour or bytes.  Timing: kernel_id 7 = the track kernels (the Capon kernels of an
+ * update count under 3; an update with n_own == n_tracks launches none, since no peak can change an own track); it exists on a context that has had tracks configured at some time. */
+typedef struct {
+    int struct_size;
+    int enable;
+    int n_tracks;            /* 1 ... max_sources */
+    int n_own;               /* 0 ... n_tracks: slots that follow their own target covariance; > 0 needs RTF enabled */
+    double max_step_rad;     /* (0, pi]: association gate and search window */
+    double min_sep_rad;      /* [0, pi]: a Capon peak this close to an own track is that talker, not an interferer */
+    int hold;                /* 0 ... 1000: updates an unmatched interferer track keeps its direction */
+} mca_hip_mvdr_tracks_config;
+int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_tracks_config *cfg);
+int mca_hip_mvdr_tracks_get_config(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_tracks_config *cfg);
+int mca_hip_mvdr_tracks_seed_dev(mca_hip_mvdr_ctx *ctx, int n_streams, const float *doa_dev, void *stream);
+int mca_hip_mvdr_tracks_seed_host(mca_hip_mvdr_ctx *ctx, int n_streams, const float *doa);
+int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *own_spectrum_dev, unsigned char *own_used_dev, void *stream);
+int mca_hip_mvdr_tracks_update_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *own_spectrum, unsigned char *own_used);
+int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *ctx, int n_streams, const float *own_doa_dev, int n_cand, const float *cand_doa_dev,
+                                      const float *cand_val_dev, void *stream);
+int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *ctx, int n_streams, int n_frames, float *doa_rad_dev, void *stream);
+int mca_hip_mvdr_tracks_fill_host(mca_hip_mvdr_ctx *ctx, int n_streams, int n_frames, float *doa_rad);   /* fill_dev through a staging buffer */
+int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *ctx, int n_streams, float *theta, int *alive, int *miss, int *gen);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream (and the
@@ -910,7 +982,8 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long b
  * 3 = spectrum (both kernels of a mca_hip_mvdr_spectrum_* call), 4 = post-filter.  kernel_id 4 exists on a context that has had the
  * post-filter enabled at some time (it stays readable after disabling); a context that never enabled it refuses 4 like every
  * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT).  5 = k_mvdr_rtf, by the same rule: it exists on a
- * context that has had RTF enabled at some time.  6 = k_mvdr_estmask, by the same rule (the mask estimator) */
+ * context that has had RTF enabled at some time.  6 = k_mvdr_estmask, by the same rule (the mask estimator).  7 = the track
+ * kernels (mca_hip_mvdr_tracks_*), by the same rule: it exists once tracks have been configured */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

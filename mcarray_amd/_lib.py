@@ -95,6 +95,18 @@ class MvdrConfig(C.Structure):
     ]
 
 
+class MvdrTracksConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("enable", C.c_int),
+        ("n_tracks", C.c_int),
+        ("n_own", C.c_int),
+        ("max_step_rad", C.c_double),
+        ("min_sep_rad", C.c_double),
+        ("hold", C.c_int),
+    ]
+
+
 class MvdrSpectrumConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -292,6 +304,16 @@ SYMBOLS = [
     ("mca_hip_mvdr_spectrum_get_grid", C.c_int, [C.c_void_p, c_fp]),
     ("mca_hip_mvdr_spectrum_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_spectrum_host", C.c_int, [C.c_void_p, C.c_int, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_tracks_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrTracksConfig)]),
+    ("mca_hip_mvdr_tracks_get_config", C.c_int, [C.c_void_p, C.POINTER(MvdrTracksConfig)]),
+    ("mca_hip_mvdr_tracks_seed_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_seed_host", C.c_int, [C.c_void_p, C.c_int, c_fp]),
+    ("mca_hip_mvdr_tracks_update_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_update_host", C.c_int, [C.c_void_p, C.c_int, c_fp, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_associate_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_fill_dev", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_fill_host", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_fp]),
+    ("mca_hip_mvdr_tracks_get", C.c_int, [C.c_void_p, C.c_int, c_fp, c_ip, c_ip, c_ip]),
     ("mca_hip_mvdr_get_covariance", C.c_int, [C.c_void_p, C.c_int, c_dp]),
     ("mca_hip_mvdr_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mca_hip_mvdr_get_timing", C.c_int, [C.c_void_p, C.c_int, c_ip, c_dp]),

@@ -884,7 +884,7 @@ class MvdrBeamformer(_StateBlob):
     set_rtf_nulls() / rtf_nulls=True: the calls that steer by estimated vectors honour null_gain, with the nulls at the vectors the
     frame itself uses for the other look directions (mca_hip_mvdr_set_rtf_nulls); without it they refuse a non-zero null gain."""
 
-    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK = 0, 1, 2, 3, 4, 5, 6
+    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK, K_TRACKS = 0, 1, 2, 3, 4, 5, 6, 7
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  null_gain=0.0, rtf_nulls=False):
@@ -910,6 +910,7 @@ class MvdrBeamformer(_StateBlob):
         self.null_gain = 0.0
         self.max_streams = max_streams
         self.spectrum_config = None
+        self._follow, self._follow_doa = False, None
         try:
             if max_sources != 1:
                 self.set_max_sources(max_sources)
@@ -1252,6 +1253,8 @@ class MvdrBeamformer(_StateBlob):
         without it, new device tensors allocated on torch's current stream."""
         A = pcm.shape[0]
         p, sa, sc = pcm_layout(pcm)
+        if doa_rad is None:
+            doa_rad = self._tracks_doa(A, n_frames, pcm, stream)
         if doa_rad.dim() != 3 or not doa_rad.is_contiguous() or doa_rad.shape[0] != A or doa_rad.shape[1] != n_frames:
             raise MCArrayHipError("doa_rad must be a contiguous tensor [streams][F][S]")
         if estimate_masks:
@@ -1315,6 +1318,95 @@ class MvdrBeamformer(_StateBlob):
         self._check(self._lib.mca_hip_mvdr_spectrum_dev(
             self.h, int(n_streams), spectrum.data_ptr() if spectrum is not None else None, peak_doa.data_ptr() if peak_doa is not None else None,
             peak_val.data_ptr() if peak_val is not None else None, stream))
+
+    def configure_tracks(self, n_tracks, n_own=0, max_step_rad=0.2, min_sep_rad=0.1, hold=3, enable=True):
+        """tracks of the look directions, kept on the device between chunks (include/mcarray_hip.h, mca_hip_mvdr_tracks_configure):
+        n_tracks 1 ... max_sources slots per stream, of which the first n_own follow their own target covariance (set_rtf() first)
+        and the others the Capon peaks (configure_spectrum() first: its grid, band and n_peaks), max_step_rad in (0, pi] the
+        association gate and search window, min_sep_rad in [0, pi] within which a peak is an own talker, hold 0 ... 1000 updates an
+        unmatched track keeps its direction.  Clears the tracks."""
+        cfg = _lib.MvdrTracksConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrTracksConfig)
+        cfg.enable = 1 if enable else 0
+        cfg.n_tracks = int(n_tracks)
+        cfg.n_own = int(n_own)
+        cfg.max_step_rad = float(max_step_rad)
+        cfg.min_sep_rad = float(min_sep_rad)
+        cfg.hold = int(hold)
+        self._check(self._lib.mca_hip_mvdr_tracks_configure(self.h, C.byref(cfg)))
+
+    def get_tracks_config(self):
+        """dict(enable, n_tracks, n_own, max_step_rad, min_sep_rad, hold) as the context holds them"""
+        cfg = _lib.MvdrTracksConfig()
+        self._check(self._lib.mca_hip_mvdr_tracks_get_config(self.h, C.byref(cfg)))
+        return dict(enable=bool(cfg.enable), n_tracks=cfg.n_tracks, n_own=cfg.n_own, max_step_rad=cfg.max_step_rad, min_sep_rad=cfg.min_sep_rad,
+                    hold=cfg.hold)
+
+    def seed_tracks(self, doa_rad):
+        """doa_rad [streams][n_tracks] (or [n_tracks] for one stream): a finite value starts a track in that slot, a NaN leaves it"""
+        d = np.ascontiguousarray(np.atleast_2d(np.asarray(doa_rad, dtype=np.float32)))
+        self._check(self._lib.mca_hip_mvdr_tracks_seed_host(self.h, d.shape[0], d.ctypes.data_as(_lib.c_fp)))
+
+    def update_tracks(self, n_streams=None, want_spectrum=False):
+        """one update of the tracks of streams 0 ... n_streams - 1 (default: all) from the state the context holds.  want_spectrum:
+        -> dict(own_spectrum float32 [A][n_own][D], own_used bool [A][n_own][K])"""
+        A = self.max_streams if n_streams is None else int(n_streams)
+        if not want_spectrum:
+            self._check(self._lib.mca_hip_mvdr_tracks_update_host(self.h, A, None, None))
+            return None
+        n_own, D = self.get_tracks_config()["n_own"], (self.spectrum_config or {}).get("n_angles", 1)
+        spec = np.zeros((max(A, 0), n_own, D), dtype=np.float32)
+        used = np.zeros((max(A, 0), n_own, self.K), dtype=np.uint8)
+        self._check(self._lib.mca_hip_mvdr_tracks_update_host(self.h, A, spec.ctypes.data_as(_lib.c_fp), used.ctypes.data_as(C.c_void_p)))
+        return dict(own_spectrum=spec, own_used=used.astype(bool))
+
+    def update_tracks_dev(self, n_streams, own_spectrum=None, own_used=None, stream=None):
+        """device tensors (torch, contiguous): own_spectrum float32 [A][n_own][D], own_used uint8 [A][n_own][K]; either may be None;
+        asynchronous on `stream` (a raw hipStream_t or None)"""
+        self._check(self._lib.mca_hip_mvdr_tracks_update_dev(self.h, int(n_streams), own_spectrum.data_ptr() if own_spectrum is not None else None,
+                                                             own_used.data_ptr() if own_used is not None else None, stream))
+
+    def associate_tracks_dev(self, n_streams, own_doa, cand_doa, cand_val, stream=None):
+        """the association alone on candidates of the caller's (device tensors, contiguous float32): own_doa [A][n_own] or None,
+        cand_doa / cand_val [A][n_cand], n_cand 1 ... 8"""
+        self._check(self._lib.mca_hip_mvdr_tracks_associate_dev(self.h, int(n_streams), own_doa.data_ptr() if own_doa is not None else None,
+                                                                int(cand_doa.shape[-1]), cand_doa.data_ptr(), cand_val.data_ptr(), stream))
+
+    def seed_tracks_dev(self, n_streams, doa_rad, stream=None):
+        self._check(self._lib.mca_hip_mvdr_tracks_seed_dev(self.h, int(n_streams), doa_rad.data_ptr(), stream))
+
+    def fill_tracks_dev(self, n_streams, n_frames, doa_rad, stream=None):
+        """writes doa_rad [A][n_frames][n_tracks] (device tensor, contiguous float32) of the next process_sources_dev() call"""
+        self._check(self._lib.mca_hip_mvdr_tracks_fill_dev(self.h, int(n_streams), int(n_frames), doa_rad.data_ptr(), stream))
+
+    def tracks(self, n_streams=None):
+        """-> dict(theta float32, alive, miss, gen int32), each [A][n_tracks]; synchronises the device"""
+        A = self.max_streams if n_streams is None else int(n_streams)
+        T = self.get_tracks_config()["n_tracks"]
+        th = np.zeros((max(A, 0), T), dtype=np.float32)
+        al, mi, ge = (np.zeros((max(A, 0), T), dtype=np.int32) for _ in range(3))
+        ip = _lib.c_ip
+        self._check(self._lib.mca_hip_mvdr_tracks_get(self.h, A, th.ctypes.data_as(_lib.c_fp), al.ctypes.data_as(ip), mi.ctypes.data_as(ip),
+                                                      ge.ctypes.data_as(ip)))
+        return dict(theta=th, alive=al, miss=mi, gen=ge)
+
+    def follow_tracks(self, enable=True):
+        """while on, process_sources_dev(..., doa_rad=None) takes its look directions from the tracks: fill_tracks_dev() into a
+        tensor of the context's, on the call's stream, with no host step"""
+        self._follow = bool(enable)
+        if not enable:
+            self._follow_doa = None
+
+    def _tracks_doa(self, A, n_frames, like, stream):
+        import torch
+        if not getattr(self, "_follow", False):
+            raise MCArrayHipError("doa_rad is None: follow_tracks(True) first")
+        T = self.get_tracks_config()["n_tracks"]
+        d = getattr(self, "_follow_doa", None)
+        if d is None or tuple(d.shape) != (A, n_frames, T) or d.device != like.device:
+            d = self._follow_doa = torch.empty((A, n_frames, T), dtype=torch.float32, device=like.device)
+        self.fill_tracks_dev(A, n_frames, d, stream)
+        return d
 
     def covariance(self, stream_index=0):
         out = np.empty((self.K, self.M, self.M, 2))

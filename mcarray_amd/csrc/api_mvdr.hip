@@ -71,12 +71,21 @@ struct mca_hip_mvdr_ctx {
     float *d_spec_grid = nullptr;
     float2 *d_spec_T = nullptr;                     // [M][N/64 + 33][Dpad] factored steering phasors of the grid (MvdrSpectrumArgs::T)
     float *d_spec_part = nullptr; size_t spec_part_cap = 0;   // partial sums [streams][chunks][4][Dpad]
+    // tracks of the look directions (mca_hip_mvdr_tracks_*): the configuration is a processing parameter like null_gain; theta, alive,
+    // miss and gen are per-stream state that no state blob carries
+    bool trk_on = false;
+    bool trk_ever = false;        // configured at some time: timing slot 7 exists
+    mca_hip_mvdr_tracks_config trk{};
+    float *d_trk_theta = nullptr; int *d_trk_int = nullptr;   // [max_streams][MCA_MAX_SOURCES]; alive, miss, gen one behind the other
+    float *d_trk_peak = nullptr;                    // [2][max_streams][MCA_MAX_SOURCES]: the Capon peaks of an update (angles, values)
+    float2 *d_trk_T0 = nullptr;                     // [max_streams][MCA_MAX_SOURCES][M][N/64 + 33] phasors of the own tracks
+    float *d_trk_part = nullptr; size_t trk_part_cap = 0;   // partial sums [streams][n_own][chunks][4][Dpad]
     StagePool stage;
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[7] = {};
-    double t_ms[7] = {};
+    int t_launches[8] = {};
+    double t_ms[8] = {};
     std::string err;
 };
 
@@ -107,6 +116,7 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
     F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
     F(c->d_em_update); F(c->d_em_target);
     F(c->d_X); F(c->d_Y); F(c->d_T); F(c->d_spec_grid); F(c->d_spec_T); F(c->d_spec_part);
+    F(c->d_trk_theta); F(c->d_trk_int); F(c->d_trk_peak); F(c->d_trk_T0); F(c->d_trk_part);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->stage.release();
     delete c;
@@ -123,6 +133,10 @@ int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
         VHIP_TRY(c, hipMemsetAsync(c->d_psi, 0, ns * c->max_sources * c->K * c->tri * sizeof(float2), st));
         VHIP_TRY(c, hipMemsetAsync(c->d_cpsi, 0, ns * c->max_sources * c->K * 4, st));
         VHIP_TRY(c, hipMemsetAsync(c->d_cphi, 0, ns * c->K * 4, st));
+    }
+    if (c->d_trk_theta) {
+        VHIP_TRY(c, hipMemsetAsync(c->d_trk_theta, 0, ns * MCA_MAX_SOURCES * 4, st));
+        VHIP_TRY(c, hipMemsetAsync(c->d_trk_int, 0, ns * MCA_MAX_SOURCES * 3 * 4, st));
     }
     VHIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
@@ -370,6 +384,7 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
     }
     (void)hipFree(c->d_tail[0]); (void)hipFree(c->d_tail[1]);
     c->d_tail[0] = nt[0]; c->d_tail[1] = nt[1]; c->tail_cur = 0; c->max_sources = max_sources;
+    if (c->trk_on && max_sources < c->trk.n_tracks) { c->trk_on = false; c->trk.enable = 0; }      // fewer slots than tracks
     return MCA_HIP_OK;
 }
 
@@ -494,6 +509,7 @@ int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_rtf_config *cfg
             F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
             c->d_psi = nullptr; c->d_cpsi = nullptr; c->d_cphi = nullptr; c->d_cphi_next = nullptr;
             c->d_D = nullptr; c->d_cap = 0; c->d_rtf_ones = nullptr; c->rtf_ones_n = 0;
+            if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }     // own tracks read Psi and a birth clears it: configured anew
         }
         c->rtf_on = on;
         if (on) c->rtf_ever = true;
@@ -999,13 +1015,11 @@ int mca_hip_mvdr_spectrum_get_grid(const mca_hip_mvdr_ctx *c, float *doa_rad)
     return MCA_HIP_OK;
 }
 
-int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, void *stream)
+extern "C++" {
+namespace {
+// both kernels of the Capon spectrum (timing slot 3), arguments checked by the caller
+int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, hipStream_t st)
 {
-    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum_dev, peak_doa_dev and peak_val_dev are all NULL");
-    hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrSpectrumArgs sa{};
     sa.phi = c->d_phi; sa.trace = c->d_trace; sa.T = c->d_spec_T;
@@ -1040,6 +1054,17 @@ int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *c, int n_streams, float *spectru
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
+}  // namespace
+}  // extern "C++"
+
+int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum_dev, peak_doa_dev and peak_val_dev are all NULL");
+    return launch_spectrum(c, n_streams, spectrum, peak_doa, peak_val, (hipStream_t)stream);
+}
 
 int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val)
 {
@@ -1059,6 +1084,258 @@ int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectr
     if (spectrum) VHIP_TRY(c, hipMemcpy(spectrum, d_s, sb, hipMemcpyDeviceToHost));
     if (peak_doa) VHIP_TRY(c, hipMemcpy(peak_doa, d_d, pb, hipMemcpyDeviceToHost));
     if (peak_val) VHIP_TRY(c, hipMemcpy(peak_val, d_v, pb, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+// ---- tracks of the look directions (kernels_mvdr_track.hip) ----
+extern "C++" {
+namespace {
+MvdrTrackState track_state(mca_hip_mvdr_ctx *c)
+{
+    const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    return MvdrTrackState{c->d_trk_theta, c->d_trk_int, c->d_trk_int + n, c->d_trk_int + 2 * n};
+}
+int tracks_ready(mca_hip_mvdr_ctx *c, int n_streams)
+{
+    if (!c->trk_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    return MCA_HIP_OK;
+}
+// the association's part of the pick kernel's arguments
+MvdrTrackPickArgs track_pick_args(mca_hip_mvdr_ctx *c)
+{
+    MvdrTrackPickArgs pa{};
+    pa.st = track_state(c);
+    pa.grid = c->d_spec_grid; pa.D = c->spec.n_angles; pa.Dpad = c->spec_dpad;
+    pa.n_tracks = c->trk.n_tracks; pa.n_own = c->trk.n_own; pa.hold = c->trk.hold;
+    pa.max_step = (float)c->trk.max_step_rad; pa.min_sep = (float)c->trk.min_sep_rad;
+    pa.psi = c->rtf_on ? c->d_psi : nullptr; pa.cpsi = c->rtf_on ? c->d_cpsi : nullptr;
+    pa.slots = c->max_sources; pa.K = c->K; pa.tri = c->tri;
+    return pa;
+}
+}  // namespace
+}  // extern "C++"
+
+int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_tracks_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first: the tracks use its grid, band and n_peaks");
+    if (cfg->enable != 0 && cfg->enable != 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
+    if (cfg->n_tracks < 1 || cfg->n_tracks > c->max_sources) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_tracks must be in [1, max_sources]");
+    if (cfg->n_own < 0 || cfg->n_own > cfg->n_tracks) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_own must be in [0, n_tracks]");
+    if (cfg->n_own > 0 && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_own > 0 needs RTF enabled (mca_hip_mvdr_set_rtf): an own track follows its target covariance");
+    if (!std::isfinite(cfg->max_step_rad) || !(cfg->max_step_rad > 0.0) || cfg->max_step_rad > M_PI)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_step_rad must be finite and in (0, pi]");
+    if (!std::isfinite(cfg->min_sep_rad) || cfg->min_sep_rad < 0.0 || cfg->min_sep_rad > M_PI)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_sep_rad must be finite and in [0, pi]");
+    if (cfg->hold < 0 || cfg->hold > 1000) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "hold must be in [0,1000]");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    if (!c->d_trk_theta) {
+        float *nth = nullptr, *npk = nullptr; int *ni = nullptr; float2 *nt0 = nullptr;
+        hipError_t e = hipMalloc((void **)&nth, n * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&ni, n * 3 * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&npk, n * 2 * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&nt0, n * c->M * (c->N / 64 + 33) * sizeof(float2));
+        if (e != hipSuccess) {
+            if (nth) (void)hipFree(nth);
+            if (ni) (void)hipFree(ni);
+            if (npk) (void)hipFree(npk);
+            if (nt0) (void)hipFree(nt0);
+            return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("track state: ") + hipGetErrorString(e));
+        }
+        c->d_trk_theta = nth; c->d_trk_int = ni; c->d_trk_peak = npk; c->d_trk_T0 = nt0;
+    }
+    VHIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
+    VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, n * 4));
+    VHIP_TRY(c, hipMemset(c->d_trk_int, 0, n * 3 * 4));
+    c->trk = *cfg; c->trk_on = cfg->enable == 1;
+    c->trk_ever = true;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_get_config(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_tracks_config *cfg)
+{
+    if (!c || !cfg) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    *cfg = c->trk;
+    cfg->struct_size = (int)sizeof(mca_hip_mvdr_tracks_config);
+    cfg->enable = c->trk_on ? 1 : 0;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_seed_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *doa, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_dev is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrTrackSeedArgs sa{track_state(c), doa, n_streams, c->trk.n_tracks};
+    t_begin(c, 7, st);
+    hipLaunchKernelGGL(k_mvdr_track_seed, dim3((unsigned)((n_streams * c->trk.n_tracks + 255) / 256)), dim3(256), 0, st, sa);
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_seed_host(mca_hip_mvdr_ctx *c, int n_streams, const float *doa)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa is NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t bytes = (size_t)n_streams * c->trk.n_tracks * 4;
+    float *d = (float *)c->stage.get(6, bytes);
+    if (!d) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffer for the host-pointer call");
+    VHIP_TRY(c, hipMemcpy(d, doa, bytes, hipMemcpyHostToDevice));
+    const int rc = mca_hip_mvdr_tracks_seed_dev(c, n_streams, d, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *own_spectrum, unsigned char *own_used, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const int n_own = c->trk.n_own, K = c->K, M = c->M, Dpad = c->spec_dpad, nhi = c->N / 64 + 1;
+    const int chunk0 = c->spec.bin_lo / MVDR_SPEC_CHUNK, n_chunks = c->spec.bin_hi / MVDR_SPEC_CHUNK - chunk0 + 1;
+    const size_t need = (size_t)n_streams * n_own * n_chunks * 4 * Dpad;
+    if (need > c->trk_part_cap) {
+        VHIP_TRY(c, hipDeviceSynchronize());
+        if (c->d_trk_part) (void)hipFree(c->d_trk_part);
+        c->d_trk_part = nullptr; c->trk_part_cap = 0;
+        VHIP_TRY(c, hipMalloc((void **)&c->d_trk_part, need * 4));
+        c->trk_part_cap = need;
+    }
+    // the Capon peaks: the kernels of mca_hip_mvdr_spectrum_dev, into the context's own rows.  Not launched where every slot is an own
+    // track: a peak then changes no track (it is within min_sep of an own track and skipped, or waits as a birth no slot takes)
+    float *pk_doa = c->d_trk_peak, *pk_val = c->d_trk_peak + (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    const bool capon = n_own < c->trk.n_tracks;
+    if (capon)
+        if (const int rc = launch_spectrum(c, n_streams, nullptr, pk_doa, pk_val, st)) return rc;
+    MvdrTrackPickArgs pa = track_pick_args(c);
+    pa.cand_doa = pk_doa; pa.cand_val = pk_val; pa.n_cand = capon ? c->spec.n_peaks : 0;
+    if (n_own > 0 && own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks
+    t_begin(c, 7, st);
+    if (n_own > 0) {
+        MvdrTrackTablesArgs ta{c->d_trk_theta, c->d_trk_T0, c->d_micx, (double)c->cfg.sample_rate / (double)c->N / 346.1, c->N, M, n_own};
+        hipLaunchKernelGGL(k_mvdr_track_tables, dim3((unsigned)(n_streams * n_own)), dim3(256), 0, st, ta);
+        MvdrTrackSpectrumArgs sa{};
+        sa.phi = c->d_phi; sa.trace = c->d_trace; sa.psi = c->d_psi; sa.cpsi = c->d_cpsi; sa.cphi = c->d_cphi;
+        sa.T0 = c->d_trk_T0; sa.T = c->d_spec_T; sa.alive = track_state(c).alive; sa.part = c->d_trk_part; sa.used = own_used;
+        sa.K = K; sa.M = M; sa.D = c->spec.n_angles; sa.Dpad = Dpad; sa.nhi = nhi; sa.nph = nhi + 32;
+        sa.bin_lo = c->spec.bin_lo; sa.bin_hi = c->spec.bin_hi; sa.chunk0 = chunk0; sa.n_chunks = n_chunks;
+        sa.n_own = n_own; sa.slots = c->max_sources;
+        sa.min_share = (float)c->rtf_min_share; sa.iterations = c->rtf_iterations; sa.ref_mic = c->rtf_ref;
+        void *kargs[1] = {&sa};
+        (void)hipLaunchKernel(mvdr_track_spectrum_kernel((M + 3) / 4), dim3((unsigned)((long long)n_streams * n_own * n_chunks)), dim3(256), kargs, 0, st);
+        pa.part = c->d_trk_part; pa.n_slices = n_chunks * 4; pa.own_spectrum = own_spectrum;
+        hipLaunchKernelGGL(k_mvdr_track_pick, dim3(n_streams), dim3(256), 0, st, pa);
+    } else {
+        hipLaunchKernelGGL(k_mvdr_track_pick, dim3(n_streams), dim3(256), 0, st, pa);
+    }
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_update_host(mca_hip_mvdr_ctx *c, int n_streams, float *own_spectrum, unsigned char *own_used)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t sb = (size_t)n_streams * c->trk.n_own * c->spec.n_angles * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
+    float *d_s = own_spectrum ? (float *)c->stage.get(4, sb) : nullptr;
+    unsigned char *d_u = own_used ? (unsigned char *)c->stage.get(5, ub) : nullptr;
+    if ((own_spectrum && sb && !d_s) || (own_used && ub && !d_u)) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    const int rc = mca_hip_mvdr_tracks_update_dev(c, n_streams, d_s, d_u, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    if (d_s) VHIP_TRY(c, hipMemcpy(own_spectrum, d_s, sb, hipMemcpyDeviceToHost));
+    if (d_u) VHIP_TRY(c, hipMemcpy(own_used, d_u, ub, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *own_doa, int n_cand, const float *cand_doa, const float *cand_val,
+                                      void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
+    if (!cand_doa || !cand_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_doa_dev / cand_val_dev is NULL");
+    if (c->trk.n_own > 0 && !own_doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_doa_dev is NULL on tracks with n_own > 0");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrTrackPickArgs pa = track_pick_args(c);
+    pa.own_doa = own_doa; pa.cand_doa = cand_doa; pa.cand_val = cand_val; pa.n_cand = n_cand;
+    t_begin(c, 7, st);
+    hipLaunchKernelGGL(k_mvdr_track_pick, dim3(n_streams), dim3(256), 0, st, pa);
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, float *doa_rad, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+    if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrTrackFillArgs fa{track_state(c), doa_rad, n_streams, n_frames, c->trk.n_tracks};
+    t_begin(c, 7, st);
+    hipLaunchKernelGGL(k_mvdr_track_fill, dim3((unsigned)(((long long)n_streams * n_frames + 255) / 256)), dim3(256), 0, st, fa);
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_fill_host(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, float *doa_rad)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+    if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t bytes = (size_t)n_streams * n_frames * c->trk.n_tracks * 4;
+    float *d = (float *)c->stage.get(6, bytes);
+    if (!d) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffer for the host-pointer call");
+    const int rc = mca_hip_mvdr_tracks_fill_dev(c, n_streams, n_frames, d, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    VHIP_TRY(c, hipMemcpy(doa_rad, d, bytes, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *c, int n_streams, float *theta, int *alive, int *miss, int *gen)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (!theta && !alive && !miss && !gen) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "theta, alive, miss and gen are all NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());
+    const size_t n = (size_t)n_streams * MCA_MAX_SOURCES, all = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    std::vector<float> hf(n);
+    std::vector<int> hi(n);
+    const int T = c->trk.n_tracks;
+    if (theta) {
+        VHIP_TRY(c, hipMemcpy(hf.data(), c->d_trk_theta, n * 4, hipMemcpyDeviceToHost));
+        for (int a = 0; a < n_streams; ++a)
+            for (int s = 0; s < T; ++s) theta[a * T + s] = hf[(size_t)a * MCA_MAX_SOURCES + s];
+    }
+    int *outs[3] = {alive, miss, gen};
+    for (int j = 0; j < 3; ++j)
+        if (outs[j]) {
+            VHIP_TRY(c, hipMemcpy(hi.data(), c->d_trk_int + j * all, n * 4, hipMemcpyDeviceToHost));
+            for (int a = 0; a < n_streams; ++a)
+                for (int s = 0; s < T; ++s) outs[j][a * T + s] = hi[(size_t)a * MCA_MAX_SOURCES + s];
+        }
     return MCA_HIP_OK;
 }
 
@@ -1226,6 +1503,11 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long byt
                                                               ", this one has " + std::to_string(c->max_sources));
     }
     const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->rtf_on ? 4 : c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1);
+    if (!rc && c->d_trk_theta) {
+        // the tracks are no part of a blob: a loaded context starts without them and is seeded again
+        VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, (size_t)c->cfg.max_streams * MCA_MAX_SOURCES * 4));
+        VHIP_TRY(c, hipMemset(c->d_trk_int, 0, (size_t)c->cfg.max_streams * MCA_MAX_SOURCES * 3 * 4));
+    }
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
 
@@ -1238,7 +1520,8 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id > 6 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever))
+    if (!c || kernel_id < 0 || kernel_id > 7 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever) ||
+        (kernel_id == 7 && !c->trk_ever))
         return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));

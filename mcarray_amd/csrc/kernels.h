@@ -95,6 +95,12 @@ __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                        
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance
 __global__ void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs p);
+__global__ void k_mvdr_track_tables(MvdrTrackTablesArgs p);                                 // tracks of the look directions (kernels_mvdr_track.hip)
+template <int Q> __global__ void k_mvdr_track_spectrum(MvdrTrackSpectrumArgs p);
+const void *mvdr_track_spectrum_kernel(int Q);
+__global__ void k_mvdr_track_pick(MvdrTrackPickArgs p);
+__global__ void k_mvdr_track_fill(MvdrTrackFillArgs p);
+__global__ void k_mvdr_track_seed(MvdrTrackSeedArgs p);
 __global__ void k_tgcc_frames(TgccFrameArgs p);
 __global__ void k_tgcc_frame_f64(const double *Lp, const double *Rp, int W, int nd, int rem, double *res, double *index);
 __global__ void k_tgcc_gate(TgccGateArgs p);

@@ -634,6 +634,67 @@ struct MvdrSpectrumPickArgs {
     float *peak_doa, *peak_val;   // [streams][n_peaks] or NULL
 };
 
+// ---- tracks of the look directions, updated on the device between chunks (kernels_mvdr_track.hip) ----
+// per stream and slot, stride MCA_MAX_SOURCES whatever max_sources is (mca_hip_mvdr_set_max_sources moves nothing)
+constexpr int MVDR_TRACK_MAX_CAND = 8;       // candidates an association call carries
+struct MvdrTrackState {
+    float *theta;             // [streams][MCA_MAX_SOURCES]
+    int *alive, *miss, *gen;  // [streams][MCA_MAX_SOURCES]
+};
+// k_mvdr_track_tables: the factored phasors of theta of every own slot, with the operations of the analysis (MvdrAnalyseArgs::T)
+struct MvdrTrackTablesArgs {
+    const float *theta;       // [streams][MCA_MAX_SOURCES]
+    float2 *T0;               // [streams][n_own][M][nhi + 32]
+    const double *mic_x;      // [M]
+    double unit;              // fs / N / 346.1
+    int N, M, n_own;
+};
+// k_mvdr_track_spectrum<Q>: T_s[i] = sum over the used bins of |d(theta_i,k)^H u_k|^2 / M, u the normalised estimated steering vector of
+// own slot s.  A workgroup takes one (stream, own slot, chunk of MVDR_SPEC_CHUNK bins), the cut of k_mvdr_spectrum<Q>
+struct MvdrTrackSpectrumArgs {
+    const float2 *phi;        // [streams][K][tri] (read only)
+    const float *trace;       // [streams][K]
+    const float2 *psi;        // [streams][slots][K][tri]
+    const float *cpsi;        // [streams][slots][K]
+    const float *cphi;        // [streams][K]
+    const float2 *T0;         // [streams][n_own][M][nph] (MvdrTrackTablesArgs)
+    const float2 *T;          // the grid's phasors (MvdrSpectrumArgs::T)
+    const int *alive;         // [streams][MCA_MAX_SOURCES]: a dead slot uses no bin
+    float *part;              // [streams][n_own][n_chunks][4][Dpad] partial sums
+    unsigned char *used;      // [streams][n_own][K] or NULL; the bins of an alive slot's chunks are written, the caller clears the rest
+    int K, M, D, Dpad, nph, nhi;
+    int bin_lo, bin_hi, chunk0, n_chunks;
+    int n_own, slots;
+    float min_share;
+    int iterations, ref_mic;
+};
+// k_mvdr_track_pick: one workgroup per stream.  With part: the own spectra summed in (chunk, wave) order and their window argmax; then
+// one lane runs the association (include/mcarray_hip.h) and the workgroup clears Psi and cpsi of the slots born
+struct MvdrTrackPickArgs {
+    MvdrTrackState st;
+    const float *part;        // [streams][n_own][n_slices][Dpad], or NULL: own_doa is given
+    const float *grid;        // [D]
+    int n_slices, D, Dpad;
+    float *own_spectrum;      // [streams][n_own][D] or NULL
+    const float *own_doa;     // [streams][n_own] (part == NULL; may be NULL when n_own == 0)
+    const float *cand_doa, *cand_val;   // [streams][n_cand]
+    int n_cand, n_tracks, n_own, hold;
+    float max_step, min_sep;
+    float2 *psi;              // [streams][slots][K][tri], or NULL on a context without RTF
+    float *cpsi;              // [streams][slots][K]
+    int slots, K, tri;
+};
+struct MvdrTrackFillArgs {
+    MvdrTrackState st;
+    float *doa_rad;           // [streams][n_frames][n_tracks]
+    int n_streams, n_frames, n_tracks;
+};
+struct MvdrTrackSeedArgs {
+    MvdrTrackState st;
+    const float *doa;         // [streams][n_tracks], NaN: leave the slot
+    int n_streams, n_tracks;
+};
+
 struct MvdrSynthArgs {
     const float2 *Y;          // [streams][S][n_frames][K]
     int n_frames, N, logH, ft;

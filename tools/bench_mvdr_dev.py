@@ -217,6 +217,49 @@ def estmask_table(a, fs, N, xs, pcm, st):
         print(json.dumps(row), flush=True)
 
 
+def tracks_table(a, fs, N, xs, pcm, st):
+    """the rows of DESIGN.md 4.11: the update of the tracks beside the spectrum call of the same process and beside the auto call that
+    feeds it, 361 angles, two look directions of which n_own = 1 and 2 follow their own target covariance"""
+    hop = N // 2
+    dev = pcm.device
+    S = 2
+    look = torch.tensor(LOOK[:S], device=dev, dtype=torch.float32)
+    doa = look[None, None, :].expand(a.streams, a.frames, S).contiguous()
+    out = torch.empty((a.streams, S, a.frames * hop), device=dev, dtype=torch.float32)
+    peaks = torch.empty((2, a.streams, S), device=dev, dtype=torch.float32)
+    for n_own in (1, 2):
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=S)
+        bf.set_rtf(True)
+        bf.set_mask_estimator(True, n_protected=1)
+        bf.configure_spectrum(361, n_peaks=S)
+        bf.configure_tracks(S, n_own, max_step_rad=0.1, min_sep_rad=0.1, hold=3)
+        bf.seed_tracks(np.tile(np.asarray(LOOK[:S], dtype=np.float32), (a.streams, 1)))
+        auto = lambda: bf._check(bf._lib.mca_hip_mvdr_sources_frames_auto_dev(bf.h, *api.pcm_layout(pcm), a.streams, a.frames, S, api._ptr(doa), None, None,
+                                                                             api._ptr(out), None, st))
+        steps = dict(auto=auto, spectrum=lambda: bf.spectrum_dev(a.streams, peak_doa=peaks[0], peak_val=peaks[1], stream=st),
+                     update=lambda: bf.update_tracks_dev(a.streams, stream=st))
+        row = dict(n_own=n_own, workload="%d streams x %d frames, %d mics, N=%d, 361 angles" % (a.streams, a.frames, a.mics, N))
+        for name in ("auto", "spectrum", "update"):
+            for _ in range(a.warmup):
+                steps[name]()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                steps[name]()
+            torch.cuda.synchronize()
+            row[name + "_ms_per_step"] = (time.perf_counter() - t0) / a.steps * 1e3
+        bf.set_timing(True)
+        for _ in range(a.steps):
+            steps["update"]()
+        for kid, kname in ((bf.K_SPECTRUM, "update_capon_kernels_ms"), (bf.K_TRACKS, "update_track_kernels_ms")):
+            n, ms = bf.get_timing(kid)
+            row[kname] = ms / max(n, 1)
+        tr = bf.tracks()
+        row["own_tracks_with_a_match"] = float((tr["miss"][:, :n_own] == 0).mean())
+        bf.close()
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -233,6 +276,7 @@ def main():
     ap.add_argument("--rtf", action="store_true", help="time the table of the estimated steering vectors (DESIGN.md 4.8)")
     ap.add_argument("--estmask", action="store_true", help="time the table of the mask estimator (DESIGN.md 4.9)")
     ap.add_argument("--rtf-nulls", action="store_true", help="time the table of the nulls at estimated steering vectors (DESIGN.md 4.10)")
+    ap.add_argument("--tracks", action="store_true", help="time the update of the tracks beside the spectrum call and the auto call (DESIGN.md 4.11)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
@@ -257,6 +301,8 @@ def main():
         return estmask_table(a, fs, N, xs, pcm, st)
     if a.rtf_nulls:
         return rtf_nulls_table(a, fs, N, xs, pcm, st)
+    if a.tracks:
+        return tracks_table(a, fs, N, xs, pcm, st)
     upd = None
     if a.update != "none":
         w = np.ones((a.streams, a.frames), dtype=np.float32)

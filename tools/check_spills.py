@@ -20,8 +20,9 @@ FIELDS = ("vgpr_spill_count", "private_segment_fixed_size")
 # the solve kernels (the hand-written k_mvdr_solve<Q, FULL> and every k_mvdr_solve_t<...>); the post-filter; the estimated steering
 # vectors: k_mvdr_rtf<Q> (two covariances in registers), k_mvdr_rtf_steering<Q> and the solve arm k_mvdr_solve_rtf_t<...>.  The arm has
 # a pattern of its own: tests/test_mvdr_nulls_abi.py counts what the first one matches beside the weighted k_mvdr_solve_t.
-# k_mvdr_estmask<Q>: the mask estimator, which is to stay without scratch as well.
-DEFAULT_PATTERNS = (r"k_mvdr_solve(?!_rtf)", r"k_mvdr_postfilter", r"k_mvdr_rtf|k_mvdr_solve_rtf", r"k_mvdr_estmask")
+# k_mvdr_estmask<Q>: the mask estimator, which is to stay without scratch as well.  k_mvdr_track*: the tracks of the look directions;
+# k_mvdr_track_spectrum<Q> holds the two covariances of k_mvdr_rtf_steering<Q> and the association keeps its state in LDS.
+DEFAULT_PATTERNS = (r"k_mvdr_solve(?!_rtf)", r"k_mvdr_postfilter", r"k_mvdr_rtf|k_mvdr_solve_rtf", r"k_mvdr_estmask", r"k_mvdr_track")
 # the template arguments a mangled k_mvdr_solve_t name ends with: NULLS, REUSE, WEIGHT (0 none, 1 per frame, 2 per frame and bin), NOISE
 SOLVE_T = re.compile(r"k_mvdr_solve_tI.*ELb(?P<NULLS>[01])ELb(?P<REUSE>[01])ELNS_10MvdrWeightE(?P<WEIGHT>[012])ELb(?P<NOISE>[01])EEEv")
 KEY = re.compile(r"^(?:  - |    )\.(\w+):\s*(.*)$")       # a key of a kernel's own map (those of its arguments sit deeper)
