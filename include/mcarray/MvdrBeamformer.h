@@ -90,6 +90,28 @@ public:
         check(mca_hip_mvdr_get_rtf_nulls(_ctx, &e));
         return e != 0;
     }
+    // The geometry of the steering vectors (mca_hip_mvdr_set_geometry).  MCA_HIP_MVDR_GEOMETRY_LINEAR_X, the default: the x coordinates
+    // of the ArrayDescription alone (Beamformer.cpp:59).  MCA_HIP_MVDR_GEOMETRY_XYZ: all three coordinates; every look direction is an
+    // azimuth round the whole circle (0: +y, +pi/2: +x) at the one elevation given here, in [-pi/2, pi/2].  A call that changes mode or
+    // elevation un-configures the spectrum and the tracks: configureSpectrum() and configureTracks() anew.  No part of the stream's state.
+    void setGeometry(int mode, double elevationRad = 0.0)
+    {
+        mca_hip_mvdr_geometry_config before, cfg;
+        check(mca_hip_mvdr_get_geometry(_ctx, &before));
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.mode = mode;
+        cfg.elevation_rad = elevationRad;
+        check(mca_hip_mvdr_set_geometry(_ctx, &cfg));
+        check(mca_hip_mvdr_get_geometry(_ctx, &cfg));
+        if (cfg.mode != before.mode || cfg.elevation_rad != before.elevation_rad) { _nAngles = 0; _nPeaks = 0; _nTracks = 0; _follow = false; }
+    }
+    void getGeometry(int &mode, double &elevationRad) const
+    {
+        mca_hip_mvdr_geometry_config cfg;
+        check(mca_hip_mvdr_get_geometry(_ctx, &cfg));
+        mode = cfg.mode;
+        elevationRad = cfg.elevation_rad;
+    }
     // The decision-directed Wiener post-filter on the outputs of both process() overloads (mca_hip_mvdr_set_postfilter): smoothing in
     // [0, 1), gainFloor in [0, 1], noiseScale in (0, 100].  Enabling starts the filter's state from zero, disabling frees it; the three
     // values may change between chunks without touching that state.

@@ -555,7 +555,7 @@ int mca_hip_tgcc_state_load(mca_hip_tgcc_ctx *ctx, const void *blob, long long b
  * [BUILD-DEFINES -- NO REFERENCE COUNTERPART]: the reference's only beamformer is the delay-and-sum of
  * mca::Beamformer::processFrame (src/mcarray/Beamformer.cpp:51-71); this module keeps its interface shape
  * (frames in, one output channel, a look direction in radians) and its steering convention (Beamformer.cpp:59:
- * x coordinate only, cos(DOA + pi/2)), and replaces the uniform weights 1/M by the minimum-variance
+ * x coordinate only, cos(DOA + pi/2); mca_hip_mvdr_set_geometry opts into all three coordinates), and replaces the uniform weights 1/M by the minimum-variance
  * distortionless-response weights of SURVEY A.9.  Per stream and bin k:
  *     Phi_t = alpha Phi_{t-1} + (1 - alpha) x x^H,   PhiL = Phi_t + loading tr(Phi_t)/M I,
  *     w = PhiL^-1 d / (d^H PhiL^-1 d),  d_m = exp(+j 2 pi k fs x_m sin(DOA) / (N c)),   Y[k] = w^H x.
@@ -971,6 +971,49 @@ int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *ctx, int n_streams, cons
 int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *ctx, int n_streams, int n_frames, float *doa_rad_dev, void *stream);
 int mca_hip_mvdr_tracks_fill_host(mca_hip_mvdr_ctx *ctx, int n_streams, int n_frames, float *doa_rad);   /* fill_dev through a staging buffer */
 int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *ctx, int n_streams, float *theta, int *alive, int *miss, int *gen);
+/* The geometry of the steering vectors.  MCA_HIP_MVDR_GEOMETRY_LINEAR_X (the default, and the bytes of every release before this
+ * setter): the steering of Beamformer.cpp:59 above, which reads the x coordinate of mic_xyz alone -- right for a line array on the x
+ * axis, wrong without an error for any other.  MCA_HIP_MVDR_GEOMETRY_XYZ: all three coordinates of mic_xyz (the context keeps them
+ * from create on) and look directions round the whole circle.  Every look direction of the module -- doa_rad of the frames calls, of
+ * mca_hip_mvdr_get_steering, the spectrum's grid and peaks, theta of the tracks -- is then an azimuth theta, any finite float; the
+ * elevation eps is one value per context.  The unit vector towards the source and the steering vector are
+ *     e(theta, eps) = (sin theta cos eps, cos theta cos eps, sin eps)
+ *     d_m           = exp(+j 2 pi k fs (r_m . e) / (N c)),   c = 346.1
+ * theta = 0 is +y, the broadside of a line array on the x axis; theta = +pi/2 is +x.  The phase is formed in double, from
+ *     cd = cos((double) theta + pi/2), cy = -cos((double) theta), u = fs / N / c,
+ *     p_m = (u x_m) (cd cos eps)  [+ (u y_m) (cy cos eps) if y_m != 0]  [- (u z_m) sin eps if z_m != 0]
+ *     table entry kk of microphone m: turns = kk p_m, reduced by its nearest integer, exp(-j 2 pi turns) in float
+ * (kk = 32 i and i: the factored tables of the module).  A coordinate that is 0 adds no term, so an array on the x axis with eps = 0
+ * gives the bytes of LINEAR_X in every call.  LINEAR_X ignores elevation_rad, which must still be finite and within +-pi/2, and
+ * mca_hip_mvdr_get_geometry reports 0 for it.
+ *
+ * The Capon spectrum in XYZ mode has a periodic grid, theta_i = -pi + i 2 pi / D, i = 0 ... D-1 (in double, reported as float;
+ * n_angles 3 ... 361), and the peak rule holds on the circle: i is a local maximum if P[i] > 0, P[i] > P[(i-1) mod D] and
+ * P[i] >= P[(i+1) mod D].  Ranking, ties and empty slots are as above.  A line array cannot tell front from back: in XYZ mode it shows
+ * every talker twice, at theta and at pi - theta, with equal values up to rounding -- ties go to the lower index.
+ *
+ * The tracks in XYZ mode live on the circle, in float32, with pi_f = 3.14159274f, two_pi_f = 6.28318548f, inv_f = 0.159154937f:
+ *     reduce(v) = clamp(wrap(fmaf(-two_pi_f, rintf(v * inv_f), v)), -pi_f, pi_f)         for a finite v; a NaN or an infinity stays
+ *     wrap(d)   = d - two_pi_f if d > pi_f;  d + two_pi_f if d < -pi_f;  d otherwise      one rounded addition
+ * Seeds, candidates and own_doa are reduced on entry, so a stored theta is always in [-pi_f, pi_f].  Every difference of the
+ * association above is wrap(x - y): own_doa[s] - theta_s in step 1, |psi - theta_s| in the min_sep test and in the gate of step 2,
+ * and |theta_i - theta_s| of the own track's search window.  Step 1 stores wrap(theta_s + clamp(...)).  LINEAR_X arithmetic is
+ * as it was.
+ *
+ * Accepted: struct_size as compiled, mode 0 or 1, elevation_rad finite with |elevation_rad| <= pi/2; anything else is
+ * MCA_HIP_ERR_INVALID_ARGUMENT and leaves everything as it was.  Geometry is a processing parameter like the null gain: state blobs
+ * neither carry nor check it, and Phi, tr, Psi, cpsi, cphi, the post-filter state and the tails do not depend on it and are kept.  A
+ * call that changes mode or elevation synchronises the device, un-configures the spectrum (its phasor table and grid are stale) and
+ * disables the tracks (their angles change meaning); both are configured anew.  A call that changes nothing is a no-op. */
+#define MCA_HIP_MVDR_GEOMETRY_LINEAR_X 0
+#define MCA_HIP_MVDR_GEOMETRY_XYZ 1
+typedef struct {
+    int struct_size;
+    int mode;                /* MCA_HIP_MVDR_GEOMETRY_LINEAR_X / _XYZ */
+    double elevation_rad;    /* eps, [-pi/2, pi/2] */
+} mca_hip_mvdr_geometry_config;
+int mca_hip_mvdr_set_geometry(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_geometry_config *cfg);
+int mca_hip_mvdr_get_geometry(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_geometry_config *cfg);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream (and the

@@ -107,6 +107,14 @@ class MvdrTracksConfig(C.Structure):
     ]
 
 
+class MvdrGeometryConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("mode", C.c_int),
+        ("elevation_rad", C.c_double),
+    ]
+
+
 class MvdrSpectrumConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -274,6 +282,8 @@ SYMBOLS = [
     ("mca_hip_mvdr_get_null_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("mca_hip_mvdr_set_rtf_nulls", C.c_int, [C.c_void_p, C.c_int]),
     ("mca_hip_mvdr_get_rtf_nulls", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("mca_hip_mvdr_set_geometry", C.c_int, [C.c_void_p, C.POINTER(MvdrGeometryConfig)]),
+    ("mca_hip_mvdr_get_geometry", C.c_int, [C.c_void_p, C.POINTER(MvdrGeometryConfig)]),
     ("mca_hip_mvdr_set_postfilter", C.c_int, [C.c_void_p, C.POINTER(MvdrPostfilterConfig)]),
     ("mca_hip_mvdr_get_postfilter", C.c_int, [C.c_void_p, C.POINTER(MvdrPostfilterConfig)]),
     ("mca_hip_mvdr_sources_frames_dev", C.c_int,

@@ -882,12 +882,17 @@ class MvdrBeamformer(_StateBlob):
     (mca_hip_mvdr_set_mask_estimator, mca_hip_mvdr_sources_frames_auto_*).  Not together with a caller's update=, update_mask= or
     target_mask=.
     set_rtf_nulls() / rtf_nulls=True: the calls that steer by estimated vectors honour null_gain, with the nulls at the vectors the
-    frame itself uses for the other look directions (mca_hip_mvdr_set_rtf_nulls); without it they refuse a non-zero null gain."""
+    frame itself uses for the other look directions (mca_hip_mvdr_set_rtf_nulls); without it they refuse a non-zero null gain.
+    set_geometry() / geometry="xyz": the steering vectors use all three coordinates of mic_positions, every look direction is an
+    azimuth round the whole circle (0: +y, +pi/2: +x) at the context's one elevation, the spectrum's grid is periodic and the tracks
+    live on the circle (mca_hip_mvdr_set_geometry).  The default "linear_x" reads the x coordinates alone, as it always did."""
+
+    GEOMETRY_LINEAR_X, GEOMETRY_XYZ = 0, 1
 
     K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK, K_TRACKS = 0, 1, 2, 3, 4, 5, 6, 7
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
-                 null_gain=0.0, rtf_nulls=False):
+                 geometry="linear_x", elevation_rad=0.0, null_gain=0.0, rtf_nulls=False):
         self._lib = _lib.load()
         xyz = _xyz(mic_positions)
         cfg = _lib.MvdrConfig()
@@ -918,6 +923,8 @@ class MvdrBeamformer(_StateBlob):
                 self.set_null_gain(null_gain)
             if rtf_nulls:
                 self.set_rtf_nulls(True)
+            if geometry not in ("linear_x", self.GEOMETRY_LINEAR_X) or elevation_rad != 0.0:
+                self.set_geometry(geometry, elevation_rad)
         except MCArrayHipError:
             self.close()
             raise
@@ -948,6 +955,27 @@ class MvdrBeamformer(_StateBlob):
         e = C.c_int(0)
         self._check(self._lib.mca_hip_mvdr_get_rtf_nulls(self.h, C.byref(e)))
         return bool(e.value)
+
+    def set_geometry(self, mode, elevation_rad=0.0):
+        """the geometry of the steering vectors (include/mcarray_hip.h, mca_hip_mvdr_set_geometry): mode "linear_x" (x coordinates
+        alone, the default) or "xyz" (all three, azimuths round the circle), elevation_rad in [-pi/2, pi/2] (ignored by "linear_x").
+        A processing parameter; a call that changes it un-configures the spectrum and disables the tracks: configure them anew."""
+        kinds = {"linear_x": self.GEOMETRY_LINEAR_X, "xyz": self.GEOMETRY_XYZ}
+        before = self.get_geometry()
+        cfg = _lib.MvdrGeometryConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrGeometryConfig)
+        cfg.mode = kinds[mode] if mode in kinds else int(mode)
+        cfg.elevation_rad = float(elevation_rad)
+        self._check(self._lib.mca_hip_mvdr_set_geometry(self.h, C.byref(cfg)))
+        if self.get_geometry() != before:
+            self.spectrum_config = None
+            self._follow, self._follow_doa = False, None
+
+    def get_geometry(self):
+        """dict(mode "linear_x" / "xyz", elevation_rad) as the context holds them"""
+        cfg = _lib.MvdrGeometryConfig()
+        self._check(self._lib.mca_hip_mvdr_get_geometry(self.h, C.byref(cfg)))
+        return dict(mode="xyz" if cfg.mode == self.GEOMETRY_XYZ else "linear_x", elevation_rad=cfg.elevation_rad)
 
     def set_postfilter(self, enable=True, smoothing=0.98, gain_floor=0.1, noise_scale=1.0):
         """the decision-directed Wiener post-filter on the outputs of every process call (include/mcarray_hip.h,
@@ -1276,7 +1304,8 @@ class MvdrBeamformer(_StateBlob):
 
     def configure_spectrum(self, n_angles, bin_lo=None, bin_hi=None, weighting="normalised", n_peaks=1):
         """the Capon spatial spectrum spectrum() evaluates on the covariance the context holds (include/mcarray_hip.h,
-        mca_hip_mvdr_spectrum_configure): n_angles 2 ... 361 from -pi/2 to pi/2, the band of bins [bin_lo, bin_hi] (default
+        mca_hip_mvdr_spectrum_configure): n_angles 2 ... 361 from -pi/2 to pi/2 (geometry "xyz": 3 ... 361 round the circle,
+        theta_i = -pi + i 2 pi / n_angles), the band of bins [bin_lo, bin_hi] (default
         1 ... N/2 - 1), weighting "power" or "normalised", n_peaks 1 ... 4.  A processing parameter: it may change between calls
         and is no part of the state blobs."""
         kinds = {"power": self.SPECTRUM_POWER, "normalised": self.SPECTRUM_NORMALISED}

@@ -24,6 +24,11 @@ struct mca_hip_mvdr_ctx {
     float *d_window = nullptr;
     float2 *d_tw = nullptr;
     double *d_micx = nullptr;
+    // the geometry of the steering vectors (mca_hip_mvdr_set_geometry): a processing parameter like null_gain
+    int geo_mode = MCA_HIP_MVDR_GEOMETRY_LINEAR_X;
+    double geo_elevation = 0.0;
+    std::vector<double> geo_u;    // [3][M]: unit * x_m, unit * y_m, unit * z_m, unit = fs / N / 346.1
+    double *d_geo_u = nullptr;    // the same on the device (MvdrGeometry::u)
     float2 *d_phi = nullptr;      // [max_streams][K][tri]
     float *d_trace = nullptr;     // [max_streams][K]
     float2 *d_phi_tail = nullptr; float *d_trace_tail = nullptr;   // exit state of the pieced tail launch (<= 128 workgroups x 64 problems), copied back behind it
@@ -111,7 +116,7 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
 {
     if (!c) return;
     auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
+    F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_geo_u); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
     F(c->d_pf_A); F(c->d_pf_pn); F(c->d_pf_ones);
     F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
     F(c->d_em_update); F(c->d_em_target);
@@ -120,6 +125,24 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->stage.release();
     delete c;
+}
+
+MvdrGeometry geometry_args(const mca_hip_mvdr_ctx *c)
+{
+    return MvdrGeometry{c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0, c->d_geo_u, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
+}
+
+// turns per unit of kk of microphone m towards theta: what the steering tables of the kernels form (mvdr_projection), on the host
+double host_projection(const mca_hip_mvdr_ctx *c, int m, double theta)
+{
+    const int M = c->M;
+    const double cd = std::cos(theta + M_PI / 2);
+    if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return c->geo_u[m] * cd;                      // (unit x_m) cd, Beamformer.cpp:59
+    const double ce = std::cos(c->geo_elevation), se = std::sin(c->geo_elevation), cy = -std::cos(theta);
+    double pr = c->geo_u[m] * (cd * ce);
+    if (c->geo_u[M + m] != 0.0) pr += c->geo_u[M + m] * (cy * ce);
+    if (c->geo_u[2 * M + m] != 0.0) pr -= c->geo_u[2 * M + m] * se;
+    return pr;
 }
 
 int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
@@ -287,6 +310,10 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     for (int i = 0; i < c->N / 2; ++i) tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / c->N), (float)(-std::sin(2.0 * M_PI * i / c->N)));
     std::vector<double> mx(c->M);
     for (int m = 0; m < c->M; ++m) mx[m] = cfg->mic_xyz[3 * m];                                                // Beamformer.cpp:59: x only
+    c->geo_u.resize((size_t)3 * c->M);                                                                          // all three for XYZ mode
+    const double unit = (double)cfg->sample_rate / (double)c->N / 346.1;
+    for (int m = 0; m < c->M; ++m)
+        for (int j = 0; j < 3; ++j) c->geo_u[(size_t)j * c->M + m] = unit * cfg->mic_xyz[3 * m + j];
 
     int rc = MCA_HIP_OK;
     auto up = [&](void **dst, const void *src, size_t bytes) -> int {
@@ -297,7 +324,7 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     auto alloc = [&](void **dst, size_t bytes) -> int { VHIP_TRY(c, hipMalloc(dst, bytes)); return MCA_HIP_OK; };
     const size_t ns = (size_t)cfg->max_streams;
     if ((rc = up((void **)&c->d_window, win.data(), win.size() * 4)) || (rc = up((void **)&c->d_tw, tw.data(), tw.size() * 8)) ||
-        (rc = up((void **)&c->d_micx, mx.data(), mx.size() * 8)) ||
+        (rc = up((void **)&c->d_micx, mx.data(), mx.size() * 8)) || (rc = up((void **)&c->d_geo_u, c->geo_u.data(), c->geo_u.size() * 8)) ||
         (rc = alloc((void **)&c->d_phi, ns * c->K * c->tri * sizeof(float2))) || (rc = alloc((void **)&c->d_trace, ns * c->K * 4)) ||
         (rc = alloc((void **)&c->d_phi_tail, (size_t)128 * 64 * c->tri * sizeof(float2))) || (rc = alloc((void **)&c->d_trace_tail, (size_t)128 * 64 * 4)) ||
         (rc = alloc((void **)&c->d_tail[0], ns * c->H * 4)) || (rc = alloc((void **)&c->d_tail[1], ns * c->H * 4)) ||
@@ -418,6 +445,34 @@ int mca_hip_mvdr_get_rtf_nulls(const mca_hip_mvdr_ctx *c, int *enable)
 {
     if (!c || !enable) return MCA_HIP_ERR_INVALID_ARGUMENT;
     *enable = c->rtf_nulls ? 1 : 0;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_set_geometry(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_geometry_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_geometry_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->mode != MCA_HIP_MVDR_GEOMETRY_LINEAR_X && cfg->mode != MCA_HIP_MVDR_GEOMETRY_XYZ)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mode must be 0 (linear, x only) or 1 (xyz)");
+    if (!std::isfinite(cfg->elevation_rad) || std::fabs(cfg->elevation_rad) > M_PI / 2)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "elevation_rad must be finite and in [-pi/2, pi/2]");
+    // LINEAR_X ignores the elevation: it is kept as 0 there, so that setting it is no change
+    const double el = cfg->mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? cfg->elevation_rad : 0.0;
+    if (cfg->mode == c->geo_mode && el == c->geo_elevation) return MCA_HIP_OK;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the tables of the former geometry
+    c->geo_mode = cfg->mode; c->geo_elevation = el;
+    c->spec_set = false;                                       // its phasor table and grid are stale (freed by the next configure)
+    if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }   // the angles change meaning: configured anew
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_geometry(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_geometry_config *cfg)
+{
+    if (!c || !cfg) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    cfg->struct_size = (int)sizeof(mca_hip_mvdr_geometry_config);
+    cfg->mode = c->geo_mode; cfg->elevation_rad = c->geo_elevation;
     return MCA_HIP_OK;
 }
 
@@ -580,7 +635,7 @@ int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_strid
     MvdrAnalyseArgs aa{};
     aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = n_frames;
     aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.S = n_sources; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = doa_rad;
-    aa.X = c->d_X; aa.T = c->d_T; aa.mic_x = c->d_micx;
+    aa.X = c->d_X; aa.T = c->d_T; aa.mic_x = c->d_micx; aa.geo = geometry_args(c);
     aa.unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;                      // Beamformer.cpp:59 without 2 pi
     t_begin(c, 0, st);
     if (c->N == FFT_N) {
@@ -964,6 +1019,8 @@ int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spec
     if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_spectrum_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     if (cfg->n_angles < 2 || cfg->n_angles > MVDR_SPEC_MAX_ANGLES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [2,361]");
+    const bool xyz = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ;
+    if (xyz && cfg->n_angles < 3) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [3,361] on the periodic grid of XYZ geometry");
     if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
     if (cfg->weighting != MCA_HIP_MVDR_SPECTRUM_POWER && cfg->weighting != MCA_HIP_MVDR_SPECTRUM_NORMALISED)
@@ -974,16 +1031,15 @@ int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spec
     // grid and steering phasors of the new angle count, in double: theta_i = -pi/2 + i pi/(D-1), u = fs/(N c) x_m cos(theta + pi/2)
     // (Beamformer.cpp:59), factors exp(-j 2 pi 32 i u), i <= N/64, and exp(-j 2 pi i u), i < 32, as in MvdrAnalyseArgs::T
     const int D = cfg->n_angles, Dpad = (D + 63) & ~63, nhi = c->N / 64 + 1, nph = nhi + 32, M = c->M;
-    std::vector<double> mx(M);
-    VHIP_TRY(c, hipMemcpy(mx.data(), c->d_micx, (size_t)M * 8, hipMemcpyDeviceToHost));
+    // XYZ geometry: the periodic grid theta_i = -pi + i 2 pi / D and the projection on e(theta, eps) (host_projection)
     std::vector<float> grid(D);
     std::vector<float2> T((size_t)M * nph * Dpad);
-    const double unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;
     for (int i = 0; i < Dpad; ++i) {
-        const double th = -M_PI / 2 + (double)(i < D ? i : D - 1) * M_PI / (double)(D - 1);     // the surplus lanes repeat the last angle
+        const double ii = (double)(i < D ? i : D - 1);                                          // the surplus lanes repeat the last angle
+        const double th = xyz ? -M_PI + ii * (2.0 * M_PI) / (double)D : -M_PI / 2 + ii * M_PI / (double)(D - 1);
         if (i < D) grid[i] = (float)th;
         for (int m = 0; m < M; ++m) {
-            const double u = unit * mx[m] * std::cos(th + M_PI / 2);
+            const double u = host_projection(c, m, th);
             for (int e = 0; e < nph; ++e) {
                 double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * u;
                 t -= std::floor(t);
@@ -1039,6 +1095,7 @@ int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *
     sa.part = c->d_spec_part;
     MvdrSpectrumPickArgs pa{};
     pa.part = c->d_spec_part; pa.grid = c->d_spec_grid; pa.n_slices = sa.n_chunks * 4; pa.D = sa.D; pa.Dpad = sa.Dpad; pa.n_peaks = c->spec.n_peaks;
+    pa.circular = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0;
     pa.spectrum = spectrum; pa.peak_doa = peak_doa; pa.peak_val = peak_val;
     const int Q = (c->M + 3) / 4;
     const size_t smem = (size_t)MVDR_SPEC_CHUNK * (c->tri * sizeof(float2) + 4);          // 68 KiB at 16 microphones
@@ -1111,6 +1168,7 @@ MvdrTrackPickArgs track_pick_args(mca_hip_mvdr_ctx *c)
     pa.max_step = (float)c->trk.max_step_rad; pa.min_sep = (float)c->trk.min_sep_rad;
     pa.psi = c->rtf_on ? c->d_psi : nullptr; pa.cpsi = c->rtf_on ? c->d_cpsi : nullptr;
     pa.slots = c->max_sources; pa.K = c->K; pa.tri = c->tri;
+    pa.circular = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0;
     return pa;
 }
 }  // namespace
@@ -1172,7 +1230,7 @@ int mca_hip_mvdr_tracks_seed_dev(mca_hip_mvdr_ctx *c, int n_streams, const float
     if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    MvdrTrackSeedArgs sa{track_state(c), doa, n_streams, c->trk.n_tracks};
+    MvdrTrackSeedArgs sa{track_state(c), doa, n_streams, c->trk.n_tracks, c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0};
     t_begin(c, 7, st);
     hipLaunchKernelGGL(k_mvdr_track_seed, dim3((unsigned)((n_streams * c->trk.n_tracks + 255) / 256)), dim3(256), 0, st, sa);
     t_end(c, st);
@@ -1223,7 +1281,7 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
     if (n_own > 0 && own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks
     t_begin(c, 7, st);
     if (n_own > 0) {
-        MvdrTrackTablesArgs ta{c->d_trk_theta, c->d_trk_T0, c->d_micx, (double)c->cfg.sample_rate / (double)c->N / 346.1, c->N, M, n_own};
+        MvdrTrackTablesArgs ta{c->d_trk_theta, c->d_trk_T0, c->d_micx, (double)c->cfg.sample_rate / (double)c->N / 346.1, c->N, M, n_own, geometry_args(c)};
         hipLaunchKernelGGL(k_mvdr_track_tables, dim3((unsigned)(n_streams * n_own)), dim3(256), 0, st, ta);
         MvdrTrackSpectrumArgs sa{};
         sa.phi = c->d_phi; sa.trace = c->d_trace; sa.psi = c->d_psi; sa.cpsi = c->d_cpsi; sa.cphi = c->d_cphi;
@@ -1402,13 +1460,10 @@ int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa
     VHIP_TRY(c, hipDeviceSynchronize());
     // the factored phasors of the look direction, as the analysis forms them (MvdrAnalyseArgs::T), the phase in double
     const int M = c->M, K = c->K, nhi = c->N / 64 + 1, nph = nhi + 32;
-    std::vector<double> mx(M);
-    VHIP_TRY(c, hipMemcpy(mx.data(), c->d_micx, (size_t)M * 8, hipMemcpyDeviceToHost));
     std::vector<float2> T((size_t)M * nph);
-    const double unit = (double)c->cfg.sample_rate / (double)c->N / 346.1, cd = std::cos(doa_rad + M_PI / 2);
     for (int m = 0; m < M; ++m)
         for (int e = 0; e < nph; ++e) {
-            double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * (unit * mx[m] * cd);
+            double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * host_projection(c, m, doa_rad);
             t -= std::rint(t);
             T[(size_t)m * nph + e] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
         }

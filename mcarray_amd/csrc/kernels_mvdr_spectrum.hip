@@ -164,7 +164,10 @@ __global__ __launch_bounds__(256) void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs
     for (int r = 0; r < MCA_MAX_SOURCES; ++r) { val[r] = -1.f; idx[r] = -1; }
     for (int i = 0; i < D; ++i) {
         const float v = Ps[i];
-        if (!(v > 0.f) || !(i == 0 || v > Ps[i - 1]) || !(i == D - 1 || v >= Ps[i + 1])) continue;
+        // on the periodic grid of XYZ mode the ends are neighbours: a row end is a peak only against the other end too
+        const bool lo = i > 0 ? v > Ps[i - 1] : (!p.circular || v > Ps[D - 1]);
+        const bool hi = i < D - 1 ? v >= Ps[i + 1] : (!p.circular || v >= Ps[0]);
+        if (!(v > 0.f) || !lo || !hi) continue;
         float cv = v;
         int ci = i;
         bool ins = false;                        // once inserted, the displaced entries move down a slot each

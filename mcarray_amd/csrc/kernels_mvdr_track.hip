@@ -22,11 +22,12 @@ __global__ __launch_bounds__(256) void k_mvdr_track_tables(MvdrTrackTablesArgs p
     const int nhi = (p.N >> 6) + 1, nph = nhi + 32;
     const int a = (int)(blockIdx.x / (unsigned)p.n_own), s = (int)(blockIdx.x % (unsigned)p.n_own);
     const double cd = cos((double)p.theta[a * MCA_MAX_SOURCES + s] + 1.57079632679489661923);
+    const double cy = p.geo.xyz ? -cos((double)p.theta[a * MCA_MAX_SOURCES + s]) : 0.0;
     float2 *T = p.T0 + (long long)blockIdx.x * p.M * nph;
     for (int e = threadIdx.x; e < p.M * nph; e += 256) {
         const int m = e / nph, i = e - m * nph;
         const int kk = i < nhi ? (i << 5) : i - nhi;
-        double turns = (double)kk * (p.unit * p.mic_x[m] * cd);
+        double turns = (double)kk * (p.geo.xyz ? mvdr_projection(p.geo, p.M, m, cd, cy) : p.unit * p.mic_x[m] * cd);
         turns -= rint(turns);
         float sn, cs;
         sincospif(2.0f * (float)turns, &sn, &cs);
@@ -133,6 +134,15 @@ const void *mvdr_track_spectrum_kernel(int Q)
     return Q >= 1 && Q <= 4 ? k[Q - 1] : nullptr;
 }
 
+// XYZ mode (circular != 0): a finite angle that enters is reduced to [-pi, pi] (a NaN or an infinity stays what it is), a difference
+// takes the shorter way round.  Otherwise the plain value and the plain difference.
+__device__ __forceinline__ float mvdr_track_angle(float v, int circular) { return circular && fabsf(v) < __int_as_float(0x7f800000) ? mvdr_reduce(v) : v; }
+__device__ __forceinline__ float mvdr_track_diff(float x, float y, int circular)
+{
+    const float d = x - y;
+    return circular ? mvdr_wrap(d) : d;
+}
+
 // The association of one stream (include/mcarray_hip.h, mca_hip_mvdr_tracks_configure: the normative text; tests/mvdr_tracks_twin.py
 // restates it operation by operation).  All in float; returns the mask of the slots born.
 __device__ __forceinline__ int mvdr_track_associate(const MvdrTrackPickArgs &p, float *theta, int *alive, int *miss, int *gen, const float *own_doa,
@@ -143,26 +153,27 @@ __device__ __forceinline__ int mvdr_track_associate(const MvdrTrackPickArgs &p, 
     // 1. own slots
     for (int s = 0; s < p.n_own; ++s) {
         if (!alive[s]) continue;
-        const float o = own_doa[s];
+        const float o = mvdr_track_angle(own_doa[s], p.circular);
         if (fabsf(o) < inf) {                                   // finite (false for a NaN)
-            const float dl = o - theta[s];
-            theta[s] = theta[s] + fminf(fmaxf(dl, -p.max_step), p.max_step);
+            const float dl = mvdr_track_diff(o, theta[s], p.circular);
+            const float th = theta[s] + fminf(fmaxf(dl, -p.max_step), p.max_step);
+            theta[s] = p.circular ? mvdr_wrap(th) : th;
             miss[s] = 0;
         } else miss[s] += 1;
     }
     // 2. candidates in the order given
     int matched = 0, n_birth = 0;
     for (int c = 0; c < p.n_cand && c < MAXC; ++c) {
-        const float psi = cand_doa[c];
+        const float psi = mvdr_track_angle(cand_doa[c], p.circular);
         if (!(cand_val[c] > 0.f) || !(fabsf(psi) < inf)) continue;
         bool own = false;
-        for (int s = 0; s < p.n_own; ++s) own = own || (alive[s] && fabsf(psi - theta[s]) <= p.min_sep);
+        for (int s = 0; s < p.n_own; ++s) own = own || (alive[s] && fabsf(mvdr_track_diff(psi, theta[s], p.circular)) <= p.min_sep);
         if (own) continue;
         int best = -1;
         float bd = 0.f;
         for (int s = p.n_own; s < p.n_tracks; ++s) {
             if (!alive[s] || (matched >> s & 1)) continue;
-            const float ds = fabsf(psi - theta[s]);
+            const float ds = fabsf(mvdr_track_diff(psi, theta[s], p.circular));
             if (ds <= p.max_step && (best < 0 || ds < bd)) { best = s; bd = ds; }
         }
         if (best >= 0) { theta[best] = psi; miss[best] = 0; matched |= 1 << best; }
@@ -219,7 +230,7 @@ __global__ __launch_bounds__(256) void k_mvdr_track_pick(MvdrTrackPickArgs p)
                 float bv = 0.f;
                 int bi = -1;
                 for (int i = 0; i < D; ++i)
-                    if (fabsf(p.grid[i] - theta[s]) <= p.max_step && Ts[s][i] > bv) { bv = Ts[s][i]; bi = i; }
+                    if (fabsf(mvdr_track_diff(p.grid[i], theta[s], p.circular)) <= p.max_step && Ts[s][i] > bv) { bv = Ts[s][i]; bi = i; }
                 if (bi >= 0 && alive[s]) own[s] = p.grid[bi];
             }
         } else if (p.own_doa) {
@@ -267,7 +278,7 @@ __global__ __launch_bounds__(256) void k_mvdr_track_seed(MvdrTrackSeedArgs p)
     const int a = id / p.n_tracks, s = id - a * p.n_tracks, o = a * MCA_MAX_SOURCES + s;
     const float v = p.doa[id];
     if (!(fabsf(v) < __int_as_float(0x7f800000))) return;       // NaN (or an infinity): leave the slot
-    p.st.theta[o] = v; p.st.alive[o] = 1; p.st.miss[o] = 0; p.st.gen[o] += 1;
+    p.st.theta[o] = mvdr_track_angle(v, p.circular); p.st.alive[o] = 1; p.st.miss[o] = 0; p.st.gen[o] += 1;
 }
 
 }  // namespace mca

@@ -1584,7 +1584,7 @@ __global__ __launch_bounds__(512) void k_mvdr_analyse_512(MvdrAnalyseArgs p, int
             const long long o = ((long long)a * p.n_frames + f_begin) * p.S + e / (M * nph);
             const double cd = cos((double)p.doa_rad[o] + 1.57079632679489661923);   // cos(DOA + M_PI/2), Beamformer.cpp:59
             const int kk = i < nhi ? (i << 5) : i - nhi;
-            double turns = (double)kk * (p.unit * p.mic_x[m] * cd);
+            double turns = (double)kk * (p.geo.xyz ? mvdr_projection(p.geo, M, m, cd, -cos((double)p.doa_rad[o])) : p.unit * p.mic_x[m] * cd);
             turns -= rint(turns);
             float sn, cs;
             sincospif(2.0f * (float)turns, &sn, &cs);

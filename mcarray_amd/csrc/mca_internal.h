@@ -461,6 +461,43 @@ struct MbSummaryArgs {
 };
 
 // ---- MVDR-style beamformer with a per-bin spatial covariance (BASELINE configs[3]) ----
+// The geometry of a context (mca_hip_mvdr_set_geometry).  xyz == 0: the steering of Beamformer.cpp:59, x only, and
+// nothing else here is read.  xyz == 1: the table entry kk of microphone m has turns = kk * mvdr_projection(...), the negated
+// projection of unit * r_m on e(theta, eps) = (sin theta cos eps, cos theta cos eps, sin eps), in double.
+struct MvdrGeometry {
+    int xyz;
+    const double *u;          // [3][M]: unit * x_m, unit * y_m, unit * z_m (products formed on the host, in double)
+    double ce, se;            // cos eps, sin eps
+};
+// cd = cos((double)theta + pi/2), the x term's spelling in both modes; cy = -cos((double)theta).  A coordinate that is 0 adds no
+// term at all, so an array on the x axis with eps = 0 (ce = 1) gives (unit x_m) * cd: the bytes of the x-only arm, signed zeros included
+__device__ __forceinline__ double mvdr_projection(const MvdrGeometry &g, int M, int m, double cd, double cy)
+{
+    const double ux = g.u[m], uy = g.u[M + m], uz = g.u[2 * M + m];
+    double pr = ux * (cd * g.ce);
+    if (uy != 0.0) pr += uy * (cy * g.ce);
+    if (uz != 0.0) pr -= uz * g.se;
+    return pr;
+}
+
+// Angles on the circle (XYZ mode; the normative text is include/mcarray_hip.h, mca_hip_mvdr_set_geometry).  All float32, every step one
+// rounded operation or an explicit fmaf, so that contraction cannot change a bit.
+constexpr float MVDR_PI_F = 3.14159274f, MVDR_TWO_PI_F = 6.28318548f, MVDR_INV_TWO_PI_F = 0.159154937f;
+// the shorter way round of a difference of two reduced angles (|d| <= 2 pi)
+__device__ __forceinline__ float mvdr_wrap(float d)
+{
+    if (d > MVDR_PI_F) d = d - MVDR_TWO_PI_F;
+    else if (d < -MVDR_PI_F) d = d + MVDR_TWO_PI_F;
+    return d;
+}
+// any finite angle into [-pi_f, pi_f]
+__device__ __forceinline__ float mvdr_reduce(float v)
+{
+    const float n = rintf(v * MVDR_INV_TWO_PI_F);
+    const float r = mvdr_wrap(fmaf(-MVDR_TWO_PI_F, n, v));
+    return fminf(fmaxf(r, -MVDR_PI_F), MVDR_PI_F);          // (only an angle beyond ~1e7 rad, whose float has no fraction left, gets here outside)
+}
+
 struct MvdrAnalyseArgs {
     const float *pcm;
     long long stream_stride, mic_stride;
@@ -476,6 +513,7 @@ struct MvdrAnalyseArgs {
     float2 *T;                // [streams][n_frames][S][M][nhi + 32], nhi = N/64 + 1
     const double *mic_x;      // [M]
     double unit;              // fs / N / 346.1
+    MvdrGeometry geo;
 };
 
 struct MvdrSolveArgs {
@@ -630,6 +668,7 @@ struct MvdrSpectrumPickArgs {
     const float *part;        // [streams][n_slices][Dpad]
     const float *grid;        // [D] (float) theta_i
     int n_slices, D, Dpad, n_peaks;
+    int circular;             // XYZ mode: the grid is periodic, the neighbours of i are (i - 1) mod D and (i + 1) mod D
     float *spectrum;          // [streams][D] or NULL
     float *peak_doa, *peak_val;   // [streams][n_peaks] or NULL
 };
@@ -648,6 +687,7 @@ struct MvdrTrackTablesArgs {
     const double *mic_x;      // [M]
     double unit;              // fs / N / 346.1
     int N, M, n_own;
+    MvdrGeometry geo;
 };
 // k_mvdr_track_spectrum<Q>: T_s[i] = sum over the used bins of |d(theta_i,k)^H u_k|^2 / M, u the normalised estimated steering vector of
 // own slot s.  A workgroup takes one (stream, own slot, chunk of MVDR_SPEC_CHUNK bins), the cut of k_mvdr_spectrum<Q>
@@ -683,6 +723,7 @@ struct MvdrTrackPickArgs {
     float2 *psi;              // [streams][slots][K][tri], or NULL on a context without RTF
     float *cpsi;              // [streams][slots][K]
     int slots, K, tri;
+    int circular;             // XYZ mode: angles live on the circle (mvdr_reduce, mvdr_wrap)
 };
 struct MvdrTrackFillArgs {
     MvdrTrackState st;
@@ -693,6 +734,7 @@ struct MvdrTrackSeedArgs {
     MvdrTrackState st;
     const float *doa;         // [streams][n_tracks], NaN: leave the slot
     int n_streams, n_tracks;
+    int circular;             // XYZ mode: the seed is reduced to [-pi, pi]
 };
 
 struct MvdrSynthArgs {

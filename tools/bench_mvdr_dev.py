@@ -277,20 +277,33 @@ def main():
     ap.add_argument("--estmask", action="store_true", help="time the table of the mask estimator (DESIGN.md 4.9)")
     ap.add_argument("--rtf-nulls", action="store_true", help="time the table of the nulls at estimated steering vectors (DESIGN.md 4.10)")
     ap.add_argument("--tracks", action="store_true", help="time the update of the tracks beside the spectrum call and the auto call (DESIGN.md 4.11)")
+    ap.add_argument("--geometry", choices=["linear_x", "xyz"], default="linear_x",
+                    help="xyz: an XYZ context (mca_hip_mvdr_set_geometry) on a uniform circular array of --mics microphones, radius 5 cm (DESIGN.md 4.12)")
+    ap.add_argument("--elevation", type=float, default=0.0, help="the elevation of --geometry xyz (radians)")
     a = ap.parse_args()
     if a.null_gain != 0.0 and a.sources < 2:
         ap.error("--null-gain needs --sources 2 ... 4")
+    xyz = a.geometry == "xyz"
+    if xyz and (a.mask or a.rtf or a.estmask or a.rtf_nulls or a.tracks or a.postfilter or a.update != "none"):
+        ap.error("--geometry xyz times the plain calls (with --sources and --null-gain)")
     if os.environ.get("MCA_HIP_LIB"):
         bind_what_the_library_has()
     fs, N = 48000, 1024
     hop, K = N // 2, N // 2 + 1
     xs = [0.32 / a.mics * m for m in range(a.mics)] if a.mics != 16 else synth.ULA16
+    if xyz:
+        xs = synth.uca(a.mics, 0.05)
+    geo = dict(geometry="xyz", elevation_rad=a.elevation) if xyz else {}
     dev = torch.device("cuda:0")
     L = (a.frames + 1) * hop
     g = torch.Generator(device=dev); g.manual_seed(1234)
     pcm = (torch.randn((a.streams, a.mics, L), device=dev, generator=g) * 0.1).contiguous()
     if a.check:
-        p0 = synth.noise_source_stream(xs, np.deg2rad(20.0), fs, L, 77) + synth.noise_source_stream(xs, np.deg2rad(-50.0), fs, L, 78, snr_db=60)
+        if xyz:
+            p0 = (synth.noise_source_stream_xyz(xs, np.deg2rad(20.0), fs, L, 77, elevation=a.elevation)
+                  + synth.noise_source_stream_xyz(xs, np.deg2rad(-150.0), fs, L, 78, snr_db=60, elevation=a.elevation))
+        else:
+            p0 = synth.noise_source_stream(xs, np.deg2rad(20.0), fs, L, 77) + synth.noise_source_stream(xs, np.deg2rad(-50.0), fs, L, 78, snr_db=60)
         pcm[0] = torch.from_numpy(p0.astype(np.float32)).to(dev)
     st = torch.cuda.current_stream().cuda_stream
     if a.mask:
@@ -313,14 +326,14 @@ def main():
         look = torch.tensor(LOOK[:a.sources], device=dev, dtype=torch.float32)
         doa = look[None, None, :].expand(a.streams, a.frames, a.sources).contiguous()
         out = torch.empty((a.streams, a.sources, a.frames * hop), device=dev, dtype=torch.float32)
-        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=a.sources)
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, max_sources=a.sources, **geo)
         if a.null_gain != 0.0:
             bf.set_null_gain(a.null_gain)
         step = lambda: bf.process_sources_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **({} if upd is None else {"update": upd}))
     else:
         doa = torch.full((a.streams, a.frames), float(np.deg2rad(20.0)), device=dev, dtype=torch.float32)
         out = torch.empty((a.streams, a.frames * hop), device=dev, dtype=torch.float32)
-        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams)
+        bf = api.MvdrBeamformer(fs, xs, N, max_streams=a.streams, **geo)
         step = lambda: bf.process_dev(pcm, a.frames, doa, out_pcm=out, stream=st, **({} if upd is None else {"update": upd}))
     if a.postfilter:
         bf.set_postfilter(True)
@@ -347,6 +360,18 @@ def main():
         tw = gt.mvdr_gate_stream(fs, N, xs, pcm[0].cpu().numpy().astype(np.float64), doa[0].cpu().numpy(), a.null_gain, upd[0].cpu().numpy())
         o0 = out[0].cpu().numpy().reshape(tw["out"].shape)
         res["audio_err_rel_max"] = float(max(np.abs(o0[s] - tw["out"][s]).max() / np.abs(tw["out"][s]).max() for s in range(o0.shape[0])))
+    elif a.check and xyz:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import mvdr_geometry_twin as gmt
+        import mvdr_nulls_twin as nt
+        bf.reset()
+        step()
+        torch.cuda.synchronize()
+        S = max(a.sources, 1)
+        with gmt.xyz_mode(a.elevation):
+            tw = nt.mvdr_nulls_stream(fs, N, xs, pcm[0].cpu().numpy().astype(np.float64), doa[0].cpu().numpy().reshape(a.frames, S), a.null_gain)
+        o0 = out[0].cpu().numpy().reshape(tw["out"].shape)
+        res["audio_err_rel_max"] = float(max(np.abs(o0[s] - tw["out"][s]).max() / np.abs(tw["out"][s]).max() for s in range(S)))
     elif a.check and a.sources:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
         import mvdr_nulls_twin as nt
@@ -374,6 +399,8 @@ def main():
     frames = a.streams * a.frames
     if a.sources:
         res.update(dict(sources=a.sources, null_gain=a.null_gain))
+    if xyz:
+        res.update(dict(geometry="xyz", elevation=a.elevation))
     res.update(dict(update=a.update, lib=os.environ.get("MCA_HIP_LIB", "default")))
     res.update(dict(workload="%d streams x %d frames, %d mics, N=%d" % (a.streams, a.frames, a.mics, N), ms_per_step=dt * 1e3,
                     frames_per_s=frames / dt, algorithmic_GBps=frames / dt * (a.mics * hop * 4 + hop * 4) / 1e9))

@@ -1,6 +1,6 @@
 """Randomised parity sweep of the 2-channel masking module, the MVDR beamformer and its sources call with soft nulls against the CPU oracle, and of the MVDR auto
 call (estimated masks) against the call fed its masks, and of the RTF call under a null gain (nulls at the estimated vectors) against its exact
-points (a one-off check like
+points, and of the sources call of an XYZ context (full microphone geometry) against its twin (a one-off check like
 tools/fuzz_parity.py): random frame lengths, methods / algorithms, channel counts, geometries, memories, loadings, chunked calls.
 usage (GPU box): python tools/fuzz_modules.py [cases] [seed]"""
 import os
@@ -14,6 +14,7 @@ from oracle import pyoracle as po  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import mvdr_nulls_twin as nt  # noqa: E402
+import mvdr_geometry_twin as gmt  # noqa: E402
 
 
 def mask_case(rng):
@@ -117,6 +118,38 @@ def mvdr_nulls_case(rng):
     return bool(np.isfinite(worst) and worst <= 5e-4), "%s cut=%d worst rel err %.1e" % (tag, cut, worst)
 
 
+def mvdr_geometry_case(rng):
+    """the sources call of an XYZ context (mca_hip_mvdr_set_geometry) against the float64 twin (tests/mvdr_geometry_twin.py): random planar
+    and 3-D arrays, a random elevation, look directions over the whole circle and up to a turn beyond it, with and without nulls"""
+    fs, N = [(8000, 256), (16000, 512), (48000, 1024)][int(rng.integers(0, 3))]
+    M, S = int(rng.integers(2, 17)), int(rng.integers(1, 5))
+    kind = ["planar", "3d", "uca"][int(rng.integers(0, 3))]
+    xyz = synth.uca(M, float(rng.uniform(0.02, 0.1))) if kind == "uca" else rng.uniform(-0.015 * M, 0.015 * M, (M, 3))
+    if kind == "planar":
+        xyz[:, 2] = 0.0
+    el = float(rng.choice([0.0, rng.uniform(-np.pi / 2, np.pi / 2)]))
+    F, A = int(rng.integers(1, 17)), int(rng.integers(1, 4))
+    alpha, loading = float(rng.choice([0.0, 0.5, 0.9, 0.95, 0.99])), float(rng.choice([1e-3, 1e-2, 1e-1]))
+    gain = 0.0 if S == 1 else float(rng.choice([0.0, 1.0, 10.0, 100.0]))
+    hop = N // 2
+    pcm = np.stack([synth.noise_source_stream_xyz(xyz, rng.uniform(-np.pi, np.pi), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)), elevation=el)
+                    + synth.noise_source_stream_xyz(xyz, rng.uniform(-np.pi, np.pi), fs, (F + 1) * hop, int(rng.integers(1, 1 << 30)), snr_db=50, elevation=el)
+                    for _ in range(A)]).astype(np.float32)
+    doa = rng.uniform(-3 * np.pi, 3 * np.pi, (A, F, S)).astype(np.float32)
+    tag = "mvdr xyz %s fs=%d N=%d M=%d S=%d A=%d F=%d el=%.2f alpha=%.2f loading=%.0e gain=%.3g" % (kind, fs, N, M, S, A, F, el, alpha, loading, gain)
+    bf = api.MvdrBeamformer(fs, xyz, N, alpha, loading, max_streams=A, max_sources=S, null_gain=gain, geometry="xyz", elevation_rad=el)
+    r = bf.process_sources(pcm, doa)
+    worst = 0.0
+    for a in range(A):
+        with gmt.xyz_mode(el):
+            tw = nt.mvdr_nulls_stream(fs, N, xyz, pcm[a].astype(np.float64), doa[a], gain, alpha, loading)
+        for s_ in range(S):
+            worst = max(worst, np.abs(r["spec"][a, s_] - tw["spec"][s_]).max() / np.abs(tw["spec"][s_]).max(),
+                        np.abs(r["out"][a, s_] - tw["out"][s_]).max() / np.abs(tw["out"][s_]).max())
+    bf.close()
+    return bool(np.isfinite(worst) and worst <= 5e-4), "%s worst rel err %.1e" % (tag, worst)
+
+
 def mvdr_auto_case(rng):
     """the auto call (masks estimated from the spectra, mca_hip_mvdr_sources_frames_auto_*) against the RTF or the masked call fed
     the masks it returned, bit for bit, and the masks against their own definition: random geometry, frame size, S, band,
@@ -204,14 +237,14 @@ def main(cases, seed):
     rng = np.random.default_rng(seed)
     bad = 0
     for case in range(cases):
-        for fn in (mask_case, mvdr_case, mvdr_nulls_case, mvdr_auto_case, mvdr_rtf_nulls_case):
+        for fn in (mask_case, mvdr_case, mvdr_nulls_case, mvdr_auto_case, mvdr_rtf_nulls_case, mvdr_geometry_case):
             try:
                 ok, msg = fn(rng)
             except api.MCArrayHipError as e:
                 ok, msg = False, "%s raised %s" % (fn.__name__, e)
             print(("ok   " if ok else "FAIL ") + "case %d: %s" % (case, msg), flush=True)
             bad += 0 if ok else 1
-    print("%d cases x 5, %d failures" % (cases, bad))
+    print("%d cases x 6, %d failures" % (cases, bad))
     return 1 if bad else 0
 
 
