@@ -21,70 +21,72 @@ using namespace mca;
 struct mca_hip_mvdr_ctx {
     mca_hip_mvdr_config cfg{};
     int N = 0, K = 0, H = 0, logH = 0, M = 0, tri = 0;
-    float *d_window = nullptr;
-    float2 *d_tw = nullptr;
-    double *d_micx = nullptr;
+    // Device memory: every d_* member owns its buffer (devbuf.h).  A state array is allocated at exactly its state size, so its n
+    // is that size (init_state, mvdr_parts); a workspace only grows, and its n is a capacity that no state size is read from.
+    DevBuf<float> d_window;
+    DevBuf<float2> d_tw;
+    DevBuf<double> d_micx;
     // the geometry of the steering vectors (mca_hip_mvdr_set_geometry): a processing parameter like null_gain
     int geo_mode = MCA_HIP_MVDR_GEOMETRY_LINEAR_X;
     double geo_elevation = 0.0;
     std::vector<double> geo_u;    // [3][M]: unit * x_m, unit * y_m, unit * z_m, unit = fs / N / 346.1
-    double *d_geo_u = nullptr;    // the same on the device (MvdrGeometry::u)
-    float2 *d_phi = nullptr;      // [max_streams][K][tri]
-    float *d_trace = nullptr;     // [max_streams][K]
-    float2 *d_phi_tail = nullptr; float *d_trace_tail = nullptr;   // exit state of the pieced tail launch (<= 128 workgroups x 64 problems), copied back behind it
+    DevBuf<double> d_geo_u;       // the same on the device (MvdrGeometry::u)
+    DevBuf<float2> d_phi;         // [max_streams][K][tri]
+    DevBuf<float> d_trace;        // [max_streams][K]
+    DevBuf<float2> d_phi_tail; DevBuf<float> d_trace_tail;   // exit state of the pieced tail launch (<= 128 workgroups x 64 problems), copied back behind it
     int max_sources = 1;          // look directions per frame a call may carry (mca_hip_mvdr_set_max_sources)
     double null_gain = 0.0;       // soft nulls at the other look directions of a call with n_sources >= 2 (mca_hip_mvdr_set_null_gain);
                                   // a processing parameter, not stream state: no part of the state blobs
     bool rtf_nulls = false;       // the RTF-bodied calls honour null_gain, at the vectors of the steering plane (mca_hip_mvdr_set_rtf_nulls);
                                   // a processing parameter like null_gain
-    float *d_tail[2] = {nullptr, nullptr}; int tail_cur = 0;   // [max_streams][max_sources][H]; a single-look call uses slot 0
+    DevBuf<float> d_tail[2]; int tail_cur = 0;   // [max_streams][max_sources][H]; a single-look call uses slot 0
     // the Wiener post-filter (mca_hip_mvdr_set_postfilter): the three values are processing parameters like null_gain; A is stream state
     bool pf_on = false;
     bool pf_ever = false;         // enabled at some time: timing slot 4 exists (a context that never enabled it refuses kernel_id 4 as it always did)
     double pf_smoothing = 0.98, pf_gain_floor = 0.1, pf_noise_scale = 1.0;
-    float *d_pf_A = nullptr;      // [max_streams][max_sources][K] |Z|^2 of the frame before; allocated while enabled
-    float *d_pf_pn = nullptr;     // workspace [y_rows][K]: the residual noise power of every output of the call; while enabled
-    float *d_pf_ones = nullptr; size_t pf_ones_n = 0;   // update weights of a call that brings none, all 1
+    DevBuf<float> d_pf_A;         // [max_streams][max_sources][K] |Z|^2 of the frame before; allocated while enabled
+    DevBuf<float> d_pf_pn;        // workspace [rows x look directions][K]: the residual noise power of every output of the call; while enabled
+    DevBuf<float> d_pf_ones;      // workspace [rows]: update weights of a call that brings none, all 1
     // steering vectors estimated from a target covariance (mca_hip_mvdr_set_rtf): the four values are processing parameters like
     // null_gain; Psi, cpsi and cphi are stream state, allocated while enabled
     bool rtf_on = false;
     bool rtf_ever = false;        // enabled at some time: timing slot 5 exists
     double rtf_alpha = 0.0, rtf_min_share = 0.05;   // (rtf_alpha: the context's alpha until set)
     int rtf_iterations = 2, rtf_ref = 0;
-    float2 *d_psi = nullptr;      // [max_streams][max_sources][K][tri]
-    float *d_cpsi = nullptr;      // [max_streams][max_sources][K]
-    float *d_cphi = nullptr;      // [max_streams][K]
-    float *d_cphi_next = nullptr; // exit value of the streams of a call, copied over d_cphi behind k_mvdr_rtf (MvdrRtfArgs::cphi_out)
-    float2 *d_D = nullptr; size_t d_cap = 0;              // workspace: the steering plane [rows x look directions][K][M] of a chunk of frames
+    DevBuf<float2> d_psi;         // [max_streams][max_sources][K][tri]
+    DevBuf<float> d_cpsi;         // [max_streams][max_sources][K]
+    DevBuf<float> d_cphi;         // [max_streams][K]
+    DevBuf<float> d_cphi_next;    // exit value of the streams of a call, copied over d_cphi behind k_mvdr_rtf (MvdrRtfArgs::cphi_out)
+    DevBuf<float2> d_D;           // workspace: the steering plane [rows x look directions][K][M] of a chunk of frames
     size_t plane_cap_cells = (size_t)1 << 27;            // its cap (1 GiB; mca_hip_mvdr_set_rtf_workspace): a call above it is cut along the frames
-    float *d_rtf_ones = nullptr; size_t rtf_ones_n = 0;   // update mask of an RTF call that brings none, all 1 [rows][K]
+    DevBuf<float> d_rtf_ones;     // workspace [rows][K]: update mask of an RTF call that brings none, all 1
     // the mask estimator (mca_hip_mvdr_set_mask_estimator): processing parameters like null_gain, and no state at all
     bool em_on = false;
     bool em_ever = false;         // enabled at some time: timing slot 6 exists
     int em_bin_lo = 0, em_bin_hi = 0, em_protected = 0;   // (em_bin_hi: N/2 until set)
     double em_lo = 0.0, em_hi = 0.05;
-    float *d_em_update = nullptr; size_t em_update_n = 0;   // workspace [rows][K]: the update mask of an auto call that hands none back; while enabled
-    float *d_em_target = nullptr; size_t em_target_n = 0;   // workspace [rows x look directions][K]: its target masks
+    DevBuf<float> d_em_update;    // workspace [rows][K]: the update mask of an auto call that hands none back; while enabled
+    DevBuf<float> d_em_target;    // workspace [rows x look directions][K]: its target masks
     // workspace
-    float2 *d_X = nullptr; size_t x_rows = 0;      // [rows][K][M]
-    float2 *d_Y = nullptr; float2 *d_T = nullptr; size_t y_rows = 0;   // rows x look directions; d_T: factored steering phasors [rows][M][N/64 + 33]
+    DevBuf<float2> d_X;           // [rows][K][M]
+    DevBuf<float2> d_Y, d_T;      // rows x look directions: [..][K], and the factored steering phasors [..][M][N/64 + 33]
     // the Capon spectrum of the held covariance (mca_hip_mvdr_spectrum_*): a processing parameter like null_gain, no part of the state blobs
     bool spec_set = false;
     mca_hip_mvdr_spectrum_config spec{};
     int spec_dpad = 0;                              // n_angles rounded up to whole waves
     std::vector<float> spec_grid;                   // [D] (float) theta_i
-    float *d_spec_grid = nullptr;
-    float2 *d_spec_T = nullptr;                     // [M][N/64 + 33][Dpad] factored steering phasors of the grid (MvdrSpectrumArgs::T)
-    float *d_spec_part = nullptr; size_t spec_part_cap = 0;   // partial sums [streams][chunks][4][Dpad]
+    DevBuf<float> d_spec_grid;
+    DevBuf<float2> d_spec_T;                        // [M][N/64 + 33][Dpad] factored steering phasors of the grid (MvdrSpectrumArgs::T)
+    DevBuf<float> d_spec_part;                      // workspace: partial sums [streams][chunks][4][Dpad]
     // tracks of the look directions (mca_hip_mvdr_tracks_*): the configuration is a processing parameter like null_gain; theta, alive,
     // miss and gen are per-stream state that no state blob carries
     bool trk_on = false;
     bool trk_ever = false;        // configured at some time: timing slot 7 exists
     mca_hip_mvdr_tracks_config trk{};
-    float *d_trk_theta = nullptr; int *d_trk_int = nullptr;   // [max_streams][MCA_MAX_SOURCES]; alive, miss, gen one behind the other
-    float *d_trk_peak = nullptr;                    // [2][max_streams][MCA_MAX_SOURCES]: the Capon peaks of an update (angles, values)
-    float2 *d_trk_T0 = nullptr;                     // [max_streams][MCA_MAX_SOURCES][M][N/64 + 33] phasors of the own tracks
-    float *d_trk_part = nullptr; size_t trk_part_cap = 0;   // partial sums [streams][n_own][chunks][4][Dpad]
+    DevBuf<float> d_trk_theta; DevBuf<int> d_trk_int;   // [max_streams][MCA_MAX_SOURCES]; alive, miss, gen one behind the other
+    DevBuf<float> d_trk_peak;                       // [2][max_streams][MCA_MAX_SOURCES]: the Capon peaks of an update (angles, values)
+    DevBuf<float2> d_trk_T0;                        // [max_streams][MCA_MAX_SOURCES][M][N/64 + 33] phasors of the own tracks
+    DevBuf<float> d_trk_part;                       // workspace: partial sums [streams][n_own][chunks][4][Dpad]
     StagePool stage;
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
@@ -112,19 +114,58 @@ int vfail(mca_hip_mvdr_ctx *c, int code, const std::string &msg)
                          std::string(#expr) + ": " + hipGetErrorString(_e));                           \
     } while (0)
 
+// what an allocation or a copy of a configuration step failed with: out of memory by its own code, `what` names the buffers
+int hip_fail(mca_hip_mvdr_ctx *c, hipError_t e, const char *what)
+{
+    return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
 void free_mvdr(mca_hip_mvdr_ctx *c)
 {
     if (!c) return;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_tw); F(c->d_micx); F(c->d_geo_u); F(c->d_phi); F(c->d_trace); F(c->d_phi_tail); F(c->d_trace_tail); F(c->d_tail[0]); F(c->d_tail[1]);
-    F(c->d_pf_A); F(c->d_pf_pn); F(c->d_pf_ones);
-    F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
-    F(c->d_em_update); F(c->d_em_target);
-    F(c->d_X); F(c->d_Y); F(c->d_T); F(c->d_spec_grid); F(c->d_spec_T); F(c->d_spec_part);
-    F(c->d_trk_theta); F(c->d_trk_int); F(c->d_trk_peak); F(c->d_trk_T0); F(c->d_trk_part);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    c->stage.release();
-    delete c;
+    delete c;                                                  // every device buffer goes with its member
+}
+
+// elements of a per-source array [max_streams][slots][row] (slots = 1: of a per-stream array [max_streams][row])
+inline size_t slot_elems(const mca_hip_mvdr_ctx *c, int slots, size_t row) { return (size_t)c->cfg.max_streams * slots * row; }
+
+// a workspace of at least n elements
+template <typename T>
+int grow_ws(mca_hip_mvdr_ctx *c, DevBuf<T> &b, size_t n, const char *what)
+{
+    const hipError_t e = b.grow(n);
+    return e == hipSuccess ? MCA_HIP_OK : hip_fail(c, e, what);
+}
+
+// weights of 1 for a call that brings none: at least n of them
+hipError_t ensure_ones(DevBuf<float> &b, size_t n)
+{
+    if (n <= b.n) return hipSuccess;
+    const std::vector<float> ones(n, 1.f);
+    return b.upload(ones.data(), n);
+}
+
+// the array [max_streams][old_slots][row] laid out anew for new_slots: the slots both layouts have keep their content, the
+// others start at zero.  Synchronous; `fresh` is empty on failure
+template <typename T>
+hipError_t reslot(const mca_hip_mvdr_ctx *c, const DevBuf<T> &old, int old_slots, int new_slots, size_t row, DevBuf<T> &fresh)
+{
+    const size_t rb = row * sizeof(T);
+    hipError_t e = fresh.alloc_zero(slot_elems(c, new_slots, row));
+    if (e == hipSuccess) e = hipMemcpy2D(fresh.p, new_slots * rb, old.p, old_slots * rb, std::min(old_slots, new_slots) * rb, (size_t)c->cfg.max_streams, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) fresh.reset();
+    return e;
+}
+
+// a slot the call leaves out restarts from nothing: the slots n_sources ... max_sources - 1 of the first n_streams streams of
+// buf [max_streams][max_sources][row_elems] are cleared on the stream.  The kernels touch only the slots below n_sources
+template <typename T>
+hipError_t clear_unused_slots(const mca_hip_mvdr_ctx *c, T *buf, size_t row_elems, int n_sources, int n_streams, hipStream_t st)
+{
+    if (n_sources >= c->max_sources) return hipSuccess;
+    const size_t rb = row_elems * sizeof(T);
+    return hipMemset2DAsync(buf + n_sources * row_elems, c->max_sources * rb, 0, (c->max_sources - n_sources) * rb, (size_t)n_streams, st);
 }
 
 MvdrGeometry geometry_args(const mca_hip_mvdr_ctx *c)
@@ -145,85 +186,51 @@ double host_projection(const mca_hip_mvdr_ctx *c, int m, double theta)
     return pr;
 }
 
+// every state array from nothing (those of a feature that is off are empty, and cleared as such)
 int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
 {
-    const size_t ns = (size_t)c->cfg.max_streams;
-    VHIP_TRY(c, hipMemsetAsync(c->d_phi, 0, ns * c->K * c->tri * sizeof(float2), st));
-    VHIP_TRY(c, hipMemsetAsync(c->d_trace, 0, ns * c->K * 4, st));
-    for (int i = 0; i < 2; ++i) VHIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, ns * c->max_sources * c->H * 4, st));
-    if (c->d_pf_A) VHIP_TRY(c, hipMemsetAsync(c->d_pf_A, 0, ns * c->max_sources * c->K * 4, st));
-    if (c->rtf_on) {
-        VHIP_TRY(c, hipMemsetAsync(c->d_psi, 0, ns * c->max_sources * c->K * c->tri * sizeof(float2), st));
-        VHIP_TRY(c, hipMemsetAsync(c->d_cpsi, 0, ns * c->max_sources * c->K * 4, st));
-        VHIP_TRY(c, hipMemsetAsync(c->d_cphi, 0, ns * c->K * 4, st));
-    }
-    if (c->d_trk_theta) {
-        VHIP_TRY(c, hipMemsetAsync(c->d_trk_theta, 0, ns * MCA_MAX_SOURCES * 4, st));
-        VHIP_TRY(c, hipMemsetAsync(c->d_trk_int, 0, ns * MCA_MAX_SOURCES * 3 * 4, st));
-    }
+    VHIP_TRY(c, c->d_phi.zero_async(st));
+    VHIP_TRY(c, c->d_trace.zero_async(st));
+    for (int i = 0; i < 2; ++i) VHIP_TRY(c, c->d_tail[i].zero_async(st));
+    VHIP_TRY(c, c->d_pf_A.zero_async(st));
+    VHIP_TRY(c, c->d_psi.zero_async(st));
+    VHIP_TRY(c, c->d_cpsi.zero_async(st));
+    VHIP_TRY(c, c->d_cphi.zero_async(st));
+    VHIP_TRY(c, c->d_trk_theta.zero_async(st));
+    VHIP_TRY(c, c->d_trk_int.zero_async(st));
     VHIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
+// the workspaces of a call of `rows` (stream, frame) pairs; plane_rows: those of a chunk of an RTF call
 int ensure_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_ones, bool rtf, size_t plane_rows = 0)
 {
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
+    int rc;
     if (rtf) {
-        const size_t cells = plane_rows * n_sources * c->K * c->M;
-        if (cells > c->d_cap) {
-            F(c->d_D); c->d_D = nullptr; c->d_cap = 0;
-            VHIP_TRY(c, hipMalloc((void **)&c->d_D, cells * sizeof(float2)));
-            c->d_cap = cells;
-        }
-        if (want_ones && rows * c->K > c->rtf_ones_n) {
-            // the solve behind k_mvdr_rtf takes a weight per cell: a call without an update mask passes ones, whose bytes are those of no weights
-            F(c->d_rtf_ones); c->d_rtf_ones = nullptr; c->rtf_ones_n = 0;
-            VHIP_TRY(c, hipMalloc((void **)&c->d_rtf_ones, rows * c->K * 4));
-            std::vector<float> ones(rows * c->K, 1.f);
-            VHIP_TRY(c, hipMemcpy(c->d_rtf_ones, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
-            c->rtf_ones_n = rows * c->K;
-        }
+        if ((rc = grow_ws(c, c->d_D, plane_rows * n_sources * c->K * c->M, "steering plane of the RTF call"))) return rc;
+        // the solve behind k_mvdr_rtf takes a weight per cell: a call without an update mask passes ones, whose bytes are those of no weights
+        if (want_ones)
+            if (const hipError_t e = ensure_ones(c->d_rtf_ones, rows * c->K)) return hip_fail(c, e, "update mask of ones of the RTF call");
         want_ones = false;
     }
-    if (c->pf_on && want_ones && rows > c->pf_ones_n) {
-        // a call without update weights still takes the gated kernels (they emit the noise plane): weights of 1, whose bytes are
-        // those of the unweighted kernels
-        F(c->d_pf_ones); c->d_pf_ones = nullptr; c->pf_ones_n = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_pf_ones, rows * 4));
-        std::vector<float> ones(rows, 1.f);
-        VHIP_TRY(c, hipMemcpy(c->d_pf_ones, ones.data(), rows * 4, hipMemcpyHostToDevice));
-        c->pf_ones_n = rows;
-    }
-    if (rows > c->x_rows) {
-        F(c->d_X); c->d_X = nullptr; c->x_rows = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_X, rows * c->K * c->M * sizeof(float2)));
-        c->x_rows = rows;
-    }
+    // a call without update weights still takes the gated kernels (they emit the noise plane): weights of 1, whose bytes are
+    // those of the unweighted kernels
+    if (c->pf_on && want_ones)
+        if (const hipError_t e = ensure_ones(c->d_pf_ones, rows)) return hip_fail(c, e, "update weights of ones of the post-filter");
+    if ((rc = grow_ws(c, c->d_X, rows * c->K * c->M, "spectra of the call"))) return rc;
     const size_t yrows = rows * n_sources;
-    if (yrows > c->y_rows) {
-        F(c->d_Y); F(c->d_T); F(c->d_pf_pn); c->d_Y = nullptr; c->d_T = nullptr; c->d_pf_pn = nullptr; c->y_rows = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_Y, yrows * c->K * sizeof(float2)));
-        VHIP_TRY(c, hipMalloc((void **)&c->d_T, yrows * c->M * (c->N / 64 + 33) * sizeof(float2)));
-        c->y_rows = yrows;
-    }
-    if (c->pf_on && !c->d_pf_pn && c->y_rows) VHIP_TRY(c, hipMalloc((void **)&c->d_pf_pn, c->y_rows * c->K * 4));
+    if ((rc = grow_ws(c, c->d_Y, yrows * c->K, "beamformed spectra of the call"))) return rc;
+    if ((rc = grow_ws(c, c->d_T, yrows * c->M * (c->N / 64 + 33), "steering tables of the call"))) return rc;
+    if (c->pf_on && (rc = grow_ws(c, c->d_pf_pn, yrows * c->K, "noise plane of the post-filter"))) return rc;
     return MCA_HIP_OK;
 }
 
 // the masks of an auto call that the caller does not take back: workspace that grows with the call's shape, as d_T does
 int ensure_estmask_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want_update, bool want_target)
 {
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    if (want_update && rows * c->K > c->em_update_n) {
-        F(c->d_em_update); c->d_em_update = nullptr; c->em_update_n = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_em_update, rows * c->K * 4));
-        c->em_update_n = rows * c->K;
-    }
-    if (want_target && rows * n_sources * c->K > c->em_target_n) {
-        F(c->d_em_target); c->d_em_target = nullptr; c->em_target_n = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_em_target, rows * n_sources * c->K * 4));
-        c->em_target_n = rows * n_sources * c->K;
-    }
+    int rc;
+    if (want_update && (rc = grow_ws(c, c->d_em_update, rows * c->K, "estimated update mask"))) return rc;
+    if (want_target && (rc = grow_ws(c, c->d_em_target, rows * n_sources * c->K, "estimated target masks"))) return rc;
     return MCA_HIP_OK;
 }
 
@@ -315,22 +322,18 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     for (int m = 0; m < c->M; ++m)
         for (int j = 0; j < 3; ++j) c->geo_u[(size_t)j * c->M + m] = unit * cfg->mic_xyz[3 * m + j];
 
-    int rc = MCA_HIP_OK;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        VHIP_TRY(c, hipMalloc(dst, bytes));
-        VHIP_TRY(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return MCA_HIP_OK;
-    };
-    auto alloc = [&](void **dst, size_t bytes) -> int { VHIP_TRY(c, hipMalloc(dst, bytes)); return MCA_HIP_OK; };
-    const size_t ns = (size_t)cfg->max_streams;
-    if ((rc = up((void **)&c->d_window, win.data(), win.size() * 4)) || (rc = up((void **)&c->d_tw, tw.data(), tw.size() * 8)) ||
-        (rc = up((void **)&c->d_micx, mx.data(), mx.size() * 8)) || (rc = up((void **)&c->d_geo_u, c->geo_u.data(), c->geo_u.size() * 8)) ||
-        (rc = alloc((void **)&c->d_phi, ns * c->K * c->tri * sizeof(float2))) || (rc = alloc((void **)&c->d_trace, ns * c->K * 4)) ||
-        (rc = alloc((void **)&c->d_phi_tail, (size_t)128 * 64 * c->tri * sizeof(float2))) || (rc = alloc((void **)&c->d_trace_tail, (size_t)128 * 64 * 4)) ||
-        (rc = alloc((void **)&c->d_tail[0], ns * c->H * 4)) || (rc = alloc((void **)&c->d_tail[1], ns * c->H * 4)) ||
-        (rc = init_state(c, nullptr))) {
-        g_mvdr_create_error = c->err; free_mvdr(c); return rc;
-    }
+    const size_t nk = slot_elems(c, 1, c->K);
+    hipError_t e = c->d_window.upload(win.data(), win.size());
+    if (e == hipSuccess) e = c->d_tw.upload(tw.data(), tw.size());
+    if (e == hipSuccess) e = c->d_micx.upload(mx.data(), mx.size());
+    if (e == hipSuccess) e = c->d_geo_u.upload(c->geo_u.data(), c->geo_u.size());
+    if (e == hipSuccess) e = c->d_phi.alloc(nk * c->tri);
+    if (e == hipSuccess) e = c->d_trace.alloc(nk);
+    if (e == hipSuccess) e = c->d_phi_tail.alloc((size_t)128 * 64 * c->tri);
+    if (e == hipSuccess) e = c->d_trace_tail.alloc((size_t)128 * 64);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = c->d_tail[i].alloc(slot_elems(c, c->max_sources, c->H));
+    const int rc = e != hipSuccess ? hip_fail(c, e, "tables and state of the context") : init_state(c, nullptr);
+    if (rc) { g_mvdr_create_error = c->err; free_mvdr(c); return rc; }
     *out = c;
     return MCA_HIP_OK;
 }
@@ -357,60 +360,23 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
     if (max_sources == c->max_sources) return MCA_HIP_OK;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     VHIP_TRY(c, hipDeviceSynchronize());
-    // new tails [max_streams][max_sources][H]: the slots both layouts have keep their content, the others start at zero
-    const size_t ns = (size_t)c->cfg.max_streams, row = (size_t)c->H * 4, bytes = ns * max_sources * row;
-    const int keep = max_sources < c->max_sources ? max_sources : c->max_sources;
-    float *nt[2] = {nullptr, nullptr};
-    hipError_t e = hipMalloc((void **)&nt[0], bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&nt[1], bytes);
-    if (e == hipSuccess) e = hipMemset(nt[0], 0, bytes);
-    if (e == hipSuccess) e = hipMemset(nt[1], 0, bytes);
-    if (e == hipSuccess) e = hipMemcpy2D(nt[0], max_sources * row, c->d_tail[c->tail_cur], c->max_sources * row, keep * row, ns, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-        if (nt[0]) (void)hipFree(nt[0]);
-        if (nt[1]) (void)hipFree(nt[1]);
-        return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("overlap-add tails of the new sources: ") + hipGetErrorString(e));
-    }
-    // Psi and cpsi [max_streams][max_sources][...] of a context with RTF enabled, by the same rule
-    float2 *npsi = nullptr; float *ncpsi = nullptr;
+    // every array [max_streams][max_sources][...] is built anew by the slot rule (reslot) and swapped in once all of them stand:
+    // a failure leaves the context as it was.  The tail that is not current starts at zero
+    const int old = c->max_sources;
+    DevBuf<float> nt[2], ncpsi, na;
+    DevBuf<float2> npsi;
+    hipError_t e = reslot(c, c->d_tail[c->tail_cur], old, max_sources, c->H, nt[0]);
+    if (e == hipSuccess) e = nt[1].alloc_zero(slot_elems(c, max_sources, c->H));
+    if (e != hipSuccess) return hip_fail(c, e, "overlap-add tails of the new sources");
     if (c->rtf_on) {
-        const size_t prow = (size_t)c->K * c->tri * sizeof(float2), crow = (size_t)c->K * 4;
-        e = hipMalloc((void **)&npsi, ns * max_sources * prow);
-        if (e == hipSuccess) e = hipMalloc((void **)&ncpsi, ns * max_sources * crow);
-        if (e == hipSuccess) e = hipMemset(npsi, 0, ns * max_sources * prow);
-        if (e == hipSuccess) e = hipMemset(ncpsi, 0, ns * max_sources * crow);
-        if (e == hipSuccess) e = hipMemcpy2D(npsi, max_sources * prow, c->d_psi, c->max_sources * prow, keep * prow, ns, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy2D(ncpsi, max_sources * crow, c->d_cpsi, c->max_sources * crow, keep * crow, ns, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            if (npsi) (void)hipFree(npsi);
-            if (ncpsi) (void)hipFree(ncpsi);
-            (void)hipFree(nt[0]); (void)hipFree(nt[1]);
-            return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("target covariances of the new sources: ") + hipGetErrorString(e));
-        }
+        e = reslot(c, c->d_psi, old, max_sources, (size_t)c->K * c->tri, npsi);
+        if (e == hipSuccess) e = reslot(c, c->d_cpsi, old, max_sources, c->K, ncpsi);
+        if (e != hipSuccess) return hip_fail(c, e, "target covariances of the new sources");
     }
-    // the post-filter's A [max_streams][max_sources][K] of an enabled context, by the same rule
-    float *na = nullptr;
-    if (c->pf_on) {
-        const size_t arow = (size_t)c->K * 4, abytes = ns * max_sources * arow;
-        e = hipMalloc((void **)&na, abytes);
-        if (e == hipSuccess) e = hipMemset(na, 0, abytes);
-        if (e == hipSuccess) e = hipMemcpy2D(na, max_sources * arow, c->d_pf_A, c->max_sources * arow, keep * arow, ns, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            if (na) (void)hipFree(na);
-            if (npsi) (void)hipFree(npsi);
-            if (ncpsi) (void)hipFree(ncpsi);
-            (void)hipFree(nt[0]); (void)hipFree(nt[1]);
-            return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("post-filter state of the new sources: ") + hipGetErrorString(e));
-        }
-        (void)hipFree(c->d_pf_A);
-        c->d_pf_A = na;
-    }
-    if (c->rtf_on) {
-        (void)hipFree(c->d_psi); (void)hipFree(c->d_cpsi);
-        c->d_psi = npsi; c->d_cpsi = ncpsi;
-    }
-    (void)hipFree(c->d_tail[0]); (void)hipFree(c->d_tail[1]);
-    c->d_tail[0] = nt[0]; c->d_tail[1] = nt[1]; c->tail_cur = 0; c->max_sources = max_sources;
+    if (c->pf_on && (e = reslot(c, c->d_pf_A, old, max_sources, c->K, na)) != hipSuccess) return hip_fail(c, e, "post-filter state of the new sources");
+    c->d_tail[0].swap(nt[0]); c->d_tail[1].swap(nt[1]); c->tail_cur = 0;
+    c->d_psi.swap(npsi); c->d_cpsi.swap(ncpsi); c->d_pf_A.swap(na);    // (empty for empty where the feature is off)
+    c->max_sources = max_sources;
     if (c->trk_on && max_sources < c->trk.n_tracks) { c->trk_on = false; c->trk.enable = 0; }      // fewer slots than tracks
     return MCA_HIP_OK;
 }
@@ -493,20 +459,11 @@ int mca_hip_mvdr_set_postfilter(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_postfilt
         VHIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
         if (on) {
             // A starts from zero; the noise plane and the ones come with the first call (ensure_ws)
-            const size_t bytes = (size_t)c->cfg.max_streams * c->max_sources * c->K * 4;
-            float *na = nullptr;
-            hipError_t e = hipMalloc((void **)&na, bytes);
-            if (e == hipSuccess) e = hipMemset(na, 0, bytes);
-            if (e != hipSuccess) {
-                if (na) (void)hipFree(na);
-                return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("post-filter state: ") + hipGetErrorString(e));
-            }
-            c->d_pf_A = na;
+            DevBuf<float> na;
+            if (const hipError_t e = na.alloc_zero(slot_elems(c, c->max_sources, c->K))) return hip_fail(c, e, "post-filter state");
+            c->d_pf_A.swap(na);
         } else {
-            if (c->d_pf_A) (void)hipFree(c->d_pf_A);
-            if (c->d_pf_pn) (void)hipFree(c->d_pf_pn);
-            if (c->d_pf_ones) (void)hipFree(c->d_pf_ones);
-            c->d_pf_A = nullptr; c->d_pf_pn = nullptr; c->d_pf_ones = nullptr; c->pf_ones_n = 0;
+            c->d_pf_A.reset(); c->d_pf_pn.reset(); c->d_pf_ones.reset();
         }
         c->pf_on = on;
         if (on) c->pf_ever = true;
@@ -539,31 +496,21 @@ int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_rtf_config *cfg
     if (on != c->rtf_on) {
         VHIP_TRY(c, hipSetDevice(c->cfg.device));
         VHIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
-        auto F = [](void *p) { if (p) (void)hipFree(p); };
         if (on) {
             // Psi = 0, cpsi = 0; cphi = 1 where the covariance holds something (its weights were not counted: taken as complete)
-            const size_t ns = (size_t)c->cfg.max_streams, nk = ns * c->K;
-            const size_t pb = ns * c->max_sources * c->K * c->tri * sizeof(float2), cb = ns * c->max_sources * c->K * 4;
-            float2 *npsi = nullptr; float *ncpsi = nullptr, *ncphi = nullptr, *nnext = nullptr;
-            std::vector<float> tr(nk);
-            hipError_t e = hipMalloc((void **)&npsi, pb);
-            if (e == hipSuccess) e = hipMalloc((void **)&ncpsi, cb);
-            if (e == hipSuccess) e = hipMalloc((void **)&ncphi, nk * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&nnext, nk * 4);
-            if (e == hipSuccess) e = hipMemset(npsi, 0, pb);
-            if (e == hipSuccess) e = hipMemset(ncpsi, 0, cb);
-            if (e == hipSuccess) e = hipMemcpy(tr.data(), c->d_trace, nk * 4, hipMemcpyDeviceToHost);
+            DevBuf<float2> npsi;
+            DevBuf<float> ncpsi, ncphi, nnext;
+            std::vector<float> tr(c->d_trace.n);
+            hipError_t e = npsi.alloc_zero(slot_elems(c, c->max_sources, (size_t)c->K * c->tri));
+            if (e == hipSuccess) e = ncpsi.alloc_zero(slot_elems(c, c->max_sources, c->K));
+            if (e == hipSuccess) e = nnext.alloc(tr.size());
+            if (e == hipSuccess) e = hipMemcpy(tr.data(), c->d_trace, c->d_trace.bytes(), hipMemcpyDeviceToHost);
             for (auto &v : tr) v = v > 1e-30f ? 1.f : 0.f;
-            if (e == hipSuccess) e = hipMemcpy(ncphi, tr.data(), nk * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                F(npsi); F(ncpsi); F(ncphi); F(nnext);
-                return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("RTF state: ") + hipGetErrorString(e));
-            }
-            c->d_psi = npsi; c->d_cpsi = ncpsi; c->d_cphi = ncphi; c->d_cphi_next = nnext;
+            if (e == hipSuccess) e = ncphi.upload(tr.data(), tr.size());
+            if (e != hipSuccess) return hip_fail(c, e, "RTF state");
+            c->d_psi.swap(npsi); c->d_cpsi.swap(ncpsi); c->d_cphi.swap(ncphi); c->d_cphi_next.swap(nnext);
         } else {
-            F(c->d_psi); F(c->d_cpsi); F(c->d_cphi); F(c->d_cphi_next); F(c->d_D); F(c->d_rtf_ones);
-            c->d_psi = nullptr; c->d_cpsi = nullptr; c->d_cphi = nullptr; c->d_cphi_next = nullptr;
-            c->d_D = nullptr; c->d_cap = 0; c->d_rtf_ones = nullptr; c->rtf_ones_n = 0;
+            c->d_psi.reset(); c->d_cpsi.reset(); c->d_cphi.reset(); c->d_cphi_next.reset(); c->d_D.reset(); c->d_rtf_ones.reset();
             if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }     // own tracks read Psi and a birth clears it: configured anew
         }
         c->rtf_on = on;
@@ -606,9 +553,7 @@ int mca_hip_mvdr_set_mask_estimator(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_estm
         if (!on) {
             VHIP_TRY(c, hipSetDevice(c->cfg.device));
             VHIP_TRY(c, hipDeviceSynchronize());               // no call in flight reads what is freed here
-            if (c->d_em_update) (void)hipFree(c->d_em_update);
-            if (c->d_em_target) (void)hipFree(c->d_em_target);
-            c->d_em_update = nullptr; c->d_em_target = nullptr; c->em_update_n = 0; c->em_target_n = 0;
+            c->d_em_update.reset(); c->d_em_target.reset();
         }
         c->em_on = on;                                         // (the workspace comes with the first auto call: ensure_estmask_ws)
         if (on) c->em_ever = true;
@@ -628,13 +573,28 @@ int mca_hip_mvdr_get_mask_estimator(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_estm
 
 namespace {
 
-// the analysis (timing slot 0): PCM -> X, and the steering tables T of doa_rad [streams][F][n_sources]
-int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams, int n_frames,
-                   int n_sources, const float *doa_rad, hipStream_t st)
+// A call with n_sources look directions per frame, every pointer of the same side (device for mvdr_frames_dev and the launches,
+// host for mvdr_frames_host).  doa [streams][F][n_sources], out_pcm [streams][n_sources][F hop], out_spec [streams][n_sources][F][K]
+// update: covariance update weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
+// rtf: the call of mca_hip_mvdr_sources_frames_rtf_*, tmask [streams][n_sources][F][K] or NULL (all 0), update its update mask
+// est: the call of mca_hip_mvdr_sources_frames_auto_* (masked, rtf on a context with RTF enabled; update and tmask NULL): both masks
+// come from k_mvdr_estmask, into em_update / em_target where the caller takes them back, else into the workspace
+struct MvdrCall {
+    int n_streams = 0, n_frames = 0, n_sources = 0;
+    const float *doa = nullptr, *update = nullptr;
+    bool masked = false;
+    const float *tmask = nullptr;
+    bool rtf = false, est = false;
+    float *em_update = nullptr, *em_target = nullptr, *out_pcm = nullptr, *out_spec = nullptr;
+};
+
+// the analysis (timing slot 0): PCM -> X, and the steering tables T of doa [streams][F][n_sources]
+int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, const MvdrCall &q, hipStream_t st)
 {
+    const int n_streams = q.n_streams, n_frames = q.n_frames;
     MvdrAnalyseArgs aa{};
     aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = n_frames;
-    aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.S = n_sources; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = doa_rad;
+    aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.S = q.n_sources; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = q.doa;
     aa.X = c->d_X; aa.T = c->d_T; aa.mic_x = c->d_micx; aa.geo = geometry_args(c);
     aa.unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;                      // Beamformer.cpp:59 without 2 pi
     t_begin(c, 0, st);
@@ -662,12 +622,13 @@ int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_strid
     return MCA_HIP_OK;
 }
 
-// the solve (timing slot 1): X, T -> Y, the covariance and, for the post-filter, the noise plane.  update: covariance update
-// weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
+// the solve (timing slot 1): X, T -> Y, the covariance and, for the post-filter, the noise plane
 // rtf: the frames f0 ... f0 + n_loop - 1 of the call (the steering plane holds those), else the whole call
-int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float *update, bool masked, bool rtf, float2 *Y, hipStream_t st,
-                 int f0 = 0, int n_loop = 0)
+int launch_solve(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStream_t st, int f0 = 0, int n_loop = 0)
 {
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
+    const float *update = q.update;
+    const bool rtf = q.rtf;
     if (!rtf) n_loop = n_frames;
     MvdrSolveArgs sa{};
     sa.X = c->d_X; sa.T = c->d_T;
@@ -677,9 +638,9 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
     sa.phi = c->d_phi; sa.trace = c->d_trace; sa.Y = Y;
     sa.n_streams = n_streams; sa.S = n_sources;
     // the kernels that store the noise plane take weights: a call without them passes ones, whose bytes are those of no weights
-    sa.update = update ? update : c->pf_on ? c->d_pf_ones : nullptr;
+    sa.update = update ? update : c->pf_on ? c->d_pf_ones.p : nullptr;
     sa.null_gain = (float)c->null_gain;
-    sa.pn = c->pf_on ? c->d_pf_pn : nullptr;
+    sa.pn = c->pf_on ? c->d_pf_pn.p : nullptr;
     const bool nulls = n_sources > 1 && sa.null_gain > 0.f;                           // a gain that rounds to 0 in fp32 is gain 0
     const int Q = (c->M + 3) / 4;                                                     // row slots per lane
     int lds = 0;
@@ -687,14 +648,14 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
     if (rtf) {
         // the right-hand sides come from the steering plane; a weight per cell always (ones for a call without an update mask)
         sa.D = c->d_D; sa.n_loop = n_loop;
-        sa.update = (update ? update : c->d_rtf_ones) + (size_t)f0 * c->K;
+        sa.update = (update ? update : c->d_rtf_ones.p) + (size_t)f0 * c->K;
         sa.X += (size_t)f0 * c->K * c->M; sa.Y += (size_t)f0 * c->K;
         if (sa.pn) sa.pn += (size_t)f0 * c->K;
         // nulls at the vectors of the plane (mvdr_frames_dev lets a gain through only under mca_hip_mvdr_set_rtf_nulls); else the RTF kernels
         if (nulls) kernel = c->pf_on ? mvdr_solve_rtf_nulls_kernel_of<true>(Q, n_sources, &lds) : mvdr_solve_rtf_nulls_kernel_of<false>(Q, n_sources, &lds);
         else kernel = c->pf_on ? mvdr_solve_rtf_kernel_of<true>(Q, c->M == 4 * Q, n_sources) : mvdr_solve_rtf_kernel_of<false>(Q, c->M == 4 * Q, n_sources);
     } else
-        kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
+        kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && q.masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
                                    c->pf_on, &lds);
     if (!kernel) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
     auto launch = [&](long long pid0, long long n_prob, int pieces) {
@@ -730,15 +691,14 @@ int launch_solve(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
 }
 
 // the target covariances and the steering plane (timing slot 5): X, T, the masks -> D, Psi, cpsi, cphi; between the analysis and the solve
-int launch_rtf(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float *update, const float *tmask, hipStream_t st, int f0, int n_loop)
+int launch_rtf(mca_hip_mvdr_ctx *c, const MvdrCall &q, hipStream_t st, int f0, int n_loop)
 {
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
+    const float *update = q.update, *tmask = q.tmask;
     // a slot the call leaves out restarts from nothing learned; the kernel touches only the slots below n_sources
-    if (f0 == 0 && n_sources < c->max_sources) {
-        const size_t prow = (size_t)c->K * c->tri * sizeof(float2), crow = (size_t)c->K * 4;
-        VHIP_TRY(c, hipMemset2DAsync(reinterpret_cast<char *>(c->d_psi) + n_sources * prow, c->max_sources * prow, 0,
-                                     (c->max_sources - n_sources) * prow, (size_t)n_streams, st));
-        VHIP_TRY(c, hipMemset2DAsync(reinterpret_cast<char *>(c->d_cpsi) + n_sources * crow, c->max_sources * crow, 0,
-                                     (c->max_sources - n_sources) * crow, (size_t)n_streams, st));
+    if (f0 == 0) {
+        VHIP_TRY(c, clear_unused_slots(c, c->d_psi.p, (size_t)c->K * c->tri, n_sources, n_streams, st));
+        VHIP_TRY(c, clear_unused_slots(c, c->d_cpsi.p, c->K, n_sources, n_streams, st));
     }
     MvdrRtfArgs ra{};
     const size_t nph = (size_t)c->N / 64 + 33;
@@ -762,16 +722,17 @@ int launch_rtf(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, 
 }
 
 // the mask estimator (timing slot 6): X, T -> the update mask and the target masks of the whole call; between the analysis and
-// k_mvdr_rtf / the solve.  target may be NULL (a call without RTF whose caller takes no target masks back)
-int launch_estmask(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, float *update, float *target, hipStream_t st)
+// k_mvdr_rtf / the solve, into em_update and em_target.  em_target may be NULL (a call without RTF whose caller takes no target masks back)
+int launch_estmask(mca_hip_mvdr_ctx *c, const MvdrCall &q, hipStream_t st)
 {
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     MvdrEstmaskArgs ea{};
     ea.X = c->d_X; ea.T = c->d_T;
     ea.n_streams = n_streams; ea.n_frames = n_frames; ea.K = c->K; ea.M = c->M; ea.S = n_sources;
     ea.bin_lo = c->em_bin_lo; ea.bin_hi = c->em_bin_hi;
     ea.n_protected = c->em_protected == 0 || c->em_protected > n_sources ? n_sources : c->em_protected;
     ea.coherence_lo = (float)c->em_lo; ea.coherence_span = (float)(c->em_hi - c->em_lo);
-    ea.update = update; ea.target = target;
+    ea.update = q.em_update; ea.target = q.em_target;
     const void *kernel = mvdr_estmask_kernel((c->M + 3) / 4);
     const long long cells = (long long)n_streams * n_frames * c->K;
     void *kargs[1] = {&ea};
@@ -782,13 +743,12 @@ int launch_estmask(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sourc
 }
 
 // the post-filter (timing slot 4): Z = G Y in place, between the solve and the synthesis
-int launch_postfilter(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, float2 *Y, hipStream_t st)
+int launch_postfilter(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStream_t st)
 {
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     // A slot the call leaves out restarts from silence, whether the call has out_pcm or not; the kernel touches only the slots
     // below n_sources
-    if (n_sources < c->max_sources)
-        VHIP_TRY(c, hipMemset2DAsync(c->d_pf_A + (size_t)n_sources * c->K, (size_t)c->max_sources * c->K * 4, 0,
-                                     (size_t)(c->max_sources - n_sources) * c->K * 4, (size_t)n_streams, st));
+    VHIP_TRY(c, clear_unused_slots(c, c->d_pf_A.p, c->K, n_sources, n_streams, st));
     MvdrPostfilterArgs fa{};
     fa.Y = Y; fa.pn = c->d_pf_pn; fa.A = c->d_pf_A;
     fa.n_streams = n_streams; fa.S = n_sources; fa.slots = c->max_sources; fa.n_frames = n_frames; fa.K = c->K;
@@ -802,23 +762,22 @@ int launch_postfilter(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_so
 }
 
 // the synthesis (timing slot 2): Y -> out_pcm [streams][n_sources][F hop], and the overlap-add tails
-int launch_synth(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources, const float2 *Y, float *out_pcm, hipStream_t st)
+int launch_synth(mca_hip_mvdr_ctx *c, const MvdrCall &q, const float2 *Y, hipStream_t st)
 {
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     MvdrSynthArgs ya{};
     ya.Y = Y; ya.n_frames = n_frames; ya.N = c->N; ya.logH = c->logH; ya.tw = c->d_tw;
     ya.S = n_sources; ya.tail_slots = c->max_sources;
     const int n_out = n_streams * n_sources;                                          // one inverse transform + overlap-add each
     ya.ft = 16;
     while (ya.ft > 2 && (long long)n_out * ((n_frames + ya.ft - 1) / ya.ft) < 1024) ya.ft >>= 1;
-    ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = out_pcm;
+    ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = q.out_pcm;
     const size_t smem3 = (size_t)(c->H + 1) * sizeof(float2) + (size_t)c->H * 4;
     if (smem3 > 64 * 1024)
         VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_synth), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3));
     // a slot the call leaves out restarts from silence.  The kernel writes only the slots below n_sources, so the clear goes
     // first: if it fails, nothing has touched the tails yet and tail_cur still names the valid ones
-    if (n_sources < c->max_sources)
-        VHIP_TRY(c, hipMemset2DAsync(ya.tail_out + (size_t)n_sources * c->H, (size_t)c->max_sources * c->H * 4, 0,
-                                     (size_t)(c->max_sources - n_sources) * c->H * 4, (size_t)n_streams, st));
+    VHIP_TRY(c, clear_unused_slots(c, ya.tail_out, c->H, n_sources, n_streams, st));
     t_begin(c, 2, st);
     hipLaunchKernelGGL(k_mvdr_synth, dim3((n_frames + ya.ft - 1) / ya.ft, n_out), dim3(c->H >= 1024 ? 512 : 256), smem3, st, ya);
     t_end(c, st);
@@ -826,25 +785,20 @@ int launch_synth(mca_hip_mvdr_ctx *c, int n_streams, int n_frames, int n_sources
     return MCA_HIP_OK;
 }
 
-// a call with n_sources look directions per frame: doa_rad [streams][F][n_sources], out_pcm [streams][n_sources][F hop],
-// out_spec [streams][n_sources][F][K]; update: covariance update weights [streams][F], or [streams][F][K] (masked), or NULL (all 1)
-// rtf: the call of mca_hip_mvdr_sources_frames_rtf_*, tmask [streams][n_sources][F][K] or NULL (all 0), update its update mask
-// est: the call of mca_hip_mvdr_sources_frames_auto_* (masked, rtf on a context with RTF enabled; update and tmask NULL): both masks
-// come from k_mvdr_estmask, into em_update / em_target where the caller takes them back, else into the workspace
-int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
-                    int n_frames, int n_sources, const float *doa_rad, const float *update, bool masked, float *out_pcm,
-                    float *out_spec, void *stream, const float *tmask = nullptr, bool rtf = false, bool est = false,
-                    float *em_update = nullptr, float *em_target = nullptr)
+// the call on device pointers: pcm with its strides, the launches on `stream`
+int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, const MvdrCall &call, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (est && !c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
-    if (rtf && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
-    if (rtf && c->null_gain != 0.0 && !c->rtf_nulls)
+    MvdrCall q = call;                                          // (an auto call: update and tmask become the estimated masks below)
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
+    if (q.est && !c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
+    if (q.rtf && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (q.rtf && c->null_gain != 0.0 && !c->rtf_nulls)
         return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0, or enable them (mca_hip_mvdr_set_rtf_nulls)");
     if (n_sources < 1 || n_sources > c->max_sources)
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
-    if (!pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
-    if (!out_pcm && !out_spec) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
+    if (!pcm || !q.doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
+    if (!q.out_pcm && !q.out_spec) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
     if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
     if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
     const long long need = (long long)(n_frames + 1) * c->H;
@@ -852,75 +806,79 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     if (n_streams > 1 && stream_stride < (long long)(c->M - 1) * mic_stride + need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_stride too short");
     if ((mic_stride & 1) || (stream_stride & 1) || (reinterpret_cast<uintptr_t>(pcm) & 7))
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
-    if (out_spec && (reinterpret_cast<uintptr_t>(out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
+    if (q.out_spec && (reinterpret_cast<uintptr_t>(q.out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     // the steering plane of an RTF call holds fc frames: all of them, or as many as the workspace cap takes (how a stream is cut does not change bytes)
     int fc = n_frames;
-    if (rtf) {
+    if (q.rtf) {
         const size_t per_frame = (size_t)n_streams * n_sources * c->K * c->M;
         if (per_frame * n_frames > c->plane_cap_cells) {
             const int fmax = (int)std::max<size_t>(1, c->plane_cap_cells / per_frame), chunks = (n_frames + fmax - 1) / fmax;
             fc = (n_frames + chunks - 1) / chunks;          // chunks of equal length, the last one shorter at most
         }
     }
-    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !update && !est, rtf, (size_t)n_streams * fc);
+    int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !q.update && !q.est, q.rtf, (size_t)n_streams * fc);
     if (rc) return rc;
-    if (est && (rc = ensure_estmask_ws(c, (size_t)n_streams * n_frames, n_sources, !em_update, rtf && !em_target))) return rc;
+    if (q.est && (rc = ensure_estmask_ws(c, (size_t)n_streams * n_frames, n_sources, !q.em_update, q.rtf && !q.em_target))) return rc;
     // the beamformed spectra go straight to the caller's buffer when one is given
-    float2 *Y = out_spec ? reinterpret_cast<float2 *>(out_spec) : c->d_Y;
-    if ((rc = launch_analyse(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, st))) return rc;
-    if (est) {
+    float2 *Y = q.out_spec ? reinterpret_cast<float2 *>(q.out_spec) : c->d_Y.p;
+    if ((rc = launch_analyse(c, pcm, stream_stride, mic_stride, q, st))) return rc;
+    if (q.est) {
         // the masks of the whole call, once, ahead of the chunk loop as the analysis is
-        if (!em_update) em_update = c->d_em_update;
-        if (!em_target && rtf) em_target = c->d_em_target;
-        if ((rc = launch_estmask(c, n_streams, n_frames, n_sources, em_update, em_target, st))) return rc;
-        update = em_update; tmask = em_target;
+        if (!q.em_update) q.em_update = c->d_em_update;
+        if (!q.em_target && q.rtf) q.em_target = c->d_em_target;
+        if ((rc = launch_estmask(c, q, st))) return rc;
+        q.update = q.em_update; q.tmask = q.em_target;
     }
-    if (rtf) {
+    if (q.rtf) {
         for (int f0 = 0; f0 < n_frames; f0 += fc) {
             const int n = std::min(fc, n_frames - f0);
-            if ((rc = launch_rtf(c, n_streams, n_frames, n_sources, update, tmask, st, f0, n))) return rc;
-            if ((rc = launch_solve(c, n_streams, n_frames, n_sources, update, masked, true, Y, st, f0, n))) return rc;
+            if ((rc = launch_rtf(c, q, st, f0, n))) return rc;
+            if ((rc = launch_solve(c, q, Y, st, f0, n))) return rc;
         }
-    } else if ((rc = launch_solve(c, n_streams, n_frames, n_sources, update, masked, false, Y, st))) return rc;
-    if (c->pf_on && (rc = launch_postfilter(c, n_streams, n_frames, n_sources, Y, st))) return rc;
-    if (out_pcm && (rc = launch_synth(c, n_streams, n_frames, n_sources, Y, out_pcm, st))) return rc;
+    } else if ((rc = launch_solve(c, q, Y, st))) return rc;
+    if (c->pf_on && (rc = launch_postfilter(c, q, Y, st))) return rc;
+    if (q.out_pcm && (rc = launch_synth(c, q, Y, st))) return rc;
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
-// the host-pointer form: n_upd floats of weights per (stream, frame), 1 or K
-int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
-                     const float *update, bool masked, float *out_pcm, float *out_spec, const float *tmask = nullptr, bool rtf = false,
-                     bool est = false, float *em_update = nullptr, float *em_target = nullptr)
+// the host-pointer form: pcm packed [streams][M][(F + 1) hop]; 1 or K (masked) floats of update weights per (stream, frame)
+int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, const MvdrCall &q)
 {
-    if (!c || !pcm || !doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c || !pcm || !q.doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long ms = (long long)(n_frames + 1) * c->H, ss = ms * c->M;
     const size_t nf = (size_t)n_streams * n_frames * n_sources;
-    float *d_pcm = (float *)c->stage.get(0, (size_t)ss * n_streams * 4), *d_doa = (float *)c->stage.get(1, nf * 4);
-    float *d_out = out_pcm ? (float *)c->stage.get(2, nf * c->H * 4) : nullptr;
-    float *d_spec = out_spec ? (float *)c->stage.get(3, nf * c->K * 8) : nullptr;
-    const size_t nu = (size_t)n_streams * n_frames * (masked ? (size_t)c->K : 1);
-    float *d_upd = update ? (float *)c->stage.get(masked ? 8 : 7, nu * 4) : nullptr;  // (slots 4 ... 6: the spectrum's; 8: the mask's own)
-    float *d_tm = tmask ? (float *)c->stage.get(9, nf * c->K * 4) : nullptr;        // [streams][n_sources][F][K]
+    const size_t nu = (size_t)n_streams * n_frames * (q.masked ? (size_t)c->K : 1);
+    auto stage = [&](int slot, const void *host, size_t bytes) { return host ? (float *)c->stage.get(slot, bytes) : nullptr; };
+    MvdrCall d = q;                                             // the same call on the staged copies
+    float *d_pcm = stage(0, pcm, (size_t)ss * n_streams * 4), *d_doa = stage(1, q.doa, nf * 4);
+    d.doa = d_doa;
+    d.out_pcm = stage(2, q.out_pcm, nf * c->H * 4);
+    d.out_spec = stage(3, q.out_spec, nf * c->K * 8);
+    float *d_upd = stage(q.masked ? 8 : 7, q.update, nu * 4);   // (slots 4 ... 6: the spectrum's; 8: the mask's own)
+    float *d_tm = stage(9, q.tmask, nf * c->K * 4);             // [streams][n_sources][F][K]
+    d.update = d_upd; d.tmask = d_tm;
     // the masks an auto call hands back are staged where the other calls stage the masks they take
-    float *d_eu = em_update ? (float *)c->stage.get(8, nu * 4) : nullptr, *d_et = em_target ? (float *)c->stage.get(9, nf * c->K * 4) : nullptr;
-    if (!d_pcm || !d_doa || (out_pcm && !d_out) || (out_spec && !d_spec) || (update && !d_upd) || (tmask && !d_tm) || (em_update && !d_eu) || (em_target && !d_et))
+    d.em_update = stage(8, q.em_update, nu * 4); d.em_target = stage(9, q.em_target, nf * c->K * 4);
+    if (!d_pcm || !d_doa || (q.out_pcm && !d.out_pcm) || (q.out_spec && !d.out_spec) || (q.update && !d_upd) || (q.tmask && !d_tm) ||
+        (q.em_update && !d.em_update) || (q.em_target && !d.em_target))
         return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    if (tmask) VHIP_TRY(c, hipMemcpy(d_tm, tmask, nf * c->K * 4, hipMemcpyHostToDevice));
+    if (q.tmask) VHIP_TRY(c, hipMemcpy(d_tm, q.tmask, nf * c->K * 4, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
-    VHIP_TRY(c, hipMemcpy(d_doa, doa_rad, nf * 4, hipMemcpyHostToDevice));
-    if (update) VHIP_TRY(c, hipMemcpy(d_upd, update, nu * 4, hipMemcpyHostToDevice));
-    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, n_streams, n_frames, n_sources, d_doa, d_upd, masked, d_out, d_spec, nullptr, d_tm, rtf, est, d_eu, d_et);
+    VHIP_TRY(c, hipMemcpy(d_doa, q.doa, nf * 4, hipMemcpyHostToDevice));
+    if (q.update) VHIP_TRY(c, hipMemcpy(d_upd, q.update, nu * 4, hipMemcpyHostToDevice));
+    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, d, nullptr);
     if (rc) return rc;
     VHIP_TRY(c, hipDeviceSynchronize());
-    if (em_update) VHIP_TRY(c, hipMemcpy(em_update, d_eu, nu * 4, hipMemcpyDeviceToHost));
-    if (em_target) VHIP_TRY(c, hipMemcpy(em_target, d_et, nf * c->K * 4, hipMemcpyDeviceToHost));
-    if (out_pcm) VHIP_TRY(c, hipMemcpy(out_pcm, d_out, nf * c->H * 4, hipMemcpyDeviceToHost));
-    if (out_spec) VHIP_TRY(c, hipMemcpy(out_spec, d_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
+    if (q.em_update) VHIP_TRY(c, hipMemcpy(q.em_update, d.em_update, nu * 4, hipMemcpyDeviceToHost));
+    if (q.em_target) VHIP_TRY(c, hipMemcpy(q.em_target, d.em_target, nf * c->K * 4, hipMemcpyDeviceToHost));
+    if (q.out_pcm) VHIP_TRY(c, hipMemcpy(q.out_pcm, d.out_pcm, nf * c->H * 4, hipMemcpyDeviceToHost));
+    if (q.out_spec) VHIP_TRY(c, hipMemcpy(q.out_spec, d.out_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
 }
 
@@ -930,7 +888,10 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
                                              int n_frames, int n_sources, const float *doa_rad, const float *update, float *out_pcm,
                                              float *out_spec, void *stream)
 {
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update, false, out_pcm, out_spec, stream);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.update = update; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
 }
 
 // update_mask [streams][F][K] or NULL (all 1)
@@ -938,7 +899,10 @@ int mca_hip_mvdr_sources_frames_masked_dev(mca_hip_mvdr_ctx *c, const float *pcm
                                            int n_frames, int n_sources, const float *doa_rad, const float *update_mask, float *out_pcm,
                                            float *out_spec, void *stream)
 {
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, stream);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.update = update_mask; q.masked = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
 }
 
 // update_mask [streams][F][K] or NULL (all 1), target_mask [streams][n_sources][F][K] or NULL (all 0)
@@ -946,14 +910,20 @@ int mca_hip_mvdr_sources_frames_rtf_dev(mca_hip_mvdr_ctx *c, const float *pcm, l
                                         int n_frames, int n_sources, const float *doa_rad, const float *update_mask, const float *target_mask,
                                         float *out_pcm, float *out_spec, void *stream)
 {
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, stream, target_mask, true);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.update = update_mask; q.masked = true; q.tmask = target_mask; q.rtf = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
 }
 
 int mca_hip_mvdr_sources_frames_rtf_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                          const float *update_mask, const float *target_mask, float *out_pcm, float *out_spec)
 {
     if (c && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
-    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec, target_mask, true);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.update = update_mask; q.masked = true; q.tmask = target_mask; q.rtf = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_host(c, pcm, q);
 }
 
 // update_mask_out [streams][F][K] and target_mask_out [streams][n_sources][F][K]: either may be NULL
@@ -964,8 +934,11 @@ int mca_hip_mvdr_sources_frames_auto_dev(mca_hip_mvdr_ctx *c, const float *pcm, 
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(update_mask_out) | reinterpret_cast<uintptr_t>(target_mask_out)) & 3)
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "update_mask_out_dev / target_mask_out_dev must be 4-byte aligned");
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, n_streams, n_frames, n_sources, doa_rad, nullptr, true, out_pcm, out_spec, stream, nullptr,
-                           c->rtf_on, true, update_mask_out, target_mask_out);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.masked = true; q.rtf = c->rtf_on; q.est = true; q.em_update = update_mask_out; q.em_target = target_mask_out;
+    q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
 }
 
 int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
@@ -973,8 +946,11 @@ int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *c, const float *pcm,
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (!c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
-    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, nullptr, true, out_pcm, out_spec, nullptr, c->rtf_on, true, update_mask_out,
-                            target_mask_out);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.masked = true; q.rtf = c->rtf_on; q.est = true; q.em_update = update_mask_out; q.em_target = target_mask_out;
+    q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_host(c, pcm, q);
 }
 
 int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
@@ -992,13 +968,19 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
 int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                               const float *update, float *out_pcm, float *out_spec)
 {
-    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update, false, out_pcm, out_spec);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.update = update; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_host(c, pcm, q);
 }
 
 int mca_hip_mvdr_sources_frames_masked_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                             const float *update_mask, float *out_pcm, float *out_spec)
 {
-    return mvdr_frames_host(c, pcm, n_streams, n_frames, n_sources, doa_rad, update_mask, true, out_pcm, out_spec);
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
+    q.update = update_mask; q.masked = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return mvdr_frames_host(c, pcm, q);
 }
 
 int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
@@ -1047,20 +1029,14 @@ int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spec
             }
         }
     }
-    float *ng = nullptr; float2 *nT = nullptr;
-    hipError_t e = hipMalloc((void **)&ng, (size_t)D * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&nT, T.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(ng, grid.data(), (size_t)D * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(nT, T.data(), T.size() * sizeof(float2), hipMemcpyHostToDevice);
+    // the former tables and spec_set stay when the new ones fail; else they go, behind the wait, with ng and nT
+    DevBuf<float> ng;
+    DevBuf<float2> nT;
+    hipError_t e = ng.upload(grid.data(), grid.size());
+    if (e == hipSuccess) e = nT.upload(T.data(), T.size());
     if (e == hipSuccess) e = hipDeviceSynchronize();            // no spectrum call in flight reads the former tables
-    if (e != hipSuccess) {
-        if (ng) (void)hipFree(ng);
-        if (nT) (void)hipFree(nT);
-        return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("steering tables of the spectrum: ") + hipGetErrorString(e));
-    }
-    if (c->d_spec_grid) (void)hipFree(c->d_spec_grid);
-    if (c->d_spec_T) (void)hipFree(c->d_spec_T);
-    c->d_spec_grid = ng; c->d_spec_T = nT; c->spec_grid.swap(grid); c->spec_dpad = Dpad; c->spec = *cfg; c->spec_set = true;
+    if (e != hipSuccess) return hip_fail(c, e, "steering tables of the spectrum");
+    c->d_spec_grid.swap(ng); c->d_spec_T.swap(nT); c->spec_grid.swap(grid); c->spec_dpad = Dpad; c->spec = *cfg; c->spec_set = true;
     return MCA_HIP_OK;
 }
 
@@ -1085,13 +1061,8 @@ int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *
     sa.power = c->spec.weighting == MCA_HIP_MVDR_SPECTRUM_POWER;
     sa.loading = (float)c->cfg.loading;
     const size_t need = (size_t)n_streams * sa.n_chunks * 4 * sa.Dpad;
-    if (need > c->spec_part_cap) {
-        VHIP_TRY(c, hipDeviceSynchronize());
-        if (c->d_spec_part) (void)hipFree(c->d_spec_part);
-        c->d_spec_part = nullptr; c->spec_part_cap = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_spec_part, need * 4));
-        c->spec_part_cap = need;
-    }
+    if (need > c->d_spec_part.n) VHIP_TRY(c, hipDeviceSynchronize());
+    if (const int rc = grow_ws(c, c->d_spec_part, need, "partial sums of the spectrum")) return rc;
     sa.part = c->d_spec_part;
     MvdrSpectrumPickArgs pa{};
     pa.part = c->d_spec_part; pa.grid = c->d_spec_grid; pa.n_slices = sa.n_chunks * 4; pa.D = sa.D; pa.Dpad = sa.Dpad; pa.n_peaks = c->spec.n_peaks;
@@ -1192,23 +1163,19 @@ int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
     if (!c->d_trk_theta) {
-        float *nth = nullptr, *npk = nullptr; int *ni = nullptr; float2 *nt0 = nullptr;
-        hipError_t e = hipMalloc((void **)&nth, n * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&ni, n * 3 * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&npk, n * 2 * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&nt0, n * c->M * (c->N / 64 + 33) * sizeof(float2));
-        if (e != hipSuccess) {
-            if (nth) (void)hipFree(nth);
-            if (ni) (void)hipFree(ni);
-            if (npk) (void)hipFree(npk);
-            if (nt0) (void)hipFree(nt0);
-            return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string("track state: ") + hipGetErrorString(e));
-        }
-        c->d_trk_theta = nth; c->d_trk_int = ni; c->d_trk_peak = npk; c->d_trk_T0 = nt0;
+        DevBuf<float> nth, npk;
+        DevBuf<int> ni;
+        DevBuf<float2> nt0;
+        hipError_t e = nth.alloc(n);
+        if (e == hipSuccess) e = ni.alloc(n * 3);
+        if (e == hipSuccess) e = npk.alloc(n * 2);
+        if (e == hipSuccess) e = nt0.alloc(n * c->M * (c->N / 64 + 33));
+        if (e != hipSuccess) return hip_fail(c, e, "track state");
+        c->d_trk_theta.swap(nth); c->d_trk_int.swap(ni); c->d_trk_peak.swap(npk); c->d_trk_T0.swap(nt0);
     }
     VHIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
-    VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, n * 4));
-    VHIP_TRY(c, hipMemset(c->d_trk_int, 0, n * 3 * 4));
+    VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
+    VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
     c->trk = *cfg; c->trk_on = cfg->enable == 1;
     c->trk_ever = true;
     return MCA_HIP_OK;
@@ -1263,13 +1230,8 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
     const int n_own = c->trk.n_own, K = c->K, M = c->M, Dpad = c->spec_dpad, nhi = c->N / 64 + 1;
     const int chunk0 = c->spec.bin_lo / MVDR_SPEC_CHUNK, n_chunks = c->spec.bin_hi / MVDR_SPEC_CHUNK - chunk0 + 1;
     const size_t need = (size_t)n_streams * n_own * n_chunks * 4 * Dpad;
-    if (need > c->trk_part_cap) {
-        VHIP_TRY(c, hipDeviceSynchronize());
-        if (c->d_trk_part) (void)hipFree(c->d_trk_part);
-        c->d_trk_part = nullptr; c->trk_part_cap = 0;
-        VHIP_TRY(c, hipMalloc((void **)&c->d_trk_part, need * 4));
-        c->trk_part_cap = need;
-    }
+    if (need > c->d_trk_part.n) VHIP_TRY(c, hipDeviceSynchronize());
+    if (const int rc = grow_ws(c, c->d_trk_part, need, "partial sums of the own tracks")) return rc;
     // the Capon peaks: the kernels of mca_hip_mvdr_spectrum_dev, into the context's own rows.  Not launched where every slot is an own
     // track: a peak then changes no track (it is within min_sep of an own track and skipped, or waits as a birth no slot takes)
     float *pk_doa = c->d_trk_peak, *pk_val = c->d_trk_peak + (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
@@ -1397,15 +1359,14 @@ int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *c, int n_streams, float *theta, in
     return MCA_HIP_OK;
 }
 
-int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
+extern "C++" {
+namespace {
+// the covariance [K][tri] of one stream or slot (the lower triangle, row by row) read back as the Hermitian [K][M][M] in double
+int read_hermitian(mca_hip_mvdr_ctx *c, const float2 *tri_dev, double *out)
 {
-    if (!c || !out) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
-    std::vector<float2> h((size_t)c->K * c->tri);
-    VHIP_TRY(c, hipMemcpy(h.data(), c->d_phi + (size_t)s * c->K * c->tri, h.size() * sizeof(float2), hipMemcpyDeviceToHost));
     const int M = c->M;
+    std::vector<float2> h((size_t)c->K * c->tri);
+    VHIP_TRY(c, hipMemcpy(h.data(), tri_dev, h.size() * sizeof(float2), hipMemcpyDeviceToHost));
     for (int k = 0; k < c->K; ++k)
         for (int i = 0; i < M; ++i)
             for (int j = 0; j <= i; ++j) {
@@ -1415,6 +1376,17 @@ int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
                 up[0] = v.x; up[1] = i == j ? 0.0 : -(double)v.y;
             }
     return MCA_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
+{
+    if (!c || !out) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());
+    return read_hermitian(c, c->d_phi + (size_t)s * c->K * c->tri, out);
 }
 
 int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *c, int s, int source, double *out, double *norm)
@@ -1427,19 +1399,8 @@ int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *c, int s, int source, d
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     VHIP_TRY(c, hipDeviceSynchronize());
     const size_t slot = (size_t)s * c->max_sources + source;
-    const int M = c->M;
-    if (out) {
-        std::vector<float2> h((size_t)c->K * c->tri);
-        VHIP_TRY(c, hipMemcpy(h.data(), c->d_psi + slot * c->K * c->tri, h.size() * sizeof(float2), hipMemcpyDeviceToHost));
-        for (int k = 0; k < c->K; ++k)
-            for (int i = 0; i < M; ++i)
-                for (int j = 0; j <= i; ++j) {
-                    const float2 v = h[(size_t)k * c->tri + i * (i + 1) / 2 + j];
-                    double *lo = out + (((size_t)k * M + i) * M + j) * 2, *up = out + (((size_t)k * M + j) * M + i) * 2;
-                    lo[0] = v.x; lo[1] = i == j ? 0.0 : v.y;
-                    up[0] = v.x; up[1] = i == j ? 0.0 : -(double)v.y;
-                }
-    }
+    if (out)
+        if (const int rc = read_hermitian(c, c->d_psi + slot * c->K * c->tri, out)) return rc;
     if (norm) {
         std::vector<float> h((size_t)c->K);
         VHIP_TRY(c, hipMemcpy(h.data(), c->d_cpsi + slot * c->K, h.size() * 4, hipMemcpyDeviceToHost));
@@ -1468,13 +1429,13 @@ int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa
             T[(size_t)m * nph + e] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
         }
     const size_t tb = T.size() * sizeof(float2), ob = (size_t)K * M * sizeof(float2);
-    char *buf = nullptr;                                        // T, the vectors, the flags
-    VHIP_TRY(c, hipMalloc((void **)&buf, tb + ob + (size_t)K));
+    DevBuf<char> buf;                                           // T, the vectors, the flags
+    if (const hipError_t e = buf.alloc(tb + ob + (size_t)K)) return hip_fail(c, e, "steering vectors");
     MvdrRtfSteerArgs ga{};
     const size_t slot = (size_t)s * c->max_sources + source;
     ga.phi = c->d_phi + (size_t)s * K * c->tri; ga.psi = c->d_psi + slot * K * c->tri;
     ga.cpsi = c->d_cpsi + slot * K; ga.cphi = c->d_cphi + (size_t)s * K;
-    ga.T = reinterpret_cast<float2 *>(buf); ga.K = K; ga.M = M;
+    ga.T = reinterpret_cast<float2 *>(buf.p); ga.K = K; ga.M = M;
     ga.min_share = (float)c->rtf_min_share; ga.iterations = c->rtf_iterations; ga.ref_mic = c->rtf_ref;
     ga.out = reinterpret_cast<float2 *>(buf + tb); ga.estimated = reinterpret_cast<unsigned char *>(buf + tb + ob);
     std::vector<float2> h((size_t)K * M);
@@ -1485,7 +1446,6 @@ int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa
     if (e == hipSuccess) e = hipLaunchKernel(mvdr_rtf_kernel(Q, true), dim3((unsigned)((K + 63) / 64)), dim3(256), kargs, 0, nullptr);
     if (e == hipSuccess) e = hipMemcpy(h.data(), buf + tb, ob, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(he.data(), buf + tb + ob, (size_t)K, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) return vfail(c, MCA_HIP_ERR_HIP, std::string("steering vectors: ") + hipGetErrorString(e));
     if (out)
         for (size_t i = 0; i < h.size(); ++i) { out[2 * i] = h[i].x; out[2 * i + 1] = h[i].y; }
@@ -1498,13 +1458,13 @@ namespace {
 constexpr unsigned MVDR_MAGIC = 0x4d435644u;   // "MCVD"
 std::vector<BlobPart> mvdr_parts(mca_hip_mvdr_ctx *c)
 {
-    const size_t ns = (size_t)c->cfg.max_streams;
-    std::vector<BlobPart> parts{{c->d_phi, ns * c->K * c->tri * sizeof(float2)}, {c->d_trace, ns * c->K * 4}, {c->d_tail[c->tail_cur], ns * c->max_sources * c->H * 4}};
-    if (c->pf_on) parts.push_back({c->d_pf_A, ns * c->max_sources * c->K * 4});
+    DevBuf<float> &tail = c->d_tail[c->tail_cur];
+    std::vector<BlobPart> parts{{c->d_phi.p, c->d_phi.bytes()}, {c->d_trace.p, c->d_trace.bytes()}, {tail.p, tail.bytes()}};
+    if (c->pf_on) parts.push_back({c->d_pf_A.p, c->d_pf_A.bytes()});
     if (c->rtf_on) {
-        parts.push_back({c->d_psi, ns * c->max_sources * c->K * c->tri * sizeof(float2)});
-        parts.push_back({c->d_cpsi, ns * c->max_sources * c->K * 4});
-        parts.push_back({c->d_cphi, ns * c->K * 4});
+        parts.push_back({c->d_psi.p, c->d_psi.bytes()});
+        parts.push_back({c->d_cpsi.p, c->d_cpsi.bytes()});
+        parts.push_back({c->d_cphi.p, c->d_cphi.bytes()});
     }
     return parts;
 }
@@ -1560,8 +1520,8 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long byt
     const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->rtf_on ? 4 : c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1);
     if (!rc && c->d_trk_theta) {
         // the tracks are no part of a blob: a loaded context starts without them and is seeded again
-        VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, (size_t)c->cfg.max_streams * MCA_MAX_SOURCES * 4));
-        VHIP_TRY(c, hipMemset(c->d_trk_int, 0, (size_t)c->cfg.max_streams * MCA_MAX_SOURCES * 3 * 4));
+        VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
+        VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
     }
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }

@@ -2,30 +2,24 @@
 // caller hands over one small chunk after another, and a hipMalloc/hipFree pair per buffer and call costs
 // more than the kernels of a small chunk.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "devbuf.h"
 
 namespace mca {
 
 struct StagePool {
     static constexpr int N = 10;          // (slots 8, 9: the update mask and the target masks of the MVDR host calls)
-    void *p[N] = {};
-    size_t cap[N] = {};
+    DevBuf<unsigned char> buf[N];
     // returns a device buffer of at least `bytes` bytes for slot i (nullptr on allocation failure or bytes == 0)
     void *get(int i, size_t bytes)
     {
         if (bytes == 0) return nullptr;
-        if (bytes > cap[i]) {
-            if (p[i]) (void)hipFree(p[i]);
-            p[i] = nullptr; cap[i] = 0;
-            const size_t want = bytes + bytes / 4;          // head room: chunk sizes of a stream vary a little
-            if (hipMalloc(&p[i], want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            cap[i] = want;
-        }
-        return p[i];
+        // head room: chunk sizes of a stream vary a little
+        if (bytes > buf[i].n && buf[i].grow(bytes + bytes / 4) != hipSuccess) return nullptr;
+        return buf[i].p;
     }
     void release()
     {
-        for (int i = 0; i < N; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr; cap[i] = 0; }
+        for (auto &b : buf) b.reset();
     }
 };
 

@@ -4,14 +4,14 @@ usage: python tools/compare_mvdr_builds.py PARENT_LIB
 The same inputs go through PARENT_LIB and through mcarray_amd/libmcarray_hip.so, each in a fresh child process (MCA_HIP_LIB names
 the library, as for the bench tools) under a time limit of its own; the second child is not started when the first one fails.  A
 child binds only the entry points its library has, runs the cases below through the host-pointer calls and leaves one SHA-256 per
-case over the spectra, the audio and the covariance read back.  The parent process requires equal digests of every case the older build ran
+case over the spectra, the audio and the covariance read back (the host-layer cases: what they name).  The parent process requires equal digests of every case the older build ran
 (exit code 1 otherwise) and never opens the GPU itself.
 
 Cases (N = 64, fs = 16 kHz, 3 streams, two calls of 5 + 4 frames; stream 2 starts with digital silence): 3, 4, 6, 8, 11, 12, 15
 and 16 microphones (both forms of every number of row slots) x 1 ... 4 look directions x null_gain 0 and 7.5 (two directions and
 more) x no update weights, a weight per frame (zeros, fractions and ones) and a weight per frame and bin x post-filter off and on.
 Then one call whose solve takes the pieced tail launch: 1000 streams x 8 frames, 16 microphones, 2 directions (516 workgroups: a
-remainder of 4, in 2 pieces)."""
+remainder of 4, in 2 pieces).  Then the paths of the host layer (host_layer_cases below)."""
 import hashlib
 import json
 import os
@@ -87,8 +87,102 @@ def child(out_path):
         doa = rng.uniform(-1.3, 1.3, (A, F, S)).astype(np.float32)
         bf = api.MvdrBeamformer(FS, [0.3 / M * m for m in range(M)], N, max_streams=A, max_sources=S)
         run("pieced tail launch: 1000 streams x 8 frames, M=16 S=2", bf, [(pcm, doa, {})], (0, 991, 992, 999))
+    host_layer_cases(api, np, has, res)
     with open(out_path, "w") as f:
         json.dump(res, f)
+
+
+def host_layer_cases(api, np, has, res):
+    """the paths of the host layer beside the plain calls (the shapes above; 6 microphones, 2 look directions of 3 slots): the RTF
+    call and its cut along the frames, the auto call, a change of max_sources under post-filter and RTF down to the state blob,
+    the post-filter toggled between calls, the spectrum and a round of the tracks"""
+    if not (has("mca_hip_mvdr_sources_frames_rtf_host") and has("mca_hip_mvdr_set_postfilter")):
+        return
+    A, F1, F, M, S = 3, 5, 9, 6, 2
+    rng = np.random.default_rng(4242)
+    xs = [0.3 / M * m for m in range(M)]
+    pcm = rng.standard_normal((A, M, (F + 1) * HOP)).astype(np.float32)
+    pcm[2, :, :3 * HOP] = 0.0
+    doa = rng.uniform(-1.3, 1.3, (A, F, S)).astype(np.float32)
+    um = rng.choice(np.array([0.0, 0.0, 1.0, 1.0, 0.3, 0.8], dtype=np.float32), size=(A, F, K))
+    tm = rng.choice(np.array([0.0, 1.0, 1.0, 0.6], dtype=np.float32), size=(A, S, F, K))
+
+    def new(max_sources=S, gain=0.0, pf=False, rtf=True):
+        bf = api.MvdrBeamformer(FS, xs, N, max_streams=A, max_sources=max_sources, null_gain=gain, rtf_nulls=gain != 0.0)
+        if pf:
+            bf.set_postfilter(True)
+        if rtf:
+            bf.set_rtf(True)
+        return bf
+
+    def call(bf, t0, t1, parts, masks=True, **kw):
+        if masks:
+            kw.update(update_mask=um[:, t0:t1], target_mask=tm[:, :, t0:t1])
+        r = bf.process_sources(pcm[:, :, t0 * HOP:(t1 + 1) * HOP], doa[:, t0:t1], **kw)
+        parts += [r[key] for key in ("spec", "out", "update_mask", "target_mask") if key in r]
+
+    def state(bf, parts, slots=S, rtf=True):
+        for a in range(A):
+            parts.append(bf.covariance(a))
+            if rtf:
+                for s in range(slots):
+                    parts += list(bf.target_covariance(a, s))
+
+    for name, cap in (("RTF call, update and target masks", None), ("RTF call cut into chunks of 2 frames", 2 * A * S * K * M * 8)):
+        bf, parts = new(), []
+        if cap:
+            bf.set_rtf_workspace(cap)                          # 5 frames: 2 + 2 + 1, 4 frames: 2 + 2
+        call(bf, 0, F1, parts)
+        call(bf, F1, F, parts)
+        state(bf, parts)
+        bf.close()
+        res[name] = digest(*parts)
+
+    if has("mca_hip_mvdr_sources_frames_auto_host"):
+        bf, parts = new(), []
+        bf.set_mask_estimator(True)
+        call(bf, 0, F1, parts, masks=False, estimate_masks=True)
+        call(bf, F1, F, parts, masks=False, estimate_masks=True)
+        state(bf, parts)
+        bf.close()
+        res["auto call, both masks handed back"] = digest(*parts)
+
+    bf, parts = new(max_sources=2, gain=7.5, pf=True), []
+    bf.set_max_sources(3)
+    call(bf, 0, F1, parts)
+    bf.set_max_sources(2)
+    call(bf, F1, F, parts)
+    state(bf, parts)
+    parts.append(np.frombuffer(bf.state_save(), dtype=np.uint8))
+    bf.close()
+    res["set_max_sources 3, call, 2, call, state blob; post-filter, RTF, nulls"] = digest(*parts)
+
+    bf, parts = new(rtf=False), []
+    call(bf, 0, F1, parts, masks=False)
+    bf.set_postfilter(True)
+    call(bf, F1, F1 + 2, parts, masks=False)
+    bf.set_postfilter(False)
+    call(bf, F1 + 2, F, parts, masks=False)
+    state(bf, parts, rtf=False)
+    parts.append(np.frombuffer(bf.state_save(), dtype=np.uint8))
+    bf.close()
+    res["post-filter off, on, off between calls"] = digest(*parts)
+
+    if has("mca_hip_mvdr_spectrum_host") and has("mca_hip_mvdr_tracks_configure"):
+        bf, parts = new(), []
+        call(bf, 0, F1, parts)
+        bf.configure_spectrum(19, n_peaks=2)
+        sp = bf.spectrum()
+        parts += [sp["spectrum"], sp["peak_doa"], sp["peak_val"]]
+        bf.configure_tracks(2, n_own=1)
+        bf.seed_tracks(np.array([[0.4, -0.7], [-0.2, 0.9], [1.1, 0.1]], dtype=np.float32))
+        for t0, t1 in ((F1, F1 + 2), (F1 + 2, F)):
+            call(bf, t0, t1, parts)
+            up = bf.update_tracks(want_spectrum=True)
+            tr = bf.tracks()
+            parts += [up["own_spectrum"], up["own_used"]] + [tr[key] for key in ("theta", "alive", "miss", "gen")]
+        bf.close()
+        res["spectrum, then tracks configured, seeded, updated and read"] = digest(*parts)
 
 
 def main():
