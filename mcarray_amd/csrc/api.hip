@@ -5,6 +5,7 @@
 // and there is no CPU fallback: without a gfx950 device mca_hip_create fails.
 #include "../../include/mcarray_hip.h"
 #include "fft1024c.h"
+#include "fold_table.h"
 #include "kernels.h"
 #include "knobs.h"
 #include "stage.h"
@@ -122,6 +123,9 @@ struct mca_hip_ctx {
     // microphones (build_merged_tables)
     bool merged = false; int n_merged = 0, Kp_m = 0;
     void *d_Bm = nullptr, *d_Btm = nullptr; unsigned short *d_mrank = nullptr;
+    // ... folded about broadside (fold_table.h): the merged rows are planar ([R | I]), d_Bm / d_Btm hold the folded values at full width in
+    // planar K order, and d_Bfold the even and the odd half-width tables of k_srp_gemm_f16_fold: [2][Kp_m / 64][192][32]
+    bool fold = false; void *d_Bfold = nullptr;
     float2 *d_bftab = nullptr; int bf_pairs = 0;   // k_beamform_wave: steering rows per grid angle, [D + 1][bf_pairs][1024] (built on first use)
     // Delay-and-sum on the half spectrum (steer.h; steer_applies): the per-channel steering table, the predicted bin per array (the last pick of
     // the previous call; -1 on a new stream), the running miss total, the rows of Y (grown on demand) and two carries between frame passes
@@ -259,7 +263,7 @@ void free_ctx(mca_hip_ctx *c)
 {
     if (!c) return;
     auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_mlist); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_mrank);
+    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_mlist); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_Bfold); F(c->d_mrank);
     F(c->d_E[0]); F(c->d_E[1]); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_doa[0]); F(c->d_doa[1]); F(c->d_vdone[0]); F(c->d_vdone[1]); F(c->d_g2_vidx); F(c->d_g2_nv); F(c->d_g2_rad); F(c->d_g2_prob);
     F(c->d_g2_reset); F(c->d_g2_post0); F(c->d_silence);
     F(c->d_trk_x); F(c->d_trk_sd); F(c->d_trk_si); F(c->d_trk_sil); F(c->d_trk_corr); F(c->d_trk_idx); F(c->d_trk_res);
@@ -388,15 +392,26 @@ int build_merged_tables(mca_hip_ctx *c)
     for (int g = 1; g < G; ++g)
         for (int d = 0; d < D; ++d)
             if (std::fabs((double)c->delays[(size_t)g * D + d] - (g + 1) * (double)c->delays[d]) > 1e-4) return MCA_HIP_OK;   // (pair (0, g + 1) has index g)
-    std::vector<unsigned short> rank((size_t)G * (K - 1) + 1, 0xffff);
+    std::vector<unsigned short> rank;
     std::vector<int> ms;
-    for (int g = 1; g <= G; ++g)
-        for (int k = 0; k < K; ++k) rank[(size_t)k * g] = 0;
-    for (size_t m = 0; m < rank.size(); ++m)
-        if (rank[m] == 0) { rank[m] = (unsigned short)ms.size(); ms.push_back((int)m); }
+    merged_products(G, K, rank, ms);
     c->n_merged = (int)ms.size();
     c->Kp_m = round_up(2 * ((c->n_merged + 63) & ~63), 32);       // (whole wave rows: the analysis kernel stores its LDS region as it stands, zeros behind n_merged)
     const int Kp = c->Kp_m;
+    c->fold = fold_applies(true, c->N, FFT_N, D, Dp, c->delays.data());
+    if (c->fold) {
+        // mirror fold (fold_table.h): planar rows, the folded values at full width for the kernels that keep it, the two half-width tables
+        FoldTables ft;
+        build_fold_tables(c->delays.data(), D, Dp, ms.data(), c->n_merged, Kp, c->N, ft);
+        auto up16 = [&](void **dst, const std::vector<uint16_t> &v, size_t at, size_t total) {
+            if (!*dst) HIP_TRY(c, hipMalloc(dst, total * 2));
+            HIP_TRY(c, hipMemcpy((char *)*dst + at * 2, v.data(), v.size() * 2, hipMemcpyHostToDevice));
+            return (int)MCA_HIP_OK;
+        };
+        int rc;
+        if ((rc = up16(&c->d_Bm, ft.full, 0, ft.full.size())) || (rc = up16(&c->d_Btm, ft.full_tiled, 0, ft.full_tiled.size())) ||
+            (rc = up16(&c->d_Bfold, ft.even, 0, 2 * ft.even.size())) || (rc = up16(&c->d_Bfold, ft.odd, ft.even.size(), 2 * ft.even.size()))) return rc;
+    } else {
     std::vector<_Float16> B((size_t)Dp * Kp, (_Float16)0.f);
     for (int d = 0; d < D; ++d)
         for (int r = 0; r < c->n_merged; ++r) {
@@ -414,6 +429,7 @@ int build_merged_tables(mca_hip_ctx *c)
                 std::memcpy(&Bt[((size_t)sl * Dp + d) * 32], &B[(size_t)d * Kp + (size_t)sl * 32], 32 * sizeof(_Float16));
         HIP_TRY(c, hipMalloc(&c->d_Btm, Bt.size() * sizeof(_Float16)));
         HIP_TRY(c, hipMemcpy(c->d_Btm, Bt.data(), Bt.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
     }
     rank.resize((rank.size() + 3) / 4 * 4, 0xffff);
     HIP_TRY(c, hipMalloc((void **)&c->d_mrank, rank.size() * sizeof(unsigned short)));
@@ -451,7 +467,7 @@ int gen_threads(const mca_hip_ctx *c, bool synthesis)
 }
 
 // which contraction kernel a chunk of `rows` frames runs on, and over how many workgroups its K range is split
-struct GemmPlan { bool v2; int ksplit; };
+struct GemmPlan { bool v2; int ksplit; bool fold; };      // fold: k_srp_gemm_f16_fold (256-row tiles, two K segments, one plane, a folding context)
 GemmPlan plan_gemm(const mca_hip_ctx *c, long long rows)
 {
     GemmPlan g;
@@ -482,6 +498,7 @@ GemmPlan plan_gemm(const mca_hip_ctx *c, long long rows)
         if (ks < 1) ks = 1;
         g.ksplit = (int)ks;
     }
+    g.fold = g.v2 && g.ksplit == 2 && c->a_planes == 1 && c->merged && c->fold;
     return g;
 }
 
@@ -1445,7 +1462,7 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         while (sa.fpb > 1 && (long long)n_arrays * ((nf + sa.fpb - 1) / sa.fpb) < 256) sa.fpb >>= 1;
         sa.power = c->cfg.use_power_floor ? c->ws().d_power : nullptr; sa.total_frames = n_frames;
         sa.window = c->d_window; sa.A = a_buf(c); sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = c->a_planes;
-        if (c->merged && c->a_planes == 1) { sa.mrank = c->d_mrank; sa.n_merged = c->n_merged; }
+        if (c->merged && c->a_planes == 1) { sa.mrank = c->d_mrank; sa.n_merged = c->n_merged; sa.planar = c->fold ? 1 : 0; }
         sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
         sa.no_phat = c->cfg.gcc_weighting == MCA_HIP_GCC_NONE ? 1 : 0;
         if (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 1 && wave16_applies(c)) sa.unsure = c->ws().d_unsure;   // (adaptive coarse pass)
@@ -1500,6 +1517,7 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         ga.rows = n_arrays * nf; ga.chunk_frames = nf; ga.total_frames = n_frames; ga.frame0 = f0;
         ga.Kp = cur_kp(c); ga.Dp = c->Dp; ga.a_row_elems = c->a_row_elems;
         ga.c_plane_elems = (long long)n_arrays * n_frames * c->Dp;
+        ga.Bf = mg ? c->d_Bfold : nullptr; ga.D = c->D;
         if (fused_partial) {
             ga.part = c->ws().d_part; ga.nvoiced = c->ws().d_nv; ga.D = c->D; ga.n_chunks = n_frames / SCAN_CHUNK;
             ga.part_plane_stride = (long long)n_arrays * ga.n_chunks * c->D;
@@ -1521,7 +1539,13 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
                 HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
                 hipLaunchKernelGGL(K, gv, dim3(512), smem, st, ga);                                                       \
             } while (0)
+            // (the slices of a call all have the call's split factor, so a 256-row slice of a folding two-segment call folds like the others)
             if (c->a_planes == 2) V2_LAUNCH(k_srp_gemm_f16_v2);
+            else if (ksplit == 2 && mg && c->fold) {
+                const size_t smem_f = (size_t)FOLD_NS * (256 + 192) * 64;
+                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_srp_gemm_f16_fold), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_f));
+                hipLaunchKernelGGL(k_srp_gemm_f16_fold, gv, dim3(512), smem_f, st, ga);
+            }
             else V2_LAUNCH(k_srp_gemm_f16_v3);
 #undef V2_LAUNCH
         } else {

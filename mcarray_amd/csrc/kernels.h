@@ -38,6 +38,7 @@ __global__ void k_srp_gemm_f32(GemmArgs p);
 template <bool SPLIT, int BN> __global__ void k_srp_gemm_f16(GemmArgs p);
 __global__ void k_srp_gemm_f16_v2(GemmArgs p);      // hi + lo planes, v_mfma_f32_32x32x16_f16
 __global__ void k_srp_gemm_f16_v3(GemmArgs p);      // one plane, v_mfma_f32_16x16x32_f16
+__global__ void k_srp_gemm_f16_fold(GemmArgs p);    // one plane, planar rows of a folding context: K half y against the even / odd half-width table
 template <int BN> __global__ void k_srp_gemm_repair(GemmArgs p);
 
 template <typename T> struct C2;

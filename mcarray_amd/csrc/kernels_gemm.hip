@@ -571,4 +571,169 @@ __global__ __launch_bounds__(512) void k_srp_gemm_f16_v3(GemmArgs p)
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_srp_gemm_f16_fold: the one-plane contraction of a context whose grid folds about broadside (fold_table.h).  The merged rows
+// are planar, [R | I], and the two K segments of the launch are the two products of the fold: workgroup (tile, y) contracts half y
+// of its 256 rows with the even (y = 0: cos) or the odd (y = 1: -sin) table of 192 column pairs, and writes its 256 x 192 result
+// mirrored into the full-width partial map y: v at column c + j, +v (even) or -v (odd) at column c - j.  The scans sum the two
+// partial maps as they do behind k_srp_gemm_f16_v3, half 0 first.  Half the multiply-accumulates, half the B-fragment reads and
+// 28 instead of 40 KiB of LDS-DMA per stage and CU.
+// From k_srp_gemm_f16_v3: the ring of 32-deep LDS-DMA stages, its swizzle, the inline-asm waits, the rolling B fragments and the
+// 16x16x32 MFMA; 8 waves as 4 x 2, wave tile 64 x 96 = 4 x 6 MFMA tiles (96 accumulator registers).  A stage is 16 row blocks of A
+// and 12 of B (16 rows x 64 B = one DMA instruction each): every wave loads two of A and one of B, the waves 0..3 one more of B,
+// so the load count a wave waits on is 4 or 3 per stage (a wave-uniform choice).
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void k_srp_gemm_f16_fold(GemmArgs p)
+{
+    constexpr int BN = 192;
+    constexpr int A_BYTES = V2_BM * V3_ROWB, B_BYTES = BN * V3_ROWB;         // 16 KiB, 12 KiB
+    constexpr int STAGE = A_BYTES + B_BYTES;                                // 28 KiB
+    constexpr int NS = FOLD_NS;
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem_g[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int row0 = blockIdx.x * V2_BM, y = blockIdx.y;
+    const int half = p.Kp / 2, ns = half / V3_BK;                           // reals per half row, its stages
+    const unsigned char *A = reinterpret_cast<const unsigned char *>(p.A);
+    const unsigned char *B = reinterpret_cast<const unsigned char *>(p.Bf) + (long long)y * ns * B_BYTES;   // [y][stage][192][32]
+    const bool b2 = wave < 4;                                               // this wave also loads the B row block 8 + wave
+
+    const int lrow = lane >> 2, pch = lane & 3;
+    const int r0 = wave * 16 + lrow;
+    const int lch = pch ^ v3_swz(r0);
+    const unsigned char *a_lane = A + ((long long)(row0 + r0) * p.a_row_elems + (long long)y * half + lch * 8) * 2;
+    const unsigned char *b_lane = B + r0 * V3_ROWB + lch * 16;
+    const long long a_blk = (long long)128 * p.a_row_elems * 2;
+    const int dst0 = wave * 1024;
+
+    f32x4 acc[4][6];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+
+    auto issue_a = [&](int s, int buf) {
+        const long long koff_a = (long long)s * V3_BK * 2;
+        unsigned char *sb = smem_g + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(a_lane + i * a_blk + koff_a), (lds_void_t *)(sb + dst0 + i * 8192), 16, 0, 0);
+    };
+    auto issue_b = [&](int s, int buf) {
+        const long long koff_b = (long long)s * B_BYTES;
+        unsigned char *sb = smem_g + buf * STAGE;
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(b_lane + koff_b), (lds_void_t *)(sb + A_BYTES + dst0), 16, 0, 0);
+        if (b2) __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(b_lane + 128 * V3_ROWB + koff_b), (lds_void_t *)(sb + A_BYTES + dst0 + 8192), 16, 0, 0);
+    };
+
+    // fragment addresses: lane (row l & 15, K chunk l >> 4); row blocks are 16 rows = 1 KiB apart
+    const int ra = wm * 64 + (lane & 15), rb = wn * 96 + (lane & 15);
+    const int a_off0 = ra * V3_ROWB + (((lane >> 4) ^ v3_swz(ra)) << 4);
+    const int b_off0 = rb * V3_ROWB + (((lane >> 4) ^ v3_swz(rb)) << 4);
+    const unsigned lds0 = (unsigned)(uintptr_t)((lds_void_t *)smem_g);
+
+#pragma unroll
+    for (int q = 0; q < NS - 1; ++q)
+        if (q < ns) { issue_a(q, q); issue_b(q, q); }
+    for (int s = 0; s < ns; ++s) {
+        const int later = min(NS - 2, ns - 1 - s);                 // stages issued after this one (loads of a wave return in order)
+        if (b2) {
+            if (later >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else if (later == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
+            if (later >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else if (later == 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        const bool more = s + NS - 1 < ns;
+        if (more) issue_a(s + NS - 1, (s + NS - 1) % NS);          // that buffer was last read in stage s-1
+#define LDS_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+        f16x8 af[4], bs[2];
+        const unsigned a_addr = lds0 + (s % NS) * STAGE + a_off0;
+        const unsigned b_addr = lds0 + (s % NS) * STAGE + A_BYTES + b_off0;
+        LDS_RD(af[0], a_addr, 0); LDS_RD(af[1], a_addr, 1024); LDS_RD(af[2], a_addr, 2048); LDS_RD(af[3], a_addr, 3072);
+        LDS_RD(bs[0], b_addr, 0); LDS_RD(bs[1], b_addr, 1024);
+        // rolling B fragments as in v3: block j's MFMAs issue, then block j + 2 is requested into the slot they read
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            if (j == 5 && more) issue_b(s + NS - 1, (s + NS - 1) % NS);
+            if (j == 0) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(bs[0]));
+            else if (j < 5) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(bs[j % 2]));
+            else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bs[j % 2]));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bs[j % 2], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (j + 2 < 6) LDS_RD(bs[j % 2], b_addr, (j + 2) * 1024);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#undef LDS_RD
+    }
+    // The result of column pair jj = wn * 96 + 16 j + (lane & 15) goes to column c + jj and, mirrored, to column c - jj; pairs beyond the
+    // centre (zero table columns) are not stored, and the lanes of the first Dp - D pairs write the map's padding columns [D, Dp) as zero
+    // (the scans read whole float4s of Dp).
+    const int cc = (p.D - 1) / 2, npad = p.Dp - p.D, jj0 = wn * 96 + (lane & 15);
+    float *Cp = p.C + (long long)y * p.c_plane_elems;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int frow = row0 + wm * 64 + i * 16 + 4 * (lane >> 4) + r;
+            if (frow < p.rows) {
+                const int arr = frow / p.chunk_frames, fl = frow - arr * p.chunk_frames;
+                float *crow = Cp + ((long long)arr * p.total_frames + p.frame0 + fl) * p.Dp;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    const int jj = jj0 + j * 16;
+                    const float v = acc[i][j][r];
+                    if (jj <= cc) {
+                        crow[cc + jj] = v;
+                        if (jj > 0) crow[cc - jj] = y ? -v : v;
+                    }
+                    if (jj < npad) crow[p.D + jj] = 0.f;
+                }
+            }
+        }
+    if (p.part) {
+        // the chunk-local results of the scan over frames as in k_srp_gemm_f16_v3, mirrored the same way (d < D only)
+        float wt[2][4];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int g4 = lane >> 4;                           // (selects, not an indexed read of the argument block)
+                const float w01 = g4 == 0 ? p.scan_w[b * 16 + r] : p.scan_w[b * 16 + 4 + r];
+                const float w23 = g4 == 2 ? p.scan_w[b * 16 + 8 + r] : p.scan_w[b * 16 + 12 + r];
+                wt[b][r] = g4 < 2 ? w01 : w23;
+            }
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+            const int frow0 = row0 + wm * 64 + ch * 32;
+            if (frow0 < p.rows) {
+                const int arr = frow0 / p.chunk_frames, chunk = (p.frame0 + frow0 - arr * p.chunk_frames) >> 5;
+                float *out = p.part + y * p.part_plane_stride + ((long long)arr * p.n_chunks + chunk) * p.D;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    float sacc = 0.f;
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) sacc = fmaf(wt[b][r], acc[2 * ch + b][j][r], sacc);
+                    sacc += __shfl_xor(sacc, 16);
+                    sacc += __shfl_xor(sacc, 32);
+                    const int jj = jj0 + j * 16;
+                    if (lane < 16 && jj <= cc) {
+                        out[cc + jj] = sacc;
+                        if (jj > 0) out[cc - jj] = y ? -sacc : sacc;
+                    }
+                }
+                if (wn == 0 && lane == 0 && y == 0) p.nvoiced[(long long)arr * p.n_chunks + chunk] = 32;
+            }
+        }
+    }
+}
+
 }  // namespace mca

@@ -656,6 +656,16 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
                 // n_merged are zero and fall into the row's padding
                 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
                 typedef float float4_t __attribute__((ext_vector_type(4)));
+                if (p.planar) {
+                    // a context that folds about broadside (fold_table.h) takes the row planar, [Re S | Im S], nmp = Kp_m / 2 reals each:
+                    // four merged sums (32 bytes of the region) per lane and step, 8 bytes of fp16 into either half
+                    for (int j = lane; j < nmp / 4; j += 64) {
+                        const float4 v0 = reinterpret_cast<const float4 *>(S)[2 * j], v1 = reinterpret_cast<const float4 *>(S)[2 * j + 1];
+                        const float4_t re = {v0.x, v0.z, v1.x, v1.z}, im = {v0.y, v0.w, v1.y, v1.w};
+                        reinterpret_cast<half4_t *>(arow)[j] = __builtin_convertvector(re, half4_t);
+                        reinterpret_cast<half4_t *>(arow + nmp)[j] = __builtin_convertvector(im, half4_t);
+                    }
+                } else
                 for (int j = lane; j < nmp / 2; j += 64) {
                     const float4 v = reinterpret_cast<const float4 *>(S)[j];
                     const float4_t vv = {v.x, v.y, v.z, v.w};

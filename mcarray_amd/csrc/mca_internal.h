@@ -130,6 +130,7 @@ struct StftPhatArgs {
     float *hist_out; const float *hist_in; int hist_base;
     const unsigned short *mrank; int n_merged;   // k_stft_phat_wave, merged index (ULA, one fp16 plane): rank of the product m = k (j - i)
                              // among the n_merged distinct ones, [(M - 1) * 512 + 1]; NULL: per-group index g * 513 + k
+    int planar;              // merged rows of a context that folds about broadside (fold_table.h): row[r] = Re S[r], row[Kp_m / 2 + r] = Im S[r] instead of interleaved
     int no_phat;             // 1: gcc_weighting NONE -- the pair products of the spectra themselves (k_stft_phat_wave, fp32 rows only)
     int skew;                       // > 0 (round 5; a launch that is exactly one resident round of two workgroups per CU): grid (arrays, run groups),
                                     // and the run groups of the first half -- dispatched first: the OLDER workgroup of every CU, which the CU's
@@ -171,6 +172,8 @@ __device__ __forceinline__ void store_a(_Float16 *row, const StftPhatArgs &p, in
     }
 }
 
+constexpr int FOLD_NS = 4;      // LDS stages of k_srp_gemm_f16_fold (28 KiB each)
+
 struct GemmArgs {
     const void *A;           // [rows][a_row_elems]
     const void *B;           // fp32: [Kp][Dp]; fp16: [planes][Dp][Kp] (k contiguous)
@@ -186,6 +189,7 @@ struct GemmArgs {
     int repair_items;        // ... halved while the list gives more work items than this (repair_ksplit_eff; 0: never)
     // chunk-local scan result from the contraction's epilogue (256 x 384 kernel, one map, no gate, 32-row blocks = scan chunks):
     // part[arr][chunk][d] = sum_t scan_w[t] C[t][d] = the recursion E = 0.8f E + 0.2f C run from zero over the chunk's frames
+    const void *Bf;          // k_srp_gemm_f16_fold: the even and the odd half-width table, [2][Kp / 64][192][32] fp16 (fold_table.h); D is set for it
     float *part; int *nvoiced; int D, n_chunks;
     long long part_plane_stride;   // a split-K launch leaves one set of results per K half (summed by k_scan_carry, half 0 first)
     float scan_w[32];
