@@ -6,6 +6,7 @@
 #ifndef MCA_HIP_MVDRBEAMFORMER_H
 #define MCA_HIP_MVDRBEAMFORMER_H
 #include <algorithm>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -93,7 +94,7 @@ public:
     // The geometry of the steering vectors (mca_hip_mvdr_set_geometry).  MCA_HIP_MVDR_GEOMETRY_LINEAR_X, the default: the x coordinates
     // of the ArrayDescription alone (Beamformer.cpp:59).  MCA_HIP_MVDR_GEOMETRY_XYZ: all three coordinates; every look direction is an
     // azimuth round the whole circle (0: +y, +pi/2: +x) at the one elevation given here, in [-pi/2, pi/2].  A call that changes mode or
-    // elevation un-configures the spectrum and the tracks: configureSpectrum() and configureTracks() anew.  No part of the stream's state.
+    // elevation un-configures the spectrum, the map and the tracks: configureSpectrum(), configureMap() and configureTracks() anew.  No part of the stream's state.
     void setGeometry(int mode, double elevationRad = 0.0)
     {
         mca_hip_mvdr_geometry_config before, cfg;
@@ -103,7 +104,7 @@ public:
         cfg.elevation_rad = elevationRad;
         check(mca_hip_mvdr_set_geometry(_ctx, &cfg));
         check(mca_hip_mvdr_get_geometry(_ctx, &cfg));
-        if (cfg.mode != before.mode || cfg.elevation_rad != before.elevation_rad) { _nAngles = 0; _nPeaks = 0; _nTracks = 0; _follow = false; }
+        if (cfg.mode != before.mode || cfg.elevation_rad != before.elevation_rad) { _nAngles = 0; _nPeaks = 0; _nAz = 0; _nEl = 0; _nMapPeaks = 0; _nTracks = 0; _follow = false; }
     }
     void getGeometry(int &mode, double &elevationRad) const
     {
@@ -223,6 +224,64 @@ public:
         check(mca_hip_mvdr_spectrum_host(_ctx, 1, nullptr, d.data(), v.data()));
         doaRadians.assign(d.begin(), d.end());
         values.assign(v.begin(), v.end());
+    }
+    // The Capon spectrum on a grid of azimuths x elevations and its peaks (mca_hip_mvdr_map_*; XYZ geometry only): nAz 3 ... 360
+    // azimuths round the circle, nEl 1 ... 91 elevations from elLoRad to elHiRad (nEl == 1: both equal), nAz nEl <= 2048; band,
+    // weighting and nPeaks as configureSpectrum().  mapPeaks(): azimuths as setDOAs() takes them, and the elevation of each.
+    void configureMap(int nAz, int nEl, double elLoRad, double elHiRad, int binLo, int binHi, int weighting = MCA_HIP_MVDR_SPECTRUM_NORMALISED,
+                      int nPeaks = 1)
+    {
+        mca_hip_mvdr_map_config cfg;
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.n_az = nAz;
+        cfg.n_el = nEl;
+        cfg.el_lo_rad = elLoRad;
+        cfg.el_hi_rad = elHiRad;
+        cfg.bin_lo = binLo;
+        cfg.bin_hi = binHi;
+        cfg.weighting = weighting;
+        cfg.n_peaks = nPeaks;
+        check(mca_hip_mvdr_map_configure(_ctx, &cfg));
+        _nAz = nAz;
+        _nEl = nEl;
+        _nMapPeaks = nPeaks;
+    }
+    void mapGrid(std::vector<double> &azRadians, std::vector<double> &elRadians) const   // [nAz], [nEl]
+    {
+        if (_nAz == 0) throw MCArrayException("mapGrid: configureMap() first");
+        std::vector<float> a(static_cast<size_t>(_nAz)), e(static_cast<size_t>(_nEl));
+        check(mca_hip_mvdr_map_get_grid(_ctx, a.data(), e.data()));
+        azRadians.assign(a.begin(), a.end());
+        elRadians.assign(e.begin(), e.end());
+    }
+    void map(std::vector<double> &values)                      // [nEl][nAz]
+    {
+        if (_nAz == 0) throw MCArrayException("map: configureMap() first");
+        std::vector<float> m(static_cast<size_t>(_nAz) * static_cast<size_t>(_nEl));
+        check(mca_hip_mvdr_map_host(_ctx, 1, m.data(), nullptr, nullptr, nullptr));
+        values.assign(m.begin(), m.end());
+    }
+    void mapPeaks(std::vector<double> &azRadians, std::vector<double> &elRadians, std::vector<double> &values)   // [nPeaks] each, ranked by value
+    {
+        if (_nAz == 0) throw MCArrayException("mapPeaks: configureMap() first");
+        const size_t n = static_cast<size_t>(_nMapPeaks);
+        std::vector<float> a(n), e(n), v(n);
+        check(mca_hip_mvdr_map_host(_ctx, 1, nullptr, a.data(), e.data(), v.data()));
+        azRadians.assign(a.begin(), a.end());
+        elRadians.assign(e.begin(), e.end());
+        values.assign(v.begin(), v.end());
+    }
+    // An elevation per look direction (mca_hip_mvdr_set_elevations_host; XYZ geometry): one value per slot of setDOAs(), radians within
+    // +-pi/2, NaN for the elevation of setGeometry(); slots beyond the vector are NaN.  mapPeaks() gives the values: setDOAs(az),
+    // setElevations(el).  Kept across reset(); a geometry change and configureTracks() reset it, and setting it disables the tracks.
+    void setElevations(const std::vector<double> &elevationsRadians)
+    {
+        if (static_cast<int>(elevationsRadians.size()) > _maxSources) throw MCArrayException("setElevations: more values than maxSources");
+        std::vector<float> e(static_cast<size_t>(_maxSources), std::numeric_limits<float>::quiet_NaN());
+        for (size_t i = 0; i < elevationsRadians.size(); ++i) e[i] = static_cast<float>(elevationsRadians[i]);
+        check(mca_hip_mvdr_set_elevations_host(_ctx, 1, e.data()));
+        _nTracks = 0;
+        _follow = false;
     }
     // Tracks of the look directions, kept on the device between chunks (mca_hip_mvdr_tracks_*): nTracks 1 ... maxSources slots, of which
     // the first nOwn follow their own target covariance (setRtf(true) first) and the others the Capon peaks (configureSpectrum()
@@ -440,6 +499,7 @@ private:
     double _doa = 0.0, _update = 1.0;
     int _maxSources = 1;
     int _nAngles = 0, _nPeaks = 0;
+    int _nAz = 0, _nEl = 0, _nMapPeaks = 0;
     int _nTracks = 0;
     bool _follow = false;
     std::vector<double> _doas;

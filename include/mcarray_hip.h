@@ -899,6 +899,47 @@ int mca_hip_mvdr_spectrum_get_grid(const mca_hip_mvdr_ctx *ctx, float *doa_rad);
 int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum_dev, float *peak_doa_dev, float *peak_val_dev,
                               void *stream);
 int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *spectrum, float *peak_doa, float *peak_val);
+/* The Capon spectrum on a grid of azimuths x elevations (XYZ geometry only; mca_hip_mvdr_set_geometry below defines e(theta, eps) and
+ * the phase).  The spectrum above scans the one cone of the context's elevation: a talker off that elevation shows at a biased
+ * azimuth with a lowered peak, and no call tells the elevation.  Per stream, with
+ *     theta_i = -pi + i 2 pi / n_az, i = 0 ... n_az-1                    the periodic grid of XYZ mode (in double)
+ *     eps_j   = el_lo + j step, step = (el_hi - el_lo)/(n_el - 1)         j = 0 ... n_el-1 (in double; n_el == 1: eps_0 = el_lo)
+ *     P[j][i] = sum over k in [bin_lo, bin_hi] with tr[k] > 1e-30 of w[k] / (d^H PhiL[k]^-1 d),   d = d(theta_i, eps_j, k)
+ * d is the XYZ steering vector of set_geometry with cos eps_j, sin eps_j in place of the context's, its phase formed in double the
+ * same way; PhiL, w[k] (weighting), the silence threshold and the zero map of a stream with no live bin in the band are the
+ * spectrum's.  With n_el = 1 and el_lo = el_hi = the context's elevation, map, peak azimuths and peak values are the bytes of
+ * mca_hip_mvdr_spectrum_dev with n_angles = n_az.
+ * Peaks: the neighbours of cell (j, i) are the 8 cells around it, periodic in azimuth ((i +- 1) mod n_az), none beyond rows 0 and
+ * n_el-1.  (j, i) is a local maximum if P > 0, P is strictly greater than (j, i-1) and the three cells of row j-1, and P is >=
+ * (j, i+1) and the three cells of row j+1: a plateau counts once.  With n_el = 1 this is the circular rule of the spectrum in XYZ
+ * mode.  Local maxima are ranked by value, descending, ties to the lower flat index j n_az + i; slot r < n_peaks gets
+ * peak_az[r] = (float) theta_i, peak_el[r] = (float) eps_j, peak_val[r] = P[j][i].  Slots beyond the number of local maxima get
+ * peak_val = 0 and the angles of slot 0; if there is no local maximum at all, azimuth 0.0 and (float) the context's elevation.  A
+ * row at exactly +-pi/2 is one direction n_az times over: its cells differ by rounding alone, and which of them is picked there,
+ * if any, is decided by that rounding.
+ * Accepted: struct_size as compiled, XYZ geometry, n_az 3 ... 360, n_el 1 ... 91, n_az n_el <= 2048, el_lo and el_hi finite with
+ * -pi/2 <= el_lo <= el_hi <= pi/2 and el_lo == el_hi where n_el == 1, the band, weighting and n_peaks as for the spectrum; anything
+ * else is MCA_HIP_ERR_INVALID_ARGUMENT and leaves the former configuration in place.  A map call before configure, with n_streams
+ * outside 1 ... max_streams or with all four outputs NULL is MCA_HIP_ERR_INVALID_ARGUMENT.  A geometry change un-configures the
+ * map, as it does the spectrum.  The configuration is a processing parameter: state blobs neither carry nor check it.  The call
+ * reads the stream state and writes none of it; no atomics: the same bytes on every run, wherever a stream sits in the batch and
+ * whatever n_streams is.  The partial sums of the scan are workspace taken in passes of streams under the cap of
+ * mca_hip_mvdr_set_rtf_workspace (one stream a pass at the least); the cap changes no byte.  Timing: kernel_id 8.
+ *   map_dev [streams][n_el][n_az] float, peak_az_dev / peak_el_dev / peak_val_dev [streams][n_peaks] float; each may be NULL, not all */
+typedef struct {
+    int struct_size;
+    int n_az;                /* 3 ... 360 */
+    int n_el;                /* 1 ... 91; n_az n_el <= 2048 */
+    double el_lo_rad, el_hi_rad;   /* -pi/2 <= el_lo <= el_hi <= pi/2; n_el == 1 needs el_lo == el_hi */
+    int bin_lo, bin_hi;      /* the band, both ends included */
+    int weighting;           /* MCA_HIP_MVDR_SPECTRUM_POWER / _NORMALISED */
+    int n_peaks;
+} mca_hip_mvdr_map_config;
+int mca_hip_mvdr_map_configure(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_map_config *cfg);
+int mca_hip_mvdr_map_get_grid(const mca_hip_mvdr_ctx *ctx, float *az, float *el);   /* [n_az] (float) theta_i, [n_el] (float) eps_j; either may be NULL */
+int mca_hip_mvdr_map_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *map_dev, float *peak_az_dev, float *peak_el_dev, float *peak_val_dev,
+                         void *stream);
+int mca_hip_mvdr_map_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *map, float *peak_az, float *peak_el, float *peak_val);
 /* Tracks of the look directions, kept on the device between chunks: which talker owns which slot.  The spectrum's peaks are ranked
  * by value, so two talkers swap slots when their levels cross -- and a slot is more than an output index: it owns a target covariance
  * Psi and cpsi, the RTF estimated from it, a place among the first n_protected directions of the mask estimator and the null aimed
@@ -1014,6 +1055,29 @@ typedef struct {
 } mca_hip_mvdr_geometry_config;
 int mca_hip_mvdr_set_geometry(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_geometry_config *cfg);
 int mca_hip_mvdr_get_geometry(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_geometry_config *cfg);
+/* An elevation per look-direction slot (XYZ geometry).  The context holds, per stream and slot s < MCA_MAX_SOURCES, a pair
+ * (cos eps, sin eps) in double on the device.  In XYZ mode the steering tables of every mca_hip_mvdr_*frames* call -- plain, sources,
+ * weighted, masked, RTF and auto -- form the look direction s of a frame of stream a with the pair of (a, s) where set_geometry above
+ * writes cos eps and sin eps, and mca_hip_mvdr_get_steering does so for its (stream_index, source).  LINEAR_X never reads the pairs.
+ *   elev_rad [streams][max_sources] float: a NaN entry means "the context's elevation" and stores the context's own pair, bit for bit
+ *   -- the state of every slot after create.  Any other entry must be within +-pi/2, compared as float (the float nearest to pi/2,
+ *   1.57079637f, is accepted), and is clamped to [-pi/2, pi/2] in double before its cosine and sine are taken.
+ * mca_hip_mvdr_set_elevations_host refuses the whole array if one entry is outside (an infinity is), and changes nothing; it forms the
+ * pairs with the host's cos and sin, as set_geometry does, so that a context at elevation 0 with eps in every slot computes the bytes
+ * of a context created at eps; it synchronises the device.  mca_hip_mvdr_set_elevations_dev reads the array on `stream` and cannot
+ * refuse a value: it CLAMPS (an infinity goes to the end of the range; NaN still means unset) and forms the pairs with the device's
+ * double cos and sin, which may differ from the host's in the last place.  The slots max_sources ... and the streams n_streams ... keep
+ * what they hold.  mca_hip_mvdr_get_elevations reports [streams][max_sources] float: NaN for an unset slot, else the angle as given
+ * (host call) or as clamped (device call); it synchronises.
+ * The elevations are a processing parameter like the null gain: state blobs neither carry nor check them, and mca_hip_mvdr_reset keeps
+ * them.  A geometry change that changes mode or elevation resets every slot to unset.  The tracks, the Capon spectrum and its peaks
+ * keep the context's one elevation: a set_elevations call -- either one, whatever it carries -- disables the tracks, as a geometry
+ * change does, and mca_hip_mvdr_tracks_configure with enable = 1 resets every slot to unset.  The loop with a second angle is
+ * mca_hip_mvdr_map_dev -> peak_az_dev as doa_rad, peak_el_dev to mca_hip_mvdr_set_elevations_dev -> the next chunk, with no host step.
+ * n_streams outside 1 ... max_streams or a NULL array is MCA_HIP_ERR_INVALID_ARGUMENT. */
+int mca_hip_mvdr_set_elevations_host(mca_hip_mvdr_ctx *ctx, int n_streams, const float *elev_rad);
+int mca_hip_mvdr_set_elevations_dev(mca_hip_mvdr_ctx *ctx, int n_streams, const float *elev_rad_dev, void *stream);
+int mca_hip_mvdr_get_elevations(mca_hip_mvdr_ctx *ctx, int n_streams, float *elev_rad);
 /* copy of the covariance of one stream: out[N/2+1][M][M] interleaved re,im double (full Hermitian matrices) */
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *ctx, int stream_index, double *out);
 /* checkpoint / resume as mca_hip_state_*: the covariances, their traces and the overlap-add tails of every stream (and the
@@ -1026,7 +1090,8 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long b
  * post-filter enabled at some time (it stays readable after disabling); a context that never enabled it refuses 4 like every
  * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT).  5 = k_mvdr_rtf, by the same rule: it exists on a
  * context that has had RTF enabled at some time.  6 = k_mvdr_estmask, by the same rule (the mask estimator).  7 = the track
- * kernels (mca_hip_mvdr_tracks_*), by the same rule: it exists once tracks have been configured */
+ * kernels (mca_hip_mvdr_tracks_*), by the same rule: it exists once tracks have been configured.  8 = both kernels of a
+ * mca_hip_mvdr_map_* call, by the same rule: it exists once the map has been configured */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

@@ -126,6 +126,20 @@ class MvdrSpectrumConfig(C.Structure):
     ]
 
 
+class MvdrMapConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("n_az", C.c_int),
+        ("n_el", C.c_int),
+        ("el_lo_rad", C.c_double),
+        ("el_hi_rad", C.c_double),
+        ("bin_lo", C.c_int),
+        ("bin_hi", C.c_int),
+        ("weighting", C.c_int),
+        ("n_peaks", C.c_int),
+    ]
+
+
 class MvdrPostfilterConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -314,6 +328,13 @@ SYMBOLS = [
     ("mca_hip_mvdr_spectrum_get_grid", C.c_int, [C.c_void_p, c_fp]),
     ("mca_hip_mvdr_spectrum_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_spectrum_host", C.c_int, [C.c_void_p, C.c_int, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_map_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrMapConfig)]),
+    ("mca_hip_mvdr_map_get_grid", C.c_int, [C.c_void_p, c_fp, c_fp]),
+    ("mca_hip_mvdr_map_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_map_host", C.c_int, [C.c_void_p, C.c_int, c_fp, c_fp, c_fp, c_fp]),
+    ("mca_hip_mvdr_set_elevations_host", C.c_int, [C.c_void_p, C.c_int, c_fp]),
+    ("mca_hip_mvdr_set_elevations_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_get_elevations", C.c_int, [C.c_void_p, C.c_int, c_fp]),
     ("mca_hip_mvdr_tracks_configure", C.c_int, [C.c_void_p, C.POINTER(MvdrTracksConfig)]),
     ("mca_hip_mvdr_tracks_get_config", C.c_int, [C.c_void_p, C.POINTER(MvdrTracksConfig)]),
     ("mca_hip_mvdr_tracks_seed_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

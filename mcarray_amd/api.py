@@ -885,11 +885,13 @@ class MvdrBeamformer(_StateBlob):
     frame itself uses for the other look directions (mca_hip_mvdr_set_rtf_nulls); without it they refuse a non-zero null gain.
     set_geometry() / geometry="xyz": the steering vectors use all three coordinates of mic_positions, every look direction is an
     azimuth round the whole circle (0: +y, +pi/2: +x) at the context's one elevation, the spectrum's grid is periodic and the tracks
-    live on the circle (mca_hip_mvdr_set_geometry).  The default "linear_x" reads the x coordinates alone, as it always did."""
+    live on the circle (mca_hip_mvdr_set_geometry).  The default "linear_x" reads the x coordinates alone, as it always did.
+    map_configure() / map(): the Capon spectrum on a grid of azimuths x elevations and its peaks, for an array that can tell the
+    elevation (geometry "xyz"; mca_hip_mvdr_map_*)."""
 
     GEOMETRY_LINEAR_X, GEOMETRY_XYZ = 0, 1
 
-    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK, K_TRACKS = 0, 1, 2, 3, 4, 5, 6, 7
+    K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK, K_TRACKS, K_MAP = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  geometry="linear_x", elevation_rad=0.0, null_gain=0.0, rtf_nulls=False):
@@ -915,6 +917,7 @@ class MvdrBeamformer(_StateBlob):
         self.null_gain = 0.0
         self.max_streams = max_streams
         self.spectrum_config = None
+        self.map_config = None
         self._follow, self._follow_doa = False, None
         try:
             if max_sources != 1:
@@ -959,7 +962,7 @@ class MvdrBeamformer(_StateBlob):
     def set_geometry(self, mode, elevation_rad=0.0):
         """the geometry of the steering vectors (include/mcarray_hip.h, mca_hip_mvdr_set_geometry): mode "linear_x" (x coordinates
         alone, the default) or "xyz" (all three, azimuths round the circle), elevation_rad in [-pi/2, pi/2] (ignored by "linear_x").
-        A processing parameter; a call that changes it un-configures the spectrum and disables the tracks: configure them anew."""
+        A processing parameter; a call that changes it un-configures the spectrum and the map and disables the tracks: configure them anew."""
         kinds = {"linear_x": self.GEOMETRY_LINEAR_X, "xyz": self.GEOMETRY_XYZ}
         before = self.get_geometry()
         cfg = _lib.MvdrGeometryConfig()
@@ -969,6 +972,7 @@ class MvdrBeamformer(_StateBlob):
         self._check(self._lib.mca_hip_mvdr_set_geometry(self.h, C.byref(cfg)))
         if self.get_geometry() != before:
             self.spectrum_config = None
+            self.map_config = None
             self._follow, self._follow_doa = False, None
 
     def get_geometry(self):
@@ -1347,6 +1351,78 @@ class MvdrBeamformer(_StateBlob):
         self._check(self._lib.mca_hip_mvdr_spectrum_dev(
             self.h, int(n_streams), spectrum.data_ptr() if spectrum is not None else None, peak_doa.data_ptr() if peak_doa is not None else None,
             peak_val.data_ptr() if peak_val is not None else None, stream))
+
+    def map_configure(self, n_az, n_el=1, el_lo_rad=None, el_hi_rad=None, bin_lo=None, bin_hi=None, weighting="normalised", n_peaks=1):
+        """the azimuth x elevation Capon map map() evaluates on the covariance the context holds (include/mcarray_hip.h,
+        mca_hip_mvdr_map_configure; geometry "xyz" only): n_az 3 ... 360 azimuths round the circle, n_el 1 ... 91 elevations from
+        el_lo_rad to el_hi_rad (default: both the context's elevation; n_el == 1 needs them equal), n_az n_el <= 2048, the band,
+        weighting and n_peaks as configure_spectrum().  A processing parameter, no part of the state blobs."""
+        kinds = {"power": self.SPECTRUM_POWER, "normalised": self.SPECTRUM_NORMALISED}
+        eps = self.get_geometry()["elevation_rad"]
+        cfg = _lib.MvdrMapConfig()
+        cfg.struct_size = C.sizeof(_lib.MvdrMapConfig)
+        cfg.n_az, cfg.n_el = int(n_az), int(n_el)
+        cfg.el_lo_rad = eps if el_lo_rad is None else float(el_lo_rad)
+        cfg.el_hi_rad = cfg.el_lo_rad if el_hi_rad is None else float(el_hi_rad)
+        cfg.bin_lo = 1 if bin_lo is None else int(bin_lo)
+        cfg.bin_hi = self.N // 2 - 1 if bin_hi is None else int(bin_hi)
+        cfg.weighting = kinds[weighting] if weighting in kinds else int(weighting)
+        cfg.n_peaks = int(n_peaks)
+        self._check(self._lib.mca_hip_mvdr_map_configure(self.h, C.byref(cfg)))
+        self.map_config = dict(n_az=cfg.n_az, n_el=cfg.n_el, el_lo_rad=cfg.el_lo_rad, el_hi_rad=cfg.el_hi_rad, bin_lo=cfg.bin_lo,
+                               bin_hi=cfg.bin_hi, weighting=cfg.weighting, n_peaks=cfg.n_peaks)
+
+    def map_grid(self):
+        """(az float32 [n_az], el float32 [n_el]): the angles of the map's grid (radians), as peak_az and peak_el report them"""
+        if getattr(self, "map_config", None) is None:
+            raise MCArrayHipError("map_configure() first")
+        az = np.empty(self.map_config["n_az"], dtype=np.float32)
+        el = np.empty(self.map_config["n_el"], dtype=np.float32)
+        self._check(self._lib.mca_hip_mvdr_map_get_grid(self.h, az.ctypes.data_as(_lib.c_fp), el.ctypes.data_as(_lib.c_fp)))
+        return az, el
+
+    def map(self, n_streams=None):
+        """the map of streams 0 ... n_streams - 1 (default: all) and its peaks -> dict(map [A][n_el][n_az], peak_az / peak_el [A][P]
+        radians, peak_val [A][P]), float32.  peak_az is a valid doa_rad[:, t, :] of the next process_sources() call.  Reads the
+        stream state, writes none of it."""
+        cfgd = getattr(self, "map_config", None)
+        A = self.max_streams if n_streams is None else int(n_streams)
+        n_el, n_az, P = (cfgd["n_el"], cfgd["n_az"], cfgd["n_peaks"]) if cfgd else (1, 1, 1)
+        m = np.empty((max(A, 0), n_el, n_az), dtype=np.float32)
+        az, el, val = (np.empty((max(A, 0), P), dtype=np.float32) for _ in range(3))
+        fp = _lib.c_fp
+        self._check(self._lib.mca_hip_mvdr_map_host(self.h, A, m.ctypes.data_as(fp), az.ctypes.data_as(fp), el.ctypes.data_as(fp), val.ctypes.data_as(fp)))
+        return dict(map=m, peak_az=az, peak_el=el, peak_val=val)
+
+    def map_dev(self, n_streams, map=None, peak_az=None, peak_el=None, peak_val=None, stream=None):
+        """device tensors (torch, contiguous float32): map [A][n_el][n_az], peak_az / peak_el / peak_val [A][n_peaks]; any may be
+        None, not all; asynchronous on `stream` (a raw hipStream_t or None)"""
+        self._check(self._lib.mca_hip_mvdr_map_dev(self.h, int(n_streams), *[t.data_ptr() if t is not None else None for t in (map, peak_az, peak_el, peak_val)],
+                                                   stream))
+
+    def set_elevations(self, elev_rad):
+        """an elevation per stream and look-direction slot, [streams][max_sources] (or [max_sources] for one stream), radians within
+        +-pi/2; NaN: the context's elevation, the state after construction (include/mcarray_hip.h, mca_hip_mvdr_set_elevations_host).
+        Geometry "xyz": the process calls steer look direction s of stream a at its own elevation.  A processing parameter, kept
+        across reset(); a geometry change and configure_tracks() reset it to unset, and setting it disables the tracks."""
+        e = np.ascontiguousarray(np.atleast_2d(np.asarray(elev_rad, dtype=np.float32)))
+        if e.ndim != 2 or e.shape[1] != self.max_sources:
+            raise MCArrayHipError("elev_rad must be [streams][max_sources]")
+        self._check(self._lib.mca_hip_mvdr_set_elevations_host(self.h, e.shape[0], e.ctypes.data_as(_lib.c_fp)))
+        self._follow, self._follow_doa = False, None
+
+    def set_elevations_dev(self, n_streams, elev_rad, stream=None):
+        """device tensor (torch, contiguous float32) [n_streams][max_sources] -- the peak_el of map_dev() for instance; values outside
+        +-pi/2 are clamped; asynchronous on `stream`"""
+        self._check(self._lib.mca_hip_mvdr_set_elevations_dev(self.h, int(n_streams), elev_rad.data_ptr(), stream))
+        self._follow, self._follow_doa = False, None
+
+    def get_elevations(self, n_streams=None):
+        """float32 [streams][max_sources]: NaN for a slot at the context's elevation"""
+        A = self.max_streams if n_streams is None else int(n_streams)
+        e = np.empty((max(A, 0), self.max_sources), dtype=np.float32)
+        self._check(self._lib.mca_hip_mvdr_get_elevations(self.h, A, e.ctypes.data_as(_lib.c_fp)))
+        return e
 
     def configure_tracks(self, n_tracks, n_own=0, max_step_rad=0.2, min_sep_rad=0.1, hold=3, enable=True):
         """tracks of the look directions, kept on the device between chunks (include/mcarray_hip.h, mca_hip_mvdr_tracks_configure):

@@ -1,8 +1,8 @@
 // api_mvdr.hip -- C ABI of the MVDR-style beamformer with a per-bin spatial covariance (include/mcarray_hip.h,
 // mca_hip_mvdr_*; BASELINE.json configs[3]; SURVEY A.9 -- no reference counterpart, conventions of Beamformer.cpp:59).
 // Host side only: owns the per-stream state (covariances, their traces, overlap-add tails) and the spectra
-// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip, kernels_mvdr_estmask.hip and
-// kernels_mvdr_postfilter.hip.  No CPU fallback.
+// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip, kernels_mvdr_estmask.hip,
+// kernels_mvdr_postfilter.hip, kernels_mvdr_spectrum.hip, kernels_mvdr_track.hip and kernels_mvdr_map.hip.  No CPU fallback.
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
@@ -31,6 +31,9 @@ struct mca_hip_mvdr_ctx {
     double geo_elevation = 0.0;
     std::vector<double> geo_u;    // [3][M]: unit * x_m, unit * y_m, unit * z_m, unit = fs / N / 346.1
     DevBuf<double> d_geo_u;       // the same on the device (MvdrGeometry::u)
+    // an elevation per look-direction slot (mca_hip_mvdr_set_elevations_*): a processing parameter, kept across reset, no part of the blobs
+    DevBuf<double2> d_slot_el;    // [max_streams][MCA_MAX_SOURCES] (cos eps, sin eps) (MvdrGeometry::slot_el); an unset slot: the context's pair
+    DevBuf<float> d_slot_val;     // [max_streams][MCA_MAX_SOURCES] the angle as mca_hip_mvdr_get_elevations reports it; NaN: unset
     DevBuf<float2> d_phi;         // [max_streams][K][tri]
     DevBuf<float> d_trace;        // [max_streams][K]
     DevBuf<float2> d_phi_tail; DevBuf<float> d_trace_tail;   // exit state of the pieced tail launch (<= 128 workgroups x 64 problems), copied back behind it
@@ -78,6 +81,15 @@ struct mca_hip_mvdr_ctx {
     DevBuf<float> d_spec_grid;
     DevBuf<float2> d_spec_T;                        // [M][N/64 + 33][Dpad] factored steering phasors of the grid (MvdrSpectrumArgs::T)
     DevBuf<float> d_spec_part;                      // workspace: partial sums [streams][chunks][4][Dpad]
+    // the azimuth x elevation Capon map (mca_hip_mvdr_map_*): a processing parameter like the spectrum's configuration
+    bool map_set = false;
+    bool map_ever = false;        // configured at some time: timing slot 8 exists
+    mca_hip_mvdr_map_config map{};
+    int map_dpad = 0;                               // n_az n_el rounded up to whole waves
+    std::vector<float> map_az, map_el;              // [n_az] (float) theta_i, [n_el] (float) eps_j
+    DevBuf<float> d_map_az, d_map_el;
+    DevBuf<float2> d_map_T;                         // [M][N/64 + 33][Dpad] over the flat list of directions j n_az + i (MvdrSpectrumArgs::T)
+    DevBuf<float> d_map_part;                       // workspace: partial sums [streams of a pass][chunks][4][Dpad]
     // tracks of the look directions (mca_hip_mvdr_tracks_*): the configuration is a processing parameter like null_gain; theta, alive,
     // miss and gen are per-stream state that no state blob carries
     bool trk_on = false;
@@ -91,8 +103,8 @@ struct mca_hip_mvdr_ctx {
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[8] = {};
-    double t_ms[8] = {};
+    int t_launches[9] = {};
+    double t_ms[9] = {};
     std::string err;
 };
 
@@ -170,20 +182,46 @@ hipError_t clear_unused_slots(const mca_hip_mvdr_ctx *c, T *buf, size_t row_elem
 
 MvdrGeometry geometry_args(const mca_hip_mvdr_ctx *c)
 {
-    return MvdrGeometry{c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0, c->d_geo_u, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
+    return MvdrGeometry{c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0, c->d_geo_u, std::cos(c->geo_elevation), std::sin(c->geo_elevation), c->d_slot_el};
+}
+
+// every look-direction slot back to unset: the context's pair, NaN as its angle.  Synchronous; the caller has waited for the device
+hipError_t reset_elevations(mca_hip_mvdr_ctx *c)
+{
+    const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    const std::vector<double2> pairs(n, make_double2(std::cos(c->geo_elevation), std::sin(c->geo_elevation)));
+    const std::vector<float> vals(n, std::nanf(""));
+    hipError_t e = hipMemcpy(c->d_slot_el, pairs.data(), n * sizeof(double2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->d_slot_val, vals.data(), n * sizeof(float), hipMemcpyHostToDevice);
+    return e;
 }
 
 // turns per unit of kk of microphone m towards theta: what the steering tables of the kernels form (mvdr_projection), on the host
-double host_projection(const mca_hip_mvdr_ctx *c, int m, double theta)
+// the XYZ arm: the projection on e(theta, eps) with ce = cos eps, se = sin eps
+double host_projection_xyz(const mca_hip_mvdr_ctx *c, int m, double theta, double ce, double se)
 {
     const int M = c->M;
-    const double cd = std::cos(theta + M_PI / 2);
-    if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return c->geo_u[m] * cd;                      // (unit x_m) cd, Beamformer.cpp:59
-    const double ce = std::cos(c->geo_elevation), se = std::sin(c->geo_elevation), cy = -std::cos(theta);
+    const double cd = std::cos(theta + M_PI / 2), cy = -std::cos(theta);
     double pr = c->geo_u[m] * (cd * ce);
     if (c->geo_u[M + m] != 0.0) pr += c->geo_u[M + m] * (cy * ce);
     if (c->geo_u[2 * M + m] != 0.0) pr -= c->geo_u[2 * M + m] * se;
     return pr;
+}
+double host_projection(const mca_hip_mvdr_ctx *c, int m, double theta)
+{
+    if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return c->geo_u[m] * std::cos(theta + M_PI / 2);   // (unit x_m) cd, Beamformer.cpp:59
+    return host_projection_xyz(c, m, theta, std::cos(c->geo_elevation), std::sin(c->geo_elevation));
+}
+
+// the factored phasors of one (direction, microphone) with projection u: exp(-j 2 pi 32 i u), i <= N/64, and exp(-j 2 pi i u), i < 32
+// (MvdrAnalyseArgs::T), written with stride `stride`
+void host_phasors(double u, int nhi, int nph, float2 *T, size_t stride)
+{
+    for (int e = 0; e < nph; ++e) {
+        double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * u;
+        t -= std::floor(t);
+        T[(size_t)e * stride] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
+    }
 }
 
 // every state array from nothing (those of a feature that is off are empty, and cleared as such)
@@ -327,6 +365,9 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     if (e == hipSuccess) e = c->d_tw.upload(tw.data(), tw.size());
     if (e == hipSuccess) e = c->d_micx.upload(mx.data(), mx.size());
     if (e == hipSuccess) e = c->d_geo_u.upload(c->geo_u.data(), c->geo_u.size());
+    if (e == hipSuccess) e = c->d_slot_el.alloc((size_t)cfg->max_streams * MCA_MAX_SOURCES);
+    if (e == hipSuccess) e = c->d_slot_val.alloc((size_t)cfg->max_streams * MCA_MAX_SOURCES);
+    if (e == hipSuccess) e = reset_elevations(c);
     if (e == hipSuccess) e = c->d_phi.alloc(nk * c->tri);
     if (e == hipSuccess) e = c->d_trace.alloc(nk);
     if (e == hipSuccess) e = c->d_phi_tail.alloc((size_t)128 * 64 * c->tri);
@@ -429,7 +470,9 @@ int mca_hip_mvdr_set_geometry(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_geometry_c
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     VHIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the tables of the former geometry
     c->geo_mode = cfg->mode; c->geo_elevation = el;
+    if (const hipError_t e = reset_elevations(c)) return hip_fail(c, e, "elevations of the look-direction slots");   // unset: the new pair
     c->spec_set = false;                                       // its phasor table and grid are stale (freed by the next configure)
+    c->map_set = false;                                        // and so are the map's
     if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }   // the angles change meaning: configured anew
     return MCA_HIP_OK;
 }
@@ -1021,12 +1064,7 @@ int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spec
         const double th = xyz ? -M_PI + ii * (2.0 * M_PI) / (double)D : -M_PI / 2 + ii * M_PI / (double)(D - 1);
         if (i < D) grid[i] = (float)th;
         for (int m = 0; m < M; ++m) {
-            const double u = host_projection(c, m, th);
-            for (int e = 0; e < nph; ++e) {
-                double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * u;
-                t -= std::floor(t);
-                T[((size_t)m * nph + e) * Dpad + i] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
-            }
+            host_phasors(host_projection(c, m, th), nhi, nph, &T[(size_t)m * nph * Dpad + i], Dpad);
         }
     }
     // the former tables and spec_set stay when the new ones fail; else they go, behind the wait, with ng and nT
@@ -1115,6 +1153,203 @@ int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectr
     return MCA_HIP_OK;
 }
 
+// ---- the azimuth x elevation Capon map (kernels_mvdr_map.hip) ----
+int mca_hip_mvdr_map_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_map_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_map_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the map needs XYZ geometry (mca_hip_mvdr_set_geometry)");
+    if (cfg->n_az < 3 || cfg->n_az > 360) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_az must be in [3,360]");
+    if (cfg->n_el < 1 || cfg->n_el > 91) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_el must be in [1,91]");
+    if (cfg->n_az * cfg->n_el > MVDR_MAP_MAX_DIRS) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_az n_el must be at most 2048");
+    if (!std::isfinite(cfg->el_lo_rad) || !std::isfinite(cfg->el_hi_rad) || cfg->el_lo_rad < -M_PI / 2 || cfg->el_hi_rad > M_PI / 2 || cfg->el_lo_rad > cfg->el_hi_rad)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations must satisfy -pi/2 <= el_lo_rad <= el_hi_rad <= pi/2");
+    if (cfg->n_el == 1 && cfg->el_lo_rad != cfg->el_hi_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_el == 1 needs el_lo_rad == el_hi_rad");
+    if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
+    if (cfg->weighting != MCA_HIP_MVDR_SPECTRUM_POWER && cfg->weighting != MCA_HIP_MVDR_SPECTRUM_NORMALISED)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "weighting must be 0 (power) or 1 (normalised)");
+    if (cfg->n_peaks < 1 || cfg->n_peaks > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_peaks must be in [1,4]");
+    if (c->map_set && cfg->n_az == c->map.n_az && cfg->n_el == c->map.n_el && cfg->el_lo_rad == c->map.el_lo_rad && cfg->el_hi_rad == c->map.el_hi_rad) {
+        c->map = *cfg;                                          // the grid and its phasors stay
+        return MCA_HIP_OK;
+    }
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    // grid and phasors in double: theta_i = -pi + i 2 pi / n_az, eps_j = el_lo + j (el_hi - el_lo)/(n_el - 1), direction j n_az + i;
+    // the layout and the factors are the spectrum's (mca_hip_mvdr_spectrum_configure), the surplus lanes repeat the last direction
+    const int n_az = cfg->n_az, n_el = cfg->n_el, D = n_az * n_el, Dpad = (D + 63) & ~63, nhi = c->N / 64 + 1, nph = nhi + 32, M = c->M;
+    const double step = n_el > 1 ? (cfg->el_hi_rad - cfg->el_lo_rad) / (double)(n_el - 1) : 0.0;
+    std::vector<float> az(n_az), el(n_el);
+    std::vector<double> azd(n_az), ce(n_el), se(n_el);
+    for (int i = 0; i < n_az; ++i) { azd[i] = -M_PI + (double)i * (2.0 * M_PI) / (double)n_az; az[i] = (float)azd[i]; }
+    for (int j = 0; j < n_el; ++j) {
+        const double eps = cfg->el_lo_rad + (double)j * step;
+        el[j] = (float)eps; ce[j] = std::cos(eps); se[j] = std::sin(eps);
+    }
+    std::vector<float2> T((size_t)M * nph * Dpad);
+    for (int d = 0; d < Dpad; ++d) {
+        const int dd = d < D ? d : D - 1, j = dd / n_az, i = dd - j * n_az;
+        for (int m = 0; m < M; ++m) host_phasors(host_projection_xyz(c, m, azd[i], ce[j], se[j]), nhi, nph, &T[(size_t)m * nph * Dpad + d], Dpad);
+    }
+    // the former tables and map_set stay when the new ones fail; else they go, behind the wait
+    DevBuf<float> na, ne;
+    DevBuf<float2> nT;
+    hipError_t e = na.upload(az.data(), az.size());
+    if (e == hipSuccess) e = ne.upload(el.data(), el.size());
+    if (e == hipSuccess) e = nT.upload(T.data(), T.size());
+    if (e == hipSuccess) e = hipDeviceSynchronize();            // no map call in flight reads the former tables
+    if (e != hipSuccess) return hip_fail(c, e, "steering tables of the map");
+    c->d_map_az.swap(na); c->d_map_el.swap(ne); c->d_map_T.swap(nT); c->map_az.swap(az); c->map_el.swap(el);
+    c->map_dpad = Dpad; c->map = *cfg; c->map_set = true; c->map_ever = true;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_map_get_grid(const mca_hip_mvdr_ctx *c, float *az, float *el)
+{
+    if (!c || (!az && !el) || !c->map_set) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (az) std::memcpy(az, c->map_az.data(), c->map_az.size() * 4);
+    if (el) std::memcpy(el, c->map_el.data(), c->map_el.size() * 4);
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float *map, float *peak_az, float *peak_el, float *peak_val, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!map && !peak_az && !peak_el && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map_dev, peak_az_dev, peak_el_dev and peak_val_dev are all NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const int D = c->map.n_az * c->map.n_el;
+    MvdrMapScanArgs ma{};
+    MvdrSpectrumArgs &sa = ma.s;
+    sa.T = c->d_map_T;
+    sa.K = c->K; sa.M = c->M; sa.D = D; sa.Dpad = c->map_dpad; sa.nhi = c->N / 64 + 1; sa.nph = sa.nhi + 32;
+    sa.bin_lo = c->map.bin_lo; sa.bin_hi = c->map.bin_hi;
+    sa.chunk0 = sa.bin_lo / MVDR_SPEC_CHUNK; sa.n_chunks = sa.bin_hi / MVDR_SPEC_CHUNK - sa.chunk0 + 1;
+    sa.power = c->map.weighting == MCA_HIP_MVDR_SPECTRUM_POWER;
+    sa.loading = (float)c->cfg.loading;
+    ma.n_tiles = (sa.Dpad + MVDR_MAP_TILE - 1) / MVDR_MAP_TILE;
+    // The partial sums are taken in passes of streams under the cap of the context's workspace (mca_hip_mvdr_set_rtf_workspace), one
+    // stream a pass at the least: 288 KiB per stream at 2048 directions and N = 1024.  A stream's bytes do not depend on its pass.
+    const size_t per = (size_t)sa.n_chunks * 4 * sa.Dpad;
+    const size_t fit = std::max<size_t>(1, c->plane_cap_cells * 2 / per);                 // (floats under the cap)
+    const int pass = (int)std::min<size_t>(fit, (size_t)n_streams);
+    if (per * pass > c->d_map_part.n) VHIP_TRY(c, hipDeviceSynchronize());
+    if (const int rc = grow_ws(c, c->d_map_part, per * pass, "partial sums of the map")) return rc;
+    sa.part = c->d_map_part;
+    MvdrMapPickArgs pa{};
+    pa.part = c->d_map_part; pa.az = c->d_map_az; pa.el = c->d_map_el; pa.n_slices = sa.n_chunks * 4;
+    pa.n_az = c->map.n_az; pa.n_el = c->map.n_el; pa.Dpad = sa.Dpad; pa.n_peaks = c->map.n_peaks; pa.ctx_el = (float)c->geo_elevation;
+    const void *kernel = mvdr_map_scan_kernel((c->M + 3) / 4);
+    const size_t smem = (size_t)MVDR_SPEC_CHUNK * (c->tri * sizeof(float2) + 4);          // 68 KiB at 16 microphones, as the spectrum's
+    if (smem > 64 * 1024) VHIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    t_begin(c, 8, st);
+    for (int s0 = 0; s0 < n_streams; s0 += pass) {
+        const int ns = std::min(pass, n_streams - s0);
+        sa.phi = c->d_phi + (size_t)s0 * c->K * c->tri; sa.trace = c->d_trace + (size_t)s0 * c->K;
+        pa.map = map ? map + (size_t)s0 * D : nullptr;
+        pa.peak_az = peak_az ? peak_az + (size_t)s0 * pa.n_peaks : nullptr;
+        pa.peak_el = peak_el ? peak_el + (size_t)s0 * pa.n_peaks : nullptr;
+        pa.peak_val = peak_val ? peak_val + (size_t)s0 * pa.n_peaks : nullptr;
+        ma.n_streams = ns;
+        void *kargs[1] = {&ma};
+        (void)hipLaunchKernel(kernel, dim3((unsigned)((long long)ns * sa.n_chunks * ma.n_tiles)), dim3(256), kargs, smem, st);
+        hipLaunchKernelGGL(k_mvdr_map_pick, dim3(ns), dim3(256), 0, st, pa);
+    }
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_map_host(mca_hip_mvdr_ctx *c, int n_streams, float *map, float *peak_az, float *peak_el, float *peak_val)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!map && !peak_az && !peak_el && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map, peak_az, peak_el and peak_val are all NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t mb = (size_t)n_streams * c->map.n_az * c->map.n_el * 4, pb = (size_t)n_streams * c->map.n_peaks * 4;
+    float *d_m = map ? (float *)c->stage.get(4, mb) : nullptr;
+    float *d_a = peak_az ? (float *)c->stage.get(5, pb) : nullptr, *d_e = peak_el ? (float *)c->stage.get(6, pb) : nullptr;
+    float *d_v = peak_val ? (float *)c->stage.get(7, pb) : nullptr;
+    if ((map && !d_m) || (peak_az && !d_a) || (peak_el && !d_e) || (peak_val && !d_v))
+        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    const int rc = mca_hip_mvdr_map_dev(c, n_streams, d_m, d_a, d_e, d_v, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    if (map) VHIP_TRY(c, hipMemcpy(map, d_m, mb, hipMemcpyDeviceToHost));
+    if (peak_az) VHIP_TRY(c, hipMemcpy(peak_az, d_a, pb, hipMemcpyDeviceToHost));
+    if (peak_el) VHIP_TRY(c, hipMemcpy(peak_el, d_e, pb, hipMemcpyDeviceToHost));
+    if (peak_val) VHIP_TRY(c, hipMemcpy(peak_val, d_v, pb, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+// ---- an elevation per look-direction slot ----
+extern "C++" {
+namespace {
+int elevations_ready(mca_hip_mvdr_ctx *c, int n_streams, const void *ptr)
+{
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!ptr) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations array is NULL");
+    return MCA_HIP_OK;
+}
+// the tracks follow azimuths at the context's elevation: a slot with an elevation of its own ends them, as a geometry change does
+void elevations_disable_tracks(mca_hip_mvdr_ctx *c)
+{
+    if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }
+}
+}  // namespace
+}  // extern "C++"
+
+int mca_hip_mvdr_set_elevations_host(mca_hip_mvdr_ctx *c, int n_streams, const float *elev_rad)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = elevations_ready(c, n_streams, elev_rad)) return rc;
+    const int S = c->max_sources;
+    const float half_pi_f = 1.57079637f;                        // (float) pi/2: the largest float the call accepts
+    for (int e = 0; e < n_streams * S; ++e)
+        if (!std::isnan(elev_rad[e]) && !(std::fabs(elev_rad[e]) <= half_pi_f))
+            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "an elevation must be NaN (the context's) or within [-pi/2, pi/2]");
+    // the pairs with the host functions of mca_hip_mvdr_set_geometry; a NaN takes the context's pair, bit for bit
+    const double ce = std::cos(c->geo_elevation), se = std::sin(c->geo_elevation);
+    std::vector<double2> pairs((size_t)n_streams * S);
+    for (size_t e = 0; e < pairs.size(); ++e) {
+        const double eps = std::min(std::max((double)elev_rad[e], -M_PI / 2), M_PI / 2);
+        pairs[e] = std::isnan(elev_rad[e]) ? make_double2(ce, se) : make_double2(std::cos(eps), std::sin(eps));
+    }
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the pairs that change here
+    VHIP_TRY(c, hipMemcpy2D(c->d_slot_el, MCA_MAX_SOURCES * sizeof(double2), pairs.data(), S * sizeof(double2), S * sizeof(double2), (size_t)n_streams, hipMemcpyHostToDevice));
+    VHIP_TRY(c, hipMemcpy2D(c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), elev_rad, S * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyHostToDevice));
+    elevations_disable_tracks(c);
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_set_elevations_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *elev_rad, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = elevations_ready(c, n_streams, elev_rad)) return rc;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrElevationsArgs ea{elev_rad, c->d_slot_el, c->d_slot_val, n_streams * c->max_sources, c->max_sources, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
+    hipLaunchKernelGGL(k_mvdr_elevations, dim3((unsigned)((ea.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ea);
+    VHIP_TRY(c, hipGetLastError());
+    elevations_disable_tracks(c);
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_get_elevations(mca_hip_mvdr_ctx *c, int n_streams, float *elev_rad)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = elevations_ready(c, n_streams, elev_rad)) return rc;
+    const int S = c->max_sources;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    VHIP_TRY(c, hipDeviceSynchronize());
+    VHIP_TRY(c, hipMemcpy2D(elev_rad, S * sizeof(float), c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
 // ---- tracks of the look directions (kernels_mvdr_track.hip) ----
 extern "C++" {
 namespace {
@@ -1176,6 +1411,7 @@ int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks
     VHIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
     VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
     VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
+    if (cfg->enable == 1) VHIP_TRY(c, reset_elevations(c));   // the tracks live at the context's elevation: every slot back to unset
     c->trk = *cfg; c->trk_on = cfg->enable == 1;
     c->trk_ever = true;
     return MCA_HIP_OK;
@@ -1421,10 +1657,14 @@ int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa
     VHIP_TRY(c, hipDeviceSynchronize());
     // the factored phasors of the look direction, as the analysis forms them (MvdrAnalyseArgs::T), the phase in double
     const int M = c->M, K = c->K, nhi = c->N / 64 + 1, nph = nhi + 32;
+    // (XYZ mode: at the elevation of the slot, mca_hip_mvdr_set_elevations_*)
+    const bool xyz = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ;
+    double2 el = make_double2(1.0, 0.0);
+    if (xyz) VHIP_TRY(c, hipMemcpy(&el, c->d_slot_el + (size_t)s * MCA_MAX_SOURCES + source, sizeof(double2), hipMemcpyDeviceToHost));
     std::vector<float2> T((size_t)M * nph);
     for (int m = 0; m < M; ++m)
         for (int e = 0; e < nph; ++e) {
-            double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * host_projection(c, m, doa_rad);
+            double t = (e < nhi ? 32.0 * e : (double)(e - nhi)) * (xyz ? host_projection_xyz(c, m, doa_rad, el.x, el.y) : host_projection(c, m, doa_rad));
             t -= std::rint(t);
             T[(size_t)m * nph + e] = make_float2((float)std::cos(2.0 * M_PI * t), (float)(-std::sin(2.0 * M_PI * t)));
         }
@@ -1535,8 +1775,8 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id > 7 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever) ||
-        (kernel_id == 7 && !c->trk_ever))
+    if (!c || kernel_id < 0 || kernel_id > 8 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever) ||
+        (kernel_id == 7 && !c->trk_ever) || (kernel_id == 8 && !c->map_ever))
         return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));

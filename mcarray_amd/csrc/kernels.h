@@ -96,6 +96,9 @@ __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                        
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance
 __global__ void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs p);
+const void *mvdr_map_scan_kernel(int Q);                                         // the azimuth x elevation Capon map (kernels_mvdr_map.hip)
+__global__ void k_mvdr_map_pick(MvdrMapPickArgs p);
+__global__ void k_mvdr_elevations(MvdrElevationsArgs p);                                    // the pairs of MvdrGeometry::slot_el (kernels_mvdr_map.hip)
 __global__ void k_mvdr_track_tables(MvdrTrackTablesArgs p);                                 // tracks of the look directions (kernels_mvdr_track.hip)
 template <int Q> __global__ void k_mvdr_track_spectrum(MvdrTrackSpectrumArgs p);
 const void *mvdr_track_spectrum_kernel(int Q);

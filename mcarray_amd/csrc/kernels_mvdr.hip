@@ -35,11 +35,12 @@ __device__ __forceinline__ void mvdr_steering_tables(const MvdrAnalyseArgs &p, i
         const long long o = ((long long)a * p.n_frames + f) * p.S + s;
         const double cd = cos((double)p.doa_rad[o] + 1.57079632679489661923);   // cos(DOA + M_PI/2), Beamformer.cpp:59
         const double cy = p.geo.xyz ? -cos((double)p.doa_rad[o]) : 0.0;          // XYZ arm (MvdrGeometry): the y term's cosine
+        const double2 el = p.geo.xyz ? p.geo.slot_el[a * MCA_MAX_SOURCES + s] : make_double2(1.0, 0.0);   // and the slot's elevation
         float2 *T = p.T + o * p.M * nph;
         for (int e = tid; e < p.M * nph; e += nthr) {
             const int m = e / nph, i = e - m * nph;
             const int kk = i < nhi ? (i << 5) : i - nhi;
-            double turns = (double)kk * (p.geo.xyz ? mvdr_projection(p.geo, p.M, m, cd, cy) : p.unit * p.mic_x[m] * cd);
+            double turns = (double)kk * (p.geo.xyz ? mvdr_projection(p.geo, p.M, m, cd, cy, el.x, el.y) : p.unit * p.mic_x[m] * cd);
             turns -= rint(turns);
             float sn, cs;
             sincospif(2.0f * (float)turns, &sn, &cs);

@@ -1581,10 +1581,12 @@ __global__ __launch_bounds__(512) void k_mvdr_analyse_512(MvdrAnalyseArgs p, int
         const int nhi = (512 >> 6) + 1, nph = nhi + 32;
         for (int e = tid; e < (f_end - f_begin) * p.S * M * nph; e += 512) {                  // rows (frame, look direction)
             const int rem = e % (M * nph), m = rem / nph, i = rem - m * nph;
-            const long long o = ((long long)a * p.n_frames + f_begin) * p.S + e / (M * nph);
+            const int row = e / (M * nph);
+            const long long o = ((long long)a * p.n_frames + f_begin) * p.S + row;
+            const double2 el = p.geo.xyz ? p.geo.slot_el[a * MCA_MAX_SOURCES + row % p.S] : make_double2(1.0, 0.0);   // the slot's elevation
             const double cd = cos((double)p.doa_rad[o] + 1.57079632679489661923);   // cos(DOA + M_PI/2), Beamformer.cpp:59
             const int kk = i < nhi ? (i << 5) : i - nhi;
-            double turns = (double)kk * (p.geo.xyz ? mvdr_projection(p.geo, M, m, cd, -cos((double)p.doa_rad[o])) : p.unit * p.mic_x[m] * cd);
+            double turns = (double)kk * (p.geo.xyz ? mvdr_projection(p.geo, M, m, cd, -cos((double)p.doa_rad[o]), el.x, el.y) : p.unit * p.mic_x[m] * cd);
             turns -= rint(turns);
             float sn, cs;
             sincospif(2.0f * (float)turns, &sn, &cs);

@@ -471,18 +471,33 @@ struct MbSummaryArgs {
 struct MvdrGeometry {
     int xyz;
     const double *u;          // [3][M]: unit * x_m, unit * y_m, unit * z_m (products formed on the host, in double)
-    double ce, se;            // cos eps, sin eps
+    double ce, se;            // cos eps, sin eps of the context: the tracks and the spectrum
+    // (cos eps, sin eps) per stream and look-direction slot, stride MCA_MAX_SOURCES (mca_hip_mvdr_set_elevations_*): what the steering
+    // tables of the frames calls read in place of ce, se.  A slot that is unset holds the context's pair, bit for bit
+    const double2 *slot_el;
 };
 // cd = cos((double)theta + pi/2), the x term's spelling in both modes; cy = -cos((double)theta).  A coordinate that is 0 adds no
 // term at all, so an array on the x axis with eps = 0 (ce = 1) gives (unit x_m) * cd: the bytes of the x-only arm, signed zeros included
-__device__ __forceinline__ double mvdr_projection(const MvdrGeometry &g, int M, int m, double cd, double cy)
+__device__ __forceinline__ double mvdr_projection(const MvdrGeometry &g, int M, int m, double cd, double cy, double ce, double se)
 {
     const double ux = g.u[m], uy = g.u[M + m], uz = g.u[2 * M + m];
-    double pr = ux * (cd * g.ce);
-    if (uy != 0.0) pr += uy * (cy * g.ce);
-    if (uz != 0.0) pr -= uz * g.se;
+    double pr = ux * (cd * ce);
+    if (uy != 0.0) pr += uy * (cy * ce);
+    if (uz != 0.0) pr -= uz * se;
     return pr;
 }
+__device__ __forceinline__ double mvdr_projection(const MvdrGeometry &g, int M, int m, double cd, double cy)
+{
+    return mvdr_projection(g, M, m, cd, cy, g.ce, g.se);
+}
+// k_mvdr_elevations: the pairs of MvdrGeometry::slot_el from angles on the device (mca_hip_mvdr_set_elevations_dev)
+struct MvdrElevationsArgs {
+    const float *elev;        // [streams][max_sources] radians; NaN: the context's elevation
+    double2 *slot_el;         // [streams][MCA_MAX_SOURCES]
+    float *slot_val;          // [streams][MCA_MAX_SOURCES] what mca_hip_mvdr_get_elevations reports: NaN, or the clamped angle
+    int n, max_sources;       // n = streams * max_sources
+    double ce, se;            // the context's pair
+};
 
 // Angles on the circle (XYZ mode; the normative text is include/mcarray_hip.h, mca_hip_mvdr_set_geometry).  All float32, every step one
 // rounded operation or an explicit fmaf, so that contraction cannot change a bit.
@@ -675,6 +690,26 @@ struct MvdrSpectrumPickArgs {
     int circular;             // XYZ mode: the grid is periodic, the neighbours of i are (i - 1) mod D and (i + 1) mod D
     float *spectrum;          // [streams][D] or NULL
     float *peak_doa, *peak_val;   // [streams][n_peaks] or NULL
+};
+
+// k_mvdr_map_scan<Q> / k_mvdr_map_pick (kernels_mvdr_map.hip): the same quantity on a grid of azimuths x elevations,
+// the directions as one flat list d = j n_az + i.  A workgroup takes one (stream, chunk of 64 bins, tile of MVDR_MAP_TILE directions):
+// two directions per lane, the one register shape of the scan that k_mvdr_spectrum<Q> runs at two workgroups per CU.  The partial sums
+// have the layout of MvdrSpectrumArgs::part, and the pick kernel adds them in the same (chunk, wave) order.
+constexpr int MVDR_MAP_TILE = 128;
+constexpr int MVDR_MAP_MAX_DIRS = 2048;
+struct MvdrMapScanArgs {
+    MvdrSpectrumArgs s;       // phi, trace and part of the first stream of the pass; T, D, Dpad of the flat list of directions
+    int n_tiles;              // ceil(Dpad / MVDR_MAP_TILE)
+    int n_streams;            // streams of the pass; blockIdx.x = (chunk n_tiles + tile) n_streams + stream, the stream fastest
+};
+struct MvdrMapPickArgs {
+    const float *part;        // [streams][n_slices][Dpad]
+    const float *az, *el;     // [n_az] (float) theta_i, [n_el] (float) eps_j
+    int n_slices, n_az, n_el, Dpad, n_peaks;
+    float ctx_el;             // (float) eps of the context: the elevation of every slot of a stream without a local maximum
+    float *map;               // [streams][n_el][n_az] or NULL
+    float *peak_az, *peak_el, *peak_val;   // [streams][n_peaks] or NULL
 };
 
 // ---- tracks of the look directions, updated on the device between chunks (kernels_mvdr_track.hip) ----
