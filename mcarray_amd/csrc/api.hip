@@ -31,8 +31,6 @@ struct TimedEvent { int id; hipEvent_t a, b; };
 
 struct mca_hip_graph;
 
-#define MCA_MAX_LANES 1
-
 // ---- switches --------------------------------------------------------------------------------------------------------------
 // Read ONCE, by mca_hip_create, into the context: nothing on a call path reads the environment.  The product switches are fields of
 // mca_hip_config (adaptive_fallback, adaptive_min_rows, adaptive_max_sources, scan_carry) with an environment override for tests and
@@ -62,32 +60,24 @@ constexpr int REPICK_GRID = 256;      // workgroups of k_scan_repick
 
 // Per-call workspace (everything a stream call allocates besides the per-array state, which lives in the context).  A call
 // can be worked off in pieces over a sub-range of its arrays -- the chunks of the host-pointer path -- with the per-array
-// state addressed at c->a0.  (Round 2 also split large device-pointer calls over 2-4 internal streams, "lanes"; measured 7 %
-// slower with two and 57 % slower with three on the bench shape, HISTORY.md, so that code is gone.)
+// state addressed at c->a0.  Every buffer grows on its own need (grow_ws, the one place that reallocates) and its n is its capacity.
 struct Workspace {
-    void *d_A = nullptr; size_t a_bytes = 0;          // A operand: [rows][a_row_elems]
-    void *d_Ax = nullptr; size_t ax_bytes = 0;        // ADAPTIVE: the two-plane A rows (repair pass, FP16X3 calls)
-    float *d_C = nullptr; size_t c_bytes = 0;         // correlation map
+    DevBuf<unsigned char> d_A;                        // A operand: [rows][a_row_elems], in bytes (the element is the precision's)
+    DevBuf<unsigned char> d_Ax;                       // ADAPTIVE: the two-plane A rows (repair pass, FP16X3 calls)
+    DevBuf<float> d_C;                                // correlation map
     int c_planes = 1;                                 // partial maps (split-K) the last contraction left in d_C
     bool partial_done = false;                        // the last contraction also left the scan's chunk-local results (d_part, d_nv)
     int part_planes = 1;                              // ... one set per K half of a split-K launch
     long long c_plane = 0;
-    float *d_Cx = nullptr; size_t cx_bytes = 0;       // ADAPTIVE: partial maps of the repair contraction
+    DevBuf<float> d_Cx;                               // ADAPTIVE: partial maps of the repair contraction
     // exact chunked scan + power gate
-    float *d_part = nullptr, *d_estart = nullptr; int *d_nv = nullptr; size_t scan_ws_chunks = 0;
-    float *d_power = nullptr; unsigned char *d_voiced = nullptr; float *d_power_out = nullptr; size_t gate_frames = 0;
+    DevBuf<float> d_part, d_estart; DevBuf<int> d_nv;
+    DevBuf<float> d_power, d_power_out; DevBuf<unsigned char> d_voiced;
     // ADAPTIVE: flags, repair list
-    unsigned char *d_flags = nullptr; int *d_chunk_from = nullptr, *d_list = nullptr, *d_need = nullptr; unsigned *d_umask = nullptr; size_t adapt_frames = 0, adapt_chunks = 0, adapt_groups = 0;
-    unsigned char *d_unsure = nullptr;                // 16 microphones: frames whose DC / Nyquist bin the coarse analysis could not vouch for (StftPhatArgs::unsure)
-    int *d_nlist = nullptr, *d_last_vchunk = nullptr; size_t lastv_arrays = 0;
-    int last_a0 = 0, last_arrays = 0;                 // the arrays this lane ran in the last call (mca_hip_copy_gate)
-    void release()
-    {
-        auto F = [](void *q) { if (q) (void)hipFree(q); };
-        F(d_A); F(d_Ax); F(d_C); F(d_Cx); F(d_part); F(d_estart); F(d_nv); F(d_power); F(d_voiced); F(d_power_out);
-        F(d_flags); F(d_chunk_from); F(d_list); F(d_need); F(d_umask); F(d_nlist); F(d_last_vchunk); F(d_unsure);
-        *this = Workspace();
-    }
+    DevBuf<unsigned char> d_flags; DevBuf<int> d_list, d_need; DevBuf<unsigned> d_umask;
+    DevBuf<int> d_chunk_from;                         // [2][chunks]: the first flagged frame per chunk, then the list of the chunks that hold one (at n / 2)
+    DevBuf<unsigned char> d_unsure;                   // 16 microphones: frames whose DC / Nyquist bin the coarse analysis could not vouch for (StftPhatArgs::unsure)
+    DevBuf<int> d_nlist, d_last_vchunk;
 };
 
 // FreqGCCBinauralLocalisation::processParametrisation (mca_hip_gcc2_process_frame): the scalars of BinauralLocalisation.cpp:320-404
@@ -112,26 +102,26 @@ struct mca_hip_ctx {
     std::vector<float> delays, grid;
     std::vector<int2> pairs;
     // device tables
-    float *d_window = nullptr, *d_grid = nullptr, *d_delays = nullptr;
-    float2 *d_tw = nullptr;       // [N/2] exp(-j 2 pi i / N), any-N kernels
-    double *d_micx = nullptr;
-    int2 *d_pairs = nullptr;
-    void *d_B = nullptr, *d_Bt = nullptr;
+    DevBuf<float> d_window, d_grid, d_delays;
+    DevBuf<float2> d_tw;          // [N/2] exp(-j 2 pi i / N), any-N kernels
+    DevBuf<double> d_micx;
+    DevBuf<int2> d_pairs;
+    DevBuf<unsigned char> d_B, d_Bt;      // (in bytes: float or fp16 by the precision, like the merged and folded tables below)
     // ULA, one fp16 operand plane (the ADAPTIVE coarse pass, plain FP16), k_stft_phat_wave: the contraction index is the PRODUCT
     // m = k * (j - i) -- pairs of spacing g at bin k steer with exp(j 2 pi k g tau_1 / N), so all (k, g) of equal product share one
     // steering column and their PHAT sums are merged before the contraction: 1 962 instead of 3 591 complex terms per row for 8
     // microphones (build_merged_tables)
     bool merged = false; int n_merged = 0, Kp_m = 0;
-    void *d_Bm = nullptr, *d_Btm = nullptr; unsigned short *d_mrank = nullptr;
+    DevBuf<unsigned char> d_Bm, d_Btm; DevBuf<unsigned short> d_mrank;
     // ... folded about broadside (fold_table.h): the merged rows are planar ([R | I]), d_Bm / d_Btm hold the folded values at full width in
     // planar K order, and d_Bfold the even and the odd half-width tables of k_srp_gemm_f16_fold: [2][Kp_m / 64][192][32]
-    bool fold = false; void *d_Bfold = nullptr;
-    float2 *d_bftab = nullptr; int bf_pairs = 0;   // k_beamform_wave: steering rows per grid angle, [D + 1][bf_pairs][1024] (built on first use)
+    bool fold = false; DevBuf<unsigned char> d_Bfold;
+    DevBuf<float2> d_bftab; int bf_pairs = 0;   // k_beamform_wave: steering rows per grid angle, [D + 1][bf_pairs][1024] (built on first use)
     // Delay-and-sum on the half spectrum (steer.h; steer_applies): the per-channel steering table, the predicted bin per array (the last pick of
     // the previous call; -1 on a new stream), the running miss total, the rows of Y (grown on demand) and two carries between frame passes
-    float4 *d_steer_rows = nullptr; float2 *d_steer_q = nullptr; float *d_steer_nyq = nullptr; int *d_steer_pred = nullptr; unsigned long long *d_steer_miss = nullptr;
-    float2 *d_steer_Y = nullptr; size_t steer_Y_rows = 0; float *d_steer_tail = nullptr;
-    int *d_steer_mlist = nullptr;                           // the miss list of the patching second pick (ScanPickArgs::n_miss): [0] its length, then steer_Y_rows entries
+    DevBuf<float4> d_steer_rows; DevBuf<float2> d_steer_q; DevBuf<float> d_steer_nyq; DevBuf<int> d_steer_pred; DevBuf<unsigned long long> d_steer_miss;
+    DevBuf<float2> d_steer_Y; DevBuf<float> d_steer_tail;
+    DevBuf<int> d_steer_mlist;                              // the miss list of the patching second pick (ScanPickArgs::n_miss): [0] its length, then an entry per row of Y
     bool steer_now = false, steer_fused_now = false;        // this call: the analysis may steer ahead (Y holds the whole call) / did
     bool steer_mlist_dirty = false;                         // misses were listed by a call whose synthesis (which empties the list) has not been enqueued
     bool steer_patched_now = false;                         // this call: the second pick patches the missed frames (no k_steer_patch launch)
@@ -143,45 +133,43 @@ struct mca_hip_ctx {
     unsigned long long steer_seq = 0, steer_seq_seen = 0, steer_call_frames[FB_RING] = {};
     bool steer_spec = true, steer_lost = false;
     // stream state (double buffered: kernels read [cur], write [cur^1])
-    float *d_E[2] = {nullptr, nullptr};
-    float *d_tail[2] = {nullptr, nullptr};
+    DevBuf<float> d_E[2];
+    DevBuf<float> d_tail[2];
     int e_cur = 0, tail_cur = 0;
-    Workspace lanes[MCA_MAX_LANES];
-    int cur_lane = 0, a0 = 0;              // the workspace in use and the first array of the piece being enqueued (host side, sequential)
+    Workspace ws;
+    int a0 = 0;                            // the first array of the piece being enqueued (host side, sequential)
     long long plan_rows = 0;               // > 0: rows of the whole call while it is worked off in pieces (plan_gemm)
     int plan_arrays = 0;                   // ... and its arrays (repair_ksplit_for)
-    int n_lanes_last = 1;
     hipStream_t io_stream[3] = {}; hipEvent_t io_ev[8] = {};   // host-pointer entry points with page-locked buffers: copy in / run / copy out
-    Workspace &ws() { return lanes[cur_lane]; }
-    double *d_gate_state = nullptr;
-    int *d_last_bin = nullptr; float *d_last_rad = nullptr, *d_last_prob = nullptr;
-    int last_arrays = 0, last_frames = 0;
-    float *d_doa[2] = {nullptr, nullptr};   // 2-mic path: smoothed _currentDOA per array
+    DevBuf<double> d_gate_state;
+    DevBuf<int> d_last_bin; DevBuf<float> d_last_rad, d_last_prob;
+    int last_arrays = 0, last_frames = 0;   // the shape of the last stream call that succeeded (mca_hip_copy_gate)
+    DevBuf<float> d_doa[2];                 // 2-mic path: smoothed _currentDOA per array
     int doa_cur = 0;
     long long gcc2_frames_done = 0;         // (kept in the state header for blob compatibility; the counters below are what runs)
-    long long *d_vdone[2] = {nullptr, nullptr};   // 2-mic path: frames that fired so far, per array (double-buffered with d_doa)
-    int *d_g2_vidx = nullptr, *d_g2_nv = nullptr; float *d_g2_rad = nullptr, *d_g2_prob = nullptr; size_t g2_rows = 0;   // gated 2-mic path
-    unsigned char *d_g2_reset = nullptr;    // [rows] per fired frame: the memory factors are zero (silence rule)
-    int *d_g2_post0 = nullptr;              // [max_arrays] first frame of the call at which the floor estimate exists
-    int *d_silence = nullptr;               // [max_arrays] _silenceFramesCounter (BinauralLocalisation.cpp:326), stream state
+    DevBuf<long long> d_vdone[2];           // 2-mic path: frames that fired so far, per array (double-buffered with d_doa)
+    DevBuf<int> d_g2_vidx, d_g2_nv; DevBuf<float> d_g2_rad, d_g2_prob;   // gated 2-mic path: workspaces of [rows], d_g2_nv [max_arrays]
+    DevBuf<unsigned char> d_g2_reset;       // [rows] per fired frame: the memory factors are zero (silence rule)
+    DevBuf<int> d_g2_post0;                 // [max_arrays] first frame of the call at which the floor estimate exists
+    DevBuf<int> d_silence;                  // [max_arrays] _silenceFramesCounter (BinauralLocalisation.cpp:326), stream state
     // the DOA tracker (mca_hip_gcc2_tracker_attach; kernels_gcc2_track.hip): slots 0 .. max_arrays - 1 belong to the stream state,
     // slot max_arrays to the frame hook
     bool tracked = false;
     mca_hip_gcc2_tracker_config trk{};      // as resolved by attach (no zeros left)
-    double *d_trk_x = nullptr, *d_trk_sd = nullptr; int *d_trk_si = nullptr;   // [slots][N] particles, [slots][2] DOA / prob, [slots][4] alive / track / upd
-    int *d_trk_sil = nullptr;               // [max_arrays] the silence counters before the call (k_gcc2_compact overwrites d_silence)
-    float *d_trk_corr = nullptr; int *d_trk_idx = nullptr; size_t trk_rows = 0;   // the rows / argmaxes of a call whose caller did not ask for them
-    double *d_trk_res = nullptr;            // [4] what the frame hook's launch returns: DOA, prob, fired (the first byte of [2]), track (an int in [3])
+    DevBuf<double> d_trk_x, d_trk_sd; DevBuf<int> d_trk_si;   // [slots][N] particles, [slots][2] DOA / prob, [slots][4] alive / track / upd
+    DevBuf<int> d_trk_sil;                  // [max_arrays] the silence counters before the call (k_gcc2_compact overwrites d_silence)
+    DevBuf<float> d_trk_corr; DevBuf<int> d_trk_idx;   // workspaces: the rows / argmaxes of a call whose caller did not ask for them
+    DevBuf<double> d_trk_res;               // [4] what the frame hook's launch returns: DOA, prob, fired (the first byte of [2]), track (an int in [3])
     // workspace
-    unsigned long long ws_gen = 0;          // bumped whenever a workspace buffer is reallocated: recorded graphs hold the old pointers
+    unsigned long long ws_gen = 0;          // bumped by grow_ws, and by nothing else, whenever a workspace buffer is reallocated: recorded graphs hold the old pointers
     std::vector<mca_hip_graph *> graphs;   // live graphs of this context (orphaned by mca_hip_destroy)
     // adaptive SRP precision: fp16 coarse scan (one plane) + exact repair (hi + lo planes)
     int tab_planes = 1;            // planes of the steering tables (2: FP16X3 and ADAPTIVE)
-    unsigned long long *d_rstats = nullptr;
+    DevBuf<unsigned long long> d_rstats;
     // lazy tails (mca_internal.h, HIST_FRAMES): what the last lazy adaptive call left for the next one, double buffered like d_E
-    float *d_hist_pcm[2] = {nullptr, nullptr};     // [max_arrays][M][HIST_SAMPLES]
-    float *d_hist_C[2] = {nullptr, nullptr};       // [max_arrays][HIST_FRAMES][Dp] coarse rows (patched where a repair pass recomputed them)
-    float *d_ehist[2] = {nullptr, nullptr};        // [max_arrays][D] the energies in front of them
+    DevBuf<float> d_hist_pcm[2];                   // [max_arrays][M][HIST_SAMPLES]
+    DevBuf<float> d_hist_C[2];                     // [max_arrays][HIST_FRAMES][Dp] coarse rows (patched where a repair pass recomputed them)
+    DevBuf<float> d_ehist[2];                      // [max_arrays][D] the energies in front of them
     int hist_cur = 0, hist_n = 0;                  // the buffers that hold the pending history, the arrays it covers
     bool hist_pending = false;                     // the state in d_E is coarse: exact = settle_history, or the next lazy call's own repair pass
     bool lazy_now = false;                         // (localise_impl) this call leaves its tails to the next: the coarse analysis keeps the PCM
@@ -207,14 +195,14 @@ struct mca_hip_ctx {
     bool fb_lost = false;                               // a report did not arrive within FB_WAIT_MS: the policy stops consuming reports (until mca_hip_reset)
     int a_row_elems = 0, a_planes = 1, a_elem = 4;
     // frame API (double)
-    double *d_fr = nullptr; size_t fr_elems = 0;
-    double *d_E64[2] = {nullptr, nullptr}; int e64_cur = 0;
-    double *d_res = nullptr;      // [S] doa, [S] prob, power
-    int *d_bins = nullptr;
-    double *d_out64 = nullptr; size_t out64_elems = 0;
+    DevBuf<double> d_fr;          // workspace: the frame's spectra [M][ccs_len]
+    DevBuf<double> d_E64[2]; int e64_cur = 0;
+    DevBuf<double> d_res;         // [S] doa, [S] prob, power
+    DevBuf<int> d_bins;
+    DevBuf<double> d_out64;       // workspace: the beamformed spectrum [ccs_len]
     // FreqGCC frame hook (double): its own smoothed correlation, apart from the stream state d_E and the steering frame state d_E64
-    double *d_g2f_corr[2] = {nullptr, nullptr}; int g2f_cur = 0;   // _prevCorrelationsReal [D], double buffered like d_E64
-    double *d_g2f_res = nullptr;                                   // [4] argmax, prob, DOA (k_frame_gcc2), linear power (k_frame_power)
+    DevBuf<double> d_g2f_corr[2]; int g2f_cur = 0;                 // _prevCorrelationsReal [D], double buffered like d_E64
+    DevBuf<double> d_g2f_res;                                      // [4] argmax, prob, DOA (k_frame_gcc2), linear power (k_frame_power)
     G2FrameState g2f;
     std::vector<double> h_stage;
     StagePool stage;              // device staging of the host-pointer entry points
@@ -259,28 +247,49 @@ double distance(const std::vector<double> &xyz, int i, int j)                   
                      std::pow(xyz[3 * j + 2] - xyz[3 * i + 2], 2));
 }
 
+// what an allocation, an upload or a fill failed with: out of memory by its own code, `what` names the buffer
+int hip_fail(mca_hip_ctx *c, hipError_t e, const char *what)
+{
+    return fail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// A workspace of at least n elements -- the one place that reallocates a buffer a call hands to kernels, and so the one place that
+// bumps ws_gen: whatever a recorded graph may have baked in is gone with the buffer (also when the allocation then fails).
+template <typename T>
+int grow_ws(mca_hip_ctx *c, DevBuf<T> &b, size_t n, const char *what)
+{
+    if (n <= b.n) return MCA_HIP_OK;
+    ++c->ws_gen;
+    const hipError_t e = b.alloc(n);
+    return e == hipSuccess ? MCA_HIP_OK : hip_fail(c, e, what);
+}
+
+// ... whose first `fill` elements start out as the byte `v` (the self-cleaning words of the adaptive path, the zero padding of the A
+// rows): filled on the null stream and waited for, since the caller's stream need not wait for the null stream by itself.  A buffer
+// that could not be filled is dropped, so that a retry starts from nothing.
+template <typename T>
+int grow_ws_filled(mca_hip_ctx *c, DevBuf<T> &b, size_t n, size_t fill, int v, const char *what)
+{
+    if (n <= b.n) return MCA_HIP_OK;
+    const int rc = grow_ws(c, b, n, what);
+    if (rc) return rc;
+    hipError_t e = hipMemset(b.p, v, fill * sizeof(T));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) return MCA_HIP_OK;
+    b.reset();
+    return hip_fail(c, e, what);
+}
+
 void free_ctx(mca_hip_ctx *c)
 {
     if (!c) return;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_tw); F(c->d_grid); F(c->d_delays); F(c->d_micx); F(c->d_pairs); F(c->d_B); F(c->d_Bt); F(c->d_bftab); F(c->d_steer_rows); F(c->d_steer_q); F(c->d_steer_nyq); F(c->d_steer_pred); F(c->d_steer_miss); F(c->d_steer_Y); F(c->d_steer_mlist); F(c->d_steer_tail); F(c->d_Bm); F(c->d_Btm); F(c->d_Bfold); F(c->d_mrank);
-    F(c->d_E[0]); F(c->d_E[1]); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_doa[0]); F(c->d_doa[1]); F(c->d_vdone[0]); F(c->d_vdone[1]); F(c->d_g2_vidx); F(c->d_g2_nv); F(c->d_g2_rad); F(c->d_g2_prob);
-    F(c->d_g2_reset); F(c->d_g2_post0); F(c->d_silence);
-    F(c->d_trk_x); F(c->d_trk_sd); F(c->d_trk_si); F(c->d_trk_sil); F(c->d_trk_corr); F(c->d_trk_idx); F(c->d_trk_res);
-    F(c->d_rstats); F(c->d_gate_state);
-    for (int i = 0; i < 2; ++i) { F(c->d_hist_pcm[i]); F(c->d_hist_C[i]); F(c->d_ehist[i]); }
     if (c->h_probe) (void)hipHostFree(c->h_probe);
     if (c->h_steer) (void)hipHostFree(c->h_steer);
-    for (Workspace &w : c->lanes) w.release();
     for (auto &e : c->io_ev) if (e) (void)hipEventDestroy(e);
     for (auto &q : c->io_stream) if (q) (void)hipStreamDestroy(q);
-    F(c->d_last_bin); F(c->d_last_rad); F(c->d_last_prob);
-    F(c->d_fr); F(c->d_E64[0]); F(c->d_E64[1]); F(c->d_res); F(c->d_bins); F(c->d_out64);
-    F(c->d_g2f_corr[0]); F(c->d_g2f_corr[1]); F(c->d_g2f_res);
-    c->stage.release();
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : c->pool) (void)hipEventDestroy(e);
-    delete c;
+    delete c;                                                  // every device buffer goes with its member
 }
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -312,18 +321,28 @@ int init_last_state(mca_hip_ctx *c, hipStream_t st)
     const size_t n = (size_t)c->cfg.max_arrays * MCA_MAX_SOURCES;
     std::vector<int> b(n, -1); std::vector<float> pr(n, -1.f);
     HIP_TRY(c, hipMemcpyAsync(c->d_last_bin, b.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->d_last_rad, 0, n * 4, st));
+    HIP_TRY(c, c->d_last_rad.zero_async(st));
     HIP_TRY(c, hipMemcpyAsync(c->d_last_prob, pr.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->d_gate_state, 0, (size_t)c->cfg.max_arrays * 4 * 8, st));
+    HIP_TRY(c, c->d_gate_state.zero_async(st));
     HIP_TRY(c, hipStreamSynchronize(st));       // (the host vectors above go out of scope; mca_hip_reset returns with nothing queued)
     return MCA_HIP_OK;
 }
 
 // steering table B of the SRP contraction = precomputeTauMatrix (SteeringBeamforming.cpp:87-88)
 // for the first pair of every delay group, laid out for the MFMA kernels.
+// a table of `bytes` bytes built on the host, into a buffer sized in bytes
+int upload_bytes(mca_hip_ctx *c, DevBuf<unsigned char> &b, const void *host, size_t bytes, const char *what)
+{
+    const hipError_t e = b.upload(static_cast<const unsigned char *>(host), bytes);
+    return e == hipSuccess ? MCA_HIP_OK : hip_fail(c, e, what);
+}
+
+// (built into locals and moved into the context behind the last upload, like build_merged_tables: a failure leaves no half of a table set)
 int build_steering_table(mca_hip_ctx *c)
 {
     const int K = c->K, D = c->D, Dp = c->Dp, Kp = c->Kp;
+    DevBuf<unsigned char> dB, dBt;
+    int rc;
     std::vector<int> first_pair(c->G);
     if (c->ula) { for (int g = 0; g < c->G; ++g) first_pair[g] = g; /* pair (0, g+1) has index g */ }
     else for (int g = 0; g < c->G; ++g) first_pair[g] = g;
@@ -338,8 +357,7 @@ int build_steering_table(mca_hip_ctx *c)
                     B[r * Dp + d] = (float)std::cos(ph);
                     B[(r + 1) * Dp + d] = (float)(-std::sin(ph));
                 }
-        HIP_TRY(c, hipMalloc(&c->d_B, B.size() * sizeof(float)));
-        HIP_TRY(c, hipMemcpy(c->d_B, B.data(), B.size() * sizeof(float), hipMemcpyHostToDevice));
+        if ((rc = upload_bytes(c, dB, B.data(), B.size() * sizeof(float), "the steering table"))) return rc;
     } else {
         const int planes = c->tab_planes;
         std::vector<_Float16> B((size_t)planes * Dp * Kp, (_Float16)0.f);
@@ -355,8 +373,7 @@ int build_steering_table(mca_hip_ctx *c)
                         if (planes == 2) B[((size_t)Dp + d) * Kp + kk] = (_Float16)(v[q] - (float)hi);
                     }
                 }
-        HIP_TRY(c, hipMalloc(&c->d_B, B.size() * sizeof(_Float16)));
-        HIP_TRY(c, hipMemcpy(c->d_B, B.data(), B.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        if ((rc = upload_bytes(c, dB, B.data(), B.size() * sizeof(_Float16), "the steering table"))) return rc;
         if (Dp == 384) {
             // the same table tiled for the 256 x 384 kernel: one 32-deep K stage of all 384 columns is 24 KiB
             // contiguous, so every LDS-DMA instruction of that kernel moves one contiguous KiB
@@ -366,10 +383,10 @@ int build_steering_table(mca_hip_ctx *c)
                 for (int sl = 0; sl < ns32; ++sl)
                     for (int d = 0; d < Dp; ++d)
                         std::memcpy(&Bt[(((size_t)pl * ns32 + sl) * Dp + d) * 32], &B[((size_t)pl * Dp + d) * Kp + (size_t)sl * 32], 32 * sizeof(_Float16));
-            HIP_TRY(c, hipMalloc(&c->d_Bt, Bt.size() * sizeof(_Float16)));
-            HIP_TRY(c, hipMemcpy(c->d_Bt, Bt.data(), Bt.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+            if ((rc = upload_bytes(c, dBt, Bt.data(), Bt.size() * sizeof(_Float16), "the tiled steering table"))) return rc;
         }
     }
+    c->d_B.swap(dB); c->d_Bt.swap(dBt);
     return MCA_HIP_OK;
 }
 
@@ -383,7 +400,6 @@ int cur_kp(const mca_hip_ctx *c) { return (c->merged && c->a_planes == 1) ? c->K
 // paths (FP32, FP16X3, the repair pass) keep the per-group index and the reference's own tables.
 int build_merged_tables(mca_hip_ctx *c)
 {
-    c->merged = false;
     // (round 6: also at 2048-sample frames, k_stft_phat_2048<..., MERGE>)
     if (!c->ula || (c->generic && !c->n2048) || c->n512 || (c->M != 4 && c->M != 8) || c->Dp % 64 != 0) return MCA_HIP_OK;
     if (c->prec != MCA_HIP_SRP_ADAPTIVE && c->prec != MCA_HIP_SRP_FP16) return MCA_HIP_OK;
@@ -395,45 +411,43 @@ int build_merged_tables(mca_hip_ctx *c)
     std::vector<unsigned short> rank;
     std::vector<int> ms;
     merged_products(G, K, rank, ms);
-    c->n_merged = (int)ms.size();
-    c->Kp_m = round_up(2 * ((c->n_merged + 63) & ~63), 32);       // (whole wave rows: the analysis kernel stores its LDS region as it stands, zeros behind n_merged)
-    const int Kp = c->Kp_m;
-    c->fold = fold_applies(true, c->N, FFT_N, D, Dp, c->delays.data());
-    if (c->fold) {
+    const int n_merged = (int)ms.size();
+    const int Kp = round_up(2 * ((n_merged + 63) & ~63), 32);       // (whole wave rows: the analysis kernel stores its LDS region as it stands, zeros behind n_merged)
+    const bool fold = fold_applies(true, c->N, FFT_N, D, Dp, c->delays.data());
+    DevBuf<unsigned char> dBm, dBtm, dBfold; DevBuf<unsigned short> dmrank;
+    int rc;
+    if (fold) {
         // mirror fold (fold_table.h): planar rows, the folded values at full width for the kernels that keep it, the two half-width tables
         FoldTables ft;
-        build_fold_tables(c->delays.data(), D, Dp, ms.data(), c->n_merged, Kp, c->N, ft);
-        auto up16 = [&](void **dst, const std::vector<uint16_t> &v, size_t at, size_t total) {
-            if (!*dst) HIP_TRY(c, hipMalloc(dst, total * 2));
-            HIP_TRY(c, hipMemcpy((char *)*dst + at * 2, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-            return (int)MCA_HIP_OK;
-        };
-        int rc;
-        if ((rc = up16(&c->d_Bm, ft.full, 0, ft.full.size())) || (rc = up16(&c->d_Btm, ft.full_tiled, 0, ft.full_tiled.size())) ||
-            (rc = up16(&c->d_Bfold, ft.even, 0, 2 * ft.even.size())) || (rc = up16(&c->d_Bfold, ft.odd, ft.even.size(), 2 * ft.even.size()))) return rc;
+        build_fold_tables(c->delays.data(), D, Dp, ms.data(), n_merged, Kp, c->N, ft);
+        ft.even.insert(ft.even.end(), ft.odd.begin(), ft.odd.end());      // [even | odd]
+        if ((rc = upload_bytes(c, dBm, ft.full.data(), ft.full.size() * 2, "the folded steering table")) ||
+            (rc = upload_bytes(c, dBtm, ft.full_tiled.data(), ft.full_tiled.size() * 2, "the tiled folded steering table")) ||
+            (rc = upload_bytes(c, dBfold, ft.even.data(), ft.even.size() * 2, "the half-width steering tables"))) return rc;
     } else {
     std::vector<_Float16> B((size_t)Dp * Kp, (_Float16)0.f);
     for (int d = 0; d < D; ++d)
-        for (int r = 0; r < c->n_merged; ++r) {
+        for (int r = 0; r < n_merged; ++r) {
             const double ph = 2.0 * M_PI * (double)ms[(size_t)r] * (double)c->delays[d] / N;
             B[(size_t)d * Kp + 2 * r] = (_Float16)(float)std::cos(ph);
             B[(size_t)d * Kp + 2 * r + 1] = (_Float16)(float)(-std::sin(ph));
         }
-    HIP_TRY(c, hipMalloc(&c->d_Bm, B.size() * sizeof(_Float16)));
-    HIP_TRY(c, hipMemcpy(c->d_Bm, B.data(), B.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    if ((rc = upload_bytes(c, dBm, B.data(), B.size() * sizeof(_Float16), "the merged steering table"))) return rc;
     if (Dp == 384) {
         const int ns32 = Kp / 32;
         std::vector<_Float16> Bt(B.size());
         for (int sl = 0; sl < ns32; ++sl)
             for (int d = 0; d < Dp; ++d)
                 std::memcpy(&Bt[((size_t)sl * Dp + d) * 32], &B[(size_t)d * Kp + (size_t)sl * 32], 32 * sizeof(_Float16));
-        HIP_TRY(c, hipMalloc(&c->d_Btm, Bt.size() * sizeof(_Float16)));
-        HIP_TRY(c, hipMemcpy(c->d_Btm, Bt.data(), Bt.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        if ((rc = upload_bytes(c, dBtm, Bt.data(), Bt.size() * sizeof(_Float16), "the tiled merged steering table"))) return rc;
     }
     }
     rank.resize((rank.size() + 3) / 4 * 4, 0xffff);
-    HIP_TRY(c, hipMalloc((void **)&c->d_mrank, rank.size() * sizeof(unsigned short)));
-    HIP_TRY(c, hipMemcpy(c->d_mrank, rank.data(), rank.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+    const hipError_t e = dmrank.upload(rank.data(), rank.size());
+    if (e != hipSuccess) return hip_fail(c, e, "the ranks of the merged index");
+    // the last upload has succeeded: only now does the context change
+    c->d_Bm.swap(dBm); c->d_Btm.swap(dBtm); c->d_Bfold.swap(dBfold); c->d_mrank.swap(dmrank);
+    c->n_merged = n_merged; c->Kp_m = Kp; c->fold = fold;
     c->merged = true;
     c->a_row_elems = cur_kp(c) * c->a_planes;
     return MCA_HIP_OK;
@@ -504,23 +518,13 @@ GemmPlan plan_gemm(const mca_hip_ctx *c, long long rows)
 
 // the A buffer of the current call: an ADAPTIVE context keeps its two-plane rows (repair pass, FP16X3 calls) apart from the
 // one-plane rows of the coarse pass, so that a buffer only ever sees one row layout (its Kp padding columns stay zero)
-void *&a_buf(mca_hip_ctx *c) { return (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 2) ? c->ws().d_Ax : c->ws().d_A; }
-size_t &a_buf_bytes(mca_hip_ctx *c) { return (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 2) ? c->ws().ax_bytes : c->ws().a_bytes; }
+DevBuf<unsigned char> &a_buf(mca_hip_ctx *c) { return (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 2) ? c->ws.d_Ax : c->ws.d_A; }
 
 int ensure_a(mca_hip_ctx *c, long long rows)
 {
     // rows rounded up to the 256-row tile of the split-K MFMA kernel, which loads whole tiles unclamped
-    size_t need_a = (size_t)((rows + 255) / 256 * 256) * c->a_row_elems * c->a_elem;
-    void *&buf = a_buf(c); size_t &bytes = a_buf_bytes(c);
-    if (need_a > bytes) {
-        if (buf) (void)hipFree(buf);
-        buf = nullptr; bytes = 0;
-        HIP_TRY(c, hipMalloc(&buf, need_a));
-        HIP_TRY(c, hipMemset(buf, 0, need_a));          // the Kp padding columns stay zero forever
-        HIP_TRY(c, hipDeviceSynchronize());             // (the caller's stream need not wait for the null stream's memset by itself)
-        bytes = need_a; ++c->ws_gen;
-    }
-    return MCA_HIP_OK;
+    const size_t need_a = (size_t)((rows + 255) / 256 * 256) * c->a_row_elems * c->a_elem;
+    return grow_ws_filled(c, a_buf(c), need_a, need_a, 0, "the A operand");          // the Kp padding columns stay zero forever
 }
 
 int ensure_workspace(mca_hip_ctx *c, long long rows_chunk, long long rows_total)
@@ -528,40 +532,19 @@ int ensure_workspace(mca_hip_ctx *c, long long rows_chunk, long long rows_total)
     int rc_a = ensure_a(c, rows_chunk);
     if (rc_a) return rc_a;
     const int planes = std::max(2, plan_gemm(c, rows_chunk).ksplit);
-    size_t need_c = (size_t)rows_total * c->Dp * sizeof(float) * planes;   // room for the partial maps of a split-K contraction
-    if (need_c > c->ws().c_bytes) {
-        if (c->ws().d_C) (void)hipFree(c->ws().d_C);
-        c->ws().d_C = nullptr; c->ws().c_bytes = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_C, need_c));
-        c->ws().c_bytes = need_c; ++c->ws_gen;
-    }
-    return MCA_HIP_OK;
+    return grow_ws(c, c->ws.d_C, (size_t)rows_total * c->Dp * planes, "the correlation map");   // room for the partial maps of a split-K contraction
 }
 
 int ensure_scan_workspace(mca_hip_ctx *c, int n_arrays, int n_frames, int n_chunks)
 {
-    const size_t need = (size_t)n_arrays * n_chunks;
-    if (need > c->ws().scan_ws_chunks) {
-        if (c->ws().d_part) (void)hipFree(c->ws().d_part);
-        if (c->ws().d_estart) (void)hipFree(c->ws().d_estart);
-        if (c->ws().d_nv) (void)hipFree(c->ws().d_nv);
-        c->ws().d_part = c->ws().d_estart = nullptr; c->ws().d_nv = nullptr; c->ws().scan_ws_chunks = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_part, need * c->D * 4 * 2));      // (two sets when a split-K contraction leaves them)
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_estart, need * c->D * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_nv, need * 4));
-        c->ws().scan_ws_chunks = need; ++c->ws_gen;
-    }
-    const size_t nf = (size_t)n_arrays * n_frames;
-    if (c->cfg.use_power_floor && nf > c->ws().gate_frames) {
-        if (c->ws().d_power) (void)hipFree(c->ws().d_power);
-        if (c->ws().d_voiced) (void)hipFree(c->ws().d_voiced);
-        if (c->ws().d_power_out) (void)hipFree(c->ws().d_power_out);
-        c->ws().d_power = c->ws().d_power_out = nullptr; c->ws().d_voiced = nullptr; c->ws().gate_frames = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_power, nf * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_power_out, nf * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_voiced, nf));
-        c->ws().gate_frames = nf; ++c->ws_gen;
-    }
+    Workspace &w = c->ws;
+    const size_t need = (size_t)n_arrays * n_chunks, nf = (size_t)n_arrays * n_frames;
+    int rc;
+    if ((rc = grow_ws(c, w.d_part, need * c->D * 2, "the scan's chunk results")) ||      // (two sets when a split-K contraction leaves them)
+        (rc = grow_ws(c, w.d_estart, need * c->D, "the scan's chunk starts")) || (rc = grow_ws(c, w.d_nv, need, "the scan's voiced counts"))) return rc;
+    if (c->cfg.use_power_floor &&
+        ((rc = grow_ws(c, w.d_power, nf, "the gate's frame powers")) || (rc = grow_ws(c, w.d_power_out, nf, "the gate's frame powers (dB)")) ||
+         (rc = grow_ws(c, w.d_voiced, nf, "the gate's flags")))) return rc;
     return MCA_HIP_OK;
 }
 
@@ -709,65 +692,25 @@ long long repair_pass_rows(const mca_hip_ctx *c, int n_arrays, int n_frames)
 
 int ensure_adapt_workspace(mca_hip_ctx *c, int n_arrays, int n_frames, int n_chunks)
 {
+    Workspace &w = c->ws;
     const size_t nf = (size_t)n_arrays * n_frames, nc = (size_t)n_arrays * n_chunks;
     const size_t ng = (size_t)n_arrays * ((n_frames + REPAIR_GROUP - 1) / REPAIR_GROUP + HIST_UNITS);     // (+ the history units of the lazy tails)
-    if (nf > c->ws().adapt_frames) {
-        if (c->ws().d_flags) (void)hipFree(c->ws().d_flags);
-        c->ws().d_flags = nullptr; c->ws().adapt_frames = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_flags, nf));
-        if (c->ws().d_unsure) (void)hipFree(c->ws().d_unsure);
-        c->ws().d_unsure = nullptr;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_unsure, nf));
-        c->ws().adapt_frames = nf; ++c->ws_gen;
-    }
-    if (nc > c->ws().adapt_chunks) {
-        if (c->ws().d_chunk_from) (void)hipFree(c->ws().d_chunk_from);
-        c->ws().d_chunk_from = nullptr; c->ws().adapt_chunks = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_chunk_from, 2 * nc * 4));   // + the list of the chunks that hold a flagged frame
-        HIP_TRY(c, hipMemset(c->ws().d_chunk_from, 0x7f, nc * 4));       // "no flagged frame"; kept so by k_scan_repick
-        HIP_TRY(c, hipDeviceSynchronize());
-        c->ws().adapt_chunks = nc; ++c->ws_gen;
-    }
-    if (ng > c->ws().adapt_groups) {
-        if (c->ws().d_list) (void)hipFree(c->ws().d_list);
-        if (c->ws().d_need) (void)hipFree(c->ws().d_need);
-        c->ws().d_list = c->ws().d_need = nullptr; c->ws().adapt_groups = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_list, ng * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_need, ng * 4));
-        HIP_TRY(c, hipMemset(c->ws().d_need, 0, ng * 4));                 // test-and-set words; released by k_repair_patch / k_scan_repick
-        if (c->ws().d_umask) (void)hipFree(c->ws().d_umask);
-        c->ws().d_umask = nullptr;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_umask, ng * (c->Dp / 32) * 4));
-        HIP_TRY(c, hipMemset(c->ws().d_umask, 0, ng * (c->Dp / 32) * 4));   // candidate columns per unit; cleared by k_scan_repick
-        HIP_TRY(c, hipDeviceSynchronize());
-        c->ws().adapt_groups = ng; ++c->ws_gen;
-    }
-    if ((size_t)n_arrays > c->ws().lastv_arrays) {
-        if (c->ws().d_last_vchunk) (void)hipFree(c->ws().d_last_vchunk);
-        c->ws().d_last_vchunk = nullptr; c->ws().lastv_arrays = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_last_vchunk, (size_t)n_arrays * 4));
-        c->ws().lastv_arrays = n_arrays; ++c->ws_gen;
-    }
-    if (!c->ws().d_nlist) {
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_nlist, 16));             // listed repair units | listed chunks, workgroups of k_scan_repick done | unused
-        HIP_TRY(c, hipMemset(c->ws().d_nlist, 0, 16));
-        HIP_TRY(c, hipDeviceSynchronize());
-        ++c->ws_gen;
-    }
+    int rc;
+    if ((rc = grow_ws(c, w.d_flags, nf, "the flags of the coarse picks")) || (rc = grow_ws(c, w.d_unsure, nf, "the unsure frames")) ||
+        // + the list of the chunks that hold a flagged frame; 0x7f: "no flagged frame", kept so by k_scan_repick
+        (rc = grow_ws_filled(c, w.d_chunk_from, 2 * nc, nc, 0x7f, "the flagged chunks")) ||
+        (rc = grow_ws(c, w.d_list, ng, "the repair list")) ||
+        (rc = grow_ws_filled(c, w.d_need, ng, ng, 0, "the repair units' marks")) ||                         // test-and-set words; released by k_repair_patch / k_scan_repick
+        (rc = grow_ws_filled(c, w.d_umask, ng * (c->Dp / 32), ng * (c->Dp / 32), 0, "the candidate columns")) ||   // per unit; cleared by k_scan_repick
+        (rc = grow_ws(c, w.d_last_vchunk, (size_t)n_arrays, "the last voiced chunks")) ||
+        (rc = grow_ws_filled(c, w.d_nlist, 4, 4, 0, "the list counters"))) return rc;                      // listed repair units | listed chunks, workgroups of k_scan_repick done | unused
     const long long rows = repair_pass_rows(c, n_arrays, n_frames);
     const int planes = c->a_planes;
     set_call_planes(c, 2);
-    const int rc = ensure_a(c, rows);
+    rc = ensure_a(c, rows);
     set_call_planes(c, planes);
     if (rc) return rc;
-    const size_t need_cx = (size_t)repair_cx_rows(rows, REPAIR_KSPLIT_MAX) * c->Dp * sizeof(float);
-    if (need_cx > c->ws().cx_bytes) {
-        if (c->ws().d_Cx) (void)hipFree(c->ws().d_Cx);
-        c->ws().d_Cx = nullptr; c->ws().cx_bytes = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->ws().d_Cx, need_cx));
-        c->ws().cx_bytes = need_cx; ++c->ws_gen;
-    }
-    return MCA_HIP_OK;
+    return grow_ws(c, w.d_Cx, (size_t)repair_cx_rows(rows, REPAIR_KSPLIT_MAX) * c->Dp, "the repair contraction's partial maps");
 }
 
 // The correctly rounded float reciprocal of d (a small positive integer): the candidate nearest 1/d in exact arithmetic
@@ -1004,47 +947,9 @@ const char *mca_hip_version(void) { return "mcarray-hip 0.1.0 (gfx950)"; }
 
 const char *mca_hip_last_error(const mca_hip_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
+// the tables, the state and the switches of a new context; on an error the caller (mca_hip_create) frees what was built
+static int init_ctx(mca_hip_ctx *c, const mca_hip_config *cfg, const hipDeviceProp_t &prop)
 {
-    if (!cfg || !out) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
-    *out = nullptr;
-    // Callers built against an earlier header pass its size: round 2 ended before gcc_weighting (PHAT), round 3 behind it -- that
-    // struct was 60 bytes of fields padded to 64, and the padding is not read -- and the fields appended since default to zero.
-    constexpr int size_r2 = (int)offsetof(mca_hip_config, gcc_weighting), size_r3 = (size_r2 + 4 + 7) / 8 * 8;
-    static_assert(size_r3 <= (int)offsetof(mca_hip_config, adaptive_min_rows), "round-3 struct size");
-    if (cfg->struct_size != (int)sizeof(mca_hip_config) && cfg->struct_size != size_r2 && cfg->struct_size != size_r3)
-        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
-    mca_hip_config cfg_full{};
-    std::memcpy(&cfg_full, cfg, cfg->struct_size == size_r3 ? (size_t)offsetof(mca_hip_config, adaptive_fallback) : (size_t)cfg->struct_size);
-    cfg_full.struct_size = (int)sizeof(mca_hip_config);
-    cfg = &cfg_full;
-    if (cfg->gcc_weighting != MCA_HIP_GCC_PHAT && cfg->gcc_weighting != MCA_HIP_GCC_NONE)
-        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "gcc_weighting must be MCA_HIP_GCC_PHAT or MCA_HIP_GCC_NONE");
-    if (cfg->gcc_weighting == MCA_HIP_GCC_NONE && cfg->srp_precision != MCA_HIP_SRP_FP32)
-        return fail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "gcc_weighting NONE needs srp_precision MCA_HIP_SRP_FP32 (un-normalised spectra do not fit fp16 operands)");
-    if (cfg->n_mics < 2 || cfg->n_mics > MCA_MAX_MICS) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_mics must be in [2,16]");
-    if (!cfg->mic_xyz) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
-    if (cfg->n_sources < 1 || cfg->n_sources > MCA_MAX_SOURCES) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources must be in [1,4]");
-    if (cfg->fft_size < 16 || (cfg->fft_size & 1) || cfg->fft_size > 8192) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be even, 16..8192");
-    if (cfg->sample_rate <= 0) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
-    if (!(cfg->doa_step_deg > 0) || cfg->doa_step_deg > 45) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_step_deg must be in (0,45]");
-    if (cfg->srp_precision < 0 || cfg->srp_precision > 3) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "bad srp_precision");
-    if (cfg->max_arrays < 1) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "max_arrays < 1");
-    if (cfg->adaptive_fallback != MCA_HIP_ADAPT_FALLBACK_AUTO && cfg->adaptive_fallback != MCA_HIP_ADAPT_FALLBACK_OFF)
-        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_fallback must be MCA_HIP_ADAPT_FALLBACK_AUTO or _OFF");
-    if (cfg->adaptive_min_rows < 0 || cfg->adaptive_max_sources < 0) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_min_rows / adaptive_max_sources < 0");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, MCA_HIP_ERR_NO_DEVICE, "no HIP device visible; libmcarray_hip has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, MCA_HIP_ERR_HIP, "hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return fail(nullptr, MCA_HIP_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(nullptr, MCA_HIP_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-
-    mca_hip_ctx *c = new mca_hip_ctx();
     c->cfg = *cfg;
     c->kn = read_knobs(*cfg);
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -1053,7 +958,7 @@ int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
     c->cfg.mic_xyz = nullptr;
     c->step = (float)(cfg->doa_step_deg * M_PI / 180.0);                    // SteeringBeamforming.cpp:39
     c->D = (int)(std::round(M_PI / (double)c->step) + 1);                   // :40
-    if (c->D < 3 || c->D > 512) { free_ctx(c); return fail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "number of steering angles must be in [3,512]"); }
+    if (c->D < 3 || c->D > 512) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "number of steering angles must be in [3,512]");
     c->P = c->M * (c->M - 1) / 2;
     // column padding of the correlation map = tile width of the contraction kernels: 192, or 64 for the fp16 kernels on
     // grids of up to 64 angles (the reference's own 37, the 2-microphone module's 61)
@@ -1124,17 +1029,6 @@ int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
         c->tau_en = (float)(c->kn.tau_scale * 8.0 * std::sqrt(2.0) * sigma_c / (30.0 * c->P));
     }
 
-    int rc = MCA_HIP_OK;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        HIP_TRY(c, hipMalloc(dst, bytes));
-        HIP_TRY(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return MCA_HIP_OK;
-    };
-    auto zalloc = [&](void **dst, size_t bytes) -> int {
-        HIP_TRY(c, hipMalloc(dst, bytes));
-        HIP_TRY(c, hipMemset(*dst, 0, bytes));
-        return MCA_HIP_OK;
-    };
     std::vector<double> micx(c->M);
     for (int m = 0; m < c->M; ++m) micx[m] = c->xyz[3 * m];
     std::vector<float> win(c->N);
@@ -1142,34 +1036,74 @@ int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
     std::vector<float2> twv(c->N / 2);
     for (int i = 0; i < c->N / 2; ++i) twv[i] = make_float2((float)std::cos(2.0 * M_PI * i / c->N), (float)(-std::sin(2.0 * M_PI * i / c->N)));
     const size_t na = (size_t)cfg->max_arrays;
-    if ((rc = up((void **)&c->d_window, win.data(), win.size() * 4)) || (rc = up((void **)&c->d_tw, twv.data(), twv.size() * 8)) || (rc = up((void **)&c->d_grid, c->grid.data(), c->grid.size() * 4)) ||
-        (rc = up((void **)&c->d_delays, c->delays.data(), c->delays.size() * 4)) || (rc = up((void **)&c->d_micx, micx.data(), micx.size() * 8)) ||
-        (rc = up((void **)&c->d_pairs, c->pairs.data(), c->pairs.size() * sizeof(int2))) ||
-        (rc = zalloc((void **)&c->d_E[0], na * c->D * 4)) || (rc = zalloc((void **)&c->d_E[1], na * c->D * 4)) ||
-        (rc = zalloc((void **)&c->d_tail[0], na * c->S * c->H * 4)) || (rc = zalloc((void **)&c->d_tail[1], na * c->S * c->H * 4)) ||
-        (rc = zalloc((void **)&c->d_gate_state, na * 4 * 8)) || (rc = zalloc((void **)&c->d_last_bin, na * MCA_MAX_SOURCES * 4)) ||
-        (rc = zalloc((void **)&c->d_last_rad, na * MCA_MAX_SOURCES * 4)) || (rc = zalloc((void **)&c->d_last_prob, na * MCA_MAX_SOURCES * 4)) ||
-        (rc = zalloc((void **)&c->d_doa[0], na * 4)) || (rc = zalloc((void **)&c->d_doa[1], na * 4)) ||
-        (rc = zalloc((void **)&c->d_vdone[0], na * 8)) || (rc = zalloc((void **)&c->d_vdone[1], na * 8)) ||
-        (rc = zalloc((void **)&c->d_silence, na * 4)) || (rc = zalloc((void **)&c->d_g2_post0, na * 4)) ||
-        (rc = zalloc((void **)&c->d_rstats, 32)) ||
-        (rc = zalloc((void **)&c->d_E64[0], c->D * 8)) || (rc = zalloc((void **)&c->d_E64[1], c->D * 8)) ||
-        (rc = zalloc((void **)&c->d_res, (2 * MCA_MAX_SOURCES + 1) * 8)) || (rc = zalloc((void **)&c->d_bins, MCA_MAX_SOURCES * 4)) ||
-        (rc = zalloc((void **)&c->d_g2f_corr[0], c->D * 8)) || (rc = zalloc((void **)&c->d_g2f_corr[1], c->D * 8)) ||
-        (rc = zalloc((void **)&c->d_g2f_res, 4 * 8))) {
-        g_create_error = c->err; free_ctx(c); return rc;
-    }
-    if (lazy_context(c)) {
-        for (int i = 0; i < 2; ++i)
-            if ((rc = zalloc((void **)&c->d_hist_pcm[i], na * c->M * HIST_SAMPLES * 4)) || (rc = zalloc((void **)&c->d_hist_C[i], na * HIST_FRAMES * c->Dp * 4)) ||
-                (rc = zalloc((void **)&c->d_ehist[i], na * c->D * 4))) { g_create_error = c->err; free_ctx(c); return rc; }
-    }
+    hipError_t e;
+    if ((e = c->d_window.upload(win.data(), win.size())) || (e = c->d_tw.upload(twv.data(), twv.size())) || (e = c->d_grid.upload(c->grid.data(), c->grid.size())) ||
+        (e = c->d_delays.upload(c->delays.data(), c->delays.size())) || (e = c->d_micx.upload(micx.data(), micx.size())) ||
+        (e = c->d_pairs.upload(c->pairs.data(), c->pairs.size())) ||
+        // the state: every array at exactly its state size (state_parts hands the buffers' own sizes to the blob code)
+        (e = c->d_gate_state.alloc_zero(na * 4)) || (e = c->d_last_bin.alloc_zero(na * MCA_MAX_SOURCES)) ||
+        (e = c->d_last_rad.alloc_zero(na * MCA_MAX_SOURCES)) || (e = c->d_last_prob.alloc_zero(na * MCA_MAX_SOURCES)) ||
+        (e = c->d_silence.alloc_zero(na)) || (e = c->d_g2_post0.alloc_zero(na)) ||
+        (e = c->d_rstats.alloc_zero(4)) ||
+        (e = c->d_res.alloc_zero(2 * MCA_MAX_SOURCES + 1)) || (e = c->d_bins.alloc_zero(MCA_MAX_SOURCES)) ||
+        (e = c->d_g2f_res.alloc_zero(4))) return hip_fail(c, e, "device memory for the tables and the state of the context");
+    for (int i = 0; i < 2; ++i)
+        if ((e = c->d_E[i].alloc_zero(na * c->D)) || (e = c->d_tail[i].alloc_zero(na * c->S * c->H)) || (e = c->d_doa[i].alloc_zero(na)) ||
+            (e = c->d_vdone[i].alloc_zero(na)) || (e = c->d_E64[i].alloc_zero(c->D)) || (e = c->d_g2f_corr[i].alloc_zero(c->D)) ||
+            (lazy_context(c) && ((e = c->d_hist_pcm[i].alloc_zero(na * c->M * HIST_SAMPLES)) || (e = c->d_hist_C[i].alloc_zero(na * HIST_FRAMES * c->Dp)) ||
+                                 (e = c->d_ehist[i].alloc_zero(na * c->D))))) return hip_fail(c, e, "device memory for the double-buffered state of the context");
     if (c->prec == MCA_HIP_SRP_ADAPTIVE && c->kn.fb_enabled) {
         if (hipHostMalloc((void **)&c->h_probe, FB_RING * 32, hipHostMallocDefault) == hipSuccess) std::memset(c->h_probe, 0, FB_RING * 32);
         else { c->h_probe = nullptr; (void)hipGetLastError(); }                    // (no page-locked memory: the mode never backs off)
     }
-    if (c->stream_ok && ((rc = build_steering_table(c)) || (rc = build_merged_tables(c)))) { g_create_error = c->err; free_ctx(c); return rc; }
-    if ((rc = init_last_state(c, nullptr))) { g_create_error = c->err; free_ctx(c); return rc; }
+    int rc;
+    if (c->stream_ok && ((rc = build_steering_table(c)) || (rc = build_merged_tables(c)))) return rc;
+    return init_last_state(c, nullptr);
+}
+
+int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
+{
+    if (!cfg || !out) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
+    *out = nullptr;
+    // Callers built against an earlier header pass its size: round 2 ended before gcc_weighting (PHAT), round 3 behind it -- that
+    // struct was 60 bytes of fields padded to 64, and the padding is not read -- and the fields appended since default to zero.
+    constexpr int size_r2 = (int)offsetof(mca_hip_config, gcc_weighting), size_r3 = (size_r2 + 4 + 7) / 8 * 8;
+    static_assert(size_r3 <= (int)offsetof(mca_hip_config, adaptive_min_rows), "round-3 struct size");
+    if (cfg->struct_size != (int)sizeof(mca_hip_config) && cfg->struct_size != size_r2 && cfg->struct_size != size_r3)
+        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    mca_hip_config cfg_full{};
+    std::memcpy(&cfg_full, cfg, cfg->struct_size == size_r3 ? (size_t)offsetof(mca_hip_config, adaptive_fallback) : (size_t)cfg->struct_size);
+    cfg_full.struct_size = (int)sizeof(mca_hip_config);
+    cfg = &cfg_full;
+    if (cfg->gcc_weighting != MCA_HIP_GCC_PHAT && cfg->gcc_weighting != MCA_HIP_GCC_NONE)
+        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "gcc_weighting must be MCA_HIP_GCC_PHAT or MCA_HIP_GCC_NONE");
+    if (cfg->gcc_weighting == MCA_HIP_GCC_NONE && cfg->srp_precision != MCA_HIP_SRP_FP32)
+        return fail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "gcc_weighting NONE needs srp_precision MCA_HIP_SRP_FP32 (un-normalised spectra do not fit fp16 operands)");
+    if (cfg->n_mics < 2 || cfg->n_mics > MCA_MAX_MICS) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_mics must be in [2,16]");
+    if (!cfg->mic_xyz) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
+    if (cfg->n_sources < 1 || cfg->n_sources > MCA_MAX_SOURCES) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources must be in [1,4]");
+    if (cfg->fft_size < 16 || (cfg->fft_size & 1) || cfg->fft_size > 8192) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be even, 16..8192");
+    if (cfg->sample_rate <= 0) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
+    if (!(cfg->doa_step_deg > 0) || cfg->doa_step_deg > 45) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_step_deg must be in (0,45]");
+    if (cfg->srp_precision < 0 || cfg->srp_precision > 3) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "bad srp_precision");
+    if (cfg->max_arrays < 1) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "max_arrays < 1");
+    if (cfg->adaptive_fallback != MCA_HIP_ADAPT_FALLBACK_AUTO && cfg->adaptive_fallback != MCA_HIP_ADAPT_FALLBACK_OFF)
+        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_fallback must be MCA_HIP_ADAPT_FALLBACK_AUTO or _OFF");
+    if (cfg->adaptive_min_rows < 0 || cfg->adaptive_max_sources < 0) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_min_rows / adaptive_max_sources < 0");
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, MCA_HIP_ERR_NO_DEVICE, "no HIP device visible; libmcarray_hip has no CPU fallback");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, MCA_HIP_ERR_HIP, "hipSetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return fail(nullptr, MCA_HIP_ERR_HIP, "hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(nullptr, MCA_HIP_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+
+    mca_hip_ctx *c = new mca_hip_ctx();
+    const int rc = init_ctx(c, cfg, prop);
+    if (rc) { g_create_error = c->err; free_ctx(c); return rc; }
     *out = c;
     return MCA_HIP_OK;
 }
@@ -1208,43 +1142,43 @@ int mca_hip_get_doa_grid(const mca_hip_ctx *c, float *out)
 }
 
 // the DOA tracker as mca_hip_gcc2_tracker_attach leaves it: no track anywhere, _currentDOA = 0, _prob = -1
-static int trk_init_state(mca_hip_ctx *c, hipStream_t st)
+// (x, sd, si: the context's own, or the buffers mca_hip_gcc2_tracker_attach is about to hand over)
+static int trk_init_state(mca_hip_ctx *c, const DevBuf<double> &x, const DevBuf<double> &sd_dev, const DevBuf<int> &si, hipStream_t st)
 {
     const size_t slots = (size_t)c->cfg.max_arrays + 1;
     std::vector<double> sd(slots * 2);
     for (size_t i = 0; i < slots; ++i) { sd[i * 2] = 0.0; sd[i * 2 + 1] = -1.0; }
-    HIP_TRY(c, hipMemsetAsync(c->d_trk_x, 0, slots * c->trk.n_particles * 8, st));
-    HIP_TRY(c, hipMemsetAsync(c->d_trk_si, 0, slots * 4 * 4, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_trk_sd, sd.data(), slots * 2 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, x.zero_async(st));
+    HIP_TRY(c, si.zero_async(st));
+    HIP_TRY(c, hipMemcpyAsync(sd_dev, sd.data(), sd_dev.bytes(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
+static int trk_init_state(mca_hip_ctx *c, hipStream_t st) { return trk_init_state(c, c->d_trk_x, c->d_trk_sd, c->d_trk_si, st); }
 
 int mca_hip_reset(mca_hip_ctx *c, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     hipStream_t st = (hipStream_t)stream;
-    const size_t na = (size_t)c->cfg.max_arrays;
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(c, hipMemsetAsync(c->d_E[i], 0, na * c->D * 4, st));
-        HIP_TRY(c, hipMemsetAsync(c->d_tail[i], 0, na * c->S * c->H * 4, st));
-        HIP_TRY(c, hipMemsetAsync(c->d_E64[i], 0, (size_t)c->D * 8, st));
-        HIP_TRY(c, hipMemsetAsync(c->d_g2f_corr[i], 0, (size_t)c->D * 8, st));
-        HIP_TRY(c, hipMemsetAsync(c->d_doa[i], 0, na * 4, st));
-        HIP_TRY(c, hipMemsetAsync(c->d_vdone[i], 0, na * 8, st));
+        HIP_TRY(c, c->d_E[i].zero_async(st));
+        HIP_TRY(c, c->d_tail[i].zero_async(st));
+        HIP_TRY(c, c->d_E64[i].zero_async(st));
+        HIP_TRY(c, c->d_g2f_corr[i].zero_async(st));
+        HIP_TRY(c, c->d_doa[i].zero_async(st));
+        HIP_TRY(c, c->d_vdone[i].zero_async(st));
     }
-    HIP_TRY(c, hipMemsetAsync(c->d_silence, 0, na * 4, st));
+    HIP_TRY(c, c->d_silence.zero_async(st));
     c->adapt_suspended = false; c->fb_state = 0; c->fb_left = 0; c->fb_backoff = 8; c->cand_heavy = false;     // new streams: the adaptive mode starts afresh
     c->fb_lost = false; c->fb_seq_seen = c->fb_calls;                                                          // (reports still in flight belong to the old streams)
     c->hist_pending = false;                                                              // ... and no call owes the next one its last rows
     // the self-cleaning words of the adaptive path (a call that failed half way may have left some set)
-    for (Workspace &w : c->lanes) {
-        if (w.d_need) HIP_TRY(c, hipMemsetAsync(w.d_need, 0, w.adapt_groups * 4, st));
-        if (w.d_umask) HIP_TRY(c, hipMemsetAsync(w.d_umask, 0, w.adapt_groups * (c->Dp / 32) * 4, st));
-        if (w.d_chunk_from) HIP_TRY(c, hipMemsetAsync(w.d_chunk_from, 0x7f, w.adapt_chunks * 4, st));
-        if (w.d_nlist) HIP_TRY(c, hipMemsetAsync(w.d_nlist, 0, 16, st));
-    }
-    if (c->d_steer_pred) HIP_TRY(c, hipMemsetAsync(c->d_steer_pred, 0xff, na * 4, st));      // no pick yet: bin -1, the initial DOA
+    Workspace &w = c->ws;
+    HIP_TRY(c, w.d_need.zero_async(st));
+    HIP_TRY(c, w.d_umask.zero_async(st));
+    if (w.d_chunk_from) HIP_TRY(c, hipMemsetAsync(w.d_chunk_from, 0x7f, w.d_chunk_from.bytes() / 2, st));
+    HIP_TRY(c, w.d_nlist.zero_async(st));
+    if (c->d_steer_pred) HIP_TRY(c, hipMemsetAsync(c->d_steer_pred, 0xff, c->d_steer_pred.bytes(), st));      // no pick yet: bin -1, the initial DOA
     if (c->d_steer_mlist) { HIP_TRY(c, hipMemsetAsync(c->d_steer_mlist, 0, 4, st)); c->steer_mlist_dirty = false; }   // (a call that failed half way may have left misses listed)
     c->steer_spec = true; c->steer_lost = false; c->steer_seq_seen = c->steer_seq;              // (reports still in flight belong to the old streams)
     c->gcc2_frames_done = 0;
@@ -1277,13 +1211,14 @@ unsigned delays_hash(const mca_hip_ctx *c)
 struct StatePart { void *ptr; size_t bytes; };
 std::vector<StatePart> state_parts(mca_hip_ctx *c)
 {
-    const size_t na = (size_t)c->cfg.max_arrays;
+    // (every one of them is allocated at exactly its state size, init_ctx: the buffer's own size is the part's)
+    auto part = [](const auto &b) { return StatePart{b.p, b.bytes()}; };
     return {
-        {c->d_E[c->e_cur], na * c->D * 4}, {c->d_tail[c->tail_cur], na * c->S * c->H * 4}, {c->d_gate_state, na * 4 * 8},
-        {c->d_last_bin, na * MCA_MAX_SOURCES * 4}, {c->d_last_rad, na * MCA_MAX_SOURCES * 4}, {c->d_last_prob, na * MCA_MAX_SOURCES * 4},
-        {c->d_doa[c->doa_cur], na * 4}, {c->d_E64[c->e64_cur], (size_t)c->D * 8}, {c->d_vdone[c->doa_cur], na * 8},
-        {c->d_silence, na * 4},
-        {c->d_g2f_corr[c->g2f_cur], (size_t)c->D * 8},     // version 3: the frame hook's correlation, then its scalars (host side)
+        part(c->d_E[c->e_cur]), part(c->d_tail[c->tail_cur]), part(c->d_gate_state),
+        part(c->d_last_bin), part(c->d_last_rad), part(c->d_last_prob),
+        part(c->d_doa[c->doa_cur]), part(c->d_E64[c->e64_cur]), part(c->d_vdone[c->doa_cur]),
+        part(c->d_silence),
+        part(c->d_g2f_corr[c->g2f_cur]),     // version 3: the frame hook's correlation, then its scalars (host side)
     };
 }
 
@@ -1297,8 +1232,7 @@ struct TrackerBlobHead { int n_particles, n_inject; unsigned long long seed; dou
 static_assert(sizeof(TrackerBlobHead) == 32, "TrackerBlobHead is 32 bytes of the blob");
 std::vector<StatePart> tracker_parts(const mca_hip_ctx *c)
 {
-    const size_t slots = (size_t)c->cfg.max_arrays + 1;
-    return {{c->d_trk_si, slots * 16}, {c->d_trk_sd, slots * 16}, {c->d_trk_x, slots * c->trk.n_particles * 8}};
+    return {{c->d_trk_si.p, c->d_trk_si.bytes()}, {c->d_trk_sd.p, c->d_trk_sd.bytes()}, {c->d_trk_x.p, c->d_trk_x.bytes()}};
 }
 size_t tracker_part_bytes(const mca_hip_ctx *c)
 {
@@ -1377,8 +1311,8 @@ int mca_hip_state_load(mca_hip_ctx *c, const void *blob, long long blob_bytes)
     HIP_TRY(c, hipDeviceSynchronize());
     const unsigned char *in = static_cast<const unsigned char *>(blob) + sizeof(h);
     for (const StatePart &p : state_parts(c)) {
-        if (h.version == 1 && p.ptr == c->d_silence) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
-        if (h.version < 3 && p.ptr == c->d_g2f_corr[c->g2f_cur]) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
+        if (h.version == 1 && p.ptr == c->d_silence.p) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
+        if (h.version < 3 && p.ptr == c->d_g2f_corr[c->g2f_cur].p) { HIP_TRY(c, hipMemset(p.ptr, 0, p.bytes)); continue; }
         HIP_TRY(c, hipMemcpy(p.ptr, in, p.bytes, hipMemcpyHostToDevice)); in += p.bytes;
     }
     if (h.version >= 3) { std::memcpy(&c->g2f, in, sizeof(G2FrameState)); in += sizeof(G2FrameState); }
@@ -1397,9 +1331,11 @@ int mca_hip_state_load(mca_hip_ctx *c, const void *blob, long long blob_bytes)
     return MCA_HIP_OK;
 }
 
-// workspace of one lane for a call of n_arrays x n_frames
-static int reserve_lane(mca_hip_ctx *c, int n_arrays, int n_frames)
+// the workspace of a call of n_arrays x n_frames
+static int steer_reserve(mca_hip_ctx *c, int n_arrays, int n_frames);
+static int reserve_impl(mca_hip_ctx *c, int n_arrays, int n_frames)
 {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const int n_chunks = (n_frames + SCAN_CHUNK - 1) / SCAN_CHUNK;
     int rc;
     if (c->prec == MCA_HIP_SRP_ADAPTIVE && adaptive_shape(c, n_arrays, n_frames)) {
@@ -1419,14 +1355,6 @@ static int reserve_lane(mca_hip_ctx *c, int n_arrays, int n_frames)
     return ensure_scan_workspace(c, n_arrays, n_frames, n_chunks);
 }
 
-static int steer_reserve(mca_hip_ctx *c, int n_arrays, int n_frames);
-static int reserve_impl(mca_hip_ctx *c, int n_arrays, int n_frames)
-{
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    c->cur_lane = 0;
-    return reserve_lane(c, n_arrays, n_frames);
-}
-
 int mca_hip_reserve(mca_hip_ctx *c, int n_arrays, int n_frames)
 {
     if (!c || n_arrays < 1 || n_frames < 1) return MCA_HIP_ERR_INVALID_ARGUMENT;
@@ -1434,7 +1362,7 @@ int mca_hip_reserve(mca_hip_ctx *c, int n_arrays, int n_frames)
     return rc ? rc : steer_reserve(c, n_arrays, n_frames);      // (the rows of Y of a context that steers on the half spectrum)
 }
 
-// STFT + PHAT + steering contraction for every frame: fills c->ws().d_C [arrays][n_frames][Dp]
+// STFT + PHAT + steering contraction for every frame: fills c->ws.d_C [arrays][n_frames][Dp]
 static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
                                int n_arrays, int n_frames, hipStream_t st)
 {
@@ -1448,8 +1376,8 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
                          plan_gemm(c, (long long)n_arrays * fc).ksplit <= 2;
     for (int f0 = 0; fused_partial && f0 < n_frames; f0 += (int)fc)
         fused_partial = plan_gemm(c, (long long)n_arrays * std::min<long long>(fc, n_frames - f0)).v2;
-    c->ws().partial_done = fused_partial;
-    c->ws().part_planes = fused_partial ? plan_gemm(c, (long long)n_arrays * fc).ksplit : 1;
+    c->ws.partial_done = fused_partial;
+    c->ws.part_planes = fused_partial ? plan_gemm(c, (long long)n_arrays * fc).ksplit : 1;
     for (int f0 = 0; f0 < n_frames; f0 += (int)fc) {
         const int nf = (int)std::min<long long>(fc, n_frames - f0);
         StftPhatArgs sa{};
@@ -1460,13 +1388,13 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         // so that a few hundred workgroups exist
         sa.fpb = 16;
         while (sa.fpb > 1 && (long long)n_arrays * ((nf + sa.fpb - 1) / sa.fpb) < 256) sa.fpb >>= 1;
-        sa.power = c->cfg.use_power_floor ? c->ws().d_power : nullptr; sa.total_frames = n_frames;
+        sa.power = c->cfg.use_power_floor ? c->ws.d_power : nullptr; sa.total_frames = n_frames;
         sa.window = c->d_window; sa.A = a_buf(c); sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = c->a_planes;
         if (c->merged && c->a_planes == 1) { sa.mrank = c->d_mrank; sa.n_merged = c->n_merged; sa.planar = c->fold ? 1 : 0; }
         sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
         sa.no_phat = c->cfg.gcc_weighting == MCA_HIP_GCC_NONE ? 1 : 0;
-        if (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 1 && wave16_applies(c)) sa.unsure = c->ws().d_unsure;   // (adaptive coarse pass)
-        if (c->lazy_now && cand_call(c, true)) sa.dead = c->ws().d_unsure;                                               // (... of a candidate-column call: frames of exact zeros)
+        if (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 1 && wave16_applies(c)) sa.unsure = c->ws.d_unsure;   // (adaptive coarse pass)
+        if (c->lazy_now && cand_call(c, true)) sa.dead = c->ws.d_unsure;                                               // (... of a candidate-column call: frames of exact zeros)
         if (c->lazy_now) sa.hist_out = c->d_hist_pcm[c->hist_cur ^ 1];       // lazy tails: the call's last frames of PCM stay behind
         if (c->steer_now && sa.mrank && !sa.power) {                          // the merged 8-microphone kernel also steers every frame at the array's predicted bin
             sa.bf.rows = c->d_steer_rows; sa.bf.q = c->d_steer_q; sa.bf.nyq = c->d_steer_nyq; sa.bf.pred = c->d_steer_pred + c->a0; sa.bf.Y = c->d_steer_Y;
@@ -1513,13 +1441,13 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
 
         GemmArgs ga{};
         const bool mg = c->merged && c->a_planes == 1;
-        ga.A = a_buf(c); ga.B = mg ? c->d_Bm : c->d_B; ga.C = c->ws().d_C; ga.Bt = mg ? c->d_Btm : c->d_Bt;
+        ga.A = a_buf(c); ga.B = mg ? c->d_Bm : c->d_B; ga.C = c->ws.d_C; ga.Bt = mg ? c->d_Btm : c->d_Bt;
         ga.rows = n_arrays * nf; ga.chunk_frames = nf; ga.total_frames = n_frames; ga.frame0 = f0;
         ga.Kp = cur_kp(c); ga.Dp = c->Dp; ga.a_row_elems = c->a_row_elems;
         ga.c_plane_elems = (long long)n_arrays * n_frames * c->Dp;
         ga.Bf = mg ? c->d_Bfold : nullptr; ga.D = c->D;
         if (fused_partial) {
-            ga.part = c->ws().d_part; ga.nvoiced = c->ws().d_nv; ga.D = c->D; ga.n_chunks = n_frames / SCAN_CHUNK;
+            ga.part = c->ws.d_part; ga.nvoiced = c->ws.d_nv; ga.D = c->D; ga.n_chunks = n_frames / SCAN_CHUNK;
             ga.part_plane_stride = (long long)n_arrays * ga.n_chunks * c->D;
             ga.scan_w[31] = 1 - 0.8f;                                              // as pa.one_minus_mu / pa.mu below
             for (int t = 30; t >= 0; --t) ga.scan_w[t] = ga.scan_w[t + 1] * 0.8f;
@@ -1528,7 +1456,7 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         // suits the full-size chunks; a shorter last chunk may still fall back to the 128 x 192 kernel
         const bool v2 = plan_gemm(c, ga.rows).v2;
         const int ksplit = plan_gemm(c, (long long)n_arrays * fc).ksplit;
-        c->ws().c_planes = ksplit; c->ws().c_plane = ga.c_plane_elems;
+        c->ws.c_planes = ksplit; c->ws.c_plane = ga.c_plane_elems;
         time_begin(c, MCA_HIP_K_SRP_GEMM, st);
         if (v2) {
             const int np = c->a_planes;
@@ -1559,13 +1487,13 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
     }
-    if (c->ws().c_planes > 2) {      // deep split-K of a small batch: fold the partial maps once, the scans read one map
-        const long long n4 = c->ws().c_plane / 4;       // Dp is a multiple of 64
+    if (c->ws.c_planes > 2) {      // deep split-K of a small batch: fold the partial maps once, the scans read one map
+        const long long n4 = c->ws.c_plane / 4;       // Dp is a multiple of 64
         time_begin(c, MCA_HIP_K_FOLD, st);
-        hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c->ws().d_C, n4, c->ws().c_planes, c->ws().c_plane);
+        hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c->ws.d_C, n4, c->ws.c_planes, c->ws.c_plane);
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
-        c->ws().c_planes = 1;
+        c->ws.c_planes = 1;
     }
 
     return MCA_HIP_OK;
@@ -1603,14 +1531,14 @@ static int settle_history(mca_hip_ctx *c, hipStream_t st)
 {
     if (!c->hist_pending) return MCA_HIP_OK;
     const int n = c->hist_n, units = n * HIST_UNITS, rows = units * REPAIR_GROUP, cur = c->hist_cur;
-    Workspace &w = c->lanes[0];
+    Workspace &w = c->ws;
     if (!w.d_list || !w.d_need || !w.d_nlist || !w.d_Ax || !w.d_Cx) return fail(c, MCA_HIP_ERR_HIP, "lazy tails: the adaptive workspace is gone");
     // The workspace was sized by the lazy call that left the debt (ensure_adapt_workspace: repair_pass_rows of its shape, capped by the
     // budget, MCA_HIP_WS_MAX_MB); the history's rows go through it in passes of at most that many rows, as localise_impl's do (ADVICE r5:
     // one pass of all of them wrote past d_Ax / d_Cx when the budget was small and the arrays many).
     const int ksplit = repair_ksplit_for(c, n);
     long long pass_rows = std::min<long long>((rows + 127) / 128 * 128, repair_pass_rows(c, n, HIST_FRAMES));
-    const long long fit_a = (long long)(w.ax_bytes / ((size_t)2 * c->Kp * 2)) / 128 * 128, fit_c = (long long)(w.cx_bytes / ((size_t)ksplit * c->Dp * 4)) / 128 * 128;
+    const long long fit_a = (long long)(w.d_Ax.n / ((size_t)2 * c->Kp * 2)) / 128 * 128, fit_c = (long long)(w.d_Cx.bytes() / ((size_t)ksplit * c->Dp * 4)) / 128 * 128;
     pass_rows = std::min(pass_rows, std::min(fit_a, fit_c));
     if (pass_rows < 128) return fail(c, MCA_HIP_ERR_HIP, "lazy tails: the adaptive workspace is smaller than one repair pass");
     const int pass_groups = (int)(pass_rows / REPAIR_GROUP);
@@ -1645,8 +1573,7 @@ static int settle_history(mca_hip_ctx *c, hipStream_t st)
     return rc;
 }
 
-// the localisation stage of the arrays [c->a0, c->a0 + n_arrays) on the workspace of lane c->cur_lane; all pointers already
-// point at the lane's first array
+// the localisation stage of the arrays [c->a0, c->a0 + n_arrays) of a call; all pointers already point at the piece's first array
 static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
                          int n_arrays, int n_frames, int *doa_bin, float *doa_rad, float *prob, float *energy, hipStream_t st)
 {
@@ -1673,38 +1600,38 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     time_begin(c, MCA_HIP_K_SCAN_PICK, st);
     if (gate) {
         GateArgs gg{};
-        gg.power_lin = c->ws().d_power; gg.n_frames = n_frames; gg.fft_n = c->N;
+        gg.power_lin = c->ws.d_power; gg.n_frames = n_frames; gg.fft_n = c->N;
         gg.needed_samples = (int)(3.0 * c->cfg.sample_rate);              // _durationToEstimatePowerFloor (SoundLocalisationImpl.h:77)
         gg.margin_db = 3.f;                                                // _noiseMarginDB (BeamformingSeparationAndLocalistaion.h:52)
-        gg.state = c->d_gate_state + a0 * 4; gg.voiced = c->ws().d_voiced; gg.power_out = c->ws().d_power_out;
+        gg.state = c->d_gate_state + a0 * 4; gg.voiced = c->ws.d_voiced; gg.power_out = c->ws.d_power_out;
         hipLaunchKernelGGL(k_gate, dim3(n_arrays), dim3(256), 0, st, gg);
     }
     ScanPickArgs pa{};
-    pa.C = c->ws().d_C; pa.c_planes = c->ws().c_planes; pa.c_plane_stride = c->ws().c_plane; pa.n_frames = n_frames; pa.Dp = c->Dp; pa.D = c->D; pa.P = c->P; pa.S = c->S;
+    pa.C = c->ws.d_C; pa.c_planes = c->ws.c_planes; pa.c_plane_stride = c->ws.c_plane; pa.n_frames = n_frames; pa.Dp = c->Dp; pa.D = c->D; pa.P = c->P; pa.S = c->S;
     pa.chunk = SCAN_CHUNK; pa.n_chunks = n_chunks;
     pa.mu = ENERGY_MU; pa.one_minus_mu = ENERGY_ONE_MINUS_MU;                 // SteeringBeamforming.h:70, .cpp:134,139 (float arithmetic)
     pa.inv_norm = exact_reciprocal(30.f * (float)c->P);
     pa.state_in = c->d_E[c->e_cur] + a0 * c->D; pa.state_out = c->d_E[c->e_cur ^ 1] + a0 * c->D;
-    pa.part_planes = c->ws().partial_done ? c->ws().part_planes : 1; pa.part_plane_stride = (long long)n_arrays * n_chunks * c->D;
-    pa.part = c->ws().d_part; pa.nvoiced = c->ws().d_nv; pa.e_start = c->ws().d_estart; pa.voiced = gate ? c->ws().d_voiced : nullptr;
+    pa.part_planes = c->ws.partial_done ? c->ws.part_planes : 1; pa.part_plane_stride = (long long)n_arrays * n_chunks * c->D;
+    pa.part = c->ws.d_part; pa.nvoiced = c->ws.d_nv; pa.e_start = c->ws.d_estart; pa.voiced = gate ? c->ws.d_voiced : nullptr;
     pa.grid = c->d_grid; pa.doa_bin = doa_bin; pa.doa_rad = doa_rad; pa.prob = prob; pa.energy = energy;
     const int gpa = (n_frames + REPAIR_GROUP - 1) / REPAIR_GROUP;
     if (adaptive) {
-        pa.mode = 1; pa.tau = c->tau_en; pa.flags = c->ws().d_flags; pa.groups_per_array = gpa;
-        pa.need = c->ws().d_need; pa.list = c->ws().d_list; pa.n_list = c->ws().d_nlist; pa.chunk_from = c->ws().d_chunk_from; pa.last_vchunk = c->ws().d_last_vchunk; pa.stats = c->d_rstats;
-        pa.unsure = wave16_applies(c) ? c->ws().d_unsure : nullptr;
+        pa.mode = 1; pa.tau = c->tau_en; pa.flags = c->ws.d_flags; pa.groups_per_array = gpa;
+        pa.need = c->ws.d_need; pa.list = c->ws.d_list; pa.n_list = c->ws.d_nlist; pa.chunk_from = c->ws.d_chunk_from; pa.last_vchunk = c->ws.d_last_vchunk; pa.stats = c->d_rstats;
+        pa.unsure = wave16_applies(c) ? c->ws.d_unsure : nullptr;
         pa.hist_base = n_arrays * gpa;
         if (lazy) { pa.lazy = 1; pa.hist_C_out = c->d_hist_C[c->hist_cur ^ 1]; pa.e_hist_out = c->d_ehist[c->hist_cur ^ 1]; }
         if (hist_valid) { pa.hist_valid = 1; pa.hist_C_in = c->d_hist_C[c->hist_cur]; pa.e_hist_in = c->d_ehist[c->hist_cur]; }
-        if (cand_call(c, lazy)) { pa.umask = c->ws().d_umask; pa.umask_words = c->Dp / 32; pa.dead = c->ws().d_unsure; }   // (dead: the unsure bytes, unused by these contexts)
-        pa.clist = c->ws().d_chunk_from + c->ws().adapt_chunks; pa.n_clist = c->ws().d_nlist + 1;   // (+ 2: see ScanPickArgs)
+        if (cand_call(c, lazy)) { pa.umask = c->ws.d_umask; pa.umask_words = c->Dp / 32; pa.dead = c->ws.d_unsure; }   // (dead: the unsure bytes, unused by these contexts)
+        pa.clist = c->ws.d_chunk_from + c->ws.d_chunk_from.n / 2; pa.n_clist = c->ws.d_nlist + 1;   // (+ 2: see ScanPickArgs)
         // steered tail: the analysis of this call steered every frame at its array's predicted bin, so the frames that miss it are patched inside
         // the second pick's launch (k_scan_repick<PL, true>) and steer_separate launches no k_steer_patch.  One batch of k_scan_pick per chunk
         // is what makes "no flagged frame in the batch" mean "the chunk's coarse picks are final".
         // Not the widest peak pick (D > 386: k_scan_pick<8, 1> has no register left for the append), and only while the launch's LDS -- energy
         // rows, the transform's table, a scratch per wave, the static arrays -- fits a CU: those calls keep the stand-alone k_steer_patch.
         const size_t tail_lds = (size_t)32 * (c->Dp + 8) * sizeof(float) + (size_t)(F1K_TWORDS + 8 * F1K_SCRATCH) * sizeof(float2) + 2048;
-        if (c->steer_now && c->steer_fused_now && c->d_steer_mlist && SCAN_SUB == SCAN_CHUNK && c->S == 1 && !gate && (size_t)n_arrays * n_frames <= c->steer_Y_rows &&
+        if (c->steer_now && c->steer_fused_now && c->d_steer_mlist && SCAN_SUB == SCAN_CHUNK && c->S == 1 && !gate && (size_t)n_arrays * n_frames < c->d_steer_mlist.n &&
             c->D - 2 <= 384 && c->D <= 512 && tail_lds <= 160 * 1024) {
             // the list is empty unless a call that listed misses never reached its synthesis (which empties it): an error in between
             if (c->steer_mlist_dirty) HIP_TRY(c, hipMemsetAsync(c->d_steer_mlist, 0, sizeof(int), st));
@@ -1725,7 +1652,7 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     }
     const int nthr = round_up(c->D, 64);
     dim3 g3(pa.n_chunks, n_arrays);
-    if (!c->ws().partial_done) hipLaunchKernelGGL(k_scan_partial, g3, dim3(round_up(c->Dp / 4, 64)), 0, st, pa);   // a thread per four delays
+    if (!c->ws.partial_done) hipLaunchKernelGGL(k_scan_partial, g3, dim3(round_up(c->Dp / 4, 64)), 0, st, pa);   // a thread per four delays
     // ungated calls: k_scan_pick composes its chunk's start value itself (the chunks further back than four have decayed below the
     // last bit); with the gate a chunk may hold no advancing frame at all and the composition runs over all of them, in order
     // The look-back drops g^4 E_{c-4} (g = 0.8^32: 3.9e-13 of E), which is below the last bit only while the map is bounded: under PHAT
@@ -1746,7 +1673,7 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     else { if (ppl == 2) LAUNCH_PICK(2, 0); else if (ppl == 6) LAUNCH_PICK(6, 0); else LAUNCH_PICK(8, 0); }
 #undef LAUNCH_PICK
     DoaFillArgs fa{};
-    fa.voiced = c->ws().d_voiced; fa.n_frames = n_frames; fa.S = c->S;
+    fa.voiced = c->ws.d_voiced; fa.n_frames = n_frames; fa.S = c->S;
     fa.doa_bin = doa_bin; fa.doa_rad = doa_rad; fa.prob = prob;
     fa.last_bin = c->d_last_bin + a0 * c->S; fa.last_rad = c->d_last_rad + a0 * c->S; fa.last_prob = c->d_last_prob + a0 * c->S;
     if (gate && !adaptive) hipLaunchKernelGGL(k_doa_fill, dim3(n_arrays), dim3(1024), 0, st, fa);   // (ADAPTIVE: after the second pick)
@@ -1765,18 +1692,18 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             StftPhatArgs sa{};
             sa.pcm = pcm; sa.array_stride = array_stride; sa.mic_stride = mic_stride;
             sa.M = c->M; sa.n_frames = n_frames; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = n_frames;
-            sa.window = c->d_window; sa.A = c->ws().d_Ax; sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = 2;
+            sa.window = c->d_window; sa.A = c->ws.d_Ax; sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = 2;
             sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
-            sa.list = c->ws().d_list; sa.n_list = c->ws().d_nlist; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = gpa;
+            sa.list = c->ws.d_list; sa.n_list = c->ws.d_nlist; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = gpa;
             if (hist_valid) { sa.hist_in = c->d_hist_pcm[c->hist_cur]; sa.hist_base = n_arrays * gpa; }
             CandArgs ca{};
             if (pa.umask) {
                 // candidate columns: the exact values where the flagged frames need them, straight into the map (no partial maps, no patch) --
                 // by the workgroup that writes a unit's rows, inside the list-mode launch (4 / 8 microphones: k_stft_phat_wave)
-                ca.A = c->ws().d_Ax; ca.B = c->d_B; ca.Kp = c->Kp; ca.Dp = c->Dp; ca.a_row_elems = c->a_row_elems;
-                ca.list = c->ws().d_list; ca.n_list = c->ws().d_nlist; ca.list0 = (int)g0; ca.pass_rows = (int)pass_rows;
-                ca.umask = c->ws().d_umask; ca.umask_words = pa.umask_words; ca.need = c->ws().d_need; ca.groups_per_array = gpa; ca.n_frames = n_frames;
-                ca.C = c->ws().d_C; ca.c_planes = c->ws().c_planes; ca.c_plane_stride = c->ws().c_plane;
+                ca.A = c->ws.d_Ax; ca.B = c->d_B; ca.Kp = c->Kp; ca.Dp = c->Dp; ca.a_row_elems = c->a_row_elems;
+                ca.list = c->ws.d_list; ca.n_list = c->ws.d_nlist; ca.list0 = (int)g0; ca.pass_rows = (int)pass_rows;
+                ca.umask = c->ws.d_umask; ca.umask_words = pa.umask_words; ca.need = c->ws.d_need; ca.groups_per_array = gpa; ca.n_frames = n_frames;
+                ca.C = c->ws.d_C; ca.c_planes = c->ws.c_planes; ca.c_plane_stride = c->ws.c_plane;
                 if (hist_valid) { ca.hist_C = c->d_hist_C[c->hist_cur]; ca.hist_base = n_arrays * gpa; }
                 sa.cand_on = 1; sa.cand = ca;       // (pa.umask: cand_call, which requires a lazy call, so lazy_context, so M is 4 or 8 -- the list-mode launch contracts)
             }
@@ -1786,9 +1713,9 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             if (sa.cand_on) continue;
             RepairPatchArgs pp{};
             pp.groups_per_array = gpa;
-            pp.C = c->ws().d_C; pp.c_planes = c->ws().c_planes; pp.c_plane_stride = c->ws().c_plane; pp.n_frames = n_frames;
+            pp.C = c->ws.d_C; pp.c_planes = c->ws.c_planes; pp.c_plane_stride = c->ws.c_plane; pp.n_frames = n_frames;
             if (hist_valid) { pp.hist_C = c->d_hist_C[c->hist_cur]; pp.hist_base = n_arrays * gpa; }
-            launch_repair_contraction(c, c->ws(), g0, pass_rows, n_arrays, pp, st);
+            launch_repair_contraction(c, c->ws, g0, pass_rows, n_arrays, pp, st);
         }
         set_call_planes(c, 1);
         const int repick_thr = std::max(nthr, 512);
@@ -1811,7 +1738,6 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     }
     if (lazy) { c->hist_cur ^= 1; c->hist_n = n_arrays; c->hist_pending = true; }
     else c->hist_pending = false;                // (settled above, or consumed by an eager adaptive call: its own last frame was repaired)
-    c->ws().last_a0 = c->a0; c->ws().last_arrays = n_arrays;
     return MCA_HIP_OK;
 }
 
@@ -1863,27 +1789,22 @@ static bool wave_beamformer_applies(const mca_hip_ctx *c)
     return !c->generic && !c->n512 && (c->S <= 2 || c->M <= 8) && c->M >= 2 && c->M <= MCA_MAX_MICS;
 }
 
-// steering rows of every grid angle (+ the initial DOA): allocated and built once, outside any capture
+// steering rows of every grid angle (+ the initial DOA): allocated and built once, outside any capture.  Built into a local and handed
+// to the context when the table kernel has run: d_bftab set means the table is there
 static int ensure_bf_table(mca_hip_ctx *c)
 {
-    if (!c->d_bftab && c->n2048) {
-        // 2048-sample frames: a row per (angle, CHANNEL), [D + 1][M][1032] (k_beamform_wave_2048)
-        HIP_TRY(c, hipMalloc((void **)&c->d_bftab, (size_t)(c->D + 1) * c->M * 1032 * sizeof(float2)));
-        c->bf_pairs = c->M;
-        const double unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;     // Beamformer.cpp:59 without 2 pi
-        hipLaunchKernelGGL(k_bf_table_2048, dim3(c->D + 1, c->M), dim3(256), 0, nullptr, c->d_bftab, c->d_grid, c->d_micx, c->M, unit);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipDeviceSynchronize());
-        return MCA_HIP_OK;
-    }
-    if (c->d_bftab || !wave_beamformer_applies(c)) return MCA_HIP_OK;
-    const int np = (c->M + 1) / 2;
-    HIP_TRY(c, hipMalloc((void **)&c->d_bftab, (size_t)(c->D + 1) * np * 1024 * sizeof(float2)));
-    c->bf_pairs = np;
-    const double unit = (double)c->cfg.sample_rate / (double)FFT_N / 346.1;     // Beamformer.cpp:59 without 2 pi
-    hipLaunchKernelGGL(k_bf_table, dim3(c->D + 1, np), dim3(256), 0, nullptr, c->d_bftab, c->d_grid, c->d_micx, c->M, np, unit);
+    if (c->d_bftab || (!c->n2048 && !wave_beamformer_applies(c))) return MCA_HIP_OK;
+    // 2048-sample frames: a row per (angle, CHANNEL), [D + 1][M][1032] (k_beamform_wave_2048); else per channel pair, [D + 1][np][1024]
+    const int np = c->n2048 ? c->M : (c->M + 1) / 2;
+    DevBuf<float2> tab;
+    const hipError_t e = tab.alloc((size_t)(c->D + 1) * np * (c->n2048 ? 1032 : 1024));
+    if (e != hipSuccess) return hip_fail(c, e, "the beamformer's steering rows");
+    const double unit = (double)c->cfg.sample_rate / (double)(c->n2048 ? c->N : FFT_N) / 346.1;     // Beamformer.cpp:59 without 2 pi
+    if (c->n2048) hipLaunchKernelGGL(k_bf_table_2048, dim3(c->D + 1, c->M), dim3(256), 0, nullptr, tab.p, c->d_grid, c->d_micx, c->M, unit);
+    else hipLaunchKernelGGL(k_bf_table, dim3(c->D + 1, np), dim3(256), 0, nullptr, tab.p, c->d_grid, c->d_micx, c->M, np, unit);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipDeviceSynchronize());
+    c->d_bftab.swap(tab); c->bf_pairs = np;
     return MCA_HIP_OK;
 }
 
@@ -1922,37 +1843,43 @@ static void steer_policy_begin(mca_hip_ctx *c)
     c->steer_spec = __atomic_load_n(&slot[0], __ATOMIC_RELAXED) * STEER_MISS_DEN <= c->steer_call_frames[(r - 1) % FB_RING] * STEER_MISS_NUM;
 }
 
-// table (once, outside any capture), state, rows of Y for this call
+// The table and the state of the steered path, once and outside any capture: built into locals and handed to the context when the table
+// kernel has run -- d_steer_rows set means all of it is there, and a failure on the way leaves the context as it was.
+static int steer_build(mca_hip_ctx *c)
+{
+    const size_t na = (size_t)c->cfg.max_arrays;
+    DevBuf<float4> rows; DevBuf<float2> q; DevBuf<float> nyq, tail; DevBuf<int> pred; DevBuf<unsigned long long> miss;
+    hipError_t e;
+    if ((e = rows.alloc((size_t)(c->D + 1) * 4 * 64)) || (e = q.alloc((size_t)(c->D + 1) * c->M * 8)) || (e = nyq.alloc((size_t)(c->D + 1) * c->M)) ||
+        (e = pred.alloc(na)) ||
+        (e = miss.alloc(3)) ||           // running total; the guard's (arrays that had a prediction); the guard's at the end of the previous call
+        (e = tail.alloc(2 * na * FFT_H)) ||
+        (e = hipMemset(pred.p, 0xff, pred.bytes())) || (e = hipMemset(miss.p, 0, miss.bytes()))) return hip_fail(c, e, "the table and the state of the steered delay-and-sum");
+    const double unit = (double)c->cfg.sample_rate / (double)FFT_N / 346.1;     // Beamformer.cpp:59 without 2 pi
+    hipLaunchKernelGGL(k_steer_table, dim3(c->D + 1, 4), dim3(64), 0, nullptr, rows.p, q.p, nyq.p, c->d_grid, c->d_micx, c->M, unit);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (!c->h_steer) {
+        if (hipHostMalloc((void **)&c->h_steer, FB_RING * 16, hipHostMallocDefault) == hipSuccess) std::memset(c->h_steer, 0, FB_RING * 16);
+        else { c->h_steer = nullptr; (void)hipGetLastError(); }
+    }
+    c->d_steer_rows.swap(rows); c->d_steer_q.swap(q); c->d_steer_nyq.swap(nyq); c->d_steer_pred.swap(pred); c->d_steer_miss.swap(miss); c->d_steer_tail.swap(tail);
+    return MCA_HIP_OK;
+}
+
+// ... and the rows of Y for this call, with the miss list that has an entry per row.  Workspaces: each grows on its own (grow_ws), a list
+// that could not be emptied is dropped
 static int steer_prepare(mca_hip_ctx *c, int n_arrays, int n_frames)
 {
-    if (!c->d_steer_rows) {
-        const size_t na = (size_t)c->cfg.max_arrays;
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_rows, (size_t)(c->D + 1) * 4 * 64 * sizeof(float4)));
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_q, (size_t)(c->D + 1) * c->M * 8 * sizeof(float2)));
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_nyq, (size_t)(c->D + 1) * c->M * sizeof(float)));
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_pred, na * sizeof(int)));
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_miss, 3 * sizeof(unsigned long long)));      // running total; the guard's (arrays that had a prediction); the guard's at the end of the previous call
-        if (hipHostMalloc((void **)&c->h_steer, FB_RING * 16, hipHostMallocDefault) == hipSuccess) std::memset(c->h_steer, 0, FB_RING * 16); else { c->h_steer = nullptr; (void)hipGetLastError(); }
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_tail, 2 * na * FFT_H * sizeof(float)));
-        HIP_TRY(c, hipMemset(c->d_steer_pred, 0xff, na * sizeof(int)));
-        HIP_TRY(c, hipMemset(c->d_steer_miss, 0, 3 * sizeof(unsigned long long)));
-        const double unit = (double)c->cfg.sample_rate / (double)FFT_N / 346.1;     // Beamformer.cpp:59 without 2 pi
-        hipLaunchKernelGGL(k_steer_table, dim3(c->D + 1, 4), dim3(64), 0, nullptr, c->d_steer_rows, c->d_steer_q, c->d_steer_nyq, c->d_grid, c->d_micx, c->M, unit);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipDeviceSynchronize());
-    }
+    int rc;
+    if (!c->d_steer_rows && (rc = steer_build(c))) return rc;
     const size_t rows = (size_t)n_arrays * steer_pass_frames(c, n_arrays, n_frames);
-    if (rows > c->steer_Y_rows) {
+    const bool relist = rows + 1 > c->d_steer_mlist.n;                      // an entry per row of Y at most, behind the list's length
+    if (rows * STEER_ROW > c->d_steer_Y.n || relist) {
         HIP_TRY(c, hipDeviceSynchronize());
-        if (c->d_steer_Y) (void)hipFree(c->d_steer_Y);
-        c->d_steer_Y = nullptr; c->steer_Y_rows = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_Y, rows * STEER_ROW * sizeof(float2)));
-        if (c->d_steer_mlist) (void)hipFree(c->d_steer_mlist);
-        c->d_steer_mlist = nullptr;
-        HIP_TRY(c, hipMalloc((void **)&c->d_steer_mlist, (rows + 1) * sizeof(int)));          // an entry per row of Y at most
-        HIP_TRY(c, hipMemset(c->d_steer_mlist, 0, sizeof(int)));
-        c->steer_mlist_dirty = false;
-        c->steer_Y_rows = rows;
+        if ((rc = grow_ws(c, c->d_steer_Y, rows * STEER_ROW, "the rows of the steered spectra")) ||
+            (rc = grow_ws_filled(c, c->d_steer_mlist, rows + 1, 1, 0, "the miss list of the steered path"))) return rc;
+        if (relist) c->steer_mlist_dirty = false;
     }
     return MCA_HIP_OK;
 }
@@ -2164,7 +2091,7 @@ int mca_hip_localise_frames_dev(mca_hip_ctx *c, const float *pcm, long long arra
     int rc = check_stream_args(c, pcm, array_stride, mic_stride, n_arrays, n_frames);
     if (rc) return rc;
     if (!doa_bin) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev is NULL");
-    c->n_lanes_last = 1; c->cur_lane = 0; c->a0 = 0;
+    c->a0 = 0;
     adapt_policy_begin(c, n_arrays, n_frames);
     c->lazy_entry = !c->host_call;
     rc = localise_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, (hipStream_t)stream);
@@ -2182,7 +2109,7 @@ static int separate_frames_dev_bins(mca_hip_ctx *c, const float *pcm, long long 
     int rc = check_stream_args(c, pcm, array_stride, mic_stride, n_arrays, n_frames);
     if (rc) return rc;
     if (!doa_rad || !out_pcm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev/out_pcm_dev is NULL");
-    c->n_lanes_last = 1; c->cur_lane = 0; c->a0 = 0;
+    c->a0 = 0;
     rc = separate_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
     if (rc) return rc;
     c->tail_cur ^= 1;
@@ -2216,7 +2143,7 @@ int mca_hip_process_frames_dev(mca_hip_ctx *c, const float *pcm, long long array
     if (!doa_bin) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev is NULL");
     if (!out_pcm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev/out_pcm_dev is NULL");
     if ((rc = ensure_bf_table(c))) return rc;
-    c->n_lanes_last = 1; c->cur_lane = 0; c->a0 = 0;
+    c->a0 = 0;
     const bool steer = steer_applies(c) && !c->host_call && !c->capturing;
     if (steer && (rc = steer_prepare(c, n_arrays, n_frames))) return rc;
     if (steer) steer_policy_begin(c);
@@ -2273,7 +2200,7 @@ int mca_hip_graph_create(mca_hip_ctx *c, const float *pcm, long long array_strid
     if (!doa_bin && !out_pcm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev and out_pcm_dev are both NULL: nothing to record");
     if (out_pcm && !doa_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL (the separation stage steers with it)");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (doa_bin && (rc = reserve_impl(c, n_arrays, n_frames))) return rc;   // recording must not allocate (a recording runs as one lane)
+    if (doa_bin && (rc = reserve_impl(c, n_arrays, n_frames))) return rc;   // recording must not allocate
     if (out_pcm && (rc = ensure_bf_table(c))) return rc;
     mca_hip_graph *g = new mca_hip_graph();
     g->c = c; g->pcm = pcm; g->array_stride = array_stride; g->mic_stride = mic_stride; g->n_arrays = n_arrays; g->n_frames = n_frames;
@@ -2344,7 +2271,6 @@ int mca_hip_graph_launch(mca_hip_graph *g, void *stream)
     if (g->out_pcm) c->tail_cur ^= 1;
     if (g->doa_bin) {
         c->last_arrays = g->n_arrays; c->last_frames = g->n_frames;
-        c->n_lanes_last = 1; c->lanes[0].last_a0 = 0; c->lanes[0].last_arrays = g->n_arrays;
     }
     return MCA_HIP_OK;
 }
@@ -2471,7 +2397,7 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
             const long long n4 = (long long)na * as / 4;
             hipLaunchKernelGGL(k_i16_to_f32, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s_run, d_i16 + (size_t)a0 * as, d_pcm + (size_t)a0 * as, n4);
         }
-        c->cur_lane = 0; c->a0 = a0;                          // the chunk's arrays on lane 0's workspace, per-array state at its offset
+        c->a0 = a0;                                           // the chunk's arrays on the one workspace, per-array state at its offset
         rc = localise_impl(c, d_pcm + (size_t)a0 * as, as, ms, na, n_frames, d_bin + a0 * fs_, d_rad + a0 * fs_, d_prob + a0 * fs_,
                            energy ? d_en + a0 * fd_ : nullptr, s_run);
         if (!rc && out_pcm) rc = separate_impl(c, d_pcm + (size_t)a0 * as, as, ms, na, n_frames, d_rad + a0 * fs_, d_out + a0 * fo_, s_run, d_bin + a0 * fs_);
@@ -2490,7 +2416,6 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
     (void)hipStreamSynchronize(s_in); (void)hipStreamSynchronize(s_run); (void)hipStreamSynchronize(s_out);
     if (rc) return rc;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
-    c->n_lanes_last = 1; c->lanes[0].last_a0 = 0; c->lanes[0].last_arrays = n_arrays;
     c->e_cur ^= 1;
     if (out_pcm) c->tail_cur ^= 1;
     // pageable result buffers: plain copies now that everything has finished
@@ -2576,14 +2501,8 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
             return fail(c, MCA_HIP_ERR_UNSUPPORTED, "the tracked call cannot be recorded into a HIP graph");
         // the rows and argmaxes of the call, where the caller does not take them
         const size_t rows = (size_t)n_arrays * n_frames;
-        if ((!corr || !argmax) && rows > c->trk_rows) {
-            if (c->d_trk_corr) (void)hipFree(c->d_trk_corr);
-            if (c->d_trk_idx) (void)hipFree(c->d_trk_idx);
-            c->d_trk_corr = nullptr; c->d_trk_idx = nullptr; c->trk_rows = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_trk_corr, rows * c->D * 4));
-            HIP_TRY(c, hipMalloc((void **)&c->d_trk_idx, rows * 4));
-            c->trk_rows = rows;
-        }
+        if (!corr && (rc = grow_ws(c, c->d_trk_corr, rows * c->D, "the tracked call's correlation rows"))) return rc;
+        if (!argmax && (rc = grow_ws(c, c->d_trk_idx, rows, "the tracked call's argmaxes"))) return rc;
         if (!argmax) argmax = c->d_trk_idx;
     }
     if (c->prec == MCA_HIP_SRP_ADAPTIVE) set_call_planes(c, 2);      // the 2-microphone path always runs the exact split
@@ -2594,7 +2513,7 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     if (trk) c->plan_rows = 0;
     if (rc) return rc;
     Gcc2ScanArgs ga{};
-    ga.C = c->ws().d_C; ga.c_planes = c->ws().c_planes; ga.c_plane_stride = c->ws().c_plane; ga.n_frames = n_frames; ga.Dp = c->Dp; ga.D = c->D;
+    ga.C = c->ws.d_C; ga.c_planes = c->ws.c_planes; ga.c_plane_stride = c->ws.c_plane; ga.n_frames = n_frames; ga.Dp = c->Dp; ga.D = c->D;
     // frames per chunk: every chunk re-reads 160 warm-up frames (recursion + DOA smoothing), so long chunks are cheaper;
     // shorter ones for small batches so that a few hundred workgroups exist
     ga.chunk = 128;
@@ -2614,28 +2533,20 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
         // estimation (power + 1e-10 per frame), then voiced = FFTLogPower > floor + 6 dB; the recursions below only see
         // the frames that fired, gated-out frames repeat the previous outputs
         const size_t rows = (size_t)n_arrays * n_frames;
-        if (rows > c->g2_rows) {
-            auto Fr = [](void *q) { if (q) (void)hipFree(q); };
-            Fr(c->d_g2_vidx); Fr(c->d_g2_nv); Fr(c->d_g2_rad); Fr(c->d_g2_prob); Fr(c->d_g2_reset);
-            c->d_g2_vidx = c->d_g2_nv = nullptr; c->d_g2_rad = c->d_g2_prob = nullptr; c->d_g2_reset = nullptr; c->g2_rows = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_g2_vidx, rows * 4));
-            HIP_TRY(c, hipMalloc((void **)&c->d_g2_nv, (size_t)c->cfg.max_arrays * 4));
-            HIP_TRY(c, hipMalloc((void **)&c->d_g2_rad, rows * 4));
-            HIP_TRY(c, hipMalloc((void **)&c->d_g2_prob, rows * 4));
-            HIP_TRY(c, hipMalloc((void **)&c->d_g2_reset, rows));
-            c->g2_rows = rows;
-        }
+        if ((rc = grow_ws(c, c->d_g2_vidx, rows, "the fired frames")) || (rc = grow_ws(c, c->d_g2_nv, (size_t)c->cfg.max_arrays, "the fired frames' counts")) ||
+            (rc = grow_ws(c, c->d_g2_rad, rows, "the gated call's DOAs")) || (rc = grow_ws(c, c->d_g2_prob, rows, "the gated call's probabilities")) ||
+            (rc = grow_ws(c, c->d_g2_reset, rows, "the silence rule's marks"))) return rc;
         GateArgs gg{};
-        gg.power_lin = c->ws().d_power; gg.n_frames = n_frames; gg.fft_n = c->N;
+        gg.power_lin = c->ws.d_power; gg.n_frames = n_frames; gg.fft_n = c->N;
         gg.needed_samples = (int)(3.0 * c->cfg.sample_rate);              // _durationToEstimatePowerFloor (SoundLocalisationImpl.h:77)
         gg.margin_db = 6.f;                                                // _noiseMarginDB (BinauralLocalisation.h:197)
         gg.eps = 1e-10;                                                    // BinauralLocalisation.cpp:391
-        gg.state = c->d_gate_state; gg.voiced = c->ws().d_voiced; gg.power_out = c->ws().d_power_out; gg.post0 = c->d_g2_post0;
+        gg.state = c->d_gate_state; gg.voiced = c->ws.d_voiced; gg.power_out = c->ws.d_power_out; gg.post0 = c->d_g2_post0;
         hipLaunchKernelGGL(k_gate, dim3(n_arrays), dim3(256), 0, st, gg);
         // the silence rule (:530-560): windowsToDecay = 3 * fs / (analysisLength / 2 - 1), int arithmetic, analysisLength = N + 2
         const int windows_to_decay = 3 * c->cfg.sample_rate / c->H;
         if (trk) HIP_TRY(c, hipMemcpyAsync(c->d_trk_sil, c->d_silence, (size_t)n_arrays * 4, hipMemcpyDeviceToDevice, st));   // the counters before the call
-        hipLaunchKernelGGL(k_gcc2_compact, dim3(n_arrays), dim3(256), 0, st, c->ws().d_voiced, n_frames, c->d_g2_vidx, c->d_g2_nv,
+        hipLaunchKernelGGL(k_gcc2_compact, dim3(n_arrays), dim3(256), 0, st, c->ws.d_voiced, n_frames, c->d_g2_vidx, c->d_g2_nv,
                            c->d_g2_post0, c->d_silence, windows_to_decay, c->d_g2_reset);
         ga.vidx = c->d_g2_vidx; ga.nv = c->d_g2_nv; ga.vreset = c->d_g2_reset;
         if (!ga.doa_rad) ga.doa_rad = c->d_g2_rad;                         // the hold-over needs them whatever the caller asked for
@@ -2649,7 +2560,7 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     hipLaunchKernelGGL(k_gcc2_scan, g, dim3(std::max(256, round_up(c->D, 64))), smem, st, ga);   // >= 4 waves: the per-frame argmax / min / sum is one wave per frame
     if (gate) {
         Gcc2FillArgs fa{};
-        fa.voiced = c->ws().d_voiced; fa.n_frames = n_frames; fa.D = c->D;
+        fa.voiced = c->ws.d_voiced; fa.n_frames = n_frames; fa.D = c->D;
         fa.argmax = argmax; fa.doa_rad = ga.doa_rad; fa.prob = ga.prob; fa.corr = corr; fa.corr_state = ga.corr_in;
         fa.last_idx = c->d_last_bin; fa.last_rad = c->d_last_rad; fa.last_prob = c->d_last_prob;
         hipLaunchKernelGGL(k_gcc2_fill, dim3(n_arrays), dim3(1024), 0, st, fa);
@@ -2657,7 +2568,7 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     if (trk) {
         Gcc2TrackArgs ta{};
         ta.corr = ga.corr; ta.corr_state = ga.corr_in; ta.argmax = argmax;
-        if (gate) { ta.voiced = c->ws().d_voiced; ta.post0 = c->d_g2_post0; ta.sil_in = c->d_trk_sil; }
+        if (gate) { ta.voiced = c->ws.d_voiced; ta.post0 = c->d_g2_post0; ta.sil_in = c->d_trk_sil; }
         ta.windows_to_decay = 3 * c->cfg.sample_rate / c->H;
         ta.n_arrays = n_arrays; ta.n_frames = n_frames;
         ta.key_a = -1; ta.state0 = 0; ta.one_kind = -1;
@@ -2668,7 +2579,6 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     HIP_TRY(c, hipGetLastError());
     c->e_cur ^= 1; c->doa_cur ^= 1;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
-    c->n_lanes_last = 1; c->lanes[0].last_a0 = 0; c->lanes[0].last_arrays = n_arrays;
     return MCA_HIP_OK;
 }
 
@@ -2735,20 +2645,17 @@ int mca_hip_gcc2_tracker_attach(mca_hip_ctx *c, const mca_hip_gcc2_tracker_confi
     if (t.sigma_init == 0.0) t.sigma_init = (double)c->step;
     if (t.sigma_step == 0.0) t.sigma_step = (double)c->step;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
+    // built into locals (the state arrays at exactly their blob sizes, tracker_parts) and handed over behind the last step: a failure
+    // leaves the context without a tracker, as it was
     const size_t slots = (size_t)c->cfg.max_arrays + 1;
-    auto drop = [&]() {
-        for (void *q : {(void *)c->d_trk_x, (void *)c->d_trk_sd, (void *)c->d_trk_si, (void *)c->d_trk_sil, (void *)c->d_trk_res}) if (q) (void)hipFree(q);
-        c->d_trk_x = c->d_trk_sd = c->d_trk_res = nullptr; c->d_trk_si = c->d_trk_sil = nullptr;
-    };
-    if (hipMalloc((void **)&c->d_trk_x, slots * t.n_particles * 8) != hipSuccess || hipMalloc((void **)&c->d_trk_sd, slots * 16) != hipSuccess ||
-        hipMalloc((void **)&c->d_trk_si, slots * 16) != hipSuccess || hipMalloc((void **)&c->d_trk_sil, slots * 4) != hipSuccess ||
-        hipMalloc((void **)&c->d_trk_res, 32) != hipSuccess) {
-        (void)hipGetLastError(); drop();
+    DevBuf<double> x, sd, res; DevBuf<int> si, sil;
+    if (x.alloc(slots * t.n_particles) != hipSuccess || sd.alloc(slots * 2) != hipSuccess || si.alloc(slots * 4) != hipSuccess ||
+        sil.alloc(slots) != hipSuccess || res.alloc(4) != hipSuccess)
         return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device memory for the DOA tracker's state");
-    }
+    const int rc = trk_init_state(c, x, sd, si, nullptr);
+    if (rc) return rc;
+    c->d_trk_x.swap(x); c->d_trk_sd.swap(sd); c->d_trk_si.swap(si); c->d_trk_sil.swap(sil); c->d_trk_res.swap(res);
     c->trk = t;
-    const int rc = trk_init_state(c, nullptr);
-    if (rc) { drop(); return rc; }
     c->tracked = true;
     return MCA_HIP_OK;
 }
@@ -2800,12 +2707,10 @@ int mca_hip_copy_gate(mca_hip_ctx *c, unsigned char *voiced, float *power)
     if (c->last_frames == 0) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "no stream call has run yet");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipDeviceSynchronize());
-    for (int i = 0; i < c->n_lanes_last; ++i) {          // every lane holds the flags of its own block of arrays
-        const Workspace &w = c->lanes[i];
-        const size_t n = (size_t)w.last_arrays * c->last_frames, off = (size_t)w.last_a0 * c->last_frames;
-        if (voiced) HIP_TRY(c, hipMemcpy(voiced + off, w.d_voiced, n, hipMemcpyDeviceToHost));
-        if (power) HIP_TRY(c, hipMemcpy(power + off, w.d_power_out, n * 4, hipMemcpyDeviceToHost));
-    }
+    // (a gated call is never worked off in pieces, process_frames_host_impl: the one workspace holds the flags of all its arrays from 0)
+    const size_t n = (size_t)c->last_arrays * c->last_frames;
+    if (voiced) HIP_TRY(c, hipMemcpy(voiced, c->ws.d_voiced, n, hipMemcpyDeviceToHost));
+    if (power) HIP_TRY(c, hipMemcpy(power, c->ws.d_power_out, n * 4, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
 }
 
@@ -2816,12 +2721,8 @@ static int upload_frames(mca_hip_ctx *c, const double *const *frames, int ccs_le
     if (ccs_len != c->N + 2) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "ccs_len != fft_size + 2");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t n = (size_t)c->M * ccs_len;
-    if (c->fr_elems < n) {
-        if (c->d_fr) (void)hipFree(c->d_fr);
-        c->d_fr = nullptr; c->fr_elems = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->d_fr, n * 8));
-        c->fr_elems = n;
-    }
+    const int rc = grow_ws(c, c->d_fr, n, "the frame's spectra");
+    if (rc) return rc;
     // SignalVector = one separate allocation per channel (mcadefs.h:86-88): gather, then one copy
     c->h_stage.resize(n);
     for (int m = 0; m < c->M; ++m) {
@@ -2843,7 +2744,7 @@ int mca_hip_steering_process_frame(mca_hip_ctx *c, const double *const *frames, 
     const float memf = 0.8f;                                                  // SteeringBeamforming.h:70
     const double mu = (double)memf, omu = (double)(1 - memf);
     double *Ein = c->d_E64[c->e64_cur], *Eout = c->d_E64[c->e64_cur ^ 1];
-    hipLaunchKernelGGL(k_frame_srp<double>, dim3(c->D), dim3(256), 0, 0, reinterpret_cast<const C2<double> *>(c->d_fr), c->K, c->D,
+    hipLaunchKernelGGL(k_frame_srp<double>, dim3(c->D), dim3(256), 0, 0, reinterpret_cast<const C2<double> *>(c->d_fr.p), c->K, c->D,
                        c->P, c->d_pairs, c->d_delays, Ein, Eout, mu, omu, c->cfg.gcc_weighting == MCA_HIP_GCC_NONE ? 1 : 0);
     hipLaunchKernelGGL(k_frame_pick<double>, dim3(1), dim3(512), 0, 0, Eout, c->D, c->P, n_sources, c->d_grid, c->d_res,
                        c->d_res + MCA_MAX_SOURCES, c->d_bins);
@@ -2865,15 +2766,10 @@ int mca_hip_beamformer_process_frame(mca_hip_ctx *c, const double *const *frames
     if (!out) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out is NULL");
     int rc = upload_frames(c, frames, ccs_len);
     if (rc) return rc;
-    if (c->out64_elems < (size_t)ccs_len) {
-        if (c->d_out64) (void)hipFree(c->d_out64);
-        c->d_out64 = nullptr; c->out64_elems = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->d_out64, (size_t)ccs_len * 8));
-        c->out64_elems = ccs_len;
-    }
+    if ((rc = grow_ws(c, c->d_out64, (size_t)ccs_len, "the beamformed spectrum"))) return rc;
     hipLaunchKernelGGL(k_frame_beamform<double>, dim3((c->K + 255) / 256), dim3(256), 0, 0,
-                       reinterpret_cast<const C2<double> *>(c->d_fr), c->M, c->K, c->cfg.sample_rate, c->d_micx, DOA,
-                       reinterpret_cast<C2<double> *>(c->d_out64));
+                       reinterpret_cast<const C2<double> *>(c->d_fr.p), c->M, c->K, c->cfg.sample_rate, c->d_micx, DOA,
+                       reinterpret_cast<C2<double> *>(c->d_out64.p));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpy(out, c->d_out64, (size_t)ccs_len * 8, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
@@ -2886,7 +2782,7 @@ int mca_hip_fft_log_power(mca_hip_ctx *c, const double *const *frames, int ccs_l
     int rc = upload_frames(c, frames, ccs_len);
     if (rc) return rc;
     double *dp = c->d_res + 2 * MCA_MAX_SOURCES;
-    hipLaunchKernelGGL(k_frame_power<double>, dim3(1), dim3(256), 0, 0, reinterpret_cast<const C2<double> *>(c->d_fr), c->M, c->K, dp);
+    hipLaunchKernelGGL(k_frame_power<double>, dim3(1), dim3(256), 0, 0, reinterpret_cast<const C2<double> *>(c->d_fr.p), c->M, c->K, dp);
     HIP_TRY(c, hipGetLastError());
     double lin = 0;
     HIP_TRY(c, hipMemcpy(&lin, dp, 8, hipMemcpyDeviceToHost));
@@ -2972,7 +2868,7 @@ int mca_hip_gcc2_process_frame(mca_hip_ctx *c, const double *const *frames, int 
     if (rc) return rc;
     G2FrameState &g = c->g2f;
     const float corr_mem = (float)g.corr_mem, doa_mem = (float)g.doa_mem;
-    const C2<double> *X = reinterpret_cast<const C2<double> *>(c->d_fr);
+    const C2<double> *X = reinterpret_cast<const C2<double> *>(c->d_fr.p);
     double *Ein = c->d_g2f_corr[c->g2f_cur], *Eout = c->d_g2f_corr[c->g2f_cur ^ 1];
     hipLaunchKernelGGL(k_frame_power<double>, dim3(1), dim3(256), 0, 0, X, 2, c->K, c->d_g2f_res + 3);
     // GCC-PHAT at the D delays of the pair (0, 1), corr = (1 - mu) R + mu prev (:438-448)

@@ -22,16 +22,16 @@ struct mca_hip_bmask_ctx {
     std::vector<double> H, center, thr;        // [45][K], [45], [45]
     std::vector<int> lo, hi;
     BmaskTables tab{};
-    float *d_window = nullptr, *d_thr = nullptr;
-    float2 *d_tw = nullptr, *d_kw = nullptr, *d_kp = nullptr;
-    int *d_kb = nullptr, *d_lo = nullptr, *d_hi = nullptr;
-    double *d_Q = nullptr;
-    float *d_tail[2] = {nullptr, nullptr};
-    long long *d_frames = nullptr;
+    DevBuf<float> d_window, d_thr;
+    DevBuf<float2> d_tw, d_kw, d_kp;
+    DevBuf<int> d_kb, d_lo, d_hi;
+    DevBuf<double> d_Q;                        // the state: each array at exactly its state size (bmask_parts)
+    DevBuf<float> d_tail[2];
+    DevBuf<long long> d_frames;
     int tail_cur = 0;
     // frame hooks (double)
-    double *d_thr64 = nullptr, *d_Q64 = nullptr, *d_h = nullptr, *d_x = nullptr, *d_ana = nullptr;   // d_h [45][N] impulse responses (built at the first frameAnalysis), d_ana [2][46 N]
-    int *d_dec = nullptr;
+    DevBuf<double> d_thr64, d_Q64, d_h, d_x, d_ana;   // d_h [45][N] impulse responses (built at the first frameAnalysis), d_ana [2][46 N]
+    DevBuf<int> d_dec;
     StagePool stage;                           // 0..2 host-pointer staging, 3 sums, 4 gains
     std::string err;
 };
@@ -84,17 +84,6 @@ void mel_filterbank(int N, int nb, int fs, double fmin, double fmax, std::vector
     }
 }
 
-void free_bmask(mca_hip_bmask_ctx *c)
-{
-    if (!c) return;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_thr); F(c->d_tw); F(c->d_kw); F(c->d_kp); F(c->d_kb); F(c->d_lo); F(c->d_hi);
-    F(c->d_Q); F(c->d_tail[0]); F(c->d_tail[1]); F(c->d_frames);
-    F(c->d_thr64); F(c->d_Q64); F(c->d_h); F(c->d_x); F(c->d_ana); F(c->d_dec);
-    c->stage.release();
-    delete c;
-}
-
 // h_b = irfft(H_b), [45][N] in double, uploaded once: h_b[n] = (1 / N) sum_k c_k H_b[k] cos(2 pi k n / N) over the band's support
 int build_impulse_responses(mca_hip_bmask_ctx *c)
 {
@@ -111,8 +100,7 @@ int build_impulse_responses(mca_hip_bmask_ctx *c)
             }
             h[(size_t)b * N + n] = acc / (double)N;
         }
-    BHIP_TRY(c, hipMalloc((void **)&c->d_h, h.size() * 8));
-    BHIP_TRY(c, hipMemcpy(c->d_h, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    BHIP_TRY(c, c->d_h.upload(h.data(), h.size()));
     return MCA_HIP_OK;
 }
 
@@ -187,41 +175,37 @@ int mca_hip_bmask_create(const mca_hip_bmask_config *cfg, mca_hip_bmask_ctx **ou
             }
         }
     }
-    if (!compact_ok) { free_bmask(c); return bfail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "a bin is covered by more than two adjacent bands"); }
+    if (!compact_ok) { delete c; return bfail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "a bin is covered by more than two adjacent bands"); }
     const size_t ns = (size_t)cfg->max_streams;
     std::vector<float> win(N);
     for (int n = 0; n < N; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / N));
     std::vector<float2> tw(N / 2);
     for (int i = 0; i < N / 2; ++i) tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / N), (float)(-std::sin(2.0 * M_PI * i / N)));
-#define BUP(dst, src, bytes) do { BHIP_TRY(c, hipMalloc((void **)&(dst), (bytes))); BHIP_TRY(c, hipMemcpy((dst), (src), (bytes), hipMemcpyHostToDevice)); } while (0)
-#define BZ(dst, bytes) do { BHIP_TRY(c, hipMalloc((void **)&(dst), (bytes))); BHIP_TRY(c, hipMemset((dst), 0, (bytes))); } while (0)
     auto body = [&]() -> int {
-        BUP(c->d_window, win.data(), win.size() * 4);
-        BUP(c->d_tw, tw.data(), tw.size() * 8);
-        BUP(c->d_kw, kw.data(), kw.size() * 8); BUP(c->d_kp, kp.data(), kp.size() * 8); BUP(c->d_kb, kb.data(), kb.size() * 4);
-        BUP(c->d_lo, c->lo.data(), BM_BANDS * 4); BUP(c->d_hi, c->hi.data(), BM_BANDS * 4);
-        BUP(c->d_thr, thr32.data(), BM_BANDS * 4);
-        BZ(c->d_Q, ns * BM_BANDS * 8);
-        BZ(c->d_tail[0], ns * 2 * c->hop * 4); BZ(c->d_tail[1], ns * 2 * c->hop * 4);
-        BZ(c->d_frames, ns * 8);
-        BUP(c->d_thr64, c->thr.data(), BM_BANDS * 8);
-        BZ(c->d_Q64, BM_BANDS * 8);
-        BZ(c->d_x, (size_t)N * 8);
-        BZ(c->d_ana, (size_t)2 * (BM_BANDS + 1) * N * 8);
-        BZ(c->d_dec, BM_BANDS * 4);
+        BHIP_TRY(c, c->d_window.upload(win.data(), win.size()));
+        BHIP_TRY(c, c->d_tw.upload(tw.data(), tw.size()));
+        BHIP_TRY(c, c->d_kw.upload(kw.data(), kw.size())); BHIP_TRY(c, c->d_kp.upload(kp.data(), kp.size())); BHIP_TRY(c, c->d_kb.upload(kb.data(), kb.size()));
+        BHIP_TRY(c, c->d_lo.upload(c->lo.data(), BM_BANDS)); BHIP_TRY(c, c->d_hi.upload(c->hi.data(), BM_BANDS));
+        BHIP_TRY(c, c->d_thr.upload(thr32.data(), BM_BANDS));
+        BHIP_TRY(c, c->d_Q.alloc_zero(ns * BM_BANDS));
+        for (int i = 0; i < 2; ++i) BHIP_TRY(c, c->d_tail[i].alloc_zero(ns * 2 * c->hop));
+        BHIP_TRY(c, c->d_frames.alloc_zero(ns));
+        BHIP_TRY(c, c->d_thr64.upload(c->thr.data(), BM_BANDS));
+        BHIP_TRY(c, c->d_Q64.alloc_zero(BM_BANDS));
+        BHIP_TRY(c, c->d_x.alloc_zero((size_t)N));
+        BHIP_TRY(c, c->d_ana.alloc_zero((size_t)2 * (BM_BANDS + 1) * N));
+        BHIP_TRY(c, c->d_dec.alloc_zero(BM_BANDS));
         return MCA_HIP_OK;
     };
     const int rc = body();
-#undef BUP
-#undef BZ
-    if (rc) { g_bmask_create_error = c->err; free_bmask(c); return rc; }
+    if (rc) { g_bmask_create_error = c->err; delete c; return rc; }
     // kernels that take more than 64 KiB of dynamic LDS are told so once, here
     if (smem_synth(N) > 64 * 1024) {
         const void *ka = N == 2048 ? reinterpret_cast<const void *>(k_bmask_analyse_2048) : reinterpret_cast<const void *>(k_bmask_analyse_gen);
         const void *ks = N == 2048 ? reinterpret_cast<const void *>(k_bmask_synth_2048) : reinterpret_cast<const void *>(k_bmask_synth_gen);
         hipError_t e = hipFuncSetAttribute(ka, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_analyse(N));
         if (e == hipSuccess) e = hipFuncSetAttribute(ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_synth(N));
-        if (e != hipSuccess) { free_bmask(c); return bfail(nullptr, MCA_HIP_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { delete c; return bfail(nullptr, MCA_HIP_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); }
     }
     BmaskTables &t = c->tab;
     t.window = c->d_window; t.tw = c->d_tw; t.kb = c->d_kb; t.kw = c->d_kw; t.kp = c->d_kp; t.lo = c->d_lo; t.hi = c->d_hi;
@@ -235,7 +219,7 @@ void mca_hip_bmask_destroy(mca_hip_bmask_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     (void)hipDeviceSynchronize();
-    free_bmask(c);
+    delete c;                                 // every device buffer goes with its member
 }
 
 int mca_hip_bmask_reset(mca_hip_bmask_ctx *c)
@@ -243,11 +227,10 @@ int mca_hip_bmask_reset(mca_hip_bmask_ctx *c)
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     BHIP_TRY(c, hipSetDevice(c->cfg.device));
     BHIP_TRY(c, hipDeviceSynchronize());
-    const size_t ns = (size_t)c->cfg.max_streams;
-    BHIP_TRY(c, hipMemset(c->d_Q, 0, ns * BM_BANDS * 8));
-    for (int i = 0; i < 2; ++i) BHIP_TRY(c, hipMemset(c->d_tail[i], 0, ns * 2 * c->hop * 4));
-    BHIP_TRY(c, hipMemset(c->d_frames, 0, ns * 8));
-    BHIP_TRY(c, hipMemset(c->d_Q64, 0, BM_BANDS * 8));
+    BHIP_TRY(c, hipMemset(c->d_Q, 0, c->d_Q.bytes()));
+    for (int i = 0; i < 2; ++i) BHIP_TRY(c, hipMemset(c->d_tail[i], 0, c->d_tail[i].bytes()));
+    BHIP_TRY(c, hipMemset(c->d_frames, 0, c->d_frames.bytes()));
+    BHIP_TRY(c, hipMemset(c->d_Q64, 0, c->d_Q64.bytes()));
     return MCA_HIP_OK;
 }
 
@@ -403,8 +386,7 @@ namespace {
 constexpr unsigned BMASK_MAGIC = 0x4d43424du;   // "MCBM"
 std::vector<BlobPart> bmask_parts(mca_hip_bmask_ctx *c)
 {
-    const size_t ns = (size_t)c->cfg.max_streams;
-    return {{c->d_Q, ns * BM_BANDS * 8}, {c->d_tail[c->tail_cur], ns * 2 * c->hop * 4}, {c->d_frames, ns * 8}, {c->d_Q64, BM_BANDS * 8}};
+    return {blob_part(c->d_Q), blob_part(c->d_tail[c->tail_cur]), blob_part(c->d_frames), blob_part(c->d_Q64)};
 }
 unsigned bmask_cfg_hash(const mca_hip_bmask_ctx *c)
 {

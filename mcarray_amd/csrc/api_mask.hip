@@ -21,17 +21,17 @@ struct mca_hip_mask_ctx {
     int N = 0, K = 0;
     std::vector<double> H, center, thr;       // [45][K], [45], [45]
     MaskParams hp{};
-    MaskParams *d_mp = nullptr;
-    float *d_window = nullptr;
-    float2 *d_tw = nullptr, *d_kw = nullptr; int *d_kb = nullptr;   // any-length stream kernel
+    DevBuf<MaskParams> d_mp;
+    DevBuf<float> d_window;
+    DevBuf<float2> d_tw, d_kw; DevBuf<int> d_kb;   // any-length stream kernel
     int hop = 0, logH = 0;
-    float *d_Q[2] = {nullptr, nullptr}, *d_noise = nullptr, *d_tail[2] = {nullptr, nullptr};
+    DevBuf<float> d_Q[2], d_noise, d_tail[2];      // the state: each array at exactly its state size (mask_parts)
     int q_cur = 0, tail_cur = 0;
     long long frames_done = 0;
     int streams_in_use = 0;           // n_streams of the first stream call after create / reset: the context counts frames once for all streams
     // frame API (double)
-    double *d_H = nullptr, *d_thr = nullptr, *d_Q64 = nullptr, *d_noise64 = nullptr, *d_io = nullptr;   // d_io: L, R, outL, outR
-    int *d_dec = nullptr;
+    DevBuf<double> d_H, d_thr, d_Q64, d_noise64, d_io;   // d_io: L, R, outL, outR
+    DevBuf<int> d_dec;
     int first_call = 0;
     StagePool stage;
     std::string err;
@@ -79,16 +79,6 @@ void mel_filterbank(int N, int nb, int fs, double fmin, double fmax, std::vector
             H[(size_t)b * K + k] = h;
         }
     }
-}
-
-void free_mask(mca_hip_mask_ctx *c)
-{
-    if (!c) return;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_mp); F(c->d_window); F(c->d_tw); F(c->d_kw); F(c->d_kb); F(c->d_Q[0]); F(c->d_Q[1]); F(c->d_noise); F(c->d_tail[0]); F(c->d_tail[1]);
-    F(c->d_H); F(c->d_thr); F(c->d_Q64); F(c->d_noise64); F(c->d_io); F(c->d_dec);
-    c->stage.release();
-    delete c;
 }
 
 }  // namespace
@@ -146,7 +136,7 @@ int mca_hip_mask_create(const mca_hip_mask_config *cfg, mca_hip_mask_ctx **out)
             }
         }
     }
-    if (!compact_ok) { free_mask(c); return mfail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "a bin is covered by more than two adjacent bands"); }
+    if (!compact_ok) { delete c; return mfail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "a bin is covered by more than two adjacent bands"); }
     if (c->N == FFT_N)
         for (int k = 0; k < c->K; ++k) { hp.kb[k] = kb[k]; hp.kw0[k] = kw[k].x; hp.kw1[k] = kw[k].y; }
     const size_t ns = (size_t)cfg->max_streams;
@@ -154,25 +144,21 @@ int mca_hip_mask_create(const mca_hip_mask_config *cfg, mca_hip_mask_ctx **out)
     for (int n = 0; n < c->N; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / c->N));
     std::vector<float2> tw(c->N / 2);
     for (int i = 0; i < c->N / 2; ++i) tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / c->N), (float)(-std::sin(2.0 * M_PI * i / c->N)));
-#define MUP(dst, src, bytes) do { MHIP_TRY(c, hipMalloc((void **)&(dst), (bytes))); MHIP_TRY(c, hipMemcpy((dst), (src), (bytes), hipMemcpyHostToDevice)); } while (0)
-#define MZ(dst, bytes) do { MHIP_TRY(c, hipMalloc((void **)&(dst), (bytes))); MHIP_TRY(c, hipMemset((dst), 0, (bytes))); } while (0)
     auto body = [&]() -> int {
-        MUP(c->d_mp, &c->hp, sizeof(MaskParams));
-        MUP(c->d_window, win.data(), win.size() * 4);
-        MUP(c->d_tw, tw.data(), tw.size() * 8); MUP(c->d_kw, kw.data(), kw.size() * 8); MUP(c->d_kb, kb.data(), kb.size() * 4);
-        MZ(c->d_Q[0], ns * 45 * 4); MZ(c->d_Q[1], ns * 45 * 4); MZ(c->d_noise, ns * 45 * 4);
-        MZ(c->d_tail[0], ns * 2 * c->hop * 4); MZ(c->d_tail[1], ns * 2 * c->hop * 4);
-        MUP(c->d_H, c->H.data(), c->H.size() * 8);
-        MUP(c->d_thr, c->thr.data(), 45 * 8);
-        MZ(c->d_Q64, 45 * 8); MZ(c->d_noise64, 45 * 8);
-        MZ(c->d_io, (size_t)4 * (c->N + 2) * 8);
-        MZ(c->d_dec, 45 * 4);
+        MHIP_TRY(c, c->d_mp.upload(&c->hp, 1));
+        MHIP_TRY(c, c->d_window.upload(win.data(), win.size()));
+        MHIP_TRY(c, c->d_tw.upload(tw.data(), tw.size())); MHIP_TRY(c, c->d_kw.upload(kw.data(), kw.size())); MHIP_TRY(c, c->d_kb.upload(kb.data(), kb.size()));
+        for (int i = 0; i < 2; ++i) { MHIP_TRY(c, c->d_Q[i].alloc_zero(ns * 45)); MHIP_TRY(c, c->d_tail[i].alloc_zero(ns * 2 * c->hop)); }
+        MHIP_TRY(c, c->d_noise.alloc_zero(ns * 45));
+        MHIP_TRY(c, c->d_H.upload(c->H.data(), c->H.size()));
+        MHIP_TRY(c, c->d_thr.upload(c->thr.data(), 45));
+        MHIP_TRY(c, c->d_Q64.alloc_zero(45)); MHIP_TRY(c, c->d_noise64.alloc_zero(45));
+        MHIP_TRY(c, c->d_io.alloc_zero((size_t)4 * (c->N + 2)));
+        MHIP_TRY(c, c->d_dec.alloc_zero(45));
         return MCA_HIP_OK;
     };
-    int rc = body();
-#undef MUP
-#undef MZ
-    if (rc) { g_mask_create_error = c->err; free_mask(c); return rc; }
+    const int rc = body();
+    if (rc) { g_mask_create_error = c->err; delete c; return rc; }
     *out = c;
     return MCA_HIP_OK;
 }
@@ -182,17 +168,16 @@ void mca_hip_mask_destroy(mca_hip_mask_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     (void)hipDeviceSynchronize();
-    free_mask(c);
+    delete c;                                 // every device buffer goes with its member
 }
 
 int mca_hip_mask_reset(mca_hip_mask_ctx *c)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     MHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const size_t ns = (size_t)c->cfg.max_streams;
-    for (int i = 0; i < 2; ++i) { MHIP_TRY(c, hipMemset(c->d_Q[i], 0, ns * 45 * 4)); MHIP_TRY(c, hipMemset(c->d_tail[i], 0, ns * 2 * c->hop * 4)); }
-    MHIP_TRY(c, hipMemset(c->d_noise, 0, ns * 45 * 4));
-    MHIP_TRY(c, hipMemset(c->d_Q64, 0, 45 * 8)); MHIP_TRY(c, hipMemset(c->d_noise64, 0, 45 * 8));
+    for (int i = 0; i < 2; ++i) { MHIP_TRY(c, hipMemset(c->d_Q[i], 0, c->d_Q[i].bytes())); MHIP_TRY(c, hipMemset(c->d_tail[i], 0, c->d_tail[i].bytes())); }
+    MHIP_TRY(c, hipMemset(c->d_noise, 0, c->d_noise.bytes()));
+    MHIP_TRY(c, hipMemset(c->d_Q64, 0, c->d_Q64.bytes())); MHIP_TRY(c, hipMemset(c->d_noise64, 0, c->d_noise64.bytes()));
     c->frames_done = 0; c->first_call = 0; c->streams_in_use = 0;
     return MCA_HIP_OK;
 }
@@ -301,9 +286,7 @@ namespace {
 constexpr unsigned MASK_MAGIC = 0x4d434d4bu;   // "MCMK"
 std::vector<BlobPart> mask_parts(mca_hip_mask_ctx *c)
 {
-    const size_t ns = (size_t)c->cfg.max_streams;
-    return {{c->d_Q[c->q_cur], ns * 45 * 4}, {c->d_noise, ns * 45 * 4}, {c->d_tail[c->tail_cur], ns * 2 * c->hop * 4},
-            {c->d_Q64, 45 * 8}, {c->d_noise64, 45 * 8}};
+    return {blob_part(c->d_Q[c->q_cur]), blob_part(c->d_noise), blob_part(c->d_tail[c->tail_cur]), blob_part(c->d_Q64), blob_part(c->d_noise64)};
 }
 unsigned mask_cfg_hash(const mca_hip_mask_ctx *c)
 {

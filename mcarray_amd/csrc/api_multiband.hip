@@ -20,14 +20,13 @@ struct mca_hip_mb_ctx {
     float step = 0.f;
     std::vector<double> coef;                 // [nbins][K]
     std::vector<float> grid, delays;          // [D]
-    float *d_window = nullptr, *d_coef = nullptr, *d_grid = nullptr;
-    float2 *d_tw = nullptr, *d_T = nullptr;
-    int *d_lo = nullptr, *d_hi = nullptr;
-    float *d_corr[2] = {nullptr, nullptr}; int corr_cur = 0;
-    double *d_gate = nullptr; float *d_cur = nullptr;
-    // workspace
-    float *d_raw = nullptr, *d_be = nullptr, *d_pf = nullptr, *d_ph = nullptr, *d_hprob = nullptr; int *d_hidx = nullptr;
-    size_t ws_rows = 0;
+    DevBuf<float> d_window, d_coef, d_grid;
+    DevBuf<float2> d_tw, d_T;
+    DevBuf<int> d_lo, d_hi;
+    DevBuf<float> d_corr[2]; int corr_cur = 0;    // the state: each array at exactly its state size (mb_parts)
+    DevBuf<double> d_gate; DevBuf<float> d_cur;
+    // workspace: each buffer grows on its own need
+    DevBuf<float> d_raw, d_be, d_pf, d_ph, d_hprob; DevBuf<int> d_hidx;
     StagePool stage;
     std::string err;
 };
@@ -50,22 +49,17 @@ int bfail(mca_hip_mb_ctx *c, int code, const std::string &msg)
                          std::string(#expr) + ": " + hipGetErrorString(_e));                           \
     } while (0)
 
-void free_mb(mca_hip_mb_ctx *c)
+// what an allocation or an upload failed with: out of memory by its own code, `what` names the buffers
+int hip_fail(mca_hip_mb_ctx *c, hipError_t e, const char *what)
 {
-    if (!c) return;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_window); F(c->d_coef); F(c->d_grid); F(c->d_tw); F(c->d_T); F(c->d_lo); F(c->d_hi);
-    F(c->d_corr[0]); F(c->d_corr[1]); F(c->d_gate); F(c->d_cur);
-    F(c->d_raw); F(c->d_be); F(c->d_pf); F(c->d_ph); F(c->d_hprob); F(c->d_hidx);
-    c->stage.release();
-    delete c;
+    return bfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 int init_state(mca_hip_mb_ctx *c, hipStream_t st)
 {
     const size_t na = (size_t)c->cfg.max_arrays;
-    for (int i = 0; i < 2; ++i) BHIP_TRY(c, hipMemsetAsync(c->d_corr[i], 0, na * c->nb * c->D * 4, st));   // :106-110
-    BHIP_TRY(c, hipMemsetAsync(c->d_gate, 0, na * 4 * 8, st));
+    for (int i = 0; i < 2; ++i) BHIP_TRY(c, c->d_corr[i].zero_async(st));   // :106-110
+    BHIP_TRY(c, c->d_gate.zero_async(st));
     std::vector<float> cur(na * 2);
     for (size_t a = 0; a < na; ++a) { cur[2 * a] = 0.f; cur[2 * a + 1] = -1.f; }                            // :81-82
     BHIP_TRY(c, hipMemcpyAsync(c->d_cur, cur.data(), cur.size() * 4, hipMemcpyHostToDevice, st));
@@ -75,17 +69,9 @@ int init_state(mca_hip_mb_ctx *c, hipStream_t st)
 
 int ensure_ws(mca_hip_mb_ctx *c, size_t rows)
 {
-    if (rows <= c->ws_rows) return MCA_HIP_OK;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_raw); F(c->d_be); F(c->d_pf); F(c->d_ph); F(c->d_hprob); F(c->d_hidx);
-    c->d_raw = c->d_be = c->d_pf = c->d_ph = c->d_hprob = nullptr; c->d_hidx = nullptr; c->ws_rows = 0;
-    BHIP_TRY(c, hipMalloc((void **)&c->d_raw, rows * c->nb * c->D * 4));
-    BHIP_TRY(c, hipMalloc((void **)&c->d_be, rows * c->nb * 4));
-    BHIP_TRY(c, hipMalloc((void **)&c->d_pf, rows * 4));
-    BHIP_TRY(c, hipMalloc((void **)&c->d_ph, rows * 4));
-    BHIP_TRY(c, hipMalloc((void **)&c->d_hprob, rows * 4));
-    BHIP_TRY(c, hipMalloc((void **)&c->d_hidx, rows * 4));
-    c->ws_rows = rows;
+    hipError_t e;
+    if ((e = c->d_raw.grow(rows * c->nb * c->D)) || (e = c->d_be.grow(rows * c->nb)) || (e = c->d_pf.grow(rows)) || (e = c->d_ph.grow(rows)) ||
+        (e = c->d_hprob.grow(rows)) || (e = c->d_hidx.grow(rows))) return hip_fail(c, e, "the workspace of the call");
     return MCA_HIP_OK;
 }
 
@@ -161,25 +147,15 @@ int mca_hip_mb_create(const mca_hip_mb_config *cfg, mca_hip_mb_ctx **out)
     std::vector<float2> tw(c->N / 2);
     for (int i = 0; i < c->N / 2; ++i) tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / c->N), (float)(-std::sin(2.0 * M_PI * i / c->N)));
 
-    int rc = MCA_HIP_OK;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        BHIP_TRY(c, hipMalloc(dst, bytes));
-        BHIP_TRY(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return MCA_HIP_OK;
-    };
-    auto zalloc = [&](void **dst, size_t bytes) -> int {
-        BHIP_TRY(c, hipMalloc(dst, bytes));
-        BHIP_TRY(c, hipMemset(*dst, 0, bytes));
-        return MCA_HIP_OK;
-    };
     const size_t na = (size_t)cfg->max_arrays;
-    if ((rc = up((void **)&c->d_window, win.data(), win.size() * 4)) || (rc = up((void **)&c->d_tw, tw.data(), tw.size() * 8)) ||
-        (rc = up((void **)&c->d_coef, coef_f.data(), coef_f.size() * 4)) || (rc = up((void **)&c->d_grid, c->grid.data(), D * 4)) ||
-        (rc = up((void **)&c->d_T, T.data(), T.size() * 8)) || (rc = up((void **)&c->d_lo, lo.data(), nb * 4)) || (rc = up((void **)&c->d_hi, hi.data(), nb * 4)) ||
-        (rc = zalloc((void **)&c->d_corr[0], na * nb * D * 4)) || (rc = zalloc((void **)&c->d_corr[1], na * nb * D * 4)) ||
-        (rc = zalloc((void **)&c->d_gate, na * 4 * 8)) || (rc = zalloc((void **)&c->d_cur, na * 2 * 4)) || (rc = init_state(c, nullptr))) {
-        g_mb_create_error = c->err; free_mb(c); return rc;
-    }
+    hipError_t e;
+    int rc = MCA_HIP_OK;
+    if ((e = c->d_window.upload(win.data(), win.size())) || (e = c->d_tw.upload(tw.data(), tw.size())) ||
+        (e = c->d_coef.upload(coef_f.data(), coef_f.size())) || (e = c->d_grid.upload(c->grid.data(), D)) ||
+        (e = c->d_T.upload(T.data(), T.size())) || (e = c->d_lo.upload(lo.data(), nb)) || (e = c->d_hi.upload(hi.data(), nb)) ||
+        (e = c->d_corr[0].alloc_zero(na * nb * D)) || (e = c->d_corr[1].alloc_zero(na * nb * D)) ||
+        (e = c->d_gate.alloc_zero(na * 4)) || (e = c->d_cur.alloc_zero(na * 2))) rc = hip_fail(c, e, "device memory for the tables and the state of the context");
+    if (rc || (rc = init_state(c, nullptr))) { g_mb_create_error = c->err; delete c; return rc; }
     *out = c;
     return MCA_HIP_OK;
 }
@@ -189,7 +165,7 @@ void mca_hip_mb_destroy(mca_hip_mb_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     (void)hipDeviceSynchronize();
-    free_mb(c);
+    delete c;                                 // every device buffer goes with its member
 }
 
 int mca_hip_mb_num_steps(const mca_hip_mb_ctx *c) { return c ? c->D : MCA_HIP_ERR_INVALID_ARGUMENT; }
@@ -283,8 +259,7 @@ namespace {
 constexpr unsigned MB_MAGIC = 0x4d434d42u;     // "MCMB"
 std::vector<BlobPart> mb_parts(mca_hip_mb_ctx *c)
 {
-    const size_t na = (size_t)c->cfg.max_arrays;
-    return {{c->d_corr[c->corr_cur], na * c->nb * c->D * 4}, {c->d_gate, na * 4 * 8}, {c->d_cur, na * 2 * 4}};
+    return {blob_part(c->d_corr[c->corr_cur]), blob_part(c->d_gate), blob_part(c->d_cur)};
 }
 unsigned mb_cfg_hash(const mca_hip_mb_ctx *c)
 {

@@ -19,11 +19,11 @@ struct mca_hip_tgcc_ctx {
     double dist = 0;
     int W = 0, hop = 0, nd = 0, W8 = 0, needed = 0, rem = 0;
     size_t smem = 0, smem_hook = 0;
-    double *d_state = nullptr;                     // [max_arrays][TGCC_STATE]
-    double *d_hook_state = nullptr;                // [TGCC_STATE] the frame hook's module
-    double *d_hook_in = nullptr;                   // padded channels of one double frame
-    double *d_hook_res = nullptr, *d_hook_out = nullptr, *d_hook_index = nullptr;
-    double *d_res = nullptr; size_t ws_rows = 0;   // [rows][TGCC_RES]
+    DevBuf<double> d_state;                        // [max_arrays][TGCC_STATE]
+    DevBuf<double> d_hook_state;                   // [TGCC_STATE] the frame hook's module
+    DevBuf<double> d_hook_in;                      // padded channels of one double frame
+    DevBuf<double> d_hook_res, d_hook_out, d_hook_index;
+    DevBuf<double> d_res;                          // workspace: [rows][TGCC_RES]
     StagePool stage;
     std::string err;
 };
@@ -46,34 +46,21 @@ int tfail(mca_hip_tgcc_ctx *c, int code, const std::string &msg)
                          std::string(#expr) + ": " + hipGetErrorString(_e));                           \
     } while (0)
 
-void free_tgcc(mca_hip_tgcc_ctx *c)
-{
-    if (!c) return;
-    auto F = [](void *p) { if (p) (void)hipFree(p); };
-    F(c->d_state); F(c->d_hook_state); F(c->d_hook_in); F(c->d_hook_res); F(c->d_hook_out); F(c->d_hook_index); F(c->d_res);
-    c->stage.release();
-    delete c;
-}
-
 // _currentDOA = 0, _prob = -1 (:88-89), _powerFloor = 0, nothing consumed, not estimated
 int init_state(mca_hip_tgcc_ctx *c, hipStream_t st)
 {
     const size_t na = (size_t)c->cfg.max_arrays;
     std::vector<double> s((na + 1) * TGCC_STATE, 0.0);
     for (size_t a = 0; a <= na; ++a) s[a * TGCC_STATE + 1] = -1.0;
-    THIP_TRY(c, hipMemcpyAsync(c->d_state, s.data(), na * TGCC_STATE * 8, hipMemcpyHostToDevice, st));
-    THIP_TRY(c, hipMemcpyAsync(c->d_hook_state, s.data() + na * TGCC_STATE, TGCC_STATE * 8, hipMemcpyHostToDevice, st));
+    THIP_TRY(c, hipMemcpyAsync(c->d_state, s.data(), c->d_state.bytes(), hipMemcpyHostToDevice, st));
+    THIP_TRY(c, hipMemcpyAsync(c->d_hook_state, s.data() + na * TGCC_STATE, c->d_hook_state.bytes(), hipMemcpyHostToDevice, st));
     THIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
 int ensure_ws(mca_hip_tgcc_ctx *c, size_t rows)
 {
-    if (rows <= c->ws_rows) return MCA_HIP_OK;
-    if (c->d_res) (void)hipFree(c->d_res);
-    c->d_res = nullptr; c->ws_rows = 0;
-    THIP_TRY(c, hipMalloc((void **)&c->d_res, rows * TGCC_RES * 8));
-    c->ws_rows = rows;
+    THIP_TRY(c, c->d_res.grow(rows * TGCC_RES));
     return MCA_HIP_OK;
 }
 
@@ -123,15 +110,15 @@ int mca_hip_tgcc_create(const mca_hip_tgcc_config *cfg, mca_hip_tgcc_ctx **out)
     c->smem = c->smem_hook + (size_t)4 * (2 * c->W8 + TGCC_RPAD_FRONT + TGCC_RPAD_BACK);
     int rc = MCA_HIP_OK;
     auto setup = [&]() -> int {
-        THIP_TRY(c, hipMalloc((void **)&c->d_state, (size_t)cfg->max_arrays * TGCC_STATE * 8));
-        THIP_TRY(c, hipMalloc((void **)&c->d_hook_state, TGCC_STATE * 8));
-        THIP_TRY(c, hipMalloc((void **)&c->d_hook_in, (size_t)(2 * c->W8 + TGCC_RPAD_FRONT + TGCC_RPAD_BACK) * 8));
-        THIP_TRY(c, hipMalloc((void **)&c->d_hook_res, TGCC_RES * 8));
-        THIP_TRY(c, hipMalloc((void **)&c->d_hook_out, 5 * 8));
-        THIP_TRY(c, hipMalloc((void **)&c->d_hook_index, (size_t)nd * 8));
+        THIP_TRY(c, c->d_state.alloc((size_t)cfg->max_arrays * TGCC_STATE));      // (the state arrays at exactly their state sizes, tgcc_parts)
+        THIP_TRY(c, c->d_hook_state.alloc(TGCC_STATE));
+        THIP_TRY(c, c->d_hook_in.alloc((size_t)(2 * c->W8 + TGCC_RPAD_FRONT + TGCC_RPAD_BACK)));
+        THIP_TRY(c, c->d_hook_res.alloc(TGCC_RES));
+        THIP_TRY(c, c->d_hook_out.alloc(5));
+        THIP_TRY(c, c->d_hook_index.alloc((size_t)nd));
         return init_state(c, nullptr);
     };
-    if ((rc = setup())) { g_tgcc_create_error = c->err; free_tgcc(c); return rc; }
+    if ((rc = setup())) { g_tgcc_create_error = c->err; delete c; return rc; }
     *out = c;
     return MCA_HIP_OK;
 }
@@ -141,7 +128,7 @@ void mca_hip_tgcc_destroy(mca_hip_tgcc_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     (void)hipDeviceSynchronize();
-    free_tgcc(c);
+    delete c;                                 // every device buffer goes with its member
 }
 
 int mca_hip_tgcc_get_geometry(const mca_hip_tgcc_ctx *c, int *window, int *hop, int *nd)
@@ -257,7 +244,7 @@ namespace {
 constexpr unsigned TGCC_MAGIC = 0x4d435447u;     // "MCTG"
 std::vector<BlobPart> tgcc_parts(mca_hip_tgcc_ctx *c)
 {
-    return {{c->d_state, (size_t)c->cfg.max_arrays * TGCC_STATE * 8}, {c->d_hook_state, TGCC_STATE * 8}};
+    return {blob_part(c->d_state), blob_part(c->d_hook_state)};
 }
 unsigned tgcc_cfg_hash(const mca_hip_tgcc_ctx *c)
 {

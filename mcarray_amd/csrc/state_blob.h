@@ -10,6 +10,8 @@
 namespace mca {
 
 struct BlobPart { void *ptr; size_t bytes; };
+// a device buffer that is allocated at exactly its state size (devbuf.h) as a part
+template <typename Buf> BlobPart blob_part(const Buf &b) { return {b.p, b.bytes()}; }
 struct BlobHeader { unsigned magic; int version; unsigned cfg_hash; int pad; long long host[4]; };
 
 inline unsigned blob_fnv(const void *data, size_t n, unsigned h = 2166136261u)

@@ -1,0 +1,246 @@
+"""Bytes of the main context's and the four module contexts' calls of this build against an older build of the library (the
+yardstick of a refactor of their host layer).
+usage: python tools/compare_builds.py PARENT_LIB
+
+The frame is tools/compare_mvdr_builds.py's: the same inputs go through PARENT_LIB and through mcarray_amd/libmcarray_hip.so, each in
+a fresh child process (MCA_HIP_LIB names the library) under a time limit of its own; the second child is not started when the first
+one fails; a child leaves one SHA-256 per case over everything the case returns, the state blob included; this process requires
+equal digests (exit code 1 otherwise) and never opens the GPU itself.
+
+Cases (2 arrays of max_arrays = 3, calls of 64, 160 and 64 frames unless said otherwise; MCA_HIP_ADAPT_MIN_ROWS = 64, adaptive_fallback
+OFF and candidate columns on, so the small batches run coarse + repair whatever the reports say):
+  device-pointer stream calls in the four precisions: 8-microphone ULA, the same with the power gate, 16-microphone ULA, 4 microphones;
+  fft_size 512 and 2048 at 4 and 8 microphones; two sources on a non-uniform array;
+  the host-pointer entry points: pageable, page-locked (the chunked path), 16-bit PCM, and under MCA_HIP_WS_MAX_MB = 1 (the sliced path);
+  a graph: 4 launches, an eager call that grows the workspace, 2 more launches;
+  the gated 2-microphone path with a tracker (the larger call takes no rows / argmaxes), its frame hook, setProbability;
+  the double frame API; the multiband, temporal-GCC, mask and bmask modules: stream calls of 6, 40 and 6 frames and their frame hooks."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import compare_mvdr_builds as frame                               # noqa: E402
+
+A_MAX, A = 3, 2
+CALLS = (64, 160, 64)
+XS4 = [0.05 * m for m in range(4)]
+
+
+def child(out_path):
+    import json
+    os.environ["MCA_HIP_ADAPT_MIN_ROWS"] = "64"                   # read by mca_hip_create
+    os.environ["MCA_HIP_ADAPT_CAND"] = "1"
+    os.environ.pop("MCA_HIP_ADAPT_FALLBACK", None)
+    api, np, has = frame.load_lib()
+    import torch
+    from mcarray_amd import synth
+    dev = torch.device("cuda:0")
+    res = {}
+    precisions = (("FP32", api.SRP_FP32), ("FP16", api.SRP_FP16), ("FP16X3", api.SRP_FP16X3), ("ADAPTIVE", api.SRP_ADAPTIVE))
+
+    def pcm_of(xs, fs, hop, frames, seed, quiet_frames=0):
+        pcm = np.stack([synth.noise_source_stream(xs, np.deg2rad(-35.0 + 50 * a), fs, (frames + 1) * hop, seed + a, snr_db=12.0) for a in range(A)])
+        pcm[:, :, :quiet_frames * hop] *= 1e-3
+        return pcm.astype(np.float32)
+
+    def ctx_of(xs, fs, N, prec, S=1, floor=False, step=0.5):
+        return api.Context(fs, xs, N, step, S, use_power_floor=floor, srp_precision=prec, max_arrays=A_MAX, adaptive_fallback=False)
+
+    def dev_call(ctx, chunk, F, parts):
+        hop = ctx.hop
+        r = [torch.zeros((A, F, ctx.S), dtype=torch.int32, device=dev), torch.zeros((A, F, ctx.S), device=dev), torch.zeros((A, F, ctx.S), device=dev),
+             torch.zeros((A, F, ctx.D), device=dev), torch.zeros((A, ctx.S, F * hop), device=dev)]
+        ctx.process_frames_dev(torch.from_numpy(chunk.copy()).to(dev), F, *r)
+        torch.cuda.synchronize()
+        parts += [t.cpu().numpy() for t in r]
+
+    def dev_stream(name, ctx, pcm, calls=CALLS):
+        parts, t0 = [], 0
+        for F in calls:
+            dev_call(ctx, pcm[:, :, t0 * ctx.hop:(t0 + F + 1) * ctx.hop], F, parts)
+            t0 += F
+        parts.append(np.frombuffer(ctx.state_save(), dtype=np.uint8))
+        ctx.close()
+        res[name] = frame.digest(*parts)
+
+    total = sum(CALLS)
+    for pname, prec in precisions:
+        for name, xs, floor in (("ULA8", synth.ULA8, False), ("ULA8 gated", synth.ULA8, True), ("ULA16", synth.ULA16, False), ("4 microphones", XS4, False)):
+            dev_stream("dev stream, %s, %s" % (name, pname), ctx_of(xs, 48000, 1024, prec, floor=floor), pcm_of(xs, 48000, 512, total, 500, 100 if floor else 0))
+        for N in (512, 2048):
+            for M in (4, 8):
+                xs = [0.04 * m for m in range(M)]
+                dev_stream("dev stream, N = %d, %d microphones, %s" % (N, M, pname), ctx_of(xs, 48000, N, prec), pcm_of(xs, 48000, N // 2, total, 510))
+    for pname, prec in precisions[:3]:
+        dev_stream("dev stream, S = 2 on a non-uniform array, %s" % pname, ctx_of(synth.REEM_C, 48000, 1024, prec, S=2, step=5.0),
+                   pcm_of(synth.REEM_C, 48000, 512, total, 520))
+
+    # the host-pointer entry points
+    def host_stream(name, ctx, pcm, convert=lambda x: x, into=None):
+        parts, t0 = [], 0
+        for F in CALLS:
+            r = ctx.process_frames_host(convert(pcm[:, :, t0 * ctx.hop:(t0 + F + 1) * ctx.hop]), want_energy=True, into=into(F) if into else None)
+            parts += [np.array(r[k]) for k in ("bin", "doa", "prob", "energy", "out", "voiced", "power") if r.get(k) is not None]
+            t0 += F
+        parts.append(np.frombuffer(ctx.state_save(), dtype=np.uint8))
+        ctx.close()
+        res[name] = frame.digest(*parts)
+
+    pcm8 = pcm_of(synth.ULA8, 48000, 512, total, 530, 100)
+    for pname, prec in (precisions[0], precisions[3]):
+        for floor in (False, True):
+            tag = "%s%s" % (pname, ", gated" if floor else "")
+            host_stream("host stream, pageable, %s" % tag, ctx_of(synth.ULA8, 48000, 1024, prec, floor=floor), pcm8)
+            host_stream("host stream, 16-bit PCM, %s" % tag, ctx_of(synth.ULA8, 48000, 1024, prec, floor=floor), pcm8,
+                        convert=lambda x: np.ascontiguousarray(np.clip(np.rint(x * 20000.0), -32768, 32767).astype(np.int16)))
+            pins = []
+
+            def pinned(x):
+                b = api.PinnedBuffer(x.shape, np.float32)
+                b.array[...] = x
+                pins.append(b)
+                return b.array
+            host_stream("host stream, page-locked input (chunks of arrays), %s" % tag, ctx_of(synth.ULA8, 48000, 1024, prec, floor=floor), pcm8, convert=pinned)
+            for b in pins:
+                b.close()
+            os.environ["MCA_HIP_WS_MAX_MB"] = "1"
+            sliced = ctx_of(synth.ULA8, 48000, 1024, prec, floor=floor)
+            del os.environ["MCA_HIP_WS_MAX_MB"]
+            host_stream("host stream, pageable, MCA_HIP_WS_MAX_MB = 1 (sliced), %s" % tag, sliced, pcm8)
+
+    # a graph: 4 launches, an eager call that grows the workspace (its state saved and restored), 2 more launches
+    for pname, prec in (precisions[0], precisions[3]):
+        ctx = ctx_of(synth.ULA8, 48000, 1024, prec)
+        F, hop = 64, 512
+        pcm = pcm_of(synth.ULA8, 48000, hop, 6 * F, 540)
+        buf = dict(pcm=torch.zeros((A, 8, (F + 1) * hop), device=dev), bin=torch.zeros((A, F, 1), dtype=torch.int32, device=dev), rad=torch.zeros((A, F, 1), device=dev),
+                   prob=torch.zeros((A, F, 1), device=dev), energy=torch.zeros((A, F, ctx.D), device=dev), out=torch.zeros((A, 1, F * hop), device=dev))
+        g = ctx.graph_create(buf["pcm"], F, buf["bin"], buf["rad"], buf["prob"], buf["energy"], buf["out"])
+        parts = []
+        for i in range(6):
+            if i == 4:
+                blob = ctx.state_save()
+                dev_call(ctx, pcm[:, :, :(160 + 1) * hop], 160, [])
+                ctx.state_load(blob)
+            buf["pcm"].copy_(torch.from_numpy(pcm[:, :, i * F * hop:(i * F + F + 1) * hop].copy()))
+            g.launch()
+            torch.cuda.synchronize()
+            parts += [buf[k].cpu().numpy() for k in ("bin", "rad", "prob", "energy", "out")]
+        parts.append(np.frombuffer(ctx.state_save(), dtype=np.uint8))
+        g.close()
+        ctx.close()
+        res["graph: 4 launches, an eager growth, 2 launches, %s" % pname] = frame.digest(*parts)
+
+    # the gated 2-microphone path with a tracker, its frame hook and setProbability
+    fs, N = 16000, 1024
+    hop = N // 2
+    pcm2 = pcm_of(synth.BINAURAL, fs, hop, total, 550, 100)
+    ctx = api.Context(fs, synth.BINAURAL, N, 3.0, 1, True, max_arrays=A_MAX)
+    ctx.gcc2_tracker_attach(seed=0x5EED0001)
+    parts, t0 = [], 0
+    for F in CALLS:
+        full = F != max(CALLS)
+        r = [torch.zeros((A, F), device=dev), torch.zeros((A, F), dtype=torch.int32, device=dev) if full else None, torch.zeros((A, F), device=dev),
+             torch.zeros((A, F), dtype=torch.uint8, device=dev), torch.zeros((A, F), dtype=torch.int32, device=dev),
+             torch.zeros((A, F, ctx.D), device=dev) if full else None]
+        ctx.gcc2_tracked_frames_dev(torch.from_numpy(pcm2[:, :, t0 * hop:(t0 + F + 1) * hop].copy()).to(dev), F, *r)
+        torch.cuda.synchronize()
+        parts += [t.cpu().numpy() for t in r if t is not None]
+        t0 += F
+    parts.append(ctx.gcc2_set_probability(np.linspace(-1.2, 1.2, 7), 1))
+    rng = np.random.default_rng(560)
+    for _ in range(3):
+        fr = rng.standard_normal((2, N + 2))
+        fr[:, 1] = 0.0
+        fr[:, N + 1] = 0.0
+        h = ctx.gcc2_process_frame(fr)
+        parts += [np.asarray([h["doa"], h["prob"], h["power"], float(h["argmax"]), float(h["fired"]), float(h["track"])]), h["corr"]]
+    parts.append(np.frombuffer(ctx.state_save(), dtype=np.uint8))
+    ctx.close()
+    res["gated 2-microphone path with a tracker, frame hook, setProbability"] = frame.digest(*parts)
+    plain = api.Context(fs, synth.BINAURAL, N, 3.0, 1, True, max_arrays=A_MAX)
+    parts, t0 = [], 0
+    for F in CALLS:
+        r = plain.gcc2_frames_host(pcm2[:, :, t0 * hop:(t0 + F + 1) * hop], want_corr=True)
+        parts += [r[k] for k in ("argmax", "doa", "prob", "corr", "voiced", "power")]
+        t0 += F
+    parts.append(np.frombuffer(plain.state_save(), dtype=np.uint8))
+    plain.close()
+    res["gated 2-microphone path, host calls"] = frame.digest(*parts)
+
+    # the double frame API
+    ctx = api.Context(16000, XS4, 256, 5.0, 2)
+    parts = []
+    for _ in range(4):
+        fr = rng.standard_normal((4, 258))
+        fr[:, 1] = 0.0
+        fr[:, 257] = 0.0
+        doa, prob, bins = ctx.steering_process_frame(fr, 2)
+        parts += [doa, prob, bins, ctx.beamformer_process_frame(fr, float(doa[0])), np.asarray([ctx.fft_log_power(fr)]), ctx.energy()]
+    parts.append(np.frombuffer(ctx.state_save(), dtype=np.uint8))
+    ctx.close()
+    res["double frame API: steering, beamformer, power"] = frame.digest(*parts)
+
+    # the four modules: stream calls of 6, 40 and 6 frames, then the frame hooks
+    def noise(n, seed):
+        return np.stack([synth.noise_source_stream(synth.BINAURAL, np.deg2rad(20.0 - 45 * a), 16000, n, seed + a) for a in range(A)]).astype(np.float32)
+
+    def blob(m):
+        return np.frombuffer(m.state_save(), dtype=np.uint8)
+
+    frames = (6, 40, 6)
+    m, parts = api.MultibandBinarualLocalisation(16000, synth.BINAURAL, nbins=5, use_power_floor=False, max_arrays=A_MAX), []
+    x = noise((max(frames) + 1) * m.hop, 600)
+    for F in frames:
+        r = m.process(x[:, :, :(F + 1) * m.hop], want_bands=True)
+        parts += [r[k] for k in ("doa", "prob", "voiced", "power", "band_idx", "energy_in_doa", "band_corr")]
+    parts.append(blob(m))
+    m.close()
+    res["multiband module"] = frame.digest(*parts)
+
+    m, parts = api.TemporalGCCBinauralLocalisation(16000, synth.BINAURAL, use_power_floor=False, max_arrays=A_MAX), []
+    x = noise((max(frames) - 1) * m.hop + m.W, 610)
+    for F in frames:
+        r = m.process(x[:, :, :(F - 1) * m.hop + m.W], want_index=True)
+        parts += [r[k] for k in ("doa", "prob", "voiced", "power", "delay_idx", "index")]
+    h = m.process_frame(x[0, 0, :m.W].astype(np.float64), x[0, 1, :m.W].astype(np.float64))
+    parts += [np.asarray([h["doa"], h["prob"], h["power"], float(h["delay_idx"]), float(h["voiced"])]), h["index"], blob(m)]
+    m.close()
+    res["temporal-GCC module and its frame hook"] = frame.digest(*parts)
+
+    m, parts = api.FastBinauralMasking(16000, 0.086, 100.0, 7000.0, fft_size=512, max_streams=A_MAX), []
+    x = noise((max(frames) + 1) * 256, 620)
+    for F in frames:
+        parts += list(m.process(x[:, :, :(F + 1) * 256]))
+    spec = rng.standard_normal((2, 514))
+    spec[:, 1] = 0.0
+    spec[:, 513] = 0.0
+    parts += list(m.process_parametrisation(spec[0], spec[1])) + [blob(m)]
+    m.close()
+    res["mask module and its frame hook"] = frame.digest(*parts)
+
+    m, parts = api.BinauralMaskingImpl(16000, 0.086, 100.0, 7000.0, max_streams=A_MAX), []
+    x = noise((max(frames) + 1) * m.hop, 630)
+    for F in frames:
+        parts += list(m.process(x[:, :, :(F + 1) * m.hop]))
+    ana = [m.frame_analysis(x[0, c, :m.W].astype(np.float64), channel=c) for c in (0, 1)]
+    left, right, dec = m.process_parametrisation(ana[0], ana[1])
+    parts += ana + [left, right, dec, m.frame_synthesis(left, channel=0), m.frame_synthesis(right, channel=1), blob(m)]
+    m.close()
+    res["bmask module and its frame hooks"] = frame.digest(*parts)
+
+    with open(out_path, "w") as f:
+        json.dump(res, f)
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--child":
+        return child(sys.argv[2])
+    if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
+        sys.exit(__doc__)
+    par, new = frame.run_both(__file__, sys.argv[1])
+    sys.exit(frame.report(par, new, "outputs and state blobs", sys.argv[1]))
+
+
+if __name__ == "__main__":
+    main()

@@ -33,7 +33,8 @@ def digest(*arrays):
     return h.hexdigest()
 
 
-def child(out_path):
+def load_lib():
+    """(in a child) the library MCA_HIP_LIB names, bound to the entry points it has -> (api, np, has)"""
     import ctypes as C
     import numpy as np
     sys.path.insert(0, ROOT)
@@ -42,7 +43,11 @@ def child(out_path):
     probe = C.CDLL(_lib.LIB_PATH)
     _lib.SYMBOLS = [sym for sym in _lib.SYMBOLS if hasattr(probe, sym[0])]     # an older build: what it lacks stays unbound
     lib = _lib.load()
-    has = lambda name: hasattr(lib, name)
+    return api, np, lambda name: hasattr(lib, name)
+
+
+def child(out_path):
+    api, np, has = load_lib()
     res = {}
 
     def run(name, bf, calls, streams):
@@ -185,33 +190,44 @@ def host_layer_cases(api, np, has, res):
         res["spectrum, then tracks configured, seeded, updated and read"] = digest(*parts)
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--child":
-        return child(sys.argv[2])
-    if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
-        sys.exit(__doc__)
+def run_both(script, parent_lib, seconds=CHILD_SECONDS):
+    """`script --child OUT` once per library, the parent's first: each a fresh process under its own time limit, the second not
+    started when the first fails -> the two dicts of digests (parent's, this build's).  This process never opens the GPU."""
     got = []
     with tempfile.TemporaryDirectory() as tmp:
-        for tag, lib in (("parent", os.path.abspath(sys.argv[1])), ("this", None)):
+        for tag, lib in (("parent", os.path.abspath(parent_lib)), ("this", None)):
             env = dict(os.environ)
             env.pop("MCA_HIP_LIB", None)
             if lib:
                 env["MCA_HIP_LIB"] = lib
             out = os.path.join(tmp, tag + ".json")
-            rc = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), sys.executable, os.path.abspath(__file__), "--child", out], env=env).returncode
+            rc = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable, os.path.abspath(script), "--child", out], env=env).returncode
             if rc != 0:
                 sys.exit("%s build (%s): the child ended with %d; nothing further is started" % (tag, lib or "default", rc))
             got.append(json.load(open(out)))
-    par, new = got
+    return got
+
+
+def report(par, new, what, parent_lib):
+    """prints a line per case the older build ran -> the exit code: 1 on a case this build lacks or on a differing digest"""
     missing = [name for name in par if name not in new]
     if missing:
         print("this build did not run %d of the parent's %d cases: %s ..." % (len(missing), len(par), missing[0]))
-        sys.exit(1)
+        return 1
     bad = [name for name in par if par[name] != new[name]]
     for name in par:
         print("%s  %s  %s" % ("DIFFERENT" if name in bad else "equal    ", new[name][:16], name))
-    print("%d cases, %d with different bytes (spectra, audio, covariance) against %s" % (len(par), len(bad), sys.argv[1]))
-    sys.exit(1 if bad else 0)
+    print("%d cases, %d with different bytes (%s) against %s" % (len(par), len(bad), what, parent_lib))
+    return 1 if bad else 0
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--child":
+        return child(sys.argv[2])
+    if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
+        sys.exit(__doc__)
+    par, new = run_both(__file__, sys.argv[1])
+    sys.exit(report(par, new, "spectra, audio, covariance", sys.argv[1]))
 
 
 if __name__ == "__main__":
