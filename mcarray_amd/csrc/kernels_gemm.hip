@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_srp_gemm_f32(GemmArgs p)
     // K range of this workgroup (split-K over blockIdx.z: partial map z goes to C + z * c_plane_elems)
     const int nk_all = p.Kp / G32_BK, per = (nk_all + gridDim.z - 1) / gridDim.z;
     const int kt0 = blockIdx.z * per, nk = min(kt0 + per, nk_all);
-    G32_GLOAD(kt0 * G32_BK);
+    if (kt0 < nk) G32_GLOAD(kt0 * G32_BK);     // (an empty split -- plan_gemm cuts some K ranges into a trailing one -- loads nothing and leaves a zero tile)
     for (int kt = kt0; kt < nk; ++kt) {
         As[akq * 4 + 0][ar] = ra0.x; As[akq * 4 + 1][ar] = ra0.y; As[akq * 4 + 2][ar] = ra0.z; As[akq * 4 + 3][ar] = ra0.w;
         As[akq * 4 + 0][ar + 64] = ra1.x; As[akq * 4 + 1][ar + 64] = ra1.y; As[akq * 4 + 2][ar + 64] = ra1.z; As[akq * 4 + 3][ar + 64] = ra1.w;

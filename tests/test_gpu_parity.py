@@ -86,7 +86,8 @@ def test_other_angle_grids_vs_oracle(step, D, S):
 
 @pytest.mark.parametrize("prec", [api.SRP_FP16X3, api.SRP_FP16])
 def test_split_k_contraction_vs_oracle(prec):
-    # >= 1024 rows with 361 angles selects the 256 x 384 split-K MFMA kernel (two partial maps summed by the scan)
+    # 8 x 136 = 1 088 rows with 361 angles run on the 128 x 192 kernel, K cut into 16 segments by plan_gemm (the partial maps folded by
+    # k_sum_planes); the 256 x 384 kernels start at 16 384 rows and are compared with a reference in tests/test_gpu_gemm_kernels.py
     fs, N, F, A = 48000, 1024, 136, 8
     xs = synth.ULA8
     pcm = np.stack([synth.noise_source_stream(xs, np.deg2rad(-75.0 + 20.0 * a), fs, (F + 1) * N // 2, 500 + a) for a in range(A)])
