@@ -60,15 +60,12 @@ constexpr int REPICK_GRID = 256;      // workgroups of k_scan_repick
 
 // Per-call workspace (everything a stream call allocates besides the per-array state, which lives in the context).  A call
 // can be worked off in pieces over a sub-range of its arrays -- the chunks of the host-pointer path -- with the per-array
-// state addressed at c->a0.  Every buffer grows on its own need (grow_ws, the one place that reallocates) and its n is its capacity.
+// state addressed at the call record's a0 (StreamCall).  Every buffer grows on its own need (grow_ws, the one place that reallocates)
+// and its n is its capacity.  Buffers only: what a contraction left in d_C travels in the call record (MapResult).
 struct Workspace {
     DevBuf<unsigned char> d_A;                        // A operand: [rows][a_row_elems], in bytes (the element is the precision's)
     DevBuf<unsigned char> d_Ax;                       // ADAPTIVE: the two-plane A rows (repair pass, FP16X3 calls)
     DevBuf<float> d_C;                                // correlation map
-    int c_planes = 1;                                 // partial maps (split-K) the last contraction left in d_C
-    bool partial_done = false;                        // the last contraction also left the scan's chunk-local results (d_part, d_nv)
-    int part_planes = 1;                              // ... one set per K half of a split-K launch
-    long long c_plane = 0;
     DevBuf<float> d_Cx;                               // ADAPTIVE: partial maps of the repair contraction
     // exact chunked scan + power gate
     DevBuf<float> d_part, d_estart; DevBuf<int> d_nv;
@@ -122,9 +119,7 @@ struct mca_hip_ctx {
     DevBuf<float4> d_steer_rows; DevBuf<float2> d_steer_q; DevBuf<float> d_steer_nyq; DevBuf<int> d_steer_pred; DevBuf<unsigned long long> d_steer_miss;
     DevBuf<float2> d_steer_Y; DevBuf<float> d_steer_tail;
     DevBuf<int> d_steer_mlist;                              // the miss list of the patching second pick (ScanPickArgs::n_miss): [0] its length, then an entry per row of Y
-    bool steer_now = false, steer_fused_now = false;        // this call: the analysis may steer ahead (Y holds the whole call) / did
     bool steer_mlist_dirty = false;                         // misses were listed by a call whose synthesis (which empties the list) has not been enqueued
-    bool steer_patched_now = false;                         // this call: the second pick patches the missed frames (no k_steer_patch launch)
     unsigned long long steer_frames_total = 0, steer_fused_calls = 0;
     // the guard of that path (steer_policy_begin): a call steers ahead of its picks unless the report of the call FB_LAG calls before it -- its
     // frames whose pick was not the predicted bin, through page-locked memory, consumed at that fixed lag like the AUTO policy's -- had more
@@ -137,9 +132,6 @@ struct mca_hip_ctx {
     DevBuf<float> d_tail[2];
     int e_cur = 0, tail_cur = 0;
     Workspace ws;
-    int a0 = 0;                            // the first array of the piece being enqueued (host side, sequential)
-    long long plan_rows = 0;               // > 0: rows of the whole call while it is worked off in pieces (plan_gemm)
-    int plan_arrays = 0;                   // ... and its arrays (repair_ksplit_for)
     hipStream_t io_stream[3] = {}; hipEvent_t io_ev[8] = {};   // host-pointer entry points with page-locked buffers: copy in / run / copy out
     DevBuf<double> d_gate_state;
     DevBuf<int> d_last_bin; DevBuf<float> d_last_rad, d_last_prob;
@@ -172,9 +164,6 @@ struct mca_hip_ctx {
     DevBuf<float> d_ehist[2];                      // [max_arrays][D] the energies in front of them
     int hist_cur = 0, hist_n = 0;                  // the buffers that hold the pending history, the arrays it covers
     bool hist_pending = false;                     // the state in d_E is coarse: exact = settle_history, or the next lazy call's own repair pass
-    bool lazy_now = false;                         // (localise_impl) this call leaves its tails to the next: the coarse analysis keeps the PCM
-    bool host_call = false;                        // inside a host-pointer entry point: its calls keep the eager form (the pageable and the page-locked path return the same bits)
-    bool lazy_entry = false;                       // this API call may leave its tails to the next (device-pointer stream calls outside captures)
     int n_cu = 256;
     unsigned long long adapt_frames_total = 0;
     float tau_en = 0.f;            // normalised energies closer than this cannot be ordered from the coarse map
@@ -183,7 +172,7 @@ struct mca_hip_ctx {
     // kernel of an adaptive call leaves its running totals in page-locked memory; the next calls read them when they have arrived
     // (no synchronisation) and suspend the mode for fb_backoff eligible calls, then probe again with one adaptive call.
     Knobs kn;
-    bool adapt_suspended = false, capturing = false;
+    bool adapt_suspended = false;                       // policy state between calls (a recording looks past it: StreamCall::recording)
     int fb_left = 0, fb_backoff = 8, fb_state = 0;      // (adapt_policy_begin)
     bool cand_heavy = false;                            // the last report had more than a fifth of the rows recomputed: whole-row repair kernels (adapt_policy_begin)
     unsigned long long fb_probe_seq = 0;
@@ -193,7 +182,7 @@ struct mca_hip_ctx {
     unsigned long long fb_m = 0;                        // eligible stream calls seen by adapt_policy_begin
     unsigned long long fb_launch_m[FB_RING] = {};       // ... and the one during which adaptive call number i + 1 was enqueued
     bool fb_lost = false;                               // a report did not arrive within FB_WAIT_MS: the policy stops consuming reports (until mca_hip_reset)
-    int a_row_elems = 0, a_planes = 1, a_elem = 4;
+    int a_elem = 4;                // bytes per element of the A operand (its row layout is the call's: RowLayout)
     // frame API (double)
     DevBuf<double> d_fr;          // workspace: the frame's spectra [M][ccs_len]
     DevBuf<double> d_E64[2]; int e64_cur = 0;
@@ -217,6 +206,32 @@ struct mca_hip_ctx {
 };
 
 namespace {
+
+// ---- the call record ------------------------------------------------------------------------------
+// What holds for ONE stream call, or one piece of it, and for nothing after it: built on the entry point's stack and handed down by
+// reference.  The context keeps what outlives a call (state, policy, counters, buffers).
+struct MapResult {                 // what run_correlation_map left in Workspace::d_C: partial maps of a split-K contraction, the elements
+    int c_planes = 1; long long c_plane = 0;       // between them,
+    bool partial_done = false; int part_planes = 1;   // whether it also left the scan's chunk-local results (d_part, d_nv), one set per K half
+};
+enum class Caller { DEVICE, HOST, RECORDING };   // a device-pointer entry point / a host-pointer one (the eager form on its pageable and its page-locked path: the same bits) / graph_record
+struct StreamCall {
+    Caller caller = Caller::DEVICE;
+    int a0 = 0;                    // the first array of the piece being enqueued: per-array state is addressed from it
+    long long rows_planned = 0;       // > 0: the rows the contraction is planned for -- the whole call's while it is worked off in pieces (plan_gemm)
+    int arrays_planned = 0;           // ... and its arrays (repair_ksplit_for)
+    // what the call decided on its way down: it leaves the repair of its last rows to the next call (the coarse analysis keeps the PCM);
+    // its analysis may steer ahead of the picks (Y holds the whole call) / did (launch_stft); the second pick patches the missed frames
+    bool lazy = false, steer = false, steer_fused = false, steer_patched = false;
+    MapResult map;
+    bool recording() const { return caller == Caller::RECORDING; }   // the mode's own kernels whatever the back-off does; no policy, no counters, no event pairs
+    bool may_lazy() const { return caller == Caller::DEVICE; }       // device-pointer calls outside recordings may leave their tails to the next call
+    long long planned(long long rows) const { return rows_planned > 0 ? rows_planned : rows; }
+    int planned_arrays(int n_arrays) const { return arrays_planned > 0 ? arrays_planned : n_arrays; }
+};
+// The row layout of the A operand in one phase of a call: 1 plane (fp32, fp16, the ADAPTIVE coarse pass) or 2 (fp16 hi + lo: FP16X3, the
+// repair pass, ADAPTIVE calls that run as FP16X3 -- mca_hip_ctx::tab_planes), the contraction depth per plane and the elements per row
+struct RowLayout { int planes, kp, row_elems; };
 
 int fail(mca_hip_ctx *c, int code, const std::string &msg)
 {
@@ -390,8 +405,12 @@ int build_steering_table(mca_hip_ctx *c)
     return MCA_HIP_OK;
 }
 
-// the contraction depth (elements per operand plane) of the current call: the merged index with one plane on a merged context
-int cur_kp(const mca_hip_ctx *c) { return (c->merged && c->a_planes == 1) ? c->Kp_m : c->Kp; }
+// the layout of rows of `planes` planes: the merged index with one plane on a merged context
+RowLayout row_layout(const mca_hip_ctx *c, int planes)
+{
+    const int kp = (c->merged && planes == 1) ? c->Kp_m : c->Kp;
+    return {planes, kp, kp * planes};
+}
 
 // Merged contraction index of the one-plane fp16 path on a uniform linear array (see mca_hip_ctx::merged).  The pairs of
 // spacing g have the delay table tau_g(d); on a ULA tau_g = g tau_1 up to the rounding of the reference's float chain
@@ -449,13 +468,12 @@ int build_merged_tables(mca_hip_ctx *c)
     c->d_Bm.swap(dBm); c->d_Btm.swap(dBtm); c->d_Bfold.swap(dBfold); c->d_mrank.swap(dmrank);
     c->n_merged = n_merged; c->Kp_m = Kp; c->fold = fold;
     c->merged = true;
-    c->a_row_elems = cur_kp(c) * c->a_planes;
     return MCA_HIP_OK;
 }
 
-void time_begin(mca_hip_ctx *c, int id, hipStream_t st)
+void time_begin(mca_hip_ctx *c, const StreamCall &call, int id, hipStream_t st)
 {
-    c->timing_open = (c->timing >> id) & 1u;
+    c->timing_open = !call.recording() && ((c->timing >> id) & 1u);      // (event pairs belong to eager calls)
     if (!c->timing_open) return;
     TimedEvent ev; ev.id = id;
     auto get = [&]() { hipEvent_t e; if (!c->pool.empty()) { e = c->pool.back(); c->pool.pop_back(); } else (void)hipEventCreate(&e); return e; };
@@ -482,56 +500,55 @@ int gen_threads(const mca_hip_ctx *c, bool synthesis)
 
 // which contraction kernel a chunk of `rows` frames runs on, and over how many workgroups its K range is split
 struct GemmPlan { bool v2; int ksplit; bool fold; };      // fold: k_srp_gemm_f16_fold (256-row tiles, two K segments, one plane, a folding context)
-GemmPlan plan_gemm(const mca_hip_ctx *c, long long rows)
+GemmPlan plan_gemm(const mca_hip_ctx *c, const RowLayout &lay, long long rows)
 {
     GemmPlan g;
-    // a call that is worked off in pieces (the chunks of the host-pointer path) plans every piece as the whole call would
-    // be planned: a row's result then does not depend on how the call was cut (same kernel, same K segments, same order)
-    if (c->plan_rows > 0) rows = c->plan_rows;
+    // (rows: StreamCall::planned -- a call that is worked off in pieces, the chunks of the host-pointer path, plans every piece as the
+    // whole call would be planned: a row's result then does not depend on how the call was cut, same kernel, same K segments, same order)
     // 256 x 384 tiles from 16 384 rows with one operand plane (128 workgroups of k_srp_gemm_f16_v3 beat the 128 x 192 kernel
     // there: 134 vs 156 us, and leave the scan's chunk results), from 32 768 rows with the hi + lo planes (343 vs 299 us at 16 384)
     // (round 6: a contraction twice as deep -- 2048-sample frames, 16 microphones: 14 350 / 15 390 elements per plane -- gives a 256 x 384
     // workgroup of a K QUARTER the work a K half has at 7 182: two planes take the big tiles from 16 384 rows there, profiles/r06_n2048.log)
-    const long long deep = cur_kp(c) >= 12288 ? 2 : 1;
-    g.v2 = c->prec != MCA_HIP_SRP_FP32 && c->Dp == 384 && rows * (c->a_planes == 2 ? deep : 1) >= 16384LL * (c->a_planes == 2 ? 2 : 1);
+    const long long deep = lay.kp >= 12288 ? 2 : 1;
+    g.v2 = c->prec != MCA_HIP_SRP_FP32 && c->Dp == 384 && rows * (lay.planes == 2 ? deep : 1) >= 16384LL * (lay.planes == 2 ? 2 : 1);
     if (g.v2) {
         // 256 x 384 tiles need >= ~256 workgroups to fill the chip: one K range from 65 536 rows, two halves from 32 768, and below that four
         // quarters where the contraction is deep (round 5: 16 microphones, 15 392 terms per row -- 16 384 rows were 128 workgroups on half
         // the CUs: 0.280 -> 0.183 ms + 0.021 for k_sum_planes, which folds the four partial maps before the scan; with the 3 968 merged terms
         // of 8 microphones the fold costs what the quarters save: 75 -> 54 + 22 us, profiles/r05_gemm_ksplit4.log)
-        g.ksplit = rows >= 65536 ? 1 : (rows >= 32768 || cur_kp(c) < 6144 ? 2 : 4);      // (6144: the merged rows of 2048-sample frames, 7 936 deep, take quarters)
+        g.ksplit = rows >= 65536 ? 1 : (rows >= 32768 || lay.kp < 6144 ? 2 : 4);      // (6144: the merged rows of 2048-sample frames, 7 936 deep, take quarters)
     } else {
         // 128 x 192 tiles: small batches (a single stream) would leave most CUs idle and walk the whole K range
         // in a handful of workgroups (0.29 ms however few frames); split K until ~512 workgroups exist, keeping
         // at least 8 K steps per workgroup
         const long long wgs = (rows + 127) / 128 * (c->Dp == 64 ? 1 : c->Dp / 192);
-        const int nk = cur_kp(c) / (c->prec == MCA_HIP_SRP_FP32 ? 16 : 32);
+        const int nk = lay.kp / (c->prec == MCA_HIP_SRP_FP32 ? 16 : 32);
         long long ks = 512 / (wgs > 0 ? wgs : 1);
         if (ks > nk / 8) ks = nk / 8;
         if (ks > 16) ks = 16;
         if (ks < 1) ks = 1;
         g.ksplit = (int)ks;
     }
-    g.fold = g.v2 && g.ksplit == 2 && c->a_planes == 1 && c->merged && c->fold;
+    g.fold = g.v2 && g.ksplit == 2 && lay.planes == 1 && c->merged && c->fold;
     return g;
 }
 
-// the A buffer of the current call: an ADAPTIVE context keeps its two-plane rows (repair pass, FP16X3 calls) apart from the
+// the A buffer of rows of this layout: an ADAPTIVE context keeps its two-plane rows (repair pass, FP16X3 calls) apart from the
 // one-plane rows of the coarse pass, so that a buffer only ever sees one row layout (its Kp padding columns stay zero)
-DevBuf<unsigned char> &a_buf(mca_hip_ctx *c) { return (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 2) ? c->ws.d_Ax : c->ws.d_A; }
+DevBuf<unsigned char> &a_buf(mca_hip_ctx *c, const RowLayout &lay) { return (c->prec == MCA_HIP_SRP_ADAPTIVE && lay.planes == 2) ? c->ws.d_Ax : c->ws.d_A; }
 
-int ensure_a(mca_hip_ctx *c, long long rows)
+int ensure_a(mca_hip_ctx *c, const RowLayout &lay, long long rows)
 {
     // rows rounded up to the 256-row tile of the split-K MFMA kernel, which loads whole tiles unclamped
-    const size_t need_a = (size_t)((rows + 255) / 256 * 256) * c->a_row_elems * c->a_elem;
-    return grow_ws_filled(c, a_buf(c), need_a, need_a, 0, "the A operand");          // the Kp padding columns stay zero forever
+    const size_t need_a = (size_t)((rows + 255) / 256 * 256) * lay.row_elems * c->a_elem;
+    return grow_ws_filled(c, a_buf(c, lay), need_a, need_a, 0, "the A operand");          // the Kp padding columns stay zero forever
 }
 
-int ensure_workspace(mca_hip_ctx *c, long long rows_chunk, long long rows_total)
+int ensure_workspace(mca_hip_ctx *c, const RowLayout &lay, long long rows_chunk, long long rows_plan, long long rows_total)      // (rows_plan: StreamCall::planned)
 {
-    int rc_a = ensure_a(c, rows_chunk);
+    int rc_a = ensure_a(c, lay, rows_chunk);
     if (rc_a) return rc_a;
-    const int planes = std::max(2, plan_gemm(c, rows_chunk).ksplit);
+    const int planes = std::max(2, plan_gemm(c, lay, rows_plan).ksplit);
     return grow_ws(c, c->ws.d_C, (size_t)rows_total * c->Dp * planes, "the correlation map");   // room for the partial maps of a split-K contraction
 }
 
@@ -551,9 +568,9 @@ int ensure_scan_workspace(mca_hip_ctx *c, int n_arrays, int n_frames, int n_chun
 // A-operand workspace budget per slice of frames (MCA_HIP_WS_MAX_MB lets the tests force the sliced path)
 long long ws_max_bytes(const mca_hip_ctx *c) { return c->kn.ws_max_bytes; }
 
-long long chunk_frames_for(const mca_hip_ctx *c, int n_arrays, int n_frames)
+long long chunk_frames_for(const mca_hip_ctx *c, const RowLayout &lay, int n_arrays, int n_frames)
 {
-    long long row_bytes = (long long)c->a_row_elems * c->a_elem;
+    long long row_bytes = (long long)lay.row_elems * c->a_elem;
     long long rows_cap = ws_max_bytes(c) / row_bytes;
     long long fc = rows_cap / n_arrays;
     if (fc >= n_frames) return n_frames;
@@ -563,22 +580,21 @@ long long chunk_frames_for(const mca_hip_ctx *c, int n_arrays, int n_frames)
 }
 
 // ---- adaptive SRP precision (MCA_HIP_SRP_ADAPTIVE) ------------------------------------------------------------
-void set_call_planes(mca_hip_ctx *c, int planes) { c->a_planes = planes; c->a_row_elems = cur_kp(c) * planes; }
-
 // Does a call of this shape run coarse + repair?  The repair pass needs the list mode of k_stft_phat (1024-sample frames,
 // more than two microphones) and has a fixed cost of a few small launches, so small batches -- which are latency bound
 // whatever the precision -- run as plain FP16X3, which is what the repair pass reproduces.  (Gated streams do take the
 // adaptive path: the planning wave lists the last 25 VOICED rows behind a flagged frame)
-bool adaptive_shape(const mca_hip_ctx *c, int n_arrays, int n_frames)
+bool adaptive_shape(const mca_hip_ctx *c, int n_arrays, int n_frames, long long rows_planned = 0)
 {
-    const long long rows = c->plan_rows > 0 ? c->plan_rows : (long long)n_arrays * n_frames;     // (see plan_gemm)
+    const long long rows = rows_planned > 0 ? rows_planned : (long long)n_arrays * n_frames;     // (see plan_gemm)
     // (more than one source: the S-th pick is a weak peak more often than not -- a second source, or noise when fewer than S
     // are active -- and a third to all of the frames are flagged: 8 x 4096 frames with S = 2 / 3 / 4 real sources spend 0.89 / 1.60 /
     // 1.76 ms in the repair pass, more than the 0.3 ms the coarse contraction saves; MCA_HIP_ADAPT_MAX_SOURCES lifts the limit)
     return c->prec == MCA_HIP_SRP_ADAPTIVE && ((!c->generic && !c->n512 && c->N == FFT_N) || ((c->n2048 || c->n512) && c->M <= 8)) && c->M > 2 && c->S <= c->kn.adapt_max_sources &&
            rows >= c->kn.adapt_min_rows && n_frames >= 2 * SCAN_CHUNK;
 }
-bool adaptive_applies(const mca_hip_ctx *c, int n_arrays, int n_frames) { return adaptive_shape(c, n_arrays, n_frames) && !c->adapt_suspended; }
+bool adaptive_applies(const mca_hip_ctx *c, const StreamCall &call, int n_arrays, int n_frames)      // (a recording looks past the suspension)
+{ return adaptive_shape(c, n_arrays, n_frames, call.rows_planned) && (call.recording() || !c->adapt_suspended); }
 // lazy tails: contexts whose adaptive calls may leave the repair of their last rows to the next call -- no power gate (the rows a frame
 // depends on are then simply the 16 before it), the wave-per-run analysis (4 / 8 microphones at 1024 samples: it keeps the PCM and reads it back)
 bool lazy_context(const mca_hip_ctx *c)
@@ -614,9 +630,9 @@ static bool cand_call(const mca_hip_ctx *c, bool lazy)
 // own, which WAITS for it if need be -- before, a call took "whatever has arrived by now" and the switch (and with it the choice between
 // candidate columns and whole rows, cand_call) could move by a call from run to run.  A report that does not arrive within FB_WAIT_MS (a
 // stream held up by something only this thread would release) ends the policy for the stream: the mode stays what it is.
-void adapt_policy_begin(mca_hip_ctx *c, int n_arrays, int n_frames)
+void adapt_policy_begin(mca_hip_ctx *c, const StreamCall &call, int n_arrays, int n_frames)
 {
-    if (!c->kn.fb_enabled || c->capturing || !c->h_probe || !adaptive_shape(c, n_arrays, n_frames)) return;
+    if (!c->kn.fb_enabled || call.recording() || !c->h_probe || !adaptive_shape(c, n_arrays, n_frames)) return;
     bool fresh = false, heavy = false;
     const unsigned long long m = c->fb_m++;
     unsigned long long seq = c->fb_seq_seen;                                   // the last report due at this call
@@ -668,13 +684,12 @@ void adapt_policy_begin(mca_hip_ctx *c, int n_arrays, int n_frames)
 // repair_ksplit_eff).  The tails of every array -- REPAIR_WARM + 1 rows
 // rounded up to repair units -- are always recomputed: a few arrays leave a few hundred rows, where 32 segments fill the chip;
 // 128 arrays leave thousands, where 32 partial maps per row cost more (k_repair_patch reads them all) than they buy.
-int repair_ksplit_for(const mca_hip_ctx *c, int n_arrays)
+int repair_ksplit_for(const mca_hip_ctx *c, int n_arrays)      // (n_arrays: StreamCall::planned_arrays)
 {
     // lazy tails: no array lists its last rows as a matter of course -- the list is as long as the content makes it, and the device-side
     // rule (repair_ksplit_eff) halves the segments when it is long
     if (lazy_context(c)) return REPAIR_KSPLIT_MAX;
-    const long long arrays = c->plan_arrays > 0 ? c->plan_arrays : n_arrays;
-    const long long tail_rows = arrays * (REPAIR_WARM + 1 + REPAIR_GROUP);
+    const long long tail_rows = (long long)n_arrays * (REPAIR_WARM + 1 + REPAIR_GROUP);
     return tail_rows <= 1024 ? 32 : (tail_rows <= 2560 ? 16 : 8);
 }
 
@@ -705,11 +720,7 @@ int ensure_adapt_workspace(mca_hip_ctx *c, int n_arrays, int n_frames, int n_chu
         (rc = grow_ws(c, w.d_last_vchunk, (size_t)n_arrays, "the last voiced chunks")) ||
         (rc = grow_ws_filled(c, w.d_nlist, 4, 4, 0, "the list counters"))) return rc;                      // listed repair units | listed chunks, workgroups of k_scan_repick done | unused
     const long long rows = repair_pass_rows(c, n_arrays, n_frames);
-    const int planes = c->a_planes;
-    set_call_planes(c, 2);
-    rc = ensure_a(c, rows);
-    set_call_planes(c, planes);
-    if (rc) return rc;
+    if ((rc = ensure_a(c, row_layout(c, 2), rows))) return rc;
     return grow_ws(c, w.d_Cx, (size_t)repair_cx_rows(rows, REPAIR_KSPLIT_MAX) * c->Dp, "the repair contraction's partial maps");
 }
 
@@ -800,8 +811,17 @@ int launch_stft_2048(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, hipStream
     return MCA_HIP_OK;
 }
 
+// the fields of StftPhatArgs that are the context's, the same for every launch
+void stft_common(const mca_hip_ctx *c, StftPhatArgs &sa)
+{
+    sa.M = c->M; sa.window = c->d_window; sa.Kp = c->Kp;
+    sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
+}
+// dynamic LDS of launch_stft's fallback kernels (k_stft_phat, fpb frames per workgroup)
+size_t stft_fallback_lds(const mca_hip_ctx *c, int fpb) { return ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)fpb * c->M) * sizeof(float2) + (size_t)fpb * 8 * sizeof(float); }
+// *steered (if given) is set when the launch is the one that also steers every frame ahead of the picks (a.bf, steer.h)
 template <typename OutT>
-int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, hipStream_t st)
+int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, hipStream_t st, bool *steered = nullptr)
 {
     const int M = c->M; const bool ula = c->ula;
     if (n2048_analysis(c)) return launch_stft_2048<OutT>(c, a, grid, st);      // (the list-mode launches of the repair pass come through here)
@@ -880,7 +900,7 @@ int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, h
         } while (0)
         if constexpr (sizeof(OutT) == 2) {
             if (mg) {          // merged contraction index: ULA, one plane
-                if (fuse) { LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true, false, true>)); c->steer_fused_now = true; }      // steering ahead of the picks (steer.h)
+                if (fuse) { LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true, false, true>)); if (steered) *steered = true; }      // steering ahead of the picks (steer.h)
                 else if (M == 8) { if (pw) LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true>)); }
                 else { if (pw) LAUNCH_K((k_stft_phat_wave<4, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<4, true, OutT, false, false, false, true>)); }
                 HIP_TRY(c, hipGetLastError());
@@ -1010,9 +1030,7 @@ static int init_ctx(mca_hip_ctx *c, const mca_hip_config *cfg, const hipDevicePr
     c->G = c->ula ? c->M - 1 : c->P;
     c->Kp = round_up(c->G * c->K * 2, 32);     // K == KG == 513 on the tuned path
     c->tab_planes = (c->prec == MCA_HIP_SRP_FP16X3 || c->prec == MCA_HIP_SRP_ADAPTIVE) ? 2 : 1;
-    c->a_planes = c->prec == MCA_HIP_SRP_FP16X3 ? 2 : 1;          // (ADAPTIVE: set per call, 1 for the coarse pass, 2 otherwise)
-    c->a_elem = c->prec == MCA_HIP_SRP_FP32 ? 4 : 2;
-    c->a_row_elems = c->Kp * c->a_planes;
+    c->a_elem = c->prec == MCA_HIP_SRP_FP32 ? 4 : 2;              // (planes of the A rows: tab_planes, but 1 for the ADAPTIVE coarse pass -- row_layout, per call)
     {
         // Error model of the coarse (one fp16 product) map, for the sensitivity test of k_scan_pick: every operand carries
         // a relative rounding error of rms ~2-3e-4 (11-bit significand), so a term a*b of the contraction is off by
@@ -1342,15 +1360,15 @@ static int reserve_impl(mca_hip_ctx *c, int n_arrays, int n_frames)
         // by the SHAPE of the call, whatever the back-off is doing at the moment: a graph recording always runs coarse + repair
         // (graph_record clears adapt_suspended), and reserving for plain FP16X3 only would make it allocate inside the capture
         // (ADVICE r3).  While the mode is suspended the eager calls run as FP16X3: their two-plane rows are reserved as well.
-        set_call_planes(c, 1);
+        const RowLayout coarse = row_layout(c, 1);
         if ((rc = ensure_adapt_workspace(c, n_arrays, n_frames, n_chunks))) return rc;
-        const long long fc1 = chunk_frames_for(c, n_arrays, n_frames);
-        if ((rc = ensure_workspace(c, (long long)n_arrays * fc1, (long long)n_arrays * n_frames))) return rc;
+        const long long fc1 = chunk_frames_for(c, coarse, n_arrays, n_frames);
+        if ((rc = ensure_workspace(c, coarse, (long long)n_arrays * fc1, (long long)n_arrays * fc1, (long long)n_arrays * n_frames))) return rc;
         if (!c->adapt_suspended) return ensure_scan_workspace(c, n_arrays, n_frames, n_chunks);
     }
-    if (c->prec == MCA_HIP_SRP_ADAPTIVE) set_call_planes(c, 2);
-    long long fc = chunk_frames_for(c, n_arrays, n_frames);
-    rc = ensure_workspace(c, (long long)n_arrays * fc, (long long)n_arrays * n_frames);
+    const RowLayout lay = row_layout(c, c->tab_planes);      // the context's own rows: two planes for FP16X3 and for ADAPTIVE calls that run as FP16X3
+    long long fc = chunk_frames_for(c, lay, n_arrays, n_frames);
+    rc = ensure_workspace(c, lay, (long long)n_arrays * fc, (long long)n_arrays * fc, (long long)n_arrays * n_frames);
     if (rc) return rc;
     return ensure_scan_workspace(c, n_arrays, n_frames, n_chunks);
 }
@@ -1362,44 +1380,46 @@ int mca_hip_reserve(mca_hip_ctx *c, int n_arrays, int n_frames)
     return rc ? rc : steer_reserve(c, n_arrays, n_frames);      // (the rows of Y of a context that steers on the half spectrum)
 }
 
-// STFT + PHAT + steering contraction for every frame: fills c->ws.d_C [arrays][n_frames][Dp]
-static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+// STFT + PHAT + steering contraction for every frame, on rows of the layout `lay`: fills c->ws.d_C [arrays][n_frames][Dp], call.map says how
+static int run_correlation_map(mca_hip_ctx *c, StreamCall &call, const RowLayout &lay, const float *pcm, long long array_stride, long long mic_stride,
                                int n_arrays, int n_frames, hipStream_t st)
 {
     int rc;
-    const long long fc = chunk_frames_for(c, n_arrays, n_frames);
-    if ((rc = ensure_workspace(c, (long long)n_arrays * fc, (long long)n_arrays * n_frames))) return rc;
+    const long long fc = chunk_frames_for(c, lay, n_arrays, n_frames);
+    auto plan = [&](long long rows) { return plan_gemm(c, lay, call.planned(rows)); };
+    if ((rc = ensure_workspace(c, lay, (long long)n_arrays * fc, call.planned((long long)n_arrays * fc), (long long)n_arrays * n_frames))) return rc;
     if ((rc = ensure_scan_workspace(c, n_arrays, n_frames, (n_frames + SCAN_CHUNK - 1) / SCAN_CHUNK))) return rc;
     // The 256 x 384 contraction leaves the chunk-local results of the scan over frames (k_scan_partial's job) when every
     // 32-row block of every launch is one scan chunk of one map: no gate, one map, whole chunks, that kernel for every slice.
-    bool fused_partial = SCAN_CHUNK == 32 && c->a_planes == 1 && !c->cfg.use_power_floor && n_frames % SCAN_CHUNK == 0 && fc % SCAN_CHUNK == 0 &&
-                         plan_gemm(c, (long long)n_arrays * fc).ksplit <= 2;
+    bool fused_partial = SCAN_CHUNK == 32 && lay.planes == 1 && !c->cfg.use_power_floor && n_frames % SCAN_CHUNK == 0 && fc % SCAN_CHUNK == 0 &&
+                         plan((long long)n_arrays * fc).ksplit <= 2;
     for (int f0 = 0; fused_partial && f0 < n_frames; f0 += (int)fc)
-        fused_partial = plan_gemm(c, (long long)n_arrays * std::min<long long>(fc, n_frames - f0)).v2;
-    c->ws.partial_done = fused_partial;
-    c->ws.part_planes = fused_partial ? plan_gemm(c, (long long)n_arrays * fc).ksplit : 1;
+        fused_partial = plan((long long)n_arrays * std::min<long long>(fc, n_frames - f0)).v2;
+    MapResult &map = call.map;
+    map.partial_done = fused_partial;
+    map.part_planes = fused_partial ? plan((long long)n_arrays * fc).ksplit : 1;
     for (int f0 = 0; f0 < n_frames; f0 += (int)fc) {
         const int nf = (int)std::min<long long>(fc, n_frames - f0);
         StftPhatArgs sa{};
         sa.pcm = pcm; sa.array_stride = array_stride; sa.mic_stride = mic_stride;
-        sa.M = c->M; sa.n_frames = nf; sa.frame0 = f0;
+        stft_common(c, sa);
+        sa.n_frames = nf; sa.frame0 = f0;
         // frames per workgroup: 16 amortise the table set-up and the half frame two neighbouring workgroups both read (17 half
         // frames of input per 16 frames; measured 4 / 8 / 16 / 32: 0.312 / 0.292 / 0.286 / 0.288 ms); small batches take fewer
         // so that a few hundred workgroups exist
         sa.fpb = 16;
         while (sa.fpb > 1 && (long long)n_arrays * ((nf + sa.fpb - 1) / sa.fpb) < 256) sa.fpb >>= 1;
         sa.power = c->cfg.use_power_floor ? c->ws.d_power : nullptr; sa.total_frames = n_frames;
-        sa.window = c->d_window; sa.A = a_buf(c); sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = c->a_planes;
-        if (c->merged && c->a_planes == 1) { sa.mrank = c->d_mrank; sa.n_merged = c->n_merged; sa.planar = c->fold ? 1 : 0; }
-        sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
+        sa.A = a_buf(c, lay); sa.a_row_elems = lay.row_elems; sa.a_planes = lay.planes;
+        if (c->merged && lay.planes == 1) { sa.mrank = c->d_mrank; sa.n_merged = c->n_merged; sa.planar = c->fold ? 1 : 0; }
         sa.no_phat = c->cfg.gcc_weighting == MCA_HIP_GCC_NONE ? 1 : 0;
-        if (c->prec == MCA_HIP_SRP_ADAPTIVE && c->a_planes == 1 && wave16_applies(c)) sa.unsure = c->ws.d_unsure;   // (adaptive coarse pass)
-        if (c->lazy_now && cand_call(c, true)) sa.dead = c->ws.d_unsure;                                               // (... of a candidate-column call: frames of exact zeros)
-        if (c->lazy_now) sa.hist_out = c->d_hist_pcm[c->hist_cur ^ 1];       // lazy tails: the call's last frames of PCM stay behind
-        if (c->steer_now && sa.mrank && !sa.power) {                          // the merged 8-microphone kernel also steers every frame at the array's predicted bin
-            sa.bf.rows = c->d_steer_rows; sa.bf.q = c->d_steer_q; sa.bf.nyq = c->d_steer_nyq; sa.bf.pred = c->d_steer_pred + c->a0; sa.bf.Y = c->d_steer_Y;
+        if (c->prec == MCA_HIP_SRP_ADAPTIVE && lay.planes == 1 && wave16_applies(c)) sa.unsure = c->ws.d_unsure;   // (adaptive coarse pass)
+        if (call.lazy && cand_call(c, true)) sa.dead = c->ws.d_unsure;                                                 // (... of a candidate-column call: frames of exact zeros)
+        if (call.lazy) sa.hist_out = c->d_hist_pcm[c->hist_cur ^ 1];         // lazy tails: the call's last frames of PCM stay behind
+        if (call.steer && sa.mrank && !sa.power) {                            // the merged 8-microphone kernel also steers every frame at the array's predicted bin
+            sa.bf.rows = c->d_steer_rows; sa.bf.q = c->d_steer_q; sa.bf.nyq = c->d_steer_nyq; sa.bf.pred = c->d_steer_pred + call.a0; sa.bf.Y = c->d_steer_Y;
         }
-        time_begin(c, MCA_HIP_K_STFT_PHAT, st);
+        time_begin(c, call, MCA_HIP_K_STFT_PHAT, st);
         if (c->n512) {
             rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft_512<float>(c, sa, dim3(0, n_arrays), st) : launch_stft_512<_Float16>(c, sa, dim3(0, n_arrays), st);
         } else if ((c->N == 4096 || c->N == 2048) && c->M == 2 && c->stream_ok) {
@@ -1433,17 +1453,17 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
             rc = MCA_HIP_OK;
         } else {
             dim3 g1((nf + sa.fpb - 1) / sa.fpb, n_arrays);
-            const size_t smem1 = ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
-            rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft<float>(c, sa, g1, smem1, st) : launch_stft<_Float16>(c, sa, g1, smem1, st);
+            const size_t smem1 = stft_fallback_lds(c, sa.fpb);
+            rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft<float>(c, sa, g1, smem1, st) : launch_stft<_Float16>(c, sa, g1, smem1, st, &call.steer_fused);
         }
         time_end(c, st);
         if (rc) return rc;
 
         GemmArgs ga{};
-        const bool mg = c->merged && c->a_planes == 1;
-        ga.A = a_buf(c); ga.B = mg ? c->d_Bm : c->d_B; ga.C = c->ws.d_C; ga.Bt = mg ? c->d_Btm : c->d_Bt;
+        const bool mg = c->merged && lay.planes == 1;
+        ga.A = a_buf(c, lay); ga.B = mg ? c->d_Bm : c->d_B; ga.C = c->ws.d_C; ga.Bt = mg ? c->d_Btm : c->d_Bt;
         ga.rows = n_arrays * nf; ga.chunk_frames = nf; ga.total_frames = n_frames; ga.frame0 = f0;
-        ga.Kp = cur_kp(c); ga.Dp = c->Dp; ga.a_row_elems = c->a_row_elems;
+        ga.Kp = lay.kp; ga.Dp = c->Dp; ga.a_row_elems = lay.row_elems;
         ga.c_plane_elems = (long long)n_arrays * n_frames * c->Dp;
         ga.Bf = mg ? c->d_Bfold : nullptr; ga.D = c->D;
         if (fused_partial) {
@@ -1454,12 +1474,12 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         }
         // one split factor per call (the scan sums the same number of partial maps for every frame): the one that
         // suits the full-size chunks; a shorter last chunk may still fall back to the 128 x 192 kernel
-        const bool v2 = plan_gemm(c, ga.rows).v2;
-        const int ksplit = plan_gemm(c, (long long)n_arrays * fc).ksplit;
-        c->ws.c_planes = ksplit; c->ws.c_plane = ga.c_plane_elems;
-        time_begin(c, MCA_HIP_K_SRP_GEMM, st);
+        const bool v2 = plan(ga.rows).v2;
+        const int ksplit = plan((long long)n_arrays * fc).ksplit;
+        map.c_planes = ksplit; map.c_plane = ga.c_plane_elems;
+        time_begin(c, call, MCA_HIP_K_SRP_GEMM, st);
         if (v2) {
-            const int np = c->a_planes;
+            const int np = lay.planes;
             const size_t smem = (size_t)(np == 2 ? 2 : 4) * np * (256 + 384) * 64;   // 32-deep stages: two with hi + lo planes, four with one plane (all 160 KiB)
             dim3 gv((ga.rows + 255) / 256, ksplit);
 #define V2_LAUNCH(K)                                                                                                      \
@@ -1468,7 +1488,7 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
                 hipLaunchKernelGGL(K, gv, dim3(512), smem, st, ga);                                                       \
             } while (0)
             // (the slices of a call all have the call's split factor, so a 256-row slice of a folding two-segment call folds like the others)
-            if (c->a_planes == 2) V2_LAUNCH(k_srp_gemm_f16_v2);
+            if (lay.planes == 2) V2_LAUNCH(k_srp_gemm_f16_v2);
             else if (ksplit == 2 && mg && c->fold) {
                 const size_t smem_f = (size_t)FOLD_NS * (256 + 192) * 64;
                 HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_srp_gemm_f16_fold), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_f));
@@ -1479,21 +1499,21 @@ static int run_correlation_map(mca_hip_ctx *c, const float *pcm, long long array
         } else {
             dim3 g2((ga.rows + 127) / 128, c->Dp == 64 ? 1 : c->Dp / 192, ksplit);
             if (c->prec == MCA_HIP_SRP_FP32) hipLaunchKernelGGL(k_srp_gemm_f32, g2, dim3(256), 0, st, ga);
-            else if (c->Dp == 64 && c->a_planes == 2) hipLaunchKernelGGL((k_srp_gemm_f16<true, 64>), g2, dim3(256), 0, st, ga);
+            else if (c->Dp == 64 && lay.planes == 2) hipLaunchKernelGGL((k_srp_gemm_f16<true, 64>), g2, dim3(256), 0, st, ga);
             else if (c->Dp == 64) hipLaunchKernelGGL((k_srp_gemm_f16<false, 64>), g2, dim3(256), 0, st, ga);
-            else if (c->a_planes == 2) hipLaunchKernelGGL((k_srp_gemm_f16<true, 192>), g2, dim3(256), 0, st, ga);
+            else if (lay.planes == 2) hipLaunchKernelGGL((k_srp_gemm_f16<true, 192>), g2, dim3(256), 0, st, ga);
             else hipLaunchKernelGGL((k_srp_gemm_f16<false, 192>), g2, dim3(256), 0, st, ga);
         }
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
     }
-    if (c->ws.c_planes > 2) {      // deep split-K of a small batch: fold the partial maps once, the scans read one map
-        const long long n4 = c->ws.c_plane / 4;       // Dp is a multiple of 64
-        time_begin(c, MCA_HIP_K_FOLD, st);
-        hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c->ws.d_C, n4, c->ws.c_planes, c->ws.c_plane);
+    if (map.c_planes > 2) {      // deep split-K of a small batch: fold the partial maps once, the scans read one map
+        const long long n4 = map.c_plane / 4;       // Dp is a multiple of 64
+        time_begin(c, call, MCA_HIP_K_FOLD, st);
+        hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c->ws.d_C, n4, map.c_planes, map.c_plane);
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
-        c->ws.c_planes = 1;
+        map.c_planes = 1;
     }
 
     return MCA_HIP_OK;
@@ -1505,12 +1525,13 @@ constexpr float ENERGY_MU = 0.8f, ENERGY_ONE_MINUS_MU = 1 - 0.8f;
 // One pass of the whole-row repair behind the list-mode analysis: the exact rows of the listed units [list0, list0 + pass_rows /
 // REPAIR_GROUP) in w.d_Ax -> three-product contraction in K segments (w.d_Cx) -> summed into the map by k_repair_patch (pp: where the
 // rows go; list0, pass_rows, col_tiles, ksplit and items are filled in here).  Shared by localise_impl and settle_history.
-static void launch_repair_contraction(mca_hip_ctx *c, Workspace &w, long long list0, long long pass_rows, int ksplit_arrays, RepairPatchArgs pp, hipStream_t st)
+// x2: the two-plane layout of the exact rows; ksplit_arrays: the arrays the K split is planned for (repair_ksplit_for)
+static void launch_repair_contraction(mca_hip_ctx *c, Workspace &w, const RowLayout &x2, long long list0, long long pass_rows, int ksplit_arrays, RepairPatchArgs pp, hipStream_t st)
 {
     GemmArgs ga{};
     ga.A = w.d_Ax; ga.B = c->d_B; ga.C = w.d_Cx; ga.Bt = c->d_Bt;
     ga.rows = (int)pass_rows; ga.chunk_frames = (int)pass_rows; ga.total_frames = (int)pass_rows; ga.frame0 = 0;
-    ga.Kp = c->Kp; ga.Dp = c->Dp; ga.a_row_elems = c->a_row_elems; ga.c_plane_elems = pass_rows * c->Dp;
+    ga.Kp = c->Kp; ga.Dp = c->Dp; ga.a_row_elems = x2.row_elems; ga.c_plane_elems = pass_rows * c->Dp;
     ga.n_list = w.d_nlist; ga.list0 = (int)list0;
     ga.repair_ksplit = repair_ksplit_for(c, ksplit_arrays); ga.repair_items = REPAIR_ITEMS;
     const int col_tiles = c->Dp == 64 ? 1 : c->Dp / 192;
@@ -1542,62 +1563,59 @@ static int settle_history(mca_hip_ctx *c, hipStream_t st)
     pass_rows = std::min(pass_rows, std::min(fit_a, fit_c));
     if (pass_rows < 128) return fail(c, MCA_HIP_ERR_HIP, "lazy tails: the adaptive workspace is smaller than one repair pass");
     const int pass_groups = (int)(pass_rows / REPAIR_GROUP);
-    const int planes_before = c->a_planes;
-    set_call_planes(c, 2);
+    const RowLayout x2 = row_layout(c, 2);
     hipLaunchKernelGGL(k_hist_list, dim3((units + 255) / 256), dim3(256), 0, st, w.d_list, w.d_nlist, w.d_need, units);
     int rc = MCA_HIP_OK;
     for (long long g0 = 0; g0 < units && !rc; g0 += pass_groups) {
         StftPhatArgs sa{};
         sa.pcm = c->d_hist_pcm[cur]; sa.array_stride = (long long)c->M * HIST_SAMPLES; sa.mic_stride = HIST_SAMPLES;
-        sa.M = c->M; sa.n_frames = HIST_FRAMES; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = HIST_FRAMES;
-        sa.window = c->d_window; sa.A = w.d_Ax; sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = 2;
-        sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
+        stft_common(c, sa);
+        sa.n_frames = HIST_FRAMES; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = HIST_FRAMES;
+        sa.A = w.d_Ax; sa.a_row_elems = x2.row_elems; sa.a_planes = 2;
         sa.list = w.d_list; sa.n_list = w.d_nlist; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = HIST_UNITS;
         sa.hist_in = c->d_hist_pcm[cur]; sa.hist_base = 0;
-        const size_t smem1 = ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
-        rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, 512), 1), smem1, st);
+        rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, 512), 1), stft_fallback_lds(c, sa.fpb), st);
         if (rc) break;
         RepairPatchArgs pp{};
         pp.groups_per_array = HIST_UNITS;
         pp.C = w.d_C; pp.c_planes = 1; pp.c_plane_stride = 0; pp.n_frames = HIST_FRAMES;
         pp.hist_C = c->d_hist_C[cur]; pp.hist_base = 0;
-        launch_repair_contraction(c, w, g0, pass_rows, n, pp, st);
+        launch_repair_contraction(c, w, x2, g0, pass_rows, n, pp, st);
     }
     if (!rc) {
         hipLaunchKernelGGL(k_hist_settle, dim3(n), dim3(std::max(round_up(c->D, 64), 64)), 0, st, c->d_ehist[cur], c->d_hist_C[cur], c->d_E[c->e_cur], w.d_nlist, c->D, c->Dp,
                            ENERGY_MU, ENERGY_ONE_MINUS_MU);
         if (hipGetLastError() != hipSuccess) rc = fail(c, MCA_HIP_ERR_HIP, "lazy tails: a launch of the settling pass failed");
     }
-    set_call_planes(c, planes_before);
-    if (!rc) c->hist_pending = false;           // (only now: a settling pass that failed leaves the debt standing and is tried again by the next consumer -- ADVICE r5)
+    if (!rc) c->hist_pending = false;          // (only now: a settling pass that failed leaves the debt standing and is tried again by the next consumer -- ADVICE r5)
     return rc;
 }
 
-// the localisation stage of the arrays [c->a0, c->a0 + n_arrays) of a call; all pointers already point at the piece's first array
-static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+// the localisation stage of the arrays [call.a0, call.a0 + n_arrays) of a call; all pointers already point at the piece's first array
+static int localise_impl(mca_hip_ctx *c, StreamCall &call, const float *pcm, long long array_stride, long long mic_stride,
                          int n_arrays, int n_frames, int *doa_bin, float *doa_rad, float *prob, float *energy, hipStream_t st)
 {
     int rc;
-    const size_t a0 = (size_t)c->a0;
-    const bool adaptive = adaptive_applies(c, n_arrays, n_frames);
+    const size_t a0 = (size_t)call.a0;
+    const bool adaptive = adaptive_applies(c, call, n_arrays, n_frames);
     // Lazy tails: this call leaves the exact repair of its last rows to the next one (lazy), and repairs the previous call's last rows
     // itself where one of its own first frames needs them (hist_valid).  Any other consumer of the state settles the debt first.
-    const bool lazy = adaptive && c->lazy_entry && !c->capturing && lazy_context(c) && c->a0 == 0 && n_frames >= 2 * SCAN_CHUNK && SCAN_CHUNK == 32;
+    const bool lazy = adaptive && call.may_lazy() && lazy_context(c) && call.a0 == 0 && n_frames >= 2 * SCAN_CHUNK && SCAN_CHUNK == 32;
     const bool hist_valid = lazy && c->hist_pending && c->hist_n == n_arrays;
     if (c->hist_pending && !hist_valid) {
-        if (c->capturing) return fail(c, MCA_HIP_ERR_HIP, "lazy tails: a recording found an unsettled state (mca_hip_graph_launch settles it first)");
+        if (call.recording()) return fail(c, MCA_HIP_ERR_HIP, "lazy tails: a recording found an unsettled state (mca_hip_graph_launch settles it first)");
         if ((rc = settle_history(c, st))) return rc;
     }
-    c->lazy_now = lazy;
-    if (c->prec == MCA_HIP_SRP_ADAPTIVE) set_call_planes(c, adaptive ? 1 : 2);
+    call.lazy = lazy;
+    // the coarse pass of an adaptive call on one fp16 plane; every other call on the context's own rows (ADAPTIVE: as FP16X3)
+    const RowLayout lay = row_layout(c, adaptive ? 1 : c->tab_planes), x2 = row_layout(c, 2);
     const int n_chunks = (n_frames + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if (adaptive && (rc = ensure_adapt_workspace(c, n_arrays, n_frames, n_chunks))) { c->lazy_now = false; return rc; }
-    rc = run_correlation_map(c, pcm, array_stride, mic_stride, n_arrays, n_frames, st);
-    c->lazy_now = false;
-    if (rc) return rc;
+    if (adaptive && (rc = ensure_adapt_workspace(c, n_arrays, n_frames, n_chunks))) return rc;
+    if ((rc = run_correlation_map(c, call, lay, pcm, array_stride, mic_stride, n_arrays, n_frames, st))) return rc;
+    const MapResult &map = call.map;
 
     const bool gate = c->cfg.use_power_floor != 0;
-    time_begin(c, MCA_HIP_K_SCAN_PICK, st);
+    time_begin(c, call, MCA_HIP_K_SCAN_PICK, st);
     if (gate) {
         GateArgs gg{};
         gg.power_lin = c->ws.d_power; gg.n_frames = n_frames; gg.fft_n = c->N;
@@ -1607,12 +1625,12 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         hipLaunchKernelGGL(k_gate, dim3(n_arrays), dim3(256), 0, st, gg);
     }
     ScanPickArgs pa{};
-    pa.C = c->ws.d_C; pa.c_planes = c->ws.c_planes; pa.c_plane_stride = c->ws.c_plane; pa.n_frames = n_frames; pa.Dp = c->Dp; pa.D = c->D; pa.P = c->P; pa.S = c->S;
+    pa.C = c->ws.d_C; pa.c_planes = map.c_planes; pa.c_plane_stride = map.c_plane; pa.n_frames = n_frames; pa.Dp = c->Dp; pa.D = c->D; pa.P = c->P; pa.S = c->S;
     pa.chunk = SCAN_CHUNK; pa.n_chunks = n_chunks;
     pa.mu = ENERGY_MU; pa.one_minus_mu = ENERGY_ONE_MINUS_MU;                 // SteeringBeamforming.h:70, .cpp:134,139 (float arithmetic)
     pa.inv_norm = exact_reciprocal(30.f * (float)c->P);
     pa.state_in = c->d_E[c->e_cur] + a0 * c->D; pa.state_out = c->d_E[c->e_cur ^ 1] + a0 * c->D;
-    pa.part_planes = c->ws.partial_done ? c->ws.part_planes : 1; pa.part_plane_stride = (long long)n_arrays * n_chunks * c->D;
+    pa.part_planes = map.partial_done ? map.part_planes : 1; pa.part_plane_stride = (long long)n_arrays * n_chunks * c->D;
     pa.part = c->ws.d_part; pa.nvoiced = c->ws.d_nv; pa.e_start = c->ws.d_estart; pa.voiced = gate ? c->ws.d_voiced : nullptr;
     pa.grid = c->d_grid; pa.doa_bin = doa_bin; pa.doa_rad = doa_rad; pa.prob = prob; pa.energy = energy;
     const int gpa = (n_frames + REPAIR_GROUP - 1) / REPAIR_GROUP;
@@ -1631,7 +1649,7 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         // Not the widest peak pick (D > 386: k_scan_pick<8, 1> has no register left for the append), and only while the launch's LDS -- energy
         // rows, the transform's table, a scratch per wave, the static arrays -- fits a CU: those calls keep the stand-alone k_steer_patch.
         const size_t tail_lds = (size_t)32 * (c->Dp + 8) * sizeof(float) + (size_t)(F1K_TWORDS + 8 * F1K_SCRATCH) * sizeof(float2) + 2048;
-        if (c->steer_now && c->steer_fused_now && c->d_steer_mlist && SCAN_SUB == SCAN_CHUNK && c->S == 1 && !gate && (size_t)n_arrays * n_frames < c->d_steer_mlist.n &&
+        if (call.steer && call.steer_fused && c->d_steer_mlist && SCAN_SUB == SCAN_CHUNK && c->S == 1 && !gate && (size_t)n_arrays * n_frames < c->d_steer_mlist.n &&
             c->D - 2 <= 384 && c->D <= 512 && tail_lds <= 160 * 1024) {
             // the list is empty unless a call that listed misses never reached its synthesis (which empties it): an error in between
             if (c->steer_mlist_dirty) HIP_TRY(c, hipMemsetAsync(c->d_steer_mlist, 0, sizeof(int), st));
@@ -1642,9 +1660,9 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             sp.window = c->d_window; sp.doa_bin = doa_bin; sp.all = 0; sp.miss = c->d_steer_miss;
             sp.bf.rows = c->d_steer_rows; sp.bf.q = c->d_steer_q; sp.bf.nyq = c->d_steer_nyq; sp.bf.pred = c->d_steer_pred + a0; sp.bf.Y = c->d_steer_Y;
             sp.y_f0 = 0; sp.y_frames = n_frames;
-            c->steer_patched_now = true;
+            call.steer_patched = true;
         }
-        if (c->h_probe && !c->capturing) {
+        if (c->h_probe && !call.recording()) {
             c->fb_frames_ring[c->fb_calls % FB_RING] = c->adapt_frames_total + (unsigned long long)n_arrays * n_frames;
             c->fb_launch_m[c->fb_calls % FB_RING] = c->fb_m > 0 ? c->fb_m - 1 : 0;       // (the eligible call this piece belongs to)
             pa.probe = c->h_probe + 4 * (c->fb_calls % FB_RING); pa.probe_seq = ++c->fb_calls;
@@ -1652,7 +1670,7 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     }
     const int nthr = round_up(c->D, 64);
     dim3 g3(pa.n_chunks, n_arrays);
-    if (!c->ws.partial_done) hipLaunchKernelGGL(k_scan_partial, g3, dim3(round_up(c->Dp / 4, 64)), 0, st, pa);   // a thread per four delays
+    if (!map.partial_done) hipLaunchKernelGGL(k_scan_partial, g3, dim3(round_up(c->Dp / 4, 64)), 0, st, pa);   // a thread per four delays
     // ungated calls: k_scan_pick composes its chunk's start value itself (the chunks further back than four have decayed below the
     // last bit); with the gate a chunk may hold no advancing frame at all and the composition runs over all of them, in order
     // The look-back drops g^4 E_{c-4} (g = 0.8^32: 3.9e-13 of E), which is below the last bit only while the map is bounded: under PHAT
@@ -1683,41 +1701,38 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         // exact repair: list the row groups the flagged frames depend on, recompute them with the hi + lo operand planes and
         // the three-product contraction, patch them into the map, pick the flagged chunks again (k_scan_repick).
         // Every launch is sized for the worst case (all rows) and exits at the device-side count.
-        time_begin(c, MCA_HIP_K_REPAIR, st);
+        time_begin(c, call, MCA_HIP_K_REPAIR, st);
         const long long pass_rows = repair_pass_rows(c, n_arrays, n_frames);
         const int pass_groups = (int)(pass_rows / REPAIR_GROUP);
         const long long all_groups = (long long)n_arrays * (gpa + (hist_valid ? HIST_UNITS : 0));     // (the list cannot be longer)
-        set_call_planes(c, 2);
-        for (long long g0 = 0; g0 < all_groups; g0 += pass_groups) {
+        for (long long g0 = 0; g0 < all_groups; g0 += pass_groups) {      // (the exact rows: two planes, x2)
             StftPhatArgs sa{};
             sa.pcm = pcm; sa.array_stride = array_stride; sa.mic_stride = mic_stride;
-            sa.M = c->M; sa.n_frames = n_frames; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = n_frames;
-            sa.window = c->d_window; sa.A = c->ws.d_Ax; sa.Kp = c->Kp; sa.a_row_elems = c->a_row_elems; sa.a_planes = 2;
-            sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
+            stft_common(c, sa);
+            sa.n_frames = n_frames; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = n_frames;
+            sa.A = c->ws.d_Ax; sa.a_row_elems = x2.row_elems; sa.a_planes = 2;
             sa.list = c->ws.d_list; sa.n_list = c->ws.d_nlist; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = gpa;
             if (hist_valid) { sa.hist_in = c->d_hist_pcm[c->hist_cur]; sa.hist_base = n_arrays * gpa; }
             CandArgs ca{};
             if (pa.umask) {
                 // candidate columns: the exact values where the flagged frames need them, straight into the map (no partial maps, no patch) --
                 // by the workgroup that writes a unit's rows, inside the list-mode launch (4 / 8 microphones: k_stft_phat_wave)
-                ca.A = c->ws.d_Ax; ca.B = c->d_B; ca.Kp = c->Kp; ca.Dp = c->Dp; ca.a_row_elems = c->a_row_elems;
+                ca.A = c->ws.d_Ax; ca.B = c->d_B; ca.Kp = c->Kp; ca.Dp = c->Dp; ca.a_row_elems = x2.row_elems;
                 ca.list = c->ws.d_list; ca.n_list = c->ws.d_nlist; ca.list0 = (int)g0; ca.pass_rows = (int)pass_rows;
                 ca.umask = c->ws.d_umask; ca.umask_words = pa.umask_words; ca.need = c->ws.d_need; ca.groups_per_array = gpa; ca.n_frames = n_frames;
-                ca.C = c->ws.d_C; ca.c_planes = c->ws.c_planes; ca.c_plane_stride = c->ws.c_plane;
+                ca.C = c->ws.d_C; ca.c_planes = map.c_planes; ca.c_plane_stride = map.c_plane;
                 if (hist_valid) { ca.hist_C = c->d_hist_C[c->hist_cur]; ca.hist_base = n_arrays * gpa; }
                 sa.cand_on = 1; sa.cand = ca;       // (pa.umask: cand_call, which requires a lazy call, so lazy_context, so M is 4 or 8 -- the list-mode launch contracts)
             }
-            const size_t smem1 = ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
             // fixed, moderate grids: the kernels of the repair pass walk their device-side work lists
-            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, LIST_GRID), 1), smem1, st))) { set_call_planes(c, 1); return rc; }
+            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, LIST_GRID), 1), stft_fallback_lds(c, sa.fpb), st))) return rc;
             if (sa.cand_on) continue;
             RepairPatchArgs pp{};
             pp.groups_per_array = gpa;
-            pp.C = c->ws.d_C; pp.c_planes = c->ws.c_planes; pp.c_plane_stride = c->ws.c_plane; pp.n_frames = n_frames;
+            pp.C = c->ws.d_C; pp.c_planes = map.c_planes; pp.c_plane_stride = map.c_plane; pp.n_frames = n_frames;
             if (hist_valid) { pp.hist_C = c->d_hist_C[c->hist_cur]; pp.hist_base = n_arrays * gpa; }
-            launch_repair_contraction(c, c->ws, g0, pass_rows, n_arrays, pp, st);
+            launch_repair_contraction(c, c->ws, x2, g0, pass_rows, call.planned_arrays(n_arrays), pp, st);
         }
-        set_call_planes(c, 1);
         const int repick_thr = std::max(nthr, 512);
         const bool tail = pa.n_miss != nullptr;             // the launch also patches the steered rows: the transform's table and a scratch per wave behind the energy rows
         const size_t smem4 = (size_t)32 * (c->Dp + 8) * sizeof(float) + (tail ? (size_t)(F1K_TWORDS + repick_thr / 64 * F1K_SCRATCH) * sizeof(float2) : 0);
@@ -1734,7 +1749,7 @@ static int localise_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         if (gate) hipLaunchKernelGGL(k_doa_fill, dim3(n_arrays), dim3(1024), 0, st, fa);   // gated-out frames repeat the last FINAL pick
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
-        c->adapt_frames_total += (unsigned long long)n_arrays * n_frames;
+        if (!call.recording()) c->adapt_frames_total += (unsigned long long)n_arrays * n_frames;      // (a recording processes no frame: mca_hip_graph_launch counts the replays)
     }
     if (lazy) { c->hist_cur ^= 1; c->hist_n = n_arrays; c->hist_pending = true; }
     else c->hist_pending = false;                // (settled above, or consumed by an eager adaptive call: its own last frame was repaired)
@@ -1888,16 +1903,16 @@ static int steer_reserve(mca_hip_ctx *c, int n_arrays, int n_frames) { return st
 
 // the separation stage of such a call: patch pass (the frames whose pick is not the predicted bin; every frame if the analysis did not steer)
 // and synthesis, in passes of frames when Y does not hold the whole call
-static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride, int n_arrays, int n_frames,
+static int steer_separate(mca_hip_ctx *c, const StreamCall &call, const float *pcm, long long array_stride, long long mic_stride, int n_arrays, int n_frames,
                           const int *doa_bin, float *out_pcm, hipStream_t st)
 {
-    const size_t a0 = (size_t)c->a0;
+    const size_t a0 = (size_t)call.a0;
     const int pf = steer_pass_frames(c, n_arrays, n_frames);
-    const bool fused = c->steer_fused_now && pf == n_frames;
-    const bool patched = fused && c->steer_patched_now;       // the second pick of the localiser patched the missed frames and counted them (localise_impl)
+    const bool fused = call.steer_fused && pf == n_frames;
+    const bool patched = fused && call.steer_patched;         // the second pick of the localiser patched the missed frames and counted them (localise_impl)
     const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2);
     float *tails[2] = {c->d_steer_tail, c->d_steer_tail + (size_t)c->cfg.max_arrays * FFT_H};
-    time_begin(c, MCA_HIP_K_BEAMFORM, st);
+    time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
     int pass = 0;
     for (int f0 = 0; f0 < n_frames; f0 += pf, ++pass) {
         const int f1 = std::min(n_frames, f0 + pf), np = f1 - f0;
@@ -1930,10 +1945,10 @@ static int steer_separate(mca_hip_ctx *c, const float *pcm, long long array_stri
     return MCA_HIP_OK;
 }
 
-static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+static int separate_impl(mca_hip_ctx *c, const StreamCall &call, const float *pcm, long long array_stride, long long mic_stride,
                          int n_arrays, int n_frames, const float *doa_rad, float *out_pcm, hipStream_t st, const int *doa_bin = nullptr)
 {
-    const size_t a0 = (size_t)c->a0;
+    const size_t a0 = (size_t)call.a0;
     if (doa_bin && c->d_bftab && c->n2048 && (reinterpret_cast<uintptr_t>(out_pcm) & 7) == 0) {
         // 2048-sample frames, the localiser's own picks: one wave per run of frames, a transform per channel (k_beamform_wave_2048)
         BeamformWaveArgs wa{};
@@ -1948,7 +1963,7 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         wa.tail_in = c->d_tail[c->tail_cur] + a0 * c->S * c->H; wa.tail_out = c->d_tail[c->tail_cur ^ 1] + a0 * c->S * c->H;
         const int wgs = (n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1);
         const size_t smem_w = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH + 4 * 512) * sizeof(float2);
-        time_begin(c, MCA_HIP_K_BEAMFORM, st);
+        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
         hipLaunchKernelGGL(k_beamform_wave_2048, dim3(wgs, n_arrays, c->S), dim3(256), smem_w, st, wa);
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
@@ -1968,7 +1983,7 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             const int runs = (n_frames + wa.ft - 1) / wa.ft;
             const size_t smem_ms = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2) + (size_t)4 * c->S * FFT_H * sizeof(float);
             const dim3 gms((runs + 3) / 4, n_arrays);
-            time_begin(c, MCA_HIP_K_BEAMFORM, st);
+            time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
 #define BFMS(NPT)                                                                                                                   \
             do {                                                                                                                    \
                 if (smem_ms > 64 * 1024) {                                                                                          \
@@ -2003,7 +2018,7 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
             if (wa.skew >= wa.ft) wa.skew = 0;
             else gb = dim3(n_arrays, wgs, c->S);
         }
-        time_begin(c, MCA_HIP_K_BEAMFORM, st);
+        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
         if (c->M & 1) hipLaunchKernelGGL(k_beamform_wave<true>, gb, dim3(256), smem, st, wa);
         else hipLaunchKernelGGL(k_beamform_wave<false>, gb, dim3(256), smem, st, wa);
         time_end(c, st);
@@ -2035,7 +2050,7 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         const long long per_cu = smem <= 80 * 1024 ? 2 : 1;
         while (ba.ft > 4 && (long long)n_arrays * ((n_frames + ba.ft - 1) / ba.ft) < 256 * per_cu) ba.ft >>= 1;
         HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_beamform_512), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        time_begin(c, MCA_HIP_K_BEAMFORM, st);
+        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
         hipLaunchKernelGGL(k_beamform_512, dim3((n_frames + ba.ft - 1) / ba.ft, n_arrays), dim3(512), smem, st, ba);
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
@@ -2053,7 +2068,7 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
         if (smem > 160 * 1024) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "fft_size x n_mics exceeds the 160 KiB LDS of a CU");
         if (smem > 64 * 1024)
             HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_beamform_gen), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        time_begin(c, MCA_HIP_K_BEAMFORM, st);
+        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
         ba.S_all = c->S;
         for (int s0 = 0; s0 < c->S; s0 += s_pass) {
             ba.s0 = s0; ba.S = std::min(s_pass, c->S - s0);
@@ -2069,7 +2084,7 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
                         (size_t)(ba.ft + 1) * c->S * sizeof(double);
     if (smem > 160 * 1024) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "n_mics/n_sources combination exceeds the 160 KiB LDS of a CU");
     dim3 g((n_frames + ba.ft - 1) / ba.ft, n_arrays);
-    time_begin(c, MCA_HIP_K_BEAMFORM, st);
+    time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
 #define BF_LAUNCH(K)                                                                                                     \
     do {                                                                                                                 \
         if (smem > 64 * 1024)                                                                                            \
@@ -2084,52 +2099,30 @@ static int separate_impl(mca_hip_ctx *c, const float *pcm, long long array_strid
     return MCA_HIP_OK;
 }
 
-int mca_hip_localise_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
-                                int n_arrays, int n_frames, int *doa_bin, float *doa_rad, float *prob,
-                                float *energy, void *stream)
+// The stream calls behind the public entry points, which build the record; graph_record and the host-pointer entry points come with
+// records of their own.  A recording enqueues into a capture: nothing runs, so no state index moves (mca_hip_graph_launch does it, per replay).
+static int localise_call(mca_hip_ctx *c, StreamCall &call, const float *pcm, long long array_stride, long long mic_stride,
+                         int n_arrays, int n_frames, int *doa_bin, float *doa_rad, float *prob, float *energy, hipStream_t st)
 {
     int rc = check_stream_args(c, pcm, array_stride, mic_stride, n_arrays, n_frames);
     if (rc) return rc;
     if (!doa_bin) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev is NULL");
-    c->a0 = 0;
-    adapt_policy_begin(c, n_arrays, n_frames);
-    c->lazy_entry = !c->host_call;
-    rc = localise_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, (hipStream_t)stream);
-    c->lazy_entry = false;
-    if (rc) return rc;
-    c->last_arrays = n_arrays; c->last_frames = n_frames;
-    c->e_cur ^= 1;
+    adapt_policy_begin(c, call, n_arrays, n_frames);
+    if ((rc = localise_impl(c, call, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, st))) return rc;
+    if (!call.recording()) { c->last_arrays = n_arrays; c->last_frames = n_frames; c->e_cur ^= 1; }
     return MCA_HIP_OK;
 }
 
 // doa_bin: the grid bins behind doa_rad when they are the localiser's own picks (NULL: arbitrary angles)
-static int separate_frames_dev_bins(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
-                                    int n_arrays, int n_frames, const float *doa_rad, float *out_pcm, void *stream, const int *doa_bin)
+static int separate_call(mca_hip_ctx *c, const StreamCall &call, const float *pcm, long long array_stride, long long mic_stride,
+                         int n_arrays, int n_frames, const float *doa_rad, float *out_pcm, hipStream_t st, const int *doa_bin)
 {
     int rc = check_stream_args(c, pcm, array_stride, mic_stride, n_arrays, n_frames);
     if (rc) return rc;
     if (!doa_rad || !out_pcm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev/out_pcm_dev is NULL");
-    c->a0 = 0;
-    rc = separate_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
-    if (rc) return rc;
-    c->tail_cur ^= 1;
+    if ((rc = separate_impl(c, call, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, st, doa_bin))) return rc;
+    if (!call.recording()) c->tail_cur ^= 1;
     return MCA_HIP_OK;
-}
-
-int mca_hip_separate_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
-                                int n_arrays, int n_frames, const float *doa_rad, float *out_pcm, void *stream)
-{
-    return separate_frames_dev_bins(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, stream, nullptr);
-}
-
-int mca_hip_separate_frames_bins_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
-                                     int n_arrays, int n_frames, const int *doa_bin, const float *doa_rad, float *out_pcm, void *stream)
-{
-    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!doa_bin) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev is NULL");
-    int rc = ensure_bf_table(c);
-    if (rc) return rc;
-    return separate_frames_dev_bins(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, stream, doa_bin);
 }
 
 int mca_hip_process_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
@@ -2143,23 +2136,43 @@ int mca_hip_process_frames_dev(mca_hip_ctx *c, const float *pcm, long long array
     if (!doa_bin) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev is NULL");
     if (!out_pcm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev/out_pcm_dev is NULL");
     if ((rc = ensure_bf_table(c))) return rc;
-    c->a0 = 0;
-    const bool steer = steer_applies(c) && !c->host_call && !c->capturing;
+    StreamCall call; hipStream_t st = (hipStream_t)stream;     // (a device-pointer call: the host-pointer entry points and the recordings run the two stages)
+    const bool steer = steer_applies(c);
     if (steer && (rc = steer_prepare(c, n_arrays, n_frames))) return rc;
     if (steer) steer_policy_begin(c);
-    c->steer_now = steer && c->steer_spec && steer_pass_frames(c, n_arrays, n_frames) == n_frames; c->steer_fused_now = false; c->steer_patched_now = false;
-    adapt_policy_begin(c, n_arrays, n_frames);
-    c->lazy_entry = !c->host_call;
-    rc = localise_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, (hipStream_t)stream);
-    c->lazy_entry = false;
-    c->steer_now = false;
-    if (!rc && steer) rc = steer_separate(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, out_pcm, (hipStream_t)stream);
-    else if (!rc) rc = separate_impl(c, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
-    c->steer_fused_now = false; c->steer_patched_now = false;      // (they describe this call only)
+    call.steer = steer && c->steer_spec && steer_pass_frames(c, n_arrays, n_frames) == n_frames;
+    adapt_policy_begin(c, call, n_arrays, n_frames);
+    rc = localise_impl(c, call, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, st);
+    if (!rc && steer) rc = steer_separate(c, call, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, out_pcm, st);
+    else if (!rc) rc = separate_impl(c, call, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, st, doa_bin);
     if (rc) return rc;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
     c->e_cur ^= 1; c->tail_cur ^= 1;
     return MCA_HIP_OK;
+}
+
+int mca_hip_localise_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+                                int n_arrays, int n_frames, int *doa_bin, float *doa_rad, float *prob,
+                                float *energy, void *stream)
+{
+    StreamCall call;
+    return localise_call(c, call, pcm, array_stride, mic_stride, n_arrays, n_frames, doa_bin, doa_rad, prob, energy, (hipStream_t)stream);
+}
+
+int mca_hip_separate_frames_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+                                int n_arrays, int n_frames, const float *doa_rad, float *out_pcm, void *stream)
+{
+    return separate_call(c, StreamCall(), pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, nullptr);
+}
+
+int mca_hip_separate_frames_bins_dev(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride,
+                                     int n_arrays, int n_frames, const int *doa_bin, const float *doa_rad, float *out_pcm, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!doa_bin) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_bin_dev is NULL");
+    int rc = ensure_bf_table(c);
+    if (rc) return rc;
+    return separate_call(c, StreamCall(), pcm, array_stride, mic_stride, n_arrays, n_frames, doa_rad, out_pcm, (hipStream_t)stream, doa_bin);
 }
 
 // ---- real-time mode: the stream call as a HIP graph ------------------------------------------
@@ -2215,25 +2228,16 @@ int mca_hip_graph_create(mca_hip_ctx *c, const float *pcm, long long array_strid
 static int graph_record(mca_hip_graph *g, int idx)
 {
     mca_hip_ctx *c = g->c;
-    const int e_cur = c->e_cur, tail_cur = c->tail_cur;
-    const unsigned timing = c->timing;
-    const unsigned long long adapt_frames = c->adapt_frames_total;
-    c->timing = 0;                              // event pairs belong to eager calls
-    const bool suspended = c->adapt_suspended;
-    c->adapt_suspended = false; c->capturing = true;   // a recording is the mode's own kernels, whatever the eager calls do at the moment
-    struct Restore { mca_hip_ctx *c; bool s; ~Restore() { c->adapt_suspended = s; c->capturing = false; } } restore{c, suspended};
+    StreamCall call;               // a recording: the mode's own kernels whatever the eager calls do at the moment, no event pairs, no state moved
+    call.caller = Caller::RECORDING;
     HIP_TRY(c, hipStreamBeginCapture(g->cap, hipStreamCaptureModeRelaxed));
     int rc = MCA_HIP_OK;
     if (g->doa_bin)
-        rc = mca_hip_localise_frames_dev(c, g->pcm, g->array_stride, g->mic_stride, g->n_arrays, g->n_frames, g->doa_bin, g->doa_rad,
-                                         g->prob, g->energy, g->cap);
+        rc = localise_call(c, call, g->pcm, g->array_stride, g->mic_stride, g->n_arrays, g->n_frames, g->doa_bin, g->doa_rad, g->prob, g->energy, g->cap);
     if (!rc && g->out_pcm)
-        rc = separate_frames_dev_bins(c, g->pcm, g->array_stride, g->mic_stride, g->n_arrays, g->n_frames, g->doa_rad, g->out_pcm, g->cap, g->doa_bin);
+        rc = separate_call(c, call, g->pcm, g->array_stride, g->mic_stride, g->n_arrays, g->n_frames, g->doa_rad, g->out_pcm, g->cap, g->doa_bin);
     hipGraph_t graph = nullptr;
     const hipError_t e = hipStreamEndCapture(g->cap, &graph);
-    c->timing = timing;
-    c->e_cur = e_cur; c->tail_cur = tail_cur;   // nothing ran: the state has not moved
-    c->adapt_frames_total = adapt_frames;       // ... and no frame was processed (mca_hip_graph_launch counts the replays)
     if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(c, MCA_HIP_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
     g->graph[idx] = graph;
@@ -2336,6 +2340,8 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
     int rc = check_stream_args(c, d_pcm, as, ms, n_arrays, n_frames);
     if (!rc && out_pcm) rc = ensure_bf_table(c);
     if (rc) return rc;
+    StreamCall call;                                             // the eager form on either path: the pageable and the page-locked one return the same bits
+    call.caller = Caller::HOST;
 
     if (!is_pinned(pcm)) {
         if (I16) {
@@ -2345,10 +2351,8 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
         } else {
             HIP_TRY(c, hipMemcpy(d_pcm, pcm, n_pcm * 4, hipMemcpyHostToDevice));
         }
-        c->host_call = true;
-        rc = mca_hip_localise_frames_dev(c, d_pcm, as, ms, n_arrays, n_frames, d_bin, d_rad, d_prob, d_en, nullptr);
-        c->host_call = false;
-        if (!rc && out_pcm) rc = separate_frames_dev_bins(c, d_pcm, as, ms, n_arrays, n_frames, d_rad, d_out, nullptr, d_bin);
+        rc = localise_call(c, call, d_pcm, as, ms, n_arrays, n_frames, d_bin, d_rad, d_prob, d_en, nullptr);
+        if (!rc && out_pcm) rc = separate_call(c, call, d_pcm, as, ms, n_arrays, n_frames, d_rad, d_out, nullptr, d_bin);
         if (rc) return rc;
         HIP_TRY(c, hipDeviceSynchronize());
         HIP_TRY(c, hipMemcpy(doa_bin, d_bin, n_fs * 4, hipMemcpyDeviceToHost));
@@ -2370,11 +2374,8 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
     // stream (a *_dev call or a graph launch that still writes d_E / d_tail, the memsets of mca_hip_reset).  This entry point
     // is synchronous anyway, so it starts from an idle device.
     HIP_TRY(c, hipDeviceSynchronize());
-    // on every exit -- also the early ones of HIP_TRY -- the planning override is dropped and the streams are drained
-    struct Guard {
-        mca_hip_ctx *c; hipStream_t s[3];
-        ~Guard() { c->plan_rows = 0; c->plan_arrays = 0; c->a0 = 0; for (hipStream_t q : s) (void)hipStreamSynchronize(q); }
-    } guard{c, {s_in, s_run, s_out}};
+    // on every exit -- also the early ones of HIP_TRY -- the streams are drained
+    struct Guard { hipStream_t s[3]; ~Guard() { for (hipStream_t q : s) (void)hipStreamSynchronize(q); } } guard{{s_in, s_run, s_out}};
     // (with the power gate the call stays one chunk: mca_hip_copy_gate reads the flags of the whole call from one workspace)
     const int nchunk = c->cfg.use_power_floor ? 1 : std::min(n_arrays, MAXC);
     const bool out_pinned[5] = {is_pinned(doa_bin), is_pinned(doa_rad), is_pinned(prob), is_pinned(energy), is_pinned(out_pcm)};
@@ -2387,9 +2388,9 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
         a0 += na;
     }
     a0 = 0;
-    adapt_policy_begin(c, n_arrays, n_frames);
-    c->plan_rows = (long long)n_arrays * n_frames;           // every chunk is planned as the whole call (bit-identical results)
-    c->plan_arrays = n_arrays;
+    adapt_policy_begin(c, call, n_arrays, n_frames);
+    call.rows_planned = (long long)n_arrays * n_frames;         // every chunk is planned as the whole call (bit-identical results)
+    call.arrays_planned = n_arrays;
     for (int k = 0; k < nchunk && !rc; ++k) {
         const int na = n_arrays / nchunk + (k < n_arrays % nchunk ? 1 : 0);
         HIP_TRY(c, hipStreamWaitEvent(s_run, c->io_ev[k], 0));
@@ -2397,11 +2398,11 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
             const long long n4 = (long long)na * as / 4;
             hipLaunchKernelGGL(k_i16_to_f32, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s_run, d_i16 + (size_t)a0 * as, d_pcm + (size_t)a0 * as, n4);
         }
-        c->a0 = a0;                                           // the chunk's arrays on the one workspace, per-array state at its offset
-        rc = localise_impl(c, d_pcm + (size_t)a0 * as, as, ms, na, n_frames, d_bin + a0 * fs_, d_rad + a0 * fs_, d_prob + a0 * fs_,
+        StreamCall piece = call;
+        piece.a0 = a0;                                        // the chunk's arrays on the one workspace, per-array state at its offset
+        rc = localise_impl(c, piece, d_pcm + (size_t)a0 * as, as, ms, na, n_frames, d_bin + a0 * fs_, d_rad + a0 * fs_, d_prob + a0 * fs_,
                            energy ? d_en + a0 * fd_ : nullptr, s_run);
-        if (!rc && out_pcm) rc = separate_impl(c, d_pcm + (size_t)a0 * as, as, ms, na, n_frames, d_rad + a0 * fs_, d_out + a0 * fo_, s_run, d_bin + a0 * fs_);
-        c->a0 = 0;
+        if (!rc && out_pcm) rc = separate_impl(c, piece, d_pcm + (size_t)a0 * as, as, ms, na, n_frames, d_rad + a0 * fs_, d_out + a0 * fo_, s_run, d_bin + a0 * fs_);
         if (rc) break;
         HIP_TRY(c, hipEventRecord(c->io_ev[MAXC + k], s_run));
         HIP_TRY(c, hipStreamWaitEvent(s_out, c->io_ev[MAXC + k], 0));
@@ -2412,7 +2413,6 @@ int process_frames_host_impl(mca_hip_ctx *c, const SampleT *pcm, int n_arrays, i
         if (out_pcm && out_pinned[4]) HIP_TRY(c, hipMemcpyAsync(out_pcm + a0 * fo_, d_out + a0 * fo_, na * fo_ * 4, hipMemcpyDeviceToHost, s_out));
         a0 += na;
     }
-    c->plan_rows = 0; c->plan_arrays = 0;
     (void)hipStreamSynchronize(s_in); (void)hipStreamSynchronize(s_run); (void)hipStreamSynchronize(s_out);
     if (rc) return rc;
     c->last_arrays = n_arrays; c->last_frames = n_frames;
@@ -2497,7 +2497,7 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     if (trk) {
         if (!trk->doa_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (c->capturing || (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
             return fail(c, MCA_HIP_ERR_UNSUPPORTED, "the tracked call cannot be recorded into a HIP graph");
         // the rows and argmaxes of the call, where the caller does not take them
         const size_t rows = (size_t)n_arrays * n_frames;
@@ -2505,15 +2505,14 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
         if (!argmax && (rc = grow_ws(c, c->d_trk_idx, rows, "the tracked call's argmaxes"))) return rc;
         if (!argmax) argmax = c->d_trk_idx;
     }
-    if (c->prec == MCA_HIP_SRP_ADAPTIVE) set_call_planes(c, 2);      // the 2-microphone path always runs the exact split
+    StreamCall call;
+    const RowLayout lay = row_layout(c, c->tab_planes);              // the context's own rows (ADAPTIVE: the 2-microphone path always runs the exact split)
     // the tracked call plans its contraction as one K range whatever the batch (plan_gemm): the rows of an array, and so its track,
     // then do not depend on how many arrays run beside it.  (The K range of two microphones is short: the split buys little.)
-    if (trk) c->plan_rows = 1LL << 40;
-    rc = run_correlation_map(c, pcm, array_stride, mic_stride, n_arrays, n_frames, st);
-    if (trk) c->plan_rows = 0;
-    if (rc) return rc;
+    if (trk) call.rows_planned = 1LL << 40;
+    if ((rc = run_correlation_map(c, call, lay, pcm, array_stride, mic_stride, n_arrays, n_frames, st))) return rc;
     Gcc2ScanArgs ga{};
-    ga.C = c->ws.d_C; ga.c_planes = c->ws.c_planes; ga.c_plane_stride = c->ws.c_plane; ga.n_frames = n_frames; ga.Dp = c->Dp; ga.D = c->D;
+    ga.C = c->ws.d_C; ga.c_planes = call.map.c_planes; ga.c_plane_stride = call.map.c_plane; ga.n_frames = n_frames; ga.Dp = c->Dp; ga.D = c->D;
     // frames per chunk: every chunk re-reads 160 warm-up frames (recursion + DOA smoothing), so long chunks are cheaper;
     // shorter ones for small batches so that a few hundred workgroups exist
     ga.chunk = 128;
@@ -2527,7 +2526,7 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     ga.grid = c->d_grid; ga.argmax = argmax; ga.doa_rad = doa_rad; ga.prob = prob; ga.corr = corr;
     if (trk && !ga.corr) ga.corr = c->d_trk_corr;
     const bool gate = c->cfg.use_power_floor != 0;
-    time_begin(c, MCA_HIP_K_GCC2_SCAN, st);
+    time_begin(c, call, MCA_HIP_K_GCC2_SCAN, st);
     if (gate) {
         // setPowerFloor + the gate of processParametrisation (BinauralLocalisation.cpp:387-404, :425-434): 3 s of floor
         // estimation (power + 1e-10 per frame), then voiced = FFTLogPower > floor + 6 dB; the recursions below only see

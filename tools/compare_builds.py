@@ -14,7 +14,19 @@ OFF and candidate columns on, so the small batches run coarse + repair whatever 
   the host-pointer entry points: pageable, page-locked (the chunked path), 16-bit PCM, and under MCA_HIP_WS_MAX_MB = 1 (the sliced path);
   a graph: 4 launches, an eager call that grows the workspace, 2 more launches;
   the gated 2-microphone path with a tracker (the larger call takes no rows / argmaxes), its frame hook, setProbability;
-  the double frame API; the multiband, temporal-GCC, mask and bmask modules: stream calls of 6, 40 and 6 frames and their frame hooks."""
+  the double frame API; the multiband, temporal-GCC, mask and bmask modules: stream calls of 6, 40 and 6 frames and their frame hooks.
+
+Sequences on ONE context (ADAPTIVE unless said otherwise), every call's outputs and the final state blob in the digest: what one call
+decided or left behind must not reach the next call, whoever the caller is:
+  a device-pointer call (lazy tails, steered), localisation alone, a pageable host call, a page-locked one (in chunks), a device-pointer
+  call with 1 array (another array count: the history is settled), one with 2 -- adaptive_fallback OFF and AUTO (the policy reads its
+  reports at a fixed lag, so a run is reproducible);
+  three device-pointer calls under MCA_HIP_WS_MAX_MB = 1 (the sliced map, the steered path in passes);
+  FP16 and ADAPTIVE: a call, a rejected call (max_arrays + 1 arrays: its error code is checked), a call;
+  a graph launched twice, an eager device-pointer call, one more launch;
+  2 microphones: mca_hip_gcc2_frames_dev, a tracked call, mca_hip_gcc2_frames_dev again (refused once a tracker is attached: the refusal's
+  code enters the digest), a tracked call;
+  4 microphones: localisation alone three times, then state_save."""
 import os
 import sys
 
@@ -181,6 +193,124 @@ def child(out_path):
     ctx.close()
     res["double frame API: steering, beamformer, power"] = frame.digest(*parts)
 
+    # sequences on ONE context that change the caller, the array count or the path between calls (the docstring's last paragraph)
+    def outs(ctx, n_arr, F, audio=True):
+        r = [torch.zeros((n_arr, F, ctx.S), dtype=torch.int32, device=dev), torch.zeros((n_arr, F, ctx.S), device=dev), torch.zeros((n_arr, F, ctx.S), device=dev),
+             torch.zeros((n_arr, F, ctx.D), device=dev)]
+        return r + ([torch.zeros((n_arr, ctx.S, F * ctx.hop), device=dev)] if audio else [])
+
+    def seq_dev(ctx, chunk, F, parts, audio=True):          # process_frames_dev, or localise_frames_dev alone
+        r = outs(ctx, chunk.shape[0], F, audio)
+        ctx.process_frames_dev(torch.from_numpy(chunk.copy()).to(dev), F, *r, separate=audio)
+        torch.cuda.synchronize()
+        parts += [t.cpu().numpy() for t in r]
+
+    def seq_host(ctx, chunk, parts, pin=False):
+        b = api.PinnedBuffer(chunk.shape, np.float32) if pin else None
+        if pin:
+            b.array[...] = chunk
+        r = ctx.process_frames_host(b.array if pin else chunk, want_energy=True)
+        parts += [np.array(r[k]) for k in ("bin", "doa", "prob", "energy", "out")]
+        if pin:
+            b.close()
+
+    def finish(name, ctx, parts):
+        parts.append(np.frombuffer(ctx.state_save(), dtype=np.uint8))
+        ctx.close()
+        res[name] = frame.digest(*parts)
+
+    def cut(pcm, hop, t0, F):
+        return pcm[:, :, t0 * hop:(t0 + F + 1) * hop]
+
+    adaptive = api.SRP_ADAPTIVE
+    seq_frames = (64, 160, 64, 160, 64, 64)
+    pcm_seq = pcm_of(synth.ULA8, 48000, 512, sum(seq_frames), 570)
+    for tag, auto in (("adaptive_fallback OFF", False), ("adaptive_fallback AUTO", True)):
+        ctx = api.Context(48000, synth.ULA8, 1024, 0.5, 1, srp_precision=adaptive, max_arrays=A_MAX, adaptive_fallback=auto)
+        parts, t0 = [], 0
+        for i, F in enumerate(seq_frames):
+            chunk = cut(pcm_seq, 512, t0, F)
+            if i == 0 or i == 5:
+                seq_dev(ctx, chunk, F, parts)
+            elif i == 1:
+                seq_dev(ctx, chunk, F, parts, audio=False)
+            elif i == 4:
+                seq_dev(ctx, chunk[:1], F, parts)           # another array count: the history is settled
+            else:
+                seq_host(ctx, chunk, parts, pin=i == 3)
+            t0 += F
+        finish("sequence: dev, localise alone, pageable host, page-locked host, dev with 1 array, dev; ADAPTIVE, %s" % tag, ctx, parts)
+
+    os.environ["MCA_HIP_WS_MAX_MB"] = "1"
+    sliced = ctx_of(synth.ULA8, 48000, 1024, adaptive)
+    del os.environ["MCA_HIP_WS_MAX_MB"]
+    dev_stream("sequence: three dev calls under MCA_HIP_WS_MAX_MB = 1 (sliced map, steered path in passes), ADAPTIVE", sliced, pcm_seq)
+
+    for pname, prec in (precisions[1], precisions[3]):
+        ctx, parts, t0 = ctx_of(synth.ULA8, 48000, 1024, prec), [], 0
+        for i, F in enumerate(CALLS):
+            if i == 1:                                       # rejected: more arrays than the context has
+                many = np.zeros((A_MAX + 1, 8, (F + 1) * 512), dtype=np.float32)
+                try:
+                    seq_dev(ctx, many, F, [])
+                    code = 0
+                except api.MCArrayHipError as e:
+                    code = int(str(e).split("error")[1].split(":")[0])
+                if code != -1:                               # MCA_HIP_ERR_INVALID_ARGUMENT
+                    sys.exit("the call with max_arrays + 1 arrays returned %d" % code)
+                parts.append(np.asarray([code]))
+            else:
+                seq_dev(ctx, cut(pcm_seq, 512, t0, F), F, parts)
+                t0 += F
+        finish("sequence: dev, a rejected call, dev; %s" % pname, ctx, parts)
+
+    ctx = ctx_of(synth.ULA8, 48000, 1024, adaptive)
+    F = 64
+    buf = [torch.zeros((A, 8, (F + 1) * 512), device=dev)] + outs(ctx, A, F)
+    g = ctx.graph_create(buf[0], F, *buf[1:])
+    parts = []
+    for i in range(4):
+        chunk = cut(pcm_seq, 512, i * F, F)
+        if i == 2:                                           # an eager call in between: it leaves lazy tails, the next launch settles them
+            seq_dev(ctx, chunk, F, parts)
+            continue
+        buf[0].copy_(torch.from_numpy(chunk.copy()))
+        g.launch()
+        torch.cuda.synchronize()
+        parts += [t.cpu().numpy() for t in buf[1:]]
+    g.close()
+    finish("sequence: a graph launched twice, an eager dev call, one more launch; ADAPTIVE", ctx, parts)
+
+    # (gcc2_frames_dev is refused once a tracker is attached, so the third call of the sequence is that refusal and a tracked call follows it)
+    ctx = api.Context(fs, synth.BINAURAL, N, 3.0, 1, True, srp_precision=adaptive, max_arrays=A_MAX)
+    parts, t0 = [], 0
+    for i, F in enumerate(CALLS + (64,)):
+        x = torch.from_numpy(cut(pcm2, hop, t0, F).copy()).to(dev)
+        r = [torch.zeros((A, F), dtype=torch.int32, device=dev), torch.zeros((A, F), device=dev), torch.zeros((A, F), device=dev), torch.zeros((A, F, ctx.D), device=dev)]
+        if i == 0:
+            ctx.gcc2_frames_dev(x, F, *r)
+            ctx.gcc2_tracker_attach(seed=0x5EED0002)
+        elif i == 2:
+            try:
+                ctx.gcc2_frames_dev(x, F, *r)
+                sys.exit("gcc2_frames_dev ran on a context with a tracker")
+            except api.MCArrayHipError as e:
+                parts.append(np.asarray([int(str(e).split("error")[1].split(":")[0])]))
+            continue
+        else:
+            ctx.gcc2_tracked_frames_dev(x, F, r[1], argmax=r[0], prob=r[2], corr=r[3])
+        torch.cuda.synchronize()
+        parts += [t.cpu().numpy() for t in r]
+        t0 += F
+    finish("sequence: gcc2_frames_dev, a tracked call, gcc2_frames_dev refused, a tracked call; 2 microphones, ADAPTIVE", ctx, parts)
+
+    ctx, parts, t0 = ctx_of(XS4, 48000, 1024, adaptive), [], 0
+    pcm4 = pcm_of(XS4, 48000, 512, total, 580)
+    for F in CALLS:
+        seq_dev(ctx, cut(pcm4, 512, t0, F), F, parts, audio=False)
+        t0 += F
+    finish("sequence: localise alone three times (lazy tails), then state_save; 4 microphones, ADAPTIVE", ctx, parts)
+
     # the four modules: stream calls of 6, 40 and 6 frames, then the frame hooks
     def noise(n, seed):
         return np.stack([synth.noise_source_stream(synth.BINAURAL, np.deg2rad(20.0 - 45 * a), 16000, n, seed + a) for a in range(A)]).astype(np.float32)
@@ -238,7 +368,7 @@ def main():
         return child(sys.argv[2])
     if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
         sys.exit(__doc__)
-    par, new = frame.run_both(__file__, sys.argv[1])
+    par, new = frame.run_both(__file__, sys.argv[1], seconds=420)
     sys.exit(frame.report(par, new, "outputs and state blobs", sys.argv[1]))
 
 
