@@ -628,8 +628,11 @@ __device__ __forceinline__ bool wave_candidates(const float *En, int D, float ta
 // BeamformingSeparationAndLocalisation.cpp:87) go onto the repair list (once: `need` is a test-and-set per group), and the chunk
 // learns which chunk its second pick has to restart from.  need / chunk_from are cleaned by the kernels that consume them
 // (k_repair_patch, k_scan_repick); the list's length is reset by k_scan_carry.
+// (Block: max(round_up(D, 64), 512) threads, a thread per delay in the recursion.  Only the widest pick covers a grid of more than 512 delays
+// -- D = 513, 514: nine waves --, so only its instantiations are bound to 576; the registers are set by waves_per_eu either way, and the
+// code of all six is what a bound of 512 gives.)
 template <int PL, int MODE>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k_scan_pick(ScanPickArgs p)   // (two workgroups per CU: <= 128 VGPRs; the plan's last round spills two)
+__global__ __launch_bounds__(PL == 8 ? 576 : 512) __attribute__((amdgpu_waves_per_eu(4))) void k_scan_pick(ScanPickArgs p)   // (two workgroups per CU: <= 128 VGPRs; the plan's last round spills two)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float *sEn = reinterpret_cast<float *>(smem_raw);                   // [SCAN_SUB][Dl]

@@ -6,12 +6,18 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC := ../../mcarray_amd/csrc
 FLAGS := -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function
-all: libgemm_harness.so
+all: libgemm_harness.so libscan_harness.so
 gemm_harness.o: gemm_harness.hip gemm_harness.h $(CSRC)/kernels_gemm.hip $(CSRC)/mca_internal.h
 	$(HIPCC) $(FLAGS) -c $< -o $@
 gemm_harness_stream.o: gemm_harness_stream.hip gemm_harness.h $(CSRC)/kernels_stream.hip $(wildcard $(CSRC)/*.h)
 	$(HIPCC) $(FLAGS) -fno-slp-vectorize -c $< -o $@
 libgemm_harness.so: gemm_harness.o gemm_harness_stream.o
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
+# the scan / peak-pick / repair-plan kernels of csrc/kernels_stream.hip behind one launcher each (tests/test_gpu_scan_kernels.py): a library
+# of its own, because a second translation unit with the same kernels cannot link into libgemm_harness.so
+scan_harness.o: scan_harness.hip gemm_harness.h $(CSRC)/kernels_stream.hip $(wildcard $(CSRC)/*.h)
+	$(HIPCC) $(FLAGS) -fno-slp-vectorize -c $< -o $@
+libscan_harness.so: scan_harness.o
+	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 clean:
-	rm -f libgemm_harness.so gemm_harness.o gemm_harness_stream.o
+	rm -f libgemm_harness.so gemm_harness.o gemm_harness_stream.o libscan_harness.so scan_harness.o
