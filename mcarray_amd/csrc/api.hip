@@ -49,14 +49,7 @@ struct Knobs {
     bool force_generic = false;        // MCA_HIP_FORCE_GENERIC: the any-length kernels at N = 1024 too (parity test of both)
     bool no_n2048 = false;             // MCA_HIP_NO_N2048: the any-length kernels at 2048-sample frames (parity of both paths)
     bool scan_carry = false;           // MCA_HIP_SCAN_CARRY / cfg.scan_carry
-    int cand = -1;                     // MCA_HIP_ADAPT_CAND: -1 / unset = by the back-off policy's reports (cand_call), 1 = wherever a lazy 4 / 8-microphone call allows (no effect on other contexts), 0 = never (whole-row repair kernels)
-    bool lazy_tails = true;            // MCA_HIP_ADAPT_LAZY=0: every adaptive call repairs its own last rows for the state it hands over (round 4)
-};
-
-// Fixed launch shapes of the adaptive repair pass, whose kernels walk device-side work lists
-constexpr int REPAIR_ITEMS = 768;     // work items above which the repair contraction halves its K split (repair_ksplit_eff)
-constexpr int LIST_GRID = 512;        // workgroups of the list-mode analysis
-constexpr int REPICK_GRID = 256;      // workgroups of k_scan_repick
+};      // (MCA_HIP_ADAPT_CAND and MCA_HIP_ADAPT_LAZY: StreamShape::cand, ::lazy_tails)
 
 // Per-call workspace (everything a stream call allocates besides the per-array state, which lives in the context).  A call
 // can be worked off in pieces over a sub-range of its arrays -- the chunks of the host-pointer path -- with the per-array
@@ -87,13 +80,10 @@ struct G2FrameState {
     double doa = 0, prob = -1;                                  // _currentDOA, _prob (:339-340)
 };
 
-struct mca_hip_ctx {
+struct mca_hip_ctx : StreamShape {      // (the fixed shape every launch plan reads: stream_plan.h)
     mca_hip_config cfg{};
     std::vector<double> xyz;
-    int M = 0, P = 0, G = 0, D = 0, Dp = 0, K = 0, N = 0, H = 0, logH = 0, Kp = 0, S = 1, prec = 0;
-    bool ula = false, stream_ok = false, generic = false;
-    bool n512 = false;             // 512-sample frames with <= 8 microphones: k_stft_phat_512 / k_beamform_512 instead of the any-length kernels
-    bool n2048 = false;            // 2048-sample frames on the wave-level 1024-point transform (kernels_2048.hip): the beamformer for any M, the analysis for M <= 8 and > 2
+    int logH = 0;
     std::string stream_why;       // why the stream API is unavailable for this configuration
     float step = 0.f;
     std::vector<float> delays, grid;
@@ -104,16 +94,12 @@ struct mca_hip_ctx {
     DevBuf<double> d_micx;
     DevBuf<int2> d_pairs;
     DevBuf<unsigned char> d_B, d_Bt;      // (in bytes: float or fp16 by the precision, like the merged and folded tables below)
-    // ULA, one fp16 operand plane (the ADAPTIVE coarse pass, plain FP16), k_stft_phat_wave: the contraction index is the PRODUCT
-    // m = k * (j - i) -- pairs of spacing g at bin k steer with exp(j 2 pi k g tau_1 / N), so all (k, g) of equal product share one
-    // steering column and their PHAT sums are merged before the contraction: 1 962 instead of 3 591 complex terms per row for 8
-    // microphones (build_merged_tables)
-    bool merged = false; int n_merged = 0, Kp_m = 0;
+    // the merged contraction index (StreamShape::merged, build_merged_tables)
     DevBuf<unsigned char> d_Bm, d_Btm; DevBuf<unsigned short> d_mrank;
     // ... folded about broadside (fold_table.h): the merged rows are planar ([R | I]), d_Bm / d_Btm hold the folded values at full width in
     // planar K order, and d_Bfold the even and the odd half-width tables of k_srp_gemm_f16_fold: [2][Kp_m / 64][192][32]
-    bool fold = false; DevBuf<unsigned char> d_Bfold;
-    DevBuf<float2> d_bftab; int bf_pairs = 0;   // k_beamform_wave: steering rows per grid angle, [D + 1][bf_pairs][1024] (built on first use)
+    DevBuf<unsigned char> d_Bfold;
+    DevBuf<float2> d_bftab;                     // k_beamform_wave: steering rows per grid angle, [D + 1][bf_pairs][1024] (built on first use)
     // Delay-and-sum on the half spectrum (steer.h; steer_applies): the per-channel steering table, the predicted bin per array (the last pick of
     // the previous call; -1 on a new stream), the running miss total, the rows of Y (grown on demand) and two carries between frame passes
     DevBuf<float4> d_steer_rows; DevBuf<float2> d_steer_q; DevBuf<float> d_steer_nyq; DevBuf<int> d_steer_pred; DevBuf<unsigned long long> d_steer_miss;
@@ -156,7 +142,6 @@ struct mca_hip_ctx {
     unsigned long long ws_gen = 0;          // bumped by grow_ws, and by nothing else, whenever a workspace buffer is reallocated: recorded graphs hold the old pointers
     std::vector<mca_hip_graph *> graphs;   // live graphs of this context (orphaned by mca_hip_destroy)
     // adaptive SRP precision: fp16 coarse scan (one plane) + exact repair (hi + lo planes)
-    int tab_planes = 1;            // planes of the steering tables (2: FP16X3 and ADAPTIVE)
     DevBuf<unsigned long long> d_rstats;
     // lazy tails (mca_internal.h, HIST_FRAMES): what the last lazy adaptive call left for the next one, double buffered like d_E
     DevBuf<float> d_hist_pcm[2];                   // [max_arrays][M][HIST_SAMPLES]
@@ -164,7 +149,6 @@ struct mca_hip_ctx {
     DevBuf<float> d_ehist[2];                      // [max_arrays][D] the energies in front of them
     int hist_cur = 0, hist_n = 0;                  // the buffers that hold the pending history, the arrays it covers
     bool hist_pending = false;                     // the state in d_E is coarse: exact = settle_history, or the next lazy call's own repair pass
-    int n_cu = 256;
     unsigned long long adapt_frames_total = 0;
     float tau_en = 0.f;            // normalised energies closer than this cannot be ordered from the coarse map
     // ADAPTIVE backs off to plain FP16X3 (the arithmetic its repair pass reproduces) while most rows need the repair -- noise
@@ -221,7 +205,7 @@ struct StreamCall {
     long long rows_planned = 0;       // > 0: the rows the contraction is planned for -- the whole call's while it is worked off in pieces (plan_gemm)
     int arrays_planned = 0;           // ... and its arrays (repair_ksplit_for)
     // what the call decided on its way down: it leaves the repair of its last rows to the next call (the coarse analysis keeps the PCM);
-    // its analysis may steer ahead of the picks (Y holds the whole call) / did (launch_stft); the second pick patches the missed frames
+    // its analysis may steer ahead of the picks (Y holds the whole call) / did (AnalysisPlan::steers); the second pick patches the missed frames
     bool lazy = false, steer = false, steer_fused = false, steer_patched = false;
     MapResult map;
     bool recording() const { return caller == Caller::RECORDING; }   // the mode's own kernels whatever the back-off does; no policy, no counters, no event pairs
@@ -307,10 +291,8 @@ void free_ctx(mca_hip_ctx *c)
     delete c;                                                  // every device buffer goes with its member
 }
 
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // (the environment is read through knobs.h, by mca_hip_create only)
-Knobs read_knobs(const mca_hip_config &cfg)
+Knobs read_knobs(const mca_hip_config &cfg, StreamShape &shape)
 {
     Knobs k;
     auto geti = [](const char *v, long long dflt) { return v ? std::atoll(v) : dflt; };
@@ -324,8 +306,8 @@ Knobs read_knobs(const mca_hip_config &cfg)
     if (const char *v = env_str("MCA_HIP_WS_MAX_MB")) k.ws_max_bytes = (long long)std::atoll(v) << 20;
     k.force_generic = env_str("MCA_HIP_FORCE_GENERIC") != nullptr;
     k.scan_carry = cfg.scan_carry != 0 || env_str("MCA_HIP_SCAN_CARRY") != nullptr;
-    if (const char *v = env_str("MCA_HIP_ADAPT_LAZY")) k.lazy_tails = std::atoi(v) != 0;
-    if (const char *v = env_str("MCA_HIP_ADAPT_CAND")) k.cand = std::atoi(v) != 0 ? 1 : 0;
+    if (const char *v = env_str("MCA_HIP_ADAPT_LAZY")) shape.lazy_tails = std::atoi(v) != 0;
+    if (const char *v = env_str("MCA_HIP_ADAPT_CAND")) shape.cand = std::atoi(v) != 0 ? 1 : 0;
     k.no_n2048 = env_str("MCA_HIP_NO_N2048") != nullptr;
     return k;
 }
@@ -408,7 +390,7 @@ int build_steering_table(mca_hip_ctx *c)
 // the layout of rows of `planes` planes: the merged index with one plane on a merged context
 RowLayout row_layout(const mca_hip_ctx *c, int planes)
 {
-    const int kp = (c->merged && planes == 1) ? c->Kp_m : c->Kp;
+    const int kp = plan_kp(*c, planes);
     return {planes, kp, kp * planes};
 }
 
@@ -488,51 +470,6 @@ void time_end(mca_hip_ctx *c, hipStream_t st)
     (void)hipEventRecord(c->events.back().b, st);
 }
 
-// threads per workgroup of the any-length kernels, measured per frame length (a workgroup's spectra fill half a
-// CU's LDS from N = 2048 on, so more waves per workgroup are the only way to more waves per CU): analysis
-// 256 / 1024 / 1024, synthesis 256 / 512 / 1024 threads for N <= 1024 / 2048 / 4096+
-int gen_threads(const mca_hip_ctx *c, bool synthesis)
-{
-    if (c->N >= 4096) return 1024;
-    if (c->N >= 2048) return synthesis ? 512 : 1024;
-    return 256;
-}
-
-// which contraction kernel a chunk of `rows` frames runs on, and over how many workgroups its K range is split
-struct GemmPlan { bool v2; int ksplit; bool fold; };      // fold: k_srp_gemm_f16_fold (256-row tiles, two K segments, one plane, a folding context)
-GemmPlan plan_gemm(const mca_hip_ctx *c, const RowLayout &lay, long long rows)
-{
-    GemmPlan g;
-    // (rows: StreamCall::planned -- a call that is worked off in pieces, the chunks of the host-pointer path, plans every piece as the
-    // whole call would be planned: a row's result then does not depend on how the call was cut, same kernel, same K segments, same order)
-    // 256 x 384 tiles from 16 384 rows with one operand plane (128 workgroups of k_srp_gemm_f16_v3 beat the 128 x 192 kernel
-    // there: 134 vs 156 us, and leave the scan's chunk results), from 32 768 rows with the hi + lo planes (343 vs 299 us at 16 384)
-    // (round 6: a contraction twice as deep -- 2048-sample frames, 16 microphones: 14 350 / 15 390 elements per plane -- gives a 256 x 384
-    // workgroup of a K QUARTER the work a K half has at 7 182: two planes take the big tiles from 16 384 rows there, profiles/r06_n2048.log)
-    const long long deep = lay.kp >= 12288 ? 2 : 1;
-    g.v2 = c->prec != MCA_HIP_SRP_FP32 && c->Dp == 384 && rows * (lay.planes == 2 ? deep : 1) >= 16384LL * (lay.planes == 2 ? 2 : 1);
-    if (g.v2) {
-        // 256 x 384 tiles need >= ~256 workgroups to fill the chip: one K range from 65 536 rows, two halves from 32 768, and below that four
-        // quarters where the contraction is deep (round 5: 16 microphones, 15 392 terms per row -- 16 384 rows were 128 workgroups on half
-        // the CUs: 0.280 -> 0.183 ms + 0.021 for k_sum_planes, which folds the four partial maps before the scan; with the 3 968 merged terms
-        // of 8 microphones the fold costs what the quarters save: 75 -> 54 + 22 us, profiles/r05_gemm_ksplit4.log)
-        g.ksplit = rows >= 65536 ? 1 : (rows >= 32768 || lay.kp < 6144 ? 2 : 4);      // (6144: the merged rows of 2048-sample frames, 7 936 deep, take quarters)
-    } else {
-        // 128 x 192 tiles: small batches (a single stream) would leave most CUs idle and walk the whole K range
-        // in a handful of workgroups (0.29 ms however few frames); split K until ~512 workgroups exist, keeping
-        // at least 8 K steps per workgroup
-        const long long wgs = (rows + 127) / 128 * (c->Dp == 64 ? 1 : c->Dp / 192);
-        const int nk = lay.kp / (c->prec == MCA_HIP_SRP_FP32 ? 16 : 32);
-        long long ks = 512 / (wgs > 0 ? wgs : 1);
-        if (ks > nk / 8) ks = nk / 8;
-        if (ks > 16) ks = 16;
-        if (ks < 1) ks = 1;
-        g.ksplit = (int)ks;
-    }
-    g.fold = g.v2 && g.ksplit == 2 && lay.planes == 1 && c->merged && c->fold;
-    return g;
-}
-
 // the A buffer of rows of this layout: an ADAPTIVE context keeps its two-plane rows (repair pass, FP16X3 calls) apart from the
 // one-plane rows of the coarse pass, so that a buffer only ever sees one row layout (its Kp padding columns stay zero)
 DevBuf<unsigned char> &a_buf(mca_hip_ctx *c, const RowLayout &lay) { return (c->prec == MCA_HIP_SRP_ADAPTIVE && lay.planes == 2) ? c->ws.d_Ax : c->ws.d_A; }
@@ -548,7 +485,7 @@ int ensure_workspace(mca_hip_ctx *c, const RowLayout &lay, long long rows_chunk,
 {
     int rc_a = ensure_a(c, lay, rows_chunk);
     if (rc_a) return rc_a;
-    const int planes = std::max(2, plan_gemm(c, lay, rows_plan).ksplit);
+    const int planes = std::max(2, plan_gemm(*c, lay.planes, rows_plan).ksplit);
     return grow_ws(c, c->ws.d_C, (size_t)rows_total * c->Dp * planes, "the correlation map");   // room for the partial maps of a split-K contraction
 }
 
@@ -599,7 +536,7 @@ bool adaptive_applies(const mca_hip_ctx *c, const StreamCall &call, int n_arrays
 // depends on are then simply the 16 before it), the wave-per-run analysis (4 / 8 microphones at 1024 samples: it keeps the PCM and reads it back)
 bool lazy_context(const mca_hip_ctx *c)
 {
-    return c->prec == MCA_HIP_SRP_ADAPTIVE && c->kn.lazy_tails && !c->cfg.use_power_floor && (c->M == 8 || c->M == 4) && !c->generic && !c->n512 &&
+    return c->prec == MCA_HIP_SRP_ADAPTIVE && c->lazy_tails && !c->cfg.use_power_floor && (c->M == 8 || c->M == 4) && !c->generic && !c->n512 &&
            c->cfg.gcc_weighting == MCA_HIP_GCC_PHAT && c->stream_ok;
 }
 
@@ -611,11 +548,10 @@ bool lazy_context(const mca_hip_ctx *c)
 // MCA_HIP_ADAPT_CAND=1 / 0 overrides the policy (always where the shape allows / never).  16 microphones keep whole rows for every flagged
 // frame: a second work list that sent the frames not bound to whole rows to candidate columns measured slower
 // (profiles/r06_m16_two_lists_negative.log; the code is tools/probes/r06_m16_two_work_lists_negative.patch).
-static bool wave16_applies(const mca_hip_ctx *c);
 static bool cand_call(const mca_hip_ctx *c, bool lazy)
 {
-    if (c->kn.cand == 0 || !lazy || wave16_applies(c) || c->S != 1 || c->Dp / 32 > CAND_WORDS_MAX) return false;
-    if (c->kn.cand == 1) return true;                                 // MCA_HIP_ADAPT_CAND=1: whatever the content (tests, sweeps, pinned contexts that want it)
+    if (c->cand == 0 || !lazy || wave16_applies(*c) || c->S != 1 || c->Dp / 32 > CAND_WORDS_MAX) return false;
+    if (c->cand == 1) return true;                                 // MCA_HIP_ADAPT_CAND=1: whatever the content (tests, sweeps, pinned contexts that want it)
     return c->kn.fb_enabled && c->h_probe && c->fb_state == 0 && !c->cand_heavy;
 }
 
@@ -739,207 +675,35 @@ static float exact_reciprocal(float d)
     return best;
 }
 
-// the coarse (one fp16 plane) analysis of a 16-microphone uniform linear array runs on k_stft_phat_wave16
-static bool wave16_applies(const mca_hip_ctx *c)
-{
-    return c->M == 16 && c->ula && !c->generic && c->cfg.gcc_weighting != MCA_HIP_GCC_NONE;
-}
-
-// 512-sample frames, up to 8 microphones: two frames of up to 8 channels per pass on the wave-level transform (k_stft_phat_512).
-// grid.x = 0: one run of frames per workgroup, sized here; list mode (a.list): grid as given, REPAIR_GROUP frames per unit.
-template <typename OutT>
-int launch_stft_512(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, hipStream_t st)
-{
-    StftPhatArgs sa = a;
-    if (!sa.list) {
-        sa.fpb = 8;
-        while (sa.fpb > 2 && (long long)grid.y * ((sa.n_frames + sa.fpb - 1) / sa.fpb) < 512) sa.fpb >>= 1;
-        grid.x = (sa.n_frames + sa.fpb - 1) / sa.fpb;
-    }
-    const size_t smem5 = ((size_t)2 * 8 * 258 + 8 * FFT_SCRATCH + TW_WIN + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
-#define L512(MT, U)                                                                                                       \
-    do {                                                                                                                  \
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_512<MT, U, OutT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem5)); \
-        hipLaunchKernelGGL((k_stft_phat_512<MT, U, OutT>), grid, dim3(512), smem5, st, sa);                               \
-    } while (0)
-    if (c->M == 8 && c->ula) L512(8, true); else if (c->M == 8) L512(8, false);
-    else if (c->M == 4 && c->ula) L512(4, true); else if (c->M == 4) L512(4, false);
-    else if (c->ula) L512(0, true); else L512(0, false);
-#undef L512
-    HIP_TRY(c, hipGetLastError());
-    return MCA_HIP_OK;
-}
-
-// 2048-sample frames, 3 .. 8 microphones: a wave per channel on the 1024-point complex transform + split, spectra in LDS, thread = two bins
-// (k_stft_phat_2048).  grid.x = 0: one run of frames per workgroup, sized here; list mode (a.list): grid as given, REPAIR_GROUP frames per unit.
-static bool n2048_analysis(const mca_hip_ctx *c) { return c->n2048 && c->M > 2 && c->M <= 8; }
-template <typename OutT>
-int launch_stft_2048(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, hipStream_t st)
-{
-    StftPhatArgs sa = a;
-    const int fp = c->M == 4 ? 2 : 1, mr = c->M == 4 ? 4 : 8;
-    if (!sa.list) {
-        sa.fpb = 16;
-        while (sa.fpb > 2 && (long long)grid.y * ((sa.n_frames + sa.fpb - 1) / sa.fpb) < 512) sa.fpb >>= 1;
-        grid.x = (sa.n_frames + sa.fpb - 1) / sa.fpb;
-    }
-    const size_t smem6 = ((size_t)fp * mr * 1026 + F1K_TWORDS + 8 * F1K_SCRATCH + (size_t)sa.fpb * c->M) * sizeof(float2) + (size_t)sa.fpb * 8 * sizeof(float);
-#define L2048(MT, U)                                                                                                      \
-    do {                                                                                                                  \
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_2048<MT, U, OutT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem6)); \
-        hipLaunchKernelGGL((k_stft_phat_2048<MT, U, OutT, false>), grid, dim3(512), smem6, st, sa);                              \
-    } while (0)
-    bool done = false;
-    if constexpr (sizeof(OutT) == 2) {
-        if (sa.mrank && sa.a_planes == 1 && !sa.list && c->ula && (c->M == 8 || c->M == 4)) {      // merged contraction index: ULA, one plane
-            if (c->M == 8) {
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_2048<8, true, _Float16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem6));
-                hipLaunchKernelGGL((k_stft_phat_2048<8, true, _Float16, true>), grid, dim3(512), smem6, st, sa);
-            } else {
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_2048<4, true, _Float16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem6));
-                hipLaunchKernelGGL((k_stft_phat_2048<4, true, _Float16, true>), grid, dim3(512), smem6, st, sa);
-            }
-            done = true;
-        }
-    }
-    if (done) { }
-    else if (c->M == 8 && c->ula) L2048(8, true); else if (c->M == 8) L2048(8, false);
-    else if (c->M == 4 && c->ula) L2048(4, true); else if (c->M == 4) L2048(4, false);
-    else if (c->ula) L2048(0, true); else L2048(0, false);
-#undef L2048
-    HIP_TRY(c, hipGetLastError());
-    return MCA_HIP_OK;
-}
-
 // the fields of StftPhatArgs that are the context's, the same for every launch
 void stft_common(const mca_hip_ctx *c, StftPhatArgs &sa)
 {
     sa.M = c->M; sa.window = c->d_window; sa.Kp = c->Kp;
     sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
 }
-// dynamic LDS of launch_stft's fallback kernels (k_stft_phat, fpb frames per workgroup)
-size_t stft_fallback_lds(const mca_hip_ctx *c, int fpb) { return ((size_t)c->M * FFT_SCRATCH + TW_WORDS + (size_t)fpb * c->M) * sizeof(float2) + (size_t)fpb * 8 * sizeof(float); }
-// *steered (if given) is set when the launch is the one that also steers every frame ahead of the picks (a.bf, steer.h)
-template <typename OutT>
-int launch_stft(mca_hip_ctx *c, const StftPhatArgs &a, dim3 grid, size_t smem, hipStream_t st, bool *steered = nullptr)
+// The one launcher of the stream path: a plan's kernel (the lookups of kernels.h; nullptr: a form the build lacks -- plan and predicate disagree, which
+// tests/test_stream_plan.py rules out), grid, block, dynamic LDS and the kernel's one argument struct.  The attribute is set exactly above the 64 KiB every kernel may have.
+int launch(mca_hip_ctx *c, const void *kernel, dim3 grid, dim3 block, size_t lds, void *args, hipStream_t st, const char *form)
 {
-    const int M = c->M; const bool ula = c->ula;
-    if (n2048_analysis(c)) return launch_stft_2048<OutT>(c, a, grid, st);      // (the list-mode launches of the repair pass come through here)
-    if (c->n512) return launch_stft_512<OutT>(c, a, grid, st);
-    // a 16-microphone uniform linear array, one fp16 operand plane (the ADAPTIVE coarse pass, plain FP16): the wave-per-run kernel
-    // with its whitened spectra packed to fp16 (k_stft_phat_wave16); the exact rows of such an array stay on k_stft_phat<16>
-    if constexpr (sizeof(OutT) == 2) {
-        if (wave16_applies(c) && a.a_planes == 1 && !a.list) {
-            StftPhatArgs w = a;
-            w.fpb = 16;
-            while (w.fpb > 1 && (long long)grid.y * ((a.n_frames + w.fpb - 1) / w.fpb) < 2048) w.fpb >>= 1;
-            dim3 gw(((a.n_frames + w.fpb - 1) / w.fpb + 3) / 4, grid.y);
-            // (one resident round of two workgroups per CU: the older workgroup's waves take more frames, StftPhatArgs::skew)
-            if ((gw.x & 1) == 0 && (long long)gw.x * gw.y == 2LL * c->n_cu && (long long)gw.x * 4 * w.fpb == a.n_frames) {
-                const int sk = (3 * w.fpb + 8) / 16;
-                if (sk > 0 && sk < w.fpb) { w.skew = sk; gw = dim3(gw.y, gw.x); }
-            }
-            const int fpa = w.fpb + w.skew;
-            const size_t smw = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH + 2 * 4 * fpa * 8) * sizeof(float2) + (1024 + 4 * fpa) * sizeof(float);   // (+ the scales and DC marks of unsure frames)
-            if (a.power) {
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_wave16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw));
-                hipLaunchKernelGGL(k_stft_phat_wave16<true>, gw, dim3(256), smw, st, w);
-            } else {
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_wave16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw));
-                hipLaunchKernelGGL(k_stft_phat_wave16<false>, gw, dim3(256), smw, st, w);
-            }
-            HIP_TRY(c, hipGetLastError());
-            return MCA_HIP_OK;
-        }
-    }
-    // 4 or 8 microphones: one wave per run of frames on the 1024-point transform of channel pairs (k_stft_phat_wave)
-    if (M == 8 || M == 4) {
-        StftPhatArgs w = a;
-        dim3 gw;
-        if (a.list) { w.fpb = 1; gw = dim3(grid.x, 1); }      // a listed group of REPAIR_GROUP = 4 frames per workgroup, a frame per wave
-        else {
-            w.fpb = 16;       // frames per wave: two waves per SIMD want 2048 runs
-            while (w.fpb > 1 && (long long)grid.y * ((a.n_frames + w.fpb - 1) / w.fpb) < 2048) w.fpb >>= 1;
-            gw = dim3(((a.n_frames + w.fpb - 1) / w.fpb + 3) / 4, grid.y);
-        }
-        // One resident round of two workgroups per CU (the bench shapes: 8 x 4096 and 128 x 256 frames of 8 microphones): the CU issues
-        // oldest-first, so the FIRST workgroup of every CU is done early (180 against 244 us on the bench shape, profiles/
-        // r05_run_queue_negative.log) and the other then runs alone at 83 % of the two-wave rate.  The first half of every array's run
-        // groups -- dispatched first -- takes more frames per wave (StftPhatArgs::skew).  (A device-side run queue, an XCD-aware mapping
-        // and one 8-wave workgroup per CU were measured slower, HISTORY.md section 10.)
-        if (!a.list && M == 8 && (gw.x & 1) == 0 && (long long)gw.x * gw.y == 2LL * c->n_cu && (long long)gw.x * 4 * w.fpb == a.n_frames) {
-            const int sk = (3 * w.fpb + 8) / 16;      // 16 frames per wave: 19 / 13 (measured 1 ... 4: 3 is best)
-            if (sk > 0 && sk < w.fpb) {
-                w.skew = sk;
-                gw = dim3(gw.y, gw.x);             // (arrays, run groups): the first half of the run groups of EVERY array is dispatched first
-            }
-        }
-        const bool mg = w.mrank != nullptr && !a.list;
-        const int nrank = 2 * (M - 1) * 64 * 4 + 8, regw = mg ? std::max(F1K_SCRATCH, (w.n_merged + 63) & ~63) : F1K_SCRATCH;
-        // (the merged kernel keeps its Nyquist bins in registers: with its 15.5 KiB regions two workgroups just fit the 160 KiB of a CU)
-        const bool fuse = mg && M == 8 && w.bf.rows != nullptr && a.power == nullptr && regw >= F1K_SCRATCH + STEER_LDS_ROWS * 64;      // steering ahead of the picks (steer.h): + the waves' steps Q
-        const size_t smw = (size_t)(F1K_TWORDS + (mg ? nrank / 4 : 0) + 4 * regw + (mg ? 0 : 4 * (w.fpb + w.skew) * (M / 2)) + (fuse ? 4 * STEER_QWORDS : 0)) * sizeof(float2);
-        const bool pl2 = a.a_planes == 2, pw = a.power != nullptr;
-#define LAUNCH_K(K)                                                                                                 \
-        do {                                                                                                         \
-            if (smw > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw)); \
-            hipLaunchKernelGGL(K, gw, dim3(256), smw, st, w);                                                        \
-        } while (0)
-#define LAUNCH_W2(MT, U, PL2, NP)                                                                                  \
-        do {                                                                                                         \
-            if (pw) LAUNCH_K((k_stft_phat_wave<MT, U, OutT, PL2, true, NP, false>));                                 \
-            else LAUNCH_K((k_stft_phat_wave<MT, U, OutT, PL2, false, NP, false>));                                   \
-        } while (0)
-#define LAUNCH_W(MT, U)                                                                                              \
-        do {                                                                                                         \
-            if constexpr (sizeof(OutT) == 2) {                                                                       \
-                if (pl2 && w.cand_on && a.list && !pw) LAUNCH_K((k_stft_phat_wave<MT, U, OutT, true, false, false, false, true>)); \
-                else if (pl2) LAUNCH_W2(MT, U, true, false); else LAUNCH_W2(MT, U, false, false);                    \
-            }                                                                                                        \
-            else { if (a.no_phat) LAUNCH_W2(MT, U, false, true); else LAUNCH_W2(MT, U, false, false); }              \
-        } while (0)
-        if constexpr (sizeof(OutT) == 2) {
-            if (mg) {          // merged contraction index: ULA, one plane
-                if (fuse) { LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true, false, true>)); if (steered) *steered = true; }      // steering ahead of the picks (steer.h)
-                else if (M == 8) { if (pw) LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<8, true, OutT, false, false, false, true>)); }
-                else { if (pw) LAUNCH_K((k_stft_phat_wave<4, true, OutT, false, true, false, true>)); else LAUNCH_K((k_stft_phat_wave<4, true, OutT, false, false, false, true>)); }
-                HIP_TRY(c, hipGetLastError());
-                return MCA_HIP_OK;
-            }
-        }
-        if (M == 8 && ula) LAUNCH_W(8, true); else if (M == 8) LAUNCH_W(8, false);
-        else if (ula) LAUNCH_W(4, true); else LAUNCH_W(4, false);
-#undef LAUNCH_W2
-#undef LAUNCH_K
-#undef LAUNCH_W
-        HIP_TRY(c, hipGetLastError());
-        return MCA_HIP_OK;
-    }
-#define LAUNCH(MT, U)                                                                                        \
-    do {                                                                                                     \
-        if (smem > 64 * 1024)                                                                                \
-            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat<MT, U, OutT>),        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));          \
-        hipLaunchKernelGGL((k_stft_phat<MT, U, OutT>), grid, dim3(512), smem, st, a);                        \
-    } while (0)
-    // 2 microphones: four frames per pass so that all eight waves transform (k_stft_phat_few)
-#define LAUNCH_FEW(MT, U)                                                                                    \
-    do {                                                                                                     \
-        const size_t smf = ((size_t)8 * FFT_SCRATCH + TW_WORDS + (size_t)a.fpb * MT) * sizeof(float2) + (size_t)a.fpb * 8 * sizeof(float); \
-        if (smf > 64 * 1024)                                                                                 \
-            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_few<MT, U, OutT>),    \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smf));           \
-        hipLaunchKernelGGL((k_stft_phat_few<MT, U, OutT>), grid, dim3(512), smf, st, a);                     \
-    } while (0)
-    // (measured: 0.51 -> 0.33 ms for 131 072 two-channel frames)
-    if (M == 2 && !ula) LAUNCH_FEW(2, false);
-    else if (M == 16 && ula) LAUNCH(16, true);
-    else if (ula) LAUNCH(0, true);
-    else LAUNCH(0, false);
-#undef LAUNCH
-#undef LAUNCH_FEW
+    if (!kernel) return fail(c, MCA_HIP_ERR_UNSUPPORTED, std::string("the build has no kernel of the form ") + form);
+    if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void *argv[1] = {args};
+    HIP_TRY(c, hipLaunchKernel(kernel, grid, block, argv, lds, st));
     HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
+}
+
+// one analysis launch: the plan's fields into the arguments, the kernel of the plan's form (named in the launcher's message) on the plan's grid
+int launch_analysis(mca_hip_ctx *c, StftPhatArgs &sa, const AnalysisPlan &p, hipStream_t st)
+{
+    static const void *(*const lookup[])(const StftForm &) = {stft_wave_kernel, stft_wave16_kernel, stft_512_kernel, stft_2048_kernel, stft_sub2_kernel, stft_gen_kernel,
+                                                              stft_block_kernel, stft_few_kernel};      // (in the order of StftFamily)
+    const StftForm &f = p.form;
+    char name[160];
+    std::snprintf(name, sizeof name, "analysis family %d: MT %d, ULA %d, fp32 %d, PL2 %d, POWER %d, NOPHAT %d, MERGE %d, CAND %d, FUSE %d", (int)f.family, f.mt, f.ula, f.f32, f.pl2,
+                  f.power, f.nophat, f.merge, f.cand, f.fuse);
+    sa.fpb = p.fpb; sa.skew = p.skew;
+    return launch(c, lookup[(int)f.family](f), p.grid, p.block, p.lds, &sa, st, name);
 }
 
 int check_stream_args(mca_hip_ctx *c, const float *pcm, long long array_stride, long long mic_stride, int n_arrays, int n_frames)
@@ -971,7 +735,8 @@ const char *mca_hip_last_error(const mca_hip_ctx *ctx) { return ctx ? ctx->err.c
 static int init_ctx(mca_hip_ctx *c, const mca_hip_config *cfg, const hipDeviceProp_t &prop)
 {
     c->cfg = *cfg;
-    c->kn = read_knobs(*cfg);
+    c->kn = read_knobs(*cfg, *c);
+    c->gate = cfg->use_power_floor != 0; c->no_phat = cfg->gcc_weighting == MCA_HIP_GCC_NONE;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     c->M = cfg->n_mics; c->S = cfg->n_sources; c->N = cfg->fft_size; c->K = c->N / 2 + 1; c->prec = cfg->srp_precision;
     c->xyz.assign(cfg->mic_xyz, cfg->mic_xyz + 3 * c->M);
@@ -1386,7 +1151,7 @@ static int run_correlation_map(mca_hip_ctx *c, StreamCall &call, const RowLayout
 {
     int rc;
     const long long fc = chunk_frames_for(c, lay, n_arrays, n_frames);
-    auto plan = [&](long long rows) { return plan_gemm(c, lay, call.planned(rows)); };
+    auto plan = [&](long long rows) { return plan_gemm(*c, lay.planes, call.planned(rows)); };
     if ((rc = ensure_workspace(c, lay, (long long)n_arrays * fc, call.planned((long long)n_arrays * fc), (long long)n_arrays * n_frames))) return rc;
     if ((rc = ensure_scan_workspace(c, n_arrays, n_frames, (n_frames + SCAN_CHUNK - 1) / SCAN_CHUNK))) return rc;
     // The 256 x 384 contraction leaves the chunk-local results of the scan over frames (k_scan_partial's job) when every
@@ -1404,58 +1169,22 @@ static int run_correlation_map(mca_hip_ctx *c, StreamCall &call, const RowLayout
         sa.pcm = pcm; sa.array_stride = array_stride; sa.mic_stride = mic_stride;
         stft_common(c, sa);
         sa.n_frames = nf; sa.frame0 = f0;
-        // frames per workgroup: 16 amortise the table set-up and the half frame two neighbouring workgroups both read (17 half
-        // frames of input per 16 frames; measured 4 / 8 / 16 / 32: 0.312 / 0.292 / 0.286 / 0.288 ms); small batches take fewer
-        // so that a few hundred workgroups exist
-        sa.fpb = 16;
-        while (sa.fpb > 1 && (long long)n_arrays * ((nf + sa.fpb - 1) / sa.fpb) < 256) sa.fpb >>= 1;
         sa.power = c->cfg.use_power_floor ? c->ws.d_power : nullptr; sa.total_frames = n_frames;
         sa.A = a_buf(c, lay); sa.a_row_elems = lay.row_elems; sa.a_planes = lay.planes;
         if (c->merged && lay.planes == 1) { sa.mrank = c->d_mrank; sa.n_merged = c->n_merged; sa.planar = c->fold ? 1 : 0; }
         sa.no_phat = c->cfg.gcc_weighting == MCA_HIP_GCC_NONE ? 1 : 0;
-        if (c->prec == MCA_HIP_SRP_ADAPTIVE && lay.planes == 1 && wave16_applies(c)) sa.unsure = c->ws.d_unsure;   // (adaptive coarse pass)
+        if (c->prec == MCA_HIP_SRP_ADAPTIVE && lay.planes == 1 && wave16_applies(*c)) sa.unsure = c->ws.d_unsure;   // (adaptive coarse pass)
         if (call.lazy && cand_call(c, true)) sa.dead = c->ws.d_unsure;                                                 // (... of a candidate-column call: frames of exact zeros)
         if (call.lazy) sa.hist_out = c->d_hist_pcm[c->hist_cur ^ 1];         // lazy tails: the call's last frames of PCM stay behind
         if (call.steer && sa.mrank && !sa.power) {                            // the merged 8-microphone kernel also steers every frame at the array's predicted bin
             sa.bf.rows = c->d_steer_rows; sa.bf.q = c->d_steer_q; sa.bf.nyq = c->d_steer_nyq; sa.bf.pred = c->d_steer_pred + call.a0; sa.bf.Y = c->d_steer_Y;
         }
+        AnalysisFlags fl;
+        fl.power = sa.power != nullptr; fl.merged = sa.mrank != nullptr; fl.steer = sa.bf.rows != nullptr; fl.no_phat = sa.no_phat != 0;
+        const AnalysisPlan ap = plan_analysis(*c, c->prec == MCA_HIP_SRP_FP32, lay.planes, n_arrays, nf, 0, 0, fl);
         time_begin(c, call, MCA_HIP_K_STFT_PHAT, st);
-        if (c->n512) {
-            rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft_512<float>(c, sa, dim3(0, n_arrays), st) : launch_stft_512<_Float16>(c, sa, dim3(0, n_arrays), st);
-        } else if ((c->N == 4096 || c->N == 2048) && c->M == 2 && c->stream_ok) {
-            // two microphones at 2048- / 4096-sample frames (FreqGCC at 32 / 44.1 / 48 kHz): 512-sample sub-sequences per channel
-            sa.fpb = 8;
-            while (sa.fpb > 2 && (long long)n_arrays * ((nf + sa.fpb - 1) / sa.fpb) < 512) sa.fpb >>= 1;
-            const size_t smem4 = ((size_t)16 * 258 + 8 * FFT_SCRATCH + TW_WIN) * sizeof(float2) + 4 * 8 * sizeof(float);
-            dim3 g4((nf + sa.fpb - 1) / sa.fpb, n_arrays);
-#define LSUB(RR, T)                                                                                                       \
-            do {                                                                                                          \
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_stft_phat_sub2<RR, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)); \
-                hipLaunchKernelGGL((k_stft_phat_sub2<RR, T>), g4, dim3(512), smem4, st, sa);                              \
-            } while (0)
-            if (c->N == 4096) { if (c->prec == MCA_HIP_SRP_FP32) LSUB(8, float); else LSUB(8, _Float16); }
-            else { if (c->prec == MCA_HIP_SRP_FP32) LSUB(4, float); else LSUB(4, _Float16); }
-#undef LSUB
-            rc = MCA_HIP_OK;
-        } else if (n2048_analysis(c)) {
-            rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft_2048<float>(c, sa, dim3(0, n_arrays), st) : launch_stft_2048<_Float16>(c, sa, dim3(0, n_arrays), st);
-        } else if (c->generic) {
-            const size_t smem1 = (size_t)c->M * (c->H + 1) * sizeof(float2) + 16;
-#define GEN_LAUNCH(K)                                                                                                     \
-            do {                                                                                                          \
-                if (smem1 > 64 * 1024)                                                                                    \
-                    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1)); \
-                hipLaunchKernelGGL(K, dim3(nf, n_arrays), dim3(gen_threads(c, false)), smem1, st, sa);                                      \
-            } while (0)
-            if (c->prec == MCA_HIP_SRP_FP32) GEN_LAUNCH(k_stft_phat_gen<float>);
-            else GEN_LAUNCH(k_stft_phat_gen<_Float16>);
-#undef GEN_LAUNCH
-            rc = MCA_HIP_OK;
-        } else {
-            dim3 g1((nf + sa.fpb - 1) / sa.fpb, n_arrays);
-            const size_t smem1 = stft_fallback_lds(c, sa.fpb);
-            rc = c->prec == MCA_HIP_SRP_FP32 ? launch_stft<float>(c, sa, g1, smem1, st) : launch_stft<_Float16>(c, sa, g1, smem1, st, &call.steer_fused);
-        }
+        rc = launch_analysis(c, sa, ap, st);
+        if (ap.steers) call.steer_fused = true;
         time_end(c, st);
         if (rc) return rc;
 
@@ -1472,40 +1201,15 @@ static int run_correlation_map(mca_hip_ctx *c, StreamCall &call, const RowLayout
             ga.scan_w[31] = 1 - 0.8f;                                              // as pa.one_minus_mu / pa.mu below
             for (int t = 30; t >= 0; --t) ga.scan_w[t] = ga.scan_w[t + 1] * 0.8f;
         }
-        // one split factor per call (the scan sums the same number of partial maps for every frame): the one that
-        // suits the full-size chunks; a shorter last chunk may still fall back to the 128 x 192 kernel
-        const bool v2 = plan(ga.rows).v2;
-        const int ksplit = plan((long long)n_arrays * fc).ksplit;
-        map.c_planes = ksplit; map.c_plane = ga.c_plane_elems;
+        const ContractionPlan gp = plan_contraction(*c, lay.planes, ga.rows, call.planned(ga.rows), call.planned((long long)n_arrays * fc));
+        map.c_planes = gp.ksplit; map.c_plane = ga.c_plane_elems;
+        const void *const one[] = {reinterpret_cast<const void *>(&k_srp_gemm_f32), nullptr, reinterpret_cast<const void *>(&k_srp_gemm_f16_v2),
+                                   reinterpret_cast<const void *>(&k_srp_gemm_f16_v3), reinterpret_cast<const void *>(&k_srp_gemm_f16_fold)};      // (in the order of GemmFamily)
+        const void *gk = gp.form.family == GemmFamily::F16 ? srp_gemm_f16_kernel(gp.form.split, gp.form.bn) : one[(int)gp.form.family];
         time_begin(c, call, MCA_HIP_K_SRP_GEMM, st);
-        if (v2) {
-            const int np = lay.planes;
-            const size_t smem = (size_t)(np == 2 ? 2 : 4) * np * (256 + 384) * 64;   // 32-deep stages: two with hi + lo planes, four with one plane (all 160 KiB)
-            dim3 gv((ga.rows + 255) / 256, ksplit);
-#define V2_LAUNCH(K)                                                                                                      \
-            do {                                                                                                          \
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-                hipLaunchKernelGGL(K, gv, dim3(512), smem, st, ga);                                                       \
-            } while (0)
-            // (the slices of a call all have the call's split factor, so a 256-row slice of a folding two-segment call folds like the others)
-            if (lay.planes == 2) V2_LAUNCH(k_srp_gemm_f16_v2);
-            else if (ksplit == 2 && mg && c->fold) {
-                const size_t smem_f = (size_t)FOLD_NS * (256 + 192) * 64;
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_srp_gemm_f16_fold), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_f));
-                hipLaunchKernelGGL(k_srp_gemm_f16_fold, gv, dim3(512), smem_f, st, ga);
-            }
-            else V2_LAUNCH(k_srp_gemm_f16_v3);
-#undef V2_LAUNCH
-        } else {
-            dim3 g2((ga.rows + 127) / 128, c->Dp == 64 ? 1 : c->Dp / 192, ksplit);
-            if (c->prec == MCA_HIP_SRP_FP32) hipLaunchKernelGGL(k_srp_gemm_f32, g2, dim3(256), 0, st, ga);
-            else if (c->Dp == 64 && lay.planes == 2) hipLaunchKernelGGL((k_srp_gemm_f16<true, 64>), g2, dim3(256), 0, st, ga);
-            else if (c->Dp == 64) hipLaunchKernelGGL((k_srp_gemm_f16<false, 64>), g2, dim3(256), 0, st, ga);
-            else if (lay.planes == 2) hipLaunchKernelGGL((k_srp_gemm_f16<true, 192>), g2, dim3(256), 0, st, ga);
-            else hipLaunchKernelGGL((k_srp_gemm_f16<false, 192>), g2, dim3(256), 0, st, ga);
-        }
+        rc = launch(c, gk, gp.grid, gp.block, gp.lds, &ga, st, "k_srp_gemm_f16");
         time_end(c, st);
-        HIP_TRY(c, hipGetLastError());
+        if (rc) return rc;
     }
     if (map.c_planes > 2) {      // deep split-K of a small batch: fold the partial maps once, the scans read one map
         const long long n4 = map.c_plane / 4;       // Dp is a multiple of 64
@@ -1526,7 +1230,7 @@ constexpr float ENERGY_MU = 0.8f, ENERGY_ONE_MINUS_MU = 1 - 0.8f;
 // REPAIR_GROUP) in w.d_Ax -> three-product contraction in K segments (w.d_Cx) -> summed into the map by k_repair_patch (pp: where the
 // rows go; list0, pass_rows, col_tiles, ksplit and items are filled in here).  Shared by localise_impl and settle_history.
 // x2: the two-plane layout of the exact rows; ksplit_arrays: the arrays the K split is planned for (repair_ksplit_for)
-static void launch_repair_contraction(mca_hip_ctx *c, Workspace &w, const RowLayout &x2, long long list0, long long pass_rows, int ksplit_arrays, RepairPatchArgs pp, hipStream_t st)
+static int launch_repair_contraction(mca_hip_ctx *c, Workspace &w, const RowLayout &x2, long long list0, long long pass_rows, int ksplit_arrays, RepairPatchArgs pp, hipStream_t st)
 {
     GemmArgs ga{};
     ga.A = w.d_Ax; ga.B = c->d_B; ga.C = w.d_Cx; ga.Bt = c->d_Bt;
@@ -1534,14 +1238,12 @@ static void launch_repair_contraction(mca_hip_ctx *c, Workspace &w, const RowLay
     ga.Kp = c->Kp; ga.Dp = c->Dp; ga.a_row_elems = x2.row_elems; ga.c_plane_elems = pass_rows * c->Dp;
     ga.n_list = w.d_nlist; ga.list0 = (int)list0;
     ga.repair_ksplit = repair_ksplit_for(c, ksplit_arrays); ga.repair_items = REPAIR_ITEMS;
-    const int col_tiles = c->Dp == 64 ? 1 : c->Dp / 192;
-    const long long max_work = (pass_rows + 127) / 128 * col_tiles * ga.repair_ksplit;
-    dim3 gg((unsigned)std::min<long long>(max_work, 768));
-    if (c->Dp == 64) hipLaunchKernelGGL((k_srp_gemm_repair<64>), gg, dim3(256), 0, st, ga);
-    else hipLaunchKernelGGL((k_srp_gemm_repair<192>), gg, dim3(256), 0, st, ga);
-    pp.Cx = w.d_Cx; pp.pass_rows = (int)pass_rows; pp.col_tiles = col_tiles; pp.ksplit = ga.repair_ksplit; pp.items = ga.repair_items;
+    const RepairContractionPlan rp = plan_repair_contraction(*c, pass_rows, ga.repair_ksplit);
+    int rc;
+    if ((rc = launch(c, srp_gemm_repair_kernel(rp.bn), rp.grid, rp.block, 0, &ga, st, "k_srp_gemm_repair"))) return rc;
+    pp.Cx = w.d_Cx; pp.pass_rows = (int)pass_rows; pp.col_tiles = rp.col_tiles; pp.ksplit = ga.repair_ksplit; pp.items = ga.repair_items;
     pp.list = w.d_list; pp.n_list = w.d_nlist; pp.list0 = (int)list0; pp.need = w.d_need; pp.Dp = c->Dp;
-    hipLaunchKernelGGL(k_repair_patch, dim3((unsigned)std::min<long long>(pass_rows, 2048)), dim3(128), 0, st, pp);
+    return launch(c, reinterpret_cast<const void *>(&k_repair_patch), rp.patch_grid, rp.patch_block, 0, &pp, st, "k_repair_patch");
 }
 
 // Lazy tails (mca_internal.h, HIST_FRAMES): the repair of a call's last rows is left to the call that needs them.  Settling the debt --
@@ -1570,17 +1272,17 @@ static int settle_history(mca_hip_ctx *c, hipStream_t st)
         StftPhatArgs sa{};
         sa.pcm = c->d_hist_pcm[cur]; sa.array_stride = (long long)c->M * HIST_SAMPLES; sa.mic_stride = HIST_SAMPLES;
         stft_common(c, sa);
-        sa.n_frames = HIST_FRAMES; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = HIST_FRAMES;
+        sa.n_frames = HIST_FRAMES; sa.frame0 = 0; sa.total_frames = HIST_FRAMES;
         sa.A = w.d_Ax; sa.a_row_elems = x2.row_elems; sa.a_planes = 2;
         sa.list = w.d_list; sa.n_list = w.d_nlist; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = HIST_UNITS;
         sa.hist_in = c->d_hist_pcm[cur]; sa.hist_base = 0;
-        rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, 512), 1), stft_fallback_lds(c, sa.fpb), st);
+        rc = launch_analysis(c, sa, plan_analysis(*c, false, 2, n, HIST_FRAMES, pass_groups, 512, AnalysisFlags{}), st);
         if (rc) break;
         RepairPatchArgs pp{};
         pp.groups_per_array = HIST_UNITS;
         pp.C = w.d_C; pp.c_planes = 1; pp.c_plane_stride = 0; pp.n_frames = HIST_FRAMES;
         pp.hist_C = c->d_hist_C[cur]; pp.hist_base = 0;
-        launch_repair_contraction(c, w, x2, g0, pass_rows, n, pp, st);
+        rc = launch_repair_contraction(c, w, x2, g0, pass_rows, n, pp, st);
     }
     if (!rc) {
         hipLaunchKernelGGL(k_hist_settle, dim3(n), dim3(std::max(round_up(c->D, 64), 64)), 0, st, c->d_ehist[cur], c->d_hist_C[cur], c->d_E[c->e_cur], w.d_nlist, c->D, c->Dp,
@@ -1637,7 +1339,7 @@ static int localise_impl(mca_hip_ctx *c, StreamCall &call, const float *pcm, lon
     if (adaptive) {
         pa.mode = 1; pa.tau = c->tau_en; pa.flags = c->ws.d_flags; pa.groups_per_array = gpa;
         pa.need = c->ws.d_need; pa.list = c->ws.d_list; pa.n_list = c->ws.d_nlist; pa.chunk_from = c->ws.d_chunk_from; pa.last_vchunk = c->ws.d_last_vchunk; pa.stats = c->d_rstats;
-        pa.unsure = wave16_applies(c) ? c->ws.d_unsure : nullptr;
+        pa.unsure = wave16_applies(*c) ? c->ws.d_unsure : nullptr;
         pa.hist_base = n_arrays * gpa;
         if (lazy) { pa.lazy = 1; pa.hist_C_out = c->d_hist_C[c->hist_cur ^ 1]; pa.e_hist_out = c->d_ehist[c->hist_cur ^ 1]; }
         if (hist_valid) { pa.hist_valid = 1; pa.hist_C_in = c->d_hist_C[c->hist_cur]; pa.e_hist_in = c->d_ehist[c->hist_cur]; }
@@ -1646,11 +1348,9 @@ static int localise_impl(mca_hip_ctx *c, StreamCall &call, const float *pcm, lon
         // steered tail: the analysis of this call steered every frame at its array's predicted bin, so the frames that miss it are patched inside
         // the second pick's launch (k_scan_repick<PL, true>) and steer_separate launches no k_steer_patch.  One batch of k_scan_pick per chunk
         // is what makes "no flagged frame in the batch" mean "the chunk's coarse picks are final".
-        // Not the widest peak pick (D > 386: k_scan_pick<8, 1> has no register left for the append), and only while the launch's LDS -- energy
-        // rows, the transform's table, a scratch per wave, the static arrays -- fits a CU: those calls keep the stand-alone k_steer_patch.
-        const size_t tail_lds = (size_t)32 * (c->Dp + 8) * sizeof(float) + (size_t)(F1K_TWORDS + 8 * F1K_SCRATCH) * sizeof(float2) + 2048;
+        // (repick_may_patch: not the widest peak pick, and only while the patching launch's LDS fits a CU -- those calls keep the stand-alone k_steer_patch)
         if (call.steer && call.steer_fused && c->d_steer_mlist && SCAN_SUB == SCAN_CHUNK && c->S == 1 && !gate && (size_t)n_arrays * n_frames < c->d_steer_mlist.n &&
-            c->D - 2 <= 384 && c->D <= 512 && tail_lds <= 160 * 1024) {
+            repick_may_patch(*c)) {
             // the list is empty unless a call that listed misses never reached its synthesis (which empties it): an error in between
             if (c->steer_mlist_dirty) HIP_TRY(c, hipMemsetAsync(c->d_steer_mlist, 0, sizeof(int), st));
             c->steer_mlist_dirty = true;
@@ -1679,17 +1379,8 @@ static int localise_impl(mca_hip_ctx *c, StreamCall &call, const float *pcm, lon
     // (ADVICE r3): NONE always runs the serial carry pass.
     pa.lookback = (!gate && !c->kn.scan_carry && c->cfg.gcc_weighting == MCA_HIP_GCC_PHAT) ? 4 : 0;
     if (!pa.lookback) hipLaunchKernelGGL(k_scan_carry, dim3(n_arrays, nthr / 64), dim3(64), 0, st, pa);   // one wave per 64 delays
-    const size_t smem3 = (size_t)SCAN_SUB * (c->Dp + 8) * sizeof(float);
-    const int ppl = c->D - 2 <= 128 ? 2 : c->D - 2 <= 384 ? 6 : 8;            // positions per lane of the peak pick
-#define LAUNCH_PICK(PL, MODE)                                                                                                       \
-    do {                                                                                                                            \
-        if (smem3 > 64 * 1024)                                                                                                      \
-            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan_pick<PL, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3)); \
-        hipLaunchKernelGGL((k_scan_pick<PL, MODE>), g3, dim3(std::max(nthr, 512)), smem3, st, pa);   /* 8 waves: the per-frame pick is one wave per frame */ \
-    } while (0)
-    if (adaptive) { if (ppl == 2) LAUNCH_PICK(2, 1); else if (ppl == 6) LAUNCH_PICK(6, 1); else LAUNCH_PICK(8, 1); }
-    else { if (ppl == 2) LAUNCH_PICK(2, 0); else if (ppl == 6) LAUNCH_PICK(6, 0); else LAUNCH_PICK(8, 0); }
-#undef LAUNCH_PICK
+    const PickPlan kp = plan_pick(*c, adaptive, n_arrays, pa.n_chunks);
+    if ((rc = launch(c, scan_pick_kernel(kp.form), kp.grid, kp.block, kp.lds, &pa, st, "k_scan_pick"))) return rc;
     DoaFillArgs fa{};
     fa.voiced = c->ws.d_voiced; fa.n_frames = n_frames; fa.S = c->S;
     fa.doa_bin = doa_bin; fa.doa_rad = doa_rad; fa.prob = prob;
@@ -1709,7 +1400,7 @@ static int localise_impl(mca_hip_ctx *c, StreamCall &call, const float *pcm, lon
             StftPhatArgs sa{};
             sa.pcm = pcm; sa.array_stride = array_stride; sa.mic_stride = mic_stride;
             stft_common(c, sa);
-            sa.n_frames = n_frames; sa.frame0 = 0; sa.fpb = REPAIR_GROUP; sa.total_frames = n_frames;
+            sa.n_frames = n_frames; sa.frame0 = 0; sa.total_frames = n_frames;
             sa.A = c->ws.d_Ax; sa.a_row_elems = x2.row_elems; sa.a_planes = 2;
             sa.list = c->ws.d_list; sa.n_list = c->ws.d_nlist; sa.list0 = (int)g0; sa.list_cap = pass_groups; sa.groups_per_array = gpa;
             if (hist_valid) { sa.hist_in = c->d_hist_pcm[c->hist_cur]; sa.hist_base = n_arrays * gpa; }
@@ -1724,28 +1415,18 @@ static int localise_impl(mca_hip_ctx *c, StreamCall &call, const float *pcm, lon
                 if (hist_valid) { ca.hist_C = c->d_hist_C[c->hist_cur]; ca.hist_base = n_arrays * gpa; }
                 sa.cand_on = 1; sa.cand = ca;       // (pa.umask: cand_call, which requires a lazy call, so lazy_context, so M is 4 or 8 -- the list-mode launch contracts)
             }
-            // fixed, moderate grids: the kernels of the repair pass walk their device-side work lists
-            if ((rc = launch_stft<_Float16>(c, sa, dim3(std::min(pass_groups, LIST_GRID), 1), stft_fallback_lds(c, sa.fpb), st))) return rc;
+            AnalysisFlags fl;
+            fl.cand_on = sa.cand_on != 0;
+            if ((rc = launch_analysis(c, sa, plan_analysis(*c, false, 2, n_arrays, n_frames, pass_groups, LIST_GRID, fl), st))) return rc;
             if (sa.cand_on) continue;
             RepairPatchArgs pp{};
             pp.groups_per_array = gpa;
             pp.C = c->ws.d_C; pp.c_planes = map.c_planes; pp.c_plane_stride = map.c_plane; pp.n_frames = n_frames;
             if (hist_valid) { pp.hist_C = c->d_hist_C[c->hist_cur]; pp.hist_base = n_arrays * gpa; }
-            launch_repair_contraction(c, c->ws, x2, g0, pass_rows, call.planned_arrays(n_arrays), pp, st);
+            if ((rc = launch_repair_contraction(c, c->ws, x2, g0, pass_rows, call.planned_arrays(n_arrays), pp, st))) return rc;
         }
-        const int repick_thr = std::max(nthr, 512);
-        const bool tail = pa.n_miss != nullptr;             // the launch also patches the steered rows: the transform's table and a scratch per wave behind the energy rows
-        const size_t smem4 = (size_t)32 * (c->Dp + 8) * sizeof(float) + (tail ? (size_t)(F1K_TWORDS + repick_thr / 64 * F1K_SCRATCH) * sizeof(float2) : 0);
-        const unsigned repick_wgs = (unsigned)std::min<long long>((long long)pa.n_chunks * n_arrays, REPICK_GRID) + (tail ? STEER_TAIL_WGS : 0);
-#define LAUNCH_REPICK(PL, T)                                                                                                        \
-        do {                                                                                                                        \
-            if (smem4 > 64 * 1024)      /* grids finer than 0.45 degrees: Dp >= 512; the patching launch always */                  \
-                HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scan_repick<PL, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)); \
-            hipLaunchKernelGGL((k_scan_repick<PL, T>), dim3(repick_wgs), dim3(repick_thr), smem4, st, pa);                          \
-        } while (0)
-        if (tail) { if (ppl == 2) LAUNCH_REPICK(2, true); else if (ppl == 6) LAUNCH_REPICK(6, true); else LAUNCH_REPICK(8, true); }
-        else { if (ppl == 2) LAUNCH_REPICK(2, false); else if (ppl == 6) LAUNCH_REPICK(6, false); else LAUNCH_REPICK(8, false); }
-#undef LAUNCH_REPICK
+        const RepickPlan rk = plan_repick(*c, pa.n_miss != nullptr, n_arrays, pa.n_chunks);      // (n_miss: the launch also patches the steered rows)
+        if ((rc = launch(c, scan_repick_kernel(rk.form), rk.grid, rk.block, rk.lds, &pa, st, "k_scan_repick"))) return rc;
         if (gate) hipLaunchKernelGGL(k_doa_fill, dim3(n_arrays), dim3(1024), 0, st, fa);   // gated-out frames repeat the last FINAL pick
         time_end(c, st);
         HIP_TRY(c, hipGetLastError());
@@ -1795,20 +1476,11 @@ int mca_hip_get_repair_columns(mca_hip_ctx *c, unsigned long long *candidate_col
     return MCA_HIP_OK;
 }
 
-// the wave-per-run beamformer (k_beamform_wave) serves the 1024-sample path (one grid row of workgroups per source) when the caller's DOAs are grid
-// bins (the localiser's own picks); everything else stays on k_beamform_ola / _512 / _gen
-static bool wave_beamformer_applies(const mca_hip_ctx *c)
-{
-    // several sources: up to 8 microphones k_beamform_wave_ms (forward transforms shared, the pair spectra in registers); more
-    // microphones with two sources a grid row of k_beamform_wave per source, with three or four k_beamform_ola
-    return !c->generic && !c->n512 && (c->S <= 2 || c->M <= 8) && c->M >= 2 && c->M <= MCA_MAX_MICS;
-}
-
 // steering rows of every grid angle (+ the initial DOA): allocated and built once, outside any capture.  Built into a local and handed
 // to the context when the table kernel has run: d_bftab set means the table is there
 static int ensure_bf_table(mca_hip_ctx *c)
 {
-    if (c->d_bftab || (!c->n2048 && !wave_beamformer_applies(c))) return MCA_HIP_OK;
+    if (c->d_bftab || (!c->n2048 && !wave_beamformer_applies(*c))) return MCA_HIP_OK;
     // 2048-sample frames: a row per (angle, CHANNEL), [D + 1][M][1032] (k_beamform_wave_2048); else per channel pair, [D + 1][np][1024]
     const int np = c->n2048 ? c->M : (c->M + 1) / 2;
     DevBuf<float2> tab;
@@ -1910,11 +1582,10 @@ static int steer_separate(mca_hip_ctx *c, const StreamCall &call, const float *p
     const int pf = steer_pass_frames(c, n_arrays, n_frames);
     const bool fused = call.steer_fused && pf == n_frames;
     const bool patched = fused && call.steer_patched;         // the second pick of the localiser patched the missed frames and counted them (localise_impl)
-    const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2);
     float *tails[2] = {c->d_steer_tail, c->d_steer_tail + (size_t)c->cfg.max_arrays * FFT_H};
     time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-    int pass = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += pf, ++pass) {
+    int pass = 0, rc = MCA_HIP_OK;
+    for (int f0 = 0; f0 < n_frames && !rc; f0 += pf, ++pass) {
         const int f1 = std::min(n_frames, f0 + pf), np = f1 - f0;
         const bool last = f1 == n_frames;
         SteerPatchArgs pa{};
@@ -1922,22 +1593,21 @@ static int steer_separate(mca_hip_ctx *c, const StreamCall &call, const float *p
         pa.window = c->d_window; pa.doa_bin = doa_bin; pa.all = fused ? 0 : 1; pa.miss = c->d_steer_miss;
         pa.bf.rows = c->d_steer_rows; pa.bf.q = c->d_steer_q; pa.bf.nyq = c->d_steer_nyq; pa.bf.pred = c->d_steer_pred + a0; pa.bf.Y = c->d_steer_Y;
         pa.y_f0 = f0; pa.y_frames = fused ? n_frames : np;
-        if (!patched) hipLaunchKernelGGL(k_steer_patch, dim3(std::min(STEER_PATCH_WGS, (np + 3) / 4)), dim3(256), smem, st, pa);
+        const SteerPlan sp = plan_steer(*c, n_arrays, np);
+        if (!patched && (rc = launch(c, reinterpret_cast<const void *>(&k_steer_patch), sp.patch_grid, sp.block, sp.lds, &pa, st, "k_steer_patch"))) break;
         SteerSynthArgs sy{};
         sy.Y = c->d_steer_Y; sy.n_frames = n_frames; sy.f0 = f0; sy.f1 = f1; sy.y_f0 = pa.y_f0; sy.y_frames = pa.y_frames;
-        sy.ft = 16;
-        while (sy.ft > 2 && (long long)n_arrays * ((np + sy.ft - 1) / sy.ft) < 1024) sy.ft >>= 1;      // (a thousand runs: one wave each)
+        sy.ft = sp.ft;
         sy.out = out_pcm;
         sy.tail_in = pass == 0 ? c->d_tail[c->tail_cur] + a0 * FFT_H : tails[(pass - 1) & 1];
         sy.tail_out = last ? c->d_tail[c->tail_cur ^ 1] + a0 * FFT_H : tails[pass & 1];
         sy.doa_bin = doa_bin; sy.pred_out = last ? c->d_steer_pred + a0 : nullptr;
         if (last && c->h_steer) { sy.report = c->h_steer + 2 * (c->steer_seq % FB_RING); sy.seq = c->steer_seq + 1; sy.miss_total = c->d_steer_miss; }
         if (patched) sy.n_miss = c->d_steer_mlist;
-        const int runs = (np + sy.ft - 1) / sy.ft;
-        hipLaunchKernelGGL(k_steer_synth, dim3((runs + 3) / 4, n_arrays), dim3(256), smem, st, sy);
+        rc = launch(c, reinterpret_cast<const void *>(&k_steer_synth), sp.synth_grid, sp.block, sp.lds, &sy, st, "k_steer_synth");
     }
     time_end(c, st);
-    HIP_TRY(c, hipGetLastError());
+    if (rc) return rc;
     c->steer_call_frames[c->steer_seq % FB_RING] = (unsigned long long)n_arrays * n_frames; ++c->steer_seq;
     c->steer_frames_total += (unsigned long long)n_arrays * n_frames;
     if (fused) ++c->steer_fused_calls;
@@ -1949,154 +1619,46 @@ static int separate_impl(mca_hip_ctx *c, const StreamCall &call, const float *pc
                          int n_arrays, int n_frames, const float *doa_rad, float *out_pcm, hipStream_t st, const int *doa_bin = nullptr)
 {
     const size_t a0 = (size_t)call.a0;
-    if (doa_bin && c->d_bftab && c->n2048 && (reinterpret_cast<uintptr_t>(out_pcm) & 7) == 0) {
-        // 2048-sample frames, the localiser's own picks: one wave per run of frames, a transform per channel (k_beamform_wave_2048)
+    const BeamformPlan bp = plan_beamform(*c, doa_bin && c->d_bftab, (reinterpret_cast<uintptr_t>(out_pcm) & 7) == 0, n_arrays, n_frames);
+    if (bp.unsupported) return fail(c, MCA_HIP_ERR_UNSUPPORTED, bp.unsupported);
+    const BeamformFamily family = bp.form.family;
+    int rc = MCA_HIP_OK;
+    if (family == BeamformFamily::WAVE_2048 || family == BeamformFamily::WAVE_MS || family == BeamformFamily::WAVE) {
+        // the localiser's own picks against the table of steering rows: a transform per channel (k_beamform_wave_2048), per channel pair with
+        // the forward transforms of a frame shared by its sources (k_beamform_wave_ms) or a grid row per source (k_beamform_wave)
         BeamformWaveArgs wa{};
         wa.pcm = pcm; wa.array_stride = array_stride; wa.mic_stride = mic_stride;
-        wa.M = c->M; wa.n_pairs = c->M; wa.n_frames = n_frames; wa.S = c->S;
-        // frames per wave: a workgroup covers 4 ft - 1 frames (one analysed twice); the smallest ft whose workgroups fit ONE resident round of
-        // two per CU (255 registers: two waves per SIMD), 16 when no such ft exists (many rounds anyway)
-        wa.ft = 16;
-        for (int ft = 2; ft <= 64; ++ft)
-            if ((long long)n_arrays * c->S * ((n_frames + 4 * ft - 2) / (4 * ft - 1)) <= 2LL * c->n_cu) { wa.ft = ft; break; }
+        wa.M = c->M; wa.n_pairs = family == BeamformFamily::WAVE_2048 ? c->M : c->bf_pairs; wa.n_frames = n_frames; wa.S = c->S;
+        wa.ft = bp.ft; wa.skew = bp.skew;
         wa.window = c->d_window; wa.doa_bin = doa_bin; wa.table = c->d_bftab; wa.out = out_pcm;
         wa.tail_in = c->d_tail[c->tail_cur] + a0 * c->S * c->H; wa.tail_out = c->d_tail[c->tail_cur ^ 1] + a0 * c->S * c->H;
-        const int wgs = (n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1);
-        const size_t smem_w = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH + 4 * 512) * sizeof(float2);
+        const void *k = family == BeamformFamily::WAVE_2048 ? reinterpret_cast<const void *>(&k_beamform_wave_2048)
+                        : family == BeamformFamily::WAVE_MS ? beamform_wave_ms_kernel(bp.form) : beamform_wave_kernel(bp.form);
         time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-        hipLaunchKernelGGL(k_beamform_wave_2048, dim3(wgs, n_arrays, c->S), dim3(256), smem_w, st, wa);
+        rc = launch(c, k, bp.grid, bp.block, bp.lds, &wa, st, "k_beamform_wave");
         time_end(c, st);
-        HIP_TRY(c, hipGetLastError());
-        return MCA_HIP_OK;
-    }
-    if (doa_bin && c->d_bftab && wave_beamformer_applies(c)) {
-        BeamformWaveArgs wa{};
-        wa.pcm = pcm; wa.array_stride = array_stride; wa.mic_stride = mic_stride;
-        wa.M = c->M; wa.n_pairs = c->bf_pairs; wa.n_frames = n_frames; wa.S = c->S;
-        wa.window = c->d_window; wa.doa_bin = doa_bin; wa.table = c->d_bftab; wa.out = out_pcm;
-        wa.tail_in = c->d_tail[c->tail_cur] + a0 * c->S * c->H; wa.tail_out = c->d_tail[c->tail_cur ^ 1] + a0 * c->S * c->H;
-        if (c->S >= 2 && c->M <= 8) {
-            // the forward transforms of a frame shared by its sources.  Frames per run (one wave each; every run re-analyses one extra
-            // frame for its overlap-add carry): long runs are cheaper per frame, short ones fill the chip -- two waves per SIMD want 2048 runs
-            wa.ft = 16;
-            while (wa.ft > 2 && (long long)n_arrays * ((n_frames + wa.ft - 1) / wa.ft) < 2048) wa.ft >>= 1;
-            const int runs = (n_frames + wa.ft - 1) / wa.ft;
-            const size_t smem_ms = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2) + (size_t)4 * c->S * FFT_H * sizeof(float);
-            const dim3 gms((runs + 3) / 4, n_arrays);
-            time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-#define BFMS(NPT)                                                                                                                   \
-            do {                                                                                                                    \
-                if (smem_ms > 64 * 1024) {                                                                                          \
-                    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_beamform_wave_ms<NPT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_ms)); \
-                    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_beamform_wave_ms<NPT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_ms));  \
-                }                                                                                                                   \
-                if (c->M & 1) hipLaunchKernelGGL((k_beamform_wave_ms<NPT, true>), gms, dim3(256), smem_ms, st, wa);                 \
-                else hipLaunchKernelGGL((k_beamform_wave_ms<NPT, false>), gms, dim3(256), smem_ms, st, wa);                         \
-            } while (0)
-            if (c->bf_pairs == 1) {          // two microphones: one pair (never odd)
-                if (smem_ms > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_beamform_wave_ms<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_ms));
-                hipLaunchKernelGGL((k_beamform_wave_ms<1, false>), gms, dim3(256), smem_ms, st, wa);
-            }
-            else if (c->bf_pairs == 2) BFMS(2);
-            else if (c->bf_pairs == 3) BFMS(3);
-            else BFMS(4);
-#undef BFMS
-            time_end(c, st);
-            HIP_TRY(c, hipGetLastError());
-            return MCA_HIP_OK;
-        }
-        // A workgroup covers 4 ft - 1 frames (the overlap-add carries are handed off inside it, k_beamform_wave); ft is the smallest run
-        // length whose workgroups are all resident at once (two per CU: 512) -- one workgroup more than that costs a whole extra round.
-        wa.ft = 2;
-        while (wa.ft < 256 && (long long)n_arrays * c->S * ((n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1)) > 512) ++wa.ft;
-        const int wgs = (n_frames + 4 * wa.ft - 2) / (4 * wa.ft - 1);
-        const size_t smem = (size_t)(F1K_TWORDS + 4 * F1K_SCRATCH) * sizeof(float2) + 4 * FFT_H * sizeof(float);
-        // one resident round of (nearly) two workgroups per CU: the older workgroup of every CU takes longer runs (BeamformWaveArgs::skew)
-        dim3 gb(wgs, n_arrays, c->S);
-        if (c->S == 1 && (wgs & 1) == 0 && wa.ft >= 8 && (long long)wgs * n_arrays > (long long)c->n_cu * 3 / 2 && (long long)wgs * n_arrays <= 2LL * c->n_cu) {
-            wa.skew = (3 * wa.ft + 8) / 16;
-            if (wa.skew >= wa.ft) wa.skew = 0;
-            else gb = dim3(n_arrays, wgs, c->S);
-        }
-        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-        if (c->M & 1) hipLaunchKernelGGL(k_beamform_wave<true>, gb, dim3(256), smem, st, wa);
-        else hipLaunchKernelGGL(k_beamform_wave<false>, gb, dim3(256), smem, st, wa);
-        time_end(c, st);
-        HIP_TRY(c, hipGetLastError());
-        return MCA_HIP_OK;
+        return rc;
     }
     BeamformArgs ba{};
     ba.pcm = pcm; ba.array_stride = array_stride; ba.mic_stride = mic_stride;
     ba.M = c->M; ba.Mpad = c->M; ba.S = c->S; ba.n_frames = n_frames; ba.fs = c->cfg.sample_rate;
-    // frames per run: every run re-analyses one extra frame for its overlap-add carry, so long runs are cheaper per
-    // frame (16 -> 64 frames: 0.344 -> 0.323 ms on the bench shape); smaller batches take shorter runs so that two
-    // workgroups per CU exist (multiples of the 4-frame batch)
-    ba.ft = 64;
-    // (the any-length kernel walks its frames one at a time behind ~15 barriers each and is latency bound: it wants as
-    // many workgroups per CU as its LDS allows, up to the 8 that fill the wave slots with 256 threads)
-    long long want_wgs = 512;
-    if (c->generic) {
-        const size_t smem_g = (size_t)(c->M + c->S) * (c->H + 1) * sizeof(float2) + (size_t)c->S * c->H * sizeof(float);
-        const long long per_cu = std::max<long long>(1, std::min<long long>((160 * 1024) / (long long)smem_g, 2048 / gen_threads(c, true)));
-        want_wgs = 256 * per_cu;
-    }
-    while (ba.ft > BF_NB && (long long)n_arrays * ((n_frames + ba.ft - 1) / ba.ft) < want_wgs) ba.ft >>= 1;
+    ba.ft = bp.ft; ba.nb = bp.nb;
     ba.window = c->d_window; ba.mic_x = c->d_micx; ba.doa_rad = doa_rad; ba.out = out_pcm;
     ba.tail_in = c->d_tail[c->tail_cur] + a0 * c->S * c->H; ba.tail_out = c->d_tail[c->tail_cur ^ 1] + a0 * c->S * c->H;
     ba.N = c->N; ba.logH = c->logH; ba.tw = c->d_tw;
-    if (c->n512) {
-        const size_t smem = ((size_t)2 * 8 * 258 + 8 * FFT_SCRATCH + TW_WIN + (size_t)2 * c->S * c->M * 41) * sizeof(float2) + (size_t)2 * c->S * sizeof(double);
-        ba.ft = 64;
-        const long long per_cu = smem <= 80 * 1024 ? 2 : 1;
-        while (ba.ft > 4 && (long long)n_arrays * ((n_frames + ba.ft - 1) / ba.ft) < 256 * per_cu) ba.ft >>= 1;
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_beamform_512), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-        hipLaunchKernelGGL(k_beamform_512, dim3((n_frames + ba.ft - 1) / ba.ft, n_arrays), dim3(512), smem, st, ba);
-        time_end(c, st);
-        HIP_TRY(c, hipGetLastError());
-        return MCA_HIP_OK;
-    }
-    if (c->generic) {
-        // all sources in one launch while M + S spectra (and the S carries) fit the 160 KiB of a CU; else as many per launch as do --
-        // 16 microphones at 2048-sample frames hold two -- each pass transforming the channels again
-        auto smem_for = [&](int s_pass) {
-            return (size_t)(c->M + s_pass) * (c->H + 1) * sizeof(float2) + (size_t)s_pass * c->H * sizeof(float) + (size_t)(ba.ft + 1) * s_pass * sizeof(double) + 8;
-        };
-        int s_pass = c->S;
-        while (s_pass > 1 && smem_for(s_pass) > 160 * 1024) --s_pass;
-        const size_t smem = smem_for(s_pass);
-        if (smem > 160 * 1024) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "fft_size x n_mics exceeds the 160 KiB LDS of a CU");
-        if (smem > 64 * 1024)
-            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_beamform_gen), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-        ba.S_all = c->S;
-        for (int s0 = 0; s0 < c->S; s0 += s_pass) {
-            ba.s0 = s0; ba.S = std::min(s_pass, c->S - s0);
-            hipLaunchKernelGGL(k_beamform_gen, dim3((n_frames + ba.ft - 1) / ba.ft, n_arrays), dim3(gen_threads(c, true)), smem, st, ba);
-        }
-        time_end(c, st);
-        HIP_TRY(c, hipGetLastError());
-        return MCA_HIP_OK;
-    }
-    ba.nb = std::max(1, BF_NB / c->S);      // 4 beamformed slots in LDS whatever the number of sources
-    const size_t smem = ((size_t)ba.M + ba.nb * c->S) * FFT_SCRATCH * sizeof(float2) + (size_t)c->S * c->M * 49 * sizeof(float2) +
-                        TW_WORDS * sizeof(float2) + (size_t)ba.nb * c->M * (1 + c->S) * sizeof(float2) +
-                        (size_t)(ba.ft + 1) * c->S * sizeof(double);
-    if (smem > 160 * 1024) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "n_mics/n_sources combination exceeds the 160 KiB LDS of a CU");
-    dim3 g((n_frames + ba.ft - 1) / ba.ft, n_arrays);
     time_begin(c, call, MCA_HIP_K_BEAMFORM, st);
-#define BF_LAUNCH(K)                                                                                                     \
-    do {                                                                                                                 \
-        if (smem > 64 * 1024)                                                                                            \
-            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL(K, g, dim3(512), smem, st, ba);                                                               \
-    } while (0)
-    if (c->M <= 8) BF_LAUNCH((k_beamform_ola<1, 4>));
-    else BF_LAUNCH((k_beamform_ola<2, 2>));
-#undef BF_LAUNCH
+    if (family == BeamformFamily::GEN) {
+        ba.S_all = c->S;
+        for (int s0 = 0; s0 < c->S && !rc; s0 += bp.s_pass) {      // (the sources in passes, each transforming the channels again: plan_beamform)
+            ba.s0 = s0; ba.S = std::min(bp.s_pass, c->S - s0);
+            rc = launch(c, reinterpret_cast<const void *>(&k_beamform_gen), bp.grid, bp.block, bp.lds, &ba, st, "k_beamform_gen");
+        }
+    } else {
+        const void *k = family == BeamformFamily::N512 ? reinterpret_cast<const void *>(&k_beamform_512) : beamform_ola_kernel(bp.form);
+        rc = launch(c, k, bp.grid, bp.block, bp.lds, &ba, st, "k_beamform_ola");
+    }
     time_end(c, st);
-    HIP_TRY(c, hipGetLastError());
-    return MCA_HIP_OK;
+    return rc;
 }
 
 // The stream calls behind the public entry points, which build the record; graph_record and the host-pointer entry points come with

@@ -1,6 +1,7 @@
-// kernels.h -- declarations of the kernels defined in kernels_*.hip (explicitly instantiated there).
+// kernels.h -- declarations of the kernels defined in kernels_*.hip (instantiated there: explicitly, or by the lookup of their family).
 #pragma once
 #include "mca_internal.h"
+#include "stream_plan.h"
 
 namespace mca {
 
@@ -33,6 +34,21 @@ template <int MT, bool ULA, typename OutT, bool PL2, bool POWER, bool NOPHAT, bo
 __global__ void k_steer_table(float4 *rows, float2 *q, float *nyq, const float *grid, const double *mic_x, int M, double unit);      // 8-microphone ULA contexts (steer.h)
 __global__ void k_steer_patch(SteerPatchArgs p);
 __global__ void k_steer_synth(SteerSynthArgs p);
+// The kernel of a form (stream_plan.h), each lookup beside its family's source, which instantiates exactly the rows of the family's
+// predicate; nullptr: not in the build
+const void *stft_wave_kernel(const StftForm &f);          // kernels_wave.hip
+const void *stft_wave16_kernel(const StftForm &f);
+const void *beamform_wave_kernel(const BeamformForm &f);
+const void *beamform_wave_ms_kernel(const BeamformForm &f);
+const void *stft_block_kernel(const StftForm &f);         // kernels_stream.hip
+const void *stft_few_kernel(const StftForm &f);
+const void *stft_512_kernel(const StftForm &f);
+const void *stft_sub2_kernel(const StftForm &f);
+const void *scan_pick_kernel(const PickForm &f);
+const void *scan_repick_kernel(const RepickForm &f);
+const void *beamform_ola_kernel(const BeamformForm &f);
+const void *stft_2048_kernel(const StftForm &f);          // kernels_2048.hip
+const void *stft_gen_kernel(const StftForm &f);           // kernels_generic.hip
 
 __global__ void k_srp_gemm_f32(GemmArgs p);
 template <bool SPLIT, int BN> __global__ void k_srp_gemm_f16(GemmArgs p);
@@ -40,6 +56,8 @@ __global__ void k_srp_gemm_f16_v2(GemmArgs p);      // hi + lo planes, v_mfma_f3
 __global__ void k_srp_gemm_f16_v3(GemmArgs p);      // one plane, v_mfma_f32_16x16x32_f16
 __global__ void k_srp_gemm_f16_fold(GemmArgs p);    // one plane, planar rows of a folding context: K half y against the even / odd half-width table
 template <int BN> __global__ void k_srp_gemm_repair(GemmArgs p);
+const void *srp_gemm_f16_kernel(bool split, int bn);      // kernels_gemm.hip
+const void *srp_gemm_repair_kernel(int bn);
 
 template <typename T> struct C2;
 template <typename T>

@@ -20,6 +20,7 @@
 #include "fft1024c.h"
 #include "mca_internal.h"
 #include "phat_pairs.h"
+#include "stream_plan.h"
 
 namespace mca {
 
@@ -258,11 +259,21 @@ __global__ __launch_bounds__(512) void k_stft_phat_2048(StftPhatArgs p)
     }                                                                     // (list mode: the barrier at the top of the next unit keeps nyq until every thread is through)
 }
 
-#define INST_2048(MT, ULA, T) template __global__ void k_stft_phat_2048<MT, ULA, T, false>(StftPhatArgs);
-INST_2048(0, false, float) INST_2048(0, true, float) INST_2048(4, false, float) INST_2048(4, true, float) INST_2048(8, false, float) INST_2048(8, true, float)
-INST_2048(0, false, _Float16) INST_2048(0, true, _Float16) INST_2048(4, false, _Float16) INST_2048(4, true, _Float16) INST_2048(8, false, _Float16) INST_2048(8, true, _Float16)
-template __global__ void k_stft_phat_2048<4, true, _Float16, true>(StftPhatArgs);
-template __global__ void k_stft_phat_2048<8, true, _Float16, true>(StftPhatArgs);
+// The kernel of a form, or nullptr where the build has none: the walk names every row of stft_2048_row (stream_plan.h) once, and
+// thereby instantiates those kernels.
+const void *stft_2048_kernel(const StftForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<3 * 2 * 2 * 2>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, MT = 4 * (r >> 3);
+        constexpr bool ULA = r & 1, F32 = r & 2, MERGE = r & 4;
+        if constexpr (stft_2048_row(MT, ULA, F32, MERGE)) {
+            using T = std::conditional_t<F32, float, _Float16>;
+            if (f.mt == MT && f.ula == ULA && f.f32 == F32 && f.merge == MERGE) kernel = reinterpret_cast<const void *>(&k_stft_phat_2048<MT, ULA, T, MERGE>);
+        }
+    });
+    return kernel;
+}
 
 // --------------------------------------------------------------------------------------
 // k_bf_table_2048: grid (D + 1, M) x 256.  Row 0: DOA = 0 rad (the module's initial _currentDOA, BeamformingSeparationAndLocalisation.cpp:51),

@@ -10,6 +10,7 @@
 //   k_srp_gemm_f32   v_mfma_f32_32x32x2_f32: bit-exact fp32 fma chain, parity anchor
 //   k_srp_gemm_f16   v_mfma_f32_32x32x16_f16 with 1 (fp16) or 3 (fp16x3 hi/lo split) products
 #include "mca_internal.h"
+#include "stream_plan.h"
 
 namespace mca {
 
@@ -237,13 +238,32 @@ __global__ __launch_bounds__(256) void k_srp_gemm_repair(GemmArgs p)
     }
 }
 
-template __global__ void k_srp_gemm_repair<192>(GemmArgs);
-template __global__ void k_srp_gemm_repair<64>(GemmArgs);
 
-template __global__ void k_srp_gemm_f16<false, 192>(GemmArgs);
-template __global__ void k_srp_gemm_f16<true, 192>(GemmArgs);
-template __global__ void k_srp_gemm_f16<false, 64>(GemmArgs);
-template __global__ void k_srp_gemm_f16<true, 64>(GemmArgs);
+// The kernels of a column tile width, or nullptr where the build has none (gemm_f16_row, stream_plan.h): the walks name every row once,
+// and thereby instantiate those kernels.
+const void *srp_gemm_f16_kernel(bool split, int bn)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 4>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, BN = 64 * (r >> 1);
+        constexpr bool SPLIT = r & 1;
+        if constexpr (gemm_f16_row(BN)) {
+            if (split == SPLIT && bn == BN) kernel = reinterpret_cast<const void *>(&k_srp_gemm_f16<SPLIT, BN>);
+        }
+    });
+    return kernel;
+}
+const void *srp_gemm_repair_kernel(int bn)
+{
+    const void *kernel = nullptr;
+    plan_static_for<4>([&](auto rc) {
+        constexpr int BN = 64 * decltype(rc)::value;
+        if constexpr (gemm_f16_row(BN)) {
+            if (bn == BN) kernel = reinterpret_cast<const void *>(&k_srp_gemm_repair<BN>);
+        }
+    });
+    return kernel;
+}
 
 // ---------------------------------------------------------------------------------------
 // The 256 x 384 contraction kernel for Dp == 384 (the 361-angle grid).  Measured on MI355X this contraction is

@@ -12,6 +12,7 @@
 //   k_beamform_gen    PCM -> FFT -> delay-and-sum (Beamformer.cpp:51-71) -> inverse FFT -> overlap-add
 #include "fft_block.h"
 #include "mca_internal.h"
+#include "stream_plan.h"
 
 namespace mca {
 
@@ -71,8 +72,11 @@ __global__ __launch_bounds__(1024) void k_stft_phat_gen(StftPhatArgs p)
     }
 }
 
-template __global__ void k_stft_phat_gen<float>(StftPhatArgs);
-template __global__ void k_stft_phat_gen<_Float16>(StftPhatArgs);
+// the kernel of a form (stream_plan.h): both output types
+const void *stft_gen_kernel(const StftForm &f)
+{
+    return f.f32 ? reinterpret_cast<const void *>(&k_stft_phat_gen<float>) : reinterpret_cast<const void *>(&k_stft_phat_gen<_Float16>);
+}
 
 // --------------------------------------------------------------------------------------
 // k_beamform_gen: grid (runs of ft frames, arrays), 256 ... 1024 threads,

@@ -13,6 +13,7 @@
 #include "phat_pairs.h"
 #include "pair_balance.h"
 #include "steer.h"
+#include "stream_plan.h"
 
 namespace mca {
 
@@ -136,11 +137,21 @@ __global__ __launch_bounds__(512) void k_stft_phat(StftPhatArgs p)
     }
 }
 
-#define INST_STFT(MT, ULA, T) template __global__ void k_stft_phat<MT, ULA, T>(StftPhatArgs);
-INST_STFT(0, false, float) INST_STFT(0, true, float)
-INST_STFT(16, true, float)
-INST_STFT(0, false, _Float16) INST_STFT(0, true, _Float16)
-INST_STFT(16, true, _Float16)
+// The kernel of a form, or nullptr where the build has none: the walk names every row of stft_block_row (stream_plan.h) once, and
+// thereby instantiates those kernels.  (The other lookups of this file are written the same way.)
+const void *stft_block_kernel(const StftForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 2 * 2>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, MT = 16 * (r >> 2);
+        constexpr bool ULA = r & 1, F32 = r & 2;
+        if constexpr (stft_block_row(MT, ULA)) {
+            using T = std::conditional_t<F32, float, _Float16>;
+            if (f.mt == MT && f.ula == ULA && f.f32 == F32) kernel = reinterpret_cast<const void *>(&k_stft_phat<MT, ULA, T>);
+        }
+    });
+    return kernel;
+}
 
 // --------------------------------------------------------------------------------------
 // k_stft_phat_few: the same stage for few microphones (instantiated for 2; with 4 it measured no faster than
@@ -217,9 +228,12 @@ __global__ __launch_bounds__(512) void k_stft_phat_few(StftPhatArgs p)
     }
 }
 
-#define INST_FEW(MT, ULA, T) template __global__ void k_stft_phat_few<MT, ULA, T>(StftPhatArgs);
-INST_FEW(2, false, float)
-INST_FEW(2, false, _Float16)
+const void *stft_few_kernel(const StftForm &f)
+{
+    static_assert(stft_few_row(2, false), "the two-microphone row");
+    if (!stft_few_row(f.mt, f.ula)) return nullptr;
+    return f.f32 ? reinterpret_cast<const void *>(&k_stft_phat_few<2, false, float>) : reinterpret_cast<const void *>(&k_stft_phat_few<2, false, _Float16>);
+}
 
 // --------------------------------------------------------------------------------------
 // k_gate -- the power gate of BeamformingSeparationAndLocalisation::processFrameLocalisation
@@ -875,12 +889,17 @@ __global__ __launch_bounds__(PL == 8 ? 576 : 512) __attribute__((amdgpu_waves_pe
     }
     if (p.lookback > 0 && act && (int)blockIdx.x == p.n_chunks - 1) p.state_out[(long long)a * D + d] = E;   // _prevEnergyInDOA (:143)
 }
-template __global__ void k_scan_pick<2, 0>(ScanPickArgs);
-template __global__ void k_scan_pick<6, 0>(ScanPickArgs);
-template __global__ void k_scan_pick<8, 0>(ScanPickArgs);
-template __global__ void k_scan_pick<2, 1>(ScanPickArgs);
-template __global__ void k_scan_pick<6, 1>(ScanPickArgs);
-template __global__ void k_scan_pick<8, 1>(ScanPickArgs);
+const void *scan_pick_kernel(const PickForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 9>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, PL = r >> 1, MODE = r & 1;
+        if constexpr (scan_pl_row(PL)) {
+            if (f.pl == PL && f.mode == MODE) kernel = reinterpret_cast<const void *>(&k_scan_pick<PL, MODE>);
+        }
+    });
+    return kernel;
+}
 
 // --------------------------------------------------------------------------------------
 // k_scan_repick / k_repair_patch -- adaptive SRP precision: the second pick of the flagged frames on the exact rows
@@ -1076,12 +1095,18 @@ __global__ __launch_bounds__(512) void k_scan_repick(ScanPickArgs p)
         if (atomicAdd(p.n_clist + 1, 1) >= max(n_part, 1) - 1) { *p.n_list = 0; *p.n_clist = 0; p.n_clist[1] = 0; }
     }
 }
-template __global__ void k_scan_repick<2, false>(ScanPickArgs);
-template __global__ void k_scan_repick<6, false>(ScanPickArgs);
-template __global__ void k_scan_repick<8, false>(ScanPickArgs);
-template __global__ void k_scan_repick<2, true>(ScanPickArgs);
-template __global__ void k_scan_repick<6, true>(ScanPickArgs);
-template __global__ void k_scan_repick<8, true>(ScanPickArgs);
+const void *scan_repick_kernel(const RepickForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 9>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, PL = r >> 1;
+        constexpr bool PATCH = r & 1;
+        if constexpr (scan_pl_row(PL)) {
+            if (f.pl == PL && f.patch == PATCH) kernel = reinterpret_cast<const void *>(&k_scan_repick<PL, PATCH>);
+        }
+    });
+    return kernel;
+}
 
 // k_repair_patch: a fixed grid walks the rows of this pass, 128 threads per row: the exact row (sum of the repair contraction's
 // split-K partial maps, plane 0 first) replaces plane 0 of the map, the other planes of that row become zero; the group's
@@ -1385,8 +1410,17 @@ __global__ __launch_bounds__(512, OCC) void k_beamform_ola(BeamformArgs p)
     }
 }
 
-template __global__ void k_beamform_ola<1, 4>(BeamformArgs);
-template __global__ void k_beamform_ola<2, 2>(BeamformArgs);
+const void *beamform_ola_kernel(const BeamformForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 4>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, CPW = (r >> 2) + 1, OCC = (r & 3) + 1;
+        if constexpr (beamform_ola_row(CPW, OCC)) {
+            if (f.cpw == CPW && f.occ == OCC) kernel = reinterpret_cast<const void *>(&k_beamform_ola<CPW, OCC>);
+        }
+    });
+    return kernel;
+}
 
 // --------------------------------------------------------------------------------------
 // 512-sample frames (16 kHz at the reference's 0.025 s frame rate) on the wave-level FFT
@@ -1475,9 +1509,19 @@ __global__ __launch_bounds__(512) void k_stft_phat_512(StftPhatArgs p)
     }                                                                       // (list mode: the barrier at the top of the next unit keeps nyq until every thread is through)
 }
 
-#define INST_512(MT, ULA, T) template __global__ void k_stft_phat_512<MT, ULA, T>(StftPhatArgs);
-INST_512(0, false, float) INST_512(0, true, float) INST_512(4, false, float) INST_512(4, true, float) INST_512(8, false, float) INST_512(8, true, float)
-INST_512(0, false, _Float16) INST_512(0, true, _Float16) INST_512(4, false, _Float16) INST_512(4, true, _Float16) INST_512(8, false, _Float16) INST_512(8, true, _Float16)
+const void *stft_512_kernel(const StftForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<3 * 2 * 2>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, MT = 4 * (r >> 2);
+        constexpr bool ULA = r & 1, F32 = r & 2;
+        if constexpr (stft_512_row(MT)) {
+            using T = std::conditional_t<F32, float, _Float16>;
+            if (f.mt == MT && f.ula == ULA && f.f32 == F32) kernel = reinterpret_cast<const void *>(&k_stft_phat_512<MT, ULA, T>);
+        }
+    });
+    return kernel;
+}
 
 // k_stft_phat_sub2<R>: the analysis + PHAT stage for TWO microphones at frames of N = 512 R samples, R = 4 or 8 --
 // FreqGCCBinauralLocalisation's 0.075 s frames (BinauralLocalisation.h:196) at 32 kHz (2048) and 44.1 / 48 kHz (4096; the
@@ -1558,10 +1602,19 @@ __global__ __launch_bounds__(512) void k_stft_phat_sub2(StftPhatArgs p)
     }
 }
 
-template __global__ void k_stft_phat_sub2<8, float>(StftPhatArgs);
-template __global__ void k_stft_phat_sub2<8, _Float16>(StftPhatArgs);
-template __global__ void k_stft_phat_sub2<4, float>(StftPhatArgs);
-template __global__ void k_stft_phat_sub2<4, _Float16>(StftPhatArgs);
+const void *stft_sub2_kernel(const StftForm &f)      // (f.mt: R)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 9>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, R = r >> 1;
+        constexpr bool F32 = r & 1;
+        if constexpr (stft_sub2_row(R)) {
+            using T = std::conditional_t<F32, float, _Float16>;
+            if (f.mt == R && f.f32 == F32) kernel = reinterpret_cast<const void *>(&k_stft_phat_sub2<R, T>);
+        }
+    });
+    return kernel;
+}
 
 // k_mvdr_analyse_512: the analysis stage of the MVDR path (kernels_mvdr.hip: k_mvdr_analyse_1024) for 512-sample frames: wave w
 // transforms channels 2 w, 2 w + 1 of the frame in one pass (up to 16 channels), then the spectra go out transposed,

@@ -19,6 +19,7 @@
 #include "phat_pairs.h"
 #include "pair_balance.h"
 #include "steer.h"
+#include "stream_plan.h"
 
 namespace mca {
 
@@ -181,8 +182,10 @@ __global__ __launch_bounds__(256, 2) void k_beamform_wave(BeamformWaveArgs p)
         for (int i = 0; i < 8; ++i) o[64 * i] = xcarry[(wave - 1) * FFT_H + lane + 64 * i] + first[i];
     }
 }
-template __global__ void k_beamform_wave<false>(BeamformWaveArgs);
-template __global__ void k_beamform_wave<true>(BeamformWaveArgs);
+const void *beamform_wave_kernel(const BeamformForm &f)
+{
+    return f.odd ? reinterpret_cast<const void *>(&k_beamform_wave<true>) : reinterpret_cast<const void *>(&k_beamform_wave<false>);
+}
 
 // --------------------------------------------------------------------------------------
 // k_beamform_wave_ms: several sources per array, the forward transforms SHARED (round 4; up to 8 microphones)
@@ -300,10 +303,20 @@ __global__ __launch_bounds__(256, 2) void k_beamform_wave_ms(BeamformWaveArgs p)
         }
     }
 }
-template __global__ void k_beamform_wave_ms<1, false>(BeamformWaveArgs);      // (two microphones: one pair)
-template __global__ void k_beamform_wave_ms<2, false>(BeamformWaveArgs); template __global__ void k_beamform_wave_ms<2, true>(BeamformWaveArgs);
-template __global__ void k_beamform_wave_ms<3, false>(BeamformWaveArgs); template __global__ void k_beamform_wave_ms<3, true>(BeamformWaveArgs);
-template __global__ void k_beamform_wave_ms<4, false>(BeamformWaveArgs); template __global__ void k_beamform_wave_ms<4, true>(BeamformWaveArgs);
+// The kernel of a form, or nullptr where the build has none: the walk names every row of beamform_ms_row (stream_plan.h) once, and
+// thereby instantiates those kernels.
+const void *beamform_wave_ms_kernel(const BeamformForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 * 5>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, NPT = r >> 1;
+        constexpr bool ODD = r & 1;
+        if constexpr (beamform_ms_row(NPT, ODD)) {
+            if (f.npt == NPT && f.odd == ODD) kernel = reinterpret_cast<const void *>(&k_beamform_wave_ms<NPT, ODD>);
+        }
+    });
+    return kernel;
+}
 
 // --------------------------------------------------------------------------------------
 // k_stft_phat_wave: STFT analysis + GCC-PHAT pair products (SteeringBeamforming.cpp:104-130 up to the steering sum), one
@@ -1063,23 +1076,26 @@ __global__ __launch_bounds__(256, 2) void k_stft_phat_wave16(StftPhatArgs p)
         for (int g = 0; g < MT - 1; ++g) store_a_wave<false>(arow, 0u, g * KG + FFT_H, out[g], p.Kp);
     }
 }
-template __global__ void k_stft_phat_wave16<false>(StftPhatArgs);
-template __global__ void k_stft_phat_wave16<true>(StftPhatArgs);
+const void *stft_wave16_kernel(const StftForm &f)
+{
+    return f.power ? reinterpret_cast<const void *>(&k_stft_phat_wave16<true>) : reinterpret_cast<const void *>(&k_stft_phat_wave16<false>);
+}
 
-#define INST_SPW1(MT, ULA, T, PL2, NP) template __global__ void k_stft_phat_wave<MT, ULA, T, PL2, false, NP, false>(StftPhatArgs); \
-                                       template __global__ void k_stft_phat_wave<MT, ULA, T, PL2, true, NP, false>(StftPhatArgs);
-#define INST_SPW(MT, ULA) INST_SPW1(MT, ULA, _Float16, false, false) INST_SPW1(MT, ULA, _Float16, true, false) INST_SPW1(MT, ULA, float, false, false) \
-                          INST_SPW1(MT, ULA, float, false, true)
-INST_SPW(8, true) INST_SPW(8, false) INST_SPW(4, true) INST_SPW(4, false)
-template __global__ void k_stft_phat_wave<8, true, _Float16, false, false, false, true>(StftPhatArgs);
-template __global__ void k_stft_phat_wave<8, true, _Float16, false, true, false, true>(StftPhatArgs);
-template __global__ void k_stft_phat_wave<4, true, _Float16, false, false, false, true>(StftPhatArgs);
-template __global__ void k_stft_phat_wave<8, true, _Float16, false, false, false, true, false, true>(StftPhatArgs);      // FUSE
-template __global__ void k_stft_phat_wave<4, true, _Float16, false, true, false, true>(StftPhatArgs);
-// list mode of a candidate-column call: two planes, no gate, with the candidate contraction of the unit behind its rows (CAND)
-template __global__ void k_stft_phat_wave<8, true, _Float16, true, false, false, false, true>(StftPhatArgs);
-template __global__ void k_stft_phat_wave<8, false, _Float16, true, false, false, false, true>(StftPhatArgs);
-template __global__ void k_stft_phat_wave<4, true, _Float16, true, false, false, false, true>(StftPhatArgs);
-template __global__ void k_stft_phat_wave<4, false, _Float16, true, false, false, false, true>(StftPhatArgs);
+// The k_stft_phat_wave of a form, or nullptr where the build has none: the walk names every row of stft_wave_row (stream_plan.h: base,
+// MERGE, FUSE and CAND forms, 41 kernels) once, and thereby instantiates those kernels.
+const void *stft_wave_kernel(const StftForm &f)
+{
+    const void *kernel = nullptr;
+    plan_static_for<2 << 8>([&](auto rc) {
+        constexpr int r = decltype(rc)::value, MT = r & 1 ? 8 : 4;
+        constexpr bool ULA = r & 2, F32 = r & 4, PL2 = r & 8, POWER = r & 16, NOPHAT = r & 32, MERGE = r & 64, CAND = r & 128, FUSE = r & 256;
+        if constexpr (stft_wave_row(MT, ULA, F32, PL2, POWER, NOPHAT, MERGE, CAND, FUSE)) {
+            using T = std::conditional_t<F32, float, _Float16>;
+            if (f.mt == MT && f.ula == ULA && f.f32 == F32 && f.pl2 == PL2 && f.power == POWER && f.nophat == NOPHAT && f.merge == MERGE && f.cand == CAND && f.fuse == FUSE)
+                kernel = reinterpret_cast<const void *>(&k_stft_phat_wave<MT, ULA, T, PL2, POWER, NOPHAT, MERGE, CAND, FUSE>);
+        }
+    });
+    return kernel;
+}
 
 }  // namespace mca

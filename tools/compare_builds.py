@@ -11,6 +11,8 @@ Cases (2 arrays of max_arrays = 3, calls of 64, 160 and 64 frames unless said ot
 OFF and candidate columns on, so the small batches run coarse + repair whatever the reports say):
   device-pointer stream calls in the four precisions: 8-microphone ULA, the same with the power gate, 16-microphone ULA, 4 microphones;
   fft_size 512 and 2048 at 4 and 8 microphones; two sources on a non-uniform array;
+  2 microphones at fft_size 1024, 2048 and 4096, and 3 microphones at 256 and 4096 (the any-length kernels), FP32 and FP16;
+  FP16 and ADAPTIVE: 16 microphones with 2 and 3 sources, 5 microphones with 1 and 2, a 5-degree grid (Dp = 64), a 0.4-degree grid (D - 2 > 384);
   the host-pointer entry points: pageable, page-locked (the chunked path), 16-bit PCM, and under MCA_HIP_WS_MAX_MB = 1 (the sliced path);
   a graph: 4 launches, an eager call that grows the workspace, 2 more launches;
   the gated 2-microphone path with a tracker (the larger call takes no rows / argmaxes), its frame hook, setProbability;
@@ -86,6 +88,22 @@ def child(out_path):
     for pname, prec in precisions[:3]:
         dev_stream("dev stream, S = 2 on a non-uniform array, %s" % pname, ctx_of(synth.REEM_C, 48000, 1024, prec, S=2, step=5.0),
                    pcm_of(synth.REEM_C, 48000, 512, total, 520))
+
+    # the kernel families the cases above do not reach (each launch of the stream path is planned by csrc/stream_plan.h)
+    for pname, prec in (precisions[0], precisions[1]):
+        for N in (1024, 2048, 4096):
+            dev_stream("dev stream, 2 microphones, N = %d, %s" % (N, pname), ctx_of(synth.BINAURAL, 48000, N, prec), pcm_of(synth.BINAURAL, 48000, N // 2, total, 570))
+        xs3 = [0.05 * m for m in range(3)]
+        for N in (256, 4096):
+            dev_stream("dev stream, 3 microphones, N = %d (any length), %s" % (N, pname), ctx_of(xs3, 48000, N, prec), pcm_of(xs3, 48000, N // 2, total, 571))
+    xs5 = [0.04 * m for m in range(5)]
+    for pname, prec in (precisions[1], precisions[3]):
+        for S in (2, 3):
+            dev_stream("dev stream, ULA16, S = %d, %s" % (S, pname), ctx_of(synth.ULA16, 48000, 1024, prec, S=S), pcm_of(synth.ULA16, 48000, 512, total, 572))
+        for S in (1, 2):
+            dev_stream("dev stream, 5 microphones, S = %d, %s" % (S, pname), ctx_of(xs5, 48000, 1024, prec, S=S), pcm_of(xs5, 48000, 512, total, 573))
+        dev_stream("dev stream, ULA8, 5 degree grid (Dp = 64), %s" % pname, ctx_of(synth.ULA8, 48000, 1024, prec, step=5.0), pcm_of(synth.ULA8, 48000, 512, total, 574))
+        dev_stream("dev stream, ULA8, 0.4 degree grid (D - 2 > 384), %s" % pname, ctx_of(synth.ULA8, 48000, 1024, prec, step=0.4), pcm_of(synth.ULA8, 48000, 512, total, 575))
 
     # the host-pointer entry points
     def host_stream(name, ctx, pcm, convert=lambda x: x, into=None):

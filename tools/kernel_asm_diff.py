@@ -5,7 +5,8 @@
           -o new.s mcarray_amd/csrc/kernels_stream.hip        (the same for the parent's file: old.s)
     python tools/kernel_asm_diff.py old.s new.s
 
-Comments and .loc lines are dropped, so a source edit that moves lines but not instructions compares equal.  Prints the number of functions,
+Comments and .loc lines are dropped and the function index in basic-block labels is normalised, so a source edit that moves lines or
+reorders functions but changes no instruction compares equal.  Prints the number of functions,
 the names of those whose bodies differ, and every kernel whose registers, scratch or workgroup bound differ.  Exit status 1 if a body differs.
 (tools/compare_builds.py compares what two builds COMPUTE on the GPU; this compares what they ARE, and needs none.)"""
 import re
@@ -17,7 +18,8 @@ def functions(path):
     out = {}
     for m in re.finditer(r"^(_Z\w+):\s*(?:;[^\n]*)?\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
         lines = [ln.split(";")[0].rstrip() for ln in m.group(2).split("\n") if not ln.strip().startswith((";", ".loc"))]
-        out[m.group(1)] = "\n".join(lines)
+        # basic-block labels carry the function's index in the file (.LBB2_7), which moves when the order of instantiation does
+        out[m.group(1)] = re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines))
     return out
 
 
