@@ -350,6 +350,24 @@ __device__ __forceinline__ float2 whiten4(float2 z, float &pw, float thr = 4e-30
     asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(zv), "v"(sv));
     return from_v2f(r);
 }
+// The two channels of a pair at one bin: whiten4 of za and of zb, with the two scales in ONE register pair {s_a, s_b} instead of two
+// pairs {s, s} that each cost a copy.  s_a scales za through the low half of src1 (op_sel_hi:[1,0], as whiten4); s_b sits in the high
+// half and therefore rides in src0, whose high half may feed the low result (fft512.h, RULE; as win_hi of steer.h).  The products
+// are whiten4's, operands exchanged: the same bits.
+template <bool NOPHAT = false>
+__device__ __forceinline__ void whiten4_pair(float2 za, float2 zb, float2 &wa, float2 &wb, float thr_a, float thr_b, float unit_a, float unit_b)
+{
+    const v2f av = to_v2f(za), bv = to_v2f(zb);
+    v2f sqa, sqb, ra, rb;
+    asm("v_pk_mul_f32 %0, %1, %1" : "=v"(sqa) : "v"(av));
+    asm("v_pk_mul_f32 %0, %1, %1" : "=v"(sqb) : "v"(bv));
+    const float pwa = sqa.x + sqa.y, pwb = sqb.x + sqb.y;
+    const v2f sv = {NOPHAT ? unit_a : (pwa > thr_a ? __builtin_amdgcn_rsqf(pwa) : 0.f), NOPHAT ? unit_b : (pwb > thr_b ? __builtin_amdgcn_rsqf(pwb) : 0.f)};
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(ra) : "v"(av), "v"(sv));
+    asm("v_pk_mul_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(rb) : "v"(bv), "v"(sv));
+    wa = from_v2f(ra);
+    wb = from_v2f(rb);
+}
 
 // A-row stores: a wave-uniform row pointer, a per-lane byte offset (the lane's residue) and a compile-time element index
 template <bool PL2>
@@ -591,11 +609,14 @@ __global__ __launch_bounds__(512) void k_stft_phat_wave(StftPhatArgs p)      // 
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     const float2 zk = z[dr16(s)], zm = z[dr16(15 - s < 12 ? 15 - s + 4 : 15 - s - 4)];      // Z[k], Z[1024 - k] (slot mate(15 - s))
-                    const float2 a2 = make_float2(zk.x + zm.x, zk.y - zm.y);                               // 2 X_a
-                    const float2 b2 = make_float2(zk.y + zm.y, zm.x - zk.x);                               // 2 X_b
-                    float pwa, pwb;
-                    Xh[2 * pr][s] = whiten4<NOPHAT>(a2, pwa, thr_a, half_a);
-                    Xh[2 * pr + 1][s] = whiten4<NOPHAT>(b2, pwb, thr_b, half_b);
+                    float2 a2, b2;                                                                         // 2 X_a, 2 X_b
+                    mirror_split(zk, zm, a2, b2);
+                    if constexpr (ULA) whiten4_pair<NOPHAT>(a2, b2, Xh[2 * pr][s], Xh[2 * pr + 1][s], thr_a, thr_b, half_a, half_b);
+                    else {                                                         // (the 8-microphone one-plane fp16 kernel off the line holds 234 registers so, 235 with the pair form)
+                        float pwa, pwb;
+                        Xh[2 * pr][s] = whiten4<NOPHAT>(a2, pwa, thr_a, half_a);
+                        Xh[2 * pr + 1][s] = whiten4<NOPHAT>(b2, pwb, thr_b, half_b);
+                    }
                     if (FUSE) {
                         float2 y = pr == 0 ? make_float2(0.f, 0.f) : Yl[64 * s];
                         if (s == 0) y = steer_mac<true>(y, a2, b2, Bu, a2, b2);

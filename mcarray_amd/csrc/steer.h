@@ -72,6 +72,22 @@ __device__ __forceinline__ float2 win_hi(float a, float b, v2f w)
     return from_v2f(r);
 }
 
+// The mirror separation of one bin: zk = Z[k], zm = Z[1024 - k] of a pair's transform give
+//     a2 = 2 X_a = (zk.x + zm.x, zk.y - zm.y),   b2 = 2 X_b = (zk.y + zm.y, zm.x - zk.x)
+// in one packed instruction each: the signs and the crossed halves ride on neg_hi and op_sel, so no register is re-paired first
+// (written as scalar expressions this was three packed adds and two moves per bin).  x - y = x + (-y) and x * 1 + y = x + y are
+// exact, so the bits are those of the scalar expressions.  b2 crosses halves through src0 and src2 of an fma with 1.0, as the
+// transform's multiplications by j do: the low result may not take the high half of src1 (fft512.h, RULE).
+__device__ __forceinline__ void mirror_split(float2 zk, float2 zm, float2 &a2, float2 &b2)
+{
+    const v2f k = to_v2f(zk), m = to_v2f(zm);
+    v2f a, b;
+    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(a) : "v"(k), "v"(m));
+    asm("v_pk_fma_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[0,0,0] neg_hi:[1,0,0]" : "=v"(b) : "v"(k), "v"(m));
+    a2 = from_v2f(a);
+    b2 = from_v2f(b);
+}
+
 // One frame of one array at the bin of its final pick, by one wave: per pair the steps of k_stft_phat_wave up to the separated spectra
 // 2 X_a, 2 X_b -- the same window, balance, transform and mirror exchange, hence the same bits -- and steer_mac / steer_nyquist on
 // them in the same order; the row of Y is replaced.  The one patch routine: k_steer_patch and the patching second pick
@@ -139,6 +155,7 @@ __device__ __forceinline__ void steer_patch_frame(const SteerPatchArgs &p, int a
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             const float2 zk = z[dr16(s)], zm = z[dr16(15 - s < 12 ? 15 - s + 4 : 15 - s - 4)];
+            // (the values of mirror_split, bit for bit; as scalar expressions here: k_steer_patch holds 218 registers with them, 224 with it)
             const float2 a2 = make_float2(zk.x + zm.x, zk.y - zm.y);                               // 2 X_a
             const float2 b2 = make_float2(zk.y + zm.y, zm.x - zk.x);                               // 2 X_b
             const float2 y = pr == 0 ? make_float2(0.f, 0.f) : Y[s];
