@@ -323,6 +323,44 @@ public:
         if (follow && _nTracks == 0) throw MCArrayException("followTracks: configureTracks() first");
         _follow = follow;
     }
+    // Map mode of the tracks (mca_hip_mvdr_tracks_set_map; XYZ geometry, configureTracks() and configureMap() first): every slot holds
+    // an azimuth and an elevation, the own tracks search a patch of the Capon map and the others follow its peaks, associated in both
+    // angles.  seedTracksMap(): one (azimuth, elevation) per slot, NaN leaves the slot.  Per chunk: process, updateTracksMap().
+    // tracksMap(): the directions as the next chunk would take them.  followTracks(true) works as above: in map mode the fill writes the
+    // elevation of every slot beside its azimuth.  configureTracks() leaves map mode.
+    void configureTracksMap(double maxStepElRadians, double minSepElRadians, bool enable = true)
+    {
+        mca_hip_mvdr_tracks_map_config cfg;
+        cfg.struct_size = static_cast<int>(sizeof(cfg));
+        cfg.enable = enable ? 1 : 0;
+        cfg.max_step_el_rad = maxStepElRadians;
+        cfg.min_sep_el_rad = minSepElRadians;
+        check(mca_hip_mvdr_tracks_set_map(_ctx, &cfg));
+    }
+    void seedTracksMap(const std::vector<double> &azRadians, const std::vector<double> &elRadians)
+    {
+        if (static_cast<int>(azRadians.size()) != _nTracks || azRadians.size() != elRadians.size() || _nTracks == 0)
+            throw MCArrayException("seedTracksMap: one azimuth and one elevation per slot of configureTracks()");
+        std::vector<float> a(azRadians.begin(), azRadians.end()), e(elRadians.begin(), elRadians.end());
+        check(mca_hip_mvdr_tracks_seed_map_host(_ctx, 1, a.data(), e.data()));
+    }
+    void updateTracksMap() { check(mca_hip_mvdr_tracks_update_map_host(_ctx, 1, nullptr, nullptr)); }
+    void tracksMap(std::vector<double> &azRadians, std::vector<double> &elRadians, std::vector<int> &alive)
+    {
+        if (_nTracks == 0) throw MCArrayException("tracksMap: configureTracks() first");
+        std::vector<float> a(static_cast<size_t>(_nTracks)), e(static_cast<size_t>(_nTracks));
+        alive.assign(static_cast<size_t>(_nTracks), 0);
+        check(mca_hip_mvdr_tracks_get_map(_ctx, 1, a.data(), e.data(), alive.data(), nullptr, nullptr));
+        // a dead slot repeats the lowest alive one, as the fill does
+        int first = -1;
+        for (int s = _nTracks - 1; s >= 0; --s) first = alive[static_cast<size_t>(s)] ? s : first;
+        azRadians.assign(static_cast<size_t>(_nTracks), 0.0);
+        elRadians.assign(static_cast<size_t>(_nTracks), 0.0);
+        for (int s = 0; s < _nTracks; ++s) {
+            const int src = alive[static_cast<size_t>(s)] ? s : first;
+            if (src >= 0) { azRadians[static_cast<size_t>(s)] = a[static_cast<size_t>(src)]; elRadians[static_cast<size_t>(s)] = e[static_cast<size_t>(src)]; }
+        }
+    }
     // the covariance the stream holds (mca_hip_mvdr_get_covariance): [N/2+1][M][M] complex as (re, im) pairs of doubles
     void covariance(std::vector<double> &phi)
     {

@@ -1012,6 +1012,74 @@ int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *ctx, int n_streams, cons
 int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *ctx, int n_streams, int n_frames, float *doa_rad_dev, void *stream);
 int mca_hip_mvdr_tracks_fill_host(mca_hip_mvdr_ctx *ctx, int n_streams, int n_frames, float *doa_rad);   /* fill_dev through a staging buffer */
 int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *ctx, int n_streams, float *theta, int *alive, int *miss, int *gen);
+/* MAP MODE of the tracks: a second angle per slot, the candidates from the azimuth x elevation Capon map (mca_hip_mvdr_map_*) in the
+ * place of the spectrum's peaks.  Opt-in, XYZ geometry.  Every slot s < n_tracks then holds (theta, eps): theta on the circle as
+ * above (mca_hip_mvdr_set_geometry: reduce, wrap), eps a float clamped to +-1.57079637f with fminf / fmaxf on entry and after every
+ * step.  n_tracks, n_own, max_step_rad, min_sep_rad and hold stay those of mca_hip_mvdr_tracks_configure; the grid, band, weighting and
+ * n_peaks are the map's, as they are at the time of each call.  Everything in float32 is one rounded operation per step or an explicit
+ * fmaf, as above.
+ *
+ * OWN tracks (s < n_own, alive): the estimator runs as above on the held (Psi_s, cpsi_s, Phi, cphi) at g0 = the XYZ geometric vector
+ * of (theta_s, eps_s) -- the steering table of the frames calls with the pair cos((double) eps_s), sin((double) eps_s) where it reads
+ * the context's.  With used, u_k as above and d(theta_i, eps_j, k) the vectors of the map's phasor table:
+ *     T_s[j][i]       = sum over the used bins k of |d(theta_i, eps_j, k)^H u_k|^2 / M
+ *     (phi_az, phi_el) = the cell that maximises T_s among the cells with |wrap(theta_i - theta_s)| <= max_step_rad and
+ *                        |eps_j - eps_s| <= max_step_el_rad (grid values as mca_hip_mvdr_map_get_grid reports them, comparisons in
+ *                        float); the maximum must be > 0 and the lower flat index j n_az + i wins ties; NaN if there is no such cell
+ * The association, per stream, is the one above with pairs:
+ *   1. own slots: s < n_own, alive, (o_az, o_el) both finite: theta_s = wrap(theta_s + clamp(wrap(reduce(o_az) - theta_s), +-max_step_rad)),
+ *      eps_s = clamp(eps_s + clamp(clamp(o_el, +-pi/2_f) - eps_s, +-max_step_el_rad), +-pi/2_f), miss = 0.  An alive own slot whose
+ *      target has an angle that is not finite: miss += 1.
+ *   2. candidates (psi, eta, val) in the order given -- the map's peaks in rank order (peak_az, peak_el, peak_val of mca_hip_mvdr_map_dev)
+ *      in an update: one with !(val > 0) or with an angle that is not finite is skipped; psi = reduce(psi), eta = clamp(eta, +-pi/2_f);
+ *      one inside the box |wrap(psi - theta_s)| <= min_sep_rad && |eta - eps_s| <= min_sep_el_rad of an alive own track is skipped.
+ *      Otherwise, among the alive slots s >= n_own not yet matched in this call with |wrap(psi - theta_s)| <= max_step_rad &&
+ *      |eta - eps_s| <= max_step_el_rad, the one with the least |wrap(psi - theta_s)| + |eta - eps_s| (one rounded addition), the lower
+ *      slot winning ties, takes (theta, eps) = (psi, eta), miss = 0 and is matched.  If there is none the candidate waits as a birth.
+ *   3., 4. as above; a slot born takes (psi, eta), and its Psi and cpsi are cleared.
+ * With every elevation equal the distance is |d theta| + 0 and the result is the association on the circle, bit for bit.  The distance
+ * is in grid angles, not along a great circle: an azimuth gate loses its meaning near eps = +-pi/2, where the map calls a row
+ * degenerate (every azimuth of it is one direction); keep tracked talkers away from the poles of the grid.
+ *
+ * mca_hip_mvdr_tracks_set_map(enable = 1) needs XYZ geometry, tracks configured with enable = 1 and the map configured;
+ * max_step_el_rad and min_sep_el_rad finite and in [0, pi]; anything else is MCA_HIP_ERR_INVALID_ARGUMENT and changes nothing.
+ * Enabling zeroes theta, eps, alive, miss and gen (it synchronises the device); enable = 0 on a context in map mode zeroes them too
+ * and resets the elevation of every look-direction slot to unset.  Everything that disables the tracks leaves map mode: a geometry
+ * change, a caller's mca_hip_mvdr_set_elevations_*, disabling RTF, mca_hip_mvdr_set_max_sources below n_tracks; so does
+ * mca_hip_mvdr_tracks_configure.  mca_hip_mvdr_reset and mca_hip_mvdr_state_load zero eps with the rest; state blobs do not carry
+ * the tracks and keep their versions.  In map mode the calls on one angle -- mca_hip_mvdr_tracks_seed_*, _update_*, _associate_dev --
+ * are refused, for they would leave eps undefined; outside it the _map calls are refused.  mca_hip_mvdr_tracks_get works in both.
+ *   seed_map: az, el [streams][n_tracks]; a slot whose az or el is not finite is left as it is; else theta = reduce(az),
+ *     eps = clamp(el), alive = 1, miss = 0, gen += 1.
+ *   update_map: own_map_dev [streams][n_own][n_el][n_az] float: T_s, or NULL; own_used_dev [streams][n_own][N/2+1] bytes, or NULL (both
+ *     all zero for a dead slot); neither is touched when n_own == 0.  Without own_map_dev only the cells of the search windows are
+ *     evaluated; the tracks are the same bytes either way.
+ *   associate_map: own_az_dev, own_el_dev [streams][n_own] (may be NULL when n_own == 0), n_cand 1 ... 8 candidates per stream.
+ *   get_map: [streams][n_tracks] of each array that is not NULL (it synchronises the device).
+ * mca_hip_mvdr_tracks_fill_dev / _host in map mode write doa_rad as above and, on the same stream, the (cos eps, sin eps) pairs of the
+ * slots s < n_tracks of the streams < n_streams: an alive slot its own eps, a dead slot (theta, eps) of the lowest alive slot, a
+ * stream without an alive slot 0 rad and unset (the context's pair).  The pairs are formed as mca_hip_mvdr_set_elevations_dev forms
+ * them -- the clamp in double, then the device's double cos and sin -- so the fill leaves the bytes that call would leave for the same
+ * angles; unlike that call it does not disable the tracks.  mca_hip_mvdr_get_elevations reports the filled angles.
+ * update_map, fill and get_map change no byte of Phi, tr, Psi, cpsi, cphi or the tails, but Psi and cpsi of a slot at its birth; the
+ * result is a pure function of state and configuration (no atomics), independent of the place in the batch, of n_streams and of the
+ * workspace cap (mca_hip_mvdr_set_rtf_workspace: u and the partial sums are taken in passes of streams under it).  Timing: kernel_id
+ * 9 = the kernels of this mode; the two map kernels of an update count under 8, and an update with n_own == n_tracks launches none. */
+typedef struct {
+    int struct_size;
+    int enable;
+    double max_step_el_rad;  /* [0, pi]: gate and search window in elevation */
+    double min_sep_el_rad;   /* [0, pi]: with min_sep_rad, the box within which a map peak is an own talker */
+} mca_hip_mvdr_tracks_map_config;
+int mca_hip_mvdr_tracks_set_map(mca_hip_mvdr_ctx *ctx, const mca_hip_mvdr_tracks_map_config *cfg);
+int mca_hip_mvdr_tracks_get_map_config(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_tracks_map_config *cfg);
+int mca_hip_mvdr_tracks_seed_map_dev(mca_hip_mvdr_ctx *ctx, int n_streams, const float *az_dev, const float *el_dev, void *stream);
+int mca_hip_mvdr_tracks_seed_map_host(mca_hip_mvdr_ctx *ctx, int n_streams, const float *az, const float *el);
+int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *ctx, int n_streams, float *own_map_dev, unsigned char *own_used_dev, void *stream);
+int mca_hip_mvdr_tracks_update_map_host(mca_hip_mvdr_ctx *ctx, int n_streams, float *own_map, unsigned char *own_used);
+int mca_hip_mvdr_tracks_associate_map_dev(mca_hip_mvdr_ctx *ctx, int n_streams, const float *own_az_dev, const float *own_el_dev, int n_cand,
+                                          const float *cand_az_dev, const float *cand_el_dev, const float *cand_val_dev, void *stream);
+int mca_hip_mvdr_tracks_get_map(mca_hip_mvdr_ctx *ctx, int n_streams, float *theta, float *eps, int *alive, int *miss, int *gen);
 /* The geometry of the steering vectors.  MCA_HIP_MVDR_GEOMETRY_LINEAR_X (the default, and the bytes of every release before this
  * setter): the steering of Beamformer.cpp:59 above, which reads the x coordinate of mic_xyz alone -- right for a line array on the x
  * axis, wrong without an error for any other.  MCA_HIP_MVDR_GEOMETRY_XYZ: all three coordinates of mic_xyz (the context keeps them
@@ -1073,7 +1141,8 @@ int mca_hip_mvdr_get_geometry(const mca_hip_mvdr_ctx *ctx, mca_hip_mvdr_geometry
  * them.  A geometry change that changes mode or elevation resets every slot to unset.  The tracks, the Capon spectrum and its peaks
  * keep the context's one elevation: a set_elevations call -- either one, whatever it carries -- disables the tracks, as a geometry
  * change does, and mca_hip_mvdr_tracks_configure with enable = 1 resets every slot to unset.  The loop with a second angle is
- * mca_hip_mvdr_map_dev -> peak_az_dev as doa_rad, peak_el_dev to mca_hip_mvdr_set_elevations_dev -> the next chunk, with no host step.
+ * mca_hip_mvdr_map_dev -> peak_az_dev as doa_rad, peak_el_dev to mca_hip_mvdr_set_elevations_dev -> the next chunk, with no host step;
+ * with identity per slot it is the tracks' map mode (mca_hip_mvdr_tracks_set_map), whose fill writes the pairs itself.
  * n_streams outside 1 ... max_streams or a NULL array is MCA_HIP_ERR_INVALID_ARGUMENT. */
 int mca_hip_mvdr_set_elevations_host(mca_hip_mvdr_ctx *ctx, int n_streams, const float *elev_rad);
 int mca_hip_mvdr_set_elevations_dev(mca_hip_mvdr_ctx *ctx, int n_streams, const float *elev_rad_dev, void *stream);
@@ -1091,7 +1160,8 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *ctx, const void *blob, long long b
  * other id outside 0 ... 3, as it always did (MCA_HIP_ERR_INVALID_ARGUMENT).  5 = k_mvdr_rtf, by the same rule: it exists on a
  * context that has had RTF enabled at some time.  6 = k_mvdr_estmask, by the same rule (the mask estimator).  7 = the track
  * kernels (mca_hip_mvdr_tracks_*), by the same rule: it exists once tracks have been configured.  8 = both kernels of a
- * mca_hip_mvdr_map_* call, by the same rule: it exists once the map has been configured */
+ * mca_hip_mvdr_map_* call, by the same rule: it exists once the map has been configured.  9 = the kernels of the tracks' map mode
+ * (mca_hip_mvdr_tracks_*_map and the fill in that mode), by the same rule: it exists once map mode has been enabled */
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *ctx, int enable);
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *ctx, int kernel_id, int *launches, double *total_ms);
 

@@ -107,6 +107,15 @@ class MvdrTracksConfig(C.Structure):
     ]
 
 
+class MvdrTracksMapConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("enable", C.c_int),
+        ("max_step_el_rad", C.c_double),
+        ("min_sep_el_rad", C.c_double),
+    ]
+
+
 class MvdrGeometryConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int),
@@ -345,6 +354,14 @@ SYMBOLS = [
     ("mca_hip_mvdr_tracks_fill_dev", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("mca_hip_mvdr_tracks_fill_host", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_fp]),
     ("mca_hip_mvdr_tracks_get", C.c_int, [C.c_void_p, C.c_int, c_fp, c_ip, c_ip, c_ip]),
+    ("mca_hip_mvdr_tracks_set_map", C.c_int, [C.c_void_p, C.POINTER(MvdrTracksMapConfig)]),
+    ("mca_hip_mvdr_tracks_get_map_config", C.c_int, [C.c_void_p, C.POINTER(MvdrTracksMapConfig)]),
+    ("mca_hip_mvdr_tracks_seed_map_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_seed_map_host", C.c_int, [C.c_void_p, C.c_int, c_fp, c_fp]),
+    ("mca_hip_mvdr_tracks_update_map_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_update_map_host", C.c_int, [C.c_void_p, C.c_int, c_fp, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_associate_map_dev", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mca_hip_mvdr_tracks_get_map", C.c_int, [C.c_void_p, C.c_int, c_fp, c_fp, c_ip, c_ip, c_ip]),
     ("mca_hip_mvdr_get_covariance", C.c_int, [C.c_void_p, C.c_int, c_dp]),
     ("mca_hip_mvdr_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("mca_hip_mvdr_get_timing", C.c_int, [C.c_void_p, C.c_int, c_ip, c_dp]),

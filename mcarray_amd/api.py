@@ -892,6 +892,7 @@ class MvdrBeamformer(_StateBlob):
     GEOMETRY_LINEAR_X, GEOMETRY_XYZ = 0, 1
 
     K_ANALYSE, K_SOLVE, K_SYNTH, K_SPECTRUM, K_POSTFILTER, K_RTF, K_ESTMASK, K_TRACKS, K_MAP = 0, 1, 2, 3, 4, 5, 6, 7, 8
+    K_TRACKS_MAP = 9
 
     def __init__(self, sample_rate, mic_positions, fft_size=1024, alpha=0.95, loading=1e-3, max_streams=1, device=0, max_sources=1,
                  geometry="linear_x", elevation_rad=0.0, null_gain=0.0, rtf_nulls=False):
@@ -1495,9 +1496,73 @@ class MvdrBeamformer(_StateBlob):
                                                       ge.ctypes.data_as(ip)))
         return dict(theta=th, alive=al, miss=mi, gen=ge)
 
+    # ---- the tracks' map mode: azimuth and elevation, fed by the Capon map (include/mcarray_hip.h, mca_hip_mvdr_tracks_set_map) ----
+    def configure_tracks_map(self, max_step_el_rad, min_sep_el_rad, enable=True):
+        """map mode of the tracks (geometry "xyz"; configure_tracks() and map_configure() first): every slot holds (theta, eps), the own
+        tracks search a patch of the map within (max_step_rad, max_step_el_rad) and the others follow the map's peaks, associated in
+        both angles; a peak inside the box (min_sep_rad, min_sep_el_rad) of an own track is that talker.  Clears the tracks."""
+        cfg = _lib.MvdrTracksMapConfig(C.sizeof(_lib.MvdrTracksMapConfig), 1 if enable else 0, float(max_step_el_rad), float(min_sep_el_rad))
+        self._check(self._lib.mca_hip_mvdr_tracks_set_map(self.h, C.byref(cfg)))
+
+    def get_tracks_map_config(self):
+        """dict(enable, max_step_el_rad, min_sep_el_rad) as the context holds them"""
+        cfg = _lib.MvdrTracksMapConfig()
+        self._check(self._lib.mca_hip_mvdr_tracks_get_map_config(self.h, C.byref(cfg)))
+        return dict(enable=bool(cfg.enable), max_step_el_rad=cfg.max_step_el_rad, min_sep_el_rad=cfg.min_sep_el_rad)
+
+    def seed_tracks_map(self, az_rad, el_rad):
+        """az_rad, el_rad [streams][n_tracks] (or [n_tracks] for one stream): a finite pair starts a track in that slot, anything else
+        leaves it"""
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(az_rad, dtype=np.float32)))
+        e = np.ascontiguousarray(np.atleast_2d(np.asarray(el_rad, dtype=np.float32)))
+        if a.shape != e.shape:
+            raise MCArrayHipError("az_rad and el_rad must have the same shape")
+        self._check(self._lib.mca_hip_mvdr_tracks_seed_map_host(self.h, a.shape[0], a.ctypes.data_as(_lib.c_fp), e.ctypes.data_as(_lib.c_fp)))
+
+    def seed_tracks_map_dev(self, n_streams, az_rad, el_rad, stream=None):
+        self._check(self._lib.mca_hip_mvdr_tracks_seed_map_dev(self.h, int(n_streams), az_rad.data_ptr(), el_rad.data_ptr(), stream))
+
+    def update_tracks_map(self, n_streams=None, want_map=False):
+        """one update of the tracks of streams 0 ... n_streams - 1 (default: all) in map mode.  want_map: -> dict(own_map float32
+        [A][n_own][n_el][n_az], own_used bool [A][n_own][K]); without it only the cells of the search windows are evaluated"""
+        A = self.max_streams if n_streams is None else int(n_streams)
+        if not want_map:
+            self._check(self._lib.mca_hip_mvdr_tracks_update_map_host(self.h, A, None, None))
+            return None
+        cfgd = getattr(self, "map_config", None) or {}
+        n_own = self.get_tracks_config()["n_own"]
+        m = np.zeros((max(A, 0), n_own, cfgd.get("n_el", 1), cfgd.get("n_az", 1)), dtype=np.float32)
+        used = np.zeros((max(A, 0), n_own, self.K), dtype=np.uint8)
+        self._check(self._lib.mca_hip_mvdr_tracks_update_map_host(self.h, A, m.ctypes.data_as(_lib.c_fp), used.ctypes.data_as(C.c_void_p)))
+        return dict(own_map=m, own_used=used.astype(bool))
+
+    def update_tracks_map_dev(self, n_streams, own_map=None, own_used=None, stream=None):
+        """device tensors (torch, contiguous): own_map float32 [A][n_own][n_el][n_az], own_used uint8 [A][n_own][K]; either may be
+        None; asynchronous on `stream` (a raw hipStream_t or None)"""
+        self._check(self._lib.mca_hip_mvdr_tracks_update_map_dev(self.h, int(n_streams), own_map.data_ptr() if own_map is not None else None,
+                                                                 own_used.data_ptr() if own_used is not None else None, stream))
+
+    def associate_tracks_map_dev(self, n_streams, own_az, own_el, cand_az, cand_el, cand_val, stream=None):
+        """the association alone on candidates of the caller's (device tensors, contiguous float32): own_az / own_el [A][n_own] or
+        None, cand_az / cand_el / cand_val [A][n_cand], n_cand 1 ... 8"""
+        self._check(self._lib.mca_hip_mvdr_tracks_associate_map_dev(self.h, int(n_streams), own_az.data_ptr() if own_az is not None else None,
+                                                                    own_el.data_ptr() if own_el is not None else None, int(cand_az.shape[-1]),
+                                                                    cand_az.data_ptr(), cand_el.data_ptr(), cand_val.data_ptr(), stream))
+
+    def tracks_map(self, n_streams=None):
+        """-> dict(theta, eps float32, alive, miss, gen int32), each [A][n_tracks]; synchronises the device"""
+        A = self.max_streams if n_streams is None else int(n_streams)
+        T = self.get_tracks_config()["n_tracks"]
+        th, ep = (np.zeros((max(A, 0), T), dtype=np.float32) for _ in range(2))
+        al, mi, ge = (np.zeros((max(A, 0), T), dtype=np.int32) for _ in range(3))
+        ip, fp = _lib.c_ip, _lib.c_fp
+        self._check(self._lib.mca_hip_mvdr_tracks_get_map(self.h, A, th.ctypes.data_as(fp), ep.ctypes.data_as(fp), al.ctypes.data_as(ip), mi.ctypes.data_as(ip),
+                                                          ge.ctypes.data_as(ip)))
+        return dict(theta=th, eps=ep, alive=al, miss=mi, gen=ge)
+
     def follow_tracks(self, enable=True):
         """while on, process_sources_dev(..., doa_rad=None) takes its look directions from the tracks: fill_tracks_dev() into a
-        tensor of the context's, on the call's stream, with no host step"""
+        tensor of the context's, on the call's stream, with no host step.  In map mode the fill carries the slots' elevations too"""
         self._follow = bool(enable)
         if not enable:
             self._follow_doa = None

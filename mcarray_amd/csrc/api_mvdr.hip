@@ -2,7 +2,7 @@
 // mca_hip_mvdr_*; BASELINE.json configs[3]; SURVEY A.9 -- no reference counterpart, conventions of Beamformer.cpp:59).
 // Host side only: owns the per-stream state (covariances, their traces, overlap-add tails) and the spectra
 // workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip, kernels_mvdr_estmask.hip,
-// kernels_mvdr_postfilter.hip, kernels_mvdr_spectrum.hip, kernels_mvdr_track.hip and kernels_mvdr_map.hip.  No CPU fallback.
+// kernels_mvdr_postfilter.hip, kernels_mvdr_spectrum.hip, kernels_mvdr_track.hip, kernels_mvdr_trk2.hip and kernels_mvdr_map.hip.  No CPU fallback.
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
 #include "kernels.h"
@@ -99,12 +99,21 @@ struct mca_hip_mvdr_ctx {
     DevBuf<float> d_trk_peak;                       // [2][max_streams][MCA_MAX_SOURCES]: the Capon peaks of an update (angles, values)
     DevBuf<float2> d_trk_T0;                        // [max_streams][MCA_MAX_SOURCES][M][N/64 + 33] phasors of the own tracks
     DevBuf<float> d_trk_part;                       // workspace: partial sums [streams][n_own][chunks][4][Dpad]
+    // the tracks' map mode (mca_hip_mvdr_tracks_set_map, kernels_mvdr_trk2.hip): a second angle per slot, the candidates from the Capon map
+    bool trk_map_on = false;
+    bool trk_map_ever = false;    // enabled at some time: timing slot 9 exists
+    mca_hip_mvdr_tracks_map_config trkm{};
+    DevBuf<float> d_trk_eps;                        // [max_streams][MCA_MAX_SOURCES], beside d_trk_theta
+    DevBuf<float> d_trk2_peak;                      // [3][max_streams][MCA_MAX_SOURCES]: the map's peaks of an update (az, el, values)
+    DevBuf<float2> d_trk2_U;                        // workspace: u [streams of a pass][n_own][chunks][64][M]
+    DevBuf<int> d_trk2_F;                           // workspace: used [streams of a pass][n_own][chunks][64]
+    DevBuf<float> d_trk2_part;                      // workspace: partial sums [streams of a pass][n_own][chunks][4][Dpad]
     StagePool stage;
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[9] = {};
-    double t_ms[9] = {};
+    int t_launches[10] = {};
+    double t_ms[10] = {};
     std::string err;
 };
 
@@ -196,6 +205,13 @@ hipError_t reset_elevations(mca_hip_mvdr_ctx *c)
     return e;
 }
 
+// the tracks end, and their map mode with them: configured anew
+void tracks_off(mca_hip_mvdr_ctx *c)
+{
+    if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }
+    c->trk_map_on = false;
+}
+
 // turns per unit of kk of microphone m towards theta: what the steering tables of the kernels form (mvdr_projection), on the host
 // the XYZ arm: the projection on e(theta, eps) with ce = cos eps, se = sin eps
 double host_projection_xyz(const mca_hip_mvdr_ctx *c, int m, double theta, double ce, double se)
@@ -236,6 +252,7 @@ int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
     VHIP_TRY(c, c->d_cphi.zero_async(st));
     VHIP_TRY(c, c->d_trk_theta.zero_async(st));
     VHIP_TRY(c, c->d_trk_int.zero_async(st));
+    VHIP_TRY(c, c->d_trk_eps.zero_async(st));
     VHIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
@@ -418,7 +435,7 @@ int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
     c->d_tail[0].swap(nt[0]); c->d_tail[1].swap(nt[1]); c->tail_cur = 0;
     c->d_psi.swap(npsi); c->d_cpsi.swap(ncpsi); c->d_pf_A.swap(na);    // (empty for empty where the feature is off)
     c->max_sources = max_sources;
-    if (c->trk_on && max_sources < c->trk.n_tracks) { c->trk_on = false; c->trk.enable = 0; }      // fewer slots than tracks
+    if (c->trk_on && max_sources < c->trk.n_tracks) tracks_off(c);                                  // fewer slots than tracks
     return MCA_HIP_OK;
 }
 
@@ -473,7 +490,7 @@ int mca_hip_mvdr_set_geometry(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_geometry_c
     if (const hipError_t e = reset_elevations(c)) return hip_fail(c, e, "elevations of the look-direction slots");   // unset: the new pair
     c->spec_set = false;                                       // its phasor table and grid are stale (freed by the next configure)
     c->map_set = false;                                        // and so are the map's
-    if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }   // the angles change meaning: configured anew
+    tracks_off(c);                                             // the angles change meaning: configured anew
     return MCA_HIP_OK;
 }
 
@@ -554,7 +571,7 @@ int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_rtf_config *cfg
             c->d_psi.swap(npsi); c->d_cpsi.swap(ncpsi); c->d_cphi.swap(ncphi); c->d_cphi_next.swap(nnext);
         } else {
             c->d_psi.reset(); c->d_cpsi.reset(); c->d_cphi.reset(); c->d_cphi_next.reset(); c->d_D.reset(); c->d_rtf_ones.reset();
-            if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }     // own tracks read Psi and a birth clears it: configured anew
+            tracks_off(c);                                               // own tracks read Psi and a birth clears it: configured anew
         }
         c->rtf_on = on;
         if (on) c->rtf_ever = true;
@@ -1298,7 +1315,7 @@ int elevations_ready(mca_hip_mvdr_ctx *c, int n_streams, const void *ptr)
 // the tracks follow azimuths at the context's elevation: a slot with an elevation of its own ends them, as a geometry change does
 void elevations_disable_tracks(mca_hip_mvdr_ctx *c)
 {
-    if (c->trk_on) { c->trk_on = false; c->trk.enable = 0; }
+    tracks_off(c);
 }
 }  // namespace
 }  // extern "C++"
@@ -1358,6 +1375,17 @@ MvdrTrackState track_state(mca_hip_mvdr_ctx *c)
     const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
     return MvdrTrackState{c->d_trk_theta, c->d_trk_int, c->d_trk_int + n, c->d_trk_int + 2 * n};
 }
+// the calls on one angle: refused in map mode, where they would leave eps undefined
+int tracks_ready_1d(mca_hip_mvdr_ctx *c)
+{
+    if (c->trk_map_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the tracks are in map mode: use the _map call (mca_hip_mvdr_tracks_set_map)");
+    return MCA_HIP_OK;
+}
+MvdrTrk2State track_state_map(mca_hip_mvdr_ctx *c, int first_stream = 0)
+{
+    const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES, o = (size_t)first_stream * MCA_MAX_SOURCES;
+    return MvdrTrk2State{c->d_trk_theta + o, c->d_trk_eps + o, c->d_trk_int + o, c->d_trk_int + n + o, c->d_trk_int + 2 * n + o};
+}
 int tracks_ready(mca_hip_mvdr_ctx *c, int n_streams)
 {
     if (!c->trk_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
@@ -1412,7 +1440,9 @@ int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks
     VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
     VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
     if (cfg->enable == 1) VHIP_TRY(c, reset_elevations(c));   // the tracks live at the context's elevation: every slot back to unset
+    if (c->d_trk_eps) VHIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
     c->trk = *cfg; c->trk_on = cfg->enable == 1;
+    c->trk_map_on = false;                                      // map mode is entered anew (mca_hip_mvdr_tracks_set_map)
     c->trk_ever = true;
     return MCA_HIP_OK;
 }
@@ -1430,6 +1460,7 @@ int mca_hip_mvdr_tracks_seed_dev(mca_hip_mvdr_ctx *c, int n_streams, const float
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (const int rc = tracks_ready_1d(c)) return rc;
     if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -1445,6 +1476,7 @@ int mca_hip_mvdr_tracks_seed_host(mca_hip_mvdr_ctx *c, int n_streams, const floa
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (const int rc = tracks_ready_1d(c)) return rc;
     if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa is NULL");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t bytes = (size_t)n_streams * c->trk.n_tracks * 4;
@@ -1461,6 +1493,7 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (const int rc = tracks_ready_1d(c)) return rc;
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const int n_own = c->trk.n_own, K = c->K, M = c->M, Dpad = c->spec_dpad, nhi = c->N / 64 + 1;
@@ -1504,6 +1537,7 @@ int mca_hip_mvdr_tracks_update_host(mca_hip_mvdr_ctx *c, int n_streams, float *o
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (const int rc = tracks_ready_1d(c)) return rc;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t sb = (size_t)n_streams * c->trk.n_own * c->spec.n_angles * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
     float *d_s = own_spectrum ? (float *)c->stage.get(4, sb) : nullptr;
@@ -1522,6 +1556,7 @@ int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *c, int n_streams, const 
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (const int rc = tracks_ready_1d(c)) return rc;
     if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
     if (!cand_doa || !cand_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_doa_dev / cand_val_dev is NULL");
     if (c->trk.n_own > 0 && !own_doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_doa_dev is NULL on tracks with n_own > 0");
@@ -1544,10 +1579,19 @@ int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *c, int n_streams, int n_frame
     if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    MvdrTrackFillArgs fa{track_state(c), doa_rad, n_streams, n_frames, c->trk.n_tracks};
-    t_begin(c, 7, st);
-    hipLaunchKernelGGL(k_mvdr_track_fill, dim3((unsigned)(((long long)n_streams * n_frames + 255) / 256)), dim3(256), 0, st, fa);
-    t_end(c, st);
+    const dim3 grid((unsigned)(((long long)n_streams * n_frames + 255) / 256));
+    if (c->trk_map_on) {
+        // map mode: the elevations of the slots travel with the azimuths, on the same stream
+        MvdrTrk2FillArgs fa{track_state_map(c), doa_rad, n_streams, n_frames, c->trk.n_tracks, c->d_slot_el, c->d_slot_val, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
+        t_begin(c, 9, st);
+        hipLaunchKernelGGL(k_mvdr_trk2_fill, grid, dim3(256), 0, st, fa);
+        t_end(c, st);
+    } else {
+        MvdrTrackFillArgs fa{track_state(c), doa_rad, n_streams, n_frames, c->trk.n_tracks};
+        t_begin(c, 7, st);
+        hipLaunchKernelGGL(k_mvdr_track_fill, grid, dim3(256), 0, st, fa);
+        t_end(c, st);
+    }
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -1592,6 +1636,233 @@ int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *c, int n_streams, float *theta, in
             for (int a = 0; a < n_streams; ++a)
                 for (int s = 0; s < T; ++s) outs[j][a * T + s] = hi[(size_t)a * MCA_MAX_SOURCES + s];
         }
+    return MCA_HIP_OK;
+}
+
+// ---- the tracks' map mode: azimuth and elevation, fed by the Capon map (kernels_mvdr_trk2.hip) ----
+extern "C++" {
+namespace {
+int tracks_map_ready(mca_hip_mvdr_ctx *c, int n_streams)
+{
+    if (const int rc = tracks_ready(c, n_streams)) return rc;
+    if (!c->trk_map_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_set_map first (with enable = 1)");
+    if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
+    return MCA_HIP_OK;
+}
+// the association's part of the pick kernel's arguments, for the streams from first_stream on
+MvdrTrk2PickArgs trk2_pick_args(mca_hip_mvdr_ctx *c, int first_stream)
+{
+    MvdrTrk2PickArgs pa{};
+    pa.st = track_state_map(c, first_stream);
+    pa.az = c->d_map_az; pa.el = c->d_map_el; pa.n_az = c->map.n_az; pa.n_el = c->map.n_el; pa.Dpad = c->map_dpad;
+    pa.n_tracks = c->trk.n_tracks; pa.n_own = c->trk.n_own; pa.hold = c->trk.hold;
+    pa.max_step = (float)c->trk.max_step_rad; pa.min_sep = (float)c->trk.min_sep_rad;
+    pa.max_step_el = (float)c->trkm.max_step_el_rad; pa.min_sep_el = (float)c->trkm.min_sep_el_rad;
+    pa.slots = c->max_sources; pa.K = c->K; pa.tri = c->tri;
+    if (c->rtf_on) {
+        pa.psi = c->d_psi + (size_t)first_stream * pa.slots * c->K * c->tri;
+        pa.cpsi = c->d_cpsi + (size_t)first_stream * pa.slots * c->K;
+    }
+    return pa;
+}
+}  // namespace
+}  // extern "C++"
+
+int mca_hip_mvdr_tracks_set_map(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks_map_config *cfg)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_tracks_map_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->enable != 0 && cfg->enable != 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
+    if (!std::isfinite(cfg->max_step_el_rad) || cfg->max_step_el_rad < 0.0 || cfg->max_step_el_rad > M_PI)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_step_el_rad must be finite and in [0, pi]");
+    if (!std::isfinite(cfg->min_sep_el_rad) || cfg->min_sep_el_rad < 0.0 || cfg->min_sep_el_rad > M_PI)
+        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_sep_el_rad must be finite and in [0, pi]");
+    if (cfg->enable == 1) {
+        if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map mode needs XYZ geometry (mca_hip_mvdr_set_geometry)");
+        if (!c->trk_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
+        if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first: map mode uses its grid, band and n_peaks");
+    }
+    if (cfg->enable == 0 && !c->trk_map_on) { c->trkm = *cfg; return MCA_HIP_OK; }      // nothing to leave
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    if (!c->d_trk_eps) {
+        DevBuf<float> ne, npk;
+        hipError_t e = ne.alloc(n);
+        if (e == hipSuccess) e = npk.alloc(n * 3);
+        if (e != hipSuccess) return hip_fail(c, e, "track state of the map mode");
+        c->d_trk_eps.swap(ne); c->d_trk2_peak.swap(npk);
+    }
+    // entering and leaving alike: the angles change meaning, so every slot starts from nothing
+    VHIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
+    VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
+    VHIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
+    VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
+    if (cfg->enable == 0) VHIP_TRY(c, reset_elevations(c));    // the tracks on one angle live at the context's elevation
+    c->trkm = *cfg; c->trk_map_on = cfg->enable == 1;
+    if (c->trk_map_on) c->trk_map_ever = true;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_get_map_config(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_tracks_map_config *cfg)
+{
+    if (!c || !cfg) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    *cfg = c->trkm;
+    cfg->struct_size = (int)sizeof(mca_hip_mvdr_tracks_map_config);
+    cfg->enable = c->trk_map_on ? 1 : 0;
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_seed_map_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *az, const float *el, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_map_ready(c, n_streams)) return rc;
+    if (!az || !el) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az_dev / el_dev is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrTrk2SeedArgs sa{track_state_map(c), az, el, n_streams, c->trk.n_tracks};
+    t_begin(c, 9, st);
+    hipLaunchKernelGGL(k_mvdr_trk2_seed, dim3((unsigned)((n_streams * c->trk.n_tracks + 255) / 256)), dim3(256), 0, st, sa);
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_seed_map_host(mca_hip_mvdr_ctx *c, int n_streams, const float *az, const float *el)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_map_ready(c, n_streams)) return rc;
+    if (!az || !el) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az / el is NULL");
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t bytes = (size_t)n_streams * c->trk.n_tracks * 4;
+    float *d_a = (float *)c->stage.get(5, bytes), *d_e = (float *)c->stage.get(6, bytes);
+    if (!d_a || !d_e) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    VHIP_TRY(c, hipMemcpy(d_a, az, bytes, hipMemcpyHostToDevice));
+    VHIP_TRY(c, hipMemcpy(d_e, el, bytes, hipMemcpyHostToDevice));
+    const int rc = mca_hip_mvdr_tracks_seed_map_dev(c, n_streams, d_a, d_e, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float *own_map, unsigned char *own_used, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_map_ready(c, n_streams)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const int n_own = c->trk.n_own, K = c->K, M = c->M, Dpad = c->map_dpad, D = c->map.n_az * c->map.n_el, nhi = c->N / 64 + 1;
+    const int chunk0 = c->map.bin_lo / MVDR_SPEC_CHUNK, n_chunks = c->map.bin_hi / MVDR_SPEC_CHUNK - chunk0 + 1;
+    // the map's peaks: the kernels of mca_hip_mvdr_map_dev (timing slot 8), into the context's own rows.  Not launched where every slot
+    // is an own track: a peak then changes no track
+    const size_t row = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
+    float *pk_az = c->d_trk2_peak, *pk_el = c->d_trk2_peak + row, *pk_val = c->d_trk2_peak + 2 * row;
+    const bool capon = n_own < c->trk.n_tracks;
+    const int n_cand = capon ? c->map.n_peaks : 0;
+    if (capon)
+        if (const int rc = mca_hip_mvdr_map_dev(c, n_streams, nullptr, pk_az, pk_el, pk_val, stream)) return rc;
+    // u, the flags and the partial sums are taken in passes of streams under the cap of the context's workspace
+    // (mca_hip_mvdr_set_rtf_workspace), one stream a pass at the least.  A stream's bytes do not depend on its pass
+    const size_t per_u = (size_t)n_own * n_chunks * MVDR_SPEC_CHUNK * M, per_f = (size_t)n_own * n_chunks * MVDR_SPEC_CHUNK;
+    const size_t per_p = (size_t)n_own * n_chunks * 4 * Dpad, per = 2 * per_u + per_f + per_p;       // (floats)
+    const int pass = n_own > 0 ? (int)std::min<size_t>(std::max<size_t>(1, c->plane_cap_cells * 2 / per), (size_t)n_streams) : n_streams;
+    if (n_own > 0) {
+        if (per_u * pass > c->d_trk2_U.n || per_p * pass > c->d_trk2_part.n) VHIP_TRY(c, hipDeviceSynchronize());
+        if (const int rc = grow_ws(c, c->d_trk2_U, per_u * pass, "steering vectors of the own tracks")) return rc;
+        if (const int rc = grow_ws(c, c->d_trk2_F, per_f * pass, "used flags of the own tracks")) return rc;
+        if (const int rc = grow_ws(c, c->d_trk2_part, per_p * pass, "partial sums of the own tracks")) return rc;
+        if (own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks, the dead slots
+    }
+    const int n_tiles = (Dpad + MVDR_MAP_TILE - 1) / MVDR_MAP_TILE;
+    t_begin(c, 9, st);
+    for (int s0 = 0; s0 < n_streams; s0 += pass) {
+        const int ns = std::min(pass, n_streams - s0);
+        MvdrTrk2PickArgs pa = trk2_pick_args(c, s0);
+        pa.cand_az = pk_az + (size_t)s0 * n_cand; pa.cand_el = pk_el + (size_t)s0 * n_cand; pa.cand_val = pk_val + (size_t)s0 * n_cand; pa.n_cand = n_cand;
+        if (n_own > 0) {
+            const MvdrTrk2State ts = track_state_map(c, s0);
+            float2 *T0 = c->d_trk_T0 + (size_t)s0 * n_own * M * (nhi + 32);
+            MvdrTrk2TablesArgs ta{ts.theta, ts.eps, ts.alive, T0, c->N, M, n_own, geometry_args(c)};
+            hipLaunchKernelGGL(k_mvdr_trk2_tables, dim3((unsigned)(ns * n_own)), dim3(256), 0, st, ta);
+            MvdrTrk2ScanArgs sa{};
+            MvdrTrackSpectrumArgs &sp = sa.s;
+            sp.phi = c->d_phi + (size_t)s0 * K * c->tri; sp.trace = c->d_trace + (size_t)s0 * K; sp.cphi = c->d_cphi + (size_t)s0 * K;
+            sp.psi = c->d_psi + (size_t)s0 * c->max_sources * K * c->tri; sp.cpsi = c->d_cpsi + (size_t)s0 * c->max_sources * K;
+            sp.T0 = T0; sp.T = c->d_map_T; sp.alive = ts.alive; sp.part = c->d_trk2_part;
+            sp.used = own_used ? own_used + (size_t)s0 * n_own * K : nullptr;
+            sp.K = K; sp.M = M; sp.D = D; sp.Dpad = Dpad; sp.nhi = nhi; sp.nph = nhi + 32;
+            sp.bin_lo = c->map.bin_lo; sp.bin_hi = c->map.bin_hi; sp.chunk0 = chunk0; sp.n_chunks = n_chunks;
+            sp.n_own = n_own; sp.slots = c->max_sources;
+            sp.min_share = (float)c->rtf_min_share; sp.iterations = c->rtf_iterations; sp.ref_mic = c->rtf_ref;
+            sa.U = c->d_trk2_U; sa.F = c->d_trk2_F; sa.az = c->d_map_az; sa.el = c->d_map_el; sa.theta = ts.theta; sa.eps = ts.eps;
+            sa.max_step = pa.max_step; sa.max_step_el = pa.max_step_el; sa.n_az = c->map.n_az; sa.n_tiles = n_tiles; sa.n_streams = ns;
+            sa.skip = own_map ? 0 : 1;
+            void *kargs[1] = {&sa};
+            (void)hipLaunchKernel(mvdr_trk2_vectors_kernel((M + 3) / 4), dim3((unsigned)((long long)ns * n_own * n_chunks)), dim3(256), kargs, 0, st);
+            hipLaunchKernelGGL(k_mvdr_trk2_scan, dim3((unsigned)((long long)ns * n_own * n_chunks * n_tiles)), dim3(256), 0, st, sa);
+            pa.part = c->d_trk2_part; pa.n_slices = n_chunks * 4;
+            pa.own_map = own_map ? own_map + (size_t)s0 * n_own * D : nullptr;
+        }
+        hipLaunchKernelGGL(k_mvdr_trk2_pick, dim3(ns), dim3(256), 0, st, pa);
+    }
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_update_map_host(mca_hip_mvdr_ctx *c, int n_streams, float *own_map, unsigned char *own_used)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_map_ready(c, n_streams)) return rc;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t mb = (size_t)n_streams * c->trk.n_own * c->map.n_az * c->map.n_el * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
+    float *d_m = own_map ? (float *)c->stage.get(4, mb) : nullptr;
+    unsigned char *d_u = own_used ? (unsigned char *)c->stage.get(5, ub) : nullptr;
+    if ((own_map && mb && !d_m) || (own_used && ub && !d_u)) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
+    const int rc = mca_hip_mvdr_tracks_update_map_dev(c, n_streams, d_m, d_u, nullptr);
+    if (rc) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    if (d_m) VHIP_TRY(c, hipMemcpy(own_map, d_m, mb, hipMemcpyDeviceToHost));
+    if (d_u) VHIP_TRY(c, hipMemcpy(own_used, d_u, ub, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_associate_map_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *own_az, const float *own_el, int n_cand, const float *cand_az,
+                                          const float *cand_el, const float *cand_val, void *stream)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_map_ready(c, n_streams)) return rc;
+    if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
+    if (!cand_az || !cand_el || !cand_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_az_dev / cand_el_dev / cand_val_dev is NULL");
+    if (c->trk.n_own > 0 && (!own_az || !own_el)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_az_dev / own_el_dev is NULL on tracks with n_own > 0");
+    hipStream_t st = (hipStream_t)stream;
+    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    MvdrTrk2PickArgs pa = trk2_pick_args(c, 0);
+    pa.own_az = c->trk.n_own > 0 ? own_az : nullptr; pa.own_el = c->trk.n_own > 0 ? own_el : nullptr;
+    pa.cand_az = cand_az; pa.cand_el = cand_el; pa.cand_val = cand_val; pa.n_cand = n_cand;
+    t_begin(c, 9, st);
+    hipLaunchKernelGGL(k_mvdr_trk2_pick, dim3(n_streams), dim3(256), 0, st, pa);
+    t_end(c, st);
+    VHIP_TRY(c, hipGetLastError());
+    return MCA_HIP_OK;
+}
+
+int mca_hip_mvdr_tracks_get_map(mca_hip_mvdr_ctx *c, int n_streams, float *theta, float *eps, int *alive, int *miss, int *gen)
+{
+    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = tracks_map_ready(c, n_streams)) return rc;
+    if (!theta && !eps && !alive && !miss && !gen) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "theta, eps, alive, miss and gen are all NULL");
+    if (theta || alive || miss || gen)
+        if (const int rc = mca_hip_mvdr_tracks_get(c, n_streams, theta, alive, miss, gen)) return rc;
+    if (eps) {
+        VHIP_TRY(c, hipSetDevice(c->cfg.device));
+        VHIP_TRY(c, hipDeviceSynchronize());
+        std::vector<float> hf((size_t)n_streams * MCA_MAX_SOURCES);
+        VHIP_TRY(c, hipMemcpy(hf.data(), c->d_trk_eps, hf.size() * 4, hipMemcpyDeviceToHost));
+        const int T = c->trk.n_tracks;
+        for (int a = 0; a < n_streams; ++a)
+            for (int s = 0; s < T; ++s) eps[a * T + s] = hf[(size_t)a * MCA_MAX_SOURCES + s];
+    }
     return MCA_HIP_OK;
 }
 
@@ -1762,6 +2033,7 @@ int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long byt
         // the tracks are no part of a blob: a loaded context starts without them and is seeded again
         VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
         VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
+        if (c->d_trk_eps) VHIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
     }
     return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
 }
@@ -1775,8 +2047,8 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id > 8 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever) ||
-        (kernel_id == 7 && !c->trk_ever) || (kernel_id == 8 && !c->map_ever))
+    if (!c || kernel_id < 0 || kernel_id > 9 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever) ||
+        (kernel_id == 7 && !c->trk_ever) || (kernel_id == 8 && !c->map_ever) || (kernel_id == 9 && !c->trk_map_ever))
         return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));

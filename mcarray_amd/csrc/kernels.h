@@ -123,6 +123,12 @@ const void *mvdr_track_spectrum_kernel(int Q);
 __global__ void k_mvdr_track_pick(MvdrTrackPickArgs p);
 __global__ void k_mvdr_track_fill(MvdrTrackFillArgs p);
 __global__ void k_mvdr_track_seed(MvdrTrackSeedArgs p);
+__global__ void k_mvdr_trk2_tables(MvdrTrk2TablesArgs p);                                   // tracks in azimuth and elevation (kernels_mvdr_trk2.hip)
+const void *mvdr_trk2_vectors_kernel(int Q);
+__global__ void k_mvdr_trk2_scan(MvdrTrk2ScanArgs p);
+__global__ void k_mvdr_trk2_pick(MvdrTrk2PickArgs p);
+__global__ void k_mvdr_trk2_fill(MvdrTrk2FillArgs p);
+__global__ void k_mvdr_trk2_seed(MvdrTrk2SeedArgs p);
 __global__ void k_tgcc_frames(TgccFrameArgs p);
 __global__ void k_tgcc_frame_f64(const double *Lp, const double *Rp, int W, int nd, int rem, double *res, double *index);
 __global__ void k_tgcc_gate(TgccGateArgs p);

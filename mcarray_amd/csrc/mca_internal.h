@@ -776,6 +776,62 @@ struct MvdrTrackSeedArgs {
     int circular;             // XYZ mode: the seed is reduced to [-pi, pi]
 };
 
+// ---- tracks in azimuth and elevation, fed by the Capon map (kernels_mvdr_trk2.hip) ----
+constexpr float MVDR_HALF_PI_F = 1.57079637f;            // (float) pi/2: the elevations of the tracks are clamped to +- this
+struct MvdrTrk2State {
+    float *theta, *eps;       // [streams][MCA_MAX_SOURCES]
+    int *alive, *miss, *gen;  // [streams][MCA_MAX_SOURCES]
+};
+// k_mvdr_trk2_tables: MvdrTrackTablesArgs in XYZ geometry with the pair of eps_s in the place of the context's
+struct MvdrTrk2TablesArgs {
+    const float *theta, *eps; // [streams][MCA_MAX_SOURCES]
+    const int *alive;
+    float2 *T0;               // [streams][n_own][M][nhi + 32]
+    int N, M, n_own;
+    MvdrGeometry geo;
+};
+// k_mvdr_trk2_vectors<Q> and k_mvdr_trk2_scan: s as k_mvdr_track_spectrum<Q> takes it, with T, D and Dpad those of the map's flat list
+// of directions; U and F carry the vectors from the one kernel to the other
+struct MvdrTrk2ScanArgs {
+    MvdrTrackSpectrumArgs s;
+    float2 *U;                // [streams][n_own][n_chunks][64][M] u of the bin, zero where it is not used
+    int *F;                   // [streams][n_own][n_chunks][64] used
+    const float *az, *el;     // [n_az], [n_el]: the map's grid
+    const float *theta, *eps; // [streams][MCA_MAX_SOURCES]: the centre of a slot's search window
+    float max_step, max_step_el;
+    int n_az, n_tiles;        // n_tiles = ceil(Dpad / MVDR_MAP_TILE)
+    int n_streams;            // of the pass; blockIdx.x = ((chunk n_tiles + tile) n_own + slot) n_streams + stream, the stream fastest
+    int skip;                 // the caller takes no map: a tile without a cell of the window is not scanned
+};
+// k_mvdr_trk2_pick: one workgroup per stream.  With part: the window argmax of every own slot; then the association in two angles
+struct MvdrTrk2PickArgs {
+    MvdrTrk2State st;
+    const float *part;        // [streams][n_own][n_slices][Dpad], or NULL: own_az / own_el are given
+    const float *az, *el;     // [n_az], [n_el]
+    int n_az, n_el, n_slices, Dpad;
+    float *own_map;           // [streams][n_own][n_el][n_az] or NULL
+    const float *own_az, *own_el;             // [streams][n_own] (part == NULL; may be NULL when n_own == 0)
+    const float *cand_az, *cand_el, *cand_val;   // [streams][n_cand]
+    int n_cand, n_tracks, n_own, hold;
+    float max_step, min_sep, max_step_el, min_sep_el;
+    float2 *psi;              // [streams][slots][K][tri]
+    float *cpsi;              // [streams][slots][K]
+    int slots, K, tri;
+};
+struct MvdrTrk2FillArgs {
+    MvdrTrk2State st;
+    float *doa_rad;           // [streams][n_frames][n_tracks]
+    int n_streams, n_frames, n_tracks;
+    double2 *slot_el;         // [streams][MCA_MAX_SOURCES] (MvdrGeometry::slot_el)
+    float *slot_val;          // [streams][MCA_MAX_SOURCES]
+    double ce, se;            // the context's pair: a stream without an alive slot
+};
+struct MvdrTrk2SeedArgs {
+    MvdrTrk2State st;
+    const float *az, *el;     // [streams][n_tracks]; a slot with a value that is not finite is left
+    int n_streams, n_tracks;
+};
+
 struct MvdrSynthArgs {
     const float2 *Y;          // [streams][S][n_frames][K]
     int n_frames, N, logH, ft;

@@ -19,7 +19,8 @@ under the same update mask, and both calls' totals; update mask and target masks
 traffic (X and T read, S + 1 masks written) as a share of the measured float4 copy rate, and the auto call's total beside the RTF
 call fed the masks the auto call returned.  --rtf-nulls times the table of DESIGN.md 4.10, one JSON line for two look directions: the solve
 of the RTF call at null gain 0 (k_mvdr_solve_rtf_t) and 100 (k_mvdr_solve_rtf_nulls_t, mca_hip_mvdr_set_rtf_nulls), the CELL nulls solve
-of the masked call at gain 100 under the same update mask, and the calls' totals; masks as in --rtf.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
+of the masked call at gain 100 under the same update mask, and the calls' totals; masks as in --rtf.  --tracks-map times the table of DESIGN.md 4.21, one JSON line for n_own = 1 and one for 2: the update of the tracks in
+map mode on a 72 x 19 map, without and with the whole own map, beside the map call and the auto call.  MCA_HIP_LIB may name an older build of the library (the yardstick of a comparison): the entry
 points it lacks are left unbound, --null-gain must then stay 0, --update none and --postfilter off (as far as the build lacks them)."""
 import argparse
 import json
@@ -260,6 +261,63 @@ def tracks_table(a, fs, N, xs, pcm, st):
         print(json.dumps(row), flush=True)
 
 
+def tracks_map_table(a, fs, N, st):
+    """the rows of DESIGN.md 4.21: the update of the tracks in map mode beside the map call of the same process and beside the auto
+    call that feeds it; a cube of 10 cm, a 72 x 19 map over elevations 0 ... 90 degrees, two look directions of which n_own = 1 and 2
+    follow their own target covariance; without and with the whole own map taken (the tile skip)"""
+    hop = N // 2
+    dev = torch.device("cuda:0")
+    S, n_az, n_el = 2, 72, 19
+    xyz = np.random.default_rng(3).uniform(-0.05, 0.05, (a.mics, 3))
+    L = (a.frames + 1) * hop
+    g = torch.Generator(device=dev); g.manual_seed(1234)
+    pcm = (torch.randn((a.streams, a.mics, L), device=dev, generator=g) * 0.1).contiguous()
+    look_el = [0.5, 0.2]
+    p0 = (synth.noise_source_stream_xyz(xyz, LOOK[0], fs, L, 77, elevation=look_el[0]) + synth.noise_source_stream_xyz(xyz, LOOK[1], fs, L, 78, elevation=look_el[1]))
+    pcm[0] = torch.from_numpy(p0.astype(np.float32)).to(dev)
+    look = torch.tensor(LOOK[:S], device=dev, dtype=torch.float32)
+    doa = look[None, None, :].expand(a.streams, a.frames, S).contiguous()
+    out = torch.empty((a.streams, S, a.frames * hop), device=dev, dtype=torch.float32)
+    peaks = torch.empty((3, a.streams, S), device=dev, dtype=torch.float32)
+    for n_own in (1, 2):
+        bf = api.MvdrBeamformer(fs, xyz, N, max_streams=a.streams, max_sources=S, geometry="xyz")
+        bf.set_rtf(True)
+        bf.set_mask_estimator(True, n_protected=1)
+        bf.configure_spectrum(n_az, n_peaks=S)
+        bf.map_configure(n_az, n_el, 0.0, np.pi / 2, n_peaks=S)
+        bf.set_elevations(np.tile(np.asarray(look_el, dtype=np.float32), (a.streams, 1)))
+        auto = lambda: bf._check(bf._lib.mca_hip_mvdr_sources_frames_auto_dev(bf.h, *api.pcm_layout(pcm), a.streams, a.frames, S, api._ptr(doa), None, None,
+                                                                             api._ptr(out), None, st))
+        auto()
+        bf.configure_tracks(S, n_own, max_step_rad=0.1, min_sep_rad=0.1, hold=3)
+        bf.configure_tracks_map(max_step_el_rad=0.1, min_sep_el_rad=0.1)
+        bf.seed_tracks_map(np.tile(np.asarray(LOOK[:S], dtype=np.float32), (a.streams, 1)), np.tile(np.asarray(look_el, dtype=np.float32), (a.streams, 1)))
+        own_map = torch.empty((a.streams, n_own, n_el, n_az), device=dev, dtype=torch.float32)
+        steps = dict(auto=auto, map=lambda: bf.map_dev(a.streams, peak_az=peaks[0], peak_el=peaks[1], peak_val=peaks[2], stream=st),
+                     update=lambda: bf.update_tracks_map_dev(a.streams, stream=st),
+                     update_with_own_map=lambda: bf.update_tracks_map_dev(a.streams, own_map=own_map, stream=st))
+        row = dict(n_own=n_own, workload="%d streams x %d frames, %d mics, N=%d, %d x %d map" % (a.streams, a.frames, a.mics, N, n_az, n_el))
+        for name in ("auto", "map", "update", "update_with_own_map"):
+            for _ in range(a.warmup):
+                steps[name]()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                steps[name]()
+            torch.cuda.synchronize()
+            row[name + "_ms_per_step"] = (time.perf_counter() - t0) / a.steps * 1e3
+        bf.set_timing(True)
+        for _ in range(a.steps):
+            steps["update"]()
+        for kid, kname in ((bf.K_MAP, "update_map_kernels_ms"), (bf.K_TRACKS_MAP, "update_trk2_kernels_ms")):
+            n, ms = bf.get_timing(kid)
+            row[kname] = ms / max(n, 1)
+        tr = bf.tracks_map()
+        row["own_tracks_with_a_match"] = float((tr["miss"][:, :n_own] == 0).mean())
+        bf.close()
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -277,6 +335,7 @@ def main():
     ap.add_argument("--estmask", action="store_true", help="time the table of the mask estimator (DESIGN.md 4.9)")
     ap.add_argument("--rtf-nulls", action="store_true", help="time the table of the nulls at estimated steering vectors (DESIGN.md 4.10)")
     ap.add_argument("--tracks", action="store_true", help="time the update of the tracks beside the spectrum call and the auto call (DESIGN.md 4.11)")
+    ap.add_argument("--tracks-map", action="store_true", help="time the update of the tracks in map mode beside the map call and the auto call (DESIGN.md 4.21)")
     ap.add_argument("--geometry", choices=["linear_x", "xyz"], default="linear_x",
                     help="xyz: an XYZ context (mca_hip_mvdr_set_geometry) on a uniform circular array of --mics microphones, radius 5 cm (DESIGN.md 4.12)")
     ap.add_argument("--elevation", type=float, default=0.0, help="the elevation of --geometry xyz (radians)")
@@ -290,6 +349,8 @@ def main():
         bind_what_the_library_has()
     fs, N = 48000, 1024
     hop, K = N // 2, N // 2 + 1
+    if a.tracks_map:
+        return tracks_map_table(a, fs, N, torch.cuda.current_stream().cuda_stream)
     xs = [0.32 / a.mics * m for m in range(a.mics)] if a.mics != 16 else synth.ULA16
     if xyz:
         xs = synth.uca(a.mics, 0.05)

@@ -22,7 +22,8 @@ FIELDS = ("vgpr_spill_count", "private_segment_fixed_size")
 # a pattern of its own: tests/test_mvdr_nulls_abi.py counts what the first one matches beside the weighted k_mvdr_solve_t.
 # k_mvdr_estmask<Q>: the mask estimator, which is to stay without scratch as well.  k_mvdr_track*: the tracks of the look directions;
 # k_mvdr_track_spectrum<Q> holds the two covariances of k_mvdr_rtf_steering<Q> and the association keeps its state in LDS.
-DEFAULT_PATTERNS = (r"k_mvdr_solve(?!_rtf)", r"k_mvdr_postfilter", r"k_mvdr_rtf|k_mvdr_solve_rtf", r"k_mvdr_estmask", r"k_mvdr_track")
+# k_mvdr_trk2*: the tracks in azimuth and elevation; k_mvdr_trk2_vectors<Q> is that kernel's estimator on its own.
+DEFAULT_PATTERNS = (r"k_mvdr_solve(?!_rtf)", r"k_mvdr_postfilter", r"k_mvdr_rtf|k_mvdr_solve_rtf", r"k_mvdr_estmask", r"k_mvdr_track", r"k_mvdr_trk2")
 # the template arguments a mangled k_mvdr_solve_t name ends with: NULLS, REUSE, WEIGHT (0 none, 1 per frame, 2 per frame and bin), NOISE
 SOLVE_T = re.compile(r"k_mvdr_solve_tI.*ELb(?P<NULLS>[01])ELb(?P<REUSE>[01])ELNS_10MvdrWeightE(?P<WEIGHT>[012])ELb(?P<NOISE>[01])EEEv")
 KEY = re.compile(r"^(?:  - |    )\.(\w+):\s*(.*)$")       # a key of a kernel's own map (those of its arguments sit deeper)
