@@ -1,11 +1,11 @@
 // api_mvdr.hip -- C ABI of the MVDR-style beamformer with a per-bin spatial covariance (include/mcarray_hip.h,
 // mca_hip_mvdr_*; BASELINE.json configs[3]; SURVEY A.9 -- no reference counterpart, conventions of Beamformer.cpp:59).
-// Host side only: owns the per-stream state (covariances, their traces, overlap-add tails) and the spectra
-// workspace, enqueues the kernels of kernels_mvdr.hip, mvdr_solve.h, kernels_mvdr_rtf.hip, kernels_mvdr_estmask.hip,
-// kernels_mvdr_postfilter.hip, kernels_mvdr_spectrum.hip, kernels_mvdr_track.hip, kernels_mvdr_trk2.hip and kernels_mvdr_map.hip.  No CPU fallback.
+// Host side only: owns the per-stream state and the workspaces, checks a call, fills the argument structs and enqueues the kernels of
+// kernels_mvdr*.hip and mvdr_solve.h.  Every launch is a plan (mvdr_plan.h: kernel form, grid, block, LDS, workspace sizes) handed to the one launch(); the
+// kernels are looked up beside their code (kernels.h); a host-pointer call lists its buffers for the one staging helper (staged).  No CPU fallback.
 #include "../../include/mcarray_hip.h"
-#include "fft512.h"
 #include "kernels.h"
+#include "mvdr_plan.h"
 #include "stage.h"
 #include "state_blob.h"
 
@@ -18,9 +18,13 @@
 
 using namespace mca;
 
-struct mca_hip_mvdr_ctx {
+// the timing slots: kernel_id of mca_hip_mvdr_get_timing (include/mcarray_hip.h)
+enum MvdrTimer { T_ANALYSE, T_SOLVE, T_SYNTH, T_SPECTRUM, T_POSTFILTER, T_RTF, T_ESTMASK, T_TRACKS, T_MAP, T_TRACKS_MAP, T_COUNT, T_NONE = -1 };
+static_assert(T_ANALYSE == 0 && T_SOLVE == 1 && T_SYNTH == 2 && T_SPECTRUM == 3 && T_POSTFILTER == 4 && T_RTF == 5 && T_ESTMASK == 6 && T_TRACKS == 7 &&
+              T_MAP == 8 && T_TRACKS_MAP == 9 && T_COUNT == 10, "the public numbering of kernel_id");
+
+struct mca_hip_mvdr_ctx : MvdrShape {
     mca_hip_mvdr_config cfg{};
-    int N = 0, K = 0, H = 0, logH = 0, M = 0, tri = 0;
     // Device memory: every d_* member owns its buffer (devbuf.h).  A state array is allocated at exactly its state size, so its n
     // is that size (init_state, mvdr_parts); a workspace only grows, and its n is a capacity that no state size is read from.
     DevBuf<float> d_window;
@@ -112,8 +116,8 @@ struct mca_hip_mvdr_ctx {
     bool timing = false;
     struct Ev { int id; hipEvent_t a, b; };
     std::vector<Ev> events;
-    int t_launches[10] = {};
-    double t_ms[10] = {};
+    int t_launches[T_COUNT] = {};
+    double t_ms[T_COUNT] = {};
     std::string err;
 };
 
@@ -151,10 +155,11 @@ void free_mvdr(mca_hip_mvdr_ctx *c)
 // elements of a per-source array [max_streams][slots][row] (slots = 1: of a per-stream array [max_streams][row])
 inline size_t slot_elems(const mca_hip_mvdr_ctx *c, int slots, size_t row) { return (size_t)c->cfg.max_streams * slots * row; }
 
-// a workspace of at least n elements
+// a workspace of at least n elements; wait: the device is waited for before it grows (a call in flight may read the former one)
 template <typename T>
-int grow_ws(mca_hip_mvdr_ctx *c, DevBuf<T> &b, size_t n, const char *what)
+int grow_ws(mca_hip_mvdr_ctx *c, DevBuf<T> &b, size_t n, const char *what, bool wait = false)
 {
+    if (wait && n > b.n) VHIP_TRY(c, hipDeviceSynchronize());
     const hipError_t e = b.grow(n);
     return e == hipSuccess ? MCA_HIP_OK : hip_fail(c, e, what);
 }
@@ -289,7 +294,7 @@ int ensure_estmask_ws(mca_hip_mvdr_ctx *c, size_t rows, int n_sources, bool want
     return MCA_HIP_OK;
 }
 
-void t_begin(mca_hip_mvdr_ctx *c, int id, hipStream_t st)
+void t_begin(mca_hip_mvdr_ctx *c, MvdrTimer id, hipStream_t st)
 {
     if (!c->timing) return;
     mca_hip_mvdr_ctx::Ev ev; ev.id = id;
@@ -303,38 +308,71 @@ void t_end(mca_hip_mvdr_ctx *c, hipStream_t st)
     (void)hipEventRecord(c->events.back().b, st);
 }
 
-// threads per workgroup of the block-cooperative FFT: a radix-4 pass has nch * N/8 work items, two per thread
-int fft_threads(int N, int nch)
+// The one launcher of the MVDR path: a kernel (the lookups of kernels.h, or kptr), a plan's grid, block and dynamic LDS, and the kernel's argument struct (arg2:
+// the second argument of the two kernels that take one).  The attribute is set exactly above the 64 KiB every kernel may have.  slot: the timing slot whose events bracket the
+// launch; T_NONE inside a stage of several launches, which keeps one pair around all of them (t_begin / t_end).  Launch errors surface at the call's hipGetLastError.
+int launch(mca_hip_mvdr_ctx *c, const void *kernel, dim3 grid, dim3 block, int lds, void *args, MvdrTimer slot, hipStream_t st, void *arg2 = nullptr)
 {
-    const int items = nch * (N / 8);
-    int t = 256;
-    while (t < 1024 && t * 2 <= items) t <<= 1;
-    return t;
+    if (lds > 64 * 1024) VHIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    void *kargs[2] = {args, arg2};
+    if (slot != T_NONE) t_begin(c, slot, st);
+    (void)hipLaunchKernel(kernel, grid, block, kargs, (size_t)lds, st);
+    if (slot != T_NONE) t_end(c, st);
+    return MCA_HIP_OK;
+}
+template <class... A> const void *kptr(void (*k)(A...)) { return reinterpret_cast<const void *>(k); }
+
+// The solve kernel of a choice (mvdr_plan.h) and the dynamic LDS of its workgroups, from each family's lookup beside its code (kernels.h); nullptr: not in the build
+const void *mvdr_solve_kernel(const MvdrSolveChoice &k, int &lds)
+{
+    const int Q = k.Q, n_sources = k.S;
+    typedef const void *(*Of)(int, bool, int, bool, int *);
+    static const Of of[3][2] = {{mvdr_solve_kernel_of<MvdrWeight::NONE, false>, nullptr}, {mvdr_solve_kernel_of<MvdrWeight::FRAME, false>, mvdr_solve_kernel_of<MvdrWeight::FRAME, true>},
+                                {mvdr_solve_kernel_of<MvdrWeight::CELL, false>, mvdr_solve_kernel_of<MvdrWeight::CELL, true>}};      // [weight][noise]
+    lds = 0;
+    switch (k.family) {
+    case MvdrSolveFamily::HAND: return mvdr_solve_hand_kernel(Q, k.full);
+    case MvdrSolveFamily::RTF: return k.noise ? mvdr_solve_rtf_kernel_of<true>(Q, k.full, n_sources) : mvdr_solve_rtf_kernel_of<false>(Q, k.full, n_sources);
+    case MvdrSolveFamily::RTF_NULLS: return k.noise ? mvdr_solve_rtf_nulls_kernel_of<true>(Q, n_sources, &lds) : mvdr_solve_rtf_nulls_kernel_of<false>(Q, n_sources, &lds);
+    default: return of[(int)k.weight][k.noise] ? of[(int)k.weight][k.noise](Q, k.full, n_sources, k.nulls, &lds) : nullptr;
+    }
+}
+
+// the staging-pool slots of the host-pointer calls (stage.h).  The pool's buffers are reused across calls by number: the numbers stay
+enum MvdrStageSlot {
+    SG_PCM = 0,           // the frames calls: the samples
+    SG_DOA = 1,           // the frames calls: the look directions
+    SG_OUT_PCM = 2,       // the frames calls: the audio
+    SG_OUT_SPEC = 3,      // the frames calls: the beamformed spectra
+    SG_SCAN = 4,          // spectrum: the spectrum; map: the map; tracks update: own_spectrum; map-mode update: own_map
+    SG_AUX1 = 5,          // spectrum: peak_doa; map: peak_az; both tracks updates: own_used; map-mode seed: az
+    SG_AUX2 = 6,          // spectrum: peak_val; map: peak_el; tracks seed and fill: doa; map-mode seed: el
+    SG_WEIGHTS = 7,       // the frames calls: the update weights per frame; map: peak_val
+    SG_UPDATE_MASK = 8,   // the frames calls: the update mask per cell, taken or (auto call) handed back
+    SG_TARGET_MASK = 9,   // the frames calls: the target masks, taken or (auto call) handed back
+};
+static_assert(SG_TARGET_MASK + 1 == StagePool::N, "a slot per buffer of the pool");
+// One buffer of a host-pointer call: host NULL: an optional one the caller leaves out, nothing staged; bytes 0: nothing staged, no error
+enum StageDir { STAGE_IN = 1, STAGE_OUT = 2 };
+struct StageBuf { MvdrStageSlot slot; const void *host; size_t bytes; int dir; void *dev; };
+// A host-pointer call on its listed buffers: the device copies, the inputs copied in the list's order, the _dev call on the null
+// stream (it reads StageBuf::dev), the wait, the outputs copied in the list's order
+template <size_t NB, class DevCall>
+int staged(mca_hip_mvdr_ctx *c, StageBuf (&bufs)[NB], DevCall &&dev_call)
+{
+    for (StageBuf &b : bufs)
+        if (b.host && b.bytes && !(b.dev = c->stage.get(b.slot, b.bytes)))
+            return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, NB == 1 ? "device staging buffer for the host-pointer call" : "device staging buffers for the host-pointer call");
+    for (StageBuf &b : bufs)
+        if (b.dev && (b.dir & STAGE_IN)) VHIP_TRY(c, hipMemcpy(b.dev, b.host, b.bytes, hipMemcpyHostToDevice));
+    if (const int rc = dev_call()) return rc;
+    VHIP_TRY(c, hipDeviceSynchronize());
+    for (StageBuf &b : bufs)
+        if (b.dev && (b.dir & STAGE_OUT)) VHIP_TRY(c, hipMemcpy(const_cast<void *>(b.host), b.dev, b.bytes, hipMemcpyDeviceToHost));
+    return MCA_HIP_OK;
 }
 
 }  // namespace
-
-namespace mca {
-
-// The solve kernel of a call (kernels.h): the hand-written kernel of kernels_mvdr.hip for the single look direction without weights, an
-// instantiation of k_mvdr_solve_t (mvdr_solve.h) for everything else.  Under the nulls one instantiation serves M = 4Q and M < 4Q.
-const void *mvdr_solve_kernel(int Q, bool full, int S, bool nulls, MvdrWeight w, bool noise, int *lds_bytes)
-{
-    *lds_bytes = 0;
-    if (mvdr_solve_hand_written(S, w, noise)) {
-        const void *k[4][2] = {{(const void *)k_mvdr_solve<1, false>, (const void *)k_mvdr_solve<1, true>}, {(const void *)k_mvdr_solve<2, false>, (const void *)k_mvdr_solve<2, true>},
-                               {(const void *)k_mvdr_solve<3, false>, (const void *)k_mvdr_solve<3, true>}, {(const void *)k_mvdr_solve<4, false>, (const void *)k_mvdr_solve<4, true>}};
-        return Q >= 1 && Q <= 4 ? k[Q - 1][full] : nullptr;
-    }
-    if (nulls) full = false;
-    switch (w) {
-    case MvdrWeight::NONE: return noise ? nullptr : mvdr_solve_kernel_of<MvdrWeight::NONE, false>(Q, full, S, nulls, lds_bytes);
-    case MvdrWeight::FRAME: return noise ? mvdr_solve_kernel_of<MvdrWeight::FRAME, true>(Q, full, S, nulls, lds_bytes) : mvdr_solve_kernel_of<MvdrWeight::FRAME, false>(Q, full, S, nulls, lds_bytes);
-    default: return noise ? mvdr_solve_kernel_of<MvdrWeight::CELL, true>(Q, full, S, nulls, lds_bytes) : mvdr_solve_kernel_of<MvdrWeight::CELL, false>(Q, full, S, nulls, lds_bytes);
-    }
-}
-
-}  // namespace mca
 
 extern "C" {
 
@@ -363,7 +401,7 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     mca_hip_mvdr_ctx *c = new mca_hip_mvdr_ctx();
     c->cfg = *cfg; c->cfg.mic_xyz = nullptr;
     c->rtf_alpha = cfg->alpha;
-    c->N = cfg->fft_size; c->H = c->N / 2; c->K = c->H + 1; c->M = cfg->n_mics; c->tri = c->M * (c->M + 1) / 2;
+    c->N = cfg->fft_size; c->H = c->N / 2; c->K = c->H + 1; c->M = cfg->n_mics; c->tri = c->M * (c->M + 1) / 2; c->max_streams = cfg->max_streams;
     c->em_bin_hi = c->N / 2;
     while ((1 << c->logH) < c->H) ++c->logH;
     std::vector<float> win(c->N);
@@ -646,40 +684,24 @@ struct MvdrCall {
     const float *tmask = nullptr;
     bool rtf = false, est = false;
     float *em_update = nullptr, *em_target = nullptr, *out_pcm = nullptr, *out_spec = nullptr;
+    // the plain call of make_call with update weights per frame; with an update mask per cell; as the RTF call; as the auto call on a context with or without RTF
+    MvdrCall weighted(const float *w) const { MvdrCall q = *this; q.update = w; return q; }
+    MvdrCall with_mask(const float *um) const { MvdrCall q = weighted(um); q.masked = true; return q; }
+    MvdrCall with_rtf(const float *um, const float *tm) const { MvdrCall q = with_mask(um); q.tmask = tm; q.rtf = true; return q; }
+    MvdrCall estimating(bool rtf_on, float *um_out, float *tm_out) const { MvdrCall q = with_mask(nullptr); q.rtf = rtf_on; q.est = true; q.em_update = um_out; q.em_target = tm_out; return q; }
 };
 
 // the analysis (timing slot 0): PCM -> X, and the steering tables T of doa [streams][F][n_sources]
 int launch_analyse(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, const MvdrCall &q, hipStream_t st)
 {
-    const int n_streams = q.n_streams, n_frames = q.n_frames;
     MvdrAnalyseArgs aa{};
-    aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = n_frames;
+    aa.pcm = pcm; aa.stream_stride = stream_stride; aa.mic_stride = mic_stride; aa.n_frames = q.n_frames;
     aa.N = c->N; aa.logH = c->logH; aa.M = c->M; aa.S = q.n_sources; aa.window = c->d_window; aa.tw = c->d_tw; aa.doa_rad = q.doa;
     aa.X = c->d_X; aa.T = c->d_T; aa.mic_x = c->d_micx; aa.geo = geometry_args(c);
     aa.unit = (double)c->cfg.sample_rate / (double)c->N / 346.1;                      // Beamformer.cpp:59 without 2 pi
-    t_begin(c, 0, st);
-    if (c->N == FFT_N) {
-        // 1024-sample frames: wave-level FFT, one wave per channel, eight channels per pass
-        int fpb = 8;
-        while (fpb > 1 && (long long)n_streams * ((n_frames + fpb - 1) / fpb) < 1024) fpb >>= 1;
-        const size_t smem1 = (size_t)(8 * 580 + TW_WORDS) * sizeof(float2);
-        VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_analyse_1024), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
-        hipLaunchKernelGGL(k_mvdr_analyse_1024, dim3((n_frames + fpb - 1) / fpb, n_streams), dim3(512), smem1, st, aa, fpb);
-    } else if (c->N == 512) {
-        // 512-sample frames: two channels per wave pass (kernels_stream.hip)
-        int fpb = 8;
-        while (fpb > 1 && (long long)n_streams * ((n_frames + fpb - 1) / fpb) < 1024) fpb >>= 1;
-        const size_t smem1 = (size_t)(16 * 258 + 8 * FFT_SCRATCH + TW_WIN) * sizeof(float2);
-        VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_analyse_512), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
-        hipLaunchKernelGGL(k_mvdr_analyse_512, dim3((n_frames + fpb - 1) / fpb, n_streams), dim3(512), smem1, st, aa, fpb);
-    } else {
-        const size_t smem1 = (size_t)c->M * (c->H + 1) * sizeof(float2);
-        if (smem1 > 64 * 1024)
-            VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_analyse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
-        hipLaunchKernelGGL(k_mvdr_analyse, dim3(n_frames, n_streams), dim3(fft_threads(c->N, c->M)), smem1, st, aa);
-    }
-    t_end(c, st);
-    return MCA_HIP_OK;
+    MvdrAnalysePlan p = plan_mvdr_analyse(*c, q.n_streams, q.n_frames);
+    const void *const kernels[] = {kptr(k_mvdr_analyse), kptr(k_mvdr_analyse_1024), kptr(k_mvdr_analyse_512)};      // (in the order of MvdrAnalyseFamily)
+    return launch(c, kernels[(int)p.family], p.l.grid, p.l.block, p.l.lds, &aa, T_ANALYSE, st, &p.fpb);
 }
 
 // the solve (timing slot 1): X, T -> Y, the covariance and, for the post-filter, the noise plane
@@ -691,60 +713,36 @@ int launch_solve(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStream_t 
     const bool rtf = q.rtf;
     if (!rtf) n_loop = n_frames;
     MvdrSolveArgs sa{};
-    sa.X = c->d_X; sa.T = c->d_T;
-    sa.n_frames = n_frames; sa.K = c->K; sa.M = c->M;
-    sa.alpha = (float)c->cfg.alpha; sa.one_minus_alpha = (float)(1.0 - c->cfg.alpha);
-    sa.loading_over_m = (float)(c->cfg.loading / c->M);
-    sa.phi = c->d_phi; sa.trace = c->d_trace; sa.Y = Y;
-    sa.n_streams = n_streams; sa.S = n_sources;
+    sa.X = c->d_X; sa.T = c->d_T; sa.n_frames = n_frames; sa.K = c->K; sa.M = c->M; sa.null_gain = (float)c->null_gain;
+    sa.alpha = (float)c->cfg.alpha; sa.one_minus_alpha = (float)(1.0 - c->cfg.alpha); sa.loading_over_m = (float)(c->cfg.loading / c->M);
+    sa.phi = c->d_phi; sa.trace = c->d_trace; sa.Y = Y; sa.n_streams = n_streams; sa.S = n_sources;
     // the kernels that store the noise plane take weights: a call without them passes ones, whose bytes are those of no weights
-    sa.update = update ? update : c->pf_on ? c->d_pf_ones.p : nullptr;
-    sa.null_gain = (float)c->null_gain;
-    sa.pn = c->pf_on ? c->d_pf_pn.p : nullptr;
-    const bool nulls = n_sources > 1 && sa.null_gain > 0.f;                           // a gain that rounds to 0 in fp32 is gain 0
-    const int Q = (c->M + 3) / 4;                                                     // row slots per lane
-    int lds = 0;
-    const void *kernel;
+    sa.update = update ? update : c->pf_on ? c->d_pf_ones.p : nullptr; sa.pn = c->pf_on ? c->d_pf_pn.p : nullptr;
+    const MvdrSolveChoice choice = plan_mvdr_solve_choice(*c, rtf, n_sources, c->null_gain, update != nullptr, q.masked, c->pf_on);
     if (rtf) {
-        // the right-hand sides come from the steering plane; a weight per cell always (ones for a call without an update mask)
+        // the right-hand sides come from the steering plane; a weight per cell always (ones for a call without an update mask).  Nulls at the
+        // vectors of the plane (mvdr_frames_dev lets a gain through only under mca_hip_mvdr_set_rtf_nulls); else the RTF kernels
         sa.D = c->d_D; sa.n_loop = n_loop;
         sa.update = (update ? update : c->d_rtf_ones.p) + (size_t)f0 * c->K;
         sa.X += (size_t)f0 * c->K * c->M; sa.Y += (size_t)f0 * c->K;
         if (sa.pn) sa.pn += (size_t)f0 * c->K;
-        // nulls at the vectors of the plane (mvdr_frames_dev lets a gain through only under mca_hip_mvdr_set_rtf_nulls); else the RTF kernels
-        if (nulls) kernel = c->pf_on ? mvdr_solve_rtf_nulls_kernel_of<true>(Q, n_sources, &lds) : mvdr_solve_rtf_nulls_kernel_of<false>(Q, n_sources, &lds);
-        else kernel = c->pf_on ? mvdr_solve_rtf_kernel_of<true>(Q, c->M == 4 * Q, n_sources) : mvdr_solve_rtf_kernel_of<false>(Q, c->M == 4 * Q, n_sources);
-    } else
-        kernel = mvdr_solve_kernel(Q, c->M == 4 * Q, n_sources, nulls, !sa.update ? MvdrWeight::NONE : update && q.masked ? MvdrWeight::CELL : MvdrWeight::FRAME,
-                                   c->pf_on, &lds);
-    if (!kernel) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
-    auto launch = [&](long long pid0, long long n_prob, int pieces) {
-        sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
-        // an unsplit launch updates the state in place; the pieces of a split one all read the entry state, so the last piece
-        // writes the exit state to a scratch copy that is moved over behind the launch
-        if (pieces > 1) { sa.phi_out = c->d_phi_tail; sa.trace_out = c->d_trace_tail; sa.out_base = pid0; }
-        else { sa.phi_out = c->d_phi; sa.trace_out = c->d_trace; sa.out_base = 0; }
-        void *kargs[1] = {&sa};
-        (void)hipLaunchKernel(kernel, dim3((unsigned)((n_prob + 63) / 64 * pieces)), dim3(256), kargs, (size_t)lds, st);
-    };
-    // 512 workgroups are resident (two per CU at 253 VGPRs) and all take the same time: the workgroups behind the last whole
-    // round (256 streams x 513 bins: 4 of 2052) would hold the GPU for a round of their own.  They go in a second launch,
-    // cut along the FRAMES into pieces that each repeat the (cheap) covariance recursion of the frames before their own.
-    const long long n_prob = (long long)n_streams * c->K, n_wg = (n_prob + 63) / 64;
-    const long long rem_wg = n_wg % 512;
-    int pieces = 1;
-    if (n_wg > 512 && rem_wg > 0 && rem_wg <= 128) {
-        while (pieces < 8 && rem_wg * pieces * 2 <= 512 && n_loop / (pieces * 2) >= 4) pieces *= 2;
     }
-    t_begin(c, 1, st);
-    if (pieces > 1 && n_wg > 512) {
-        const long long main_prob = (n_wg - rem_wg) * 64, tail_prob = n_prob - main_prob;       // tail_prob <= 128 x 64: the scratch copy's size
-        launch(0, main_prob, 1);
-        launch(main_prob, tail_prob, pieces);
-        VHIP_TRY(c, hipMemcpyAsync(c->d_phi + main_prob * c->tri, c->d_phi_tail, (size_t)tail_prob * c->tri * sizeof(float2), hipMemcpyDeviceToDevice, st));
-        VHIP_TRY(c, hipMemcpyAsync(c->d_trace + main_prob, c->d_trace_tail, (size_t)tail_prob * 4, hipMemcpyDeviceToDevice, st));
-    } else {
-        launch(0, n_prob, 1);
+    int lds = 0;                                                // the lookup's; the plan's (mvdr_solve_lds) is what the CPU table pins: one value
+    const void *const kernel = mvdr_solve_kernel(choice, lds);
+    if (!kernel || lds != mvdr_solve_lds(choice)) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
+    const MvdrSolveSplit sp = plan_mvdr_solve_split(*c, n_streams, n_loop);
+    auto piece = [&](long long pid0, long long n_prob, int pieces, dim3 grid) {
+        sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
+        if (pieces > 1) { sa.phi_out = c->d_phi_tail; sa.trace_out = c->d_trace_tail; sa.out_base = pid0; }      // the scratch copy (MvdrSolveSplit)
+        else { sa.phi_out = c->d_phi; sa.trace_out = c->d_trace; sa.out_base = 0; }
+        return launch(c, kernel, grid, sp.block, lds, &sa, T_NONE, st);
+    };
+    t_begin(c, T_SOLVE, st);
+    piece(0, sp.main_prob, 1, sp.grid);
+    if (sp.scratch) {
+        piece(sp.main_prob, sp.tail_prob, sp.pieces, sp.tail_grid);
+        VHIP_TRY(c, hipMemcpyAsync(c->d_phi + sp.main_prob * c->tri, c->d_phi_tail, (size_t)sp.tail_prob * c->tri * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        VHIP_TRY(c, hipMemcpyAsync(c->d_trace + sp.main_prob, c->d_trace_tail, (size_t)sp.tail_prob * 4, hipMemcpyDeviceToDevice, st));
     }
     t_end(c, st);
     return MCA_HIP_OK;
@@ -768,15 +766,9 @@ int launch_rtf(mca_hip_mvdr_ctx *c, const MvdrCall &q, hipStream_t st, int f0, i
     ra.alpha = (float)c->cfg.alpha; ra.one_minus_alpha = (float)(1.0 - c->cfg.alpha);
     ra.talpha = (float)c->rtf_alpha; ra.one_minus_talpha = (float)(1.0 - c->rtf_alpha);
     ra.min_share = (float)c->rtf_min_share; ra.iterations = c->rtf_iterations; ra.ref_mic = c->rtf_ref;
-    ra.phi = c->d_phi; ra.trace = c->d_trace; ra.psi = c->d_psi; ra.cpsi = c->d_cpsi; ra.cphi_in = c->d_cphi; ra.cphi_out = c->d_cphi_next;
-    ra.D = c->d_D;
-    const int Q = (c->M + 3) / 4;
-    const void *kernel = mvdr_rtf_kernel(Q, false);
-    const long long n_prob = (long long)n_streams * n_sources * c->K;
-    void *kargs[1] = {&ra};
-    t_begin(c, 5, st);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)((n_prob + 63) / 64)), dim3(256), kargs, 0, st);
-    t_end(c, st);
+    ra.phi = c->d_phi; ra.trace = c->d_trace; ra.psi = c->d_psi; ra.cpsi = c->d_cpsi; ra.cphi_in = c->d_cphi; ra.cphi_out = c->d_cphi_next; ra.D = c->d_D;
+    const MvdrLaunch l = plan_mvdr_rtf(*c, n_streams, n_sources, n_frames, c->plane_cap_cells).l;
+    launch(c, mvdr_rtf_kernel(c->Q(), false), l.grid, l.block, l.lds, &ra, T_RTF, st);
     VHIP_TRY(c, hipMemcpyAsync(c->d_cphi, c->d_cphi_next, (size_t)n_streams * c->K * 4, hipMemcpyDeviceToDevice, st));
     return MCA_HIP_OK;
 }
@@ -787,38 +779,28 @@ int launch_estmask(mca_hip_mvdr_ctx *c, const MvdrCall &q, hipStream_t st)
 {
     const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     MvdrEstmaskArgs ea{};
-    ea.X = c->d_X; ea.T = c->d_T;
-    ea.n_streams = n_streams; ea.n_frames = n_frames; ea.K = c->K; ea.M = c->M; ea.S = n_sources;
+    ea.X = c->d_X; ea.T = c->d_T; ea.n_streams = n_streams; ea.n_frames = n_frames; ea.K = c->K; ea.M = c->M; ea.S = n_sources;
     ea.bin_lo = c->em_bin_lo; ea.bin_hi = c->em_bin_hi;
     ea.n_protected = c->em_protected == 0 || c->em_protected > n_sources ? n_sources : c->em_protected;
     ea.coherence_lo = (float)c->em_lo; ea.coherence_span = (float)(c->em_hi - c->em_lo);
     ea.update = q.em_update; ea.target = q.em_target;
-    const void *kernel = mvdr_estmask_kernel((c->M + 3) / 4);
-    const long long cells = (long long)n_streams * n_frames * c->K;
-    void *kargs[1] = {&ea};
-    t_begin(c, 6, st);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)((cells + 63) / 64)), dim3(256), kargs, 0, st);
-    t_end(c, st);
-    return MCA_HIP_OK;
+    const MvdrLaunch l = plan_mvdr_estmask(*c, n_streams, n_frames);
+    return launch(c, mvdr_estmask_kernel(c->Q()), l.grid, l.block, l.lds, &ea, T_ESTMASK, st);
 }
 
 // the post-filter (timing slot 4): Z = G Y in place, between the solve and the synthesis
 int launch_postfilter(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStream_t st)
 {
     const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
-    // A slot the call leaves out restarts from silence, whether the call has out_pcm or not; the kernel touches only the slots
-    // below n_sources
+    // A slot the call leaves out restarts from silence, whether the call has out_pcm or not; the kernel touches only the slots below n_sources
     VHIP_TRY(c, clear_unused_slots(c, c->d_pf_A.p, c->K, n_sources, n_streams, st));
     MvdrPostfilterArgs fa{};
     fa.Y = Y; fa.pn = c->d_pf_pn; fa.A = c->d_pf_A;
     fa.n_streams = n_streams; fa.S = n_sources; fa.slots = c->max_sources; fa.n_frames = n_frames; fa.K = c->K;
     fa.smoothing = (float)c->pf_smoothing; fa.one_minus_smoothing = (float)(1.0 - c->pf_smoothing);
     fa.gain_floor = (float)c->pf_gain_floor; fa.noise_scale = (float)c->pf_noise_scale;
-    const long long cells = (long long)n_streams * n_sources * c->K;
-    t_begin(c, 4, st);
-    hipLaunchKernelGGL(k_mvdr_postfilter, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fa);
-    t_end(c, st);
-    return MCA_HIP_OK;
+    const MvdrLaunch l = plan_mvdr_postfilter(*c, n_streams, n_sources);
+    return launch(c, kptr(k_mvdr_postfilter), l.grid, l.block, l.lds, &fa, T_POSTFILTER, st);
 }
 
 // the synthesis (timing slot 2): Y -> out_pcm [streams][n_sources][F hop], and the overlap-add tails
@@ -826,21 +808,13 @@ int launch_synth(mca_hip_mvdr_ctx *c, const MvdrCall &q, const float2 *Y, hipStr
 {
     const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     MvdrSynthArgs ya{};
-    ya.Y = Y; ya.n_frames = n_frames; ya.N = c->N; ya.logH = c->logH; ya.tw = c->d_tw;
-    ya.S = n_sources; ya.tail_slots = c->max_sources;
-    const int n_out = n_streams * n_sources;                                          // one inverse transform + overlap-add each
-    ya.ft = 16;
-    while (ya.ft > 2 && (long long)n_out * ((n_frames + ya.ft - 1) / ya.ft) < 1024) ya.ft >>= 1;
+    const MvdrSynthPlan p = plan_mvdr_synth(*c, n_streams, n_sources, n_frames);
+    ya.Y = Y; ya.n_frames = n_frames; ya.N = c->N; ya.logH = c->logH; ya.tw = c->d_tw; ya.S = n_sources; ya.tail_slots = c->max_sources; ya.ft = p.ft;
     ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = q.out_pcm;
-    const size_t smem3 = (size_t)(c->H + 1) * sizeof(float2) + (size_t)c->H * 4;
-    if (smem3 > 64 * 1024)
-        VHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mvdr_synth), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3));
     // a slot the call leaves out restarts from silence.  The kernel writes only the slots below n_sources, so the clear goes
     // first: if it fails, nothing has touched the tails yet and tail_cur still names the valid ones
     VHIP_TRY(c, clear_unused_slots(c, ya.tail_out, c->H, n_sources, n_streams, st));
-    t_begin(c, 2, st);
-    hipLaunchKernelGGL(k_mvdr_synth, dim3((n_frames + ya.ft - 1) / ya.ft, n_out), dim3(c->H >= 1024 ? 512 : 256), smem3, st, ya);
-    t_end(c, st);
+    if (const int rc = launch(c, kptr(k_mvdr_synth), p.l.grid, p.l.block, p.l.lds, &ya, T_SYNTH, st)) return rc;
     c->tail_cur ^= 1;
     return MCA_HIP_OK;
 }
@@ -869,15 +843,8 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     if (q.out_spec && (reinterpret_cast<uintptr_t>(q.out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    // the steering plane of an RTF call holds fc frames: all of them, or as many as the workspace cap takes (how a stream is cut does not change bytes)
-    int fc = n_frames;
-    if (q.rtf) {
-        const size_t per_frame = (size_t)n_streams * n_sources * c->K * c->M;
-        if (per_frame * n_frames > c->plane_cap_cells) {
-            const int fmax = (int)std::max<size_t>(1, c->plane_cap_cells / per_frame), chunks = (n_frames + fmax - 1) / fmax;
-            fc = (n_frames + chunks - 1) / chunks;          // chunks of equal length, the last one shorter at most
-        }
-    }
+    // the steering plane of an RTF call holds fc frames: all of them, or as many as the workspace cap takes
+    const int fc = q.rtf ? plan_mvdr_rtf(*c, n_streams, n_sources, n_frames, c->plane_cap_cells).fc : n_frames;
     int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !q.update && !q.est, q.rtf, (size_t)n_streams * fc);
     if (rc) return rc;
     if (q.est && (rc = ensure_estmask_ws(c, (size_t)n_streams * n_frames, n_sources, !q.em_update, q.rtf && !q.em_target))) return rc;
@@ -913,33 +880,25 @@ int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, const MvdrCall &q)
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long ms = (long long)(n_frames + 1) * c->H, ss = ms * c->M;
     const size_t nf = (size_t)n_streams * n_frames * n_sources;
-    const size_t nu = (size_t)n_streams * n_frames * (q.masked ? (size_t)c->K : 1);
-    auto stage = [&](int slot, const void *host, size_t bytes) { return host ? (float *)c->stage.get(slot, bytes) : nullptr; };
-    MvdrCall d = q;                                             // the same call on the staged copies
-    float *d_pcm = stage(0, pcm, (size_t)ss * n_streams * 4), *d_doa = stage(1, q.doa, nf * 4);
-    d.doa = d_doa;
-    d.out_pcm = stage(2, q.out_pcm, nf * c->H * 4);
-    d.out_spec = stage(3, q.out_spec, nf * c->K * 8);
-    float *d_upd = stage(q.masked ? 8 : 7, q.update, nu * 4);   // (slots 4 ... 6: the spectrum's; 8: the mask's own)
-    float *d_tm = stage(9, q.tmask, nf * c->K * 4);             // [streams][n_sources][F][K]
-    d.update = d_upd; d.tmask = d_tm;
-    // the masks an auto call hands back are staged where the other calls stage the masks they take
-    d.em_update = stage(8, q.em_update, nu * 4); d.em_target = stage(9, q.em_target, nf * c->K * 4);
-    if (!d_pcm || !d_doa || (q.out_pcm && !d.out_pcm) || (q.out_spec && !d.out_spec) || (q.update && !d_upd) || (q.tmask && !d_tm) ||
-        (q.em_update && !d.em_update) || (q.em_target && !d.em_target))
-        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    if (q.tmask) VHIP_TRY(c, hipMemcpy(d_tm, q.tmask, nf * c->K * 4, hipMemcpyHostToDevice));
-    VHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)ss * n_streams * 4, hipMemcpyHostToDevice));
-    VHIP_TRY(c, hipMemcpy(d_doa, q.doa, nf * 4, hipMemcpyHostToDevice));
-    if (q.update) VHIP_TRY(c, hipMemcpy(d_upd, q.update, nu * 4, hipMemcpyHostToDevice));
-    const int rc = mvdr_frames_dev(c, d_pcm, ss, ms, d, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    if (q.em_update) VHIP_TRY(c, hipMemcpy(q.em_update, d.em_update, nu * 4, hipMemcpyDeviceToHost));
-    if (q.em_target) VHIP_TRY(c, hipMemcpy(q.em_target, d.em_target, nf * c->K * 4, hipMemcpyDeviceToHost));
-    if (q.out_pcm) VHIP_TRY(c, hipMemcpy(q.out_pcm, d.out_pcm, nf * c->H * 4, hipMemcpyDeviceToHost));
-    if (q.out_spec) VHIP_TRY(c, hipMemcpy(q.out_spec, d.out_spec, nf * c->K * 8, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    const size_t nu = (size_t)n_streams * n_frames * (q.masked ? (size_t)c->K : 1), tb = nf * c->K * 4;      // (target masks: [streams][n_sources][F][K])
+    // (the target mask goes first; the masks an auto call hands back are staged where the other calls stage the masks they take)
+    StageBuf b[] = {{SG_TARGET_MASK, q.tmask, tb, STAGE_IN}, {SG_PCM, pcm, (size_t)ss * n_streams * 4, STAGE_IN}, {SG_DOA, q.doa, nf * 4, STAGE_IN},
+                    {q.masked ? SG_UPDATE_MASK : SG_WEIGHTS, q.update, nu * 4, STAGE_IN}, {SG_UPDATE_MASK, q.em_update, nu * 4, STAGE_OUT},
+                    {SG_TARGET_MASK, q.em_target, tb, STAGE_OUT}, {SG_OUT_PCM, q.out_pcm, nf * c->H * 4, STAGE_OUT}, {SG_OUT_SPEC, q.out_spec, nf * c->K * 8, STAGE_OUT}};
+    return staged(c, b, [&] {
+        MvdrCall d = q;                                         // the same call on the staged copies
+        d.tmask = (float *)b[0].dev; d.doa = (float *)b[2].dev; d.update = (float *)b[3].dev; d.em_update = (float *)b[4].dev; d.em_target = (float *)b[5].dev;
+        d.out_pcm = (float *)b[6].dev; d.out_spec = (float *)b[7].dev;
+        return mvdr_frames_dev(c, (float *)b[1].dev, ss, ms, d, nullptr);
+    });
+}
+
+// the call every mca_hip_mvdr_*frames* entry point starts from
+extern "C++" MvdrCall make_call(int n_streams, int n_frames, int n_sources, const float *doa, float *out_pcm, float *out_spec)
+{
+    MvdrCall q;
+    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa; q.out_pcm = out_pcm; q.out_spec = out_spec;
+    return q;
 }
 
 }  // namespace
@@ -948,10 +907,7 @@ int mca_hip_mvdr_sources_frames_weighted_dev(mca_hip_mvdr_ctx *c, const float *p
                                              int n_frames, int n_sources, const float *doa_rad, const float *update, float *out_pcm,
                                              float *out_spec, void *stream)
 {
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.update = update; q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).weighted(update), stream);
 }
 
 // update_mask [streams][F][K] or NULL (all 1)
@@ -959,10 +915,7 @@ int mca_hip_mvdr_sources_frames_masked_dev(mca_hip_mvdr_ctx *c, const float *pcm
                                            int n_frames, int n_sources, const float *doa_rad, const float *update_mask, float *out_pcm,
                                            float *out_spec, void *stream)
 {
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.update = update_mask; q.masked = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).with_mask(update_mask), stream);
 }
 
 // update_mask [streams][F][K] or NULL (all 1), target_mask [streams][n_sources][F][K] or NULL (all 0)
@@ -970,20 +923,14 @@ int mca_hip_mvdr_sources_frames_rtf_dev(mca_hip_mvdr_ctx *c, const float *pcm, l
                                         int n_frames, int n_sources, const float *doa_rad, const float *update_mask, const float *target_mask,
                                         float *out_pcm, float *out_spec, void *stream)
 {
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.update = update_mask; q.masked = true; q.tmask = target_mask; q.rtf = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).with_rtf(update_mask, target_mask), stream);
 }
 
 int mca_hip_mvdr_sources_frames_rtf_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                          const float *update_mask, const float *target_mask, float *out_pcm, float *out_spec)
 {
     if (c && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.update = update_mask; q.masked = true; q.tmask = target_mask; q.rtf = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_host(c, pcm, q);
+    return mvdr_frames_host(c, pcm, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).with_rtf(update_mask, target_mask));
 }
 
 // update_mask_out [streams][F][K] and target_mask_out [streams][n_sources][F][K]: either may be NULL
@@ -994,11 +941,7 @@ int mca_hip_mvdr_sources_frames_auto_dev(mca_hip_mvdr_ctx *c, const float *pcm, 
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(update_mask_out) | reinterpret_cast<uintptr_t>(target_mask_out)) & 3)
         return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "update_mask_out_dev / target_mask_out_dev must be 4-byte aligned");
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.masked = true; q.rtf = c->rtf_on; q.est = true; q.em_update = update_mask_out; q.em_target = target_mask_out;
-    q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, q, stream);
+    return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).estimating(c->rtf_on, update_mask_out, target_mask_out), stream);
 }
 
 int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
@@ -1006,11 +949,7 @@ int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *c, const float *pcm,
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (!c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.masked = true; q.rtf = c->rtf_on; q.est = true; q.em_update = update_mask_out; q.em_target = target_mask_out;
-    q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_host(c, pcm, q);
+    return mvdr_frames_host(c, pcm, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).estimating(c->rtf_on, update_mask_out, target_mask_out));
 }
 
 int mca_hip_mvdr_sources_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stride, long long mic_stride, int n_streams,
@@ -1028,19 +967,13 @@ int mca_hip_mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long str
 int mca_hip_mvdr_sources_frames_weighted_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                               const float *update, float *out_pcm, float *out_spec)
 {
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.update = update; q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_host(c, pcm, q);
+    return mvdr_frames_host(c, pcm, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).weighted(update));
 }
 
 int mca_hip_mvdr_sources_frames_masked_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                             const float *update_mask, float *out_pcm, float *out_spec)
 {
-    MvdrCall q;
-    q.n_streams = n_streams; q.n_frames = n_frames; q.n_sources = n_sources; q.doa = doa_rad;
-    q.update = update_mask; q.masked = true; q.out_pcm = out_pcm; q.out_spec = out_spec;
-    return mvdr_frames_host(c, pcm, q);
+    return mvdr_frames_host(c, pcm, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).with_mask(update_mask));
 }
 
 int mca_hip_mvdr_sources_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
@@ -1104,36 +1037,34 @@ int mca_hip_mvdr_spectrum_get_grid(const mca_hip_mvdr_ctx *c, float *doa_rad)
 
 extern "C++" {
 namespace {
+// the part of the arguments every scan shares (MvdrSpectrumArgs, MvdrTrackSpectrumArgs): the state of the streams from first_stream on, the
+// grid's phasors and sizes, the band and its chunks
+template <class Args>
+void scan_args(const mca_hip_mvdr_ctx *c, Args &sa, const MvdrBand &b, const float2 *T, int D, int Dpad, int bin_lo, int bin_hi, int first_stream = 0)
+{
+    sa.phi = c->d_phi + (size_t)first_stream * c->K * c->tri; sa.trace = c->d_trace + (size_t)first_stream * c->K; sa.T = T;
+    sa.K = c->K; sa.M = c->M; sa.D = D; sa.Dpad = Dpad; sa.nhi = b.nhi; sa.nph = b.nph;
+    sa.bin_lo = bin_lo; sa.bin_hi = bin_hi; sa.chunk0 = b.chunk0; sa.n_chunks = b.n_chunks;
+}
 // both kernels of the Capon spectrum (timing slot 3), arguments checked by the caller
 int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, hipStream_t st)
 {
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    const MvdrScanPlan p = plan_mvdr_spectrum(*c, c->spec.bin_lo, c->spec.bin_hi, c->spec_dpad, n_streams);
     MvdrSpectrumArgs sa{};
-    sa.phi = c->d_phi; sa.trace = c->d_trace; sa.T = c->d_spec_T;
-    sa.K = c->K; sa.M = c->M; sa.D = c->spec.n_angles; sa.Dpad = c->spec_dpad; sa.nhi = c->N / 64 + 1; sa.nph = sa.nhi + 32;
-    sa.bin_lo = c->spec.bin_lo; sa.bin_hi = c->spec.bin_hi;
-    sa.chunk0 = sa.bin_lo / MVDR_SPEC_CHUNK; sa.n_chunks = sa.bin_hi / MVDR_SPEC_CHUNK - sa.chunk0 + 1;
-    sa.power = c->spec.weighting == MCA_HIP_MVDR_SPECTRUM_POWER;
-    sa.loading = (float)c->cfg.loading;
-    const size_t need = (size_t)n_streams * sa.n_chunks * 4 * sa.Dpad;
-    if (need > c->d_spec_part.n) VHIP_TRY(c, hipDeviceSynchronize());
-    if (const int rc = grow_ws(c, c->d_spec_part, need, "partial sums of the spectrum")) return rc;
+    scan_args(c, sa, p.b, c->d_spec_T, c->spec.n_angles, c->spec_dpad, c->spec.bin_lo, c->spec.bin_hi);
+    sa.power = c->spec.weighting == MCA_HIP_MVDR_SPECTRUM_POWER; sa.loading = (float)c->cfg.loading;
+    if (const int rc = grow_ws(c, c->d_spec_part, p.per_part * n_streams, "partial sums of the spectrum", true)) return rc;
     sa.part = c->d_spec_part;
     MvdrSpectrumPickArgs pa{};
-    pa.part = c->d_spec_part; pa.grid = c->d_spec_grid; pa.n_slices = sa.n_chunks * 4; pa.D = sa.D; pa.Dpad = sa.Dpad; pa.n_peaks = c->spec.n_peaks;
+    pa.part = c->d_spec_part; pa.grid = c->d_spec_grid; pa.n_slices = p.b.n_slices; pa.D = sa.D; pa.Dpad = sa.Dpad; pa.n_peaks = c->spec.n_peaks;
     pa.circular = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0;
     pa.spectrum = spectrum; pa.peak_doa = peak_doa; pa.peak_val = peak_val;
-    const int Q = (c->M + 3) / 4;
-    const size_t smem = (size_t)MVDR_SPEC_CHUNK * (c->tri * sizeof(float2) + 4);          // 68 KiB at 16 microphones
-    const dim3 grid((unsigned)((long long)n_streams * sa.n_chunks));
-    const void *kernel = Q == 1 ? reinterpret_cast<const void *>(k_mvdr_spectrum<1>) : Q == 2 ? reinterpret_cast<const void *>(k_mvdr_spectrum<2>)
-                       : Q == 3 ? reinterpret_cast<const void *>(k_mvdr_spectrum<3>) : reinterpret_cast<const void *>(k_mvdr_spectrum<4>);
-    if (smem > 64 * 1024) VHIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    void *kargs[1] = {&sa};
-    t_begin(c, 3, st);
-    (void)hipLaunchKernel(kernel, grid, dim3(256), kargs, smem, st);
-    hipLaunchKernelGGL(k_mvdr_spectrum_pick, dim3(n_streams), dim3(256), 0, st, pa);
+    t_begin(c, T_SPECTRUM, st);
+    const int rc = launch(c, mvdr_spectrum_kernel(c->Q()), p.grid(p.wg_scan, n_streams), dim3(256), p.lds, &sa, T_NONE, st);
+    if (!rc) launch(c, kptr(k_mvdr_spectrum_pick), dim3(n_streams), dim3(256), 0, &pa, T_NONE, st);
     t_end(c, st);
+    if (rc) return rc;
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -1157,17 +1088,8 @@ int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectr
     if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum, peak_doa and peak_val are all NULL");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t sb = (size_t)n_streams * c->spec.n_angles * 4, pb = (size_t)n_streams * c->spec.n_peaks * 4;
-    float *d_s = spectrum ? (float *)c->stage.get(4, sb) : nullptr;
-    float *d_d = peak_doa ? (float *)c->stage.get(5, pb) : nullptr, *d_v = peak_val ? (float *)c->stage.get(6, pb) : nullptr;
-    if ((spectrum && !d_s) || (peak_doa && !d_d) || (peak_val && !d_v))
-        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    const int rc = mca_hip_mvdr_spectrum_dev(c, n_streams, d_s, d_d, d_v, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    if (spectrum) VHIP_TRY(c, hipMemcpy(spectrum, d_s, sb, hipMemcpyDeviceToHost));
-    if (peak_doa) VHIP_TRY(c, hipMemcpy(peak_doa, d_d, pb, hipMemcpyDeviceToHost));
-    if (peak_val) VHIP_TRY(c, hipMemcpy(peak_val, d_v, pb, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_SCAN, spectrum, sb, STAGE_OUT}, {SG_AUX1, peak_doa, pb, STAGE_OUT}, {SG_AUX2, peak_val, pb, STAGE_OUT}};
+    return staged(c, b, [&] { return mca_hip_mvdr_spectrum_dev(c, n_streams, (float *)b[0].dev, (float *)b[1].dev, (float *)b[2].dev, nullptr); });
 }
 
 // ---- the azimuth x elevation Capon map (kernels_mvdr_map.hip) ----
@@ -1239,43 +1161,31 @@ int mca_hip_mvdr_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float *map, float *
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const int D = c->map.n_az * c->map.n_el;
+    // the partial sums are taken in passes of streams under the workspace cap (MvdrScanPlan): 288 KiB per stream at 2048 directions and N = 1024
+    const MvdrScanPlan p = plan_mvdr_map(*c, c->map.bin_lo, c->map.bin_hi, c->map_dpad, n_streams, c->plane_cap_cells);
+    if (const int rc = grow_ws(c, c->d_map_part, p.per_part * p.pass, "partial sums of the map", true)) return rc;
     MvdrMapScanArgs ma{};
     MvdrSpectrumArgs &sa = ma.s;
-    sa.T = c->d_map_T;
-    sa.K = c->K; sa.M = c->M; sa.D = D; sa.Dpad = c->map_dpad; sa.nhi = c->N / 64 + 1; sa.nph = sa.nhi + 32;
-    sa.bin_lo = c->map.bin_lo; sa.bin_hi = c->map.bin_hi;
-    sa.chunk0 = sa.bin_lo / MVDR_SPEC_CHUNK; sa.n_chunks = sa.bin_hi / MVDR_SPEC_CHUNK - sa.chunk0 + 1;
-    sa.power = c->map.weighting == MCA_HIP_MVDR_SPECTRUM_POWER;
-    sa.loading = (float)c->cfg.loading;
-    ma.n_tiles = (sa.Dpad + MVDR_MAP_TILE - 1) / MVDR_MAP_TILE;
-    // The partial sums are taken in passes of streams under the cap of the context's workspace (mca_hip_mvdr_set_rtf_workspace), one
-    // stream a pass at the least: 288 KiB per stream at 2048 directions and N = 1024.  A stream's bytes do not depend on its pass.
-    const size_t per = (size_t)sa.n_chunks * 4 * sa.Dpad;
-    const size_t fit = std::max<size_t>(1, c->plane_cap_cells * 2 / per);                 // (floats under the cap)
-    const int pass = (int)std::min<size_t>(fit, (size_t)n_streams);
-    if (per * pass > c->d_map_part.n) VHIP_TRY(c, hipDeviceSynchronize());
-    if (const int rc = grow_ws(c, c->d_map_part, per * pass, "partial sums of the map")) return rc;
-    sa.part = c->d_map_part;
+    sa.power = c->map.weighting == MCA_HIP_MVDR_SPECTRUM_POWER; sa.loading = (float)c->cfg.loading; sa.part = c->d_map_part;
+    ma.n_tiles = p.b.n_tiles;
     MvdrMapPickArgs pa{};
-    pa.part = c->d_map_part; pa.az = c->d_map_az; pa.el = c->d_map_el; pa.n_slices = sa.n_chunks * 4;
-    pa.n_az = c->map.n_az; pa.n_el = c->map.n_el; pa.Dpad = sa.Dpad; pa.n_peaks = c->map.n_peaks; pa.ctx_el = (float)c->geo_elevation;
-    const void *kernel = mvdr_map_scan_kernel((c->M + 3) / 4);
-    const size_t smem = (size_t)MVDR_SPEC_CHUNK * (c->tri * sizeof(float2) + 4);          // 68 KiB at 16 microphones, as the spectrum's
-    if (smem > 64 * 1024) VHIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    t_begin(c, 8, st);
-    for (int s0 = 0; s0 < n_streams; s0 += pass) {
-        const int ns = std::min(pass, n_streams - s0);
-        sa.phi = c->d_phi + (size_t)s0 * c->K * c->tri; sa.trace = c->d_trace + (size_t)s0 * c->K;
+    pa.part = c->d_map_part; pa.az = c->d_map_az; pa.el = c->d_map_el; pa.n_slices = p.b.n_slices;
+    pa.n_az = c->map.n_az; pa.n_el = c->map.n_el; pa.Dpad = c->map_dpad; pa.n_peaks = c->map.n_peaks; pa.ctx_el = (float)c->geo_elevation;
+    int rc = MCA_HIP_OK;
+    t_begin(c, T_MAP, st);
+    for (int s0 = 0; s0 < n_streams && !rc; s0 += p.pass) {
+        const int ns = std::min(p.pass, n_streams - s0);
+        scan_args(c, sa, p.b, c->d_map_T, D, c->map_dpad, c->map.bin_lo, c->map.bin_hi, s0);
         pa.map = map ? map + (size_t)s0 * D : nullptr;
         pa.peak_az = peak_az ? peak_az + (size_t)s0 * pa.n_peaks : nullptr;
         pa.peak_el = peak_el ? peak_el + (size_t)s0 * pa.n_peaks : nullptr;
         pa.peak_val = peak_val ? peak_val + (size_t)s0 * pa.n_peaks : nullptr;
         ma.n_streams = ns;
-        void *kargs[1] = {&ma};
-        (void)hipLaunchKernel(kernel, dim3((unsigned)((long long)ns * sa.n_chunks * ma.n_tiles)), dim3(256), kargs, smem, st);
-        hipLaunchKernelGGL(k_mvdr_map_pick, dim3(ns), dim3(256), 0, st, pa);
+        rc = launch(c, mvdr_map_scan_kernel(c->Q()), p.grid(p.wg_scan, ns), dim3(256), p.lds, &ma, T_NONE, st);
+        if (!rc) launch(c, kptr(k_mvdr_map_pick), dim3(ns), dim3(256), 0, &pa, T_NONE, st);
     }
     t_end(c, st);
+    if (rc) return rc;
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -1288,19 +1198,8 @@ int mca_hip_mvdr_map_host(mca_hip_mvdr_ctx *c, int n_streams, float *map, float 
     if (!map && !peak_az && !peak_el && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map, peak_az, peak_el and peak_val are all NULL");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t mb = (size_t)n_streams * c->map.n_az * c->map.n_el * 4, pb = (size_t)n_streams * c->map.n_peaks * 4;
-    float *d_m = map ? (float *)c->stage.get(4, mb) : nullptr;
-    float *d_a = peak_az ? (float *)c->stage.get(5, pb) : nullptr, *d_e = peak_el ? (float *)c->stage.get(6, pb) : nullptr;
-    float *d_v = peak_val ? (float *)c->stage.get(7, pb) : nullptr;
-    if ((map && !d_m) || (peak_az && !d_a) || (peak_el && !d_e) || (peak_val && !d_v))
-        return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    const int rc = mca_hip_mvdr_map_dev(c, n_streams, d_m, d_a, d_e, d_v, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    if (map) VHIP_TRY(c, hipMemcpy(map, d_m, mb, hipMemcpyDeviceToHost));
-    if (peak_az) VHIP_TRY(c, hipMemcpy(peak_az, d_a, pb, hipMemcpyDeviceToHost));
-    if (peak_el) VHIP_TRY(c, hipMemcpy(peak_el, d_e, pb, hipMemcpyDeviceToHost));
-    if (peak_val) VHIP_TRY(c, hipMemcpy(peak_val, d_v, pb, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_SCAN, map, mb, STAGE_OUT}, {SG_AUX1, peak_az, pb, STAGE_OUT}, {SG_AUX2, peak_el, pb, STAGE_OUT}, {SG_WEIGHTS, peak_val, pb, STAGE_OUT}};
+    return staged(c, b, [&] { return mca_hip_mvdr_map_dev(c, n_streams, (float *)b[0].dev, (float *)b[1].dev, (float *)b[2].dev, (float *)b[3].dev, nullptr); });
 }
 
 // ---- an elevation per look-direction slot ----
@@ -1311,11 +1210,6 @@ int elevations_ready(mca_hip_mvdr_ctx *c, int n_streams, const void *ptr)
     if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
     if (!ptr) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations array is NULL");
     return MCA_HIP_OK;
-}
-// the tracks follow azimuths at the context's elevation: a slot with an elevation of its own ends them, as a geometry change does
-void elevations_disable_tracks(mca_hip_mvdr_ctx *c)
-{
-    tracks_off(c);
 }
 }  // namespace
 }  // extern "C++"
@@ -1340,7 +1234,7 @@ int mca_hip_mvdr_set_elevations_host(mca_hip_mvdr_ctx *c, int n_streams, const f
     VHIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the pairs that change here
     VHIP_TRY(c, hipMemcpy2D(c->d_slot_el, MCA_MAX_SOURCES * sizeof(double2), pairs.data(), S * sizeof(double2), S * sizeof(double2), (size_t)n_streams, hipMemcpyHostToDevice));
     VHIP_TRY(c, hipMemcpy2D(c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), elev_rad, S * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyHostToDevice));
-    elevations_disable_tracks(c);
+    tracks_off(c);                                             // they follow azimuths at the context's elevation: a slot with one of its own ends them
     return MCA_HIP_OK;
 }
 
@@ -1350,9 +1244,9 @@ int mca_hip_mvdr_set_elevations_dev(mca_hip_mvdr_ctx *c, int n_streams, const fl
     if (const int rc = elevations_ready(c, n_streams, elev_rad)) return rc;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrElevationsArgs ea{elev_rad, c->d_slot_el, c->d_slot_val, n_streams * c->max_sources, c->max_sources, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
-    hipLaunchKernelGGL(k_mvdr_elevations, dim3((unsigned)((ea.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ea);
+    launch(c, kptr(k_mvdr_elevations), grid_for(ea.n, 256), dim3(256), 0, &ea, T_NONE, (hipStream_t)stream);
     VHIP_TRY(c, hipGetLastError());
-    elevations_disable_tracks(c);
+    tracks_off(c);
     return MCA_HIP_OK;
 }
 
@@ -1465,9 +1359,7 @@ int mca_hip_mvdr_tracks_seed_dev(mca_hip_mvdr_ctx *c, int n_streams, const float
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrackSeedArgs sa{track_state(c), doa, n_streams, c->trk.n_tracks, c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0};
-    t_begin(c, 7, st);
-    hipLaunchKernelGGL(k_mvdr_track_seed, dim3((unsigned)((n_streams * c->trk.n_tracks + 255) / 256)), dim3(256), 0, st, sa);
-    t_end(c, st);
+    launch(c, kptr(k_mvdr_track_seed), grid_for(n_streams * c->trk.n_tracks, 256), dim3(256), 0, &sa, T_TRACKS, st);
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -1479,14 +1371,8 @@ int mca_hip_mvdr_tracks_seed_host(mca_hip_mvdr_ctx *c, int n_streams, const floa
     if (const int rc = tracks_ready_1d(c)) return rc;
     if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa is NULL");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const size_t bytes = (size_t)n_streams * c->trk.n_tracks * 4;
-    float *d = (float *)c->stage.get(6, bytes);
-    if (!d) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffer for the host-pointer call");
-    VHIP_TRY(c, hipMemcpy(d, doa, bytes, hipMemcpyHostToDevice));
-    const int rc = mca_hip_mvdr_tracks_seed_dev(c, n_streams, d, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_AUX2, doa, (size_t)n_streams * c->trk.n_tracks * 4, STAGE_IN}};
+    return staged(c, b, [&] { return mca_hip_mvdr_tracks_seed_dev(c, n_streams, (float *)b[0].dev, nullptr); });
 }
 
 int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *own_spectrum, unsigned char *own_used, void *stream)
@@ -1496,11 +1382,9 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
     if (const int rc = tracks_ready_1d(c)) return rc;
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const int n_own = c->trk.n_own, K = c->K, M = c->M, Dpad = c->spec_dpad, nhi = c->N / 64 + 1;
-    const int chunk0 = c->spec.bin_lo / MVDR_SPEC_CHUNK, n_chunks = c->spec.bin_hi / MVDR_SPEC_CHUNK - chunk0 + 1;
-    const size_t need = (size_t)n_streams * n_own * n_chunks * 4 * Dpad;
-    if (need > c->d_trk_part.n) VHIP_TRY(c, hipDeviceSynchronize());
-    if (const int rc = grow_ws(c, c->d_trk_part, need, "partial sums of the own tracks")) return rc;
+    const int n_own = c->trk.n_own;
+    const MvdrScanPlan p = plan_mvdr_tracks(*c, c->spec.bin_lo, c->spec.bin_hi, c->spec_dpad, n_own, n_streams);
+    if (const int rc = grow_ws(c, c->d_trk_part, p.per_part * n_streams, "partial sums of the own tracks", true)) return rc;
     // the Capon peaks: the kernels of mca_hip_mvdr_spectrum_dev, into the context's own rows.  Not launched where every slot is an own
     // track: a peak then changes no track (it is within min_sep of an own track and skipped, or waits as a birth no slot takes)
     float *pk_doa = c->d_trk_peak, *pk_val = c->d_trk_peak + (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
@@ -1509,25 +1393,21 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
         if (const int rc = launch_spectrum(c, n_streams, nullptr, pk_doa, pk_val, st)) return rc;
     MvdrTrackPickArgs pa = track_pick_args(c);
     pa.cand_doa = pk_doa; pa.cand_val = pk_val; pa.n_cand = capon ? c->spec.n_peaks : 0;
-    if (n_own > 0 && own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks
-    t_begin(c, 7, st);
+    if (n_own > 0 && own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * c->K, st));      // the bins outside the band's chunks
+    t_begin(c, T_TRACKS, st);
     if (n_own > 0) {
-        MvdrTrackTablesArgs ta{c->d_trk_theta, c->d_trk_T0, c->d_micx, (double)c->cfg.sample_rate / (double)c->N / 346.1, c->N, M, n_own, geometry_args(c)};
-        hipLaunchKernelGGL(k_mvdr_track_tables, dim3((unsigned)(n_streams * n_own)), dim3(256), 0, st, ta);
+        MvdrTrackTablesArgs ta{c->d_trk_theta, c->d_trk_T0, c->d_micx, (double)c->cfg.sample_rate / (double)c->N / 346.1, c->N, c->M, n_own, geometry_args(c)};
+        launch(c, kptr(k_mvdr_track_tables), p.grid(p.wg_tables, n_streams), dim3(256), 0, &ta, T_NONE, st);
         MvdrTrackSpectrumArgs sa{};
-        sa.phi = c->d_phi; sa.trace = c->d_trace; sa.psi = c->d_psi; sa.cpsi = c->d_cpsi; sa.cphi = c->d_cphi;
-        sa.T0 = c->d_trk_T0; sa.T = c->d_spec_T; sa.alive = track_state(c).alive; sa.part = c->d_trk_part; sa.used = own_used;
-        sa.K = K; sa.M = M; sa.D = c->spec.n_angles; sa.Dpad = Dpad; sa.nhi = nhi; sa.nph = nhi + 32;
-        sa.bin_lo = c->spec.bin_lo; sa.bin_hi = c->spec.bin_hi; sa.chunk0 = chunk0; sa.n_chunks = n_chunks;
+        scan_args(c, sa, p.b, c->d_spec_T, c->spec.n_angles, c->spec_dpad, c->spec.bin_lo, c->spec.bin_hi);
+        sa.psi = c->d_psi; sa.cpsi = c->d_cpsi; sa.cphi = c->d_cphi;
+        sa.T0 = c->d_trk_T0; sa.alive = track_state(c).alive; sa.part = c->d_trk_part; sa.used = own_used;
         sa.n_own = n_own; sa.slots = c->max_sources;
         sa.min_share = (float)c->rtf_min_share; sa.iterations = c->rtf_iterations; sa.ref_mic = c->rtf_ref;
-        void *kargs[1] = {&sa};
-        (void)hipLaunchKernel(mvdr_track_spectrum_kernel((M + 3) / 4), dim3((unsigned)((long long)n_streams * n_own * n_chunks)), dim3(256), kargs, 0, st);
-        pa.part = c->d_trk_part; pa.n_slices = n_chunks * 4; pa.own_spectrum = own_spectrum;
-        hipLaunchKernelGGL(k_mvdr_track_pick, dim3(n_streams), dim3(256), 0, st, pa);
-    } else {
-        hipLaunchKernelGGL(k_mvdr_track_pick, dim3(n_streams), dim3(256), 0, st, pa);
+        launch(c, mvdr_track_spectrum_kernel(c->Q()), p.grid(p.wg_scan, n_streams), dim3(256), 0, &sa, T_NONE, st);
+        pa.part = c->d_trk_part; pa.n_slices = p.b.n_slices; pa.own_spectrum = own_spectrum;
     }
+    launch(c, kptr(k_mvdr_track_pick), dim3(n_streams), dim3(256), 0, &pa, T_NONE, st);
     t_end(c, st);
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
@@ -1540,15 +1420,8 @@ int mca_hip_mvdr_tracks_update_host(mca_hip_mvdr_ctx *c, int n_streams, float *o
     if (const int rc = tracks_ready_1d(c)) return rc;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t sb = (size_t)n_streams * c->trk.n_own * c->spec.n_angles * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
-    float *d_s = own_spectrum ? (float *)c->stage.get(4, sb) : nullptr;
-    unsigned char *d_u = own_used ? (unsigned char *)c->stage.get(5, ub) : nullptr;
-    if ((own_spectrum && sb && !d_s) || (own_used && ub && !d_u)) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    const int rc = mca_hip_mvdr_tracks_update_dev(c, n_streams, d_s, d_u, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    if (d_s) VHIP_TRY(c, hipMemcpy(own_spectrum, d_s, sb, hipMemcpyDeviceToHost));
-    if (d_u) VHIP_TRY(c, hipMemcpy(own_used, d_u, ub, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_SCAN, own_spectrum, sb, STAGE_OUT}, {SG_AUX1, own_used, ub, STAGE_OUT}};      // (n_own == 0: nothing of either)
+    return staged(c, b, [&] { return mca_hip_mvdr_tracks_update_dev(c, n_streams, (float *)b[0].dev, (unsigned char *)b[1].dev, nullptr); });
 }
 
 int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *own_doa, int n_cand, const float *cand_doa, const float *cand_val,
@@ -1564,9 +1437,7 @@ int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *c, int n_streams, const 
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrackPickArgs pa = track_pick_args(c);
     pa.own_doa = own_doa; pa.cand_doa = cand_doa; pa.cand_val = cand_val; pa.n_cand = n_cand;
-    t_begin(c, 7, st);
-    hipLaunchKernelGGL(k_mvdr_track_pick, dim3(n_streams), dim3(256), 0, st, pa);
-    t_end(c, st);
+    launch(c, kptr(k_mvdr_track_pick), dim3(n_streams), dim3(256), 0, &pa, T_TRACKS, st);
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -1579,18 +1450,14 @@ int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *c, int n_streams, int n_frame
     if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const dim3 grid((unsigned)(((long long)n_streams * n_frames + 255) / 256));
+    const dim3 grid = grid_for((long long)n_streams * n_frames, 256);
     if (c->trk_map_on) {
         // map mode: the elevations of the slots travel with the azimuths, on the same stream
         MvdrTrk2FillArgs fa{track_state_map(c), doa_rad, n_streams, n_frames, c->trk.n_tracks, c->d_slot_el, c->d_slot_val, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
-        t_begin(c, 9, st);
-        hipLaunchKernelGGL(k_mvdr_trk2_fill, grid, dim3(256), 0, st, fa);
-        t_end(c, st);
+        launch(c, kptr(k_mvdr_trk2_fill), grid, dim3(256), 0, &fa, T_TRACKS_MAP, st);
     } else {
         MvdrTrackFillArgs fa{track_state(c), doa_rad, n_streams, n_frames, c->trk.n_tracks};
-        t_begin(c, 7, st);
-        hipLaunchKernelGGL(k_mvdr_track_fill, grid, dim3(256), 0, st, fa);
-        t_end(c, st);
+        launch(c, kptr(k_mvdr_track_fill), grid, dim3(256), 0, &fa, T_TRACKS, st);
     }
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
@@ -1603,14 +1470,8 @@ int mca_hip_mvdr_tracks_fill_host(mca_hip_mvdr_ctx *c, int n_streams, int n_fram
     if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
     if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is NULL");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const size_t bytes = (size_t)n_streams * n_frames * c->trk.n_tracks * 4;
-    float *d = (float *)c->stage.get(6, bytes);
-    if (!d) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffer for the host-pointer call");
-    const int rc = mca_hip_mvdr_tracks_fill_dev(c, n_streams, n_frames, d, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    VHIP_TRY(c, hipMemcpy(doa_rad, d, bytes, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_AUX2, doa_rad, (size_t)n_streams * n_frames * c->trk.n_tracks * 4, STAGE_OUT}};
+    return staged(c, b, [&] { return mca_hip_mvdr_tracks_fill_dev(c, n_streams, n_frames, (float *)b[0].dev, nullptr); });
 }
 
 int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *c, int n_streams, float *theta, int *alive, int *miss, int *gen)
@@ -1721,9 +1582,7 @@ int mca_hip_mvdr_tracks_seed_map_dev(mca_hip_mvdr_ctx *c, int n_streams, const f
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrk2SeedArgs sa{track_state_map(c), az, el, n_streams, c->trk.n_tracks};
-    t_begin(c, 9, st);
-    hipLaunchKernelGGL(k_mvdr_trk2_seed, dim3((unsigned)((n_streams * c->trk.n_tracks + 255) / 256)), dim3(256), 0, st, sa);
-    t_end(c, st);
+    launch(c, kptr(k_mvdr_trk2_seed), grid_for(n_streams * c->trk.n_tracks, 256), dim3(256), 0, &sa, T_TRACKS_MAP, st);
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -1735,14 +1594,8 @@ int mca_hip_mvdr_tracks_seed_map_host(mca_hip_mvdr_ctx *c, int n_streams, const 
     if (!az || !el) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az / el is NULL");
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t bytes = (size_t)n_streams * c->trk.n_tracks * 4;
-    float *d_a = (float *)c->stage.get(5, bytes), *d_e = (float *)c->stage.get(6, bytes);
-    if (!d_a || !d_e) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    VHIP_TRY(c, hipMemcpy(d_a, az, bytes, hipMemcpyHostToDevice));
-    VHIP_TRY(c, hipMemcpy(d_e, el, bytes, hipMemcpyHostToDevice));
-    const int rc = mca_hip_mvdr_tracks_seed_map_dev(c, n_streams, d_a, d_e, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_AUX1, az, bytes, STAGE_IN}, {SG_AUX2, el, bytes, STAGE_IN}};
+    return staged(c, b, [&] { return mca_hip_mvdr_tracks_seed_map_dev(c, n_streams, (float *)b[0].dev, (float *)b[1].dev, nullptr); });
 }
 
 int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float *own_map, unsigned char *own_used, void *stream)
@@ -1751,8 +1604,7 @@ int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
     hipStream_t st = (hipStream_t)stream;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    const int n_own = c->trk.n_own, K = c->K, M = c->M, Dpad = c->map_dpad, D = c->map.n_az * c->map.n_el, nhi = c->N / 64 + 1;
-    const int chunk0 = c->map.bin_lo / MVDR_SPEC_CHUNK, n_chunks = c->map.bin_hi / MVDR_SPEC_CHUNK - chunk0 + 1;
+    const int n_own = c->trk.n_own, K = c->K, M = c->M, D = c->map.n_az * c->map.n_el;
     // the map's peaks: the kernels of mca_hip_mvdr_map_dev (timing slot 8), into the context's own rows.  Not launched where every slot
     // is an own track: a peak then changes no track
     const size_t row = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
@@ -1761,49 +1613,43 @@ int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float
     const int n_cand = capon ? c->map.n_peaks : 0;
     if (capon)
         if (const int rc = mca_hip_mvdr_map_dev(c, n_streams, nullptr, pk_az, pk_el, pk_val, stream)) return rc;
-    // u, the flags and the partial sums are taken in passes of streams under the cap of the context's workspace
-    // (mca_hip_mvdr_set_rtf_workspace), one stream a pass at the least.  A stream's bytes do not depend on its pass
-    const size_t per_u = (size_t)n_own * n_chunks * MVDR_SPEC_CHUNK * M, per_f = (size_t)n_own * n_chunks * MVDR_SPEC_CHUNK;
-    const size_t per_p = (size_t)n_own * n_chunks * 4 * Dpad, per = 2 * per_u + per_f + per_p;       // (floats)
-    const int pass = n_own > 0 ? (int)std::min<size_t>(std::max<size_t>(1, c->plane_cap_cells * 2 / per), (size_t)n_streams) : n_streams;
+    // u, the flags and the partial sums are taken in passes of streams under the workspace cap (MvdrScanPlan)
+    const MvdrScanPlan p = plan_mvdr_tracks_map(*c, c->map.bin_lo, c->map.bin_hi, c->map_dpad, n_own, n_streams, c->plane_cap_cells);
+    const int pass = p.pass;
     if (n_own > 0) {
-        if (per_u * pass > c->d_trk2_U.n || per_p * pass > c->d_trk2_part.n) VHIP_TRY(c, hipDeviceSynchronize());
-        if (const int rc = grow_ws(c, c->d_trk2_U, per_u * pass, "steering vectors of the own tracks")) return rc;
-        if (const int rc = grow_ws(c, c->d_trk2_F, per_f * pass, "used flags of the own tracks")) return rc;
-        if (const int rc = grow_ws(c, c->d_trk2_part, per_p * pass, "partial sums of the own tracks")) return rc;
+        if (const int rc = grow_ws(c, c->d_trk2_U, p.per_u * pass, "steering vectors of the own tracks", true)) return rc;
+        if (const int rc = grow_ws(c, c->d_trk2_F, p.per_f * pass, "used flags of the own tracks", true)) return rc;
+        if (const int rc = grow_ws(c, c->d_trk2_part, p.per_part * pass, "partial sums of the own tracks", true)) return rc;
         if (own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks, the dead slots
     }
-    const int n_tiles = (Dpad + MVDR_MAP_TILE - 1) / MVDR_MAP_TILE;
-    t_begin(c, 9, st);
+    t_begin(c, T_TRACKS_MAP, st);
     for (int s0 = 0; s0 < n_streams; s0 += pass) {
         const int ns = std::min(pass, n_streams - s0);
         MvdrTrk2PickArgs pa = trk2_pick_args(c, s0);
         pa.cand_az = pk_az + (size_t)s0 * n_cand; pa.cand_el = pk_el + (size_t)s0 * n_cand; pa.cand_val = pk_val + (size_t)s0 * n_cand; pa.n_cand = n_cand;
         if (n_own > 0) {
             const MvdrTrk2State ts = track_state_map(c, s0);
-            float2 *T0 = c->d_trk_T0 + (size_t)s0 * n_own * M * (nhi + 32);
+            float2 *T0 = c->d_trk_T0 + (size_t)s0 * n_own * M * p.b.nph;
             MvdrTrk2TablesArgs ta{ts.theta, ts.eps, ts.alive, T0, c->N, M, n_own, geometry_args(c)};
-            hipLaunchKernelGGL(k_mvdr_trk2_tables, dim3((unsigned)(ns * n_own)), dim3(256), 0, st, ta);
+            launch(c, kptr(k_mvdr_trk2_tables), p.grid(p.wg_tables, ns), dim3(256), 0, &ta, T_NONE, st);
             MvdrTrk2ScanArgs sa{};
             MvdrTrackSpectrumArgs &sp = sa.s;
-            sp.phi = c->d_phi + (size_t)s0 * K * c->tri; sp.trace = c->d_trace + (size_t)s0 * K; sp.cphi = c->d_cphi + (size_t)s0 * K;
+            scan_args(c, sp, p.b, c->d_map_T, D, c->map_dpad, c->map.bin_lo, c->map.bin_hi, s0);
+            sp.cphi = c->d_cphi + (size_t)s0 * K;
             sp.psi = c->d_psi + (size_t)s0 * c->max_sources * K * c->tri; sp.cpsi = c->d_cpsi + (size_t)s0 * c->max_sources * K;
-            sp.T0 = T0; sp.T = c->d_map_T; sp.alive = ts.alive; sp.part = c->d_trk2_part;
+            sp.T0 = T0; sp.alive = ts.alive; sp.part = c->d_trk2_part;
             sp.used = own_used ? own_used + (size_t)s0 * n_own * K : nullptr;
-            sp.K = K; sp.M = M; sp.D = D; sp.Dpad = Dpad; sp.nhi = nhi; sp.nph = nhi + 32;
-            sp.bin_lo = c->map.bin_lo; sp.bin_hi = c->map.bin_hi; sp.chunk0 = chunk0; sp.n_chunks = n_chunks;
             sp.n_own = n_own; sp.slots = c->max_sources;
             sp.min_share = (float)c->rtf_min_share; sp.iterations = c->rtf_iterations; sp.ref_mic = c->rtf_ref;
             sa.U = c->d_trk2_U; sa.F = c->d_trk2_F; sa.az = c->d_map_az; sa.el = c->d_map_el; sa.theta = ts.theta; sa.eps = ts.eps;
-            sa.max_step = pa.max_step; sa.max_step_el = pa.max_step_el; sa.n_az = c->map.n_az; sa.n_tiles = n_tiles; sa.n_streams = ns;
+            sa.max_step = pa.max_step; sa.max_step_el = pa.max_step_el; sa.n_az = c->map.n_az; sa.n_tiles = p.b.n_tiles; sa.n_streams = ns;
             sa.skip = own_map ? 0 : 1;
-            void *kargs[1] = {&sa};
-            (void)hipLaunchKernel(mvdr_trk2_vectors_kernel((M + 3) / 4), dim3((unsigned)((long long)ns * n_own * n_chunks)), dim3(256), kargs, 0, st);
-            hipLaunchKernelGGL(k_mvdr_trk2_scan, dim3((unsigned)((long long)ns * n_own * n_chunks * n_tiles)), dim3(256), 0, st, sa);
-            pa.part = c->d_trk2_part; pa.n_slices = n_chunks * 4;
+            launch(c, mvdr_trk2_vectors_kernel(c->Q()), p.grid(p.wg_vectors, ns), dim3(256), 0, &sa, T_NONE, st);
+            launch(c, kptr(k_mvdr_trk2_scan), p.grid(p.wg_scan, ns), dim3(256), 0, &sa, T_NONE, st);
+            pa.part = c->d_trk2_part; pa.n_slices = p.b.n_slices;
             pa.own_map = own_map ? own_map + (size_t)s0 * n_own * D : nullptr;
         }
-        hipLaunchKernelGGL(k_mvdr_trk2_pick, dim3(ns), dim3(256), 0, st, pa);
+        launch(c, kptr(k_mvdr_trk2_pick), dim3(ns), dim3(256), 0, &pa, T_NONE, st);
     }
     t_end(c, st);
     VHIP_TRY(c, hipGetLastError());
@@ -1816,15 +1662,8 @@ int mca_hip_mvdr_tracks_update_map_host(mca_hip_mvdr_ctx *c, int n_streams, floa
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
     VHIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t mb = (size_t)n_streams * c->trk.n_own * c->map.n_az * c->map.n_el * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
-    float *d_m = own_map ? (float *)c->stage.get(4, mb) : nullptr;
-    unsigned char *d_u = own_used ? (unsigned char *)c->stage.get(5, ub) : nullptr;
-    if ((own_map && mb && !d_m) || (own_used && ub && !d_u)) return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    const int rc = mca_hip_mvdr_tracks_update_map_dev(c, n_streams, d_m, d_u, nullptr);
-    if (rc) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    if (d_m) VHIP_TRY(c, hipMemcpy(own_map, d_m, mb, hipMemcpyDeviceToHost));
-    if (d_u) VHIP_TRY(c, hipMemcpy(own_used, d_u, ub, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    StageBuf b[] = {{SG_SCAN, own_map, mb, STAGE_OUT}, {SG_AUX1, own_used, ub, STAGE_OUT}};      // (n_own == 0: nothing of either)
+    return staged(c, b, [&] { return mca_hip_mvdr_tracks_update_map_dev(c, n_streams, (float *)b[0].dev, (unsigned char *)b[1].dev, nullptr); });
 }
 
 int mca_hip_mvdr_tracks_associate_map_dev(mca_hip_mvdr_ctx *c, int n_streams, const float *own_az, const float *own_el, int n_cand, const float *cand_az,
@@ -1840,9 +1679,7 @@ int mca_hip_mvdr_tracks_associate_map_dev(mca_hip_mvdr_ctx *c, int n_streams, co
     MvdrTrk2PickArgs pa = trk2_pick_args(c, 0);
     pa.own_az = c->trk.n_own > 0 ? own_az : nullptr; pa.own_el = c->trk.n_own > 0 ? own_el : nullptr;
     pa.cand_az = cand_az; pa.cand_el = cand_el; pa.cand_val = cand_val; pa.n_cand = n_cand;
-    t_begin(c, 9, st);
-    hipLaunchKernelGGL(k_mvdr_trk2_pick, dim3(n_streams), dim3(256), 0, st, pa);
-    t_end(c, st);
+    launch(c, kptr(k_mvdr_trk2_pick), dim3(n_streams), dim3(256), 0, &pa, T_TRACKS_MAP, st);
     VHIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
@@ -2047,9 +1884,10 @@ int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
 
 int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, double *total_ms)
 {
-    if (!c || kernel_id < 0 || kernel_id > 9 || (kernel_id == 4 && !c->pf_ever) || (kernel_id == 5 && !c->rtf_ever) || (kernel_id == 6 && !c->em_ever) ||
-        (kernel_id == 7 && !c->trk_ever) || (kernel_id == 8 && !c->map_ever) || (kernel_id == 9 && !c->trk_map_ever))
-        return MCA_HIP_ERR_INVALID_ARGUMENT;
+    // slot -> the flag that opens it: a slot of a feature exists once the feature was ever on (a context that never had it refuses the id as it always did)
+    static bool mca_hip_mvdr_ctx::*const opens[T_COUNT] = {nullptr, nullptr, nullptr, nullptr, &mca_hip_mvdr_ctx::pf_ever, &mca_hip_mvdr_ctx::rtf_ever, &mca_hip_mvdr_ctx::em_ever,
+                                                           &mca_hip_mvdr_ctx::trk_ever, &mca_hip_mvdr_ctx::map_ever, &mca_hip_mvdr_ctx::trk_map_ever};
+    if (!c || kernel_id < 0 || kernel_id >= T_COUNT || (opens[kernel_id] && !(c->*opens[kernel_id]))) return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
         VHIP_TRY(c, hipEventSynchronize(e.b));
         float ms = 0.f;

@@ -93,12 +93,11 @@ __global__ void k_mvdr_analyse(MvdrAnalyseArgs p);
 __global__ void k_mvdr_analyse_1024(MvdrAnalyseArgs p, int fpb);
 __global__ void k_mvdr_analyse_512(MvdrAnalyseArgs p, int fpb);
 template <int Q, bool FULL> __global__ void k_mvdr_solve(MvdrSolveArgs p);                 // one look direction, no weights (kernels_mvdr.hip)
+const void *mvdr_solve_hand_kernel(int Q, bool full);
 // every other solve (mvdr_solve.h; mca_internal.h on the parameters and on mvdr_solve_form, which fixes S1, PF and REUSE per row)
 template <int Q, bool FULL, int S, int S1, bool PF, bool NULLS, bool REUSE, MvdrWeight WEIGHT, bool NOISE> __global__ void k_mvdr_solve_t(MvdrSolveArgs p);
 // the instantiations of one (WEIGHT, NOISE), each group in a translation unit of its own (kernels_mvdr_solve_*.hip)
 template <MvdrWeight WEIGHT, bool NOISE> const void *mvdr_solve_kernel_of(int Q, bool full, int S, bool nulls, int *lds_bytes);
-// the solve kernel of a call with Q row slots, M == 4 Q (full), S look directions, ...; its dynamic LDS; nullptr: not in the build
-const void *mvdr_solve_kernel(int Q, bool full, int S, bool nulls, MvdrWeight w, bool noise, int *lds_bytes);
 // the solve with the right-hand sides from the steering plane of k_mvdr_rtf (mvdr_solve.h; kernels_mvdr_solve_rtf*.hip)
 template <int Q, bool FULL, int S, int S1, bool PF, bool NOISE> __global__ void k_mvdr_solve_rtf_t(MvdrSolveArgs p);
 template <bool NOISE> const void *mvdr_solve_rtf_kernel_of(int Q, bool full, int S);
@@ -113,6 +112,7 @@ const void *mvdr_estmask_kernel(int Q);                                         
 __global__ void k_mvdr_postfilter(MvdrPostfilterArgs p);                                   // decision-directed Wiener gain on the solve's output
 __global__ void k_mvdr_synth(MvdrSynthArgs p);
 template <int Q> __global__ void k_mvdr_spectrum(MvdrSpectrumArgs p);                      // Capon spatial spectrum of the held covariance
+const void *mvdr_spectrum_kernel(int Q);                                         // kernels_mvdr_spectrum.hip
 __global__ void k_mvdr_spectrum_pick(MvdrSpectrumPickArgs p);
 const void *mvdr_map_scan_kernel(int Q);                                         // the azimuth x elevation Capon map (kernels_mvdr_map.hip)
 __global__ void k_mvdr_map_pick(MvdrMapPickArgs p);

@@ -274,6 +274,14 @@ template __global__ void k_mvdr_solve<2, true>(MvdrSolveArgs);
 template __global__ void k_mvdr_solve<3, true>(MvdrSolveArgs);
 template __global__ void k_mvdr_solve<4, true>(MvdrSolveArgs);
 
+// the hand-written kernel of Q row slots, M == 4 Q (full); nullptr: not in the build
+const void *mvdr_solve_hand_kernel(int Q, bool full)
+{
+    const void *k[4][2] = {{(const void *)k_mvdr_solve<1, false>, (const void *)k_mvdr_solve<1, true>}, {(const void *)k_mvdr_solve<2, false>, (const void *)k_mvdr_solve<2, true>},
+                           {(const void *)k_mvdr_solve<3, false>, (const void *)k_mvdr_solve<3, true>}, {(const void *)k_mvdr_solve<4, false>, (const void *)k_mvdr_solve<4, true>}};
+    return Q >= 1 && Q <= 4 ? k[Q - 1][full] : nullptr;
+}
+
 // --------------------------------------------------------------------------------------
 // k_mvdr_synth: grid (runs of ft frames, streams * sources), 256 threads, LDS = (H + 1) float2 + H floats.
 // A run starts one frame early to rebuild the overlap-add carry the previous run leaves (as k_beamform_gen).

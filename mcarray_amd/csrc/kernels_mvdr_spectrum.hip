@@ -41,6 +41,12 @@ template __global__ void k_mvdr_spectrum<2>(MvdrSpectrumArgs);
 template __global__ void k_mvdr_spectrum<3>(MvdrSpectrumArgs);
 template __global__ void k_mvdr_spectrum<4>(MvdrSpectrumArgs);
 
+const void *mvdr_spectrum_kernel(int Q)
+{
+    return Q == 1 ? reinterpret_cast<const void *>(k_mvdr_spectrum<1>) : Q == 2 ? reinterpret_cast<const void *>(k_mvdr_spectrum<2>)
+         : Q == 3 ? reinterpret_cast<const void *>(k_mvdr_spectrum<3>) : reinterpret_cast<const void *>(k_mvdr_spectrum<4>);
+}
+
 // One workgroup per stream: P[i] = the partial sums of the stream in (chunk, wave) order -- no atomics, the same bytes on every
 // run -- then the peaks (include/mcarray_hip.h: local maxima ranked by value, ties to the lower index; empty slots repeat slot 0
 // with value 0).  At most 361 angles and 4 peaks: one lane walks the row.

@@ -11,7 +11,8 @@ Cases (N = 64, fs = 16 kHz, 3 streams, two calls of 5 + 4 frames; stream 2 start
 and 16 microphones (both forms of every number of row slots) x 1 ... 4 look directions x null_gain 0 and 7.5 (two directions and
 more) x no update weights, a weight per frame (zeros, fractions and ones) and a weight per frame and bin x post-filter off and on.
 Then one call whose solve takes the pieced tail launch: 1000 streams x 8 frames, 16 microphones, 2 directions (516 workgroups: a
-remainder of 4, in 2 pieces).  Then the paths of the host layer (host_layer_cases below)."""
+remainder of 4, in 2 pieces).  Then the paths of the host layer (host_layer_cases below) and the cuts the launch plans make under the
+workspace cap (plan_cases)."""
 import hashlib
 import json
 import os
@@ -188,6 +189,64 @@ def host_layer_cases(api, np, has, res):
             parts += [up["own_spectrum"], up["own_used"]] + [tr[key] for key in ("theta", "alive", "miss", "gen")]
         bf.close()
         res["spectrum, then tracks configured, seeded, updated and read"] = digest(*parts)
+    plan_cases(api, np, has, res)
+
+
+def plan_cases(api, np, has, res):
+    """the cuts the launch plans decide under the workspace cap, which change no byte (4 microphones off the line, 3 streams, 2 look
+    directions): an RTF call in chunks of unequal length, a map of 8 x 3 directions a stream a pass, and an update of the map-mode
+    tracks with one own track a stream a pass -- each beside the same calls under the default cap, whose digest must be the same"""
+    A, F, M, S = 3, 5, 4, 2
+    rng = np.random.default_rng(2828)
+    xyz = [[0.0, 0.0, 0.0], [0.07, 0.0, 0.0], [0.0, 0.07, 0.0], [0.02, 0.03, 0.06]]
+    pcm = rng.standard_normal((A, M, (F + 1) * HOP)).astype(np.float32)
+    doa = rng.uniform(-1.3, 1.3, (A, F, S)).astype(np.float32)
+    um = rng.choice(np.array([0.0, 1.0, 1.0, 0.3], dtype=np.float32), size=(A, F, K))
+    tm = rng.choice(np.array([0.0, 1.0, 1.0, 0.6], dtype=np.float32), size=(A, S, F, K))
+
+    def rtf_call(bf, parts):
+        r = bf.process_sources(pcm, doa, update_mask=um, target_mask=tm)
+        parts += [r["spec"], r["out"]] + [bf.covariance(a) for a in range(A)]
+        for a in range(A):
+            for s in range(S):
+                parts += list(bf.target_covariance(a, s))
+
+    digests = {}
+    for cut in (False, True):
+        bf, parts = api.MvdrBeamformer(FS, xyz, N, max_streams=A, max_sources=S), []
+        bf.set_rtf(True)
+        if cut:
+            bf.set_rtf_workspace(2 * A * S * K * M * 8)         # room for 2 of the 5 frames: chunks of 2, 2 and 1
+        rtf_call(bf, parts)
+        bf.close()
+        digests["rtf", cut] = digest(*parts)
+    res["plan: RTF call of 5 frames, M=4, whole"] = digests["rtf", False]
+    res["plan: RTF call of 5 frames, M=4, cut into 2 + 2 + 1"] = digests["rtf", True]
+    assert digests["rtf", False] == digests["rtf", True], "the cut of an RTF call changed bytes"
+    if not (has("mca_hip_mvdr_map_host") and has("mca_hip_mvdr_tracks_update_map_host")):
+        return
+    for cut in (False, True):
+        bf, parts = api.MvdrBeamformer(FS, xyz, N, max_streams=A, max_sources=S, geometry="xyz"), []
+        bf.set_rtf(True)
+        rtf_call(bf, parts)
+        bf.configure_spectrum(8, 1, 30)
+        bf.map_configure(8, 3, 0.0, 1.0, 1, 30, n_peaks=2)      # 24 directions: 64 lanes, one chunk of bins: 256 floats of partial sums a stream
+        if cut:
+            bf.set_rtf_workspace(256 * 4)                       # one stream a pass
+        mp = bf.map()
+        parts += [mp[key] for key in ("map", "peak_az", "peak_el", "peak_val")]
+        res["plan: map of 8 x 3 directions, %s" % ("a stream a pass" if cut else "one pass")] = digests["map", cut] = digest(*parts)
+        bf.configure_tracks(2, n_own=1)
+        bf.configure_tracks_map(0.6, 0.3)
+        bf.seed_tracks_map(np.array([[0.4, -0.7], [-0.2, 0.9], [1.1, 0.1]], dtype=np.float32), np.array([[0.2, 0.5], [0.7, 0.1], [0.4, 0.4]], dtype=np.float32))
+        if cut:
+            bf.set_rtf_workspace(832 * 4)                       # u, flags and partial sums of one own track: 832 floats a stream: one stream a pass (the map: 3)
+        up = bf.update_tracks_map(want_map=True)
+        tr = bf.tracks_map()
+        parts += [up["own_map"], up["own_used"]] + [tr[key] for key in ("theta", "eps", "alive", "miss", "gen")]
+        bf.close()
+        res["plan: map-mode tracks update, one own track, %s" % ("a stream a pass" if cut else "one pass")] = digests["tracks", cut] = digest(*parts)
+    assert digests["map", False] == digests["map", True] and digests["tracks", False] == digests["tracks", True], "the passes of a map call changed bytes"
 
 
 def run_both(script, parent_lib, seconds=CHILD_SECONDS):
