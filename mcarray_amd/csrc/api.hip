@@ -6,9 +6,9 @@
 #include "../../include/mcarray_hip.h"
 #include "fft1024c.h"
 #include "fold_table.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "knobs.h"
-#include "stage.h"
 
 #include <chrono>
 #include <cmath>
@@ -22,8 +22,6 @@
 using namespace mca;
 
 namespace {
-
-std::string g_create_error;
 
 struct TimedEvent { int id; hipEvent_t a, b; };
 
@@ -217,19 +215,9 @@ struct StreamCall {
 // repair pass, ADAPTIVE calls that run as FP16X3 -- mca_hip_ctx::tab_planes), the contraction depth per plane and the elements per row
 struct RowLayout { int planes, kp, row_elems; };
 
-int fail(mca_hip_ctx *c, int code, const std::string &msg)
-{
-    if (c) c->err = msg; else g_create_error = msg;
-    return code;
-}
-
-#define HIP_TRY(ctx, expr)                                                                              \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return fail(ctx, _e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP,   \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                            \
-    } while (0)
+mca_hip_ctx *const NO_CTX = nullptr;             // a failing create (and the calls that have no context): the text goes to the creation error
+// the staging-pool slots of the host-pointer calls (process_frames_host_impl keeps its own); the numbers stay
+enum Gcc2StageSlot { SG_PCM = 0, SG_ARGMAX = 1, SG_DOA = 2, SG_PROB = 3, SG_CORR = 4, SG_TRACK = 5, SG_FIRED = 6, SG_PROB_IN = 5, SG_PROB_OUT = 6 };
 
 // ---- the reference's helper chain, host side (exact float/double sequence of
 //      src/mcarray/microhponeArrayHelpers.cpp:38-120; [BUILD-DEFINES] double sin) ----
@@ -244,12 +232,6 @@ double distance(const std::vector<double> &xyz, int i, int j)                   
 {
     return std::sqrt(std::pow(xyz[3 * j] - xyz[3 * i], 2) + std::pow(xyz[3 * j + 1] - xyz[3 * i + 1], 2) +
                      std::pow(xyz[3 * j + 2] - xyz[3 * i + 2], 2));
-}
-
-// what an allocation, an upload or a fill failed with: out of memory by its own code, `what` names the buffer
-int hip_fail(mca_hip_ctx *c, hipError_t e, const char *what)
-{
-    return fail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 // A workspace of at least n elements -- the one place that reallocates a buffer a call hands to kernels, and so the one place that
@@ -681,13 +663,13 @@ void stft_common(const mca_hip_ctx *c, StftPhatArgs &sa)
     sa.M = c->M; sa.window = c->d_window; sa.Kp = c->Kp;
     sa.N = c->N; sa.logH = c->logH; sa.kg = c->K; sa.ula = c->ula ? 1 : 0; sa.tw = c->d_tw;
 }
-// The one launcher of the stream path: a plan's kernel (the lookups of kernels.h; nullptr: a form the build lacks -- plan and predicate disagree, which
-// tests/test_stream_plan.py rules out), grid, block, dynamic LDS and the kernel's one argument struct.  The attribute is set exactly above the 64 KiB every kernel may have.
+// The launcher of the stream path, on the attribute rule of host_common.h (lds_limit): a plan's kernel (the lookups of kernels.h; nullptr: a form the build lacks -- plan and predicate disagree, which
+// tests/test_stream_plan.py rules out), grid, block, dynamic LDS and the kernel's one argument struct; every launch is checked.
 int launch(mca_hip_ctx *c, const void *kernel, dim3 grid, dim3 block, size_t lds, void *args, hipStream_t st, const char *form)
 {
     if (!kernel) return fail(c, MCA_HIP_ERR_UNSUPPORTED, std::string("the build has no kernel of the form ") + form);
-    if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void *argv[1] = {args};
+    if (const int rc = lds_limit(c, kernel, lds)) return rc;
     HIP_TRY(c, hipLaunchKernel(kernel, grid, block, argv, lds, st));
     HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
@@ -729,7 +711,7 @@ static int settle_history(mca_hip_ctx *c, hipStream_t st);    // lazy tails: exa
 
 const char *mca_hip_version(void) { return "mcarray-hip 0.1.0 (gfx950)"; }
 
-const char *mca_hip_last_error(const mca_hip_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+const char *mca_hip_last_error(const mca_hip_ctx *ctx) { return last_error(ctx); }
 
 // the tables, the state and the switches of a new context; on an error the caller (mca_hip_create) frees what was built
 static int init_ctx(mca_hip_ctx *c, const mca_hip_config *cfg, const hipDeviceProp_t &prop)
@@ -846,47 +828,43 @@ static int init_ctx(mca_hip_ctx *c, const mca_hip_config *cfg, const hipDevicePr
 
 int mca_hip_create(const mca_hip_config *cfg, mca_hip_ctx **out)
 {
-    if (!cfg || !out) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
+    if (!cfg || !out) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
     *out = nullptr;
     // Callers built against an earlier header pass its size: round 2 ended before gcc_weighting (PHAT), round 3 behind it -- that
     // struct was 60 bytes of fields padded to 64, and the padding is not read -- and the fields appended since default to zero.
     constexpr int size_r2 = (int)offsetof(mca_hip_config, gcc_weighting), size_r3 = (size_r2 + 4 + 7) / 8 * 8;
     static_assert(size_r3 <= (int)offsetof(mca_hip_config, adaptive_min_rows), "round-3 struct size");
     if (cfg->struct_size != (int)sizeof(mca_hip_config) && cfg->struct_size != size_r2 && cfg->struct_size != size_r3)
-        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+        return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     mca_hip_config cfg_full{};
     std::memcpy(&cfg_full, cfg, cfg->struct_size == size_r3 ? (size_t)offsetof(mca_hip_config, adaptive_fallback) : (size_t)cfg->struct_size);
     cfg_full.struct_size = (int)sizeof(mca_hip_config);
     cfg = &cfg_full;
     if (cfg->gcc_weighting != MCA_HIP_GCC_PHAT && cfg->gcc_weighting != MCA_HIP_GCC_NONE)
-        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "gcc_weighting must be MCA_HIP_GCC_PHAT or MCA_HIP_GCC_NONE");
+        return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "gcc_weighting must be MCA_HIP_GCC_PHAT or MCA_HIP_GCC_NONE");
     if (cfg->gcc_weighting == MCA_HIP_GCC_NONE && cfg->srp_precision != MCA_HIP_SRP_FP32)
-        return fail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "gcc_weighting NONE needs srp_precision MCA_HIP_SRP_FP32 (un-normalised spectra do not fit fp16 operands)");
-    if (cfg->n_mics < 2 || cfg->n_mics > MCA_MAX_MICS) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_mics must be in [2,16]");
-    if (!cfg->mic_xyz) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
-    if (cfg->n_sources < 1 || cfg->n_sources > MCA_MAX_SOURCES) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources must be in [1,4]");
-    if (cfg->fft_size < 16 || (cfg->fft_size & 1) || cfg->fft_size > 8192) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be even, 16..8192");
-    if (cfg->sample_rate <= 0) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
-    if (!(cfg->doa_step_deg > 0) || cfg->doa_step_deg > 45) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_step_deg must be in (0,45]");
-    if (cfg->srp_precision < 0 || cfg->srp_precision > 3) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "bad srp_precision");
-    if (cfg->max_arrays < 1) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "max_arrays < 1");
+        return fail(NO_CTX, MCA_HIP_ERR_UNSUPPORTED, "gcc_weighting NONE needs srp_precision MCA_HIP_SRP_FP32 (un-normalised spectra do not fit fp16 operands)");
+    if (cfg->n_mics < 2 || cfg->n_mics > MCA_MAX_MICS) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "n_mics must be in [2,16]");
+    if (!cfg->mic_xyz) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
+    if (cfg->n_sources < 1 || cfg->n_sources > MCA_MAX_SOURCES) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources must be in [1,4]");
+    if (cfg->fft_size < 16 || (cfg->fft_size & 1) || cfg->fft_size > 8192) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be even, 16..8192");
+    if (cfg->sample_rate <= 0) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
+    if (!(cfg->doa_step_deg > 0) || cfg->doa_step_deg > 45) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_step_deg must be in (0,45]");
+    if (cfg->srp_precision < 0 || cfg->srp_precision > 3) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "bad srp_precision");
+    if (cfg->max_arrays < 1) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "max_arrays < 1");
     if (cfg->adaptive_fallback != MCA_HIP_ADAPT_FALLBACK_AUTO && cfg->adaptive_fallback != MCA_HIP_ADAPT_FALLBACK_OFF)
-        return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_fallback must be MCA_HIP_ADAPT_FALLBACK_AUTO or _OFF");
-    if (cfg->adaptive_min_rows < 0 || cfg->adaptive_max_sources < 0) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_min_rows / adaptive_max_sources < 0");
+        return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_fallback must be MCA_HIP_ADAPT_FALLBACK_AUTO or _OFF");
+    if (cfg->adaptive_min_rows < 0 || cfg->adaptive_max_sources < 0) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "adaptive_min_rows / adaptive_max_sources < 0");
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, MCA_HIP_ERR_NO_DEVICE, "no HIP device visible; libmcarray_hip has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, MCA_HIP_ERR_HIP, "hipSetDevice failed");
+    if (const int rc = check_device(NO_CTX, cfg->device)) return rc;
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return fail(nullptr, MCA_HIP_ERR_HIP, "hipGetDeviceProperties failed");
+    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return fail(NO_CTX, MCA_HIP_ERR_HIP, "hipGetDeviceProperties failed");
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(nullptr, MCA_HIP_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+        return fail(NO_CTX, MCA_HIP_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
 
     mca_hip_ctx *c = new mca_hip_ctx();
     const int rc = init_ctx(c, cfg, prop);
-    if (rc) { g_create_error = c->err; free_ctx(c); return rc; }
+    if (rc) return create_failed(c, rc, free_ctx);
     *out = c;
     return MCA_HIP_OK;
 }
@@ -896,14 +874,13 @@ static void graph_orphan(mca_hip_graph *g);
 
 void mca_hip_destroy(mca_hip_ctx *ctx)
 {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->cfg.device);
-    (void)hipDeviceSynchronize();
-    // graphs that outlive their context: their recordings point into this context's buffers, so they go now; the handle
-    // stays valid for mca_hip_graph_destroy and fails cleanly in mca_hip_graph_launch
-    for (mca_hip_graph *g : ctx->graphs) graph_orphan(g);
-    ctx->graphs.clear();
-    free_ctx(ctx);
+    destroy_ctx(ctx, [](mca_hip_ctx *c) {
+        // graphs that outlive their context: their recordings point into this context's buffers, so they go now; the handle
+        // stays valid for mca_hip_graph_destroy and fails cleanly in mca_hip_graph_launch
+        for (mca_hip_graph *g : c->graphs) graph_orphan(g);
+        c->graphs.clear();
+        free_ctx(c);
+    });
 }
 
 int mca_hip_num_steps(const mca_hip_ctx *c) { return c ? c->D : MCA_HIP_ERR_INVALID_ARGUMENT; }
@@ -1811,7 +1788,7 @@ int mca_hip_graph_launch(mca_hip_graph *g, void *stream)
 {
     if (!g) return MCA_HIP_ERR_INVALID_ARGUMENT;
     mca_hip_ctx *c = g->c;
-    if (!c) { g_create_error = "mca_hip_graph_launch: the context of this graph has been destroyed"; return MCA_HIP_ERR_INVALID_ARGUMENT; }
+    if (!c) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_graph_launch: the context of this graph has been destroyed");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (g->doa_bin && c->hist_pending) {          // lazy tails: a recording takes the state as exact
         const int rc = settle_history(c, (hipStream_t)stream);
@@ -2015,13 +1992,13 @@ void mca_hip_host_free(void *p) { if (p) (void)hipHostFree(p); }
 int mca_hip_host_register(void *p, long long bytes)
 {
     if (!p || bytes <= 0) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); g_create_error = "hipHostRegister failed"; return MCA_HIP_ERR_HIP; }
+    if (hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); return fail(NO_CTX, MCA_HIP_ERR_HIP, "hipHostRegister failed"); }
     return MCA_HIP_OK;
 }
 int mca_hip_host_unregister(void *p)
 {
     if (!p) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (hipHostUnregister(p) != hipSuccess) { (void)hipGetLastError(); g_create_error = "hipHostUnregister failed"; return MCA_HIP_ERR_HIP; }
+    if (hipHostUnregister(p) != hipSuccess) { (void)hipGetLastError(); return fail(NO_CTX, MCA_HIP_ERR_HIP, "hipHostUnregister failed"); }
     return MCA_HIP_OK;
 }
 
@@ -2115,10 +2092,8 @@ static int gcc2_frames_impl(mca_hip_ctx *c, const float *pcm, long long array_st
     }
     const int nslot = GCC2_DOAWARM + ga.chunk;
     const size_t smem = (size_t)nslot * ((c->D + 3) / 4 * 4 + 4) * sizeof(float) + ((size_t)nslot * 5 + 1) * sizeof(float);
-    if (smem > 64 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_gcc2_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     dim3 g((n_frames + ga.chunk - 1) / ga.chunk, n_arrays);
-    hipLaunchKernelGGL(k_gcc2_scan, g, dim3(std::max(256, round_up(c->D, 64))), smem, st, ga);   // >= 4 waves: the per-frame argmax / min / sum is one wave per frame
+    if ((rc = launch_kernel(c, k_gcc2_scan, g, dim3(std::max(256, round_up(c->D, 64))), smem, st, ga))) return rc;   // >= 4 waves: the per-frame argmax / min / sum is one wave per frame
     if (gate) {
         Gcc2FillArgs fa{};
         fa.voiced = c->ws.d_voiced; fa.n_frames = n_frames; fa.D = c->D;
@@ -2168,24 +2143,15 @@ int mca_hip_gcc2_tracked_frames_host(mca_hip_ctx *c, const float *pcm, int n_arr
     if (n_arrays < 1 || n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays/n_frames < 1");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long ms = (long long)(n_frames + 1) * c->H, as = ms * c->M;
-    const size_t n_pcm = (size_t)as * n_arrays, n_f = (size_t)n_arrays * n_frames, n_corr = corr ? n_f * c->D : 0;
-    float *d_pcm = (float *)c->stage.get(0, n_pcm * 4), *d_rad = (float *)c->stage.get(2, n_f * 4), *d_prob = (float *)c->stage.get(3, n_f * 4);
-    float *d_corr = (float *)c->stage.get(4, n_corr * 4);
-    int *d_idx = (int *)c->stage.get(1, n_f * 4), *d_track = (int *)c->stage.get(5, n_f * 4);
-    unsigned char *d_fired = (unsigned char *)c->stage.get(6, n_f);
-    if (!d_pcm || !d_idx || !d_rad || !d_prob || !d_track || !d_fired || (corr && !d_corr))
-        return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    HIP_TRY(c, hipMemcpy(d_pcm, pcm, n_pcm * 4, hipMemcpyHostToDevice));
-    const int rc = mca_hip_gcc2_tracked_frames_dev(c, d_pcm, as, ms, n_arrays, n_frames, d_idx, d_rad, d_prob, d_fired, d_track, d_corr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(doa_rad, d_rad, n_f * 4, hipMemcpyDeviceToHost));
-    if (argmax) HIP_TRY(c, hipMemcpy(argmax, d_idx, n_f * 4, hipMemcpyDeviceToHost));
-    if (prob) HIP_TRY(c, hipMemcpy(prob, d_prob, n_f * 4, hipMemcpyDeviceToHost));
-    if (fired) HIP_TRY(c, hipMemcpy(fired, d_fired, n_f, hipMemcpyDeviceToHost));
-    if (track) HIP_TRY(c, hipMemcpy(track, d_track, n_f * 4, hipMemcpyDeviceToHost));
-    if (corr) HIP_TRY(c, hipMemcpy(corr, d_corr, n_corr * 4, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    const size_t n_pcm = (size_t)as * n_arrays, n_f = (size_t)n_arrays * n_frames;
+    // (the _dev call gets a buffer for every optional output but the rows, whatever the caller takes back)
+    StageBuf b[] = {{SG_PCM, pcm, n_pcm * 4, STAGE_IN}, {SG_DOA, doa_rad, n_f * 4, STAGE_OUT}, {SG_ARGMAX, argmax, n_f * 4, STAGE_OUT | STAGE_ALWAYS},
+                    {SG_PROB, prob, n_f * 4, STAGE_OUT | STAGE_ALWAYS}, {SG_FIRED, fired, n_f, STAGE_OUT | STAGE_ALWAYS}, {SG_TRACK, track, n_f * 4, STAGE_OUT | STAGE_ALWAYS},
+                    {SG_CORR, corr, n_f * c->D * 4, STAGE_OUT}};
+    return staged(c, b, [&] {
+        return mca_hip_gcc2_tracked_frames_dev(c, (float *)b[0].dev, as, ms, n_arrays, n_frames, (int *)b[2].dev, (float *)b[1].dev, (float *)b[3].dev, (unsigned char *)b[4].dev,
+                                               (int *)b[5].dev, (float *)b[6].dev, nullptr);
+    });
 }
 
 int mca_hip_gcc2_tracker_attach(mca_hip_ctx *c, const mca_hip_gcc2_tracker_config *cfg)
@@ -2244,21 +2210,13 @@ int mca_hip_gcc2_frames_host(mca_hip_ctx *c, const float *pcm, int n_arrays, int
     if (n_arrays < 1 || n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays/n_frames < 1");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long ms = (long long)(n_frames + 1) * c->H, as = ms * c->M;
-    const size_t n_pcm = (size_t)as * n_arrays, n_f = (size_t)n_arrays * n_frames, n_corr = corr ? n_f * c->D : 0;
-    float *d_pcm = (float *)c->stage.get(0, n_pcm * 4), *d_rad = (float *)c->stage.get(2, n_f * 4), *d_prob = (float *)c->stage.get(3, n_f * 4);
-    float *d_corr = (float *)c->stage.get(4, n_corr * 4);
-    int *d_idx = (int *)c->stage.get(1, n_f * 4);
-    if (!d_pcm || !d_idx || !d_rad || !d_prob || (corr && !d_corr))
-        return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    HIP_TRY(c, hipMemcpy(d_pcm, pcm, n_pcm * 4, hipMemcpyHostToDevice));
-    const int rc = mca_hip_gcc2_frames_dev(c, d_pcm, as, ms, n_arrays, n_frames, d_idx, d_rad, d_prob, d_corr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(argmax, d_idx, n_f * 4, hipMemcpyDeviceToHost));
-    if (doa_rad) HIP_TRY(c, hipMemcpy(doa_rad, d_rad, n_f * 4, hipMemcpyDeviceToHost));
-    if (prob) HIP_TRY(c, hipMemcpy(prob, d_prob, n_f * 4, hipMemcpyDeviceToHost));
-    if (corr) HIP_TRY(c, hipMemcpy(corr, d_corr, n_corr * 4, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    const size_t n_pcm = (size_t)as * n_arrays, n_f = (size_t)n_arrays * n_frames;
+    // (the _dev call gets a buffer for doa_rad and prob whatever the caller takes back)
+    StageBuf b[] = {{SG_PCM, pcm, n_pcm * 4, STAGE_IN}, {SG_ARGMAX, argmax, n_f * 4, STAGE_OUT}, {SG_DOA, doa_rad, n_f * 4, STAGE_OUT | STAGE_ALWAYS},
+                    {SG_PROB, prob, n_f * 4, STAGE_OUT | STAGE_ALWAYS}, {SG_CORR, corr, n_f * c->D * 4, STAGE_OUT}};
+    return staged(c, b, [&] {
+        return mca_hip_gcc2_frames_dev(c, (float *)b[0].dev, as, ms, n_arrays, n_frames, (int *)b[1].dev, (float *)b[2].dev, (float *)b[3].dev, (float *)b[4].dev, nullptr);
+    });
 }
 
 int mca_hip_copy_gate(mca_hip_ctx *c, unsigned char *voiced, float *power)
@@ -2374,7 +2332,7 @@ static int gcc2_prob_host(mca_hip_ctx *c, const TC *row, const double *doas, dou
 {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipDeviceSynchronize());
-    double *d_in = (double *)c->stage.get(5, (size_t)n * 8), *d_out = (double *)c->stage.get(6, (size_t)n * 8);
+    double *d_in = (double *)c->stage.get(SG_PROB_IN, (size_t)n * 8), *d_out = (double *)c->stage.get(SG_PROB_OUT, (size_t)n * 8);
     if (!d_in || !d_out) return fail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
     HIP_TRY(c, hipMemcpy(d_in, doas, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL((k_gcc2_prob<TC, double>), dim3((n + 255) / 256, 1), dim3(256), 0, 0, row, 0LL, c->D, c->step, c->d_grid, d_in, d_out, n);

@@ -3,9 +3,9 @@
 // (MultibandBinarualLocalisation.cpp:52-123), owns the per-array state, enqueues the kernels.  No CPU fallback.
 #include "../../include/mcarray_hip.h"
 #include "fft512.h"
+#include "host_common.h"
 #include "kernels.h"
-#include "stage.h"
-#include "state_blob.h"
+#include "module_plan.h"
 
 #include <cmath>
 #include <cstring>
@@ -33,37 +33,19 @@ struct mca_hip_mb_ctx {
 
 namespace {
 
-std::string g_mb_create_error;
-
-int bfail(mca_hip_mb_ctx *c, int code, const std::string &msg)
-{
-    if (c) c->err = msg; else g_mb_create_error = msg;
-    return code;
-}
-
-#define BHIP_TRY(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return bfail(ctx, _e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP,  \
-                         std::string(#expr) + ": " + hipGetErrorString(_e));                           \
-    } while (0)
-
-// what an allocation or an upload failed with: out of memory by its own code, `what` names the buffers
-int hip_fail(mca_hip_mb_ctx *c, hipError_t e, const char *what)
-{
-    return bfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+mca_hip_mb_ctx *const NO_CTX = nullptr;          // a failing create: the text goes to the module's creation error
+enum MbStageSlot { SG_PCM, SG_DOA, SG_PROB, SG_POWER, SG_VOICED, SG_BAND_IDX, SG_ENERGY, SG_BAND_CORR };      // the staging-pool slots of the host-pointer call: the numbers stay
+void free_mb(mca_hip_mb_ctx *c) { delete c; }      // every device buffer goes with its member
 
 int init_state(mca_hip_mb_ctx *c, hipStream_t st)
 {
     const size_t na = (size_t)c->cfg.max_arrays;
-    for (int i = 0; i < 2; ++i) BHIP_TRY(c, c->d_corr[i].zero_async(st));   // :106-110
-    BHIP_TRY(c, c->d_gate.zero_async(st));
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, c->d_corr[i].zero_async(st));   // :106-110
+    HIP_TRY(c, c->d_gate.zero_async(st));
     std::vector<float> cur(na * 2);
     for (size_t a = 0; a < na; ++a) { cur[2 * a] = 0.f; cur[2 * a + 1] = -1.f; }                            // :81-82
-    BHIP_TRY(c, hipMemcpyAsync(c->d_cur, cur.data(), cur.size() * 4, hipMemcpyHostToDevice, st));
-    BHIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_cur, cur.data(), cur.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
@@ -79,25 +61,22 @@ int ensure_ws(mca_hip_mb_ctx *c, size_t rows)
 
 extern "C" {
 
-const char *mca_hip_mb_last_error(const mca_hip_mb_ctx *ctx) { return ctx ? ctx->err.c_str() : g_mb_create_error.c_str(); }
+const char *mca_hip_mb_last_error(const mca_hip_mb_ctx *ctx) { return last_error(ctx); }
 
 int mca_hip_mb_create(const mca_hip_mb_config *cfg, mca_hip_mb_ctx **out)
 {
-    if (!cfg || !out) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
+    if (!cfg || !out) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
     *out = nullptr;
-    if (cfg->struct_size != (int)sizeof(mca_hip_mb_config)) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
-    if (cfg->fft_size < 64 || (cfg->fft_size & (cfg->fft_size - 1)) || cfg->fft_size > 8192) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be a power of two in [64,8192]");
-    if (cfg->sample_rate <= 0) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
-    if (!cfg->mic_xyz) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
-    if (cfg->nbins < 1 || cfg->nbins > 27) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "nbins must be in [1,27] (nbins x 37 delays <= 1024 threads)");
-    if (cfg->max_arrays < 1) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "max_arrays < 1");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mb_config)) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->fft_size < 64 || (cfg->fft_size & (cfg->fft_size - 1)) || cfg->fft_size > 8192) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be a power of two in [64,8192]");
+    if (cfg->sample_rate <= 0) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
+    if (!cfg->mic_xyz) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
+    if (cfg->nbins < 1 || cfg->nbins > 27) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "nbins must be in [1,27] (nbins x 37 delays <= 1024 threads)");
+    if (cfg->max_arrays < 1) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "max_arrays < 1");
     const double *x = cfg->mic_xyz;
     const double dist = std::sqrt(std::pow(x[3] - x[0], 2) + std::pow(x[4] - x[1], 2) + std::pow(x[5] - x[2], 2));   // distance(0,1) :61
-    if (!(dist > 0)) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "the two microphones coincide");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bfail(nullptr, MCA_HIP_ERR_NO_DEVICE, "no HIP device visible; libmcarray_hip has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return bfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    if (hipSetDevice(cfg->device) != hipSuccess) return bfail(nullptr, MCA_HIP_ERR_HIP, "hipSetDevice failed");
+    if (!(dist > 0)) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "the two microphones coincide");
+    if (const int rc = check_device(NO_CTX, cfg->device)) return rc;
 
     mca_hip_mb_ctx *c = new mca_hip_mb_ctx();
     c->cfg = *cfg; c->cfg.mic_xyz = nullptr;
@@ -155,18 +134,12 @@ int mca_hip_mb_create(const mca_hip_mb_config *cfg, mca_hip_mb_ctx **out)
         (e = c->d_T.upload(T.data(), T.size())) || (e = c->d_lo.upload(lo.data(), nb)) || (e = c->d_hi.upload(hi.data(), nb)) ||
         (e = c->d_corr[0].alloc_zero(na * nb * D)) || (e = c->d_corr[1].alloc_zero(na * nb * D)) ||
         (e = c->d_gate.alloc_zero(na * 4)) || (e = c->d_cur.alloc_zero(na * 2))) rc = hip_fail(c, e, "device memory for the tables and the state of the context");
-    if (rc || (rc = init_state(c, nullptr))) { g_mb_create_error = c->err; delete c; return rc; }
+    if (rc || (rc = init_state(c, nullptr))) return create_failed(c, rc, free_mb);
     *out = c;
     return MCA_HIP_OK;
 }
 
-void mca_hip_mb_destroy(mca_hip_mb_ctx *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->cfg.device);
-    (void)hipDeviceSynchronize();
-    delete c;                                 // every device buffer goes with its member
-}
+void mca_hip_mb_destroy(mca_hip_mb_ctx *c) { destroy_ctx(c, free_mb); }
 
 int mca_hip_mb_num_steps(const mca_hip_mb_ctx *c) { return c ? c->D : MCA_HIP_ERR_INVALID_ARGUMENT; }
 
@@ -180,7 +153,7 @@ int mca_hip_mb_get_filters(const mca_hip_mb_ctx *c, double *out)
 int mca_hip_mb_reset(mca_hip_mb_ctx *c, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    BHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     return init_state(c, (hipStream_t)stream);
 }
 
@@ -189,14 +162,14 @@ int mca_hip_mb_frames_dev(mca_hip_mb_ctx *c, const float *pcm, long long array_s
                           float *energy_in_doa, float *band_corr, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!pcm || !doa_rad || !prob) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev / prob_dev is NULL");
-    if (n_arrays < 1 || n_arrays > c->cfg.max_arrays) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays outside [1, max_arrays]");
-    if (n_frames < 1) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+    if (!pcm || !doa_rad || !prob) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev / prob_dev is NULL");
+    if (n_arrays < 1 || n_arrays > c->cfg.max_arrays) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays outside [1, max_arrays]");
+    if (n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
     const long long need = (long long)(n_frames + 1) * c->H;
-    if (ch_stride < need) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "ch_stride shorter than (n_frames+1)*hop samples");
-    if (n_arrays > 1 && array_stride < ch_stride + need) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "array_stride too short");
+    if (ch_stride < need) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "ch_stride shorter than (n_frames+1)*hop samples");
+    if (n_arrays > 1 && array_stride < ch_stride + need) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "array_stride too short");
     if ((ch_stride & 1) || (array_stride & 1) || (reinterpret_cast<uintptr_t>(pcm) & 7))
-        return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
     hipStream_t st = (hipStream_t)stream;
     int rc = ensure_ws(c, (size_t)n_arrays * n_frames);
     if (rc) return rc;
@@ -206,41 +179,21 @@ int mca_hip_mb_frames_dev(mca_hip_mb_ctx *c, const float *pcm, long long array_s
     aa.N = c->N; aa.logH = c->logH; aa.nbins = c->nb; aa.D = c->D;
     aa.window = c->d_window; aa.tw = c->d_tw; aa.coef = c->d_coef; aa.lo = c->d_lo; aa.hi = c->d_hi; aa.T = c->d_T;
     aa.raw = c->d_raw; aa.band_energy = c->d_be; aa.p_full = c->d_pf; aa.p_half = c->d_ph;
-    if (c->N == FFT_N) {
-        // 1024-sample frames: wave-level FFT, 4 frames x 2 channels per pass
-        int fpb = 16;
-        while (fpb > 4 && (long long)n_arrays * ((n_frames + fpb - 1) / fpb) < 512) fpb >>= 1;
-        const size_t smem1 = (size_t)8 * FFT_SCRATCH * 8 + (size_t)4 * 520 * (8 + 4) + (size_t)TW_WORDS * 8 + 16 * 4;
-        BHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mb_analyse_1024), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
-        hipLaunchKernelGGL(k_mb_analyse_1024, dim3((n_frames + fpb - 1) / fpb, n_arrays), dim3(512), smem1, st, aa, fpb);
-    } else if (c->N == 512) {
-        // 512-sample frames: both channels of a frame in one 512-point complex transform, 8 frames per pass
-        int fpb = 32;
-        while (fpb > 8 && (long long)n_arrays * ((n_frames + fpb - 1) / fpb) < 512) fpb >>= 1;
-        const size_t smem1 = (size_t)(16 * 258 + 8 * FFT_SCRATCH + TW_WIN) * 8 + 16 * 4;
-        BHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mb_analyse_512), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
-        hipLaunchKernelGGL(k_mb_analyse_512, dim3((n_frames + fpb - 1) / fpb, n_arrays), dim3(512), smem1, st, aa, fpb);
-    } else {
-        const size_t smem1 = (size_t)2 * (c->H + 1) * 8 + (size_t)c->K * 8 + (size_t)c->K * 4 + 8 * 4;
-        if (smem1 > 64 * 1024)
-            BHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mb_analyse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1));
-        hipLaunchKernelGGL(k_mb_analyse, dim3(n_frames, n_arrays), dim3(256), smem1, st, aa);
-    }
+    const MbAnalysePlan pa = plan_mb_analyse(c->N, n_arrays, n_frames);
+    if (pa.form == FORM_GEN) rc = launch_kernel(c, k_mb_analyse, pa.l.grid, pa.l.block, pa.l.lds, st, aa);
+    else rc = launch_kernel(c, pa.form == FORM_A ? k_mb_analyse_1024 : k_mb_analyse_512, pa.l.grid, pa.l.block, pa.l.lds, st, aa, pa.fpb);
+    if (rc) return rc;
 
     MbScanArgs sa{};
     sa.raw = c->d_raw; sa.band_energy = c->d_be; sa.n_frames = n_frames; sa.nbins = c->nb; sa.D = c->D;
-    // frames per chunk: every chunk re-reads 24 warm-up frames; its smoothed correlations stay in LDS (chunk x nbins x D floats)
-    sa.chunk = (size_t)32 * (c->nb * c->D + c->D + c->nb) * 4 <= 80 * 1024 ? 32 : 16;
+    const MbScanPlan ps = plan_mb_scan(c->nb, c->D, n_arrays, n_frames);
+    sa.chunk = ps.chunk;
     const float mem = 0.4f;                                                     // _corrMemoryFactor (MultibandBinarualLocalisation.h:46)
     sa.mem = mem; sa.one_minus_mem = 1 - mem;
     sa.corr_in = c->d_corr[c->corr_cur]; sa.corr_out = c->d_corr[c->corr_cur ^ 1];
     sa.hist_idx = c->d_hidx; sa.hist_prob = c->d_hprob;
     sa.band_idx = band_idx; sa.energy_in_doa = energy_in_doa; sa.band_corr = band_corr;
-    const int BD = c->nb * c->D;
-    const size_t smem2 = (size_t)sa.chunk * (BD + c->D) * 4 + (size_t)sa.chunk * c->nb * 4;
-    if (smem2 > 64 * 1024)
-        BHIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_mb_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2));
-    hipLaunchKernelGGL(k_mb_scan, dim3((n_frames + sa.chunk - 1) / sa.chunk, n_arrays), dim3((BD + 63) / 64 * 64), smem2, st, sa);
+    if ((rc = launch_kernel(c, k_mb_scan, ps.l.grid, ps.l.block, ps.l.lds, st, sa))) return rc;
 
     MbSummaryArgs ma{};
     ma.p_full = c->d_pf; ma.p_half = c->d_ph; ma.hist_idx = c->d_hidx; ma.hist_prob = c->d_hprob;
@@ -248,8 +201,9 @@ int mca_hip_mb_frames_dev(mca_hip_mb_ctx *c, const float *pcm, long long array_s
     ma.use_floor = c->cfg.use_power_floor; ma.margin_db = 3.0f;                 // _noiseMarginDB (.h:47)
     ma.grid = c->d_grid; ma.gate = c->d_gate; ma.cur = c->d_cur;
     ma.doa_rad = doa_rad; ma.prob = prob; ma.power = power; ma.voiced = voiced;
-    hipLaunchKernelGGL(k_mb_summary, dim3(n_arrays), dim3(256), 0, st, ma);
-    BHIP_TRY(c, hipGetLastError());
+    const Launch pm = plan_mb_summary(n_arrays);
+    if ((rc = launch_kernel(c, k_mb_summary, pm.grid, pm.block, pm.lds, st, ma))) return rc;
+    HIP_TRY(c, hipGetLastError());
     c->corr_cur ^= 1;
     return MCA_HIP_OK;
 }
@@ -269,57 +223,35 @@ unsigned mb_cfg_hash(const mca_hip_mb_ctx *c)
 }  // namespace
 }  // extern "C++"
 
-long long mca_hip_mb_state_size(const mca_hip_mb_ctx *c)
-{
-    return c ? blob_size(mb_parts(const_cast<mca_hip_mb_ctx *>(c))) : (long long)MCA_HIP_ERR_INVALID_ARGUMENT;
-}
+long long mca_hip_mb_state_size(const mca_hip_mb_ctx *c) { return state_size(c, c ? mb_parts(const_cast<mca_hip_mb_ctx *>(c)) : std::vector<BlobPart>()); }
 
 int mca_hip_mb_state_save(mca_hip_mb_ctx *c, void *blob, long long bytes)
 {
-    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    BHIP_TRY(c, hipSetDevice(c->cfg.device));
-    BlobHeader h{MB_MAGIC, 1, mb_cfg_hash(c), 0, {0, 0, 0, 0}};
-    const int rc = blob_save(mb_parts(c), h, blob, bytes);
-    return rc ? bfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
+    return c ? state_save(c, mb_parts(c), BlobHeader{MB_MAGIC, 1, mb_cfg_hash(c), 0, {0, 0, 0, 0}}, blob, bytes) : MCA_HIP_ERR_INVALID_ARGUMENT;
 }
 
 int mca_hip_mb_state_load(mca_hip_mb_ctx *c, const void *blob, long long bytes)
 {
-    if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    BHIP_TRY(c, hipSetDevice(c->cfg.device));
     BlobHeader h;
-    const int rc = blob_load(mb_parts(c), MB_MAGIC, mb_cfg_hash(c), blob, bytes, &h);
-    return rc ? bfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
+    return c ? state_load(c, mb_parts(c), MB_MAGIC, 1, mb_cfg_hash(c), blob, bytes, &h) : MCA_HIP_ERR_INVALID_ARGUMENT;
 }
 
 int mca_hip_mb_frames_host(mca_hip_mb_ctx *c, const float *pcm, int n_arrays, int n_frames, float *doa_rad, float *prob,
                            unsigned char *voiced, float *power, int *band_idx, float *energy_in_doa, float *band_corr)
 {
-    if (!c || !pcm || !doa_rad || !prob) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_arrays < 1 || n_frames < 1) return bfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays/n_frames < 1");
-    BHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c || !pcm || !doa_rad || !prob) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_arrays < 1 || n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_arrays/n_frames < 1");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long cs = (long long)(n_frames + 1) * c->H, as = 2 * cs;
     const size_t nf = (size_t)n_arrays * n_frames;
-    const size_t n_bi = band_idx ? nf * c->nb : 0, n_eid = energy_in_doa ? nf * c->D : 0, n_bc = band_corr ? nf * c->nb * c->D : 0;
-    float *d_pcm = (float *)c->stage.get(0, (size_t)as * n_arrays * 4), *d_rad = (float *)c->stage.get(1, nf * 4);
-    float *d_prob = (float *)c->stage.get(2, nf * 4), *d_pow = (float *)c->stage.get(3, nf * 4);
-    unsigned char *d_v = (unsigned char *)c->stage.get(4, nf);
-    int *d_bi = (int *)c->stage.get(5, n_bi * 4);
-    float *d_eid = (float *)c->stage.get(6, n_eid * 4), *d_bc = (float *)c->stage.get(7, n_bc * 4);
-    if (!d_pcm || !d_rad || !d_prob || !d_pow || !d_v || (band_idx && !d_bi) || (energy_in_doa && !d_eid) || (band_corr && !d_bc))
-        return bfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, "device staging buffers for the host-pointer call");
-    BHIP_TRY(c, hipMemcpy(d_pcm, pcm, (size_t)as * n_arrays * 4, hipMemcpyHostToDevice));
-    const int rc = mca_hip_mb_frames_dev(c, d_pcm, as, cs, n_arrays, n_frames, d_rad, d_prob, d_v, d_pow, d_bi, d_eid, d_bc, nullptr);
-    if (rc) return rc;
-    BHIP_TRY(c, hipDeviceSynchronize());
-    BHIP_TRY(c, hipMemcpy(doa_rad, d_rad, nf * 4, hipMemcpyDeviceToHost));
-    BHIP_TRY(c, hipMemcpy(prob, d_prob, nf * 4, hipMemcpyDeviceToHost));
-    if (voiced) BHIP_TRY(c, hipMemcpy(voiced, d_v, nf, hipMemcpyDeviceToHost));
-    if (power) BHIP_TRY(c, hipMemcpy(power, d_pow, nf * 4, hipMemcpyDeviceToHost));
-    if (band_idx) BHIP_TRY(c, hipMemcpy(band_idx, d_bi, n_bi * 4, hipMemcpyDeviceToHost));
-    if (energy_in_doa) BHIP_TRY(c, hipMemcpy(energy_in_doa, d_eid, n_eid * 4, hipMemcpyDeviceToHost));
-    if (band_corr) BHIP_TRY(c, hipMemcpy(band_corr, d_bc, n_bc * 4, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
+    // (the _dev call gets a buffer for voiced and power whatever the caller takes back)
+    StageBuf b[] = {{SG_PCM, pcm, (size_t)as * n_arrays * 4, STAGE_IN}, {SG_DOA, doa_rad, nf * 4, STAGE_OUT}, {SG_PROB, prob, nf * 4, STAGE_OUT},
+                    {SG_VOICED, voiced, nf, STAGE_OUT | STAGE_ALWAYS}, {SG_POWER, power, nf * 4, STAGE_OUT | STAGE_ALWAYS}, {SG_BAND_IDX, band_idx, nf * c->nb * 4, STAGE_OUT},
+                    {SG_ENERGY, energy_in_doa, nf * c->D * 4, STAGE_OUT}, {SG_BAND_CORR, band_corr, nf * c->nb * c->D * 4, STAGE_OUT}};
+    return staged(c, b, [&] {
+        return mca_hip_mb_frames_dev(c, (float *)b[0].dev, as, cs, n_arrays, n_frames, (float *)b[1].dev, (float *)b[2].dev, (unsigned char *)b[3].dev, (float *)b[4].dev,
+                                     (int *)b[5].dev, (float *)b[6].dev, (float *)b[7].dev, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -4,10 +4,9 @@
 // kernels_mvdr*.hip and mvdr_solve.h.  Every launch is a plan (mvdr_plan.h: kernel form, grid, block, LDS, workspace sizes) handed to the one launch(); the
 // kernels are looked up beside their code (kernels.h); a host-pointer call lists its buffers for the one staging helper (staged).  No CPU fallback.
 #include "../../include/mcarray_hip.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "mvdr_plan.h"
-#include "stage.h"
-#include "state_blob.h"
 
 #include <algorithm>
 #include <cmath>
@@ -123,27 +122,7 @@ struct mca_hip_mvdr_ctx : MvdrShape {
 
 namespace {
 
-std::string g_mvdr_create_error;
-
-int vfail(mca_hip_mvdr_ctx *c, int code, const std::string &msg)
-{
-    if (c) c->err = msg; else g_mvdr_create_error = msg;
-    return code;
-}
-
-#define VHIP_TRY(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return vfail(ctx, _e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP,  \
-                         std::string(#expr) + ": " + hipGetErrorString(_e));                           \
-    } while (0)
-
-// what an allocation or a copy of a configuration step failed with: out of memory by its own code, `what` names the buffers
-int hip_fail(mca_hip_mvdr_ctx *c, hipError_t e, const char *what)
-{
-    return vfail(c, e == hipErrorOutOfMemory ? MCA_HIP_ERR_OUT_OF_MEMORY : MCA_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+mca_hip_mvdr_ctx *const NO_CTX = nullptr;        // a failing create: the text goes to the module's creation error
 
 void free_mvdr(mca_hip_mvdr_ctx *c)
 {
@@ -159,7 +138,7 @@ inline size_t slot_elems(const mca_hip_mvdr_ctx *c, int slots, size_t row) { ret
 template <typename T>
 int grow_ws(mca_hip_mvdr_ctx *c, DevBuf<T> &b, size_t n, const char *what, bool wait = false)
 {
-    if (wait && n > b.n) VHIP_TRY(c, hipDeviceSynchronize());
+    if (wait && n > b.n) HIP_TRY(c, hipDeviceSynchronize());
     const hipError_t e = b.grow(n);
     return e == hipSuccess ? MCA_HIP_OK : hip_fail(c, e, what);
 }
@@ -248,17 +227,17 @@ void host_phasors(double u, int nhi, int nph, float2 *T, size_t stride)
 // every state array from nothing (those of a feature that is off are empty, and cleared as such)
 int init_state(mca_hip_mvdr_ctx *c, hipStream_t st)
 {
-    VHIP_TRY(c, c->d_phi.zero_async(st));
-    VHIP_TRY(c, c->d_trace.zero_async(st));
-    for (int i = 0; i < 2; ++i) VHIP_TRY(c, c->d_tail[i].zero_async(st));
-    VHIP_TRY(c, c->d_pf_A.zero_async(st));
-    VHIP_TRY(c, c->d_psi.zero_async(st));
-    VHIP_TRY(c, c->d_cpsi.zero_async(st));
-    VHIP_TRY(c, c->d_cphi.zero_async(st));
-    VHIP_TRY(c, c->d_trk_theta.zero_async(st));
-    VHIP_TRY(c, c->d_trk_int.zero_async(st));
-    VHIP_TRY(c, c->d_trk_eps.zero_async(st));
-    VHIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, c->d_phi.zero_async(st));
+    HIP_TRY(c, c->d_trace.zero_async(st));
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, c->d_tail[i].zero_async(st));
+    HIP_TRY(c, c->d_pf_A.zero_async(st));
+    HIP_TRY(c, c->d_psi.zero_async(st));
+    HIP_TRY(c, c->d_cpsi.zero_async(st));
+    HIP_TRY(c, c->d_cphi.zero_async(st));
+    HIP_TRY(c, c->d_trk_theta.zero_async(st));
+    HIP_TRY(c, c->d_trk_int.zero_async(st));
+    HIP_TRY(c, c->d_trk_eps.zero_async(st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     return MCA_HIP_OK;
 }
 
@@ -308,12 +287,12 @@ void t_end(mca_hip_mvdr_ctx *c, hipStream_t st)
     (void)hipEventRecord(c->events.back().b, st);
 }
 
-// The one launcher of the MVDR path: a kernel (the lookups of kernels.h, or kptr), a plan's grid, block and dynamic LDS, and the kernel's argument struct (arg2:
-// the second argument of the two kernels that take one).  The attribute is set exactly above the 64 KiB every kernel may have.  slot: the timing slot whose events bracket the
+// The launcher of the MVDR path, on the attribute rule of host_common.h (lds_limit): a kernel (the lookups of kernels.h, or kptr), a plan's grid, block and dynamic LDS, and the kernel's argument struct (arg2:
+// the second argument of the two kernels that take one).  slot: the timing slot whose events bracket the
 // launch; T_NONE inside a stage of several launches, which keeps one pair around all of them (t_begin / t_end).  Launch errors surface at the call's hipGetLastError.
 int launch(mca_hip_mvdr_ctx *c, const void *kernel, dim3 grid, dim3 block, int lds, void *args, MvdrTimer slot, hipStream_t st, void *arg2 = nullptr)
 {
-    if (lds > 64 * 1024) VHIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (const int rc = lds_limit(c, kernel, (size_t)lds)) return rc;      // (outside the events, and before any is recorded)
     void *kargs[2] = {args, arg2};
     if (slot != T_NONE) t_begin(c, slot, st);
     (void)hipLaunchKernel(kernel, grid, block, kargs, (size_t)lds, st);
@@ -352,51 +331,30 @@ enum MvdrStageSlot {
     SG_TARGET_MASK = 9,   // the frames calls: the target masks, taken or (auto call) handed back
 };
 static_assert(SG_TARGET_MASK + 1 == StagePool::N, "a slot per buffer of the pool");
-// One buffer of a host-pointer call: host NULL: an optional one the caller leaves out, nothing staged; bytes 0: nothing staged, no error
-enum StageDir { STAGE_IN = 1, STAGE_OUT = 2 };
-struct StageBuf { MvdrStageSlot slot; const void *host; size_t bytes; int dir; void *dev; };
-// A host-pointer call on its listed buffers: the device copies, the inputs copied in the list's order, the _dev call on the null
-// stream (it reads StageBuf::dev), the wait, the outputs copied in the list's order
-template <size_t NB, class DevCall>
-int staged(mca_hip_mvdr_ctx *c, StageBuf (&bufs)[NB], DevCall &&dev_call)
-{
-    for (StageBuf &b : bufs)
-        if (b.host && b.bytes && !(b.dev = c->stage.get(b.slot, b.bytes)))
-            return vfail(c, MCA_HIP_ERR_OUT_OF_MEMORY, NB == 1 ? "device staging buffer for the host-pointer call" : "device staging buffers for the host-pointer call");
-    for (StageBuf &b : bufs)
-        if (b.dev && (b.dir & STAGE_IN)) VHIP_TRY(c, hipMemcpy(b.dev, b.host, b.bytes, hipMemcpyHostToDevice));
-    if (const int rc = dev_call()) return rc;
-    VHIP_TRY(c, hipDeviceSynchronize());
-    for (StageBuf &b : bufs)
-        if (b.dev && (b.dir & STAGE_OUT)) VHIP_TRY(c, hipMemcpy(const_cast<void *>(b.host), b.dev, b.bytes, hipMemcpyDeviceToHost));
-    return MCA_HIP_OK;
-}
+// (a host-pointer call lists its buffers for staged, host_common.h: host NULL means nothing staged)
 
 }  // namespace
 
 extern "C" {
 
-const char *mca_hip_mvdr_last_error(const mca_hip_mvdr_ctx *ctx) { return ctx ? ctx->err.c_str() : g_mvdr_create_error.c_str(); }
+const char *mca_hip_mvdr_last_error(const mca_hip_mvdr_ctx *ctx) { return last_error(ctx); }
 
 int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
 {
-    if (!cfg || !out) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
+    if (!cfg || !out) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg/out is NULL");
     *out = nullptr;
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_config)) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_config)) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     if (cfg->fft_size < 64 || (cfg->fft_size & (cfg->fft_size - 1)) || cfg->fft_size > 8192)
-        return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be a power of two in [64,8192]");
-    if (cfg->sample_rate <= 0) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
-    if (cfg->n_mics < 2 || cfg->n_mics > 16) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "n_mics must be in [2,16]");
-    if (!cfg->mic_xyz) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
-    if (!(cfg->alpha >= 0.0 && cfg->alpha < 1.0)) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "alpha must be in [0,1)");
-    if (!(cfg->loading > 0.0)) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "loading must be > 0 (the first M-1 covariances of a stream are rank deficient)");
-    if (cfg->max_streams < 1) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "max_streams < 1");
+        return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "fft_size must be a power of two in [64,8192]");
+    if (cfg->sample_rate <= 0) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "sample_rate <= 0");
+    if (cfg->n_mics < 2 || cfg->n_mics > 16) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "n_mics must be in [2,16]");
+    if (!cfg->mic_xyz) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_xyz is NULL");
+    if (!(cfg->alpha >= 0.0 && cfg->alpha < 1.0)) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "alpha must be in [0,1)");
+    if (!(cfg->loading > 0.0)) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "loading must be > 0 (the first M-1 covariances of a stream are rank deficient)");
+    if (cfg->max_streams < 1) return fail(NO_CTX, MCA_HIP_ERR_INVALID_ARGUMENT, "max_streams < 1");
     if ((size_t)cfg->n_mics * (cfg->fft_size / 2 + 1) * 8 > 160 * 1024)
-        return vfail(nullptr, MCA_HIP_ERR_UNSUPPORTED, "n_mics spectra of N/2+1 bins exceed the 160 KiB LDS of a CU");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return vfail(nullptr, MCA_HIP_ERR_NO_DEVICE, "no HIP device visible; libmcarray_hip has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return vfail(nullptr, MCA_HIP_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    if (hipSetDevice(cfg->device) != hipSuccess) return vfail(nullptr, MCA_HIP_ERR_HIP, "hipSetDevice failed");
+        return fail(NO_CTX, MCA_HIP_ERR_UNSUPPORTED, "n_mics spectra of N/2+1 bins exceed the 160 KiB LDS of a CU");
+    if (const int rc = check_device(NO_CTX, cfg->device)) return rc;
 
     mca_hip_mvdr_ctx *c = new mca_hip_mvdr_ctx();
     c->cfg = *cfg; c->cfg.mic_xyz = nullptr;
@@ -429,33 +387,27 @@ int mca_hip_mvdr_create(const mca_hip_mvdr_config *cfg, mca_hip_mvdr_ctx **out)
     if (e == hipSuccess) e = c->d_trace_tail.alloc((size_t)128 * 64);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = c->d_tail[i].alloc(slot_elems(c, c->max_sources, c->H));
     const int rc = e != hipSuccess ? hip_fail(c, e, "tables and state of the context") : init_state(c, nullptr);
-    if (rc) { g_mvdr_create_error = c->err; free_mvdr(c); return rc; }
+    if (rc) return create_failed(c, rc, free_mvdr);
     *out = c;
     return MCA_HIP_OK;
 }
 
-void mca_hip_mvdr_destroy(mca_hip_mvdr_ctx *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->cfg.device);
-    (void)hipDeviceSynchronize();
-    free_mvdr(c);
-}
+void mca_hip_mvdr_destroy(mca_hip_mvdr_ctx *c) { destroy_ctx(c, free_mvdr); }
 
 int mca_hip_mvdr_reset(mca_hip_mvdr_ctx *c, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     return init_state(c, (hipStream_t)stream);
 }
 
 int mca_hip_mvdr_set_max_sources(mca_hip_mvdr_ctx *c, int max_sources)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (max_sources < 1 || max_sources > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_sources must be in [1,4]");
+    if (max_sources < 1 || max_sources > MCA_MAX_SOURCES) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_sources must be in [1,4]");
     if (max_sources == c->max_sources) return MCA_HIP_OK;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
     // every array [max_streams][max_sources][...] is built anew by the slot rule (reslot) and swapped in once all of them stand:
     // a failure leaves the context as it was.  The tail that is not current starts at zero
     const int old = c->max_sources;
@@ -483,7 +435,7 @@ int mca_hip_mvdr_set_null_gain(mca_hip_mvdr_ctx *c, double null_gain)
     // the cap: the denominator of the nulled output cancels by up to 1 + null_gain, and fp32 eps (1 + 1000) stays an order of
     // magnitude under the module's 5e-4 parity bar
     if (!std::isfinite(null_gain) || null_gain < 0.0 || null_gain > 1000.0)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "null_gain must be finite and in [0,1000]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "null_gain must be finite and in [0,1000]");
     c->null_gain = null_gain;
     return MCA_HIP_OK;
 }
@@ -498,7 +450,7 @@ int mca_hip_mvdr_get_null_gain(const mca_hip_mvdr_ctx *c, double *null_gain)
 int mca_hip_mvdr_set_rtf_nulls(mca_hip_mvdr_ctx *c, int enable)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (enable != 0 && enable != 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
+    if (enable != 0 && enable != 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
     c->rtf_nulls = enable == 1;
     return MCA_HIP_OK;
 }
@@ -513,17 +465,17 @@ int mca_hip_mvdr_get_rtf_nulls(const mca_hip_mvdr_ctx *c, int *enable)
 int mca_hip_mvdr_set_geometry(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_geometry_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_geometry_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_geometry_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     if (cfg->mode != MCA_HIP_MVDR_GEOMETRY_LINEAR_X && cfg->mode != MCA_HIP_MVDR_GEOMETRY_XYZ)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mode must be 0 (linear, x only) or 1 (xyz)");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mode must be 0 (linear, x only) or 1 (xyz)");
     if (!std::isfinite(cfg->elevation_rad) || std::fabs(cfg->elevation_rad) > M_PI / 2)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "elevation_rad must be finite and in [-pi/2, pi/2]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "elevation_rad must be finite and in [-pi/2, pi/2]");
     // LINEAR_X ignores the elevation: it is kept as 0 there, so that setting it is no change
     const double el = cfg->mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? cfg->elevation_rad : 0.0;
     if (cfg->mode == c->geo_mode && el == c->geo_elevation) return MCA_HIP_OK;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the tables of the former geometry
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the tables of the former geometry
     c->geo_mode = cfg->mode; c->geo_elevation = el;
     if (const hipError_t e = reset_elevations(c)) return hip_fail(c, e, "elevations of the look-direction slots");   // unset: the new pair
     c->spec_set = false;                                       // its phasor table and grid are stale (freed by the next configure)
@@ -543,18 +495,18 @@ int mca_hip_mvdr_get_geometry(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_geometry_c
 int mca_hip_mvdr_set_postfilter(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_postfilter_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_postfilter_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_postfilter_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     if (!std::isfinite(cfg->smoothing) || cfg->smoothing < 0.0 || cfg->smoothing >= 1.0)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "smoothing must be finite and in [0,1)");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "smoothing must be finite and in [0,1)");
     if (!std::isfinite(cfg->gain_floor) || cfg->gain_floor < 0.0 || cfg->gain_floor > 1.0)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "gain_floor must be finite and in [0,1]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "gain_floor must be finite and in [0,1]");
     if (!std::isfinite(cfg->noise_scale) || !(cfg->noise_scale > 0.0) || cfg->noise_scale > 100.0)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "noise_scale must be finite and in (0,100]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "noise_scale must be finite and in (0,100]");
     const bool on = cfg->enable != 0;
     if (on != c->pf_on) {
-        VHIP_TRY(c, hipSetDevice(c->cfg.device));
-        VHIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        HIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
         if (on) {
             // A starts from zero; the noise plane and the ones come with the first call (ensure_ws)
             DevBuf<float> na;
@@ -582,18 +534,18 @@ int mca_hip_mvdr_get_postfilter(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_postfilt
 int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_rtf_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_rtf_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_rtf_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     if (!std::isfinite(cfg->target_alpha) || cfg->target_alpha < 0.0 || cfg->target_alpha >= 1.0)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "target_alpha must be finite and in [0,1)");
-    if (cfg->iterations < 1 || cfg->iterations > 4) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "iterations must be in [1,4]");
-    if (cfg->ref_mic < 0 || cfg->ref_mic >= c->M) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "ref_mic must be in [0, n_mics)");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "target_alpha must be finite and in [0,1)");
+    if (cfg->iterations < 1 || cfg->iterations > 4) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "iterations must be in [1,4]");
+    if (cfg->ref_mic < 0 || cfg->ref_mic >= c->M) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "ref_mic must be in [0, n_mics)");
     if (!std::isfinite(cfg->min_share) || cfg->min_share < 0.0 || cfg->min_share >= 1.0)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_share must be finite and in [0,1)");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_share must be finite and in [0,1)");
     const bool on = cfg->enable != 0;
     if (on != c->rtf_on) {
-        VHIP_TRY(c, hipSetDevice(c->cfg.device));
-        VHIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        HIP_TRY(c, hipDeviceSynchronize());                   // no call in flight reads what is freed here
         if (on) {
             // Psi = 0, cpsi = 0; cphi = 1 where the covariance holds something (its weights were not counted: taken as complete)
             DevBuf<float2> npsi;
@@ -621,7 +573,7 @@ int mca_hip_mvdr_set_rtf(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_rtf_config *cfg
 int mca_hip_mvdr_set_rtf_workspace(mca_hip_mvdr_ctx *c, long long max_bytes)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (max_bytes < 8) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_bytes must be at least 8");
+    if (max_bytes < 8) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_bytes must be at least 8");
     c->plane_cap_cells = (size_t)(max_bytes / 8);          // (a plane already held stays until a call needs a larger one)
     return MCA_HIP_OK;
 }
@@ -638,19 +590,19 @@ int mca_hip_mvdr_get_rtf(const mca_hip_mvdr_ctx *c, mca_hip_mvdr_rtf_config *cfg
 int mca_hip_mvdr_set_mask_estimator(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_estmask_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_estmask_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_estmask_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
     if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
     if (!std::isfinite(cfg->coherence_lo) || !std::isfinite(cfg->coherence_hi) || cfg->coherence_lo < 0.0 || cfg->coherence_hi > 1.0 ||
         !(cfg->coherence_hi - cfg->coherence_lo >= 1e-3))
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the thresholds must be finite with 0 <= coherence_lo, coherence_hi <= 1 and coherence_hi - coherence_lo >= 1e-3");
-    if (cfg->n_protected < 0 || cfg->n_protected > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_protected must be in [0,4]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the thresholds must be finite with 0 <= coherence_lo, coherence_hi <= 1 and coherence_hi - coherence_lo >= 1e-3");
+    if (cfg->n_protected < 0 || cfg->n_protected > MCA_MAX_SOURCES) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_protected must be in [0,4]");
     const bool on = cfg->enable != 0;
     if (on != c->em_on) {
         if (!on) {
-            VHIP_TRY(c, hipSetDevice(c->cfg.device));
-            VHIP_TRY(c, hipDeviceSynchronize());               // no call in flight reads what is freed here
+            HIP_TRY(c, hipSetDevice(c->cfg.device));
+            HIP_TRY(c, hipDeviceSynchronize());               // no call in flight reads what is freed here
             c->d_em_update.reset(); c->d_em_target.reset();
         }
         c->em_on = on;                                         // (the workspace comes with the first auto call: ensure_estmask_ws)
@@ -729,7 +681,7 @@ int launch_solve(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStream_t 
     }
     int lds = 0;                                                // the lookup's; the plan's (mvdr_solve_lds) is what the CPU table pins: one value
     const void *const kernel = mvdr_solve_kernel(choice, lds);
-    if (!kernel || lds != mvdr_solve_lds(choice)) return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
+    if (!kernel || lds != mvdr_solve_lds(choice)) return fail(c, MCA_HIP_ERR_UNSUPPORTED, "no MVDR solve kernel for this call in the build");
     const MvdrSolveSplit sp = plan_mvdr_solve_split(*c, n_streams, n_loop);
     auto piece = [&](long long pid0, long long n_prob, int pieces, dim3 grid) {
         sa.pid0 = pid0; sa.n_prob = n_prob; sa.pieces = pieces;
@@ -741,8 +693,8 @@ int launch_solve(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStream_t 
     piece(0, sp.main_prob, 1, sp.grid);
     if (sp.scratch) {
         piece(sp.main_prob, sp.tail_prob, sp.pieces, sp.tail_grid);
-        VHIP_TRY(c, hipMemcpyAsync(c->d_phi + sp.main_prob * c->tri, c->d_phi_tail, (size_t)sp.tail_prob * c->tri * sizeof(float2), hipMemcpyDeviceToDevice, st));
-        VHIP_TRY(c, hipMemcpyAsync(c->d_trace + sp.main_prob, c->d_trace_tail, (size_t)sp.tail_prob * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_phi + sp.main_prob * c->tri, c->d_phi_tail, (size_t)sp.tail_prob * c->tri * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_trace + sp.main_prob, c->d_trace_tail, (size_t)sp.tail_prob * 4, hipMemcpyDeviceToDevice, st));
     }
     t_end(c, st);
     return MCA_HIP_OK;
@@ -755,8 +707,8 @@ int launch_rtf(mca_hip_mvdr_ctx *c, const MvdrCall &q, hipStream_t st, int f0, i
     const float *update = q.update, *tmask = q.tmask;
     // a slot the call leaves out restarts from nothing learned; the kernel touches only the slots below n_sources
     if (f0 == 0) {
-        VHIP_TRY(c, clear_unused_slots(c, c->d_psi.p, (size_t)c->K * c->tri, n_sources, n_streams, st));
-        VHIP_TRY(c, clear_unused_slots(c, c->d_cpsi.p, c->K, n_sources, n_streams, st));
+        HIP_TRY(c, clear_unused_slots(c, c->d_psi.p, (size_t)c->K * c->tri, n_sources, n_streams, st));
+        HIP_TRY(c, clear_unused_slots(c, c->d_cpsi.p, c->K, n_sources, n_streams, st));
     }
     MvdrRtfArgs ra{};
     const size_t nph = (size_t)c->N / 64 + 33;
@@ -769,7 +721,7 @@ int launch_rtf(mca_hip_mvdr_ctx *c, const MvdrCall &q, hipStream_t st, int f0, i
     ra.phi = c->d_phi; ra.trace = c->d_trace; ra.psi = c->d_psi; ra.cpsi = c->d_cpsi; ra.cphi_in = c->d_cphi; ra.cphi_out = c->d_cphi_next; ra.D = c->d_D;
     const MvdrLaunch l = plan_mvdr_rtf(*c, n_streams, n_sources, n_frames, c->plane_cap_cells).l;
     launch(c, mvdr_rtf_kernel(c->Q(), false), l.grid, l.block, l.lds, &ra, T_RTF, st);
-    VHIP_TRY(c, hipMemcpyAsync(c->d_cphi, c->d_cphi_next, (size_t)n_streams * c->K * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_cphi, c->d_cphi_next, (size_t)n_streams * c->K * 4, hipMemcpyDeviceToDevice, st));
     return MCA_HIP_OK;
 }
 
@@ -793,7 +745,7 @@ int launch_postfilter(mca_hip_mvdr_ctx *c, const MvdrCall &q, float2 *Y, hipStre
 {
     const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
     // A slot the call leaves out restarts from silence, whether the call has out_pcm or not; the kernel touches only the slots below n_sources
-    VHIP_TRY(c, clear_unused_slots(c, c->d_pf_A.p, c->K, n_sources, n_streams, st));
+    HIP_TRY(c, clear_unused_slots(c, c->d_pf_A.p, c->K, n_sources, n_streams, st));
     MvdrPostfilterArgs fa{};
     fa.Y = Y; fa.pn = c->d_pf_pn; fa.A = c->d_pf_A;
     fa.n_streams = n_streams; fa.S = n_sources; fa.slots = c->max_sources; fa.n_frames = n_frames; fa.K = c->K;
@@ -813,7 +765,7 @@ int launch_synth(mca_hip_mvdr_ctx *c, const MvdrCall &q, const float2 *Y, hipStr
     ya.tail_in = c->d_tail[c->tail_cur]; ya.tail_out = c->d_tail[c->tail_cur ^ 1]; ya.out = q.out_pcm;
     // a slot the call leaves out restarts from silence.  The kernel writes only the slots below n_sources, so the clear goes
     // first: if it fails, nothing has touched the tails yet and tail_cur still names the valid ones
-    VHIP_TRY(c, clear_unused_slots(c, ya.tail_out, c->H, n_sources, n_streams, st));
+    HIP_TRY(c, clear_unused_slots(c, ya.tail_out, c->H, n_sources, n_streams, st));
     if (const int rc = launch(c, kptr(k_mvdr_synth), p.l.grid, p.l.block, p.l.lds, &ya, T_SYNTH, st)) return rc;
     c->tail_cur ^= 1;
     return MCA_HIP_OK;
@@ -825,24 +777,24 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     MvdrCall q = call;                                          // (an auto call: update and tmask become the estimated masks below)
     const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
-    if (q.est && !c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
-    if (q.rtf && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (q.est && !c->em_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
+    if (q.rtf && !c->rtf_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
     if (q.rtf && c->null_gain != 0.0 && !c->rtf_nulls)
-        return vfail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0, or enable them (mca_hip_mvdr_set_rtf_nulls)");
+        return fail(c, MCA_HIP_ERR_UNSUPPORTED, "nulls at estimated steering vectors are not built: set the null gain to 0, or enable them (mca_hip_mvdr_set_rtf_nulls)");
     if (n_sources < 1 || n_sources > c->max_sources)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
-    if (!pcm || !q.doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
-    if (!q.out_pcm && !q.out_spec) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_sources outside [1, max_sources] (mca_hip_mvdr_set_max_sources; " + std::to_string(c->max_sources) + " here)");
+    if (!pcm || !q.doa) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev / doa_rad_dev is NULL");
+    if (!q.out_pcm && !q.out_spec) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_pcm_dev and out_spec_dev are both NULL");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
     const long long need = (long long)(n_frames + 1) * c->H;
-    if (mic_stride < need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_stride shorter than (n_frames+1)*hop samples");
-    if (n_streams > 1 && stream_stride < (long long)(c->M - 1) * mic_stride + need) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_stride too short");
+    if (mic_stride < need) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mic_stride shorter than (n_frames+1)*hop samples");
+    if (n_streams > 1 && stream_stride < (long long)(c->M - 1) * mic_stride + need) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_stride too short");
     if ((mic_stride & 1) || (stream_stride & 1) || (reinterpret_cast<uintptr_t>(pcm) & 7))
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
-    if (q.out_spec && (reinterpret_cast<uintptr_t>(q.out_spec) & 7)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "pcm_dev must be 8-byte aligned with even strides (float2 loads)");
+    if (q.out_spec && (reinterpret_cast<uintptr_t>(q.out_spec) & 7)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out_spec_dev must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     // the steering plane of an RTF call holds fc frames: all of them, or as many as the workspace cap takes
     const int fc = q.rtf ? plan_mvdr_rtf(*c, n_streams, n_sources, n_frames, c->plane_cap_cells).fc : n_frames;
     int rc = ensure_ws(c, (size_t)n_streams * n_frames, n_sources, !q.update && !q.est, q.rtf, (size_t)n_streams * fc);
@@ -867,17 +819,17 @@ int mvdr_frames_dev(mca_hip_mvdr_ctx *c, const float *pcm, long long stream_stri
     } else if ((rc = launch_solve(c, q, Y, st))) return rc;
     if (c->pf_on && (rc = launch_postfilter(c, q, Y, st))) return rc;
     if (q.out_pcm && (rc = launch_synth(c, q, Y, st))) return rc;
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
 // the host-pointer form: pcm packed [streams][M][(F + 1) hop]; 1 or K (masked) floats of update weights per (stream, frame)
 int mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, const MvdrCall &q)
 {
-    if (!c || !pcm || !q.doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c || !pcm || !q.doa) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     const int n_streams = q.n_streams, n_frames = q.n_frames, n_sources = q.n_sources;
-    if (n_streams < 1 || n_frames < 1 || n_sources < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (n_streams < 1 || n_frames < 1 || n_sources < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams/n_frames/n_sources < 1");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const long long ms = (long long)(n_frames + 1) * c->H, ss = ms * c->M;
     const size_t nf = (size_t)n_streams * n_frames * n_sources;
     const size_t nu = (size_t)n_streams * n_frames * (q.masked ? (size_t)c->K : 1), tb = nf * c->K * 4;      // (target masks: [streams][n_sources][F][K])
@@ -929,7 +881,7 @@ int mca_hip_mvdr_sources_frames_rtf_dev(mca_hip_mvdr_ctx *c, const float *pcm, l
 int mca_hip_mvdr_sources_frames_rtf_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_streams, int n_frames, int n_sources, const float *doa_rad,
                                          const float *update_mask, const float *target_mask, float *out_pcm, float *out_spec)
 {
-    if (c && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (c && !c->rtf_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
     return mvdr_frames_host(c, pcm, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).with_rtf(update_mask, target_mask));
 }
 
@@ -940,7 +892,7 @@ int mca_hip_mvdr_sources_frames_auto_dev(mca_hip_mvdr_ctx *c, const float *pcm, 
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(update_mask_out) | reinterpret_cast<uintptr_t>(target_mask_out)) & 3)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "update_mask_out_dev / target_mask_out_dev must be 4-byte aligned");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "update_mask_out_dev / target_mask_out_dev must be 4-byte aligned");
     return mvdr_frames_dev(c, pcm, stream_stride, mic_stride, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).estimating(c->rtf_on, update_mask_out, target_mask_out), stream);
 }
 
@@ -948,7 +900,7 @@ int mca_hip_mvdr_sources_frames_auto_host(mca_hip_mvdr_ctx *c, const float *pcm,
                                           float *update_mask_out, float *target_mask_out, float *out_pcm, float *out_spec)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!c->em_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
+    if (!c->em_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the mask estimator is not enabled on this context (mca_hip_mvdr_set_mask_estimator)");
     return mvdr_frames_host(c, pcm, make_call(n_streams, n_frames, n_sources, doa_rad, out_pcm, out_spec).estimating(c->rtf_on, update_mask_out, target_mask_out));
 }
 
@@ -991,18 +943,18 @@ int mca_hip_mvdr_frames_host(mca_hip_mvdr_ctx *c, const float *pcm, int n_stream
 int mca_hip_mvdr_spectrum_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_spectrum_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_spectrum_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
-    if (cfg->n_angles < 2 || cfg->n_angles > MVDR_SPEC_MAX_ANGLES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [2,361]");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_spectrum_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->n_angles < 2 || cfg->n_angles > MVDR_SPEC_MAX_ANGLES) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [2,361]");
     const bool xyz = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ;
-    if (xyz && cfg->n_angles < 3) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [3,361] on the periodic grid of XYZ geometry");
+    if (xyz && cfg->n_angles < 3) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_angles must be in [3,361] on the periodic grid of XYZ geometry");
     if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
     if (cfg->weighting != MCA_HIP_MVDR_SPECTRUM_POWER && cfg->weighting != MCA_HIP_MVDR_SPECTRUM_NORMALISED)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "weighting must be 0 (power) or 1 (normalised)");
-    if (cfg->n_peaks < 1 || cfg->n_peaks > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_peaks must be in [1,4]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "weighting must be 0 (power) or 1 (normalised)");
+    if (cfg->n_peaks < 1 || cfg->n_peaks > MCA_MAX_SOURCES) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_peaks must be in [1,4]");
     if (c->spec_set && cfg->n_angles == c->spec.n_angles) { c->spec = *cfg; return MCA_HIP_OK; }    // the grid and its phasors stay
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     // grid and steering phasors of the new angle count, in double: theta_i = -pi/2 + i pi/(D-1), u = fs/(N c) x_m cos(theta + pi/2)
     // (Beamformer.cpp:59), factors exp(-j 2 pi 32 i u), i <= N/64, and exp(-j 2 pi i u), i < 32, as in MvdrAnalyseArgs::T
     const int D = cfg->n_angles, Dpad = (D + 63) & ~63, nhi = c->N / 64 + 1, nph = nhi + 32, M = c->M;
@@ -1049,7 +1001,7 @@ void scan_args(const mca_hip_mvdr_ctx *c, Args &sa, const MvdrBand &b, const flo
 // both kernels of the Capon spectrum (timing slot 3), arguments checked by the caller
 int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, hipStream_t st)
 {
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const MvdrScanPlan p = plan_mvdr_spectrum(*c, c->spec.bin_lo, c->spec.bin_hi, c->spec_dpad, n_streams);
     MvdrSpectrumArgs sa{};
     scan_args(c, sa, p.b, c->d_spec_T, c->spec.n_angles, c->spec_dpad, c->spec.bin_lo, c->spec.bin_hi);
@@ -1065,7 +1017,7 @@ int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *
     if (!rc) launch(c, kptr(k_mvdr_spectrum_pick), dim3(n_streams), dim3(256), 0, &pa, T_NONE, st);
     t_end(c, st);
     if (rc) return rc;
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 }  // namespace
@@ -1074,19 +1026,19 @@ int launch_spectrum(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *
 int mca_hip_mvdr_spectrum_dev(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum_dev, peak_doa_dev and peak_val_dev are all NULL");
+    if (!c->spec_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!spectrum && !peak_doa && !peak_val) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum_dev, peak_doa_dev and peak_val_dev are all NULL");
     return launch_spectrum(c, n_streams, spectrum, peak_doa, peak_val, (hipStream_t)stream);
 }
 
 int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectrum, float *peak_doa, float *peak_val)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (!spectrum && !peak_doa && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum, peak_doa and peak_val are all NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->spec_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!spectrum && !peak_doa && !peak_val) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "spectrum, peak_doa and peak_val are all NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t sb = (size_t)n_streams * c->spec.n_angles * 4, pb = (size_t)n_streams * c->spec.n_peaks * 4;
     StageBuf b[] = {{SG_SCAN, spectrum, sb, STAGE_OUT}, {SG_AUX1, peak_doa, pb, STAGE_OUT}, {SG_AUX2, peak_val, pb, STAGE_OUT}};
     return staged(c, b, [&] { return mca_hip_mvdr_spectrum_dev(c, n_streams, (float *)b[0].dev, (float *)b[1].dev, (float *)b[2].dev, nullptr); });
@@ -1096,25 +1048,25 @@ int mca_hip_mvdr_spectrum_host(mca_hip_mvdr_ctx *c, int n_streams, float *spectr
 int mca_hip_mvdr_map_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_map_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_map_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
-    if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the map needs XYZ geometry (mca_hip_mvdr_set_geometry)");
-    if (cfg->n_az < 3 || cfg->n_az > 360) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_az must be in [3,360]");
-    if (cfg->n_el < 1 || cfg->n_el > 91) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_el must be in [1,91]");
-    if (cfg->n_az * cfg->n_el > MVDR_MAP_MAX_DIRS) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_az n_el must be at most 2048");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_map_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the map needs XYZ geometry (mca_hip_mvdr_set_geometry)");
+    if (cfg->n_az < 3 || cfg->n_az > 360) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_az must be in [3,360]");
+    if (cfg->n_el < 1 || cfg->n_el > 91) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_el must be in [1,91]");
+    if (cfg->n_az * cfg->n_el > MVDR_MAP_MAX_DIRS) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_az n_el must be at most 2048");
     if (!std::isfinite(cfg->el_lo_rad) || !std::isfinite(cfg->el_hi_rad) || cfg->el_lo_rad < -M_PI / 2 || cfg->el_hi_rad > M_PI / 2 || cfg->el_lo_rad > cfg->el_hi_rad)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations must satisfy -pi/2 <= el_lo_rad <= el_hi_rad <= pi/2");
-    if (cfg->n_el == 1 && cfg->el_lo_rad != cfg->el_hi_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_el == 1 needs el_lo_rad == el_hi_rad");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations must satisfy -pi/2 <= el_lo_rad <= el_hi_rad <= pi/2");
+    if (cfg->n_el == 1 && cfg->el_lo_rad != cfg->el_hi_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_el == 1 needs el_lo_rad == el_hi_rad");
     if (cfg->bin_lo < 0 || cfg->bin_lo > cfg->bin_hi || cfg->bin_hi > c->N / 2)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the band must satisfy 0 <= bin_lo <= bin_hi <= N/2");
     if (cfg->weighting != MCA_HIP_MVDR_SPECTRUM_POWER && cfg->weighting != MCA_HIP_MVDR_SPECTRUM_NORMALISED)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "weighting must be 0 (power) or 1 (normalised)");
-    if (cfg->n_peaks < 1 || cfg->n_peaks > MCA_MAX_SOURCES) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_peaks must be in [1,4]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "weighting must be 0 (power) or 1 (normalised)");
+    if (cfg->n_peaks < 1 || cfg->n_peaks > MCA_MAX_SOURCES) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_peaks must be in [1,4]");
     if (c->map_set && cfg->n_az == c->map.n_az && cfg->n_el == c->map.n_el && cfg->el_lo_rad == c->map.el_lo_rad && cfg->el_hi_rad == c->map.el_hi_rad) {
         c->map = *cfg;                                          // the grid and its phasors stay
         return MCA_HIP_OK;
     }
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     // grid and phasors in double: theta_i = -pi + i 2 pi / n_az, eps_j = el_lo + j (el_hi - el_lo)/(n_el - 1), direction j n_az + i;
     // the layout and the factors are the spectrum's (mca_hip_mvdr_spectrum_configure), the surplus lanes repeat the last direction
     const int n_az = cfg->n_az, n_el = cfg->n_el, D = n_az * n_el, Dpad = (D + 63) & ~63, nhi = c->N / 64 + 1, nph = nhi + 32, M = c->M;
@@ -1155,10 +1107,10 @@ int mca_hip_mvdr_map_get_grid(const mca_hip_mvdr_ctx *c, float *az, float *el)
 int mca_hip_mvdr_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float *map, float *peak_az, float *peak_el, float *peak_val, void *stream)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (!map && !peak_az && !peak_el && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map_dev, peak_az_dev, peak_el_dev and peak_val_dev are all NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->map_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!map && !peak_az && !peak_el && !peak_val) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map_dev, peak_az_dev, peak_el_dev and peak_val_dev are all NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const int D = c->map.n_az * c->map.n_el;
     // the partial sums are taken in passes of streams under the workspace cap (MvdrScanPlan): 288 KiB per stream at 2048 directions and N = 1024
@@ -1186,17 +1138,17 @@ int mca_hip_mvdr_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float *map, float *
     }
     t_end(c, st);
     if (rc) return rc;
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
 int mca_hip_mvdr_map_host(mca_hip_mvdr_ctx *c, int n_streams, float *map, float *peak_az, float *peak_el, float *peak_val)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (!map && !peak_az && !peak_el && !peak_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map, peak_az, peak_el and peak_val are all NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->map_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!map && !peak_az && !peak_el && !peak_val) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map, peak_az, peak_el and peak_val are all NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t mb = (size_t)n_streams * c->map.n_az * c->map.n_el * 4, pb = (size_t)n_streams * c->map.n_peaks * 4;
     StageBuf b[] = {{SG_SCAN, map, mb, STAGE_OUT}, {SG_AUX1, peak_az, pb, STAGE_OUT}, {SG_AUX2, peak_el, pb, STAGE_OUT}, {SG_WEIGHTS, peak_val, pb, STAGE_OUT}};
     return staged(c, b, [&] { return mca_hip_mvdr_map_dev(c, n_streams, (float *)b[0].dev, (float *)b[1].dev, (float *)b[2].dev, (float *)b[3].dev, nullptr); });
@@ -1207,8 +1159,8 @@ extern "C++" {
 namespace {
 int elevations_ready(mca_hip_mvdr_ctx *c, int n_streams, const void *ptr)
 {
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
-    if (!ptr) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations array is NULL");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!ptr) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the elevations array is NULL");
     return MCA_HIP_OK;
 }
 }  // namespace
@@ -1222,7 +1174,7 @@ int mca_hip_mvdr_set_elevations_host(mca_hip_mvdr_ctx *c, int n_streams, const f
     const float half_pi_f = 1.57079637f;                        // (float) pi/2: the largest float the call accepts
     for (int e = 0; e < n_streams * S; ++e)
         if (!std::isnan(elev_rad[e]) && !(std::fabs(elev_rad[e]) <= half_pi_f))
-            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "an elevation must be NaN (the context's) or within [-pi/2, pi/2]");
+            return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "an elevation must be NaN (the context's) or within [-pi/2, pi/2]");
     // the pairs with the host functions of mca_hip_mvdr_set_geometry; a NaN takes the context's pair, bit for bit
     const double ce = std::cos(c->geo_elevation), se = std::sin(c->geo_elevation);
     std::vector<double2> pairs((size_t)n_streams * S);
@@ -1230,10 +1182,10 @@ int mca_hip_mvdr_set_elevations_host(mca_hip_mvdr_ctx *c, int n_streams, const f
         const double eps = std::min(std::max((double)elev_rad[e], -M_PI / 2), M_PI / 2);
         pairs[e] = std::isnan(elev_rad[e]) ? make_double2(ce, se) : make_double2(std::cos(eps), std::sin(eps));
     }
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the pairs that change here
-    VHIP_TRY(c, hipMemcpy2D(c->d_slot_el, MCA_MAX_SOURCES * sizeof(double2), pairs.data(), S * sizeof(double2), S * sizeof(double2), (size_t)n_streams, hipMemcpyHostToDevice));
-    VHIP_TRY(c, hipMemcpy2D(c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), elev_rad, S * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());                       // no call in flight reads the pairs that change here
+    HIP_TRY(c, hipMemcpy2D(c->d_slot_el, MCA_MAX_SOURCES * sizeof(double2), pairs.data(), S * sizeof(double2), S * sizeof(double2), (size_t)n_streams, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy2D(c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), elev_rad, S * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyHostToDevice));
     tracks_off(c);                                             // they follow azimuths at the context's elevation: a slot with one of its own ends them
     return MCA_HIP_OK;
 }
@@ -1242,10 +1194,10 @@ int mca_hip_mvdr_set_elevations_dev(mca_hip_mvdr_ctx *c, int n_streams, const fl
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = elevations_ready(c, n_streams, elev_rad)) return rc;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrElevationsArgs ea{elev_rad, c->d_slot_el, c->d_slot_val, n_streams * c->max_sources, c->max_sources, std::cos(c->geo_elevation), std::sin(c->geo_elevation)};
     launch(c, kptr(k_mvdr_elevations), grid_for(ea.n, 256), dim3(256), 0, &ea, T_NONE, (hipStream_t)stream);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     tracks_off(c);
     return MCA_HIP_OK;
 }
@@ -1255,9 +1207,9 @@ int mca_hip_mvdr_get_elevations(mca_hip_mvdr_ctx *c, int n_streams, float *elev_
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = elevations_ready(c, n_streams, elev_rad)) return rc;
     const int S = c->max_sources;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
-    VHIP_TRY(c, hipMemcpy2D(elev_rad, S * sizeof(float), c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy2D(elev_rad, S * sizeof(float), c->d_slot_val, MCA_MAX_SOURCES * sizeof(float), S * sizeof(float), (size_t)n_streams, hipMemcpyDeviceToHost));
     return MCA_HIP_OK;
 }
 
@@ -1272,7 +1224,7 @@ MvdrTrackState track_state(mca_hip_mvdr_ctx *c)
 // the calls on one angle: refused in map mode, where they would leave eps undefined
 int tracks_ready_1d(mca_hip_mvdr_ctx *c)
 {
-    if (c->trk_map_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the tracks are in map mode: use the _map call (mca_hip_mvdr_tracks_set_map)");
+    if (c->trk_map_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "the tracks are in map mode: use the _map call (mca_hip_mvdr_tracks_set_map)");
     return MCA_HIP_OK;
 }
 MvdrTrk2State track_state_map(mca_hip_mvdr_ctx *c, int first_stream = 0)
@@ -1282,8 +1234,8 @@ MvdrTrk2State track_state_map(mca_hip_mvdr_ctx *c, int first_stream = 0)
 }
 int tracks_ready(mca_hip_mvdr_ctx *c, int n_streams)
 {
-    if (!c->trk_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
-    if (n_streams < 1 || n_streams > c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
+    if (!c->trk_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
+    if (n_streams < 1 || n_streams > c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_streams outside [1, max_streams]");
     return MCA_HIP_OK;
 }
 // the association's part of the pick kernel's arguments
@@ -1305,19 +1257,19 @@ MvdrTrackPickArgs track_pick_args(mca_hip_mvdr_ctx *c)
 int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_tracks_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
-    if (!c->spec_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first: the tracks use its grid, band and n_peaks");
-    if (cfg->enable != 0 && cfg->enable != 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
-    if (cfg->n_tracks < 1 || cfg->n_tracks > c->max_sources) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_tracks must be in [1, max_sources]");
-    if (cfg->n_own < 0 || cfg->n_own > cfg->n_tracks) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_own must be in [0, n_tracks]");
-    if (cfg->n_own > 0 && !c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_own > 0 needs RTF enabled (mca_hip_mvdr_set_rtf): an own track follows its target covariance");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_tracks_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (!c->spec_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_spectrum_configure first: the tracks use its grid, band and n_peaks");
+    if (cfg->enable != 0 && cfg->enable != 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
+    if (cfg->n_tracks < 1 || cfg->n_tracks > c->max_sources) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_tracks must be in [1, max_sources]");
+    if (cfg->n_own < 0 || cfg->n_own > cfg->n_tracks) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_own must be in [0, n_tracks]");
+    if (cfg->n_own > 0 && !c->rtf_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_own > 0 needs RTF enabled (mca_hip_mvdr_set_rtf): an own track follows its target covariance");
     if (!std::isfinite(cfg->max_step_rad) || !(cfg->max_step_rad > 0.0) || cfg->max_step_rad > M_PI)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_step_rad must be finite and in (0, pi]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_step_rad must be finite and in (0, pi]");
     if (!std::isfinite(cfg->min_sep_rad) || cfg->min_sep_rad < 0.0 || cfg->min_sep_rad > M_PI)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_sep_rad must be finite and in [0, pi]");
-    if (cfg->hold < 0 || cfg->hold > 1000) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "hold must be in [0,1000]");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_sep_rad must be finite and in [0, pi]");
+    if (cfg->hold < 0 || cfg->hold > 1000) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "hold must be in [0,1000]");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
     if (!c->d_trk_theta) {
         DevBuf<float> nth, npk;
@@ -1330,11 +1282,11 @@ int mca_hip_mvdr_tracks_configure(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks
         if (e != hipSuccess) return hip_fail(c, e, "track state");
         c->d_trk_theta.swap(nth); c->d_trk_int.swap(ni); c->d_trk_peak.swap(npk); c->d_trk_T0.swap(nt0);
     }
-    VHIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
-    VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
-    VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
-    if (cfg->enable == 1) VHIP_TRY(c, reset_elevations(c));   // the tracks live at the context's elevation: every slot back to unset
-    if (c->d_trk_eps) VHIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
+    HIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
+    HIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
+    HIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
+    if (cfg->enable == 1) HIP_TRY(c, reset_elevations(c));   // the tracks live at the context's elevation: every slot back to unset
+    if (c->d_trk_eps) HIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
     c->trk = *cfg; c->trk_on = cfg->enable == 1;
     c->trk_map_on = false;                                      // map mode is entered anew (mca_hip_mvdr_tracks_set_map)
     c->trk_ever = true;
@@ -1355,12 +1307,12 @@ int mca_hip_mvdr_tracks_seed_dev(mca_hip_mvdr_ctx *c, int n_streams, const float
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
     if (const int rc = tracks_ready_1d(c)) return rc;
-    if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_dev is NULL");
+    if (!doa) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrackSeedArgs sa{track_state(c), doa, n_streams, c->trk.n_tracks, c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ ? 1 : 0};
     launch(c, kptr(k_mvdr_track_seed), grid_for(n_streams * c->trk.n_tracks, 256), dim3(256), 0, &sa, T_TRACKS, st);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1369,8 +1321,8 @@ int mca_hip_mvdr_tracks_seed_host(mca_hip_mvdr_ctx *c, int n_streams, const floa
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
     if (const int rc = tracks_ready_1d(c)) return rc;
-    if (!doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa is NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!doa) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa is NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     StageBuf b[] = {{SG_AUX2, doa, (size_t)n_streams * c->trk.n_tracks * 4, STAGE_IN}};
     return staged(c, b, [&] { return mca_hip_mvdr_tracks_seed_dev(c, n_streams, (float *)b[0].dev, nullptr); });
 }
@@ -1381,7 +1333,7 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
     if (const int rc = tracks_ready(c, n_streams)) return rc;
     if (const int rc = tracks_ready_1d(c)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const int n_own = c->trk.n_own;
     const MvdrScanPlan p = plan_mvdr_tracks(*c, c->spec.bin_lo, c->spec.bin_hi, c->spec_dpad, n_own, n_streams);
     if (const int rc = grow_ws(c, c->d_trk_part, p.per_part * n_streams, "partial sums of the own tracks", true)) return rc;
@@ -1393,7 +1345,7 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
         if (const int rc = launch_spectrum(c, n_streams, nullptr, pk_doa, pk_val, st)) return rc;
     MvdrTrackPickArgs pa = track_pick_args(c);
     pa.cand_doa = pk_doa; pa.cand_val = pk_val; pa.n_cand = capon ? c->spec.n_peaks : 0;
-    if (n_own > 0 && own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * c->K, st));      // the bins outside the band's chunks
+    if (n_own > 0 && own_used) HIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * c->K, st));      // the bins outside the band's chunks
     t_begin(c, T_TRACKS, st);
     if (n_own > 0) {
         MvdrTrackTablesArgs ta{c->d_trk_theta, c->d_trk_T0, c->d_micx, (double)c->cfg.sample_rate / (double)c->N / 346.1, c->N, c->M, n_own, geometry_args(c)};
@@ -1409,7 +1361,7 @@ int mca_hip_mvdr_tracks_update_dev(mca_hip_mvdr_ctx *c, int n_streams, float *ow
     }
     launch(c, kptr(k_mvdr_track_pick), dim3(n_streams), dim3(256), 0, &pa, T_NONE, st);
     t_end(c, st);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1418,7 +1370,7 @@ int mca_hip_mvdr_tracks_update_host(mca_hip_mvdr_ctx *c, int n_streams, float *o
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
     if (const int rc = tracks_ready_1d(c)) return rc;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t sb = (size_t)n_streams * c->trk.n_own * c->spec.n_angles * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
     StageBuf b[] = {{SG_SCAN, own_spectrum, sb, STAGE_OUT}, {SG_AUX1, own_used, ub, STAGE_OUT}};      // (n_own == 0: nothing of either)
     return staged(c, b, [&] { return mca_hip_mvdr_tracks_update_dev(c, n_streams, (float *)b[0].dev, (unsigned char *)b[1].dev, nullptr); });
@@ -1430,15 +1382,15 @@ int mca_hip_mvdr_tracks_associate_dev(mca_hip_mvdr_ctx *c, int n_streams, const 
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
     if (const int rc = tracks_ready_1d(c)) return rc;
-    if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
-    if (!cand_doa || !cand_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_doa_dev / cand_val_dev is NULL");
-    if (c->trk.n_own > 0 && !own_doa) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_doa_dev is NULL on tracks with n_own > 0");
+    if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
+    if (!cand_doa || !cand_val) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_doa_dev / cand_val_dev is NULL");
+    if (c->trk.n_own > 0 && !own_doa) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_doa_dev is NULL on tracks with n_own > 0");
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrackPickArgs pa = track_pick_args(c);
     pa.own_doa = own_doa; pa.cand_doa = cand_doa; pa.cand_val = cand_val; pa.n_cand = n_cand;
     launch(c, kptr(k_mvdr_track_pick), dim3(n_streams), dim3(256), 0, &pa, T_TRACKS, st);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1446,10 +1398,10 @@ int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *c, int n_streams, int n_frame
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
-    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
-    if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
+    if (n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+    if (!doa_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const dim3 grid = grid_for((long long)n_streams * n_frames, 256);
     if (c->trk_map_on) {
         // map mode: the elevations of the slots travel with the azimuths, on the same stream
@@ -1459,7 +1411,7 @@ int mca_hip_mvdr_tracks_fill_dev(mca_hip_mvdr_ctx *c, int n_streams, int n_frame
         MvdrTrackFillArgs fa{track_state(c), doa_rad, n_streams, n_frames, c->trk.n_tracks};
         launch(c, kptr(k_mvdr_track_fill), grid, dim3(256), 0, &fa, T_TRACKS, st);
     }
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1467,9 +1419,9 @@ int mca_hip_mvdr_tracks_fill_host(mca_hip_mvdr_ctx *c, int n_streams, int n_fram
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
-    if (n_frames < 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
-    if (!doa_rad) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (n_frames < 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_frames < 1");
+    if (!doa_rad) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     StageBuf b[] = {{SG_AUX2, doa_rad, (size_t)n_streams * n_frames * c->trk.n_tracks * 4, STAGE_OUT}};
     return staged(c, b, [&] { return mca_hip_mvdr_tracks_fill_dev(c, n_streams, n_frames, (float *)b[0].dev, nullptr); });
 }
@@ -1478,22 +1430,22 @@ int mca_hip_mvdr_tracks_get(mca_hip_mvdr_ctx *c, int n_streams, float *theta, in
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_ready(c, n_streams)) return rc;
-    if (!theta && !alive && !miss && !gen) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "theta, alive, miss and gen are all NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
+    if (!theta && !alive && !miss && !gen) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "theta, alive, miss and gen are all NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
     const size_t n = (size_t)n_streams * MCA_MAX_SOURCES, all = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
     std::vector<float> hf(n);
     std::vector<int> hi(n);
     const int T = c->trk.n_tracks;
     if (theta) {
-        VHIP_TRY(c, hipMemcpy(hf.data(), c->d_trk_theta, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(hf.data(), c->d_trk_theta, n * 4, hipMemcpyDeviceToHost));
         for (int a = 0; a < n_streams; ++a)
             for (int s = 0; s < T; ++s) theta[a * T + s] = hf[(size_t)a * MCA_MAX_SOURCES + s];
     }
     int *outs[3] = {alive, miss, gen};
     for (int j = 0; j < 3; ++j)
         if (outs[j]) {
-            VHIP_TRY(c, hipMemcpy(hi.data(), c->d_trk_int + j * all, n * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(hi.data(), c->d_trk_int + j * all, n * 4, hipMemcpyDeviceToHost));
             for (int a = 0; a < n_streams; ++a)
                 for (int s = 0; s < T; ++s) outs[j][a * T + s] = hi[(size_t)a * MCA_MAX_SOURCES + s];
         }
@@ -1506,8 +1458,8 @@ namespace {
 int tracks_map_ready(mca_hip_mvdr_ctx *c, int n_streams)
 {
     if (const int rc = tracks_ready(c, n_streams)) return rc;
-    if (!c->trk_map_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_set_map first (with enable = 1)");
-    if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
+    if (!c->trk_map_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_set_map first (with enable = 1)");
+    if (!c->map_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first");
     return MCA_HIP_OK;
 }
 // the association's part of the pick kernel's arguments, for the streams from first_stream on
@@ -1532,20 +1484,20 @@ MvdrTrk2PickArgs trk2_pick_args(mca_hip_mvdr_ctx *c, int first_stream)
 int mca_hip_mvdr_tracks_set_map(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks_map_config *cfg)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!cfg) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_tracks_map_config)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
-    if (cfg->enable != 0 && cfg->enable != 1) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
+    if (!cfg) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (cfg->struct_size != (int)sizeof(mca_hip_mvdr_tracks_map_config)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "struct_size mismatch");
+    if (cfg->enable != 0 && cfg->enable != 1) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "enable must be 0 or 1");
     if (!std::isfinite(cfg->max_step_el_rad) || cfg->max_step_el_rad < 0.0 || cfg->max_step_el_rad > M_PI)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_step_el_rad must be finite and in [0, pi]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "max_step_el_rad must be finite and in [0, pi]");
     if (!std::isfinite(cfg->min_sep_el_rad) || cfg->min_sep_el_rad < 0.0 || cfg->min_sep_el_rad > M_PI)
-        return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_sep_el_rad must be finite and in [0, pi]");
+        return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "min_sep_el_rad must be finite and in [0, pi]");
     if (cfg->enable == 1) {
-        if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map mode needs XYZ geometry (mca_hip_mvdr_set_geometry)");
-        if (!c->trk_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
-        if (!c->map_set) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first: map mode uses its grid, band and n_peaks");
+        if (c->geo_mode != MCA_HIP_MVDR_GEOMETRY_XYZ) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "map mode needs XYZ geometry (mca_hip_mvdr_set_geometry)");
+        if (!c->trk_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_tracks_configure first (with enable = 1)");
+        if (!c->map_set) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "mca_hip_mvdr_map_configure first: map mode uses its grid, band and n_peaks");
     }
     if (cfg->enable == 0 && !c->trk_map_on) { c->trkm = *cfg; return MCA_HIP_OK; }      // nothing to leave
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t n = (size_t)c->cfg.max_streams * MCA_MAX_SOURCES;
     if (!c->d_trk_eps) {
         DevBuf<float> ne, npk;
@@ -1555,11 +1507,11 @@ int mca_hip_mvdr_tracks_set_map(mca_hip_mvdr_ctx *c, const mca_hip_mvdr_tracks_m
         c->d_trk_eps.swap(ne); c->d_trk2_peak.swap(npk);
     }
     // entering and leaving alike: the angles change meaning, so every slot starts from nothing
-    VHIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
-    VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
-    VHIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
-    VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
-    if (cfg->enable == 0) VHIP_TRY(c, reset_elevations(c));    // the tracks on one angle live at the context's elevation
+    HIP_TRY(c, hipDeviceSynchronize());                       // no update in flight writes what is cleared here
+    HIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
+    HIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
+    HIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
+    if (cfg->enable == 0) HIP_TRY(c, reset_elevations(c));    // the tracks on one angle live at the context's elevation
     c->trkm = *cfg; c->trk_map_on = cfg->enable == 1;
     if (c->trk_map_on) c->trk_map_ever = true;
     return MCA_HIP_OK;
@@ -1578,12 +1530,12 @@ int mca_hip_mvdr_tracks_seed_map_dev(mca_hip_mvdr_ctx *c, int n_streams, const f
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
-    if (!az || !el) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az_dev / el_dev is NULL");
+    if (!az || !el) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az_dev / el_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrk2SeedArgs sa{track_state_map(c), az, el, n_streams, c->trk.n_tracks};
     launch(c, kptr(k_mvdr_trk2_seed), grid_for(n_streams * c->trk.n_tracks, 256), dim3(256), 0, &sa, T_TRACKS_MAP, st);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1591,8 +1543,8 @@ int mca_hip_mvdr_tracks_seed_map_host(mca_hip_mvdr_ctx *c, int n_streams, const 
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
-    if (!az || !el) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az / el is NULL");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!az || !el) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "az / el is NULL");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t bytes = (size_t)n_streams * c->trk.n_tracks * 4;
     StageBuf b[] = {{SG_AUX1, az, bytes, STAGE_IN}, {SG_AUX2, el, bytes, STAGE_IN}};
     return staged(c, b, [&] { return mca_hip_mvdr_tracks_seed_map_dev(c, n_streams, (float *)b[0].dev, (float *)b[1].dev, nullptr); });
@@ -1603,7 +1555,7 @@ int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const int n_own = c->trk.n_own, K = c->K, M = c->M, D = c->map.n_az * c->map.n_el;
     // the map's peaks: the kernels of mca_hip_mvdr_map_dev (timing slot 8), into the context's own rows.  Not launched where every slot
     // is an own track: a peak then changes no track
@@ -1620,7 +1572,7 @@ int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float
         if (const int rc = grow_ws(c, c->d_trk2_U, p.per_u * pass, "steering vectors of the own tracks", true)) return rc;
         if (const int rc = grow_ws(c, c->d_trk2_F, p.per_f * pass, "used flags of the own tracks", true)) return rc;
         if (const int rc = grow_ws(c, c->d_trk2_part, p.per_part * pass, "partial sums of the own tracks", true)) return rc;
-        if (own_used) VHIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks, the dead slots
+        if (own_used) HIP_TRY(c, hipMemsetAsync(own_used, 0, (size_t)n_streams * n_own * K, st));      // the bins outside the band's chunks, the dead slots
     }
     t_begin(c, T_TRACKS_MAP, st);
     for (int s0 = 0; s0 < n_streams; s0 += pass) {
@@ -1652,7 +1604,7 @@ int mca_hip_mvdr_tracks_update_map_dev(mca_hip_mvdr_ctx *c, int n_streams, float
         launch(c, kptr(k_mvdr_trk2_pick), dim3(ns), dim3(256), 0, &pa, T_NONE, st);
     }
     t_end(c, st);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1660,7 +1612,7 @@ int mca_hip_mvdr_tracks_update_map_host(mca_hip_mvdr_ctx *c, int n_streams, floa
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t mb = (size_t)n_streams * c->trk.n_own * c->map.n_az * c->map.n_el * 4, ub = (size_t)n_streams * c->trk.n_own * c->K;
     StageBuf b[] = {{SG_SCAN, own_map, mb, STAGE_OUT}, {SG_AUX1, own_used, ub, STAGE_OUT}};      // (n_own == 0: nothing of either)
     return staged(c, b, [&] { return mca_hip_mvdr_tracks_update_map_dev(c, n_streams, (float *)b[0].dev, (unsigned char *)b[1].dev, nullptr); });
@@ -1671,16 +1623,16 @@ int mca_hip_mvdr_tracks_associate_map_dev(mca_hip_mvdr_ctx *c, int n_streams, co
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
-    if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
-    if (!cand_az || !cand_el || !cand_val) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_az_dev / cand_el_dev / cand_val_dev is NULL");
-    if (c->trk.n_own > 0 && (!own_az || !own_el)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_az_dev / own_el_dev is NULL on tracks with n_own > 0");
+    if (n_cand < 1 || n_cand > MVDR_TRACK_MAX_CAND) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "n_cand must be in [1,8]");
+    if (!cand_az || !cand_el || !cand_val) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "cand_az_dev / cand_el_dev / cand_val_dev is NULL");
+    if (c->trk.n_own > 0 && (!own_az || !own_el)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "own_az_dev / own_el_dev is NULL on tracks with n_own > 0");
     hipStream_t st = (hipStream_t)stream;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
     MvdrTrk2PickArgs pa = trk2_pick_args(c, 0);
     pa.own_az = c->trk.n_own > 0 ? own_az : nullptr; pa.own_el = c->trk.n_own > 0 ? own_el : nullptr;
     pa.cand_az = cand_az; pa.cand_el = cand_el; pa.cand_val = cand_val; pa.n_cand = n_cand;
     launch(c, kptr(k_mvdr_trk2_pick), dim3(n_streams), dim3(256), 0, &pa, T_TRACKS_MAP, st);
-    VHIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return MCA_HIP_OK;
 }
 
@@ -1688,14 +1640,14 @@ int mca_hip_mvdr_tracks_get_map(mca_hip_mvdr_ctx *c, int n_streams, float *theta
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
     if (const int rc = tracks_map_ready(c, n_streams)) return rc;
-    if (!theta && !eps && !alive && !miss && !gen) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "theta, eps, alive, miss and gen are all NULL");
+    if (!theta && !eps && !alive && !miss && !gen) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "theta, eps, alive, miss and gen are all NULL");
     if (theta || alive || miss || gen)
         if (const int rc = mca_hip_mvdr_tracks_get(c, n_streams, theta, alive, miss, gen)) return rc;
     if (eps) {
-        VHIP_TRY(c, hipSetDevice(c->cfg.device));
-        VHIP_TRY(c, hipDeviceSynchronize());
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        HIP_TRY(c, hipDeviceSynchronize());
         std::vector<float> hf((size_t)n_streams * MCA_MAX_SOURCES);
-        VHIP_TRY(c, hipMemcpy(hf.data(), c->d_trk_eps, hf.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(hf.data(), c->d_trk_eps, hf.size() * 4, hipMemcpyDeviceToHost));
         const int T = c->trk.n_tracks;
         for (int a = 0; a < n_streams; ++a)
             for (int s = 0; s < T; ++s) eps[a * T + s] = hf[(size_t)a * MCA_MAX_SOURCES + s];
@@ -1710,7 +1662,7 @@ int read_hermitian(mca_hip_mvdr_ctx *c, const float2 *tri_dev, double *out)
 {
     const int M = c->M;
     std::vector<float2> h((size_t)c->K * c->tri);
-    VHIP_TRY(c, hipMemcpy(h.data(), tri_dev, h.size() * sizeof(float2), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h.data(), tri_dev, h.size() * sizeof(float2), hipMemcpyDeviceToHost));
     for (int k = 0; k < c->K; ++k)
         for (int i = 0; i < M; ++i)
             for (int j = 0; j <= i; ++j) {
@@ -1727,27 +1679,27 @@ int read_hermitian(mca_hip_mvdr_ctx *c, const float2 *tri_dev, double *out)
 int mca_hip_mvdr_get_covariance(mca_hip_mvdr_ctx *c, int s, double *out)
 {
     if (!c || !out) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
+    if (s < 0 || s >= c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
     return read_hermitian(c, c->d_phi + (size_t)s * c->K * c->tri, out);
 }
 
 int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *c, int s, int source, double *out, double *norm)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!out && !norm) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out and norm are both NULL");
-    if (!c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
-    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
-    if (source < 0 || source >= c->max_sources) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "source outside [0, max_sources)");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
+    if (!out && !norm) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out and norm are both NULL");
+    if (!c->rtf_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (s < 0 || s >= c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
+    if (source < 0 || source >= c->max_sources) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "source outside [0, max_sources)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
     const size_t slot = (size_t)s * c->max_sources + source;
     if (out)
         if (const int rc = read_hermitian(c, c->d_psi + slot * c->K * c->tri, out)) return rc;
     if (norm) {
         std::vector<float> h((size_t)c->K);
-        VHIP_TRY(c, hipMemcpy(h.data(), c->d_cpsi + slot * c->K, h.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(h.data(), c->d_cpsi + slot * c->K, h.size() * 4, hipMemcpyDeviceToHost));
         for (int k = 0; k < c->K; ++k) norm[k] = h[k];
     }
     return MCA_HIP_OK;
@@ -1756,19 +1708,19 @@ int mca_hip_mvdr_get_target_covariance(mca_hip_mvdr_ctx *c, int s, int source, d
 int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa_rad, double *out, unsigned char *estimated)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    if (!out && !estimated) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out and estimated are both NULL");
-    if (!c->rtf_on) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
-    if (s < 0 || s >= c->cfg.max_streams) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
-    if (source < 0 || source >= c->max_sources) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "source outside [0, max_sources)");
-    if (!std::isfinite(doa_rad)) return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is not finite");
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
-    VHIP_TRY(c, hipDeviceSynchronize());
+    if (!out && !estimated) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "out and estimated are both NULL");
+    if (!c->rtf_on) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "RTF is not enabled on this context (mca_hip_mvdr_set_rtf)");
+    if (s < 0 || s >= c->cfg.max_streams) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "stream_index out of range");
+    if (source < 0 || source >= c->max_sources) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "source outside [0, max_sources)");
+    if (!std::isfinite(doa_rad)) return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "doa_rad is not finite");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipDeviceSynchronize());
     // the factored phasors of the look direction, as the analysis forms them (MvdrAnalyseArgs::T), the phase in double
     const int M = c->M, K = c->K, nhi = c->N / 64 + 1, nph = nhi + 32;
     // (XYZ mode: at the elevation of the slot, mca_hip_mvdr_set_elevations_*)
     const bool xyz = c->geo_mode == MCA_HIP_MVDR_GEOMETRY_XYZ;
     double2 el = make_double2(1.0, 0.0);
-    if (xyz) VHIP_TRY(c, hipMemcpy(&el, c->d_slot_el + (size_t)s * MCA_MAX_SOURCES + source, sizeof(double2), hipMemcpyDeviceToHost));
+    if (xyz) HIP_TRY(c, hipMemcpy(&el, c->d_slot_el + (size_t)s * MCA_MAX_SOURCES + source, sizeof(double2), hipMemcpyDeviceToHost));
     std::vector<float2> T((size_t)M * nph);
     for (int m = 0; m < M; ++m)
         for (int e = 0; e < nph; ++e) {
@@ -1794,7 +1746,7 @@ int mca_hip_mvdr_get_steering(mca_hip_mvdr_ctx *c, int s, int source, double doa
     if (e == hipSuccess) e = hipLaunchKernel(mvdr_rtf_kernel(Q, true), dim3((unsigned)((K + 63) / 64)), dim3(256), kargs, 0, nullptr);
     if (e == hipSuccess) e = hipMemcpy(h.data(), buf + tb, ob, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(he.data(), buf + tb + ob, (size_t)K, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vfail(c, MCA_HIP_ERR_HIP, std::string("steering vectors: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, MCA_HIP_ERR_HIP, std::string("steering vectors: ") + hipGetErrorString(e));
     if (out)
         for (size_t i = 0; i < h.size(); ++i) { out[2 * i] = h[i].x; out[2 * i + 1] = h[i].y; }
     if (estimated) std::memcpy(estimated, he.data(), (size_t)K);
@@ -1826,15 +1778,11 @@ unsigned mvdr_cfg_hash(const mca_hip_mvdr_ctx *c)
 }  // namespace
 }  // extern "C++"
 
-long long mca_hip_mvdr_state_size(const mca_hip_mvdr_ctx *c)
-{
-    return c ? blob_size(mvdr_parts(const_cast<mca_hip_mvdr_ctx *>(c))) : (long long)MCA_HIP_ERR_INVALID_ARGUMENT;
-}
+long long mca_hip_mvdr_state_size(const mca_hip_mvdr_ctx *c) { return state_size(c, c ? mvdr_parts(const_cast<mca_hip_mvdr_ctx *>(c)) : std::vector<BlobPart>()); }
 
 int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *c, void *blob, long long bytes)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
     // version 1: one tail per stream (a context that never raised max_sources writes what it always wrote);
     // version 2: max_sources tails per stream, the maximum in host[0];
     // version 3: a context with the post-filter enabled -- the same and A behind the tails, the maximum in host[0], 1 in host[1]
@@ -1842,37 +1790,35 @@ int mca_hip_mvdr_state_save(mca_hip_mvdr_ctx *c, void *blob, long long bytes)
     if (c->pf_on) { h.version = 3; h.host[0] = c->max_sources; h.host[1] = 1; }
     // version 4: a context with RTF enabled -- the same (A only with the post-filter, 1 in host[1] then), Psi, cpsi and cphi behind it, 1 in host[2]
     if (c->rtf_on) { h.version = 4; h.host[0] = c->max_sources; h.host[1] = c->pf_on ? 1 : 0; h.host[2] = 1; }
-    const int rc = blob_save(mvdr_parts(c), h, blob, bytes);
-    return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
+    return state_save(c, mvdr_parts(c), h, blob, bytes);
 }
 
 int mca_hip_mvdr_state_load(mca_hip_mvdr_ctx *c, const void *blob, long long bytes)
 {
     if (!c) return MCA_HIP_ERR_INVALID_ARGUMENT;
-    VHIP_TRY(c, hipSetDevice(c->cfg.device));
     BlobHeader h;
-    if (blob && bytes >= (long long)sizeof(BlobHeader)) {
+    if (blob && bytes >= (long long)sizeof(BlobHeader)) {      // the feature parts: what the blob holds is what the context has
         std::memcpy(&h, blob, sizeof(h));
         const int blob_max = h.version >= 2 && h.version <= 4 ? (int)h.host[0] : 1;
         const bool blob_pf = h.version == 3 || (h.version == 4 && h.host[1] != 0), known = h.magic == MVDR_MAGIC && h.version >= 1 && h.version <= 4;
         if (known && (h.version == 4) != c->rtf_on)
-            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, h.version == 4 ? "state blob was saved with RTF enabled, this context has it disabled"
+            return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, h.version == 4 ? "state blob was saved with RTF enabled, this context has it disabled"
                                                                          : "state blob was saved without RTF, this context has it enabled");
         if (known && blob_pf != c->pf_on)
-            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, blob_pf ? "state blob was saved with the post-filter enabled, this context has it disabled"
+            return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, blob_pf ? "state blob was saved with the post-filter enabled, this context has it disabled"
                                                                   : "state blob was saved without the post-filter, this context has it enabled");
         if (known && blob_max != c->max_sources)
-            return vfail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with max_sources = " + std::to_string(blob_max) +
+            return fail(c, MCA_HIP_ERR_INVALID_ARGUMENT, "state blob was saved by a context with max_sources = " + std::to_string(blob_max) +
                                                               ", this one has " + std::to_string(c->max_sources));
     }
-    const int rc = blob_load(mvdr_parts(c), MVDR_MAGIC, mvdr_cfg_hash(c), blob, bytes, &h, c->rtf_on ? 4 : c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1);
+    const int rc = state_load(c, mvdr_parts(c), MVDR_MAGIC, c->rtf_on ? 4 : c->pf_on ? 3 : c->max_sources > 1 ? 2 : 1, mvdr_cfg_hash(c), blob, bytes, &h);
     if (!rc && c->d_trk_theta) {
         // the tracks are no part of a blob: a loaded context starts without them and is seeded again
-        VHIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
-        VHIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
-        if (c->d_trk_eps) VHIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
+        HIP_TRY(c, hipMemset(c->d_trk_theta, 0, c->d_trk_theta.bytes()));
+        HIP_TRY(c, hipMemset(c->d_trk_int, 0, c->d_trk_int.bytes()));
+        if (c->d_trk_eps) HIP_TRY(c, hipMemset(c->d_trk_eps, 0, c->d_trk_eps.bytes()));
     }
-    return rc ? vfail(c, rc == 2 ? MCA_HIP_ERR_HIP : MCA_HIP_ERR_INVALID_ARGUMENT, blob_error(rc)) : MCA_HIP_OK;
+    return rc;
 }
 
 int mca_hip_mvdr_set_timing(mca_hip_mvdr_ctx *c, int enable)
@@ -1889,9 +1835,9 @@ int mca_hip_mvdr_get_timing(mca_hip_mvdr_ctx *c, int kernel_id, int *launches, d
                                                            &mca_hip_mvdr_ctx::trk_ever, &mca_hip_mvdr_ctx::map_ever, &mca_hip_mvdr_ctx::trk_map_ever};
     if (!c || kernel_id < 0 || kernel_id >= T_COUNT || (opens[kernel_id] && !(c->*opens[kernel_id]))) return MCA_HIP_ERR_INVALID_ARGUMENT;
     for (auto &e : c->events) {
-        VHIP_TRY(c, hipEventSynchronize(e.b));
+        HIP_TRY(c, hipEventSynchronize(e.b));
         float ms = 0.f;
-        VHIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
+        HIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
         c->t_ms[e.id] += ms; c->t_launches[e.id] += 1;
         (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b);
     }

@@ -8,6 +8,7 @@
 #include "fft1024c.h"
 #include "fft512.h"
 #include "mca_internal.h"
+#include "module_plan.h"
 
 #include <algorithm>
 
@@ -20,15 +21,9 @@ struct MvdrShape {
     int Q() const { return (M + 3) / 4; }      // row slots per lane of the quad kernels
 };
 
-struct MvdrLaunch { dim3 grid, block; size_t lds; };
-inline dim3 grid_for(long long n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
+typedef Launch MvdrLaunch;      // (grid_for, run_length and the 512-point layout: module_plan.h)
 // frames per workgroup: `most`, halved down to `least` while n_rows x n_frames frames make fewer than 1024 workgroups
-inline int mvdr_run_len(int n_rows, int n_frames, int most, int least)
-{
-    int len = most;
-    while (len > least && (long long)n_rows * ((n_frames + len - 1) / len) < 1024) len >>= 1;
-    return len;
-}
+inline int mvdr_run_len(int n_rows, int n_frames, int most, int least) { return run_length(n_rows, n_frames, 1024, least, most); }
 
 // ---- the analysis: PCM -> X and the steering tables
 enum class MvdrAnalyseFamily { GEN, N1024, N512 };      // k_mvdr_analyse / _1024 / _512
@@ -43,8 +38,8 @@ inline MvdrAnalysePlan plan_mvdr_analyse(const MvdrShape &c, int n_streams, int 
     }
     // 1024-sample frames: wave-level FFT, one wave per channel, eight channels per pass; 512: two channels per wave pass (kernels_stream.hip)
     const int fpb = mvdr_run_len(n_streams, n_frames, 8, 1);
-    const size_t words = c.N == FFT_N ? 8 * 580 + TW_WORDS : 16 * 258 + 8 * FFT_SCRATCH + TW_WIN;
-    return {c.N == FFT_N ? MvdrAnalyseFamily::N1024 : MvdrAnalyseFamily::N512, fpb, {dim3((n_frames + fpb - 1) / fpb, n_streams), dim3(512), words * sizeof(float2)}};
+    const size_t lds = c.N == FFT_N ? (size_t)(8 * 580 + TW_WORDS) * sizeof(float2) : N512_LAYOUT_BYTES;
+    return {c.N == FFT_N ? MvdrAnalyseFamily::N1024 : MvdrAnalyseFamily::N512, fpb, {dim3((n_frames + fpb - 1) / fpb, n_streams), dim3(512), lds}};
 }
 
 // ---- the solve: which kernel, and how the launch is cut

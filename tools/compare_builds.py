@@ -16,7 +16,12 @@ OFF and candidate columns on, so the small batches run coarse + repair whatever 
   the host-pointer entry points: pageable, page-locked (the chunked path), 16-bit PCM, and under MCA_HIP_WS_MAX_MB = 1 (the sliced path);
   a graph: 4 launches, an eager call that grows the workspace, 2 more launches;
   the gated 2-microphone path with a tracker (the larger call takes no rows / argmaxes), its frame hook, setProbability;
-  the double frame API; the multiband, temporal-GCC, mask and bmask modules: stream calls of 6, 40 and 6 frames and their frame hooks.
+  the double frame API; the multiband, temporal-GCC, mask and bmask modules: stream calls of 6, 40 and 6 frames and their frame hooks;
+  every form of the modules' launch plans (csrc/module_plan.h), in host-pointer calls and in device-pointer calls of 6, 40 and 6 frames, the optional
+  outputs taken in one and left out in the other: mask at N = 1024 and 2048, NOISY (whose first call is one chunk) at 1024 and 256; bmask at frames of
+  1024, 2048 and 512 samples; multiband at N = 1024, 512 and 256; temporal GCC at 0.2 m and 48 kHz (above 64 KiB of LDS) and 16 kHz;
+  the 2-microphone host calls, plain and tracked, and the four modules' host calls with every optional output left out (through the C ABI where
+  the wrappers always take them): the _dev call behind them still gets a device buffer for some of them.
 
 Sequences on ONE context (ADAPTIVE unless said otherwise), every call's outputs and the final state blob in the digest: what one call
 decided or left behind must not reach the next call, whoever the caller is:
@@ -376,6 +381,137 @@ def child(out_path):
     parts += ana + [left, right, dec, m.frame_synthesis(left, channel=0), m.frame_synthesis(right, channel=1), blob(m)]
     m.close()
     res["bmask module and its frame hooks"] = frame.digest(*parts)
+
+    # every form of the modules' launch plans (csrc/module_plan.h), each in host-pointer calls and in device-pointer calls on a context of its own;
+    # the optional outputs are taken in one of the two and left out in the other
+    def cpu(ts):
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in ts if t is not None]
+
+    def z(shape, dtype=torch.float32):
+        return torch.zeros(shape, dtype=dtype, device=dev)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def masking(name, make, hop, seed):
+        x = noise((max(frames) + 1) * hop, seed)
+        for tag, host in (("host calls, decisions taken", True), ("device calls, no decisions", False)):
+            m, parts = make(), []
+            for F in frames:
+                if host:
+                    parts += list(m.process(x[:, :, :(F + 1) * hop]))
+                else:
+                    out = z((A, 2, F * hop))
+                    m.process_dev(up(x[:, :, :(F + 1) * hop]), F, out, None)
+                    parts += cpu([out])
+            parts.append(blob(m))
+            m.close()
+            res["%s, %s" % (name, tag)] = frame.digest(*parts)
+
+    for n_fft in (1024, 2048):
+        masking("mask module, N = %d" % n_fft, lambda: api.FastBinauralMasking(16000, 0.086, 100.0, 7000.0, fft_size=n_fft, max_streams=A_MAX), n_fft // 2, 640)
+    masking("mask module, NOISY and its first call, N = 1024", lambda: api.FastBinauralMasking(16000, 0.086, 100.0, 7000.0, method=api.NOISY, max_streams=A_MAX), 512, 641)
+    masking("mask module, NOISY and its first call, N = 256 (any length)",
+            lambda: api.FastBinauralMasking(16000, 0.086, 100.0, 7000.0, method=api.NOISY, fft_size=256, max_streams=A_MAX), 128, 642)
+    for fs_b, W in ((16000, 1024), (48000, 2048), (8000, 512)):
+        def make_bmask():
+            m = api.BinauralMaskingImpl(fs_b, 0.086, 100.0, 3500.0, max_streams=A_MAX)
+            if m.W != W:
+                sys.exit("bmask at %d Hz has frames of %d samples" % (fs_b, m.W))
+            return m
+        masking("bmask module, frames of %d samples" % W, make_bmask, W // 2, 650)
+
+    for n_fft, host_bands in ((1024, False), (512, False), (256, True)):
+        for host in (True, False):
+            m, parts = api.MultibandBinarualLocalisation(16000, synth.BINAURAL, nbins=5, use_power_floor=False, fft_size=n_fft, max_arrays=A_MAX), []
+            x = noise((max(frames) + 1) * m.hop, 660)
+            for F in frames:
+                if host:
+                    r = m.process(x[:, :, :(F + 1) * m.hop], want_bands=host_bands)
+                    parts += [r[k] for k in ("doa", "prob", "voiced", "power", "band_idx", "energy_in_doa", "band_corr") if r[k] is not None]
+                else:                                        # what the host calls of this size left out is taken, and the other way round
+                    o = [z((A, F)), z((A, F))] + ([None] * 5 if host_bands else
+                                                  [z((A, F), torch.uint8), z((A, F)), z((A, F, 5), torch.int32), z((A, F, m.D)), z((A, F, 5, m.D))])
+                    m.process_dev(up(x[:, :, :(F + 1) * m.hop]), F, *o)
+                    parts += cpu(o)
+            parts.append(blob(m))
+            m.close()
+            res["multiband module, N = %d, %s" % (n_fft, "host calls" if host else "device calls")] = frame.digest(*parts)
+
+    pair = [[-0.1, 0.0, 0.0], [0.1, 0.0, 0.0]]               # 0.2 m: 27 delay pairs at 48 kHz (72 304 bytes of LDS), 9 at 16 kHz (23 392)
+    for fs_t in (48000, 16000):
+        for host in (True, False):
+            m, parts = api.TemporalGCCBinauralLocalisation(fs_t, pair, use_power_floor=False, max_arrays=A_MAX), []
+            x = noise((max(frames) - 1) * m.hop + m.W, 670)
+            for F in frames:
+                cutx = x[:, :, :(F - 1) * m.hop + m.W]
+                r = m.process(cutx) if host else m.process_dev(up(cutx), want_index=True)
+                parts += [r[k] for k in ("doa", "prob", "voiced", "power", "delay_idx")] if host else cpu([r[k] for k in ("doa", "prob", "voiced", "power", "delay_idx", "index")])
+            parts.append(blob(m))
+            m.close()
+            res["temporal-GCC module, %d Hz, %s" % (fs_t, "host calls, no index" if host else "device calls, the index taken")] = frame.digest(*parts)
+
+    # the 2-microphone host calls with every optional output left out (the wrappers always take them: the C ABI directly)
+    import ctypes as C
+    for tracked in (False, True):
+        ctx = api.Context(fs, synth.BINAURAL, N, 3.0, 1, True, max_arrays=A_MAX)
+        if tracked:
+            ctx.gcc2_tracker_attach(seed=0x5EED0003)
+        parts, t0 = [], 0
+        for F in frames:
+            x = np.ascontiguousarray(pcm2[:, :, t0 * hop:(t0 + F + 1) * hop])
+            one = np.empty((A, F), dtype=np.float32 if tracked else np.int32)
+            xp, op = x.ctypes.data_as(C.POINTER(C.c_float)), one.ctypes.data_as(C.POINTER(C.c_float if tracked else C.c_int))
+            if tracked:
+                rc = ctx._lib.mca_hip_gcc2_tracked_frames_host(ctx.h, xp, A, F, None, op, None, None, None, None)
+            else:
+                rc = ctx._lib.mca_hip_gcc2_frames_host(ctx.h, xp, A, F, op, None, None, None)
+            if rc != 0:
+                sys.exit("the 2-microphone host call without optional outputs returned %d" % rc)
+            parts.append(one)
+            t0 += F
+        finish("2-microphone host calls, %s, optional outputs left out" % ("tracked" if tracked else "plain"), ctx, parts)
+
+    # the modules' host calls with every optional output left out: the _dev call behind them still gets a device buffer for some of them
+    # (StageBuf, STAGE_ALWAYS).  The multiband and temporal-GCC wrappers always take theirs: the C ABI directly
+    fpt = C.POINTER(C.c_float)
+    for name, m in (("mask", api.FastBinauralMasking(16000, 0.086, 100.0, 7000.0, fft_size=512, max_streams=A_MAX)),
+                    ("bmask", api.BinauralMaskingImpl(16000, 0.086, 100.0, 7000.0, max_streams=A_MAX))):
+        x, parts = noise((max(frames) + 1) * m.hop, 680), []
+        for F in frames:
+            out, dec = m.process(x[:, :, :(F + 1) * m.hop], want_decisions=False)
+            if dec is not None:
+                sys.exit("the %s wrapper took decisions" % name)
+            parts.append(out)
+        parts.append(blob(m))
+        m.close()
+        res["%s module, host calls without decisions" % name] = frame.digest(*parts)
+    m, parts = api.MultibandBinarualLocalisation(16000, synth.BINAURAL, nbins=5, use_power_floor=False, max_arrays=A_MAX), []
+    x = noise((max(frames) + 1) * m.hop, 681)
+    for F in frames:
+        xc = np.ascontiguousarray(x[:, :, :(F + 1) * m.hop])
+        doa, prob = np.empty((A, F), dtype=np.float32), np.empty((A, F), dtype=np.float32)
+        rc = m._lib.mca_hip_mb_frames_host(m.h, xc.ctypes.data_as(fpt), A, F, doa.ctypes.data_as(fpt), prob.ctypes.data_as(fpt), None, None, None, None, None)
+        if rc != 0:
+            sys.exit("the multiband host call without optional outputs returned %d" % rc)
+        parts += [doa, prob]
+    parts.append(blob(m))
+    m.close()
+    res["multiband module, host calls, optional outputs left out"] = frame.digest(*parts)
+    for fs_t in (48000, 16000):
+        m, parts = api.TemporalGCCBinauralLocalisation(fs_t, pair, use_power_floor=False, max_arrays=A_MAX), []
+        x = noise((max(frames) - 1) * m.hop + m.W, 682)
+        for F in frames:
+            xc = np.ascontiguousarray(x[:, :, :(F - 1) * m.hop + m.W])
+            doa = np.empty((A, F), dtype=np.float32)
+            rc = m._lib.mca_hip_tgcc_frames_host(m.h, xc.ctypes.data_as(fpt), A, F, doa.ctypes.data_as(fpt), None, None, None, None, None)
+            if rc != 0:
+                sys.exit("the temporal-GCC host call without optional outputs returned %d" % rc)
+            parts.append(doa)
+        parts.append(blob(m))
+        m.close()
+        res["temporal-GCC module, %d Hz, host calls, optional outputs left out" % fs_t] = frame.digest(*parts)
 
     with open(out_path, "w") as f:
         json.dump(res, f)
